@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- stabilised frames/s on synthetic NV12 clips (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k|1080p] [--mode auto|warp]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k|1080p] [--mode auto|warp] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input: --batch consecutive frames of
 this rank's clip (default 256 in pipeline mode: four passes over the 64-frame input ring), each emitted
@@ -26,7 +26,8 @@ Rank 0 prints ONE JSON line with the driver's contract plus
   "host":         what the rank costs the host: CPU seconds (user + system, all threads) per 1000 frames of the timed region, and
   "cpu_baseline_full_pipeline": the oracle's whole consume_frame / pull_frame loop (detector, LK, smoothing, warp), and
   "parity_check": one frame emitted after the timed region compared bit for bit with the oracle's warp of the same input
-                  frame under the rotation the pipeline reports for it (the run fails if they differ).
+                  frame under the rotation the pipeline reports for it (the run fails if they differ), and
+  "dump_outputs": with --dump-outputs DIR, the arrays written under DIR and their shapes.
 """
 import argparse
 import importlib
@@ -36,6 +37,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -94,7 +96,18 @@ def parse():
                     help="leave out the extra copy-ingest pass behind the timed region (used when the command runs under rocprofv3, so that the "
                          "kernel population of the trace is the timed pipeline's)")
     ap.add_argument("--traffic", default=None, help="measured HBM bytes per launch from PMC passes (profiles/)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned to its caller in the last step as DIR/<name>.npy (float32 pixels, "
+                         "float64 rotations; at most 64 MB in all: a fixed, seeded sample of each frame when the frames are larger), so that two builds "
+                         "can be compared output for output.  Implies --fixed-preroll: the same arguments then give the same inputs and frame schedule")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.rehearse_launcher:
+        ap.error("--dump-outputs: a launcher rehearsal computes nothing")
+    if args.dump_outputs:
+        args.fixed_preroll = True  # the adaptive pre-roll's length depends on the host's timing, and with it the frames the last step emits
+    return args
 
 
 def synth_ring(torch, dev, w, h, n, seed):
@@ -289,6 +302,39 @@ def side_pass(torch, pull, args, what):
     return {"value": round(args.steps * args.batch / el, 1), "unit": "frames/s", "steps": args.steps, "frames_per_step": args.batch,
             "step_ms": {"median": round(float(np.median(ms)), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)},
             "what": what + f"; {args.steps} steps of {args.batch} frames after a pre-roll of 1024 frames + {args.warmup} steps, behind the timed region"}
+
+
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: everything written together (the contract's ceiling is 64 MB)
+
+
+def dump_outputs(torch, out_dir, frames, rotations=None):
+    """--dump-outputs: the frames the timed path handed its caller in its last step, as out_dir/<name>.npy in float32, and the warp
+    rotation of each (float64, pipeline mode).  frames = {name: [one tensor per frame, in emission order]}.  When the frames do not
+    fit in DUMP_BYTES, every frame of a name is sampled at the same element positions, drawn with a seed fixed by the name and the
+    frame shape: the same arguments sample the same pixels.  Returns {name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    written, budget = {}, DUMP_BYTES - 4096 * (len(frames) + 1)  # (.npy headers)
+    if rotations is not None:
+        r = np.asarray(rotations, np.float64)
+        np.save(os.path.join(out_dir, "warp_rotation.npy"), r)
+        written["warp_rotation"] = list(r.shape)
+        budget -= r.nbytes
+    total = sum(len(ts) * ts[0].numel() for ts in frames.values())
+    for name, ts in frames.items():
+        n = ts[0].numel()
+        k = min(n, budget // 4 * n // total)  # elements per frame: every name gets the same fraction of its frames
+        if k < n:
+            seed = zlib.crc32(f"{name} {tuple(ts[0].shape)}".encode())
+            idx = torch.from_numpy(np.sort(np.random.default_rng(seed).choice(n, k, replace=False))).to(ts[0].device)
+            a = torch.stack([t.reshape(-1)[idx] for t in ts])
+        else:
+            a = torch.stack(ts)
+        if a.dtype == torch.int16:  # 16-bit pixels (P010 planes, BGR16) are unsigned
+            a = a.to(torch.int32) & 0xFFFF
+        a = a.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def launch_ranks(args):
@@ -645,6 +691,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
+    # --dump-outputs (outside the timed region, before anything else writes the output ring): the frames of the last timed step that
+    # the ring still holds -- the last min(batch, ring) -- and, in pipeline mode, the warp rotation the handle reports for each
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        held = range(n_warm + n_timed - min(args.batch, args.ring), n_warm + n_timed)
+        names = ("y", "uv") if nv12_out or p010_out else ("bgr16",) if p010 else ("bgr",)
+        frames = {nm: [outs[i % args.ring][j] if len(names) > 1 else outs[i % args.ring] for i in held] for j, nm in enumerate(names)}
+        rots = [stab.warp_rotation(preroll + i) for i in held] if mode == "pipeline" else None
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(torch, args.dump_outputs, frames, rots), "frames": len(held),
+                  "what": f"the last {len(held)} frames of the last timed step, pixel values as float32, one row per frame: whole frames when they "
+                          "fit in 64 MB, else the same seeded sample of element positions of every frame (shape: frames x sample)"}
+
     # correctness tie-in (outside the timed region): the next frame the pipeline emits, against the oracle's warp of the
     # same input frame under the rotation the pipeline reports for it (FrameSourceWarp.cpp:471-475); bit for bit
     parity, parity_against = None, None
@@ -847,6 +905,8 @@ def main():
                                                                    "achieved": round(base_bytes / alone_us / 1e3, 1),
                                                                    "frac": round(base_bytes / alone_us / 1e3 / HBM_PEAK_GBS, 4)}},
         }
+        if dumped:
+            line["dump_outputs"] = dumped
         if copy_ingest:
             line["copy_ingest"] = copy_ingest
         if ieee_map:

@@ -1360,3 +1360,37 @@ def test_bench_line_of_the_plane_wise_outputs():
         assert abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-3
         assert len(line["step_ms"]["all"]) == 3 and line["step_ms"]["min"] <= line["step_ms"]["median"] <= line["step_ms"]["max"]
         assert line["host"]["cpu_seconds_per_1000_frames"] > 0 and line["host"]["pinned_cpus"] >= 1
+
+
+def test_bench_dump_outputs_are_the_same_run_for_run(tmp_path):
+    """bench.py --dump-outputs DIR: what the timed path returned in its last step -- the frames the output ring still holds and their
+    warp rotations -- as float32 / float64 .npy files under 64 MB in all.  The same arguments give the same inputs and frame schedule
+    (the dump implies a fixed pre-roll), so two runs write the same arrays; --steps sets the number of timed steps.  The warp-only
+    mode dumps its NV12 planes."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+
+    def run(out, *extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "1080p", "--steps", "3", "--warmup", "1", "--batch", "24",
+                            "--ring", "16", "--no-cpu-baseline", "--skip-copy-pass", "--dump-outputs", str(out), *extra],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and len(line["step_ms"]["all"]) == 3 and line["ms_per_step"] > 0
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64 * 10 ** 6
+        return line, {f.stem: np.load(f) for f in out.iterdir()}
+    line, a = run(tmp_path / "a", "--preroll", "40")
+    assert line["preroll"] == 40 and line["parity_check"] == "ok"
+    assert sorted(a) == ["bgr", "warp_rotation"] and line["dump_outputs"]["arrays"]["bgr"][0] == 16
+    assert a["bgr"].dtype == np.float32 and a["warp_rotation"].dtype == np.float64 and a["warp_rotation"].shape == (16, 3, 3)
+    assert a["bgr"].max() <= 255 and len(np.unique(a["bgr"])) > 50   # real pixels, not an empty buffer
+    _, b = run(tmp_path / "b", "--preroll", "40")
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    line, w = run(tmp_path / "w", "--mode", "warp", "--out-format", "nv12-planar")
+    assert sorted(w) == ["uv", "y"] and w["y"].shape[0] == 16 and w["y"].dtype == np.float32

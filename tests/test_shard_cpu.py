@@ -146,3 +146,40 @@ def test_bench_cpu_baseline_legs_of_the_plane_wise_outputs():
         leg = bench.cpu_baseline_planar(frame, w, h, K, Ko, cw, ch, depth, blend=blend, budget_s=0.2, threads=1)
         assert leg["kind"] == "port" and leg["unit"] == "frames/s" and leg["cores"] == 1 and leg["value"] > 0
         assert "plane-wise" in leg["sample"] and ("NV12" if depth == 8 else "P010") in leg["sample"]
+
+
+def test_bench_dump_outputs_fits_and_samples_the_same_pixels(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 pixels (16-bit ones read unsigned) and float64 rotations, whole frames when they fit,
+    otherwise the same seeded element positions of every frame, and never more than 64 MB in all -- here 64 frames of the 4K BGR output."""
+    import sys
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    small = [torch.full((7, 5, 3), i, dtype=torch.uint8) for i in range(3)]
+    p010 = [torch.full((4, 6), -64, dtype=torch.int16)]
+    got = bench.dump_outputs(torch, str(tmp_path / "small"), {"bgr": small, "y": p010}, rotations=[np.eye(3)] * 3)
+    assert got == {"warp_rotation": [3, 3, 3], "bgr": [3, 7, 5, 3], "y": [1, 4, 6]}
+    a = np.load(tmp_path / "small" / "bgr.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, np.stack([t.numpy() for t in small]).astype(np.float32))
+    assert np.load(tmp_path / "small" / "y.npy").dtype == np.float32 and np.all(np.load(tmp_path / "small" / "y.npy") == 65472.0)
+    assert np.load(tmp_path / "small" / "warp_rotation.npy").dtype == np.float64
+    # 4K BGR output (3524 x 1999), 64 frames: 1.35 G elements -> sampled
+    big = torch.arange(1999 * 3524 * 3, dtype=torch.int32).reshape(1999, 3524, 3)
+    frames = [((big + i) % 251).to(torch.uint8) for i in range(64)]
+    for d in ("a", "b"):
+        got = bench.dump_outputs(torch, str(tmp_path / d), {"bgr": frames}, rotations=[np.eye(3)] * 64)
+        assert got["bgr"][0] == 64 and 0 < got["bgr"][1] < 1999 * 3524 * 3
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 64 * 10 ** 6
+    a, b = np.load(tmp_path / "a" / "bgr.npy"), np.load(tmp_path / "b" / "bgr.npy")
+    assert np.array_equal(a, b)
+    assert np.array_equal((a[1] - a[0]) % 251, np.ones(a.shape[1]))   # the same positions in every frame
+
+
+def test_bench_refuses_steps_below_one():
+    """--steps is the number of timed steps and ms_per_step divides by it: zero or negative steps, a negative warm-up, or a dump of a
+    launcher rehearsal (which computes nothing) are refused before anything runs."""
+    for argv in (("--steps", "0"), ("--steps", "-3"), ("--warmup", "-1"), ("--rehearse-launcher", "--dump-outputs", "x")):
+        r = _bench(*argv)
+        assert r.returncode == 2 and "n_gpus" not in r.stdout, (argv, r.stdout, r.stderr[-500:])
