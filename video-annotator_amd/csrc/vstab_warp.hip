@@ -534,6 +534,9 @@ static vstab_status warp_impl(const void *y, size_t pitch_y, const void *uv, siz
     a.p = to_params(params);
     const int vec_ok = aligned(dst, 4) && pitch_dst % 4 == 0 && (!nv12_out || (aligned(dst_uv, 4) && pitch_dst_uv % 4 == 0));
     const bool small_pitch = pitch_y < (1u << 24) && pitch_uv < (1u << 24) && (uint64_t)pitch_y * sh < (1ull << 32);
+    // the staged loads of the tiled kernels form chroma row offsets in 32 bits as well: a chroma plane of 4 GiB or more is sampled
+    // from global memory with 64-bit addresses instead (the direct kernel in plain mode, the gather path of the tiled kernels otherwise)
+    const bool stage32 = small_pitch && (uint64_t)pitch_uv * (sh / 2) < (1ull << 32);
     if (rot_bottom && map_mode != VSTAB_MAP_CREATEMAP_CL && map_mode != VSTAB_MAP_FISH_TO_RECT && map_mode != VSTAB_MAP_CREATEMAP_CL_OPENCL)
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_rs: the per-row warp exists for the fisheye -> pinhole modes (0, 1, 5) only");
     const bool plain = map_mode == VSTAB_MAP_CREATEMAP_CL && !nv12_out && !qmap && !rot_bottom;
@@ -541,20 +544,20 @@ static vstab_status warp_impl(const void *y, size_t pitch_y, const void *uv, siz
     if (planar) {  // the plane-wise warp: its own kernel (vstab_warp_planar.hip); the map is always evaluated
         if (qmap) return fail(VSTAB_ERR_UNSUPPORTED, "vstab_warp_nv12_mapped: the quantised map holds no chroma positions -- VSTAB_OUT_NV12_PLANAR goes through vstab_warp_nv12_ex");
         if (sw < 16 || sh < 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: the plane-wise warp needs a source of at least 16 x 2");
-        const bool src16 = aligned(y, 16) && aligned(uv, 16) && pitch_y % 16 == 0 && pitch_uv % 16 == 0;  // 16-byte staging loads
+        const bool src16 = stage32 && aligned(y, 16) && aligned(uv, 16) && pitch_y % 16 == 0 && pitch_uv % 16 == 0;  // 16-byte staging loads
         const bool dst16 = aligned(dst, 16) && aligned(dst_uv, 16) && pitch_dst % 16 == 0 && pitch_dst_uv % 16 == 0;
         return launch_warp_planar(a, params, map_mode, 8, 0, src16, dst16, rot_bottom, static_cast<hipStream_t>(stream));
     }
-    bool direct = !small_pitch;
+    bool direct = !small_pitch || (plain && !stage32);
 #ifdef VSTAB_DEV
     static const int variant = getenv("VSTAB_WARP_VARIANT") ? atoi(getenv("VSTAB_WARP_VARIANT")) : 2;
     direct = direct || (plain && variant == 1);
 #endif
-    if (direct) {  // frames of 4 GiB and more: the direct-gather kernel with 64-bit addressing
+    if (direct) {  // planes of 4 GiB and more: the direct-gather kernel with 64-bit addressing
         dim3 grid(div_up(dw, WARP_TILE_W), div_up(dh, WARP_TILE_H));
         hipLaunchKernelGGL(k_warp_nv12_bgr, grid, dim3(16, 16), 0, static_cast<hipStream_t>(stream), a, vec_ok);
     } else {
-        const bool src_vec_ok = aligned(y, 8) && aligned(uv, 8) && pitch_y % 8 == 0 && pitch_uv % 8 == 0;  // 8-byte staging loads
+        const bool src_vec_ok = stage32 && aligned(y, 8) && aligned(uv, 8) && pitch_y % 8 == 0 && pitch_uv % 8 == 0;  // 8-byte staging loads
         return launch_warp_fused(a, params, map_mode, nv12_out, src_vec_ok, vec_ok, qmap, qpitch, rot_bottom, static_cast<hipStream_t>(stream));
     }
     VSTAB_HIP_TRY(hipGetLastError());

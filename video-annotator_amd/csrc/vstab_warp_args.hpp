@@ -72,9 +72,9 @@ __device__ __forceinline__ uint32_t load_u32_bytes(const uint8_t *p, int valid) 
 vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int map_mode, bool nv12_out, bool src_vec_ok, bool dst_vec_ok,
                                const void *qmap, int qpitch, const float *rot_bottom, hipStream_t st);
 // the 10-bit pixel path on the LDS-tiled kernel: a.y / a.uv = P010 planes (16-byte aligned, pitches multiples of 16), a.dst = 16-bit
-// BGR with a.pitch_dst bytes per row; map modes 0 / 1 only
-vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int map_mode, int blend, const float *rot_bottom, bool p010_out, bool dst_vec_ok,
-                                 hipStream_t st);
+// BGR with a.pitch_dst bytes per row; map modes 0 / 1 only.  src_vec_ok false: nothing is staged, every pixel is sampled from global memory
+vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int map_mode, int blend, const float *rot_bottom, bool p010_out, bool src_vec_ok,
+                                 bool dst_vec_ok, hipStream_t st);
 
 // the plane-wise warp (vstab_warp_planar.hip): a.dst / a.dst_uv = the output planes; depth 8 (NV12 bytes) or 10 (P010 words)
 vstab_status launch_warp_planar(const WarpArgs &a, const float params[17], int map_mode, int depth, int blend, bool src_vec_ok, bool dst_vec_ok,

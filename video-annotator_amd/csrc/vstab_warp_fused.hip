@@ -109,7 +109,9 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
         int sy_ = (int)(256.0f * rn), sx_ = 256 - sy_ * ux_n;  // uniform: divmod(256, ux_n)
         if (sx_ < 0) sx_ += ux_n, sy_--;
         if (sx_ >= ux_n) sx_ -= ux_n, sy_++;
-        const uint32_t pitch_y = (uint32_t)a.pitch_y, pitch_uv = (uint32_t)a.pitch_uv;  // < 2^24, frame < 4 GiB (host check)
+        // < 2^24, pitch_y * sh and pitch_uv * sh / 2 < 2^32: src_vec_ok is only set under those host checks (warp_impl in vstab_warp.hip,
+        // vstab_warp_p010 / _planes), so the 32-bit row offsets below cannot wrap
+        const uint32_t pitch_y = (uint32_t)a.pitch_y, pitch_uv = (uint32_t)a.pitch_uv;
         // no per-lane branch around any load, so that all of them are in flight under the map phase; a trip that no
         // thread of the workgroup needs (most boxes have fewer than 256 blocks) is skipped by a scalar branch: its
         // ~30 vector instructions of index arithmetic per thread were 4 % of the kernel each (35.4 -> 34.2 us alone at 4K)
@@ -505,12 +507,12 @@ extern "C" __attribute__((visibility("default"))) void vstab_dev_set_timing(void
 
 // The 10-bit pixel path on the same kernel (DEPTH 10): fisheye -> pinhole maps (modes 0 / 1 / 5, optionally a rotation per
 // output row), both blends; called by vstab_warp_p010 when the planes allow 16-byte staging loads.
-vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int map_mode, int blend, const float *rot_bottom, bool p010_out, bool dst_vec_ok,
-                                 hipStream_t st) {
+vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int map_mode, int blend, const float *rot_bottom, bool p010_out, bool src_vec_ok,
+                                 bool dst_vec_ok, hipStream_t st) {
     FusedArgs ta;
     ta.w = a;
     ta.p32 = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
-    ta.src_vec_ok = 1, ta.dst_vec_ok = dst_vec_ok;
+    ta.src_vec_ok = src_vec_ok, ta.dst_vec_ok = dst_vec_ok;
     ta.qmap = nullptr, ta.qpitch = 0;
     for (int k = 0; k < 9; k++) ta.rs_d[k] = rot_bottom ? rot_bottom[k] - params[8 + k] : 0.0f;
     ta.rs_den = (float)(a.dh > 1 ? a.dh - 1 : 1);

@@ -162,6 +162,8 @@ extern "C" vstab_status vstab_warp_p010_planes(const void *y, size_t pitch_y, co
                           pitch_uv >= (size_t)sw * 2 && pitch_y < (1u << 24) && pitch_uv < (1u << 24) && (uint64_t)pitch_y * sh < (1ull << 32) &&
                           (uint64_t)pitch_dst_y * dh < (1ull << 32);
     if (!tiled_ok) return fail(VSTAB_ERR_UNSUPPORTED, "vstab_warp_p010_planes: needs 16-byte aligned source planes and a fisheye -> pinhole map");
+    // the staged loads form chroma row offsets in 32 bits: a chroma plane of 4 GiB or more is sampled from global memory (64-bit addresses)
+    const bool stage32 = (uint64_t)pitch_uv * (sh / 2) < (1ull << 32);
     WarpArgs wa;
     wa.y = static_cast<const uint8_t *>(y), wa.uv = static_cast<const uint8_t *>(uv), wa.dst = static_cast<uint8_t *>(dst_y), wa.dst_uv = static_cast<uint8_t *>(dst_uv);
     wa.pitch_y = pitch_y, wa.pitch_uv = pitch_uv, wa.pitch_dst = pitch_dst_y, wa.pitch_dst_uv = pitch_dst_uv;
@@ -169,7 +171,7 @@ extern "C" vstab_status vstab_warp_p010_planes(const void *y, size_t pitch_y, co
     wa.p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7],
             {params[8], params[9], params[10], params[11], params[12], params[13], params[14], params[15], params[16]}};
     const bool vec = reinterpret_cast<uintptr_t>(dst_y) % 8 == 0 && reinterpret_cast<uintptr_t>(dst_uv) % 8 == 0 && pitch_dst_y % 8 == 0 && pitch_dst_uv % 8 == 0;
-    return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, true, vec, static_cast<hipStream_t>(stream));
+    return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, true, stage32, vec, static_cast<hipStream_t>(stream));
 }
 
 // The plane-wise 10-bit warp (vstab_warp_planar.hip, DEPTH 10): P010 planes in and out, no colour conversion at all.
@@ -197,7 +199,9 @@ extern "C" vstab_status vstab_warp_p010_planar(const void *y, size_t pitch_y, co
     wa.sw = sw, wa.sh = sh, wa.dw = dw, wa.dh = dh;
     wa.p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7],
             {params[8], params[9], params[10], params[11], params[12], params[13], params[14], params[15], params[16]}};
-    const bool src16 = reinterpret_cast<uintptr_t>(y) % 16 == 0 && reinterpret_cast<uintptr_t>(uv) % 16 == 0 && pitch_y % 16 == 0 && pitch_uv % 16 == 0;
+    // 16-byte staging loads; their chroma row offsets are 32-bit: a chroma plane of 4 GiB or more is sampled from global memory instead
+    const bool src16 = reinterpret_cast<uintptr_t>(y) % 16 == 0 && reinterpret_cast<uintptr_t>(uv) % 16 == 0 && pitch_y % 16 == 0 && pitch_uv % 16 == 0 &&
+                       (uint64_t)pitch_uv * (sh / 2) < (1ull << 32);
     const bool dst16 = reinterpret_cast<uintptr_t>(dst_y) % 16 == 0 && reinterpret_cast<uintptr_t>(dst_uv) % 16 == 0 && pitch_dst_y % 16 == 0 && pitch_dst_uv % 16 == 0;
     return launch_warp_planar(wa, params, map_mode, 10, blend, src16, dst16, rot_bottom, static_cast<hipStream_t>(stream));
 }
@@ -230,7 +234,8 @@ extern "C" vstab_status vstab_warp_p010(const void *y, size_t pitch_y, const voi
     const bool tiled_ok = (map_mode == VSTAB_MAP_CREATEMAP_CL || map_mode == VSTAB_MAP_FISH_TO_RECT || map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL) && sw >= 8 &&
                           reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
                           reinterpret_cast<uintptr_t>(uv) % 16 == 0 && pitch_y % 16 == 0 && pitch_uv % 16 == 0 && pitch_y < (1u << 24) &&
-                          pitch_uv < (1u << 24) && (uint64_t)pitch_y * sh < (1ull << 32);
+                          pitch_uv < (1u << 24) && (uint64_t)pitch_y * sh < (1ull << 32) &&
+                          (uint64_t)pitch_uv * (sh / 2) < (1ull << 32);  // (the staged loads form chroma row offsets in 32 bits)
     static const bool force_direct = getenv("VSTAB_P010_DIRECT") != nullptr;  // development: the direct-gather kernel for every call
     if (tiled_ok && !force_direct) {
         WarpArgs wa;
@@ -239,7 +244,7 @@ extern "C" vstab_status vstab_warp_p010(const void *y, size_t pitch_y, const voi
         wa.sw = sw, wa.sh = sh, wa.dw = dw, wa.dh = dh;
         wa.p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7],
                 {params[8], params[9], params[10], params[11], params[12], params[13], params[14], params[15], params[16]}};
-        return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, false, true, static_cast<hipStream_t>(stream));
+        return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, false, true, true, static_cast<hipStream_t>(stream));
     }
     P010Args a;
     a.y = static_cast<const uint8_t *>(y), a.uv = static_cast<const uint8_t *>(uv), a.dst = static_cast<uint16_t *>(dst);

@@ -179,7 +179,7 @@ __device__ __forceinline__ bool warp_tile_planar(const FusedArgs &ta, uint32_t *
     // row after row.  The lane's part of the source offset is computed ONCE per tile; an instruction adds a scalar row offset.  The four
     // waves take the row groups of the luma box, then of the chroma box, in turn.  Chunks outside the source (tiles at the frame's edge)
     // are not fetched but written as limited-range black. --------------------------------------------------------------------------------
-    const int ux_n = wb / BW;
+    const int ux_n = wb / BW;  // <= 64 whenever use_lds: probe_tile's `fits` keeps a box row within one instruction's 64 lanes (rpi >= 1)
     {
         if (use_lds) {
             const float rn = __builtin_amdgcn_rcpf((float)ux_n);
@@ -192,7 +192,9 @@ __device__ __forceinline__ bool warp_tile_planar(const FusedArgs &ta, uint32_t *
             const int colp = bx0 + BW * col;  // first source sample of the lane's chunk within a row (a chroma row: the same bytes per luma column)
             const int sw_al = a.sw & ~(BW - 1);
             const bool col_ok = (uint32_t)colp < (uint32_t)sw_al;
-            const uint32_t pitch_y = (uint32_t)a.pitch_y, pitch_uv = (uint32_t)a.pitch_uv;  // < 2^24, frame < 4 GiB (host check)
+            // < 2^24, pitch_y * sh and pitch_uv * sh / 2 < 2^32: src_vec_ok is only set under those host checks (warp_impl in vstab_warp.hip,
+            // vstab_warp_p010_planar), so the 32-bit row offsets below cannot wrap
+            const uint32_t pitch_y = (uint32_t)a.pitch_y, pitch_uv = (uint32_t)a.pitch_uv;
             const uint32_t lane_y = (uint32_t)r0 * pitch_y + (uint32_t)(colp * BPS), lane_c = (uint32_t)r0 * pitch_uv + (uint32_t)(colp * BPS);
             const int hc = hb >> 1;
             const int nl = (hb + rpi - 1) / rpi, nc = (hc + rpi - 1) / rpi;

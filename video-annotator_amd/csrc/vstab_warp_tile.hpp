@@ -171,7 +171,10 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
 #ifdef VSTAB_DEV
     const bool fits = (wb + ta.lds_pad) * hb <= ta.lds_capacity_px && (wb >> 3) * (hb >> 1) <= STAGE_MAX * 256;  // experiment: padded LDS rows
 #else
-    const bool fits = wb * hb <= ta.lds_capacity_px && (wb / BLOCK_W) * (hb >> 1) <= STAGE_MAX * 256;
+    // PLANAR: one LDS-DMA wave instruction stages floor(64 / (wb / BLOCK_W)) whole box rows (vstab_warp_planar.hip), so a box row
+    // must not have more than 64 chunks -- a wider box (anamorphic output cameras, tiles wholly above or below the source) is split,
+    // and then sampled from global memory
+    const bool fits = wb * hb <= ta.lds_capacity_px && (wb / BLOCK_W) * (hb >> 1) <= STAGE_MAX * 256 && (!PLANAR || wb / BLOCK_W <= 64);
 #endif
     if (lane == 0) {
         *reinterpret_cast<uint4 *>(hdr) = make_uint4((uint32_t)bx0, (uint32_t)by0, (uint32_t)wb, (uint32_t)hb);
