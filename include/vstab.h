@@ -61,10 +61,11 @@ VSTAB_API int vstab_struct_size(int which);
  * initialised with vstab_config_default() and then modified, never zero-filled or assembled by hand.  vstab_frame is always
  * allocated and zeroed by the library before a source callback fills it in.  Version 4: abi_version, vstab_frame.dmabuf_modifier;
  * map_precision defaults to VSTAB_MAP_PRECISION_OPENCL.  Version 5: vstab_config.read_ahead, two more counters in vstab_profile.
+ * Version 6: vstab_config.resample.
  * The value is "VSB" + the version in the low byte: no field an older layout had at this offset (a preset 0..5) can hold it, so a
  * struct filled in against an older header is refused whatever its contents -- and with it every later call that would write a
  * larger vstab_profile into that caller's smaller one, since no handle is ever created for it. */
-#define VSTAB_ABI_VERSION 0x56534205
+#define VSTAB_ABI_VERSION 0x56534206
 VSTAB_API int vstab_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -241,6 +242,34 @@ VSTAB_API vstab_status vstab_warp_p010_planes(const void *y, size_t pitch_y, con
  * NV12 output (cvtColor's BT.601 constants) at 10 bits, offsets 64 / 512; defined in the oracle (vo_cvt_bgr10_p010).  Pitches in bytes. */
 VSTAB_API vstab_status vstab_cvt_bgr16_p010(const void *src_bgr16, size_t pitch_src, int width, int height, void *dst_y, size_t pitch_y,
                                             void *dst_uv, size_t pitch_uv, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Bicubic resampling: cv::remap's INTER_CUBIC, which FrameSourceWarp.hpp:90 admits and FrameSourceWarp.cpp:311 hands to cv::remap.
+ * OpenCV 4.5's CPU path for 8-bit data, restated (tests/cubic_def.py holds it in numpy, tests/golden/cubic_kat.npz pins it):
+ *   quantisation  as INTER_LINEAR: sx = cvRound(32 * mapx) (half to even; NaN / out of int range -> INT_MIN), X = saturate_cast<short>(sx >> 5),
+ *                 fx = sx & 31; the same for y;
+ *   footprint     rows Y - 1 .. Y + 2, columns X - 1 .. X + 2;
+ *   weights       entry fy * 32 + fx of OpenCV's fixed-point table (initInterTab2D(INTER_CUBIC)): interpolateCubic (A = -0.75) in fp32,
+ *                 w[k1][k2] = saturate_cast<short>(cvRound(c_fy[k1] * c_fx[k2] * 32768.f)), then the correction that makes the 16 weights
+ *                 sum to 32768 (vstab_cubic_weights returns the table);
+ *   blend         per channel sat_u8((sum_k w_k * (tap_k inside ? S_k : border) + (1 << 14)) >> 15) -- cubic overshoots, so it saturates.
+ * ------------------------------------------------------------------------------------------ */
+/* The weight table: 1024 entries (index fy * 32 + fx) of 16 int16 weights, w[k1 * 4 + k2] for tap (X - 1 + k2, Y - 1 + k1).  Host memory. */
+VSTAB_API vstab_status vstab_cubic_weights(int16_t out[16384]);
+/* cv::remap(INTER_CUBIC, BORDER_CONSTANT) of an 8-bit source of `channels` (1, 2 or 3) interleaved channels with float map planes (pitches in
+ * bytes; map planes 4-byte aligned).  border[0 .. channels - 1] in [0, 255]: the value of every tap outside the source; a footprint wholly
+ * outside gives the border value. */
+VSTAB_API vstab_status vstab_remap_cubic(const void *src, size_t pitch_src, int src_width, int src_height, int channels, const void *map_x,
+                                         size_t pitch_x, const void *map_y, size_t pitch_y, const int border[3], void *dst, size_t pitch_dst,
+                                         int dst_width, int dst_height, void *stream);
+/* vstab_warp_nv12_ex with INTER_CUBIC in place of INTER_LINEAR, map modes 0 .. 5 (the map of each mode bit for bit).  out_format:
+ *   VSTAB_OUT_BGR8         cvtColor(NV12 -> BGR) of the frame, then the cubic remap with border 0;
+ *   VSTAB_OUT_NV12_PLANAR  the plane-wise definition above (vstab_out_format) with the cubic remap: luma with the map, border 16; the
+ *                          interleaved chroma plane with map(2 cx, 2 cy) * 0.5f, border (128, 128).  dst_uv as for vstab_warp_nv12_ex.
+ * VSTAB_OUT_NV12 (through BGR) and any other value are refused with VSTAB_ERR_INVALID.  Source even-sized, chroma plane 2-byte aligned. */
+VSTAB_API vstab_status vstab_warp_nv12_cubic(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                             const float params[17], int map_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv,
+                                             size_t pitch_dst_uv, int dst_width, int dst_height, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Tracking front-end (device images in; small point lists on the host, as in the reference where
@@ -495,8 +524,15 @@ typedef struct vstab_config {
                             output bytes per frame away from the reference's GPU result).  Every path of the
                             handle honours it: cached map (tracking off), read-out rotations, INTER_NEAREST, pixel_depth 10.
                             lens_mode 1 ignores it (those maps are this library's own definitions, IEEE throughout). */
+    int resample;        /* VSTAB_RESAMPLE_DEFAULT (0): `interpolation` decides, as before.  VSTAB_RESAMPLE_CUBIC (2 = cv::INTER_CUBIC): every
+                            8-bit BGR and plane-wise NV12 pull warps with vstab_warp_nv12_cubic (both lens modes, both map precisions, tracking
+                            on or off); rotations, frame log and look-ahead are those of the default.  Needs interpolation = 1 and 8-bit
+                            pixels (vstab_create refuses it with INTER_NEAREST or pixel_depth 10).  At pull time the NV12-through-BGR
+                            pull is refused before any frame is taken (the frame can still be pulled in a served format); a frame
+                            that carries a readout_rotation is refused and consumed, as with INTER_NEAREST.  (A separate field: `interpolation` keeps refusing 2.) */
 } vstab_config;
 enum { VSTAB_MAP_PRECISION_IEEE = 0, VSTAB_MAP_PRECISION_OPENCL = 1 };
+enum { VSTAB_RESAMPLE_DEFAULT = 0, VSTAB_RESAMPLE_CUBIC = 2 };
 
 typedef struct vstab_handle vstab_handle;
 
@@ -583,7 +619,7 @@ typedef struct vstab_profile {
     long epochs_in_turn; /* planned key frames whose detection and tracker launches ran on the second of the handle's two epoch streams, beside
                             the epoch still being tracked on the first (frames up to 1920 x 1200 with a caller on the default stream; 0 otherwise) */
 } vstab_profile;
-/* Loads the library's five GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
+/* Loads the library's six GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
  * milliseconds in the middle of the first frames -- and on ROCm 7.2 such a late load can FAULT ("write access to a read-only page") when the
  * process has unloaded another module before it (hipModuleUnload; an OpenCL program released by a filter next door): the new code object may
  * be placed where the old one was still mapped read-only.  vstab_create calls this itself; a host that uses the stateless operators
