@@ -92,8 +92,11 @@ class Plane:
         self.ptr = self.buf.data_ptr() + GUARD_ROWS * self.pitch
 
     def host(self, dtype=np.uint8, shape=None):
-        """-> the plane's bytes as `dtype` (shape (rows, rb / itemsize) or `shape`), after checking every canary byte."""
-        a = self.buf.cpu().numpy().reshape(self.rows + 2 * GUARD_ROWS, self.pitch)
+        """-> the plane's bytes as `dtype` (shape (rows, rb / itemsize) or `shape`), after checking every canary byte (of a pitch wider
+        than the row plus 64 bytes -- a plane past 4 GiB --, the first 64 canary bytes right of each row)."""
+        import torch
+        cols = min(self.pitch, _al(self.rb, 16) + 64)
+        a = torch.as_strided(self.buf, (self.rows + 2 * GUARD_ROWS, cols), (self.pitch, 1)).cpu().numpy()
         g = GUARD_ROWS
         bad = int((a[:g] != CANARY).sum() + (a[g + self.rows:] != CANARY).sum() + (a[g:g + self.rows, self.rb:] != CANARY).sum())
         assert bad == 0, f"{bad} bytes written outside the plane"
@@ -149,6 +152,21 @@ def warp_nv12_mapped(vs, s, qmap, dw, dh, out_format, cuda):
         return o.host(shape=(dh, dw, 3))
     oy, ou = out_nv12(dw, dh, cuda)
     _call(vs, "vstab_warp_nv12_mapped", s.y, s.pitch_y, s.uv, s.pitch_uv, s.w, s.h, qmap.data_ptr(), int(out_format), oy.ptr, oy.pitch, ou.ptr,
+          ou.pitch, dw, dh, vs._stream())
+    return oy.host(), ou.host()
+
+
+def warp_nv12_cubic(vs, s, params, dw, dh, mode, out_format, cuda, out=None):
+    """vstab_warp_nv12_cubic -> BGR (dh, dw, 3), or (y, uv) plane-wise NV12.  out: the output Plane (BGR) or (luma, chroma) Planes,
+    for callers that place the output themselves; default canaried planes of the natural size."""
+    p, pp = _f(params)
+    if out_format == vs.OUT_BGR8:
+        o = out or Plane(dh, 3 * dw, cuda)
+        _call(vs, "vstab_warp_nv12_cubic", s.y, s.pitch_y, s.uv, s.pitch_uv, s.w, s.h, pp, int(mode), int(out_format), o.ptr, o.pitch, None, 0,
+              dw, dh, vs._stream())
+        return o.host(shape=(dh, dw, 3))
+    oy, ou = out or out_nv12(dw, dh, cuda)
+    _call(vs, "vstab_warp_nv12_cubic", s.y, s.pitch_y, s.uv, s.pitch_uv, s.w, s.h, pp, int(mode), int(out_format), oy.ptr, oy.pitch, ou.ptr,
           ou.pitch, dw, dh, vs._stream())
     return oy.host(), ou.host()
 

@@ -196,7 +196,9 @@ def test_warp_cubic_unaligned_and_pitched_planes(vs, cuda):
 
 
 def test_warp_cubic_extreme_box_shapes(vs, cuda):
-    """Wide flat and tall narrow source boxes (anisotropic cameras): over the LDS budget, sampled from global memory."""
+    """Wide flat and tall narrow source boxes (anisotropic cameras).  The BGR tiles of the 2048 x 32 and 4096 x 64 sets are over the
+    LDS budget and sampled from global memory; every luma and chroma tile, and every tile of the 64 x 1024 set, is staged
+    (tests/test_cubic_tiles_cpu.py counts them; test_cubic_paths_gpu.py has the sets that gather luma and chroma)."""
     for sw, sh, dw, dh, sx, sy in [(2048, 32, 128, 64, 15.0, 0.25), (64, 1024, 128, 64, 0.125, 15.0), (4096, 64, 200, 70, 15.5, 0.3)]:
         f = synth.nv12(61, sw, sh)
         Ki = np.array([[100.0 * sx, 0, sw / 2], [0, 100.0 * sy, sh / 2], [0, 0, 1]])
