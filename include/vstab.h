@@ -272,6 +272,31 @@ VSTAB_API vstab_status vstab_warp_nv12_cubic(const void *y, size_t pitch_y, cons
                                              size_t pitch_dst_uv, int dst_width, int dst_height, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Lanczos resampling: cv::remap's INTER_LANCZOS4 (4), the fourth mode FrameSourceWarp.hpp:90 can hand to cv::remap.  OpenCV 4.5's CPU
+ * path for 8-bit data, restated (tests/lanczos4_def.py holds it in numpy, tests/golden/lanczos4_kat.npz pins it):
+ *   quantisation  as INTER_LINEAR and INTER_CUBIC (above);
+ *   footprint     rows Y - 3 .. Y + 4, columns X - 3 .. X + 4;
+ *   1-D rows      interpolateLanczos4(x), x = k / 32: s0 = sin(y0), c0 = cos(y0) of y0 = -(x + 3) * pi / 4 in double; coefficient i =
+ *                 (float)((cs[i][0] * s0 + cs[i][1] * c0) / (y * y)), y = -(x + 3 - i) * pi / 4; summed in fp32 in order i = 0..7, each
+ *                 multiplied by 1.f / sum in fp32; x = 0 gives [0, 0, 0, 1, 0, 0, 0, 0];
+ *   weights       entry fy * 32 + fx of OpenCV's fixed-point table (initInterTab2D(INTER_LANCZOS4)): w[k1][k2] =
+ *                 saturate_cast<short>(cvRound(c_fy[k1] * c_fx[k2] * 32768.f)), the product in fp32, then the correction that makes the
+ *                 64 weights sum to 32768, searched in k1, k2 in {4, 5} (vstab_lanczos4_weights returns the table).  Entry 0 is not the
+ *                 identity: 32767 at tap (3, 3) and 1 at tap (4, 4);
+ *   blend         per channel sat_u8((sum_k w_k * (tap_k inside ? S_k : border) + (1 << 14)) >> 15).
+ * ------------------------------------------------------------------------------------------ */
+/* The weight table: 1024 entries (index fy * 32 + fx) of 64 int16 weights, w[k1 * 8 + k2] for tap (X - 3 + k2, Y - 3 + k1).  Host memory. */
+VSTAB_API vstab_status vstab_lanczos4_weights(int16_t out[65536]);
+/* vstab_remap_cubic with INTER_LANCZOS4: the same arguments and the same checks. */
+VSTAB_API vstab_status vstab_remap_lanczos4(const void *src, size_t pitch_src, int src_width, int src_height, int channels, const void *map_x,
+                                            size_t pitch_x, const void *map_y, size_t pitch_y, const int border[3], void *dst, size_t pitch_dst,
+                                            int dst_width, int dst_height, void *stream);
+/* vstab_warp_nv12_cubic with INTER_LANCZOS4: the same arguments, output formats (VSTAB_OUT_BGR8, VSTAB_OUT_NV12_PLANAR) and checks. */
+VSTAB_API vstab_status vstab_warp_nv12_lanczos4(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                                const float params[17], int map_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv,
+                                                size_t pitch_dst_uv, int dst_width, int dst_height, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tracking front-end (device images in; small point lists on the host, as in the reference where
  * goodFeaturesToTrack / calcOpticalFlowPyrLK return std::vector<Point2f>).  These calls
  * synchronise `stream` before returning because their outputs live in host memory.
@@ -529,10 +554,11 @@ typedef struct vstab_config {
                             on or off); rotations, frame log and look-ahead are those of the default.  Needs interpolation = 1 and 8-bit
                             pixels (vstab_create refuses it with INTER_NEAREST or pixel_depth 10).  At pull time the NV12-through-BGR
                             pull is refused before any frame is taken (the frame can still be pulled in a served format); a frame
-                            that carries a readout_rotation is refused and consumed, as with INTER_NEAREST.  (A separate field: `interpolation` keeps refusing 2.) */
+                            that carries a readout_rotation is refused and consumed, as with INTER_NEAREST.  (A separate field: `interpolation` keeps refusing 2.)
+                            VSTAB_RESAMPLE_LANCZOS4 (4 = cv::INTER_LANCZOS4): the same, with vstab_warp_nv12_lanczos4 (`interpolation` refuses 4). */
 } vstab_config;
 enum { VSTAB_MAP_PRECISION_IEEE = 0, VSTAB_MAP_PRECISION_OPENCL = 1 };
-enum { VSTAB_RESAMPLE_DEFAULT = 0, VSTAB_RESAMPLE_CUBIC = 2 };
+enum { VSTAB_RESAMPLE_DEFAULT = 0, VSTAB_RESAMPLE_CUBIC = 2, VSTAB_RESAMPLE_LANCZOS4 = 4 };
 
 typedef struct vstab_handle vstab_handle;
 
@@ -619,7 +645,7 @@ typedef struct vstab_profile {
     long epochs_in_turn; /* planned key frames whose detection and tracker launches ran on the second of the handle's two epoch streams, beside
                             the epoch still being tracked on the first (frames up to 1920 x 1200 with a caller on the default stream; 0 otherwise) */
 } vstab_profile;
-/* Loads the library's six GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
+/* Loads the library's seven GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
  * milliseconds in the middle of the first frames -- and on ROCm 7.2 such a late load can FAULT ("write access to a read-only page") when the
  * process has unloaded another module before it (hipModuleUnload; an OpenCL program released by a filter next door): the new code object may
  * be placed where the old one was still mapped read-only.  vstab_create calls this itself; a host that uses the stateless operators

@@ -80,6 +80,7 @@ class FrameSourceWarp : public FrameSource {
         cfg.preset = input_camera, cfg.scale = scale, cfg.crop_borders = crop_borders, cfg.zoom = zoom;
         cfg.smooth_radius = smooth_radius, cfg.interpolation = interpolation, cfg.stream = hip_stream;
         if (interpolation == 2) cfg.interpolation = 1, cfg.resample = VSTAB_RESAMPLE_CUBIC;  // cv::INTER_CUBIC: vstab_config.resample
+        if (interpolation == 4) cfg.interpolation = 1, cfg.resample = VSTAB_RESAMPLE_LANCZOS4;  // cv::INTER_LANCZOS4: likewise
         init(cfg);
     }
     // Motion from an external sensor instead of optical flow -- the gyro path the reference stubs (gpmf.cpp:5-11,

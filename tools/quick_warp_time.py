@@ -1,6 +1,7 @@
 """Quick timing of the fused warp kernel (development helper).
 env: QW, QH source size; QMODE 0..4 (map mode; 0 = createMap.cl preset cameras); QFMT 0 BGR / 1 NV12 / 2 plane-wise NV12;
-QCUBIC=1 the INTER_CUBIC warp (vstab_warp_nv12_cubic; QFMT 0 or 2) in place of the bilinear one."""
+QCUBIC=1 the INTER_CUBIC warp (vstab_warp_nv12_cubic; QFMT 0 or 2) in place of the bilinear one; QLANCZOS=1 the INTER_LANCZOS4 warp
+(vstab_warp_nv12_lanczos4; QFMT 0 or 2)."""
 import importlib, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,6 +35,8 @@ if os.environ.get("QRS"):   # a rotation per output row (rolling shutter): the l
     run = lambda i: vs.warp_nv12_rs(frames[i % nf], p, rb, cw, ch, mode, fmt, out=outs[i % nf])
 elif os.environ.get("QCUBIC") == "1":
     run = lambda i: vs.warp_nv12_cubic(frames[i % nf], p, cw, ch, mode, fmt, out=outs[i % nf])
+elif os.environ.get("QLANCZOS") == "1":
+    run = lambda i: vs.warp_nv12_lanczos4(frames[i % nf], p, cw, ch, mode, fmt, out=outs[i % nf])
 else:
     run = lambda i: vs.warp_nv12(frames[i % nf], p, cw, ch, mode, fmt, out=outs[i % nf])
 for i in range(nf): run(i)
@@ -58,4 +61,5 @@ else:
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / n
 b = w * h * 1.5 + out_bytes
-print(f"{'cubic ' if os.environ.get('QCUBIC') == '1' else ''}warp {w}x{h} -> {cw}x{ch} mode {mode} fmt {fmt}: {ms*1000:.1f} us/frame  {b/ms/1e6:.1f} GB/s  ({b/ms/1e6/8000*100:.1f}% of 8 TB/s)")
+kind = "cubic " if os.environ.get("QCUBIC") == "1" else "lanczos4 " if os.environ.get("QLANCZOS") == "1" else ""
+print(f"{kind}warp {w}x{h} -> {cw}x{ch} mode {mode} fmt {fmt}: {ms*1000:.1f} us/frame  {b/ms/1e6:.1f} GB/s  ({b/ms/1e6/8000*100:.1f}% of 8 TB/s)")

@@ -81,7 +81,7 @@ PROJ_RECT, PROJ_FISH = 0, 1
 MAP_CREATEMAP_CL, MAP_FISH_TO_RECT, MAP_FISH_TO_FISH, MAP_RECT_TO_RECT, MAP_RECT_TO_FISH, MAP_CREATEMAP_CL_OPENCL = range(6)
 OUT_BGR8, OUT_NV12, OUT_NV12_PLANAR = 0, 1, 2
 MAP_PRECISION_IEEE, MAP_PRECISION_OPENCL = 0, 1
-RESAMPLE_DEFAULT, RESAMPLE_CUBIC = 0, 2  # vstab_config.resample (2 = cv::INTER_CUBIC)
+RESAMPLE_DEFAULT, RESAMPLE_CUBIC, RESAMPLE_LANCZOS4 = 0, 2, 4  # vstab_config.resample (2 = cv::INTER_CUBIC, 4 = cv::INTER_LANCZOS4)
 _pp = _c.POINTER(_vp)
 
 # name -> (restype, argtypes); mirrors include/vstab.h one to one
@@ -156,6 +156,9 @@ SIGNATURES = {
     "vstab_cubic_weights": (_i, [_c.POINTER(_c.c_int16)]),
     "vstab_remap_cubic": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _ip, _vp, _sz, _i, _i, _vp]),
     "vstab_warp_nv12_cubic": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_lanczos4_weights": (_i, [_c.POINTER(_c.c_int16)]),
+    "vstab_remap_lanczos4": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _ip, _vp, _sz, _i, _i, _vp]),
+    "vstab_warp_nv12_lanczos4": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -355,6 +358,46 @@ def warp_nv12_cubic(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_
     yo, co = out
     _check(_L.vstab_warp_nv12_cubic(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), int(out_format), yo.data_ptr(), yo.stride(0), co.data_ptr(),
                                     co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_cubic")
+    return yo, co
+
+
+def lanczos4_weights():
+    """vstab_lanczos4_weights: the INTER_LANCZOS4 fixed-point table the kernels use -> (1024, 8, 8) int16, entry fy * 32 + fx."""
+    w = np.zeros(1024 * 64, np.int16)
+    _check(_L.vstab_lanczos4_weights(w.ctypes.data_as(_c.POINTER(_c.c_int16))), "vstab_lanczos4_weights")
+    return w.reshape(1024, 8, 8)
+
+
+def remap_lanczos4(src, mapx, mapy, border=(0, 0, 0), out=None):
+    """vstab_remap_lanczos4: cv::remap(INTER_LANCZOS4, BORDER_CONSTANT border).  Arguments as remap_cubic."""
+    import torch
+    cn = 1 if src.dim() == 2 else src.shape[2]
+    sh, sw = src.shape[0], src.shape[1]
+    dh, dw = mapx.shape
+    if out is None:
+        out = torch.empty((dh, dw) if src.dim() == 2 else (dh, dw, cn), dtype=torch.uint8, device=src.device)
+    b = (_i * 3)(*(list(border) + [0, 0, 0])[:3])
+    _check(_L.vstab_remap_lanczos4(src.data_ptr(), src.stride(0), sw, sh, cn, mapx.data_ptr(), mapx.stride(0) * 4, mapy.data_ptr(), mapy.stride(0) * 4,
+                                   b, out.data_ptr(), out.stride(0), dw, dh, _stream()), "vstab_remap_lanczos4")
+    return out
+
+
+def warp_nv12_lanczos4(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, out=None):
+    """vstab_warp_nv12_lanczos4: the warp with INTER_LANCZOS4.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma) tensors."""
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    p = np.ascontiguousarray(params, np.float32)
+    if out_format == OUT_BGR8:
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
+        _check(_L.vstab_warp_nv12_lanczos4(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), OUT_BGR8, out.data_ptr(), out.stride(0), None, 0, dw, dh,
+                                           _stream()), "vstab_warp_nv12_lanczos4")
+        return out
+    if out is None:
+        out = nv12_out_planes(dw, dh, nv12.device)
+    yo, co = out
+    _check(_L.vstab_warp_nv12_lanczos4(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), int(out_format), yo.data_ptr(), yo.stride(0), co.data_ptr(),
+                                       co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_lanczos4")
     return yo, co
 
 

@@ -41,6 +41,7 @@ vstab_status preload_fused_kernels();
 vstab_status preload_p010_kernels();
 vstab_status preload_planar_kernels();
 vstab_status preload_cubic_kernels();
+vstab_status preload_lanczos4_kernels();
 bool launch_events_pending();
 
 // vstab_pack_p010 with a choice of planes (vstab_warp.hip): luma_only narrows the luma plane alone -- what the 10-bit

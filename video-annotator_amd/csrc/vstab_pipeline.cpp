@@ -1519,6 +1519,7 @@ vstab_status vstab_preload_kernels(void) {
     VSTAB_TRY(preload_p010_kernels());
     VSTAB_TRY(preload_planar_kernels());
     VSTAB_TRY(preload_cubic_kernels());
+    VSTAB_TRY(preload_lanczos4_kernels());
     return VSTAB_OK;
 }
 
@@ -1532,10 +1533,13 @@ vstab_status vstab_create(const vstab_config *cfg, const vstab_source *src, vsta
         return fail(VSTAB_ERR_INVALID, "vstab_create: interpolation must be INTER_LINEAR (1, the only mode the reference passes) or INTER_NEAREST (0)");
     if (cfg->interpolation == 0 && (cfg->lens_mode != 0 || cfg->pixel_depth == 10))
         return fail(VSTAB_ERR_INVALID, "vstab_create: INTER_NEAREST exists for the reference's own map (lens_mode 0, 8-bit pixels)");
-    if (cfg->resample != VSTAB_RESAMPLE_DEFAULT && cfg->resample != VSTAB_RESAMPLE_CUBIC)
-        return fail(VSTAB_ERR_INVALID, "vstab_create: resample must be VSTAB_RESAMPLE_DEFAULT (0) or VSTAB_RESAMPLE_CUBIC (2)");
+    if (cfg->resample != VSTAB_RESAMPLE_DEFAULT && cfg->resample != VSTAB_RESAMPLE_CUBIC && cfg->resample != VSTAB_RESAMPLE_LANCZOS4)
+        return fail(VSTAB_ERR_INVALID,
+                    "vstab_create: resample must be VSTAB_RESAMPLE_DEFAULT (0), VSTAB_RESAMPLE_CUBIC (2) or VSTAB_RESAMPLE_LANCZOS4 (4)");
     if (cfg->resample == VSTAB_RESAMPLE_CUBIC && (cfg->interpolation != 1 || cfg->pixel_depth == 10))
         return fail(VSTAB_ERR_INVALID, "vstab_create: VSTAB_RESAMPLE_CUBIC needs interpolation = INTER_LINEAR (1) and 8-bit pixels");
+    if (cfg->resample == VSTAB_RESAMPLE_LANCZOS4 && (cfg->interpolation != 1 || cfg->pixel_depth == 10))
+        return fail(VSTAB_ERR_INVALID, "vstab_create: VSTAB_RESAMPLE_LANCZOS4 needs interpolation = INTER_LINEAR (1) and 8-bit pixels");
     if (!(cfg->scale > 0) || !(cfg->zoom > 0)) return fail(VSTAB_ERR_INVALID, "vstab_create: scale and zoom must be positive");
     if (cfg->smoother < VSTAB_SMOOTHER_SG || cfg->smoother > VSTAB_SMOOTHER_FIXED) return fail(VSTAB_ERR_INVALID, "vstab_create: unknown smoother");
     if (cfg->lens_mode != 0 && cfg->lens_mode != 1) return fail(VSTAB_ERR_INVALID, "vstab_create: lens_mode must be 0 or 1");
@@ -1663,6 +1667,9 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
     if (H->cfg.resample == VSTAB_RESAMPLE_CUBIC && out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12_PLANAR)
         return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: VSTAB_RESAMPLE_CUBIC emits 8-bit BGR or plane-wise NV12 frames (vstab_pull_frame / _frames / "
                                        "_host / vstab_peek_frame / vstab_pull_frame_nv12_planar), not NV12 through BGR");
+    if (H->cfg.resample == VSTAB_RESAMPLE_LANCZOS4 && out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12_PLANAR)
+        return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: VSTAB_RESAMPLE_LANCZOS4 emits 8-bit BGR or plane-wise NV12 frames (vstab_pull_frame / _frames / "
+                                       "_host / vstab_peek_frame / vstab_pull_frame_nv12_planar), not NV12 through BGR");
     HT t_total(HostTimers::TOTAL);
     while (H->queue.size() <= (size_t)H->cfg.smooth_radius) {  // :453
         if (!H->have_inflight && !H->have_ready && !H->have_estimating && H->prefetched.empty() && H->src_eof) {  // every frame read has been queued
@@ -1723,9 +1730,9 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
     if (S.have_readout) map_params(H->Kin, H->Kout, S.readout * warp_R, p_bottom);
     bool cached = false;
     // (the quantised map holds no chroma positions: the plane-wise warp always evaluates its map)
-    // (nor does the cubic warp read it: it evaluates the map of every frame)
-    const bool cubic = H->cfg.resample == VSTAB_RESAMPLE_CUBIC;
-    if (H->map_cache && !cubic && !S.have_readout && !out_is_10bit(out_format) && out_format != VSTAB_OUT_NV12_PLANAR) {
+    // (nor do the cubic and Lanczos warps read it: they evaluate the map of every frame)
+    const bool cubic = H->cfg.resample == VSTAB_RESAMPLE_CUBIC, lanczos4 = H->cfg.resample == VSTAB_RESAMPLE_LANCZOS4;
+    if (H->map_cache && !cubic && !lanczos4 && !S.have_readout && !out_is_10bit(out_format) && out_format != VSTAB_OUT_NV12_PLANAR) {
         if (H->qmap_valid && std::memcmp(p, H->qmap_params, sizeof(p)) == 0) {
             cached = true;
         } else if (H->have_last_params && std::memcmp(p, H->last_params, sizeof(p)) == 0) {
@@ -1782,6 +1789,14 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
             }
             else st = vstab_warp_nv12_cubic(S.y, S.pitch_y, S.uv, S.pitch_uv, H->w, H->h, p, H->map_mode, out_format, dst, pitch_dst, dst_uv,
                                             pitch_dst_uv, H->ow, H->oh, H->stream);
+        } else if (lanczos4) {
+            // (as for the cubic warp above)
+            if (S.have_readout) {
+                (void)take_launch_events();
+                st = fail(VSTAB_ERR_INVALID, "VSTAB_RESAMPLE_LANCZOS4 warps frames without a read-out rotation (vstab_frame.readout_rotation)");
+            }
+            else st = vstab_warp_nv12_lanczos4(S.y, S.pitch_y, S.uv, S.pitch_uv, H->w, H->h, p, H->map_mode, out_format, dst, pitch_dst, dst_uv,
+                                               pitch_dst_uv, H->ow, H->oh, H->stream);
         } else if (H->cfg.interpolation == 0) {
             // (vstab_warp_nv12_nearest_ex takes the profiler's event pair like the other warp kernels; a refused request launches nothing,
             //  so the pair armed by GpuStage is taken back here instead of staying pending for somebody else's launch)
