@@ -297,6 +297,42 @@ VSTAB_API vstab_status vstab_warp_nv12_lanczos4(const void *y, size_t pitch_y, c
                                                 size_t pitch_dst_uv, int dst_width, int dst_height, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Border modes: cv::remap(src, dst, mapx, mapy, INTER_LINEAR, borderMode, borderValue), whose borderMode FrameSourceWarp.cpp:306-312 leaves
+ * at BORDER_CONSTANT / Scalar().  The values are OpenCV's cv::BorderTypes.  ffmpeg's deshake `edge` option maps onto them: clamp =
+ * BORDER_REPLICATE, mirror = BORDER_REFLECT_101, blank = BORDER_CONSTANT.  OpenCV 4.5's CPU path for 8-bit data, restated
+ * (tests/border_def.py holds it in numpy, tests/golden/border_kat.npz pins it):
+ *   quantisation  as INTER_LINEAR above: sx = cvRound(32 * mapx), X = saturate_cast<short>(sx >> 5), fx = sx & 31; the same for y;
+ *   taps          (X + i, Y + j), i, j in {0, 1}, read at (borderInterpolate(X + i, w, mode), borderInterpolate(Y + j, h, mode)):
+ *                 REPLICATE clamps to [0, len - 1]; REFLECT / REFLECT_101 run OpenCV's loop
+ *                 do { p = p < 0 ? -p - 1 + delta : len - 1 - (p - len) - delta; } while ((unsigned)p >= len), delta = 1 for REFLECT_101,
+ *                 and len == 1 gives 0.  Every output pixel reads four source pixels: no pixel lies "wholly outside", and a NaN map entry
+ *                 (X = Y = -32768, the 0/0 axis pixel of map mode 0) is interpolated like any other position;
+ *   blend         sat_u8((w00 p00 + w01 p01 + w10 p10 + w11 p11 + 512) >> 10), w00 = (32 - fx)(32 - fy), w01 = fx (32 - fy),
+ *                 w10 = (32 - fx) fy, w11 = fx fy -- the bilinear warp's;
+ *   CONSTANT      taps outside take the border value, byte for byte what the warp without a border mode gives (BGR 0; plane-wise 16 and
+ *                 (128, 128); vstab_remap_bilinear's 0).
+ * WRAP (3), TRANSPARENT (5) and any other value are refused with VSTAB_ERR_INVALID.
+ * ------------------------------------------------------------------------------------------ */
+enum { VSTAB_BORDER_CONSTANT = 0, VSTAB_BORDER_REPLICATE = 1, VSTAB_BORDER_REFLECT = 2, VSTAB_BORDER_REFLECT_101 = 4 };
+/* cv::remap(INTER_LINEAR, border_mode) of an 8-bit source of `channels` (1, 2 or 3) interleaved channels with float map planes (pitches in
+ * bytes; map planes 4-byte aligned).  CONSTANT: border value 0, the bytes of vstab_remap_bilinear for channels 1 and 3. */
+VSTAB_API vstab_status vstab_remap_bilinear_border(const void *src, size_t pitch_src, int src_width, int src_height, int channels,
+                                                   const void *map_x, size_t pitch_x, const void *map_y, size_t pitch_y, int border_mode,
+                                                   void *dst, size_t pitch_dst, int dst_width, int dst_height, void *stream);
+/* vstab_warp_nv12_ex with a border mode, map modes 0 .. 5 (the map of each mode bit for bit); rot_bottom != NULL adds vstab_warp_nv12_rs's
+ * rotation per output row (map modes 0, 1 and 5; the others are refused with VSTAB_ERR_INVALID).  out_format:
+ *   VSTAB_OUT_BGR8         cvtColor(NV12 -> BGR) of the frame, then the remap with border_mode (CONSTANT: value 0);
+ *   VSTAB_OUT_NV12_PLANAR  the plane-wise definition above (vstab_out_format): luma with the map; the interleaved chroma plane with
+ *                          map(2 cx, 2 cy) * 0.5f, border-interpolated over the chroma plane's own size src_width / 2 x src_height / 2
+ *                          (CONSTANT: values 16 and (128, 128)).  dst_uv as for vstab_warp_nv12_ex.
+ * VSTAB_OUT_NV12 (through BGR) and any other value are refused with VSTAB_ERR_INVALID.  Source even-sized and <= 32767, chroma plane
+ * 2-byte aligned.  CONSTANT gives the bytes of vstab_warp_nv12_ex / vstab_warp_nv12_rs. */
+VSTAB_API vstab_status vstab_warp_nv12_border(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                              const float params[17], const float *rot_bottom, int map_mode, int out_format, int border_mode,
+                                              void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dst_width, int dst_height,
+                                              void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tracking front-end (device images in; small point lists on the host, as in the reference where
  * goodFeaturesToTrack / calcOpticalFlowPyrLK return std::vector<Point2f>).  These calls
  * synchronise `stream` before returning because their outputs live in host memory.
@@ -645,7 +681,7 @@ typedef struct vstab_profile {
     long epochs_in_turn; /* planned key frames whose detection and tracker launches ran on the second of the handle's two epoch streams, beside
                             the epoch still being tracked on the first (frames up to 1920 x 1200 with a caller on the default stream; 0 otherwise) */
 } vstab_profile;
-/* Loads the library's seven GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
+/* Loads the library's eight GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
  * milliseconds in the middle of the first frames -- and on ROCm 7.2 such a late load can FAULT ("write access to a read-only page") when the
  * process has unloaded another module before it (hipModuleUnload; an OpenCL program released by a filter next door): the new code object may
  * be placed where the old one was still mapped read-only.  vstab_create calls this itself; a host that uses the stateless operators
@@ -653,6 +689,13 @@ typedef struct vstab_profile {
 VSTAB_API vstab_status vstab_preload_kernels(void);
 /* level 0 = off, 1 = time every 8th warp launch only (event records are expensive host calls), 2 = every GPU stage */
 VSTAB_API vstab_status vstab_enable_profiling(vstab_handle *h, int level);
+/* cv::remap's borderMode for the frames this handle warps (the Border modes above), from the next pull on; it may change between pulls, and
+ * each frame is warped with the mode in force when it is pulled.  VSTAB_BORDER_CONSTANT (the default) keeps the handle's usual warp kernels
+ * and output.  Any other mode routes the 8-bit BGR pulls (vstab_pull_frame / _frames / _host / vstab_peek_frame) and the plane-wise pull
+ * (vstab_pull_frame_nv12_planar) to vstab_warp_nv12_border, with a frame's read-out rotation where it has one; vstab_pull_frame_nv12 (NV12
+ * through BGR) is then refused with VSTAB_ERR_INVALID before any frame is taken.  A non-constant mode is VSTAB_ERR_UNSUPPORTED on handles with
+ * pixel_depth 10, interpolation 0 (INTER_NEAREST) or resample != VSTAB_RESAMPLE_DEFAULT; unknown modes and a NULL handle are VSTAB_ERR_INVALID. */
+VSTAB_API vstab_status vstab_set_border_mode(vstab_handle *h, int border_mode);
 /* Synchronises the stream, folds all pending event pairs into the sums and returns them. */
 VSTAB_API vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out);
 

@@ -128,6 +128,15 @@ class FrameSourceWarp : public FrameSource {
     int output_height() const { return m_out_h; }
     // storage for the next returned frame: width*3 <= pitch, output_height() rows, device memory
     void set_output(void *device_bgr, size_t pitch) { m_out = device_bgr, m_pitch = pitch; }
+    // cv::remap's borderMode for the frames pulled from now on (FrameSourceWarp.cpp:306-312 passes BORDER_CONSTANT): a cv::BorderTypes value,
+    // BORDER_CONSTANT (0), BORDER_REPLICATE (1), BORDER_REFLECT (2) or BORDER_REFLECT_101 (4) -- vstab_set_border_mode
+    void set_border_mode(int cv_border_type) {
+        const vstab_status st = vstab_set_border_mode(m_handle, cv_border_type);
+        if (st != VSTAB_OK) {
+            std::fprintf(stderr, "FrameSourceWarp: %s\n", vstab_last_error());
+            throw (int)st;
+        }
+    }
 
     BGRFrame pull_frame() override {  // FrameSourceWarp.cpp:452-476
         if (!m_out) throw -1;

@@ -82,6 +82,8 @@ MAP_CREATEMAP_CL, MAP_FISH_TO_RECT, MAP_FISH_TO_FISH, MAP_RECT_TO_RECT, MAP_RECT
 OUT_BGR8, OUT_NV12, OUT_NV12_PLANAR = 0, 1, 2
 MAP_PRECISION_IEEE, MAP_PRECISION_OPENCL = 0, 1
 RESAMPLE_DEFAULT, RESAMPLE_CUBIC, RESAMPLE_LANCZOS4 = 0, 2, 4  # vstab_config.resample (2 = cv::INTER_CUBIC, 4 = cv::INTER_LANCZOS4)
+# cv::remap's borderMode (cv::BorderTypes values): vstab_remap_bilinear_border, vstab_warp_nv12_border, vstab_set_border_mode
+BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 = 0, 1, 2, 4
 _pp = _c.POINTER(_vp)
 
 # name -> (restype, argtypes); mirrors include/vstab.h one to one
@@ -159,6 +161,9 @@ SIGNATURES = {
     "vstab_lanczos4_weights": (_i, [_c.POINTER(_c.c_int16)]),
     "vstab_remap_lanczos4": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _ip, _vp, _sz, _i, _i, _vp]),
     "vstab_warp_nv12_lanczos4": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_remap_bilinear_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _vp, _sz, _i, _i, _vp]),
+    "vstab_warp_nv12_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_set_border_mode": (_i, [_vp, _i]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -453,6 +458,43 @@ def warp_nv12(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, 
     return yo, co
 
 
+def remap_bilinear_border(src, mapx, mapy, border_mode=BORDER_REFLECT_101, out=None):
+    """vstab_remap_bilinear_border: cv::remap(INTER_LINEAR, border_mode; BORDER_CONSTANT with value 0).  src: (h, w) or (h, w, cn) uint8 CUDA
+    tensor, cn 1..3; mapx / mapy: (dh, dw) float32 CUDA tensors."""
+    import torch
+    cn = 1 if src.dim() == 2 else src.shape[2]
+    sh, sw = src.shape[0], src.shape[1]
+    dh, dw = mapx.shape
+    if out is None:
+        out = torch.empty((dh, dw) if src.dim() == 2 else (dh, dw, cn), dtype=torch.uint8, device=src.device)
+    _check(_L.vstab_remap_bilinear_border(src.data_ptr(), src.stride(0), sw, sh, cn, mapx.data_ptr(), mapx.stride(0) * 4, mapy.data_ptr(),
+                                          mapy.stride(0) * 4, int(border_mode), out.data_ptr(), out.stride(0), dw, dh, _stream()),
+           "vstab_remap_bilinear_border")
+    return out
+
+
+def warp_nv12_border(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, border_mode=BORDER_REFLECT_101, rot_bottom=None, out=None):
+    """vstab_warp_nv12_border: the bilinear warp with a border mode (rot_bottom: vstab_warp_nv12_rs's rotation of the last output row).
+    OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma) tensors."""
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    p = np.ascontiguousarray(params, np.float32)
+    rb = None if rot_bottom is None else np.ascontiguousarray(rot_bottom, np.float32).reshape(9)
+    rbp = None if rb is None else _fptr(rb)
+    if out_format == OUT_BGR8:
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
+        _check(_L.vstab_warp_nv12_border(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, int(mode), OUT_BGR8, int(border_mode), out.data_ptr(),
+                                         out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_border")
+        return out
+    if out is None:
+        out = nv12_out_planes(dw, dh, nv12.device)
+    yo, co = out
+    _check(_L.vstab_warp_nv12_border(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, int(mode), int(out_format), int(border_mode), yo.data_ptr(),
+                                     yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_border")
+    return yo, co
+
+
 def warp_nv12_rs(nv12, params, rot_bottom, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, out=None):
     """vstab_warp_nv12_rs: the warp with a rotation per output row (first row params[8:17], last row rot_bottom)."""
     import torch
@@ -711,8 +753,9 @@ class Stabilizer:
     """vstab_handle wrapper.  `frames`: list of packed NV12 CUDA tensors (cycled by the C ring
     source for `total` pulls) or a Python iterable of such tensors (python callback source)."""
 
-    def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, **cfg_kw):
-        """hold (iterable sources): vstab_frame.hold -- how many further pulls each tensor is kept alive and unchanged
+    def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, **cfg_kw):
+        """border_mode: vstab_set_border_mode right after create (BORDER_* constants; None keeps the constant border).
+        hold (iterable sources): vstab_frame.hold -- how many further pulls each tensor is kept alive and unchanged
         for; from smooth_radius + 14 on the library uses the tensors in place instead of copying them.
         bit_depth / readouts (list sources): P010 frames as int16 tensors of shape (h * 3 / 2, w); one 3x3 read-out
         rotation per ring frame (vstab_frame.readout_rotation).  ring_hold (list sources): the hold the ring source
@@ -771,6 +814,12 @@ class Stabilizer:
         _check(_L.vstab_get_output_info(self._h, _c.byref(ow), _c.byref(oh), _dptr(Ki), _dptr(Ko)), "vstab_get_output_info")
         self.out_size = (ow.value, oh.value)
         self.K_in, self.K_out = Ki.reshape(3, 3), Ko.reshape(3, 3)
+        if border_mode is not None:
+            self.set_border_mode(border_mode)
+
+    def set_border_mode(self, border_mode):
+        """vstab_set_border_mode: cv::remap's borderMode for the frames pulled from now on."""
+        _check(_L.vstab_set_border_mode(self._h, int(border_mode)), "vstab_set_border_mode")
 
     def pull_into(self, out, timing=None):
         """Returns True, or False at end of stream (the reference throws EOF)."""

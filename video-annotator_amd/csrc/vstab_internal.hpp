@@ -42,7 +42,13 @@ vstab_status preload_p010_kernels();
 vstab_status preload_planar_kernels();
 vstab_status preload_cubic_kernels();
 vstab_status preload_lanczos4_kernels();
+vstab_status preload_border_kernels();
 bool launch_events_pending();
+
+// the cv::BorderTypes the border warp serves (vstab_warp_nv12_border, vstab_set_border_mode)
+inline bool border_mode_valid(int m) {
+    return m == VSTAB_BORDER_CONSTANT || m == VSTAB_BORDER_REPLICATE || m == VSTAB_BORDER_REFLECT || m == VSTAB_BORDER_REFLECT_101;
+}
 
 // vstab_pack_p010 with a choice of planes (vstab_warp.hip): luma_only narrows the luma plane alone -- what the 10-bit
 // pipeline needs for its tracker

@@ -886,6 +886,7 @@ struct vstab_handle {
     DevBuf qmap;
     float qmap_params[17] = {0}, last_params[17] = {0};
     bool qmap_valid = false, have_last_params = false, map_cache = true;  // VSTAB_MAP_CACHE=0 disables
+    int border_mode = VSTAB_BORDER_CONSTANT;  // vstab_set_border_mode: applies from the next pull
     long warps_from_cache = 0;
     PinnedBuf marker_pts;           // vstab_config.debug: rotating sets of marker centres, read by the kernel in place
     unsigned marker_set = 0;
@@ -1520,6 +1521,7 @@ vstab_status vstab_preload_kernels(void) {
     VSTAB_TRY(preload_planar_kernels());
     VSTAB_TRY(preload_cubic_kernels());
     VSTAB_TRY(preload_lanczos4_kernels());
+    VSTAB_TRY(preload_border_kernels());
     return VSTAB_OK;
 }
 
@@ -1670,6 +1672,12 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
     if (H->cfg.resample == VSTAB_RESAMPLE_LANCZOS4 && out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12_PLANAR)
         return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: VSTAB_RESAMPLE_LANCZOS4 emits 8-bit BGR or plane-wise NV12 frames (vstab_pull_frame / _frames / "
                                        "_host / vstab_peek_frame / vstab_pull_frame_nv12_planar), not NV12 through BGR");
+    // (the mode in force for this pull: a border warp serves the same two formats as the cubic one, refused before any frame is dequeued)
+    const int border_mode = H->border_mode;
+    const bool border = border_mode != VSTAB_BORDER_CONSTANT;
+    if (border && out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12_PLANAR)
+        return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: a border mode other than VSTAB_BORDER_CONSTANT emits 8-bit BGR or plane-wise NV12 frames "
+                                       "(vstab_pull_frame / _frames / _host / vstab_peek_frame / vstab_pull_frame_nv12_planar), not NV12 through BGR");
     HT t_total(HostTimers::TOTAL);
     while (H->queue.size() <= (size_t)H->cfg.smooth_radius) {  // :453
         if (!H->have_inflight && !H->have_ready && !H->have_estimating && H->prefetched.empty() && H->src_eof) {  // every frame read has been queued
@@ -1730,9 +1738,10 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
     if (S.have_readout) map_params(H->Kin, H->Kout, S.readout * warp_R, p_bottom);
     bool cached = false;
     // (the quantised map holds no chroma positions: the plane-wise warp always evaluates its map)
-    // (nor do the cubic and Lanczos warps read it: they evaluate the map of every frame)
+    // (nor do the cubic, Lanczos and border warps read it: they evaluate the map of every frame; the cached map's kernel has the constant
+    //  border built in)
     const bool cubic = H->cfg.resample == VSTAB_RESAMPLE_CUBIC, lanczos4 = H->cfg.resample == VSTAB_RESAMPLE_LANCZOS4;
-    if (H->map_cache && !cubic && !lanczos4 && !S.have_readout && !out_is_10bit(out_format) && out_format != VSTAB_OUT_NV12_PLANAR) {
+    if (H->map_cache && !cubic && !lanczos4 && !border && !S.have_readout && !out_is_10bit(out_format) && out_format != VSTAB_OUT_NV12_PLANAR) {
         if (H->qmap_valid && std::memcmp(p, H->qmap_params, sizeof(p)) == 0) {
             cached = true;
         } else if (H->have_last_params && std::memcmp(p, H->last_params, sizeof(p)) == 0) {
@@ -1780,6 +1789,9 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
                 if (st == VSTAB_OK) st = vstab_cvt_bgr16_p010(H->bgr16_out.p, bpitch, H->ow, H->oh, dst, pitch_dst, dst_uv, pitch_dst_uv, H->stream);
             }
         }
+        else if (border)
+            st = vstab_warp_nv12_border(S.y, S.pitch_y, S.uv, S.pitch_uv, H->w, H->h, p, S.have_readout ? p_bottom + 8 : nullptr, H->map_mode,
+                                        out_format, border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, H->ow, H->oh, H->stream);
         else if (cubic) {
             // (a frame that carries a read-out rotation can never be served: it is consumed, as INTER_NEAREST consumes it below, and the
             //  profiler's event pair is taken back; the output format was checked on entry)
@@ -1921,6 +1933,17 @@ vstab_status vstab_peek_frame(vstab_handle *h, void *dst, size_t pitch_dst) { re
 vstab_status vstab_enable_profiling(vstab_handle *h, int enable) {
     if (!h) return fail(VSTAB_ERR_INVALID, "null handle");
     h->profiling = enable < 0 ? 0 : enable > 2 ? 2 : enable;
+    return VSTAB_OK;
+}
+
+vstab_status vstab_set_border_mode(vstab_handle *h, int border_mode) {
+    if (!h) return fail(VSTAB_ERR_INVALID, "vstab_set_border_mode: null handle");
+    if (!border_mode_valid(border_mode))
+        return fail(VSTAB_ERR_INVALID, "vstab_set_border_mode: border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)");
+    if (border_mode != VSTAB_BORDER_CONSTANT && (h->cfg.pixel_depth == 10 || h->cfg.interpolation == 0 || h->cfg.resample != VSTAB_RESAMPLE_DEFAULT))
+        return fail(VSTAB_ERR_UNSUPPORTED, "vstab_set_border_mode: border modes other than VSTAB_BORDER_CONSTANT are served for 8-bit pixels with "
+                                           "INTER_LINEAR (interpolation 1) and resample VSTAB_RESAMPLE_DEFAULT");
+    h->border_mode = border_mode;
     return VSTAB_OK;
 }
 

@@ -1,0 +1,456 @@
+// vstab_warp_border.hip -- cv::remap's INTER_LINEAR with a border mode for gfx950: the fused NV12 -> BGR8 warp, the plane-wise NV12 -> NV12
+// warp and the stateless remap of map planes.  Definition (include/vstab.h, vstab_warp_nv12_border; tests/border_def.py): the map quantised
+// to 1/32 pixel and blended as the bilinear warp does it ((sum of four products + 512) >> 10), each of the four taps (X + i, Y + j) read at
+// (borderInterpolate(X + i, w), borderInterpolate(Y + j, h)) -- BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 -- or, BORDER_CONSTANT,
+// the border value where it lies outside the source.
+//
+// The warp kernels (k_warp_border) follow k_warp_cubic's scheme on 64 x 16 output tiles, one workgroup of 256 threads, four rows per thread:
+//   1. map      the exact map of the thread's four pixels in registers (k_quantised_map's arithmetic for every mode; the per-row rotation of
+//               vstab_warp_nv12_rs where RS), quantised;
+//   2. box      min / max of X .. X + 1 and Y .. Y + 1 over every pixel of the tile, reduced over the workgroup, in VIRTUAL coordinates: a
+//               reflected border has no pixel "wholly outside", so a tile far outside the source still reads (mirrored) picture;
+//   3. stage    each virtual position of the box read once through borderInterpolate, converted (BGRx dwords; luma bytes / chroma pairs in
+//               the plane-wise kernel);
+//   4. blend    4 LDS reads per pixel at their natural alignment, v_dot2_i32_i16 on channel pairs gathered by v_perm_b32.
+// A box over the LDS budget (the axis pixel of map mode 0 at -32768, strong minification) is sampled from global memory with the same
+// arithmetic; so is every pixel of the stateless remap.
+#include <climits>
+
+#include <hip/hip_ext.h>
+
+#include "vstab_internal.hpp"
+#include "vstab_resample.hpp"
+
+namespace vstab {
+
+constexpr int BORDER_TW = 64, BORDER_TH = 16, BORDER_RW = 4;  // tile; rows per thread (4 waves x 4 rows)
+constexpr int BORDER_LDS_BYTES = 24 * 1024;                   // stage budget per workgroup, as k_warp_cubic's
+
+struct BorderArgs {
+    CubicArgs c;
+    float rs_d[9];  // RS: rotation of the last output row minus the first's (c.w.p.r), fp32
+    float rs_den;   // and (float)max(dh - 1, 1)
+};
+
+// OpenCV's borderInterpolate in closed form: REPLICATE clamps; REFLECT folds by the period 2 len, REFLECT_101 by 2 len - 2 (len 1 -> 0).
+// Equal to OpenCV's loop for every p in [-32768, 32768] and len in [1, 32767] (tests/test_border_cpu.py restates it).  CONSTANT: p itself.
+template <int BORDER>
+__device__ __forceinline__ int border_index(int p, int len) {
+    if constexpr (BORDER == VSTAB_BORDER_CONSTANT) {
+        return p;
+    } else {
+        if ((unsigned)p < (unsigned)len) return p;
+        if constexpr (BORDER == VSTAB_BORDER_REPLICATE) {
+            return p < 0 ? 0 : len - 1;
+        } else {
+            constexpr int D = BORDER == VSTAB_BORDER_REFLECT_101 ? 1 : 0;
+            if (D && len == 1) return 0;
+            const int per = 2 * len - 2 * D;
+            int q = p % per;
+            q += q < 0 ? per : 0;
+            return q < len ? q : per - 1 + D - q;  // REFLECT: 2 len - 1 - q; REFLECT_101: 2 len - 2 - q
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Sources: a virtual position (X, Y) as a dword with one channel per byte -- read at its border-interpolated position, or the border value
+// (CONSTANT) where it lies outside.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int BORDER>
+struct BorderNv12Bgr {  // NV12 planes converted with the cvtColor arithmetic (BGRx); CONSTANT border 0
+    const uint8_t *y, *uv;
+    size_t pitch_y, pitch_uv;
+    int w, h;
+    __device__ __forceinline__ uint32_t at(int X, int Y) const {  // X, Y inside
+        const int yv = y[(size_t)Y * pitch_y + X];
+        const uint16_t c = *reinterpret_cast<const uint16_t *>(uv + (size_t)(Y >> 1) * pitch_uv + (X & ~1));
+        int b, g, r;
+        yuv_to_bgr(yv, chroma_term(c & 255, c >> 8), b, g, r);
+        return (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
+    }
+    __device__ __forceinline__ uint32_t row_col(int X, int Y) const {  // X, Y already border-interpolated
+        if constexpr (BORDER == VSTAB_BORDER_CONSTANT) {
+            if (!((unsigned)X < (unsigned)w && (unsigned)Y < (unsigned)h)) return 0;
+        }
+        return at(X, Y);
+    }
+};
+template <int CN, int BORDER>
+struct BorderBytes {  // CN interleaved 8-bit channels per pixel
+    const uint8_t *p;
+    size_t pitch;
+    int w, h;
+    uint32_t border;  // CONSTANT: one byte per channel
+    __device__ __forceinline__ uint32_t at(int X, int Y) const {  // X, Y inside
+        const uint8_t *s = p + (size_t)Y * pitch + (size_t)X * CN;
+        uint32_t v = s[0];
+        if constexpr (CN > 1) v |= (uint32_t)s[1] << 8;
+        if constexpr (CN > 2) v |= (uint32_t)s[2] << 16;
+        return v;
+    }
+    __device__ __forceinline__ uint32_t row_col(int X, int Y) const {  // X, Y already border-interpolated
+        if constexpr (BORDER == VSTAB_BORDER_CONSTANT) {
+            if (!((unsigned)X < (unsigned)w && (unsigned)Y < (unsigned)h)) return border;
+        }
+        return at(X, Y);
+    }
+};
+
+// bilinear tap: the top-left virtual position and the two weight pairs {w00, w01}, {w10, w11} as int16 halves
+struct BorderTap {
+    int X, Y;
+    uint32_t w0, w1;
+};
+template <int BORDER>
+__device__ __forceinline__ BorderTap border_tap(float ax32, float ay32, int w, int h) {
+    const CubicTap t = cubic_tap(ax32, ay32);  // cvRound, sat16(s >> 5), s & 31: INTER_LINEAR's quantisation
+    const uint32_t fx = t.f & 31, fy = t.f >> 5;
+    BorderTap b;
+    b.X = t.X, b.Y = t.Y;
+    if constexpr (BORDER == VSTAB_BORDER_CONSTANT) {
+        // every position outside is the border value: a pair of taps wholly outside may move to (-2, -1) / (len, len + 1), which keeps the box
+        // inside [-2, len + 1] (the axis pixel of map mode 0 would stretch it to -32768 otherwise)
+        b.X = min(max(b.X, -2), w), b.Y = min(max(b.Y, -2), h);
+    }
+    b.w0 = ((32 - fx) * (32 - fy)) | ((fx * (32 - fy)) << 16);
+    b.w1 = ((32 - fx) * fy) | ((fx * fy) << 16);
+    return b;
+}
+
+// One channel (byte CH of every tap dword): the horizontally adjacent taps' channel gathered into an int16 pair by v_perm_b32, two
+// v_dot2_i32_i16 against the weight pairs.  Weights sum to 1024: no overflow, no saturation needed.
+template <int CH>
+__device__ __forceinline__ uint32_t border_channel(uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11, const BorderTap &t) {
+    constexpr uint32_t sel = CH | 0x0c00u | ((4u + CH) << 16) | 0x0c000000u;  // [left.CH, 0, right.CH, 0]
+    typedef short short2v __attribute__((ext_vector_type(2)));
+    int acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t01, t00, sel)), __builtin_bit_cast(short2v, t.w0), 512, false);
+    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t11, t10, sel)), __builtin_bit_cast(short2v, t.w1), acc, false);
+    return (uint32_t)acc >> 10;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The tile's phases.
+// ---------------------------------------------------------------------------------------------------------------------
+struct BorderBox {
+    int x0, y0, w, h;
+    bool lds;  // staged (uniform over the workgroup)
+};
+
+// min / max of the top-left tap positions a thread passes in, reduced over the workgroup through red[16] in LDS; the box covers X .. X + 1,
+// Y .. Y + 1 of all of them
+__device__ __forceinline__ BorderBox border_box(int mnx, int mxx, int mny, int mxy, int *red, int cap_elems) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        mnx = min(mnx, __shfl_xor(mnx, m)), mxx = max(mxx, __shfl_xor(mxx, m));
+        mny = min(mny, __shfl_xor(mny, m)), mxy = max(mxy, __shfl_xor(mxy, m));
+    }
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();  // red[] may still be read by a previous box
+    if ((threadIdx.x & 63) == 0) red[4 * wave] = mnx, red[4 * wave + 1] = mxx, red[4 * wave + 2] = mny, red[4 * wave + 3] = mxy;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++) mnx = min(mnx, red[4 * k]), mxx = max(mxx, red[4 * k + 1]), mny = min(mny, red[4 * k + 2]), mxy = max(mxy, red[4 * k + 3]);
+    const bool have = mnx <= mxx;  // else the tile has no pixel (cannot happen: every thread evaluates a clamped pixel)
+    BorderBox b;  // the same in every lane: scalar registers
+    b.x0 = __builtin_amdgcn_readfirstlane(mnx), b.y0 = __builtin_amdgcn_readfirstlane(mny);
+    b.w = __builtin_amdgcn_readfirstlane(have ? mxx - mnx + 2 : 0), b.h = __builtin_amdgcn_readfirstlane(have ? mxy - mny + 2 : 0);
+    b.lds = have && (long)b.w * b.h <= cap_elems;
+    return b;
+}
+
+// every virtual position of the box read once (rows by wave, columns by lane).  A box inside the source -- most tiles -- reads it as it
+// is; any other goes through borderInterpolate, each column's position once for all its rows (the fold's integer remainder is ~20 vector
+// instructions: evaluated per staged element it made the kernel VALU-bound at twice the cost of this form)
+template <int BORDER, typename T, typename Src>
+__device__ __forceinline__ void border_stage(const Src &s, const BorderBox &b, T *lds) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (b.x0 >= 0 && b.x0 + b.w <= s.w && b.y0 >= 0 && b.y0 + b.h <= s.h) {  // uniform
+        for (int r = wave; r < b.h; r += 4)
+            for (int c = lane; c < b.w; c += 64) lds[r * b.w + c] = (T)s.at(b.x0 + c, b.y0 + r);
+    } else {
+        for (int c = lane; c < b.w; c += 64) {
+            const int sx = border_index<BORDER>(b.x0 + c, s.w);
+            for (int r = wave; r < b.h; r += 4) lds[r * b.w + c] = (T)s.row_col(sx, border_index<BORDER>(b.y0 + r, s.h));
+        }
+    }
+}
+
+template <int BORDER, typename T, typename Src>
+__device__ __forceinline__ void border_taps(const Src &s, const BorderBox &b, const T *lds, const BorderTap &t, uint32_t (&v)[4]) {
+    if (b.lds) {
+        const int at = (t.Y - b.y0) * b.w + (t.X - b.x0);
+        if constexpr (sizeof(T) < 4) {
+            // luma bytes / chroma pairs: one ds_read_u8 / ds_read_u16 per tap, at its natural alignment.  Volatile, because the compiler
+            // otherwise merges the two taps of a row into one read at a 1- or 2-byte boundary, which gfx950 executes lane by lane
+            // (profiles/r05_lds_access_cost.txt)
+            typedef __attribute__((address_space(3))) T LdsT;
+            const volatile LdsT *q = (const volatile LdsT *)(lds + at);
+            v[0] = q[0], v[1] = q[1], v[2] = q[b.w], v[3] = q[b.w + 1];
+        } else {  // BGRx dwords: 4-byte aligned whatever the tap
+            const T *q = lds + at;
+            v[0] = q[0], v[1] = q[1], v[2] = q[b.w], v[3] = q[b.w + 1];
+        }
+    } else {
+        const int x0 = border_index<BORDER>(t.X, s.w), x1 = border_index<BORDER>(t.X + 1, s.w);
+        const int y0 = border_index<BORDER>(t.Y, s.h), y1 = border_index<BORDER>(t.Y + 1, s.h);
+        v[0] = s.row_col(x0, y0), v[1] = s.row_col(x1, y0), v[2] = s.row_col(x0, y1), v[3] = s.row_col(x1, y1);
+    }
+}
+
+// 32 * map of output pixel (x, y): cubic_map's arithmetic; RS: the row's own rotation, m_k = fmaf(t, rs_d[k], r[k]) with
+// t = (float)y / rs_den, fed to the mode's arithmetic as the per-row warp (vstab_warp_tile.hpp, map_phase) does
+template <int MODE, bool RS>
+__device__ __forceinline__ void border_map(const BorderArgs &ba, int x, int y, float rfx, float rfy, float &ax, float &ay) {
+    if constexpr (!RS) {
+        cubic_map<MODE>(ba.c, x, y, rfx, rfy, ax, ay);
+    } else {
+        const MapParams &p0 = ba.c.w.p;
+        MapParams P = p0;
+        const float t = div_with_rcp((float)y, ba.rs_den, rcp_refined(ba.rs_den));
+#pragma unroll
+        for (int k = 0; k < 9; k++) P.r[k] = __builtin_fmaf(t, ba.rs_d[k], p0.r[k]);
+        MapParams32 p32 = ba.c.p32;
+        p32.r02 = P.r[2], p32.r12 = P.r[5], p32.r22 = P.r[8];
+        const float vy = norm_coord<MODE>((float)y - P.ocy, P.ofy, rfy);
+        const RowTerm rt = {P.r[1] * vy, P.r[4] * vy, P.r[7] * vy};
+        const float vx = norm_coord<MODE>((float)x - P.ocx, P.ofx, rfx);
+        const ColTerm ct = {P.r[0] * vx, P.r[3] * vx, P.r[6] * vx};
+        map_pixel_ex<MODE>(p32, P, ct, rt, vx, vy, ax, ay);
+    }
+}
+
+// k_warp_border -- NV12 in; PLANAR false: BGR8 out (cvtColor then cv::remap INTER_LINEAR, border mode BORDER; CONSTANT value 0); PLANAR
+// true: the plane-wise warp (luma; chroma at the even pixels' positions halved over the chroma plane's own size; CONSTANT values 16 and
+// (128, 128)).  MODE: map modes 0 .. 5, RS with modes 0 / 1 / 5.
+template <int MODE, bool PLANAR, bool RS, int BORDER>
+__global__ void __launch_bounds__(256) k_warp_border(BorderArgs ba) {
+    const WarpArgs &a = ba.c.w;
+    __shared__ __attribute__((aligned(16))) uint8_t stage[BORDER_LDS_BYTES];
+    __shared__ __attribute__((aligned(16))) int red[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = blockIdx.x * BORDER_TW + lane, y0 = blockIdx.y * BORDER_TH + wave * BORDER_RW;
+    const float rfx = rcp_refined(a.p.ofx), rfy = rcp_refined(a.p.ofy);
+    // 1. map (pixels right of / below the image are evaluated as the last column / row: never stored, inside the box)
+    BorderTap t[BORDER_RW];
+    float ax[BORDER_RW], ay[BORDER_RW];
+#pragma unroll
+    for (int j = 0; j < BORDER_RW; j++) {
+        border_map<MODE, RS>(ba, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
+        t[j] = border_tap<BORDER>(ax[j], ay[j], a.sw, a.sh);
+    }
+    // 2. box of the luma / BGR taps: every pixel, no "touches the source" filter
+    int mnx = INT_MAX, mxx = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
+#pragma unroll
+    for (int j = 0; j < BORDER_RW; j++) mnx = min(mnx, t[j].X), mxx = max(mxx, t[j].X), mny = min(mny, t[j].Y), mxy = max(mxy, t[j].Y);
+    if constexpr (!PLANAR) {
+        const BorderNv12Bgr<BORDER> src = {a.y, a.uv, a.pitch_y, a.pitch_uv, a.sw, a.sh};
+        uint32_t *lds = reinterpret_cast<uint32_t *>(stage);
+        const BorderBox b = border_box(mnx, mxx, mny, mxy, red, BORDER_LDS_BYTES / 4);
+        // 3. stage
+        if (b.lds) border_stage<BORDER>(src, b, lds);
+        __syncthreads();
+        // 4. blend
+#pragma unroll
+        for (int j = 0; j < BORDER_RW; j++) {
+            const int y = y0 + j;
+            if (x >= a.dw || y >= a.dh) continue;
+            uint32_t v[4];
+            border_taps<BORDER>(src, b, lds, t[j], v);
+            uint8_t *o = a.dst + (size_t)y * a.pitch_dst + (size_t)x * 3;
+            o[0] = (uint8_t)border_channel<0>(v[0], v[1], v[2], v[3], t[j]);
+            o[1] = (uint8_t)border_channel<1>(v[0], v[1], v[2], v[3], t[j]);
+            o[2] = (uint8_t)border_channel<2>(v[0], v[1], v[2], v[3], t[j]);
+        }
+    } else {
+        // chroma sample (x / 2, y / 2) of every even output pixel: the map halved (exact) and quantised again, over the chroma plane's size
+        const int cw = a.sw >> 1, ch = a.sh >> 1;
+        const bool cact = !(lane & 1);
+        BorderTap tc[BORDER_RW / 2];
+        int cmnx = INT_MAX, cmxx = INT_MIN, cmny = INT_MAX, cmxy = INT_MIN;
+#pragma unroll
+        for (int k = 0; k < BORDER_RW / 2; k++) {
+            tc[k] = border_tap<BORDER>(ax[2 * k] * 0.5f, ay[2 * k] * 0.5f, cw, ch);
+            if (cact) cmnx = min(cmnx, tc[k].X), cmxx = max(cmxx, tc[k].X), cmny = min(cmny, tc[k].Y), cmxy = max(cmxy, tc[k].Y);
+        }
+        const BorderBytes<1, BORDER> sy = {a.y, a.pitch_y, a.sw, a.sh, 16u};
+        const BorderBytes<2, BORDER> suv = {a.uv, a.pitch_uv, cw, ch, 0x8080u};
+        uint8_t *lds_y = stage;                                                      // luma bytes: half the budget
+        uint16_t *lds_c = reinterpret_cast<uint16_t *>(stage + BORDER_LDS_BYTES / 2);  // chroma pairs: the other half
+        const BorderBox by = border_box(mnx, mxx, mny, mxy, red, BORDER_LDS_BYTES / 2);
+        const BorderBox bc = border_box(cmnx, cmxx, cmny, cmxy, red, BORDER_LDS_BYTES / 4);
+        if (by.lds) border_stage<BORDER>(sy, by, lds_y);
+        if (bc.lds) border_stage<BORDER>(suv, bc, lds_c);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < BORDER_RW; j++) {
+            const int y = y0 + j;
+            if (x >= a.dw || y >= a.dh) continue;
+            uint32_t v[4];
+            border_taps<BORDER>(sy, by, lds_y, t[j], v);
+            a.dst[(size_t)y * a.pitch_dst + x] = (uint8_t)border_channel<0>(v[0], v[1], v[2], v[3], t[j]);
+            if (cact && !(j & 1)) {
+                const BorderTap &q = tc[j / 2];
+                border_taps<BORDER>(suv, bc, lds_c, q, v);
+                uint8_t *o = a.dst_uv + (size_t)(y >> 1) * a.pitch_dst_uv + (size_t)x;  // chroma sample x / 2: bytes x, x + 1
+                o[0] = (uint8_t)border_channel<0>(v[0], v[1], v[2], v[3], q), o[1] = (uint8_t)border_channel<1>(v[0], v[1], v[2], v[3], q);
+            }
+        }
+    }
+}
+
+// k_remap_border -- cv::remap(INTER_LINEAR, BORDER) of CN interleaved 8-bit channels with float map planes (CONSTANT value 0): the stateless
+// building block (any map, NaN / huge / tie entries included).  One thread per output pixel, taps from global memory.
+template <int CN, int BORDER>
+__global__ void __launch_bounds__(256) k_remap_border(const uint8_t *__restrict__ src, size_t pitch_src, int sw, int sh, const float *__restrict__ mapx,
+                                                      size_t pitch_x, const float *__restrict__ mapy, size_t pitch_y, uint8_t *__restrict__ dst,
+                                                      size_t pitch_dst, int dw, int dh) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= dw || y >= dh) return;
+    const float mx = reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(mapx) + (size_t)y * pitch_x)[x];
+    const float my = reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(mapy) + (size_t)y * pitch_y)[x];
+    const BorderTap t = border_tap<BORDER>(mx * 32.0f, my * 32.0f, sw, sh);
+    const BorderBytes<CN, BORDER> s = {src, pitch_src, sw, sh, 0u};
+    const BorderBox none = {0, 0, 0, 0, false};
+    uint32_t v[4];
+    border_taps<BORDER>(s, none, (const uint32_t *)nullptr, t, v);
+    uint8_t *o = dst + (size_t)y * pitch_dst + (size_t)x * CN;
+    o[0] = (uint8_t)border_channel<0>(v[0], v[1], v[2], v[3], t);
+    if constexpr (CN > 1) o[1] = (uint8_t)border_channel<1>(v[0], v[1], v[2], v[3], t);
+    if constexpr (CN > 2) o[2] = (uint8_t)border_channel<2>(v[0], v[1], v[2], v[3], t);
+}
+
+// Kernels of this translation unit are one code object: see preload_warp_kernels
+vstab_status preload_border_kernels() {
+    hipFuncAttributes at;
+    VSTAB_HIP_TRY(hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_remap_border<1, VSTAB_BORDER_CONSTANT>)));
+    return VSTAB_OK;
+}
+
+template <int MODE, bool PLANAR, bool RS, int BORDER>
+static void launch_warp_border(const BorderArgs &ba, dim3 grid, const LaunchEvents &ev, hipStream_t st) {
+    auto kernel = k_warp_border<MODE, PLANAR, RS, BORDER>;
+    if (ev.start) hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ev.start, ev.stop, 0, ba);
+    else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ba);
+}
+
+template <bool PLANAR, bool RS, int BORDER>
+static void launch_warp_border_mode(const BorderArgs &ba, int map_mode, dim3 grid, const LaunchEvents &ev, hipStream_t st) {
+    if constexpr (RS) {  // modes 0 / 1 / 5 (checked by the caller)
+        switch (map_mode) {
+            case VSTAB_MAP_CREATEMAP_CL: launch_warp_border<MAP_CREATEMAP_CL, PLANAR, true, BORDER>(ba, grid, ev, st); break;
+            case VSTAB_MAP_FISH_TO_RECT: launch_warp_border<MAP_FISH_TO_RECT, PLANAR, true, BORDER>(ba, grid, ev, st); break;
+            default: launch_warp_border<MAP_CREATEMAP_CL_OPENCL, PLANAR, true, BORDER>(ba, grid, ev, st); break;
+        }
+    } else {
+        switch (map_mode) {
+            case VSTAB_MAP_CREATEMAP_CL: launch_warp_border<MAP_CREATEMAP_CL, PLANAR, false, BORDER>(ba, grid, ev, st); break;
+            case VSTAB_MAP_FISH_TO_RECT: launch_warp_border<MAP_FISH_TO_RECT, PLANAR, false, BORDER>(ba, grid, ev, st); break;
+            case VSTAB_MAP_FISH_TO_FISH: launch_warp_border<MAP_FISH_TO_FISH, PLANAR, false, BORDER>(ba, grid, ev, st); break;
+            case VSTAB_MAP_RECT_TO_RECT: launch_warp_border<MAP_RECT_TO_RECT, PLANAR, false, BORDER>(ba, grid, ev, st); break;
+            case VSTAB_MAP_RECT_TO_FISH: launch_warp_border<MAP_RECT_TO_FISH, PLANAR, false, BORDER>(ba, grid, ev, st); break;
+            default: launch_warp_border<MAP_CREATEMAP_CL_OPENCL, PLANAR, false, BORDER>(ba, grid, ev, st); break;
+        }
+    }
+}
+
+template <bool PLANAR, bool RS>
+static void launch_warp_border_any(const BorderArgs &ba, int map_mode, int border_mode, dim3 grid, const LaunchEvents &ev, hipStream_t st) {
+    switch (border_mode) {
+        case VSTAB_BORDER_CONSTANT: launch_warp_border_mode<PLANAR, RS, VSTAB_BORDER_CONSTANT>(ba, map_mode, grid, ev, st); break;
+        case VSTAB_BORDER_REPLICATE: launch_warp_border_mode<PLANAR, RS, VSTAB_BORDER_REPLICATE>(ba, map_mode, grid, ev, st); break;
+        case VSTAB_BORDER_REFLECT: launch_warp_border_mode<PLANAR, RS, VSTAB_BORDER_REFLECT>(ba, map_mode, grid, ev, st); break;
+        default: launch_warp_border_mode<PLANAR, RS, VSTAB_BORDER_REFLECT_101>(ba, map_mode, grid, ev, st); break;
+    }
+}
+
+static inline bool border_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+}  // namespace vstab
+
+using namespace vstab;
+
+extern "C" {
+
+vstab_status vstab_remap_bilinear_border(const void *src, size_t pitch_src, int sw, int sh, int channels, const void *map_x, size_t pitch_x,
+                                         const void *map_y, size_t pitch_y, int border_mode, void *dst, size_t pitch_dst, int dw, int dh,
+                                         void *stream) {
+    if (!src || !map_x || !map_y || !dst) return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: null pointer");
+    if (channels < 1 || channels > 3) return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: channels must be 1, 2 or 3");
+    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || sw > 32767 || sh > 32767 || dw > 32767 || dh > 32767)
+        return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: sizes must be in [1, 32767]");
+    if (pitch_src < (size_t)sw * channels || pitch_dst < (size_t)dw * channels || pitch_x < (size_t)dw * 4 || pitch_y < (size_t)dw * 4 || pitch_x % 4 ||
+        pitch_y % 4 || !border_aligned(map_x, 4) || !border_aligned(map_y, 4))
+        return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: pitch smaller than a row, or map planes not 4-byte aligned");
+    if (!border_mode_valid(border_mode))
+        return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or "
+                                       "_REFLECT_101 (4)");
+    const dim3 grid(div_up(dw, 64), div_up(dh, 4));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define VSTAB_LAUNCH(CN, B)                                                                                                                 \
+    hipLaunchKernelGGL((k_remap_border<CN, B>), grid, dim3(256), 0, s, (const uint8_t *)src, pitch_src, sw, sh, (const float *)map_x, pitch_x, \
+                       (const float *)map_y, pitch_y, (uint8_t *)dst, pitch_dst, dw, dh)
+#define VSTAB_BORDERS(CN)                                                                       \
+    switch (border_mode) {                                                                      \
+        case VSTAB_BORDER_CONSTANT: VSTAB_LAUNCH(CN, VSTAB_BORDER_CONSTANT); break;             \
+        case VSTAB_BORDER_REPLICATE: VSTAB_LAUNCH(CN, VSTAB_BORDER_REPLICATE); break;           \
+        case VSTAB_BORDER_REFLECT: VSTAB_LAUNCH(CN, VSTAB_BORDER_REFLECT); break;               \
+        default: VSTAB_LAUNCH(CN, VSTAB_BORDER_REFLECT_101); break;                             \
+    }
+    if (channels == 1) VSTAB_BORDERS(1)
+    else if (channels == 2) VSTAB_BORDERS(2)
+    else VSTAB_BORDERS(3)
+#undef VSTAB_BORDERS
+#undef VSTAB_LAUNCH
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
+vstab_status vstab_warp_nv12_border(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                    const float *rot_bottom, int map_mode, int out_format, int border_mode, void *dst, size_t pitch_dst, void *dst_uv,
+                                    size_t pitch_dst_uv, int dw, int dh, void *stream) {
+    if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: null pointer");
+    if (sw <= 0 || sh <= 0 || (sw & 1) || (sh & 1) || sw > 32767 || sh > 32767)
+        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: source must be even-sized and <= 32767");
+    if (dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: output size must be in [1, 32767]");
+    if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: unknown map mode");
+    if (rot_bottom && map_mode != VSTAB_MAP_CREATEMAP_CL && map_mode != VSTAB_MAP_FISH_TO_RECT && map_mode != VSTAB_MAP_CREATEMAP_CL_OPENCL)
+        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: a rotation per output row (rot_bottom) is served for map modes 0, 1 and 5");
+    if (out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12_PLANAR)
+        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: the border warp emits VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR (NV12 through BGR is not served)");
+    if (!border_mode_valid(border_mode))
+        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or "
+                                       "_REFLECT_101 (4)");
+    const bool planar = out_format == VSTAB_OUT_NV12_PLANAR;
+    if (pitch_y < (size_t)sw || pitch_uv < (size_t)sw || pitch_dst < (size_t)dw * (planar ? 1 : 3))
+        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: pitch smaller than row");
+    if (planar && (!dst_uv || pitch_dst_uv < (size_t)((dw + 1) / 2) * 2))
+        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: plane-wise output needs a chroma plane of 2*ceil(width/2) bytes per row");
+    if (!border_aligned(uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: chroma plane must be 2-B aligned");
+    BorderArgs ba;
+    WarpArgs &a = ba.c.w;
+    a.y = (const uint8_t *)y, a.uv = (const uint8_t *)uv, a.dst = (uint8_t *)dst, a.dst_uv = planar ? (uint8_t *)dst_uv : nullptr;
+    a.pitch_y = pitch_y, a.pitch_uv = pitch_uv, a.pitch_dst = pitch_dst, a.pitch_dst_uv = planar ? pitch_dst_uv : 0;
+    a.sw = sw, a.sh = sh, a.dw = dw, a.dh = dh;
+    MapParams &p = a.p;
+    p.icx = params[0], p.icy = params[1], p.ifx = params[2], p.ify = params[3];
+    p.ocx = params[4], p.ocy = params[5], p.ofx = params[6], p.ofy = params[7];
+    for (int i = 0; i < 9; i++) p.r[i] = params[8 + i];
+    ba.c.p32 = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
+    for (int k = 0; k < 9; k++) ba.rs_d[k] = rot_bottom ? rot_bottom[k] - params[8 + k] : 0.0f;  // fp32, as the definition forms it
+    ba.rs_den = (float)(dh > 1 ? dh - 1 : 1);
+    const dim3 grid(div_up(dw, BORDER_TW), div_up(dh, BORDER_TH));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const LaunchEvents ev = take_launch_events();  // a profiling caller's pair: the kernel's own start / end stamps
+    if (planar) {
+        if (rot_bottom) launch_warp_border_any<true, true>(ba, map_mode, border_mode, grid, ev, st);
+        else launch_warp_border_any<true, false>(ba, map_mode, border_mode, grid, ev, st);
+    } else {
+        if (rot_bottom) launch_warp_border_any<false, true>(ba, map_mode, border_mode, grid, ev, st);
+        else launch_warp_border_any<false, false>(ba, map_mode, border_mode, grid, ev, st);
+    }
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
+}  // extern "C"
