@@ -333,6 +333,39 @@ VSTAB_API vstab_status vstab_warp_nv12_border(const void *y, size_t pitch_y, con
                                               void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Border modes of the cubic and Lanczos resamplers: cv::remap(src, dst, mapx, mapy, INTER_CUBIC or INTER_LANCZOS4, borderMode, borderValue),
+ * the interpolation and the border chosen independently as cv::remap takes them.  OpenCV 4.5's CPU remapBicubic / remapLanczos4 for 8-bit
+ * data on the branch taken when borderMode is not BORDER_CONSTANT (tests/resample_border_def.py holds it in numpy,
+ * tests/golden/resample_border_kat.npz pins it):
+ *   quantisation, weights, blend  as "Bicubic resampling" / "Lanczos resampling" above: (sum + 2^14) >> 15, saturated;
+ *   taps          tap (X - 1 + i, Y - 1 + j) (cubic) or (X - 3 + i, Y - 3 + j) (Lanczos) is read at (borderInterpolate(x, w, mode),
+ *                 borderInterpolate(y, h, mode)) with the modes of "Border modes" above.  Every output pixel reads its full footprint; a NaN
+ *                 map entry (X = Y = -32768) is folded like any other position, so positions reach -32771 .. 32771;
+ *   sum           OpenCV's cval * ONE + sum((S - cval) * w) is sum(S * w) here: every entry of both tables sums to 32768.
+ * BORDER_CONSTANT through these entry points gives exactly the bytes of vstab_remap_cubic / _lanczos4 (with border[]) and
+ * vstab_warp_nv12_cubic / _lanczos4.  WRAP (3), TRANSPARENT (5) and any other value are refused with VSTAB_ERR_INVALID.
+ * ------------------------------------------------------------------------------------------ */
+/* vstab_remap_cubic / vstab_remap_lanczos4 with a border mode: the same arguments and checks, plus border_mode.  border[] is read under
+ * VSTAB_BORDER_CONSTANT only (and may be NULL otherwise). */
+VSTAB_API vstab_status vstab_remap_cubic_border(const void *src, size_t pitch_src, int src_width, int src_height, int channels, const void *map_x,
+                                                size_t pitch_x, const void *map_y, size_t pitch_y, int border_mode, const int border[3], void *dst,
+                                                size_t pitch_dst, int dst_width, int dst_height, void *stream);
+VSTAB_API vstab_status vstab_remap_lanczos4_border(const void *src, size_t pitch_src, int src_width, int src_height, int channels,
+                                                   const void *map_x, size_t pitch_x, const void *map_y, size_t pitch_y, int border_mode,
+                                                   const int border[3], void *dst, size_t pitch_dst, int dst_width, int dst_height, void *stream);
+/* vstab_warp_nv12_cubic / vstab_warp_nv12_lanczos4 with a border mode: the same arguments and output formats (VSTAB_OUT_BGR8,
+ * VSTAB_OUT_NV12_PLANAR), plus border_mode.  VSTAB_OUT_NV12_PLANAR folds luma over the source and the interleaved chroma plane, with
+ * map(2 cx, 2 cy) * 0.5f, over its own size src_width / 2 x src_height / 2, as vstab_warp_nv12_border does.  Source even-sized and
+ * <= 32767, chroma plane 2-byte aligned; every argument is checked before any launch. */
+VSTAB_API vstab_status vstab_warp_nv12_cubic_border(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                                    const float params[17], int map_mode, int out_format, int border_mode, void *dst,
+                                                    size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dst_width, int dst_height, void *stream);
+VSTAB_API vstab_status vstab_warp_nv12_lanczos4_border(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width,
+                                                       int src_height, const float params[17], int map_mode, int out_format, int border_mode,
+                                                       void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dst_width,
+                                                       int dst_height, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tracking front-end (device images in; small point lists on the host, as in the reference where
  * goodFeaturesToTrack / calcOpticalFlowPyrLK return std::vector<Point2f>).  These calls
  * synchronise `stream` before returning because their outputs live in host memory.
@@ -681,7 +714,7 @@ typedef struct vstab_profile {
     long epochs_in_turn; /* planned key frames whose detection and tracker launches ran on the second of the handle's two epoch streams, beside
                             the epoch still being tracked on the first (frames up to 1920 x 1200 with a caller on the default stream; 0 otherwise) */
 } vstab_profile;
-/* Loads the library's eight GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
+/* Loads the library's nine GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
  * milliseconds in the middle of the first frames -- and on ROCm 7.2 such a late load can FAULT ("write access to a read-only page") when the
  * process has unloaded another module before it (hipModuleUnload; an OpenCL program released by a filter next door): the new code object may
  * be placed where the old one was still mapped read-only.  vstab_create calls this itself; a host that uses the stateless operators
@@ -696,6 +729,12 @@ VSTAB_API vstab_status vstab_enable_profiling(vstab_handle *h, int level);
  * through BGR) is then refused with VSTAB_ERR_INVALID before any frame is taken.  A non-constant mode is VSTAB_ERR_UNSUPPORTED on handles with
  * pixel_depth 10, interpolation 0 (INTER_NEAREST) or resample != VSTAB_RESAMPLE_DEFAULT; unknown modes and a NULL handle are VSTAB_ERR_INVALID. */
 VSTAB_API vstab_status vstab_set_border_mode(vstab_handle *h, int border_mode);
+/* vstab_set_border_mode for every 8-bit resampler: the same handle state, and vstab_set_border_mode is the INTER_LINEAR subset of it.  On
+ * handles with resample VSTAB_RESAMPLE_CUBIC or VSTAB_RESAMPLE_LANCZOS4 a non-constant mode routes the BGR pulls and the plane-wise pull to
+ * vstab_warp_nv12_cubic_border / _lanczos4_border (such handles keep refusing frames that carry a read-out rotation); NV12 through BGR is
+ * refused as above.  A non-constant mode is VSTAB_ERR_UNSUPPORTED on handles with pixel_depth 10 or interpolation 0 (INTER_NEAREST); unknown
+ * modes and a NULL handle are VSTAB_ERR_INVALID. */
+VSTAB_API vstab_status vstab_set_border_mode_ex(vstab_handle *h, int border_mode);
 /* Synchronises the stream, folds all pending event pairs into the sums and returns them. */
 VSTAB_API vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out);
 

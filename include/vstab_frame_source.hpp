@@ -129,9 +129,10 @@ class FrameSourceWarp : public FrameSource {
     // storage for the next returned frame: width*3 <= pitch, output_height() rows, device memory
     void set_output(void *device_bgr, size_t pitch) { m_out = device_bgr, m_pitch = pitch; }
     // cv::remap's borderMode for the frames pulled from now on (FrameSourceWarp.cpp:306-312 passes BORDER_CONSTANT): a cv::BorderTypes value,
-    // BORDER_CONSTANT (0), BORDER_REPLICATE (1), BORDER_REFLECT (2) or BORDER_REFLECT_101 (4) -- vstab_set_border_mode
+    // BORDER_CONSTANT (0), BORDER_REPLICATE (1), BORDER_REFLECT (2) or BORDER_REFLECT_101 (4), with cv::INTER_LINEAR, INTER_CUBIC or
+    // INTER_LANCZOS4 -- vstab_set_border_mode_ex
     void set_border_mode(int cv_border_type) {
-        const vstab_status st = vstab_set_border_mode(m_handle, cv_border_type);
+        const vstab_status st = vstab_set_border_mode_ex(m_handle, cv_border_type);
         if (st != VSTAB_OK) {
             std::fprintf(stderr, "FrameSourceWarp: %s\n", vstab_last_error());
             throw (int)st;

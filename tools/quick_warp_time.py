@@ -2,7 +2,8 @@
 env: QW, QH source size; QMODE 0..4 (map mode; 0 = createMap.cl preset cameras); QFMT 0 BGR / 1 NV12 / 2 plane-wise NV12;
 QCUBIC=1 the INTER_CUBIC warp (vstab_warp_nv12_cubic; QFMT 0 or 2) in place of the bilinear one; QLANCZOS=1 the INTER_LANCZOS4 warp
 (vstab_warp_nv12_lanczos4; QFMT 0 or 2); QBORDER=1 / 2 / 4 the bilinear warp with cv::remap's BORDER_REPLICATE / _REFLECT / _REFLECT_101
-(vstab_warp_nv12_border; QFMT 0 or 2; with QRS the rotation per output row).
+(vstab_warp_nv12_border; QFMT 0 or 2; with QRS the rotation per output row); QBORDER with QCUBIC=1 / QLANCZOS=1 the cubic / Lanczos warp
+with that border mode (vstab_warp_nv12_cubic_border / _lanczos4_border; QFMT 0 or 2).
 QPIPE=1: frames/s of the whole pipeline instead (bench.py's 4K setup: its shaky 64-frame ring used in place, preset camera, smooth_radius 30,
 tracking on, the default map precision; 1024-frame preroll, then four 256-frame steps timed with device events), QFMT 0 (vstab_pull_frame) or
 2 (vstab_pull_frame_nv12_planar), QBORDER the handle's border mode (vstab_set_border_mode)."""
@@ -65,7 +66,11 @@ rb = None
 if os.environ.get("QRS"):   # a rotation per output row (rolling shutter): the last row turned by 0.4 degrees about y
     a = np.deg2rad(0.4)
     rb = (np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]]) @ np.asarray(p[8:17], np.float64).reshape(3, 3)).astype(np.float32)
-if border:
+if border and os.environ.get("QCUBIC") == "1":
+    run = lambda i: vs.warp_nv12_cubic_border(frames[i % nf], p, cw, ch, mode, fmt, border, out=outs[i % nf])
+elif border and os.environ.get("QLANCZOS") == "1":
+    run = lambda i: vs.warp_nv12_lanczos4_border(frames[i % nf], p, cw, ch, mode, fmt, border, out=outs[i % nf])
+elif border:
     run = lambda i: vs.warp_nv12_border(frames[i % nf], p, cw, ch, mode, fmt, border, rot_bottom=rb, out=outs[i % nf])
 elif rb is not None:
     run = lambda i: vs.warp_nv12_rs(frames[i % nf], p, rb, cw, ch, mode, fmt, out=outs[i % nf])

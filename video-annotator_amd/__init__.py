@@ -82,7 +82,8 @@ MAP_CREATEMAP_CL, MAP_FISH_TO_RECT, MAP_FISH_TO_FISH, MAP_RECT_TO_RECT, MAP_RECT
 OUT_BGR8, OUT_NV12, OUT_NV12_PLANAR = 0, 1, 2
 MAP_PRECISION_IEEE, MAP_PRECISION_OPENCL = 0, 1
 RESAMPLE_DEFAULT, RESAMPLE_CUBIC, RESAMPLE_LANCZOS4 = 0, 2, 4  # vstab_config.resample (2 = cv::INTER_CUBIC, 4 = cv::INTER_LANCZOS4)
-# cv::remap's borderMode (cv::BorderTypes values): vstab_remap_bilinear_border, vstab_warp_nv12_border, vstab_set_border_mode
+# cv::remap's borderMode (cv::BorderTypes values): vstab_remap_bilinear_border, vstab_warp_nv12_border, vstab_set_border_mode; with INTER_CUBIC /
+# INTER_LANCZOS4: vstab_remap_{cubic,lanczos4}_border, vstab_warp_nv12_{cubic,lanczos4}_border, vstab_set_border_mode_ex
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 = 0, 1, 2, 4
 _pp = _c.POINTER(_vp)
 
@@ -164,6 +165,11 @@ SIGNATURES = {
     "vstab_remap_bilinear_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _vp, _sz, _i, _i, _vp]),
     "vstab_warp_nv12_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_set_border_mode": (_i, [_vp, _i]),
+    "vstab_remap_cubic_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _ip, _vp, _sz, _i, _i, _vp]),
+    "vstab_remap_lanczos4_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _ip, _vp, _sz, _i, _i, _vp]),
+    "vstab_warp_nv12_cubic_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_warp_nv12_lanczos4_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_set_border_mode_ex": (_i, [_vp, _i]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -495,6 +501,59 @@ def warp_nv12_border(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT
     return yo, co
 
 
+def _remap_resample_border(fn, name, src, mapx, mapy, border_mode, border, out):
+    import torch
+    cn = 1 if src.dim() == 2 else src.shape[2]
+    sh, sw = src.shape[0], src.shape[1]
+    dh, dw = mapx.shape
+    if out is None:
+        out = torch.empty((dh, dw) if src.dim() == 2 else (dh, dw, cn), dtype=torch.uint8, device=src.device)
+    b = (_i * 3)(*(list(border) + [0, 0, 0])[:3])
+    _check(fn(src.data_ptr(), src.stride(0), sw, sh, cn, mapx.data_ptr(), mapx.stride(0) * 4, mapy.data_ptr(), mapy.stride(0) * 4, int(border_mode), b,
+              out.data_ptr(), out.stride(0), dw, dh, _stream()), name)
+    return out
+
+
+def remap_cubic_border(src, mapx, mapy, border_mode=BORDER_REFLECT_101, border=(0, 0, 0), out=None):
+    """vstab_remap_cubic_border: cv::remap(INTER_CUBIC, border_mode; border values under BORDER_CONSTANT only).  Arguments as remap_cubic."""
+    return _remap_resample_border(_L.vstab_remap_cubic_border, "vstab_remap_cubic_border", src, mapx, mapy, border_mode, border, out)
+
+
+def remap_lanczos4_border(src, mapx, mapy, border_mode=BORDER_REFLECT_101, border=(0, 0, 0), out=None):
+    """vstab_remap_lanczos4_border: cv::remap(INTER_LANCZOS4, border_mode; border values under BORDER_CONSTANT only).  Arguments as remap_cubic."""
+    return _remap_resample_border(_L.vstab_remap_lanczos4_border, "vstab_remap_lanczos4_border", src, mapx, mapy, border_mode, border, out)
+
+
+def _warp_resample_border(fn, name, nv12, params, dw, dh, mode, out_format, border_mode, out):
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    p = np.ascontiguousarray(params, np.float32)
+    if out_format == OUT_BGR8:
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
+        _check(fn(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), OUT_BGR8, int(border_mode), out.data_ptr(), out.stride(0), None, 0, dw, dh,
+                  _stream()), name)
+        return out
+    if out is None:
+        out = nv12_out_planes(dw, dh, nv12.device)
+    yo, co = out
+    _check(fn(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), int(out_format), int(border_mode), yo.data_ptr(), yo.stride(0), co.data_ptr(),
+              co.stride(0), dw, dh, _stream()), name)
+    return yo, co
+
+
+def warp_nv12_cubic_border(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, border_mode=BORDER_REFLECT_101, out=None):
+    """vstab_warp_nv12_cubic_border: the INTER_CUBIC warp with a border mode.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma)."""
+    return _warp_resample_border(_L.vstab_warp_nv12_cubic_border, "vstab_warp_nv12_cubic_border", nv12, params, dw, dh, mode, out_format, border_mode,
+                                 out)
+
+
+def warp_nv12_lanczos4_border(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, border_mode=BORDER_REFLECT_101, out=None):
+    """vstab_warp_nv12_lanczos4_border: the INTER_LANCZOS4 warp with a border mode.  Arguments and results as warp_nv12_cubic_border."""
+    return _warp_resample_border(_L.vstab_warp_nv12_lanczos4_border, "vstab_warp_nv12_lanczos4_border", nv12, params, dw, dh, mode, out_format,
+                                 border_mode, out)
+
+
 def warp_nv12_rs(nv12, params, rot_bottom, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, out=None):
     """vstab_warp_nv12_rs: the warp with a rotation per output row (first row params[8:17], last row rot_bottom)."""
     import torch
@@ -754,7 +813,7 @@ class Stabilizer:
     source for `total` pulls) or a Python iterable of such tensors (python callback source)."""
 
     def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, **cfg_kw):
-        """border_mode: vstab_set_border_mode right after create (BORDER_* constants; None keeps the constant border).
+        """border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
         hold (iterable sources): vstab_frame.hold -- how many further pulls each tensor is kept alive and unchanged
         for; from smooth_radius + 14 on the library uses the tensors in place instead of copying them.
         bit_depth / readouts (list sources): P010 frames as int16 tensors of shape (h * 3 / 2, w); one 3x3 read-out
@@ -815,11 +874,15 @@ class Stabilizer:
         self.out_size = (ow.value, oh.value)
         self.K_in, self.K_out = Ki.reshape(3, 3), Ko.reshape(3, 3)
         if border_mode is not None:
-            self.set_border_mode(border_mode)
+            self.set_border_mode_ex(border_mode)
 
     def set_border_mode(self, border_mode):
         """vstab_set_border_mode: cv::remap's borderMode for the frames pulled from now on."""
         _check(_L.vstab_set_border_mode(self._h, int(border_mode)), "vstab_set_border_mode")
+
+    def set_border_mode_ex(self, border_mode):
+        """vstab_set_border_mode_ex: set_border_mode for INTER_LINEAR, INTER_CUBIC and INTER_LANCZOS4 handles."""
+        _check(_L.vstab_set_border_mode_ex(self._h, int(border_mode)), "vstab_set_border_mode_ex")
 
     def pull_into(self, out, timing=None):
         """Returns True, or False at end of stream (the reference throws EOF)."""

@@ -1522,6 +1522,7 @@ vstab_status vstab_preload_kernels(void) {
     VSTAB_TRY(preload_cubic_kernels());
     VSTAB_TRY(preload_lanczos4_kernels());
     VSTAB_TRY(preload_border_kernels());
+    VSTAB_TRY(preload_resample_border_kernels());
     return VSTAB_OK;
 }
 
@@ -1738,8 +1739,8 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
     if (S.have_readout) map_params(H->Kin, H->Kout, S.readout * warp_R, p_bottom);
     bool cached = false;
     // (the quantised map holds no chroma positions: the plane-wise warp always evaluates its map)
-    // (nor do the cubic, Lanczos and border warps read it: they evaluate the map of every frame; the cached map's kernel has the constant
-    //  border built in)
+    // (nor do the cubic, Lanczos and border warps read it, with or without a border mode: they evaluate the map of every frame; the cached
+    //  map's kernel has the constant border built in)
     const bool cubic = H->cfg.resample == VSTAB_RESAMPLE_CUBIC, lanczos4 = H->cfg.resample == VSTAB_RESAMPLE_LANCZOS4;
     if (H->map_cache && !cubic && !lanczos4 && !border && !S.have_readout && !out_is_10bit(out_format) && out_format != VSTAB_OUT_NV12_PLANAR) {
         if (H->qmap_valid && std::memcmp(p, H->qmap_params, sizeof(p)) == 0) {
@@ -1789,7 +1790,7 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
                 if (st == VSTAB_OK) st = vstab_cvt_bgr16_p010(H->bgr16_out.p, bpitch, H->ow, H->oh, dst, pitch_dst, dst_uv, pitch_dst_uv, H->stream);
             }
         }
-        else if (border)
+        else if (border && !cubic && !lanczos4)
             st = vstab_warp_nv12_border(S.y, S.pitch_y, S.uv, S.pitch_uv, H->w, H->h, p, S.have_readout ? p_bottom + 8 : nullptr, H->map_mode,
                                         out_format, border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, H->ow, H->oh, H->stream);
         else if (cubic) {
@@ -1799,6 +1800,9 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
                 (void)take_launch_events();
                 st = fail(VSTAB_ERR_INVALID, "VSTAB_RESAMPLE_CUBIC warps frames without a read-out rotation (vstab_frame.readout_rotation)");
             }
+            else if (border)
+                st = vstab_warp_nv12_cubic_border(S.y, S.pitch_y, S.uv, S.pitch_uv, H->w, H->h, p, H->map_mode, out_format, border_mode, dst, pitch_dst,
+                                                  dst_uv, pitch_dst_uv, H->ow, H->oh, H->stream);
             else st = vstab_warp_nv12_cubic(S.y, S.pitch_y, S.uv, S.pitch_uv, H->w, H->h, p, H->map_mode, out_format, dst, pitch_dst, dst_uv,
                                             pitch_dst_uv, H->ow, H->oh, H->stream);
         } else if (lanczos4) {
@@ -1807,6 +1811,9 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
                 (void)take_launch_events();
                 st = fail(VSTAB_ERR_INVALID, "VSTAB_RESAMPLE_LANCZOS4 warps frames without a read-out rotation (vstab_frame.readout_rotation)");
             }
+            else if (border)
+                st = vstab_warp_nv12_lanczos4_border(S.y, S.pitch_y, S.uv, S.pitch_uv, H->w, H->h, p, H->map_mode, out_format, border_mode, dst,
+                                                     pitch_dst, dst_uv, pitch_dst_uv, H->ow, H->oh, H->stream);
             else st = vstab_warp_nv12_lanczos4(S.y, S.pitch_y, S.uv, S.pitch_uv, H->w, H->h, p, H->map_mode, out_format, dst, pitch_dst, dst_uv,
                                                pitch_dst_uv, H->ow, H->oh, H->stream);
         } else if (H->cfg.interpolation == 0) {
@@ -1943,6 +1950,18 @@ vstab_status vstab_set_border_mode(vstab_handle *h, int border_mode) {
     if (border_mode != VSTAB_BORDER_CONSTANT && (h->cfg.pixel_depth == 10 || h->cfg.interpolation == 0 || h->cfg.resample != VSTAB_RESAMPLE_DEFAULT))
         return fail(VSTAB_ERR_UNSUPPORTED, "vstab_set_border_mode: border modes other than VSTAB_BORDER_CONSTANT are served for 8-bit pixels with "
                                            "INTER_LINEAR (interpolation 1) and resample VSTAB_RESAMPLE_DEFAULT");
+    h->border_mode = border_mode;
+    return VSTAB_OK;
+}
+
+vstab_status vstab_set_border_mode_ex(vstab_handle *h, int border_mode) {
+    if (!h) return fail(VSTAB_ERR_INVALID, "vstab_set_border_mode_ex: null handle");
+    if (!border_mode_valid(border_mode))
+        return fail(VSTAB_ERR_INVALID, "vstab_set_border_mode_ex: border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or "
+                                       "_REFLECT_101 (4)");
+    if (border_mode != VSTAB_BORDER_CONSTANT && (h->cfg.pixel_depth == 10 || h->cfg.interpolation == 0))
+        return fail(VSTAB_ERR_UNSUPPORTED, "vstab_set_border_mode_ex: border modes other than VSTAB_BORDER_CONSTANT are served for 8-bit pixels with "
+                                           "INTER_LINEAR, INTER_CUBIC or INTER_LANCZOS4");
     h->border_mode = border_mode;
     return VSTAB_OK;
 }

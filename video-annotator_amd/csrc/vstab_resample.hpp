@@ -1,6 +1,6 @@
-// vstab_resample.hpp -- what the cv::remap kernels of the cubic and Lanczos warps (vstab_warp_cubic.hip, vstab_warp_lanczos4.hip) share:
-// the launch arguments, the quantisation of a map position (the same for INTER_LINEAR, INTER_CUBIC and INTER_LANCZOS4), the sources a tap
-// reads, and the map of an output pixel.
+// vstab_resample.hpp -- what the cv::remap kernels of the cubic and Lanczos warps (vstab_warp_cubic.hip, vstab_warp_lanczos4.hip,
+// vstab_warp_resample_border.hip) share: the launch arguments, the quantisation of a map position (the same for INTER_LINEAR, INTER_CUBIC and
+// INTER_LANCZOS4), the sources a tap reads, the blends, and the map of an output pixel.
 #pragma once
 #include <climits>
 
@@ -59,6 +59,39 @@ struct SrcBytes {  // CN interleaved 8-bit channels per pixel
         return border;
     }
 };
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The blends: (sum + 2^14) >> 15 from the fixed-point tables (vstab_cubic.hpp, vstab_lanczos4.hpp).
+// ---------------------------------------------------------------------------------------------------------------------
+// One channel (byte CH of every tap dword) of the blend: channel pairs of horizontally adjacent taps gathered into int16 pairs by
+// v_perm_b32, eight v_dot2_i32_i16 against the weight pairs.  |sum| < 16 * 32767 * 255: no overflow.
+template <int CH>
+__device__ __forceinline__ uint32_t cubic_channel(const uint32_t (&t)[16], const uint32_t (&w)[8]) {
+    constexpr uint32_t sel = CH | 0x0c00u | ((4u + CH) << 16) | 0x0c000000u;  // [left.CH, 0, right.CH, 0]
+    typedef short short2v __attribute__((ext_vector_type(2)));
+    int acc = 1 << 14;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[4 * r + 1], t[4 * r], sel)), __builtin_bit_cast(short2v, w[2 * r]),
+                                     acc, false);
+        acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[4 * r + 3], t[4 * r + 2], sel)),
+                                     __builtin_bit_cast(short2v, w[2 * r + 1]), acc, false);
+    }
+    return (uint32_t)sat8(acc >> 15);
+}
+
+// One footprint row of one channel (byte CH of every tap dword): channel pairs of horizontally adjacent taps gathered into int16 pairs by
+// v_perm_b32, four v_dot2_i32_i16 against the row's weight pairs.  |sum| over the 64 taps < 64 * 32767 * 255: no overflow.
+template <int CH>
+__device__ __forceinline__ int lz_row(int acc, const uint32_t (&t)[8], const uint4 &w) {
+    constexpr uint32_t sel = CH | 0x0c00u | ((4u + CH) << 16) | 0x0c000000u;  // [left.CH, 0, right.CH, 0]
+    typedef short short2v __attribute__((ext_vector_type(2)));
+    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[1], t[0], sel)), __builtin_bit_cast(short2v, w.x), acc, false);
+    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[3], t[2], sel)), __builtin_bit_cast(short2v, w.y), acc, false);
+    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[5], t[4], sel)), __builtin_bit_cast(short2v, w.z), acc, false);
+    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[7], t[6], sel)), __builtin_bit_cast(short2v, w.w), acc, false);
+    return acc;
+}
 
 // 32 * map of output pixel (x, y): k_quantised_map's arithmetic (the fused kernels' map, bit for bit, in every mode)
 template <int MODE>

@@ -38,23 +38,6 @@ __device__ __forceinline__ void cubic_weights(int f, uint32_t (&w)[8]) {
     w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
 }
 
-// One channel (byte CH of every tap dword) of the blend: channel pairs of horizontally adjacent taps gathered into int16 pairs by
-// v_perm_b32, eight v_dot2_i32_i16 against the weight pairs.  |sum| < 16 * 32767 * 255: no overflow.
-template <int CH>
-__device__ __forceinline__ uint32_t cubic_channel(const uint32_t (&t)[16], const uint32_t (&w)[8]) {
-    constexpr uint32_t sel = CH | 0x0c00u | ((4u + CH) << 16) | 0x0c000000u;  // [left.CH, 0, right.CH, 0]
-    typedef short short2v __attribute__((ext_vector_type(2)));
-    int acc = 1 << 14;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[4 * r + 1], t[4 * r], sel)), __builtin_bit_cast(short2v, w[2 * r]),
-                                     acc, false);
-        acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[4 * r + 3], t[4 * r + 2], sel)),
-                                     __builtin_bit_cast(short2v, w[2 * r + 1]), acc, false);
-    }
-    return (uint32_t)sat8(acc >> 15);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The tile's phases.
 // ---------------------------------------------------------------------------------------------------------------------

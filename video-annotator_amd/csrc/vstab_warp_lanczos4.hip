@@ -33,19 +33,6 @@ __device__ __forceinline__ bool lz_touches(const CubicTap &t, int w, int h) { re
 // row r of an entry's weights: 8 int16 as 4 packed pairs, pair h = columns 2 h (low half) and 2 h + 1
 __device__ __forceinline__ uint4 lz_weights(int f, int r) { return reinterpret_cast<const uint4 *>(g_lanczos4.w)[8 * f + r]; }
 
-// One footprint row of one channel (byte CH of every tap dword): channel pairs of horizontally adjacent taps gathered into int16 pairs by
-// v_perm_b32, four v_dot2_i32_i16 against the row's weight pairs.  |sum| over the 64 taps < 64 * 32767 * 255: no overflow.
-template <int CH>
-__device__ __forceinline__ int lz_row(int acc, const uint32_t (&t)[8], const uint4 &w) {
-    constexpr uint32_t sel = CH | 0x0c00u | ((4u + CH) << 16) | 0x0c000000u;  // [left.CH, 0, right.CH, 0]
-    typedef short short2v __attribute__((ext_vector_type(2)));
-    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[1], t[0], sel)), __builtin_bit_cast(short2v, w.x), acc, false);
-    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[3], t[2], sel)), __builtin_bit_cast(short2v, w.y), acc, false);
-    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[5], t[4], sel)), __builtin_bit_cast(short2v, w.z), acc, false);
-    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t[7], t[6], sel)), __builtin_bit_cast(short2v, w.w), acc, false);
-    return acc;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The tile's phases.
 // ---------------------------------------------------------------------------------------------------------------------
