@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- stabilised frames/s on synthetic NV12 clips (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k|1080p] [--mode auto|warp] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k|1080p] [--mode auto|warp] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input: --batch consecutive frames of
 this rank's clip (default 256 in pipeline mode: four passes over the 64-frame input ring), each emitted
@@ -15,19 +15,25 @@ independent clip per rank (weak scaling, no data-path collective; SURVEY.md sect
 starts the N ranks itself (torch.distributed.run as a child process, before any GPU call) and
 relays rank 0's line; under torch.distributed.run WORLD_SIZE must equal --gpus.
 
-Rank 0 prints ONE JSON line with the driver's contract plus
+Rank 0 prints ONE JSON line with the driver's contract plus what the timed region itself yields:
   "roofline":     the fused undistort-remap kernel's algorithmic bytes / its average duration in the timed region --
                   the kernel's own start / end stamps (hipExtLaunchKernelGGL events on its launch stream, every 8th
                   launch; what rocprofv3's kernel trace reports) -- against the 8 TB/s HBM peak, and
-  "cpu_baseline": the CPU oracle (a port of the reference's cvtColor -> createMap -> remap path)
-                  timed on a bounded sample on this host's cores (all the box's share; "cpu_baseline_1_thread": one), and
-  "copy_ingest":  the same pipeline with every frame COPIED into the library's ring (vstab_frame.hold = 0, what a decoder
-                  that recycles its surface gives), measured after the timed region in the same windowing (steps x batch), and
   "host":         what the rank costs the host: CPU seconds (user + system, all threads) per 1000 frames of the timed region, and
-  "cpu_baseline_full_pipeline": the oracle's whole consume_frame / pull_frame loop (detector, LK, smoothing, warp), and
+  "stages_timed_region": host waits and warp launches of the pipeline as they were in the timed region, and
+  "dump_outputs": with --dump-outputs DIR, the arrays written under DIR and their shapes.
+A plain run does nothing else: it sets up, warms up, times the steps, dumps and prints.  With --full the run goes on, behind
+the timed region and the dump, to measure and check what takes runs of its own:
   "parity_check": one frame emitted after the timed region compared bit for bit with the oracle's warp of the same input
                   frame under the rotation the pipeline reports for it (the run fails if they differ), and
-  "dump_outputs": with --dump-outputs DIR, the arrays written under DIR and their shapes.
+  "stages":       every GPU stage timed, from a short extra pass, and "roofline.alone": the warp kernel launched back to back
+                  with nothing beside it, and
+  "copy_ingest":  the same pipeline with every frame COPIED into the library's ring (vstab_frame.hold = 0, what a decoder
+                  that recycles its surface gives), measured after the timed region in the same windowing (steps x batch), and
+  "ieee_map":     the same pipeline with the CPU-reproducible map, in the same windowing, and
+  "cpu_baseline": the CPU oracle (a port of the reference's cvtColor -> createMap -> remap path)
+                  timed on a bounded sample on this host's cores (all the box's share; "cpu_baseline_1_thread": one), and
+  "cpu_baseline_full_pipeline": the oracle's whole consume_frame / pull_frame loop (detector, LK, smoothing, warp).
 """
 import argparse
 import importlib
@@ -68,7 +74,10 @@ def parse():
                     help="bgr = what FrameSourceWarp emits (the BASELINE metric); nv12 = encoder hand-off through BGR (the BGR frame converted in the "
                          "kernel); p010 = the same for --workload 4k-p010; nv12-planar / p010-planar = SURVEY.md 8(f) row 2 as written: the planes "
                          "remapped as they are, no colour round trip (vstab_pull_frame_nv12_planar / vstab_pull_frame_p010_planar)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region (and the dump): the parity check of an emitted frame, the per-stage pass, the warp kernel alone, "
+                         "the copy-ingest and IEEE-map side passes and the CPU baselines.  A plain run measures the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baselines")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the driver's multi-GPU runs); gloo only for rehearsing ranks on one GPU")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0")
@@ -87,13 +96,13 @@ def parse():
                          "compiler builds it for gfx950 (bit-identical to that code object, which is also the parity checker of the run); "
                          "ieee = createMap.cl with every operation IEEE-rounded (CPU-reproducible; checked against the CPU oracle)")
     ap.add_argument("--skip-ieee-pass", action="store_true",
-                    help="leave out the short extra pass that reports the IEEE-map rate beside the default run's (key `ieee_map`)")
+                    help="--full: leave out the short extra pass that reports the IEEE-map rate beside the default run's (key `ieee_map`)")
     ap.add_argument("--pull", choices=("batch", "single"), default="single",
                     help="pipeline mode, BGR output: one vstab_pull_frame call per frame from this Python loop (default), or one "
                          "vstab_pull_frames call per step (the consumer's loop in C, as the reference's DisplayImage.cpp runs it); "
                          "measured equal within the run-to-run noise at 4K (DESIGN.md section 6)")
     ap.add_argument("--skip-copy-pass", action="store_true",
-                    help="leave out the extra copy-ingest pass behind the timed region (used when the command runs under rocprofv3, so that the "
+                    help="--full: leave out the extra copy-ingest pass behind the timed region (used when the command runs under rocprofv3, so that the "
                          "kernel population of the trace is the timed pipeline's)")
     ap.add_argument("--traffic", default=None, help="measured HBM bytes per launch from PMC passes (profiles/)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -703,10 +712,10 @@ def main():
                   "what": f"the last {len(held)} frames of the last timed step, pixel values as float32, one row per frame: whole frames when they "
                           "fit in 64 MB, else the same seeded sample of element positions of every frame (shape: frames x sample)"}
 
-    # correctness tie-in (outside the timed region): the next frame the pipeline emits, against the oracle's warp of the
+    # correctness tie-in (--full, outside the timed region): the next frame the pipeline emits, against the oracle's warp of the
     # same input frame under the rotation the pipeline reports for it (FrameSourceWarp.cpp:471-475); bit for bit
     parity, parity_against = None, None
-    if mode == "pipeline" and rank == 0:
+    if mode == "pipeline" and rank == 0 and args.full:
         import oracle
         # the checker's OpenMP threads are created on first use and keep the CPU mask of that moment for good: give them this GPU's
         # whole share of the host (the CPU baseline legs below run on the same pool), then go back to the handle's few CPUs
@@ -779,17 +788,17 @@ def main():
     if rank == 0:
         kms = [a.elapsed_time(b) for a, b in kernel_events]
         avg_ms = float(np.mean(kms)) if kms else None
-        stages = None
+        stages, timed_stages = None, None
         if mode == "pipeline":
             p1, p0 = stab.profile(), stab._prof0
             d = {k: p1[k] - p0[k] for k in p1}
             avg_ms = d["gpu_warp_ms"] / max(1, d["warp_timed"])  # every 8th warp launch: the kernel's own start / end stamps
-            stages = {k: round(v / max(1, d["frames_emitted"]) * 1e3, 2) for k, v in d.items() if k.endswith("_ms")}
-            stages = {k.replace("_ms", "_us_per_frame"): v for k, v in stages.items()}
-            stages["key_frames"] = int(d["key_frames"])
-            timed_stages = {k: v for k, v in stages.items() if k.startswith("host_") or k == "key_frames"}
+            timed_stages = {k.replace("_ms", "_us_per_frame"): round(v / max(1, d["frames_emitted"]) * 1e3, 2) for k, v in d.items()
+                            if k.endswith("_ms") and k.startswith("host_")}
+            timed_stages["key_frames"] = int(d["key_frames"])
             timed_stages["gpu_warp_us_per_timed_launch"] = round(avg_ms * 1e3, 2)
             timed_stages["warp_launches_timed"] = int(d["warp_timed"])
+        if mode == "pipeline" and args.full:
             # per-stage table from a short extra pass with every stage timed (outside the timed region)
             stab.enable_profiling(2)
             q0 = stab.profile()
@@ -801,9 +810,9 @@ def main():
             stages["key_frames_per_120"] = int(dq["key_frames"])
         # the same kernel with nothing beside it (no tracker / pyramid / detection kernels on other streams): back-to-back
         # launches on this stream, every launch with its own start / end stamps -- the figure that isolates kernel quality
-        # from co-scheduling
+        # from co-scheduling (--full, like the side passes below)
         alone_us, copy_ingest, ieee_map = None, None, None
-        if mode == "pipeline":
+        if mode == "pipeline" and args.full:
             pa = vs.map_params(K, Ko, rot(7))
             run_alone = lambda i: vs.warp_nv12(clip[i % len(clip)], pa, cw, ch, map_mode, out_fmt, out=outs[i % args.ring])  # cycling inputs and outputs: nothing stays in the caches
             if p010:
@@ -913,25 +922,27 @@ def main():
             line["ieee_map"] = ieee_map
         if stages:
             line["stages"] = stages  # every GPU stage timed (extra pass outside the timed region; chained LK launches off)
+        if timed_stages:
             line["stages_timed_region"] = timed_stages  # host waits + warp launches as they were in the timed region
-        try:
-            os.sched_setaffinity(0, cpu_mask)  # the CPU legs run on this GPU's share of the host, not on the few CPUs the handle's threads were kept on
-        except OSError:
-            pass
-        if world == 1 and not args.no_cpu_baseline and planar:  # the plane-wise outputs are priced against the plane-wise restatement
-            f0 = clip[0].cpu().numpy()
-            line["cpu_baseline"] = cpu_baseline_planar(f0.view(np.uint16) if p010 else f0, w, h, K, Ko, cw, ch, 10 if p010 else 8, blend=1 if p010 else 0)
-            line["cpu_baseline_1_thread"] = cpu_baseline_planar(f0.view(np.uint16) if p010 else f0, w, h, K, Ko, cw, ch, 10 if p010 else 8, blend=1 if p010 else 0,
-                                                                budget_s=6.0, threads=1)
-        elif world == 1 and not args.no_cpu_baseline and p010:
-            line["cpu_baseline"] = cpu_baseline_p010(clip[0].cpu().numpy().view(np.uint16), w, h, K, Ko, cw, ch)
-        elif world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(w, h, K, Ko, cw, ch)
-            line["cpu_baseline_1_thread"] = cpu_baseline(w, h, K, Ko, cw, ch, budget_s=6.0, threads=1)
-            if mode == "pipeline" and not args.no_tracking:
-                host_ring = [f.cpu().numpy() for f in clip]
-                host_frames = [host_ring[i % len(host_ring)] for i in range(400)]  # bounded by the time budget inside
-                line["cpu_baseline_full_pipeline"] = cpu_baseline_full(host_frames, K, Ko, cw, ch, w, h)
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            try:
+                os.sched_setaffinity(0, cpu_mask)  # the CPU legs run on this GPU's share of the host, not on the few CPUs the handle's threads were kept on
+            except OSError:
+                pass
+            if planar:  # the plane-wise outputs are priced against the plane-wise restatement
+                f0 = clip[0].cpu().numpy()
+                line["cpu_baseline"] = cpu_baseline_planar(f0.view(np.uint16) if p010 else f0, w, h, K, Ko, cw, ch, 10 if p010 else 8, blend=1 if p010 else 0)
+                line["cpu_baseline_1_thread"] = cpu_baseline_planar(f0.view(np.uint16) if p010 else f0, w, h, K, Ko, cw, ch, 10 if p010 else 8,
+                                                                    blend=1 if p010 else 0, budget_s=6.0, threads=1)
+            elif p010:
+                line["cpu_baseline"] = cpu_baseline_p010(clip[0].cpu().numpy().view(np.uint16), w, h, K, Ko, cw, ch)
+            else:
+                line["cpu_baseline"] = cpu_baseline(w, h, K, Ko, cw, ch)
+                line["cpu_baseline_1_thread"] = cpu_baseline(w, h, K, Ko, cw, ch, budget_s=6.0, threads=1)
+                if mode == "pipeline" and not args.no_tracking:
+                    host_ring = [f.cpu().numpy() for f in clip]
+                    host_frames = [host_ring[i % len(host_ring)] for i in range(400)]  # bounded by the time budget inside
+                    line["cpu_baseline_full_pipeline"] = cpu_baseline_full(host_frames, K, Ko, cw, ch, w, h)
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.destroy_process_group()

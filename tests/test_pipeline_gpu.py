@@ -1262,7 +1262,7 @@ def test_bench_launches_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--workload", "1080p",
-                        "--steps", "20", "--warmup", "5", "--batch", "8", "--preroll", "40", "--fixed-preroll", "--ring", "16", "--no-cpu-baseline"],
+                        "--steps", "20", "--warmup", "5", "--batch", "8", "--preroll", "40", "--fixed-preroll", "--ring", "16", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1284,7 +1284,7 @@ def test_bench_four_ranks_share_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     shape = ["--workload", "1080p", "--steps", "4", "--warmup", "1", "--batch", "64", "--preroll", "200", "--fixed-preroll", "--ring", "16", "--no-cpu-baseline",
-             "--skip-copy-pass"]
+             "--skip-copy-pass", "--full"]
 
     def bench_line(extra):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra + shape, env=env, capture_output=True, text=True, timeout=900)
@@ -1324,7 +1324,7 @@ def test_bench_rccl_branch_runs_on_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--dist-backend", "nccl", "--workload", "1080p",
-                        "--steps", "2", "--batch", "8", "--preroll", "40", "--fixed-preroll", "--ring", "16", "--no-cpu-baseline"],
+                        "--steps", "2", "--batch", "8", "--preroll", "40", "--fixed-preroll", "--ring", "16", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1347,7 +1347,7 @@ def test_bench_line_of_the_plane_wise_outputs():
     for workload, fmt, bytes_per_launch in (("1080p", "nv12-planar", 1920 * 1080 * 3 // 2 + 1759 * 998 + 2 * 880 * 499),
                                             ("4k-p010", "p010-planar", 2 * (3840 * 2160 * 3 // 2 + 3524 * 1999 + 2 * 1762 * 1000))):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--out-format", fmt, "--steps", "3", "--warmup", "1",
-                            "--batch", "16", "--preroll", "80", "--fixed-preroll", "--ring", "16", "--no-cpu-baseline"],
+                            "--batch", "16", "--preroll", "80", "--fixed-preroll", "--ring", "16", "--no-cpu-baseline", "--full"],
                            env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1365,8 +1365,8 @@ def test_bench_line_of_the_plane_wise_outputs():
 def test_bench_dump_outputs_are_the_same_run_for_run(tmp_path):
     """bench.py --dump-outputs DIR: what the timed path returned in its last step -- the frames the output ring still holds and their
     warp rotations -- as float32 / float64 .npy files under 64 MB in all.  The same arguments give the same inputs and frame schedule
-    (the dump implies a fixed pre-roll), so two runs write the same arrays; --steps sets the number of timed steps.  The warp-only
-    mode dumps its NV12 planes."""
+    (the dump implies a fixed pre-roll), so two runs write the same arrays -- a --full run and a plain one, which checks and measures
+    nothing behind its timed region; --steps sets the number of timed steps.  The warp-only mode dumps its NV12 planes."""
     import json
     import subprocess
     import sys
@@ -1384,12 +1384,14 @@ def test_bench_dump_outputs_are_the_same_run_for_run(tmp_path):
         assert line["steps"] == 3 and len(line["step_ms"]["all"]) == 3 and line["ms_per_step"] > 0
         assert sum(f.stat().st_size for f in out.iterdir()) <= 64 * 10 ** 6
         return line, {f.stem: np.load(f) for f in out.iterdir()}
-    line, a = run(tmp_path / "a", "--preroll", "40")
-    assert line["preroll"] == 40 and line["parity_check"] == "ok"
+    line, a = run(tmp_path / "a", "--preroll", "40", "--full")
+    assert line["preroll"] == 40 and line["parity_check"] == "ok" and "stages" in line and line["roofline"]["alone"]
     assert sorted(a) == ["bgr", "warp_rotation"] and line["dump_outputs"]["arrays"]["bgr"][0] == 16
     assert a["bgr"].dtype == np.float32 and a["warp_rotation"].dtype == np.float64 and a["warp_rotation"].shape == (16, 3, 3)
     assert a["bgr"].max() <= 255 and len(np.unique(a["bgr"])) > 50   # real pixels, not an empty buffer
-    _, b = run(tmp_path / "b", "--preroll", "40")
+    plain, b = run(tmp_path / "b", "--preroll", "40")
+    assert plain["preroll"] == 40 and plain["parity_check"] is None and plain["roofline"]["alone"] is None and plain["stages_timed_region"]
+    assert not {"stages", "copy_ingest", "ieee_map", "cpu_baseline"} & set(plain)
     for k in a:
         assert np.array_equal(a[k], b[k]), k
     line, w = run(tmp_path / "w", "--mode", "warp", "--out-format", "nv12-planar")

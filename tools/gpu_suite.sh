@@ -1,6 +1,6 @@
 #!/bin/bash
-# usage (GPU box): bash tools/gpu_suite.sh [tag]   -- the whole -m gpu suite in one process, smoke(), then the driver's bench command twice;
-# logs and the two bench lines under gpurun_out/<tag>/
+# usage (GPU box): bash tools/gpu_suite.sh [tag]   -- the whole -m gpu suite in one process, smoke(), then the driver's bench command
+# with --full (parity check, side passes, CPU baselines) twice; logs and the two bench lines in the folder $O below
 set -o pipefail
 TAG=${1:-suite}
 O=gpurun_out/$TAG
@@ -11,7 +11,7 @@ tail -4 $O/gputest.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 for i in 1 2; do
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench_default_$i.json 2> $O/bench_default_$i.err || { tail -5 $O/bench_default_$i.err; exit 1; }
+  timeout -k 10 400 python bench.py --steps 20 --warmup 5 --full > $O/bench_default_$i.json 2> $O/bench_default_$i.err || { tail -5 $O/bench_default_$i.err; exit 1; }
   python - <<PY
 import json
 d = json.loads(open("$O/bench_default_$i.json").read().strip().splitlines()[-1])
