@@ -90,6 +90,8 @@ def lib():
         L.vo_pyr_lk.argtypes = [u8p, c.c_size_t, u8p, c.c_size_t, c.c_int, c.c_int, f32p, c.c_int, f32p, u8p]
         L.vo_pyr_lk_iterations.argtypes = [u8p, c.c_size_t, u8p, c.c_size_t, c.c_int, c.c_int, f32p, c.c_int, f32p, u8p, c.c_void_p]
         L.vo_pyr_lk.restype = c.c_int
+        L.vo_pyr_lk_trace.argtypes = [u8p, c.c_size_t, u8p, c.c_size_t, c.c_int, c.c_int, f32p, c.c_int, f32p, u8p, c.c_void_p, f32p]
+        L.vo_pyr_lk_trace.restype = c.c_int
         _LIB = L
     return _LIB
 
@@ -535,6 +537,22 @@ def pyr_lk_iterations(prev, nxt, pts):
     lib().vo_pyr_lk_iterations(ap, a.strides[0], bp, b.strides[0], w, h, pp, n, _p(out, ctypes.c_float), _p(st, ctypes.c_uint8),
                                it.ctypes.data_as(ctypes.c_void_p))
     return out, st, it
+
+
+def pyr_lk_trace(prev, nxt, pts):
+    """pyr_lk plus where every feature stood after each pyramid level (that level's coordinates; NaN for levels the pyramid
+    lacks): -> (next, status, (n, 4, 2) float32, number of levels)."""
+    a, ap = _u8(prev)
+    b, bp = _u8(nxt)
+    h, w = a.shape
+    p, pp = _f32(np.asarray(pts, np.float32).reshape(-1, 2))
+    n = p.shape[0]
+    out = np.zeros((n, 2), np.float32)
+    st = np.zeros(n, np.uint8)
+    lv = np.full((n, 4, 2), np.nan, np.float32)
+    nl = lib().vo_pyr_lk_trace(ap, a.strides[0], bp, b.strides[0], w, h, pp, n, _p(out, ctypes.c_float), _p(st, ctypes.c_uint8), None,
+                               _p(lv, ctypes.c_float))
+    return out, st, lv, nl
 
 
 def pyr_lk(prev, nxt, pts):

@@ -1012,9 +1012,13 @@ static void vo_lk_point(const vo_level *I, const vo_level *J, int level, int max
 
 /* prev_pts/next_pts: n (x,y) pairs; status: n bytes.  Returns number of pyramid levels used. */
 /* iterations (may be NULL): n x 4 ints, the Gauss-Newton iterations each feature ran on pyramid levels 0..3 -- what
- * decides how long the slowest workgroup of the GPU tracker runs. */
-VO_API int vo_pyr_lk_iterations(const uint8_t *prev, size_t ppitch, const uint8_t *next, size_t npitch, int w,
-                                int h, const float *prev_pts, int n, float *next_pts, uint8_t *status, int *iterations) {
+ * decides how long the slowest workgroup of the GPU tracker runs.
+ * level_pts (may be NULL): n x 4 (x, y) floats, where each feature stood in the next image after pyramid level 0..3 -- the
+ * point that level's iterations ended on, in that level's coordinates (a skipped level: the point it started from; levels the
+ * pyramid does not have are left alone).  The GPU tracker fetches the next frame pair's blocks ahead around these
+ * (tests/lk_segments.py). */
+VO_API int vo_pyr_lk_trace(const uint8_t *prev, size_t ppitch, const uint8_t *next, size_t npitch, int w, int h,
+                           const float *prev_pts, int n, float *next_pts, uint8_t *status, int *iterations, float *level_pts) {
     vo_level I[VO_LK_MAXLEVEL + 1], J[VO_LK_MAXLEVEL + 1];
     int nl = vo_build_pyramid(prev, ppitch, w, h, I, 1);
     vo_build_pyramid(next, npitch, w, h, J, 0);
@@ -1022,16 +1026,23 @@ VO_API int vo_pyr_lk_iterations(const uint8_t *prev, size_t ppitch, const uint8_
     if (iterations) memset(iterations, 0, sizeof(int) * 4 * (size_t)n);
     for (int level = nl - 1; level >= 0; level--) {
 #pragma omp parallel for schedule(dynamic, 4)
-        for (int i = 0; i < n; i++)
+        for (int i = 0; i < n; i++) {
             vo_lk_point(&I[level], &J[level], level, nl - 1, prev_pts + 2 * i, next_pts + 2 * i,
                         status + i, iterations ? iterations + 4 * i + level : NULL);
+            if (level_pts) level_pts[8 * i + 2 * level] = next_pts[2 * i], level_pts[8 * i + 2 * level + 1] = next_pts[2 * i + 1];
+        }
     }
     vo_free_pyramid(I, nl);
     vo_free_pyramid(J, nl);
     return nl;
 }
 
+VO_API int vo_pyr_lk_iterations(const uint8_t *prev, size_t ppitch, const uint8_t *next, size_t npitch, int w,
+                                int h, const float *prev_pts, int n, float *next_pts, uint8_t *status, int *iterations) {
+    return vo_pyr_lk_trace(prev, ppitch, next, npitch, w, h, prev_pts, n, next_pts, status, iterations, NULL);
+}
+
 VO_API int vo_pyr_lk(const uint8_t *prev, size_t ppitch, const uint8_t *next, size_t npitch, int w,
                      int h, const float *prev_pts, int n, float *next_pts, uint8_t *status) {
-    return vo_pyr_lk_iterations(prev, ppitch, next, npitch, w, h, prev_pts, n, next_pts, status, NULL);
+    return vo_pyr_lk_trace(prev, ppitch, next, npitch, w, h, prev_pts, n, next_pts, status, NULL, NULL);
 }

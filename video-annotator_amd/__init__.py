@@ -174,6 +174,10 @@ SIGNATURES = {
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
     _f.restype, _f.argtypes = _res, _args
+# test hook, not part of include/vstab.h (lk_segments below)
+_L.vstabx_lk_segments.restype = _i
+_L.vstabx_lk_segments.argtypes = [_pp, _c.POINTER(_sz), _i, _i, _fp, _i, _ip, _i, _pp, _c.POINTER(_sz), _pp, _i, _c.POINTER(_c.c_uint32),
+                                  _c.POINTER(_c.c_uint32), _u8p, _vp]
 
 lib = _L
 ABI_VERSION = 0x56534206  # include/vstab.h: VSTAB_ABI_VERSION ("VSB" + layout version 6)
@@ -732,6 +736,45 @@ def pyr_lk(prev, nxt, pts):
     _check(_L.vstab_pyr_lk(prev.data_ptr(), prev.stride(0), nxt.data_ptr(), nxt.stride(0), w, h, _fptr(p), n, _fptr(out),
                            st.ctypes.data_as(_u8p), _stream()), "vstab_pyr_lk")
     return out, st
+
+
+def lk_segments(frames, pts, segs, uv=None, rings=None, bad_parent=-1, want_pyr=False, w=None, h=None, stream=None):
+    """Test hook vstabx_lk_segments (not part of include/vstab.h): the K + 1 (h, w) uint8 device luma views `frames` (pitched views
+    allowed), n start points, launches of segs[s] frame pairs each (sum K), the first from pts and every later one chained behind the
+    one before.  uv / rings (K + 1 device tensors each): level 1 and the ring copy by k_pack_pyr.  bad_parent: the launch that gets a
+    wrong parent tag.  -> (host records (K, n, 4) uint32, device records (K, n, 4) uint32, pyramid bytes (K + 1, ...) uint8 or None).
+    w / h / pts / frames are taken as given, and stream (default: torch's current one), so that a test of the refusals can hand in what
+    it likes without a device."""
+    n_fr = len(frames)
+    h = frames[0].shape[0] if h is None else h
+    w = frames[0].shape[1] if w is None else w
+    p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+    n = p.shape[0]
+    sg = np.ascontiguousarray(segs, np.int32)
+    K = int(sg.sum()) if sg.size else 0
+    fptrs = (_vp * max(1, n_fr))(*[f.data_ptr() for f in frames])
+    fpit = (_sz * max(1, n_fr))(*[f.stride(0) for f in frames])
+    uptrs = upit = rptrs = None
+    if uv is not None:
+        uptrs = (_vp * len(uv))(*[u.data_ptr() for u in uv])
+        upit = (_sz * len(uv))(*[u.stride(0) for u in uv])
+    if rings is not None:
+        rptrs = (_vp * len(rings))(*[r.data_ptr() for r in rings])
+    hrec = np.zeros((max(K, 0), n, 4), np.uint32)
+    drec = np.zeros((max(K, 0), n, 4), np.uint32)
+    pyr = None
+    if want_pyr:
+        lw, lh, nb = w, h, 0
+        for _ in range(3):
+            lw, lh = (lw + 1) // 2, (lh + 1) // 2
+            if lw <= 21 or lh <= 21:
+                break
+            nb += lw * lh
+        pyr = np.zeros((n_fr, max(nb, 1)), np.uint8)
+    _check(_L.vstabx_lk_segments(fptrs, fpit, int(w), int(h), _fptr(p), n, sg.ctypes.data_as(_ip), int(sg.size), uptrs, upit, rptrs,
+                                 int(bad_parent), hrec.ctypes.data_as(_c.POINTER(_c.c_uint32)), drec.ctypes.data_as(_c.POINTER(_c.c_uint32)),
+                                 None if pyr is None else pyr.ctypes.data_as(_u8p), _stream() if stream is None else stream), "vstabx_lk_segments")
+    return hrec, drec, pyr
 
 
 def estimate_rotation(prev_xy, cur_xy, K_in, K_out, seed=1):
