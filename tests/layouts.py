@@ -271,3 +271,89 @@ def planar_tile_states(mapx, mapy, sw, sh, depth, margin=0):
         else:
             counts["staged"] += 1
     return counts, rwb, cap
+
+
+# ---- the XCD band / tile schedule, restated (vstab_warp_tile.hpp tile_schedule, the three launchers, the block -> tile prologue of
+# k_warp_fused / k_warp_planar).  The constants are the launchers' own; test_tile_schedule_cpu.py pins them against the sources. ------------
+TILES32_RWB8 = 1536          # launch_warp_fused / launch_warp_planar: 64 x 32 tiles (rwb 8) from this many 64 x 32 tiles on
+FUSED_LDS_KB = {4: 20, 8: 40}
+FUSED10_LDS_KB, FUSED10_RWB, FUSED10_TAIL_TILES = 40, 8, 1024
+TAIL_SLOTS_PER_RESIDENT = 256.0   # tail on when the launch has more tiles than 256 x (workgroups a CU holds): more than one round
+SLOTS_PER_WG_PER_CU = 32          # tile_schedule: 32 CUs per XCD
+LDS_BUDGET_KB = 160
+
+
+def fused_launch(dw, dh):
+    """(rwb, lds_kb, tail_rounds) launch_warp_fused picks."""
+    tiles32 = -(-dw // 64) * -(-dh // 32)
+    rwb = 4 if tiles32 < TILES32_RWB8 else 8
+    lds_kb = FUSED_LDS_KB[rwb]
+    tail = 0.5 if -(-dw // 64) * -(-dh // (4 * rwb)) > TAIL_SLOTS_PER_RESIDENT * (LDS_BUDGET_KB // lds_kb) else 0.0
+    return rwb, lds_kb, tail
+
+
+def fused10_launch(dw, dh):
+    """(rwb, lds_kb, tail_rounds) launch_warp_fused10 picks."""
+    tiles = -(-dw // 64) * -(-dh // (4 * FUSED10_RWB))
+    return FUSED10_RWB, FUSED10_LDS_KB, (0.5 if tiles > FUSED10_TAIL_TILES else 0.0)
+
+
+def planar_resident(rwb, lds_kb):
+    return min(LDS_BUDGET_KB // lds_kb, 7 if rwb == 8 else 8, 8)
+
+
+def planar_schedule_launch(dw, dh, depth):
+    """(rwb, lds_kb, tail_rounds) launch_warp_planar picks."""
+    rwb, lds_kb, _ = planar_launch(dw, dh, depth)
+    tail = 0.25 if -(-dw // 64) * -(-dh // (4 * rwb)) > TAIL_SLOTS_PER_RESIDENT * planar_resident(rwb, lds_kb) else 0.0
+    return rwb, lds_kb, tail
+
+
+def _lround(v):
+    return int(np.floor(v + 0.5)) if v >= 0 else -int(np.floor(-v + 0.5))
+
+
+def tile_schedule(dw, dh, rwb, lds_kb, tail_rounds):
+    """-> dict(tiles_x, band_y (9), split_y (8), shares (8), grid) as tile_schedule fills FusedArgs and sizes the grid."""
+    tiles_x = -(-dw // 64)
+    th = 4 * rwb
+    ts = th // 2
+    half_rows = -(-dh // ts)
+    slots = SLOTS_PER_WG_PER_CU * max(1, min(8, LDS_BUDGET_KB // lds_kb))
+    band_y = [min(dh, (k * half_rows // 8) * ts) for k in range(9)]
+    band_y[8] = dh
+    split_y, shares = [], []
+    for k in range(8):
+        rows = band_y[k + 1] - band_y[k]
+        tall_rows_max = rows // th
+        tail_tall_rows = min(tall_rows_max, _lround(tail_rounds * slots / tiles_x))
+        tall_rows = tall_rows_max - tail_tall_rows
+        split_y.append(band_y[k] + tall_rows * th)
+        shares.append(tall_rows * tiles_x + -(-(band_y[k + 1] - split_y[k]) // ts) * tiles_x)
+    return dict(tiles_x=tiles_x, band_y=band_y, split_y=split_y, shares=shares, grid=8 * max(shares))
+
+
+def block_tiles(s, rwb):
+    """The prologue of k_warp_fused / k_warp_planar for every block of the grid of schedule `s`: -> list of (block, x0, ys, rows) of the
+    live blocks -- rows 4 rwb for a tall tile (done whole, or as two half-height tiles), 2 rwb for a half-height one -- and the number
+    of blocks that return at once."""
+    th = 4 * rwb
+    ts = th // 2
+    tx = s["tiles_x"]
+    live, idle = [], 0
+    for b in range(s["grid"]):
+        k, idx = b & 7, b >> 3
+        y_lo, y_sp, y_hi = s["band_y"][k], s["split_y"][k], s["band_y"][k + 1]
+        n_tall = ((y_sp - y_lo) // th) * tx
+        if idx < n_tall:
+            row = idx // tx
+            live.append((b, (idx - row * tx) * 64, y_lo + row * th, th))
+        else:
+            i2 = idx - n_tall
+            row = i2 // tx
+            ys = y_sp + row * ts
+            if ys >= y_hi:
+                idle += 1
+                continue
+            live.append((b, (i2 - row * tx) * 64, ys, ts))
+    return live, idle

@@ -889,9 +889,10 @@ def test_rolling_shutter_readout_rotation_reaches_the_warp(vs, cuda, clip, prec)
     assert differ >= 6                                             # it is not a no-op
 
 
-def _check_against_oracle_state_machine(vs, cuda, frames, K, w, h, r, seed):
-    """Whole-pipeline equivalence on an arbitrary clip: decisions, counts, rotations handed to the warp, pixels."""
-    stab, outs = run_product(vs, cuda, frames, smooth_radius=r, seed=seed)
+def _check_against_oracle_state_machine(vs, cuda, frames, K, w, h, r, seed, **cfg):
+    """Whole-pipeline equivalence on an arbitrary clip: decisions, counts, rotations handed to the warp, pixels.  cfg: further
+    vstab_config fields of the handle (a camera preset other than the default must match K)."""
+    stab, outs = run_product(vs, cuda, frames, smooth_radius=r, seed=seed, **cfg)
     log = stab.frame_log()
     n = len(frames)
     assert len(outs) == max(n - 1, 0) and len(log) == max(n - 1, 0)
@@ -1106,6 +1107,100 @@ def test_pipeline_at_4k_baseline_config(vs, cuda):
     bgr = expect.warp(frames[1], oracle.map_params(K, Ko, s2.warp_rotation(0)), cw, ch)
     ey, euv = oracle.cvt_bgr_nv12(bgr)
     assert np.array_equal(y.cpu().numpy(), ey) and np.array_equal(uv.cpu().numpy().reshape(euv.shape), euv)
+
+
+def _ring_clip(cuda, w, h, K, n, seed, keep=None):
+    """The first `keep` frames of bench.shaky_ring's periodic clip of n frames (rendered on the GPU), on the host, and their rotations."""
+    import torch
+    import bench
+    dev_frames, rots = bench.shaky_ring(torch, cuda, w, h, K, n, seed=seed)
+    keep = n if keep is None else keep
+    return [f.cpu().numpy() for f in dev_frames[:keep]], rots[:keep]
+
+
+def test_pipeline_at_gopro53_87(vs, cuda):
+    """5312 x 4648 (5.3K 8:7, the largest GoPro mode) through a 4:3 preset, r = 1, 4 frames, against the oracle's state machine --
+    decisions, counts, rotations, every emitted frame -- and rotations close to the ground truth."""
+    w, h, r = 5312, 4648, 1
+    K = oracle.get_preset_camera(oracle.GOPRO_H4B_WIDE43_MEASURED, w, h)
+    frames, rots = _ring_clip(cuda, w, h, K, 48, 11, keep=4)
+    log = _check_against_oracle_state_machine(vs, cuda, frames, K, w, h, r, 2, preset=oracle.GOPRO_H4B_WIDE43_MEASURED)
+    assert len(log) == 3
+    for k, lg in enumerate(log, start=1):
+        assert lg["inliers"] >= 40 and oracle.rotation_angle(lg["R"] @ (rots[k] @ rots[k - 1].T).T) < 3e-3, (k, lg["inliers"])
+
+
+@pytest.mark.parametrize("env", [{}, {"VSTAB_PREFETCH": "16"}])
+def test_pipeline_portrait_1080x1920(vs, cuda, monkeypatch, env):
+    """A portrait frame (h > w: every pyramid level, LK border and warp band is portrait; a small frame, so epochs run in turn) against
+    the oracle's state machine over a clip long enough for the 21-frame key-frame counter to fire twice, r = 2, with the default
+    read-ahead and the deepest one."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    w, h, n = 1080, 1920, 44
+    K = oracle.get_preset_camera(4, w, h)
+    frames, _ = _ring_clip(cuda, w, h, K, 120, 3, keep=n)
+    log = _check_against_oracle_state_machine(vs, cuda, frames, K, w, h, 2, 7)
+    keys = [k for k, l in enumerate(log) if l["key"]]
+    assert len([k for k in keys if k > 0]) >= 2 and all(l["inliers"] >= 40 for l in log if not l["key"]), keys
+
+
+def test_epochs_in_turn_at_the_small_frame_bound(vs, cuda, monkeypatch):
+    """Epochs run in turn on the second stream for frames of at most 1920 x 1200 pixels: at 1200 x 1920 (exactly the bound, portrait)
+    the handle's counter says the second stream took epochs, at 1202 x 1920 (just over) it never does; on both, frames, key frames and
+    per-frame counts are those of the run with everything on one stream (VSTAB_EPOCH_OVERLAP=0)."""
+    import torch
+    import bench
+    n = 70
+    for w, in_turn in ((1200, True), (1202, False)):
+        h = 1920
+        K = oracle.get_preset_camera(4, w, h)
+        dev_frames, _ = bench.shaky_ring(torch, cuda, w, h, K, n, seed=7)
+        runs = []
+        for env in ({}, {"VSTAB_EPOCH_OVERLAP": "0"}):
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            stab = vs.Stabilizer(dev_frames, total=n, smooth_radius=2, seed=4)
+            outs = []
+            while True:
+                o = stab.pull()
+                if o is None:
+                    break
+                outs.append(o.cpu().numpy())
+            log = [(l["key"], l["n_corners"], l["n_tracked"], l["inliers"]) for l in stab.frame_log()]
+            runs.append((stab.profile()["epochs_in_turn"], log, outs))
+            stab.close()
+            for k in env:
+                monkeypatch.delenv(k)
+        (second, log, outs), (second0, log0, outs0) = runs
+        assert (second > 0) == in_turn and second0 == 0, (w, second, second0)
+        assert sum(l[0] for l in log) >= 3, (w, log)
+        assert log == log0, w
+        assert len(outs) == len(outs0) == n - 1 and all(np.array_equal(a, b) for a, b in zip(outs, outs0)), w
+        del dev_frames, runs, outs, outs0
+
+
+def test_pipeline_pull_p010_planar_at_gopro53_169(vs, cuda):
+    """pixel_depth = 10 at 5312 x 2988: vstab_pull_frame_p010_planar = the plane-wise 10-bit warp of the original 16-bit planes under the
+    rotation the handle reports, both blends (as test_planar_gpu.py::test_pipeline_pull_p010_planar at 640 x 360)."""
+    import torch
+    w, h, n, r = 5312, 2988, 4, 1
+    K = oracle.get_preset_camera(4, w, h)
+    frames8, _ = _ring_clip(cuda, w, h, K, 48, 13, keep=n)
+    rng = np.random.default_rng(9)
+    wide = [((f.astype(np.uint16) << 8) | (rng.integers(0, 4, f.shape, dtype=np.uint16) << 6) | rng.integers(0, 64, f.shape, dtype=np.uint16)) for f in frames8]
+    dev_frames = [torch.from_numpy(x.view(np.int16)).to(cuda) for x in wide]
+    Ko, (cw, ch) = oracle.get_output_camera(K, w, h)
+    for blend in (0, 1):
+        stab = vs.Stabilizer(dev_frames, total=n, bit_depth=10, smooth_radius=r, seed=5, pixel_depth=10, blend=blend)
+        for i in range(n - 1):
+            oy = torch.empty((ch, cw), dtype=torch.int16, device=cuda)
+            ouv = torch.empty(((ch + 1) // 2, 2 * ((cw + 1) // 2)), dtype=torch.int16, device=cuda)
+            assert stab.pull_p010_planar_into(oy, ouv), i
+            p = oracle.map_params(K, Ko, stab.warp_rotation(i))
+            ey, euv = expect.warp_p010_planar(wide[i + 1][:h], wide[i + 1][h:], p, cw, ch, None, blend)
+            assert np.array_equal(oy.cpu().numpy().view(np.uint16), ey) and np.array_equal(ouv.cpu().numpy().view(np.uint16), euv), (blend, i)
+        stab.close()
 
 
 def test_long_bench_shaped_run_1080p(vs, cuda):
