@@ -92,6 +92,8 @@ def lib():
         L.vo_pyr_lk.restype = c.c_int
         L.vo_pyr_lk_trace.argtypes = [u8p, c.c_size_t, u8p, c.c_size_t, c.c_int, c.c_int, f32p, c.c_int, f32p, u8p, c.c_void_p, f32p]
         L.vo_pyr_lk_trace.restype = c.c_int
+        L.vo_pyr_lk_sums.argtypes = [u8p, c.c_size_t, u8p, c.c_size_t, c.c_int, c.c_int, f32p, c.c_int, f32p, u8p, c.c_void_p]
+        L.vo_pyr_lk_sums.restype = c.c_int
         _LIB = L
     return _LIB
 
@@ -553,6 +555,22 @@ def pyr_lk_trace(prev, nxt, pts):
     nl = lib().vo_pyr_lk_trace(ap, a.strides[0], bp, b.strides[0], w, h, pp, n, _p(out, ctypes.c_float), _p(st, ctypes.c_uint8), None,
                                _p(lv, ctypes.c_float))
     return out, st, lv, nl
+
+
+def pyr_lk_sums(prev, nxt, pts):
+    """pyr_lk plus, per feature, the largest |sum Ix^2|, |sum Ix Iy|, |sum Iy^2| (the window's gradient matrix on any level) and
+    |sum diff Ix|, |sum diff Iy| (any Gauss-Newton iteration), exact: -> (next, status, (n, 5) int64)."""
+    a, ap = _u8(prev)
+    b, bp = _u8(nxt)
+    h, w = a.shape
+    p, pp = _f32(np.asarray(pts, np.float32).reshape(-1, 2))
+    n = p.shape[0]
+    out = np.zeros((n, 2), np.float32)
+    st = np.zeros(n, np.uint8)
+    sums = np.zeros((n, 5), np.int64)
+    lib().vo_pyr_lk_sums(ap, a.strides[0], bp, b.strides[0], w, h, pp, n, _p(out, ctypes.c_float), _p(st, ctypes.c_uint8),
+                         sums.ctypes.data_as(ctypes.c_void_p))
+    return out, st, sums
 
 
 def pyr_lk(prev, nxt, pts):

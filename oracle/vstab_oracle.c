@@ -900,9 +900,15 @@ VO_API void vo_set_lk_accumulation(int mode) { vo_lk_float_acc = mode != 0; }
 static int vo_lk_final_check = 1;
 VO_API void vo_set_lk_final_check(int on) { vo_lk_final_check = on != 0; }
 
-/* iters (may be NULL): incremented once per Gauss-Newton iteration this call starts (vo_pyr_lk_iterations) */
+static inline void vo_lk_sum_max(int64_t *m, int64_t v) {
+    if (v < 0) v = -v;
+    if (v > *m) *m = v;
+}
+
+/* iters (may be NULL): incremented once per Gauss-Newton iteration this call starts (vo_pyr_lk_iterations)
+ * sums (may be NULL): 5 int64, raised to the largest |sum A11|, |A12|, |A22| (this level's window) and |b1|, |b2| (every iteration) */
 static void vo_lk_point(const vo_level *I, const vo_level *J, int level, int max_level,
-                        const float *prev_pt, float *next_pt, uint8_t *status, int *iters) {
+                        const float *prev_pt, float *next_pt, uint8_t *status, int *iters, int64_t *sums) {
     const float half = (VO_LK_WIN - 1) * 0.5f;
     const float lscale = (float)(1.0 / (1 << level));
     float ppx = prev_pt[0] * lscale, ppy = prev_pt[1] * lscale;
@@ -948,6 +954,7 @@ static void vo_lk_point(const vo_level *I, const vo_level *J, int level, int max
             sA22 += (int64_t)iyval * iyval;
             fA11 += (float)(ixval * ixval), fA12 += (float)(ixval * iyval), fA22 += (float)(iyval * iyval);
         }
+    if (sums) vo_lk_sum_max(sums, sA11), vo_lk_sum_max(sums + 1, sA12), vo_lk_sum_max(sums + 2, sA22);
     float A11 = (float)sA11 * FLT_SCALE, A12 = (float)sA12 * FLT_SCALE, A22 = (float)sA22 * FLT_SCALE;
     if (vo_lk_float_acc) A11 = fA11 * FLT_SCALE, A12 = fA12 * FLT_SCALE, A22 = fA22 * FLT_SCALE;
     float D = A11 * A22 - A12 * A12;
@@ -986,6 +993,7 @@ static void vo_lk_point(const vo_level *I, const vo_level *J, int level, int max
                 sb2 += (int64_t)diff * Iyw[y * VO_LK_WIN + x];
                 fb1 += (float)(diff * Ixw[y * VO_LK_WIN + x]), fb2 += (float)(diff * Iyw[y * VO_LK_WIN + x]);
             }
+        if (sums) vo_lk_sum_max(sums + 3, sb1), vo_lk_sum_max(sums + 4, sb2);
         float b1 = (float)sb1 * FLT_SCALE, b2 = (float)sb2 * FLT_SCALE;
         if (vo_lk_float_acc) b1 = fb1 * FLT_SCALE, b2 = fb2 * FLT_SCALE;
         float dx = (A12 * b2 - A22 * b1) * D, dy = (A12 * b1 - A11 * b2) * D;
@@ -1016,25 +1024,39 @@ static void vo_lk_point(const vo_level *I, const vo_level *J, int level, int max
  * level_pts (may be NULL): n x 4 (x, y) floats, where each feature stood in the next image after pyramid level 0..3 -- the
  * point that level's iterations ended on, in that level's coordinates (a skipped level: the point it started from; levels the
  * pyramid does not have are left alone).  The GPU tracker fetches the next frame pair's blocks ahead around these
- * (tests/lk_segments.py). */
-VO_API int vo_pyr_lk_trace(const uint8_t *prev, size_t ppitch, const uint8_t *next, size_t npitch, int w, int h,
-                           const float *prev_pts, int n, float *next_pts, uint8_t *status, int *iterations, float *level_pts) {
+ * (tests/lk_segments.py).
+ * sums (may be NULL): n x 5 int64, per feature the largest |sum A11|, |sum A12|, |sum A22|, |sum b1|, |sum b2| over its levels and
+ * Gauss-Newton iterations -- the magnitudes the GPU tracker's int32 pieces must hold (vo_pyr_lk_sums). */
+VO_API int vo_pyr_lk_trace_sums(const uint8_t *prev, size_t ppitch, const uint8_t *next, size_t npitch, int w, int h,
+                                const float *prev_pts, int n, float *next_pts, uint8_t *status, int *iterations, float *level_pts,
+                                int64_t *sums) {
     vo_level I[VO_LK_MAXLEVEL + 1], J[VO_LK_MAXLEVEL + 1];
     int nl = vo_build_pyramid(prev, ppitch, w, h, I, 1);
     vo_build_pyramid(next, npitch, w, h, J, 0);
     for (int i = 0; i < n; i++) status[i] = 1;
     if (iterations) memset(iterations, 0, sizeof(int) * 4 * (size_t)n);
+    if (sums) memset(sums, 0, sizeof(int64_t) * 5 * (size_t)n);
     for (int level = nl - 1; level >= 0; level--) {
 #pragma omp parallel for schedule(dynamic, 4)
         for (int i = 0; i < n; i++) {
             vo_lk_point(&I[level], &J[level], level, nl - 1, prev_pts + 2 * i, next_pts + 2 * i,
-                        status + i, iterations ? iterations + 4 * i + level : NULL);
+                        status + i, iterations ? iterations + 4 * i + level : NULL, sums ? sums + 5 * i : NULL);
             if (level_pts) level_pts[8 * i + 2 * level] = next_pts[2 * i], level_pts[8 * i + 2 * level + 1] = next_pts[2 * i + 1];
         }
     }
     vo_free_pyramid(I, nl);
     vo_free_pyramid(J, nl);
     return nl;
+}
+
+VO_API int vo_pyr_lk_trace(const uint8_t *prev, size_t ppitch, const uint8_t *next, size_t npitch, int w, int h,
+                           const float *prev_pts, int n, float *next_pts, uint8_t *status, int *iterations, float *level_pts) {
+    return vo_pyr_lk_trace_sums(prev, ppitch, next, npitch, w, h, prev_pts, n, next_pts, status, iterations, level_pts, NULL);
+}
+
+VO_API int vo_pyr_lk_sums(const uint8_t *prev, size_t ppitch, const uint8_t *next, size_t npitch, int w, int h,
+                          const float *prev_pts, int n, float *next_pts, uint8_t *status, int64_t *sums) {
+    return vo_pyr_lk_trace_sums(prev, ppitch, next, npitch, w, h, prev_pts, n, next_pts, status, NULL, NULL, sums);
 }
 
 VO_API int vo_pyr_lk_iterations(const uint8_t *prev, size_t ppitch, const uint8_t *next, size_t npitch, int w,
