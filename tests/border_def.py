@@ -40,7 +40,7 @@ def border_interpolate_loop(p, n, mode):
 
 
 def border_interpolate(p, n, mode):
-    """The closed form the kernels use (csrc/vstab_warp_border.hip, border_index): REPLICATE clamps; REFLECT folds by the period 2 n and
+    """The closed form the kernels use (csrc/vstab_resample.hpp, border_index): REPLICATE clamps; REFLECT folds by the period 2 n and
     REFLECT_101 by 2 n - 2 (n == 1 -> 0); CONSTANT leaves p as it is."""
     p = np.asarray(p, np.int64)
     if mode == CONSTANT:

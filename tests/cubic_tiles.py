@@ -3,7 +3,7 @@ map planes.  Test infrastructure only (a plain module, imported by the tests).
 
 Per 64 x 16 output tile and plane:
   pixels    every pixel of the tile, those right of / below the image evaluated at the last column / row (min(x, dw - 1), min(y, dh - 1))
-  luma/BGR  the quantised map (cubic_def.quantise) of each pixel; only footprints that touch the source (cubic_touches) count
+  luma/BGR  the quantised map (cubic_def.quantise) of each pixel; only footprints that touch the source (Cubic::touches) count
   chroma    the even lanes (even x) of rows y0 and y0 + 2 of each wave -- the even rows of the tile --, quantised from 0.5f * map
             against the (sw / 2) x (sh / 2) chroma plane
   box       X / Y extremes of the touching footprints, columns min X - 1 .. max X + 2, rows min Y - 1 .. max Y + 2

@@ -1,15 +1,34 @@
-// vstab_resample.hpp -- what the cv::remap kernels of the cubic and Lanczos warps (vstab_warp_cubic.hip, vstab_warp_lanczos4.hip,
-// vstab_warp_resample_border.hip) share: the launch arguments, the quantisation of a map position (the same for INTER_LINEAR, INTER_CUBIC and
-// INTER_LANCZOS4), the sources a tap reads, the blends, and the map of an output pixel.
+// vstab_resample.hpp -- the device side of the cv::remap kernels beside the headline warp: INTER_CUBIC (vstab_warp_cubic.hip), INTER_LANCZOS4
+// (vstab_warp_lanczos4.hip) and INTER_LINEAR with a border mode (vstab_warp_border.hip), each with BORDER_CONSTANT, _REPLICATE, _REFLECT and
+// _REFLECT_101.  One statement of each thing: the quantisation of a map position (the same for all three resamplers), OpenCV's
+// borderInterpolate, the sources a tap reads, the tile's box, its staging into LDS, the read of a footprint row, the blends' channel
+// arithmetic, the map of an output pixel, and -- for cubic and Lanczos with a non-constant border -- the tile and the stateless remap
+// themselves, over a resampler trait.
+//
+// The tile (resample_tile; k_warp_cubic, k_warp_lanczos4 and k_warp_border run the same phases from the same pieces in their own units,
+// for the reasons given there and in DESIGN.md §16): 64 x 16 output pixels, one workgroup of 256 threads, four rows per thread:
+//   1. map      the exact map of the thread's four pixels in registers (k_quantised_map's arithmetic for every mode), quantised;
+//   2. box      min / max of the footprints over the tile, reduced over the workgroup: exact, not probed.  BORDER_CONSTANT: the footprints
+//               that touch the source (a tile with none has no box).  Other modes: every footprint, in VIRTUAL coordinates -- a reflected
+//               border has no pixel "wholly outside", so a tile far outside the source still reads (mirrored) picture;
+//   3. stage    each position of the box read once and converted (BGRx dwords; luma bytes / chroma pairs plane-wise): the border value in
+//               every position outside (CONSTANT), or the source at the border-interpolated position;
+//   4. blend    K LDS reads per footprint row, each at its natural alignment, v_dot2_i32_i16 on channel pairs gathered by v_perm_b32.
+// A box over the LDS budget (strong minification, degenerate rotations, the axis pixel of map mode 0 at -32768) is sampled from global
+// memory with the same arithmetic; so is every pixel of the stateless remap.  The map is never written to memory.
 #pragma once
 #include <climits>
 
+#include "../../include/vstab.h"
 #include "vstab_device.hpp"
 #include "vstab_warp_args.hpp"
 
 namespace vstab {
 
-struct CubicArgs {  // the warp kernels' one argument (both resamplers)
+constexpr int RESAMPLE_TW = 64, RESAMPLE_TH = 16, RESAMPLE_RW = 4;  // tile; rows per thread (4 waves x 4 rows)
+constexpr int RESAMPLE_LDS_BYTES = 24 * 1024;                       // stage budget per workgroup: six workgroups per CU by LDS
+
+struct CubicArgs {  // the warp kernels' one argument (all resamplers)
     WarpArgs w;
     MapParams32 p32;
 };
@@ -24,46 +43,188 @@ __device__ __forceinline__ CubicTap cubic_tap(float ax32, float ay32) {  // ax32
     return {min(max(sx >> 5, -32768), 32767), min(max(sy >> 5, -32768), 32767), (sy & 31) * 32 + (sx & 31)};
 }
 
+// 32 * map of output pixel (x, y): k_quantised_map's arithmetic (the fused kernels' map, bit for bit, in every mode)
+template <int MODE>
+__device__ __forceinline__ void cubic_map(const CubicArgs &c, int x, int y, float rfx, float rfy, float &ax, float &ay) {
+    const MapParams &p = c.w.p;
+    const float vy = norm_coord<MODE>((float)y - p.ocy, p.ofy, rfy);
+    const RowTerm rt = {p.r[1] * vy, p.r[4] * vy, p.r[7] * vy};
+    const float vx = norm_coord<MODE>((float)x - p.ocx, p.ofx, rfx);
+    const ColTerm ct = {p.r[0] * vx, p.r[3] * vx, p.r[6] * vx};
+    map_pixel_ex<MODE>(c.p32, p, ct, rt, vx, vy, ax, ay);
+}
+
+// OpenCV's borderInterpolate in closed form: REPLICATE clamps; REFLECT folds by the period 2 len, REFLECT_101 by 2 len - 2 (len 1 -> 0).
+// Equal to OpenCV's loop for every p in [-32768, 32768] and len in [1, 32767] (tests/test_border_cpu.py restates it).  CONSTANT: p itself.
+template <int BORDER>
+__device__ __forceinline__ int border_index(int p, int len) {
+    if constexpr (BORDER == VSTAB_BORDER_CONSTANT) {
+        return p;
+    } else {
+        if ((unsigned)p < (unsigned)len) return p;
+        if constexpr (BORDER == VSTAB_BORDER_REPLICATE) {
+            return p < 0 ? 0 : len - 1;
+        } else {
+            constexpr int D = BORDER == VSTAB_BORDER_REFLECT_101 ? 1 : 0;
+            if (D && len == 1) return 0;
+            const int per = 2 * len - 2 * D;
+            int q = p % per;
+            q += q < 0 ? per : 0;
+            return q < len ? q : per - 1 + D - q;  // REFLECT: 2 len - 1 - q; REFLECT_101: 2 len - 2 - q
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
-// Sources: a tap (X, Y) of a plane as a dword with one channel per byte, the border value where it lies outside.
+// Sources: a position (X, Y) as a dword with one channel per byte -- read at its border-interpolated position, or the border value
+// (CONSTANT) where it lies outside.
 // ---------------------------------------------------------------------------------------------------------------------
-struct SrcNv12Bgr {  // NV12 planes converted with the cvtColor arithmetic (BGRx); border 0 (cv::remap's Scalar(0))
+template <int BORDER>
+struct BorderNv12Bgr {  // NV12 planes converted with the cvtColor arithmetic (BGRx); CONSTANT border 0 (cv::remap's Scalar(0))
     const uint8_t *y, *uv;
     size_t pitch_y, pitch_uv;
     int w, h;
-    __device__ __forceinline__ uint32_t operator()(int X, int Y) const {
-        if ((unsigned)X < (unsigned)w && (unsigned)Y < (unsigned)h) {
-            const int yv = y[(size_t)Y * pitch_y + X];
-            const uint16_t c = *reinterpret_cast<const uint16_t *>(uv + (size_t)(Y >> 1) * pitch_uv + (X & ~1));
-            int b, g, r;
-            yuv_to_bgr(yv, chroma_term(c & 255, c >> 8), b, g, r);
-            return (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
+    __device__ __forceinline__ uint32_t at(int X, int Y) const {  // X, Y inside
+        const int yv = y[(size_t)Y * pitch_y + X];
+        const uint16_t c = *reinterpret_cast<const uint16_t *>(uv + (size_t)(Y >> 1) * pitch_uv + (X & ~1));
+        int b, g, r;
+        yuv_to_bgr(yv, chroma_term(c & 255, c >> 8), b, g, r);
+        return (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
+    }
+    __device__ __forceinline__ uint32_t row_col(int X, int Y) const {  // X, Y already border-interpolated
+        if constexpr (BORDER == VSTAB_BORDER_CONSTANT) {
+            if ((unsigned)X < (unsigned)w && (unsigned)Y < (unsigned)h) return at(X, Y);
+            return 0;
+        } else {
+            return at(X, Y);
         }
-        return 0;
     }
 };
-template <int CN>
-struct SrcBytes {  // CN interleaved 8-bit channels per pixel
+template <int CN, int BORDER>
+struct BorderBytes {  // CN interleaved 8-bit channels per pixel
     const uint8_t *p;
     size_t pitch;
     int w, h;
-    uint32_t border;  // one byte per channel
-    __device__ __forceinline__ uint32_t operator()(int X, int Y) const {
-        if ((unsigned)X < (unsigned)w && (unsigned)Y < (unsigned)h) {
-            const uint8_t *s = p + (size_t)Y * pitch + (size_t)X * CN;
-            uint32_t v = s[0];
-            if constexpr (CN > 1) v |= (uint32_t)s[1] << 8;
-            if constexpr (CN > 2) v |= (uint32_t)s[2] << 16;
-            return v;
+    uint32_t border;  // CONSTANT: one byte per channel
+    __device__ __forceinline__ uint32_t at(int X, int Y) const {  // X, Y inside
+        const uint8_t *s = p + (size_t)Y * pitch + (size_t)X * CN;
+        uint32_t v = s[0];
+        if constexpr (CN > 1) v |= (uint32_t)s[1] << 8;
+        if constexpr (CN > 2) v |= (uint32_t)s[2] << 16;
+        return v;
+    }
+    __device__ __forceinline__ uint32_t row_col(int X, int Y) const {  // X, Y already border-interpolated
+        if constexpr (BORDER == VSTAB_BORDER_CONSTANT) {
+            if ((unsigned)X < (unsigned)w && (unsigned)Y < (unsigned)h) return at(X, Y);
+            return border;
+        } else {
+            return at(X, Y);
         }
-        return border;
     }
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The blends: (sum + 2^14) >> 15 from the fixed-point tables (vstab_cubic.hpp, vstab_lanczos4.hpp).
+// The tile's box, its staging and the read of a footprint row.
 // ---------------------------------------------------------------------------------------------------------------------
-// One channel (byte CH of every tap dword) of the blend: channel pairs of horizontally adjacent taps gathered into int16 pairs by
+struct TileBox {
+    int x0, y0, w, h;
+    bool lds;  // staged (uniform over the workgroup)
+};
+
+// min / max of the tap anchors (X, Y) a thread passes in, reduced over the workgroup through red[16] in LDS.  The box covers the K x K
+// footprint X - LO .. X - LO + K - 1 of all of them (<1, 4> cubic, <3, 8> Lanczos, <0, 2> bilinear).  No anchor from any thread: no box.
+// SCALAR: the box, the same in every lane, in scalar registers.  The kernels whose box is in virtual coordinates were measured with it, the
+// cubic and Lanczos kernels of the constant border without; each keeps its form ("After the consolidation").
+template <int LO, int K, bool SCALAR>
+__device__ __forceinline__ TileBox tile_box(int mnx, int mxx, int mny, int mxy, int *red, int cap_elems) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        mnx = min(mnx, __shfl_xor(mnx, m)), mxx = max(mxx, __shfl_xor(mxx, m));
+        mny = min(mny, __shfl_xor(mny, m)), mxy = max(mxy, __shfl_xor(mxy, m));
+    }
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();  // red[] may still be read by a previous box
+    if ((threadIdx.x & 63) == 0) red[4 * wave] = mnx, red[4 * wave + 1] = mxx, red[4 * wave + 2] = mny, red[4 * wave + 3] = mxy;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++) mnx = min(mnx, red[4 * k]), mxx = max(mxx, red[4 * k + 1]), mny = min(mny, red[4 * k + 2]), mxy = max(mxy, red[4 * k + 3]);
+    const bool have = mnx <= mxx;
+    TileBox b;
+    if constexpr (SCALAR) {
+        b.x0 = __builtin_amdgcn_readfirstlane(mnx - LO), b.y0 = __builtin_amdgcn_readfirstlane(mny - LO);
+        b.w = __builtin_amdgcn_readfirstlane(have ? mxx - mnx + K : 0), b.h = __builtin_amdgcn_readfirstlane(have ? mxy - mny + K : 0);
+    } else {
+        b.x0 = mnx - LO, b.y0 = mny - LO, b.w = have ? mxx - mnx + K : 0, b.h = have ? mxy - mny + K : 0;
+    }
+    b.lds = have && (long)b.w * b.h <= cap_elems;
+    return b;
+}
+
+// every position of the box read once (rows by wave, columns by lane).  FOLD false (the cubic and Lanczos kernels of the constant border,
+// whose box hugs the source): position by position, the border value outside.  FOLD true (virtual coordinates): a box inside the source --
+// most tiles -- reads it as it is; any other goes through borderInterpolate, each column's position once for all its rows (the fold's
+// integer remainder is ~20 vector instructions: evaluated per staged element it made the kernel VALU-bound at twice the cost of this form)
+template <int BORDER, bool FOLD, typename T, typename Src>
+__device__ __forceinline__ void stage_box(const Src &s, const TileBox &b, T *lds) {
+    if constexpr (!FOLD) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        for (int r = wave; r < b.h; r += 4)
+            for (int c = lane; c < b.w; c += 64) lds[r * b.w + c] = (T)s.row_col(b.x0 + c, b.y0 + r);
+    } else {
+        const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        if (b.x0 >= 0 && b.x0 + b.w <= s.w && b.y0 >= 0 && b.y0 + b.h <= s.h) {  // uniform
+            for (int r = wave; r < b.h; r += 4)
+                for (int c = lane; c < b.w; c += 64) lds[r * b.w + c] = (T)s.at(b.x0 + c, b.y0 + r);
+        } else {
+            for (int c = lane; c < b.w; c += 64) {
+                const int sx = border_index<BORDER>(b.x0 + c, s.w);
+                for (int r = wave; r < b.h; r += 4) lds[r * b.w + c] = (T)s.row_col(sx, border_index<BORDER>(b.y0 + r, s.h));
+            }
+        }
+    }
+}
+
+// K horizontally adjacent taps of the staged box, each read at its natural alignment.  BGRx dwords are 4-byte aligned whatever the tap, so
+// the compiler's ds_read2_b32 pairs are aligned too.  Luma bytes / chroma pairs: one ds_read_u8 / ds_read_u16 per tap -- volatile, because
+// the compiler otherwise merges the adjacent taps into ds_read_b32 / ds_read_b64 at a 1- or 2-byte boundary, which gfx950 executes lane by
+// lane: 64 cycles instead of 2.3 (profiles/r05_lds_access_cost.txt)
+template <int K, typename T>
+__device__ __forceinline__ void lds_row(const T *p, uint32_t *v) {
+    if constexpr (sizeof(T) < 4) {
+        typedef __attribute__((address_space(3))) T LdsT;
+        const volatile LdsT *q = (const volatile LdsT *)p;
+#pragma unroll
+        for (int c = 0; c < K; c++) v[c] = q[c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < K; c++) v[c] = p[c];
+    }
+}
+
+// Footprint rows: rows(r, v) fills v[0 .. K - 1] with the taps of footprint row r -- from the staged box, or from the source itself when the
+// box was not staged (uniform over the workgroup), each tap border-interpolated.
+template <int BORDER, int K, int LO, typename T, typename Src>
+struct TapRows {
+    const Src &s;
+    TileBox b;
+    const T *lds;
+    int X, Y;  // the tap (by value: a reference into the thread's tap array kept that array in scratch)
+    __device__ __forceinline__ void operator()(int r, uint32_t (&v)[K]) const {
+        if (b.lds) {
+            const int at = (Y - LO + r - b.y0) * b.w + (X - LO - b.x0);
+            lds_row<K>(lds + at, v);
+        } else {
+            const int sy = border_index<BORDER>(Y - LO + r, s.h);
+#pragma unroll
+            for (int c = 0; c < K; c++) v[c] = s.row_col(border_index<BORDER>(X - LO + c, s.w), sy);
+        }
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The blends' channel arithmetic: (sum + 2^14) >> 15 from the fixed-point tables (vstab_cubic.hpp, vstab_lanczos4.hpp).
+// ---------------------------------------------------------------------------------------------------------------------
+// One channel (byte CH of every tap dword) of the cubic blend: channel pairs of horizontally adjacent taps gathered into int16 pairs by
 // v_perm_b32, eight v_dot2_i32_i16 against the weight pairs.  |sum| < 16 * 32767 * 255: no overflow.
 template <int CH>
 __device__ __forceinline__ uint32_t cubic_channel(const uint32_t (&t)[16], const uint32_t (&w)[8]) {
@@ -80,7 +241,7 @@ __device__ __forceinline__ uint32_t cubic_channel(const uint32_t (&t)[16], const
     return (uint32_t)sat8(acc >> 15);
 }
 
-// One footprint row of one channel (byte CH of every tap dword): channel pairs of horizontally adjacent taps gathered into int16 pairs by
+// One footprint row of one channel of the Lanczos blend: channel pairs of horizontally adjacent taps gathered into int16 pairs by
 // v_perm_b32, four v_dot2_i32_i16 against the row's weight pairs.  |sum| over the 64 taps < 64 * 32767 * 255: no overflow.
 template <int CH>
 __device__ __forceinline__ int lz_row(int acc, const uint32_t (&t)[8], const uint4 &w) {
@@ -93,15 +254,119 @@ __device__ __forceinline__ int lz_row(int acc, const uint32_t (&t)[8], const uin
     return acc;
 }
 
-// 32 * map of output pixel (x, y): k_quantised_map's arithmetic (the fused kernels' map, bit for bit, in every mode)
-template <int MODE>
-__device__ __forceinline__ void cubic_map(const CubicArgs &c, int x, int y, float rfx, float rfy, float &ax, float &ay) {
-    const MapParams &p = c.w.p;
-    const float vy = norm_coord<MODE>((float)y - p.ocy, p.ofy, rfy);
-    const RowTerm rt = {p.r[1] * vy, p.r[4] * vy, p.r[7] * vy};
-    const float vx = norm_coord<MODE>((float)x - p.ocx, p.ofx, rfx);
-    const ColTerm ct = {p.r[0] * vx, p.r[3] * vx, p.r[6] * vx};
-    map_pixel_ex<MODE>(c.p32, p, ct, rt, vx, vy, ax, ay);
+// ---------------------------------------------------------------------------------------------------------------------
+// Cubic and Lanczos with BORDER_REPLICATE, _REFLECT or _REFLECT_101, over a resampler trait R: the footprint R::K, R::LO and
+// R::blend<CN>(rows, f), the channels 0 .. CN - 1 of the output as one byte each, from the footprint's rows and the table entry f (the
+// trait lives beside its weight table, in the resampler's unit).  The constant border's kernels keep a tile of their own there, from the
+// same pieces: only the footprints that touch the source enter their box, and a pixel whose footprint does not touch is the border value.
+// ---------------------------------------------------------------------------------------------------------------------
+// the footprint's first column / row and the one before its last: anchors for tile_box<0, 2>.  (Passing X, Y to tile_box<LO, K> is the same
+// box, but not the same code: the compiler's output for the border kernels was measured in this form and is kept to the instruction.)
+template <typename R>
+__device__ __forceinline__ void footprint_extent(const CubicTap &t, int &mnx, int &mxx, int &mny, int &mxy) {
+    mnx = min(mnx, t.X - R::LO), mxx = max(mxx, t.X - R::LO + R::K - 2);
+    mny = min(mny, t.Y - R::LO), mxy = max(mxy, t.Y - R::LO + R::K - 2);
+}
+
+// one output sample
+template <typename R, int CN, int BORDER, typename T, typename Src>
+__device__ __forceinline__ uint32_t resample_pixel(const Src &s, const TileBox &b, const T *lds, const CubicTap &t) {
+    const TapRows<BORDER, R::K, R::LO, T, Src> rows = {s, b, lds, t.X, t.Y};
+    return R::template blend<CN>(rows, t.f);
+}
+
+// The warp of one tile.  PLANAR false: BGR8 out (cvtColor then cv::remap with the resampler and border mode BORDER); PLANAR true: the
+// plane-wise warp (luma; chroma at the even pixels' positions halved, folded over the chroma plane's own size).
+// stage: RESAMPLE_LDS_BYTES, 16-byte aligned; red: 16 ints, 16-byte aligned (read back as ds_read_b96 / ds_read2_b32).
+template <typename R, int MODE, bool PLANAR, int BORDER>
+__device__ __forceinline__ void resample_tile(const CubicArgs &c, uint8_t *stage, int *red) {
+    static_assert(BORDER != VSTAB_BORDER_CONSTANT, "BORDER_CONSTANT is served by k_warp_cubic / k_warp_lanczos4");
+    const WarpArgs &a = c.w;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = blockIdx.x * RESAMPLE_TW + lane, y0 = blockIdx.y * RESAMPLE_TH + wave * RESAMPLE_RW;
+    const float rfx = rcp_refined(a.p.ofx), rfy = rcp_refined(a.p.ofy);
+    // 1. map (pixels right of / below the image are evaluated as the last column / row: never stored, inside the box)
+    CubicTap t[RESAMPLE_RW];
+    float ax[RESAMPLE_RW], ay[RESAMPLE_RW];
+#pragma unroll
+    for (int j = 0; j < RESAMPLE_RW; j++) {
+        cubic_map<MODE>(c, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
+        t[j] = cubic_tap(ax[j], ay[j]);
+    }
+    // 2. box of the luma / BGR footprints: every pixel, no "touches the source" filter
+    int mnx = INT_MAX, mxx = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
+#pragma unroll
+    for (int j = 0; j < RESAMPLE_RW; j++) footprint_extent<R>(t[j], mnx, mxx, mny, mxy);
+    if constexpr (!PLANAR) {
+        const BorderNv12Bgr<BORDER> src = {a.y, a.uv, a.pitch_y, a.pitch_uv, a.sw, a.sh};
+        uint32_t *lds = reinterpret_cast<uint32_t *>(stage);
+        const TileBox b = tile_box<0, 2, true>(mnx, mxx, mny, mxy, red, RESAMPLE_LDS_BYTES / 4);
+        // 3. stage
+        if (b.lds) stage_box<BORDER, true>(src, b, lds);
+        __syncthreads();
+        // 4. blend
+#pragma unroll
+        for (int j = 0; j < RESAMPLE_RW; j++) {
+            const int y = y0 + j;
+            if (x >= a.dw || y >= a.dh) continue;
+            const uint32_t bgr = resample_pixel<R, 3, BORDER>(src, b, (const uint32_t *)lds, t[j]);
+            uint8_t *o = a.dst + (size_t)y * a.pitch_dst + (size_t)x * 3;
+            o[0] = (uint8_t)bgr, o[1] = (uint8_t)(bgr >> 8), o[2] = (uint8_t)(bgr >> 16);
+        }
+    } else {
+        // chroma sample (x / 2, y / 2) of every even output pixel: the map halved (exact) and quantised again, over the chroma plane's size
+        const int cw = a.sw >> 1, ch = a.sh >> 1;
+        const bool cact = !(lane & 1);
+        CubicTap tc[RESAMPLE_RW / 2];
+        int cmnx = INT_MAX, cmxx = INT_MIN, cmny = INT_MAX, cmxy = INT_MIN;
+#pragma unroll
+        for (int k = 0; k < RESAMPLE_RW / 2; k++) {
+            tc[k] = cubic_tap(ax[2 * k] * 0.5f, ay[2 * k] * 0.5f);
+            if (cact) footprint_extent<R>(tc[k], cmnx, cmxx, cmny, cmxy);
+        }
+        const BorderBytes<1, BORDER> sy = {a.y, a.pitch_y, a.sw, a.sh, 0u};
+        const BorderBytes<2, BORDER> suv = {a.uv, a.pitch_uv, cw, ch, 0u};
+        uint8_t *lds_y = stage;                                                         // luma bytes: half the budget
+        uint16_t *lds_c = reinterpret_cast<uint16_t *>(stage + RESAMPLE_LDS_BYTES / 2);  // chroma pairs: the other half
+        const TileBox by = tile_box<0, 2, true>(mnx, mxx, mny, mxy, red, RESAMPLE_LDS_BYTES / 2);
+        const TileBox bc = tile_box<0, 2, true>(cmnx, cmxx, cmny, cmxy, red, RESAMPLE_LDS_BYTES / 4);
+        if (by.lds) stage_box<BORDER, true>(sy, by, lds_y);
+        if (bc.lds) stage_box<BORDER, true>(suv, bc, lds_c);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RESAMPLE_RW; j++) {
+            const int y = y0 + j;
+            if (x >= a.dw || y >= a.dh) continue;
+            a.dst[(size_t)y * a.pitch_dst + x] = (uint8_t)resample_pixel<R, 1, BORDER>(sy, by, (const uint8_t *)lds_y, t[j]);
+            if (cact && !(j & 1)) {
+                const uint32_t UV = resample_pixel<R, 2, BORDER>(suv, bc, (const uint16_t *)lds_c, tc[j / 2]);
+                uint8_t *o = a.dst_uv + (size_t)(y >> 1) * a.pitch_dst_uv + (size_t)x;  // chroma sample x / 2: bytes x, x + 1
+                o[0] = (uint8_t)UV, o[1] = (uint8_t)(UV >> 8);
+            }
+        }
+    }
+}
+
+// The stateless remap's pixel: cv::remap(resampler, BORDER) of CN interleaved 8-bit channels with float map planes (any map, NaN / huge /
+// tie entries included).  One thread per output pixel, taps from global memory.
+#define VSTAB_REMAP_PARAMS                                                                                                                             \
+    const uint8_t *__restrict__ src, size_t pitch_src, int sw, int sh, const float *__restrict__ mapx, size_t pitch_x, const float *__restrict__ mapy, \
+        size_t pitch_y
+#define VSTAB_REMAP_DST uint8_t *__restrict__ dst, size_t pitch_dst, int dw, int dh
+template <typename R, int CN, int BORDER>
+__device__ __forceinline__ void remap_pixel(VSTAB_REMAP_PARAMS, VSTAB_REMAP_DST) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= dw || y >= dh) return;
+    const float mx = reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(mapx) + (size_t)y * pitch_x)[x];
+    const float my = reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(mapy) + (size_t)y * pitch_y)[x];
+    const CubicTap t = cubic_tap(mx * 32.0f, my * 32.0f);
+    const BorderBytes<CN, BORDER> s = {src, pitch_src, sw, sh, 0u};
+    const TileBox none = {0, 0, 0, 0, false};
+    const uint32_t out = resample_pixel<R, CN, BORDER>(s, none, (const uint32_t *)nullptr, t);
+    uint8_t *o = dst + (size_t)y * pitch_dst + (size_t)x * CN;
+    o[0] = (uint8_t)out;
+    if constexpr (CN > 1) o[1] = (uint8_t)(out >> 8);
+    if constexpr (CN > 2) o[2] = (uint8_t)(out >> 16);
 }
 
 }  // namespace vstab

@@ -4,7 +4,10 @@
 // (borderInterpolate(X + i, w), borderInterpolate(Y + j, h)) -- BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 -- or, BORDER_CONSTANT,
 // the border value where it lies outside the source.
 //
-// The warp kernels (k_warp_border) follow k_warp_cubic's scheme on 64 x 16 output tiles, one workgroup of 256 threads, four rows per thread:
+// The warp kernels (k_warp_border) follow the resamplers' tile (vstab_resample.hpp) with the pieces it is made of -- the sources, the box, the
+// staging, the row read -- and a tap, a map and a blend of their own: the tap carries its computed weights and, for the constant border,
+// is clamped where it lies wholly outside; the map may take a rotation per output row.  64 x 16 output tiles, one workgroup of 256
+// threads, four rows per thread:
 //   1. map      the exact map of the thread's four pixels in registers (k_quantised_map's arithmetic for every mode; the per-row rotation of
 //               vstab_warp_nv12_rs where RS), quantised;
 //   2. box      min / max of X .. X + 1 and Y .. Y + 1 over every pixel of the tile, reduced over the workgroup, in VIRTUAL coordinates: a
@@ -14,18 +17,9 @@
 //   4. blend    4 LDS reads per pixel at their natural alignment, v_dot2_i32_i16 on channel pairs gathered by v_perm_b32.
 // A box over the LDS budget (the axis pixel of map mode 0 at -32768, strong minification) is sampled from global memory with the same
 // arithmetic; so is every pixel of the stateless remap.
-#include <climits>
-
-#include <hip/hip_ext.h>
-
-#include "vstab_border.hpp"
-#include "vstab_internal.hpp"
-#include "vstab_resample.hpp"
+#include "vstab_resample_host.hpp"
 
 namespace vstab {
-
-constexpr int BORDER_TW = 64, BORDER_TH = 16, BORDER_RW = 4;  // tile; rows per thread (4 waves x 4 rows)
-constexpr int BORDER_LDS_BYTES = 24 * 1024;                   // stage budget per workgroup, as k_warp_cubic's
 
 struct BorderArgs {
     CubicArgs c;
@@ -69,20 +63,11 @@ __device__ __forceinline__ uint32_t border_channel(uint32_t t00, uint32_t t01, u
 // The tile's phases.
 // ---------------------------------------------------------------------------------------------------------------------
 template <int BORDER, typename T, typename Src>
-__device__ __forceinline__ void border_taps(const Src &s, const BorderBox &b, const T *lds, const BorderTap &t, uint32_t (&v)[4]) {
+__device__ __forceinline__ void border_taps(const Src &s, const TileBox &b, const T *lds, const BorderTap &t, uint32_t (&v)[4]) {
     if (b.lds) {
         const int at = (t.Y - b.y0) * b.w + (t.X - b.x0);
-        if constexpr (sizeof(T) < 4) {
-            // luma bytes / chroma pairs: one ds_read_u8 / ds_read_u16 per tap, at its natural alignment.  Volatile, because the compiler
-            // otherwise merges the two taps of a row into one read at a 1- or 2-byte boundary, which gfx950 executes lane by lane
-            // (profiles/r05_lds_access_cost.txt)
-            typedef __attribute__((address_space(3))) T LdsT;
-            const volatile LdsT *q = (const volatile LdsT *)(lds + at);
-            v[0] = q[0], v[1] = q[1], v[2] = q[b.w], v[3] = q[b.w + 1];
-        } else {  // BGRx dwords: 4-byte aligned whatever the tap
-            const T *q = lds + at;
-            v[0] = q[0], v[1] = q[1], v[2] = q[b.w], v[3] = q[b.w + 1];
-        }
+        const T *q = lds + at;
+        lds_row<2>(q, v), lds_row<2>(q + b.w, v + 2);
     } else {
         const int x0 = border_index<BORDER>(t.X, s.w), x1 = border_index<BORDER>(t.X + 1, s.w);
         const int y0 = border_index<BORDER>(t.Y, s.h), y1 = border_index<BORDER>(t.Y + 1, s.h);
@@ -118,33 +103,33 @@ __device__ __forceinline__ void border_map(const BorderArgs &ba, int x, int y, f
 template <int MODE, bool PLANAR, bool RS, int BORDER>
 __global__ void __launch_bounds__(256) k_warp_border(BorderArgs ba) {
     const WarpArgs &a = ba.c.w;
-    __shared__ __attribute__((aligned(16))) uint8_t stage[BORDER_LDS_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[RESAMPLE_LDS_BYTES];
     __shared__ __attribute__((aligned(16))) int red[16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = blockIdx.x * BORDER_TW + lane, y0 = blockIdx.y * BORDER_TH + wave * BORDER_RW;
+    const int x = blockIdx.x * RESAMPLE_TW + lane, y0 = blockIdx.y * RESAMPLE_TH + wave * RESAMPLE_RW;
     const float rfx = rcp_refined(a.p.ofx), rfy = rcp_refined(a.p.ofy);
     // 1. map (pixels right of / below the image are evaluated as the last column / row: never stored, inside the box)
-    BorderTap t[BORDER_RW];
-    float ax[BORDER_RW], ay[BORDER_RW];
+    BorderTap t[RESAMPLE_RW];
+    float ax[RESAMPLE_RW], ay[RESAMPLE_RW];
 #pragma unroll
-    for (int j = 0; j < BORDER_RW; j++) {
+    for (int j = 0; j < RESAMPLE_RW; j++) {
         border_map<MODE, RS>(ba, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
         t[j] = border_tap<BORDER>(ax[j], ay[j], a.sw, a.sh);
     }
     // 2. box of the luma / BGR taps: every pixel, no "touches the source" filter
     int mnx = INT_MAX, mxx = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
 #pragma unroll
-    for (int j = 0; j < BORDER_RW; j++) mnx = min(mnx, t[j].X), mxx = max(mxx, t[j].X), mny = min(mny, t[j].Y), mxy = max(mxy, t[j].Y);
+    for (int j = 0; j < RESAMPLE_RW; j++) mnx = min(mnx, t[j].X), mxx = max(mxx, t[j].X), mny = min(mny, t[j].Y), mxy = max(mxy, t[j].Y);
     if constexpr (!PLANAR) {
         const BorderNv12Bgr<BORDER> src = {a.y, a.uv, a.pitch_y, a.pitch_uv, a.sw, a.sh};
         uint32_t *lds = reinterpret_cast<uint32_t *>(stage);
-        const BorderBox b = border_box(mnx, mxx, mny, mxy, red, BORDER_LDS_BYTES / 4);
+        const TileBox b = tile_box<0, 2, true>(mnx, mxx, mny, mxy, red, RESAMPLE_LDS_BYTES / 4);
         // 3. stage
-        if (b.lds) border_stage<BORDER>(src, b, lds);
+        if (b.lds) stage_box<BORDER, true>(src, b, lds);
         __syncthreads();
         // 4. blend
 #pragma unroll
-        for (int j = 0; j < BORDER_RW; j++) {
+        for (int j = 0; j < RESAMPLE_RW; j++) {
             const int y = y0 + j;
             if (x >= a.dw || y >= a.dh) continue;
             uint32_t v[4];
@@ -158,24 +143,24 @@ __global__ void __launch_bounds__(256) k_warp_border(BorderArgs ba) {
         // chroma sample (x / 2, y / 2) of every even output pixel: the map halved (exact) and quantised again, over the chroma plane's size
         const int cw = a.sw >> 1, ch = a.sh >> 1;
         const bool cact = !(lane & 1);
-        BorderTap tc[BORDER_RW / 2];
+        BorderTap tc[RESAMPLE_RW / 2];
         int cmnx = INT_MAX, cmxx = INT_MIN, cmny = INT_MAX, cmxy = INT_MIN;
 #pragma unroll
-        for (int k = 0; k < BORDER_RW / 2; k++) {
+        for (int k = 0; k < RESAMPLE_RW / 2; k++) {
             tc[k] = border_tap<BORDER>(ax[2 * k] * 0.5f, ay[2 * k] * 0.5f, cw, ch);
             if (cact) cmnx = min(cmnx, tc[k].X), cmxx = max(cmxx, tc[k].X), cmny = min(cmny, tc[k].Y), cmxy = max(cmxy, tc[k].Y);
         }
         const BorderBytes<1, BORDER> sy = {a.y, a.pitch_y, a.sw, a.sh, 16u};
         const BorderBytes<2, BORDER> suv = {a.uv, a.pitch_uv, cw, ch, 0x8080u};
         uint8_t *lds_y = stage;                                                      // luma bytes: half the budget
-        uint16_t *lds_c = reinterpret_cast<uint16_t *>(stage + BORDER_LDS_BYTES / 2);  // chroma pairs: the other half
-        const BorderBox by = border_box(mnx, mxx, mny, mxy, red, BORDER_LDS_BYTES / 2);
-        const BorderBox bc = border_box(cmnx, cmxx, cmny, cmxy, red, BORDER_LDS_BYTES / 4);
-        if (by.lds) border_stage<BORDER>(sy, by, lds_y);
-        if (bc.lds) border_stage<BORDER>(suv, bc, lds_c);
+        uint16_t *lds_c = reinterpret_cast<uint16_t *>(stage + RESAMPLE_LDS_BYTES / 2);  // chroma pairs: the other half
+        const TileBox by = tile_box<0, 2, true>(mnx, mxx, mny, mxy, red, RESAMPLE_LDS_BYTES / 2);
+        const TileBox bc = tile_box<0, 2, true>(cmnx, cmxx, cmny, cmxy, red, RESAMPLE_LDS_BYTES / 4);
+        if (by.lds) stage_box<BORDER, true>(sy, by, lds_y);
+        if (bc.lds) stage_box<BORDER, true>(suv, bc, lds_c);
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < BORDER_RW; j++) {
+        for (int j = 0; j < RESAMPLE_RW; j++) {
             const int y = y0 + j;
             if (x >= a.dw || y >= a.dh) continue;
             uint32_t v[4];
@@ -203,7 +188,7 @@ __global__ void __launch_bounds__(256) k_remap_border(const uint8_t *__restrict_
     const float my = reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(mapy) + (size_t)y * pitch_y)[x];
     const BorderTap t = border_tap<BORDER>(mx * 32.0f, my * 32.0f, sw, sh);
     const BorderBytes<CN, BORDER> s = {src, pitch_src, sw, sh, 0u};
-    const BorderBox none = {0, 0, 0, 0, false};
+    const TileBox none = {0, 0, 0, 0, false};
     uint32_t v[4];
     border_taps<BORDER>(s, none, (const uint32_t *)nullptr, t, v);
     uint8_t *o = dst + (size_t)y * pitch_dst + (size_t)x * CN;
@@ -219,45 +204,6 @@ vstab_status preload_border_kernels() {
     return VSTAB_OK;
 }
 
-template <int MODE, bool PLANAR, bool RS, int BORDER>
-static void launch_warp_border(const BorderArgs &ba, dim3 grid, const LaunchEvents &ev, hipStream_t st) {
-    auto kernel = k_warp_border<MODE, PLANAR, RS, BORDER>;
-    if (ev.start) hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ev.start, ev.stop, 0, ba);
-    else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ba);
-}
-
-template <bool PLANAR, bool RS, int BORDER>
-static void launch_warp_border_mode(const BorderArgs &ba, int map_mode, dim3 grid, const LaunchEvents &ev, hipStream_t st) {
-    if constexpr (RS) {  // modes 0 / 1 / 5 (checked by the caller)
-        switch (map_mode) {
-            case VSTAB_MAP_CREATEMAP_CL: launch_warp_border<MAP_CREATEMAP_CL, PLANAR, true, BORDER>(ba, grid, ev, st); break;
-            case VSTAB_MAP_FISH_TO_RECT: launch_warp_border<MAP_FISH_TO_RECT, PLANAR, true, BORDER>(ba, grid, ev, st); break;
-            default: launch_warp_border<MAP_CREATEMAP_CL_OPENCL, PLANAR, true, BORDER>(ba, grid, ev, st); break;
-        }
-    } else {
-        switch (map_mode) {
-            case VSTAB_MAP_CREATEMAP_CL: launch_warp_border<MAP_CREATEMAP_CL, PLANAR, false, BORDER>(ba, grid, ev, st); break;
-            case VSTAB_MAP_FISH_TO_RECT: launch_warp_border<MAP_FISH_TO_RECT, PLANAR, false, BORDER>(ba, grid, ev, st); break;
-            case VSTAB_MAP_FISH_TO_FISH: launch_warp_border<MAP_FISH_TO_FISH, PLANAR, false, BORDER>(ba, grid, ev, st); break;
-            case VSTAB_MAP_RECT_TO_RECT: launch_warp_border<MAP_RECT_TO_RECT, PLANAR, false, BORDER>(ba, grid, ev, st); break;
-            case VSTAB_MAP_RECT_TO_FISH: launch_warp_border<MAP_RECT_TO_FISH, PLANAR, false, BORDER>(ba, grid, ev, st); break;
-            default: launch_warp_border<MAP_CREATEMAP_CL_OPENCL, PLANAR, false, BORDER>(ba, grid, ev, st); break;
-        }
-    }
-}
-
-template <bool PLANAR, bool RS>
-static void launch_warp_border_any(const BorderArgs &ba, int map_mode, int border_mode, dim3 grid, const LaunchEvents &ev, hipStream_t st) {
-    switch (border_mode) {
-        case VSTAB_BORDER_CONSTANT: launch_warp_border_mode<PLANAR, RS, VSTAB_BORDER_CONSTANT>(ba, map_mode, grid, ev, st); break;
-        case VSTAB_BORDER_REPLICATE: launch_warp_border_mode<PLANAR, RS, VSTAB_BORDER_REPLICATE>(ba, map_mode, grid, ev, st); break;
-        case VSTAB_BORDER_REFLECT: launch_warp_border_mode<PLANAR, RS, VSTAB_BORDER_REFLECT>(ba, map_mode, grid, ev, st); break;
-        default: launch_warp_border_mode<PLANAR, RS, VSTAB_BORDER_REFLECT_101>(ba, map_mode, grid, ev, st); break;
-    }
-}
-
-static inline bool border_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace vstab
 
 using namespace vstab;
@@ -267,33 +213,18 @@ extern "C" {
 vstab_status vstab_remap_bilinear_border(const void *src, size_t pitch_src, int sw, int sh, int channels, const void *map_x, size_t pitch_x,
                                          const void *map_y, size_t pitch_y, int border_mode, void *dst, size_t pitch_dst, int dw, int dh,
                                          void *stream) {
-    if (!src || !map_x || !map_y || !dst) return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: null pointer");
-    if (channels < 1 || channels > 3) return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: channels must be 1, 2 or 3");
-    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || sw > 32767 || sh > 32767 || dw > 32767 || dh > 32767)
-        return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: sizes must be in [1, 32767]");
-    if (pitch_src < (size_t)sw * channels || pitch_dst < (size_t)dw * channels || pitch_x < (size_t)dw * 4 || pitch_y < (size_t)dw * 4 || pitch_x % 4 ||
-        pitch_y % 4 || !border_aligned(map_x, 4) || !border_aligned(map_y, 4))
-        return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: pitch smaller than a row, or map planes not 4-byte aligned");
-    if (!border_mode_valid(border_mode))
-        return fail(VSTAB_ERR_INVALID, "vstab_remap_bilinear_border: border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or "
-                                       "_REFLECT_101 (4)");
+    uint32_t none;
+    const vstab_status st = check_remap("vstab_remap_bilinear_border", src, pitch_src, sw, sh, channels, map_x, pitch_x, map_y, pitch_y, &border_mode, false,
+                                        nullptr, dst, pitch_dst, dw, dh, none);
+    if (st != VSTAB_OK) return st;
     const dim3 grid(div_up(dw, 64), div_up(dh, 4));
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define VSTAB_LAUNCH(CN, B)                                                                                                                 \
-    hipLaunchKernelGGL((k_remap_border<CN, B>), grid, dim3(256), 0, s, (const uint8_t *)src, pitch_src, sw, sh, (const float *)map_x, pitch_x, \
-                       (const float *)map_y, pitch_y, (uint8_t *)dst, pitch_dst, dw, dh)
-#define VSTAB_BORDERS(CN)                                                                       \
-    switch (border_mode) {                                                                      \
-        case VSTAB_BORDER_CONSTANT: VSTAB_LAUNCH(CN, VSTAB_BORDER_CONSTANT); break;             \
-        case VSTAB_BORDER_REPLICATE: VSTAB_LAUNCH(CN, VSTAB_BORDER_REPLICATE); break;           \
-        case VSTAB_BORDER_REFLECT: VSTAB_LAUNCH(CN, VSTAB_BORDER_REFLECT); break;               \
-        default: VSTAB_LAUNCH(CN, VSTAB_BORDER_REFLECT_101); break;                             \
-    }
-    if (channels == 1) VSTAB_BORDERS(1)
-    else if (channels == 2) VSTAB_BORDERS(2)
-    else VSTAB_BORDERS(3)
-#undef VSTAB_BORDERS
-#undef VSTAB_LAUNCH
+    with_channels(channels, [&](auto cn) {
+        with_border_mode(border_mode, [&](auto border) {
+            hipLaunchKernelGGL((k_remap_border<decltype(cn)::value, decltype(border)::value>), grid, dim3(256), 0, s, (const uint8_t *)src, pitch_src, sw, sh,
+                               (const float *)map_x, pitch_x, (const float *)map_y, pitch_y, (uint8_t *)dst, pitch_dst, dw, dh);
+        });
+    });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }
@@ -301,46 +232,24 @@ vstab_status vstab_remap_bilinear_border(const void *src, size_t pitch_src, int 
 vstab_status vstab_warp_nv12_border(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                     const float *rot_bottom, int map_mode, int out_format, int border_mode, void *dst, size_t pitch_dst, void *dst_uv,
                                     size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: null pointer");
-    if (sw <= 0 || sh <= 0 || (sw & 1) || (sh & 1) || sw > 32767 || sh > 32767)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: source must be even-sized and <= 32767");
-    if (dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: output size must be in [1, 32767]");
-    if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: unknown map mode");
-    if (rot_bottom && map_mode != VSTAB_MAP_CREATEMAP_CL && map_mode != VSTAB_MAP_FISH_TO_RECT && map_mode != VSTAB_MAP_CREATEMAP_CL_OPENCL)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: a rotation per output row (rot_bottom) is served for map modes 0, 1 and 5");
-    if (out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12_PLANAR)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: the border warp emits VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR (NV12 through BGR is not served)");
-    if (!border_mode_valid(border_mode))
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or "
-                                       "_REFLECT_101 (4)");
-    const bool planar = out_format == VSTAB_OUT_NV12_PLANAR;
-    if (pitch_y < (size_t)sw || pitch_uv < (size_t)sw || pitch_dst < (size_t)dw * (planar ? 1 : 3))
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: pitch smaller than row");
-    if (planar && (!dst_uv || pitch_dst_uv < (size_t)((dw + 1) / 2) * 2))
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: plane-wise output needs a chroma plane of 2*ceil(width/2) bytes per row");
-    if (!border_aligned(uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_border: chroma plane must be 2-B aligned");
     BorderArgs ba;
-    WarpArgs &a = ba.c.w;
-    a.y = (const uint8_t *)y, a.uv = (const uint8_t *)uv, a.dst = (uint8_t *)dst, a.dst_uv = planar ? (uint8_t *)dst_uv : nullptr;
-    a.pitch_y = pitch_y, a.pitch_uv = pitch_uv, a.pitch_dst = pitch_dst, a.pitch_dst_uv = planar ? pitch_dst_uv : 0;
-    a.sw = sw, a.sh = sh, a.dw = dw, a.dh = dh;
-    MapParams &p = a.p;
-    p.icx = params[0], p.icy = params[1], p.ifx = params[2], p.ify = params[3];
-    p.ocx = params[4], p.ocy = params[5], p.ofx = params[6], p.ofy = params[7];
-    for (int i = 0; i < 9; i++) p.r[i] = params[8 + i];
-    ba.c.p32 = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
+    const vstab_status st = check_warp_nv12("vstab_warp_nv12_border", "the border warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode,
+                                            out_format, &border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, ba.c);
+    if (st != VSTAB_OK) return st;
     for (int k = 0; k < 9; k++) ba.rs_d[k] = rot_bottom ? rot_bottom[k] - params[8 + k] : 0.0f;  // fp32, as the definition forms it
     ba.rs_den = (float)(dh > 1 ? dh - 1 : 1);
-    const dim3 grid(div_up(dw, BORDER_TW), div_up(dh, BORDER_TH));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LaunchEvents ev = take_launch_events();  // a profiling caller's pair: the kernel's own start / end stamps
-    if (planar) {
-        if (rot_bottom) launch_warp_border_any<true, true>(ba, map_mode, border_mode, grid, ev, st);
-        else launch_warp_border_any<true, false>(ba, map_mode, border_mode, grid, ev, st);
-    } else {
-        if (rot_bottom) launch_warp_border_any<false, true>(ba, map_mode, border_mode, grid, ev, st);
-        else launch_warp_border_any<false, false>(ba, map_mode, border_mode, grid, ev, st);
-    }
+    with_map_mode(map_mode, [&](auto mode) {
+        with_border_mode(border_mode, [&](auto border) {
+            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
+                with_bool(rot_bottom != nullptr, [&](auto rs) {
+                    constexpr int MODE = decltype(mode)::value;
+                    // the rotation per output row is served (and checked above) for map modes 0, 1 and 5 only
+                    if constexpr (!decltype(rs)::value || MODE == MAP_CREATEMAP_CL || MODE == MAP_FISH_TO_RECT || MODE == MAP_CREATEMAP_CL_OPENCL)
+                        launch_tiles(k_warp_border<MODE, decltype(planar)::value, decltype(rs)::value, decltype(border)::value>, ba, dw, dh, stream);
+                });
+            });
+        });
+    });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }

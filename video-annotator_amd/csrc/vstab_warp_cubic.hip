@@ -1,145 +1,109 @@
-// vstab_warp_cubic.hip -- cv::remap's INTER_CUBIC for gfx950: the fused NV12 -> BGR8 warp, the plane-wise NV12 -> NV12 warp and the
-// stateless remap of map planes.  Definition (include/vstab.h, vstab_warp_nv12_cubic; tests/cubic_def.py): the map quantised to 1/32 pixel
-// as for INTER_LINEAR, a 4 x 4 footprint at (X - 1 .. X + 2, Y - 1 .. Y + 2), 16 integer weights from OpenCV's fixed-point table
-// (vstab_cubic.hpp), border value substituted for each tap outside the source, (sum + 2^14) >> 15 saturated to 0..255.
+// vstab_warp_cubic.hip -- cv::remap's INTER_CUBIC for gfx950, with every border mode: the fused NV12 -> BGR8 warp, the plane-wise
+// NV12 -> NV12 warp and the stateless remap of map planes.  Definition (include/vstab.h, vstab_warp_nv12_cubic and "Border modes of the cubic
+// and Lanczos resamplers"; tests/cubic_def.py, tests/resample_border_def.py): the map quantised to 1/32 pixel as for INTER_LINEAR, a 4 x 4
+// footprint at (X - 1 .. X + 2, Y - 1 .. Y + 2), 16 integer weights from OpenCV's fixed-point table (vstab_cubic.hpp), each tap outside the
+// source the border value (BORDER_CONSTANT) or read at its borderInterpolate position, (sum + 2^14) >> 15 saturated to 0..255.
 //
-// The warp kernels (k_warp_cubic) work on 64 x 16 output tiles, one workgroup of 256 threads each, four rows per thread:
-//   1. map      the exact map of the thread's four pixels in registers (k_quantised_map's arithmetic for every mode), quantised;
-//   2. box      the tile's source box: min / max of the footprints that touch the source, reduced over the workgroup -- exact, not probed;
-//   3. stage    the box read into LDS once per source pixel, converted (BGRx dwords; luma bytes / chroma pairs in the plane-wise
-//               kernel), the border value in every position outside the source;
-//   4. blend    16 LDS reads per pixel, each at its natural alignment (ds_read2_b32 pairs of BGRx dwords; one ds_read_u8 per luma
-//               tap, one ds_read_u16 per chroma pair), weights from the table (two 16-byte loads, cache-resident), v_dot2_i32_i16 on
-//               channel pairs gathered by v_perm_b32.
-// A box over the LDS budget (strong minification, degenerate rotations) is sampled from global memory instead; so is every pixel of the
-// stateless remap.  The map is never written to memory.
-#include <climits>
-
-#include <hip/hip_ext.h>
-
+// The tile's phases, the remap and the entry points are the resamplers' common ones (vstab_resample.hpp, vstab_resample_host.hpp).  This
+// unit holds the cubic table, the cubic blend, the constant border's tile (k_warp_cubic) and the kernels under their names.
 #include "vstab_cubic.hpp"
-#include "vstab_internal.hpp"
-#include "vstab_resample.hpp"
+#include "vstab_resample_host.hpp"
 
 namespace vstab {
 
 __device__ const CubicTable g_cubic = make_cubic_table();  // in the code object's read-only data: loaded with the kernels
 
-constexpr int CUBIC_TW = 64, CUBIC_TH = 16, CUBIC_RW = 4;  // tile; rows per thread (4 waves x 4 rows)
-constexpr int CUBIC_LDS_BYTES = 24 * 1024;                 // stage budget per workgroup: six workgroups per CU by LDS
-
-// some tap of the footprint inside a w x h source
-__device__ __forceinline__ bool cubic_touches(const CubicTap &t, int w, int h) { return t.X + 2 >= 0 && t.X - 1 < w && t.Y + 2 >= 0 && t.Y - 1 < h; }
-
-// the 16 weights of an entry as 8 packed int16 pairs: pair 2 r + h = row r, columns 2 h (low half) and 2 h + 1
+// the 16 weights of an entry as 8 packed int16 pairs (two 16-byte loads, cache-resident): pair 2 r + h = row r, columns 2 h (low half) and
+// 2 h + 1
 __device__ __forceinline__ void cubic_weights(int f, uint32_t (&w)[8]) {
     const uint4 *p = reinterpret_cast<const uint4 *>(g_cubic.w) + 2 * f;
     const uint4 a = p[0], b = p[1];
     w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The tile's phases.
-// ---------------------------------------------------------------------------------------------------------------------
-struct CubicBox {
-    int x0, y0, w, h;
-    bool lds;  // staged (uniform over the workgroup)
-};
-
-// min / max of the tap columns and rows over the footprints a thread passes in (any that touch the source), reduced over the workgroup
-// through red[16] in LDS.  The box covers X - 1 .. X + 2 of all of them; it lies inside [-3, w + 2] x [-3, h + 2].
-__device__ __forceinline__ CubicBox cubic_box(int mnx, int mxx, int mny, int mxy, int *red, int cap_elems) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        mnx = min(mnx, __shfl_xor(mnx, m)), mxx = max(mxx, __shfl_xor(mxx, m));
-        mny = min(mny, __shfl_xor(mny, m)), mxy = max(mxy, __shfl_xor(mxy, m));
-    }
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();  // red[] may still be read by a previous box
-    if ((threadIdx.x & 63) == 0) red[4 * wave] = mnx, red[4 * wave + 1] = mxx, red[4 * wave + 2] = mny, red[4 * wave + 3] = mxy;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; k++) mnx = min(mnx, red[4 * k]), mxx = max(mxx, red[4 * k + 1]), mny = min(mny, red[4 * k + 2]), mxy = max(mxy, red[4 * k + 3]);
-    const bool have = mnx <= mxx;  // else no footprint of the tile touches the source
-    CubicBox b;
-    b.x0 = mnx - 1, b.y0 = mny - 1, b.w = have ? mxx - mnx + 4 : 0, b.h = have ? mxy - mny + 4 : 0;
-    b.lds = have && (long)b.w * b.h <= cap_elems;
-    return b;
-}
-
+// the constant border's 16 taps: from the staged box (16 LDS reads), or from the source itself when the box was not staged
 template <typename T, typename Src>
-__device__ __forceinline__ void cubic_stage(const Src &s, const CubicBox &b, T *lds) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int r = wave; r < b.h; r += 4)
-        for (int c = lane; c < b.w; c += 64) lds[r * b.w + c] = (T)s(b.x0 + c, b.y0 + r);
-}
-
-template <typename T, typename Src>
-__device__ __forceinline__ void cubic_taps(const Src &s, const CubicBox &b, const T *lds, const CubicTap &t, uint32_t (&v)[16]) {
+__device__ __forceinline__ void cubic_taps(const Src &s, const TileBox &b, const T *lds, const CubicTap &t, uint32_t (&v)[16]) {
     if (b.lds) {
         const int at = (t.Y - 1 - b.y0) * b.w + (t.X - 1 - b.x0);
-        if constexpr (sizeof(T) < 4) {
-            // luma bytes / chroma pairs: one ds_read_u8 / ds_read_u16 per tap, at its natural alignment.  Volatile, because the compiler
-            // otherwise merges the adjacent taps of a row into ds_read_b32 / ds_read_b64 at a 1- or 2-byte boundary, which gfx950 executes
-            // lane by lane: 64 cycles instead of 2.3 (profiles/r05_lds_access_cost.txt)
-            typedef __attribute__((address_space(3))) T LdsT;
-            const volatile LdsT *q = (const volatile LdsT *)(lds + at);
+        const T *q = lds + at;
 #pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-                for (int c = 0; c < 4; c++) v[4 * r + c] = q[r * b.w + c];
-        } else {  // BGRx dwords: 4-byte aligned whatever the tap, so the compiler's ds_read2_b32 pairs are aligned too
-            const T *q = lds + at;
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#pragma unroll
-                for (int c = 0; c < 4; c++) v[4 * r + c] = q[r * b.w + c];
-        }
+        for (int r = 0; r < 4; r++) lds_row<4>(q + r * b.w, v + 4 * r);
     } else {
 #pragma unroll
         for (int r = 0; r < 4; r++)
 #pragma unroll
-            for (int c = 0; c < 4; c++) v[4 * r + c] = s(t.X - 1 + c, t.Y - 1 + r);
+            for (int c = 0; c < 4; c++) v[4 * r + c] = s.row_col(t.X - 1 + c, t.Y - 1 + r);
     }
 }
 
+struct Cubic {
+    static constexpr int K = 4, LO = 1;
+    // some tap of the footprint inside a w x h source
+    __device__ __forceinline__ static bool touches(const CubicTap &t, int w, int h) { return t.X + 2 >= 0 && t.X - 1 < w && t.Y + 2 >= 0 && t.Y - 1 < h; }
+    // all 16 taps, then channel by channel
+    template <int CN, typename Rows>
+    __device__ __forceinline__ static uint32_t blend(const Rows &rows, int f) {
+        uint32_t w[8], v[16];
+        cubic_weights(f, w);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            uint32_t row[4];
+            rows(r, row);
+#pragma unroll
+            for (int c = 0; c < 4; c++) v[4 * r + c] = row[c];
+        }
+        return channels<CN>(v, w);
+    }
+    template <int CN>
+    __device__ __forceinline__ static uint32_t channels(const uint32_t (&v)[16], const uint32_t (&w)[8]) {
+        uint32_t out = cubic_channel<0>(v, w);
+        if constexpr (CN > 1) out |= cubic_channel<1>(v, w) << 8;
+        if constexpr (CN > 2) out |= cubic_channel<2>(v, w) << 16;
+        return out;
+    }
+};
+
 // k_warp_cubic -- NV12 in; PLANAR false: BGR8 out (cvtColor then cv::remap INTER_CUBIC, border 0); PLANAR true: the plane-wise warp
 // (luma border 16; chroma at the even pixels' positions halved, border (128, 128)).
+// The tile's phases (vstab_resample.hpp) with what the constant border alone has: only footprints that touch the source enter the box, a
+// tile with none has no box, a pixel whose footprint does not touch is the border value.  Kept apart from resample_tile because through it
+// and the trait's row functor the compiler's instruction counts for these kernels rose ("After the consolidation").
 template <int MODE, bool PLANAR>
 __global__ void __launch_bounds__(256) k_warp_cubic(CubicArgs c) {
     const WarpArgs &a = c.w;
-    __shared__ __attribute__((aligned(16))) uint8_t stage[CUBIC_LDS_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[RESAMPLE_LDS_BYTES];
     __shared__ __attribute__((aligned(16))) int red[16];  // read back as ds_read_b96 / ds_read2_b32: 16-byte aligned
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = blockIdx.x * CUBIC_TW + lane, y0 = blockIdx.y * CUBIC_TH + wave * CUBIC_RW;
+    const int x = blockIdx.x * RESAMPLE_TW + lane, y0 = blockIdx.y * RESAMPLE_TH + wave * RESAMPLE_RW;
     const float rfx = rcp_refined(a.p.ofx), rfy = rcp_refined(a.p.ofy);
     // 1. map (pixels right of / below the image are evaluated as the last column / row: never stored, inside the box)
-    CubicTap t[CUBIC_RW], tc[CUBIC_RW / 2];
-    float ax[CUBIC_RW], ay[CUBIC_RW];
+    CubicTap t[RESAMPLE_RW], tc[RESAMPLE_RW / 2];
+    float ax[RESAMPLE_RW], ay[RESAMPLE_RW];
 #pragma unroll
-    for (int j = 0; j < CUBIC_RW; j++) {
+    for (int j = 0; j < RESAMPLE_RW; j++) {
         cubic_map<MODE>(c, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
         t[j] = cubic_tap(ax[j], ay[j]);
     }
     // 2. box of the luma / BGR taps
     int mnx = INT_MAX, mxx = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
 #pragma unroll
-    for (int j = 0; j < CUBIC_RW; j++)
-        if (cubic_touches(t[j], a.sw, a.sh)) mnx = min(mnx, t[j].X), mxx = max(mxx, t[j].X), mny = min(mny, t[j].Y), mxy = max(mxy, t[j].Y);
+    for (int j = 0; j < RESAMPLE_RW; j++)
+        if (Cubic::touches(t[j], a.sw, a.sh)) mnx = min(mnx, t[j].X), mxx = max(mxx, t[j].X), mny = min(mny, t[j].Y), mxy = max(mxy, t[j].Y);
     if constexpr (!PLANAR) {
-        const SrcNv12Bgr src = {a.y, a.uv, a.pitch_y, a.pitch_uv, a.sw, a.sh};
+        const BorderNv12Bgr<VSTAB_BORDER_CONSTANT> src = {a.y, a.uv, a.pitch_y, a.pitch_uv, a.sw, a.sh};
         uint32_t *lds = reinterpret_cast<uint32_t *>(stage);
-        const CubicBox b = cubic_box(mnx, mxx, mny, mxy, red, CUBIC_LDS_BYTES / 4);
+        const TileBox b = tile_box<1, 4, false>(mnx, mxx, mny, mxy, red, RESAMPLE_LDS_BYTES / 4);
         // 3. stage
-        if (b.lds) cubic_stage(src, b, lds);
+        if (b.lds) stage_box<VSTAB_BORDER_CONSTANT, false>(src, b, lds);
         __syncthreads();
         // 4. blend
 #pragma unroll
-        for (int j = 0; j < CUBIC_RW; j++) {
+        for (int j = 0; j < RESAMPLE_RW; j++) {
             const int y = y0 + j;
             if (x >= a.dw || y >= a.dh) continue;
             uint32_t B = 0, G = 0, R = 0;
-            if (cubic_touches(t[j], a.sw, a.sh)) {
+            if (Cubic::touches(t[j], a.sw, a.sh)) {
                 uint32_t v[16], w[8];
                 cubic_weights(t[j].f, w);
                 cubic_taps(src, b, lds, t[j], v);
@@ -154,26 +118,26 @@ __global__ void __launch_bounds__(256) k_warp_cubic(CubicArgs c) {
         const bool cact = !(lane & 1);
         int cmnx = INT_MAX, cmxx = INT_MIN, cmny = INT_MAX, cmxy = INT_MIN;
 #pragma unroll
-        for (int k = 0; k < CUBIC_RW / 2; k++) {
+        for (int k = 0; k < RESAMPLE_RW / 2; k++) {
             tc[k] = cubic_tap(ax[2 * k] * 0.5f, ay[2 * k] * 0.5f);
-            if (cact && cubic_touches(tc[k], cw, ch))
+            if (cact && Cubic::touches(tc[k], cw, ch))
                 cmnx = min(cmnx, tc[k].X), cmxx = max(cmxx, tc[k].X), cmny = min(cmny, tc[k].Y), cmxy = max(cmxy, tc[k].Y);
         }
-        const SrcBytes<1> sy = {a.y, a.pitch_y, a.sw, a.sh, 16u};
-        const SrcBytes<2> suv = {a.uv, a.pitch_uv, cw, ch, 0x8080u};
+        const BorderBytes<1, VSTAB_BORDER_CONSTANT> sy = {a.y, a.pitch_y, a.sw, a.sh, 16u};
+        const BorderBytes<2, VSTAB_BORDER_CONSTANT> suv = {a.uv, a.pitch_uv, cw, ch, 0x8080u};
         uint8_t *lds_y = stage;                                                     // luma bytes: half the budget
-        uint16_t *lds_c = reinterpret_cast<uint16_t *>(stage + CUBIC_LDS_BYTES / 2);  // chroma pairs: the other half
-        const CubicBox by = cubic_box(mnx, mxx, mny, mxy, red, CUBIC_LDS_BYTES / 2);
-        const CubicBox bc = cubic_box(cmnx, cmxx, cmny, cmxy, red, CUBIC_LDS_BYTES / 4);
-        if (by.lds) cubic_stage(sy, by, lds_y);
-        if (bc.lds) cubic_stage(suv, bc, lds_c);
+        uint16_t *lds_c = reinterpret_cast<uint16_t *>(stage + RESAMPLE_LDS_BYTES / 2);  // chroma pairs: the other half
+        const TileBox by = tile_box<1, 4, false>(mnx, mxx, mny, mxy, red, RESAMPLE_LDS_BYTES / 2);
+        const TileBox bc = tile_box<1, 4, false>(cmnx, cmxx, cmny, cmxy, red, RESAMPLE_LDS_BYTES / 4);
+        if (by.lds) stage_box<VSTAB_BORDER_CONSTANT, false>(sy, by, lds_y);
+        if (bc.lds) stage_box<VSTAB_BORDER_CONSTANT, false>(suv, bc, lds_c);
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < CUBIC_RW; j++) {
+        for (int j = 0; j < RESAMPLE_RW; j++) {
             const int y = y0 + j;
             if (x >= a.dw || y >= a.dh) continue;
             uint32_t Y = 16;
-            if (cubic_touches(t[j], a.sw, a.sh)) {
+            if (Cubic::touches(t[j], a.sw, a.sh)) {
                 uint32_t v[16], w[8];
                 cubic_weights(t[j].f, w);
                 cubic_taps(sy, by, lds_y, t[j], v);
@@ -183,7 +147,7 @@ __global__ void __launch_bounds__(256) k_warp_cubic(CubicArgs c) {
             if (cact && !(j & 1)) {
                 const CubicTap &q = tc[j / 2];
                 uint32_t U = 128, V = 128;
-                if (cubic_touches(q, cw, ch)) {
+                if (Cubic::touches(q, cw, ch)) {
                     uint32_t v[16], w[8];
                     cubic_weights(q.f, w);
                     cubic_taps(suv, bc, lds_c, q, v);
@@ -196,33 +160,52 @@ __global__ void __launch_bounds__(256) k_warp_cubic(CubicArgs c) {
     }
 }
 
-// k_remap_cubic -- cv::remap(INTER_CUBIC, BORDER_CONSTANT border) of CN interleaved 8-bit channels with float map planes: the
-// stateless building block (any map, NaN / huge / tie entries included).  One thread per output pixel, taps from global memory.
+// k_warp_cubic_border -- the warp with border mode BORDER (REPLICATE, REFLECT, REFLECT_101); k_remap_cubic / k_remap_cubic_border -- the
+// stateless remap, constant border (value border) / border mode BORDER
+template <int MODE, bool PLANAR, int BORDER>
+__global__ void __launch_bounds__(256) k_warp_cubic_border(CubicArgs c) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[RESAMPLE_LDS_BYTES];
+    __shared__ __attribute__((aligned(16))) int red[16];
+    resample_tile<Cubic, MODE, PLANAR, BORDER>(c, stage, red);
+}
 template <int CN>
-__global__ void __launch_bounds__(256) k_remap_cubic(const uint8_t *__restrict__ src, size_t pitch_src, int sw, int sh, const float *__restrict__ mapx,
-                                                     size_t pitch_x, const float *__restrict__ mapy, size_t pitch_y, uint32_t border,
-                                                     uint8_t *__restrict__ dst, size_t pitch_dst, int dw, int dh) {
+__global__ void __launch_bounds__(256) k_remap_cubic(VSTAB_REMAP_PARAMS, uint32_t border, VSTAB_REMAP_DST) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= dw || y >= dh) return;
     const float mx = reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(mapx) + (size_t)y * pitch_x)[x];
     const float my = reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(mapy) + (size_t)y * pitch_y)[x];
     const CubicTap t = cubic_tap(mx * 32.0f, my * 32.0f);
     uint32_t out = border;
-    if (cubic_touches(t, sw, sh)) {
-        const SrcBytes<CN> s = {src, pitch_src, sw, sh, border};
-        const CubicBox none = {0, 0, 0, 0, false};
+    if (Cubic::touches(t, sw, sh)) {
+        const BorderBytes<CN, VSTAB_BORDER_CONSTANT> s = {src, pitch_src, sw, sh, border};
+        const TileBox none = {0, 0, 0, 0, false};
         uint32_t v[16], w[8];
         cubic_weights(t.f, w);
         cubic_taps(s, none, (const uint32_t *)nullptr, t, v);
-        out = cubic_channel<0>(v, w);
-        if constexpr (CN > 1) out |= cubic_channel<1>(v, w) << 8;
-        if constexpr (CN > 2) out |= cubic_channel<2>(v, w) << 16;
+        out = Cubic::channels<CN>(v, w);
     }
     uint8_t *o = dst + (size_t)y * pitch_dst + (size_t)x * CN;
     o[0] = (uint8_t)out;
     if constexpr (CN > 1) o[1] = (uint8_t)(out >> 8);
     if constexpr (CN > 2) o[2] = (uint8_t)(out >> 16);
 }
+template <int CN, int BORDER>
+__global__ void __launch_bounds__(256) k_remap_cubic_border(VSTAB_REMAP_PARAMS, VSTAB_REMAP_DST) {
+    remap_pixel<Cubic, CN, BORDER>(src, pitch_src, sw, sh, mapx, pitch_x, mapy, pitch_y, dst, pitch_dst, dw, dh);
+}
+
+struct CubicKernels {
+    template <int MODE, bool PLANAR, int BORDER>
+    static auto warp() {
+        if constexpr (BORDER == VSTAB_BORDER_CONSTANT) return k_warp_cubic<MODE, PLANAR>;
+        else return k_warp_cubic_border<MODE, PLANAR, BORDER>;
+    }
+    template <int CN, int BORDER>
+    static auto remap() {
+        if constexpr (BORDER == VSTAB_BORDER_CONSTANT) return k_remap_cubic<CN>;
+        else return k_remap_cubic_border<CN, BORDER>;
+    }
+};
 
 // Kernels of this translation unit (and the weight table with them) are one code object: see preload_warp_kernels
 vstab_status preload_cubic_kernels() {
@@ -230,15 +213,6 @@ vstab_status preload_cubic_kernels() {
     VSTAB_HIP_TRY(hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_remap_cubic<1>)));
     return VSTAB_OK;
 }
-
-template <int MODE, bool PLANAR>
-static void launch_warp_cubic(const CubicArgs &c, dim3 grid, const LaunchEvents &ev, hipStream_t st) {
-    auto kernel = k_warp_cubic<MODE, PLANAR>;
-    if (ev.start) hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ev.start, ev.stop, 0, c);
-    else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, c);
-}
-
-static inline bool cubic_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 }  // namespace vstab
 
@@ -255,73 +229,28 @@ vstab_status vstab_cubic_weights(int16_t *out) {
 
 vstab_status vstab_remap_cubic(const void *src, size_t pitch_src, int sw, int sh, int channels, const void *map_x, size_t pitch_x, const void *map_y,
                                size_t pitch_y, const int border[3], void *dst, size_t pitch_dst, int dw, int dh, void *stream) {
-    if (!src || !map_x || !map_y || !dst || !border) return fail(VSTAB_ERR_INVALID, "vstab_remap_cubic: null pointer");
-    if (channels < 1 || channels > 3) return fail(VSTAB_ERR_INVALID, "vstab_remap_cubic: channels must be 1, 2 or 3");
-    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || sw > 32767 || sh > 32767 || dw > 32767 || dh > 32767)
-        return fail(VSTAB_ERR_INVALID, "vstab_remap_cubic: sizes must be in [1, 32767]");
-    if (pitch_src < (size_t)sw * channels || pitch_dst < (size_t)dw * channels || pitch_x < (size_t)dw * 4 || pitch_y < (size_t)dw * 4 || pitch_x % 4 ||
-        pitch_y % 4 || !cubic_aligned(map_x, 4) || !cubic_aligned(map_y, 4))
-        return fail(VSTAB_ERR_INVALID, "vstab_remap_cubic: pitch smaller than a row, or map planes not 4-byte aligned");
-    uint32_t b = 0;
-    for (int k = 0; k < channels; k++) {
-        if (border[k] < 0 || border[k] > 255) return fail(VSTAB_ERR_INVALID, "vstab_remap_cubic: border values must be in [0, 255]");
-        b |= (uint32_t)border[k] << (8 * k);
-    }
-    const dim3 grid(div_up(dw, 64), div_up(dh, 4));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define VSTAB_LAUNCH(CN)                                                                                                                   \
-    hipLaunchKernelGGL(k_remap_cubic<CN>, grid, dim3(256), 0, s, (const uint8_t *)src, pitch_src, sw, sh, (const float *)map_x, pitch_x, \
-                       (const float *)map_y, pitch_y, b, (uint8_t *)dst, pitch_dst, dw, dh)
-    if (channels == 1) VSTAB_LAUNCH(1);
-    else if (channels == 2) VSTAB_LAUNCH(2);
-    else VSTAB_LAUNCH(3);
-#undef VSTAB_LAUNCH
-    VSTAB_HIP_TRY(hipGetLastError());
-    return VSTAB_OK;
+    return remap_resample<CubicKernels>("vstab_remap_cubic", src, pitch_src, sw, sh, channels, map_x, pitch_x, map_y, pitch_y, nullptr, border, dst,
+                                        pitch_dst, dw, dh, stream);
+}
+
+vstab_status vstab_remap_cubic_border(const void *src, size_t pitch_src, int sw, int sh, int channels, const void *map_x, size_t pitch_x,
+                                      const void *map_y, size_t pitch_y, int border_mode, const int border[3], void *dst, size_t pitch_dst, int dw,
+                                      int dh, void *stream) {
+    return remap_resample<CubicKernels>("vstab_remap_cubic_border", src, pitch_src, sw, sh, channels, map_x, pitch_x, map_y, pitch_y, &border_mode, border,
+                                        dst, pitch_dst, dw, dh, stream);
 }
 
 vstab_status vstab_warp_nv12_cubic(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17], int map_mode,
                                    int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_cubic: null pointer");
-    if (sw <= 0 || sh <= 0 || (sw & 1) || (sh & 1) || sw > 32767 || sh > 32767)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_cubic: source must be even-sized and <= 32767");
-    if (dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_cubic: output size must be in [1, 32767]");
-    if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_cubic: unknown map mode");
-    if (out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12_PLANAR)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_cubic: the cubic warp emits VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR (NV12 through BGR is not served)");
-    const bool planar = out_format == VSTAB_OUT_NV12_PLANAR;
-    if (pitch_y < (size_t)sw || pitch_uv < (size_t)sw || pitch_dst < (size_t)dw * (planar ? 1 : 3))
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_cubic: pitch smaller than row");
-    if (planar && (!dst_uv || pitch_dst_uv < (size_t)((dw + 1) / 2) * 2))
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_cubic: plane-wise output needs a chroma plane of 2*ceil(width/2) bytes per row");
-    if (!cubic_aligned(uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_cubic: chroma plane must be 2-B aligned");
-    CubicArgs c;
-    WarpArgs &a = c.w;
-    a.y = (const uint8_t *)y, a.uv = (const uint8_t *)uv, a.dst = (uint8_t *)dst, a.dst_uv = planar ? (uint8_t *)dst_uv : nullptr;
-    a.pitch_y = pitch_y, a.pitch_uv = pitch_uv, a.pitch_dst = pitch_dst, a.pitch_dst_uv = planar ? pitch_dst_uv : 0;
-    a.sw = sw, a.sh = sh, a.dw = dw, a.dh = dh;
-    MapParams &p = a.p;
-    p.icx = params[0], p.icy = params[1], p.ifx = params[2], p.ify = params[3];
-    p.ocx = params[4], p.ocy = params[5], p.ofx = params[6], p.ofy = params[7];
-    for (int i = 0; i < 9; i++) p.r[i] = params[8 + i];
-    c.p32 = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
-    const dim3 grid(div_up(dw, CUBIC_TW), div_up(dh, CUBIC_TH));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LaunchEvents ev = take_launch_events();  // a profiling caller's pair: the kernel's own start / end stamps
-#define VSTAB_MODES(P)                                                                                 \
-    switch (map_mode) {                                                                                \
-        case VSTAB_MAP_CREATEMAP_CL: launch_warp_cubic<MAP_CREATEMAP_CL, P>(c, grid, ev, st); break;   \
-        case VSTAB_MAP_FISH_TO_RECT: launch_warp_cubic<MAP_FISH_TO_RECT, P>(c, grid, ev, st); break;   \
-        case VSTAB_MAP_FISH_TO_FISH: launch_warp_cubic<MAP_FISH_TO_FISH, P>(c, grid, ev, st); break;   \
-        case VSTAB_MAP_RECT_TO_RECT: launch_warp_cubic<MAP_RECT_TO_RECT, P>(c, grid, ev, st); break;   \
-        case VSTAB_MAP_RECT_TO_FISH: launch_warp_cubic<MAP_RECT_TO_FISH, P>(c, grid, ev, st); break;   \
-        default: launch_warp_cubic<MAP_CREATEMAP_CL_OPENCL, P>(c, grid, ev, st); break;                \
-    }
-    if (planar) VSTAB_MODES(true)
-    else VSTAB_MODES(false)
-#undef VSTAB_MODES
-    VSTAB_HIP_TRY(hipGetLastError());
-    return VSTAB_OK;
+    return warp_resample<CubicKernels>("vstab_warp_nv12_cubic", "the cubic warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, nullptr,
+                                       dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
+}
+
+vstab_status vstab_warp_nv12_cubic_border(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                          int map_mode, int out_format, int border_mode, void *dst, size_t pitch_dst, void *dst_uv,
+                                          size_t pitch_dst_uv, int dw, int dh, void *stream) {
+    return warp_resample<CubicKernels>("vstab_warp_nv12_cubic_border", "", y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, &border_mode,
+                                       dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
 }
 
 }  // extern "C"
