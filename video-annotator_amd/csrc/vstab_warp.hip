@@ -6,11 +6,7 @@
 #include <climits>
 #include <cstdlib>
 
-#include <hip/hip_ext.h>
-
-#include "vstab_device.hpp"
-#include "vstab_internal.hpp"
-#include "vstab_warp_args.hpp"
+#include "vstab_warp_host.hpp"
 
 namespace vstab {
 
@@ -336,16 +332,6 @@ __global__ void __launch_bounds__(64) k_draw_markers(uint8_t *__restrict__ dst, 
     }
 }
 
-static MapParams to_params(const float p[17]) {
-    MapParams m;
-    m.icx = p[0], m.icy = p[1], m.ifx = p[2], m.ify = p[3];
-    m.ocx = p[4], m.ocy = p[5], m.ofx = p[6], m.ofy = p[7];
-    for (int i = 0; i < 9; i++) m.r[i] = p[8 + i];
-    return m;
-}
-
-static inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace vstab
 
 using namespace vstab;
@@ -359,7 +345,7 @@ vstab_status pack_p010_planes(const void *y, size_t pitch_y, const void *uv, siz
     if (pitch_y < (size_t)width * 2 || pitch_uv < (size_t)width * 2) return fail(VSTAB_ERR_INVALID, "vstab_pack_p010: pitch smaller than row");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int rows = luma_only ? height : height + height / 2;
-    const bool vec = aligned(y, 16) && aligned(uv, 16) && aligned(dst, 8) && pitch_y % 16 == 0 && pitch_uv % 16 == 0 && width % 8 == 0;
+    const bool vec = ptr_aligned(y, 16) && ptr_aligned(uv, 16) && ptr_aligned(dst, 8) && pitch_y % 16 == 0 && pitch_uv % 16 == 0 && width % 8 == 0;
     if (vec) {
         const int units = width / 8;
         dim3 grid(std::min<unsigned>(div_up((unsigned)((long)units * rows), 256), 2048));
@@ -386,7 +372,7 @@ vstab_status pack_nv12_planes(const void *y, size_t pitch_y, const void *uv, siz
     if (pitch_y < (size_t)width || pitch_uv < (size_t)width)
         return fail(VSTAB_ERR_INVALID, "vstab_pack_nv12: pitch smaller than row");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool v16 = aligned(y, 16) && aligned(uv, 16) && aligned(dst, 16) && pitch_y % 16 == 0 &&
+    const bool v16 = ptr_aligned(y, 16) && ptr_aligned(uv, 16) && ptr_aligned(dst, 16) && pitch_y % 16 == 0 &&
                      pitch_uv % 16 == 0 && width % 16 == 0;
     const int rows = height + height / 2;
     if (v16) {
@@ -394,12 +380,12 @@ vstab_status pack_nv12_planes(const void *y, size_t pitch_y, const void *uv, siz
         dim3 grid(std::min<unsigned>(div_up((unsigned)((long)vecs * rows), 256), 1024));
         hipExtLaunchKernelGGL(k_pack_nv12<uint4>, grid, dim3(256), 0, s, nullptr, done, 0, (const uint8_t *)y, pitch_y,
                            (const uint8_t *)uv, pitch_uv, vecs, height, (uint8_t *)dst, (size_t)width);
-    } else if (aligned(y, 8) && aligned(uv, 8) && aligned(dst, 8) && pitch_y % 8 == 0 && pitch_uv % 8 == 0 && width % 8 == 0) {
+    } else if (ptr_aligned(y, 8) && ptr_aligned(uv, 8) && ptr_aligned(dst, 8) && pitch_y % 8 == 0 && pitch_uv % 8 == 0 && width % 8 == 0) {
         const int vecs = width / 8;
         dim3 grid(std::min<unsigned>(div_up((unsigned)((long)vecs * rows), 256), 1024));
         hipExtLaunchKernelGGL(k_pack_nv12<uint2>, grid, dim3(256), 0, s, nullptr, done, 0, (const uint8_t *)y, pitch_y,
                            (const uint8_t *)uv, pitch_uv, vecs, height, (uint8_t *)dst, (size_t)width);
-    } else if (aligned(y, 4) && aligned(uv, 4) && aligned(dst, 4) && pitch_y % 4 == 0 && pitch_uv % 4 == 0 && width % 4 == 0) {
+    } else if (ptr_aligned(y, 4) && ptr_aligned(uv, 4) && ptr_aligned(dst, 4) && pitch_y % 4 == 0 && pitch_uv % 4 == 0 && width % 4 == 0) {
         const int vecs = width / 4;
         dim3 grid(std::min<unsigned>(div_up((unsigned)((long)vecs * rows), 256), 1024));
         hipExtLaunchKernelGGL(k_pack_nv12<uint32_t>, grid, dim3(256), 0, s, nullptr, done, 0, (const uint8_t *)y, pitch_y,
@@ -442,7 +428,7 @@ vstab_status vstab_cvt_nv12_bgr(const void *y, size_t pitch_y, const void *uv, s
         return fail(VSTAB_ERR_INVALID, "vstab_cvt_nv12_bgr: width and height must be even");  // OpenCV asserts
     if (pitch_y < (size_t)width || pitch_uv < (size_t)width || pitch_dst < (size_t)width * 3)
         return fail(VSTAB_ERR_INVALID, "vstab_cvt_nv12_bgr: pitch smaller than row");
-    const int vec_ok = aligned(y, 8) && aligned(uv, 8) && aligned(dst, 8) && pitch_y % 8 == 0 &&
+    const int vec_ok = ptr_aligned(y, 8) && ptr_aligned(uv, 8) && ptr_aligned(dst, 8) && pitch_y % 8 == 0 &&
                        pitch_uv % 8 == 0 && pitch_dst % 8 == 0;
     dim3 block(32, 8);
     dim3 grid(div_up(div_up(width, 8), 32), div_up(div_up(height, 2), 8));
@@ -460,19 +446,17 @@ vstab_status vstab_create_map_ex(void *map_x, size_t pitch_x, void *map_y, size_
     if (pitch_x < (size_t)cols * 4 || pitch_y < (size_t)cols * 4 || pitch_x % 4 || pitch_y % 4)
         return fail(VSTAB_ERR_INVALID, "vstab_create_map: bad pitch");
     if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_create_map: unknown map mode");
-    const int vec_ok = aligned(map_x, 16) && aligned(map_y, 16) && pitch_x % 16 == 0 && pitch_y % 16 == 0;
+    const int vec_ok = ptr_aligned(map_x, 16) && ptr_aligned(map_y, 16) && pitch_x % 16 == 0 && pitch_y % 16 == 0;
     dim3 grid(div_up(div_up(cols, 4), 16), div_up(rows, 16));
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define VSTAB_LAUNCH(K) hipLaunchKernelGGL(K, grid, dim3(16, 16), 0, s, (float *)map_x, pitch_x, (float *)map_y, pitch_y, cols, rows, to_params(params), vec_ok)
-    switch (map_mode) {
-        case VSTAB_MAP_CREATEMAP_CL: VSTAB_LAUNCH(k_create_map); break;
-        case VSTAB_MAP_FISH_TO_RECT: VSTAB_LAUNCH(k_create_map_ex<MAP_FISH_TO_RECT>); break;
-        case VSTAB_MAP_FISH_TO_FISH: VSTAB_LAUNCH(k_create_map_ex<MAP_FISH_TO_FISH>); break;
-        case VSTAB_MAP_RECT_TO_RECT: VSTAB_LAUNCH(k_create_map_ex<MAP_RECT_TO_RECT>); break;
-        case VSTAB_MAP_RECT_TO_FISH: VSTAB_LAUNCH(k_create_map_ex<MAP_RECT_TO_FISH>); break;
-        default: VSTAB_LAUNCH(k_create_map_ex<MAP_CREATEMAP_CL_OPENCL>); break;
-    }
-#undef VSTAB_LAUNCH
+    with_map_mode(map_mode, [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(16, 16), 0, s, (float *)map_x, pitch_x, (float *)map_y, pitch_y, cols, rows, map_params(params), vec_ok);
+        };
+        if constexpr (MODE == MAP_CREATEMAP_CL) launch(k_create_map);  // createMap.cl itself
+        else launch(k_create_map_ex<MODE>);
+    });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }
@@ -526,26 +510,23 @@ static vstab_status warp_impl(const void *y, size_t pitch_y, const void *uv, siz
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: pitch smaller than row");
     if (nv12_out && (!dst_uv || pitch_dst_uv < (size_t)((dw + 1) / 2) * 2))
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: NV12 output needs a chroma plane of 2*ceil(width/2) bytes per row");
-    if (!aligned(uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: chroma plane must be 2-B aligned");
+    if (!ptr_aligned(uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: chroma plane must be 2-B aligned");
     WarpArgs a;
-    a.y = (const uint8_t *)y, a.uv = (const uint8_t *)uv, a.dst = (uint8_t *)dst, a.dst_uv = (uint8_t *)dst_uv;
-    a.pitch_y = pitch_y, a.pitch_uv = pitch_uv, a.pitch_dst = pitch_dst, a.pitch_dst_uv = pitch_dst_uv;
-    a.sw = sw, a.sh = sh, a.dw = dw, a.dh = dh;
-    a.p = to_params(params);
-    const int vec_ok = aligned(dst, 4) && pitch_dst % 4 == 0 && (!nv12_out || (aligned(dst_uv, 4) && pitch_dst_uv % 4 == 0));
-    const bool small_pitch = pitch_y < (1u << 24) && pitch_uv < (1u << 24) && (uint64_t)pitch_y * sh < (1ull << 32);
-    // the staged loads of the tiled kernels form chroma row offsets in 32 bits as well: a chroma plane of 4 GiB or more is sampled
-    // from global memory with 64-bit addresses instead (the direct kernel in plain mode, the gather path of the tiled kernels otherwise)
-    const bool stage32 = small_pitch && (uint64_t)pitch_uv * (sh / 2) < (1ull << 32);
-    if (rot_bottom && map_mode != VSTAB_MAP_CREATEMAP_CL && map_mode != VSTAB_MAP_FISH_TO_RECT && map_mode != VSTAB_MAP_CREATEMAP_CL_OPENCL)
+    fill_warp_args(a, y, pitch_y, uv, pitch_uv, sw, sh, params, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh);
+    const int vec_ok = ptr_aligned(dst, 4) && pitch_dst % 4 == 0 && (!nv12_out || (ptr_aligned(dst_uv, 4) && pitch_dst_uv % 4 == 0));
+    // a chroma plane of 4 GiB or more (staged_offsets32: rows without chroma) is sampled from global memory with 64-bit addresses: the direct
+    // kernel in plain mode, the gather path of the tiled kernels otherwise
+    const StagedOffsets32 off32 = staged_offsets32(pitch_y, pitch_uv, sh);
+    const bool small_pitch = off32.rows, stage32 = off32.chroma;
+    if (rot_bottom && !map_mode_fish_to_pinhole(map_mode))
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_rs: the per-row warp exists for the fisheye -> pinhole modes (0, 1, 5) only");
     const bool plain = map_mode == VSTAB_MAP_CREATEMAP_CL && !nv12_out && !qmap && !rot_bottom;
     if (!plain && !small_pitch) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: source pitch too large for this mode");
     if (planar) {  // the plane-wise warp: its own kernel (vstab_warp_planar.hip); the map is always evaluated
         if (qmap) return fail(VSTAB_ERR_UNSUPPORTED, "vstab_warp_nv12_mapped: the quantised map holds no chroma positions -- VSTAB_OUT_NV12_PLANAR goes through vstab_warp_nv12_ex");
         if (sw < 16 || sh < 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: the plane-wise warp needs a source of at least 16 x 2");
-        const bool src16 = stage32 && aligned(y, 16) && aligned(uv, 16) && pitch_y % 16 == 0 && pitch_uv % 16 == 0;  // 16-byte staging loads
-        const bool dst16 = aligned(dst, 16) && aligned(dst_uv, 16) && pitch_dst % 16 == 0 && pitch_dst_uv % 16 == 0;
+        const bool src16 = stage32 && ptr_aligned(y, 16) && ptr_aligned(uv, 16) && pitch_y % 16 == 0 && pitch_uv % 16 == 0;  // 16-byte staging loads
+        const bool dst16 = ptr_aligned(dst, 16) && ptr_aligned(dst_uv, 16) && pitch_dst % 16 == 0 && pitch_dst_uv % 16 == 0;
         return launch_warp_planar(a, params, map_mode, 8, 0, src16, dst16, rot_bottom, static_cast<hipStream_t>(stream));
     }
     bool direct = !small_pitch || (plain && !stage32);
@@ -557,7 +538,7 @@ static vstab_status warp_impl(const void *y, size_t pitch_y, const void *uv, siz
         dim3 grid(div_up(dw, WARP_TILE_W), div_up(dh, WARP_TILE_H));
         hipLaunchKernelGGL(k_warp_nv12_bgr, grid, dim3(16, 16), 0, static_cast<hipStream_t>(stream), a, vec_ok);
     } else {
-        const bool src_vec_ok = stage32 && aligned(y, 8) && aligned(uv, 8) && pitch_y % 8 == 0 && pitch_uv % 8 == 0;  // 8-byte staging loads
+        const bool src_vec_ok = stage32 && ptr_aligned(y, 8) && ptr_aligned(uv, 8) && pitch_y % 8 == 0 && pitch_uv % 8 == 0;  // 8-byte staging loads
         return launch_warp_fused(a, params, map_mode, nv12_out, src_vec_ok, vec_ok, qmap, qpitch, rot_bottom, static_cast<hipStream_t>(stream));
     }
     VSTAB_HIP_TRY(hipGetLastError());
@@ -599,22 +580,14 @@ size_t vstab_quantised_map_bytes(int dst_width, int dst_height) {
 vstab_status vstab_quantised_map(void *qmap, int dw, int dh, const float params[17], int map_mode, void *stream) {
     if (!qmap || !params || dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767) return fail(VSTAB_ERR_INVALID, "vstab_quantised_map: bad argument");
     if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_quantised_map: unknown map mode");
-    if (!aligned(qmap, 16)) return fail(VSTAB_ERR_INVALID, "vstab_quantised_map: the buffer must be 16-byte aligned");
+    if (!ptr_aligned(qmap, 16)) return fail(VSTAB_ERR_INVALID, "vstab_quantised_map: the buffer must be 16-byte aligned");
     const int qpitch = (dw + 3) & ~3;
-    const MapParams p = to_params(params);
-    const MapParams32 p32 = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
     dim3 grid(div_up(qpitch / 4, 16), div_up(dh, 16));
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define VSTAB_LAUNCH(M) hipLaunchKernelGGL(k_quantised_map<M>, grid, dim3(256), 0, st, static_cast<int2 *>(qmap), qpitch, dw, dh, p, p32)
-    switch (map_mode) {
-        case VSTAB_MAP_CREATEMAP_CL: VSTAB_LAUNCH(MAP_CREATEMAP_CL); break;
-        case VSTAB_MAP_FISH_TO_RECT: VSTAB_LAUNCH(MAP_FISH_TO_RECT); break;
-        case VSTAB_MAP_FISH_TO_FISH: VSTAB_LAUNCH(MAP_FISH_TO_FISH); break;
-        case VSTAB_MAP_RECT_TO_RECT: VSTAB_LAUNCH(MAP_RECT_TO_RECT); break;
-        case VSTAB_MAP_RECT_TO_FISH: VSTAB_LAUNCH(MAP_RECT_TO_FISH); break;
-        default: VSTAB_LAUNCH(MAP_CREATEMAP_CL_OPENCL); break;
-    }
-#undef VSTAB_LAUNCH
+    with_map_mode(map_mode, [&](auto mode) {
+        hipLaunchKernelGGL(k_quantised_map<decltype(mode)::value>, grid, dim3(256), 0, st, static_cast<int2 *>(qmap), qpitch, dw, dh, map_params(params),
+                           map_params32(params));
+    });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }
@@ -622,7 +595,7 @@ vstab_status vstab_quantised_map(void *qmap, int dw, int dh, const float params[
 vstab_status vstab_warp_nv12_mapped(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const void *qmap,
                                     int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh,
                                     void *stream) {
-    if (!qmap || !aligned(qmap, 16)) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_mapped: the quantised map must be a 16-byte aligned device buffer");
+    if (!qmap || !ptr_aligned(qmap, 16)) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_mapped: the quantised map must be a 16-byte aligned device buffer");
     static const float unused[17] = {0};
     return warp_impl(y, pitch_y, uv, pitch_uv, sw, sh, unused, VSTAB_MAP_CREATEMAP_CL, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream,
                      qmap, (dw + 3) & ~3);
@@ -633,25 +606,15 @@ vstab_status vstab_warp_nv12_nearest_ex(const void *y, size_t pitch_y, const voi
     if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_nearest: null pointer");
     if (sw <= 0 || sh <= 0 || (sw & 1) || (sh & 1) || sw > 32767 || sh > 32767 || dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767)
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_nearest: sizes must be in [1, 32767], source even");
-    if (pitch_y < (size_t)sw || pitch_uv < (size_t)sw || pitch_dst < (size_t)dw * 3 || !aligned(uv, 2) || pitch_uv % 2)
+    if (pitch_y < (size_t)sw || pitch_uv < (size_t)sw || pitch_dst < (size_t)dw * 3 || !ptr_aligned(uv, 2) || pitch_uv % 2)
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_nearest: bad pitch or chroma alignment");
     if (map_mode != VSTAB_MAP_CREATEMAP_CL && map_mode != VSTAB_MAP_CREATEMAP_CL_OPENCL)
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_nearest: the nearest-neighbour warp exists for the reference's own map (modes 0 and 5)");
     WarpArgs a;
-    a.y = (const uint8_t *)y, a.uv = (const uint8_t *)uv, a.dst = (uint8_t *)dst, a.dst_uv = nullptr;
-    a.pitch_y = pitch_y, a.pitch_uv = pitch_uv, a.pitch_dst = pitch_dst, a.pitch_dst_uv = 0;
-    a.sw = sw, a.sh = sh, a.dw = dw, a.dh = dh;
-    a.p = to_params(params);
-    const dim3 grid(div_up(dw, 64), div_up(dh, 4));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LaunchEvents ev = take_launch_events();  // a profiling caller's pair: the kernel's own start / end stamps
-    if (map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL) {
-        if (ev.start) hipExtLaunchKernelGGL(k_warp_nearest<true>, grid, dim3(256), 0, st, ev.start, ev.stop, 0, a);
-        else hipLaunchKernelGGL(k_warp_nearest<true>, grid, dim3(256), 0, st, a);
-    } else {
-        if (ev.start) hipExtLaunchKernelGGL(k_warp_nearest<false>, grid, dim3(256), 0, st, ev.start, ev.stop, 0, a);
-        else hipLaunchKernelGGL(k_warp_nearest<false>, grid, dim3(256), 0, st, a);
-    }
+    fill_warp_args(a, y, pitch_y, uv, pitch_uv, sw, sh, params, dst, pitch_dst, nullptr, 0, dw, dh);
+    with_bool(map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL, [&](auto ocl) {
+        launch_kernel(k_warp_nearest<decltype(ocl)::value>, dim3(div_up(dw, 64), div_up(dh, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }

@@ -17,7 +17,7 @@
 //   4. blend    4 LDS reads per pixel at their natural alignment, v_dot2_i32_i16 on channel pairs gathered by v_perm_b32.
 // A box over the LDS budget (the axis pixel of map mode 0 at -32768, strong minification) is sampled from global memory with the same
 // arithmetic; so is every pixel of the stateless remap.
-#include "vstab_resample_host.hpp"
+#include "vstab_warp_host.hpp"
 
 namespace vstab {
 
@@ -236,15 +236,14 @@ vstab_status vstab_warp_nv12_border(const void *y, size_t pitch_y, const void *u
     const vstab_status st = check_warp_nv12("vstab_warp_nv12_border", "the border warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode,
                                             out_format, &border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, ba.c);
     if (st != VSTAB_OK) return st;
-    for (int k = 0; k < 9; k++) ba.rs_d[k] = rot_bottom ? rot_bottom[k] - params[8 + k] : 0.0f;  // fp32, as the definition forms it
-    ba.rs_den = (float)(dh > 1 ? dh - 1 : 1);
+    fill_rolling_shutter(ba, params, rot_bottom, dh);
     with_map_mode(map_mode, [&](auto mode) {
         with_border_mode(border_mode, [&](auto border) {
             with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
                 with_bool(rot_bottom != nullptr, [&](auto rs) {
                     constexpr int MODE = decltype(mode)::value;
                     // the rotation per output row is served (and checked above) for map modes 0, 1 and 5 only
-                    if constexpr (!decltype(rs)::value || MODE == MAP_CREATEMAP_CL || MODE == MAP_FISH_TO_RECT || MODE == MAP_CREATEMAP_CL_OPENCL)
+                    if constexpr (!decltype(rs)::value || map_mode_fish_to_pinhole(MODE))
                         launch_tiles(k_warp_border<MODE, decltype(planar)::value, decltype(rs)::value, decltype(border)::value>, ba, dw, dh, stream);
                 });
             });

@@ -4,10 +4,10 @@
 // footprint at (X - 1 .. X + 2, Y - 1 .. Y + 2), 16 integer weights from OpenCV's fixed-point table (vstab_cubic.hpp), each tap outside the
 // source the border value (BORDER_CONSTANT) or read at its borderInterpolate position, (sum + 2^14) >> 15 saturated to 0..255.
 //
-// The tile's phases, the remap and the entry points are the resamplers' common ones (vstab_resample.hpp, vstab_resample_host.hpp).  This
+// The tile's phases, the remap and the entry points are the resamplers' common ones (vstab_resample.hpp, vstab_warp_host.hpp).  This
 // unit holds the cubic table, the cubic blend, the constant border's tile (k_warp_cubic) and the kernels under their names.
 #include "vstab_cubic.hpp"
-#include "vstab_resample_host.hpp"
+#include "vstab_warp_host.hpp"
 
 namespace vstab {
 

@@ -28,12 +28,8 @@
 #include <cmath>
 #include <cstdlib>
 
-#include <hip/hip_ext.h>
-
-#include "vstab_device.hpp"
 #include "vstab_device10.hpp"
-#include "vstab_internal.hpp"
-#include "vstab_warp_args.hpp"
+#include "vstab_warp_host.hpp"
 #include "vstab_warp_tile.hpp"
 
 namespace vstab {
@@ -109,8 +105,8 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
         int sy_ = (int)(256.0f * rn), sx_ = 256 - sy_ * ux_n;  // uniform: divmod(256, ux_n)
         if (sx_ < 0) sx_ += ux_n, sy_--;
         if (sx_ >= ux_n) sx_ -= ux_n, sy_++;
-        // < 2^24, pitch_y * sh and pitch_uv * sh / 2 < 2^32: src_vec_ok is only set under those host checks (warp_impl in vstab_warp.hip,
-        // vstab_warp_p010 / _planes), so the 32-bit row offsets below cannot wrap
+        // src_vec_ok is only set under staged_offsets32(...).chroma (vstab_warp_host.hpp: pitches < 2^24, pitch_y * sh and pitch_uv * sh / 2
+        // < 2^32), so the 32-bit row offsets below cannot wrap
         const uint32_t pitch_y = (uint32_t)a.pitch_y, pitch_uv = (uint32_t)a.pitch_uv;
         // no per-lane branch around any load, so that all of them are in flight under the map phase; a trip that no
         // thread of the workgroup needs (most boxes have fewer than 256 blocks) is skipped by a scalar branch: its
@@ -498,7 +494,7 @@ __global__ void __launch_bounds__(256, DEPTH == 10 ? 5 : (RWB == 8 || map_mode_i
 
 using namespace vstab;
 
-// Launch of the fused kernel; called by warp_impl (vstab_warp.hip) after argument validation.
+// Launches of the fused kernel; called by the C-ABI entry points (vstab_warp.hip, vstab_warp_p010.hip) after argument validation.
 namespace vstab {
 #ifdef VSTAB_DEV
 static unsigned long long *g_dev_timing = nullptr;
@@ -510,15 +506,7 @@ extern "C" __attribute__((visibility("default"))) void vstab_dev_set_timing(void
 vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int map_mode, int blend, const float *rot_bottom, bool p010_out, bool src_vec_ok,
                                  bool dst_vec_ok, hipStream_t st) {
     FusedArgs ta;
-    ta.w = a;
-    ta.p32 = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
-    ta.src_vec_ok = src_vec_ok, ta.dst_vec_ok = dst_vec_ok;
-    ta.qmap = nullptr, ta.qpitch = 0;
-    for (int k = 0; k < 9; k++) ta.rs_d[k] = rot_bottom ? rot_bottom[k] - params[8 + k] : 0.0f;
-    ta.rs_den = (float)(a.dh > 1 ? a.dh - 1 : 1);
-#ifdef VSTAB_DEV
-    ta.timing = nullptr, ta.ablate = 0, ta.lds_pad = 0;
-#endif
+    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, nullptr, 0, rot_bottom);
     // 64 x 32 tiles, 40 KB of LDS.  The fp16 blend stages 8-byte pixels (three halves): half as many fit, and a tall tile whose box is
     // over that is done as two half-height tiles (SPLIT) -- measured faster than 64 x 16 tiles throughout (47.3 against 49.1 us at 4K).
     const int lds_kb = 40;
@@ -528,31 +516,19 @@ vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int 
     const dim3 grid(tile_schedule(ta, rwb, lds_kb, tiles > 1024 ? 0.5 : 0.0));
     if (half) ta.lds_capacity_px /= 2;
     const size_t lds_bytes = (size_t)lds_kb * 1024;
-    const LaunchEvents ev = take_launch_events();
-#define VSTAB_LAUNCH10(R, M, B, F)                                                                                                  \
-    do {                                                                                                                            \
-        if (ev.start) hipExtLaunchKernelGGL((k_warp_fused<R, M, F, false, 10, B>), grid, dim3(256), lds_bytes, st, ev.start, ev.stop, 0, ta); \
-        else hipLaunchKernelGGL((k_warp_fused<R, M, F, false, 10, B>), grid, dim3(256), lds_bytes, st, ta);                            \
-    } while (0)
-#define VSTAB_LAUNCH10_M(M)                                                      \
-    do {                                                                         \
-        if (p010_out) {                                                          \
-            if (half) VSTAB_LAUNCH10(8, M, VSTAB_BLEND_FP16, 3);                 \
-            else VSTAB_LAUNCH10(8, M, VSTAB_BLEND_EXACT, 3);                     \
-        } else if (half) VSTAB_LAUNCH10(8, M, VSTAB_BLEND_FP16, 2);              \
-        else VSTAB_LAUNCH10(8, M, VSTAB_BLEND_EXACT, 2);                         \
-    } while (0)
-    if (rot_bottom) {
-        if (map_mode == VSTAB_MAP_CREATEMAP_CL) VSTAB_LAUNCH10_M(MAP_RS_CREATEMAP_CL);
-        else if (map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL) VSTAB_LAUNCH10_M(MAP_RS_CREATEMAP_CL_OPENCL);
-        else VSTAB_LAUNCH10_M(MAP_RS_FISH_TO_RECT);
-    } else {
-        if (map_mode == VSTAB_MAP_CREATEMAP_CL) VSTAB_LAUNCH10_M(MAP_CREATEMAP_CL);
-        else if (map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL) VSTAB_LAUNCH10_M(MAP_CREATEMAP_CL_OPENCL);
-        else VSTAB_LAUNCH10_M(MAP_FISH_TO_RECT);
-    }
-#undef VSTAB_LAUNCH10_M
-#undef VSTAB_LAUNCH10
+    vstab_status status = VSTAB_OK;
+    with_map_mode(map_mode, rot_bottom != nullptr, [&](auto mode) {
+        with_either<VSTAB_BLEND_FP16, VSTAB_BLEND_EXACT>(half, [&](auto blend_c) {
+            with_either<3, 2>(p010_out, [&](auto fmt) {
+                constexpr int MODE = decltype(mode)::value;
+                if constexpr (map_mode_fish_to_pinhole(map_mode_base(MODE)))
+                    launch_kernel(k_warp_fused<8, MODE, decltype(fmt)::value, false, 10, decltype(blend_c)::value>, grid, dim3(256), lds_bytes, st, ta);
+                else  // the callers check the mode first; no kernel exists, and nothing is launched
+                    status = fail(VSTAB_ERR_INVALID, "launch_warp_fused10: the 10-bit tiled kernels serve map modes 0, 1 and 5 only");
+            });
+        });
+    });
+    if (status != VSTAB_OK) return status;
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }
@@ -560,14 +536,7 @@ vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int 
 vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int map_mode, bool nv12_out, bool src_vec_ok, bool dst_vec_ok,
                                const void *qmap, int qpitch, const float *rot_bottom, hipStream_t st) {
     FusedArgs ta;
-    ta.w = a;
-    ta.p32 = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
-    ta.src_vec_ok = src_vec_ok, ta.dst_vec_ok = dst_vec_ok;
-    ta.qmap = static_cast<const int2 *>(qmap), ta.qpitch = qpitch;
-    for (int k = 0; k < 9; k++) ta.rs_d[k] = rot_bottom ? rot_bottom[k] - params[8 + k] : 0.0f;  // fp32, as the definition forms it
-    ta.rs_den = (float)(a.dh > 1 ? a.dh - 1 : 1);
-    if (rot_bottom)  // modes 0 / 1 / 5 only (checked by the caller)
-        map_mode = map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL ? (int)MAP_RS_CREATEMAP_CL_OPENCL : map_mode + (int)MAP_RS_CREATEMAP_CL;
+    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, qmap, qpitch, rot_bottom);
 #ifdef VSTAB_DEV
     ta.timing = g_dev_timing;
     static const int ablate = getenv("VSTAB_ABLATE") ? atoi(getenv("VSTAB_ABLATE")) : 0;
@@ -589,37 +558,19 @@ vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int ma
 #endif
     const size_t lds_bytes = (size_t)lds_kb * 1024;
     const dim3 grid(tile_schedule(ta, rwb, lds_kb, tail_rounds));
-    // a profiling caller may have left an event pair for this launch: the kernel's own start / end stamps
-    const LaunchEvents ev = take_launch_events();
-#define VSTAB_LAUNCH(R, M, F, C)                                                                                            \
-    do {                                                                                                                    \
-        if (ev.start) hipExtLaunchKernelGGL((k_warp_fused<R, M, F, C>), grid, dim3(256), lds_bytes, st, ev.start, ev.stop, 0, ta); \
-        else hipLaunchKernelGGL((k_warp_fused<R, M, F, C>), grid, dim3(256), lds_bytes, st, ta);                              \
-    } while (0)
-#define VSTAB_LAUNCH_RF(M, C)                                  \
-    do {                                                       \
-        if (rwb == 8 && !nv12_out) VSTAB_LAUNCH(8, M, 0, C);   \
-        else if (rwb == 8) VSTAB_LAUNCH(8, M, 1, C);           \
-        else if (!nv12_out) VSTAB_LAUNCH(4, M, 0, C);          \
-        else VSTAB_LAUNCH(4, M, 1, C);                         \
-    } while (0)
-    if (qmap) {  // the map phase reads the quantised map: the map mode no longer matters
-        VSTAB_LAUNCH_RF(MAP_CREATEMAP_CL, true);
-    } else {
-        switch (map_mode) {
-            case VSTAB_MAP_CREATEMAP_CL: VSTAB_LAUNCH_RF(MAP_CREATEMAP_CL, false); break;
-            case VSTAB_MAP_FISH_TO_RECT: VSTAB_LAUNCH_RF(MAP_FISH_TO_RECT, false); break;
-            case VSTAB_MAP_FISH_TO_FISH: VSTAB_LAUNCH_RF(MAP_FISH_TO_FISH, false); break;
-            case VSTAB_MAP_RECT_TO_RECT: VSTAB_LAUNCH_RF(MAP_RECT_TO_RECT, false); break;
-            case VSTAB_MAP_RECT_TO_FISH: VSTAB_LAUNCH_RF(MAP_RECT_TO_FISH, false); break;
-            case VSTAB_MAP_CREATEMAP_CL_OPENCL: VSTAB_LAUNCH_RF(MAP_CREATEMAP_CL_OPENCL, false); break;
-            case MAP_RS_CREATEMAP_CL: VSTAB_LAUNCH_RF(MAP_RS_CREATEMAP_CL, false); break;
-            case MAP_RS_CREATEMAP_CL_OPENCL: VSTAB_LAUNCH_RF(MAP_RS_CREATEMAP_CL_OPENCL, false); break;
-            default: VSTAB_LAUNCH_RF(MAP_RS_FISH_TO_RECT, false); break;
-        }
-    }
-#undef VSTAB_LAUNCH_RF
-#undef VSTAB_LAUNCH
+    // CACHED: the map phase reads the quantised map, the map mode no longer matters (the kernels exist under MAP_CREATEMAP_CL)
+    with_map_mode(qmap ? (int)VSTAB_MAP_CREATEMAP_CL : map_mode, !qmap && rot_bottom != nullptr, [&](auto mode) {
+        with_bool(qmap != nullptr, [&](auto cached) {
+            with_either<8, 4>(rwb == 8, [&](auto rows) {
+                with_either<1, 0>(nv12_out, [&](auto fmt) {
+                    constexpr int MODE = decltype(mode)::value;
+                    constexpr bool CACHED = decltype(cached)::value;
+                    if constexpr (!CACHED || MODE == MAP_CREATEMAP_CL)
+                        launch_kernel(k_warp_fused<decltype(rows)::value, MODE, decltype(fmt)::value, CACHED>, grid, dim3(256), lds_bytes, st, ta);
+                });
+            });
+        });
+    });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }

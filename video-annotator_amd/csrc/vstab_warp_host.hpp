@@ -1,6 +1,8 @@
-// vstab_resample_host.hpp -- the host side of the entry points of vstab_warp_cubic.hip, vstab_warp_lanczos4.hip and vstab_warp_border.hip:
-// the argument checks (every one before any launch, in one order, each message under the entry point's own name), the kernel argument, the
-// dispatch of a run-time mode to a template argument, and the launches.
+// vstab_warp_host.hpp -- the host side of every warp translation unit (vstab_warp.hip, vstab_warp_fused.hip, vstab_warp_planar.hip,
+// vstab_warp_p010.hip, vstab_warp_cubic.hip, vstab_warp_lanczos4.hip, vstab_warp_border.hip): each fact once.  The alignment predicate, the
+// kernel arguments from the C arguments (MapParams, MapParams32, WarpArgs, the rolling-shutter pair, FusedArgs' common part), the conditions
+// for 32-bit staged offsets, the dispatch of a run-time mode to a template argument, the launch with a profiler's event pair, and the
+// resamplers' argument checks (every one before any launch, in one order, each message under the entry point's own name).
 #pragma once
 #include <hip/hip_ext.h>
 
@@ -13,47 +15,133 @@ namespace vstab {
 
 inline bool ptr_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Kernel arguments from the C arguments.  params[17]: the two cameras and the rotation, as include/vstab.h lays them out.
+// ---------------------------------------------------------------------------------------------------------------------
+inline MapParams map_params(const float params[17]) {
+    MapParams m;
+    m.icx = params[0], m.icy = params[1], m.ifx = params[2], m.ify = params[3];
+    m.ocx = params[4], m.ocy = params[5], m.ofx = params[6], m.ofy = params[7];
+    for (int i = 0; i < 9; i++) m.r[i] = params[8 + i];
+    return m;
+}
+// the source camera scaled to the 1/32-pixel grid of cv::remap's quantisation, and the rotation's third column
+inline MapParams32 map_params32(const float params[17]) {
+    return {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
+}
+inline void fill_warp_args(WarpArgs &a, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17], void *dst,
+                           size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh) {
+    a.y = (const uint8_t *)y, a.uv = (const uint8_t *)uv, a.dst = (uint8_t *)dst, a.dst_uv = (uint8_t *)dst_uv;
+    a.pitch_y = pitch_y, a.pitch_uv = pitch_uv, a.pitch_dst = pitch_dst, a.pitch_dst_uv = pitch_dst_uv;
+    a.sw = sw, a.sh = sh, a.dw = dw, a.dh = dh;
+    a.p = map_params(params);
+}
+// The rotation per output row (FusedArgs, BorderArgs, P010Args: rs_d, rs_den): the last row's rotation minus the first's, fp32 as the
+// definition forms it, and the row count it is spread over.  rot_bottom null: one rotation, rs_d all zero.
+template <typename Args>
+void fill_rolling_shutter(Args &a, const float params[17], const float *rot_bottom, int dh) {
+    for (int k = 0; k < 9; k++) a.rs_d[k] = rot_bottom ? rot_bottom[k] - params[8 + k] : 0.0f;
+    a.rs_den = (float)(dh > 1 ? dh - 1 : 1);
+}
+// what the three launchers of the tiled kernels set alike; the tile shape (tile_schedule) and the VSTAB_DEV fields' values are theirs
+inline void fill_fused_args(FusedArgs &ta, const WarpArgs &a, const float params[17], bool src_vec_ok, bool dst_vec_ok, const void *qmap, int qpitch,
+                            const float *rot_bottom) {
+    ta.w = a;
+    ta.p32 = map_params32(params);
+    ta.src_vec_ok = src_vec_ok, ta.dst_vec_ok = dst_vec_ok;
+    ta.qmap = static_cast<const int2 *>(qmap), ta.qpitch = qpitch;
+    fill_rolling_shutter(ta, params, rot_bottom, a.dh);
+#ifdef VSTAB_DEV
+    ta.timing = nullptr, ta.ablate = 0, ta.lds_pad = 0;
+#endif
+}
+
+// staged_offsets32 -- when the staged loads of the tiled kernels (warp_tile, warp_tile_planar) may form their row offsets in 32 bits.
+//   rows    both pitches < 2^24 (operands of a 24-bit multiply) and pitch_y * sh < 2^32: every luma row offset fits.  Without it the tiled
+//           kernels are not launched at all (the direct-gather kernel with 64-bit addresses, or a refusal).
+//   chroma  and pitch_uv * (sh / 2) < 2^32: every chroma row offset fits as well.  Without it src_vec_ok is false: nothing is staged, the
+//           tiled kernel samples every pixel from global memory with 64-bit addresses.
+struct StagedOffsets32 {
+    bool rows, chroma;
+};
+inline StagedOffsets32 staged_offsets32(size_t pitch_y, size_t pitch_uv, int sh) {
+    const bool rows = pitch_y < (1u << 24) && pitch_uv < (1u << 24) && (uint64_t)pitch_y * sh < (1ull << 32);
+    return {rows, rows && (uint64_t)pitch_uv * (sh / 2) < (1ull << 32)};
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // f(std::integral_constant<..., the mode>) for a checked run-time mode
+// ---------------------------------------------------------------------------------------------------------------------
+template <int M>
+using mode_constant = std::integral_constant<int, M>;
 template <typename F>
 void with_map_mode(int map_mode, F &&f) {
     switch (map_mode) {
-        case VSTAB_MAP_CREATEMAP_CL: f(std::integral_constant<int, MAP_CREATEMAP_CL>{}); break;
-        case VSTAB_MAP_FISH_TO_RECT: f(std::integral_constant<int, MAP_FISH_TO_RECT>{}); break;
-        case VSTAB_MAP_FISH_TO_FISH: f(std::integral_constant<int, MAP_FISH_TO_FISH>{}); break;
-        case VSTAB_MAP_RECT_TO_RECT: f(std::integral_constant<int, MAP_RECT_TO_RECT>{}); break;
-        case VSTAB_MAP_RECT_TO_FISH: f(std::integral_constant<int, MAP_RECT_TO_FISH>{}); break;
-        default: f(std::integral_constant<int, MAP_CREATEMAP_CL_OPENCL>{}); break;
+        case VSTAB_MAP_CREATEMAP_CL: f(mode_constant<MAP_CREATEMAP_CL>{}); break;
+        case VSTAB_MAP_FISH_TO_RECT: f(mode_constant<MAP_FISH_TO_RECT>{}); break;
+        case VSTAB_MAP_FISH_TO_FISH: f(mode_constant<MAP_FISH_TO_FISH>{}); break;
+        case VSTAB_MAP_RECT_TO_RECT: f(mode_constant<MAP_RECT_TO_RECT>{}); break;
+        case VSTAB_MAP_RECT_TO_FISH: f(mode_constant<MAP_RECT_TO_FISH>{}); break;
+        default: f(mode_constant<MAP_CREATEMAP_CL_OPENCL>{}); break;
     }
 }
+// rs (a rotation per output row; checked: map modes 0, 1 and 5 only): the mode's MAP_RS_* form
+template <typename F>
+void with_map_mode(int map_mode, bool rs, F &&f) {
+    if (!rs) return with_map_mode(map_mode, f);
+    switch (map_mode) {
+        case VSTAB_MAP_CREATEMAP_CL: f(mode_constant<MAP_RS_CREATEMAP_CL>{}); break;
+        case VSTAB_MAP_CREATEMAP_CL_OPENCL: f(mode_constant<MAP_RS_CREATEMAP_CL_OPENCL>{}); break;
+        default: f(mode_constant<MAP_RS_FISH_TO_RECT>{}); break;
+    }
+}
+// the fisheye -> pinhole maps (modes 0, 1, 5): the only ones that take a rotation per output row (so the only ones with a MAP_RS_*
+// form), and the only ones the 10-bit tiled kernels serve.  Asked of the public VSTAB_MAP_* values by the argument checks and of the
+// kernels' MAP_* template values (a base mode: map_mode_base) by the launchers: the two enumerations agree on 0 .. 5, and the internal
+// MAP_RS_* values 6 .. 8 are not among the three, so a caller's map_mode 6 is refused like any unknown mode.
+static_assert((int)VSTAB_MAP_CREATEMAP_CL == (int)MAP_CREATEMAP_CL && (int)VSTAB_MAP_FISH_TO_RECT == (int)MAP_FISH_TO_RECT &&
+                  (int)VSTAB_MAP_FISH_TO_FISH == (int)MAP_FISH_TO_FISH && (int)VSTAB_MAP_RECT_TO_RECT == (int)MAP_RECT_TO_RECT &&
+                  (int)VSTAB_MAP_RECT_TO_FISH == (int)MAP_RECT_TO_FISH && (int)VSTAB_MAP_CREATEMAP_CL_OPENCL == (int)MAP_CREATEMAP_CL_OPENCL,
+              "the public map modes and the kernels' template values are one numbering");
+constexpr bool map_mode_fish_to_pinhole(int mode) { return mode == MAP_CREATEMAP_CL || mode == MAP_FISH_TO_RECT || mode == MAP_CREATEMAP_CL_OPENCL; }
 template <typename F>
 void with_border_mode(int border_mode, F &&f) {
     switch (border_mode) {
-        case VSTAB_BORDER_CONSTANT: f(std::integral_constant<int, VSTAB_BORDER_CONSTANT>{}); break;
-        case VSTAB_BORDER_REPLICATE: f(std::integral_constant<int, VSTAB_BORDER_REPLICATE>{}); break;
-        case VSTAB_BORDER_REFLECT: f(std::integral_constant<int, VSTAB_BORDER_REFLECT>{}); break;
-        default: f(std::integral_constant<int, VSTAB_BORDER_REFLECT_101>{}); break;
+        case VSTAB_BORDER_CONSTANT: f(mode_constant<VSTAB_BORDER_CONSTANT>{}); break;
+        case VSTAB_BORDER_REPLICATE: f(mode_constant<VSTAB_BORDER_REPLICATE>{}); break;
+        case VSTAB_BORDER_REFLECT: f(mode_constant<VSTAB_BORDER_REFLECT>{}); break;
+        default: f(mode_constant<VSTAB_BORDER_REFLECT_101>{}); break;
     }
 }
 template <typename F>
 void with_channels(int channels, F &&f) {
-    if (channels == 1) f(std::integral_constant<int, 1>{});
-    else if (channels == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 3>{});
+    if (channels == 1) f(mode_constant<1>{});
+    else if (channels == 2) f(mode_constant<2>{});
+    else f(mode_constant<3>{});
 }
 template <typename F>
 void with_bool(bool b, F &&f) {
     if (b) f(std::true_type{});
     else f(std::false_type{});
 }
+// one of two values of a template argument: rows per wave 8 / 4, output formats, blends
+template <int A, int B, typename F>
+void with_either(bool first, F &&f) {
+    if (first) f(mode_constant<A>{});
+    else f(mode_constant<B>{});
+}
 
-// a tile kernel on its grid; a profiling caller's event pair takes the kernel's own start / end stamps
+// A kernel that takes one argument block, launched; a profiling caller's event pair (take_launch_events) takes the kernel's own start / end stamps
+template <typename Kernel, typename Args>
+void launch_kernel(Kernel kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Args &args) {
+    const LaunchEvents ev = take_launch_events();
+    if (ev.start) hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, st, ev.start, ev.stop, 0, args);
+    else hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, args);
+}
+// a resampler's tile kernel on its grid
 template <typename Kernel, typename Args>
 void launch_tiles(Kernel kernel, const Args &args, int dw, int dh, void *stream) {
-    const dim3 grid(div_up(dw, RESAMPLE_TW), div_up(dh, RESAMPLE_TH));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LaunchEvents ev = take_launch_events();
-    if (ev.start) hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ev.start, ev.stop, 0, args);
-    else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, args);
+    launch_kernel(kernel, dim3(div_up(dw, RESAMPLE_TW), div_up(dh, RESAMPLE_TH)), dim3(256), 0, static_cast<hipStream_t>(stream), args);
 }
 
 // The NV12 warps' arguments, checked, into the kernel argument.  who: the subject of the output-format message ("the cubic warp "; "").
@@ -66,7 +154,7 @@ inline vstab_status check_warp_nv12(const std::string &n, const char *who, const
         return fail(VSTAB_ERR_INVALID, n + ": source must be even-sized and <= 32767");
     if (dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767) return fail(VSTAB_ERR_INVALID, n + ": output size must be in [1, 32767]");
     if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, n + ": unknown map mode");
-    if (rot_bottom && map_mode != VSTAB_MAP_CREATEMAP_CL && map_mode != VSTAB_MAP_FISH_TO_RECT && map_mode != VSTAB_MAP_CREATEMAP_CL_OPENCL)
+    if (rot_bottom && !map_mode_fish_to_pinhole(map_mode))
         return fail(VSTAB_ERR_INVALID, n + ": a rotation per output row (rot_bottom) is served for map modes 0, 1 and 5");
     if (out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12_PLANAR)
         return fail(VSTAB_ERR_INVALID, n + ": " + who + "emits VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR (NV12 through BGR is not served)");
@@ -78,15 +166,8 @@ inline vstab_status check_warp_nv12(const std::string &n, const char *who, const
     if (planar && (!dst_uv || pitch_dst_uv < (size_t)((dw + 1) / 2) * 2))
         return fail(VSTAB_ERR_INVALID, n + ": plane-wise output needs a chroma plane of 2*ceil(width/2) bytes per row");
     if (!ptr_aligned(uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, n + ": chroma plane must be 2-B aligned");
-    WarpArgs &a = c.w;
-    a.y = (const uint8_t *)y, a.uv = (const uint8_t *)uv, a.dst = (uint8_t *)dst, a.dst_uv = planar ? (uint8_t *)dst_uv : nullptr;
-    a.pitch_y = pitch_y, a.pitch_uv = pitch_uv, a.pitch_dst = pitch_dst, a.pitch_dst_uv = planar ? pitch_dst_uv : 0;
-    a.sw = sw, a.sh = sh, a.dw = dw, a.dh = dh;
-    MapParams &p = a.p;
-    p.icx = params[0], p.icy = params[1], p.ifx = params[2], p.ify = params[3];
-    p.ocx = params[4], p.ocy = params[5], p.ofx = params[6], p.ofy = params[7];
-    for (int i = 0; i < 9; i++) p.r[i] = params[8 + i];
-    c.p32 = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
+    fill_warp_args(c.w, y, pitch_y, uv, pitch_uv, sw, sh, params, dst, pitch_dst, planar ? dst_uv : nullptr, planar ? pitch_dst_uv : 0, dw, dh);
+    c.p32 = map_params32(params);
     return VSTAB_OK;
 }
 

@@ -4,11 +4,11 @@
 // an 8 x 8 footprint at (X - 3 .. X + 4, Y - 3 .. Y + 4), 64 integer weights from OpenCV's fixed-point table (vstab_lanczos4.hpp), each tap
 // outside the source the border value (BORDER_CONSTANT) or read at its borderInterpolate position, (sum + 2^14) >> 15 saturated to 0..255.
 //
-// The tile's phases, the remap and the entry points are the resamplers' common ones (vstab_resample.hpp, vstab_resample_host.hpp).  This
+// The tile's phases, the remap and the entry points are the resamplers' common ones (vstab_resample.hpp, vstab_warp_host.hpp).  This
 // unit holds the Lanczos table, the Lanczos blend, the constant border's tile (k_warp_lanczos4) and the kernels under their names.  The table is 128 KiB, four times the L1: the rows of an entry a
 // pixel reads depend on its fractions only, and neighbouring pixels share fy.
 #include "vstab_lanczos4.hpp"
-#include "vstab_resample_host.hpp"
+#include "vstab_warp_host.hpp"
 
 namespace vstab {
 

@@ -14,11 +14,8 @@
 // Direct gather, two output pixels per thread: this path is about the format, the 8-bit kernel carries the rate.
 #include <cstdlib>
 
-#include <hip/hip_ext.h>
-
 #include "vstab_device10.hpp"
-#include "vstab_internal.hpp"
-#include "vstab_warp_args.hpp"
+#include "vstab_warp_host.hpp"
 
 namespace vstab {
 
@@ -144,65 +141,77 @@ vstab_status preload_p010_kernels() {
 
 using namespace vstab;
 
+namespace {
+
+// The three P010 warps differ in what leaves them -- 16-bit BGR (vstab_warp_p010), P010 planes from the fused kernel (_planes), P010 planes
+// plane by plane (_planar) -- and in which of the shared checks they make.
+enum P010Out { P010_BGR16, P010_PLANES, P010_PLANAR };
+
+// Their arguments, checked in one order with each message under the entry point's own name n, into the kernel argument.  dst / dst_uv: the
+// output planes (BGR16: dst alone).  _planes leaves the source planes and the map mode to its tiled_ok (VSTAB_ERR_UNSUPPORTED, not _INVALID).
+vstab_status check_warp_p010(const std::string &n, P010Out out, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh,
+                             const float params[17], const float *rot_bottom, int map_mode, int blend, void *dst, size_t pitch_dst, void *dst_uv,
+                             size_t pitch_dst_uv, int dw, int dh, WarpArgs &a) {
+    const bool planes = out != P010_BGR16;
+    if (!y || !uv || !dst || (planes && !dst_uv) || !params) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
+    if (sw < (planes ? 8 : 4) || sh < 2 || (sw & 1) || (sh & 1) || dw <= 0 || dh <= 0 || sw > 32767 || sh > 32767 || dw > 32767 || dh > 32767)
+        return fail(VSTAB_ERR_INVALID, n + ": sizes must be in [1, 32767], source even and at least " + (planes ? "8 x 2" : "4 x 2"));
+    const bool src_bad = pitch_y < (size_t)sw * 2 || pitch_uv < (size_t)sw * 2 || pitch_y % 2 || pitch_uv % 4 || !ptr_aligned(y, 2) || !ptr_aligned(uv, 4);
+    const bool dst_bad = planes ? pitch_dst < (size_t)dw * 2 || pitch_dst % 2 || pitch_dst_uv < (size_t)((dw + 1) / 2) * 4 || pitch_dst_uv % 4 ||
+                                      !ptr_aligned(dst, 2) || !ptr_aligned(dst_uv, 4)
+                                : pitch_dst < (size_t)dw * 6 || pitch_dst % 2 || !ptr_aligned(dst, 2);
+    if (out == P010_BGR16 && (src_bad || dst_bad)) return fail(VSTAB_ERR_INVALID, n + ": bad pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
+    if (out == P010_PLANAR && src_bad)
+        return fail(VSTAB_ERR_INVALID, n + ": bad source pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
+    if (planes && dst_bad) return fail(VSTAB_ERR_INVALID, n + ": bad output pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
+    if (out != P010_PLANES && (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL))
+        return fail(VSTAB_ERR_INVALID, n + ": unknown map mode");
+    if (blend != VSTAB_BLEND_EXACT && blend != VSTAB_BLEND_FP16) return fail(VSTAB_ERR_INVALID, n + ": unknown blend");
+    if (out == P010_PLANAR) {
+        if (rot_bottom && !map_mode_fish_to_pinhole(map_mode))
+            return fail(VSTAB_ERR_INVALID, n + ": the per-row warp exists for the fisheye -> pinhole modes (0, 1, 5) only");
+        if (!staged_offsets32(pitch_y, pitch_uv, sh).rows) return fail(VSTAB_ERR_INVALID, n + ": source pitch too large");
+    }
+    fill_warp_args(a, y, pitch_y, uv, pitch_uv, sw, sh, params, dst, pitch_dst, planes ? dst_uv : nullptr, planes ? pitch_dst_uv : 0, dw, dh);
+    return VSTAB_OK;
+}
+
+// the planes and pitches of the source allow 16-byte staging loads
+bool source_16(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv) {
+    return ptr_aligned(y, 16) && ptr_aligned(uv, 16) && pitch_y % 16 == 0 && pitch_uv % 16 == 0;
+}
+
+}  // namespace
+
 // The same warp with P010 planes out, fused (FMT 3 of the tiled kernel): VSTAB_ERR_UNSUPPORTED when the planes do not allow the tiled
 // kernel (the caller then warps to 16-bit BGR and converts: vstab_pull_frame_p010 does).
 extern "C" vstab_status vstab_warp_p010_planes(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                                const float *rot_bottom, int map_mode, int blend, void *dst_y, size_t pitch_dst_y, void *dst_uv,
                                                size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    if (!y || !uv || !dst_y || !dst_uv || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planes: null pointer");
-    if (sw < 8 || sh < 2 || (sw & 1) || (sh & 1) || dw <= 0 || dh <= 0 || sw > 32767 || sh > 32767 || dw > 32767 || dh > 32767)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planes: sizes must be in [1, 32767], source even and at least 8 x 2");
-    if (pitch_dst_y < (size_t)dw * 2 || pitch_dst_y % 2 || pitch_dst_uv < (size_t)((dw + 1) / 2) * 4 || pitch_dst_uv % 4 ||
-        reinterpret_cast<uintptr_t>(dst_y) % 2 || reinterpret_cast<uintptr_t>(dst_uv) % 4)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planes: bad output pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
-    if (blend != VSTAB_BLEND_EXACT && blend != VSTAB_BLEND_FP16) return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planes: unknown blend");
-    const bool tiled_ok = (map_mode == VSTAB_MAP_CREATEMAP_CL || map_mode == VSTAB_MAP_FISH_TO_RECT || map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL) &&
-                          reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
-                          reinterpret_cast<uintptr_t>(uv) % 16 == 0 && pitch_y % 16 == 0 && pitch_uv % 16 == 0 && pitch_y >= (size_t)sw * 2 &&
-                          pitch_uv >= (size_t)sw * 2 && pitch_y < (1u << 24) && pitch_uv < (1u << 24) && (uint64_t)pitch_y * sh < (1ull << 32) &&
-                          (uint64_t)pitch_dst_y * dh < (1ull << 32);
-    if (!tiled_ok) return fail(VSTAB_ERR_UNSUPPORTED, "vstab_warp_p010_planes: needs 16-byte aligned source planes and a fisheye -> pinhole map");
-    // the staged loads form chroma row offsets in 32 bits: a chroma plane of 4 GiB or more is sampled from global memory (64-bit addresses)
-    const bool stage32 = (uint64_t)pitch_uv * (sh / 2) < (1ull << 32);
     WarpArgs wa;
-    wa.y = static_cast<const uint8_t *>(y), wa.uv = static_cast<const uint8_t *>(uv), wa.dst = static_cast<uint8_t *>(dst_y), wa.dst_uv = static_cast<uint8_t *>(dst_uv);
-    wa.pitch_y = pitch_y, wa.pitch_uv = pitch_uv, wa.pitch_dst = pitch_dst_y, wa.pitch_dst_uv = pitch_dst_uv;
-    wa.sw = sw, wa.sh = sh, wa.dw = dw, wa.dh = dh;
-    wa.p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7],
-            {params[8], params[9], params[10], params[11], params[12], params[13], params[14], params[15], params[16]}};
-    const bool vec = reinterpret_cast<uintptr_t>(dst_y) % 8 == 0 && reinterpret_cast<uintptr_t>(dst_uv) % 8 == 0 && pitch_dst_y % 8 == 0 && pitch_dst_uv % 8 == 0;
-    return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, true, stage32, vec, static_cast<hipStream_t>(stream));
+    const vstab_status st = check_warp_p010("vstab_warp_p010_planes", P010_PLANES, y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst_y,
+                                            pitch_dst_y, dst_uv, pitch_dst_uv, dw, dh, wa);
+    if (st != VSTAB_OK) return st;
+    const StagedOffsets32 off32 = staged_offsets32(pitch_y, pitch_uv, sh);
+    const bool tiled_ok = map_mode_fish_to_pinhole(map_mode) && source_16(y, pitch_y, uv, pitch_uv) && pitch_y >= (size_t)sw * 2 && pitch_uv >= (size_t)sw * 2 &&
+                          off32.rows && (uint64_t)pitch_dst_y * dh < (1ull << 32);
+    if (!tiled_ok) return fail(VSTAB_ERR_UNSUPPORTED, "vstab_warp_p010_planes: needs 16-byte aligned source planes and a fisheye -> pinhole map");
+    // a chroma plane of 4 GiB or more (staged_offsets32) is sampled from global memory (64-bit addresses)
+    const bool vec = ptr_aligned(dst_y, 8) && ptr_aligned(dst_uv, 8) && pitch_dst_y % 8 == 0 && pitch_dst_uv % 8 == 0;
+    return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, true, off32.chroma, vec, static_cast<hipStream_t>(stream));
 }
 
 // The plane-wise 10-bit warp (vstab_warp_planar.hip, DEPTH 10): P010 planes in and out, no colour conversion at all.
 extern "C" vstab_status vstab_warp_p010_planar(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                                const float *rot_bottom, int map_mode, int blend, void *dst_y, size_t pitch_dst_y, void *dst_uv,
                                                size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    if (!y || !uv || !dst_y || !dst_uv || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planar: null pointer");
-    if (sw < 8 || sh < 2 || (sw & 1) || (sh & 1) || dw <= 0 || dh <= 0 || sw > 32767 || sh > 32767 || dw > 32767 || dh > 32767)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planar: sizes must be in [1, 32767], source even and at least 8 x 2");
-    if (pitch_y < (size_t)sw * 2 || pitch_uv < (size_t)sw * 2 || pitch_y % 2 || pitch_uv % 4 || reinterpret_cast<uintptr_t>(y) % 2 ||
-        reinterpret_cast<uintptr_t>(uv) % 4)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planar: bad source pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
-    if (pitch_dst_y < (size_t)dw * 2 || pitch_dst_y % 2 || pitch_dst_uv < (size_t)((dw + 1) / 2) * 4 || pitch_dst_uv % 4 ||
-        reinterpret_cast<uintptr_t>(dst_y) % 2 || reinterpret_cast<uintptr_t>(dst_uv) % 4)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planar: bad output pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
-    if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planar: unknown map mode");
-    if (blend != VSTAB_BLEND_EXACT && blend != VSTAB_BLEND_FP16) return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planar: unknown blend");
-    if (rot_bottom && map_mode != VSTAB_MAP_CREATEMAP_CL && map_mode != VSTAB_MAP_FISH_TO_RECT && map_mode != VSTAB_MAP_CREATEMAP_CL_OPENCL)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planar: the per-row warp exists for the fisheye -> pinhole modes (0, 1, 5) only");
-    if (!(pitch_y < (1u << 24) && pitch_uv < (1u << 24) && (uint64_t)pitch_y * sh < (1ull << 32)))
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_p010_planar: source pitch too large");
     WarpArgs wa;
-    wa.y = static_cast<const uint8_t *>(y), wa.uv = static_cast<const uint8_t *>(uv), wa.dst = static_cast<uint8_t *>(dst_y), wa.dst_uv = static_cast<uint8_t *>(dst_uv);
-    wa.pitch_y = pitch_y, wa.pitch_uv = pitch_uv, wa.pitch_dst = pitch_dst_y, wa.pitch_dst_uv = pitch_dst_uv;
-    wa.sw = sw, wa.sh = sh, wa.dw = dw, wa.dh = dh;
-    wa.p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7],
-            {params[8], params[9], params[10], params[11], params[12], params[13], params[14], params[15], params[16]}};
-    // 16-byte staging loads; their chroma row offsets are 32-bit: a chroma plane of 4 GiB or more is sampled from global memory instead
-    const bool src16 = reinterpret_cast<uintptr_t>(y) % 16 == 0 && reinterpret_cast<uintptr_t>(uv) % 16 == 0 && pitch_y % 16 == 0 && pitch_uv % 16 == 0 &&
-                       (uint64_t)pitch_uv * (sh / 2) < (1ull << 32);
-    const bool dst16 = reinterpret_cast<uintptr_t>(dst_y) % 16 == 0 && reinterpret_cast<uintptr_t>(dst_uv) % 16 == 0 && pitch_dst_y % 16 == 0 && pitch_dst_uv % 16 == 0;
+    const vstab_status st = check_warp_p010("vstab_warp_p010_planar", P010_PLANAR, y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst_y,
+                                            pitch_dst_y, dst_uv, pitch_dst_uv, dw, dh, wa);
+    if (st != VSTAB_OK) return st;
+    // 16-byte staging loads; a chroma plane of 4 GiB or more (staged_offsets32) is sampled from global memory instead
+    const bool src16 = source_16(y, pitch_y, uv, pitch_uv) && staged_offsets32(pitch_y, pitch_uv, sh).chroma;
+    const bool dst16 = ptr_aligned(dst_y, 16) && ptr_aligned(dst_uv, 16) && pitch_dst_y % 16 == 0 && pitch_dst_uv % 16 == 0;
     return launch_warp_planar(wa, params, map_mode, 10, blend, src16, dst16, rot_bottom, static_cast<hipStream_t>(stream));
 }
 
@@ -211,7 +220,7 @@ extern "C" vstab_status vstab_cvt_bgr16_p010(const void *src_bgr16, size_t pitch
     if (!src_bgr16 || !dst_y || !dst_uv) return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr16_p010: null pointer");
     if (width <= 0 || height <= 0 || width > 32767 || height > 32767) return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr16_p010: sizes must be in [1, 32767]");
     if (pitch_src < (size_t)width * 6 || pitch_src % 2 || pitch_y < (size_t)width * 2 || pitch_y % 2 || pitch_uv < (size_t)((width + 1) / 2) * 4 || pitch_uv % 4 ||
-        reinterpret_cast<uintptr_t>(src_bgr16) % 2 || reinterpret_cast<uintptr_t>(dst_y) % 2 || reinterpret_cast<uintptr_t>(dst_uv) % 4)
+        !ptr_aligned(src_bgr16, 2) || !ptr_aligned(dst_y, 2) || !ptr_aligned(dst_uv, 4))
         return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr16_p010: bad pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
     hipLaunchKernelGGL(k_cvt_bgr10_p010, dim3(div_up(div_up(width, 2), 64), div_up(height, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t *>(src_bgr16), pitch_src, width, height, static_cast<uint8_t *>(dst_y), pitch_y, static_cast<uint8_t *>(dst_uv), pitch_uv);
@@ -221,61 +230,28 @@ extern "C" vstab_status vstab_cvt_bgr16_p010(const void *src_bgr16, size_t pitch
 
 extern "C" vstab_status vstab_warp_p010(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                         const float *rot_bottom, int map_mode, int blend, void *dst, size_t pitch_dst, int dw, int dh, void *stream) {
-    if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_p010: null pointer");
-    if (sw < 4 || sh < 2 || (sw & 1) || (sh & 1) || dw <= 0 || dh <= 0 || sw > 32767 || sh > 32767 || dw > 32767 || dh > 32767)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_p010: sizes must be in [1, 32767], source even and at least 4 x 2");
-    if (pitch_y < (size_t)sw * 2 || pitch_uv < (size_t)sw * 2 || pitch_dst < (size_t)dw * 6 || pitch_y % 2 || pitch_uv % 4 || pitch_dst % 2 ||
-        reinterpret_cast<uintptr_t>(y) % 2 || reinterpret_cast<uintptr_t>(uv) % 4 || reinterpret_cast<uintptr_t>(dst) % 2)
-        return fail(VSTAB_ERR_INVALID, "vstab_warp_p010: bad pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
-    if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_warp_p010: unknown map mode");
-    if (blend != VSTAB_BLEND_EXACT && blend != VSTAB_BLEND_FP16) return fail(VSTAB_ERR_INVALID, "vstab_warp_p010: unknown blend");
+    WarpArgs wa;
+    const vstab_status st = check_warp_p010("vstab_warp_p010", P010_BGR16, y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst, pitch_dst,
+                                            nullptr, 0, dw, dh, wa);
+    if (st != VSTAB_OK) return st;
     // The LDS-tiled kernel (the 8-bit hot kernel's structure with a 10:10:10 LDS pixel) serves the fisheye -> pinhole maps when
-    // the planes allow its 16-byte staging loads; everything else takes the direct-gather kernel below.  Same results.
-    const bool tiled_ok = (map_mode == VSTAB_MAP_CREATEMAP_CL || map_mode == VSTAB_MAP_FISH_TO_RECT || map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL) && sw >= 8 &&
-                          reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
-                          reinterpret_cast<uintptr_t>(uv) % 16 == 0 && pitch_y % 16 == 0 && pitch_uv % 16 == 0 && pitch_y < (1u << 24) &&
-                          pitch_uv < (1u << 24) && (uint64_t)pitch_y * sh < (1ull << 32) &&
-                          (uint64_t)pitch_uv * (sh / 2) < (1ull << 32);  // (the staged loads form chroma row offsets in 32 bits)
+    // the planes allow its 16-byte staging loads and 32-bit staged offsets; everything else takes the direct-gather kernel below.  Same results.
+    const bool tiled_ok = map_mode_fish_to_pinhole(map_mode) && sw >= 8 && source_16(y, pitch_y, uv, pitch_uv) && staged_offsets32(pitch_y, pitch_uv, sh).chroma;
     static const bool force_direct = getenv("VSTAB_P010_DIRECT") != nullptr;  // development: the direct-gather kernel for every call
-    if (tiled_ok && !force_direct) {
-        WarpArgs wa;
-        wa.y = static_cast<const uint8_t *>(y), wa.uv = static_cast<const uint8_t *>(uv), wa.dst = static_cast<uint8_t *>(dst), wa.dst_uv = nullptr;
-        wa.pitch_y = pitch_y, wa.pitch_uv = pitch_uv, wa.pitch_dst = pitch_dst, wa.pitch_dst_uv = 0;
-        wa.sw = sw, wa.sh = sh, wa.dw = dw, wa.dh = dh;
-        wa.p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7],
-                {params[8], params[9], params[10], params[11], params[12], params[13], params[14], params[15], params[16]}};
-        return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, false, true, true, static_cast<hipStream_t>(stream));
-    }
+    if (tiled_ok && !force_direct) return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, false, true, true, static_cast<hipStream_t>(stream));
     P010Args a;
-    a.y = static_cast<const uint8_t *>(y), a.uv = static_cast<const uint8_t *>(uv), a.dst = static_cast<uint16_t *>(dst);
+    a.y = wa.y, a.uv = wa.uv, a.dst = static_cast<uint16_t *>(dst);
     a.pitch_y = pitch_y, a.pitch_uv = pitch_uv, a.pitch_dst = pitch_dst;
     a.sw = sw, a.sh = sh, a.dw = dw, a.dh = dh;
-    a.p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7],
-           {params[8], params[9], params[10], params[11], params[12], params[13], params[14], params[15], params[16]}};
+    a.p = wa.p;
     a.rs = rot_bottom != nullptr;
-    for (int k = 0; k < 9; k++) a.rs_d[k] = rot_bottom ? rot_bottom[k] - params[8 + k] : 0.0f;
-    a.rs_den = (float)(dh > 1 ? dh - 1 : 1);
+    fill_rolling_shutter(a, params, rot_bottom, dh);
     const dim3 grid(div_up(dw, 64), div_up(dh, 8));  // 64 columns x 4 pairs of rows per workgroup
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const LaunchEvents ev = take_launch_events();  // a profiling caller's pair: the kernel's own start / end stamps
-#define VSTAB_LAUNCH_B(M, B)                                                                                   \
-    do {                                                                                                       \
-        if (ev.start) hipExtLaunchKernelGGL((k_warp_p010<M, B>), grid, dim3(256), 0, s, ev.start, ev.stop, 0, a); \
-        else hipLaunchKernelGGL((k_warp_p010<M, B>), grid, dim3(256), 0, s, a);                                  \
-    } while (0)
-#define VSTAB_LAUNCH(M)                                              \
-    if (blend == VSTAB_BLEND_FP16) VSTAB_LAUNCH_B(M, VSTAB_BLEND_FP16); \
-    else VSTAB_LAUNCH_B(M, VSTAB_BLEND_EXACT)
-    switch (map_mode) {
-        case VSTAB_MAP_CREATEMAP_CL: VSTAB_LAUNCH(MAP_CREATEMAP_CL); break;
-        case VSTAB_MAP_FISH_TO_RECT: VSTAB_LAUNCH(MAP_FISH_TO_RECT); break;
-        case VSTAB_MAP_FISH_TO_FISH: VSTAB_LAUNCH(MAP_FISH_TO_FISH); break;
-        case VSTAB_MAP_RECT_TO_RECT: VSTAB_LAUNCH(MAP_RECT_TO_RECT); break;
-        case VSTAB_MAP_CREATEMAP_CL_OPENCL: VSTAB_LAUNCH(MAP_CREATEMAP_CL_OPENCL); break;
-        default: VSTAB_LAUNCH(MAP_RECT_TO_FISH); break;
-    }
-#undef VSTAB_LAUNCH
-#undef VSTAB_LAUNCH_B
+    with_map_mode(map_mode, [&](auto mode) {  // (the rotation per row is the kernel's run-time a.rs: no MAP_RS_* forms here)
+        with_either<VSTAB_BLEND_FP16, VSTAB_BLEND_EXACT>(blend == VSTAB_BLEND_FP16, [&](auto blend_c) {
+            launch_kernel(k_warp_p010<decltype(mode)::value, decltype(blend_c)::value>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+        });
+    });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }

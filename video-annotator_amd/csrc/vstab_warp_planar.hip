@@ -22,12 +22,8 @@
 #include <cmath>
 #include <cstdlib>
 
-#include <hip/hip_ext.h>
-
-#include "vstab_device.hpp"
 #include "vstab_device10.hpp"
-#include "vstab_internal.hpp"
-#include "vstab_warp_args.hpp"
+#include "vstab_warp_host.hpp"
 #include "vstab_warp_tile.hpp"
 
 namespace vstab {
@@ -192,8 +188,8 @@ __device__ __forceinline__ bool warp_tile_planar(const FusedArgs &ta, uint32_t *
             const int colp = bx0 + BW * col;  // first source sample of the lane's chunk within a row (a chroma row: the same bytes per luma column)
             const int sw_al = a.sw & ~(BW - 1);
             const bool col_ok = (uint32_t)colp < (uint32_t)sw_al;
-            // < 2^24, pitch_y * sh and pitch_uv * sh / 2 < 2^32: src_vec_ok is only set under those host checks (warp_impl in vstab_warp.hip,
-            // vstab_warp_p010_planar), so the 32-bit row offsets below cannot wrap
+            // src_vec_ok is only set under staged_offsets32(...).chroma (vstab_warp_host.hpp: pitches < 2^24, pitch_y * sh and pitch_uv * sh / 2
+            // < 2^32), so the 32-bit row offsets below cannot wrap
             const uint32_t pitch_y = (uint32_t)a.pitch_y, pitch_uv = (uint32_t)a.pitch_uv;
             const uint32_t lane_y = (uint32_t)r0 * pitch_y + (uint32_t)(colp * BPS), lane_c = (uint32_t)r0 * pitch_uv + (uint32_t)(colp * BPS);
             const int hc = hb >> 1;
@@ -511,15 +507,8 @@ __global__ void __launch_bounds__(256, RWB == 8 ? 5 : 6) k_warp_planar(FusedArgs
 vstab_status launch_warp_planar(const WarpArgs &a, const float params[17], int map_mode, int depth, int blend, bool src_vec_ok, bool dst_vec_ok,
                                 const float *rot_bottom, hipStream_t st) {
     FusedArgs ta;
-    ta.w = a;
-    ta.p32 = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
-    ta.src_vec_ok = src_vec_ok, ta.dst_vec_ok = dst_vec_ok;
-    ta.qmap = nullptr, ta.qpitch = 0;
-    for (int k = 0; k < 9; k++) ta.rs_d[k] = rot_bottom ? rot_bottom[k] - params[8 + k] : 0.0f;
-    ta.rs_den = (float)(a.dh > 1 ? a.dh - 1 : 1);
-    if (rot_bottom) map_mode = map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL ? (int)MAP_RS_CREATEMAP_CL_OPENCL : map_mode + (int)MAP_RS_CREATEMAP_CL;
+    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, nullptr, 0, rot_bottom);
 #ifdef VSTAB_DEV
-    ta.timing = nullptr, ta.lds_pad = 0;
     ta.ablate = getenv("VSTAB_ABLATE") ? atoi(getenv("VSTAB_ABLATE")) : 0;
 #endif
     // 64 x 32 tiles; LDS per workgroup: header + scratch + 1.5 bytes (3 at 10 bits) per pixel of the box.  24 KB (8-bit) lets six
@@ -544,36 +533,17 @@ vstab_status launch_warp_planar(const WarpArgs &a, const float params[17], int m
     const dim3 grid(tile_schedule(ta, rwb, lds_kb, tail_rounds));
     const size_t lds_bytes = (size_t)lds_kb * 1024;
     ta.lds_capacity_px = (int)((lds_bytes - 32 - 4 * 768 * (size_t)bps) * 2 / (3 * (size_t)bps));
-    const LaunchEvents ev = take_launch_events();
-#define VSTAB_LAUNCHP(R, M, D, B)                                                                                                 \
-    do {                                                                                                                          \
-        if (ev.start) hipExtLaunchKernelGGL((k_warp_planar<R, M, D, B>), grid, dim3(256), lds_bytes, st, ev.start, ev.stop, 0, ta); \
-        else hipLaunchKernelGGL((k_warp_planar<R, M, D, B>), grid, dim3(256), lds_bytes, st, ta);                                  \
-    } while (0)
-#define VSTAB_LAUNCHP_M(M)                                                               \
-    do {                                                                                 \
-        if (depth == 10) {                                                               \
-            if (blend == VSTAB_BLEND_FP16) {                                             \
-                if (rwb == 8) VSTAB_LAUNCHP(8, M, 10, VSTAB_BLEND_FP16);                 \
-                else VSTAB_LAUNCHP(4, M, 10, VSTAB_BLEND_FP16);                          \
-            } else if (rwb == 8) VSTAB_LAUNCHP(8, M, 10, VSTAB_BLEND_EXACT);             \
-            else VSTAB_LAUNCHP(4, M, 10, VSTAB_BLEND_EXACT);                             \
-        } else if (rwb == 8) VSTAB_LAUNCHP(8, M, 8, 0);                                  \
-        else VSTAB_LAUNCHP(4, M, 8, 0);                                                  \
-    } while (0)
-    switch (map_mode) {
-        case VSTAB_MAP_CREATEMAP_CL: VSTAB_LAUNCHP_M(MAP_CREATEMAP_CL); break;
-        case VSTAB_MAP_FISH_TO_RECT: VSTAB_LAUNCHP_M(MAP_FISH_TO_RECT); break;
-        case VSTAB_MAP_FISH_TO_FISH: VSTAB_LAUNCHP_M(MAP_FISH_TO_FISH); break;
-        case VSTAB_MAP_RECT_TO_RECT: VSTAB_LAUNCHP_M(MAP_RECT_TO_RECT); break;
-        case VSTAB_MAP_RECT_TO_FISH: VSTAB_LAUNCHP_M(MAP_RECT_TO_FISH); break;
-        case VSTAB_MAP_CREATEMAP_CL_OPENCL: VSTAB_LAUNCHP_M(MAP_CREATEMAP_CL_OPENCL); break;
-        case MAP_RS_CREATEMAP_CL: VSTAB_LAUNCHP_M(MAP_RS_CREATEMAP_CL); break;
-        case MAP_RS_CREATEMAP_CL_OPENCL: VSTAB_LAUNCHP_M(MAP_RS_CREATEMAP_CL_OPENCL); break;
-        default: VSTAB_LAUNCHP_M(MAP_RS_FISH_TO_RECT); break;
-    }
-#undef VSTAB_LAUNCHP_M
-#undef VSTAB_LAUNCHP
+    with_map_mode(map_mode, rot_bottom != nullptr, [&](auto mode) {
+        with_either<10, 8>(depth == 10, [&](auto depth_c) {
+            with_either<VSTAB_BLEND_FP16, VSTAB_BLEND_EXACT>(depth == 10 && blend == VSTAB_BLEND_FP16, [&](auto blend_c) {
+                with_either<8, 4>(rwb == 8, [&](auto rows) {
+                    constexpr int DEPTH = decltype(depth_c)::value, BLEND = decltype(blend_c)::value;
+                    if constexpr (DEPTH == 10 || BLEND == VSTAB_BLEND_EXACT)  // 8-bit samples have the one, exact blend
+                        launch_kernel(k_warp_planar<decltype(rows)::value, decltype(mode)::value, DEPTH, BLEND>, grid, dim3(256), lds_bytes, st, ta);
+                });
+            });
+        });
+    });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }
