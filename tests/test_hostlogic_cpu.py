@@ -1,7 +1,7 @@
 """CPU tests of the pipeline's host-side bookkeeping with hand-made buffers, through the library's vstabx_* test hooks
 (video-annotator_amd/csrc/vstab_hostlogic.hpp): the parser of the tracker's result records (what Tracker::track_wait runs on
 the records k_lk_track writes into mapped host memory) and the DMA-BUF import cache (resolve_dmabuf).  No device needed -- these
-are the parts of vstab_pipeline.cpp that the sanitizer build (tools/run_sanitized_tests.sh) could not reach otherwise."""
+are the parts of the pipeline's host code that the sanitizer build (tools/run_sanitized_tests.sh) could not reach otherwise."""
 import ctypes
 
 import numpy as np

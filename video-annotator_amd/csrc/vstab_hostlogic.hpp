@@ -1,6 +1,7 @@
 // vstab_hostlogic.hpp -- host-side bookkeeping of the pipeline that does not need a device: the parser of the tracker's result
-// records and the import cache of DMA-BUF objects.  Kept apart from vstab_pipeline.cpp so that the CPU test suite (and its
-// sanitizer build, tools/run_sanitized_tests.sh) can drive them with hand-made buffers through the vstabx_* test hooks.
+// records and the import cache of DMA-BUF objects.  Kept apart from the units that use them (vstab_track_host.cpp, vstab_pipeline.cpp) so
+// that the CPU test suite (and its sanitizer build, tools/run_sanitized_tests.sh) can drive them with hand-made buffers through the
+// vstabx_* test hooks (vstab_testhooks.cpp).
 #pragma once
 #include <cstdint>
 #include <cstring>

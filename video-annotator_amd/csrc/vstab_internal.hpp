@@ -58,4 +58,51 @@ vstab_status pack_p010_planes(const void *y, size_t pitch_y, const void *uv, siz
 // vstab_pack_nv12 with an optional event that completes with the copy kernel (bound to the launch: no marker packet on the stream)
 vstab_status pack_nv12_planes(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int width, int height, void *dst, void *stream, hipEvent_t done);
 
+#define VSTAB_TRY(expr)                   \
+    do {                                  \
+        vstab_status st_ = (expr);        \
+        if (st_ != VSTAB_OK) return st_;  \
+    } while (0)
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t n = 0;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr, n = 0;
+    }
+    vstab_status ensure(size_t bytes) {
+        if (bytes <= n) return VSTAB_OK;
+        release();
+        if (hipMalloc(&p, bytes) != hipSuccess) return fail(VSTAB_ERR_NOMEM, "hipMalloc failed");
+        n = bytes;
+        return VSTAB_OK;
+    }
+    template <typename T>
+    T *as() const { return static_cast<T *>(p); }
+};
+
+struct PinnedBuf {  // host memory the device can read and write directly (mapped, coherent)
+    void *p = nullptr;
+    size_t n = 0;
+    void *dev() const {
+        void *d = nullptr;
+        return hipHostGetDevicePointer(&d, p, 0) == hipSuccess ? d : nullptr;
+    }
+    ~PinnedBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+    vstab_status ensure(size_t bytes) {
+        if (bytes <= n) return VSTAB_OK;
+        if (p) (void)hipHostFree(p);
+        p = nullptr, n = 0;
+        if (hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess) return fail(VSTAB_ERR_NOMEM, "hipHostMalloc failed");
+        n = bytes;
+        return VSTAB_OK;
+    }
+    template <typename T>
+    T *as() const { return static_cast<T *>(p); }
+};
+
 }  // namespace vstab

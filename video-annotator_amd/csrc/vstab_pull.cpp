@@ -1,0 +1,325 @@
+// vstab_pull.cpp -- FrameSourceWarp::pull_frame (:452-476) behind the pull entry points of the C ABI, as its seven steps, and
+// vstab_set_border_mode / _ex, whose mode those steps read.
+#include <cmath>
+
+#include "vstab_pipeline.hpp"
+
+constexpr int OUT_BGR16 = 16;        // internal: the 10-bit path's output (vstab_pull_frame_bgr16)
+constexpr int OUT_P010 = 17;         // internal: the 10-bit path's frame as P010 planes (vstab_pull_frame_p010)
+constexpr int OUT_P010_PLANAR = 18;  // internal: the 10-bit frame warped plane by plane (vstab_pull_frame_p010_planar)
+static inline bool out_is_10bit(int f) { return f == OUT_BGR16 || f == OUT_P010 || f == OUT_P010_PLANAR; }
+static inline bool out_has_chroma_plane(int f) { return f == VSTAB_OUT_NV12 || f == VSTAB_OUT_NV12_PLANAR || f == OUT_P010 || f == OUT_P010_PLANAR; }
+
+struct Pull {  // one pull on its way through the steps: what the caller asked for and the border mode in force, then what the steps add
+    const int out_format;
+    void *const dst, *const dst_uv;
+    const size_t pitch_dst, pitch_dst_uv;
+    const int border_mode;
+    int slot = -1;
+    Mat3 warp_R;
+    float p[17], p_bottom[17];
+    const float *rot_bottom = nullptr;  // the last row's rotation (in p_bottom) when the frame carries a read-out rotation
+    bool cached = false;
+};
+
+// 1. the formats this handle does not emit
+static vstab_status refuse_formats(const vstab_handle *H, const Pull &P) {
+    if ((H->cfg.pixel_depth == 10) != out_is_10bit(P.out_format))
+        return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: a pixel_depth 10 handle emits through vstab_pull_frame_bgr16, an 8-bit handle through the others");
+    if (P.out_format == VSTAB_OUT_BGR8 || P.out_format == VSTAB_OUT_NV12_PLANAR) return VSTAB_OK;
+    static const char served[] = " emits 8-bit BGR or plane-wise NV12 frames (vstab_pull_frame / _frames / _host / vstab_peek_frame / vstab_pull_frame_nv12_planar), not NV12 through BGR";
+    // (refused before any frame is dequeued: the caller can pull the same frame in a format the cubic warp serves)
+    if (H->cfg.resample != VSTAB_RESAMPLE_DEFAULT) return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: ") + resample_name(H->cfg.resample) + served);
+    // (the mode in force for this pull: a border warp serves the same two formats as the cubic one, refused before any frame is dequeued)
+    if (P.border_mode != VSTAB_BORDER_CONSTANT) return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: a border mode other than VSTAB_BORDER_CONSTANT") + served);
+    return VSTAB_OK;
+}
+
+// 2. consume frames until the look-ahead window of the next one to emit is complete, or upstream has ended
+static vstab_status advance_until_due(vstab_handle *H) {
+    while (H->queue.size() <= (size_t)H->cfg.smooth_radius) {  // :453
+        if (!H->have_inflight && !H->have_ready && !H->have_estimating && H->prefetched.empty() && H->src_eof) {  // every frame read has been queued
+            if (H->src_error) return fail(VSTAB_ERR_SOURCE, "upstream pull failed with " + std::to_string(H->src_error));
+            // :456-461 pretend the camera kept its last orientation (once per call while draining)
+            if (H->sg) H->sg->add(H->measured);
+            break;
+        }
+        // 1. LK results of the frame in flight -> surviving corners
+        if (H->have_inflight) VSTAB_TRY(finish_wait(H));
+        // 2. the rotation estimate that was started a frame ago (it ran beside everything since) -> queue its frame; then
+        //    the frame just read starts its estimate on the worker thread
+        finish_estimate(H);
+        post_estimate(H);
+        // 3. key-frame rule + LK launch for the oldest prefetched frame, and the launches that can be enqueued ahead of it
+        if (H->prefetched.empty() && !H->src_eof) {
+            const vstab_status st = prefetch_next(H);
+            if (st != VSTAB_OK && st != VSTAB_EOF) return st;
+        }
+        if (!H->prefetched.empty() && !H->have_inflight) {
+            const size_t queued = H->queue.size();
+            VSTAB_TRY(launch_tracking(H));
+            if (H->queue.size() != queued) continue;  // (tracking off: the frame is queued at once) re-check :453 before :456
+        }
+        // 4. read ahead: pull + copy + pyramid of the following frames (prefetch stream)
+        while ((int)H->prefetched.size() < H->prefetch_depth && !H->src_eof) {
+            const vstab_status st = prefetch_next(H);
+            if (st != VSTAB_OK && st != VSTAB_EOF) return st;
+        }
+    }
+    return VSTAB_OK;
+}
+
+// 3. the frame at the head of the queue: its stabilising rotation and the parameter sets of its warp
+static void smooth(vstab_handle *H, Pull &P) {
+    P.slot = H->queue.front().first;
+    const Mat3 measured = H->queue.front().second;
+    H->queue.pop_front();
+    Mat3 corrected;
+    {
+        HostStage hs(&H->prof.host_smooth_ms);
+        if (H->cfg.smoother == VSTAB_SMOOTHER_SG)
+            corrected = H->sg->filter();  // :471
+        else if (H->cfg.smoother == VSTAB_SMOOTHER_KALMAN)
+            corrected = H->kalman.update(measured);
+        else if (H->cfg.smoother == VSTAB_SMOOTHER_FIXED)
+            corrected = Mat3::identity();  // hold the orientation of the first frame
+        else
+            corrected = measured;
+        const Mat3 correction = corrected * measured.inv();  // :472
+        P.warp_R = correction.inv();                         // :475
+    }
+    H->warp_log.push_back(P.warp_R);
+    if (H->warp_log.size() > vstab_handle::LOG_KEEP) H->warp_log.pop_front(), H->warp_log_base++;
+    H->prof.frames_emitted++, H->prof.warp_launches++;
+    map_params(H->Kin, H->Kout, P.warp_R, P.p);
+    const vstab_handle::Slot &S = H->slots[P.slot];
+    // rolling shutter: the camera kept turning while the rows were read out; the last row is warped with the stabilising
+    // rotation of the orientation it was exposed at (measured' = readout * measured  =>  W' = readout * W)
+    if (S.have_readout) map_params(H->Kin, H->Kout, S.readout * P.warp_R, P.p_bottom), P.rot_bottom = P.p_bottom + 8;
+}
+
+// 4. whether the quantised map of an earlier frame serves this one (written down now if this is the second frame in a row with its parameters)
+static vstab_status choose_cached_map(vstab_handle *H, Pull &P) {
+    // (the quantised map holds no chroma positions: the plane-wise warp always evaluates its map)
+    // (nor do the cubic, Lanczos and border warps read it, with or without a border mode: they evaluate the map of every frame; the cached
+    //  map's kernel has the constant border built in)
+    if (!H->map_cache || H->cfg.resample != VSTAB_RESAMPLE_DEFAULT || P.border_mode != VSTAB_BORDER_CONSTANT || P.rot_bottom || out_is_10bit(P.out_format) ||
+        P.out_format == VSTAB_OUT_NV12_PLANAR)
+        return VSTAB_OK;
+    if (H->qmap_valid && std::memcmp(P.p, H->qmap_params, sizeof(P.p)) == 0) {
+        P.cached = true;
+    } else if (H->have_last_params && std::memcmp(P.p, H->last_params, sizeof(P.p)) == 0) {
+        // second frame in a row with these parameters: write the map down now (same stream, ahead of the warp)
+        VSTAB_TRY(H->qmap.ensure(vstab_quantised_map_bytes(H->ow, H->oh)));
+        VSTAB_TRY(vstab_quantised_map(H->qmap.p, H->ow, H->oh, P.p, H->map_mode, H->stream));
+        std::memcpy(H->qmap_params, P.p, sizeof(P.p));
+        H->qmap_valid = P.cached = true;
+    }
+    std::memcpy(H->last_params, P.p, sizeof(P.p));
+    H->have_last_params = true;
+    H->warps_from_cache += P.cached;
+    return VSTAB_OK;
+}
+
+// (every warp launcher takes the profiler's event pair; a request refused by launch_warp itself launches nothing, so the pair armed by
+//  GpuStage is taken back here instead of staying pending for somebody else's launch)
+static vstab_status refuse_launch(const std::string &msg) {
+    (void)take_launch_events();
+    return fail(VSTAB_ERR_INVALID, msg);
+}
+
+// 5. the warp kernel for this (out_format, resample, border, interpolation, readout, cached)
+static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
+    const vstab_handle::Slot &S = H->slots[P.slot];
+    const int out_format = P.out_format, w = H->w, h = H->h, ow = H->ow, oh = H->oh, mode = H->map_mode;
+    const bool border = P.border_mode != VSTAB_BORDER_CONSTANT;
+    const bool resampled = H->cfg.resample != VSTAB_RESAMPLE_DEFAULT, lanczos4 = H->cfg.resample == VSTAB_RESAMPLE_LANCZOS4;  // (else CUBIC: vstab_create)
+    // the profiling events bracket the launch call and nothing else, so the interval is the kernel
+    // (plus its dispatch), not host work between two API calls
+    GpuStage gs(H, vstab_handle::ST_WARP);
+#ifdef VSTAB_DEV
+    // development builds: VSTAB_DEV_SKIP_WARP=1 launches no warp at all, so that tools/lk_timeline.py sees the tracker chain with
+    // nothing but the pyramid kernels beside it (how much of an iteration is the chain, how much is contention with the warp)
+    static const bool skip_warp = getenv("VSTAB_DEV_SKIP_WARP") != nullptr;
+    if (skip_warp) {
+        (void)take_launch_events();
+        return VSTAB_OK;
+    }
+#endif
+    if (out_format == OUT_BGR16)
+        return vstab_warp_p010(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, P.dst, P.pitch_dst, ow, oh, H->stream);
+    if (out_format == OUT_P010_PLANAR)
+        return vstab_warp_p010_planar(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, P.dst, P.pitch_dst, P.dst_uv,
+                                      P.pitch_dst_uv, ow, oh, H->stream);
+    if (out_format == OUT_P010) {
+        vstab_status st = vstab_warp_p010_planes(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, P.dst, P.pitch_dst,
+                                                 P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+        if (st == VSTAB_ERR_UNSUPPORTED) {
+            const size_t bpitch = ((size_t)ow * 6 + 255) & ~(size_t)255;
+            st = H->bgr16_out.ensure(bpitch * oh);
+            if (st == VSTAB_OK)
+                st = vstab_warp_p010(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, H->bgr16_out.p, bpitch, ow, oh, H->stream);
+            if (st == VSTAB_OK) st = vstab_cvt_bgr16_p010(H->bgr16_out.p, bpitch, ow, oh, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, H->stream);
+        }
+        return st;
+    }
+    if (border && !resampled)
+        return vstab_warp_nv12_border(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.border_mode, P.dst, P.pitch_dst, P.dst_uv,
+                                      P.pitch_dst_uv, ow, oh, H->stream);
+    if (resampled) {  // the cubic and Lanczos warps: the same two signatures, without and with a border mode
+        // (a frame that carries a read-out rotation can never be served: it is consumed, as INTER_NEAREST consumes it below, and the
+        //  profiler's event pair is taken back; the output format was checked on entry)
+        if (P.rot_bottom) return refuse_launch(std::string(resample_name(H->cfg.resample)) + " warps frames without a read-out rotation (vstab_frame.readout_rotation)");
+        const auto plain = lanczos4 ? vstab_warp_nv12_lanczos4 : vstab_warp_nv12_cubic;
+        const auto bordered = lanczos4 ? vstab_warp_nv12_lanczos4_border : vstab_warp_nv12_cubic_border;
+        if (border)
+            return bordered(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, out_format, P.border_mode, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+        return plain(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+    }
+    if (H->cfg.interpolation == 0) {
+        if (out_format != VSTAB_OUT_BGR8 || P.rot_bottom) return refuse_launch("INTER_NEAREST emits 8-bit BGR frames without a read-out rotation");
+        return vstab_warp_nv12_nearest_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, P.dst, P.pitch_dst, ow, oh, H->stream);
+    }
+    if (P.cached)
+        return vstab_warp_nv12_mapped(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, H->qmap.p, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+    if (P.rot_bottom)
+        return vstab_warp_nv12_rs(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh,
+                                  H->stream);
+    return vstab_warp_nv12_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+}
+
+// 6. vstab_config.debug: a marker on every feature tracked into the frame (marker_pts holds MARKER_SETS rotating sets of MARKER_CAP centres)
+constexpr int MARKER_SETS = 16, MARKER_CAP = 256;
+static vstab_status draw_markers(vstab_handle *H, const Pull &P) {
+    vstab_handle::Slot &S = H->slots[P.slot];
+    const Mat3 &warp_R = P.warp_R;
+    // where the warp sends each tracked feature: input pixel -> ray -> R^T -> output projection (the inverse of the map)
+    int *host = H->marker_pts.as<int>() + 2 * MARKER_CAP * (H->marker_set % MARKER_SETS);
+    int *dev = static_cast<int *>(H->marker_pts.dev()) + 2 * MARKER_CAP * (H->marker_set % MARKER_SETS);
+    H->marker_set++;
+    const bool out_fish = H->map_mode == VSTAB_MAP_FISH_TO_FISH || H->map_mode == VSTAB_MAP_RECT_TO_FISH;
+    int n = 0;
+    for (size_t i = 0; i + 1 < S.feats.size() && n < MARKER_CAP; i += 2) {
+        const double a = (S.feats[i] - H->Kin(0, 2)) / H->Kin(0, 0), b = (S.feats[i + 1] - H->Kin(1, 2)) / H->Kin(1, 1);
+        double rx = a, ry = b, rz = 1;
+        if (H->in_fish) {
+            const double th = std::hypot(a, b), sc = th > 0 ? std::sin(th) / th : 1.0;
+            rx = a * sc, ry = b * sc, rz = std::cos(th);
+        }
+        const double ox = warp_R(0, 0) * rx + warp_R(1, 0) * ry + warp_R(2, 0) * rz, oy = warp_R(0, 1) * rx + warp_R(1, 1) * ry + warp_R(2, 1) * rz,
+                     oz = warp_R(0, 2) * rx + warp_R(1, 2) * ry + warp_R(2, 2) * rz;
+        if (!(oz > 0)) continue;
+        double u = ox / oz, v = oy / oz;
+        if (out_fish) {
+            const double r = std::hypot(ox, oy), th = std::atan2(r, oz), sc = r > 0 ? th / r : 1.0;
+            u = ox * sc, v = oy * sc;
+        }
+        host[2 * n] = (int)std::nearbyint(H->Kout(0, 2) + u * H->Kout(0, 0)), host[2 * n + 1] = (int)std::nearbyint(H->Kout(1, 2) + v * H->Kout(1, 1));
+        n++;
+    }
+    S.feats.clear();
+    if (P.out_format == VSTAB_OUT_NV12 || P.out_format == VSTAB_OUT_NV12_PLANAR)
+        return vstab_draw_markers(P.dst, P.pitch_dst, H->ow, H->oh, 1, dev, n, 3, 235u, H->stream);
+    return vstab_draw_markers(P.dst, P.pitch_dst, H->ow, H->oh, 3, dev, n, 3, 0x0000FF00u, H->stream);
+}
+
+// 7. the slot goes back to the ring, behind the warp that read it
+static vstab_status release_slot(vstab_handle *H, int slot) {
+    vstab_handle::Slot &S = H->slots[slot];
+    S.queued = false, S.freed_at = ++H->free_counter;
+    if (!S.borrowed) {
+        S.warp_pending = true, S.warped = -1;
+        H->uncovered.push_back(slot);  // the next copy into this slot waits for an event recorded behind this warp
+        if ((int)H->uncovered.size() >= vstab_handle::WARP_EVENT_STRIDE) VSTAB_TRY(H->cover_warps());
+    } else if (!H->borrows.empty()) {
+        for (vstab_handle::PendingBorrow &b : H->borrows)
+            if (b.serial == S.ingest_serial) {
+                b.warp_enqueued = true;
+                if (++H->uncovered_borrows >= vstab_handle::WARP_EVENT_STRIDE) VSTAB_TRY(H->cover_warps());
+                break;
+            }
+    }
+    return VSTAB_OK;
+}
+
+// FrameSourceWarp::pull_frame, :452-476
+static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv) {
+    if (!H || !dst || (out_has_chroma_plane(out_format) && !dst_uv)) return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: null argument");
+    Pull P{out_format, dst, dst_uv, pitch_dst, pitch_dst_uv, H->border_mode};
+    VSTAB_TRY(refuse_formats(H, P));
+    HT t_total(HostTimers::TOTAL);
+    VSTAB_TRY(advance_until_due(H));
+    if (H->queue.empty()) return VSTAB_EOF;  // :465-467
+    smooth(H, P);
+    VSTAB_TRY(choose_cached_map(H, P));
+    HT t_warp(HostTimers::WARP);
+    VSTAB_TRY(vstab_handle::wait_if_pending(H->stream, H->slots[P.slot].ingested));  // the slot was filled on the prefetch stream (long ago, as a rule)
+    vstab_status st = launch_warp(H, P);
+    if (st == VSTAB_OK && H->cfg.debug && !H->slots[P.slot].feats.empty() && !out_is_10bit(out_format)) {  // (markers are drawn into 8-bit outputs)
+        VSTAB_TRY(H->marker_pts.ensure(sizeof(int) * 2 * MARKER_CAP * MARKER_SETS));
+        st = draw_markers(H, P);
+    }
+    VSTAB_TRY(release_slot(H, P.slot));
+    return st;
+}
+
+// vstab_set_border_mode / _ex: `resamplers`: whether a CUBIC or LANCZOS4 handle is served; `served`: how the refusal names what is
+static vstab_status set_border_mode(vstab_handle *h, int border_mode, const char *fn, bool resamplers, const char *served) {
+    if (!h) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!border_mode_valid(border_mode))
+        return fail(VSTAB_ERR_INVALID, std::string(fn) + ": border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)");
+    if (border_mode != VSTAB_BORDER_CONSTANT && (h->cfg.pixel_depth == 10 || h->cfg.interpolation == 0 || (!resamplers && h->cfg.resample != VSTAB_RESAMPLE_DEFAULT)))
+        return fail(VSTAB_ERR_UNSUPPORTED, std::string(fn) + ": border modes other than VSTAB_BORDER_CONSTANT are served for 8-bit pixels with " + served);
+    h->border_mode = border_mode;
+    return VSTAB_OK;
+}
+
+extern "C" {
+
+vstab_status vstab_pull_frame(vstab_handle *h, void *dst, size_t pitch_dst) { return pull_frame_impl(h, VSTAB_OUT_BGR8, dst, pitch_dst, nullptr, 0); }
+
+vstab_status vstab_pull_frames(vstab_handle *h, int n, void *const *dst, const size_t *pitch_dst, int n_dst, int first, int *n_done) {
+    if (n_done) *n_done = 0;
+    if (!h || !dst || !pitch_dst || n < 0 || n_dst <= 0 || first < 0) return fail(VSTAB_ERR_INVALID, "vstab_pull_frames: bad argument");
+    for (int i = 0; i < n; i++) {
+        const int k = (int)(((long)first + i) % n_dst);
+        const vstab_status st = pull_frame_impl(h, VSTAB_OUT_BGR8, dst[k], pitch_dst[k], nullptr, 0);
+        if (st != VSTAB_OK) return st;
+        if (n_done) *n_done = i + 1;
+    }
+    return VSTAB_OK;
+}
+
+vstab_status vstab_pull_frame_host(vstab_handle *h, void *dst, size_t pitch_dst) {
+    if (!h || !dst || pitch_dst < (size_t)h->ow * 3) return fail(VSTAB_ERR_INVALID, "vstab_pull_frame_host: bad argument");
+    const size_t dpitch = ((size_t)h->ow * 3 + 255) & ~(size_t)255;
+    VSTAB_TRY(h->host_out.ensure(dpitch * h->oh));
+    const vstab_status st = pull_frame_impl(h, VSTAB_OUT_BGR8, h->host_out.p, dpitch, nullptr, 0);
+    if (st != VSTAB_OK) return st;
+    VSTAB_HIP_TRY(hipMemcpy2DAsync(dst, pitch_dst, h->host_out.p, dpitch, (size_t)h->ow * 3, h->oh, hipMemcpyDeviceToHost, h->stream));
+    VSTAB_HIP_TRY(hipStreamSynchronize(h->stream));
+    return VSTAB_OK;
+}
+
+vstab_status vstab_pull_frame_bgr16(vstab_handle *h, void *dst, size_t pitch_dst) { return pull_frame_impl(h, OUT_BGR16, dst, pitch_dst, nullptr, 0); }
+
+vstab_status vstab_pull_frame_p010(vstab_handle *h, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv) {
+    if (!h || !dst_y || !dst_uv) return fail(VSTAB_ERR_INVALID, "vstab_pull_frame_p010: null argument");
+    // the warp writes the planes itself (OUT_P010) where the frame's planes allow the tiled kernel; pull_frame_impl falls back
+    // to a 16-bit BGR buffer of the handle + vstab_cvt_bgr16_p010 otherwise
+    return pull_frame_impl(h, OUT_P010, dst_y, pitch_y, dst_uv, pitch_uv);
+}
+
+vstab_status vstab_pull_frame_nv12(vstab_handle *h, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv) { return pull_frame_impl(h, VSTAB_OUT_NV12, dst_y, pitch_y, dst_uv, pitch_uv); }
+
+vstab_status vstab_pull_frame_nv12_planar(vstab_handle *h, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv) { return pull_frame_impl(h, VSTAB_OUT_NV12_PLANAR, dst_y, pitch_y, dst_uv, pitch_uv); }
+
+vstab_status vstab_pull_frame_p010_planar(vstab_handle *h, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv) { return pull_frame_impl(h, OUT_P010_PLANAR, dst_y, pitch_y, dst_uv, pitch_uv); }
+
+vstab_status vstab_peek_frame(vstab_handle *h, void *dst, size_t pitch_dst) { return vstab_pull_frame(h, dst, pitch_dst); }  // :478-480
+
+vstab_status vstab_set_border_mode(vstab_handle *h, int border_mode) { return set_border_mode(h, border_mode, "vstab_set_border_mode", false, "INTER_LINEAR (interpolation 1) and resample VSTAB_RESAMPLE_DEFAULT"); }
+
+vstab_status vstab_set_border_mode_ex(vstab_handle *h, int border_mode) { return set_border_mode(h, border_mode, "vstab_set_border_mode_ex", true, "INTER_LINEAR, INTER_CUBIC or INTER_LANCZOS4"); }
+
+}  // extern "C"

@@ -1,0 +1,226 @@
+// vstab_stateless.cpp -- the entry points of the C ABI that involve no handle: struct sizes and defaults, vstab_preload_kernels, the ring
+// source, the stateless tracking / motion operators and the rotation-filter object.
+#include <cstring>
+
+#include "vstab_motion.hpp"
+#include "vstab_track_host.hpp"
+
+using namespace vstab;
+
+extern "C" {
+
+int vstab_struct_size(int which) {
+    switch (which) {
+        case 0: return (int)sizeof(vstab_frame);
+        case 1: return (int)sizeof(vstab_source);
+        case 2: return (int)sizeof(vstab_config);
+        case 3: return (int)sizeof(vstab_frame_log);
+        case 4: return (int)sizeof(vstab_profile);
+        default: return -1;
+    }
+}
+
+int vstab_abi_version(void) { return VSTAB_ABI_VERSION; }
+
+void vstab_config_default(vstab_config *cfg) {
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->abi_version = VSTAB_ABI_VERSION;
+    cfg->preset = VSTAB_GOPRO_H4B_WIDE169_MEASURED;
+    cfg->scale = 1, cfg->crop_borders = 0, cfg->zoom = 1, cfg->smooth_radius = 30;  // FrameSourceWarp.hpp:86-89
+    cfg->interpolation = 1, cfg->smoother = VSTAB_SMOOTHER_SG, cfg->tracking = 1, cfg->seed = 1, cfg->stream = nullptr;
+    cfg->lens_mode = 0, cfg->in_projection = VSTAB_PROJ_FISH, cfg->out_projection = VSTAB_PROJ_RECT;
+    cfg->in_dfov = 0, cfg->out_dfov = 0, cfg->out_width = 0, cfg->out_height = 0, cfg->out_cx = -1, cfg->out_cy = -1, cfg->debug = 0;
+    cfg->pixel_depth = 8, cfg->blend = VSTAB_BLEND_EXACT;
+    // the reference's map is what ITS kernel computes on this GPU (createMap.cl through ROCm's OpenCL compiler): the default
+    cfg->map_precision = VSTAB_MAP_PRECISION_OPENCL;
+    cfg->read_ahead = 0;  // the library's default (PREFETCH_DEPTH)
+    cfg->resample = VSTAB_RESAMPLE_DEFAULT;
+}
+
+vstab_status vstab_preload_kernels(void) {
+    VSTAB_TRY(preload_track_kernels());
+    VSTAB_TRY(preload_warp_kernels());
+    VSTAB_TRY(preload_fused_kernels());
+    VSTAB_TRY(preload_p010_kernels());
+    VSTAB_TRY(preload_planar_kernels());
+    VSTAB_TRY(preload_cubic_kernels());
+    VSTAB_TRY(preload_lanczos4_kernels());
+    VSTAB_TRY(preload_border_kernels());
+    return VSTAB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// ring source
+// ---------------------------------------------------------------------------------------------
+struct vstab_ring_source {
+    std::vector<const void *> frames;
+    int w, h;
+    size_t pitch;
+    long total, pos;
+    int bit_depth = 8;
+    int hold = 1 << 30;  // what the source promises: by default the caller owns the frames for the life of the source and never rewrites them
+    std::vector<double> readout;  // optional: 9 doubles per ring frame (vstab_frame.readout_rotation)
+};
+
+static int ring_fill(vstab_ring_source *s, vstab_frame *out) {
+    if (s->pos >= s->total) return VSTAB_EOF;
+    const uint8_t *p = static_cast<const uint8_t *>(s->frames[(size_t)(s->pos % (long)s->frames.size())]);
+    out->y = p, out->uv = p + s->pitch * s->h, out->pitch_y = out->pitch_uv = s->pitch;
+    out->width = s->w, out->height = s->h, out->mem = 0, out->pts = s->pos;
+    out->hold = s->hold;
+    out->bit_depth = s->bit_depth;
+    if (!s->readout.empty()) out->readout_rotation = &s->readout[9 * (size_t)(s->pos % (long)s->frames.size())];
+    return 0;
+}
+static int ring_pull(void *user, vstab_frame *out) {
+    vstab_ring_source *s = static_cast<vstab_ring_source *>(user);
+    const int rc = ring_fill(s, out);
+    if (rc == 0) s->pos++;
+    return rc;
+}
+static int ring_peek(void *user, vstab_frame *out) { return ring_fill(static_cast<vstab_ring_source *>(user), out); }
+
+void vstab_ring_source_set_hold(vstab_ring_source *s, int hold) {
+    if (s) s->hold = hold < 0 ? 0 : hold;
+}
+
+vstab_status vstab_ring_source_create(const void *const *frames, int n_frames, int width, int height, size_t pitch,
+                                      long total_frames, vstab_ring_source **out, vstab_source *as_source) {
+    if (!frames || n_frames <= 0 || !out || !as_source || width <= 0 || height <= 0 || pitch < (size_t)width)
+        return fail(VSTAB_ERR_INVALID, "vstab_ring_source_create: bad argument");
+    vstab_ring_source *s = new vstab_ring_source;
+    s->frames.assign(frames, frames + n_frames);
+    s->w = width, s->h = height, s->pitch = pitch, s->total = total_frames, s->pos = 0;
+    as_source->pull = ring_pull, as_source->peek = ring_peek, as_source->user = s;
+    *out = s;
+    return VSTAB_OK;
+}
+
+vstab_status vstab_ring_source_create_ex(const void *const *frames, int n_frames, int width, int height, size_t pitch, long total_frames, int bit_depth,
+                                         const double *readout_rotations, vstab_ring_source **out, vstab_source *as_source) {
+    if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12 && bit_depth != 16) return fail(VSTAB_ERR_INVALID, "vstab_ring_source_create: bit_depth must be 8, 10, 12 or 16");
+    if (pitch < (size_t)width * (bit_depth > 8 ? 2 : 1)) return fail(VSTAB_ERR_INVALID, "vstab_ring_source_create: bad argument");
+    VSTAB_TRY(vstab_ring_source_create(frames, n_frames, width, height, pitch, total_frames, out, as_source));
+    (*out)->bit_depth = bit_depth;
+    if (readout_rotations) (*out)->readout.assign(readout_rotations, readout_rotations + 9 * (size_t)n_frames);
+    return VSTAB_OK;
+}
+
+void vstab_ring_source_destroy(vstab_ring_source *s) { delete s; }
+
+// ---------------------------------------------------------------------------------------------
+// stateless tracking / motion entry points
+// ---------------------------------------------------------------------------------------------
+vstab_status vstab_pyr_down(const void *src, size_t pitch_src, int width, int height, void *dst, size_t pitch_dst, void *stream) {
+    if (!src || !dst || width <= 0 || height <= 0 || pitch_src < (size_t)width || pitch_dst < (size_t)((width + 1) / 2))
+        return fail(VSTAB_ERR_INVALID, "vstab_pyr_down: bad argument");
+    return launch_pyr_down((const uint8_t *)src, pitch_src, width, height, (uint8_t *)dst, pitch_dst, static_cast<hipStream_t>(stream));
+}
+
+vstab_status vstab_pyr_down_x2(const void *src, size_t pitch_src, int width, int height, void *mid, size_t pitch_mid, void *dst, size_t pitch_dst, void *stream) {
+    const int mw = (width + 1) / 2, mh = (height + 1) / 2;
+    if (!src || !mid || !dst || width <= 0 || height <= 0 || pitch_src < (size_t)width || pitch_mid < (size_t)mw || pitch_dst < (size_t)((mw + 1) / 2))
+        return fail(VSTAB_ERR_INVALID, "vstab_pyr_down_x2: bad argument");
+    if (!pyr_down_x2_ok(width, height)) {  // tiny images: two single-level launches, the same bytes
+        VSTAB_TRY(launch_pyr_down((const uint8_t *)src, pitch_src, width, height, (uint8_t *)mid, pitch_mid, static_cast<hipStream_t>(stream)));
+        return launch_pyr_down((const uint8_t *)mid, pitch_mid, mw, mh, (uint8_t *)dst, pitch_dst, static_cast<hipStream_t>(stream));
+    }
+    return launch_pyr_down_x2((const uint8_t *)src, pitch_src, width, height, (uint8_t *)mid, pitch_mid, (uint8_t *)dst, pitch_dst, static_cast<hipStream_t>(stream));
+}
+
+vstab_status vstab_min_eig(const void *gray, size_t pitch, int width, int height, void *eig, void *stream) {
+    if (!gray || !eig || width <= 0 || height <= 0 || pitch < (size_t)width) return fail(VSTAB_ERR_INVALID, "vstab_min_eig: bad argument");
+    DevBuf mb;
+    VSTAB_TRY(mb.ensure(16));
+    VSTAB_TRY(launch_min_eig((const uint8_t *)gray, pitch, width, height, (float *)eig, mb.as<int>(), static_cast<hipStream_t>(stream)));
+    VSTAB_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    return VSTAB_OK;
+}
+
+vstab_status vstab_good_features_ex(const void *gray, size_t pitch, int width, int height, int max_corners, double quality,
+                                    double min_distance, int detector, float *xy, int *count, int *detector_used, void *stream) {
+    if (!gray || !xy || !count || width < 3 || height < 3 || pitch < (size_t)width || max_corners <= 0 ||
+        (detector != VSTAB_DETECTOR_AUTO && detector != VSTAB_DETECTOR_TWO_PASS))
+        return fail(VSTAB_ERR_INVALID, "vstab_good_features: bad argument");
+    Tracker t;
+    VSTAB_TRY(t.init(width, height));
+    t.set_two_pass_detector(detector == VSTAB_DETECTOR_TWO_PASS);
+    std::vector<float> out;
+    VSTAB_TRY(t.good_features((const uint8_t *)gray, pitch, max_corners, quality, min_distance, out, static_cast<hipStream_t>(stream)));
+    *count = (int)(out.size() / 2);
+    std::memcpy(xy, out.data(), sizeof(float) * out.size());
+    if (detector_used) *detector_used = (detector == VSTAB_DETECTOR_TWO_PASS || t.fused_overflows()) ? VSTAB_DETECTOR_TWO_PASS : VSTAB_DETECTOR_FUSED;
+    return VSTAB_OK;
+}
+
+vstab_status vstab_good_features(const void *gray, size_t pitch, int width, int height, int max_corners, double quality,
+                                 double min_distance, float *xy, int *count, void *stream) {
+    return vstab_good_features_ex(gray, pitch, width, height, max_corners, quality, min_distance, VSTAB_DETECTOR_AUTO, xy, count, nullptr, stream);
+}
+
+vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height,
+                          const float *prev_xy, int n, float *next_xy, unsigned char *status, void *stream) {
+    if (!prev || !next || (n > 0 && (!prev_xy || !next_xy || !status)) || n < 0 || width <= 0 || height <= 0 ||
+        pitch_prev < (size_t)width || pitch_next < (size_t)width)
+        return fail(VSTAB_ERR_INVALID, "vstab_pyr_lk: bad argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Tracker t;
+    VSTAB_TRY(t.init(width, height));
+    VSTAB_TRY(t.build_pyramid(0, (const uint8_t *)prev, pitch_prev, st));
+    VSTAB_TRY(t.build_pyramid(1, (const uint8_t *)next, pitch_next, st));
+    std::vector<float> p(prev_xy, prev_xy + 2 * (size_t)n), q;
+    std::vector<uint8_t> s;
+    VSTAB_TRY(t.track(t.pyramid(0, (const uint8_t *)prev, pitch_prev), t.pyramid(1, (const uint8_t *)next, pitch_next), p, q, s, st));
+    if (n > 0) {
+        std::memcpy(next_xy, q.data(), sizeof(float) * q.size());
+        std::memcpy(status, s.data(), s.size());
+    }
+    return VSTAB_OK;
+}
+
+vstab_status vstab_estimate_rotation(const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9],
+                                     uint64_t seed, double R[9], int *inliers) {
+    if ((n > 0 && (!prev_xy || !cur_xy)) || n < 0 || !K_in || !K_out || !R || !inliers)
+        return fail(VSTAB_ERR_INVALID, "vstab_estimate_rotation: bad argument");
+    Mat3 ki, ko, r;
+    std::memcpy(ki.m, K_in, sizeof(ki.m)), std::memcpy(ko.m, K_out, sizeof(ko.m));
+    Pcg32 rng(seed);
+    *inliers = estimate_rotation(prev_xy, cur_xy, n, ki, ko, rng, r);
+    std::memcpy(R, r.m, sizeof(r.m));
+    return VSTAB_OK;
+}
+
+vstab_status vstab_sg_weights(int m, double *weights) {
+    if (m < 0 || !weights) return fail(VSTAB_ERR_INVALID, "vstab_sg_weights: bad argument");
+    const std::vector<double> w = sg_weights(m);
+    std::memcpy(weights, w.data(), sizeof(double) * w.size());
+    return VSTAB_OK;
+}
+
+struct vstab_rotation_filter {
+    RotationFilterSG f;
+    explicit vstab_rotation_filter(int m) : f(m) {}
+};
+
+vstab_status vstab_rotation_filter_create(int m, vstab_rotation_filter **out) {
+    if (m < 0 || !out) return fail(VSTAB_ERR_INVALID, "vstab_rotation_filter_create: bad argument");
+    *out = new vstab_rotation_filter(m);
+    return VSTAB_OK;
+}
+vstab_status vstab_rotation_filter_add(vstab_rotation_filter *f, const double R[9]) {
+    if (!f || !R) return fail(VSTAB_ERR_INVALID, "vstab_rotation_filter_add: null argument");
+    Mat3 r;
+    std::memcpy(r.m, R, sizeof(r.m));
+    f->f.add(r);
+    return VSTAB_OK;
+}
+vstab_status vstab_rotation_filter_filter(const vstab_rotation_filter *f, double R_out[9]) {
+    if (!f || !R_out) return fail(VSTAB_ERR_INVALID, "vstab_rotation_filter_filter: null argument");
+    const Mat3 r = f->f.filter();
+    std::memcpy(R_out, r.m, sizeof(r.m));
+    return VSTAB_OK;
+}
+void vstab_rotation_filter_destroy(vstab_rotation_filter *f) { delete f; }
+
+}  // extern "C"

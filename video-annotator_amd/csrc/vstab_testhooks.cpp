@@ -1,0 +1,157 @@
+// vstab_testhooks.cpp -- the vstabx_* test hooks.
+#include <algorithm>
+
+#include "vstab_hostlogic.hpp"
+#include "vstab_track_host.hpp"
+
+using namespace vstab;
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Test hooks (vstabx_*: not part of the ABI of include/vstab.h, no device needed): the CPU suite -- and its sanitizer build -- drive
+// the host-side bookkeeping of vstab_hostlogic.hpp with hand-made buffers (tests/test_hostlogic_cpu.py).
+// ---------------------------------------------------------------------------------------------------------------------------------
+extern "C" {
+// Decode n hand-made tracker records as Tracker::track_wait does.  Returns the LkParse code; *n_out entries in xy / status; *next =
+// the first record that was not ready (or n).
+__attribute__((visibility("default"))) int vstabx_parse_records(const uint32_t *rec, int n, uint32_t seq, int expect_n, float *xy, unsigned char *status,
+                                                                 int *n_out, int *next) {
+    std::vector<float> pts;
+    std::vector<uint8_t> st;
+    int nx = 0;
+    const LkParse r = lk_parse_records(rec, 0, n, seq, (size_t)expect_n, pts, st, &nx);
+    for (size_t i = 0; i < st.size(); i++) xy[2 * i] = pts[2 * i], xy[2 * i + 1] = pts[2 * i + 1], status[i] = st[i];
+    *n_out = (int)st.size(), *next = nx;
+    return (int)r;
+}
+// Run a sequence of n lookups (object ids = inodes, all of one size unless sizes is given) through a DmaBufCache with fake import /
+// destroy functions.  counts = {imports, evictions, mapped now, destroys seen, largest number mapped at once}; bases[i] = the base the
+// i-th lookup returned (id * 4096 for the fake import: a stale mapping would show); fail_id: the import of this id fails (-1: none).
+__attribute__((visibility("default"))) int vstabx_dmabuf_cache_sim(const unsigned long long *ids, const size_t *sizes, int n, int cap, long window,
+                                                                    long long fail_id, long *counts, unsigned long long *bases) {
+    DmaBufCache<unsigned long long> cache;
+    cache.cap = cap;
+    long destroys = 0, peak = 0;
+    std::vector<unsigned long long> live;
+    int failures = 0;
+    for (int i = 0; i < n; i++) {
+        uint8_t *base = nullptr;
+        const unsigned long long id = ids[i];
+        const bool ok = cache.lookup(id, sizes ? sizes[i] : 4096, window,
+                                     [&](unsigned long long &h, uint8_t *&b) {
+                                         if ((long long)id == fail_id) return false;
+                                         h = id, b = reinterpret_cast<uint8_t *>(static_cast<uintptr_t>(id * 4096));
+                                         live.push_back(id);
+                                         return true;
+                                     },
+                                     [&](unsigned long long &h) {
+                                         destroys++;
+                                         for (size_t k = 0; k < live.size(); k++)
+                                             if (live[k] == h) {
+                                                 live.erase(live.begin() + (long)k);
+                                                 break;
+                                             }
+                                     },
+                                     base);
+        failures += !ok;
+        bases[i] = ok ? static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(base)) : ~0ull;
+        peak = std::max<long>(peak, (long)cache.size());
+    }
+    counts[0] = cache.imports, counts[1] = cache.evictions, counts[2] = (long)cache.size(), counts[3] = destroys, counts[4] = peak;
+    cache.clear([&](unsigned long long &) { destroys++; });
+    counts[5] = destroys;
+    return failures;
+}
+
+// THE FIRST HOOK THAT NEEDS A DEVICE (tests/test_lk_segments_gpu.py; its argument checks run without one: tests/test_lk_segments_cpu.py).
+// Tracks n points through K = sum(seg) frame pairs of the K + 1 device luma frames (frames[i], pitches[i]; w x h) the way the pipeline
+// does: every frame's pyramid by Tracker::build_pyramid, then one launch per entry of seg (1 .. LK_SEG_MAX pairs each) on `stream` --
+// the first by Tracker::track_launch from pts, every later one by Tracker::track_launch_chained behind the one before it (non-zero
+// increasing tags, zeroed device records, host records in mapped memory).
+//   uv, uv_pitches, rings (all NULL, or K + 1 entries each): level 1 of frame i is written by launch_pack_pyr together with the copy
+//       of (frames[i], uv[i]) into the device buffer rings[i] (w * h * 3 / 2 bytes), and the frame is tracked from the ring's luma --
+//       the pipeline's ingest of a frame upstream recycles.  Only where pack_pyr_ok holds for every frame.
+//   bad_parent: the launch of this index (1 .. n_seg - 1; -1 = none) is handed a parent tag that is not its parent's.
+//   host_rec, dev_rec: K * n records of 4 uint32 each, pair-major -- what the kernel left in the mapped and in the device copy.
+//   pyr_out (optional): levels 1 .. of every frame's pyramid, dense, frame after frame.
+// Bad arguments are refused with VSTAB_ERR_INVALID before anything touches the device.
+__attribute__((visibility("default"))) int vstabx_lk_segments(const void *const *frames, const size_t *pitches, int w, int h, const float *pts, int n,
+                                                               const int *seg, int n_seg, const void *const *uv, const size_t *uv_pitches,
+                                                               void *const *rings, int bad_parent, uint32_t *host_rec, uint32_t *dev_rec,
+                                                               uint8_t *pyr_out, void *stream) {
+    if (!frames || !pitches || !pts || !seg || !host_rec || !dev_rec || w <= 0 || h <= 0 || n <= 0 || n_seg <= 0 || n_seg > Tracker::REC_BUFS)
+        return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: bad argument");
+    int K = 0;
+    for (int s = 0; s < n_seg; s++) {
+        if (seg[s] < 1 || seg[s] > LK_SEG_MAX) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: a launch covers 1 .. LK_SEG_MAX frame pairs");
+        K += seg[s];
+    }
+    // (the record buffers rotate through REC_BUFS: every pair of the call keeps its own)
+    if (K > Tracker::REC_BUFS) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: more frame pairs than record buffers");
+    if (bad_parent != -1 && (bad_parent < 1 || bad_parent >= n_seg)) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: bad_parent is not a chained launch");
+    const bool pack = uv || uv_pitches || rings;
+    if (pack && (!uv || !uv_pitches || !rings)) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: uv, uv_pitches and rings go together");
+    if (pack && lk_levels(w, h) < 2) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: a one-level pyramid has no level 1 to pack");
+    for (int i = 0; i <= K; i++) {
+        if (!frames[i] || pitches[i] < (size_t)w || pitches[i] >= (1u << 24) || (uint64_t)pitches[i] * (uint64_t)h >= (1ull << 32))
+            return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: bad frame");
+        // (level 1 is the Tracker's: a hipMalloc'd buffer, pitch (w + 1) / 2 -- the ring stands in for its base, which is aligned)
+        if (pack && (!uv[i] || !rings[i] || !pack_pyr_ok(frames[i], pitches[i], uv[i], uv_pitches[i], w, h, rings[i], rings[i], (size_t)((w + 1) / 2))))
+            return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: planes not aligned for the fused copy");
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Tracker t;
+    VSTAB_TRY(t.init(w, h));
+    VSTAB_TRY(t.reserve_slots(n));
+    const int levels = t.levels();
+    size_t pyr_bytes = 0;
+    for (int l = 1; l < levels; l++) pyr_bytes += (size_t)t.level_w(l) * t.level_h(l);
+    // frame i -> pyramid set i % PYR_SETS: a launch spans at most LK_SEG_MAX + 1 < PYR_SETS frames, and a set is rebuilt only behind
+    // every launch that reads it (one stream)
+    std::vector<LkPyramid> pyr(K + 1);
+    int built = -1;
+    auto build = [&](int i) -> vstab_status {
+        const int s = i % PYR_SETS;
+        const uint8_t *y = static_cast<const uint8_t *>(frames[i]);
+        size_t pitch = pitches[i];
+        if (pack) {
+            uint8_t *ring = static_cast<uint8_t *>(rings[i]);
+            VSTAB_TRY(launch_pack_pyr(y, pitch, static_cast<const uint8_t *>(uv[i]), uv_pitches[i], w, h, ring, t.level1(s), t.level1_pitch(), st));
+            y = ring, pitch = (size_t)w;
+        }
+        VSTAB_TRY(t.build_pyramid(s, y, pitch, st, nullptr, nullptr, pack));
+        pyr[i] = t.pyramid(s, y, pitch);
+        if (pyr_out) {
+            uint8_t *o = pyr_out + pyr_bytes * i;
+            for (int l = 1; l < levels; l++) {
+                const size_t lw = (size_t)t.level_w(l), lh = (size_t)t.level_h(l);
+                VSTAB_HIP_TRY(hipMemcpyAsync(o, pyr[i].img[l], lw * lh, hipMemcpyDeviceToHost, st));
+                o += lw * lh;
+            }
+        }
+        built = i;
+        return VSTAB_OK;
+    };
+    std::vector<Tracker::Launch> launches(n_seg);
+    std::vector<float> start(pts, pts + 2 * (size_t)n);
+    int first = 0;
+    for (int s = 0; s < n_seg; s++) {
+        for (int i = built + 1; i <= first + seg[s]; i++) VSTAB_TRY(build(i));
+        if (s == 0) {
+            VSTAB_TRY(t.track_launch(&pyr[first], seg[s], start, st, false, launches[s]));
+        } else {
+            Tracker::Launch parent = launches[s - 1];
+            if (s == bad_parent) parent.seq[parent.n_frames - 1] ^= 0x40u;  // a tag the parent never wrote (nor any launch of this call)
+            VSTAB_TRY(t.track_launch_chained(&pyr[first], seg[s], parent, st, launches[s]));
+        }
+        first += seg[s];
+    }
+    VSTAB_HIP_TRY(hipStreamSynchronize(st));
+    int k = 0;
+    for (int s = 0; s < n_seg; s++)
+        for (int i = 0; i < seg[s]; i++, k++) {
+            std::memcpy(host_rec + (size_t)k * n * 4, t.host_records(launches[s], i), (size_t)n * 16);
+            VSTAB_HIP_TRY(hipMemcpy(dev_rec + (size_t)k * n * 4, t.dev_records(launches[s], i), (size_t)n * 16, hipMemcpyDeviceToHost));
+        }
+    return VSTAB_OK;
+}
+}  // extern "C"
