@@ -489,6 +489,49 @@ VSTAB_API vstab_status vstab_draw_markers(void *dst, size_t pitch, int width, in
                                           void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Lens distortion: OpenCV's fisheye (Kannala-Brandt) model on the INPUT camera, the `distortion_coefficients` k1 .. k4 the reference's
+ * Camera carries (FrameSourceWarp.hpp) and hands to every fisheye::undistortPoints call:
+ *   theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),   image radius = f theta_d.
+ * All zero is the ideal equidistant lens of every other entry point, bit for bit.  dist / D: the four coefficients, floats in the device
+ * operators (like params), doubles in the host functions.
+ *   map     the operations of map modes 1 / 2 (VSTAB_MAP_FISH_TO_RECT / _FISH_TO_FISH) up to theta = atan(rad); then, every operation
+ *           an IEEE binary32 operation of its own (nothing fused):
+ *             s2 = theta * theta;  g = k4;  g = g * s2 + k3;  g = g * s2 + k2;  g = g * s2 + k1;  theta_d = theta * (1 + g * s2);
+ *           and k = theta_d / rad (1 on the axis), map = centre + (p * k) * focal; outside (NaN) exactly where modes 1 / 2 are.
+ *           tests/distort_def.py states it in numpy, tests/golden/distort_kat.npz pins it.
+ *   points  OpenCV 4.5's fisheye::undistortPoints: theta_d clipped to pi/2; Newton from theta = theta_d with
+ *           fix = (theta (1 + k1 theta^2 + ...) - theta_d) / (1 + 3 k1 theta^2 + 5 k2 theta^4 + 7 k3 theta^6 + 9 k4 theta^8), at most 10
+ *           steps, stop at |fix| < 1e-8; scale = tan(theta) / theta_d; a point that did not converge, or whose theta changed sign, becomes
+ *           (-1e6, -1e6).
+ * Accepted coefficients: all four finite, and 1 + 3 k1 theta^2 + 5 k2 theta^4 + 7 k3 theta^6 + 9 k4 theta^8 > 0 at the 1025 points
+ * theta = i (pi/2) / 1024 (fp64): theta_d must increase on [0, pi/2] -- the warp kernels bound a tile's source box by the map on the tile's
+ * perimeter, which holds for a map that does not fold.  Anything else is VSTAB_ERR_INVALID ("the distortion must keep theta_d increasing
+ * on [0, pi/2]"), from every entry point below.  map_mode: VSTAB_MAP_FISH_TO_RECT or VSTAB_MAP_FISH_TO_FISH; any other is
+ * VSTAB_ERR_INVALID ("distortion belongs to a fisheye input (map modes 1 and 2)").
+ * Not served with distortion: the output camera, the rotation per output row, 10-bit planes, and the nearest, cubic, Lanczos and border
+ * warps as fused kernels -- the stateless vstab_remap_* operators take the planes of vstab_create_map_dist, which covers every resampler
+ * and border mode.
+ * ------------------------------------------------------------------------------------------ */
+/* vstab_fisheye_undistort_points through the distorted lens. */
+VSTAB_API vstab_status vstab_fisheye_undistort_points_d(const double *pts, int n, const double K[9], const double D[4], const double *R,
+                                                        const double *P, double *out);
+/* vstab_estimate_rotation with the input lens's coefficients: both point sets are undistorted with D. */
+VSTAB_API vstab_status vstab_estimate_rotation_d(const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9],
+                                                 const double D[4], uint64_t seed, double R[9], int *inliers);
+/* vstab_create_map_ex / vstab_quantised_map with the polynomial. */
+VSTAB_API vstab_status vstab_create_map_dist(void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows, const float params[17],
+                                             const float dist[4], int map_mode, void *stream);
+VSTAB_API vstab_status vstab_quantised_map_dist(void *qmap, int dst_width, int dst_height, const float params[17], const float dist[4], int map_mode,
+                                                void *stream);
+/* vstab_warp_nv12_ex with the polynomial: the LDS-tiled kernels of modes 1 / 2 (small or unaligned sources: their gather path).
+ * out_format: VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR; VSTAB_OUT_NV12 (through BGR) and any other value are refused with
+ * VSTAB_ERR_INVALID.  Arguments are checked as vstab_warp_nv12_cubic checks them and in its order, except the map mode: it is checked
+ * behind all of them (pointers, sizes, output format, pitches, chroma alignment), then the coefficients, last. */
+VSTAB_API vstab_status vstab_warp_nv12_dist(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                            const float params[17], const float dist[4], int map_mode, int out_format, void *dst, size_t pitch_dst,
+                                            void *dst_uv, size_t pitch_dst_uv, int dst_width, int dst_height, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The pipeline object: drop-in for FrameSourceWarp behind the FrameSource pull interface
  * (FrameSource.hpp:9-24, FrameSourceWarp.hpp:83-91).
  * ------------------------------------------------------------------------------------------ */
@@ -735,6 +778,17 @@ VSTAB_API vstab_status vstab_set_border_mode(vstab_handle *h, int border_mode);
  * refused as above.  A non-constant mode is VSTAB_ERR_UNSUPPORTED on handles with pixel_depth 10 or interpolation 0 (INTER_NEAREST); unknown
  * modes and a NULL handle are VSTAB_ERR_INVALID. */
 VSTAB_API vstab_status vstab_set_border_mode_ex(vstab_handle *h, int border_mode);
+/* The calibrated input lens of a handle (Lens distortion above): K, a row-major camera matrix with fx, fy > 0, zero skew and last row
+ * 0 0 1 (NULL keeps the camera vstab_create derived from in_dfov), and the four coefficients D.  From then on the rotation estimate
+ * undistorts the tracked points with D (vstab_estimate_rotation_d), the warp is vstab_warp_nv12_dist (a run of frames with equal parameters:
+ * vstab_quantised_map_dist once, then vstab_warp_nv12_mapped), and the `debug` markers are projected through the distorted lens.  Served
+ * pulls: vstab_pull_frame, _frames, _host, _nv12_planar and vstab_peek_frame; vstab_pull_frame_nv12 is refused before a frame is taken, a
+ * frame that carries a readout_rotation is refused and consumed (as INTER_NEAREST does).  D = 0 gives the frames of a handle without the call.
+ * Allowed on a handle with lens_mode 1, in_projection VSTAB_PROJ_FISH, resample VSTAB_RESAMPLE_DEFAULT, 8-bit pixels and the constant
+ * border, before the first pull; anything else, a bad K and coefficients that are not accepted are VSTAB_ERR_INVALID, the message naming
+ * the cause, and the handle is unchanged.  On a calibrated handle vstab_set_border_mode / _ex refuse a non-constant mode with
+ * VSTAB_ERR_INVALID. */
+VSTAB_API vstab_status vstab_set_input_calibration(vstab_handle *h, const double K[9], const double D[4]);
 /* Synchronises the stream, folds all pending event pairs into the sums and returns them. */
 VSTAB_API vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out);
 

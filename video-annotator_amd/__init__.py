@@ -170,6 +170,12 @@ SIGNATURES = {
     "vstab_warp_nv12_cubic_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_warp_nv12_lanczos4_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_set_border_mode_ex": (_i, [_vp, _i]),
+    "vstab_set_input_calibration": (_i, [_vp, _dp, _dp]),
+    "vstab_fisheye_undistort_points_d": (_i, [_dp, _i, _dp, _dp, _dp, _dp, _dp]),
+    "vstab_estimate_rotation_d": (_i, [_fp, _fp, _i, _dp, _dp, _dp, _u64, _dp, _ip]),
+    "vstab_create_map_dist": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _vp]),
+    "vstab_quantised_map_dist": (_i, [_vp, _i, _i, _fp, _fp, _i, _vp]),
+    "vstab_warp_nv12_dist": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -178,6 +184,9 @@ for _name, (_res, _args) in SIGNATURES.items():
 _L.vstabx_lk_segments.restype = _i
 _L.vstabx_lk_segments.argtypes = [_pp, _c.POINTER(_sz), _i, _i, _fp, _i, _ip, _i, _pp, _c.POINTER(_sz), _pp, _i, _c.POINTER(_c.c_uint32),
                                   _c.POINTER(_c.c_uint32), _u8p, _vp]
+
+_L.vstabx_warps_from_cache.restype = _c.c_long
+_L.vstabx_warps_from_cache.argtypes = [_vp]
 
 lib = _L
 ABI_VERSION = 0x56534206  # include/vstab.h: VSTAB_ABI_VERSION ("VSB" + layout version 6)
@@ -244,12 +253,18 @@ def lens_camera(projection, dfov_deg, width, height, cx=-1.0, cy=-1.0):
     return K.reshape(3, 3)
 
 
-def fisheye_undistort_points(pts, K, R=None, P=None):
+def fisheye_undistort_points(pts, K, R=None, P=None, D=None):
+    """D: k1..k4 of the lens (vstab_fisheye_undistort_points_d), None = the ideal equidistant lens."""
     p = np.ascontiguousarray(pts, np.float64).reshape(-1, 2)
     Kc = np.ascontiguousarray(K, np.float64).reshape(9)
     Rc = None if R is None else np.ascontiguousarray(R, np.float64).reshape(9)
     Pc = None if P is None else np.ascontiguousarray(P, np.float64).reshape(9)
     out = np.zeros_like(p)
+    if D is not None:
+        Dc = np.ascontiguousarray(D, np.float64).reshape(4)
+        _check(_L.vstab_fisheye_undistort_points_d(_dptr(p), p.shape[0], _dptr(Kc), _dptr(Dc), None if Rc is None else _dptr(Rc),
+                                                   None if Pc is None else _dptr(Pc), _dptr(out)), "vstab_fisheye_undistort_points_d")
+        return out
     _check(_L.vstab_fisheye_undistort_points(_dptr(p), p.shape[0], _dptr(Kc), None if Rc is None else _dptr(Rc),
                                              None if Pc is None else _dptr(Pc), _dptr(out)),
            "vstab_fisheye_undistort_points")
@@ -319,6 +334,17 @@ def create_map(params, cols, rows, device="cuda", mode=MAP_CREATEMAP_CL):
     else:
         _check(_L.vstab_create_map_ex(mx.data_ptr(), mx.stride(0) * 4, my.data_ptr(), my.stride(0) * 4, cols, rows,
                                       _fptr(p), int(mode), _stream()), "vstab_create_map_ex")
+    return mx, my
+
+
+def create_map_dist(params, dist, cols, rows, mode=MAP_FISH_TO_RECT, device="cuda"):
+    """vstab_create_map_dist: the map planes of mode 1 / 2 with the input lens's k1..k4."""
+    import torch
+    p, d = np.ascontiguousarray(params, np.float32), np.ascontiguousarray(dist, np.float32).reshape(4)
+    mx = torch.empty((rows, cols), dtype=torch.float32, device=device)
+    my = torch.empty((rows, cols), dtype=torch.float32, device=device)
+    _check(_L.vstab_create_map_dist(mx.data_ptr(), mx.stride(0) * 4, my.data_ptr(), my.stride(0) * 4, cols, rows, _fptr(p), _fptr(d), int(mode),
+                                    _stream()), "vstab_create_map_dist")
     return mx, my
 
 
@@ -465,6 +491,26 @@ def warp_nv12(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, 
     yo, co = out
     _check(_L.vstab_warp_nv12_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), int(out_format), yo.data_ptr(), yo.stride(0),
                                  co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_ex")
+    return yo, co
+
+
+def warp_nv12_dist(nv12, params, dist, dw, dh, mode=MAP_FISH_TO_RECT, out_format=OUT_BGR8, out=None):
+    """vstab_warp_nv12_dist: warp_nv12 in mode 1 / 2 with the input lens's k1..k4.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR ->
+    (luma, chroma) tensors."""
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    p, d = np.ascontiguousarray(params, np.float32), np.ascontiguousarray(dist, np.float32).reshape(4)
+    if out_format == OUT_BGR8:
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
+        _check(_L.vstab_warp_nv12_dist(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), OUT_BGR8, out.data_ptr(), out.stride(0), None, 0,
+                                       dw, dh, _stream()), "vstab_warp_nv12_dist")
+        return out
+    if out is None:
+        out = nv12_out_planes(dw, dh, nv12.device)
+    yo, co = out
+    _check(_L.vstab_warp_nv12_dist(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(out_format), yo.data_ptr(), yo.stride(0),
+                                   co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_dist")
     return yo, co
 
 
@@ -659,6 +705,15 @@ def quantised_map(params, dw, dh, mode=MAP_CREATEMAP_CL, device="cuda"):
     return q
 
 
+def quantised_map_dist(params, dist, dw, dh, mode=MAP_FISH_TO_RECT, device="cuda"):
+    """vstab_quantised_map_dist: quantised_map of mode 1 / 2 with the input lens's k1..k4 (for warp_nv12_mapped)."""
+    import torch
+    p, d = np.ascontiguousarray(params, np.float32), np.ascontiguousarray(dist, np.float32).reshape(4)
+    q = torch.empty(_L.vstab_quantised_map_bytes(dw, dh), dtype=torch.uint8, device=device)
+    _check(_L.vstab_quantised_map_dist(q.data_ptr(), dw, dh, _fptr(p), _fptr(d), int(mode), _stream()), "vstab_quantised_map_dist")
+    return q
+
+
 def warp_nv12_mapped(nv12, qmap, dw, dh, out_format=OUT_BGR8, out=None):
     import torch
     yp, uvp, pitch, w, h = _planes(nv12)
@@ -777,13 +832,19 @@ def lk_segments(frames, pts, segs, uv=None, rings=None, bad_parent=-1, want_pyr=
     return hrec, drec, pyr
 
 
-def estimate_rotation(prev_xy, cur_xy, K_in, K_out, seed=1):
+def estimate_rotation(prev_xy, cur_xy, K_in, K_out, seed=1, D=None):
+    """D: k1..k4 of the input lens (vstab_estimate_rotation_d), None = the ideal equidistant lens."""
     a = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
     b = np.ascontiguousarray(cur_xy, np.float32).reshape(-1, 2)
     Ki = np.ascontiguousarray(K_in, np.float64).reshape(9)
     Ko = np.ascontiguousarray(K_out, np.float64).reshape(9)
     R = np.zeros(9)
     inl = _c.c_int()
+    if D is not None:
+        Dc = np.ascontiguousarray(D, np.float64).reshape(4)
+        _check(_L.vstab_estimate_rotation_d(_fptr(a), _fptr(b), a.shape[0], _dptr(Ki), _dptr(Ko), _dptr(Dc), seed, _dptr(R), _c.byref(inl)),
+               "vstab_estimate_rotation_d")
+        return R.reshape(3, 3), inl.value
     _check(_L.vstab_estimate_rotation(_fptr(a), _fptr(b), a.shape[0], _dptr(Ki), _dptr(Ko), seed, _dptr(R), _c.byref(inl)),
            "vstab_estimate_rotation")
     return R.reshape(3, 3), inl.value
@@ -855,8 +916,10 @@ class Stabilizer:
     """vstab_handle wrapper.  `frames`: list of packed NV12 CUDA tensors (cycled by the C ring
     source for `total` pulls) or a Python iterable of such tensors (python callback source)."""
 
-    def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, **cfg_kw):
+    def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, calibration=None,
+                 **cfg_kw):
         """border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
+        calibration: (K, D) for set_input_calibration right after create, applied after border_mode (K None keeps the camera from in_dfov).
         hold (iterable sources): vstab_frame.hold -- how many further pulls each tensor is kept alive and unchanged
         for; from smooth_radius + 14 on the library uses the tensors in place instead of copying them.
         bit_depth / readouts (list sources): P010 frames as int16 tensors of shape (h * 3 / 2, w); one 3x3 read-out
@@ -918,6 +981,21 @@ class Stabilizer:
         self.K_in, self.K_out = Ki.reshape(3, 3), Ko.reshape(3, 3)
         if border_mode is not None:
             self.set_border_mode_ex(border_mode)
+        if calibration is not None:
+            self.set_input_calibration(*calibration)
+
+    def set_input_calibration(self, K, D):
+        """vstab_set_input_calibration: the calibrated input lens, camera matrix K (3x3, or None) and k1..k4 (a scalar 0 stands for four zeros),
+        before the first pull."""
+        Kc = None if K is None else np.ascontiguousarray(K, np.float64).reshape(9)
+        Dc = np.ascontiguousarray(np.broadcast_to(np.asarray(D, np.float64), (4,)))
+        _check(_L.vstab_set_input_calibration(self._h, None if Kc is None else _dptr(Kc), _dptr(Dc)), "vstab_set_input_calibration")
+        if Kc is not None:
+            self.K_in = Kc.reshape(3, 3).copy()
+
+    def warps_from_cache(self):
+        """Test hook vstabx_warps_from_cache: warps of this handle that read the quantised map of an earlier frame with equal parameters."""
+        return int(_L.vstabx_warps_from_cache(self._h))
 
     def set_border_mode(self, border_mode):
         """vstab_set_border_mode: cv::remap's borderMode for the frames pulled from now on."""

@@ -106,10 +106,26 @@ __device__ __forceinline__ float sqrt_rn(float x) {
 
 // createMap.cl:13-50 with the primitives above; returns 32*map (exact power-of-two scaling folded
 // into the constants: c32 = 32*src_center, f32 = 32*src_focal), i.e. the value cv::remap rounds.
+// k1..k4 of the input lens (OpenCV's fisheye model: theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8)); read by
+// the MAP_FISHD_* modes only, zero everywhere else
+struct Distortion {
+    float k1, k2, k3, k4;
+};
 struct MapParams32 {
     float icx32, icy32, ifx32, ify32;
     float r02, r12, r22;
+    Distortion d;
 };
+// theta -> theta_d, every operation rounded on its own (the translation units are built with -ffp-contract=off): DESIGN.md section 18.
+// d = 0 returns `at` bit for bit.
+__device__ __forceinline__ float distort_theta(float at, const Distortion &d) {
+    const float s2 = at * at;
+    float g = d.k4;
+    g = g * s2 + d.k3;
+    g = g * s2 + d.k2;
+    g = g * s2 + d.k1;
+    return at * (1.0f + g * s2);
+}
 __device__ __forceinline__ void map_pixel32(const MapParams32 &p, const ColTerm &c, const RowTerm &r,
                                             float &ax, float &ay) {
     const float wx = (c.a0 + r.b0) + p.r02;
@@ -215,16 +231,19 @@ enum MapMode { MAP_CREATEMAP_CL = 0, MAP_FISH_TO_RECT = 1, MAP_FISH_TO_FISH = 2,
                // createMap.cl with the arithmetic ROCm's OpenCL compiler gives it on gfx950 (below)
                MAP_CREATEMAP_CL_OPENCL = 5,
                // internal: modes 0 / 1 / 5 with a per-row rotation (rolling shutter, BASELINE config 5)
-               MAP_RS_CREATEMAP_CL = 6, MAP_RS_FISH_TO_RECT = 7, MAP_RS_CREATEMAP_CL_OPENCL = 8 };
+               MAP_RS_CREATEMAP_CL = 6, MAP_RS_FISH_TO_RECT = 7, MAP_RS_CREATEMAP_CL_OPENCL = 8,
+               // internal: modes 1 / 2 with the input lens's distortion polynomial (vstab_*_dist)
+               MAP_FISHD_TO_RECT = 9, MAP_FISHD_TO_FISH = 10 };
 // the projection pair (and arithmetic) of a mode: the rolling-shutter modes share their base mode's
-constexpr bool map_mode_is_rs(int mode) { return mode >= MAP_RS_CREATEMAP_CL; }
+constexpr bool map_mode_is_rs(int mode) { return mode >= MAP_RS_CREATEMAP_CL && mode <= MAP_RS_CREATEMAP_CL_OPENCL; }
 constexpr int map_mode_base(int mode) {
     return mode == MAP_RS_CREATEMAP_CL ? MAP_CREATEMAP_CL : mode == MAP_RS_FISH_TO_RECT ? MAP_FISH_TO_RECT : mode == MAP_RS_CREATEMAP_CL_OPENCL ? MAP_CREATEMAP_CL_OPENCL : mode;
 }
 template <int MODE>
 struct ModeTraits {
-    static constexpr bool out_fish = MODE == MAP_FISH_TO_FISH || MODE == MAP_RECT_TO_FISH;
-    static constexpr bool in_fish = MODE == MAP_FISH_TO_RECT || MODE == MAP_FISH_TO_FISH || MODE == MAP_CREATEMAP_CL || MODE == MAP_CREATEMAP_CL_OPENCL;
+    static constexpr bool dist = MODE == MAP_FISHD_TO_RECT || MODE == MAP_FISHD_TO_FISH;  // theta -> theta_d on the way into the input lens
+    static constexpr bool out_fish = MODE == MAP_FISH_TO_FISH || MODE == MAP_RECT_TO_FISH || MODE == MAP_FISHD_TO_FISH;
+    static constexpr bool in_fish = MODE == MAP_FISH_TO_RECT || MODE == MAP_FISH_TO_FISH || MODE == MAP_CREATEMAP_CL || MODE == MAP_CREATEMAP_CL_OPENCL || dist;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -389,6 +408,7 @@ __device__ __forceinline__ void map_pixel_ex(const MapParams32 &p, const MapPara
             g = __builtin_fmaf(g, s, -0.33333125710487366f);
             float at = __builtin_fmaf(t * s, g, t);
             at = inv ? (1.57079637050628662109375f - at) + (-4.37113900018624283e-8f) : at;
+            if constexpr (ModeTraits<MODE>::dist) at = distort_theta(at, p.d);
             const float k = zero ? 1.0f : div_with_rcp(at, rad, rr);
             ax = p.icx32 + (px * k) * p.ifx32;
             ay = p.icy32 + (py * k) * p.ify32;

@@ -62,14 +62,48 @@ bool preset_camera(int preset, int w, int h, Mat3 &K) {
     return true;
 }
 
-// OpenCV 4.5 fisheye::undistortPoints with D = 0: theta_d clipped to pi/2, scale = tan(theta)/theta.
-void fisheye_undistort(const double *pts, int n, const Mat3 &K, const Mat3 &RR, double *out, bool fish) {
+vstab_status check_distortion(const std::string &n, const double D[4]) {
+    bool ok = D && std::isfinite(D[0]) && std::isfinite(D[1]) && std::isfinite(D[2]) && std::isfinite(D[3]);
+    for (int i = 0; ok && i <= 1024; i++) {  // d theta_d / d theta on a grid of [0, pi/2]
+        const double t = i * (M_PI / 2.) / 1024, t2 = t * t, t4 = t2 * t2, t6 = t4 * t2, t8 = t6 * t2;
+        ok = 1 + 3 * D[0] * t2 + 5 * D[1] * t4 + 7 * D[2] * t6 + 9 * D[3] * t8 > 0;
+    }
+    return ok ? VSTAB_OK : fail(VSTAB_ERR_INVALID, n + ": the distortion must keep theta_d increasing on [0, pi/2]");
+}
+
+// theta_d -> theta as OpenCV 4.5's fisheye::undistortPoints inverts the polynomial: Newton from theta = theta_d, at most 10 steps, stop at
+// |fix| < 1e-8.  False when it did not converge or theta changed sign.  k = 0: the first step is zero and theta = theta_d.
+bool fisheye_theta(double theta_d, const double k[4], double &theta) {
+    bool converged = false;
+    theta = theta_d;
+    for (int j = 0; j < 10 && !converged; j++) {
+        const double t2 = theta * theta, t4 = t2 * t2, t6 = t4 * t2, t8 = t6 * t2;
+        const double a = k[0] * t2, b = k[1] * t4, c = k[2] * t6, d = k[3] * t8;
+        const double fix = (theta * (1 + a + b + c + d) - theta_d) / (1 + 3 * a + 5 * b + 7 * c + 9 * d);
+        theta -= fix;
+        converged = std::fabs(fix) < 1e-8;
+    }
+    return converged && !((theta_d < 0 && theta > 0) || (theta_d > 0 && theta < 0));
+}
+
+// OpenCV 4.5 fisheye::undistortPoints: theta_d clipped to pi/2, theta from fisheye_theta, scale = tan(theta)/theta_d; a point whose theta
+// was not found is (-1e6, -1e6).  D null = zero: today's ideal lens, bit for bit.
+void fisheye_undistort(const double *pts, int n, const Mat3 &K, const Mat3 &RR, double *out, bool fish, const double *D) {
+    static const double zero[4] = {0, 0, 0, 0};
+    const double *k = D ? D : zero;
     for (int i = 0; i < n; i++) {
         const double pwx = (pts[2 * i] - K(0, 2)) / K(0, 0), pwy = (pts[2 * i + 1] - K(1, 2)) / K(1, 1);
         double theta_d = std::sqrt(pwx * pwx + pwy * pwy);
         theta_d = std::min(std::max(-M_PI / 2., theta_d), M_PI / 2.);
         double scale = 0.0;
-        if (std::fabs(theta_d) > 1e-8) scale = std::tan(theta_d) / theta_d;
+        if (fish && std::fabs(theta_d) > 1e-8) {
+            double theta;
+            if (!fisheye_theta(theta_d, k, theta)) {
+                out[2 * i] = out[2 * i + 1] = -1000000.0;
+                continue;
+            }
+            scale = std::tan(theta) / theta_d;
+        }
         if (!fish) scale = 1.0;
         const double ux = pwx * scale, uy = pwy * scale;
         const double x = RR(0, 0) * ux + RR(0, 1) * uy + RR(0, 2);
@@ -177,9 +211,10 @@ vstab_status vstab_lens_camera(int projection, double dfov_deg, int width, int h
     return VSTAB_OK;
 }
 
-vstab_status vstab_fisheye_undistort_points(const double *pts, int n, const double K[9], const double *R,
-                                            const double *P, double *out) {
-    if (!pts || !K || !out || n < 0) return fail(VSTAB_ERR_INVALID, "vstab_fisheye_undistort_points: bad argument");
+static vstab_status undistort_points(const std::string &name, const double *pts, int n, const double K[9], const double *D, const double *R, const double *P,
+                                     double *out) {
+    if (!pts || !K || !out || n < 0) return fail(VSTAB_ERR_INVALID, name + ": bad argument");
+    if (D) VSTAB_TRY(check_distortion(name, D));
     Mat3 k, rr = Mat3::identity();
     std::memcpy(k.m, K, sizeof(k.m));
     if (R) std::memcpy(rr.m, R, sizeof(rr.m));
@@ -188,8 +223,18 @@ vstab_status vstab_fisheye_undistort_points(const double *pts, int n, const doub
         std::memcpy(p.m, P, sizeof(p.m));
         rr = p * rr;
     }
-    fisheye_undistort(pts, n, k, rr, out);
+    fisheye_undistort(pts, n, k, rr, out, true, D);
     return VSTAB_OK;
+}
+
+vstab_status vstab_fisheye_undistort_points(const double *pts, int n, const double K[9], const double *R, const double *P, double *out) {
+    return undistort_points("vstab_fisheye_undistort_points", pts, n, K, nullptr, R, P, out);
+}
+
+vstab_status vstab_fisheye_undistort_points_d(const double *pts, int n, const double K[9], const double D[4], const double *R, const double *P,
+                                              double *out) {
+    if (!D) return fail(VSTAB_ERR_INVALID, "vstab_fisheye_undistort_points_d: bad argument");
+    return undistort_points("vstab_fisheye_undistort_points_d", pts, n, K, D, R, P, out);
 }
 
 void vstab_map_params(const double K_in[9], const double K_out[9], const double R[9], float params[17]) {

@@ -34,7 +34,10 @@ struct Mat3 {
 
 bool preset_camera(int preset, int w, int h, Mat3 &K);
 // fish = false: pinhole input, the points are only normalised and rotated
-void fisheye_undistort(const double *pts, int n, const Mat3 &K, const Mat3 &RR, double *out, bool fish = true);
+// D: k1..k4 of the fisheye lens (checked by the caller: check_distortion), null = an ideal equidistant lens
+void fisheye_undistort(const double *pts, int n, const Mat3 &K, const Mat3 &RR, double *out, bool fish = true, const double *D = nullptr);
+// theta_d -> theta through k1..k4 (Newton, as fisheye_undistort runs it); false when no theta was found
+bool fisheye_theta(double theta_d, const double k[4], double &theta);
 // camera matrix of a libdewobble-style lens (projection 0 rect / 1 fish, diagonal field of view in degrees)
 bool lens_camera(int projection, double dfov_deg, int w, int h, double cx, double cy, Mat3 &K);
 void output_camera(const Mat3 &Kin, int w, int h, double scale, bool crop, double zoom, Mat3 &Kout, int &ow, int &oh);

@@ -50,6 +50,16 @@ inline bool border_mode_valid(int m) {
     return m == VSTAB_BORDER_CONSTANT || m == VSTAB_BORDER_REPLICATE || m == VSTAB_BORDER_REFLECT || m == VSTAB_BORDER_REFLECT_101;
 }
 
+// k1..k4 of a fisheye lens as every entry point that takes them accepts them (vstab_geometry.cpp): all finite, and theta_d increasing
+// on [0, pi/2] -- the warp kernels' perimeter probe bounds a tile's source box only for a map that does not fold
+vstab_status check_distortion(const std::string &n, const double D[4]);
+inline vstab_status check_distortion(const std::string &n, const float D[4]) {
+    const double d[4] = {D[0], D[1], D[2], D[3]};
+    return check_distortion(n, d);
+}
+// the map modes whose input camera is a fisheye lens, i.e. the ones the distortion belongs to
+inline bool map_mode_takes_distortion(int map_mode) { return map_mode == VSTAB_MAP_FISH_TO_RECT || map_mode == VSTAB_MAP_FISH_TO_FISH; }
+
 // vstab_pack_p010 with a choice of planes (vstab_warp.hip): luma_only narrows the luma plane alone -- what the 10-bit
 // pipeline needs for its tracker
 vstab_status pack_p010_planes(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int width, int height, void *dst, bool luma_only,

@@ -40,9 +40,9 @@ class EstimateWorker {
             th_.join();
         }
     }
-    void post(const float *prev, const float *cur, int n, const Mat3 *Kin, const Mat3 *Kout, Pcg32 *rng, bool in_fish) {
+    void post(const float *prev, const float *cur, int n, const Mat3 *Kin, const Mat3 *Kout, Pcg32 *rng, bool in_fish, const double *D) {
         if (!th_.joinable()) th_ = std::thread([this] { run(); });
-        prev_ = prev, cur_ = cur, n_ = n, Kin_ = Kin, Kout_ = Kout, rng_ = rng, in_fish_ = in_fish;
+        prev_ = prev, cur_ = cur, n_ = n, Kin_ = Kin, Kout_ = Kout, rng_ = rng, in_fish_ = in_fish, D_ = D;
         {
             std::lock_guard<std::mutex> lk(m_);
             state_.store(POSTED, std::memory_order_release);
@@ -74,7 +74,7 @@ class EstimateWorker {
                 st = state_.load(std::memory_order_acquire);
             }
             if (st == QUIT) return;
-            inliers_ = estimate_rotation(prev_, cur_, n_, *Kin_, *Kout_, *rng_, R_, in_fish_);
+            inliers_ = estimate_rotation(prev_, cur_, n_, *Kin_, *Kout_, *rng_, R_, in_fish_, D_);
             int posted = POSTED;  // a destructor that stored QUIT meanwhile must not be answered with DONE
             if (!state_.compare_exchange_strong(posted, DONE, std::memory_order_acq_rel)) return;
         }
@@ -88,6 +88,7 @@ class EstimateWorker {
     const Mat3 *Kin_ = nullptr, *Kout_ = nullptr;
     Pcg32 *rng_ = nullptr;
     bool in_fish_ = true;
+    const double *D_ = nullptr;
     Mat3 R_;
     int inliers_ = 0;
 };
@@ -126,6 +127,12 @@ struct vstab_handle {
     Mat3 Kin, Kout;
     int map_mode = VSTAB_MAP_CREATEMAP_CL;  // createMap.cl for the preset path, a projection pair in lens mode
     bool in_fish = true;
+    // vstab_set_input_calibration: the input lens's k1..k4 (fp64 for the rotation estimate and the markers, fp32 for the map); Kin is then the
+    // calibrated camera matrix where one was given
+    bool calibrated = false, pulled = false;  // pulled: a pull has started to consume frames
+    double dist[4] = {0, 0, 0, 0};
+    float dist32[4] = {0, 0, 0, 0};
+    const double *distortion() const { return calibrated ? dist : nullptr; }
     Tracker tracker;
 
     struct Slot {

@@ -32,6 +32,8 @@ static vstab_status refuse_formats(const vstab_handle *H, const Pull &P) {
     if (H->cfg.resample != VSTAB_RESAMPLE_DEFAULT) return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: ") + resample_name(H->cfg.resample) + served);
     // (the mode in force for this pull: a border warp serves the same two formats as the cubic one, refused before any frame is dequeued)
     if (P.border_mode != VSTAB_BORDER_CONSTANT) return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: a border mode other than VSTAB_BORDER_CONSTANT") + served);
+    // (nor does the distorted-lens warp of a calibrated handle)
+    if (H->calibrated) return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: a calibrated handle (vstab_set_input_calibration)") + served);
     return VSTAB_OK;
 }
 
@@ -111,7 +113,8 @@ static vstab_status choose_cached_map(vstab_handle *H, Pull &P) {
     } else if (H->have_last_params && std::memcmp(P.p, H->last_params, sizeof(P.p)) == 0) {
         // second frame in a row with these parameters: write the map down now (same stream, ahead of the warp)
         VSTAB_TRY(H->qmap.ensure(vstab_quantised_map_bytes(H->ow, H->oh)));
-        VSTAB_TRY(vstab_quantised_map(H->qmap.p, H->ow, H->oh, P.p, H->map_mode, H->stream));
+        if (H->calibrated) VSTAB_TRY(vstab_quantised_map_dist(H->qmap.p, H->ow, H->oh, P.p, H->dist32, H->map_mode, H->stream));
+        else VSTAB_TRY(vstab_quantised_map(H->qmap.p, H->ow, H->oh, P.p, H->map_mode, H->stream));
         std::memcpy(H->qmap_params, P.p, sizeof(P.p));
         H->qmap_valid = P.cached = true;
     }
@@ -180,8 +183,13 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
         if (out_format != VSTAB_OUT_BGR8 || P.rot_bottom) return refuse_launch("INTER_NEAREST emits 8-bit BGR frames without a read-out rotation");
         return vstab_warp_nv12_nearest_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, P.dst, P.pitch_dst, ow, oh, H->stream);
     }
+    // (a calibrated handle: a frame that carries a read-out rotation is consumed, as INTER_NEAREST consumes it above)
+    if (H->calibrated && P.rot_bottom) return refuse_launch("a calibrated handle (vstab_set_input_calibration) warps frames without a read-out rotation");
     if (P.cached)
         return vstab_warp_nv12_mapped(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, H->qmap.p, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+    if (H->calibrated)
+        return vstab_warp_nv12_dist(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, H->dist32, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh,
+                                    H->stream);
     if (P.rot_bottom)
         return vstab_warp_nv12_rs(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh,
                                   H->stream);
@@ -203,7 +211,10 @@ static vstab_status draw_markers(vstab_handle *H, const Pull &P) {
         const double a = (S.feats[i] - H->Kin(0, 2)) / H->Kin(0, 0), b = (S.feats[i + 1] - H->Kin(1, 2)) / H->Kin(1, 1);
         double rx = a, ry = b, rz = 1;
         if (H->in_fish) {
-            const double th = std::hypot(a, b), sc = th > 0 ? std::sin(th) / th : 1.0;
+            const double thd = std::hypot(a, b);  // theta_d of a calibrated lens: back to theta first
+            double th = thd;
+            if (H->calibrated && !fisheye_theta(thd, H->dist, th)) continue;
+            const double sc = thd > 0 ? std::sin(th) / thd : 1.0;
             rx = a * sc, ry = b * sc, rz = std::cos(th);
         }
         const double ox = warp_R(0, 0) * rx + warp_R(1, 0) * ry + warp_R(2, 0) * rz, oy = warp_R(0, 1) * rx + warp_R(1, 1) * ry + warp_R(2, 1) * rz,
@@ -247,6 +258,7 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
     if (!H || !dst || (out_has_chroma_plane(out_format) && !dst_uv)) return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: null argument");
     Pull P{out_format, dst, dst_uv, pitch_dst, pitch_dst_uv, H->border_mode};
     VSTAB_TRY(refuse_formats(H, P));
+    H->pulled = true;
     HT t_total(HostTimers::TOTAL);
     VSTAB_TRY(advance_until_due(H));
     if (H->queue.empty()) return VSTAB_EOF;  // :465-467
@@ -270,6 +282,8 @@ static vstab_status set_border_mode(vstab_handle *h, int border_mode, const char
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)");
     if (border_mode != VSTAB_BORDER_CONSTANT && (h->cfg.pixel_depth == 10 || h->cfg.interpolation == 0 || (!resamplers && h->cfg.resample != VSTAB_RESAMPLE_DEFAULT)))
         return fail(VSTAB_ERR_UNSUPPORTED, std::string(fn) + ": border modes other than VSTAB_BORDER_CONSTANT are served for 8-bit pixels with " + served);
+    if (border_mode != VSTAB_BORDER_CONSTANT && h->calibrated)
+        return fail(VSTAB_ERR_INVALID, std::string(fn) + ": a calibrated handle (vstab_set_input_calibration) warps with VSTAB_BORDER_CONSTANT");
     h->border_mode = border_mode;
     return VSTAB_OK;
 }

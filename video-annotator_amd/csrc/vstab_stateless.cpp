@@ -179,16 +179,32 @@ vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const void *next,
     return VSTAB_OK;
 }
 
-vstab_status vstab_estimate_rotation(const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9],
-                                     uint64_t seed, double R[9], int *inliers) {
-    if ((n > 0 && (!prev_xy || !cur_xy)) || n < 0 || !K_in || !K_out || !R || !inliers)
-        return fail(VSTAB_ERR_INVALID, "vstab_estimate_rotation: bad argument");
+}  // extern "C"
+
+// D: the input lens's k1..k4 (vstab_estimate_rotation_d), else null
+static vstab_status estimate_rotation_impl(const std::string &name, const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9],
+                                           const double *D, uint64_t seed, double R[9], int *inliers) {
+    if ((n > 0 && (!prev_xy || !cur_xy)) || n < 0 || !K_in || !K_out || !R || !inliers) return fail(VSTAB_ERR_INVALID, name + ": bad argument");
+    if (D) VSTAB_TRY(check_distortion(name, D));
     Mat3 ki, ko, r;
     std::memcpy(ki.m, K_in, sizeof(ki.m)), std::memcpy(ko.m, K_out, sizeof(ko.m));
     Pcg32 rng(seed);
-    *inliers = estimate_rotation(prev_xy, cur_xy, n, ki, ko, rng, r);
+    *inliers = estimate_rotation(prev_xy, cur_xy, n, ki, ko, rng, r, true, D);
     std::memcpy(R, r.m, sizeof(r.m));
     return VSTAB_OK;
+}
+
+extern "C" {
+
+vstab_status vstab_estimate_rotation(const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9],
+                                     uint64_t seed, double R[9], int *inliers) {
+    return estimate_rotation_impl("vstab_estimate_rotation", prev_xy, cur_xy, n, K_in, K_out, nullptr, seed, R, inliers);
+}
+
+vstab_status vstab_estimate_rotation_d(const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9], const double D[4],
+                                       uint64_t seed, double R[9], int *inliers) {
+    if (!D) return fail(VSTAB_ERR_INVALID, "vstab_estimate_rotation_d: bad argument");
+    return estimate_rotation_impl("vstab_estimate_rotation_d", prev_xy, cur_xy, n, K_in, K_out, D, seed, R, inliers);
 }
 
 vstab_status vstab_sg_weights(int m, double *weights) {

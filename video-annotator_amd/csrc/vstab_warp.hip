@@ -145,11 +145,11 @@ __global__ void __launch_bounds__(256) k_create_map(float *__restrict__ mapx, si
 template <int MODE>
 __global__ void __launch_bounds__(256) k_create_map_ex(float *__restrict__ mapx, size_t pitch_x,
                                                        float *__restrict__ mapy, size_t pitch_y,
-                                                       int cols, int rows, MapParams p, int vec_ok) {
+                                                       int cols, int rows, MapParams p, int vec_ok, Distortion d) {
     const int x0 = (blockIdx.x * 16 + threadIdx.x) * 4;
     const int y = blockIdx.y * 16 + threadIdx.y;
     if (x0 >= cols || y >= rows) return;
-    const MapParams32 in = {p.icx, p.icy, p.ifx, p.ify, p.r[2], p.r[5], p.r[8]};  // unscaled here
+    const MapParams32 in = {p.icx, p.icy, p.ifx, p.ify, p.r[2], p.r[5], p.r[8], d};  // unscaled here
     constexpr bool OCL = MODE == MAP_CREATEMAP_CL_OPENCL;
     const float vy = OCL ? ocl_div((float)y - p.ocy, p.ofy) : ((float)y - p.ocy) / p.ofy;
     const RowTerm rt = {p.r[1] * vy, p.r[4] * vy, p.r[7] * vy};
@@ -438,27 +438,55 @@ vstab_status vstab_cvt_nv12_bgr(const void *y, size_t pitch_y, const void *uv, s
     return VSTAB_OK;
 }
 
-vstab_status vstab_create_map_ex(void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows,
-                                 const float params[17], int map_mode, void *stream) {
-    if (!map_x || !map_y || !params) return fail(VSTAB_ERR_INVALID, "vstab_create_map: null pointer");
+}  // extern "C"
+
+// the map planes' arguments, checked; dist != null: vstab_create_map_dist (map modes 1 and 2 with the input lens's polynomial)
+static vstab_status create_map_impl(const std::string &n, void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows, const float params[17],
+                                    const float *dist, bool with_dist, int map_mode, void *stream) {
+    if (!map_x || !map_y || !params || (with_dist && !dist)) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
     if (cols <= 0 || rows <= 0 || cols > 32767 || rows > 32767)
-        return fail(VSTAB_ERR_INVALID, "vstab_create_map: size must be in [1, 32767] (createMap.cl:10-11)");
+        return fail(VSTAB_ERR_INVALID, n + ": size must be in [1, 32767] (createMap.cl:10-11)");
     if (pitch_x < (size_t)cols * 4 || pitch_y < (size_t)cols * 4 || pitch_x % 4 || pitch_y % 4)
-        return fail(VSTAB_ERR_INVALID, "vstab_create_map: bad pitch");
-    if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_create_map: unknown map mode");
+        return fail(VSTAB_ERR_INVALID, n + ": bad pitch");
+    if (with_dist) {
+        if (!map_mode_takes_distortion(map_mode)) return fail(VSTAB_ERR_INVALID, n + ": distortion belongs to a fisheye input (map modes 1 and 2)");
+        VSTAB_TRY(check_distortion(n, dist));
+    } else if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) {
+        return fail(VSTAB_ERR_INVALID, n + ": unknown map mode");
+    }
     const int vec_ok = ptr_aligned(map_x, 16) && ptr_aligned(map_y, 16) && pitch_x % 16 == 0 && pitch_y % 16 == 0;
     dim3 grid(div_up(div_up(cols, 4), 16), div_up(rows, 16));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    with_map_mode(map_mode, [&](auto mode) {
-        constexpr int MODE = decltype(mode)::value;
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(16, 16), 0, s, (float *)map_x, pitch_x, (float *)map_y, pitch_y, cols, rows, map_params(params), vec_ok);
-        };
-        if constexpr (MODE == MAP_CREATEMAP_CL) launch(k_create_map);  // createMap.cl itself
-        else launch(k_create_map_ex<MODE>);
-    });
+    if (with_dist) {
+        const Distortion d = {dist[0], dist[1], dist[2], dist[3]};
+        with_dist_mode(map_mode, [&](auto mode) {
+            hipLaunchKernelGGL(k_create_map_ex<decltype(mode)::value>, grid, dim3(16, 16), 0, s, (float *)map_x, pitch_x, (float *)map_y, pitch_y, cols, rows,
+                               map_params(params), vec_ok, d);
+        });
+    } else {
+        with_map_mode(map_mode, [&](auto mode) {
+            constexpr int MODE = decltype(mode)::value;
+            if constexpr (MODE == MAP_CREATEMAP_CL)  // createMap.cl itself
+                hipLaunchKernelGGL(k_create_map, grid, dim3(16, 16), 0, s, (float *)map_x, pitch_x, (float *)map_y, pitch_y, cols, rows, map_params(params), vec_ok);
+            else
+                hipLaunchKernelGGL(k_create_map_ex<MODE>, grid, dim3(16, 16), 0, s, (float *)map_x, pitch_x, (float *)map_y, pitch_y, cols, rows,
+                                   map_params(params), vec_ok, Distortion());
+        });
+    }
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
+}
+
+extern "C" {
+
+vstab_status vstab_create_map_ex(void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows,
+                                 const float params[17], int map_mode, void *stream) {
+    return create_map_impl("vstab_create_map", map_x, pitch_x, map_y, pitch_y, cols, rows, params, nullptr, false, map_mode, stream);
+}
+
+vstab_status vstab_create_map_dist(void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows, const float params[17],
+                                   const float dist[4], int map_mode, void *stream) {
+    return create_map_impl("vstab_create_map_dist", map_x, pitch_x, map_y, pitch_y, cols, rows, params, dist, true, map_mode, stream);
 }
 
 vstab_status vstab_create_map(void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows,
@@ -495,7 +523,7 @@ vstab_status vstab_remap_bilinear(const void *src, size_t pitch_src, int sw, int
 static vstab_status warp_impl(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh,
                               const float params[17], int map_mode, int out_format, void *dst, size_t pitch_dst,
                               void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream, const void *qmap, int qpitch,
-                              const float *rot_bottom = nullptr) {
+                              const float *rot_bottom = nullptr, const float *dist = nullptr) {
     if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: null pointer");
     if (sw <= 0 || sh <= 0 || (sw & 1) || (sh & 1) || sw > 32767 || sh > 32767)
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: source must be even-sized and <= 32767");
@@ -527,7 +555,7 @@ static vstab_status warp_impl(const void *y, size_t pitch_y, const void *uv, siz
         if (sw < 16 || sh < 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: the plane-wise warp needs a source of at least 16 x 2");
         const bool src16 = stage32 && ptr_aligned(y, 16) && ptr_aligned(uv, 16) && pitch_y % 16 == 0 && pitch_uv % 16 == 0;  // 16-byte staging loads
         const bool dst16 = ptr_aligned(dst, 16) && ptr_aligned(dst_uv, 16) && pitch_dst % 16 == 0 && pitch_dst_uv % 16 == 0;
-        return launch_warp_planar(a, params, map_mode, 8, 0, src16, dst16, rot_bottom, static_cast<hipStream_t>(stream));
+        return launch_warp_planar(a, params, map_mode, 8, 0, src16, dst16, rot_bottom, static_cast<hipStream_t>(stream), dist);
     }
     bool direct = !small_pitch || (plain && !stage32);
 #ifdef VSTAB_DEV
@@ -539,7 +567,7 @@ static vstab_status warp_impl(const void *y, size_t pitch_y, const void *uv, siz
         hipLaunchKernelGGL(k_warp_nv12_bgr, grid, dim3(16, 16), 0, static_cast<hipStream_t>(stream), a, vec_ok);
     } else {
         const bool src_vec_ok = stage32 && ptr_aligned(y, 8) && ptr_aligned(uv, 8) && pitch_y % 8 == 0 && pitch_uv % 8 == 0;  // 8-byte staging loads
-        return launch_warp_fused(a, params, map_mode, nv12_out, src_vec_ok, vec_ok, qmap, qpitch, rot_bottom, static_cast<hipStream_t>(stream));
+        return launch_warp_fused(a, params, map_mode, nv12_out, src_vec_ok, vec_ok, qmap, qpitch, rot_bottom, static_cast<hipStream_t>(stream), dist);
     }
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
@@ -590,6 +618,40 @@ vstab_status vstab_quantised_map(void *qmap, int dw, int dh, const float params[
     });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
+}
+
+vstab_status vstab_quantised_map_dist(void *qmap, int dw, int dh, const float params[17], const float dist[4], int map_mode, void *stream) {
+    const std::string n = "vstab_quantised_map_dist";
+    if (!qmap || !params || !dist || dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767) return fail(VSTAB_ERR_INVALID, n + ": bad argument");
+    if (!map_mode_takes_distortion(map_mode)) return fail(VSTAB_ERR_INVALID, n + ": distortion belongs to a fisheye input (map modes 1 and 2)");
+    if (!ptr_aligned(qmap, 16)) return fail(VSTAB_ERR_INVALID, n + ": the buffer must be 16-byte aligned");
+    VSTAB_TRY(check_distortion(n, dist));
+    const int qpitch = (dw + 3) & ~3;
+    dim3 grid(div_up(qpitch / 4, 16), div_up(dh, 16));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    with_dist_mode(map_mode, [&](auto mode) {
+        hipLaunchKernelGGL(k_quantised_map<decltype(mode)::value>, grid, dim3(256), 0, st, static_cast<int2 *>(qmap), qpitch, dw, dh, map_params(params),
+                           map_params32(params, dist));
+    });
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
+vstab_status vstab_warp_nv12_dist(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                  const float dist[4], int map_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv,
+                                  int dw, int dh, void *stream) {
+    const std::string n = "vstab_warp_nv12_dist";
+    if (!dist) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
+    // check_warp_nv12's checks in its order, except that the map mode is checked behind them: every mode but 1 and 2, known or not, gets
+    // the one message below (check_warp_nv12 is handed a mode it accepts), then the coefficients
+    const bool fish_in = map_mode_takes_distortion(map_mode);
+    CubicArgs c;
+    VSTAB_TRY(check_warp_nv12(n, "the distorted-lens warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr,
+                              fish_in ? map_mode : (int)VSTAB_MAP_FISH_TO_RECT, out_format, nullptr, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, c));
+    if (!fish_in) return fail(VSTAB_ERR_INVALID, n + ": distortion belongs to a fisheye input (map modes 1 and 2)");
+    VSTAB_TRY(check_distortion(n, dist));
+    return warp_impl(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream, nullptr, 0, nullptr,
+                     dist);
 }
 
 vstab_status vstab_warp_nv12_mapped(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const void *qmap,

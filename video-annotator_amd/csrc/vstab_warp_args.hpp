@@ -69,15 +69,17 @@ __device__ __forceinline__ uint32_t load_u32_bytes(const uint8_t *p, int valid) 
     return v;
 }
 
+// dist: k1..k4 of the input lens (map modes 1 and 2, BGR8, no quantised map, one rotation per frame: the MAP_FISHD_* kernels), else null
 vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int map_mode, bool nv12_out, bool src_vec_ok, bool dst_vec_ok,
-                               const void *qmap, int qpitch, const float *rot_bottom, hipStream_t st);
+                               const void *qmap, int qpitch, const float *rot_bottom, hipStream_t st, const float *dist = nullptr);
 // the 10-bit pixel path on the LDS-tiled kernel: a.y / a.uv = P010 planes (16-byte aligned, pitches multiples of 16), a.dst = 16-bit
 // BGR with a.pitch_dst bytes per row; map modes 0 / 1 only.  src_vec_ok false: nothing is staged, every pixel is sampled from global memory
 vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int map_mode, int blend, const float *rot_bottom, bool p010_out, bool src_vec_ok,
                                  bool dst_vec_ok, hipStream_t st);
 
 // the plane-wise warp (vstab_warp_planar.hip): a.dst / a.dst_uv = the output planes; depth 8 (NV12 bytes) or 10 (P010 words)
+// dist: as for launch_warp_fused (depth 8 only)
 vstab_status launch_warp_planar(const WarpArgs &a, const float params[17], int map_mode, int depth, int blend, bool src_vec_ok, bool dst_vec_ok,
-                                const float *rot_bottom, hipStream_t st);
+                                const float *rot_bottom, hipStream_t st, const float *dist = nullptr);
 
 }  // namespace vstab

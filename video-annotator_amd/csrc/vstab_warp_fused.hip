@@ -410,7 +410,11 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                 const uint32_t d = __builtin_amdgcn_perm(hi, lo, sel);
                 if (lane < nfull) *reinterpret_cast<uint32_t *>(o + (uint32_t)(4 * lane)) = d;
                 else if (lane == nfull && rem) {
-                    for (int i = 0; i < rem; i++) o[4 * lane + i] = (d >> (8 * i)) & 255;
+                    uint32_t l4 = 4u * (uint32_t)lane;
+                    // formed here: hoisted out of the tile loop as a 64-bit offset, it is the one value the 64 x 32 kernels of the distorted-lens
+                    // modes have no register for (8 bytes of scratch)
+                    if constexpr (ModeTraits<BASE>::dist) asm volatile("" : "+v"(l4));
+                    for (int i = 0; i < rem; i++) o[l4 + i] = (d >> (8 * i)) & 255;
                 }
             } else if (col_live) {
                 o[3 * lane] = out[j] & 255, o[3 * lane + 1] = (out[j] >> 8) & 255, o[3 * lane + 2] = (out[j] >> 16) & 255;
@@ -534,9 +538,9 @@ vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int 
 }
 
 vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int map_mode, bool nv12_out, bool src_vec_ok, bool dst_vec_ok,
-                               const void *qmap, int qpitch, const float *rot_bottom, hipStream_t st) {
+                               const void *qmap, int qpitch, const float *rot_bottom, hipStream_t st, const float *dist) {
     FusedArgs ta;
-    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, qmap, qpitch, rot_bottom);
+    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, qmap, qpitch, rot_bottom, dist);
 #ifdef VSTAB_DEV
     ta.timing = g_dev_timing;
     static const int ablate = getenv("VSTAB_ABLATE") ? atoi(getenv("VSTAB_ABLATE")) : 0;
@@ -558,6 +562,16 @@ vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int ma
 #endif
     const size_t lds_bytes = (size_t)lds_kb * 1024;
     const dim3 grid(tile_schedule(ta, rwb, lds_kb, tail_rounds));
+    if (dist) {  // the input lens's polynomial: modes 1 / 2 to BGR8, the map always evaluated (the caller has checked all of it)
+        if (nv12_out || qmap || rot_bottom) return fail(VSTAB_ERR_INVALID, "launch_warp_fused: the distorted-lens kernels emit BGR8 from one rotation per frame");
+        with_dist_mode(map_mode, [&](auto mode) {
+            with_either<8, 4>(rwb == 8, [&](auto rows) {
+                launch_kernel(k_warp_fused<decltype(rows)::value, decltype(mode)::value, 0, false>, grid, dim3(256), lds_bytes, st, ta);
+            });
+        });
+        VSTAB_HIP_TRY(hipGetLastError());
+        return VSTAB_OK;
+    }
     // CACHED: the map phase reads the quantised map, the map mode no longer matters (the kernels exist under MAP_CREATEMAP_CL)
     with_map_mode(qmap ? (int)VSTAB_MAP_CREATEMAP_CL : map_mode, !qmap && rot_bottom != nullptr, [&](auto mode) {
         with_bool(qmap != nullptr, [&](auto cached) {

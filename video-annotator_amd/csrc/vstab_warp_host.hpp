@@ -26,8 +26,11 @@ inline MapParams map_params(const float params[17]) {
     return m;
 }
 // the source camera scaled to the 1/32-pixel grid of cv::remap's quantisation, and the rotation's third column
-inline MapParams32 map_params32(const float params[17]) {
-    return {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16]};
+// dist: k1..k4 of the input lens (the vstab_*_dist entry points), else null: zeros, which no other mode reads
+inline MapParams32 map_params32(const float params[17], const float *dist = nullptr) {
+    MapParams32 m = {params[0] * 32.0f, params[1] * 32.0f, params[2] * 32.0f, params[3] * 32.0f, params[10], params[13], params[16], {0.0f, 0.0f, 0.0f, 0.0f}};
+    if (dist) m.d = {dist[0], dist[1], dist[2], dist[3]};
+    return m;
 }
 inline void fill_warp_args(WarpArgs &a, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17], void *dst,
                            size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh) {
@@ -45,9 +48,9 @@ void fill_rolling_shutter(Args &a, const float params[17], const float *rot_bott
 }
 // what the three launchers of the tiled kernels set alike; the tile shape (tile_schedule) and the VSTAB_DEV fields' values are theirs
 inline void fill_fused_args(FusedArgs &ta, const WarpArgs &a, const float params[17], bool src_vec_ok, bool dst_vec_ok, const void *qmap, int qpitch,
-                            const float *rot_bottom) {
+                            const float *rot_bottom, const float *dist = nullptr) {
     ta.w = a;
-    ta.p32 = map_params32(params);
+    ta.p32 = map_params32(params, dist);
     ta.src_vec_ok = src_vec_ok, ta.dst_vec_ok = dst_vec_ok;
     ta.qmap = static_cast<const int2 *>(qmap), ta.qpitch = qpitch;
     fill_rolling_shutter(ta, params, rot_bottom, a.dh);
@@ -94,6 +97,12 @@ void with_map_mode(int map_mode, bool rs, F &&f) {
         case VSTAB_MAP_CREATEMAP_CL_OPENCL: f(mode_constant<MAP_RS_CREATEMAP_CL_OPENCL>{}); break;
         default: f(mode_constant<MAP_RS_FISH_TO_RECT>{}); break;
     }
+}
+// the input lens's distortion (checked: map modes 1 and 2 only): the mode's MAP_FISHD_* form
+template <typename F>
+void with_dist_mode(int map_mode, F &&f) {
+    if (map_mode == VSTAB_MAP_FISH_TO_RECT) f(mode_constant<MAP_FISHD_TO_RECT>{});
+    else f(mode_constant<MAP_FISHD_TO_FISH>{});
 }
 // the fisheye -> pinhole maps (modes 0, 1, 5): the only ones that take a rotation per output row (so the only ones with a MAP_RS_*
 // form), and the only ones the 10-bit tiled kernels serve.  Asked of the public VSTAB_MAP_* values by the argument checks and of the

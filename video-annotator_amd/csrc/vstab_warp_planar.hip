@@ -505,9 +505,9 @@ __global__ void __launch_bounds__(256, RWB == 8 ? 5 : 6) k_warp_planar(FusedArgs
 // the four planes, pitches in bytes; depth 8 (NV12 bytes) or 10 (P010 words); src_vec_ok: source planes and pitches 16-byte aligned
 // (else every pixel takes the global-memory path: correct, slow); dst_vec_ok: destination planes and pitches 16-byte aligned.
 vstab_status launch_warp_planar(const WarpArgs &a, const float params[17], int map_mode, int depth, int blend, bool src_vec_ok, bool dst_vec_ok,
-                                const float *rot_bottom, hipStream_t st) {
+                                const float *rot_bottom, hipStream_t st, const float *dist) {
     FusedArgs ta;
-    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, nullptr, 0, rot_bottom);
+    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, nullptr, 0, rot_bottom, dist);
 #ifdef VSTAB_DEV
     ta.ablate = getenv("VSTAB_ABLATE") ? atoi(getenv("VSTAB_ABLATE")) : 0;
 #endif
@@ -533,6 +533,16 @@ vstab_status launch_warp_planar(const WarpArgs &a, const float params[17], int m
     const dim3 grid(tile_schedule(ta, rwb, lds_kb, tail_rounds));
     const size_t lds_bytes = (size_t)lds_kb * 1024;
     ta.lds_capacity_px = (int)((lds_bytes - 32 - 4 * 768 * (size_t)bps) * 2 / (3 * (size_t)bps));
+    if (dist) {  // the input lens's polynomial: modes 1 / 2, NV12 bytes, one rotation per frame (the caller has checked all of it)
+        if (depth != 8 || rot_bottom) return fail(VSTAB_ERR_INVALID, "launch_warp_planar: the distorted-lens kernels take NV12 and one rotation per frame");
+        with_dist_mode(map_mode, [&](auto mode) {
+            with_either<8, 4>(rwb == 8, [&](auto rows) {
+                launch_kernel(k_warp_planar<decltype(rows)::value, decltype(mode)::value, 8, VSTAB_BLEND_EXACT>, grid, dim3(256), lds_bytes, st, ta);
+            });
+        });
+        VSTAB_HIP_TRY(hipGetLastError());
+        return VSTAB_OK;
+    }
     with_map_mode(map_mode, rot_bottom != nullptr, [&](auto mode) {
         with_either<10, 8>(depth == 10, [&](auto depth_c) {
             with_either<VSTAB_BLEND_FP16, VSTAB_BLEND_EXACT>(depth == 10 && blend == VSTAB_BLEND_FP16, [&](auto blend_c) {

@@ -108,7 +108,7 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
         qx = q.x, qy = q.y;
     } else {
         float ax, ay;
-        if constexpr (BASE == MAP_CREATEMAP_CL || BASE == MAP_FISH_TO_RECT || BASE == MAP_CREATEMAP_CL_OPENCL) {
+        if constexpr (BASE == MAP_CREATEMAP_CL || BASE == MAP_FISH_TO_RECT || BASE == MAP_CREATEMAP_CL_OPENCL || BASE == MAP_FISHD_TO_RECT) {
             // The box needs the map to a fraction of a pixel only (it has a pixel of margin and never decides a result),
             // so the probe uses the approximate reciprocal / rsqrt instructions and fused operations: a third of the
             // dependent chain of the exact evaluation, on the one wave the other three are waiting for.
@@ -138,9 +138,15 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
             g = __builtin_fmaf(g, s2, -0.33333125710487366f);
             float at = __builtin_fmaf(t * s2, g, t);
             at = inv ? 1.57079637050628662109375f - at : at;
+            if constexpr (BASE == MAP_FISHD_TO_RECT) {  // theta -> theta_d (fused: the probe decides no result)
+                const Distortion &dk = ta.p32.d;
+                const float a2 = at * at;
+                const float pd = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(dk.k4, a2, dk.k3), a2, dk.k2), a2, dk.k1);
+                at = at * __builtin_fmaf(pd, a2, 1.0f);
+            }
             const float k = at * rs;  // atan(rad) / rad; NaN on the axis (q == 0) only widens the box
             ax = __builtin_fmaf(ux * k, ta.p32.ifx32, ta.p32.icx32), ay = __builtin_fmaf(uy * k, ta.p32.ify32, ta.p32.icy32);
-            if (BASE == MAP_FISH_TO_RECT && !(wz > 0.0f)) ax = ay = __builtin_nanf("");
+            if ((BASE == MAP_FISH_TO_RECT || BASE == MAP_FISHD_TO_RECT) && !(wz > 0.0f)) ax = ay = __builtin_nanf("");
         } else {
             const float vx = div_with_rcp((float)(x0 + px) - a.p.ocx, a.p.ofx, rfx);
             const float vy = div_with_rcp((float)(y0 + py) - a.p.ocy, a.p.ofy, rfy);
@@ -187,11 +193,13 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
 // sequence of map_pixel32_x2 (vstab_device.hpp) for every pair, written step by step ACROSS the pairs, so that NP
 // independent packed instructions stand between an instruction and the one that needs its result (the compiler
 // otherwise emits the chains one after the other, separated by the s_nop a dependent packed-fp32 instruction needs).
+// DIST (MAP_FISHD_TO_RECT): distort_theta's steps (vstab_device.hpp) between the arc tangent and the division by the radius, every
+// multiplication and addition an instruction of its own.
 // ---------------------------------------------------------------------------------------------------------------------
 #define VSTAB_EACH _Pragma("unroll") for (int c = 0; c < NP; c++)
-template <int NP, bool FISH_TO_RECT>
+template <int NP, bool FISH_TO_RECT, bool DIST = false>
 __device__ __forceinline__ void map_pairs_ieee(float icx32, float icy32, float ifx32, float ify32, const f32x2 (&wx)[NP], const f32x2 (&wy)[NP],
-                                               const f32x2 (&wz)[NP], f32x2 (&ax)[NP], f32x2 (&ay)[NP]) {
+                                               const f32x2 (&wz)[NP], f32x2 (&ax)[NP], f32x2 (&ay)[NP], const Distortion &dk = Distortion()) {
     f32x2 rz[NP], e[NP], px[NP], py[NP], ex[NP], ey[NP], q[NP], y[NP], g[NP], h[NP], d[NP], rad[NP], rr[NP], t[NP], s[NP], at[NP], k[NP];
     i32x2 inv[NP];
     const f32x2 one = splat2(1.0f), half = splat2(0.5f);
@@ -235,6 +243,18 @@ __device__ __forceinline__ void map_pairs_ieee(float icx32, float icy32, float i
     VSTAB_EACH g[c] = fma2(g[c], s[c], splat2(-0.33333125710487366f));
     VSTAB_EACH at[c] = fma2(t[c] * s[c], g[c], t[c]);
     VSTAB_EACH at[c] = inv[c] ? (splat2(1.57079637050628662109375f) - at[c]) + splat2(-4.37113900018624283e-8f) : at[c];
+    if constexpr (DIST) {  // at = distort_theta(at, dk); s and g are free again
+        VSTAB_EACH s[c] = at[c] * at[c];
+        VSTAB_EACH g[c] = splat2(dk.k4) * s[c];
+        VSTAB_EACH g[c] = g[c] + splat2(dk.k3);
+        VSTAB_EACH g[c] = g[c] * s[c];
+        VSTAB_EACH g[c] = g[c] + splat2(dk.k2);
+        VSTAB_EACH g[c] = g[c] * s[c];
+        VSTAB_EACH g[c] = g[c] + splat2(dk.k1);
+        VSTAB_EACH g[c] = g[c] * s[c];
+        VSTAB_EACH g[c] = one + g[c];
+        VSTAB_EACH at[c] = at[c] * g[c];
+    }
     // k = div_with_rcp2(at, rad, rr)
     VSTAB_EACH k[c] = at[c] * rr[c];
     VSTAB_EACH e[c] = fma2(-rad[c], k[c], at[c]);
@@ -348,7 +368,7 @@ __device__ __forceinline__ void map_phase(const FusedArgs &ta, const int x, cons
         const float icx32 = ta.p32.icx32, icy32 = ta.p32.icy32, ifx32 = ta.p32.ifx32, ify32 = ta.p32.ify32;
         auto bcast = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
         auto bcast2 = [&bcast](float v, int j) { return (f32x2){bcast(v, j), bcast(v, j + 1)}; };
-        if constexpr (BASE == MAP_CREATEMAP_CL || BASE == MAP_FISH_TO_RECT) {
+        if constexpr (BASE == MAP_CREATEMAP_CL || BASE == MAP_FISH_TO_RECT || BASE == MAP_FISHD_TO_RECT) {
             // row pairs in lock-step groups of MAP_GROUP (more pairs in flight would push the kernel past 64 registers and
             // take wave slots away from the tracker and pyramid kernels that run beside it)
             constexpr int NP = RW / 2 < MAP_GROUP ? RW / 2 : MAP_GROUP;
@@ -368,7 +388,7 @@ __device__ __forceinline__ void map_phase(const FusedArgs &ta, const int x, cons
                         wz[c] = (splat2(ct.a2) + bcast2(b2_l, j)) + splat2(a.p.r[8]);
                     }
                 }
-                map_pairs_ieee<NP, BASE == MAP_FISH_TO_RECT>(icx32, icy32, ifx32, ify32, wx, wy, wz, ax, ay);
+                map_pairs_ieee<NP, BASE != MAP_CREATEMAP_CL, BASE == MAP_FISHD_TO_RECT>(icx32, icy32, ifx32, ify32, wx, wy, wz, ax, ay, ta.p32.d);
 #pragma unroll
                 for (int c = 0; c < NP; c++) {
                     const int j = 2 * (g0 + c);
