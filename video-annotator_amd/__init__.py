@@ -187,6 +187,11 @@ _L.vstabx_lk_segments.argtypes = [_pp, _c.POINTER(_sz), _i, _i, _fp, _i, _ip, _i
 
 _L.vstabx_warps_from_cache.restype = _c.c_long
 _L.vstabx_warps_from_cache.argtypes = [_vp]
+# test hooks of the corner detector (corners_fused and Stabilizer.detector_counters below)
+_L.vstabx_corners_fused.restype = _i
+_L.vstabx_corners_fused.argtypes = [_vp, _sz, _i, _i, _d, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _vp]
+_L.vstabx_detector_counters.restype = _i
+_L.vstabx_detector_counters.argtypes = [_vp, _c.POINTER(_c.c_long)]
 
 lib = _L
 ABI_VERSION = 0x56534206  # include/vstab.h: VSTAB_ABI_VERSION ("VSB" + layout version 6)
@@ -782,6 +787,28 @@ def good_features(gray, max_corners=200, quality=0.01, min_distance=30.0, detect
     return xy[:n.value].copy()
 
 
+CORNERS_FUSED_FILL = 0xA5A5A5A5A5A5A5A5  # what vstabx_corners_fused fills its key buffer with before the kernels run
+
+
+def corners_fused(gray, quality=0.01, cap=1 << 18, canary=64, w=None, h=None, stream=None):
+    """Test hook vstabx_corners_fused (not part of include/vstab.h): the one-pass detector's raw output on the (h, w) uint8 device luma
+    view `gray` (pitched views allowed) with a key buffer of exactly `cap` keys and `canary` more behind it.
+    -> (keys (cap + canary,) uint64 as the kernels left them over the fill, keys kept, tiles that spilled, per-tile survivor counts
+    (tiles_y, tiles_x) uint32).  w / h / stream are taken as given, so that a test of the refusals needs no device."""
+    h = gray.shape[0] if h is None else h
+    w = gray.shape[1] if w is None else w
+    cap, canary = int(cap), int(canary)
+    ok = 0 < cap <= 1 << 24 and 0 < canary <= 1 << 16    # (the library refuses the rest: nothing is allocated for them here)
+    keys = np.zeros(cap + canary if ok else 1, np.uint64)
+    counts = np.zeros(2, np.uint32)
+    tx, ty = max(1, (int(w) + 63) // 64), max(1, (int(h) + 30) // 31)
+    tiles = np.zeros((ty, tx) if tx * ty < 1 << 21 else (1, 1), np.uint32)   # (2^21 tiles are over 2^31 pixels: refused)
+    _check(_L.vstabx_corners_fused(gray.data_ptr(), gray.stride(0), int(w), int(h), float(quality), cap & 0xFFFFFFFF, canary & 0xFFFFFFFF,
+                                   keys.ctypes.data_as(_c.POINTER(_u64)), counts.ctypes.data_as(_c.POINTER(_c.c_uint)),
+                                   tiles.ctypes.data_as(_c.POINTER(_c.c_uint)), _stream() if stream is None else stream), "vstabx_corners_fused")
+    return keys, int(counts[0]), int(counts[1]), tiles
+
+
 def pyr_lk(prev, nxt, pts):
     h, w = prev.shape
     p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
@@ -996,6 +1023,13 @@ class Stabilizer:
     def warps_from_cache(self):
         """Test hook vstabx_warps_from_cache: warps of this handle that read the quantised map of an earlier frame with equal parameters."""
         return int(_L.vstabx_warps_from_cache(self._h))
+
+    def detector_counters(self):
+        """Test hook vstabx_detector_counters: speculative selections that found more than Tracker::SPEC_CAP candidates, fused detections
+        that overflowed the key buffer, the key capacity now in force."""
+        out = (_c.c_long * 3)()
+        _check(_L.vstabx_detector_counters(self._h, out), "vstabx_detector_counters")
+        return dict(spec_over_cap=out[0], fused_overflows=out[1], key_capacity=out[2])
 
     def set_border_mode(self, border_mode):
         """vstab_set_border_mode: cv::remap's borderMode for the frames pulled from now on."""

@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "vstab_hostlogic.hpp"
+#include "vstab_pipeline.hpp"
 #include "vstab_track_host.hpp"
 
 using namespace vstab;
@@ -152,6 +153,54 @@ __attribute__((visibility("default"))) int vstabx_lk_segments(const void *const 
             std::memcpy(host_rec + (size_t)k * n * 4, t.host_records(launches[s], i), (size_t)n * 16);
             VSTAB_HIP_TRY(hipMemcpy(dev_rec + (size_t)k * n * 4, t.dev_records(launches[s], i), (size_t)n * 16, hipMemcpyDeviceToHost));
         }
+    return VSTAB_OK;
+}
+
+// THE RAW OUTPUT OF THE ONE-PASS DETECTOR (tests/test_corner_paths_gpu.py; its argument checks run without a device:
+// tests/test_corner_tiles_cpu.py).  Runs launch_corners_fused (k_corners_fused, then k_filter_keys) on the w x h device luma plane `gray`
+// with a key buffer of exactly `cap` keys followed by `canary` keys the kernels must not touch; the whole buffer is filled with the byte
+// 0xA5 first.
+//   keys_out    cap + canary keys as the kernels left them: the first min(counts_out[0], cap) are keys (float bits << 32 | raster index),
+//               unsorted; everything behind them still holds the fill
+//   counts_out  {keys kept (may exceed cap), tiles that spilled}
+//   tile_counts div_up(w, 64) * div_up(h, 31) survivor counts of k_corners_fused, tile rows first
+// Bad arguments are refused with VSTAB_ERR_INVALID before anything touches the device.
+__attribute__((visibility("default"))) int vstabx_corners_fused(const void *gray, size_t pitch, int w, int h, double quality, unsigned int cap, unsigned int canary,
+                                                                 unsigned long long *keys_out, unsigned int *counts_out, unsigned int *tile_counts,
+                                                                 void *stream) {
+    if (!gray || !keys_out || !counts_out || !tile_counts) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: bad argument");
+    if (w < 3 || h < 3 || pitch < (size_t)w) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: an image is at least 3 x 3 and its pitch at least its width");
+    if ((uint64_t)pitch * (uint64_t)h >= (1ull << 32) || (uint64_t)w * (uint64_t)h >= (1ull << 31))
+        return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: planes of 4 GiB or more and images of 2^31 pixels or more are not supported");
+    if (!(quality > 0.0) || !(quality <= 1.0)) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: quality lies in (0, 1]");
+    if (cap < 1 || cap > (1u << 24)) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: cap is 1 .. 2^24 keys");
+    if (canary < 1 || canary > (1u << 16)) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: canary is 1 .. 2^16 keys");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // launch_corners_fused lays the scratch out per tile: 256 key slots, a dense 64 x 31 float map, and -- last -- the survivor counts
+    const size_t tiles = (size_t)div_up((unsigned)w, 64u) * div_up((unsigned)h, 31u), scratch_bytes = corners_fused_scratch_bytes(w, h);
+    if (scratch_bytes != tiles * (256 * sizeof(unsigned long long) + 64 * 31 * sizeof(float) + sizeof(unsigned int)))
+        return fail(VSTAB_ERR_DEVICE, "vstabx_corners_fused: the scratch layout of launch_corners_fused is not the one this hook reads");
+    const size_t n_keys = (size_t)cap + canary;
+    DevBuf scratch, keys, small;
+    VSTAB_TRY(scratch.ensure(scratch_bytes));
+    VSTAB_TRY(keys.ensure(n_keys * sizeof(unsigned long long)));
+    VSTAB_TRY(small.ensure(256));
+    VSTAB_HIP_TRY(hipMemsetAsync(scratch.p, 0, scratch_bytes, st));
+    VSTAB_HIP_TRY(hipMemsetAsync(keys.p, 0xA5, n_keys * sizeof(unsigned long long), st));
+    VSTAB_TRY(launch_corners_fused(static_cast<const uint8_t *>(gray), pitch, w, h, quality, scratch.p, keys.as<unsigned long long>(), cap, small.as<unsigned int>(), st));
+    VSTAB_HIP_TRY(hipMemcpyAsync(keys_out, keys.p, n_keys * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    VSTAB_HIP_TRY(hipMemcpyAsync(counts_out, small.as<unsigned int>() + 4, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    VSTAB_HIP_TRY(hipMemcpyAsync(tile_counts, scratch.as<uint8_t>() + (scratch_bytes - tiles * sizeof(unsigned int)), tiles * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    VSTAB_HIP_TRY(hipStreamSynchronize(st));
+    return VSTAB_OK;
+}
+
+// The detector's bookkeeping of a handle (not in vstab_profile: the ABI layout stays): out = {speculative selections that found more
+// candidates than Tracker::SPEC_CAP (the key frame then detects synchronously), fused detections that overflowed the key buffer (the
+// two-pass detector re-ran them), the key capacity now in force (0 before the first synchronous detection)}.
+__attribute__((visibility("default"))) int vstabx_detector_counters(const vstab_handle *h, long *out) {
+    if (!h || !out) return fail(VSTAB_ERR_INVALID, "vstabx_detector_counters: bad argument");
+    out[0] = h->tracker.spec_over_cap(), out[1] = h->tracker.fused_overflows(), out[2] = (long)h->tracker.key_capacity();
     return VSTAB_OK;
 }
 }  // extern "C"

@@ -188,7 +188,10 @@ vstab_status Tracker::spec_launch(const uint8_t *gray, size_t pitch, double qual
 int Tracker::spec_select(int max_corners, double min_distance, std::vector<float> &xy, unsigned int *n_seen) {
     const unsigned int n = spec_host_.as<unsigned int>()[0];
     if (n_seen) *n_seen = n;
-    if (n > SPEC_CAP) return 3;
+    if (n > SPEC_CAP) {
+        spec_over_cap_.fetch_add(1, std::memory_order_relaxed);
+        return 3;
+    }
     select_corners(reinterpret_cast<unsigned long long *>(spec_host_.as<uint8_t>() + 64), n, max_corners, min_distance, xy);
     return 2;
 }

@@ -71,6 +71,9 @@ class Tracker {
     long selections_by_helper() const { return selections_by_helper_.load(std::memory_order_relaxed); }
     void set_two_pass_detector(bool on) { two_pass_detector_ = on; }
     long fused_overflows() const { return fused_overflows_; }
+    // (vstabx_detector_counters) speculative selections that found more than SPEC_CAP candidates; the key capacity of good_features now
+    long spec_over_cap() const { return spec_over_cap_.load(std::memory_order_relaxed); }
+    unsigned int key_capacity() const { return cap_; }
     // Host half of the speculative detection on a helper thread: waits for the kernels' results and runs the
     // sort + minimum-distance pass, so that by the time the key frame comes its corners are simply there.
     void spec_select_async(int max_corners, double min_distance);
@@ -198,6 +201,7 @@ class Tracker {
     const long spec_late_us_ = getenv("VSTAB_SPEC_HELPER_DELAY_US") ? atol(getenv("VSTAB_SPEC_HELPER_DELAY_US")) : 0;  // development: the helper wakes up late
     long selections_by_caller_ = 0;                 // speculative detections whose corners the caller selected itself / the helper thread selected
     std::atomic<long> selections_by_helper_{0};
+    std::atomic<long> spec_over_cap_{0};            // selections (by either thread) that ended in state 3 for their count
     int spec_max_ = 200;
     double spec_dist_ = 30.0;
     std::vector<float> spec_xy_;
