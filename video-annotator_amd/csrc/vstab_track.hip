@@ -459,14 +459,23 @@ __global__ void __launch_bounds__(256) k_corner_candidates(const float *__restri
 // over the image: the eigenvalue map never goes to HBM.  A workgroup owns 64 x 31 output
 // pixels and evaluates the eigenvalue on the 66 x 33 pixels around them (the halo ring is recomputed, 1.11x), so the
 // 3x3 maximum test needs nothing from a neighbour.
-//   load    72 x 38 source bytes (REFLECT_101) -> LDS
-//   deriv   68 x 36 Sobel pairs: a thread owns 4 columns x 3 rows and shares the per-row terms D = I(x+1) - I(x-1),
-//           S = I(x) k0 + (I(x-1) + I(x+1)) k1 between them (5 source rows for 3 output rows); same float operation
-//           order as k_min_eig -> identical bits; floats -> LDS
-//   eig     a thread owns 3 x 3 pixels: the 5 x 5 products go to double once, the 3-row column sums are shared by
-//           the three pixels of a row (box sums of float products are exact in double in any order: <= 48
-//           significant bits), 33 instead of 81 double additions per pixel; eigenvalue in float as k_min_eig
-//   nms     eigenvalues -> LDS; 3x3 maximum with v_max3, threshold, wave-aggregated append of 64-bit keys
+//   load    72 x 38 source bytes -> LDS, one dword per thread and round (row = index / 18 by multiply and shift)
+//   prod    68 x 35 Sobel pairs and their float products dx dx, dx dy, dy dy, each formed ONCE per derivative pixel:
+//           119 threads (two waves, the other two wait at the barrier: an idle wave issues nothing) own 4 columns x
+//           5 rows each and share the per-row terms D = I(x+1) - I(x-1), S = I(x) k0 + (I(x-1) + I(x+1)) k1 between
+//           them (7 source rows for 5 output rows); same float operation order as k_min_eig -> identical bits.  The
+//           derivative at a position mirrored across the image border has the sign of the mirrored axis flipped
+//           (k_min_eig): that leaves dx dx and dy dy as they are and flips dx dy when exactly one axis is mirrored.
+//           Three float planes -> LDS
+//   box     242 threads own 3 x 3 pixels: per quantity the 5 x 5 products are widened once and added in double (box
+//           sums of float products are exact in double in any order: <= 48 significant bits), the middle pair of a
+//           column or row is shared by the sums around it: 40 additions per quantity for 9 box sums; ONE
+//           double -> float conversion per box sum
+//   eig     behind a barrier, since the eigenvalues take the storage of the dx dx plane: eigenvalue in float as
+//           k_min_eig -> LDS, tile maximum
+//   nms     3x3 maximum with v_max3, threshold, append of 64-bit keys with one LDS atomic per wave
+// A tile whose 72 x 38 source bytes all lie inside an image of dword-aligned rows (one workgroup-uniform test) takes
+// a path without reflection arithmetic, sign flips and image-bounds tests.
 // The threshold quality * max(frame) is not known until every tile is done, so a tile filters with a LOWER bound of
 // it -- quality * max(own tile, frame maximum published so far) -- and k_filter_keys applies the final threshold to
 // the survivors.  Which candidates survive the first filter depends on timing; the set that survives the second
@@ -474,131 +483,192 @@ __global__ void __launch_bounds__(256) k_corner_candidates(const float *__restri
 // =============================================================================================
 constexpr int CF_TW = 64, CF_TH = 31;                  // output pixels per tile
 constexpr int CF_EH = CF_TH + 2;                      // eigenvalue region: 66 x 33, image (oy - 1 .., ox - 1 ..)
-constexpr int CF_DH = 36, CF_DP = 68;                 // derivative region: 68 x 36, image (oy - 2 .., ox - 2 ..); 35 rows used
-constexpr int CF_SW = 72, CF_SH = 38;                  // source tile: image (oy - 3 .., ox - 4 ..)
+constexpr int CF_DH = 35, CF_DP = 68;                 // derivative-product region: 68 x 35, image (oy - 2 .., ox - 2 ..)
+constexpr int CF_SW = 72, CF_SH = 38;                  // source tile: image (oy - 3 .., ox - 4 ..); 37 rows used
 constexpr int CF_EP = 67;
 constexpr int CF_SLOTS = 256;                          // key slots per tile (a tile holds at most 1984 / 4 strict 3x3 maxima; fine noise reaches ~220)
+constexpr int CF_PC = CF_DP / 4, CF_PR = 5, CF_PG = CF_DH / CF_PR;  // prod: 17 column groups of 4, 7 row groups of 5
+constexpr int CF_BX = 22, CF_BY = 11;                  // box / eig: 22 x 11 blocks of 3 x 3
+static_assert(CF_PC * 4 == CF_DP && CF_PG * CF_PR == CF_DH && CF_DH + 2 <= CF_SH && CF_PC * CF_PG <= 256, "prod ownership covers the region");
+static_assert(CF_BX * 3 == CF_TW + 2 && CF_BY * 3 == CF_EH && CF_EH + 2 == CF_DH && CF_BX * CF_BY <= 256, "box ownership covers the region");
+static_assert(CF_EH * CF_EP <= CF_DH * CF_DP, "the eigenvalues fit the plane they take over");
 
-__device__ __forceinline__ float ubyte_f32(uint32_t v, int b) { return (float)((v >> (8 * b)) & 255u); }  // v_cvt_f32_ubyteN
+// e / d for 0 <= e < n as one 24-bit multiply and a shift (the compiler's division by a constant is a 64-bit multiply-high)
+constexpr bool cf_div_magic_ok(int d, int magic, int n) {
+    for (int e = 0; e < n; e++)
+        if (((e * magic) >> 16) != e / d) return false;
+    return true;
+}
+static_assert(cf_div_magic_ok(CF_SW / 4, 3641, CF_SH * (CF_SW / 4) + 256) && cf_div_magic_ok(CF_PC, 3856, 256) && cf_div_magic_ok(CF_BX, 2979, 256),
+              "division constants");
 
-// threshold + 3x3 maximum test over the eigenvalues in LDS.  DENSE = false: survivors are appended to the tile's slots
+// byte B of v as a float.  Written as the instruction: from (float)((v >> 8 B) & 255) the compiler builds the differences and sums of two
+// bytes in integers (an SDWA operation and a conversion apiece) where the six floats of a row, converted once, serve all of them.
+// Static VALU instructions of the prod phase per wave with the plain C++ form / with this one: 329 / 272 on the interior path, 410 / 348
+// on the border path (hipcc of ROCm 7.2, -O3; count the instructions between the second and third barrier of a path to see whether a
+// later compiler still needs it -- results are the same bits either way).
+template <int B>
+__device__ __forceinline__ float ubyte_f32(uint32_t v) {
+    float f;
+    if (B == 0) asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(f) : "v"(v));
+    if (B == 1) asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(f) : "v"(v));
+    if (B == 2) asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(f) : "v"(v));
+    if (B == 3) asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(f) : "v"(v));
+    return f;
+}
+
+// threshold + 3x3 maximum test over the eigenvalues in LDS: lane = column, a wave walks its 8 rows (the last wave 7) with a rolling
+// row maximum.  DENSE = false: survivors are appended to the tile's slots, one LDS atomic per wave for the rows' survivors together
 // (*bcount counts all of them, also those past the last slot); DENSE = true: every pixel of the tile is written, the
-// eigenvalue for a survivor and -inf otherwise.
-template <bool DENSE>
+// eigenvalue for a survivor and -inf otherwise.  INTERIOR: every pixel of the tile is an interior pixel of the image.
+template <bool DENSE, bool INTERIOR>
 __device__ __forceinline__ void cf_nonmax(const float (&es)[CF_EH][CF_EP], int tid, int ox, int oy, int w, int h, float thr_lb,
                                           unsigned long long *__restrict__ my_slots, unsigned int *bcount, float *__restrict__ dense) {
-    const int tx = tid & 63, r0 = (tid >> 6) * 8;
+    const int tx = tid & 63, r0 = __builtin_amdgcn_readfirstlane(tid >> 6) * 8;  // the rows are the wave's: scalar
     const int x = ox + tx;
+    const bool x_in = INTERIOR || (x >= 1 && x < w - 1);
     float rm0 = fmaxf(fmaxf(es[r0][tx], es[r0][tx + 1]), es[r0][tx + 2]);
     float c1 = es[r0 + 1][tx + 1];
     float rm1 = fmaxf(fmaxf(es[r0 + 1][tx], c1), es[r0 + 1][tx + 2]);
+    float v[8];
+    bool cand[8];
+    unsigned long long ballot[8];
+    unsigned int total = 0;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const int ty = r0 + r;
-        if (ty >= CF_TH) break;  // wave-uniform (the last wave owns 7 rows)
-        const float c2 = es[ty + 2][tx + 1];
-        const float rm2 = fmaxf(fmaxf(es[ty + 2][tx], c2), es[ty + 2][tx + 2]);
+        const bool row = r < 7 || ty < CF_TH;            // scalar; false only for the last wave's eighth row
+        const int below = r < 7 ? ty + 2 : min(ty + 2, CF_EH - 1);
+        const float c2 = es[below][tx + 1];
+        const float rm2 = fmaxf(fmaxf(es[below][tx], c2), es[below][tx + 2]);
         const float m = fmaxf(fmaxf(rm0, rm1), rm2);
         const int y = oy + ty;
-        const bool cand = x >= 1 && y >= 1 && x < w - 1 && y < h - 1 && c1 > thr_lb && c1 == m;
+        cand[r] = row && x_in && (INTERIOR || (y >= 1 && y < h - 1)) && c1 > thr_lb && c1 == m;
         if (DENSE) {
-            dense[ty * CF_TW + tx] = cand ? c1 : -__builtin_inff();
+            if (row) dense[ty * CF_TW + tx] = cand[r] ? c1 : -__builtin_inff();
         } else {
-            const unsigned long long ballot = __ballot(cand);
-            if (ballot) {
-                unsigned int base = 0;
-                if (tx == 0) base = atomicAdd(bcount, (unsigned int)__popcll(ballot));  // LDS
-                base = __builtin_amdgcn_readfirstlane(base);
-                const unsigned int slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0));
-                if (cand && slot < CF_SLOTS) my_slots[slot] = ((unsigned long long)__float_as_uint(c1) << 32) | (unsigned int)(y * w + x);
-            }
+            v[r] = c1;
+            ballot[r] = __builtin_amdgcn_ballot_w64(cand[r]);
+            total += (unsigned int)__popcll(ballot[r]);
         }
         rm0 = rm1, rm1 = rm2, c1 = c2;
     }
+    if (!DENSE && total) {
+        unsigned int base = 0;
+        if (tx == 0) base = atomicAdd(bcount, total);  // LDS
+        base = __builtin_amdgcn_readfirstlane(base);
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            if (!ballot[r]) continue;
+            const unsigned int slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot[r] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot[r], 0));
+            if (cand[r] && slot < CF_SLOTS) my_slots[slot] = ((unsigned long long)__float_as_uint(v[r]) << 32) | (unsigned int)((oy + r0 + r) * w + x);
+            base += (unsigned int)__popcll(ballot[r]);
+        }
+    }
 }
 
-__global__ void __launch_bounds__(256) k_corners_fused(const uint8_t *__restrict__ src, size_t pitch, int w, int h, double quality,
-                                                       unsigned int *__restrict__ max_key, unsigned long long *__restrict__ slots,
-                                                       unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok) {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];
-    __shared__ __attribute__((aligned(16))) float dxs[CF_DH][CF_DP], dys[CF_DH][CF_DP];
-    __shared__ float es[CF_EH][CF_EP];
-    __shared__ int bmax;
-    __shared__ unsigned int bcount;
-    const int tid = threadIdx.x;
-    const int ox = blockIdx.x * CF_TW, oy = blockIdx.y * CF_TH;
-    // frame maximum published so far (biased bits): a lower bound of the final one.  Device-scope load: the atomics
-    // of other XCDs do not pass through this XCD's L2.
-    const unsigned int seen = __hip_atomic_load(max_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) bmax = INT_MIN, bcount = 0;
-    for (int e = tid; e < CF_SH * (CF_SW / 4); e += 256) {
-        const int ry = e / (CF_SW / 4), rd = e - ry * (CF_SW / 4);
-        reinterpret_cast<uint32_t *>(&tile[ry][0])[rd] = load4_reflect(src, (uint32_t)pitch, w, h, ox - 4 + 4 * rd, oy - 3 + ry, vec_ok != 0);
+// load: the source tile, dword e of it <-> row e / 18, bytes 4 (e % 18) ..; a thread's three loads are in flight together
+constexpr int CF_LOADS = (CF_SH * (CF_SW / 4) + 255) / 256;
+template <bool INTERIOR>
+__device__ __forceinline__ void cf_load(uint32_t (&v)[CF_LOADS], const uint8_t *__restrict__ src, uint32_t pitch, int w, int h, int ox, int oy, bool vec_ok,
+                                        int tid) {
+#pragma unroll
+    for (int k = 0; k < CF_LOADS; k++) {
+        const int e = tid + 256 * k;
+        const int ry = __mul24(e, 3641) >> 16, rd = e - ry * (CF_SW / 4);
+        v[k] = 0;
+        if (e >= CF_SH * (CF_SW / 4)) continue;
+        if (INTERIOR) v[k] = *reinterpret_cast<const uint32_t *>(src + ((uint32_t)(oy - 3 + ry) * pitch + (uint32_t)(ox - 4 + 4 * rd)));
+        else v[k] = load4_reflect(src, pitch, w, h, ox - 4 + 4 * rd, oy - 3 + ry, vec_ok);
     }
-    __syncthreads();
+}
+__device__ __forceinline__ void cf_store(uint8_t (&tile)[CF_SH][CF_SW], const uint32_t (&v)[CF_LOADS], int tid) {
+#pragma unroll
+    for (int k = 0; k < CF_LOADS; k++)
+        if (tid + 256 * k < CF_SH * (CF_SW / 4)) reinterpret_cast<uint32_t *>(&tile[0][0])[tid + 256 * k] = v[k];
+}
+
+// prod: product entry (r, q) <-> image (oy - 2 + r, ox - 2 + q) <-> tile[r + 1][q + 2]; a thread owns q = 4c .. 4c+3, r = 5g .. 5g+4
+template <bool INTERIOR>
+__device__ __forceinline__ void cf_products(const uint8_t (&tile)[CF_SH][CF_SW], float (&prod)[3][CF_DH][CF_DP], int ox, int oy, int w, int h, int tid) {
+    if (tid >= CF_PC * CF_PG) return;
     const float scale = (float)(1.0 / (4.0 * 3.0 * 255.0));
     const float k0 = 2.0f * scale, k1 = scale;
-    if (tid < 17 * 12) {
-        const int g = tid / 17, c = tid - g * 17;
-        // derivative entry (r, q) <-> image (oy - 2 + r, ox - 2 + q) <-> tile[r + 1][q + 2]; this thread: q = 4c .. 4c+3, r = 3g .. 3g+2
-        float D[5][4], S[5][4];
+    const int g = __mul24(tid, 3856) >> 16, c = tid - g * CF_PC;
+    uint32_t flip_x[4];  // the sign bit where the column lies outside the image
 #pragma unroll
-        for (int j = 0; j < 5; j++) {
-            const uint32_t *row = reinterpret_cast<const uint32_t *>(&tile[3 * g + j][4 * c]);
-            const uint32_t lo = row[0], hi = row[1];  // bytes 4c .. 4c+7; columns q-1 .. q+4 are bytes 1 .. 6
-            const float f[6] = {ubyte_f32(lo, 1), ubyte_f32(lo, 2), ubyte_f32(lo, 3), ubyte_f32(hi, 0), ubyte_f32(hi, 1), ubyte_f32(hi, 2)};
+    for (int i = 0; i < 4; i++) {
+        const int gx = ox - 2 + 4 * c + i;
+        flip_x[i] = !INTERIOR && (gx < 0 || gx >= w) ? 0x80000000u : 0u;
+    }
+    float D[CF_PR + 2][4], S[CF_PR + 2][4];
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                D[j][i] = f[i + 2] - f[i];
-                S[j][i] = f[i + 1] * k0 + (f[i] + f[i + 2]) * k1;
-            }
-        }
+    for (int j = 0; j < CF_PR + 2; j++) {
+        const uint32_t *row = reinterpret_cast<const uint32_t *>(&tile[CF_PR * g + j][4 * c]);
+        const uint32_t lo = row[0], hi = row[1];  // bytes 4c .. 4c+7; columns q-1 .. q+4 are bytes 1 .. 6
+        const float f[6] = {ubyte_f32<1>(lo), ubyte_f32<2>(lo), ubyte_f32<3>(lo), ubyte_f32<0>(hi), ubyte_f32<1>(hi), ubyte_f32<2>(hi)};
 #pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const int gy = oy - 2 + 3 * g + r;
-            const bool fy = gy < 0 || gy >= h;
-            float dx[4], dy[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int gx = ox - 2 + 4 * c + i;
-                dx[i] = (D[r][i] + D[r + 2][i]) * k1 + D[r + 1][i] * k0;
-                dy[i] = S[r + 2][i] - S[r][i];
-                if (gx < 0 || gx >= w) dx[i] = -dx[i];
-                if (fy) dy[i] = -dy[i];
-            }
-            *reinterpret_cast<float4 *>(&dxs[3 * g + r][4 * c]) = make_float4(dx[0], dx[1], dx[2], dx[3]);
-            *reinterpret_cast<float4 *>(&dys[3 * g + r][4 * c]) = make_float4(dy[0], dy[1], dy[2], dy[3]);
+        for (int i = 0; i < 4; i++) {
+            D[j][i] = f[i + 2] - f[i];
+            S[j][i] = f[i + 1] * k0 + (f[i] + f[i + 2]) * k1;
         }
     }
-    __syncthreads();
-    int best = INT_MIN;
-    if (tid < 22 * 11) {
-        const int by = tid / 22, bx = tid - by * 22;
-        // eigenvalue entry (ey, ex) <-> image (oy - 1 + ey, ox - 1 + ex) <-> derivative rows ey .. ey+2, columns ex .. ex+2
-        float a_[5][5], b_[5][5];
 #pragma unroll
-        for (int j = 0; j < 5; j++)
+    for (int r = 0; r < CF_PR; r++) {
+        const int gy = oy - 2 + CF_PR * g + r;
+        const uint32_t flip_y = !INTERIOR && (gy < 0 || gy >= h) ? 0x80000000u : 0u;
+        float xx[4], xy[4], yy[4];
 #pragma unroll
-            for (int i = 0; i < 5; i++) a_[j][i] = dxs[3 * by + j][3 * bx + i], b_[j][i] = dys[3 * by + j][3 * bx + i];
-        float sum[3][3][3];  // [quantity][row][column] box sums rounded to float
+        for (int i = 0; i < 4; i++) {
+            const float dx = (D[r][i] + D[r + 2][i]) * k1 + D[r + 1][i] * k0;
+            const float dy = S[r + 2][i] - S[r][i];
+            xx[i] = dx * dx, yy[i] = dy * dy;
+            xy[i] = INTERIOR ? dx * dy : __uint_as_float(__float_as_uint(dx * dy) ^ flip_x[i] ^ flip_y);
+        }
+        *reinterpret_cast<float4 *>(&prod[0][CF_PR * g + r][4 * c]) = make_float4(xx[0], xx[1], xx[2], xx[3]);
+        *reinterpret_cast<float4 *>(&prod[1][CF_PR * g + r][4 * c]) = make_float4(xy[0], xy[1], xy[2], xy[3]);
+        *reinterpret_cast<float4 *>(&prod[2][CF_PR * g + r][4 * c]) = make_float4(yy[0], yy[1], yy[2], yy[3]);
+    }
+}
+
+// the three sums of three consecutive terms out of five, exact in double: the middle pair is shared by the first two
+__device__ __forceinline__ void cf_sum3of5(double p0, double p1, double p2, double p3, double p4, double &s0, double &s1, double &s2) {
+    const double m = p1 + p2;
+    s0 = p0 + m, s1 = m + p3, s2 = (p2 + p3) + p4;
+}
+
+// box + eig: eigenvalue entry (ey, ex) <-> image (oy - 1 + ey, ox - 1 + ex) <-> product rows ey .. ey+2, columns ex .. ex+2; a thread owns
+// ex = 3bx .. 3bx+2, ey = 3by .. 3by+2.  `es` is the storage of prod[0]: every thread has its box sums in registers before any
+// eigenvalue is stored.  Returns the thread's maximum over the in-image eigenvalues (int-bit order, as k_min_eig).
+template <bool INTERIOR>
+__device__ __forceinline__ int cf_eigenvalues(const float (&prod)[3][CF_DH][CF_DP], float (&es)[CF_EH][CF_EP], int ox, int oy, int w, int h, int tid) {
+    const bool active = tid < CF_BX * CF_BY;
+    const int t = min(tid, CF_BX * CF_BY - 1);  // the 14 threads without a block add up the last one's sums and store nothing
+    const int by = __mul24(t, 2979) >> 16, bx = t - by * CF_BX;
+    float sum[3][3][3];  // [quantity][row][column] box sums rounded to float
+    {
 #pragma unroll
         for (int q = 0; q < 3; q++) {
             double col[3][5];
 #pragma unroll
-            for (int j = 0; j < 5; j++)
+            for (int i = 0; i < 5; i++) {
+                double p[5];
 #pragma unroll
-                for (int i = 0; i < 5; i++) {
-                    const float u = q == 2 ? b_[j][i] : a_[j][i], v = q == 0 ? a_[j][i] : b_[j][i];
-                    const double p = (double)(u * v);
+                for (int j = 0; j < 5; j++) p[j] = (double)prod[q][3 * by + j][3 * bx + i];
+                cf_sum3of5(p[0], p[1], p[2], p[3], p[4], col[0][i], col[1][i], col[2][i]);
+            }
 #pragma unroll
-                    for (int e = 0; e < 3; e++)
-                        if (j >= e && j <= e + 2) col[e][i] = j == e ? p : col[e][i] + p;
-                }
+            for (int e = 0; e < 3; e++) {
+                double s[3];
+                cf_sum3of5(col[e][0], col[e][1], col[e][2], col[e][3], col[e][4], s[0], s[1], s[2]);
 #pragma unroll
-            for (int e = 0; e < 3; e++)
-#pragma unroll
-                for (int i = 0; i < 3; i++) sum[q][e][i] = (float)((col[e][i] + col[e][i + 1]) + col[e][i + 2]);
+                for (int i = 0; i < 3; i++) sum[q][e][i] = (float)s[i];
+            }
         }
+    }
+    __syncthreads();
+    int best = INT_MIN;
+    if (active) {
 #pragma unroll
         for (int e = 0; e < 3; e++)
 #pragma unroll
@@ -607,9 +677,34 @@ __global__ void __launch_bounds__(256) k_corners_fused(const uint8_t *__restrict
                 const float ev = (a + cc) - sqrtf((a - cc) * (a - cc) + b * b);
                 es[3 * by + e][3 * bx + i] = ev;
                 const int gx = ox - 1 + 3 * bx + i, gy = oy - 1 + 3 * by + e;
-                if (gx >= 0 && gx < w && gy >= 0 && gy < h) best = max(best, __float_as_int(ev));
+                if (INTERIOR || (gx >= 0 && gx < w && gy >= 0 && gy < h)) best = max(best, __float_as_int(ev));
             }
     }
+    return best;
+}
+
+template <bool INTERIOR>
+__device__ __forceinline__ void cf_tile(uint8_t (&tile)[CF_SH][CF_SW], float (&prod)[3][CF_DH][CF_DP], int &bmax, unsigned int &bcount, unsigned int &bseen,
+                                        const uint8_t *__restrict__ src, uint32_t pitch, int w, int h, double quality, unsigned int *__restrict__ max_key,
+                                        unsigned long long *__restrict__ slots, unsigned int *__restrict__ tile_counts, float *__restrict__ spill, bool vec_ok) {
+    float (&es)[CF_EH][CF_EP] = *reinterpret_cast<float (*)[CF_EH][CF_EP]>(&prod[0][0][0]);
+    const int tid = threadIdx.x;
+    const int ox = blockIdx.x * CF_TW, oy = blockIdx.y * CF_TH;
+    uint32_t v[CF_LOADS];
+    cf_load<INTERIOR>(v, src, pitch, w, h, ox, oy, vec_ok, tid);
+    if (tid == 0) bmax = INT_MIN, bcount = 0;
+    cf_store(tile, v, tid);
+    // frame maximum published so far (biased bits): a lower bound of the final one.  Device-scope load: the atomics
+    // of other XCDs do not pass through this XCD's L2.  Every workgroup reads this one address, and the memory side serves
+    // such reads one after the other: ONE lane asks -- in the last wave, which has no part in the products, and behind
+    // the tile's loads, so that no wait for those waits for this -- and nothing needs the answer before the eigenvalues
+    // are done.
+    unsigned int seen = 0;
+    if (tid == 255) seen = __hip_atomic_load(max_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    cf_products<INTERIOR>(tile, prod, ox, oy, w, h, tid);
+    __syncthreads();
+    int best = cf_eigenvalues<INTERIOR>(prod, es, ox, oy, w, h, tid);
     // tile maximum (same int-bit order as k_min_eig)
     best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x111, 0xf, 0xf, false));
     best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x112, 0xf, 0xf, false));
@@ -618,23 +713,42 @@ __global__ void __launch_bounds__(256) k_corners_fused(const uint8_t *__restrict
     best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x142, 0xa, 0xf, false));
     best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x143, 0xc, 0xf, false));
     if ((tid & 63) == 63) atomicMax(&bmax, best);
+    if (tid == 255) bseen = seen;
     __syncthreads();
     const int tile_max = bmax;
+    seen = bseen;
     // Every workgroup hitting one address costs ~11 ns apiece on this part (all XCDs meet at the memory side):
     // only a tile that raises the maximum it saw publishes.
     if (tid == 0 && ((unsigned int)tile_max ^ 0x80000000u) > seen) atomicMax(max_key, (unsigned int)tile_max ^ 0x80000000u);
     // lower bound of the frame threshold; only meaningful for a non-negative maximum (float order == int order)
     const int lb_bits = max(tile_max, (int)(seen ^ 0x80000000u));
     const float thr_lb = lb_bits >= 0 ? (float)((double)__int_as_float(lb_bits) * quality) : -__builtin_inff();
-    // 3x3 maximum test: lane = column, a wave walks 8 rows with a rolling row-maximum
     const int tile_idx = blockIdx.y * gridDim.x + blockIdx.x;
-    cf_nonmax<false>(es, tid, ox, oy, w, h, thr_lb, slots + (size_t)tile_idx * CF_SLOTS, &bcount, nullptr);
+    cf_nonmax<false, INTERIOR>(es, tid, ox, oy, w, h, thr_lb, slots + (size_t)tile_idx * CF_SLOTS, &bcount, nullptr);
     __syncthreads();
     const unsigned int n = bcount;
     if (tid == 0) tile_counts[tile_idx] = n;
     // A tile with more survivors than slots (an eigenvalue plateau: a smooth ramp, a periodic texture) leaves them as a
     // dense 64 x 31 map instead (-inf = not a survivor); k_filter_keys scans that with the final threshold.
-    if (n > CF_SLOTS) cf_nonmax<true>(es, tid, ox, oy, w, h, thr_lb, nullptr, nullptr, spill + (size_t)tile_idx * (CF_TW * CF_TH));
+    if (n > CF_SLOTS) cf_nonmax<true, INTERIOR>(es, tid, ox, oy, w, h, thr_lb, nullptr, nullptr, spill + (size_t)tile_idx * (CF_TW * CF_TH));
+}
+
+// the tile's 72 x 38 source bytes at image (oy - 3 .., ox - 4 ..) lie inside the image, and its rows are dword aligned
+__device__ __forceinline__ bool cf_interior(int ox, int oy, int w, int h, int vec_ok) {
+    return vec_ok && ox >= 4 && ox - 4 + CF_SW <= w && oy >= 3 && oy - 3 + CF_SH <= h;
+}
+
+__global__ void __launch_bounds__(256) k_corners_fused(const uint8_t *__restrict__ src, size_t pitch, int w, int h, double quality,
+                                                       unsigned int *__restrict__ max_key, unsigned long long *__restrict__ slots,
+                                                       unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];
+    __shared__ __attribute__((aligned(16))) float prod[3][CF_DH][CF_DP];  // dx dx, dx dy, dy dy; then the eigenvalues in place of dx dx
+    __shared__ int bmax;
+    __shared__ unsigned int bcount, bseen;
+    if (cf_interior(blockIdx.x * CF_TW, blockIdx.y * CF_TH, w, h, vec_ok))
+        cf_tile<true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true);
+    else
+        cf_tile<false>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0);
 }
 
 // k_filter_keys -- the final threshold quality * max(frame) over the survivors of k_corners_fused.  A workgroup
