@@ -508,9 +508,9 @@ VSTAB_API vstab_status vstab_draw_markers(void *dst, size_t pitch, int width, in
  * perimeter, which holds for a map that does not fold.  Anything else is VSTAB_ERR_INVALID ("the distortion must keep theta_d increasing
  * on [0, pi/2]"), from every entry point below.  map_mode: VSTAB_MAP_FISH_TO_RECT or VSTAB_MAP_FISH_TO_FISH; any other is
  * VSTAB_ERR_INVALID ("distortion belongs to a fisheye input (map modes 1 and 2)").
- * Not served with distortion: the output camera, the rotation per output row, 10-bit planes, and the nearest, cubic, Lanczos and border
- * warps as fused kernels -- the stateless vstab_remap_* operators take the planes of vstab_create_map_dist, which covers every resampler
- * and border mode.
+ * Served with distortion: INTER_LINEAR with the constant border (vstab_warp_nv12_dist), and every 8-bit resampler with every border mode as
+ * a fused kernel (vstab_warp_nv12_dist_ex).  Not served with distortion: the output camera, the rotation per output row, 10-bit planes,
+ * INTER_NEAREST, and NV12 through BGR -- the stateless vstab_remap_* operators take the planes of vstab_create_map_dist.
  * ------------------------------------------------------------------------------------------ */
 /* vstab_fisheye_undistort_points through the distorted lens. */
 VSTAB_API vstab_status vstab_fisheye_undistort_points_d(const double *pts, int n, const double K[9], const double D[4], const double *R,
@@ -530,6 +530,27 @@ VSTAB_API vstab_status vstab_quantised_map_dist(void *qmap, int dst_width, int d
 VSTAB_API vstab_status vstab_warp_nv12_dist(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
                                             const float params[17], const float dist[4], int map_mode, int out_format, void *dst, size_t pitch_dst,
                                             void *dst_uv, size_t pitch_dst_uv, int dst_width, int dst_height, void *stream);
+/* vstab_warp_nv12_dist for every 8-bit resampler and border mode.  resample: VSTAB_RESAMPLE_DEFAULT (INTER_LINEAR), _CUBIC or _LANCZOS4;
+ * border_mode: VSTAB_BORDER_CONSTANT, _REPLICATE, _REFLECT or _REFLECT_101; map_mode: 1 or 2; out_format: VSTAB_OUT_BGR8 or
+ * VSTAB_OUT_NV12_PLANAR.  Nothing new is defined: the frame is the map of "Lens distortion" above (tests/distort_def.py: maps) fed to the
+ * resampler's own definition -- vstab_warp_nv12_cubic / _lanczos4 (tests/cubic_def.py, tests/lanczos4_def.py: remap_* and planar_mapped),
+ * vstab_warp_nv12_border (tests/border_def.py) and the border modes of the cubic and Lanczos resamplers (tests/resample_border_def.py).
+ * DEFAULT with CONSTANT is vstab_warp_nv12_dist itself, same bytes; DEFAULT with another mode runs vstab_warp_nv12_border's tile kernel,
+ * CUBIC / LANCZOS4 the resampler's tile kernel for that border, each with the distorted map: the tile's source box is the exact
+ * reduction over the tile's own map, as without distortion.  The quantised map (vstab_quantised_map_dist) serves DEFAULT + CONSTANT only.
+ * Every refusal is VSTAB_ERR_INVALID, made before any device work, in this order, each message behind "vstab_warp_nv12_dist_ex: ":
+ *   1. dist NULL: "null pointer";
+ *   2. vstab_warp_nv12_cubic_border's checks in its order: "null pointer" (y, uv, dst, params), "source must be even-sized and <= 32767",
+ *      "output size must be in [1, 32767]", "the distorted-lens warp emits VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR (NV12 through BGR is
+ *      not served)", "border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)", "pitch smaller
+ *      than row", "plane-wise output needs a chroma plane of 2*ceil(width/2) bytes per row", "chroma plane must be 2-B aligned";
+ *   3. "resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)";
+ *   4. every map mode but 1 and 2, known or not: "distortion belongs to a fisheye input (map modes 1 and 2)";
+ *   5. "the distortion must keep theta_d increasing on [0, pi/2]". */
+VSTAB_API vstab_status vstab_warp_nv12_dist_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                               const float params[17], const float dist[4], int map_mode, int resample, int border_mode,
+                                               int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dst_width,
+                                               int dst_height, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The pipeline object: drop-in for FrameSourceWarp behind the FrameSource pull interface
@@ -786,9 +807,19 @@ VSTAB_API vstab_status vstab_set_border_mode_ex(vstab_handle *h, int border_mode
  * frame that carries a readout_rotation is refused and consumed (as INTER_NEAREST does).  D = 0 gives the frames of a handle without the call.
  * Allowed on a handle with lens_mode 1, in_projection VSTAB_PROJ_FISH, resample VSTAB_RESAMPLE_DEFAULT, 8-bit pixels and the constant
  * border, before the first pull; anything else, a bad K and coefficients that are not accepted are VSTAB_ERR_INVALID, the message naming
- * the cause, and the handle is unchanged.  On a calibrated handle vstab_set_border_mode / _ex refuse a non-constant mode with
- * VSTAB_ERR_INVALID. */
+ * the cause, and the handle is unchanged.  On a handle calibrated through this call vstab_set_border_mode / _ex refuse a non-constant mode
+ * with VSTAB_ERR_INVALID (vstab_set_input_calibration_ex below lifts the two restrictions). */
 VSTAB_API vstab_status vstab_set_input_calibration(vstab_handle *h, const double K[9], const double D[4]);
+/* vstab_set_input_calibration for every 8-bit resampler and border mode: the same call and the same refusals, message for message under
+ * this name, except that a handle with resample VSTAB_RESAMPLE_CUBIC or _LANCZOS4 and a handle with a non-constant border mode set are
+ * accepted.  The warp is vstab_warp_nv12_dist_ex with the handle's resampler and the border mode in force at the pull (the quantised map
+ * serves VSTAB_RESAMPLE_DEFAULT with VSTAB_BORDER_CONSTANT only); on a handle calibrated this way vstab_set_border_mode / _ex behave as on
+ * a handle without a calibration, and the mode may change between pulls.  What stays refused (VSTAB_ERR_INVALID, the handle unchanged):
+ * lens_mode other than 1, an input that is not a fisheye lens, pixel_depth 10, a call after the first pull, a bad K, coefficients that are
+ * not accepted.  vstab_pull_frame_nv12 is refused before a frame is taken, a frame that carries a readout_rotation is refused and consumed.
+ * The rotation estimate and the `debug` markers go through the distorted lens as with vstab_set_input_calibration: they do not depend on
+ * the resampler. */
+VSTAB_API vstab_status vstab_set_input_calibration_ex(vstab_handle *h, const double K[9], const double D[4]);
 /* Synchronises the stream, folds all pending event pairs into the sums and returns them. */
 VSTAB_API vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out);
 

@@ -171,11 +171,13 @@ SIGNATURES = {
     "vstab_warp_nv12_lanczos4_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_set_border_mode_ex": (_i, [_vp, _i]),
     "vstab_set_input_calibration": (_i, [_vp, _dp, _dp]),
+    "vstab_set_input_calibration_ex": (_i, [_vp, _dp, _dp]),
     "vstab_fisheye_undistort_points_d": (_i, [_dp, _i, _dp, _dp, _dp, _dp, _dp]),
     "vstab_estimate_rotation_d": (_i, [_fp, _fp, _i, _dp, _dp, _dp, _u64, _dp, _ip]),
     "vstab_create_map_dist": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _vp]),
     "vstab_quantised_map_dist": (_i, [_vp, _i, _i, _fp, _fp, _i, _vp]),
     "vstab_warp_nv12_dist": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_warp_nv12_dist_ex": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -516,6 +518,27 @@ def warp_nv12_dist(nv12, params, dist, dw, dh, mode=MAP_FISH_TO_RECT, out_format
     yo, co = out
     _check(_L.vstab_warp_nv12_dist(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(out_format), yo.data_ptr(), yo.stride(0),
                                    co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_dist")
+    return yo, co
+
+
+def warp_nv12_dist_ex(nv12, params, dist, dw, dh, mode=MAP_FISH_TO_RECT, resample=RESAMPLE_DEFAULT, border_mode=BORDER_CONSTANT, out_format=OUT_BGR8,
+                      out=None):
+    """vstab_warp_nv12_dist_ex: warp_nv12_dist with a resampler (RESAMPLE_DEFAULT, _CUBIC, _LANCZOS4) and a border mode (BORDER_*).  OUT_BGR8 ->
+    (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma) tensors."""
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    p, d = np.ascontiguousarray(params, np.float32), np.ascontiguousarray(dist, np.float32).reshape(4)
+    if out_format == OUT_BGR8:
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
+        _check(_L.vstab_warp_nv12_dist_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), OUT_BGR8,
+                                          out.data_ptr(), out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_dist_ex")
+        return out
+    if out is None:
+        out = nv12_out_planes(dw, dh, nv12.device)
+    yo, co = out
+    _check(_L.vstab_warp_nv12_dist_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), int(out_format),
+                                      yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_dist_ex")
     return yo, co
 
 
@@ -944,9 +967,10 @@ class Stabilizer:
     source for `total` pulls) or a Python iterable of such tensors (python callback source)."""
 
     def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, calibration=None,
-                 **cfg_kw):
+                 calibration_ex=None, **cfg_kw):
         """border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
         calibration: (K, D) for set_input_calibration right after create, applied after border_mode (K None keeps the camera from in_dfov).
+        calibration_ex: the same through set_input_calibration_ex (every resampler and border mode).
         hold (iterable sources): vstab_frame.hold -- how many further pulls each tensor is kept alive and unchanged
         for; from smooth_radius + 14 on the library uses the tensors in place instead of copying them.
         bit_depth / readouts (list sources): P010 frames as int16 tensors of shape (h * 3 / 2, w); one 3x3 read-out
@@ -1010,15 +1034,24 @@ class Stabilizer:
             self.set_border_mode_ex(border_mode)
         if calibration is not None:
             self.set_input_calibration(*calibration)
+        if calibration_ex is not None:
+            self.set_input_calibration_ex(*calibration_ex)
+
+    def _calibrate(self, fn, K, D):
+        Kc = None if K is None else np.ascontiguousarray(K, np.float64).reshape(9)
+        Dc = np.ascontiguousarray(np.broadcast_to(np.asarray(D, np.float64), (4,)))
+        _check(getattr(_L, fn)(self._h, None if Kc is None else _dptr(Kc), _dptr(Dc)), fn)
+        if Kc is not None:
+            self.K_in = Kc.reshape(3, 3).copy()
 
     def set_input_calibration(self, K, D):
         """vstab_set_input_calibration: the calibrated input lens, camera matrix K (3x3, or None) and k1..k4 (a scalar 0 stands for four zeros),
         before the first pull."""
-        Kc = None if K is None else np.ascontiguousarray(K, np.float64).reshape(9)
-        Dc = np.ascontiguousarray(np.broadcast_to(np.asarray(D, np.float64), (4,)))
-        _check(_L.vstab_set_input_calibration(self._h, None if Kc is None else _dptr(Kc), _dptr(Dc)), "vstab_set_input_calibration")
-        if Kc is not None:
-            self.K_in = Kc.reshape(3, 3).copy()
+        self._calibrate("vstab_set_input_calibration", K, D)
+
+    def set_input_calibration_ex(self, K, D):
+        """vstab_set_input_calibration_ex: set_input_calibration for INTER_LINEAR, INTER_CUBIC and INTER_LANCZOS4 handles, with any border mode."""
+        self._calibrate("vstab_set_input_calibration_ex", K, D)
 
     def warps_from_cache(self):
         """Test hook vstabx_warps_from_cache: warps of this handle that read the quantised map of an earlier frame with equal parameters."""

@@ -635,27 +635,40 @@ vstab_status vstab_get_output_info(const vstab_handle *h, int *width, int *heigh
     return VSTAB_OK;
 }
 
-vstab_status vstab_set_input_calibration(vstab_handle *h, const double K[9], const double D[4]) {
-    const std::string n = "vstab_set_input_calibration: ";
+}  // extern "C"
+
+// vstab_set_input_calibration / _ex: `resamplers`: whether a CUBIC or LANCZOS4 handle and a border mode are served (vstab_warp_nv12_dist_ex)
+static vstab_status set_input_calibration(vstab_handle *h, const double K[9], const double D[4], const char *fn, bool resamplers) {
+    const std::string n = std::string(fn) + ": ";
     if (!h || !D) return fail(VSTAB_ERR_INVALID, n + "null argument");
     const vstab_config &c = h->cfg;
     if (c.lens_mode != 1) return fail(VSTAB_ERR_INVALID, n + "a calibration belongs to lens_mode 1 (the preset path derives its output camera from the input's)");
     if (c.in_projection != VSTAB_PROJ_FISH) return fail(VSTAB_ERR_INVALID, n + "distortion belongs to a fisheye input (in_projection VSTAB_PROJ_FISH)");
     // (lens_mode 1 is INTER_LINEAR: vstab_create)
-    if (c.resample != VSTAB_RESAMPLE_DEFAULT)
+    if (!resamplers && c.resample != VSTAB_RESAMPLE_DEFAULT)
         return fail(VSTAB_ERR_INVALID, n + "the distorted-lens warp resamples with VSTAB_RESAMPLE_DEFAULT, this handle with " + resample_name(c.resample));
     if (c.pixel_depth == 10) return fail(VSTAB_ERR_INVALID, n + "the distorted-lens warp takes 8-bit pixels, this is a pixel_depth 10 handle");
-    if (h->border_mode != VSTAB_BORDER_CONSTANT)
+    if (!resamplers && h->border_mode != VSTAB_BORDER_CONSTANT)
         return fail(VSTAB_ERR_INVALID, n + "the distorted-lens warp has the constant border, this handle has another border mode set (vstab_set_border_mode)");
     if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the calibration must be set before the first pull");
     if (K && !(std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5]) && K[0] > 0 && K[4] > 0 && K[1] == 0 && K[3] == 0 &&
                K[6] == 0 && K[7] == 0 && K[8] == 1))
         return fail(VSTAB_ERR_INVALID, n + "K must be a camera matrix with fx, fy > 0, zero skew and last row 0 0 1");
-    VSTAB_TRY(check_distortion("vstab_set_input_calibration", D));
+    VSTAB_TRY(check_distortion(fn, D));
     if (K) std::memcpy(h->Kin.m, K, sizeof(h->Kin.m));
     for (int i = 0; i < 4; i++) h->dist[i] = D[i], h->dist32[i] = (float)D[i];
-    h->calibrated = true;
+    h->calibrated = true, h->calibrated_borders = resamplers;
     return VSTAB_OK;
+}
+
+extern "C" {
+
+vstab_status vstab_set_input_calibration(vstab_handle *h, const double K[9], const double D[4]) {
+    return set_input_calibration(h, K, D, "vstab_set_input_calibration", false);
+}
+
+vstab_status vstab_set_input_calibration_ex(vstab_handle *h, const double K[9], const double D[4]) {
+    return set_input_calibration(h, K, D, "vstab_set_input_calibration_ex", true);
 }
 
 // test hook (not part of include/vstab.h): how many of the handle's warps read the quantised map written for an earlier frame

@@ -130,6 +130,7 @@ struct vstab_handle {
     // vstab_set_input_calibration: the input lens's k1..k4 (fp64 for the rotation estimate and the markers, fp32 for the map); Kin is then the
     // calibrated camera matrix where one was given
     bool calibrated = false, pulled = false;  // pulled: a pull has started to consume frames
+    bool calibrated_borders = false;          // calibrated through vstab_set_input_calibration_ex: vstab_set_border_mode / _ex as without a calibration
     double dist[4] = {0, 0, 0, 0};
     float dist32[4] = {0, 0, 0, 0};
     const double *distortion() const { return calibrated ? dist : nullptr; }

@@ -166,6 +166,16 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
         }
         return st;
     }
+    // a calibrated handle: vstab_warp_nv12_dist_ex with the handle's resampler and the pull's border mode (INTER_LINEAR with the constant
+    // border: vstab_warp_nv12_dist, or the quantised map of an earlier frame).  A frame that carries a read-out rotation is consumed, as
+    // INTER_NEAREST consumes it below
+    if (H->calibrated) {
+        if (P.rot_bottom) return refuse_launch("a calibrated handle (vstab_set_input_calibration) warps frames without a read-out rotation");
+        if (P.cached)
+            return vstab_warp_nv12_mapped(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, H->qmap.p, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+        return vstab_warp_nv12_dist_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, H->dist32, mode, H->cfg.resample, P.border_mode, out_format, P.dst, P.pitch_dst,
+                                       P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+    }
     if (border && !resampled)
         return vstab_warp_nv12_border(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.border_mode, P.dst, P.pitch_dst, P.dst_uv,
                                       P.pitch_dst_uv, ow, oh, H->stream);
@@ -183,13 +193,8 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
         if (out_format != VSTAB_OUT_BGR8 || P.rot_bottom) return refuse_launch("INTER_NEAREST emits 8-bit BGR frames without a read-out rotation");
         return vstab_warp_nv12_nearest_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, P.dst, P.pitch_dst, ow, oh, H->stream);
     }
-    // (a calibrated handle: a frame that carries a read-out rotation is consumed, as INTER_NEAREST consumes it above)
-    if (H->calibrated && P.rot_bottom) return refuse_launch("a calibrated handle (vstab_set_input_calibration) warps frames without a read-out rotation");
     if (P.cached)
         return vstab_warp_nv12_mapped(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, H->qmap.p, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
-    if (H->calibrated)
-        return vstab_warp_nv12_dist(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, H->dist32, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh,
-                                    H->stream);
     if (P.rot_bottom)
         return vstab_warp_nv12_rs(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh,
                                   H->stream);
@@ -282,7 +287,7 @@ static vstab_status set_border_mode(vstab_handle *h, int border_mode, const char
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)");
     if (border_mode != VSTAB_BORDER_CONSTANT && (h->cfg.pixel_depth == 10 || h->cfg.interpolation == 0 || (!resamplers && h->cfg.resample != VSTAB_RESAMPLE_DEFAULT)))
         return fail(VSTAB_ERR_UNSUPPORTED, std::string(fn) + ": border modes other than VSTAB_BORDER_CONSTANT are served for 8-bit pixels with " + served);
-    if (border_mode != VSTAB_BORDER_CONSTANT && h->calibrated)
+    if (border_mode != VSTAB_BORDER_CONSTANT && h->calibrated && !h->calibrated_borders)
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": a calibrated handle (vstab_set_input_calibration) warps with VSTAB_BORDER_CONSTANT");
     h->border_mode = border_mode;
     return VSTAB_OK;

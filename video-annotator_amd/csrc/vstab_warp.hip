@@ -654,6 +654,27 @@ vstab_status vstab_warp_nv12_dist(const void *y, size_t pitch_y, const void *uv,
                      dist);
 }
 
+vstab_status vstab_warp_nv12_dist_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                     const float dist[4], int map_mode, int resample, int border_mode, int out_format, void *dst, size_t pitch_dst,
+                                     void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
+    const std::string n = "vstab_warp_nv12_dist_ex";
+    if (!dist) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
+    // vstab_warp_nv12_dist's order: check_warp_nv12's checks (handed a mode it accepts), the resampler, the map mode, the coefficients
+    const bool fish_in = map_mode_takes_distortion(map_mode);
+    CubicArgs c;
+    VSTAB_TRY(check_warp_nv12(n, "the distorted-lens warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr,
+                              fish_in ? map_mode : (int)VSTAB_MAP_FISH_TO_RECT, out_format, &border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, c,
+                              dist));
+    if (resample != VSTAB_RESAMPLE_DEFAULT && resample != VSTAB_RESAMPLE_CUBIC && resample != VSTAB_RESAMPLE_LANCZOS4)
+        return fail(VSTAB_ERR_INVALID, n + ": resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)");
+    if (!fish_in) return fail(VSTAB_ERR_INVALID, n + ": distortion belongs to a fisheye input (map modes 1 and 2)");
+    VSTAB_TRY(check_distortion(n, dist));
+    if (resample == VSTAB_RESAMPLE_CUBIC) return launch_warp_cubic_dist(c, map_mode, out_format, border_mode, stream);
+    if (resample == VSTAB_RESAMPLE_LANCZOS4) return launch_warp_lanczos4_dist(c, map_mode, out_format, border_mode, stream);
+    if (border_mode != VSTAB_BORDER_CONSTANT) return launch_warp_border_dist(c, map_mode, out_format, border_mode, stream);
+    return vstab_warp_nv12_dist(y, pitch_y, uv, pitch_uv, sw, sh, params, dist, map_mode, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
+}
+
 vstab_status vstab_warp_nv12_mapped(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const void *qmap,
                                     int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh,
                                     void *stream) {

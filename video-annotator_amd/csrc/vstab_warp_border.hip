@@ -204,6 +204,33 @@ vstab_status preload_border_kernels() {
     return VSTAB_OK;
 }
 
+// k_warp_border of checked arguments on its grid.  rs: a rotation per output row, served (and checked) for map modes 0, 1 and 5 only.
+// dist: ba.c.p32.d holds the input lens's coefficients (map modes 1 and 2), no rotation per row, a non-constant border: INTER_LINEAR
+// with the constant border and a distorted lens is k_warp_fused / k_warp_planar (vstab_warp_nv12_dist).
+static vstab_status launch_warp_border(const BorderArgs &ba, int map_mode, bool dist, bool rs, int out_format, int border_mode, void *stream) {
+    with_map_mode_or_dist(map_mode, dist, [&](auto mode) {
+        with_border_mode(border_mode, [&](auto border) {
+            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
+                with_bool(rs, [&](auto rs_c) {
+                    constexpr int MODE = decltype(mode)::value, BORDER = decltype(border)::value;
+                    constexpr bool RS = decltype(rs_c)::value;
+                    if constexpr (ModeTraits<MODE>::dist ? !RS && BORDER != VSTAB_BORDER_CONSTANT : !RS || map_mode_fish_to_pinhole(MODE))
+                        launch_tiles(k_warp_border<MODE, decltype(planar)::value, RS, BORDER>, ba, ba.c.w.dw, ba.c.w.dh, stream);
+                });
+            });
+        });
+    });
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
+vstab_status launch_warp_border_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream) {
+    BorderArgs ba;
+    ba.c = c;
+    fill_rolling_shutter(ba, nullptr, nullptr, c.w.dh);
+    return launch_warp_border(ba, map_mode, true, false, out_format, border_mode, stream);
+}
+
 }  // namespace vstab
 
 using namespace vstab;
@@ -237,20 +264,7 @@ vstab_status vstab_warp_nv12_border(const void *y, size_t pitch_y, const void *u
                                             out_format, &border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, ba.c);
     if (st != VSTAB_OK) return st;
     fill_rolling_shutter(ba, params, rot_bottom, dh);
-    with_map_mode(map_mode, [&](auto mode) {
-        with_border_mode(border_mode, [&](auto border) {
-            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
-                with_bool(rot_bottom != nullptr, [&](auto rs) {
-                    constexpr int MODE = decltype(mode)::value;
-                    // the rotation per output row is served (and checked above) for map modes 0, 1 and 5 only
-                    if constexpr (!decltype(rs)::value || map_mode_fish_to_pinhole(MODE))
-                        launch_tiles(k_warp_border<MODE, decltype(planar)::value, decltype(rs)::value, decltype(border)::value>, ba, dw, dh, stream);
-                });
-            });
-        });
-    });
-    VSTAB_HIP_TRY(hipGetLastError());
-    return VSTAB_OK;
+    return launch_warp_border(ba, map_mode, false, rot_bottom != nullptr, out_format, border_mode, stream);
 }
 
 }  // extern "C"

@@ -214,6 +214,10 @@ vstab_status preload_cubic_kernels() {
     return VSTAB_OK;
 }
 
+vstab_status launch_warp_cubic_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream) {
+    return launch_warp_resample<CubicKernels>(c, map_mode, true, out_format, border_mode, stream);
+}
+
 }  // namespace vstab
 
 using namespace vstab;

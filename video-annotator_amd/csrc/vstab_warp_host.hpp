@@ -104,6 +104,12 @@ void with_dist_mode(int map_mode, F &&f) {
     if (map_mode == VSTAB_MAP_FISH_TO_RECT) f(mode_constant<MAP_FISHD_TO_RECT>{});
     else f(mode_constant<MAP_FISHD_TO_FISH>{});
 }
+// a checked mode of either kind: dist (the coefficients are in MapParams32::d): its MAP_FISHD_* form
+template <typename F>
+void with_map_mode_or_dist(int map_mode, bool dist, F &&f) {
+    if (dist) with_dist_mode(map_mode, f);
+    else with_map_mode(map_mode, f);
+}
 // the fisheye -> pinhole maps (modes 0, 1, 5): the only ones that take a rotation per output row (so the only ones with a MAP_RS_*
 // form), and the only ones the 10-bit tiled kernels serve.  Asked of the public VSTAB_MAP_* values by the argument checks and of the
 // kernels' MAP_* template values (a base mode: map_mode_base) by the launchers: the two enumerations agree on 0 .. 5, and the internal
@@ -154,10 +160,11 @@ void launch_tiles(Kernel kernel, const Args &args, int dw, int dh, void *stream)
 }
 
 // The NV12 warps' arguments, checked, into the kernel argument.  who: the subject of the output-format message ("the cubic warp "; "").
-// rot_bottom: vstab_warp_nv12_border's rotation per output row, else null.  border_mode: null where the entry point has none.
+// rot_bottom: vstab_warp_nv12_border's rotation per output row, else null.  border_mode: null where the entry point has none.  dist: the
+// input lens's k1..k4 (vstab_warp_nv12_dist_ex, which checks them and the mode they belong to itself, behind these checks), else null.
 inline vstab_status check_warp_nv12(const std::string &n, const char *who, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh,
                                     const float params[17], const float *rot_bottom, int map_mode, int out_format, const int *border_mode, void *dst,
-                                    size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh, CubicArgs &c) {
+                                    size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh, CubicArgs &c, const float *dist = nullptr) {
     if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
     if (sw <= 0 || sh <= 0 || (sw & 1) || (sh & 1) || sw > 32767 || sh > 32767)
         return fail(VSTAB_ERR_INVALID, n + ": source must be even-sized and <= 32767");
@@ -176,7 +183,7 @@ inline vstab_status check_warp_nv12(const std::string &n, const char *who, const
         return fail(VSTAB_ERR_INVALID, n + ": plane-wise output needs a chroma plane of 2*ceil(width/2) bytes per row");
     if (!ptr_aligned(uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, n + ": chroma plane must be 2-B aligned");
     fill_warp_args(c.w, y, pitch_y, uv, pitch_uv, sw, sh, params, dst, pitch_dst, planar ? dst_uv : nullptr, planar ? pitch_dst_uv : 0, dw, dh);
-    c.p32 = map_params32(params);
+    c.p32 = map_params32(params, dist);
     return VSTAB_OK;
 }
 
@@ -210,6 +217,19 @@ inline vstab_status check_remap(const std::string &n, const void *src, size_t pi
 // The entry points of a resampler (cubic, Lanczos) over its kernels KS: KS::warp<MODE, PLANAR, BORDER>() and KS::remap<CN, BORDER>(), the
 // kernel of each combination (BORDER_CONSTANT: the kernels that carry the border value).  border_mode null: the constant-border entry points.
 // ---------------------------------------------------------------------------------------------------------------------
+// the warp kernel of checked arguments on its grid; dist: c.p32.d holds the input lens's coefficients (map modes 1 and 2)
+template <typename KS>
+vstab_status launch_warp_resample(const CubicArgs &c, int map_mode, bool dist, int out_format, int border_mode, void *stream) {
+    with_map_mode_or_dist(map_mode, dist, [&](auto mode) {
+        with_border_mode(border_mode, [&](auto border) {
+            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
+                launch_tiles(KS::template warp<decltype(mode)::value, decltype(planar)::value, decltype(border)::value>(), c, c.w.dw, c.w.dh, stream);
+            });
+        });
+    });
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
 template <typename KS>
 vstab_status warp_resample(const char *name, const char *who, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh,
                            const float params[17], int map_mode, int out_format, const int *border_mode, void *dst, size_t pitch_dst, void *dst_uv,
@@ -218,16 +238,13 @@ vstab_status warp_resample(const char *name, const char *who, const void *y, siz
     const vstab_status st = check_warp_nv12(name, who, y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr, map_mode, out_format, border_mode, dst, pitch_dst,
                                             dst_uv, pitch_dst_uv, dw, dh, c);
     if (st != VSTAB_OK) return st;
-    with_map_mode(map_mode, [&](auto mode) {
-        with_border_mode(border_mode ? *border_mode : VSTAB_BORDER_CONSTANT, [&](auto border) {
-            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
-                launch_tiles(KS::template warp<decltype(mode)::value, decltype(planar)::value, decltype(border)::value>(), c, dw, dh, stream);
-            });
-        });
-    });
-    VSTAB_HIP_TRY(hipGetLastError());
-    return VSTAB_OK;
+    return launch_warp_resample<KS>(c, map_mode, false, out_format, border_mode ? *border_mode : VSTAB_BORDER_CONSTANT, stream);
 }
+// vstab_warp_nv12_dist_ex's kernels, one launcher per resampler's unit: c checked and filled by check_warp_nv12 with the coefficients, the
+// map mode 1 or 2.  launch_warp_border_dist: the non-constant modes (INTER_LINEAR with the constant border is vstab_warp_nv12_dist).
+vstab_status launch_warp_cubic_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream);
+vstab_status launch_warp_lanczos4_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream);
+vstab_status launch_warp_border_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream);
 
 template <typename KS>
 vstab_status remap_resample(const char *name, const void *src, size_t pitch_src, int sw, int sh, int channels, const void *map_x, size_t pitch_x,

@@ -204,6 +204,10 @@ vstab_status preload_lanczos4_kernels() {
     return VSTAB_OK;
 }
 
+vstab_status launch_warp_lanczos4_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream) {
+    return launch_warp_resample<Lanczos4Kernels>(c, map_mode, true, out_format, border_mode, stream);
+}
+
 }  // namespace vstab
 
 using namespace vstab;
