@@ -1,11 +1,12 @@
 """Development helper (tools/dev/libvstab_dev.so, `make -C video-annotator_amd dev`): eight wall-clock stamps per wave of
 one launch of the fused warp kernel -> how long each phase of a tile takes, workgroup durations, residency over time.
-env: QW, QH, QMODE as tools/quick_warp_time.py."""
+usage: python tools/wg_timeline.py [development library]; env: QW, QH, QMODE as tools/quick_warp_time.py; QDUMP=file.npz also saves
+blockIdx, start and end (us) of every workgroup that ran a tile, for fits of the per-tile cost (profiles/dead_tiles_bands_4k.txt)."""
 import ctypes, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import devlib
-vs = devlib.load()
+vs = devlib.load(sys.argv[1] if len(sys.argv) > 1 else None)
 w, h = int(os.environ.get("QW", 3840)), int(os.environ.get("QH", 2160))
 mode = int(os.environ.get("QMODE", 0))
 K = vs.get_preset_camera(4, w, h); Ko, (cw, ch) = vs.get_output_camera(K, w, h)
@@ -30,6 +31,7 @@ t -= t0
 start, end = t[:, :, 0].min(axis=1), t[:, :, 7].max(axis=1)
 dur = end - start
 print(f"workgroups {len(t)}  span {end.max():.2f} us")
+if os.environ.get("QDUMP"): np.savez(os.environ["QDUMP"], blk=blk, start=start, end=end)
 print(f"workgroup duration us: median {np.median(dur):.2f} p10 {np.percentile(dur,10):.2f} p90 {np.percentile(dur,90):.2f} max {dur.max():.2f}; "
       f"sum {dur.sum():.0f} us -> mean residency {dur.sum()/end.max():.0f} workgroups")
 names = ["probe + barrier", "load issue", "map", "convert", "barrier", "sample + blend", "store"]

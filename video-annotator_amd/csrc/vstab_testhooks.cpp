@@ -4,6 +4,7 @@
 #include "vstab_hostlogic.hpp"
 #include "vstab_pipeline.hpp"
 #include "vstab_track_host.hpp"
+#include "vstab_warp_bands.hpp"
 
 using namespace vstab;
 
@@ -192,6 +193,49 @@ __attribute__((visibility("default"))) int vstabx_corners_fused(const void *gray
     VSTAB_HIP_TRY(hipMemcpyAsync(counts_out, small.as<unsigned int>() + 4, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipMemcpyAsync(tile_counts, scratch.as<uint8_t>() + (scratch_bytes - tiles * sizeof(unsigned int)), tiles * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipStreamSynchronize(st));
+    return VSTAB_OK;
+}
+
+// The cost-weighted XCD bands of the fused warp (vstab_warp_bands.hpp; tests/test_band_schedule_cpu.py), no device needed.
+// weighted_bands for a dw x dh output: out = {band_y[9], split_y[8], tiles_x, grid}.  cost NULL: tile_schedule's even bands.
+__attribute__((visibility("default"))) int vstabx_weighted_bands(int dw, int dh, int rwb, int lds_kb, double tail_rounds, const uint32_t *cost, int n_cost,
+                                                                  int *out) {
+    if (!out || dw < 1 || dh < 1 || (rwb != 4 && rwb != 8) || lds_kb < 1 || !(tail_rounds >= 0.0) || n_cost < 0)
+        return fail(VSTAB_ERR_INVALID, "vstabx_weighted_bands: bad argument");
+    FusedArgs ta = {};
+    ta.w.dw = dw, ta.w.dh = dh;
+    const unsigned grid = cost ? weighted_bands(ta, rwb, lds_kb, tail_rounds, cost, n_cost) : tile_schedule(ta, rwb, lds_kb, tail_rounds);
+    for (int k = 0; k < 9; k++) out[k] = ta.band_y[k];
+    for (int k = 0; k < 8; k++) out[9 + k] = ta.split_y[k];
+    out[17] = ta.tiles_x, out[18] = (int)grid;
+    return VSTAB_OK;
+}
+// band_costs: the model's cost of every half-height tile row (64 x ts tiles); cost has div_up(dh, ts) entries.
+__attribute__((visibility("default"))) int vstabx_band_costs(const float *params, int nan_behind, int sw, int sh, int dw, int dh, int ts, uint32_t *cost, int n_cost) {
+    if (!params || !cost || sw < 1 || sh < 1 || dw < 1 || dh < 1 || (ts != 8 && ts != 16) || n_cost != (int)div_up((unsigned)dh, (unsigned)ts))
+        return fail(VSTAB_ERR_INVALID, "vstabx_band_costs: bad argument");
+    std::vector<uint32_t> c;
+    band_costs(params, nan_behind != 0, sw, sh, dw, dh, ts, c);
+    std::copy(c.begin(), c.end(), cost);
+    return VSTAB_OK;
+}
+// n launches (17 parameters each) of one sw x sh -> dw x dh warp through a fresh BandCache: out = 19 integers per launch as
+// vstabx_weighted_bands; counts = {hits, misses, entries}.
+__attribute__((visibility("default"))) int vstabx_band_cache_run(const float *params, int n, int sw, int sh, int dw, int dh, int map_mode, int rwb, int lds_kb,
+                                                                  double tail_rounds, int *out, long *counts) {
+    if (!params || !out || !counts || n < 1 || sw < 1 || sh < 1 || dw < 1 || dh < 1 || (rwb != 4 && rwb != 8) || lds_kb < 1 || !(tail_rounds >= 0.0))
+        return fail(VSTAB_ERR_INVALID, "vstabx_band_cache_run: bad argument");
+    BandCache cache;
+    for (int i = 0; i < n; i++) {
+        FusedArgs ta = {};
+        ta.w.sw = sw, ta.w.sh = sh, ta.w.dw = dw, ta.w.dh = dh;
+        const unsigned grid = cache.schedule(ta, params + 17 * (size_t)i, map_mode, rwb, lds_kb, tail_rounds);
+        int *o = out + 19 * (size_t)i;
+        for (int k = 0; k < 9; k++) o[k] = ta.band_y[k];
+        for (int k = 0; k < 8; k++) o[9 + k] = ta.split_y[k];
+        o[17] = ta.tiles_x, o[18] = (int)grid;
+    }
+    counts[0] = cache.hits, counts[1] = cache.misses, counts[2] = (long)cache.entries.size();
     return VSTAB_OK;
 }
 

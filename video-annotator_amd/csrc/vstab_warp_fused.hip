@@ -23,12 +23,17 @@
 // Bit-exactness never depends on the box: a pixel whose 2x2 footprint is not inside the staged box (degenerate
 // rotations, a box larger than the LDS budget, unaligned planes) is sampled straight from global memory with per-tap
 // zeroing (gather_pixel), which computes the same integers.  HBM traffic = the NV12 frame once + the output once.
+// One result does depend on the probe since the dead tiles: in the fisheye -> pinhole modes with one rotation per frame a tile whose 64
+// perimeter samples all lie beyond the same source edge by DEAD_MARGIN = 16 source pixels, with neighbouring samples less than 12 pixels
+// apart, is stored as zeros without being mapped or sampled (tile_dead_rule, vstab_warp_tile.hpp, has the bound and its argument): a third
+// of the tiles of the 4K headline output, whose pinhole picture of the fisheye frame is a pincushion.
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
 
 #include "vstab_device10.hpp"
+#include "vstab_warp_bands.hpp"
 #include "vstab_warp_host.hpp"
 #include "vstab_warp_tile.hpp"
 
@@ -63,6 +68,8 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
     constexpr int PD = PIX8 ? 2 : 1;
     constexpr bool RS = map_mode_is_rs(MODE);    // per-row rotation (BASELINE config 5)
     constexpr int BASE = map_mode_base(MODE);    // the projection pair and its arithmetic
+    // tiles wholly outside the source are found by the probe and only store zeros (tile_dead_rule, vstab_warp_tile.hpp: the modes it is argued for)
+    constexpr bool DEAD = !CACHED && !RS && (BASE == MAP_CREATEMAP_CL || BASE == MAP_CREATEMAP_CL_OPENCL || BASE == MAP_FISH_TO_RECT);
     uint32_t *const tile = smem + 8;  // smem[0..4]: the tile header (box, flag), written by wave 0
     const WarpArgs &a = ta.w;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -72,7 +79,7 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
     // ---- probe (wave 0 only; the other waves wait at the barrier without taking issue slots) --------------------
     if (wave == 0) {
         __builtin_amdgcn_s_setprio(3);  // three waves wait for this one
-        probe_tile<TH, STAGE_MAX, MODE, CACHED>(ta, x0, y0, lane, rfx, rfy, smem);
+        probe_tile<TH, STAGE_MAX, MODE, CACHED, false, 8, DEAD>(ta, x0, y0, lane, rfx, rfy, smem);
         __builtin_amdgcn_s_setprio(VSTAB_WARP_PRIO);
     }
     __syncthreads();
@@ -83,6 +90,10 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
         if (box_state == 2) return false;  // uniform
     }
     const bool use_lds = box_state == 1;
+    // uniform.  A dead tile skips load, map, convert and sample, keeps the barrier below (the half-height loop of the kernel reuses the header:
+    // without a barrier between these reads and the next probe, wave 0 could overwrite it before a late wave has read it) and runs the store
+    // code on zeros -- what the pixel-by-pixel branch below yields for a footprint outside the source
+    const bool dead = DEAD && box_state == 3;
     const int x = x0 + lane;
     VSTAB_STAMP(1);
 
@@ -139,7 +150,10 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
     VSTAB_STAMP(2);
     // ---- map: RW exact evaluations per thread (lane = column, rows y0 + wave * RW + j): vstab_warp_tile.hpp -----
     int qxb[RW], qyb[RW];  // quantised coordinates + QB
-    {
+    if (dead) {
+#pragma unroll
+        for (int j = 0; j < RW; j++) qxb[j] = qyb[j] = 0;
+    } else {
         int unused_cx[RW / 2], unused_cy[RW / 2];
         const float unused_qm[4] = {QMAGIC, QMAGIC, QMAGIC, QMAGIC};
         map_phase<RW, MODE, CACHED, false>(ta, x, y0, wave, lane, rfx, rfy, qxb, qyb, unused_cx, unused_cy, unused_qm);
@@ -218,7 +232,10 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
     // ---- sample + blend -----------------------------------------------------------------------------------------
     const bool col_live = x < a.dw;
     uint32_t out[RW];
-    {
+    if (dead) {
+#pragma unroll
+        for (int j = 0; j < RW; j++) out[j] = 0;
+    } else {
         // box origin in the registers' representation, each ONE scalar (left to itself the compiler subtracts the origin and the
         // representation's offset from every coordinate separately: 16 vector instructions per thread)
         int cx = bx0 + (QB >> 5), cy = by0 + (QB >> 5);
@@ -561,7 +578,15 @@ vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int ma
     if (const char *e = getenv("VSTAB_TAIL_ROUNDS")) tail_rounds = atof(e);
 #endif
     const size_t lds_bytes = (size_t)lds_kb * 1024;
-    const dim3 grid(tile_schedule(ta, rwb, lds_kb, tail_rounds));
+    // Bands by cost instead of by rows (vstab_warp_bands.hpp) where the launch has several rounds of tiles -- the condition that turns the
+    // tail on; a launch that is resident at once gains nothing from it -- and the kernel knows dead tiles (warp_tile: DEAD)
+    bool weighted = tail_rounds > 0.0 && !dist && !qmap && !rot_bottom &&
+                    (map_mode == MAP_CREATEMAP_CL || map_mode == MAP_FISH_TO_RECT || map_mode == MAP_CREATEMAP_CL_OPENCL);
+#ifdef VSTAB_DEV
+    if (const char *e = getenv("VSTAB_BANDS")) weighted = weighted && atoi(e) != 0;
+#endif
+    static BandCache band_cache;
+    const dim3 grid(weighted ? band_cache.schedule(ta, params, map_mode, rwb, lds_kb, tail_rounds) : tile_schedule(ta, rwb, lds_kb, tail_rounds));
     if (dist) {  // the input lens's polynomial: modes 1 / 2 to BGR8, the map always evaluated (the caller has checked all of it)
         if (nv12_out || qmap || rot_bottom) return fail(VSTAB_ERR_INVALID, "launch_warp_fused: the distorted-lens kernels emit BGR8 from one rotation per frame");
         with_dist_mode(map_mode, [&](auto mode) {

@@ -84,13 +84,67 @@ struct StageTrips {
     static constexpr int value = RW == 8 ? 3 : RW == 4 ? 2 : (RWB == 8 ? 2 : 1);
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The dead-tile rule (probe_tile<..., DEAD>): true, wave-uniformly, when every pixel of the tile certainly maps outside the source, so
+// that cv::remap's BORDER_CONSTANT makes the whole tile zero.  ax, ay = this lane's perimeter sample of 32 * map (the probe's approximate
+// arithmetic, unclamped), wz = its ray's depth.  A pixel is live iff -1 <= X <= sw - 1 and -1 <= Y <= sh - 1 (X, Y = floor(rint(32 * map) / 32)).
+//
+// Only for the fisheye -> pinhole maps with one rotation per frame (MAP_CREATEMAP_CL, MAP_CREATEMAP_CL_OPENCL, MAP_FISH_TO_RECT): a
+// homography (wz is linear in the output pixel, so wz > 0 on the perimeter samples, which include the tile's four corners, means wz > 0
+// on the whole convex tile) followed by the radial map u -> atan(|u|) u / |u|, both local diffeomorphisms.  A coordinate function of
+// such a map has no critical point inside the tile, so its extremes over the tile lie on the perimeter.  Never for a caller's map
+// (arbitrary), the distorted-lens polynomials (need not be monotone) or a rotation per row (the argument is not made for them).
+//
+//   same side   all 64 samples lie beyond the SAME source edge by at least M = DEAD_MARGIN source pixels:
+//               max X < -1 - M, or min X >= sw + M, or the same for Y.
+//   slope       2 L <= M - 1 at every sample, where L = DEAD_STRETCH max(ifx, ify) max(1 / ofx, 1 / ofy) / wz bounds the map's slope
+//               (source pixels per output pixel) wherever the ray's depth is at least that sample's wz.
+//   guard       adjacent samples (2 to 4 output pixels apart along an edge of the tile; DPP row_shr:1 inside each 16-lane side) differ
+//               by less than G = DEAD_GUARD = 3 M / 4 source pixels in X and in Y: what the slope bound promises (4 L <= 2 M - 2),
+//               observed -- a second, independent witness that the map is tame between the samples.
+//   finite      wz > 0 and |32 * map| < 2^21 at every sample (a NaN fails every comparison): else the tile is not dead.
+//
+// Why this is safe with M = 16.  (1) Every point of the perimeter lies within 2 output pixels, along an edge, of a sample (the samples are
+// 4 apart on the long edges with 3-pixel gaps at two corners, at most 3 apart on the sides), and the four corners are samples.
+// (2) Along a straight segment the ray moves by |dv| <= max(1 / ofx, 1 / ofy) per pixel, w = R v as much, and u = w_xy / wz by
+// |du| <= |dv| (1 + r) / wz with r = |u|; the radial map u -> atan(r) u / r stretches by at most atan(r) / r (its singular values are
+// atan(r) / r and 1 / (1 + r^2)), and (1 + r) atan(r) / r <= 1.6665 for every r (its maximum, at r = 2.7): DEAD_STRETCH = 1.67.  So a
+// source coordinate moves by at most L per output pixel, with wz taken at the point.  (3) wz is linear in the output pixel, so on the
+// tile it is nowhere smaller than at the corner where it is smallest, which is a sample: the L of that sample holds on the whole tile.
+// (4) Hence every perimeter point is within 2 L <= M - 1 pixels of a sample's coordinate, all of which are M beyond one edge: the whole
+// perimeter is beyond that edge by a pixel, and by the diffeomorphism so is the whole tile.  (5) The pixel that remains covers the
+// probe's arithmetic (approximate reciprocal and reciprocal square root, fused operations: a few ulp of coordinates below 2^16, under
+// 0.1 pixel) and cv::remap's rounding to 1 / 32.  At the 4K headline (input focal length twice the output's) 2 L is 6.7 at wz = 1; the
+// rule gives up where wz < 0.45.  tests/test_dead_tiles_cpu.py restates the rule in numpy and counts wrongly dead tiles against
+// the exact fp64 map at every pixel (cameras, rotations to 30 degrees, wz <= 0 inside a tile, a source smaller than a tile): none.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int DEAD_MARGIN = 16;                 // M, source pixels
+constexpr int DEAD_GUARD = 3 * DEAD_MARGIN / 4;  // G, source pixels between adjacent perimeter samples
+constexpr float DEAD_STRETCH = 1.67f;            // >= max over r of (1 + r) atan(r) / r
+// rz = 1 / wz of this lane's sample; slope32 = 32 max(ifx, ify) max(1 / ofx, 1 / ofy) (uniform)
+__device__ __forceinline__ bool tile_dead_rule(float ax, float ay, float wz, float rz, float slope32, int sw, int sh) {
+    const float pax = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ax), __float_as_int(ax), 0x111, 0xf, 0xf, false));
+    const float pay = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ay), __float_as_int(ay), 0x111, 0xf, 0xf, false));
+    const bool ok = wz > 0.0f && __builtin_fabsf(ax) < 2097152.0f && __builtin_fabsf(ay) < 2097152.0f &&
+                    __builtin_fabsf(ax - pax) < 32.0f * DEAD_GUARD && __builtin_fabsf(ay - pay) < 32.0f * DEAD_GUARD &&
+                    2.0f * DEAD_STRETCH * slope32 * rz <= 32.0f * (DEAD_MARGIN - 1);
+    const float lo = -32.0f * (1 + DEAD_MARGIN), hx = 32.0f * (float)(sw + DEAD_MARGIN), hy = 32.0f * (float)(sh + DEAD_MARGIN);
+    const uint64_t all = __builtin_amdgcn_ballot_w64(true);
+    const bool side = __builtin_amdgcn_ballot_w64(ax < lo) == all || __builtin_amdgcn_ballot_w64(ax >= hx) == all ||
+                      __builtin_amdgcn_ballot_w64(ay < lo) == all || __builtin_amdgcn_ballot_w64(ay >= hy) == all;
+    return __builtin_amdgcn_ballot_w64(ok) == all && side;
+}
+
 // The source bounding box of the output tile at (x0, y0), 64 x TH pixels, from the map on 64 perimeter pixels of the
 // tile (one per lane; a continuous map attains its coordinate extremes on the perimeter).  Lane 0 writes
 // {bx0, by0, wb, hb, use_lds} to hdr.  Run by one wave.
 // PLANAR (vstab_warp_planar.hip): the box also has to hold the taps of the chroma plane, whose positions are the luma positions of the
 // even pixels halved and rounded again -- up to three luma pixels further right / down and one further left / up than the luma taps --
 // and it is staged in blocks of BLOCK_W (a power of two) source pixels, with a border of black blocks up to two pixels outside the source.
-template <int TH, int STAGE_MAX, int MODE, bool CACHED, bool PLANAR = false, int BLOCK_W = 8>
+// DEAD (opt-in; the fused kernel's fisheye -> pinhole modes with one rotation per frame): a tile whose every pixel maps outside the
+// source is reported as state 3 and the caller stores zeros without mapping or sampling it -- the one place where the approximate probe
+// decides a result, so the rule is one-sided (see tile_dead_rule below): a tile it misses is merely done the long way.
+template <int TH, int STAGE_MAX, int MODE, bool CACHED, bool PLANAR = false, int BLOCK_W = 8, bool DEAD = false>
 __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, int lane, float rfx, float rfy, uint32_t *hdr) {
     constexpr bool RS = map_mode_is_rs(MODE);    // per-row rotation
     constexpr int BASE = map_mode_base(MODE);    // the projection pair and its arithmetic
@@ -103,13 +157,15 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
     else px = 63, py = side;
     px = min(px, a.dw - 1 - x0), py = min(py, a.dh - 1 - y0);
     int qx, qy;
+    bool dead = false;
     if constexpr (CACHED) {
         const int2 q = ta.qmap[(size_t)(y0 + py) * ta.qpitch + (x0 + px)];
         qx = q.x, qy = q.y;
     } else {
         float ax, ay;
         if constexpr (BASE == MAP_CREATEMAP_CL || BASE == MAP_FISH_TO_RECT || BASE == MAP_CREATEMAP_CL_OPENCL || BASE == MAP_FISHD_TO_RECT) {
-            // The box needs the map to a fraction of a pixel only (it has a pixel of margin and never decides a result),
+            // The box needs the map to a fraction of a pixel only (it has a pixel of margin and never decides a result; the dead-tile rule
+            // that reads the same samples has a margin of 16),
             // so the probe uses the approximate reciprocal / rsqrt instructions and fused operations: a third of the
             // dependent chain of the exact evaluation, on the one wave the other three are waiting for.
             const float vx = ((float)(x0 + px) - a.p.ocx) * rfx, vy = ((float)(y0 + py) - a.p.ocy) * rfy;
@@ -147,6 +203,7 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
             const float k = at * rs;  // atan(rad) / rad; NaN on the axis (q == 0) only widens the box
             ax = __builtin_fmaf(ux * k, ta.p32.ifx32, ta.p32.icx32), ay = __builtin_fmaf(uy * k, ta.p32.ify32, ta.p32.icy32);
             if ((BASE == MAP_FISH_TO_RECT || BASE == MAP_FISHD_TO_RECT) && !(wz > 0.0f)) ax = ay = __builtin_nanf("");
+            if constexpr (DEAD) dead = tile_dead_rule(ax, ay, wz, rz, __builtin_fmaxf(ta.p32.ifx32, ta.p32.ify32) * __builtin_fmaxf(rfx, rfy), a.sw, a.sh);
         } else {
             const float vx = div_with_rcp((float)(x0 + px) - a.p.ocx, a.p.ofx, rfx);
             const float vy = div_with_rcp((float)(y0 + py) - a.p.ocy, a.p.ofy, rfy);
@@ -185,6 +242,9 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
     if (lane == 0) {
         *reinterpret_cast<uint4 *>(hdr) = make_uint4((uint32_t)bx0, (uint32_t)by0, (uint32_t)wb, (uint32_t)hb);
         hdr[4] = stageable ? (fits ? 1u : 2u) : 0u;  // 2: the box is over the LDS budget -- a tall tile is then done as two half-height tiles
+        if constexpr (DEAD) {
+            if (dead) hdr[4] = 3u;                   // 3: every pixel of the tile is outside the source (wave-uniform)
+        }
     }
 }
 
