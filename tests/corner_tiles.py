@@ -1,4 +1,4 @@
-"""The one-pass corner detector (k_corners_fused, then k_filter_keys; csrc/vstab_track.hip) restated per tile on the oracle's
+"""The one-pass corner detector (k_corners_fused, then k_filter_keys; csrc/vstab_corners.hip) restated per tile on the oracle's
 eigenvalue map, and the frames that put its tiles, its k_filter_keys workgroups and its key buffer into a chosen state.  No GPU here.
 
 A tile is 64 x 31 output pixels (TW x TH).  k_corners_fused takes the tile's own maximum over the in-image part of the 66 x 33

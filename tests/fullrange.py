@@ -8,7 +8,7 @@ The 10-bit kernels carry value-range arguments in their comments (video-annotato
 The synthetic frames of the older tests (8-bit limited range x 4) never reach any of them.  p010_extreme_frame does, and reach()
 counts -- exactly, on the oracle's map -- how often a parameter set makes each branch decide, so that a test can commit to it.
 
-The tracker keeps its LK sums in int32 pieces whose bounds are argued in vstab_track.hip.  contrast_* build 0 / 255 content
+The tracker keeps its LK sums in int32 pieces whose bounds are argued in vstab_lk.hip.  contrast_* build 0 / 255 content
 (checkerboards, hard steps, saturated rectangles) whose window sums pass 2^31, which the smooth synthetic frames never do."""
 import numpy as np
 

@@ -1,5 +1,5 @@
 """Expected records and a CPU model of the fetch-ahead decisions of the LK tracker's multi-pair launches (k_lk_track,
-video-annotator_amd/csrc/vstab_track.hip).  Test infrastructure only (a plain module, imported by the tests).
+video-annotator_amd/csrc/vstab_lk.hip).  Test infrastructure only (a plain module, imported by the tests).
 
 Records.  A launch tracks every slot through a SEGMENT of frame pairs; a chained launch starts from the device records of its
 parent's last pair.  expected() chains oracle.pyr_lk over the slots that survive: a slot lost in pair i reports status 0 there (at

@@ -35,7 +35,9 @@ void set_launch_events(hipEvent_t start, hipEvent_t stop);
 LaunchEvents take_launch_events();
 
 // one per translation unit with kernels: loads that unit's code object now (vstab_preload_kernels)
-vstab_status preload_track_kernels();
+vstab_status preload_pyramid_kernels();
+vstab_status preload_corner_kernels();
+vstab_status preload_lk_kernels();
 vstab_status preload_warp_kernels();
 vstab_status preload_fused_kernels();
 vstab_status preload_p010_kernels();

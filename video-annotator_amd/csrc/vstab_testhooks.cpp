@@ -177,10 +177,8 @@ __attribute__((visibility("default"))) int vstabx_corners_fused(const void *gray
     if (cap < 1 || cap > (1u << 24)) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: cap is 1 .. 2^24 keys");
     if (canary < 1 || canary > (1u << 16)) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: canary is 1 .. 2^16 keys");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // launch_corners_fused lays the scratch out per tile: 256 key slots, a dense 64 x 31 float map, and -- last -- the survivor counts
-    const size_t tiles = (size_t)div_up((unsigned)w, 64u) * div_up((unsigned)h, 31u), scratch_bytes = corners_fused_scratch_bytes(w, h);
-    if (scratch_bytes != tiles * (256 * sizeof(unsigned long long) + 64 * 31 * sizeof(float) + sizeof(unsigned int)))
-        return fail(VSTAB_ERR_DEVICE, "vstabx_corners_fused: the scratch layout of launch_corners_fused is not the one this hook reads");
+    const CornersFusedScratch lay(w, h);  // the layout launch_corners_fused uses: the survivor counts are read back from it below
+    const size_t scratch_bytes = lay.bytes;
     const size_t n_keys = (size_t)cap + canary;
     DevBuf scratch, keys, small;
     VSTAB_TRY(scratch.ensure(scratch_bytes));
@@ -191,7 +189,7 @@ __attribute__((visibility("default"))) int vstabx_corners_fused(const void *gray
     VSTAB_TRY(launch_corners_fused(static_cast<const uint8_t *>(gray), pitch, w, h, quality, scratch.p, keys.as<unsigned long long>(), cap, small.as<unsigned int>(), st));
     VSTAB_HIP_TRY(hipMemcpyAsync(keys_out, keys.p, n_keys * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipMemcpyAsync(counts_out, small.as<unsigned int>() + 4, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    VSTAB_HIP_TRY(hipMemcpyAsync(tile_counts, scratch.as<uint8_t>() + (scratch_bytes - tiles * sizeof(unsigned int)), tiles * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    VSTAB_HIP_TRY(hipMemcpyAsync(tile_counts, scratch.as<uint8_t>() + lay.counts_off, (size_t)lay.tiles * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipStreamSynchronize(st));
     return VSTAB_OK;
 }

@@ -1,4 +1,4 @@
-// vstab_track.hpp -- launchers of the tracking kernels (vstab_track.hip).
+// vstab_track.hpp -- launchers of the tracking kernels (vstab_pyramid.hip, vstab_corners.hip, vstab_lk.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,6 +42,18 @@ vstab_status launch_pyr_down_x2(const uint8_t *src, size_t spitch, int sw, int s
 vstab_status launch_min_eig(const uint8_t *src, size_t pitch, int w, int h, float *eig, int *max_bits, hipStream_t s);
 vstab_status launch_corner_candidates(const float *eig, int w, int h, const int *max_bits, double quality,
                                       unsigned long long *keys, unsigned int *count, unsigned int cap, hipStream_t s);
+// The scratch of the fused detector for a w x h image, laid out in ONE place: a tile is CF_TW x CF_TH output pixels, and the buffer holds
+// CF_SLOTS key slots per tile, then a dense CF_TW x CF_TH float map per tile (written only by a tile with more survivors than slots),
+// then -- last -- one survivor count per tile (tile rows first).
+constexpr int CF_TW = 64, CF_TH = 31, CF_SLOTS = 256;
+struct CornersFusedScratch {
+    int tiles_x, tiles_y, tiles;
+    size_t slots_off, spill_off, counts_off, bytes;
+    CornersFusedScratch(int w, int h)
+        : tiles_x((w + CF_TW - 1) / CF_TW), tiles_y((h + CF_TH - 1) / CF_TH), tiles(tiles_x * tiles_y), slots_off(0),
+          spill_off(slots_off + (size_t)tiles * CF_SLOTS * sizeof(unsigned long long)), counts_off(spill_off + (size_t)tiles * CF_TW * CF_TH * sizeof(float)),
+          bytes(counts_off + (size_t)tiles * sizeof(unsigned int)) {}
+};
 size_t corners_fused_scratch_bytes(int w, int h);
 vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h, double quality, void *scratch, unsigned long long *keys,
                                   unsigned int cap, unsigned int *small, hipStream_t s);

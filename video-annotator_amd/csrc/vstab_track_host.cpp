@@ -1,5 +1,5 @@
 // vstab_track_host.cpp -- class Tracker (vstab_track_host.hpp): the pyramid sets, the host half of goodFeaturesToTrack, the speculative
-// detection with its helper thread, and the LK segment launches whose records the host polls.  Host C++; the kernels are vstab_track.hip's.
+// detection with its helper thread, and the LK segment launches whose records the host polls.  Host C++; the kernels are those of vstab_pyramid.hip, vstab_corners.hip and vstab_lk.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
