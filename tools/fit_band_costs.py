@@ -1,6 +1,7 @@
 """Development helper: least-squares fit of the per-tile cost model of the weighted XCD bands (csrc/vstab_warp_bands.hpp) to the
 per-workgroup durations tools/wg_timeline.py saved (QDUMP=file.npz), and the per-XCD table of such a dump.
-usage: python tools/fit_band_costs.py <dump.npz> even|weighted     (4K headline geometry, identity rotation, as wg_timeline.py runs it)
+usage: python tools/fit_band_costs.py <dump.npz> even|weighted [library]     (4K headline geometry, identity rotation, as wg_timeline.py
+runs it; weighted: the bands of the build that made the dump -- lib/libvstab.so, or the library named, whose cost constants may differ)
 Every workgroup is one tile of the schedule: a tall 64 x 32 tile (done whole, or as two half-height tiles when its box is over the LDS
 budget) or a half-height 64 x 16 tile of a band's tail; dead or live by the kernel's rule (tests/dead_tiles.py); a live tile's staged box
 from the exact map (tests/layouts.py tile_boxes).  Model: duration = dead | live constant per tile kind + slope * staged 8 x 2 blocks."""
@@ -25,7 +26,12 @@ p = oracle.map_params(K, Ko, np.eye(3))
 s = layouts.tile_schedule(cw, ch, rwb, lds_kb, tail)
 if kind == "weighted":
     import importlib
-    lib = importlib.import_module("video-annotator_amd").lib
+    if len(sys.argv) > 3:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import devlib
+        lib = devlib.load(sys.argv[3]).lib
+    else:
+        lib = importlib.import_module("video-annotator_amd").lib
     u32p, ip, fp = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)
     lib.vstabx_band_costs.argtypes = [fp, ctypes.c_int] + [ctypes.c_int] * 5 + [u32p, ctypes.c_int]
     lib.vstabx_weighted_bands.argtypes = [ctypes.c_int] * 4 + [ctypes.c_double, u32p, ctypes.c_int, ip]

@@ -55,16 +55,22 @@ static inline unsigned weighted_bands(FusedArgs &ta, int rwb, int lds_kb, double
     return 8u * (unsigned)share;
 }
 
-// The cost model: what a 64 x ts half-height tile (a tall tile is two of them) holds a workgroup slot for, in units of 0.01 us at the 4K
-// headline -- an XCD is through with its band when its 128 slots have worked off the durations of the band's tiles.  Fitted to the
-// per-workgroup durations of one launch (tools/wg_timeline.py, tools/fit_band_costs.py; profiles/dead_tiles_bands_4k.txt): a dead tall tile
-// lasts 2.7 us (it was 6.8 us before the kernel knew dead tiles), a live one 6.2 us on average = 4.4 us + 0.0058 us per staged block of
-// 8 x 2 source pixels.  The static instruction census (a dead tile about 70 vector instructions per thread against 630 + 157 per trip
-// of the staging loop) put a dead tile at a ninth of a live one; by the clock it is 0.44, because a dead tile is all latency -- the
-// probe's dependent chain on one wave, a barrier, the stores -- and bands weighed with the census ratios overloaded the outer XCDs
-// (32 - 33 us against 23 - 25 us in the middle).
+// The cost model: what a 64 x ts half-height tile (a tall tile is two of them) holds a workgroup slot for, in relative units -- an XCD is
+// through with its band when its 128 slots have worked off the durations of the band's tiles.  First fitted to the per-workgroup
+// durations of one launch at the 4K headline (tools/wg_timeline.py, tools/fit_band_costs.py; profiles/dead_tiles_bands_4k.txt), a unit
+// then being 0.01 us: a dead tall tile 2.7 us, a live one 4.4 us + 0.0058 us per staged block of 8 x 2 source pixels.  The static
+// instruction census (a dead tile about 70 vector instructions per thread against 630 + 157 per trip of the staging loop) put a dead
+// tile at a ninth of a live one; by the clock it was 0.44, because a dead tile is all latency -- the probe's dependent chain on one wave,
+// a barrier, the stores -- and bands weighed with the census ratios overloaded the outer XCDs (32 - 33 us against 23 - 25 us in the middle).
+// The clock's fit is a starting point, not the optimum (profiles/dead_store_4k.txt): its eight stamps are about 0.8 us of every tile, a
+// third of a dead one (a later dump reads dead tall 2.60 us, live tall 5.69 us + 0.0031 us per block), the model leaves out that
+// workgroups are dealt in blockIdx order, and the bands are a step function of the constants.  The per-block cost is therefore chosen by
+// the kernel's own time in the product build: 0.45 was the best of the four sets tried (0.58, 0.45, 0.30 per block at 135 / 220, and
+// 135 / 260 / 0.58), by 0.1 to 0.3 us of 27.4 us, at ONE shape (the 4K headline) with the identity rotation -- it rests on that; in the
+// pipeline (rotations of a shaky clip) the same constant is worth 2 % of the headline.  BAND_COST_DEAD and the floor of a live tile stay
+// as tests/test_band_schedule_cpu.py pins them.
 constexpr uint32_t BAND_COST_DEAD = 135, BAND_COST_LIVE = 220;
-constexpr double BAND_COST_PER_BLOCK = 0.58;
+constexpr double BAND_COST_PER_BLOCK = 0.45;
 
 // cost[r] of half-height tile row r (64 x ts tiles) of a dw x dh output under params (the 17 map parameters; fisheye -> pinhole): the
 // exact map in double at the tile corners; a tile whose four corners lie beyond the same source edge counts as dead, any other as live
