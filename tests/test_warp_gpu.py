@@ -37,10 +37,39 @@ def test_pack_nv12_pitched_and_unaligned(vs, cuda):
         assert np.array_equal(out, oracle.pack_nv12(ybuf[:, off:off + w], uvbuf[:, off:off + w]))
 
 
+# (w, h, pitch_y, pitch_uv, byte offset of the first sample of both planes, the copy's vector width): every rung by each of its causes
+PACK_RUNGS = [(64, 36, 64, 64, 0, 16),
+              (72, 20, 72, 72, 0, 8), (64, 20, 72, 88, 0, 8), (64, 20, 80, 96, 8, 8),        # by width, by pitch, by base
+              (36, 10, 36, 44, 0, 4), (64, 20, 68, 76, 0, 4), (64, 20, 80, 96, 4, 4),
+              (30, 18, 37, 41, 3, 1), (64, 20, 80, 96, 2, 1)]                                # by pitch and base, by base
+
+
+def test_pack_nv12_every_vector_width(vs, cuda):
+    """vstab_pack_nv12 copies with the widest of 16 / 8 / 4 / 1 bytes that both source bases, both pitches and the width are a multiple of
+    (the destination is a fresh allocation with the width as its pitch): each of the four, bit for bit, and the width itself recomputed
+    here from what the call is handed."""
+    import torch
+    rng = np.random.default_rng(7)
+    rungs = set()
+    for w, h, py, puv, off, rung in PACK_RUNGS:
+        yb = rng.integers(0, 256, off + h * py, dtype=np.uint8)
+        ub = rng.integers(0, 256, off + (h // 2) * puv, dtype=np.uint8)
+        yd = torch.as_strided(dev(yb, cuda), (h, w), (py, 1), off)
+        ud = torch.as_strided(dev(ub, cuda), (h // 2, w), (puv, 1), off)
+        facts = (yd.data_ptr(), ud.data_ptr(), yd.stride(0), ud.stride(0), w)
+        assert facts[2:] == (py, puv, w)
+        got = next(v for v in (16, 8, 4, 1) if all(f % v == 0 for f in facts))
+        assert got == rung, (w, h, py, puv, off, got)
+        rungs.add(got)
+        exp = oracle.pack_nv12(yb[off:].reshape(h, py)[:, :w], ub[off:].reshape(h // 2, puv)[:, :w])
+        assert np.array_equal(vs.pack_nv12(yd, ud).cpu().numpy(), exp), (w, h, py, puv, off)
+    assert rungs == {16, 8, 4, 1}
+
+
 def test_pack_p010_narrowing(vs, cuda):
     import torch
     rng = np.random.default_rng(3)
-    for w, h, pitch, off in [(64, 36, 64, 0), (1920, 1080, 1920, 0), (30, 18, 37, 3), (72, 20, 80, 4)]:
+    for w, h, pitch, off in [(64, 36, 64, 0), (1920, 1080, 1920, 0), (30, 18, 37, 3), (72, 20, 80, 4), (36, 10, 40, 0)]:
         yb = rng.integers(0, 65536, (h, pitch + off), dtype=np.uint16)
         ub = rng.integers(0, 65536, (h // 2, pitch + off), dtype=np.uint16)
         yd, ud = torch.from_numpy(yb.view(np.int16)).to(cuda), torch.from_numpy(ub.view(np.int16)).to(cuda)
@@ -67,6 +96,48 @@ def test_create_map_bit_exact_vs_oracle(vs, cuda):
             ox, oy = oracle.create_map(p, cw, ch)
             assert np.array_equal(mx.cpu().numpy().view(np.uint32), ox.view(np.uint32)), (w, rv)
             assert np.array_equal(my.cpu().numpy().view(np.uint32), oy.view(np.uint32)), (w, rv)
+
+
+@pytest.mark.parametrize("op", ["create_map", "create_map_ex", "create_map_dist"])
+def test_map_planes_vector_and_scalar_store(vs, cuda, op):
+    """The store the map-plane kernels share, on both of its paths: 18 x 5 entries, so the fifth group of four columns holds two.
+    Base 16-byte aligned and pitch 80: 16-byte stores, the last group's two columns one by one and the two floats of padding behind
+    them untouched.  Pitch 72, or the base 4 bytes on: every column one by one."""
+    import ctypes
+    import distort_def as dd
+    import torch
+    from test_distort_gpu import cameras
+    from test_lens_gpu import LENSES
+    cols, rows, canary = 18, 5, -12345.0
+    rv = oracle.rodrigues(ROTS[1])
+    fp = lambda a: np.ascontiguousarray(a, np.float32).ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    if op == "create_map":
+        K, Ko, _ = cams(128, 72)
+        p = oracle.map_params(K, Ko, rv)
+        ex, ey = oracle.create_map(p, cols, rows)
+        call = lambda x, y, pitch: vs.lib.vstab_create_map(x, pitch, y, pitch, cols, rows, fp(p), None)
+    elif op == "create_map_ex":   # fisheye -> fisheye of test_lens_gpu.py, the top left corner of its 481 x 271 map
+        ip, ifov, outp, ofov = LENSES[1]
+        mode = oracle.map_mode(ip, outp)
+        p = oracle.map_params(oracle.lens_camera(ip, ifov, 640, 360), oracle.lens_camera(outp, ofov, 481, 271), rv)
+        ex, ey = oracle.create_map_ex(p, cols, rows, mode)
+        call = lambda x, y, pitch: vs.lib.vstab_create_map_ex(x, pitch, y, pitch, cols, rows, fp(p), mode, None)
+    else:                         # the definition of test_distort_gpu.py, the top left corner of its 96 x 64 map
+        p = oracle.map_params(*cameras(128, 72, 96, 64, 1), rv)
+        ex, ey = dd.maps(p, cols, rows, 1, dd.D_A)
+        call = lambda x, y, pitch: vs.lib.vstab_create_map_dist(x, pitch, y, pitch, cols, rows, fp(p), fp(dd.D_A), 1, None)
+    assert not np.isnan(ex).any() and not np.isnan(ey).any()
+    for off, pitch in [(0, 80), (0, 72), (4, 80)]:       # bytes
+        bufs = [torch.full((off // 4 + rows * pitch // 4 + 4,), canary, dtype=torch.float32, device=cuda) for _ in range(2)]
+        mx, my = (torch.as_strided(b, (rows, pitch // 4), (pitch // 4, 1), off // 4) for b in bufs)
+        assert mx.data_ptr() % 16 == off and my.data_ptr() % 16 == off
+        torch.cuda.current_stream().synchronize()       # the library's null stream does not wait for the fill otherwise
+        assert call(mx.data_ptr(), my.data_ptr(), pitch) == vs.OK, vs.lib.vstab_last_error()
+        torch.cuda.synchronize()
+        for b, m, e in ((bufs[0], mx, ex), (bufs[1], my, ey)):
+            assert np.array_equal(m[:, :cols].cpu().numpy().view(np.uint32), e.view(np.uint32)), (op, off, pitch)
+            assert bool((m[:, cols:] == canary).all()), (op, off, pitch)                      # pitch 80: columns 18 and 19
+            assert bool((b[:off // 4] == canary).all()) and bool((b[off // 4 + rows * pitch // 4:] == canary).all())
 
 
 def test_create_map_nan_at_optical_axis(vs, cuda):

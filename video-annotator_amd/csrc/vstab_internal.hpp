@@ -38,6 +38,7 @@ LaunchEvents take_launch_events();
 vstab_status preload_pyramid_kernels();
 vstab_status preload_corner_kernels();
 vstab_status preload_lk_kernels();
+vstab_status preload_plane_kernels();
 vstab_status preload_warp_kernels();
 vstab_status preload_fused_kernels();
 vstab_status preload_p010_kernels();
@@ -62,7 +63,7 @@ inline vstab_status check_distortion(const std::string &n, const float D[4]) {
 // the map modes whose input camera is a fisheye lens, i.e. the ones the distortion belongs to
 inline bool map_mode_takes_distortion(int map_mode) { return map_mode == VSTAB_MAP_FISH_TO_RECT || map_mode == VSTAB_MAP_FISH_TO_FISH; }
 
-// vstab_pack_p010 with a choice of planes (vstab_warp.hip): luma_only narrows the luma plane alone -- what the 10-bit
+// vstab_pack_p010 with a choice of planes (vstab_plane_ops.hip): luma_only narrows the luma plane alone -- what the 10-bit
 // pipeline needs for its tracker
 vstab_status pack_p010_planes(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int width, int height, void *dst, bool luma_only,
                               void *stream);

@@ -42,6 +42,7 @@ vstab_status vstab_preload_kernels(void) {
     VSTAB_TRY(preload_pyramid_kernels());
     VSTAB_TRY(preload_corner_kernels());
     VSTAB_TRY(preload_lk_kernels());
+    VSTAB_TRY(preload_plane_kernels());
     VSTAB_TRY(preload_warp_kernels());
     VSTAB_TRY(preload_fused_kernels());
     VSTAB_TRY(preload_p010_kernels());

@@ -515,7 +515,7 @@ __global__ void __launch_bounds__(256, DEPTH == 10 ? 5 : (RWB == 8 || map_mode_i
 
 using namespace vstab;
 
-// Launches of the fused kernel; called by the C-ABI entry points (vstab_warp.hip, vstab_warp_p010.hip) after argument validation.
+// Launches of the fused kernel; called by launch_warp_bilinear (vstab_warp.hip) and the C-ABI entry points of vstab_warp_p010.hip after argument validation.
 namespace vstab {
 #ifdef VSTAB_DEV
 static unsigned long long *g_dev_timing = nullptr;

@@ -1,5 +1,5 @@
 // vstab_warp_host.hpp -- the host side of every warp translation unit (vstab_warp.hip, vstab_warp_fused.hip, vstab_warp_planar.hip,
-// vstab_warp_p010.hip, vstab_warp_cubic.hip, vstab_warp_lanczos4.hip, vstab_warp_border.hip): each fact once.  The alignment predicate, the
+// vstab_warp_p010.hip, vstab_warp_cubic.hip, vstab_warp_lanczos4.hip, vstab_warp_border.hip) and of vstab_plane_ops.hip: each fact once.  The alignment predicate, the
 // kernel arguments from the C arguments (MapParams, MapParams32, WarpArgs, the rolling-shutter pair, FusedArgs' common part), the conditions
 // for 32-bit staged offsets, the dispatch of a run-time mode to a template argument, the launch with a profiler's event pair, and the
 // resamplers' argument checks (every one before any launch, in one order, each message under the entry point's own name).

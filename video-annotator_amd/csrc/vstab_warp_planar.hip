@@ -501,7 +501,7 @@ __global__ void __launch_bounds__(256, RWB == 8 ? 5 : 6) k_warp_planar(FusedArgs
     for (int i = 0; i < n_half; i++) warp_tile_planar<RWB, RWB / 2, MODE, false, DEPTH, BLEND>(ta, smem, x0, ys + i * TS);
 }
 
-// Launch; called by the C-ABI entry points (vstab_warp.hip, vstab_warp_p010.hip) after argument validation.  a.y / a.uv / a.dst / a.dst_uv:
+// Launch; called by launch_warp_bilinear (vstab_warp.hip) and the C-ABI entry points of vstab_warp_p010.hip after argument validation.  a.y / a.uv / a.dst / a.dst_uv:
 // the four planes, pitches in bytes; depth 8 (NV12 bytes) or 10 (P010 words); src_vec_ok: source planes and pitches 16-byte aligned
 // (else every pixel takes the global-memory path: correct, slow); dst_vec_ok: destination planes and pitches 16-byte aligned.
 vstab_status launch_warp_planar(const WarpArgs &a, const float params[17], int map_mode, int depth, int blend, bool src_vec_ok, bool dst_vec_ok,
