@@ -551,6 +551,29 @@ VSTAB_API vstab_status vstab_warp_nv12_dist_ex(const void *y, size_t pitch_y, co
                                                const float params[17], const float dist[4], int map_mode, int resample, int border_mode,
                                                int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dst_width,
                                                int dst_height, void *stream);
+/* The whole 8-bit surface behind one call: a rotation per output row (rot_bottom, as vstab_warp_nv12_rs; NULL: one rotation), a
+ * calibrated lens (dist = k1..k4; NULL: the ideal lens), a resampler (VSTAB_RESAMPLE_DEFAULT, _CUBIC, _LANCZOS4), a border mode
+ * (VSTAB_BORDER_*), out_format VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR.  Nothing new is defined: the frame is the map fed to the
+ * resampler's own definition (tests/rs_resample_def.py).  The map without dist: map_mode's, row y with the rotation
+ * m_k = fmaf(t, rot_bottom[k] - params[8 + k], params[8 + k]), t = (float)y / (float)max(dst_height - 1, 1) (IEEE), for map modes 0, 1
+ * and 5.  With dist: the map of "Lens distortion" above, modes 1 and 2 without rot_bottom, mode 1 with it, the row's m in place of the
+ * rotation.  Chroma from map(2cx, 2cy) * 0.5f over the chroma plane's own size, as everywhere else.
+ * Where an older entry point serves the combination the call is that entry point's launch, same bytes: vstab_warp_nv12_ex, _cubic[_border],
+ * _lanczos4[_border], _border (no rot_bottom, no dist); vstab_warp_nv12_dist_ex (dist alone); vstab_warp_nv12_border (DEFAULT with
+ * rot_bottom).  CUBIC / LANCZOS4 with rot_bottom run k_warp_cubic_rs / k_warp_lanczos4_rs, DEFAULT with dist and rot_bottom k_warp_border.
+ * Every refusal is VSTAB_ERR_INVALID, made before any device work, in this order, each message behind "vstab_warp_nv12_rs_ex: ":
+ *   1. vstab_warp_nv12_border's checks in its order: "null pointer" (y, uv, dst, params), "source must be even-sized and <= 32767", "output
+ *      size must be in [1, 32767]", "unknown map mode", "a rotation per output row (rot_bottom) is served for map modes 0, 1 and 5", "the
+ *      per-row warp emits VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR (NV12 through BGR is not served)", "border_mode must be
+ *      VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)", "pitch smaller than row", "plane-wise output needs a
+ *      chroma plane of 2*ceil(width/2) bytes per row", "chroma plane must be 2-B aligned";
+ *   2. "resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)";
+ *   3. with dist: "distortion belongs to a fisheye input (map modes 1 and 2)", then "the distortion must keep theta_d increasing on
+ *      [0, pi/2]". */
+VSTAB_API vstab_status vstab_warp_nv12_rs_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                             const float params[17], const float *rot_bottom, const float *dist, int map_mode, int resample,
+                                             int border_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv,
+                                             int dst_width, int dst_height, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The pipeline object: drop-in for FrameSourceWarp behind the FrameSource pull interface
@@ -778,7 +801,7 @@ typedef struct vstab_profile {
     long epochs_in_turn; /* planned key frames whose detection and tracker launches ran on the second of the handle's two epoch streams, beside
                             the epoch still being tracked on the first (frames up to 1920 x 1200 with a caller on the default stream; 0 otherwise) */
 } vstab_profile;
-/* Loads the library's nine GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
+/* Loads the library's eleven GPU code objects now.  The HIP runtime loads a code object at the first launch of one of its kernels -- tens of
  * milliseconds in the middle of the first frames -- and on ROCm 7.2 such a late load can FAULT ("write access to a read-only page") when the
  * process has unloaded another module before it (hipModuleUnload; an OpenCL program released by a filter next door): the new code object may
  * be placed where the old one was still mapped read-only.  vstab_create calls this itself; a host that uses the stateless operators
@@ -820,6 +843,17 @@ VSTAB_API vstab_status vstab_set_input_calibration(vstab_handle *h, const double
  * The rotation estimate and the `debug` markers go through the distorted lens as with vstab_set_input_calibration: they do not depend on
  * the resampler. */
 VSTAB_API vstab_status vstab_set_input_calibration_ex(vstab_handle *h, const double K[9], const double D[4]);
+/* What a handle does with a frame that carries a readout_rotation where its warp used to have no rotation per row: handles with resample
+ * VSTAB_RESAMPLE_CUBIC or _LANCZOS4, calibrated handles (vstab_set_input_calibration / _ex), or both.  VSTAB_READOUT_REFUSE (the default):
+ * as before, the frame is refused and consumed.  VSTAB_READOUT_PER_ROW: the frame is warped by vstab_warp_nv12_rs_ex -- the first row with
+ * the stabilising rotation W, the last with readout * W -- with the handle's resampler, the border mode in force at the pull and the
+ * handle's coefficients, in the BGR pulls and in vstab_pull_frame_nv12_planar.  The mode may change between pulls.  Frames without a
+ * read-out rotation are untouched, the quantised map of a calibrated handle included: a frame with a read-out rotation neither uses nor
+ * refreshes it.  Still refused: vstab_pull_frame_nv12 (NV12 through BGR), INTER_NEAREST handles and, at ingest, any map other than
+ * fisheye -> pinhole.  VSTAB_ERR_UNSUPPORTED on handles with pixel_depth 10 or interpolation 0; an unknown mode and a NULL handle are
+ * VSTAB_ERR_INVALID. */
+enum { VSTAB_READOUT_REFUSE = 0, VSTAB_READOUT_PER_ROW = 1 };
+VSTAB_API vstab_status vstab_set_readout_warp(vstab_handle *h, int mode);
 /* Synchronises the stream, folds all pending event pairs into the sums and returns them. */
 VSTAB_API vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out);
 

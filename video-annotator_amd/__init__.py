@@ -85,6 +85,7 @@ RESAMPLE_DEFAULT, RESAMPLE_CUBIC, RESAMPLE_LANCZOS4 = 0, 2, 4  # vstab_config.re
 # cv::remap's borderMode (cv::BorderTypes values): vstab_remap_bilinear_border, vstab_warp_nv12_border, vstab_set_border_mode; with INTER_CUBIC /
 # INTER_LANCZOS4: vstab_remap_{cubic,lanczos4}_border, vstab_warp_nv12_{cubic,lanczos4}_border, vstab_set_border_mode_ex
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 = 0, 1, 2, 4
+READOUT_REFUSE, READOUT_PER_ROW = 0, 1  # vstab_set_readout_warp
 _pp = _c.POINTER(_vp)
 
 # name -> (restype, argtypes); mirrors include/vstab.h one to one
@@ -165,6 +166,8 @@ SIGNATURES = {
     "vstab_remap_bilinear_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _vp, _sz, _i, _i, _vp]),
     "vstab_warp_nv12_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_set_border_mode": (_i, [_vp, _i]),
+    "vstab_warp_nv12_rs_ex": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_set_readout_warp": (_i, [_vp, _i]),
     "vstab_remap_cubic_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _ip, _vp, _sz, _i, _i, _vp]),
     "vstab_remap_lanczos4_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _ip, _vp, _sz, _i, _i, _vp]),
     "vstab_warp_nv12_cubic_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
@@ -539,6 +542,30 @@ def warp_nv12_dist_ex(nv12, params, dist, dw, dh, mode=MAP_FISH_TO_RECT, resampl
     yo, co = out
     _check(_L.vstab_warp_nv12_dist_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), int(out_format),
                                       yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_dist_ex")
+    return yo, co
+
+
+def warp_nv12_rs_ex(nv12, params, dw, dh, rot_bottom=None, dist=None, mode=MAP_CREATEMAP_CL, resample=RESAMPLE_DEFAULT, border_mode=BORDER_CONSTANT,
+                    out_format=OUT_BGR8, out=None):
+    """vstab_warp_nv12_rs_ex: the 8-bit warp with a rotation per output row (rot_bottom, 9 floats or None), a calibrated lens (dist, k1..k4 or
+    None), a resampler (RESAMPLE_*) and a border mode (BORDER_*).  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma) tensors."""
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    p = np.ascontiguousarray(params, np.float32)
+    rb = None if rot_bottom is None else np.ascontiguousarray(rot_bottom, np.float32).reshape(9)
+    d = None if dist is None else np.ascontiguousarray(dist, np.float32).reshape(4)
+    rbp, dp = None if rb is None else _fptr(rb), None if d is None else _fptr(d)
+    if out_format == OUT_BGR8:
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
+        _check(_L.vstab_warp_nv12_rs_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, dp, int(mode), int(resample), int(border_mode), OUT_BGR8,
+                                        out.data_ptr(), out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_rs_ex")
+        return out
+    if out is None:
+        out = nv12_out_planes(dw, dh, nv12.device)
+    yo, co = out
+    _check(_L.vstab_warp_nv12_rs_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, dp, int(mode), int(resample), int(border_mode), int(out_format),
+                                    yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_rs_ex")
     return yo, co
 
 
@@ -1067,6 +1094,11 @@ class Stabilizer:
     def set_border_mode(self, border_mode):
         """vstab_set_border_mode: cv::remap's borderMode for the frames pulled from now on."""
         _check(_L.vstab_set_border_mode(self._h, int(border_mode)), "vstab_set_border_mode")
+
+    def set_readout_warp(self, mode):
+        """vstab_set_readout_warp: READOUT_PER_ROW warps a frame that carries a read-out rotation row by row on cubic, Lanczos and calibrated
+        handles (READOUT_REFUSE, the default, refuses and consumes it); applies from the next pull."""
+        _check(_L.vstab_set_readout_warp(self._h, int(mode)), "vstab_set_readout_warp")
 
     def set_border_mode_ex(self, border_mode):
         """vstab_set_border_mode_ex: set_border_mode for INTER_LINEAR, INTER_CUBIC and INTER_LANCZOS4 handles."""

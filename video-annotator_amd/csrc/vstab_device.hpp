@@ -233,15 +233,18 @@ enum MapMode { MAP_CREATEMAP_CL = 0, MAP_FISH_TO_RECT = 1, MAP_FISH_TO_FISH = 2,
                // internal: modes 0 / 1 / 5 with a per-row rotation (rolling shutter, BASELINE config 5)
                MAP_RS_CREATEMAP_CL = 6, MAP_RS_FISH_TO_RECT = 7, MAP_RS_CREATEMAP_CL_OPENCL = 8,
                // internal: modes 1 / 2 with the input lens's distortion polynomial (vstab_*_dist)
-               MAP_FISHD_TO_RECT = 9, MAP_FISHD_TO_FISH = 10 };
+               MAP_FISHD_TO_RECT = 9, MAP_FISHD_TO_FISH = 10,
+               // internal: mode 9 with a per-row rotation (vstab_warp_nv12_rs_ex: k_warp_border, k_warp_cubic_rs, k_warp_lanczos4_rs)
+               MAP_RS_FISHD_TO_RECT = 11 };
 // the projection pair (and arithmetic) of a mode: the rolling-shutter modes share their base mode's
-constexpr bool map_mode_is_rs(int mode) { return mode >= MAP_RS_CREATEMAP_CL && mode <= MAP_RS_CREATEMAP_CL_OPENCL; }
+constexpr bool map_mode_is_rs(int mode) { return (mode >= MAP_RS_CREATEMAP_CL && mode <= MAP_RS_CREATEMAP_CL_OPENCL) || mode == MAP_RS_FISHD_TO_RECT; }
 constexpr int map_mode_base(int mode) {
-    return mode == MAP_RS_CREATEMAP_CL ? MAP_CREATEMAP_CL : mode == MAP_RS_FISH_TO_RECT ? MAP_FISH_TO_RECT : mode == MAP_RS_CREATEMAP_CL_OPENCL ? MAP_CREATEMAP_CL_OPENCL : mode;
+    return mode == MAP_RS_CREATEMAP_CL ? MAP_CREATEMAP_CL : mode == MAP_RS_FISH_TO_RECT ? MAP_FISH_TO_RECT : mode == MAP_RS_CREATEMAP_CL_OPENCL ? MAP_CREATEMAP_CL_OPENCL :
+           mode == MAP_RS_FISHD_TO_RECT ? MAP_FISHD_TO_RECT : mode;
 }
 template <int MODE>
 struct ModeTraits {
-    static constexpr bool dist = MODE == MAP_FISHD_TO_RECT || MODE == MAP_FISHD_TO_FISH;  // theta -> theta_d on the way into the input lens
+    static constexpr bool dist = MODE == MAP_FISHD_TO_RECT || MODE == MAP_FISHD_TO_FISH || MODE == MAP_RS_FISHD_TO_RECT;  // theta -> theta_d on the way into the input lens
     static constexpr bool out_fish = MODE == MAP_FISH_TO_FISH || MODE == MAP_RECT_TO_FISH || MODE == MAP_FISHD_TO_FISH;
     static constexpr bool in_fish = MODE == MAP_FISH_TO_RECT || MODE == MAP_FISH_TO_FISH || MODE == MAP_CREATEMAP_CL || MODE == MAP_CREATEMAP_CL_OPENCL || dist;
 };

@@ -1,5 +1,5 @@
 // vstab_pull.cpp -- FrameSourceWarp::pull_frame (:452-476) behind the pull entry points of the C ABI, as its seven steps, and
-// vstab_set_border_mode / _ex, whose mode those steps read.
+// vstab_set_border_mode / _ex and vstab_set_readout_warp, whose modes those steps read.
 #include <cmath>
 
 #include "vstab_pipeline.hpp"
@@ -166,6 +166,11 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
         }
         return st;
     }
+    // vstab_set_readout_warp(VSTAB_READOUT_PER_ROW): a frame with a read-out rotation on a handle whose warp has no rotation per row of its
+    // own -- a cubic or Lanczos handle, a calibrated one, or both (the formats were checked on entry; the quantised map was not chosen)
+    if (P.rot_bottom && H->readout_warp == VSTAB_READOUT_PER_ROW && (H->calibrated || resampled))
+        return vstab_warp_nv12_rs_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, H->calibrated ? H->dist32 : nullptr, mode, H->cfg.resample,
+                                     P.border_mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
     // a calibrated handle: vstab_warp_nv12_dist_ex with the handle's resampler and the pull's border mode (INTER_LINEAR with the constant
     // border: vstab_warp_nv12_dist, or the quantised map of an earlier frame).  A frame that carries a read-out rotation is consumed, as
     // INTER_NEAREST consumes it below
@@ -294,6 +299,16 @@ static vstab_status set_border_mode(vstab_handle *h, int border_mode, const char
 }
 
 extern "C" {
+
+vstab_status vstab_set_readout_warp(vstab_handle *h, int mode) {
+    if (!h) return fail(VSTAB_ERR_INVALID, "vstab_set_readout_warp: null handle");
+    if (mode != VSTAB_READOUT_REFUSE && mode != VSTAB_READOUT_PER_ROW)
+        return fail(VSTAB_ERR_INVALID, "vstab_set_readout_warp: mode must be VSTAB_READOUT_REFUSE (0) or VSTAB_READOUT_PER_ROW (1)");
+    if (h->cfg.pixel_depth == 10 || h->cfg.interpolation == 0)
+        return fail(VSTAB_ERR_UNSUPPORTED, "vstab_set_readout_warp: served for 8-bit pixels with INTER_LINEAR, INTER_CUBIC or INTER_LANCZOS4");
+    h->readout_warp = mode;
+    return VSTAB_OK;
+}
 
 vstab_status vstab_pull_frame(vstab_handle *h, void *dst, size_t pitch_dst) { return pull_frame_impl(h, VSTAB_OUT_BGR8, dst, pitch_dst, nullptr, 0); }
 

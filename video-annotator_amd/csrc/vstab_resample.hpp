@@ -32,6 +32,11 @@ struct CubicArgs {  // the warp kernels' one argument (all resamplers)
     WarpArgs w;
     MapParams32 p32;
 };
+struct BorderArgs {  // the kernels that take a rotation per output row (k_warp_border, k_warp_cubic_rs, k_warp_lanczos4_rs)
+    CubicArgs c;
+    float rs_d[9];  // RS: rotation of the last output row minus the first's (c.w.p.r), fp32
+    float rs_den;   // and (float)max(dh - 1, 1)
+};
 
 // cvRound (NaN / outside the int range -> INT_MIN), then cv::remap's split: X = saturate_cast<short>(sx >> 5), f = sx & 31
 struct CubicTap {
@@ -52,6 +57,28 @@ __device__ __forceinline__ void cubic_map(const CubicArgs &c, int x, int y, floa
     const float vx = norm_coord<MODE>((float)x - p.ocx, p.ofx, rfx);
     const ColTerm ct = {p.r[0] * vx, p.r[3] * vx, p.r[6] * vx};
     map_pixel_ex<MODE>(c.p32, p, ct, rt, vx, vy, ax, ay);
+}
+
+// 32 * map of output pixel (x, y): cubic_map's arithmetic; RS: the row's own rotation, m_k = fmaf(t, rs_d[k], r[k]) with
+// t = (float)y / rs_den, fed to the mode's arithmetic as the per-row warp (vstab_warp_tile.hpp, map_phase) does
+template <int MODE, bool RS>
+__device__ __forceinline__ void border_map(const BorderArgs &ba, int x, int y, float rfx, float rfy, float &ax, float &ay) {
+    if constexpr (!RS) {
+        cubic_map<MODE>(ba.c, x, y, rfx, rfy, ax, ay);
+    } else {
+        const MapParams &p0 = ba.c.w.p;
+        MapParams P = p0;
+        const float t = div_with_rcp((float)y, ba.rs_den, rcp_refined(ba.rs_den));
+#pragma unroll
+        for (int k = 0; k < 9; k++) P.r[k] = __builtin_fmaf(t, ba.rs_d[k], p0.r[k]);
+        MapParams32 p32 = ba.c.p32;
+        p32.r02 = P.r[2], p32.r12 = P.r[5], p32.r22 = P.r[8];
+        const float vy = norm_coord<MODE>((float)y - P.ocy, P.ofy, rfy);
+        const RowTerm rt = {P.r[1] * vy, P.r[4] * vy, P.r[7] * vy};
+        const float vx = norm_coord<MODE>((float)x - P.ocx, P.ofx, rfx);
+        const ColTerm ct = {P.r[0] * vx, P.r[3] * vx, P.r[6] * vx};
+        map_pixel_ex<MODE>(p32, P, ct, rt, vx, vy, ax, ay);
+    }
 }
 
 // OpenCV's borderInterpolate in closed form: REPLICATE clamps; REFLECT folds by the period 2 len, REFLECT_101 by 2 len - 2 (len 1 -> 0).
@@ -340,6 +367,101 @@ __device__ __forceinline__ void resample_tile(const CubicArgs &c, uint8_t *stage
             a.dst[(size_t)y * a.pitch_dst + x] = (uint8_t)resample_pixel<R, 1, BORDER>(sy, by, (const uint8_t *)lds_y, t[j]);
             if (cact && !(j & 1)) {
                 const uint32_t UV = resample_pixel<R, 2, BORDER>(suv, bc, (const uint16_t *)lds_c, tc[j / 2]);
+                uint8_t *o = a.dst_uv + (size_t)(y >> 1) * a.pitch_dst_uv + (size_t)x;  // chroma sample x / 2: bytes x, x + 1
+                o[0] = (uint8_t)UV, o[1] = (uint8_t)(UV >> 8);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Cubic and Lanczos with a rotation per output row (k_warp_cubic_rs, k_warp_lanczos4_rs; map modes 0, 1 and 5, and MAP_RS_FISHD_TO_RECT: the
+// calibrated lens), every border mode: resample_tile's phases with border_map<MODE, true> as the map.  BORDER_CONSTANT goes through the
+// same tile with the constant border's touch filter (R::touches, as k_warp_cubic / k_warp_lanczos4 have it): only the footprints that
+// touch the source enter the box, a tile with none has no box, a pixel whose footprint does not touch is the border value.
+// ---------------------------------------------------------------------------------------------------------------------
+// whether the pixel of tap t is blended (any other is the border value): every pixel, but for the constant border
+template <typename R, int BORDER>
+__device__ __forceinline__ bool resample_blends(const CubicTap &t, int w, int h) {
+    if constexpr (BORDER == VSTAB_BORDER_CONSTANT) return R::touches(t, w, h);
+    else return true;
+}
+// tap j of the thread's taps without an index into the array: where the compiler keeps the blend loop rolled (the Lanczos BGR kernels) an
+// indexed read puts the array into scratch memory; a chain of selects keeps it in registers, and folds to t[j] where the loop is unrolled
+template <int N>
+__device__ __forceinline__ CubicTap pick_tap(const CubicTap (&t)[N], int j) {
+    CubicTap r = t[0];
+#pragma unroll
+    for (int k = 1; k < N; k++)
+        if (j == k) r = t[k];
+    return r;
+}
+// stage, red: as for resample_tile
+template <typename R, int MODE, bool PLANAR, int BORDER>
+__device__ __forceinline__ void resample_tile_rs(const BorderArgs &ba, uint8_t *stage, int *red) {
+    const WarpArgs &a = ba.c.w;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = blockIdx.x * RESAMPLE_TW + lane, y0 = blockIdx.y * RESAMPLE_TH + wave * RESAMPLE_RW;
+    const float rfx = rcp_refined(a.p.ofx), rfy = rcp_refined(a.p.ofy);
+    // 1. map, each row's matrix formed where it is consumed (pixels right of / below the image are evaluated as the last column / row)
+    CubicTap t[RESAMPLE_RW];
+    float ax[RESAMPLE_RW], ay[RESAMPLE_RW];
+#pragma unroll
+    for (int j = 0; j < RESAMPLE_RW; j++) {
+        border_map<MODE, true>(ba, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
+        t[j] = cubic_tap(ax[j], ay[j]);
+    }
+    // 2. box of the luma / BGR footprints, in virtual coordinates: every pixel (CONSTANT: those that touch the source)
+    int mnx = INT_MAX, mxx = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
+#pragma unroll
+    for (int j = 0; j < RESAMPLE_RW; j++)
+        if (resample_blends<R, BORDER>(t[j], a.sw, a.sh)) footprint_extent<R>(t[j], mnx, mxx, mny, mxy);
+    if constexpr (!PLANAR) {
+        const BorderNv12Bgr<BORDER> src = {a.y, a.uv, a.pitch_y, a.pitch_uv, a.sw, a.sh};
+        uint32_t *lds = reinterpret_cast<uint32_t *>(stage);
+        const TileBox b = tile_box<0, 2, true>(mnx, mxx, mny, mxy, red, RESAMPLE_LDS_BYTES / 4);
+        // 3. stage
+        if (b.lds) stage_box<BORDER, true>(src, b, lds);
+        __syncthreads();
+        // 4. blend
+#pragma unroll
+        for (int j = 0; j < RESAMPLE_RW; j++) {
+            const int y = y0 + j;
+            if (x >= a.dw || y >= a.dh) continue;
+            const CubicTap q = pick_tap(t, j);
+            const uint32_t bgr = resample_blends<R, BORDER>(q, a.sw, a.sh) ? resample_pixel<R, 3, BORDER>(src, b, (const uint32_t *)lds, q) : 0u;
+            uint8_t *o = a.dst + (size_t)y * a.pitch_dst + (size_t)x * 3;
+            o[0] = (uint8_t)bgr, o[1] = (uint8_t)(bgr >> 8), o[2] = (uint8_t)(bgr >> 16);
+        }
+    } else {
+        // chroma sample (x / 2, y / 2) of every even output pixel: the map halved (exact) and quantised again, over the chroma plane's size
+        const int cw = a.sw >> 1, ch = a.sh >> 1;
+        const bool cact = !(lane & 1);
+        CubicTap tc[RESAMPLE_RW / 2];
+        int cmnx = INT_MAX, cmxx = INT_MIN, cmny = INT_MAX, cmxy = INT_MIN;
+#pragma unroll
+        for (int k = 0; k < RESAMPLE_RW / 2; k++) {
+            tc[k] = cubic_tap(ax[2 * k] * 0.5f, ay[2 * k] * 0.5f);
+            if (cact && resample_blends<R, BORDER>(tc[k], cw, ch)) footprint_extent<R>(tc[k], cmnx, cmxx, cmny, cmxy);
+        }
+        const BorderBytes<1, BORDER> sy = {a.y, a.pitch_y, a.sw, a.sh, 16u};  // (the border values: read by BORDER_CONSTANT alone)
+        const BorderBytes<2, BORDER> suv = {a.uv, a.pitch_uv, cw, ch, 0x8080u};
+        uint8_t *lds_y = stage;                                                         // luma bytes: half the budget
+        uint16_t *lds_c = reinterpret_cast<uint16_t *>(stage + RESAMPLE_LDS_BYTES / 2);  // chroma pairs: the other half
+        const TileBox by = tile_box<0, 2, true>(mnx, mxx, mny, mxy, red, RESAMPLE_LDS_BYTES / 2);
+        const TileBox bc = tile_box<0, 2, true>(cmnx, cmxx, cmny, cmxy, red, RESAMPLE_LDS_BYTES / 4);
+        if (by.lds) stage_box<BORDER, true>(sy, by, lds_y);
+        if (bc.lds) stage_box<BORDER, true>(suv, bc, lds_c);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RESAMPLE_RW; j++) {
+            const int y = y0 + j;
+            if (x >= a.dw || y >= a.dh) continue;
+            const CubicTap q = pick_tap(t, j);
+            a.dst[(size_t)y * a.pitch_dst + x] = (uint8_t)(resample_blends<R, BORDER>(q, a.sw, a.sh) ? resample_pixel<R, 1, BORDER>(sy, by, (const uint8_t *)lds_y, q) : 16u);
+            if (cact && !(j & 1)) {
+                const CubicTap qc = pick_tap(tc, j / 2);
+                const uint32_t UV = resample_blends<R, BORDER>(qc, cw, ch) ? resample_pixel<R, 2, BORDER>(suv, bc, (const uint16_t *)lds_c, qc) : 0x8080u;
                 uint8_t *o = a.dst_uv + (size_t)(y >> 1) * a.pitch_dst_uv + (size_t)x;  // chroma sample x / 2: bytes x, x + 1
                 o[0] = (uint8_t)UV, o[1] = (uint8_t)(UV >> 8);
             }

@@ -237,6 +237,44 @@ vstab_status vstab_warp_nv12_dist_ex(const void *y, size_t pitch_y, const void *
                      dst_uv, pitch_dst_uv, dw, dh, stream);
 }
 
+vstab_status vstab_warp_nv12_rs_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                   const float *rot_bottom, const float *dist, int map_mode, int resample, int border_mode, int out_format, void *dst,
+                                   size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
+    const std::string n = "vstab_warp_nv12_rs_ex";
+    BorderArgs ba;
+    VSTAB_TRY(check_warp_nv12(n, "the per-row warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, out_format, &border_mode, dst, pitch_dst,
+                              dst_uv, pitch_dst_uv, dw, dh, ba.c, dist));
+    if (resample != VSTAB_RESAMPLE_DEFAULT && resample != VSTAB_RESAMPLE_CUBIC && resample != VSTAB_RESAMPLE_LANCZOS4)
+        return fail(VSTAB_ERR_INVALID, n + ": resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)");
+    if (dist) {
+        if (!map_mode_takes_distortion(map_mode)) return fail(VSTAB_ERR_INVALID, n + ": distortion belongs to a fisheye input (map modes 1 and 2)");
+        VSTAB_TRY(check_distortion(n, dist));
+    }
+    const bool constant = border_mode == VSTAB_BORDER_CONSTANT, cubic = resample == VSTAB_RESAMPLE_CUBIC;
+    // what an older entry point serves is that entry point's
+    if (!rot_bottom && dist)
+        return vstab_warp_nv12_dist_ex(y, pitch_y, uv, pitch_uv, sw, sh, params, dist, map_mode, resample, border_mode, out_format, dst, pitch_dst, dst_uv,
+                                       pitch_dst_uv, dw, dh, stream);
+    if (resample == VSTAB_RESAMPLE_DEFAULT && !dist) {
+        if (!rot_bottom && constant)
+            return vstab_warp_nv12_ex(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
+        return vstab_warp_nv12_border(y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, out_format, border_mode, dst, pitch_dst, dst_uv,
+                                      pitch_dst_uv, dw, dh, stream);
+    }
+    if (!rot_bottom) {
+        if (constant)
+            return (cubic ? vstab_warp_nv12_cubic : vstab_warp_nv12_lanczos4)(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, dst, pitch_dst,
+                                                                              dst_uv, pitch_dst_uv, dw, dh, stream);
+        return (cubic ? vstab_warp_nv12_cubic_border : vstab_warp_nv12_lanczos4_border)(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format,
+                                                                                        border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
+    }
+    // new ground: a rotation per row under the cubic and Lanczos resamplers, and under every resampler through a calibrated lens (map mode 1:
+    // rot_bottom admits modes 0, 1 and 5, dist modes 1 and 2)
+    fill_rolling_shutter(ba, params, rot_bottom, dh);
+    if (resample == VSTAB_RESAMPLE_DEFAULT) return launch_warp_border(ba, map_mode, true, true, out_format, border_mode, stream);
+    return (cubic ? launch_warp_cubic_rs : launch_warp_lanczos4_rs)(ba, map_mode, dist != nullptr, out_format, border_mode, stream);
+}
+
 vstab_status vstab_warp_nv12_nearest_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                         int map_mode, void *dst, size_t pitch_dst, int dw, int dh, void *stream) {
     if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_nearest: null pointer");

@@ -21,12 +21,6 @@
 
 namespace vstab {
 
-struct BorderArgs {
-    CubicArgs c;
-    float rs_d[9];  // RS: rotation of the last output row minus the first's (c.w.p.r), fp32
-    float rs_den;   // and (float)max(dh - 1, 1)
-};
-
 // bilinear tap: the top-left virtual position and the two weight pairs {w00, w01}, {w10, w11} as int16 halves
 struct BorderTap {
     int X, Y;
@@ -75,31 +69,9 @@ __device__ __forceinline__ void border_taps(const Src &s, const TileBox &b, cons
     }
 }
 
-// 32 * map of output pixel (x, y): cubic_map's arithmetic; RS: the row's own rotation, m_k = fmaf(t, rs_d[k], r[k]) with
-// t = (float)y / rs_den, fed to the mode's arithmetic as the per-row warp (vstab_warp_tile.hpp, map_phase) does
-template <int MODE, bool RS>
-__device__ __forceinline__ void border_map(const BorderArgs &ba, int x, int y, float rfx, float rfy, float &ax, float &ay) {
-    if constexpr (!RS) {
-        cubic_map<MODE>(ba.c, x, y, rfx, rfy, ax, ay);
-    } else {
-        const MapParams &p0 = ba.c.w.p;
-        MapParams P = p0;
-        const float t = div_with_rcp((float)y, ba.rs_den, rcp_refined(ba.rs_den));
-#pragma unroll
-        for (int k = 0; k < 9; k++) P.r[k] = __builtin_fmaf(t, ba.rs_d[k], p0.r[k]);
-        MapParams32 p32 = ba.c.p32;
-        p32.r02 = P.r[2], p32.r12 = P.r[5], p32.r22 = P.r[8];
-        const float vy = norm_coord<MODE>((float)y - P.ocy, P.ofy, rfy);
-        const RowTerm rt = {P.r[1] * vy, P.r[4] * vy, P.r[7] * vy};
-        const float vx = norm_coord<MODE>((float)x - P.ocx, P.ofx, rfx);
-        const ColTerm ct = {P.r[0] * vx, P.r[3] * vx, P.r[6] * vx};
-        map_pixel_ex<MODE>(p32, P, ct, rt, vx, vy, ax, ay);
-    }
-}
-
 // k_warp_border -- NV12 in; PLANAR false: BGR8 out (cvtColor then cv::remap INTER_LINEAR, border mode BORDER; CONSTANT value 0); PLANAR
 // true: the plane-wise warp (luma; chroma at the even pixels' positions halved over the chroma plane's own size; CONSTANT values 16 and
-// (128, 128)).  MODE: map modes 0 .. 5, RS with modes 0 / 1 / 5.
+// (128, 128)).  MODE: map modes 0 .. 5, RS with modes 0 / 1 / 5 and with MAP_RS_FISHD_TO_RECT (the calibrated lens, map mode 1).
 template <int MODE, bool PLANAR, bool RS, int BORDER>
 __global__ void __launch_bounds__(256) k_warp_border(BorderArgs ba) {
     const WarpArgs &a = ba.c.w;
@@ -205,9 +177,19 @@ vstab_status preload_border_kernels() {
 }
 
 // k_warp_border of checked arguments on its grid.  rs: a rotation per output row, served (and checked) for map modes 0, 1 and 5 only.
-// dist: ba.c.p32.d holds the input lens's coefficients (map modes 1 and 2), no rotation per row, a non-constant border: INTER_LINEAR
-// with the constant border and a distorted lens is k_warp_fused / k_warp_planar (vstab_warp_nv12_dist).
-static vstab_status launch_warp_border(const BorderArgs &ba, int map_mode, bool dist, bool rs, int out_format, int border_mode, void *stream) {
+// dist: ba.c.p32.d holds the input lens's coefficients.  Without a rotation per row: map modes 1 and 2, a non-constant border (INTER_LINEAR
+// with the constant border and a distorted lens is k_warp_fused / k_warp_planar, vstab_warp_nv12_dist).  With one (vstab_warp_nv12_rs_ex):
+// map mode 1 as MAP_RS_FISHD_TO_RECT, every border mode.
+vstab_status launch_warp_border(const BorderArgs &ba, int map_mode, bool dist, bool rs, int out_format, int border_mode, void *stream) {
+    if (dist && rs) {
+        with_border_mode(border_mode, [&](auto border) {
+            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
+                launch_tiles(k_warp_border<MAP_RS_FISHD_TO_RECT, decltype(planar)::value, true, decltype(border)::value>, ba, ba.c.w.dw, ba.c.w.dh, stream);
+            });
+        });
+        VSTAB_HIP_TRY(hipGetLastError());
+        return VSTAB_OK;
+    }
     with_map_mode_or_dist(map_mode, dist, [&](auto mode) {
         with_border_mode(border_mode, [&](auto border) {
             with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {

@@ -246,6 +246,33 @@ vstab_status launch_warp_cubic_dist(const CubicArgs &c, int map_mode, int out_fo
 vstab_status launch_warp_lanczos4_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream);
 vstab_status launch_warp_border_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream);
 
+// vstab_warp_nv12_rs_ex's kernels: a rotation per output row (ba checked, its rs_d / rs_den filled by fill_rolling_shutter) under the cubic
+// and Lanczos resamplers, every border mode.  KS::warp_rs<MODE, PLANAR, BORDER>() is the kernel; MODE is the map mode 0, 1 or 5 itself (the
+// kernel's map is border_map<MODE, true>) or, dist, MAP_RS_FISHD_TO_RECT (map mode 1 with the coefficients in ba.c.p32.d).
+template <typename F>
+void with_rs_mode(int map_mode, bool dist, F &&f) {
+    if (dist) f(mode_constant<MAP_RS_FISHD_TO_RECT>{});
+    else if (map_mode == VSTAB_MAP_CREATEMAP_CL) f(mode_constant<MAP_CREATEMAP_CL>{});
+    else if (map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL) f(mode_constant<MAP_CREATEMAP_CL_OPENCL>{});
+    else f(mode_constant<MAP_FISH_TO_RECT>{});
+}
+template <typename KS>
+vstab_status launch_warp_resample_rs(const BorderArgs &ba, int map_mode, bool dist, int out_format, int border_mode, void *stream) {
+    with_rs_mode(map_mode, dist, [&](auto mode) {
+        with_border_mode(border_mode, [&](auto border) {
+            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
+                launch_tiles(KS::template warp_rs<decltype(mode)::value, decltype(planar)::value, decltype(border)::value>(), ba, ba.c.w.dw, ba.c.w.dh, stream);
+            });
+        });
+    });
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+vstab_status launch_warp_cubic_rs(const BorderArgs &ba, int map_mode, bool dist, int out_format, int border_mode, void *stream);
+vstab_status launch_warp_lanczos4_rs(const BorderArgs &ba, int map_mode, bool dist, int out_format, int border_mode, void *stream);
+// k_warp_border of checked arguments (vstab_warp_border.hip): rs with dist is INTER_LINEAR on a calibrated lens with a rotation per row
+vstab_status launch_warp_border(const BorderArgs &ba, int map_mode, bool dist, bool rs, int out_format, int border_mode, void *stream);
+
 template <typename KS>
 vstab_status remap_resample(const char *name, const void *src, size_t pitch_src, int sw, int sh, int channels, const void *map_x, size_t pitch_x,
                             const void *map_y, size_t pitch_y, const int *border_mode, const int border[3], void *dst, size_t pitch_dst, int dw, int dh,

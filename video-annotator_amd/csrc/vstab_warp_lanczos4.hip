@@ -184,11 +184,24 @@ __global__ void __launch_bounds__(256) k_remap_lanczos4_border(VSTAB_REMAP_PARAM
     remap_pixel<Lanczos4, CN, BORDER>(src, pitch_src, sw, sh, mapx, pitch_x, mapy, pitch_y, dst, pitch_dst, dw, dh);
 }
 
+// k_warp_lanczos4_rs -- the warp with a rotation per output row (vstab_warp_nv12_rs_ex; map modes 0, 1, 5 and MAP_RS_FISHD_TO_RECT), every
+// border mode, BORDER_CONSTANT included: resample_tile_rs (vstab_resample.hpp)
+template <int MODE, bool PLANAR, int BORDER>
+__global__ void __launch_bounds__(256) k_warp_lanczos4_rs(BorderArgs ba) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[RESAMPLE_LDS_BYTES];
+    __shared__ __attribute__((aligned(16))) int red[16];
+    resample_tile_rs<Lanczos4, MODE, PLANAR, BORDER>(ba, stage, red);
+}
+
 struct Lanczos4Kernels {
     template <int MODE, bool PLANAR, int BORDER>
     static auto warp() {
         if constexpr (BORDER == VSTAB_BORDER_CONSTANT) return k_warp_lanczos4<MODE, PLANAR>;
         else return k_warp_lanczos4_border<MODE, PLANAR, BORDER>;
+    }
+    template <int MODE, bool PLANAR, int BORDER>
+    static auto warp_rs() {
+        return k_warp_lanczos4_rs<MODE, PLANAR, BORDER>;
     }
     template <int CN, int BORDER>
     static auto remap() {
@@ -206,6 +219,10 @@ vstab_status preload_lanczos4_kernels() {
 
 vstab_status launch_warp_lanczos4_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream) {
     return launch_warp_resample<Lanczos4Kernels>(c, map_mode, true, out_format, border_mode, stream);
+}
+
+vstab_status launch_warp_lanczos4_rs(const BorderArgs &ba, int map_mode, bool dist, int out_format, int border_mode, void *stream) {
+    return launch_warp_resample_rs<Lanczos4Kernels>(ba, map_mode, dist, out_format, border_mode, stream);
 }
 
 }  // namespace vstab
