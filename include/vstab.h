@@ -366,6 +366,46 @@ VSTAB_API vstab_status vstab_warp_nv12_lanczos4_border(const void *y, size_t pit
                                                        int dst_height, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Keep edges: where the warped frame does not cover the output, the output keeps what the caller had there -- vid.stab's default border
+ * (`keep`), how deshake and Gyroflow users hide moving black wedges without inventing mirrored picture, and cv::remap's own
+ * BORDER_TRANSPARENT.  The feature has entry points of its own (the border modes above keep refusing TRANSPARENT (5)), and the history
+ * belongs to the caller, who passes the frame to keep as `prev`: encoders and players hold their last output anyway.  INTER_LINEAR, 8-bit
+ * (tests/keep_def.py holds the definition in numpy, tests/golden/keep_kat.npz pins it):
+ *   quantisation  as INTER_LINEAR above: sx = cvRound(32 * mapx) (NaN / outside the int range: INT_MIN), X = saturate_cast<short>(sx >> 5),
+ *                 fx = sx & 31; the same for y;
+ *   written       an output sample is WRITTEN iff its 2 x 2 footprint lies wholly inside the plane it reads: 0 <= X <= len_x - 2 and
+ *                 0 <= Y <= len_y - 2 -- cv::remap's inlier test (unsigned)X < w - 1.  A written sample has exactly the bytes the
+ *                 constant-border bilinear warp gives, (sum of four products + 512) >> 10; no border value enters it;
+ *   kept          every other sample: dst receives the byte of prev at the same position, or is not stored at all when prev == dst.
+ * So: an exact hit on the last column or row (X == len_x - 1, fx == 0) is kept, as in OpenCV; a NaN map entry (X = Y = -32768) is kept; a
+ * plane with len < 2 keeps everything.
+ * Planes.  BGR8: the colour conversion comes before the remap, and the samples are decided over the full-size frame, all three channels
+ * together.  Plane-wise NV12: luma is decided over src_width x src_height; the interleaved chroma plane is decided independently, with
+ * map(2 cx, 2 cy) * 0.5f over its own size src_width / 2 x src_height / 2, the pair (U, V) kept or written together -- as
+ * vstab_warp_nv12_border treats the planes.  This is cv::remap BORDER_TRANSPARENT's rule for 1- and 2-channel data; for 3-channel data
+ * (BGR) the rule is DEFINED here, not claimed equal to OpenCV's branch for it.
+ * Aliasing.  prev may be exactly dst -- the same pointer and the same pitch; for plane-wise output both planes -- which is the in-place
+ * case, BORDER_TRANSPARENT itself.  Any other overlap of the byte ranges of prev and dst is refused with VSTAB_ERR_INVALID, and so is
+ * prev == NULL.  prev is never written.
+ * Out of scope, and not offered in a keep-edge form: the calibrated lens, INTER_CUBIC, INTER_LANCZOS4, INTER_NEAREST and the 10-bit warps.
+ * ------------------------------------------------------------------------------------------ */
+/* The keep-edge remap of an 8-bit source of `channels` (1, 2 or 3) interleaved channels with float map planes (pitches in bytes; map planes
+ * 4-byte aligned).  vstab_remap_bilinear_border's checks in their order, then prev: "null pointer", "prev pitch smaller than row", the
+ * aliasing rule. */
+VSTAB_API vstab_status vstab_remap_bilinear_keep(const void *src, size_t pitch_src, int src_width, int src_height, int channels,
+                                                 const void *map_x, size_t pitch_x, const void *map_y, size_t pitch_y, const void *prev,
+                                                 size_t pitch_prev, void *dst, size_t pitch_dst, int dst_width, int dst_height, void *stream);
+/* The keep-edge warp of an NV12 frame, map modes 0 .. 5 (the map of each mode bit for bit); rot_bottom != NULL adds vstab_warp_nv12_rs's
+ * rotation per output row (map modes 0, 1 and 5; the others are refused with VSTAB_ERR_INVALID).  out_format: VSTAB_OUT_BGR8 (prev, dst:
+ * BGR frames; prev_uv, dst_uv ignored) or VSTAB_OUT_NV12_PLANAR (prev / prev_uv, dst / dst_uv: the luma and the chroma planes, dst_uv as
+ * for vstab_warp_nv12_ex); every other value is VSTAB_ERR_INVALID.  vstab_warp_nv12_border's checks in their order, then prev as above;
+ * every check runs before any launch. */
+VSTAB_API vstab_status vstab_warp_nv12_keep(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                            const float params[17], const float *rot_bottom, int map_mode, int out_format, const void *prev,
+                                            size_t pitch_prev, const void *prev_uv, size_t pitch_prev_uv, void *dst, size_t pitch_dst,
+                                            void *dst_uv, size_t pitch_dst_uv, int dst_width, int dst_height, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tracking front-end (device images in; small point lists on the host, as in the reference where
  * goodFeaturesToTrack / calcOpticalFlowPyrLK return std::vector<Point2f>).  These calls
  * synchronise `stream` before returning because their outputs live in host memory.
@@ -854,6 +894,17 @@ VSTAB_API vstab_status vstab_set_input_calibration_ex(vstab_handle *h, const dou
  * VSTAB_ERR_INVALID. */
 enum { VSTAB_READOUT_REFUSE = 0, VSTAB_READOUT_PER_ROW = 1 };
 VSTAB_API vstab_status vstab_set_readout_warp(vstab_handle *h, int mode);
+/* vstab_pull_frame / vstab_pull_frame_nv12_planar with kept edges ("Keep edges" above): the next frame, warped by vstab_warp_nv12_keep with
+ * the caller's previous output prev (prev_y / prev_uv) -- a second buffer (a ring of two outputs), or dst itself (in place).  A frame that
+ * carries a read-out rotation is warped per row, as a plain INTER_LINEAR pull warps it.  Keep pulls and plain pulls may alternate frame by
+ * frame; a keep pull neither reads nor refreshes the quantised map.  The debug markers (vstab_config.debug) are drawn after the warp, as
+ * in every pull, so with the history in place they persist in kept areas.  Refused before any frame is dequeued, in this order: a NULL argument
+ * (VSTAB_ERR_INVALID); a pixel_depth 10 handle (VSTAB_ERR_INVALID, vstab_pull_frame's message); VSTAB_ERR_UNSUPPORTED for a handle with
+ * resample VSTAB_RESAMPLE_CUBIC or _LANCZOS4, interpolation 0, a border mode in force other than VSTAB_BORDER_CONSTANT, a calibrated
+ * handle; a prev pitch smaller than a row and the aliasing rule (VSTAB_ERR_INVALID).  There is no vstab_pull_frames / _host / vstab_peek_frame form. */
+VSTAB_API vstab_status vstab_pull_frame_keep(vstab_handle *h, void *dst_bgr, size_t pitch_dst, const void *prev_bgr, size_t pitch_prev);
+VSTAB_API vstab_status vstab_pull_frame_nv12_planar_keep(vstab_handle *h, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv,
+                                                         const void *prev_y, size_t pitch_prev_y, const void *prev_uv, size_t pitch_prev_uv);
 /* Synchronises the stream, folds all pending event pairs into the sums and returns them. */
 VSTAB_API vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out);
 

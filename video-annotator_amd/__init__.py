@@ -181,6 +181,10 @@ SIGNATURES = {
     "vstab_quantised_map_dist": (_i, [_vp, _i, _i, _fp, _fp, _i, _vp]),
     "vstab_warp_nv12_dist": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_warp_nv12_dist_ex": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_remap_bilinear_keep": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_warp_nv12_keep": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_pull_frame_keep": (_i, [_vp, _vp, _sz, _vp, _sz]),
+    "vstab_pull_frame_nv12_planar_keep": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -603,6 +607,45 @@ def warp_nv12_border(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT
     yo, co = out
     _check(_L.vstab_warp_nv12_border(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, int(mode), int(out_format), int(border_mode), yo.data_ptr(),
                                      yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_border")
+    return yo, co
+
+
+def remap_bilinear_keep(src, mapx, mapy, prev, out=None):
+    """vstab_remap_bilinear_keep: cv::remap(INTER_LINEAR) where the 2 x 2 footprint lies inside src, prev's bytes everywhere else
+    (BORDER_TRANSPARENT).  src: (h, w) or (h, w, cn) uint8 CUDA tensor, cn 1..3; mapx / mapy: (dh, dw) float32 CUDA tensors; prev: the frame to
+    keep, shaped as the output.  out: a tensor of its own (default: a new one), or prev itself -- in place."""
+    import torch
+    cn = 1 if src.dim() == 2 else src.shape[2]
+    sh, sw = src.shape[0], src.shape[1]
+    dh, dw = mapx.shape
+    if out is None:
+        out = torch.empty((dh, dw) if src.dim() == 2 else (dh, dw, cn), dtype=torch.uint8, device=src.device)
+    _check(_L.vstab_remap_bilinear_keep(src.data_ptr(), src.stride(0), sw, sh, cn, mapx.data_ptr(), mapx.stride(0) * 4, mapy.data_ptr(),
+                                        mapy.stride(0) * 4, prev.data_ptr(), prev.stride(0), out.data_ptr(), out.stride(0), dw, dh, _stream()),
+           "vstab_remap_bilinear_keep")
+    return out
+
+
+def warp_nv12_keep(nv12, params, dw, dh, prev, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, rot_bottom=None, out=None):
+    """vstab_warp_nv12_keep: the bilinear warp where its footprint lies inside the source, prev's bytes everywhere else.  OUT_BGR8: prev a
+    (dh, dw, 3) tensor -> (dh, dw, 3) tensor; OUT_NV12_PLANAR: prev a (luma, chroma) pair -> (luma, chroma) tensors.  out: tensors of their
+    own (default: new ones), or prev itself -- in place.  rot_bottom: vstab_warp_nv12_rs's rotation of the last output row."""
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    p = np.ascontiguousarray(params, np.float32)
+    rb = None if rot_bottom is None else np.ascontiguousarray(rot_bottom, np.float32).reshape(9)
+    rbp = None if rb is None else _fptr(rb)
+    if out_format == OUT_BGR8:
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
+        _check(_L.vstab_warp_nv12_keep(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, int(mode), OUT_BGR8, prev.data_ptr(), prev.stride(0), None, 0,
+                                       out.data_ptr(), out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_keep")
+        return out
+    if out is None:
+        out = nv12_out_planes(dw, dh, nv12.device)
+    (yo, co), (py, pc) = out, prev
+    _check(_L.vstab_warp_nv12_keep(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, int(mode), int(out_format), py.data_ptr(), py.stride(0), pc.data_ptr(),
+                                   pc.stride(0), yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_keep")
     return yo, co
 
 
@@ -1169,6 +1212,24 @@ class Stabilizer:
         """-> (luma, chroma) tensors, or None at end of stream."""
         y, uv = nv12_out_planes(self.out_size[0], self.out_size[1])
         return (y, uv) if self.pull_nv12_into(y, uv, planar) else None
+
+    def pull_keep_into(self, out, prev):
+        """vstab_pull_frame_keep: the next frame into out, with prev's bytes where the warped frame does not cover the output.  prev: the
+        previous output -- another tensor (a ring of two), or out itself (in place).  Returns True, or False at end of stream."""
+        st = _L.vstab_pull_frame_keep(self._h, out.data_ptr(), out.stride(0), prev.data_ptr(), prev.stride(0))
+        if st == EOF:
+            return False
+        _check(st, "vstab_pull_frame_keep")
+        return True
+
+    def pull_nv12_planar_keep_into(self, y, uv, prev_y, prev_uv):
+        """vstab_pull_frame_nv12_planar_keep: pull_keep_into for the plane-wise warp; (prev_y, prev_uv) another pair of planes, or (y, uv)."""
+        st = _L.vstab_pull_frame_nv12_planar_keep(self._h, y.data_ptr(), y.stride(0), uv.data_ptr(), uv.stride(0), prev_y.data_ptr(), prev_y.stride(0),
+                                                  prev_uv.data_ptr(), prev_uv.stride(0))
+        if st == EOF:
+            return False
+        _check(st, "vstab_pull_frame_nv12_planar_keep")
+        return True
 
     def pull_p010_planar_into(self, out_y, out_uv):
         """pixel_depth = 10 handles: the frame warped plane by plane (vstab_pull_frame_p010_planar), P010 planes as pull_p010_into."""

@@ -46,11 +46,42 @@ vstab_status preload_planar_kernels();
 vstab_status preload_cubic_kernels();
 vstab_status preload_lanczos4_kernels();
 vstab_status preload_border_kernels();
+vstab_status preload_keep_kernels();
 bool launch_events_pending();
 
 // the cv::BorderTypes the border warps serve (vstab_warp_nv12_border, vstab_warp_nv12_cubic_border / _lanczos4_border, vstab_set_border_mode / _ex)
 inline bool border_mode_valid(int m) {
     return m == VSTAB_BORDER_CONSTANT || m == VSTAB_BORDER_REPLICATE || m == VSTAB_BORDER_REFLECT || m == VSTAB_BORDER_REFLECT_101;
+}
+
+// The keep-edge entry points' history (include/vstab.h, "Keep edges"): each plane of prev beside the plane of dst it stands for.  prev is dst
+// itself -- same pointer and same pitch, in every plane: in place -- or its bytes overlap no plane of dst.  The stateless entry points ask
+// this behind their other checks, the pulls before a frame is dequeued; every message stands under the caller's name n.
+struct KeepPlane {
+    const void *prev;
+    size_t pitch_prev;
+    const void *dst;
+    size_t pitch_dst, row_bytes;
+    int rows;
+};
+inline vstab_status check_keep_prev(const std::string &n, const KeepPlane *pl, int planes, bool &in_place) {
+    for (int k = 0; k < planes; k++)
+        if (!pl[k].prev) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
+    for (int k = 0; k < planes; k++)
+        if (pl[k].pitch_prev < pl[k].row_bytes) return fail(VSTAB_ERR_INVALID, n + ": prev pitch smaller than row");
+    int same = 0;
+    for (int k = 0; k < planes; k++) same += pl[k].prev == pl[k].dst && pl[k].pitch_prev == pl[k].pitch_dst;
+    in_place = same == planes;
+    bool overlap = same != 0 && !in_place;  // one plane in place, the other not
+    for (int k = 0; k < planes && !in_place; k++)
+        for (int m = 0; m < planes; m++) {
+            const uintptr_t p0 = reinterpret_cast<uintptr_t>(pl[k].prev), d0 = reinterpret_cast<uintptr_t>(pl[m].dst);
+            const uintptr_t p1 = p0 + pl[k].pitch_prev * (size_t)(pl[k].rows - 1) + pl[k].row_bytes;
+            const uintptr_t d1 = d0 + pl[m].pitch_dst * (size_t)(pl[m].rows - 1) + pl[m].row_bytes;
+            overlap = overlap || (p0 < d1 && d0 < p1);
+        }
+    if (overlap) return fail(VSTAB_ERR_INVALID, n + ": prev must be dst itself (same pointer and pitch, every plane) or must not overlap it");
+    return VSTAB_OK;
 }
 
 // k1..k4 of a fisheye lens as every entry point that takes them accepts them (vstab_geometry.cpp): all finite, and theta_d increasing

@@ -10,11 +10,18 @@ constexpr int OUT_P010_PLANAR = 18;  // internal: the 10-bit frame warped plane 
 static inline bool out_is_10bit(int f) { return f == OUT_BGR16 || f == OUT_P010 || f == OUT_P010_PLANAR; }
 static inline bool out_has_chroma_plane(int f) { return f == VSTAB_OUT_NV12 || f == VSTAB_OUT_NV12_PLANAR || f == OUT_P010 || f == OUT_P010_PLANAR; }
 
+struct KeepPrev {  // a keep pull (vstab_pull_frame_keep / _nv12_planar_keep): its entry point's name, the caller's previous output
+    const char *fn;
+    const void *prev, *prev_uv;
+    size_t pitch_prev, pitch_prev_uv;
+};
+
 struct Pull {  // one pull on its way through the steps: what the caller asked for and the border mode in force, then what the steps add
     const int out_format;
     void *const dst, *const dst_uv;
     const size_t pitch_dst, pitch_dst_uv;
     const int border_mode;
+    const KeepPrev *const keep = nullptr;  // a keep pull
     int slot = -1;
     Mat3 warp_R;
     float p[17], p_bottom[17];
@@ -35,6 +42,22 @@ static vstab_status refuse_formats(const vstab_handle *H, const Pull &P) {
     // (nor does the distorted-lens warp of a calibrated handle)
     if (H->calibrated) return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: a calibrated handle (vstab_set_input_calibration)") + served);
     return VSTAB_OK;
+}
+
+// 1b. a keep pull: the handles whose warp has no keep-edge form, then the caller's history (all before a frame is dequeued)
+static vstab_status refuse_keep(const vstab_handle *H, const Pull &P) {
+    const KeepPrev &k = *P.keep;
+    const std::string n = k.fn;
+    if (H->cfg.resample != VSTAB_RESAMPLE_DEFAULT) return fail(VSTAB_ERR_UNSUPPORTED, n + ": " + resample_name(H->cfg.resample) + " has no keep-edge warp");
+    if (H->cfg.interpolation == 0) return fail(VSTAB_ERR_UNSUPPORTED, n + ": INTER_NEAREST has no keep-edge warp");
+    if (P.border_mode != VSTAB_BORDER_CONSTANT)
+        return fail(VSTAB_ERR_UNSUPPORTED, n + ": a border mode other than VSTAB_BORDER_CONSTANT is in force (vstab_set_border_mode)");
+    if (H->calibrated) return fail(VSTAB_ERR_UNSUPPORTED, n + ": a calibrated handle (vstab_set_input_calibration) has no keep-edge warp");
+    const bool planar = P.out_format == VSTAB_OUT_NV12_PLANAR;
+    const KeepPlane planes[2] = {{k.prev, k.pitch_prev, P.dst, P.pitch_dst, (size_t)H->ow * (planar ? 1 : 3), H->oh},
+                                 {k.prev_uv, k.pitch_prev_uv, P.dst_uv, P.pitch_dst_uv, (size_t)((H->ow + 1) / 2) * 2, (H->oh + 1) / 2}};
+    bool in_place;
+    return check_keep_prev(n, planes, planar ? 2 : 1, in_place);
 }
 
 // 2. consume frames until the look-ahead window of the next one to emit is complete, or upstream has ended
@@ -105,6 +128,8 @@ static vstab_status choose_cached_map(vstab_handle *H, Pull &P) {
     // (the quantised map holds no chroma positions: the plane-wise warp always evaluates its map)
     // (nor do the cubic, Lanczos and border warps read it, with or without a border mode: they evaluate the map of every frame; the cached
     //  map's kernel has the constant border built in)
+    // (a keep pull neither reads nor updates this state: plain pulls around it see the parameters of the plain pull before)
+    if (P.keep) return VSTAB_OK;
     if (!H->map_cache || H->cfg.resample != VSTAB_RESAMPLE_DEFAULT || P.border_mode != VSTAB_BORDER_CONSTANT || P.rot_bottom || out_is_10bit(P.out_format) ||
         P.out_format == VSTAB_OUT_NV12_PLANAR)
         return VSTAB_OK;
@@ -166,6 +191,10 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
         }
         return st;
     }
+    // a keep pull (refuse_keep: INTER_LINEAR, constant border, ideal lens): with the frame's read-out rotation where it has one
+    if (P.keep)
+        return vstab_warp_nv12_keep(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.keep->prev, P.keep->pitch_prev, P.keep->prev_uv,
+                                    P.keep->pitch_prev_uv, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
     // vstab_set_readout_warp(VSTAB_READOUT_PER_ROW): a frame with a read-out rotation on a handle whose warp has no rotation per row of its
     // own -- a cubic or Lanczos handle, a calibrated one, or both (the formats were checked on entry; the quantised map was not chosen)
     if (P.rot_bottom && H->readout_warp == VSTAB_READOUT_PER_ROW && (H->calibrated || resampled))
@@ -264,10 +293,14 @@ static vstab_status release_slot(vstab_handle *H, int slot) {
 }
 
 // FrameSourceWarp::pull_frame, :452-476
-static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv) {
+static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv,
+                                    const KeepPrev *keep = nullptr) {
+    if (keep && (!H || !dst || !keep->prev || (out_has_chroma_plane(out_format) && (!dst_uv || !keep->prev_uv))))
+        return fail(VSTAB_ERR_INVALID, std::string(keep->fn) + ": null argument");
     if (!H || !dst || (out_has_chroma_plane(out_format) && !dst_uv)) return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: null argument");
-    Pull P{out_format, dst, dst_uv, pitch_dst, pitch_dst_uv, H->border_mode};
+    Pull P{out_format, dst, dst_uv, pitch_dst, pitch_dst_uv, H->border_mode, keep};
     VSTAB_TRY(refuse_formats(H, P));
+    if (keep) VSTAB_TRY(refuse_keep(H, P));
     H->pulled = true;
     HT t_total(HostTimers::TOTAL);
     VSTAB_TRY(advance_until_due(H));
@@ -349,6 +382,17 @@ vstab_status vstab_pull_frame_nv12(vstab_handle *h, void *dst_y, size_t pitch_y,
 vstab_status vstab_pull_frame_nv12_planar(vstab_handle *h, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv) { return pull_frame_impl(h, VSTAB_OUT_NV12_PLANAR, dst_y, pitch_y, dst_uv, pitch_uv); }
 
 vstab_status vstab_pull_frame_p010_planar(vstab_handle *h, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv) { return pull_frame_impl(h, OUT_P010_PLANAR, dst_y, pitch_y, dst_uv, pitch_uv); }
+
+vstab_status vstab_pull_frame_keep(vstab_handle *h, void *dst, size_t pitch_dst, const void *prev, size_t pitch_prev) {
+    const KeepPrev keep = {"vstab_pull_frame_keep", prev, nullptr, pitch_prev, 0};
+    return pull_frame_impl(h, VSTAB_OUT_BGR8, dst, pitch_dst, nullptr, 0, &keep);
+}
+
+vstab_status vstab_pull_frame_nv12_planar_keep(vstab_handle *h, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv, const void *prev_y, size_t pitch_prev_y,
+                                               const void *prev_uv, size_t pitch_prev_uv) {
+    const KeepPrev keep = {"vstab_pull_frame_nv12_planar_keep", prev_y, prev_uv, pitch_prev_y, pitch_prev_uv};
+    return pull_frame_impl(h, VSTAB_OUT_NV12_PLANAR, dst_y, pitch_y, dst_uv, pitch_uv, &keep);
+}
 
 vstab_status vstab_peek_frame(vstab_handle *h, void *dst, size_t pitch_dst) { return vstab_pull_frame(h, dst, pitch_dst); }  // :478-480
 

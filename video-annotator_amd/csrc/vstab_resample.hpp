@@ -3,7 +3,7 @@
 // _REFLECT_101.  One statement of each thing: the quantisation of a map position (the same for all three resamplers), OpenCV's
 // borderInterpolate, the sources a tap reads, the tile's box, its staging into LDS, the read of a footprint row, the blends' channel
 // arithmetic, the map of an output pixel, and -- for cubic and Lanczos with a non-constant border -- the tile and the stateless remap
-// themselves, over a resampler trait.
+// themselves, over a resampler trait.  The bilinear tap is here too: the keep-edge kernels (vstab_warp_keep.hip) blend with it.
 //
 // The tile (resample_tile; k_warp_cubic, k_warp_lanczos4 and k_warp_border run the same phases from the same pieces in their own units,
 // for the reasons given there and in DESIGN.md §16): 64 x 16 output pixels, one workgroup of 256 threads, four rows per thread:
@@ -225,6 +225,55 @@ __device__ __forceinline__ void lds_row(const T *p, uint32_t *v) {
     } else {
 #pragma unroll
         for (int c = 0; c < K; c++) v[c] = p[c];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The bilinear tap, its read and its blend (k_warp_border, k_remap_border; k_warp_keep, k_remap_keep in vstab_warp_keep.hip).
+// ---------------------------------------------------------------------------------------------------------------------
+// bilinear tap: the top-left virtual position and the two weight pairs {w00, w01}, {w10, w11} as int16 halves
+struct BorderTap {
+    int X, Y;
+    uint32_t w0, w1;
+};
+template <int BORDER>
+__device__ __forceinline__ BorderTap border_tap(float ax32, float ay32, int w, int h) {
+    const CubicTap t = cubic_tap(ax32, ay32);  // cvRound, sat16(s >> 5), s & 31: INTER_LINEAR's quantisation
+    const uint32_t fx = t.f & 31, fy = t.f >> 5;
+    BorderTap b;
+    b.X = t.X, b.Y = t.Y;
+    if constexpr (BORDER == VSTAB_BORDER_CONSTANT) {
+        // every position outside is the border value: a pair of taps wholly outside may move to (-2, -1) / (len, len + 1), which keeps the box
+        // inside [-2, len + 1] (the axis pixel of map mode 0 would stretch it to -32768 otherwise)
+        b.X = min(max(b.X, -2), w), b.Y = min(max(b.Y, -2), h);
+    }
+    b.w0 = ((32 - fx) * (32 - fy)) | ((fx * (32 - fy)) << 16);
+    b.w1 = ((32 - fx) * fy) | ((fx * fy) << 16);
+    return b;
+}
+
+// One channel (byte CH of every tap dword): the horizontally adjacent taps' channel gathered into an int16 pair by v_perm_b32, two
+// v_dot2_i32_i16 against the weight pairs.  Weights sum to 1024: no overflow, no saturation needed.
+template <int CH>
+__device__ __forceinline__ uint32_t border_channel(uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11, const BorderTap &t) {
+    constexpr uint32_t sel = CH | 0x0c00u | ((4u + CH) << 16) | 0x0c000000u;  // [left.CH, 0, right.CH, 0]
+    typedef short short2v __attribute__((ext_vector_type(2)));
+    int acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t01, t00, sel)), __builtin_bit_cast(short2v, t.w0), 512, false);
+    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t11, t10, sel)), __builtin_bit_cast(short2v, t.w1), acc, false);
+    return (uint32_t)acc >> 10;
+}
+
+// the four taps of t: from the staged box, or from the source itself when the box was not staged (uniform over the workgroup)
+template <int BORDER, typename T, typename Src>
+__device__ __forceinline__ void border_taps(const Src &s, const TileBox &b, const T *lds, const BorderTap &t, uint32_t (&v)[4]) {
+    if (b.lds) {
+        const int at = (t.Y - b.y0) * b.w + (t.X - b.x0);
+        const T *q = lds + at;
+        lds_row<2>(q, v), lds_row<2>(q + b.w, v + 2);
+    } else {
+        const int x0 = border_index<BORDER>(t.X, s.w), x1 = border_index<BORDER>(t.X + 1, s.w);
+        const int y0 = border_index<BORDER>(t.Y, s.h), y1 = border_index<BORDER>(t.Y + 1, s.h);
+        v[0] = s.row_col(x0, y0), v[1] = s.row_col(x1, y0), v[2] = s.row_col(x0, y1), v[3] = s.row_col(x1, y1);
     }
 }
 

@@ -50,6 +50,7 @@ vstab_status vstab_preload_kernels(void) {
     VSTAB_TRY(preload_cubic_kernels());
     VSTAB_TRY(preload_lanczos4_kernels());
     VSTAB_TRY(preload_border_kernels());
+    VSTAB_TRY(preload_keep_kernels());
     return VSTAB_OK;
 }
 

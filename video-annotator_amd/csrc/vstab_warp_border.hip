@@ -21,54 +21,9 @@
 
 namespace vstab {
 
-// bilinear tap: the top-left virtual position and the two weight pairs {w00, w01}, {w10, w11} as int16 halves
-struct BorderTap {
-    int X, Y;
-    uint32_t w0, w1;
-};
-template <int BORDER>
-__device__ __forceinline__ BorderTap border_tap(float ax32, float ay32, int w, int h) {
-    const CubicTap t = cubic_tap(ax32, ay32);  // cvRound, sat16(s >> 5), s & 31: INTER_LINEAR's quantisation
-    const uint32_t fx = t.f & 31, fy = t.f >> 5;
-    BorderTap b;
-    b.X = t.X, b.Y = t.Y;
-    if constexpr (BORDER == VSTAB_BORDER_CONSTANT) {
-        // every position outside is the border value: a pair of taps wholly outside may move to (-2, -1) / (len, len + 1), which keeps the box
-        // inside [-2, len + 1] (the axis pixel of map mode 0 would stretch it to -32768 otherwise)
-        b.X = min(max(b.X, -2), w), b.Y = min(max(b.Y, -2), h);
-    }
-    b.w0 = ((32 - fx) * (32 - fy)) | ((fx * (32 - fy)) << 16);
-    b.w1 = ((32 - fx) * fy) | ((fx * fy) << 16);
-    return b;
-}
-
-// One channel (byte CH of every tap dword): the horizontally adjacent taps' channel gathered into an int16 pair by v_perm_b32, two
-// v_dot2_i32_i16 against the weight pairs.  Weights sum to 1024: no overflow, no saturation needed.
-template <int CH>
-__device__ __forceinline__ uint32_t border_channel(uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11, const BorderTap &t) {
-    constexpr uint32_t sel = CH | 0x0c00u | ((4u + CH) << 16) | 0x0c000000u;  // [left.CH, 0, right.CH, 0]
-    typedef short short2v __attribute__((ext_vector_type(2)));
-    int acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t01, t00, sel)), __builtin_bit_cast(short2v, t.w0), 512, false);
-    acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(t11, t10, sel)), __builtin_bit_cast(short2v, t.w1), acc, false);
-    return (uint32_t)acc >> 10;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The tile's phases.
-// ---------------------------------------------------------------------------------------------------------------------
-template <int BORDER, typename T, typename Src>
-__device__ __forceinline__ void border_taps(const Src &s, const TileBox &b, const T *lds, const BorderTap &t, uint32_t (&v)[4]) {
-    if (b.lds) {
-        const int at = (t.Y - b.y0) * b.w + (t.X - b.x0);
-        const T *q = lds + at;
-        lds_row<2>(q, v), lds_row<2>(q + b.w, v + 2);
-    } else {
-        const int x0 = border_index<BORDER>(t.X, s.w), x1 = border_index<BORDER>(t.X + 1, s.w);
-        const int y0 = border_index<BORDER>(t.Y, s.h), y1 = border_index<BORDER>(t.Y + 1, s.h);
-        v[0] = s.row_col(x0, y0), v[1] = s.row_col(x1, y0), v[2] = s.row_col(x0, y1), v[3] = s.row_col(x1, y1);
-    }
-}
-
+// The tap, its read (border_taps) and its blend (border_channel) are in vstab_resample.hpp: the keep-edge kernels (vstab_warp_keep.hip)
+// share them.
+//
 // k_warp_border -- NV12 in; PLANAR false: BGR8 out (cvtColor then cv::remap INTER_LINEAR, border mode BORDER; CONSTANT value 0); PLANAR
 // true: the plane-wise warp (luma; chroma at the even pixels' positions halved over the chroma plane's own size; CONSTANT values 16 and
 // (128, 128)).  MODE: map modes 0 .. 5, RS with modes 0 / 1 / 5 and with MAP_RS_FISHD_TO_RECT (the calibrated lens, map mode 1).
