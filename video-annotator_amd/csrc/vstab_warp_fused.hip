@@ -17,8 +17,11 @@
 //   convert  the loaded blocks are converted ONCE per source pixel to BGRx with the cvtColor fixed-point arithmetic and
 //            written to LDS (ds_write_b128); blocks outside the source become the zero border of BORDER_CONSTANT.
 //   sample   when every footprint of the wave lies inside the staged box (the normal case, one wave-uniform test) all
-//            2 RW tap-pair reads of a thread are issued before the first blend; otherwise pixel by pixel with the
-//            global-memory gather for footprints outside the box.
+//            2 RW tap-pair reads of a thread are issued before the first blend.  A wave at the source edge -- footprints
+//            outside the box, all of them wholly outside the source and so zero under BORDER_CONSTANT -- takes the same
+//            batched reads with those footprints pulled into the box and zeroed afterwards, or stores zeros when nothing
+//            of it touches the source (edge_wave); only a footprint that touches the source outside the box sends its
+//            wave pixel by pixel, with the global-memory gather for such footprints.
 //   store    rows transposed to 4-byte-per-lane stores with ds_bpermute.
 // Bit-exactness never depends on the box: a pixel whose 2x2 footprint is not inside the staged box (degenerate
 // rotations, a box larger than the LDS budget, unaligned planes) is sampled straight from global memory with per-tap
@@ -38,6 +41,99 @@
 #include "vstab_warp_tile.hpp"
 
 namespace vstab {
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The batched sample of a thread's RW pixels from the staged box: all tap reads of TAP_GROUP rows first, then their blends.
+// Xr, Yr = the upper left tap of each footprint relative to the box's origin; every footprint must lie inside the box (the caller's
+// wave-wide test, or its clamp).  tile_lds = LDS byte address of the box, wb4 = its row pitch in bytes, both scalars.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int RW, int DEPTH, int BLEND>
+__device__ __forceinline__ void sample_batched(const FusedArgs &ta, const int (&Xr)[RW], const int (&Yr)[RW], const int (&qxb)[RW], const int (&qyb)[RW],
+                                               const uint32_t tile_lds, const uint32_t wb4, uint32_t (&out)[RW]) {
+    constexpr bool PIX8 = DEPTH == 10 && BLEND == VSTAB_BLEND_FP16;
+    constexpr int TG = RW < TAP_GROUP ? RW : TAP_GROUP;  // rows whose tap reads are in flight together
+    if constexpr (PIX8) {
+#pragma unroll
+        for (int j0 = 0; j0 < RW; j0 += TG) {
+            uint2 t0[TG], t1[TG], t2[TG], t3[TG];
+#pragma unroll
+            for (int j = 0; j < TG; j++) {
+                uint32_t ax8, au;  // (as below: shift-add, multiply-add, add)
+                asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(ax8) : "v"(Xr[j0 + j]), "s"(tile_lds));
+                asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(au) : "v"(Yr[j0 + j]), "s"(wb4), "v"(ax8));
+                const LdsPair *u = reinterpret_cast<const LdsPair *>(au), *l = reinterpret_cast<const LdsPair *>(au + wb4);
+                const u32x2 v0 = u[0], v1 = u[1], v2 = l[0], v3 = l[1];
+                t0[j] = make_uint2(v0.x, v0.y), t1[j] = make_uint2(v1.x, v1.y), t2[j] = make_uint2(v2.x, v2.y), t3[j] = make_uint2(v3.x, v3.y);
+            }
+#pragma unroll
+            for (int j = 0; j < TG; j++) out[j0 + j] = blend_bgr10h(t0[j], t1[j], t2[j], t3[j], qxb[j0 + j] & 31, qyb[j0 + j] & 31);
+        }
+    } else
+#pragma unroll
+    for (int j0 = 0; j0 < RW; j0 += TG) {
+        uint32_t t0[TG], t1[TG], t2[TG], t3[TG];
+#pragma unroll
+        for (int j = 0; j < TG; j++) {
+            // LDS addresses by hand: shift-add and multiply-add for the upper tap row, one add for the lower (written as
+            // instructions: the compiler re-associates the expression into four)
+            uint32_t ax4, au;
+            asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(ax4) : "v"(Xr[j0 + j]), "s"(tile_lds));
+            asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(au) : "v"(Yr[j0 + j]), "s"(wb4), "v"(ax4));
+            const LdsWord *u = reinterpret_cast<const LdsWord *>(au), *l = reinterpret_cast<const LdsWord *>(au + wb4);
+            t0[j] = u[0], t1[j] = u[1], t2[j] = l[0], t3[j] = l[1];
+        }
+#pragma unroll
+        for (int j = 0; j < TG; j++) {
+#ifdef VSTAB_DEV
+            if (ta.ablate & 2) out[j0 + j] = t0[j] ^ t1[j] ^ t2[j] ^ t3[j] ^ (qxb[j0 + j] & 31) ^ (qyb[j0 + j] & 31);
+            else
+#endif
+            out[j0 + j] = DEPTH == 10 ? blend_bgr10<BLEND>(t0[j], t1[j], t2[j], t3[j], qxb[j0 + j] & 31, qyb[j0 + j] & 31)
+                                      : blend_bgrx(t0[j], t1[j], t2[j], t3[j], qxb[j0 + j] & 31, qyb[j0 + j] & 31);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// What a wave with a footprint outside the staged box can do instead of going pixel by pixel (wave-uniform).  A footprint wholly
+// outside the source -- gather_pixel_far's test: not (-1 <= X <= sw - 1 and -1 <= Y <= sh - 1) -- is zero under BORDER_CONSTANT (four
+// border taps, (0 + 512) >> 10), whatever the box; one that straddles an edge (X = -1, X = sw - 1, ...) is not, and lies in the box's
+// zero border when there is a box.
+//   EDGE_OUTSIDE  every footprint of the wave is wholly outside the source: zeros, with or without a box
+//   EDGE_CLAMP    the box is staged and every footprint outside it is wholly outside the source: the batched sample with those
+//                 footprints pulled into the box, then zeroed
+//   EDGE_GATHER   a footprint that touches the source is not in the box (a box that had to be cut, a box over the LDS budget,
+//                 unaligned planes, a degenerate rotation): pixel by pixel
+// keep: bit j = pixel j touches the source.  Xr, Yr: box-relative upper left taps; wlim, hlim: the box's limits for them (wlim = 0: no box).
+// ---------------------------------------------------------------------------------------------------------------------
+// PATHS: which of the two a kernel has (edge_paths below).
+enum { EDGE_GATHER = 0, EDGE_CLAMP = 1, EDGE_OUTSIDE = 2 };
+// Two of the 68 kernels stay as they were, or nearly, because the register allocation of the whole kernel turns on it (profiles/edge_waves_4k.txt
+// has the resource table): the 64 x 32 kernel of a caller's map to BGR has EDGE_OUTSIDE only (with EDGE_CLAMP it goes from 72 to 73
+// registers, seven waves to six), the 64 x 32 per-row form of map mode 0 to BGR has neither (with either it spills 12 bytes).
+constexpr int edge_paths(int rwb, int mode, int fmt, bool cached) {
+    return rwb == 8 && fmt == 0 && mode == MAP_RS_CREATEMAP_CL ? 0 : rwb == 8 && fmt == 0 && cached ? 1 : 2;
+}
+template <int RW, int PATHS>
+__device__ __forceinline__ int edge_wave(const WarpArgs &a, const int bx0, const int by0, const int (&Xr)[RW], const int (&Yr)[RW], const uint32_t wlim,
+                                         const uint32_t hlim, const bool use_lds, uint32_t &keep) {
+    // -1 <= X <= sw - 1 as ONE unsigned comparison of the box-relative coordinate against scalars: (uint32_t)(Xr + bx0 + 1) < sw + 1
+    if constexpr (PATHS == 0) return EDGE_GATHER;
+    int fx = bx0 + 1, fy = by0 + 1;
+    asm("" : "+s"(fx), "+s"(fy));
+    const uint32_t sx = (uint32_t)a.sw + 1u, sy = (uint32_t)a.sh + 1u;
+    bool gather = false;
+    keep = 0;
+#pragma unroll
+    for (int j = 0; j < RW; j++) {
+        const bool touches = (uint32_t)(Xr[j] + fx) < sx && (uint32_t)(Yr[j] + fy) < sy;
+        const bool inbox = (uint32_t)Xr[j] < wlim && (uint32_t)Yr[j] < hlim;
+        keep |= (touches ? 1u : 0u) << j;
+        gather = gather || (touches && !inbox);
+    }
+    if (!__builtin_amdgcn_ballot_w64(keep != 0)) return EDGE_OUTSIDE;
+    return PATHS == 2 && use_lds && !__builtin_amdgcn_ballot_w64(gather) ? EDGE_CLAMP : EDGE_GATHER;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // One output tile: 64 columns x 4 RW rows at (x0, y0).  All 256 threads of the workgroup take part.
@@ -254,46 +350,22 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
         }
         if (!__builtin_amdgcn_ballot_w64(mxx >= wlim || mxy >= hlim)) {
             // every footprint of the wave lies in the staged box: all tap reads first, then the blends
-            constexpr int TG = RW < TAP_GROUP ? RW : TAP_GROUP;  // rows whose tap reads are in flight together
-            if constexpr (PIX8) {
+            sample_batched<RW, DEPTH, BLEND>(ta, Xr, Yr, qxb, qyb, tile_lds, wb4, out);
+        } else if (uint32_t keep; const int edge = edge_wave<RW, edge_paths(RWB, MODE, FMT, CACHED)>(a, bx0, by0, Xr, Yr, wlim, hlim, use_lds, keep)) {
+            // a wave at the source edge with nothing to gather (at 4K one wave in eight of the live tiles: the pinhole picture of the fisheye frame is a
+            // pincushion, and the pixels beyond its edge map far outside the box, which the probe cuts to one step round the source)
+            if (edge == EDGE_CLAMP) {
+                // the footprints that are not in the box are wholly outside the source: pulled onto the box's last column / row (a negative
+                // coordinate is huge as unsigned), sampled with the others and then zeroed
+                int Xc[RW], Yc[RW];
 #pragma unroll
-                for (int j0 = 0; j0 < RW; j0 += TG) {
-                    uint2 t0[TG], t1[TG], t2[TG], t3[TG];
+                for (int j = 0; j < RW; j++) Xc[j] = (int)min((uint32_t)Xr[j], wlim - 1u), Yc[j] = (int)min((uint32_t)Yr[j], hlim - 1u);
+                sample_batched<RW, DEPTH, BLEND>(ta, Xc, Yc, qxb, qyb, tile_lds, wb4, out);
 #pragma unroll
-                    for (int j = 0; j < TG; j++) {
-                        uint32_t ax8, au;  // (as below: shift-add, multiply-add, add)
-                        asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(ax8) : "v"(Xr[j0 + j]), "s"(tile_lds));
-                        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(au) : "v"(Yr[j0 + j]), "s"(wb4), "v"(ax8));
-                        const LdsPair *u = reinterpret_cast<const LdsPair *>(au), *l = reinterpret_cast<const LdsPair *>(au + wb4);
-                        const u32x2 v0 = u[0], v1 = u[1], v2 = l[0], v3 = l[1];
-                        t0[j] = make_uint2(v0.x, v0.y), t1[j] = make_uint2(v1.x, v1.y), t2[j] = make_uint2(v2.x, v2.y), t3[j] = make_uint2(v3.x, v3.y);
-                    }
+                for (int j = 0; j < RW; j++) out[j] &= (uint32_t)__builtin_amdgcn_sbfe(keep, j, 1);  // bit j as 0 / ~0
+            } else {
 #pragma unroll
-                    for (int j = 0; j < TG; j++) out[j0 + j] = blend_bgr10h(t0[j], t1[j], t2[j], t3[j], qxb[j0 + j] & 31, qyb[j0 + j] & 31);
-                }
-            } else
-#pragma unroll
-            for (int j0 = 0; j0 < RW; j0 += TG) {
-                uint32_t t0[TG], t1[TG], t2[TG], t3[TG];
-#pragma unroll
-                for (int j = 0; j < TG; j++) {
-                    // LDS addresses by hand: shift-add and multiply-add for the upper tap row, one add for the lower (written as
-                    // instructions: the compiler re-associates the expression into four)
-                    uint32_t ax4, au;
-                    asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(ax4) : "v"(Xr[j0 + j]), "s"(tile_lds));
-                    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(au) : "v"(Yr[j0 + j]), "s"(wb4), "v"(ax4));
-                    const LdsWord *u = reinterpret_cast<const LdsWord *>(au), *l = reinterpret_cast<const LdsWord *>(au + wb4);
-                    t0[j] = u[0], t1[j] = u[1], t2[j] = l[0], t3[j] = l[1];
-                }
-#pragma unroll
-                for (int j = 0; j < TG; j++) {
-#ifdef VSTAB_DEV
-                    if (ta.ablate & 2) out[j0 + j] = t0[j] ^ t1[j] ^ t2[j] ^ t3[j] ^ (qxb[j0 + j] & 31) ^ (qyb[j0 + j] & 31);
-                    else
-#endif
-                    out[j0 + j] = DEPTH == 10 ? blend_bgr10<BLEND>(t0[j], t1[j], t2[j], t3[j], qxb[j0 + j] & 31, qyb[j0 + j] & 31)
-                                              : blend_bgrx(t0[j], t1[j], t2[j], t3[j], qxb[j0 + j] & 31, qyb[j0 + j] & 31);
-                }
+                for (int j = 0; j < RW; j++) out[j] = 0;
             }
         } else {
             // rare (source border with a box that had to be cut, degenerate rotation, box over the LDS budget): pixel by
