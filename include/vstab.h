@@ -616,6 +616,63 @@ VSTAB_API vstab_status vstab_warp_nv12_rs_ex(const void *y, size_t pitch_y, cons
                                              int dst_width, int dst_height, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pinhole lens distortion: OpenCV's Brown-Conrady model on a RECTILINEAR input camera (in_projection VSTAB_PROJ_RECT, map modes 3 and 4),
+ * the (k1, k2, p1, p2, k3) of cv::calibrateCamera, in that order.  All zero is the ideal pinhole of every other entry point.  dist / D: the
+ * five coefficients, floats in the device operators (like params), doubles in the host functions.
+ *   map     the operations of map modes 3 / 4 (VSTAB_MAP_RECT_TO_RECT / _RECT_TO_FISH) up to x = wx / wz, y = wy / wz; then, every
+ *           operation an IEEE binary32 operation of its own (nothing fused):
+ *             xx = x * x;  yy = y * y;  xy = x * y;  r2 = xx + yy;
+ *             g = k3;  g = g * r2 + k2;  g = g * r2 + k1;  rad = 1 + g * r2;
+ *             a = 2 * xy;  dx = p1 * a + p2 * (r2 + 2 * xx);  dy = p1 * (r2 + 2 * yy) + p2 * a;
+ *             xd = x * rad + dx;  yd = y * rad + dy;
+ *           and map = centre + (xd, yd) * focal; outside (NaN) exactly where modes 3 / 4 are (wz <= 0; mode 4: rho >= pi).  Infinities
+ *           and NaN the polynomial produces far off the axis are quantised as everywhere (cvRound: INT_MIN, outside the source).
+ *           tests/pinhole_def.py states it in numpy, tests/golden/pinhole_kat.npz pins it.
+ *   points  OpenCV 4.5's cv::undistortPoints with its default criteria: x0 = (u - cx) / fx, y0 = (v - cy) / fy, start at (x0, y0), exactly
+ *           five steps and no epsilon test:
+ *             r2 = x x + y y;  icdist = 1 / (1 + ((k3 r2 + k2) r2 + k1) r2);  icdist < 0: (x, y) = (x0, y0), stop;
+ *             dX = 2 p1 x y + p2 (r2 + 2 x x);  dY = p1 (r2 + 2 y y) + 2 p2 x y;  x = (x0 - dX) icdist;  y = (y0 - dY) icdist;
+ *           then R and P as vstab_fisheye_undistort_points applies them.
+ * Accepted coefficients: all five finite, in fp64 and after the cast to fp32.  Anything else is VSTAB_ERR_INVALID ("the five distortion
+ * coefficients must be finite").  There is no monotonicity rule (OpenCV has none): the kernels that serve these modes take a tile's source
+ * box as the exact reduction over the tile's own map, which needs no monotone map.  map_mode: VSTAB_MAP_RECT_TO_RECT or
+ * VSTAB_MAP_RECT_TO_FISH; any other is VSTAB_ERR_INVALID ("pinhole distortion belongs to a rectilinear input (map modes 3 and 4)").
+ * Not served: 10-bit planes, a rotation per output row, the keep-edge warp, the quantised map, INTER_NEAREST, NV12 through BGR, the
+ * rational and thin-prism terms (k4..k6, s1..s4), a distorted output camera.
+ * ------------------------------------------------------------------------------------------ */
+/* cv::undistortPoints(pts, K, D, R, P) as stated above.  R, P: NULL = identity.  "bad argument" for a NULL pts / K / D / out or n < 0. */
+VSTAB_API vstab_status vstab_undistort_points_pinhole(const double *pts, int n, const double K[9], const double D[5], const double *R,
+                                                      const double *P, double *out);
+/* vstab_estimate_rotation for a rectilinear input lens with D: both point sets are undistorted as above.  D = 0: the estimate a
+ * rectilinear pipeline handle makes without a calibration. */
+VSTAB_API vstab_status vstab_estimate_rotation_pinhole(const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9],
+                                                       const double D[5], uint64_t seed, double R[9], int *inliers);
+/* vstab_create_map_ex of modes 3 / 4 with the polynomial.  Checked in this order: "null pointer", "size must be in [1, 32767]
+ * (createMap.cl:10-11)", "bad pitch", the map mode, the coefficients. */
+VSTAB_API vstab_status vstab_create_map_pinhole(void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows, const float params[17],
+                                                const float dist[5], int map_mode, void *stream);
+/* The warp through the distorted rectilinear lens, every 8-bit resampler and border mode.  resample: VSTAB_RESAMPLE_DEFAULT (INTER_LINEAR),
+ * _CUBIC or _LANCZOS4; border_mode: VSTAB_BORDER_CONSTANT, _REPLICATE, _REFLECT or _REFLECT_101; map_mode: 3 or 4; out_format:
+ * VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR.  Nothing new is defined behind the map: the frame is the map above (tests/pinhole_def.py: maps)
+ * fed to the resampler's own definition, as for vstab_warp_nv12_dist_ex.  DEFAULT runs vstab_warp_nv12_border's tile kernel (the constant
+ * border included), CUBIC / LANCZOS4 the tile kernels that vstab_warp_nv12_rs_ex runs for them, each with the distorted map and one
+ * rotation.  With dist all zero the call is the older entry point's launch, same bytes: vstab_warp_nv12_ex, _border, _cubic[_border] or
+ * _lanczos4[_border].
+ * Every refusal is VSTAB_ERR_INVALID, made before any device work, in this order, each message behind "vstab_warp_nv12_pinhole: ":
+ *   1. dist NULL: "null pointer";
+ *   2. vstab_warp_nv12_cubic_border's checks in its order: "null pointer" (y, uv, dst, params), "source must be even-sized and <= 32767",
+ *      "output size must be in [1, 32767]", "the pinhole-lens warp emits VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR (NV12 through BGR is
+ *      not served)", "border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)", "pitch smaller
+ *      than row", "plane-wise output needs a chroma plane of 2*ceil(width/2) bytes per row", "chroma plane must be 2-B aligned";
+ *   3. "resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)";
+ *   4. every map mode but 3 and 4, known or not: "pinhole distortion belongs to a rectilinear input (map modes 3 and 4)";
+ *   5. "the five distortion coefficients must be finite". */
+VSTAB_API vstab_status vstab_warp_nv12_pinhole(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                               const float params[17], const float dist[5], int map_mode, int resample, int border_mode,
+                                               int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dst_width,
+                                               int dst_height, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The pipeline object: drop-in for FrameSourceWarp behind the FrameSource pull interface
  * (FrameSource.hpp:9-24, FrameSourceWarp.hpp:83-91).
  * ------------------------------------------------------------------------------------------ */
@@ -883,6 +940,23 @@ VSTAB_API vstab_status vstab_set_input_calibration(vstab_handle *h, const double
  * The rotation estimate and the `debug` markers go through the distorted lens as with vstab_set_input_calibration: they do not depend on
  * the resampler. */
 VSTAB_API vstab_status vstab_set_input_calibration_ex(vstab_handle *h, const double K[9], const double D[4]);
+/* "Pinhole lens distortion" on a handle: a rectilinear input camera with D = (k1, k2, p1, p2, k3), and
+ * optionally its calibrated camera matrix K (NULL keeps the camera vstab_create derived from in_dfov; the rule for K is
+ * vstab_set_input_calibration's).  The handle then estimates its rotations with D (both point sets through cv::undistortPoints as above),
+ * inverts the lens where it places the debug markers, and warps every BGR, _frames, _host, peek and plane-wise pull through
+ * vstab_warp_nv12_pinhole with its resampler and the border mode in force at the pull (vstab_set_border_mode / _ex, before or after this
+ * call, as on an uncalibrated handle).  The quantised-map cache steps aside.  Accepted: a handle with lens_mode 1, in_projection
+ * VSTAB_PROJ_RECT, 8-bit pixels, INTER_LINEAR or resample VSTAB_RESAMPLE_CUBIC / _LANCZOS4, not yet pulled from.  Each refusal is
+ * VSTAB_ERR_INVALID behind "vstab_set_input_pinhole: " and leaves the handle as it was: "null argument" (h, D), "a calibration belongs to
+ * lens_mode 1 (the preset path derives its output camera from the input's)", "pinhole distortion belongs to a rectilinear input
+ * (in_projection VSTAB_PROJ_RECT)", "the pinhole-lens warp takes 8-bit pixels, this is a pixel_depth 10 handle", "the pinhole-lens warp
+ * resamples with INTER_LINEAR, INTER_CUBIC or INTER_LANCZOS4, this handle with INTER_NEAREST", "the calibration must be set before the
+ * first pull", "K must be a camera matrix with fx, fy > 0, zero skew and last row 0 0 1", "the five distortion coefficients must be
+ * finite".  Such a handle refuses: NV12 through BGR (vstab_pull_frame_nv12), before a frame is taken, with VSTAB_ERR_INVALID; the keep-edge
+ * pulls with VSTAB_ERR_UNSUPPORTED; and a frame that carries a readout_rotation, which is refused and consumed whatever
+ * vstab_set_readout_warp says (the refusal every rectilinear input makes when it takes such a frame from upstream).
+ * vstab_set_input_calibration[_ex] keep refusing a rectilinear input. */
+VSTAB_API vstab_status vstab_set_input_pinhole(vstab_handle *h, const double K[9], const double D[5]);
 /* What a handle does with a frame that carries a readout_rotation where its warp used to have no rotation per row: handles with resample
  * VSTAB_RESAMPLE_CUBIC or _LANCZOS4, calibrated handles (vstab_set_input_calibration / _ex), or both.  VSTAB_READOUT_REFUSE (the default):
  * as before, the frame is refused and consumed.  VSTAB_READOUT_PER_ROW: the frame is warped by vstab_warp_nv12_rs_ex -- the first row with

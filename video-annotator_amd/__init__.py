@@ -185,6 +185,11 @@ SIGNATURES = {
     "vstab_warp_nv12_keep": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_pull_frame_keep": (_i, [_vp, _vp, _sz, _vp, _sz]),
     "vstab_pull_frame_nv12_planar_keep": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
+    "vstab_set_input_pinhole": (_i, [_vp, _dp, _dp]),
+    "vstab_undistort_points_pinhole": (_i, [_dp, _i, _dp, _dp, _dp, _dp, _dp]),
+    "vstab_estimate_rotation_pinhole": (_i, [_fp, _fp, _i, _dp, _dp, _dp, _u64, _dp, _ip]),
+    "vstab_create_map_pinhole": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _vp]),
+    "vstab_warp_nv12_pinhole": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -285,6 +290,18 @@ def fisheye_undistort_points(pts, K, R=None, P=None, D=None):
     return out
 
 
+def undistort_points_pinhole(pts, K, D, R=None, P=None):
+    """vstab_undistort_points_pinhole: cv::undistortPoints of a rectilinear lens with D = (k1, k2, p1, p2, k3) -> (n, 2) float64."""
+    p = np.ascontiguousarray(pts, np.float64).reshape(-1, 2)
+    Kc, Dc = np.ascontiguousarray(K, np.float64).reshape(9), np.ascontiguousarray(D, np.float64).reshape(5)
+    Rc = None if R is None else np.ascontiguousarray(R, np.float64).reshape(9)
+    Pc = None if P is None else np.ascontiguousarray(P, np.float64).reshape(9)
+    out = np.zeros_like(p)
+    _check(_L.vstab_undistort_points_pinhole(_dptr(p), p.shape[0], _dptr(Kc), _dptr(Dc), None if Rc is None else _dptr(Rc),
+                                             None if Pc is None else _dptr(Pc), _dptr(out)), "vstab_undistort_points_pinhole")
+    return out
+
+
 def map_params(K_in, K_out, R):
     a = np.ascontiguousarray(K_in, np.float64).reshape(9)
     b = np.ascontiguousarray(K_out, np.float64).reshape(9)
@@ -359,6 +376,17 @@ def create_map_dist(params, dist, cols, rows, mode=MAP_FISH_TO_RECT, device="cud
     my = torch.empty((rows, cols), dtype=torch.float32, device=device)
     _check(_L.vstab_create_map_dist(mx.data_ptr(), mx.stride(0) * 4, my.data_ptr(), my.stride(0) * 4, cols, rows, _fptr(p), _fptr(d), int(mode),
                                     _stream()), "vstab_create_map_dist")
+    return mx, my
+
+
+def create_map_pinhole(params, dist, cols, rows, mode=MAP_RECT_TO_RECT, device="cuda"):
+    """vstab_create_map_pinhole: the map planes of mode 3 / 4 with the rectilinear input lens's (k1, k2, p1, p2, k3)."""
+    import torch
+    p, d = np.ascontiguousarray(params, np.float32), np.ascontiguousarray(dist, np.float32).reshape(5)
+    mx = torch.empty((rows, cols), dtype=torch.float32, device=device)
+    my = torch.empty((rows, cols), dtype=torch.float32, device=device)
+    _check(_L.vstab_create_map_pinhole(mx.data_ptr(), mx.stride(0) * 4, my.data_ptr(), my.stride(0) * 4, cols, rows, _fptr(p), _fptr(d), int(mode),
+                                       _stream()), "vstab_create_map_pinhole")
     return mx, my
 
 
@@ -546,6 +574,27 @@ def warp_nv12_dist_ex(nv12, params, dist, dw, dh, mode=MAP_FISH_TO_RECT, resampl
     yo, co = out
     _check(_L.vstab_warp_nv12_dist_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), int(out_format),
                                       yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_dist_ex")
+    return yo, co
+
+
+def warp_nv12_pinhole(nv12, params, dist, dw, dh, mode=MAP_RECT_TO_RECT, resample=RESAMPLE_DEFAULT, border_mode=BORDER_CONSTANT, out_format=OUT_BGR8,
+                      out=None):
+    """vstab_warp_nv12_pinhole: the warp through a rectilinear lens with dist = (k1, k2, p1, p2, k3), map mode 3 / 4, with a resampler
+    (RESAMPLE_DEFAULT, _CUBIC, _LANCZOS4) and a border mode (BORDER_*).  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma)."""
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    p, d = np.ascontiguousarray(params, np.float32), np.ascontiguousarray(dist, np.float32).reshape(5)
+    if out_format == OUT_BGR8:
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
+        _check(_L.vstab_warp_nv12_pinhole(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), OUT_BGR8,
+                                          out.data_ptr(), out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_pinhole")
+        return out
+    if out is None:
+        out = nv12_out_planes(dw, dh, nv12.device)
+    yo, co = out
+    _check(_L.vstab_warp_nv12_pinhole(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), int(out_format),
+                                      yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_pinhole")
     return yo, co
 
 
@@ -970,6 +1019,19 @@ def estimate_rotation(prev_xy, cur_xy, K_in, K_out, seed=1, D=None):
     return R.reshape(3, 3), inl.value
 
 
+def estimate_rotation_pinhole(prev_xy, cur_xy, K_in, K_out, D, seed=1):
+    """vstab_estimate_rotation_pinhole: estimate_rotation for a rectilinear input lens with D = (k1, k2, p1, p2, k3) -> (R, inliers)."""
+    a = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
+    b = np.ascontiguousarray(cur_xy, np.float32).reshape(-1, 2)
+    Ki, Ko = np.ascontiguousarray(K_in, np.float64).reshape(9), np.ascontiguousarray(K_out, np.float64).reshape(9)
+    Dc = np.ascontiguousarray(D, np.float64).reshape(5)
+    R = np.zeros(9)
+    inl = _c.c_int()
+    _check(_L.vstab_estimate_rotation_pinhole(_fptr(a), _fptr(b), a.shape[0], _dptr(Ki), _dptr(Ko), _dptr(Dc), seed, _dptr(R), _c.byref(inl)),
+           "vstab_estimate_rotation_pinhole")
+    return R.reshape(3, 3), inl.value
+
+
 def gyro_integrate(samples, rate_scale, t_prev_first_row, t_first_row, t_last_row):
     """vstab_gyro_integrate.  samples: (n, 5) doubles {start_ts, end_ts, roll, pitch, yaw} (the reference's GyroFrame,
     gpmf.cpp:5-11) -> (R_delta, R_readout) 3x3."""
@@ -1037,10 +1099,11 @@ class Stabilizer:
     source for `total` pulls) or a Python iterable of such tensors (python callback source)."""
 
     def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, calibration=None,
-                 calibration_ex=None, **cfg_kw):
+                 calibration_ex=None, pinhole=None, **cfg_kw):
         """border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
         calibration: (K, D) for set_input_calibration right after create, applied after border_mode (K None keeps the camera from in_dfov).
         calibration_ex: the same through set_input_calibration_ex (every resampler and border mode).
+        pinhole: (K, D) for set_input_pinhole right after create: a rectilinear input lens with D = (k1, k2, p1, p2, k3) (K None as above).
         hold (iterable sources): vstab_frame.hold -- how many further pulls each tensor is kept alive and unchanged
         for; from smooth_radius + 14 on the library uses the tensors in place instead of copying them.
         bit_depth / readouts (list sources): P010 frames as int16 tensors of shape (h * 3 / 2, w); one 3x3 read-out
@@ -1106,6 +1169,8 @@ class Stabilizer:
             self.set_input_calibration(*calibration)
         if calibration_ex is not None:
             self.set_input_calibration_ex(*calibration_ex)
+        if pinhole is not None:
+            self.set_input_pinhole(*pinhole)
 
     def _calibrate(self, fn, K, D):
         Kc = None if K is None else np.ascontiguousarray(K, np.float64).reshape(9)
@@ -1122,6 +1187,15 @@ class Stabilizer:
     def set_input_calibration_ex(self, K, D):
         """vstab_set_input_calibration_ex: set_input_calibration for INTER_LINEAR, INTER_CUBIC and INTER_LANCZOS4 handles, with any border mode."""
         self._calibrate("vstab_set_input_calibration_ex", K, D)
+
+    def set_input_pinhole(self, K, D):
+        """vstab_set_input_pinhole: a rectilinear input lens with camera matrix K (3x3, or None) and D = (k1, k2, p1, p2, k3), before the first
+        pull."""
+        Kc = None if K is None else np.ascontiguousarray(K, np.float64).reshape(9)
+        Dc = np.ascontiguousarray(D, np.float64).reshape(5)
+        _check(_L.vstab_set_input_pinhole(self._h, None if Kc is None else _dptr(Kc), _dptr(Dc)), "vstab_set_input_pinhole")
+        if Kc is not None:
+            self.K_in = Kc.reshape(3, 3).copy()
 
     def warps_from_cache(self):
         """Test hook vstabx_warps_from_cache: warps of this handle that read the quantised map of an earlier frame with equal parameters."""

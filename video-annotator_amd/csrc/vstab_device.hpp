@@ -126,6 +126,20 @@ __device__ __forceinline__ float distort_theta(float at, const Distortion &d) {
     g = g * s2 + d.k1;
     return at * (1.0f + g * s2);
 }
+// normalised pinhole coordinates -> distorted ones through OpenCV's (k1, k2, p1, p2, k3), every operation rounded on its own: DESIGN.md
+// section 23.  d = 0 returns (x, y) bit for bit wherever x * x + y * y is finite.
+__device__ __forceinline__ void distort_pinhole(float x, float y, const float *d, float &xd, float &yd) {
+    const float k1 = d[0], k2 = d[1], p1 = d[2], p2 = d[3], k3 = d[4];
+    const float xx = x * x, yy = y * y, xy = x * y, r2 = xx + yy;
+    float g = k3;
+    g = g * r2 + k2;
+    g = g * r2 + k1;
+    const float rad = 1.0f + g * r2;
+    const float a = 2.0f * xy;
+    const float dx = p1 * a + p2 * (r2 + 2.0f * xx);
+    const float dy = p1 * (r2 + 2.0f * yy) + p2 * a;
+    xd = x * rad + dx, yd = y * rad + dy;
+}
 __device__ __forceinline__ void map_pixel32(const MapParams32 &p, const ColTerm &c, const RowTerm &r,
                                             float &ax, float &ay) {
     const float wx = (c.a0 + r.b0) + p.r02;
@@ -235,7 +249,9 @@ enum MapMode { MAP_CREATEMAP_CL = 0, MAP_FISH_TO_RECT = 1, MAP_FISH_TO_FISH = 2,
                // internal: modes 1 / 2 with the input lens's distortion polynomial (vstab_*_dist)
                MAP_FISHD_TO_RECT = 9, MAP_FISHD_TO_FISH = 10,
                // internal: mode 9 with a per-row rotation (vstab_warp_nv12_rs_ex: k_warp_border, k_warp_cubic_rs, k_warp_lanczos4_rs)
-               MAP_RS_FISHD_TO_RECT = 11 };
+               MAP_RS_FISHD_TO_RECT = 11,
+               // internal: modes 3 / 4 with the input lens's Brown-Conrady polynomial (vstab_*_pinhole)
+               MAP_RECTD_TO_RECT = 12, MAP_RECTD_TO_FISH = 13 };
 // the projection pair (and arithmetic) of a mode: the rolling-shutter modes share their base mode's
 constexpr bool map_mode_is_rs(int mode) { return (mode >= MAP_RS_CREATEMAP_CL && mode <= MAP_RS_CREATEMAP_CL_OPENCL) || mode == MAP_RS_FISHD_TO_RECT; }
 constexpr int map_mode_base(int mode) {
@@ -245,7 +261,8 @@ constexpr int map_mode_base(int mode) {
 template <int MODE>
 struct ModeTraits {
     static constexpr bool dist = MODE == MAP_FISHD_TO_RECT || MODE == MAP_FISHD_TO_FISH || MODE == MAP_RS_FISHD_TO_RECT;  // theta -> theta_d on the way into the input lens
-    static constexpr bool out_fish = MODE == MAP_FISH_TO_FISH || MODE == MAP_RECT_TO_FISH || MODE == MAP_FISHD_TO_FISH;
+    static constexpr bool rectd = MODE == MAP_RECTD_TO_RECT || MODE == MAP_RECTD_TO_FISH;  // (k1, k2, p1, p2, k3) on the way into a rectilinear input lens
+    static constexpr bool out_fish = MODE == MAP_FISH_TO_FISH || MODE == MAP_RECT_TO_FISH || MODE == MAP_FISHD_TO_FISH || MODE == MAP_RECTD_TO_FISH;
     static constexpr bool in_fish = MODE == MAP_FISH_TO_RECT || MODE == MAP_FISH_TO_FISH || MODE == MAP_CREATEMAP_CL || MODE == MAP_CREATEMAP_CL_OPENCL || dist;
 };
 
@@ -362,9 +379,10 @@ __device__ __forceinline__ float norm_coord(float n, float d, float rcp_refined_
 // the map-plane kernel -- the scaling is an exact power of two either way), P the output camera and rotation.
 // c / r are the hoisted column / row products for pinhole output; vx, vy the normalised output coordinates for
 // fisheye output.  Outside (NaN) when the output ray is beyond 180 degrees or lands behind the input camera.
+// pd: the five coefficients of the MAP_RECTD_* modes (MapParams32 has room for four), read by no other mode.
 template <int MODE>
 __device__ __forceinline__ void map_pixel_ex(const MapParams32 &p, const MapParams &P, const ColTerm &c, const RowTerm &r,
-                                             float vx, float vy, float &ax, float &ay) {
+                                             float vx, float vy, float &ax, float &ay, const float *pd = nullptr) {
     if constexpr (MODE == MAP_CREATEMAP_CL) {
         map_pixel32(p, c, r, ax, ay);
     } else if constexpr (MODE == MAP_CREATEMAP_CL_OPENCL) {
@@ -415,6 +433,11 @@ __device__ __forceinline__ void map_pixel_ex(const MapParams32 &p, const MapPara
             const float k = zero ? 1.0f : div_with_rcp(at, rad, rr);
             ax = p.icx32 + (px * k) * p.ifx32;
             ay = p.icy32 + (py * k) * p.ify32;
+        } else if constexpr (ModeTraits<MODE>::rectd) {
+            float xd, yd;
+            distort_pinhole(px, py, pd, xd, yd);
+            ax = p.icx32 + xd * p.ifx32;
+            ay = p.icy32 + yd * p.ify32;
         } else {
             ax = p.icx32 + px * p.ifx32;
             ay = p.icy32 + py * p.ify32;

@@ -86,8 +86,26 @@ bool fisheye_theta(double theta_d, const double k[4], double &theta) {
     return converged && !((theta_d < 0 && theta > 0) || (theta_d > 0 && theta < 0));
 }
 
+// OpenCV 4.5 cv::undistortPoints with its default criteria for one normalised point of a rectilinear lens with D = (k1, k2, p1, p2, k3): five
+// fixed-point steps from (x0, y0), no epsilon test; a negative 1 / (radial factor) gives the point back as it came
+void pinhole_undistort_normalised(double x0, double y0, const double D[5], double &x, double &y) {
+    const double k1 = D[0], k2 = D[1], p1 = D[2], p2 = D[3], k3 = D[4];
+    x = x0, y = y0;
+    for (int j = 0; j < 5; j++) {
+        const double r2 = x * x + y * y;
+        const double icdist = 1 / (1 + ((k3 * r2 + k2) * r2 + k1) * r2);
+        if (icdist < 0) {
+            x = x0, y = y0;
+            break;
+        }
+        const double dX = 2 * p1 * x * y + p2 * (r2 + 2 * x * x), dY = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
+        x = (x0 - dX) * icdist, y = (y0 - dY) * icdist;
+    }
+}
+
 // OpenCV 4.5 fisheye::undistortPoints: theta_d clipped to pi/2, theta from fisheye_theta, scale = tan(theta)/theta_d; a point whose theta
-// was not found is (-1e6, -1e6).  D null = zero: today's ideal lens, bit for bit.
+// was not found is (-1e6, -1e6).  D null = zero: today's ideal lens, bit for bit.  fish false: a rectilinear lens, D its (k1, k2, p1, p2, k3)
+// (five; pinhole_undistort_normalised) or null for the ideal pinhole.
 void fisheye_undistort(const double *pts, int n, const Mat3 &K, const Mat3 &RR, double *out, bool fish, const double *D) {
     static const double zero[4] = {0, 0, 0, 0};
     const double *k = D ? D : zero;
@@ -105,7 +123,8 @@ void fisheye_undistort(const double *pts, int n, const Mat3 &K, const Mat3 &RR, 
             scale = std::tan(theta) / theta_d;
         }
         if (!fish) scale = 1.0;
-        const double ux = pwx * scale, uy = pwy * scale;
+        double ux = pwx * scale, uy = pwy * scale;
+        if (!fish && D) pinhole_undistort_normalised(pwx, pwy, D, ux, uy);
         const double x = RR(0, 0) * ux + RR(0, 1) * uy + RR(0, 2);
         const double y = RR(1, 0) * ux + RR(1, 1) * uy + RR(1, 2);
         const double z = RR(2, 0) * ux + RR(2, 1) * uy + RR(2, 2);
@@ -235,6 +254,23 @@ vstab_status vstab_fisheye_undistort_points_d(const double *pts, int n, const do
                                               double *out) {
     if (!D) return fail(VSTAB_ERR_INVALID, "vstab_fisheye_undistort_points_d: bad argument");
     return undistort_points("vstab_fisheye_undistort_points_d", pts, n, K, D, R, P, out);
+}
+
+vstab_status vstab_undistort_points_pinhole(const double *pts, int n, const double K[9], const double D[5], const double *R, const double *P,
+                                            double *out) {
+    const std::string name = "vstab_undistort_points_pinhole";
+    if (!pts || !K || !D || !out || n < 0) return fail(VSTAB_ERR_INVALID, name + ": bad argument");
+    VSTAB_TRY(check_pinhole_distortion(name, D));
+    Mat3 k, rr = Mat3::identity();
+    std::memcpy(k.m, K, sizeof(k.m));
+    if (R) std::memcpy(rr.m, R, sizeof(rr.m));
+    if (P) {
+        Mat3 p;
+        std::memcpy(p.m, P, sizeof(p.m));
+        rr = p * rr;
+    }
+    fisheye_undistort(pts, n, k, rr, out, false, D);
+    return VSTAB_OK;
 }
 
 void vstab_map_params(const double K_in[9], const double K_out[9], const double R[9], float params[17]) {

@@ -34,10 +34,13 @@ struct Mat3 {
 
 bool preset_camera(int preset, int w, int h, Mat3 &K);
 // fish = false: pinhole input, the points are only normalised and rotated
-// D: k1..k4 of the fisheye lens (checked by the caller: check_distortion), null = an ideal equidistant lens
+// D: k1..k4 of the fisheye lens (checked by the caller: check_distortion), null = an ideal equidistant lens; fish = false: the rectilinear
+// lens's (k1, k2, p1, p2, k3) (check_pinhole_distortion), null = the ideal pinhole
 void fisheye_undistort(const double *pts, int n, const Mat3 &K, const Mat3 &RR, double *out, bool fish = true, const double *D = nullptr);
 // theta_d -> theta through k1..k4 (Newton, as fisheye_undistort runs it); false when no theta was found
 bool fisheye_theta(double theta_d, const double k[4], double &theta);
+// cv::undistortPoints' five fixed-point steps for one normalised point of a rectilinear lens with D = (k1, k2, p1, p2, k3)
+void pinhole_undistort_normalised(double x0, double y0, const double D[5], double &x, double &y);
 // camera matrix of a libdewobble-style lens (projection 0 rect / 1 fish, diagonal field of view in degrees)
 bool lens_camera(int projection, double dfov_deg, int w, int h, double cx, double cy, Mat3 &K);
 void output_camera(const Mat3 &Kin, int w, int h, double scale, bool crop, double zoom, Mat3 &Kout, int &ow, int &oh);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <string>
 
@@ -93,6 +94,20 @@ inline vstab_status check_distortion(const std::string &n, const float D[4]) {
 }
 // the map modes whose input camera is a fisheye lens, i.e. the ones the distortion belongs to
 inline bool map_mode_takes_distortion(int map_mode) { return map_mode == VSTAB_MAP_FISH_TO_RECT || map_mode == VSTAB_MAP_FISH_TO_FISH; }
+
+// (k1, k2, p1, p2, k3) of a rectilinear lens as every *_pinhole entry point accepts them: all five finite, in fp64 and after the cast to
+// fp32.  No monotonicity rule: the kernels that serve them take a tile's box as the exact reduction of the tile's own map.
+inline vstab_status check_pinhole_distortion(const std::string &n, const double D[5]) {
+    for (int i = 0; i < 5; i++)
+        if (!std::isfinite(D[i]) || !std::isfinite((float)D[i])) return fail(VSTAB_ERR_INVALID, n + ": the five distortion coefficients must be finite");
+    return VSTAB_OK;
+}
+inline vstab_status check_pinhole_distortion(const std::string &n, const float D[5]) {
+    const double d[5] = {D[0], D[1], D[2], D[3], D[4]};
+    return check_pinhole_distortion(n, d);
+}
+// the map modes whose input camera is rectilinear, i.e. the ones those coefficients belong to
+inline bool map_mode_takes_pinhole(int map_mode) { return map_mode == VSTAB_MAP_RECT_TO_RECT || map_mode == VSTAB_MAP_RECT_TO_FISH; }
 
 // vstab_pack_p010 with a choice of planes (vstab_plane_ops.hip): luma_only narrows the luma plane alone -- what the 10-bit
 // pipeline needs for its tracker

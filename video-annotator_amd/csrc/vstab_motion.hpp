@@ -34,7 +34,7 @@ void rodrigues_inv(const Mat3 &R, double rvec[3]);
 // (fisheye) pixels.  Returns the number of RANSAC inliers; R = rotation since the last frame.
 // in_fish = false: pinhole input lens (libdewobble in_p=rect); the reference only has fisheye input.
 int estimate_rotation(const float *prev, const float *cur, int n, const Mat3 &Kin, const Mat3 &Kout, Pcg32 &rng,
-                      Mat3 &R, bool in_fish = true, const double *D = nullptr);  // D: the input lens's k1..k4 (checked), null = none
+                      Mat3 &R, bool in_fish = true, const double *D = nullptr);  // D: the input lens's k1..k4, or (in_fish false) its k1 k2 p1 p2 k3 (checked), null = none
 
 // Savitzky-Golay weights for (m, t=0, n=2, s=0) -- gram_sg::SavitzkyGolayFilterConfig(r,0,2,0),
 // FrameSourceWarp.cpp:212.

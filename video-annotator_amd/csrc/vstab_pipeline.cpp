@@ -663,6 +663,26 @@ static vstab_status set_input_calibration(vstab_handle *h, const double K[9], co
 
 extern "C" {
 
+vstab_status vstab_set_input_pinhole(vstab_handle *h, const double K[9], const double D[5]) {
+    const std::string n = "vstab_set_input_pinhole: ";
+    if (!h || !D) return fail(VSTAB_ERR_INVALID, n + "null argument");
+    const vstab_config &c = h->cfg;
+    if (c.lens_mode != 1) return fail(VSTAB_ERR_INVALID, n + "a calibration belongs to lens_mode 1 (the preset path derives its output camera from the input's)");
+    if (c.in_projection != VSTAB_PROJ_RECT) return fail(VSTAB_ERR_INVALID, n + "pinhole distortion belongs to a rectilinear input (in_projection VSTAB_PROJ_RECT)");
+    if (c.pixel_depth == 10) return fail(VSTAB_ERR_INVALID, n + "the pinhole-lens warp takes 8-bit pixels, this is a pixel_depth 10 handle");
+    if (c.interpolation == 0 && c.resample == VSTAB_RESAMPLE_DEFAULT)
+        return fail(VSTAB_ERR_INVALID, n + "the pinhole-lens warp resamples with INTER_LINEAR, INTER_CUBIC or INTER_LANCZOS4, this handle with INTER_NEAREST");
+    if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the calibration must be set before the first pull");
+    if (K && !(std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5]) && K[0] > 0 && K[4] > 0 && K[1] == 0 && K[3] == 0 &&
+               K[6] == 0 && K[7] == 0 && K[8] == 1))
+        return fail(VSTAB_ERR_INVALID, n + "K must be a camera matrix with fx, fy > 0, zero skew and last row 0 0 1");
+    VSTAB_TRY(check_pinhole_distortion("vstab_set_input_pinhole", D));
+    if (K) std::memcpy(h->Kin.m, K, sizeof(h->Kin.m));
+    for (int i = 0; i < 5; i++) h->pdist[i] = D[i], h->pdist32[i] = (float)D[i];
+    h->pinhole = true;
+    return VSTAB_OK;
+}
+
 vstab_status vstab_set_input_calibration(vstab_handle *h, const double K[9], const double D[4]) {
     return set_input_calibration(h, K, D, "vstab_set_input_calibration", false);
 }

@@ -133,7 +133,12 @@ struct vstab_handle {
     bool calibrated_borders = false;          // calibrated through vstab_set_input_calibration_ex: vstab_set_border_mode / _ex as without a calibration
     double dist[4] = {0, 0, 0, 0};
     float dist32[4] = {0, 0, 0, 0};
-    const double *distortion() const { return calibrated ? dist : nullptr; }
+    // vstab_set_input_pinhole: a rectilinear input lens's (k1, k2, p1, p2, k3); the handle then warps through vstab_warp_nv12_pinhole
+    bool pinhole = false;
+    double pdist[5] = {0, 0, 0, 0, 0};
+    float pdist32[5] = {0, 0, 0, 0, 0};
+    // the coefficients the rotation estimate undistorts with: k1..k4 where in_fish, the five of a rectilinear lens otherwise
+    const double *distortion() const { return calibrated ? dist : pinhole ? pdist : nullptr; }
     Tracker tracker;
 
     struct Slot {

@@ -148,15 +148,23 @@ __global__ void __launch_bounds__(256) k_create_map(float *__restrict__ mapx, si
     store_map4(mapx, pitch_x, mapy, pitch_y, x0, y, cols, vec_ok, mx, my);
 }
 
-// k_create_map_ex -- the generalised map (modes 1..4, vstab_device.hpp map_pixel_ex) as map planes.
-template <int MODE>
+// k_create_map_ex -- the generalised map (modes 1..4, vstab_device.hpp map_pixel_ex) as map planes.  Lens: the input lens's coefficients --
+// Distortion (k1..k4 of a fisheye lens, MAP_FISHD_*; zero for the ideal modes) or PinholeLens (the five of a rectilinear lens, MAP_RECTD_*).
+struct PinholeLens {
+    float k[5];  // k1, k2, p1, p2, k3
+};
+__device__ __forceinline__ Distortion lens_fisheye(const Distortion &d) { return d; }
+__device__ __forceinline__ Distortion lens_fisheye(const PinholeLens &) { return Distortion{0.0f, 0.0f, 0.0f, 0.0f}; }
+__device__ __forceinline__ const float *lens_pinhole(const Distortion &) { return nullptr; }
+__device__ __forceinline__ const float *lens_pinhole(const PinholeLens &d) { return d.k; }
+template <int MODE, typename Lens = Distortion>
 __global__ void __launch_bounds__(256) k_create_map_ex(float *__restrict__ mapx, size_t pitch_x,
                                                        float *__restrict__ mapy, size_t pitch_y,
-                                                       int cols, int rows, MapParams p, int vec_ok, Distortion d) {
+                                                       int cols, int rows, MapParams p, int vec_ok, Lens d) {
     const int x0 = (blockIdx.x * 16 + threadIdx.x) * 4;
     const int y = blockIdx.y * 16 + threadIdx.y;
     if (x0 >= cols || y >= rows) return;
-    const MapParams32 in = {p.icx, p.icy, p.ifx, p.ify, p.r[2], p.r[5], p.r[8], d};  // unscaled here
+    const MapParams32 in = {p.icx, p.icy, p.ifx, p.ify, p.r[2], p.r[5], p.r[8], lens_fisheye(d)};  // unscaled here
     constexpr bool OCL = MODE == MAP_CREATEMAP_CL_OPENCL;
     const float vy = OCL ? ocl_div((float)y - p.ocy, p.ofy) : ((float)y - p.ocy) / p.ofy;
     const RowTerm rt = {p.r[1] * vy, p.r[4] * vy, p.r[7] * vy};
@@ -168,7 +176,7 @@ __global__ void __launch_bounds__(256) k_create_map_ex(float *__restrict__ mapx,
         // the map-plane operator runs the OpenCL build's instruction stream literally; the fused kernel and the
         // quantised map use its shortened form with this one as the fall-back (vstab_device.hpp)
         if constexpr (OCL) map_pixel_ocl_literal(p.icx, p.icy, p.ifx, p.ify, p.r, ct.a0, ct.a1, ct.a2, vy, mx[i], my[i]);
-        else map_pixel_ex<MODE>(in, p, ct, rt, vx, vy, mx[i], my[i]);
+        else map_pixel_ex<MODE>(in, p, ct, rt, vx, vy, mx[i], my[i], lens_pinhole(d));
     }
     store_map4(mapx, pitch_x, mapy, pitch_y, x0, y, cols, vec_ok, mx, my);
 }
@@ -292,6 +300,25 @@ vstab_status create_map_impl(const std::string &n, void *map_x, size_t pitch_x, 
     return VSTAB_OK;
 }
 
+// vstab_create_map_pinhole: the map planes of modes 3 / 4 through a rectilinear lens's (k1, k2, p1, p2, k3)
+vstab_status create_map_pinhole_impl(const std::string &n, void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows,
+                                     const float params[17], const float dist[5], int map_mode, void *stream) {
+    if (!map_x || !map_y || !params || !dist) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
+    if (cols <= 0 || rows <= 0 || cols > 32767 || rows > 32767) return fail(VSTAB_ERR_INVALID, n + ": size must be in [1, 32767] (createMap.cl:10-11)");
+    if (pitch_x < (size_t)cols * 4 || pitch_y < (size_t)cols * 4 || pitch_x % 4 || pitch_y % 4) return fail(VSTAB_ERR_INVALID, n + ": bad pitch");
+    if (!map_mode_takes_pinhole(map_mode)) return fail(VSTAB_ERR_INVALID, n + ": pinhole distortion belongs to a rectilinear input (map modes 3 and 4)");
+    VSTAB_TRY(check_pinhole_distortion(n, dist));
+    const int vec_ok = ptr_aligned(map_x, 16) && ptr_aligned(map_y, 16) && pitch_x % 16 == 0 && pitch_y % 16 == 0;
+    dim3 grid(div_up(div_up(cols, 4), 16), div_up(rows, 16));
+    const PinholeLens d = {{dist[0], dist[1], dist[2], dist[3], dist[4]}};
+    with_pinhole_mode(map_mode, [&](auto mode) {
+        hipLaunchKernelGGL((k_create_map_ex<decltype(mode)::value, PinholeLens>), grid, dim3(16, 16), 0, static_cast<hipStream_t>(stream), (float *)map_x, pitch_x,
+                           (float *)map_y, pitch_y, cols, rows, map_params(params), vec_ok, d);
+    });
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
 // the quantised map's arguments, checked; with_dist: vstab_quantised_map_dist, which checks the coefficients last
 vstab_status quantised_map_impl(const std::string &n, void *qmap, int dw, int dh, const float params[17], const float *dist, bool with_dist, int map_mode,
                                 void *stream) {
@@ -401,6 +428,11 @@ vstab_status vstab_create_map_ex(void *map_x, size_t pitch_x, void *map_y, size_
 vstab_status vstab_create_map_dist(void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows, const float params[17],
                                    const float dist[4], int map_mode, void *stream) {
     return create_map_impl("vstab_create_map_dist", map_x, pitch_x, map_y, pitch_y, cols, rows, params, dist, true, map_mode, stream);
+}
+
+vstab_status vstab_create_map_pinhole(void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows, const float params[17],
+                                      const float dist[5], int map_mode, void *stream) {
+    return create_map_pinhole_impl("vstab_create_map_pinhole", map_x, pitch_x, map_y, pitch_y, cols, rows, params, dist, map_mode, stream);
 }
 
 vstab_status vstab_create_map(void *map_x, size_t pitch_x, void *map_y, size_t pitch_y, int cols, int rows,

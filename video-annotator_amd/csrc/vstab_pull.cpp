@@ -41,6 +41,7 @@ static vstab_status refuse_formats(const vstab_handle *H, const Pull &P) {
     if (P.border_mode != VSTAB_BORDER_CONSTANT) return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: a border mode other than VSTAB_BORDER_CONSTANT") + served);
     // (nor does the distorted-lens warp of a calibrated handle)
     if (H->calibrated) return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: a calibrated handle (vstab_set_input_calibration)") + served);
+    if (H->pinhole) return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: a calibrated handle (vstab_set_input_pinhole)") + served);
     return VSTAB_OK;
 }
 
@@ -53,6 +54,7 @@ static vstab_status refuse_keep(const vstab_handle *H, const Pull &P) {
     if (P.border_mode != VSTAB_BORDER_CONSTANT)
         return fail(VSTAB_ERR_UNSUPPORTED, n + ": a border mode other than VSTAB_BORDER_CONSTANT is in force (vstab_set_border_mode)");
     if (H->calibrated) return fail(VSTAB_ERR_UNSUPPORTED, n + ": a calibrated handle (vstab_set_input_calibration) has no keep-edge warp");
+    if (H->pinhole) return fail(VSTAB_ERR_UNSUPPORTED, n + ": a calibrated handle (vstab_set_input_pinhole) has no keep-edge warp");
     const bool planar = P.out_format == VSTAB_OUT_NV12_PLANAR;
     const KeepPlane planes[2] = {{k.prev, k.pitch_prev, P.dst, P.pitch_dst, (size_t)H->ow * (planar ? 1 : 3), H->oh},
                                  {k.prev_uv, k.pitch_prev_uv, P.dst_uv, P.pitch_dst_uv, (size_t)((H->ow + 1) / 2) * 2, (H->oh + 1) / 2}};
@@ -129,7 +131,8 @@ static vstab_status choose_cached_map(vstab_handle *H, Pull &P) {
     // (nor do the cubic, Lanczos and border warps read it, with or without a border mode: they evaluate the map of every frame; the cached
     //  map's kernel has the constant border built in)
     // (a keep pull neither reads nor updates this state: plain pulls around it see the parameters of the plain pull before)
-    if (P.keep) return VSTAB_OK;
+    // (nor does the pinhole-lens warp: vstab_set_input_pinhole)
+    if (P.keep || H->pinhole) return VSTAB_OK;
     if (!H->map_cache || H->cfg.resample != VSTAB_RESAMPLE_DEFAULT || P.border_mode != VSTAB_BORDER_CONSTANT || P.rot_bottom || out_is_10bit(P.out_format) ||
         P.out_format == VSTAB_OUT_NV12_PLANAR)
         return VSTAB_OK;
@@ -195,6 +198,14 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
     if (P.keep)
         return vstab_warp_nv12_keep(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.keep->prev, P.keep->pitch_prev, P.keep->prev_uv,
                                     P.keep->pitch_prev_uv, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+    // vstab_set_input_pinhole: vstab_warp_nv12_pinhole with the handle's resampler and the pull's border mode.  It has no rotation per row,
+    // whatever vstab_set_readout_warp says.  (A rectilinear input refuses a frame that carries a read-out rotation where it takes it from
+    // upstream, prefetch_next; should such a frame ever get here it is consumed, as INTER_NEAREST consumes it below.)
+    if (H->pinhole) {
+        if (P.rot_bottom) return refuse_launch("a calibrated handle (vstab_set_input_pinhole) warps frames without a read-out rotation");
+        return vstab_warp_nv12_pinhole(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, H->pdist32, mode, H->cfg.resample, P.border_mode, out_format, P.dst, P.pitch_dst,
+                                       P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+    }
     // vstab_set_readout_warp(VSTAB_READOUT_PER_ROW): a frame with a read-out rotation on a handle whose warp has no rotation per row of its
     // own -- a cubic or Lanczos handle, a calibrated one, or both (the formats were checked on entry; the quantised map was not chosen)
     if (P.rot_bottom && H->readout_warp == VSTAB_READOUT_PER_ROW && (H->calibrated || resampled))
@@ -255,6 +266,8 @@ static vstab_status draw_markers(vstab_handle *H, const Pull &P) {
             if (H->calibrated && !fisheye_theta(thd, H->dist, th)) continue;
             const double sc = thd > 0 ? std::sin(th) / thd : 1.0;
             rx = a * sc, ry = b * sc, rz = std::cos(th);
+        } else if (H->pinhole) {
+            pinhole_undistort_normalised(a, b, H->pdist, rx, ry);  // the distorted pinhole lens: back to the ideal one first
         }
         const double ox = warp_R(0, 0) * rx + warp_R(1, 0) * ry + warp_R(2, 0) * rz, oy = warp_R(0, 1) * rx + warp_R(1, 1) * ry + warp_R(2, 1) * rz,
                      oz = warp_R(0, 2) * rx + warp_R(1, 2) * ry + warp_R(2, 2) * rz;

@@ -36,6 +36,7 @@ struct BorderArgs {  // the kernels that take a rotation per output row (k_warp_
     CubicArgs c;
     float rs_d[9];  // RS: rotation of the last output row minus the first's (c.w.p.r), fp32
     float rs_den;   // and (float)max(dh - 1, 1)
+    float pd[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // MAP_RECTD_*: k1, k2, p1, p2, k3 of a rectilinear input lens (vstab_warp_nv12_pinhole); no other mode reads them
 };
 
 // cvRound (NaN / outside the int range -> INT_MIN), then cv::remap's split: X = saturate_cast<short>(sx >> 5), f = sx & 31
@@ -49,14 +50,15 @@ __device__ __forceinline__ CubicTap cubic_tap(float ax32, float ay32) {  // ax32
 }
 
 // 32 * map of output pixel (x, y): k_quantised_map's arithmetic (the fused kernels' map, bit for bit, in every mode)
+// pd: BorderArgs::pd for the MAP_RECTD_* modes
 template <int MODE>
-__device__ __forceinline__ void cubic_map(const CubicArgs &c, int x, int y, float rfx, float rfy, float &ax, float &ay) {
+__device__ __forceinline__ void cubic_map(const CubicArgs &c, int x, int y, float rfx, float rfy, float &ax, float &ay, const float *pd = nullptr) {
     const MapParams &p = c.w.p;
     const float vy = norm_coord<MODE>((float)y - p.ocy, p.ofy, rfy);
     const RowTerm rt = {p.r[1] * vy, p.r[4] * vy, p.r[7] * vy};
     const float vx = norm_coord<MODE>((float)x - p.ocx, p.ofx, rfx);
     const ColTerm ct = {p.r[0] * vx, p.r[3] * vx, p.r[6] * vx};
-    map_pixel_ex<MODE>(c.p32, p, ct, rt, vx, vy, ax, ay);
+    map_pixel_ex<MODE>(c.p32, p, ct, rt, vx, vy, ax, ay, pd);
 }
 
 // 32 * map of output pixel (x, y): cubic_map's arithmetic; RS: the row's own rotation, m_k = fmaf(t, rs_d[k], r[k]) with
@@ -64,7 +66,7 @@ __device__ __forceinline__ void cubic_map(const CubicArgs &c, int x, int y, floa
 template <int MODE, bool RS>
 __device__ __forceinline__ void border_map(const BorderArgs &ba, int x, int y, float rfx, float rfy, float &ax, float &ay) {
     if constexpr (!RS) {
-        cubic_map<MODE>(ba.c, x, y, rfx, rfy, ax, ay);
+        cubic_map<MODE>(ba.c, x, y, rfx, rfy, ax, ay, ba.pd);
     } else {
         const MapParams &p0 = ba.c.w.p;
         MapParams P = p0;
@@ -425,7 +427,8 @@ __device__ __forceinline__ void resample_tile(const CubicArgs &c, uint8_t *stage
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Cubic and Lanczos with a rotation per output row (k_warp_cubic_rs, k_warp_lanczos4_rs; map modes 0, 1 and 5, and MAP_RS_FISHD_TO_RECT: the
-// calibrated lens), every border mode: resample_tile's phases with border_map<MODE, true> as the map.  BORDER_CONSTANT goes through the
+// calibrated lens), every border mode: resample_tile's phases with border_map<MODE, true> as the map.  The MAP_RECTD_* modes (a rectilinear
+// lens's five coefficients, which travel in BorderArgs) ride the same tile with one rotation: border_map<MODE, false>.  BORDER_CONSTANT goes through the
 // same tile with the constant border's touch filter (R::touches, as k_warp_cubic / k_warp_lanczos4 have it): only the footprints that
 // touch the source enter the box, a tile with none has no box, a pixel whose footprint does not touch is the border value.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -457,7 +460,7 @@ __device__ __forceinline__ void resample_tile_rs(const BorderArgs &ba, uint8_t *
     float ax[RESAMPLE_RW], ay[RESAMPLE_RW];
 #pragma unroll
     for (int j = 0; j < RESAMPLE_RW; j++) {
-        border_map<MODE, true>(ba, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
+        border_map<MODE, !ModeTraits<MODE>::rectd>(ba, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
         t[j] = cubic_tap(ax[j], ay[j]);
     }
     // 2. box of the luma / BGR footprints, in virtual coordinates: every pixel (CONSTANT: those that touch the source)

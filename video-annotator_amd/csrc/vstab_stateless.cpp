@@ -185,15 +185,16 @@ vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const void *next,
 
 }  // extern "C"
 
-// D: the input lens's k1..k4 (vstab_estimate_rotation_d), else null
+// D: the input lens's k1..k4 (vstab_estimate_rotation_d) or, in_fish false, the rectilinear lens's (k1, k2, p1, p2, k3)
+// (vstab_estimate_rotation_pinhole), else null
 static vstab_status estimate_rotation_impl(const std::string &name, const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9],
-                                           const double *D, uint64_t seed, double R[9], int *inliers) {
+                                           const double *D, uint64_t seed, double R[9], int *inliers, bool in_fish = true) {
     if ((n > 0 && (!prev_xy || !cur_xy)) || n < 0 || !K_in || !K_out || !R || !inliers) return fail(VSTAB_ERR_INVALID, name + ": bad argument");
-    if (D) VSTAB_TRY(check_distortion(name, D));
+    if (D) VSTAB_TRY(in_fish ? check_distortion(name, D) : check_pinhole_distortion(name, D));
     Mat3 ki, ko, r;
     std::memcpy(ki.m, K_in, sizeof(ki.m)), std::memcpy(ko.m, K_out, sizeof(ko.m));
     Pcg32 rng(seed);
-    *inliers = estimate_rotation(prev_xy, cur_xy, n, ki, ko, rng, r, true, D);
+    *inliers = estimate_rotation(prev_xy, cur_xy, n, ki, ko, rng, r, in_fish, D);
     std::memcpy(R, r.m, sizeof(r.m));
     return VSTAB_OK;
 }
@@ -209,6 +210,12 @@ vstab_status vstab_estimate_rotation_d(const float *prev_xy, const float *cur_xy
                                        uint64_t seed, double R[9], int *inliers) {
     if (!D) return fail(VSTAB_ERR_INVALID, "vstab_estimate_rotation_d: bad argument");
     return estimate_rotation_impl("vstab_estimate_rotation_d", prev_xy, cur_xy, n, K_in, K_out, D, seed, R, inliers);
+}
+
+vstab_status vstab_estimate_rotation_pinhole(const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9], const double D[5],
+                                             uint64_t seed, double R[9], int *inliers) {
+    if (!D) return fail(VSTAB_ERR_INVALID, "vstab_estimate_rotation_pinhole: bad argument");
+    return estimate_rotation_impl("vstab_estimate_rotation_pinhole", prev_xy, cur_xy, n, K_in, K_out, D, seed, R, inliers, false);
 }
 
 vstab_status vstab_sg_weights(int m, double *weights) {

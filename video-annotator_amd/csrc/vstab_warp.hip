@@ -275,6 +275,42 @@ vstab_status vstab_warp_nv12_rs_ex(const void *y, size_t pitch_y, const void *uv
     return (cubic ? launch_warp_cubic_rs : launch_warp_lanczos4_rs)(ba, map_mode, dist != nullptr, out_format, border_mode, stream);
 }
 
+// A rectilinear input lens with OpenCV's (k1, k2, p1, p2, k3): include/vstab.h, "Pinhole lens distortion".  The order: dist, check_warp_nv12's
+// checks -- handed a mode it accepts, so that every mode but 3 and 4, known or not, gets the one message behind them --, the resampler, the
+// map mode, the coefficients.  All zero: the older entry point's launch.
+vstab_status vstab_warp_nv12_pinhole(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                     const float dist[5], int map_mode, int resample, int border_mode, int out_format, void *dst, size_t pitch_dst,
+                                     void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
+    const std::string n = "vstab_warp_nv12_pinhole";
+    if (!dist) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
+    const bool rect_in = map_mode_takes_pinhole(map_mode);
+    BorderArgs ba;
+    VSTAB_TRY(check_warp_nv12(n, "the pinhole-lens warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr, rect_in ? map_mode : (int)VSTAB_MAP_RECT_TO_RECT,
+                              out_format, &border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, ba.c));
+    if (resample != VSTAB_RESAMPLE_DEFAULT && resample != VSTAB_RESAMPLE_CUBIC && resample != VSTAB_RESAMPLE_LANCZOS4)
+        return fail(VSTAB_ERR_INVALID, n + ": resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)");
+    if (!rect_in) return fail(VSTAB_ERR_INVALID, n + ": pinhole distortion belongs to a rectilinear input (map modes 3 and 4)");
+    VSTAB_TRY(check_pinhole_distortion(n, dist));
+    const bool constant = border_mode == VSTAB_BORDER_CONSTANT, cubic = resample == VSTAB_RESAMPLE_CUBIC;
+    if (dist[0] == 0.0f && dist[1] == 0.0f && dist[2] == 0.0f && dist[3] == 0.0f && dist[4] == 0.0f) {  // the ideal pinhole: what served it before
+        if (resample == VSTAB_RESAMPLE_DEFAULT) {
+            if (constant)
+                return vstab_warp_nv12_ex(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
+            return vstab_warp_nv12_border(y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr, map_mode, out_format, border_mode, dst, pitch_dst, dst_uv,
+                                          pitch_dst_uv, dw, dh, stream);
+        }
+        if (constant)
+            return (cubic ? vstab_warp_nv12_cubic : vstab_warp_nv12_lanczos4)(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, dst, pitch_dst,
+                                                                              dst_uv, pitch_dst_uv, dw, dh, stream);
+        return (cubic ? vstab_warp_nv12_cubic_border : vstab_warp_nv12_lanczos4_border)(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format,
+                                                                                        border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
+    }
+    fill_rolling_shutter(ba, params, nullptr, dh);
+    for (int k = 0; k < 5; k++) ba.pd[k] = dist[k];
+    if (resample == VSTAB_RESAMPLE_DEFAULT) return launch_warp_border_pinhole(ba, map_mode, out_format, border_mode, stream);
+    return (cubic ? launch_warp_cubic_pinhole : launch_warp_lanczos4_pinhole)(ba, map_mode, out_format, border_mode, stream);
+}
+
 vstab_status vstab_warp_nv12_nearest_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                         int map_mode, void *dst, size_t pitch_dst, int dw, int dh, void *stream) {
     if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_nearest: null pointer");

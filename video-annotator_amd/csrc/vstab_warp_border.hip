@@ -26,7 +26,8 @@ namespace vstab {
 //
 // k_warp_border -- NV12 in; PLANAR false: BGR8 out (cvtColor then cv::remap INTER_LINEAR, border mode BORDER; CONSTANT value 0); PLANAR
 // true: the plane-wise warp (luma; chroma at the even pixels' positions halved over the chroma plane's own size; CONSTANT values 16 and
-// (128, 128)).  MODE: map modes 0 .. 5, RS with modes 0 / 1 / 5 and with MAP_RS_FISHD_TO_RECT (the calibrated lens, map mode 1).
+// (128, 128)).  MODE: map modes 0 .. 5, RS with modes 0 / 1 / 5 and with MAP_RS_FISHD_TO_RECT (the calibrated lens, map mode 1); without RS
+// also MAP_RECTD_TO_RECT / _FISH (a rectilinear lens's five coefficients in ba.pd, map modes 3 / 4).
 template <int MODE, bool PLANAR, bool RS, int BORDER>
 __global__ void __launch_bounds__(256) k_warp_border(BorderArgs ba) {
     const WarpArgs &a = ba.c.w;
@@ -166,6 +167,19 @@ vstab_status launch_warp_border_dist(const CubicArgs &c, int map_mode, int out_f
     ba.c = c;
     fill_rolling_shutter(ba, nullptr, nullptr, c.w.dh);
     return launch_warp_border(ba, map_mode, true, false, out_format, border_mode, stream);
+}
+
+// INTER_LINEAR through a rectilinear lens with ba.pd (vstab_warp_nv12_pinhole), every border mode, BORDER_CONSTANT included
+vstab_status launch_warp_border_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream) {
+    with_pinhole_mode(map_mode, [&](auto mode) {
+        with_border_mode(border_mode, [&](auto border) {
+            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
+                launch_tiles(k_warp_border<decltype(mode)::value, decltype(planar)::value, false, decltype(border)::value>, ba, ba.c.w.dw, ba.c.w.dh, stream);
+            });
+        });
+    });
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
 }
 
 }  // namespace vstab

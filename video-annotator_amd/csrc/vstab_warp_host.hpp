@@ -273,6 +273,30 @@ vstab_status launch_warp_lanczos4_rs(const BorderArgs &ba, int map_mode, bool di
 // k_warp_border of checked arguments (vstab_warp_border.hip): rs with dist is INTER_LINEAR on a calibrated lens with a rotation per row
 vstab_status launch_warp_border(const BorderArgs &ba, int map_mode, bool dist, bool rs, int out_format, int border_mode, void *stream);
 
+// vstab_warp_nv12_pinhole's kernels: a rectilinear input lens with (k1, k2, p1, p2, k3) in ba.pd (checked; map mode 3 or 4; rs_d zero), one
+// launcher per resampler's unit.  The kernels are the ones that take a BorderArgs -- k_warp_border<MODE, PLANAR, false, BORDER> and
+// KS::warp_rs<MODE, PLANAR, BORDER>() -- with MODE the mode's MAP_RECTD_* form, whose map is border_map<MODE, false>.
+template <typename F>
+void with_pinhole_mode(int map_mode, F &&f) {
+    if (map_mode == VSTAB_MAP_RECT_TO_RECT) f(mode_constant<MAP_RECTD_TO_RECT>{});
+    else f(mode_constant<MAP_RECTD_TO_FISH>{});
+}
+template <typename KS>
+vstab_status launch_warp_resample_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream) {
+    with_pinhole_mode(map_mode, [&](auto mode) {
+        with_border_mode(border_mode, [&](auto border) {
+            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
+                launch_tiles(KS::template warp_rs<decltype(mode)::value, decltype(planar)::value, decltype(border)::value>(), ba, ba.c.w.dw, ba.c.w.dh, stream);
+            });
+        });
+    });
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+vstab_status launch_warp_cubic_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream);
+vstab_status launch_warp_lanczos4_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream);
+vstab_status launch_warp_border_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream);
+
 template <typename KS>
 vstab_status remap_resample(const char *name, const void *src, size_t pitch_src, int sw, int sh, int channels, const void *map_x, size_t pitch_x,
                             const void *map_y, size_t pitch_y, const int *border_mode, const int border[3], void *dst, size_t pitch_dst, int dw, int dh,

@@ -185,7 +185,8 @@ __global__ void __launch_bounds__(256) k_remap_lanczos4_border(VSTAB_REMAP_PARAM
 }
 
 // k_warp_lanczos4_rs -- the warp with a rotation per output row (vstab_warp_nv12_rs_ex; map modes 0, 1, 5 and MAP_RS_FISHD_TO_RECT), every
-// border mode, BORDER_CONSTANT included: resample_tile_rs (vstab_resample.hpp)
+// border mode, BORDER_CONSTANT included: resample_tile_rs (vstab_resample.hpp).  MAP_RECTD_TO_RECT / _FISH (vstab_warp_nv12_pinhole): the
+// same tile with one rotation and the rectilinear lens's five coefficients, which travel in BorderArgs
 template <int MODE, bool PLANAR, int BORDER>
 __global__ void __launch_bounds__(256) k_warp_lanczos4_rs(BorderArgs ba) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[RESAMPLE_LDS_BYTES];
@@ -223,6 +224,10 @@ vstab_status launch_warp_lanczos4_dist(const CubicArgs &c, int map_mode, int out
 
 vstab_status launch_warp_lanczos4_rs(const BorderArgs &ba, int map_mode, bool dist, int out_format, int border_mode, void *stream) {
     return launch_warp_resample_rs<Lanczos4Kernels>(ba, map_mode, dist, out_format, border_mode, stream);
+}
+
+vstab_status launch_warp_lanczos4_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream) {
+    return launch_warp_resample_pinhole<Lanczos4Kernels>(ba, map_mode, out_format, border_mode, stream);
 }
 
 }  // namespace vstab
