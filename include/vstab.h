@@ -441,6 +441,35 @@ VSTAB_API vstab_status vstab_good_features_ex(const void *gray, size_t pitch, in
                                               int max_corners, double quality, double min_distance, int detector,
                                               float *xy, int *count, int *detector_used, void *stream);
 
+/* ---- Detection mask ----------------------------------------------------------------------------------------------------------------
+ * goodFeaturesToTrack's `mask` argument, as OpenCV 4.5's goodFeaturesToTrack(gray, corners, max_corners, quality, min_distance, mask, 3,
+ * false, 0.04) applies it on its CPU path.  mask: width x height bytes, pitch_mask >= width; non-zero = "a corner may be reported here".
+ *   1. The eigenvalue map is cornerMinEigenVal(3, 3) of the whole image: the mask plays no part in it, the derivative and box windows
+ *      read masked-out pixels.
+ *   2. maxVal is the maximum of the map over the pixels with mask != 0 (minMaxLoc(eig, 0, &maxVal, 0, 0, mask)); with no such pixel the
+ *      result is 0 corners.
+ *   3. The threshold is (float)((double)maxVal * quality), strict >, applied to every pixel.
+ *   4. The 3 x 3 maximum test runs over all pixels: a masked-out neighbour competes, and a masked-in pixel beside a stronger masked-out one
+ *      is not a corner (dilate knows no mask).
+ *   5. A pixel is a candidate iff it is an interior pixel, passes 3 and 4, and mask != 0 there.
+ *   6. The order (value descending, ties: later raster index first), the min_distance grid and max_corners are those of
+ *      vstab_good_features.
+ * A mask that is non-zero everywhere gives the corners of vstab_good_features_ex bit for bit.  The detectors take the maximum in the order of
+ * the floats' bits read as int32, which is the float order while the maximum is not negative: a frame whose maximum -- under a mask, whose
+ * maximum over the masked-in pixels -- is negative (a frame of rounding noise around zero) is outside what this definition covers, with
+ * or without a mask.  The mask governs DETECTION only: the tracker follows a corner wherever it goes, into masked-out areas too, as
+ * calcOpticalFlowPyrLK does.
+ *
+ * vstab_good_features_mask is vstab_good_features_ex with a device mask.  mask == NULL: the launches and the corners of
+ * vstab_good_features_ex.  detector: VSTAB_DETECTOR_AUTO and VSTAB_DETECTOR_FUSED (the same here: the fused pass, and the two-pass detector
+ * behind it when more than 2^18 keys survive) or VSTAB_DETECTOR_TWO_PASS; all honour the mask and give the same corners.  Refused with
+ * VSTAB_ERR_INVALID before any launch, in this order: "vstab_good_features_mask: bad argument" (what vstab_good_features_ex refuses, an
+ * unknown detector included); with a mask, "vstab_good_features_mask: the mask's pitch is smaller than the image's width" and
+ * "vstab_good_features_mask: mask planes of 4 GiB or more are not supported" ((uint64_t)pitch_mask * height >= 2^32). */
+VSTAB_API vstab_status vstab_good_features_mask(const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask,
+                                                int max_corners, double quality, double min_distance, int detector,
+                                                float *xy, int *count, int *detector_used, void *stream);
+
 /* Replaces calcOpticalFlowPyrLK with default parameters (win 21x21, maxLevel 3, 30 iterations,
  * eps 0.01, minEigThreshold 1e-4), FrameSourceWarp.cpp:252.  prev/next: device gray images of the
  * same size; prev_xy: n host (x,y) pairs; next_xy / status: host outputs (n pairs / n bytes). */
@@ -968,6 +997,19 @@ VSTAB_API vstab_status vstab_set_input_pinhole(vstab_handle *h, const double K[9
  * VSTAB_ERR_INVALID. */
 enum { VSTAB_READOUT_REFUSE = 0, VSTAB_READOUT_PER_ROW = 1 };
 VSTAB_API vstab_status vstab_set_readout_warp(vstab_handle *h, int mode);
+/* The detection mask of a handle ("Detection mask" above): every corner detection of the handle -- the first frame's, a key frame's, the
+ * one run ahead of a planned key frame -- reports corners only where mask != 0.  mask: bytes of the size of the input luma plane
+ * (the vstab_frame width x height upstream delivers; a pixel_depth 10 handle takes one as well, its detector reads the luma narrowed to 8 bits either way), in
+ * device (mem = VSTAB_MEM_DEVICE) or host memory (VSTAB_MEM_HOST), rows pitch_mask bytes apart.  The handle copies it into device memory of
+ * its own; the call returns when the copy is complete, and the caller may free the mask (a device mask is read
+ * on the null stream: writes to it on a non-blocking stream have to be complete).  mask == NULL removes the mask (pitch_mask and mem
+ * are not looked at).  Allowed before the first pull only.  A handle without a mask behaves as it always did.  Refused with VSTAB_ERR_INVALID,
+ * the handle unchanged, in this order: "vstab_set_detection_mask: null handle"; "vstab_set_detection_mask: no detector runs on this handle
+ * (tracking = 0)"; "vstab_set_detection_mask: the mask must be set before the first pull"; with a mask, "vstab_set_detection_mask: the
+ * mask's pitch is smaller than the frame's width" and "vstab_set_detection_mask: mem must be VSTAB_MEM_DEVICE (0) or VSTAB_MEM_HOST (1)".
+ * A static overlay (a burnt-in clock, a logo, a bonnet) is best masked out together with a margin of about 16 px: the tracker's 21 x 21
+ * window reaches that far from a corner on the first pyramid level. */
+VSTAB_API vstab_status vstab_set_detection_mask(vstab_handle *h, const void *mask, size_t pitch_mask, int mem);
 /* vstab_pull_frame / vstab_pull_frame_nv12_planar with kept edges ("Keep edges" above): the next frame, warped by vstab_warp_nv12_keep with
  * the caller's previous output prev (prev_y / prev_uv) -- a second buffer (a ring of two outputs), or dst itself (in place).  A frame that
  * carries a read-out rotation is warped per row, as a plain INTER_LINEAR pull warps it.  Keep pulls and plain pulls may alternate frame by

@@ -138,6 +138,15 @@ class FrameSourceWarp : public FrameSource {
             throw (int)st;
         }
     }
+    // goodFeaturesToTrack's mask for find_corners (FrameSourceWarp.cpp:228-240 passes none): bytes of the input's size, non-zero = "a corner
+    // may be reported here", in host (VSTAB_MEM_HOST) or device memory; before the first pull_frame -- vstab_set_detection_mask
+    void set_detection_mask(const void *mask, size_t pitch, int mem = VSTAB_MEM_HOST) {
+        const vstab_status st = vstab_set_detection_mask(m_handle, mask, pitch, mem);
+        if (st != VSTAB_OK) {
+            std::fprintf(stderr, "FrameSourceWarp: %s\n", vstab_last_error());
+            throw (int)st;
+        }
+    }
 
     BGRFrame pull_frame() override {  // FrameSourceWarp.cpp:452-476
         if (!m_out) throw -1;

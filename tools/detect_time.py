@@ -1,5 +1,10 @@
 """Run the corner detectors at 4K and 1080p a few times (for rocprofv3 --kernel-trace --stats).
-usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only]   -- LIB: another build of the library (tools/devlib.py), for parent / branch runs"""
+usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overlay,roi}] [--alternations K]
+   LIB: another build of the library (tools/devlib.py), for parent / branch runs
+   --mask: K alternations of N unmasked detections (k_corners_fused) and N detections under the mask (k_corners_fused_masked,
+           vstab_good_features_mask) per size, in one process: `full` is non-zero everywhere, `overlay` is zero on a box over 9 % of the frame
+           grown by 16 px (the lower left), `roi` leaves a window of a tenth of the fused detector's tiles.
+   tools/kernel_medians.py <dir> turns the kernel trace into medians per kernel and grid."""
 import argparse, hashlib, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
@@ -12,14 +17,44 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--lib", default=None)
 ap.add_argument("--n", type=int, default=20)
 ap.add_argument("--fused-only", action="store_true")
+ap.add_argument("--mask", choices=("full", "overlay", "roi"), default=None)
+ap.add_argument("--alternations", type=int, default=3)
 a = ap.parse_args()
 if a.lib:
     import devlib
     vs = devlib.load(a.lib)
 else:
     vs = importlib.import_module("video-annotator_amd")
+
+
+def make_mask(kind, w, h):
+    m = np.full((h, w), 255, np.uint8)
+    if kind == "overlay":     # the box of the 640 x 360 clip (rows 250..339, columns 20..259: 9.4 % of the frame) scaled, grown by 16 px
+        s = w / 640.0
+        m[max(int(250 * s) - 16, 0):min(int(340 * s) + 16, h), max(int(20 * s) - 16, 0):min(int(260 * s) + 16, w)] = 0
+    if kind == "roi":         # a centred window of sqrt(1/10) of either side: a tenth of the 64 x 31 tiles
+        m[:] = 0
+        rw, rh = int(w * 0.1 ** 0.5), int(h * 0.1 ** 0.5)
+        m[(h - rh) // 2:(h - rh) // 2 + rh, (w - rw) // 2:(w - rw) // 2 + rw] = 255
+    return m
+
+
 for w, h in ((3840, 2160), (1920, 1080)):
     g = torch.from_numpy(np.ascontiguousarray(synth.luma(41, w, h, rects=400))).cuda()
+    if a.mask:
+        mh = make_mask(a.mask, w, h)
+        m = torch.from_numpy(mh).cuda()
+        tiles = [(ty, tx) for ty in range(0, h, 31) for tx in range(0, w, 64)]
+        live = sum(bool(mh[max(ty - 1, 0):ty + 32, max(tx - 1, 0):tx + 65].any()) for ty, tx in tiles)
+        for _ in range(a.alternations):
+            for masked in (False, True):
+                info = {}
+                for _ in range(a.n):
+                    c = vs.good_features_mask(g, m, detector=vs.DETECTOR_FUSED, info=info) if masked else vs.good_features(g, detector=vs.DETECTOR_AUTO, info=info)
+                torch.cuda.synchronize()
+        print(w, h, "mask", a.mask, "masked-in %.1f %%" % (100.0 * (mh != 0).mean()), "tiles that do not return early", live, "of", len(tiles),
+              "detector", info["detector_used"], "corners", len(c), hashlib.sha1(np.ascontiguousarray(c).tobytes()).hexdigest()[:12], flush=True)
+        continue
     for det in (vs.DETECTOR_AUTO,) if a.fused_only else (vs.DETECTOR_AUTO, vs.DETECTOR_TWO_PASS):
         info = {}
         for _ in range(a.n):

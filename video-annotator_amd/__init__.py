@@ -190,6 +190,8 @@ SIGNATURES = {
     "vstab_estimate_rotation_pinhole": (_i, [_fp, _fp, _i, _dp, _dp, _dp, _u64, _dp, _ip]),
     "vstab_create_map_pinhole": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _vp]),
     "vstab_warp_nv12_pinhole": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_good_features_mask": (_i, [_vp, _sz, _i, _i, _vp, _sz, _i, _d, _d, _i, _fp, _ip, _ip, _vp]),
+    "vstab_set_detection_mask": (_i, [_vp, _vp, _sz, _i]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -204,6 +206,8 @@ _L.vstabx_warps_from_cache.argtypes = [_vp]
 # test hooks of the corner detector (corners_fused and Stabilizer.detector_counters below)
 _L.vstabx_corners_fused.restype = _i
 _L.vstabx_corners_fused.argtypes = [_vp, _sz, _i, _i, _d, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _vp]
+_L.vstabx_corners_fused_mask.restype = _i
+_L.vstabx_corners_fused_mask.argtypes = [_vp, _sz, _i, _i, _vp, _sz, _d, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _vp]
 _L.vstabx_detector_counters.restype = _i
 _L.vstabx_detector_counters.argtypes = [_vp, _c.POINTER(_c.c_long)]
 
@@ -929,6 +933,21 @@ def good_features(gray, max_corners=200, quality=0.01, min_distance=30.0, detect
     return xy[:n.value].copy()
 
 
+def good_features_mask(gray, mask, max_corners=200, quality=0.01, min_distance=30.0, detector=DETECTOR_AUTO, info=None):
+    """vstab_good_features_mask: good_features under a detection mask, an (h, w) uint8 device tensor or view (any pitch and base address;
+    non-zero = "a corner may be reported here"), or None for no mask.  detector: DETECTOR_AUTO, DETECTOR_FUSED or DETECTOR_TWO_PASS;
+    info["detector_used"] (if a dict is given) says which kernel path produced the corners."""
+    h, w = gray.shape
+    xy = np.zeros((max_corners, 2), np.float32)
+    n, used = _c.c_int(), _c.c_int()
+    _check(_L.vstab_good_features_mask(gray.data_ptr(), gray.stride(0), w, h, None if mask is None else mask.data_ptr(), 0 if mask is None else mask.stride(0),
+                                       max_corners, quality, min_distance, detector, _fptr(xy), _c.byref(n), _c.byref(used), _stream()),
+           "vstab_good_features_mask")
+    if info is not None:
+        info["detector_used"] = used.value
+    return xy[:n.value].copy()
+
+
 CORNERS_FUSED_FILL = 0xA5A5A5A5A5A5A5A5  # what vstabx_corners_fused fills its key buffer with before the kernels run
 
 
@@ -948,6 +967,25 @@ def corners_fused(gray, quality=0.01, cap=1 << 18, canary=64, w=None, h=None, st
     _check(_L.vstabx_corners_fused(gray.data_ptr(), gray.stride(0), int(w), int(h), float(quality), cap & 0xFFFFFFFF, canary & 0xFFFFFFFF,
                                    keys.ctypes.data_as(_c.POINTER(_u64)), counts.ctypes.data_as(_c.POINTER(_c.c_uint)),
                                    tiles.ctypes.data_as(_c.POINTER(_c.c_uint)), _stream() if stream is None else stream), "vstabx_corners_fused")
+    return keys, int(counts[0]), int(counts[1]), tiles
+
+
+def corners_fused_mask(gray, mask, quality=0.01, cap=1 << 18, canary=64, w=None, h=None, stream=None, mask_ptr=None, mask_pitch=None):
+    """Test hook vstabx_corners_fused_mask: corners_fused under the detection mask `mask`, an (h, w) uint8 device tensor or view; the same
+    outputs.  mask_ptr / mask_pitch (for a test of the refusals, which needs no device) stand in for the tensor's."""
+    h = gray.shape[0] if h is None else h
+    w = gray.shape[1] if w is None else w
+    cap, canary = int(cap), int(canary)
+    ok = 0 < cap <= 1 << 24 and 0 < canary <= 1 << 16
+    keys = np.zeros(cap + canary if ok else 1, np.uint64)
+    counts = np.zeros(2, np.uint32)
+    tx, ty = max(1, (int(w) + 63) // 64), max(1, (int(h) + 30) // 31)
+    tiles = np.zeros((ty, tx) if tx * ty < 1 << 21 else (1, 1), np.uint32)
+    mp = mask.data_ptr() if mask_ptr is None else mask_ptr
+    mpitch = mask.stride(0) if mask_pitch is None else mask_pitch
+    _check(_L.vstabx_corners_fused_mask(gray.data_ptr(), gray.stride(0), int(w), int(h), mp, mpitch, float(quality), cap & 0xFFFFFFFF, canary & 0xFFFFFFFF,
+                                        keys.ctypes.data_as(_c.POINTER(_u64)), counts.ctypes.data_as(_c.POINTER(_c.c_uint)),
+                                        tiles.ctypes.data_as(_c.POINTER(_c.c_uint)), _stream() if stream is None else stream), "vstabx_corners_fused_mask")
     return keys, int(counts[0]), int(counts[1]), tiles
 
 
@@ -1099,8 +1137,9 @@ class Stabilizer:
     source for `total` pulls) or a Python iterable of such tensors (python callback source)."""
 
     def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, calibration=None,
-                 calibration_ex=None, pinhole=None, **cfg_kw):
-        """border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
+                 calibration_ex=None, pinhole=None, detection_mask=None, **cfg_kw):
+        """detection_mask: set_detection_mask right after create (a device tensor or a numpy array of the luma plane's size).
+        border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
         calibration: (K, D) for set_input_calibration right after create, applied after border_mode (K None keeps the camera from in_dfov).
         calibration_ex: the same through set_input_calibration_ex (every resampler and border mode).
         pinhole: (K, D) for set_input_pinhole right after create: a rectilinear input lens with D = (k1, k2, p1, p2, k3) (K None as above).
@@ -1171,6 +1210,20 @@ class Stabilizer:
             self.set_input_calibration_ex(*calibration_ex)
         if pinhole is not None:
             self.set_input_pinhole(*pinhole)
+        if detection_mask is not None:
+            self.set_detection_mask(detection_mask)
+
+    def set_detection_mask(self, mask):
+        """vstab_set_detection_mask: goodFeaturesToTrack's mask for every detection of this handle, before the first pull.  mask: (h, w) uint8,
+        non-zero = "a corner may be reported here" -- a device tensor or view (VSTAB_MEM_DEVICE), a numpy array (VSTAB_MEM_HOST; any row stride),
+        or None to remove the mask.  The handle keeps a copy."""
+        if mask is None:
+            _check(_L.vstab_set_detection_mask(self._h, None, 0, 0), "vstab_set_detection_mask")
+        elif isinstance(mask, np.ndarray):
+            assert mask.dtype == np.uint8 and mask.ndim == 2 and mask.strides[1] == 1
+            _check(_L.vstab_set_detection_mask(self._h, mask.ctypes.data, mask.strides[0], 1), "vstab_set_detection_mask")
+        else:
+            _check(_L.vstab_set_detection_mask(self._h, mask.data_ptr(), mask.stride(0), 0), "vstab_set_detection_mask")
 
     def _calibrate(self, fn, K, D):
         Kc = None if K is None else np.ascontiguousarray(K, np.float64).reshape(9)

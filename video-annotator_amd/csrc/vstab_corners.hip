@@ -1,5 +1,6 @@
 // vstab_corners.hip -- Shi-Tomasi corner response + non-maximum suppression + compaction for gfx950: the one-pass detector
-// (k_corners_fused, k_filter_keys) and the two-pass one behind it (k_min_eig, k_corner_candidates).  Replaces the OpenCV call at
+// (k_corners_fused, k_filter_keys), the two-pass one behind it (k_min_eig, k_corner_candidates) and their forms under a detection mask
+// (k_corners_fused_masked; k_masked_max, k_corner_candidates_masked).  Replaces the OpenCV call at
 // FrameSourceWarp.cpp:230 (goodFeaturesToTrack).  Compiled with -ffp-contract=off: float results are bit-reproducible.
 #include <climits>
 
@@ -182,9 +183,12 @@ __device__ __forceinline__ float ubyte_f32(uint32_t v) {
 // row maximum.  DENSE = false: survivors are appended to the tile's slots, one LDS atomic per wave for the rows' survivors together
 // (*bcount counts all of them, also those past the last slot); DENSE = true: every pixel of the tile is written, the
 // eigenvalue for a survivor and -inf otherwise.  INTERIOR: every pixel of the tile is an interior pixel of the image.
-template <bool DENSE, bool INTERIOR>
+// MASKED (k_corners_fused_masked): a survivor also has a non-zero mask byte; `mtile` holds the tile's mask bytes in the layout of the
+// source tile (pixel (ty, tx) of the tile <-> mtile[ty + 3][tx + 4]).  Its neighbours compete in the maximum whatever their mask bytes say.
+template <bool DENSE, bool INTERIOR, bool MASKED = false>
 __device__ __forceinline__ void cf_nonmax(const float (&es)[CF_EH][CF_EP], int tid, int ox, int oy, int w, int h, float thr_lb,
-                                          unsigned long long *__restrict__ my_slots, unsigned int *bcount, float *__restrict__ dense) {
+                                          unsigned long long *__restrict__ my_slots, unsigned int *bcount, float *__restrict__ dense,
+                                          const uint8_t (*mtile)[CF_SW] = nullptr) {
     const int tx = tid & 63, r0 = __builtin_amdgcn_readfirstlane(tid >> 6) * 8;  // the rows are the wave's: scalar
     const int x = ox + tx;
     const bool x_in = INTERIOR || (x >= 1 && x < w - 1);
@@ -205,6 +209,7 @@ __device__ __forceinline__ void cf_nonmax(const float (&es)[CF_EH][CF_EP], int t
         const float m = fmaxf(fmaxf(rm0, rm1), rm2);
         const int y = oy + ty;
         cand[r] = row && x_in && (INTERIOR || (y >= 1 && y < h - 1)) && c1 > thr_lb && c1 == m;
+        if (MASKED) cand[r] = cand[r] && mtile[ty + 3][tx + 4] != 0;  // (ty + 3 <= 34 < CF_SH also for the last wave's eighth row)
         if (DENSE) {
             if (row) dense[ty * CF_TW + tx] = cand[r] ? c1 : -__builtin_inff();
         } else {
@@ -229,8 +234,11 @@ __device__ __forceinline__ void cf_nonmax(const float (&es)[CF_EH][CF_EP], int t
 }
 
 // load: the source tile, dword e of it <-> row e / 18, bytes 4 (e % 18) ..; a thread's three loads are in flight together
+// (MASKED, here and in cf_store, cf_products and cf_interior, changes nothing in the function: it gives k_corners_fused_masked instantiations of
+//  its own.  An instantiation that both kernels inlined would be cloned where k_corners_fused alone has it moved into its only caller, and
+//  the optimiser's choices behind that differ: the unmasked kernel's instructions stay exactly what they were this way.)
 constexpr int CF_LOADS = (CF_SH * (CF_SW / 4) + 255) / 256;
-template <bool INTERIOR>
+template <bool INTERIOR, bool MASKED = false>
 __device__ __forceinline__ void cf_load(uint32_t (&v)[CF_LOADS], const uint8_t *__restrict__ src, uint32_t pitch, int w, int h, int ox, int oy, bool vec_ok,
                                         int tid) {
 #pragma unroll
@@ -243,14 +251,53 @@ __device__ __forceinline__ void cf_load(uint32_t (&v)[CF_LOADS], const uint8_t *
         else v[k] = load4_reflect(src, pitch, w, h, ox - 4 + 4 * rd, oy - 3 + ry, vec_ok);
     }
 }
+template <bool MASKED = false>
 __device__ __forceinline__ void cf_store(uint8_t (&tile)[CF_SH][CF_SW], const uint32_t (&v)[CF_LOADS], int tid) {
 #pragma unroll
     for (int k = 0; k < CF_LOADS; k++)
         if (tid + 256 * k < CF_SH * (CF_SW / 4)) reinterpret_cast<uint32_t *>(&tile[0][0])[tid + 256 * k] = v[k];
 }
 
-// prod: product entry (r, q) <-> image (oy - 2 + r, ox - 2 + q) <-> tile[r + 1][q + 2]; a thread owns q = 4c .. 4c+3, r = 5g .. 5g+4
+// The mask bytes of the tile in the layout and with the addressing of cf_load: dwords where the mask's rows are dword aligned, bytes
+// otherwise -- but nothing is mirrored: a byte outside the image is never read and counts as zero ("masked out").  INTERIOR says that
+// the 72 x 38 bytes lie inside the image (the mask has the image's size), vec_ok that the MASK's base and pitch are 4-byte aligned.
 template <bool INTERIOR>
+__device__ __forceinline__ void cf_load_mask(uint32_t (&v)[CF_LOADS], const uint8_t *__restrict__ mask, uint32_t pitch, int w, int h, int ox, int oy, bool vec_ok,
+                                             int tid) {
+#pragma unroll
+    for (int k = 0; k < CF_LOADS; k++) {
+        const int e = tid + 256 * k;
+        const int ry = __mul24(e, 3641) >> 16, rd = e - ry * (CF_SW / 4);
+        v[k] = 0;
+        if (e >= CF_SH * (CF_SW / 4)) continue;
+        const int gx = ox - 4 + 4 * rd, gy = oy - 3 + ry;
+        if (!INTERIOR && (gy < 0 || gy >= h)) continue;
+        const uint8_t *row = mask + (uint32_t)gy * pitch;
+        if (vec_ok && (INTERIOR || (gx >= 0 && gx + 4 <= w))) {
+            v[k] = *reinterpret_cast<const uint32_t *>(row + gx);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (INTERIOR || (gx + i >= 0 && gx + i < w)) v[k] |= (uint32_t)row[gx + i] << (8 * i);
+        }
+    }
+}
+// whether one of the thread's mask dwords holds a non-zero byte of the 66 x 33 pixels the tile takes its maximum over: rows 2 .. 34 of
+// the 38, bytes 3 .. 68 of the 72 (the last byte of the first dword, the first byte of the last, every byte of those between)
+__device__ __forceinline__ bool cf_mask_any(const uint32_t (&v)[CF_LOADS], int tid) {
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < CF_LOADS; k++) {
+        const int e = tid + 256 * k;
+        const int ry = __mul24(e, 3641) >> 16, rd = e - ry * (CF_SW / 4);
+        const uint32_t sel = rd == 0 ? 0xff000000u : rd == CF_SW / 4 - 1 ? 0x000000ffu : 0xffffffffu;
+        any = any || (ry >= 2 && ry <= CF_EH + 1 && (v[k] & sel) != 0);  // (a dword past the tile is zero: cf_load_mask)
+    }
+    return any;
+}
+
+// prod: product entry (r, q) <-> image (oy - 2 + r, ox - 2 + q) <-> tile[r + 1][q + 2]; a thread owns q = 4c .. 4c+3, r = 5g .. 5g+4
+template <bool INTERIOR, bool MASKED = false>
 __device__ __forceinline__ void cf_products(const uint8_t (&tile)[CF_SH][CF_SW], float (&prod)[3][CF_DH][CF_DP], int ox, int oy, int w, int h, int tid) {
     if (tid >= CF_PC * CF_PG) return;
     const float scale = (float)(1.0 / (4.0 * 3.0 * 255.0));
@@ -301,8 +348,11 @@ __device__ __forceinline__ void cf_sum3of5(double p0, double p1, double p2, doub
 // box + eig: eigenvalue entry (ey, ex) <-> image (oy - 1 + ey, ox - 1 + ex) <-> product rows ey .. ey+2, columns ex .. ex+2; a thread owns
 // ex = 3bx .. 3bx+2, ey = 3by .. 3by+2.  `es` is the storage of prod[0]: every thread has its box sums in registers before any
 // eigenvalue is stored.  Returns the thread's maximum over the in-image eigenvalues (int-bit order, as k_min_eig).
-template <bool INTERIOR>
-__device__ __forceinline__ int cf_eigenvalues(const float (&prod)[3][CF_DH][CF_DP], float (&es)[CF_EH][CF_EP], int ox, int oy, int w, int h, int tid) {
+// MASKED: the maximum runs over the eigenvalues with a non-zero mask byte instead (entry (ey, ex) <-> mtile[ey + 2][ex + 3]; a byte outside
+// the image is zero there).  The mask bytes must be in `mtile` before the call: the barrier in here orders them before their readers.
+template <bool INTERIOR, bool MASKED = false>
+__device__ __forceinline__ int cf_eigenvalues(const float (&prod)[3][CF_DH][CF_DP], float (&es)[CF_EH][CF_EP], int ox, int oy, int w, int h, int tid,
+                                              const uint8_t (*mtile)[CF_SW] = nullptr) {
     const bool active = tid < CF_BX * CF_BY;
     const int t = min(tid, CF_BX * CF_BY - 1);  // the 14 threads without a block add up the last one's sums and store nothing
     const int by = __mul24(t, 2979) >> 16, bx = t - by * CF_BX;
@@ -338,23 +388,47 @@ __device__ __forceinline__ int cf_eigenvalues(const float (&prod)[3][CF_DH][CF_D
                 const float ev = (a + cc) - sqrtf((a - cc) * (a - cc) + b * b);
                 es[3 * by + e][3 * bx + i] = ev;
                 const int gx = ox - 1 + 3 * bx + i, gy = oy - 1 + 3 * by + e;
-                if (INTERIOR || (gx >= 0 && gx < w && gy >= 0 && gy < h)) best = max(best, __float_as_int(ev));
+                if (MASKED) {
+                    if (mtile[3 * by + e + 2][3 * bx + i + 3] != 0) best = max(best, __float_as_int(ev));
+                } else if (INTERIOR || (gx >= 0 && gx < w && gy >= 0 && gy < h)) best = max(best, __float_as_int(ev));
             }
     }
     return best;
 }
 
-template <bool INTERIOR>
+// MASKED (k_corners_fused_masked; `mask`: a w x h plane of bytes, non-zero = "a corner may be reported here"):
+//   - a tile without a non-zero mask byte among the in-image pixels of its 66 x 33 eigenvalues writes a count of 0 and returns before it
+//     loads the source: it publishes no maximum and no key.  The test is one value for the workgroup (a flag per wave in LDS behind one barrier), so every barrier
+//     below is reached by all of its threads or by none;
+//   - the tile maximum, and with it the published frame maximum, runs over the eigenvalues with a non-zero mask byte;
+//   - a survivor has a non-zero mask byte (cf_nonmax), while the 3 x 3 maximum it is compared with knows no mask.
+// The mask bytes wait in three registers while the source tile is in use and take its place in LDS behind the products.
+template <bool INTERIOR, bool MASKED = false>
 __device__ __forceinline__ void cf_tile(uint8_t (&tile)[CF_SH][CF_SW], float (&prod)[3][CF_DH][CF_DP], int &bmax, unsigned int &bcount, unsigned int &bseen,
                                         const uint8_t *__restrict__ src, uint32_t pitch, int w, int h, double quality, unsigned int *__restrict__ max_key,
-                                        unsigned long long *__restrict__ slots, unsigned int *__restrict__ tile_counts, float *__restrict__ spill, bool vec_ok) {
+                                        unsigned long long *__restrict__ slots, unsigned int *__restrict__ tile_counts, float *__restrict__ spill, bool vec_ok,
+                                        const uint8_t *__restrict__ mask = nullptr, uint32_t mpitch = 0, bool mvec_ok = false) {
     float (&es)[CF_EH][CF_EP] = *reinterpret_cast<float (*)[CF_EH][CF_EP]>(&prod[0][0][0]);
     const int tid = threadIdx.x;
     const int ox = blockIdx.x * CF_TW, oy = blockIdx.y * CF_TH;
+    uint32_t mv[CF_LOADS];
+    if (MASKED) {
+        cf_load_mask<INTERIOR>(mv, mask, mpitch, w, h, ox, oy, mvec_ok, tid);
+        // one flag per wave in LDS nobody uses yet (prod is first written behind the barrier that follows cf_store), one barrier, the
+        // same answer in every thread
+        uint32_t *flags = reinterpret_cast<uint32_t *>(&prod[2][0][0]);
+        const bool mine = __builtin_amdgcn_ballot_w64(cf_mask_any(mv, tid)) != 0;
+        if ((tid & 63) == 0) flags[tid >> 6] = mine;
+        __syncthreads();
+        if ((flags[0] | flags[1] | flags[2] | flags[3]) == 0) {
+            if (tid == 0) tile_counts[blockIdx.y * gridDim.x + blockIdx.x] = 0;
+            return;
+        }
+    }
     uint32_t v[CF_LOADS];
-    cf_load<INTERIOR>(v, src, pitch, w, h, ox, oy, vec_ok, tid);
+    cf_load<INTERIOR, MASKED>(v, src, pitch, w, h, ox, oy, vec_ok, tid);
     if (tid == 0) bmax = INT_MIN, bcount = 0;
-    cf_store(tile, v, tid);
+    cf_store<MASKED>(tile, v, tid);
     // frame maximum published so far (biased bits): a lower bound of the final one.  Device-scope load: the atomics
     // of other XCDs do not pass through this XCD's L2.  Every workgroup reads this one address, and the memory side serves
     // such reads one after the other: ONE lane asks -- in the last wave, which has no part in the products, and behind
@@ -363,9 +437,10 @@ __device__ __forceinline__ void cf_tile(uint8_t (&tile)[CF_SH][CF_SW], float (&p
     unsigned int seen = 0;
     if (tid == 255) seen = __hip_atomic_load(max_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    cf_products<INTERIOR>(tile, prod, ox, oy, w, h, tid);
+    cf_products<INTERIOR, MASKED>(tile, prod, ox, oy, w, h, tid);
     __syncthreads();
-    int best = cf_eigenvalues<INTERIOR>(prod, es, ox, oy, w, h, tid);
+    if (MASKED) cf_store<MASKED>(tile, mv, tid);  // the source bytes are dead; cf_eigenvalues' barrier stands between this and the first reader
+    int best = cf_eigenvalues<INTERIOR, MASKED>(prod, es, ox, oy, w, h, tid, tile);
     // tile maximum (same int-bit order as k_min_eig)
     best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x111, 0xf, 0xf, false));
     best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x112, 0xf, 0xf, false));
@@ -385,16 +460,17 @@ __device__ __forceinline__ void cf_tile(uint8_t (&tile)[CF_SH][CF_SW], float (&p
     const int lb_bits = max(tile_max, (int)(seen ^ 0x80000000u));
     const float thr_lb = lb_bits >= 0 ? (float)((double)__int_as_float(lb_bits) * quality) : -__builtin_inff();
     const int tile_idx = blockIdx.y * gridDim.x + blockIdx.x;
-    cf_nonmax<false, INTERIOR>(es, tid, ox, oy, w, h, thr_lb, slots + (size_t)tile_idx * CF_SLOTS, &bcount, nullptr);
+    cf_nonmax<false, INTERIOR, MASKED>(es, tid, ox, oy, w, h, thr_lb, slots + (size_t)tile_idx * CF_SLOTS, &bcount, nullptr, tile);
     __syncthreads();
     const unsigned int n = bcount;
     if (tid == 0) tile_counts[tile_idx] = n;
     // A tile with more survivors than slots (an eigenvalue plateau: a smooth ramp, a periodic texture) leaves them as a
     // dense 64 x 31 map instead (-inf = not a survivor); k_filter_keys scans that with the final threshold.
-    if (n > CF_SLOTS) cf_nonmax<true, INTERIOR>(es, tid, ox, oy, w, h, thr_lb, nullptr, nullptr, spill + (size_t)tile_idx * (CF_TW * CF_TH));
+    if (n > CF_SLOTS) cf_nonmax<true, INTERIOR, MASKED>(es, tid, ox, oy, w, h, thr_lb, nullptr, nullptr, spill + (size_t)tile_idx * (CF_TW * CF_TH), tile);
 }
 
 // the tile's 72 x 38 source bytes at image (oy - 3 .., ox - 4 ..) lie inside the image, and its rows are dword aligned
+template <bool MASKED = false>
 __device__ __forceinline__ bool cf_interior(int ox, int oy, int w, int h, int vec_ok) {
     return vec_ok && ox >= 4 && ox - 4 + CF_SW <= w && oy >= 3 && oy - 3 + CF_SH <= h;
 }
@@ -410,6 +486,78 @@ __global__ void __launch_bounds__(256) k_corners_fused(const uint8_t *__restrict
         cf_tile<true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true);
     else
         cf_tile<false>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0);
+}
+
+// k_corners_fused_masked -- k_corners_fused under a detection mask (goodFeaturesToTrack's `mask`; vstab.h, "Detection mask"): the same
+// phases over the same LDS, cf_tile<., MASKED = true>.  The frame maximum it publishes is the maximum over the masked-in pixels, so
+// quality * max(own, seen) is still a lower bound of the final threshold and k_filter_keys serves it unchanged.
+// (amdgpu_waves_per_eu: left alone the compiler takes 130 VGPRs here -- three workgroups per CU where k_corners_fused has four; asked for
+//  four waves per SIMD it fits 128 without a spill.  DESIGN.md section 24 has the table.)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) k_corners_fused_masked(const uint8_t *__restrict__ src, size_t pitch, int w, int h, double quality,
+                                                              unsigned int *__restrict__ max_key, unsigned long long *__restrict__ slots,
+                                                              unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok,
+                                                              const uint8_t *__restrict__ mask, size_t mpitch, int mvec_ok) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];  // the source bytes; behind the products, the mask bytes
+    __shared__ __attribute__((aligned(16))) float prod[3][CF_DH][CF_DP];
+    __shared__ int bmax;
+    __shared__ unsigned int bcount, bseen;
+    if (cf_interior<true>(blockIdx.x * CF_TW, blockIdx.y * CF_TH, w, h, vec_ok))
+        cf_tile<true, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true, mask, (uint32_t)mpitch,
+                            mvec_ok != 0);
+    else
+        cf_tile<false, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0, mask,
+                             (uint32_t)mpitch, mvec_ok != 0);
+}
+
+// The two-pass detector under a mask: k_min_eig as it is, then
+// k_masked_max -- minMaxLoc(eig, ., &maxVal, ., ., mask): the maximum of the eigenvalue map over the pixels with a non-zero mask byte, in
+// the int-bit order and into a word initialised as k_min_eig's (launch_masked_max).  64 x 16 pixels per workgroup, a wave per 4 rows;
+// reduced inside the wave (DPP), one LDS atomic per wave, one global atomic per workgroup.
+__global__ void __launch_bounds__(256) k_masked_max(const float *__restrict__ eig, int w, int h, const uint8_t *__restrict__ mask, size_t mpitch,
+                                                    int *__restrict__ max_bits) {
+    __shared__ int bmax;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) bmax = INT_MIN;
+    __syncthreads();
+    const int x = blockIdx.x * 64 + lane;
+    int best = INT_MIN;
+    if (x < w) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int y = blockIdx.y * 16 + wave * 4 + r;
+            if (y < h && mask[(size_t)y * mpitch + x] != 0) best = max(best, __float_as_int(eig[(size_t)y * w + x]));
+        }
+    }
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x111, 0xf, 0xf, false));
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x112, 0xf, 0xf, false));
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x114, 0xf, 0xf, false));
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x118, 0xf, 0xf, false));
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x142, 0xa, 0xf, false));
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x143, 0xc, 0xf, false));
+    if (lane == 63) atomicMax(&bmax, best);
+    __syncthreads();
+    if (tid == 0) atomicMax(max_bits, bmax);
+}
+
+// k_corner_candidates_masked -- k_corner_candidates plus the gate: a candidate has a non-zero mask byte.  The threshold (max_bits: the
+// masked maximum) and the 3 x 3 maximum test run over every pixel, masked out or not.
+__global__ void __launch_bounds__(256) k_corner_candidates_masked(const float *__restrict__ eig, int w, int h, const int *__restrict__ max_bits, double quality,
+                                                                  unsigned long long *__restrict__ keys, unsigned int *__restrict__ count, unsigned int cap,
+                                                                  const uint8_t *__restrict__ mask, size_t mpitch) {
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x < 1 || y < 1 || x >= w - 1 || y >= h - 1) return;
+    if (mask[(size_t)y * mpitch + x] == 0) return;
+    const float thr = (float)((double)__int_as_float(*max_bits) * quality);
+    const float *p = eig + (size_t)y * w + x;
+    const float v = p[0];
+    if (!(v > thr)) return;
+    float m = v;
+    m = fmaxf(m, p[-w - 1]), m = fmaxf(m, p[-w]), m = fmaxf(m, p[-w + 1]);
+    m = fmaxf(m, p[-1]), m = fmaxf(m, p[1]);
+    m = fmaxf(m, p[w - 1]), m = fmaxf(m, p[w]), m = fmaxf(m, p[w + 1]);
+    if (v != m) return;
+    const unsigned int slot = atomicAdd(count, 1u);
+    if (slot < cap) keys[slot] = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned int)(y * w + x);
 }
 
 // k_filter_keys -- the final threshold quality * max(frame) over the survivors of k_corners_fused.  A workgroup
@@ -488,24 +636,34 @@ vstab_status launch_min_eig(const uint8_t *src, size_t pitch, int w, int h, floa
     return VSTAB_OK;
 }
 
-vstab_status launch_corner_candidates(const float *eig, int w, int h, const int *max_bits, double quality,
-                                      unsigned long long *keys, unsigned int *count, unsigned int cap,
-                                      hipStream_t s) {
-    VSTAB_HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned int), s));
-    dim3 grid(div_up(w, 64), div_up(h, 4));
-    hipLaunchKernelGGL(k_corner_candidates, grid, dim3(64, 4), 0, s, eig, w, h, max_bits, quality, keys, count, cap);
+// the masked maximum of an eigenvalue map (behind launch_min_eig, whose max_bits holds the maximum of the whole frame) into *masked_max_bits
+vstab_status launch_masked_max(const float *eig, int w, int h, const uint8_t *mask, size_t mpitch, int *masked_max_bits, hipStream_t s) {
+    VSTAB_HIP_TRY(hipMemsetAsync(masked_max_bits, 0x80, sizeof(int), s));  // as launch_min_eig
+    hipLaunchKernelGGL(k_masked_max, dim3(div_up(w, 64), div_up(h, 16)), dim3(256), 0, s, eig, w, h, mask, mpitch, masked_max_bits);
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }
 
-// Fused detector.  small: 8 dwords of device memory {biased maximum bits, -, -, -, keys kept, tiles that spilled, -, -};
+vstab_status launch_corner_candidates(const float *eig, int w, int h, const int *max_bits, double quality,
+                                      unsigned long long *keys, unsigned int *count, unsigned int cap,
+                                      hipStream_t s, const uint8_t *mask, size_t mpitch) {
+    VSTAB_HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned int), s));
+    dim3 grid(div_up(w, 64), div_up(h, 4));
+    if (mask) hipLaunchKernelGGL(k_corner_candidates_masked, grid, dim3(64, 4), 0, s, eig, w, h, max_bits, quality, keys, count, cap, mask, mpitch);
+    else hipLaunchKernelGGL(k_corner_candidates, grid, dim3(64, 4), 0, s, eig, w, h, max_bits, quality, keys, count, cap);
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
+// Fused detector (mask, optional: a w x h plane of bytes of pitch mpitch with (uint64_t)mpitch * h < 2^32; k_corners_fused_masked takes
+// the place of k_corners_fused then, everything else is the same).  small: 8 dwords of device memory {biased maximum bits, -, -, -, keys kept, tiles that spilled, -, -};
 // scratch: corners_fused_scratch_bytes(w, h) (per tile: 256 key slots, a count, and room for a dense 64 x 31 map that
 // only a tile with more survivors than slots writes).  On return (stream order) keys holds min(small[4], cap) keys; the
 // result is complete iff small[4] <= cap.
 size_t corners_fused_scratch_bytes(int w, int h) { return CornersFusedScratch(w, h).bytes; }
 
 vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h, double quality, void *scratch, unsigned long long *keys,
-                                  unsigned int cap, unsigned int *small, hipStream_t s) {
+                                  unsigned int cap, unsigned int *small, hipStream_t s, const uint8_t *mask, size_t mpitch) {
     VSTAB_HIP_TRY(hipMemsetAsync(small, 0, 8 * sizeof(unsigned int), s));
     const int vec_ok = reinterpret_cast<uintptr_t>(src) % 4 == 0 && pitch % 4 == 0;
     const CornersFusedScratch lay(w, h);
@@ -513,7 +671,13 @@ vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h
     unsigned long long *slots = reinterpret_cast<unsigned long long *>(base + lay.slots_off);
     float *spill = reinterpret_cast<float *>(base + lay.spill_off);
     unsigned int *tile_counts = reinterpret_cast<unsigned int *>(base + lay.counts_off);
-    hipLaunchKernelGGL(k_corners_fused, dim3(lay.tiles_x, lay.tiles_y), dim3(256), 0, s, src, pitch, w, h, quality, small, slots, tile_counts, spill, vec_ok);
+    if (mask) {
+        const int mvec_ok = reinterpret_cast<uintptr_t>(mask) % 4 == 0 && mpitch % 4 == 0;
+        hipLaunchKernelGGL(k_corners_fused_masked, dim3(lay.tiles_x, lay.tiles_y), dim3(256), 0, s, src, pitch, w, h, quality, small, slots, tile_counts, spill,
+                           vec_ok, mask, mpitch, mvec_ok);
+    } else {
+        hipLaunchKernelGGL(k_corners_fused, dim3(lay.tiles_x, lay.tiles_y), dim3(256), 0, s, src, pitch, w, h, quality, small, slots, tile_counts, spill, vec_ok);
+    }
     hipLaunchKernelGGL(k_filter_keys, dim3(div_up(lay.tiles, FK_TILES)), dim3(256), 0, s, slots, tile_counts, spill, lay.tiles, lay.tiles_x, w, small, quality, keys,
                        small + 4, cap);
     VSTAB_HIP_TRY(hipGetLastError());
@@ -525,6 +689,7 @@ vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h
 vstab_status preload_corner_kernels() {
     hipFuncAttributes at;
     VSTAB_HIP_TRY(hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_corners_fused)));
+    // (k_corners_fused_masked, k_masked_max and k_corner_candidates_masked are kernels of this unit: the same code object, loaded with it)
     return VSTAB_OK;
 }
 

@@ -687,6 +687,18 @@ vstab_status vstab_set_input_calibration(vstab_handle *h, const double K[9], con
     return set_input_calibration(h, K, D, "vstab_set_input_calibration", false);
 }
 
+// The handle's detection mask: the Tracker keeps a copy and every detection of the handle reads it (seed_corners, track_frame's detection on
+// demand, Tracker::spec_launch).  Before the first pull nothing is in flight, so no stream has to be ordered behind the copy.
+vstab_status vstab_set_detection_mask(vstab_handle *h, const void *mask, size_t pitch_mask, int mem) {
+    const std::string n = "vstab_set_detection_mask: ";
+    if (!h) return fail(VSTAB_ERR_INVALID, n + "null handle");
+    if (!h->cfg.tracking) return fail(VSTAB_ERR_INVALID, n + "no detector runs on this handle (tracking = 0)");
+    if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the mask must be set before the first pull");
+    if (mask && pitch_mask < (size_t)h->w) return fail(VSTAB_ERR_INVALID, n + "the mask's pitch is smaller than the frame's width");
+    if (mask && mem != VSTAB_MEM_DEVICE && mem != VSTAB_MEM_HOST) return fail(VSTAB_ERR_INVALID, n + "mem must be VSTAB_MEM_DEVICE (0) or VSTAB_MEM_HOST (1)");
+    return h->tracker.copy_mask(mask, pitch_mask, mem == VSTAB_MEM_HOST);
+}
+
 vstab_status vstab_set_input_calibration_ex(vstab_handle *h, const double K[9], const double D[4]) {
     return set_input_calibration(h, K, D, "vstab_set_input_calibration_ex", true);
 }

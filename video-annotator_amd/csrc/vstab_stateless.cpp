@@ -142,20 +142,38 @@ vstab_status vstab_min_eig(const void *gray, size_t pitch, int width, int height
     return VSTAB_OK;
 }
 
-vstab_status vstab_good_features_ex(const void *gray, size_t pitch, int width, int height, int max_corners, double quality,
-                                    double min_distance, int detector, float *xy, int *count, int *detector_used, void *stream) {
+// vstab_good_features_ex (fn "vstab_good_features", no mask, VSTAB_DETECTOR_FUSED refused as ever) and vstab_good_features_mask
+static vstab_status good_features_op(const char *fn, bool fused_ok, const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask,
+                                     int max_corners, double quality, double min_distance, int detector, float *xy, int *count, int *detector_used,
+                                     void *stream) {
     if (!gray || !xy || !count || width < 3 || height < 3 || pitch < (size_t)width || max_corners <= 0 ||
-        (detector != VSTAB_DETECTOR_AUTO && detector != VSTAB_DETECTOR_TWO_PASS))
-        return fail(VSTAB_ERR_INVALID, "vstab_good_features: bad argument");
+        (detector != VSTAB_DETECTOR_AUTO && detector != VSTAB_DETECTOR_TWO_PASS && !(fused_ok && detector == VSTAB_DETECTOR_FUSED)))
+        return fail(VSTAB_ERR_INVALID, std::string(fn) + ": bad argument");
+    if (mask && pitch_mask < (size_t)width) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": the mask's pitch is smaller than the image's width");
+    if (mask && (uint64_t)pitch_mask * (uint64_t)height >= (1ull << 32))
+        return fail(VSTAB_ERR_INVALID, std::string(fn) + ": mask planes of 4 GiB or more are not supported");
     Tracker t;
     VSTAB_TRY(t.init(width, height));
     t.set_two_pass_detector(detector == VSTAB_DETECTOR_TWO_PASS);
+    t.set_mask(static_cast<const uint8_t *>(mask), pitch_mask);
     std::vector<float> out;
     VSTAB_TRY(t.good_features((const uint8_t *)gray, pitch, max_corners, quality, min_distance, out, static_cast<hipStream_t>(stream)));
     *count = (int)(out.size() / 2);
     std::memcpy(xy, out.data(), sizeof(float) * out.size());
     if (detector_used) *detector_used = (detector == VSTAB_DETECTOR_TWO_PASS || t.fused_overflows()) ? VSTAB_DETECTOR_TWO_PASS : VSTAB_DETECTOR_FUSED;
     return VSTAB_OK;
+}
+
+vstab_status vstab_good_features_ex(const void *gray, size_t pitch, int width, int height, int max_corners, double quality,
+                                    double min_distance, int detector, float *xy, int *count, int *detector_used, void *stream) {
+    return good_features_op("vstab_good_features", false, gray, pitch, width, height, nullptr, 0, max_corners, quality, min_distance, detector, xy, count,
+                            detector_used, stream);
+}
+
+vstab_status vstab_good_features_mask(const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask, int max_corners,
+                                      double quality, double min_distance, int detector, float *xy, int *count, int *detector_used, void *stream) {
+    return good_features_op("vstab_good_features_mask", true, gray, pitch, width, height, mask, pitch_mask, max_corners, quality, min_distance, detector, xy,
+                            count, detector_used, stream);
 }
 
 vstab_status vstab_good_features(const void *gray, size_t pitch, int width, int height, int max_corners, double quality,

@@ -157,6 +157,38 @@ __attribute__((visibility("default"))) int vstabx_lk_segments(const void *const 
     return VSTAB_OK;
 }
 
+// the body of vstabx_corners_fused and vstabx_corners_fused_mask (both below); fn names the hook in the refusals, masked says whether `mask` is looked at
+static int corners_fused_hook(const std::string &fn, const void *gray, size_t pitch, int w, int h, const void *mask, size_t pitch_mask, bool masked, double quality,
+                              unsigned int cap, unsigned int canary, unsigned long long *keys_out, unsigned int *counts_out, unsigned int *tile_counts,
+                              void *stream) {
+    if (!gray || !keys_out || !counts_out || !tile_counts || (masked && !mask)) return fail(VSTAB_ERR_INVALID, fn + ": bad argument");
+    if (w < 3 || h < 3 || pitch < (size_t)w) return fail(VSTAB_ERR_INVALID, fn + ": an image is at least 3 x 3 and its pitch at least its width");
+    if ((uint64_t)pitch * (uint64_t)h >= (1ull << 32) || (uint64_t)w * (uint64_t)h >= (1ull << 31))
+        return fail(VSTAB_ERR_INVALID, fn + ": planes of 4 GiB or more and images of 2^31 pixels or more are not supported");
+    if (!(quality > 0.0) || !(quality <= 1.0)) return fail(VSTAB_ERR_INVALID, fn + ": quality lies in (0, 1]");
+    if (cap < 1 || cap > (1u << 24)) return fail(VSTAB_ERR_INVALID, fn + ": cap is 1 .. 2^24 keys");
+    if (canary < 1 || canary > (1u << 16)) return fail(VSTAB_ERR_INVALID, fn + ": canary is 1 .. 2^16 keys");
+    if (masked && pitch_mask < (size_t)w) return fail(VSTAB_ERR_INVALID, fn + ": the mask's pitch is smaller than the image's width");
+    if (masked && (uint64_t)pitch_mask * (uint64_t)h >= (1ull << 32)) return fail(VSTAB_ERR_INVALID, fn + ": mask planes of 4 GiB or more are not supported");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const CornersFusedScratch lay(w, h);  // the layout launch_corners_fused uses: the survivor counts are read back from it below
+    const size_t scratch_bytes = lay.bytes;
+    const size_t n_keys = (size_t)cap + canary;
+    DevBuf scratch, keys, small;
+    VSTAB_TRY(scratch.ensure(scratch_bytes));
+    VSTAB_TRY(keys.ensure(n_keys * sizeof(unsigned long long)));
+    VSTAB_TRY(small.ensure(256));
+    // (under a mask the scratch starts out as garbage, as a Tracker's does: a tile that returns early has to WRITE its count of 0)
+    VSTAB_HIP_TRY(hipMemsetAsync(scratch.p, masked ? 0xA5 : 0, scratch_bytes, st));
+    VSTAB_HIP_TRY(hipMemsetAsync(keys.p, 0xA5, n_keys * sizeof(unsigned long long), st));
+    VSTAB_TRY(launch_corners_fused(static_cast<const uint8_t *>(gray), pitch, w, h, quality, scratch.p, keys.as<unsigned long long>(), cap, small.as<unsigned int>(), st,
+                                   static_cast<const uint8_t *>(mask), pitch_mask));
+    VSTAB_HIP_TRY(hipMemcpyAsync(keys_out, keys.p, n_keys * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    VSTAB_HIP_TRY(hipMemcpyAsync(counts_out, small.as<unsigned int>() + 4, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    VSTAB_HIP_TRY(hipMemcpyAsync(tile_counts, scratch.as<uint8_t>() + lay.counts_off, (size_t)lay.tiles * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    VSTAB_HIP_TRY(hipStreamSynchronize(st));
+    return VSTAB_OK;
+}
 // THE RAW OUTPUT OF THE ONE-PASS DETECTOR (tests/test_corner_paths_gpu.py; its argument checks run without a device:
 // tests/test_corner_tiles_cpu.py).  Runs launch_corners_fused (k_corners_fused, then k_filter_keys) on the w x h device luma plane `gray`
 // with a key buffer of exactly `cap` keys followed by `canary` keys the kernels must not touch; the whole buffer is filled with the byte
@@ -169,29 +201,16 @@ __attribute__((visibility("default"))) int vstabx_lk_segments(const void *const 
 __attribute__((visibility("default"))) int vstabx_corners_fused(const void *gray, size_t pitch, int w, int h, double quality, unsigned int cap, unsigned int canary,
                                                                  unsigned long long *keys_out, unsigned int *counts_out, unsigned int *tile_counts,
                                                                  void *stream) {
-    if (!gray || !keys_out || !counts_out || !tile_counts) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: bad argument");
-    if (w < 3 || h < 3 || pitch < (size_t)w) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: an image is at least 3 x 3 and its pitch at least its width");
-    if ((uint64_t)pitch * (uint64_t)h >= (1ull << 32) || (uint64_t)w * (uint64_t)h >= (1ull << 31))
-        return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: planes of 4 GiB or more and images of 2^31 pixels or more are not supported");
-    if (!(quality > 0.0) || !(quality <= 1.0)) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: quality lies in (0, 1]");
-    if (cap < 1 || cap > (1u << 24)) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: cap is 1 .. 2^24 keys");
-    if (canary < 1 || canary > (1u << 16)) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused: canary is 1 .. 2^16 keys");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const CornersFusedScratch lay(w, h);  // the layout launch_corners_fused uses: the survivor counts are read back from it below
-    const size_t scratch_bytes = lay.bytes;
-    const size_t n_keys = (size_t)cap + canary;
-    DevBuf scratch, keys, small;
-    VSTAB_TRY(scratch.ensure(scratch_bytes));
-    VSTAB_TRY(keys.ensure(n_keys * sizeof(unsigned long long)));
-    VSTAB_TRY(small.ensure(256));
-    VSTAB_HIP_TRY(hipMemsetAsync(scratch.p, 0, scratch_bytes, st));
-    VSTAB_HIP_TRY(hipMemsetAsync(keys.p, 0xA5, n_keys * sizeof(unsigned long long), st));
-    VSTAB_TRY(launch_corners_fused(static_cast<const uint8_t *>(gray), pitch, w, h, quality, scratch.p, keys.as<unsigned long long>(), cap, small.as<unsigned int>(), st));
-    VSTAB_HIP_TRY(hipMemcpyAsync(keys_out, keys.p, n_keys * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    VSTAB_HIP_TRY(hipMemcpyAsync(counts_out, small.as<unsigned int>() + 4, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    VSTAB_HIP_TRY(hipMemcpyAsync(tile_counts, scratch.as<uint8_t>() + lay.counts_off, (size_t)lay.tiles * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    VSTAB_HIP_TRY(hipStreamSynchronize(st));
-    return VSTAB_OK;
+    return corners_fused_hook("vstabx_corners_fused", gray, pitch, w, h, nullptr, 0, false, quality, cap, canary, keys_out, counts_out, tile_counts, stream);
+}
+// vstabx_corners_fused under a detection mask (tests/test_detection_mask_gpu.py, tests/mask_def.py): k_corners_fused_masked, then
+// k_filter_keys.  mask: a w x h device plane of bytes of pitch pitch_mask, not NULL.  The same outputs (the scratch is filled with the byte 0xA5 first, so
+// the count of 0 a tile that returns early reports is one it wrote) and the same refusals under this hook's name, then the mask's: a pitch below w, a
+// plane of 4 GiB or more.
+__attribute__((visibility("default"))) int vstabx_corners_fused_mask(const void *gray, size_t pitch, int w, int h, const void *mask, size_t pitch_mask, double quality,
+                                                                      unsigned int cap, unsigned int canary, unsigned long long *keys_out, unsigned int *counts_out,
+                                                                      unsigned int *tile_counts, void *stream) {
+    return corners_fused_hook("vstabx_corners_fused_mask", gray, pitch, w, h, mask, pitch_mask, true, quality, cap, canary, keys_out, counts_out, tile_counts, stream);
 }
 
 // The cost-weighted XCD bands of the fused warp (vstab_warp_bands.hpp; tests/test_band_schedule_cpu.py), no device needed.

@@ -40,8 +40,13 @@ bool pyr_down_x2_ok(int sw, int sh);
 vstab_status launch_pyr_down_x2(const uint8_t *src, size_t spitch, int sw, int sh, uint8_t *mid, size_t mpitch, uint8_t *dst, size_t dpitch, hipStream_t s,
                                 hipEvent_t done = nullptr);
 vstab_status launch_min_eig(const uint8_t *src, size_t pitch, int w, int h, float *eig, int *max_bits, hipStream_t s);
+// mask (optional, here and in launch_corners_fused): the detection mask, a w x h plane of bytes of pitch mpitch, non-zero = "a corner may
+// be reported here" (vstab.h, "Detection mask").  Without one the launches are those of the unmasked detector.  With one, max_bits of
+// launch_corner_candidates is the MASKED maximum (launch_masked_max behind launch_min_eig).
 vstab_status launch_corner_candidates(const float *eig, int w, int h, const int *max_bits, double quality,
-                                      unsigned long long *keys, unsigned int *count, unsigned int cap, hipStream_t s);
+                                      unsigned long long *keys, unsigned int *count, unsigned int cap, hipStream_t s, const uint8_t *mask = nullptr,
+                                      size_t mpitch = 0);
+vstab_status launch_masked_max(const float *eig, int w, int h, const uint8_t *mask, size_t mpitch, int *masked_max_bits, hipStream_t s);
 // The scratch of the fused detector for a w x h image, laid out in ONE place: a tile is CF_TW x CF_TH output pixels, and the buffer holds
 // CF_SLOTS key slots per tile, then a dense CF_TW x CF_TH float map per tile (written only by a tile with more survivors than slots),
 // then -- last -- one survivor count per tile (tile rows first).
@@ -56,7 +61,7 @@ struct CornersFusedScratch {
 };
 size_t corners_fused_scratch_bytes(int w, int h);
 vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h, double quality, void *scratch, unsigned long long *keys,
-                                  unsigned int cap, unsigned int *small, hipStream_t s);
+                                  unsigned int cap, unsigned int *small, hipStream_t s, const uint8_t *mask = nullptr, size_t mpitch = 0);
 // One tracker launch = a SEGMENT of up to LK_SEG_MAX consecutive frame pairs (k_lk_track): pair i is (pyr[i], pyr[i + 1]).
 //   prev_pts  the n start points of pair 0 (device-readable), or NULL when
 //   chain_in  the device records of the parent launch's last pair, whose sequence number is parent_seq: slot f starts from the

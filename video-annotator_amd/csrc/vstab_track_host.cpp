@@ -73,6 +73,20 @@ vstab_status Tracker::build_pyramid(int s, const uint8_t *gray, size_t pitch, hi
     return VSTAB_OK;
 }
 
+vstab_status Tracker::copy_mask(const void *mask, size_t pitch, bool host) {
+    if (!mask) {
+        set_mask(nullptr, 0);
+        return VSTAB_OK;
+    }
+    const size_t own_pitch = ((size_t)w_ + 3) & ~(size_t)3;
+    VSTAB_TRY(mask_buf_.ensure(own_pitch * (size_t)h_));
+    VSTAB_HIP_TRY(hipMemset(mask_buf_.p, 0, own_pitch * (size_t)h_));  // the padding bytes are never read; zero all the same
+    VSTAB_HIP_TRY(hipMemcpy2D(mask_buf_.p, own_pitch, mask, pitch, (size_t)w_, (size_t)h_, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+    VSTAB_HIP_TRY(hipDeviceSynchronize());  // (a device-to-device copy may return before it is done: the caller may free the mask after this call)
+    set_mask(mask_buf_.as<uint8_t>(), own_pitch);
+    return VSTAB_OK;
+}
+
 void Tracker::select_corners(unsigned long long *k, unsigned int n, int max_corners, double min_distance, std::vector<float> &xy) {
     xy.clear();
     const int cell = (int)std::nearbyint(min_distance);
@@ -140,9 +154,9 @@ vstab_status Tracker::good_features(const uint8_t *gray, size_t pitch, int max_c
         // one pass: eigenvalue, threshold and 3x3 maximum test fused, the eigenvalue map never stored
         VSTAB_TRY(raw_keys_.ensure(corners_fused_scratch_bytes(w_, h_)));
 #ifdef VSTAB_DEV
-        if (getenv("VSTAB_DEV_DET_TWICE")) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st));
+        if (getenv("VSTAB_DEV_DET_TWICE")) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st, mask_, mask_pitch_));
 #endif
-        VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st));
+        VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st, mask_, mask_pitch_));
         VSTAB_HIP_TRY(hipMemcpyAsync(hsmall_.p, count, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
         VSTAB_HIP_TRY(hipStreamSynchronize(st));
         const unsigned int kept = hsmall_.as<unsigned int>()[0];
@@ -152,9 +166,13 @@ vstab_status Tracker::good_features(const uint8_t *gray, size_t pitch, int max_c
     VSTAB_TRY(eig_.ensure(sizeof(float) * (size_t)w_ * h_));
     if (!eig) eig = eig_.as<float>();
     VSTAB_TRY(launch_min_eig(gray, pitch, w_, h_, eig, max_bits, st));
+    if (mask_) {  // the threshold of a masked detection comes from the maximum over the masked-in pixels: small_[1], beside the frame's
+        VSTAB_TRY(launch_masked_max(eig, w_, h_, mask_, mask_pitch_, max_bits + 1, st));
+        max_bits += 1;
+    }
     unsigned int n = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
-        VSTAB_TRY(launch_corner_candidates(eig, w_, h_, max_bits, quality, keys_.as<unsigned long long>(), count, cap_, st));
+        VSTAB_TRY(launch_corner_candidates(eig, w_, h_, max_bits, quality, keys_.as<unsigned long long>(), count, cap_, st, mask_, mask_pitch_));
         VSTAB_HIP_TRY(hipMemcpyAsync(hsmall_.p, count, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
         VSTAB_HIP_TRY(hipStreamSynchronize(st));
         n = *hsmall_.as<unsigned int>();
@@ -175,9 +193,9 @@ vstab_status Tracker::spec_launch(const uint8_t *gray, size_t pitch, double qual
     unsigned int *count = spec_small_.as<unsigned int>() + 4;
 #ifdef VSTAB_DEV
     static const bool det_twice = getenv("VSTAB_DEV_DET_TWICE") != nullptr;  // sensitivity of the frame rate to the detector: everything twice, same result
-    if (det_twice) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st));
+    if (det_twice) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st, mask_, mask_pitch_));
 #endif
-    VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st));
+    VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st, mask_, mask_pitch_));
     VSTAB_HIP_TRY(hipMemcpyAsync(spec_host_.p, count, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));  // {keys kept, tiles that spilled}
     VSTAB_HIP_TRY(hipMemcpyAsync(spec_host_.as<uint8_t>() + 64, spec_keys_.p, sizeof(unsigned long long) * SPEC_CAP, hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipEventRecord(spec_ev_, st));

@@ -70,6 +70,14 @@ class Tracker {
     long selections_by_caller() const { return selections_by_caller_; }
     long selections_by_helper() const { return selections_by_helper_.load(std::memory_order_relaxed); }
     void set_two_pass_detector(bool on) { two_pass_detector_ = on; }
+    // The detection mask (vstab.h, "Detection mask"): a device plane of w x h bytes, non-zero = "a corner may be reported here", read by
+    // every detection from now on -- good_features (fused, two-pass and the fall-back between them) and spec_launch.  NULL: no mask, the
+    // launches of the unmasked detector.  set_mask borrows the caller's plane; copy_mask keeps a copy in device memory of the Tracker's
+    // own (base and pitch 4-byte aligned: the kernels' dword path) and returns when the copy is complete.  Only while nothing is in flight.
+    void set_mask(const uint8_t *mask, size_t pitch) { mask_ = mask, mask_pitch_ = mask ? pitch : 0; }
+    vstab_status copy_mask(const void *mask, size_t pitch, bool host);
+    const uint8_t *mask() const { return mask_; }
+    size_t mask_pitch() const { return mask_pitch_; }
     long fused_overflows() const { return fused_overflows_; }
     // (vstabx_detector_counters) speculative selections that found more than SPEC_CAP candidates; the key capacity of good_features now
     long spec_over_cap() const { return spec_over_cap_.load(std::memory_order_relaxed); }
@@ -187,6 +195,9 @@ class Tracker {
     DevBuf pyr_[PYR_SETS + PYR_DEV_EXTRA][LK_MAX_LEVELS], eig_, keys_, small_;  // pyramid sets: previous, current, prefetched x2
     DevBuf spec_raw_, spec_keys_, spec_small_, raw_keys_;
     bool two_pass_detector_ = false;
+    const uint8_t *mask_ = nullptr;  // the detection mask in force (mask_buf_'s, or a caller's), NULL for none
+    size_t mask_pitch_ = 0;
+    DevBuf mask_buf_;
     const bool single_level_pyramid_ = getenv("VSTAB_PYR_SINGLE") != nullptr;  // development: one launch per pyramid level
     long fused_overflows_ = 0;
     PinnedBuf spec_host_;
