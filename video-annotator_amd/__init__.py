@@ -431,21 +431,7 @@ def remap_cubic(src, mapx, mapy, border=(0, 0, 0), out=None):
 
 def warp_nv12_cubic(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, out=None):
     """vstab_warp_nv12_cubic: the warp with INTER_CUBIC.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma) tensors."""
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p = np.ascontiguousarray(params, np.float32)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_cubic(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), OUT_BGR8, out.data_ptr(), out.stride(0), None, 0, dw, dh,
-                                        _stream()), "vstab_warp_nv12_cubic")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_cubic(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), int(out_format), yo.data_ptr(), yo.stride(0), co.data_ptr(),
-                                    co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_cubic")
-    return yo, co
+    return _warp_nv12(_L.vstab_warp_nv12_cubic, nv12, dw, dh, out_format, out, (_f32(params), int(mode)))
 
 
 def lanczos4_weights():
@@ -471,21 +457,7 @@ def remap_lanczos4(src, mapx, mapy, border=(0, 0, 0), out=None):
 
 def warp_nv12_lanczos4(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, out=None):
     """vstab_warp_nv12_lanczos4: the warp with INTER_LANCZOS4.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma) tensors."""
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p = np.ascontiguousarray(params, np.float32)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_lanczos4(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), OUT_BGR8, out.data_ptr(), out.stride(0), None, 0, dw, dh,
-                                           _stream()), "vstab_warp_nv12_lanczos4")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_lanczos4(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), int(out_format), yo.data_ptr(), yo.stride(0), co.data_ptr(),
-                                       co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_lanczos4")
-    return yo, co
+    return _warp_nv12(_L.vstab_warp_nv12_lanczos4, nv12, dw, dh, out_format, out, (_f32(params), int(mode)))
 
 
 def warp_nv12_bgr(nv12, params, dw, dh, out=None):
@@ -521,109 +493,63 @@ def nv12_out_planes(dw, dh, device="cuda"):
             torch.empty(((dh + 1) // 2, 2 * ((dw + 1) // 2)), dtype=torch.uint8, device=device))
 
 
-def warp_nv12(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, out=None):
-    """vstab_warp_nv12_ex.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12 -> (luma, chroma) tensors."""
+def _f32(a, n=None):
+    """A float32 array for _fptr (n: its length), or None for None."""
+    return None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1 if n is None else n)
+
+
+def _warp_nv12(fn, nv12, dw, dh, out_format, out, head, tail=()):
+    """The body of every warp_nv12* wrapper: fn(the source planes, *head, out_format, *tail, the output planes, dw, dh, the stream).  head and
+    tail: the middle of the C argument list, float32 arrays in it passed by pointer (None: a null pointer).  OUT_BGR8 -> the (dh, dw, 3) tensor;
+    the other formats -> the (luma, chroma) tensors.  out: the caller's tensor / pair, default new ones."""
     import torch
     yp, uvp, pitch, w, h = _planes(nv12)
-    p = np.ascontiguousarray(params, np.float32)
     if out_format == OUT_BGR8:
         if out is None:
             out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), OUT_BGR8, out.data_ptr(),
-                                     out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_ex")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), int(out_format), yo.data_ptr(), yo.stride(0),
-                                 co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_ex")
-    return yo, co
+        planes = (out.data_ptr(), out.stride(0), None, 0)
+    else:
+        if out is None:
+            out = nv12_out_planes(dw, dh, nv12.device)
+        yo, co = out
+        out = yo, co
+        planes = (yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0))
+    head, tail = ([_fptr(a) if isinstance(a, np.ndarray) else a for a in part] for part in (head, tail))
+    _check(fn(yp, pitch, uvp, pitch, w, h, *head, int(out_format), *tail, *planes, dw, dh, _stream()), fn.__name__)
+    return out
+
+
+def warp_nv12(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, out=None):
+    """vstab_warp_nv12_ex.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12 -> (luma, chroma) tensors."""
+    return _warp_nv12(_L.vstab_warp_nv12_ex, nv12, dw, dh, out_format, out, (_f32(params), int(mode)))
 
 
 def warp_nv12_dist(nv12, params, dist, dw, dh, mode=MAP_FISH_TO_RECT, out_format=OUT_BGR8, out=None):
     """vstab_warp_nv12_dist: warp_nv12 in mode 1 / 2 with the input lens's k1..k4.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR ->
     (luma, chroma) tensors."""
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p, d = np.ascontiguousarray(params, np.float32), np.ascontiguousarray(dist, np.float32).reshape(4)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_dist(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), OUT_BGR8, out.data_ptr(), out.stride(0), None, 0,
-                                       dw, dh, _stream()), "vstab_warp_nv12_dist")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_dist(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(out_format), yo.data_ptr(), yo.stride(0),
-                                   co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_dist")
-    return yo, co
+    return _warp_nv12(_L.vstab_warp_nv12_dist, nv12, dw, dh, out_format, out, (_f32(params), _f32(dist, 4), int(mode)))
 
 
 def warp_nv12_dist_ex(nv12, params, dist, dw, dh, mode=MAP_FISH_TO_RECT, resample=RESAMPLE_DEFAULT, border_mode=BORDER_CONSTANT, out_format=OUT_BGR8,
                       out=None):
     """vstab_warp_nv12_dist_ex: warp_nv12_dist with a resampler (RESAMPLE_DEFAULT, _CUBIC, _LANCZOS4) and a border mode (BORDER_*).  OUT_BGR8 ->
     (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma) tensors."""
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p, d = np.ascontiguousarray(params, np.float32), np.ascontiguousarray(dist, np.float32).reshape(4)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_dist_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), OUT_BGR8,
-                                          out.data_ptr(), out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_dist_ex")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_dist_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), int(out_format),
-                                      yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_dist_ex")
-    return yo, co
+    return _warp_nv12(_L.vstab_warp_nv12_dist_ex, nv12, dw, dh, out_format, out, (_f32(params), _f32(dist, 4), int(mode), int(resample), int(border_mode)))
 
 
 def warp_nv12_pinhole(nv12, params, dist, dw, dh, mode=MAP_RECT_TO_RECT, resample=RESAMPLE_DEFAULT, border_mode=BORDER_CONSTANT, out_format=OUT_BGR8,
                       out=None):
     """vstab_warp_nv12_pinhole: the warp through a rectilinear lens with dist = (k1, k2, p1, p2, k3), map mode 3 / 4, with a resampler
     (RESAMPLE_DEFAULT, _CUBIC, _LANCZOS4) and a border mode (BORDER_*).  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma)."""
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p, d = np.ascontiguousarray(params, np.float32), np.ascontiguousarray(dist, np.float32).reshape(5)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_pinhole(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), OUT_BGR8,
-                                          out.data_ptr(), out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_pinhole")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_pinhole(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(d), int(mode), int(resample), int(border_mode), int(out_format),
-                                      yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_pinhole")
-    return yo, co
+    return _warp_nv12(_L.vstab_warp_nv12_pinhole, nv12, dw, dh, out_format, out, (_f32(params), _f32(dist, 5), int(mode), int(resample), int(border_mode)))
 
 
 def warp_nv12_rs_ex(nv12, params, dw, dh, rot_bottom=None, dist=None, mode=MAP_CREATEMAP_CL, resample=RESAMPLE_DEFAULT, border_mode=BORDER_CONSTANT,
                     out_format=OUT_BGR8, out=None):
     """vstab_warp_nv12_rs_ex: the 8-bit warp with a rotation per output row (rot_bottom, 9 floats or None), a calibrated lens (dist, k1..k4 or
     None), a resampler (RESAMPLE_*) and a border mode (BORDER_*).  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma) tensors."""
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p = np.ascontiguousarray(params, np.float32)
-    rb = None if rot_bottom is None else np.ascontiguousarray(rot_bottom, np.float32).reshape(9)
-    d = None if dist is None else np.ascontiguousarray(dist, np.float32).reshape(4)
-    rbp, dp = None if rb is None else _fptr(rb), None if d is None else _fptr(d)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_rs_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, dp, int(mode), int(resample), int(border_mode), OUT_BGR8,
-                                        out.data_ptr(), out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_rs_ex")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_rs_ex(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, dp, int(mode), int(resample), int(border_mode), int(out_format),
-                                    yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_rs_ex")
-    return yo, co
+    return _warp_nv12(_L.vstab_warp_nv12_rs_ex, nv12, dw, dh, out_format, out,
+                      (_f32(params), _f32(rot_bottom, 9), _f32(dist, 4), int(mode), int(resample), int(border_mode)))
 
 
 def remap_bilinear_border(src, mapx, mapy, border_mode=BORDER_REFLECT_101, out=None):
@@ -644,23 +570,7 @@ def remap_bilinear_border(src, mapx, mapy, border_mode=BORDER_REFLECT_101, out=N
 def warp_nv12_border(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, border_mode=BORDER_REFLECT_101, rot_bottom=None, out=None):
     """vstab_warp_nv12_border: the bilinear warp with a border mode (rot_bottom: vstab_warp_nv12_rs's rotation of the last output row).
     OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma) tensors."""
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p = np.ascontiguousarray(params, np.float32)
-    rb = None if rot_bottom is None else np.ascontiguousarray(rot_bottom, np.float32).reshape(9)
-    rbp = None if rb is None else _fptr(rb)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_border(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, int(mode), OUT_BGR8, int(border_mode), out.data_ptr(),
-                                         out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_border")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_border(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, int(mode), int(out_format), int(border_mode), yo.data_ptr(),
-                                     yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_border")
-    return yo, co
+    return _warp_nv12(_L.vstab_warp_nv12_border, nv12, dw, dh, out_format, out, (_f32(params), _f32(rot_bottom, 9), int(mode)), (int(border_mode),))
 
 
 def remap_bilinear_keep(src, mapx, mapy, prev, out=None):
@@ -683,23 +593,11 @@ def warp_nv12_keep(nv12, params, dw, dh, prev, mode=MAP_CREATEMAP_CL, out_format
     """vstab_warp_nv12_keep: the bilinear warp where its footprint lies inside the source, prev's bytes everywhere else.  OUT_BGR8: prev a
     (dh, dw, 3) tensor -> (dh, dw, 3) tensor; OUT_NV12_PLANAR: prev a (luma, chroma) pair -> (luma, chroma) tensors.  out: tensors of their
     own (default: new ones), or prev itself -- in place.  rot_bottom: vstab_warp_nv12_rs's rotation of the last output row."""
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p = np.ascontiguousarray(params, np.float32)
-    rb = None if rot_bottom is None else np.ascontiguousarray(rot_bottom, np.float32).reshape(9)
-    rbp = None if rb is None else _fptr(rb)
     if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_keep(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, int(mode), OUT_BGR8, prev.data_ptr(), prev.stride(0), None, 0,
-                                       out.data_ptr(), out.stride(0), None, 0, dw, dh, _stream()), "vstab_warp_nv12_keep")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    (yo, co), (py, pc) = out, prev
-    _check(_L.vstab_warp_nv12_keep(yp, pitch, uvp, pitch, w, h, _fptr(p), rbp, int(mode), int(out_format), py.data_ptr(), py.stride(0), pc.data_ptr(),
-                                   pc.stride(0), yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_keep")
-    return yo, co
+        history = (prev.data_ptr(), prev.stride(0), None, 0)
+    else:
+        history = (prev[0].data_ptr(), prev[0].stride(0), prev[1].data_ptr(), prev[1].stride(0))
+    return _warp_nv12(_L.vstab_warp_nv12_keep, nv12, dw, dh, out_format, out, (_f32(params), _f32(rot_bottom, 9), int(mode)), history)
 
 
 def _remap_resample_border(fn, name, src, mapx, mapy, border_mode, border, out):
@@ -725,54 +623,19 @@ def remap_lanczos4_border(src, mapx, mapy, border_mode=BORDER_REFLECT_101, borde
     return _remap_resample_border(_L.vstab_remap_lanczos4_border, "vstab_remap_lanczos4_border", src, mapx, mapy, border_mode, border, out)
 
 
-def _warp_resample_border(fn, name, nv12, params, dw, dh, mode, out_format, border_mode, out):
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p = np.ascontiguousarray(params, np.float32)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(fn(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), OUT_BGR8, int(border_mode), out.data_ptr(), out.stride(0), None, 0, dw, dh,
-                  _stream()), name)
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(fn(yp, pitch, uvp, pitch, w, h, _fptr(p), int(mode), int(out_format), int(border_mode), yo.data_ptr(), yo.stride(0), co.data_ptr(),
-              co.stride(0), dw, dh, _stream()), name)
-    return yo, co
-
-
 def warp_nv12_cubic_border(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, border_mode=BORDER_REFLECT_101, out=None):
     """vstab_warp_nv12_cubic_border: the INTER_CUBIC warp with a border mode.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12_PLANAR -> (luma, chroma)."""
-    return _warp_resample_border(_L.vstab_warp_nv12_cubic_border, "vstab_warp_nv12_cubic_border", nv12, params, dw, dh, mode, out_format, border_mode,
-                                 out)
+    return _warp_nv12(_L.vstab_warp_nv12_cubic_border, nv12, dw, dh, out_format, out, (_f32(params), int(mode)), (int(border_mode),))
 
 
 def warp_nv12_lanczos4_border(nv12, params, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, border_mode=BORDER_REFLECT_101, out=None):
     """vstab_warp_nv12_lanczos4_border: the INTER_LANCZOS4 warp with a border mode.  Arguments and results as warp_nv12_cubic_border."""
-    return _warp_resample_border(_L.vstab_warp_nv12_lanczos4_border, "vstab_warp_nv12_lanczos4_border", nv12, params, dw, dh, mode, out_format,
-                                 border_mode, out)
+    return _warp_nv12(_L.vstab_warp_nv12_lanczos4_border, nv12, dw, dh, out_format, out, (_f32(params), int(mode)), (int(border_mode),))
 
 
 def warp_nv12_rs(nv12, params, rot_bottom, dw, dh, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, out=None):
     """vstab_warp_nv12_rs: the warp with a rotation per output row (first row params[8:17], last row rot_bottom)."""
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    p = np.ascontiguousarray(params, np.float32)
-    rb = np.ascontiguousarray(rot_bottom, np.float32).reshape(9)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_rs(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(rb), int(mode), OUT_BGR8, out.data_ptr(), out.stride(0), None, 0,
-                                     dw, dh, _stream()), "vstab_warp_nv12_rs")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_rs(yp, pitch, uvp, pitch, w, h, _fptr(p), _fptr(rb), int(mode), int(out_format), yo.data_ptr(), yo.stride(0),
-                                 co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_rs")
-    return yo, co
+    return _warp_nv12(_L.vstab_warp_nv12_rs, nv12, dw, dh, out_format, out, (_f32(params), _f32(rot_bottom, 9), int(mode)))
 
 
 BLEND_EXACT, BLEND_FP16 = 0, 1
@@ -866,25 +729,9 @@ def quantised_map_dist(params, dist, dw, dh, mode=MAP_FISH_TO_RECT, device="cuda
 
 
 def warp_nv12_mapped(nv12, qmap, dw, dh, out_format=OUT_BGR8, out=None):
-    import torch
-    yp, uvp, pitch, w, h = _planes(nv12)
-    if out_format == OUT_BGR8:
-        if out is None:
-            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
-        _check(_L.vstab_warp_nv12_mapped(yp, pitch, uvp, pitch, w, h, qmap.data_ptr(), OUT_BGR8, out.data_ptr(), out.stride(0), None, 0,
-                                         dw, dh, _stream()), "vstab_warp_nv12_mapped")
-        return out
-    if out is None:
-        out = nv12_out_planes(dw, dh, nv12.device)
-    yo, co = out
-    _check(_L.vstab_warp_nv12_mapped(yp, pitch, uvp, pitch, w, h, qmap.data_ptr(), int(out_format), yo.data_ptr(), yo.stride(0),
-                                     co.data_ptr(), co.stride(0), dw, dh, _stream()), "vstab_warp_nv12_mapped")
-    return yo, co
+    return _warp_nv12(_L.vstab_warp_nv12_mapped, nv12, dw, dh, out_format, out, (qmap.data_ptr(),))
 
 
-# ---------------------------------------------------------------------------------------------
-# tracking front-end / motion model
-# ---------------------------------------------------------------------------------------------
 def pyr_down(img):
     import torch
     h, w = img.shape

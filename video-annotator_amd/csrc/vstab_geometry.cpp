@@ -62,13 +62,13 @@ bool preset_camera(int preset, int w, int h, Mat3 &K) {
     return true;
 }
 
-vstab_status check_distortion(const std::string &n, const double D[4]) {
+vstab_status check_distortion(const char *n, const double D[4]) {
     bool ok = D && std::isfinite(D[0]) && std::isfinite(D[1]) && std::isfinite(D[2]) && std::isfinite(D[3]);
     for (int i = 0; ok && i <= 1024; i++) {  // d theta_d / d theta on a grid of [0, pi/2]
         const double t = i * (M_PI / 2.) / 1024, t2 = t * t, t4 = t2 * t2, t6 = t4 * t2, t8 = t6 * t2;
         ok = 1 + 3 * D[0] * t2 + 5 * D[1] * t4 + 7 * D[2] * t6 + 9 * D[3] * t8 > 0;
     }
-    return ok ? VSTAB_OK : fail(VSTAB_ERR_INVALID, n + ": the distortion must keep theta_d increasing on [0, pi/2]");
+    return ok ? VSTAB_OK : fail(VSTAB_ERR_INVALID, std::string(n) + ": the distortion must keep theta_d increasing on [0, pi/2]");
 }
 
 // theta_d -> theta as OpenCV 4.5's fisheye::undistortPoints inverts the polynomial: Newton from theta = theta_d, at most 10 steps, stop at
@@ -233,7 +233,7 @@ vstab_status vstab_lens_camera(int projection, double dfov_deg, int width, int h
 static vstab_status undistort_points(const std::string &name, const double *pts, int n, const double K[9], const double *D, const double *R, const double *P,
                                      double *out) {
     if (!pts || !K || !out || n < 0) return fail(VSTAB_ERR_INVALID, name + ": bad argument");
-    if (D) VSTAB_TRY(check_distortion(name, D));
+    if (D) VSTAB_TRY(check_distortion(name.c_str(), D));
     Mat3 k, rr = Mat3::identity();
     std::memcpy(k.m, K, sizeof(k.m));
     if (R) std::memcpy(rr.m, R, sizeof(rr.m));
@@ -260,7 +260,7 @@ vstab_status vstab_undistort_points_pinhole(const double *pts, int n, const doub
                                             double *out) {
     const std::string name = "vstab_undistort_points_pinhole";
     if (!pts || !K || !D || !out || n < 0) return fail(VSTAB_ERR_INVALID, name + ": bad argument");
-    VSTAB_TRY(check_pinhole_distortion(name, D));
+    VSTAB_TRY(check_pinhole_distortion(name.c_str(), D));
     Mat3 k, rr = Mat3::identity();
     std::memcpy(k.m, K, sizeof(k.m));
     if (R) std::memcpy(rr.m, R, sizeof(rr.m));

@@ -65,11 +65,11 @@ struct KeepPlane {
     size_t pitch_dst, row_bytes;
     int rows;
 };
-inline vstab_status check_keep_prev(const std::string &n, const KeepPlane *pl, int planes, bool &in_place) {
+inline vstab_status check_keep_prev(const char *n, const KeepPlane *pl, int planes, bool &in_place) {
     for (int k = 0; k < planes; k++)
-        if (!pl[k].prev) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
+        if (!pl[k].prev) return fail(VSTAB_ERR_INVALID, std::string(n) + ": null pointer");
     for (int k = 0; k < planes; k++)
-        if (pl[k].pitch_prev < pl[k].row_bytes) return fail(VSTAB_ERR_INVALID, n + ": prev pitch smaller than row");
+        if (pl[k].pitch_prev < pl[k].row_bytes) return fail(VSTAB_ERR_INVALID, std::string(n) + ": prev pitch smaller than row");
     int same = 0;
     for (int k = 0; k < planes; k++) same += pl[k].prev == pl[k].dst && pl[k].pitch_prev == pl[k].pitch_dst;
     in_place = same == planes;
@@ -81,14 +81,15 @@ inline vstab_status check_keep_prev(const std::string &n, const KeepPlane *pl, i
             const uintptr_t d1 = d0 + pl[m].pitch_dst * (size_t)(pl[m].rows - 1) + pl[m].row_bytes;
             overlap = overlap || (p0 < d1 && d0 < p1);
         }
-    if (overlap) return fail(VSTAB_ERR_INVALID, n + ": prev must be dst itself (same pointer and pitch, every plane) or must not overlap it");
+    if (overlap) return fail(VSTAB_ERR_INVALID, std::string(n) + ": prev must be dst itself (same pointer and pitch, every plane) or must not overlap it");
     return VSTAB_OK;
 }
 
-// k1..k4 of a fisheye lens as every entry point that takes them accepts them (vstab_geometry.cpp): all finite, and theta_d increasing
+// k1..k4 of a fisheye lens as every entry point that takes them accepts them (vstab_geometry.cpp; n: its name, a string only in a refusal):
+// all finite, and theta_d increasing
 // on [0, pi/2] -- the warp kernels' perimeter probe bounds a tile's source box only for a map that does not fold
-vstab_status check_distortion(const std::string &n, const double D[4]);
-inline vstab_status check_distortion(const std::string &n, const float D[4]) {
+vstab_status check_distortion(const char *n, const double D[4]);
+inline vstab_status check_distortion(const char *n, const float D[4]) {
     const double d[4] = {D[0], D[1], D[2], D[3]};
     return check_distortion(n, d);
 }
@@ -97,12 +98,12 @@ inline bool map_mode_takes_distortion(int map_mode) { return map_mode == VSTAB_M
 
 // (k1, k2, p1, p2, k3) of a rectilinear lens as every *_pinhole entry point accepts them: all five finite, in fp64 and after the cast to
 // fp32.  No monotonicity rule: the kernels that serve them take a tile's box as the exact reduction of the tile's own map.
-inline vstab_status check_pinhole_distortion(const std::string &n, const double D[5]) {
+inline vstab_status check_pinhole_distortion(const char *n, const double D[5]) {
     for (int i = 0; i < 5; i++)
-        if (!std::isfinite(D[i]) || !std::isfinite((float)D[i])) return fail(VSTAB_ERR_INVALID, n + ": the five distortion coefficients must be finite");
+        if (!std::isfinite(D[i]) || !std::isfinite((float)D[i])) return fail(VSTAB_ERR_INVALID, std::string(n) + ": the five distortion coefficients must be finite");
     return VSTAB_OK;
 }
-inline vstab_status check_pinhole_distortion(const std::string &n, const float D[5]) {
+inline vstab_status check_pinhole_distortion(const char *n, const float D[5]) {
     const double d[5] = {D[0], D[1], D[2], D[3], D[4]};
     return check_pinhole_distortion(n, d);
 }

@@ -283,16 +283,16 @@ vstab_status create_map_impl(const std::string &n, void *map_x, size_t pitch_x, 
     if (pitch_x < (size_t)cols * 4 || pitch_y < (size_t)cols * 4 || pitch_x % 4 || pitch_y % 4)
         return fail(VSTAB_ERR_INVALID, n + ": bad pitch");
     VSTAB_TRY(check_map_mode(n, map_mode, with_dist));
-    if (with_dist) VSTAB_TRY(check_distortion(n, dist));
+    if (with_dist) VSTAB_TRY(check_distortion(n.c_str(), dist));
     const int vec_ok = ptr_aligned(map_x, 16) && ptr_aligned(map_y, 16) && pitch_x % 16 == 0 && pitch_y % 16 == 0;
     dim3 grid(div_up(div_up(cols, 4), 16), div_up(rows, 16));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Distortion d = with_dist ? Distortion{dist[0], dist[1], dist[2], dist[3]} : Distortion();
-    with_map_mode_or_dist(map_mode, with_dist, [&](auto mode) {
+    with_kernel_mode(kernel_mode_tag(map_mode, with_dist ? LENS_FISHEYE : LENS_IDEAL, false), [&](auto mode) {
         constexpr int MODE = decltype(mode)::value;
         if constexpr (MODE == MAP_CREATEMAP_CL)  // createMap.cl itself
             hipLaunchKernelGGL(k_create_map, grid, dim3(16, 16), 0, s, (float *)map_x, pitch_x, (float *)map_y, pitch_y, cols, rows, map_params(params), vec_ok);
-        else
+        else if constexpr (mode_plain_or_dist(MODE))
             hipLaunchKernelGGL(k_create_map_ex<MODE>, grid, dim3(16, 16), 0, s, (float *)map_x, pitch_x, (float *)map_y, pitch_y, cols, rows,
                                map_params(params), vec_ok, d);
     });
@@ -307,13 +307,14 @@ vstab_status create_map_pinhole_impl(const std::string &n, void *map_x, size_t p
     if (cols <= 0 || rows <= 0 || cols > 32767 || rows > 32767) return fail(VSTAB_ERR_INVALID, n + ": size must be in [1, 32767] (createMap.cl:10-11)");
     if (pitch_x < (size_t)cols * 4 || pitch_y < (size_t)cols * 4 || pitch_x % 4 || pitch_y % 4) return fail(VSTAB_ERR_INVALID, n + ": bad pitch");
     if (!map_mode_takes_pinhole(map_mode)) return fail(VSTAB_ERR_INVALID, n + ": pinhole distortion belongs to a rectilinear input (map modes 3 and 4)");
-    VSTAB_TRY(check_pinhole_distortion(n, dist));
+    VSTAB_TRY(check_pinhole_distortion(n.c_str(), dist));
     const int vec_ok = ptr_aligned(map_x, 16) && ptr_aligned(map_y, 16) && pitch_x % 16 == 0 && pitch_y % 16 == 0;
     dim3 grid(div_up(div_up(cols, 4), 16), div_up(rows, 16));
     const PinholeLens d = {{dist[0], dist[1], dist[2], dist[3], dist[4]}};
-    with_pinhole_mode(map_mode, [&](auto mode) {
-        hipLaunchKernelGGL((k_create_map_ex<decltype(mode)::value, PinholeLens>), grid, dim3(16, 16), 0, static_cast<hipStream_t>(stream), (float *)map_x, pitch_x,
-                           (float *)map_y, pitch_y, cols, rows, map_params(params), vec_ok, d);
+    with_kernel_mode(kernel_mode_tag(map_mode, LENS_PINHOLE, false), [&](auto mode) {
+        if constexpr (ModeTraits<decltype(mode)::value>::rectd)
+            hipLaunchKernelGGL((k_create_map_ex<decltype(mode)::value, PinholeLens>), grid, dim3(16, 16), 0, static_cast<hipStream_t>(stream), (float *)map_x, pitch_x,
+                               (float *)map_y, pitch_y, cols, rows, map_params(params), vec_ok, d);
     });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
@@ -325,13 +326,14 @@ vstab_status quantised_map_impl(const std::string &n, void *qmap, int dw, int dh
     if (!qmap || !params || (with_dist && !dist) || dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767) return fail(VSTAB_ERR_INVALID, n + ": bad argument");
     VSTAB_TRY(check_map_mode(n, map_mode, with_dist));
     if (!ptr_aligned(qmap, 16)) return fail(VSTAB_ERR_INVALID, n + ": the buffer must be 16-byte aligned");
-    if (with_dist) VSTAB_TRY(check_distortion(n, dist));
+    if (with_dist) VSTAB_TRY(check_distortion(n.c_str(), dist));
     const int qpitch = (dw + 3) & ~3;
     dim3 grid(div_up(qpitch / 4, 16), div_up(dh, 16));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    with_map_mode_or_dist(map_mode, with_dist, [&](auto mode) {
-        hipLaunchKernelGGL(k_quantised_map<decltype(mode)::value>, grid, dim3(256), 0, st, static_cast<int2 *>(qmap), qpitch, dw, dh, map_params(params),
-                           map_params32(params, dist));
+    with_kernel_mode(kernel_mode_tag(map_mode, with_dist ? LENS_FISHEYE : LENS_IDEAL, false), [&](auto mode) {
+        if constexpr (mode_plain_or_dist(decltype(mode)::value))
+            hipLaunchKernelGGL(k_quantised_map<decltype(mode)::value>, grid, dim3(256), 0, st, static_cast<int2 *>(qmap), qpitch, dw, dh, map_params(params),
+                               map_params32(params, dist));
     });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;

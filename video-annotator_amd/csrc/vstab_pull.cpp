@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "vstab_pipeline.hpp"
+#include "vstab_warp_request.hpp"
 
 constexpr int OUT_BGR16 = 16;        // internal: the 10-bit path's output (vstab_pull_frame_bgr16)
 constexpr int OUT_P010 = 17;         // internal: the 10-bit path's frame as P010 planes (vstab_pull_frame_p010)
@@ -59,7 +60,7 @@ static vstab_status refuse_keep(const vstab_handle *H, const Pull &P) {
     const KeepPlane planes[2] = {{k.prev, k.pitch_prev, P.dst, P.pitch_dst, (size_t)H->ow * (planar ? 1 : 3), H->oh},
                                  {k.prev_uv, k.pitch_prev_uv, P.dst_uv, P.pitch_dst_uv, (size_t)((H->ow + 1) / 2) * 2, (H->oh + 1) / 2}};
     bool in_place;
-    return check_keep_prev(n, planes, planar ? 2 : 1, in_place);
+    return check_keep_prev(k.fn, planes, planar ? 2 : 1, in_place);
 }
 
 // 2. consume frames until the look-ahead window of the next one to emit is complete, or upstream has ended
@@ -194,56 +195,38 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
         }
         return st;
     }
-    // a keep pull (refuse_keep: INTER_LINEAR, constant border, ideal lens): with the frame's read-out rotation where it has one
-    if (P.keep)
-        return vstab_warp_nv12_keep(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.keep->prev, P.keep->pitch_prev, P.keep->prev_uv,
-                                    P.keep->pitch_prev_uv, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
-    // vstab_set_input_pinhole: vstab_warp_nv12_pinhole with the handle's resampler and the pull's border mode.  It has no rotation per row,
-    // whatever vstab_set_readout_warp says.  (A rectilinear input refuses a frame that carries a read-out rotation where it takes it from
-    // upstream, prefetch_next; should such a frame ever get here it is consumed, as INTER_NEAREST consumes it below.)
-    if (H->pinhole) {
-        if (P.rot_bottom) return refuse_launch("a calibrated handle (vstab_set_input_pinhole) warps frames without a read-out rotation");
-        return vstab_warp_nv12_pinhole(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, H->pdist32, mode, H->cfg.resample, P.border_mode, out_format, P.dst, P.pitch_dst,
-                                       P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+    // The 8-bit warps: one request from the handle and the pull, the pipeline's own refusals, then the stateless warps' one path
+    // (warp_nv12: vstab_warp_request.hpp), under the name of the stateless entry point that stands for this handle.
+    const bool per_row = P.rot_bottom && H->readout_warp == VSTAB_READOUT_PER_ROW;  // vstab_set_readout_warp(VSTAB_READOUT_PER_ROW)
+    // a frame that carries a read-out rotation where the handle's warp has no rotation per row: it is consumed, as INTER_NEAREST consumes it
+    // below.  (A rectilinear input refuses such a frame where it takes it from upstream, prefetch_next; a keep pull warps it per row.)
+    if (P.rot_bottom && !P.keep) {
+        if (H->pinhole) return refuse_launch("a calibrated handle (vstab_set_input_pinhole) warps frames without a read-out rotation");
+        if (H->calibrated && !per_row) return refuse_launch("a calibrated handle (vstab_set_input_calibration) warps frames without a read-out rotation");
+        if (resampled && !per_row) return refuse_launch(std::string(resample_name(H->cfg.resample)) + " warps frames without a read-out rotation (vstab_frame.readout_rotation)");
     }
-    // vstab_set_readout_warp(VSTAB_READOUT_PER_ROW): a frame with a read-out rotation on a handle whose warp has no rotation per row of its
-    // own -- a cubic or Lanczos handle, a calibrated one, or both (the formats were checked on entry; the quantised map was not chosen)
-    if (P.rot_bottom && H->readout_warp == VSTAB_READOUT_PER_ROW && (H->calibrated || resampled))
-        return vstab_warp_nv12_rs_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, H->calibrated ? H->dist32 : nullptr, mode, H->cfg.resample,
-                                     P.border_mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
-    // a calibrated handle: vstab_warp_nv12_dist_ex with the handle's resampler and the pull's border mode (INTER_LINEAR with the constant
-    // border: vstab_warp_nv12_dist, or the quantised map of an earlier frame).  A frame that carries a read-out rotation is consumed, as
-    // INTER_NEAREST consumes it below
-    if (H->calibrated) {
-        if (P.rot_bottom) return refuse_launch("a calibrated handle (vstab_set_input_calibration) warps frames without a read-out rotation");
-        if (P.cached)
-            return vstab_warp_nv12_mapped(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, H->qmap.p, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
-        return vstab_warp_nv12_dist_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, H->dist32, mode, H->cfg.resample, P.border_mode, out_format, P.dst, P.pitch_dst,
-                                       P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
-    }
-    if (border && !resampled)
-        return vstab_warp_nv12_border(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.border_mode, P.dst, P.pitch_dst, P.dst_uv,
-                                      P.pitch_dst_uv, ow, oh, H->stream);
-    if (resampled) {  // the cubic and Lanczos warps: the same two signatures, without and with a border mode
-        // (a frame that carries a read-out rotation can never be served: it is consumed, as INTER_NEAREST consumes it below, and the
-        //  profiler's event pair is taken back; the output format was checked on entry)
-        if (P.rot_bottom) return refuse_launch(std::string(resample_name(H->cfg.resample)) + " warps frames without a read-out rotation (vstab_frame.readout_rotation)");
-        const auto plain = lanczos4 ? vstab_warp_nv12_lanczos4 : vstab_warp_nv12_cubic;
-        const auto bordered = lanczos4 ? vstab_warp_nv12_lanczos4_border : vstab_warp_nv12_cubic_border;
-        if (border)
-            return bordered(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, out_format, P.border_mode, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
-        return plain(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
-    }
-    if (H->cfg.interpolation == 0) {
+    if (H->cfg.interpolation == 0) {  // (vstab_create, vstab_set_*: such a handle has no resampler, lens, border mode or keep pull)
         if (out_format != VSTAB_OUT_BGR8 || P.rot_bottom) return refuse_launch("INTER_NEAREST emits 8-bit BGR frames without a read-out rotation");
         return vstab_warp_nv12_nearest_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, P.dst, P.pitch_dst, ow, oh, H->stream);
     }
-    if (P.cached)
-        return vstab_warp_nv12_mapped(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, H->qmap.p, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
-    if (P.rot_bottom)
-        return vstab_warp_nv12_rs(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, P.rot_bottom, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh,
-                                  H->stream);
-    return vstab_warp_nv12_ex(S.y, S.pitch_y, S.uv, S.pitch_uv, w, h, P.p, mode, out_format, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+    static const float no_params[17] = {0};
+    WarpRequest q = {.e = ENTRY_EX, .y = S.y, .pitch_y = S.pitch_y, .uv = S.uv, .pitch_uv = S.pitch_uv, .sw = w, .sh = h, .params = P.p, .rot_bottom = P.rot_bottom,
+                     .map_mode = mode, .out_format = out_format, .dst = P.dst, .pitch_dst = P.pitch_dst, .dst_uv = P.dst_uv, .pitch_dst_uv = P.pitch_dst_uv,
+                     .dw = ow, .dh = oh, .stream = H->stream};
+    if (P.keep) {  // (refuse_keep: INTER_LINEAR, constant border, ideal lens)
+        q.e = ENTRY_KEEP, q.keep = true;
+        q.prev = P.keep->prev, q.pitch_prev = P.keep->pitch_prev, q.prev_uv = P.keep->prev_uv, q.pitch_prev_uv = P.keep->pitch_prev_uv;
+        return warp_nv12(q);
+    }
+    q.resample = H->cfg.resample, q.border_mode = P.border_mode;
+    if (H->pinhole) q.e = ENTRY_PINHOLE, q.pinhole = H->pdist32;
+    else if (P.rot_bottom && (H->calibrated || resampled)) q.e = ENTRY_RS_EX, q.dist = H->calibrated ? H->dist32 : nullptr;
+    else if (P.cached) q.e = ENTRY_MAPPED, q.params = no_params, q.qmap = H->qmap.p, q.qpitch = (ow + 3) & ~3, q.map_mode = VSTAB_MAP_CREATEMAP_CL;  // (the map is written down, the lens with it)
+    else if (H->calibrated) q.e = ENTRY_DIST_EX, q.dist = H->dist32;
+    else if (resampled) q.e = lanczos4 ? (border ? ENTRY_LANCZOS4_BORDER : ENTRY_LANCZOS4) : (border ? ENTRY_CUBIC_BORDER : ENTRY_CUBIC);
+    else if (border) q.e = ENTRY_BORDER;
+    else if (P.rot_bottom) q.e = ENTRY_RS;
+    return warp_nv12(q);
 }
 
 // 6. vstab_config.debug: a marker on every feature tracked into the frame (marker_pts holds MARKER_SETS rotating sets of MARKER_CAP centres)

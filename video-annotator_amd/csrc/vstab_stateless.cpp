@@ -208,7 +208,7 @@ vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const void *next,
 static vstab_status estimate_rotation_impl(const std::string &name, const float *prev_xy, const float *cur_xy, int n, const double K_in[9], const double K_out[9],
                                            const double *D, uint64_t seed, double R[9], int *inliers, bool in_fish = true) {
     if ((n > 0 && (!prev_xy || !cur_xy)) || n < 0 || !K_in || !K_out || !R || !inliers) return fail(VSTAB_ERR_INVALID, name + ": bad argument");
-    if (D) VSTAB_TRY(in_fish ? check_distortion(name, D) : check_pinhole_distortion(name, D));
+    if (D) VSTAB_TRY(in_fish ? check_distortion(name.c_str(), D) : check_pinhole_distortion(name.c_str(), D));
     Mat3 ki, ko, r;
     std::memcpy(ki.m, K_in, sizeof(ki.m)), std::memcpy(ko.m, K_out, sizeof(ko.m));
     Pcg32 rng(seed);

@@ -5,6 +5,7 @@
 #include "vstab_pipeline.hpp"
 #include "vstab_track_host.hpp"
 #include "vstab_warp_bands.hpp"
+#include "vstab_warp_request.hpp"
 
 using namespace vstab;
 
@@ -253,6 +254,18 @@ __attribute__((visibility("default"))) int vstabx_band_cache_run(const float *pa
         o[17] = ta.tiles_x, o[18] = (int)grid;
     }
     counts[0] = cache.hits, counts[1] = cache.misses, counts[2] = (long)cache.entries.size();
+    return VSTAB_OK;
+}
+
+// The routing of the 8-bit NV12 warps (warp_route, vstab_warp_request.hpp; tests/test_warp_routes_cpu.py), no device needed.  lens: 0 ideal,
+// 1 fisheye coefficients, 2 pinhole coefficients, 3 pinhole coefficients all zero; border_entry: 0 the entry point has no border mode, 1 it
+// exists for its border kernels, 2 the border mode is an option beside a resampler; rs, keep, qmap: 0 / 1.  out = {family (0: no route),
+// argument block, kernel mode tag}.
+__attribute__((visibility("default"))) int vstabx_warp_route(int map_mode, int lens, int rs, int resample, int border_entry, int border_mode, int out_format, int keep,
+                                                              int qmap, int *out) {
+    if (!out) return fail(VSTAB_ERR_INVALID, "vstabx_warp_route: bad argument");
+    const WarpRoute r = warp_route(map_mode, lens, rs != 0, resample, border_entry, border_mode, out_format, keep != 0, qmap != 0);
+    out[0] = r.family, out[1] = r.block, out[2] = r.mode;
     return VSTAB_OK;
 }
 

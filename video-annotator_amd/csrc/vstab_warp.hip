@@ -1,6 +1,7 @@
-// vstab_warp.hip -- the bilinear NV12 warp's C entry points for gfx950 (MI355X): their argument checks, the choice between the direct-gather
-// kernel, the fused tile kernel (vstab_warp_fused.hip) and the plane-wise kernel (vstab_warp_planar.hip), and the two direct-gather
-// kernels themselves, k_warp_nv12_bgr and k_warp_nearest.  Compiled with -ffp-contract=off.
+// vstab_warp.hip -- the 8-bit NV12 warps' one host path for gfx950 (MI355X), warp_nv12: a WarpRequest checked, routed and launched; the
+// bilinear entry points' own argument checks and their choice between the direct-gather kernel, the fused tile kernel
+// (vstab_warp_fused.hip) and the plane-wise kernel (vstab_warp_planar.hip); the C entry points that are not a resampler's, a border's or
+// the keep-edge warp's; and the two direct-gather kernels themselves, k_warp_nv12_bgr and k_warp_nearest.  Compiled with -ffp-contract=off.
 //
 // HBM-bound gather work (no MFMA): coalesced wide stores, enough workgroups to fill 256 CUs, the map in registers.
 #include <cstdlib>
@@ -95,51 +96,48 @@ __global__ void __launch_bounds__(256) k_warp_nearest(WarpArgs a) {
 
 namespace {
 
-// The arguments of vstab_warp_nv12_ex / _rs / _mapped, checked, into the kernel argument; every message under vstab_warp_nv12 but the
+// A request of vstab_warp_nv12_ex / _rs / _mapped, checked, into the kernel argument; every message under vstab_warp_nv12 but the
 // per-row rule.  check_warp_nv12 (vstab_warp_host.hpp) makes the same checks under the caller's name, with a narrower output format.
-vstab_status check_warp_bilinear(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
-                                 const float *rot_bottom, int map_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv,
-                                 int dw, int dh, WarpArgs &a) {
-    if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: null pointer");
-    if (sw <= 0 || sh <= 0 || (sw & 1) || (sh & 1) || sw > 32767 || sh > 32767)
+vstab_status check_warp_bilinear(const WarpRequest &q, WarpArgs &a) {
+    if (!q.y || !q.uv || !q.dst || !q.params) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: null pointer");
+    if (q.sw <= 0 || q.sh <= 0 || (q.sw & 1) || (q.sh & 1) || q.sw > 32767 || q.sh > 32767)
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: source must be even-sized and <= 32767");
-    if (dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767)
+    if (q.dw <= 0 || q.dh <= 0 || q.dw > 32767 || q.dh > 32767)
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: output size must be in [1, 32767]");
-    if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: unknown map mode");
-    if (out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12 && out_format != VSTAB_OUT_NV12_PLANAR)
+    if (q.map_mode < VSTAB_MAP_CREATEMAP_CL || q.map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: unknown map mode");
+    if (q.out_format != VSTAB_OUT_BGR8 && q.out_format != VSTAB_OUT_NV12 && q.out_format != VSTAB_OUT_NV12_PLANAR)
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: unknown output format");
-    const bool nv12_out = out_format != VSTAB_OUT_BGR8;
-    if (pitch_y < (size_t)sw || pitch_uv < (size_t)sw || pitch_dst < (size_t)dw * (nv12_out ? 1 : 3))
+    const bool nv12_out = q.out_format != VSTAB_OUT_BGR8;
+    if (q.pitch_y < (size_t)q.sw || q.pitch_uv < (size_t)q.sw || q.pitch_dst < (size_t)q.dw * (nv12_out ? 1 : 3))
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: pitch smaller than row");
-    if (nv12_out && (!dst_uv || pitch_dst_uv < (size_t)((dw + 1) / 2) * 2))
+    if (nv12_out && (!q.dst_uv || q.pitch_dst_uv < (size_t)((q.dw + 1) / 2) * 2))
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: NV12 output needs a chroma plane of 2*ceil(width/2) bytes per row");
-    if (!ptr_aligned(uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: chroma plane must be 2-B aligned");
-    if (rot_bottom && !map_mode_fish_to_pinhole(map_mode))
+    if (!ptr_aligned(q.uv, 2) || q.pitch_uv % 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: chroma plane must be 2-B aligned");
+    if (q.rot_bottom && !map_mode_fish_to_pinhole(q.map_mode))
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_rs: the per-row warp exists for the fisheye -> pinhole modes (0, 1, 5) only");
-    fill_warp_args(a, y, pitch_y, uv, pitch_uv, sw, sh, params, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh);
+    fill_warp_args(a, q, true);
     return VSTAB_OK;
 }
 
-// Checked arguments on the kernel that serves them: the plane-wise kernel for VSTAB_OUT_NV12_PLANAR, else the direct-gather kernel or the
-// fused tile kernel.  qmap: vstab_warp_nv12_mapped's quantised map, rot_bottom: vstab_warp_nv12_rs's rotation of the last row, dist: the
-// input lens's k1..k4 (vstab_warp_nv12_dist); null each where the entry point has none.
-vstab_status launch_warp_bilinear(const WarpArgs &a, const float params[17], int map_mode, int out_format, const void *qmap, int qpitch,
-                                  const float *rot_bottom, const float *dist, void *stream) {
-    const bool planar = out_format == VSTAB_OUT_NV12_PLANAR;
-    const bool nv12_out = out_format == VSTAB_OUT_NV12 || planar;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+// A checked request on the bilinear kernel that serves it (WARP_PLANAR, WARP_FUSED): the plane-wise kernel for VSTAB_OUT_NV12_PLANAR, else
+// the fused tile kernel or, for planes of 4 GiB and more, the direct-gather kernel.  What only the planes decide is refused here, under
+// the fixed name vstab_warp_nv12, and with it the one checked request without a route: a quantised map with plane-wise output.
+vstab_status launch_warp_bilinear(const WarpArgs &a, const WarpRequest &q) {
+    const bool planar = q.planar();
+    const bool nv12_out = q.out_format == VSTAB_OUT_NV12 || planar;
+    hipStream_t st = static_cast<hipStream_t>(q.stream);
     // a chroma plane of 4 GiB or more (staged_offsets32: rows without chroma) is sampled from global memory with 64-bit addresses: the direct
     // kernel in plain mode, the gather path of the tiled kernels otherwise
     const StagedOffsets32 off32 = staged_offsets32(a.pitch_y, a.pitch_uv, a.sh);
     const bool small_pitch = off32.rows, stage32 = off32.chroma;
-    const bool plain = map_mode == VSTAB_MAP_CREATEMAP_CL && !nv12_out && !qmap && !rot_bottom;
+    const bool plain = q.map_mode == VSTAB_MAP_CREATEMAP_CL && !nv12_out && !q.qmap && !q.rot_bottom;
     if (!plain && !small_pitch) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: source pitch too large for this mode");
     if (planar) {  // the plane-wise warp: its own kernel (vstab_warp_planar.hip); the map is always evaluated
-        if (qmap) return fail(VSTAB_ERR_UNSUPPORTED, "vstab_warp_nv12_mapped: the quantised map holds no chroma positions -- VSTAB_OUT_NV12_PLANAR goes through vstab_warp_nv12_ex");
+        if (q.qmap) return fail(VSTAB_ERR_UNSUPPORTED, "vstab_warp_nv12_mapped: the quantised map holds no chroma positions -- VSTAB_OUT_NV12_PLANAR goes through vstab_warp_nv12_ex");
         if (a.sw < 16 || a.sh < 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: the plane-wise warp needs a source of at least 16 x 2");
         const bool src16 = stage32 && ptr_aligned(a.y, 16) && ptr_aligned(a.uv, 16) && a.pitch_y % 16 == 0 && a.pitch_uv % 16 == 0;  // 16-byte staging loads
         const bool dst16 = ptr_aligned(a.dst, 16) && ptr_aligned(a.dst_uv, 16) && a.pitch_dst % 16 == 0 && a.pitch_dst_uv % 16 == 0;
-        return launch_warp_planar(a, params, map_mode, 8, 0, src16, dst16, rot_bottom, st, dist);
+        return launch_warp_planar(a, q.params, q.map_mode, 8, 0, src16, dst16, q.rot_bottom, st, q.dist);
     }
     const bool vec_ok = ptr_aligned(a.dst, 4) && a.pitch_dst % 4 == 0 && (!nv12_out || (ptr_aligned(a.dst_uv, 4) && a.pitch_dst_uv % 4 == 0));
     const bool src_vec_ok = stage32 && ptr_aligned(a.y, 8) && ptr_aligned(a.uv, 8) && a.pitch_y % 8 == 0 && a.pitch_uv % 8 == 0;  // 8-byte staging loads
@@ -148,38 +146,35 @@ vstab_status launch_warp_bilinear(const WarpArgs &a, const float params[17], int
     static const int variant = getenv("VSTAB_WARP_VARIANT") ? atoi(getenv("VSTAB_WARP_VARIANT")) : 2;
     direct = direct || (plain && variant == 1);
 #endif
-    if (!direct) return launch_warp_fused(a, params, map_mode, nv12_out, src_vec_ok, vec_ok, qmap, qpitch, rot_bottom, st, dist);
+    if (!direct) return launch_warp_fused(a, q.params, q.map_mode, nv12_out, src_vec_ok, vec_ok, q.qmap, q.qpitch, q.rot_bottom, st, q.dist);
     // planes of 4 GiB and more: the direct-gather kernel with 64-bit addressing
     hipLaunchKernelGGL(k_warp_nv12_bgr, dim3(div_up(a.dw, WARP_TILE_W), div_up(a.dh, WARP_TILE_H)), dim3(16, 16), 0, st, a, (int)vec_ok);
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }
 
-// vstab_warp_nv12_dist_ex, and vstab_warp_nv12_dist as its default resampler with the constant border (two checks that cannot fire then),
-// each under its own name n.  The order: check_warp_nv12's checks -- handed a mode it accepts, so that every mode but 1 and 2, known or
-// not, gets the one message behind them --, the resampler, the map mode, the coefficients.
-vstab_status warp_dist(const std::string &n, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
-                       const float dist[4], int map_mode, int resample, int border_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv,
-                       size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    if (!dist) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
-    const bool fish_in = map_mode_takes_distortion(map_mode);
-    CubicArgs c;
-    VSTAB_TRY(check_warp_nv12(n, "the distorted-lens warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr,
-                              fish_in ? map_mode : (int)VSTAB_MAP_FISH_TO_RECT, out_format, &border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, c,
-                              dist));
-    if (resample != VSTAB_RESAMPLE_DEFAULT && resample != VSTAB_RESAMPLE_CUBIC && resample != VSTAB_RESAMPLE_LANCZOS4)
-        return fail(VSTAB_ERR_INVALID, n + ": resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)");
-    if (!fish_in) return fail(VSTAB_ERR_INVALID, n + ": distortion belongs to a fisheye input (map modes 1 and 2)");
-    VSTAB_TRY(check_distortion(n, dist));
-    if (resample == VSTAB_RESAMPLE_CUBIC) return launch_warp_cubic_dist(c, map_mode, out_format, border_mode, stream);
-    if (resample == VSTAB_RESAMPLE_LANCZOS4) return launch_warp_lanczos4_dist(c, map_mode, out_format, border_mode, stream);
-    if (border_mode != VSTAB_BORDER_CONSTANT) return launch_warp_border_dist(c, map_mode, out_format, border_mode, stream);
-    // no check_warp_bilinear: check_warp_nv12 made the same checks with a narrower output format (and there is no rotation per row), so
-    // whatever passed it passes those, and c.w is the kernel argument they would fill
-    return launch_warp_bilinear(c.w, params, map_mode, out_format, nullptr, 0, nullptr, dist, stream);
-}
-
 }  // namespace
+
+// Every 8-bit NV12 warp: checked once, routed once (warp_route), launched once.  ba is the argument block of every family: the kernels
+// take it whole (ARGS_BORDER; ARGS_KEEP adds the history to it) or its ba.c (ARGS_CUBIC) or its ba.c.w (ARGS_WARP).
+vstab_status warp_nv12(const WarpRequest &q) {
+    BorderArgs ba;
+    if (q.e.who) VSTAB_TRY(check_warp_nv12(q, ba.c));
+    else VSTAB_TRY(check_warp_bilinear(q, ba.c.w));
+    bool in_place = false;
+    if (q.keep) VSTAB_TRY(check_keep_prev(q, in_place));
+    const WarpRoute r = warp_route(q);
+    fill_rolling_shutter(ba, q.params, q.rot_bottom, q.dh);
+    if (q.pinhole)
+        for (int k = 0; k < 5; k++) ba.pd[k] = q.pinhole[k];
+    switch (r.family) {
+        case WARP_BORDER: return launch_warp_border(ba, r, q.out_format, q.border_mode, q.stream);
+        case WARP_CUBIC: return launch_warp_cubic(ba, r, q.out_format, q.border_mode, q.stream);
+        case WARP_LANCZOS4: return launch_warp_lanczos4(ba, r, q.out_format, q.border_mode, q.stream);
+        case WARP_KEEP: return launch_warp_keep(ba, r, q, in_place);
+        default: return launch_warp_bilinear(ba.c.w, q);  // (WARP_NONE: refused there)
+    }
+}
 
 // Kernels of this translation unit are one code object, loaded by the runtime at the first launch of any of them.  Touching one of them
 // here (vstab_preload_kernels) moves that load to a moment the caller chooses.
@@ -198,18 +193,17 @@ extern "C" {
 vstab_status vstab_warp_nv12_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh,
                                 const float params[17], int map_mode, int out_format, void *dst, size_t pitch_dst,
                                 void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    WarpArgs a;
-    VSTAB_TRY(check_warp_bilinear(y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr, map_mode, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, a));
-    return launch_warp_bilinear(a, params, map_mode, out_format, nullptr, 0, nullptr, nullptr, stream);
+    return warp_nv12({.e = ENTRY_EX, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .map_mode = map_mode,
+                      .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw, .dh = dh, .stream = stream});
 }
 
 vstab_status vstab_warp_nv12_rs(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                 const float rot_bottom[9], int map_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv,
                                 size_t pitch_dst_uv, int dw, int dh, void *stream) {
     if (!rot_bottom) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_rs: null pointer");
-    WarpArgs a;
-    VSTAB_TRY(check_warp_bilinear(y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, a));
-    return launch_warp_bilinear(a, params, map_mode, out_format, nullptr, 0, rot_bottom, nullptr, stream);
+    return warp_nv12({.e = ENTRY_RS, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .rot_bottom = rot_bottom,
+                      .map_mode = map_mode, .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw,
+                      .dh = dh, .stream = stream});
 }
 
 vstab_status vstab_warp_nv12_mapped(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const void *qmap,
@@ -217,98 +211,44 @@ vstab_status vstab_warp_nv12_mapped(const void *y, size_t pitch_y, const void *u
                                     void *stream) {
     if (!qmap || !ptr_aligned(qmap, 16)) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_mapped: the quantised map must be a 16-byte aligned device buffer");
     static const float unused[17] = {0};
-    WarpArgs a;
-    VSTAB_TRY(check_warp_bilinear(y, pitch_y, uv, pitch_uv, sw, sh, unused, nullptr, VSTAB_MAP_CREATEMAP_CL, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv,
-                                  dw, dh, a));
-    return launch_warp_bilinear(a, unused, VSTAB_MAP_CREATEMAP_CL, out_format, qmap, (dw + 3) & ~3, nullptr, nullptr, stream);
+    return warp_nv12({.e = ENTRY_MAPPED, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = unused, .qmap = qmap,
+                      .qpitch = (dw + 3) & ~3, .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw,
+                      .dh = dh, .stream = stream});
 }
 
+// vstab_warp_nv12_dist is vstab_warp_nv12_dist_ex's default resampler with the constant border (two checks that cannot fire then), each
+// under its own name
 vstab_status vstab_warp_nv12_dist(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                   const float dist[4], int map_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv,
                                   int dw, int dh, void *stream) {
-    return warp_dist("vstab_warp_nv12_dist", y, pitch_y, uv, pitch_uv, sw, sh, params, dist, map_mode, VSTAB_RESAMPLE_DEFAULT, VSTAB_BORDER_CONSTANT,
-                     out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
+    return warp_nv12({.e = ENTRY_DIST, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .dist = dist,
+                      .map_mode = map_mode, .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw,
+                      .dh = dh, .stream = stream});
 }
 
 vstab_status vstab_warp_nv12_dist_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                      const float dist[4], int map_mode, int resample, int border_mode, int out_format, void *dst, size_t pitch_dst,
                                      void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    return warp_dist("vstab_warp_nv12_dist_ex", y, pitch_y, uv, pitch_uv, sw, sh, params, dist, map_mode, resample, border_mode, out_format, dst, pitch_dst,
-                     dst_uv, pitch_dst_uv, dw, dh, stream);
+    return warp_nv12({.e = ENTRY_DIST_EX, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .dist = dist,
+                      .map_mode = map_mode, .resample = resample, .border_mode = border_mode, .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst,
+                      .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw, .dh = dh, .stream = stream});
 }
 
 vstab_status vstab_warp_nv12_rs_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                    const float *rot_bottom, const float *dist, int map_mode, int resample, int border_mode, int out_format, void *dst,
                                    size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    const std::string n = "vstab_warp_nv12_rs_ex";
-    BorderArgs ba;
-    VSTAB_TRY(check_warp_nv12(n, "the per-row warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, out_format, &border_mode, dst, pitch_dst,
-                              dst_uv, pitch_dst_uv, dw, dh, ba.c, dist));
-    if (resample != VSTAB_RESAMPLE_DEFAULT && resample != VSTAB_RESAMPLE_CUBIC && resample != VSTAB_RESAMPLE_LANCZOS4)
-        return fail(VSTAB_ERR_INVALID, n + ": resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)");
-    if (dist) {
-        if (!map_mode_takes_distortion(map_mode)) return fail(VSTAB_ERR_INVALID, n + ": distortion belongs to a fisheye input (map modes 1 and 2)");
-        VSTAB_TRY(check_distortion(n, dist));
-    }
-    const bool constant = border_mode == VSTAB_BORDER_CONSTANT, cubic = resample == VSTAB_RESAMPLE_CUBIC;
-    // what an older entry point serves is that entry point's
-    if (!rot_bottom && dist)
-        return vstab_warp_nv12_dist_ex(y, pitch_y, uv, pitch_uv, sw, sh, params, dist, map_mode, resample, border_mode, out_format, dst, pitch_dst, dst_uv,
-                                       pitch_dst_uv, dw, dh, stream);
-    if (resample == VSTAB_RESAMPLE_DEFAULT && !dist) {
-        if (!rot_bottom && constant)
-            return vstab_warp_nv12_ex(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
-        return vstab_warp_nv12_border(y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, out_format, border_mode, dst, pitch_dst, dst_uv,
-                                      pitch_dst_uv, dw, dh, stream);
-    }
-    if (!rot_bottom) {
-        if (constant)
-            return (cubic ? vstab_warp_nv12_cubic : vstab_warp_nv12_lanczos4)(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, dst, pitch_dst,
-                                                                              dst_uv, pitch_dst_uv, dw, dh, stream);
-        return (cubic ? vstab_warp_nv12_cubic_border : vstab_warp_nv12_lanczos4_border)(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format,
-                                                                                        border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
-    }
-    // new ground: a rotation per row under the cubic and Lanczos resamplers, and under every resampler through a calibrated lens (map mode 1:
-    // rot_bottom admits modes 0, 1 and 5, dist modes 1 and 2)
-    fill_rolling_shutter(ba, params, rot_bottom, dh);
-    if (resample == VSTAB_RESAMPLE_DEFAULT) return launch_warp_border(ba, map_mode, true, true, out_format, border_mode, stream);
-    return (cubic ? launch_warp_cubic_rs : launch_warp_lanczos4_rs)(ba, map_mode, dist != nullptr, out_format, border_mode, stream);
+    return warp_nv12({.e = ENTRY_RS_EX, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .rot_bottom = rot_bottom,
+                      .dist = dist, .map_mode = map_mode, .resample = resample, .border_mode = border_mode, .out_format = out_format, .dst = dst,
+                      .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw, .dh = dh, .stream = stream});
 }
 
-// A rectilinear input lens with OpenCV's (k1, k2, p1, p2, k3): include/vstab.h, "Pinhole lens distortion".  The order: dist, check_warp_nv12's
-// checks -- handed a mode it accepts, so that every mode but 3 and 4, known or not, gets the one message behind them --, the resampler, the
-// map mode, the coefficients.  All zero: the older entry point's launch.
+// A rectilinear input lens with OpenCV's (k1, k2, p1, p2, k3): include/vstab.h, "Pinhole lens distortion"
 vstab_status vstab_warp_nv12_pinhole(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                      const float dist[5], int map_mode, int resample, int border_mode, int out_format, void *dst, size_t pitch_dst,
                                      void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    const std::string n = "vstab_warp_nv12_pinhole";
-    if (!dist) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
-    const bool rect_in = map_mode_takes_pinhole(map_mode);
-    BorderArgs ba;
-    VSTAB_TRY(check_warp_nv12(n, "the pinhole-lens warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr, rect_in ? map_mode : (int)VSTAB_MAP_RECT_TO_RECT,
-                              out_format, &border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, ba.c));
-    if (resample != VSTAB_RESAMPLE_DEFAULT && resample != VSTAB_RESAMPLE_CUBIC && resample != VSTAB_RESAMPLE_LANCZOS4)
-        return fail(VSTAB_ERR_INVALID, n + ": resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)");
-    if (!rect_in) return fail(VSTAB_ERR_INVALID, n + ": pinhole distortion belongs to a rectilinear input (map modes 3 and 4)");
-    VSTAB_TRY(check_pinhole_distortion(n, dist));
-    const bool constant = border_mode == VSTAB_BORDER_CONSTANT, cubic = resample == VSTAB_RESAMPLE_CUBIC;
-    if (dist[0] == 0.0f && dist[1] == 0.0f && dist[2] == 0.0f && dist[3] == 0.0f && dist[4] == 0.0f) {  // the ideal pinhole: what served it before
-        if (resample == VSTAB_RESAMPLE_DEFAULT) {
-            if (constant)
-                return vstab_warp_nv12_ex(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
-            return vstab_warp_nv12_border(y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr, map_mode, out_format, border_mode, dst, pitch_dst, dst_uv,
-                                          pitch_dst_uv, dw, dh, stream);
-        }
-        if (constant)
-            return (cubic ? vstab_warp_nv12_cubic : vstab_warp_nv12_lanczos4)(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format, dst, pitch_dst,
-                                                                              dst_uv, pitch_dst_uv, dw, dh, stream);
-        return (cubic ? vstab_warp_nv12_cubic_border : vstab_warp_nv12_lanczos4_border)(y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format,
-                                                                                        border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
-    }
-    fill_rolling_shutter(ba, params, nullptr, dh);
-    for (int k = 0; k < 5; k++) ba.pd[k] = dist[k];
-    if (resample == VSTAB_RESAMPLE_DEFAULT) return launch_warp_border_pinhole(ba, map_mode, out_format, border_mode, stream);
-    return (cubic ? launch_warp_cubic_pinhole : launch_warp_lanczos4_pinhole)(ba, map_mode, out_format, border_mode, stream);
+    return warp_nv12({.e = ENTRY_PINHOLE, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .pinhole = dist,
+                      .map_mode = map_mode, .resample = resample, .border_mode = border_mode, .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst,
+                      .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw, .dh = dh, .stream = stream});
 }
 
 vstab_status vstab_warp_nv12_nearest_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
@@ -337,8 +277,8 @@ vstab_status vstab_warp_nv12_nearest(const void *y, size_t pitch_y, const void *
 vstab_status vstab_warp_nv12_bgr(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh,
                                  const float params[17], void *dst, size_t pitch_dst, int dw, int dh,
                                  void *stream) {
-    return vstab_warp_nv12_ex(y, pitch_y, uv, pitch_uv, sw, sh, params, VSTAB_MAP_CREATEMAP_CL, VSTAB_OUT_BGR8, dst, pitch_dst,
-                              nullptr, 0, dw, dh, stream);
+    return warp_nv12({.e = ENTRY_EX, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .dst = dst,
+                      .pitch_dst = pitch_dst, .dst_uv = nullptr, .pitch_dst_uv = 0, .dw = dw, .dh = dh, .stream = stream});
 }
 
 }  // extern "C"

@@ -132,49 +132,23 @@ vstab_status preload_border_kernels() {
     return VSTAB_OK;
 }
 
-// k_warp_border of checked arguments on its grid.  rs: a rotation per output row, served (and checked) for map modes 0, 1 and 5 only.
-// dist: ba.c.p32.d holds the input lens's coefficients.  Without a rotation per row: map modes 1 and 2, a non-constant border (INTER_LINEAR
-// with the constant border and a distorted lens is k_warp_fused / k_warp_planar, vstab_warp_nv12_dist).  With one (vstab_warp_nv12_rs_ex):
-// map mode 1 as MAP_RS_FISHD_TO_RECT, every border mode.
-vstab_status launch_warp_border(const BorderArgs &ba, int map_mode, bool dist, bool rs, int out_format, int border_mode, void *stream) {
-    if (dist && rs) {
+// k_warp_border of a route (WARP_BORDER) on its grid.  What is instantiated is what is served: the map modes 0 .. 5 with every border mode,
+// and with a rotation per output row for modes 0, 1 and 5; a calibrated fisheye lens (ba.c.p32.d) with one rotation under a non-constant
+// border (INTER_LINEAR with the constant border is k_warp_fused / k_warp_planar) and, as MAP_RS_FISHD_TO_RECT, with a rotation per row under
+// every border mode; a rectilinear lens (ba.pd) with one rotation under every border mode.
+vstab_status launch_warp_border(const BorderArgs &ba, const WarpRoute &r, int out_format, int border_mode, void *stream) {
+    with_kernel_mode(route_kernel_mode(r.mode), [&](auto mode) {
         with_border_mode(border_mode, [&](auto border) {
             with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
-                launch_tiles(k_warp_border<MAP_RS_FISHD_TO_RECT, decltype(planar)::value, true, decltype(border)::value>, ba, ba.c.w.dw, ba.c.w.dh, stream);
-            });
-        });
-        VSTAB_HIP_TRY(hipGetLastError());
-        return VSTAB_OK;
-    }
-    with_map_mode_or_dist(map_mode, dist, [&](auto mode) {
-        with_border_mode(border_mode, [&](auto border) {
-            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
-                with_bool(rs, [&](auto rs_c) {
+                with_bool(map_mode_is_rs(r.mode), [&](auto rs_c) {
                     constexpr int MODE = decltype(mode)::value, BORDER = decltype(border)::value;
                     constexpr bool RS = decltype(rs_c)::value;
-                    if constexpr (ModeTraits<MODE>::dist ? !RS && BORDER != VSTAB_BORDER_CONSTANT : !RS || map_mode_fish_to_pinhole(MODE))
-                        launch_tiles(k_warp_border<MODE, decltype(planar)::value, RS, BORDER>, ba, ba.c.w.dw, ba.c.w.dh, stream);
+                    constexpr bool served = MODE == MAP_RS_FISHD_TO_RECT ? RS
+                                            : ModeTraits<MODE>::rectd    ? !RS
+                                            : ModeTraits<MODE>::dist     ? !RS && BORDER != VSTAB_BORDER_CONSTANT
+                                                                         : MODE <= MAP_CREATEMAP_CL_OPENCL && (!RS || map_mode_fish_to_pinhole(MODE));
+                    if constexpr (served) launch_tiles(k_warp_border<MODE, decltype(planar)::value, RS, BORDER>, ba, ba.c.w.dw, ba.c.w.dh, stream);
                 });
-            });
-        });
-    });
-    VSTAB_HIP_TRY(hipGetLastError());
-    return VSTAB_OK;
-}
-
-vstab_status launch_warp_border_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream) {
-    BorderArgs ba;
-    ba.c = c;
-    fill_rolling_shutter(ba, nullptr, nullptr, c.w.dh);
-    return launch_warp_border(ba, map_mode, true, false, out_format, border_mode, stream);
-}
-
-// INTER_LINEAR through a rectilinear lens with ba.pd (vstab_warp_nv12_pinhole), every border mode, BORDER_CONSTANT included
-vstab_status launch_warp_border_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream) {
-    with_pinhole_mode(map_mode, [&](auto mode) {
-        with_border_mode(border_mode, [&](auto border) {
-            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
-                launch_tiles(k_warp_border<decltype(mode)::value, decltype(planar)::value, false, decltype(border)::value>, ba, ba.c.w.dw, ba.c.w.dh, stream);
             });
         });
     });
@@ -210,12 +184,9 @@ vstab_status vstab_remap_bilinear_border(const void *src, size_t pitch_src, int 
 vstab_status vstab_warp_nv12_border(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
                                     const float *rot_bottom, int map_mode, int out_format, int border_mode, void *dst, size_t pitch_dst, void *dst_uv,
                                     size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    BorderArgs ba;
-    const vstab_status st = check_warp_nv12("vstab_warp_nv12_border", "the border warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode,
-                                            out_format, &border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, ba.c);
-    if (st != VSTAB_OK) return st;
-    fill_rolling_shutter(ba, params, rot_bottom, dh);
-    return launch_warp_border(ba, map_mode, false, rot_bottom != nullptr, out_format, border_mode, stream);
+    return warp_nv12({.e = ENTRY_BORDER, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .rot_bottom = rot_bottom,
+                      .map_mode = map_mode, .border_mode = border_mode, .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst, .dst_uv = dst_uv,
+                      .pitch_dst_uv = pitch_dst_uv, .dw = dw, .dh = dh, .stream = stream});
 }
 
 }  // extern "C"

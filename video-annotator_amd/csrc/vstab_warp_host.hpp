@@ -1,8 +1,9 @@
 // vstab_warp_host.hpp -- the host side of every warp translation unit (vstab_warp.hip, vstab_warp_fused.hip, vstab_warp_planar.hip,
 // vstab_warp_p010.hip, vstab_warp_cubic.hip, vstab_warp_lanczos4.hip, vstab_warp_border.hip) and of vstab_plane_ops.hip: each fact once.  The alignment predicate, the
 // kernel arguments from the C arguments (MapParams, MapParams32, WarpArgs, the rolling-shutter pair, FusedArgs' common part), the conditions
-// for 32-bit staged offsets, the dispatch of a run-time mode to a template argument, the launch with a profiler's event pair, and the
-// resamplers' argument checks (every one before any launch, in one order, each message under the entry point's own name).
+// for 32-bit staged offsets, the dispatch of a run-time mode to a template argument, the launch with a profiler's event pair, the
+// argument checks of a WarpRequest (vstab_warp_request.hpp) and of the stateless remaps (every one before any launch, in one order, each
+// message under the entry point's own name), and the resamplers' launch of a route.
 #pragma once
 #include <hip/hip_ext.h>
 
@@ -10,6 +11,7 @@
 
 #include "vstab_internal.hpp"
 #include "vstab_resample.hpp"
+#include "vstab_warp_request.hpp"
 
 namespace vstab {
 
@@ -104,12 +106,30 @@ void with_dist_mode(int map_mode, F &&f) {
     if (map_mode == VSTAB_MAP_FISH_TO_RECT) f(mode_constant<MAP_FISHD_TO_RECT>{});
     else f(mode_constant<MAP_FISHD_TO_FISH>{});
 }
-// a checked mode of either kind: dist (the coefficients are in MapParams32::d): its MAP_FISHD_* form
+// The one dispatch of the kernels that are launched for a route: the mode tag the routing chose (warp_route; kernel_mode_tag for the map
+// kernels of vstab_plane_ops.hip) -> f(mode_constant<tag>).  f is instantiated for every tag: each launcher guards its kernel with
+// `if constexpr` on the tags it serves, so that no other combination is instantiated.
 template <typename F>
-void with_map_mode_or_dist(int map_mode, bool dist, F &&f) {
-    if (dist) with_dist_mode(map_mode, f);
-    else with_map_mode(map_mode, f);
+void with_kernel_mode(int mode, F &&f) {
+    switch (mode) {
+        case MAP_CREATEMAP_CL: f(mode_constant<MAP_CREATEMAP_CL>{}); break;
+        case MAP_FISH_TO_RECT: f(mode_constant<MAP_FISH_TO_RECT>{}); break;
+        case MAP_FISH_TO_FISH: f(mode_constant<MAP_FISH_TO_FISH>{}); break;
+        case MAP_RECT_TO_RECT: f(mode_constant<MAP_RECT_TO_RECT>{}); break;
+        case MAP_RECT_TO_FISH: f(mode_constant<MAP_RECT_TO_FISH>{}); break;
+        case MAP_CREATEMAP_CL_OPENCL: f(mode_constant<MAP_CREATEMAP_CL_OPENCL>{}); break;
+        case MAP_RS_CREATEMAP_CL: f(mode_constant<MAP_RS_CREATEMAP_CL>{}); break;
+        case MAP_RS_FISH_TO_RECT: f(mode_constant<MAP_RS_FISH_TO_RECT>{}); break;
+        case MAP_RS_CREATEMAP_CL_OPENCL: f(mode_constant<MAP_RS_CREATEMAP_CL_OPENCL>{}); break;
+        case MAP_FISHD_TO_RECT: f(mode_constant<MAP_FISHD_TO_RECT>{}); break;
+        case MAP_FISHD_TO_FISH: f(mode_constant<MAP_FISHD_TO_FISH>{}); break;
+        case MAP_RS_FISHD_TO_RECT: f(mode_constant<MAP_RS_FISHD_TO_RECT>{}); break;
+        case MAP_RECTD_TO_RECT: f(mode_constant<MAP_RECTD_TO_RECT>{}); break;
+        default: f(mode_constant<MAP_RECTD_TO_FISH>{}); break;
+    }
 }
+// the tags of one rotation per frame through an ideal or a calibrated fisheye lens: the map modes themselves and their MAP_FISHD_* forms
+constexpr bool mode_plain_or_dist(int mode) { return mode <= MAP_CREATEMAP_CL_OPENCL || mode == MAP_FISHD_TO_RECT || mode == MAP_FISHD_TO_FISH; }
 // the fisheye -> pinhole maps (modes 0, 1, 5): the only ones that take a rotation per output row (so the only ones with a MAP_RS_*
 // form), and the only ones the 10-bit tiled kernels serve.  Asked of the public VSTAB_MAP_* values by the argument checks and of the
 // kernels' MAP_* template values (a base mode: map_mode_base) by the launchers: the two enumerations agree on 0 .. 5, and the internal
@@ -159,32 +179,54 @@ void launch_tiles(Kernel kernel, const Args &args, int dw, int dh, void *stream)
     launch_kernel(kernel, dim3(div_up(dw, RESAMPLE_TW), div_up(dh, RESAMPLE_TH)), dim3(256), 0, static_cast<hipStream_t>(stream), args);
 }
 
-// The NV12 warps' arguments, checked, into the kernel argument.  who: the subject of the output-format message ("the cubic warp "; "").
-// rot_bottom: vstab_warp_nv12_border's rotation per output row, else null.  border_mode: null where the entry point has none.  dist: the
-// input lens's k1..k4 (vstab_warp_nv12_dist_ex, which checks them and the mode they belong to itself, behind these checks), else null.
-inline vstab_status check_warp_nv12(const std::string &n, const char *who, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh,
-                                    const float params[17], const float *rot_bottom, int map_mode, int out_format, const int *border_mode, void *dst,
-                                    size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh, CubicArgs &c, const float *dist = nullptr) {
-    if (!y || !uv || !dst || !params) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
-    if (sw <= 0 || sh <= 0 || (sw & 1) || (sh & 1) || sw > 32767 || sh > 32767)
-        return fail(VSTAB_ERR_INVALID, n + ": source must be even-sized and <= 32767");
-    if (dw <= 0 || dh <= 0 || dw > 32767 || dh > 32767) return fail(VSTAB_ERR_INVALID, n + ": output size must be in [1, 32767]");
-    if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return fail(VSTAB_ERR_INVALID, n + ": unknown map mode");
-    if (rot_bottom && !map_mode_fish_to_pinhole(map_mode))
-        return fail(VSTAB_ERR_INVALID, n + ": a rotation per output row (rot_bottom) is served for map modes 0, 1 and 5");
-    if (out_format != VSTAB_OUT_BGR8 && out_format != VSTAB_OUT_NV12_PLANAR)
-        return fail(VSTAB_ERR_INVALID, n + ": " + who + "emits VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR (NV12 through BGR is not served)");
-    if (border_mode && !border_mode_valid(*border_mode))
-        return fail(VSTAB_ERR_INVALID, n + ": border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)");
-    const bool planar = out_format == VSTAB_OUT_NV12_PLANAR;
-    if (pitch_y < (size_t)sw || pitch_uv < (size_t)sw || pitch_dst < (size_t)dw * (planar ? 1 : 3))
-        return fail(VSTAB_ERR_INVALID, n + ": pitch smaller than row");
-    if (planar && (!dst_uv || pitch_dst_uv < (size_t)((dw + 1) / 2) * 2))
-        return fail(VSTAB_ERR_INVALID, n + ": plane-wise output needs a chroma plane of 2*ceil(width/2) bytes per row");
-    if (!ptr_aligned(uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, n + ": chroma plane must be 2-B aligned");
-    fill_warp_args(c.w, y, pitch_y, uv, pitch_uv, sw, sh, params, dst, pitch_dst, planar ? dst_uv : nullptr, planar ? pitch_dst_uv : 0, dw, dh);
-    c.p32 = map_params32(params, dist);
+// The kernel argument of a request's planes.  chroma_out false: an output without a chroma plane (dst_uv null, whatever the caller passed).
+inline void fill_warp_args(WarpArgs &a, const WarpRequest &q, bool chroma_out) {
+    fill_warp_args(a, q.y, q.pitch_y, q.uv, q.pitch_uv, q.sw, q.sh, q.params, q.dst, q.pitch_dst, chroma_out ? q.dst_uv : nullptr, chroma_out ? q.pitch_dst_uv : 0,
+                   q.dw, q.dh);
+}
+
+// A request of every entry point but the bilinear ones (those: check_warp_bilinear, vstab_warp.hip), checked, into the kernel argument:
+// every check before any launch, in one order, each message under the entry point's own name.  The order: the planes; then the resampler,
+// the map mode of the lens and its coefficients.
+inline vstab_status check_warp_nv12(const WarpRequest &q, CubicArgs &c) {
+    const auto refuse = [&](const std::string &what) { return fail(VSTAB_ERR_INVALID, std::string(q.e.name) + ": " + what); };
+    // an entry point that exists for a lens needs its coefficients, and is checked here with a mode that passes, so that every mode but that
+    // lens's, known or not, gets the one message behind these checks
+    const bool fish_entry = q.e.lens == LENS_FISHEYE, rect_entry = q.e.lens == LENS_PINHOLE;
+    const bool lens_mode = fish_entry ? map_mode_takes_distortion(q.map_mode) : rect_entry ? map_mode_takes_pinhole(q.map_mode) : true;
+    const int map_mode = lens_mode ? q.map_mode : (int)VSTAB_MAP_FISH_TO_RECT;
+    if (!q.y || !q.uv || !q.dst || !q.params || (fish_entry && !q.dist) || (rect_entry && !q.pinhole)) return refuse("null pointer");
+    if (q.sw <= 0 || q.sh <= 0 || (q.sw & 1) || (q.sh & 1) || q.sw > 32767 || q.sh > 32767) return refuse("source must be even-sized and <= 32767");
+    if (q.dw <= 0 || q.dh <= 0 || q.dw > 32767 || q.dh > 32767) return refuse("output size must be in [1, 32767]");
+    if (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL) return refuse("unknown map mode");
+    if (q.rot_bottom && !map_mode_fish_to_pinhole(map_mode)) return refuse("a rotation per output row (rot_bottom) is served for map modes 0, 1 and 5");
+    if (q.out_format != VSTAB_OUT_BGR8 && q.out_format != VSTAB_OUT_NV12_PLANAR)
+        return refuse(std::string(q.e.who) + "emits VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR (NV12 through BGR is not served)");
+    if (!border_mode_valid(q.border_mode))  // (an entry point without one: VSTAB_BORDER_CONSTANT)
+        return refuse("border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)");
+    const bool planar = q.planar();
+    if (q.pitch_y < (size_t)q.sw || q.pitch_uv < (size_t)q.sw || q.pitch_dst < (size_t)q.dw * (planar ? 1 : 3)) return refuse("pitch smaller than row");
+    if (planar && (!q.dst_uv || q.pitch_dst_uv < (size_t)((q.dw + 1) / 2) * 2)) return refuse("plane-wise output needs a chroma plane of 2*ceil(width/2) bytes per row");
+    if (!ptr_aligned(q.uv, 2) || q.pitch_uv % 2) return refuse("chroma plane must be 2-B aligned");
+    fill_warp_args(c.w, q, planar);
+    c.p32 = map_params32(q.params, q.dist);
+    if (q.resample != VSTAB_RESAMPLE_DEFAULT && q.resample != VSTAB_RESAMPLE_CUBIC && q.resample != VSTAB_RESAMPLE_LANCZOS4)
+        return refuse("resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)");
+    if (q.dist) {
+        if (!map_mode_takes_distortion(q.map_mode)) return refuse("distortion belongs to a fisheye input (map modes 1 and 2)");
+        VSTAB_TRY(check_distortion(q.e.name, q.dist));
+    }
+    if (q.pinhole) {
+        if (!map_mode_takes_pinhole(q.map_mode)) return refuse("pinhole distortion belongs to a rectilinear input (map modes 3 and 4)");
+        VSTAB_TRY(check_pinhole_distortion(q.e.name, q.pinhole));
+    }
     return VSTAB_OK;
+}
+// a keep request's history (vstab_internal.hpp), behind its other checks
+inline vstab_status check_keep_prev(const WarpRequest &q, bool &in_place) {
+    const KeepPlane planes[2] = {{q.prev, q.pitch_prev, q.dst, q.pitch_dst, (size_t)q.dw * (q.planar() ? 1 : 3), q.dh},
+                                 {q.prev_uv, q.pitch_prev_uv, q.dst_uv, q.pitch_dst_uv, (size_t)((q.dw + 1) / 2) * 2, (q.dh + 1) / 2}};
+    return check_keep_prev(q.e.name, planes, q.planar() ? 2 : 1, in_place);
 }
 
 // The stateless remaps' arguments, checked.  border_mode: null where the entry point has none (the border is constant, and its values are
@@ -214,88 +256,36 @@ inline vstab_status check_remap(const std::string &n, const void *src, size_t pi
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The entry points of a resampler (cubic, Lanczos) over its kernels KS: KS::warp<MODE, PLANAR, BORDER>() and KS::remap<CN, BORDER>(), the
-// kernel of each combination (BORDER_CONSTANT: the kernels that carry the border value).  border_mode null: the constant-border entry points.
+// A resampler (cubic, Lanczos) over its kernels KS: KS::warp<MODE, PLANAR, BORDER>(), KS::warp_rs<MODE, PLANAR, BORDER>() and
+// KS::remap<CN, BORDER>(), the kernel of each combination (BORDER_CONSTANT: the kernels that carry the border value).  remap_resample's
+// border_mode null: the constant-border entry points.
 // ---------------------------------------------------------------------------------------------------------------------
-// the warp kernel of checked arguments on its grid; dist: c.p32.d holds the input lens's coefficients (map modes 1 and 2)
+// The warp kernel of a route on its grid.  ARGS_CUBIC: KS::warp over ba.c, one rotation per frame through an ideal or a calibrated fisheye
+// lens.  ARGS_BORDER: KS::warp_rs over ba -- a rotation per output row (the map mode 0, 1 or 5 itself: the kernel's map is
+// border_map<MODE, true>; MAP_RS_FISHD_TO_RECT: map mode 1 with the coefficients in ba.c.p32.d) or a rectilinear lens with (k1, k2, p1, p2,
+// k3) in ba.pd (MAP_RECTD_*, whose map is border_map<MODE, false>; rs_d zero) --, every border mode, BORDER_CONSTANT included.
 template <typename KS>
-vstab_status launch_warp_resample(const CubicArgs &c, int map_mode, bool dist, int out_format, int border_mode, void *stream) {
-    with_map_mode_or_dist(map_mode, dist, [&](auto mode) {
+vstab_status launch_warp_resample(const BorderArgs &ba, const WarpRoute &r, int out_format, int border_mode, void *stream) {
+    with_kernel_mode(route_kernel_mode(r.mode), [&](auto mode) {
         with_border_mode(border_mode, [&](auto border) {
             with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
-                launch_tiles(KS::template warp<decltype(mode)::value, decltype(planar)::value, decltype(border)::value>(), c, c.w.dw, c.w.dh, stream);
+                constexpr int MODE = decltype(mode)::value, BORDER = decltype(border)::value;
+                constexpr bool PLANAR = decltype(planar)::value;
+                if constexpr (mode_plain_or_dist(MODE))
+                    if (r.block == ARGS_CUBIC) launch_tiles(KS::template warp<MODE, PLANAR, BORDER>(), ba.c, ba.c.w.dw, ba.c.w.dh, stream);
+                if constexpr (map_mode_fish_to_pinhole(MODE) || MODE == MAP_RS_FISHD_TO_RECT || ModeTraits<MODE>::rectd)
+                    if (r.block == ARGS_BORDER) launch_tiles(KS::template warp_rs<MODE, PLANAR, BORDER>(), ba, ba.c.w.dw, ba.c.w.dh, stream);
             });
         });
     });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }
-template <typename KS>
-vstab_status warp_resample(const char *name, const char *who, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh,
-                           const float params[17], int map_mode, int out_format, const int *border_mode, void *dst, size_t pitch_dst, void *dst_uv,
-                           size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    CubicArgs c;
-    const vstab_status st = check_warp_nv12(name, who, y, pitch_y, uv, pitch_uv, sw, sh, params, nullptr, map_mode, out_format, border_mode, dst, pitch_dst,
-                                            dst_uv, pitch_dst_uv, dw, dh, c);
-    if (st != VSTAB_OK) return st;
-    return launch_warp_resample<KS>(c, map_mode, false, out_format, border_mode ? *border_mode : VSTAB_BORDER_CONSTANT, stream);
-}
-// vstab_warp_nv12_dist_ex's kernels, one launcher per resampler's unit: c checked and filled by check_warp_nv12 with the coefficients, the
-// map mode 1 or 2.  launch_warp_border_dist: the non-constant modes (INTER_LINEAR with the constant border is vstab_warp_nv12_dist).
-vstab_status launch_warp_cubic_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream);
-vstab_status launch_warp_lanczos4_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream);
-vstab_status launch_warp_border_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream);
-
-// vstab_warp_nv12_rs_ex's kernels: a rotation per output row (ba checked, its rs_d / rs_den filled by fill_rolling_shutter) under the cubic
-// and Lanczos resamplers, every border mode.  KS::warp_rs<MODE, PLANAR, BORDER>() is the kernel; MODE is the map mode 0, 1 or 5 itself (the
-// kernel's map is border_map<MODE, true>) or, dist, MAP_RS_FISHD_TO_RECT (map mode 1 with the coefficients in ba.c.p32.d).
-template <typename F>
-void with_rs_mode(int map_mode, bool dist, F &&f) {
-    if (dist) f(mode_constant<MAP_RS_FISHD_TO_RECT>{});
-    else if (map_mode == VSTAB_MAP_CREATEMAP_CL) f(mode_constant<MAP_CREATEMAP_CL>{});
-    else if (map_mode == VSTAB_MAP_CREATEMAP_CL_OPENCL) f(mode_constant<MAP_CREATEMAP_CL_OPENCL>{});
-    else f(mode_constant<MAP_FISH_TO_RECT>{});
-}
-template <typename KS>
-vstab_status launch_warp_resample_rs(const BorderArgs &ba, int map_mode, bool dist, int out_format, int border_mode, void *stream) {
-    with_rs_mode(map_mode, dist, [&](auto mode) {
-        with_border_mode(border_mode, [&](auto border) {
-            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
-                launch_tiles(KS::template warp_rs<decltype(mode)::value, decltype(planar)::value, decltype(border)::value>(), ba, ba.c.w.dw, ba.c.w.dh, stream);
-            });
-        });
-    });
-    VSTAB_HIP_TRY(hipGetLastError());
-    return VSTAB_OK;
-}
-vstab_status launch_warp_cubic_rs(const BorderArgs &ba, int map_mode, bool dist, int out_format, int border_mode, void *stream);
-vstab_status launch_warp_lanczos4_rs(const BorderArgs &ba, int map_mode, bool dist, int out_format, int border_mode, void *stream);
-// k_warp_border of checked arguments (vstab_warp_border.hip): rs with dist is INTER_LINEAR on a calibrated lens with a rotation per row
-vstab_status launch_warp_border(const BorderArgs &ba, int map_mode, bool dist, bool rs, int out_format, int border_mode, void *stream);
-
-// vstab_warp_nv12_pinhole's kernels: a rectilinear input lens with (k1, k2, p1, p2, k3) in ba.pd (checked; map mode 3 or 4; rs_d zero), one
-// launcher per resampler's unit.  The kernels are the ones that take a BorderArgs -- k_warp_border<MODE, PLANAR, false, BORDER> and
-// KS::warp_rs<MODE, PLANAR, BORDER>() -- with MODE the mode's MAP_RECTD_* form, whose map is border_map<MODE, false>.
-template <typename F>
-void with_pinhole_mode(int map_mode, F &&f) {
-    if (map_mode == VSTAB_MAP_RECT_TO_RECT) f(mode_constant<MAP_RECTD_TO_RECT>{});
-    else f(mode_constant<MAP_RECTD_TO_FISH>{});
-}
-template <typename KS>
-vstab_status launch_warp_resample_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream) {
-    with_pinhole_mode(map_mode, [&](auto mode) {
-        with_border_mode(border_mode, [&](auto border) {
-            with_bool(out_format == VSTAB_OUT_NV12_PLANAR, [&](auto planar) {
-                launch_tiles(KS::template warp_rs<decltype(mode)::value, decltype(planar)::value, decltype(border)::value>(), ba, ba.c.w.dw, ba.c.w.dh, stream);
-            });
-        });
-    });
-    VSTAB_HIP_TRY(hipGetLastError());
-    return VSTAB_OK;
-}
-vstab_status launch_warp_cubic_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream);
-vstab_status launch_warp_lanczos4_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream);
-vstab_status launch_warp_border_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream);
+// one launcher per unit of tile kernels: ba checked and filled (rs_d / rs_den by fill_rolling_shutter, pd), r the route that names the unit's family
+vstab_status launch_warp_cubic(const BorderArgs &ba, const WarpRoute &r, int out_format, int border_mode, void *stream);
+vstab_status launch_warp_lanczos4(const BorderArgs &ba, const WarpRoute &r, int out_format, int border_mode, void *stream);
+vstab_status launch_warp_border(const BorderArgs &ba, const WarpRoute &r, int out_format, int border_mode, void *stream);
+vstab_status launch_warp_keep(const BorderArgs &ba, const WarpRoute &r, const WarpRequest &q, bool in_place);
 
 template <typename KS>
 vstab_status remap_resample(const char *name, const void *src, size_t pitch_src, int sw, int sh, int channels, const void *map_x, size_t pitch_x,

@@ -221,6 +221,29 @@ static bool keep_vec_ok(const void *prev, size_t pitch_prev, const void *dst, si
     return ptr_aligned(prev, 16) && ptr_aligned(dst, 16) && pitch_prev % 16 == 0 && pitch_dst % 16 == 0;
 }
 
+// k_warp_keep of a route (WARP_KEEP) on its grid: ba and the request's history (checked: check_keep_prev, which found in_place)
+vstab_status launch_warp_keep(const BorderArgs &ba, const WarpRoute &r, const WarpRequest &q, bool in_place) {
+    const bool planar = q.planar();
+    KeepArgs ka;
+    ka.b = ba;
+    ka.prev = (const uint8_t *)q.prev, ka.pitch_prev = q.pitch_prev;
+    ka.prev_uv = planar ? (const uint8_t *)q.prev_uv : nullptr, ka.pitch_prev_uv = planar ? q.pitch_prev_uv : 0;
+    ka.in_place = in_place;
+    ka.vec = keep_vec_ok(q.prev, q.pitch_prev, q.dst, q.pitch_dst), ka.vec_uv = planar && keep_vec_ok(q.prev_uv, q.pitch_prev_uv, q.dst_uv, q.pitch_dst_uv);
+    with_kernel_mode(route_kernel_mode(r.mode), [&](auto mode) {
+        with_bool(planar, [&](auto pl) {
+            with_bool(map_mode_is_rs(r.mode), [&](auto rs) {
+                constexpr int MODE = decltype(mode)::value;
+                constexpr bool RS = decltype(rs)::value;
+                if constexpr (MODE <= MAP_CREATEMAP_CL_OPENCL && (!RS || map_mode_fish_to_pinhole(MODE)))
+                    launch_tiles(k_warp_keep<MODE, decltype(pl)::value, RS>, ka, q.dw, q.dh, q.stream);
+            });
+        });
+    });
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
 }  // namespace vstab
 
 using namespace vstab;
@@ -249,31 +272,10 @@ vstab_status vstab_remap_bilinear_keep(const void *src, size_t pitch_src, int sw
 vstab_status vstab_warp_nv12_keep(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17], const float *rot_bottom,
                                   int map_mode, int out_format, const void *prev, size_t pitch_prev, const void *prev_uv, size_t pitch_prev_uv, void *dst,
                                   size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    static const char n[] = "vstab_warp_nv12_keep";
-    KeepArgs ka;
-    VSTAB_TRY(check_warp_nv12(n, "the keep-edge warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, out_format, nullptr, dst, pitch_dst, dst_uv,
-                              pitch_dst_uv, dw, dh, ka.b.c));
-    const bool planar = out_format == VSTAB_OUT_NV12_PLANAR;
-    const KeepPlane planes[2] = {{prev, pitch_prev, dst, pitch_dst, (size_t)dw * (planar ? 1 : 3), dh},
-                                 {prev_uv, pitch_prev_uv, dst_uv, pitch_dst_uv, (size_t)((dw + 1) / 2) * 2, (dh + 1) / 2}};
-    bool in_place;
-    VSTAB_TRY(check_keep_prev(n, planes, planar ? 2 : 1, in_place));
-    fill_rolling_shutter(ka.b, params, rot_bottom, dh);
-    ka.prev = (const uint8_t *)prev, ka.pitch_prev = pitch_prev;
-    ka.prev_uv = planar ? (const uint8_t *)prev_uv : nullptr, ka.pitch_prev_uv = planar ? pitch_prev_uv : 0;
-    ka.in_place = in_place;
-    ka.vec = keep_vec_ok(prev, pitch_prev, dst, pitch_dst), ka.vec_uv = planar && keep_vec_ok(prev_uv, pitch_prev_uv, dst_uv, pitch_dst_uv);
-    with_map_mode(map_mode, [&](auto mode) {
-        with_bool(planar, [&](auto pl) {
-            with_bool(rot_bottom != nullptr, [&](auto rs) {
-                constexpr int MODE = decltype(mode)::value;
-                constexpr bool RS = decltype(rs)::value;
-                if constexpr (!RS || map_mode_fish_to_pinhole(MODE)) launch_tiles(k_warp_keep<MODE, decltype(pl)::value, RS>, ka, dw, dh, stream);
-            });
-        });
-    });
-    VSTAB_HIP_TRY(hipGetLastError());
-    return VSTAB_OK;
+    return warp_nv12({.e = ENTRY_KEEP, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .rot_bottom = rot_bottom,
+                      .keep = true, .prev = prev, .pitch_prev = pitch_prev, .prev_uv = prev_uv, .pitch_prev_uv = pitch_prev_uv, .map_mode = map_mode,
+                      .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw, .dh = dh,
+                      .stream = stream});
 }
 
 }  // extern "C"

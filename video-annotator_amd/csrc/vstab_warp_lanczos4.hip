@@ -218,16 +218,8 @@ vstab_status preload_lanczos4_kernels() {
     return VSTAB_OK;
 }
 
-vstab_status launch_warp_lanczos4_dist(const CubicArgs &c, int map_mode, int out_format, int border_mode, void *stream) {
-    return launch_warp_resample<Lanczos4Kernels>(c, map_mode, true, out_format, border_mode, stream);
-}
-
-vstab_status launch_warp_lanczos4_rs(const BorderArgs &ba, int map_mode, bool dist, int out_format, int border_mode, void *stream) {
-    return launch_warp_resample_rs<Lanczos4Kernels>(ba, map_mode, dist, out_format, border_mode, stream);
-}
-
-vstab_status launch_warp_lanczos4_pinhole(const BorderArgs &ba, int map_mode, int out_format, int border_mode, void *stream) {
-    return launch_warp_resample_pinhole<Lanczos4Kernels>(ba, map_mode, out_format, border_mode, stream);
+vstab_status launch_warp_lanczos4(const BorderArgs &ba, const WarpRoute &r, int out_format, int border_mode, void *stream) {
+    return launch_warp_resample<Lanczos4Kernels>(ba, r, out_format, border_mode, stream);
 }
 
 }  // namespace vstab
@@ -256,18 +248,19 @@ vstab_status vstab_remap_lanczos4_border(const void *src, size_t pitch_src, int 
                                            border, dst, pitch_dst, dw, dh, stream);
 }
 
-vstab_status vstab_warp_nv12_lanczos4(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
-                                      int map_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh,
-                                      void *stream) {
-    return warp_resample<Lanczos4Kernels>("vstab_warp_nv12_lanczos4", "the Lanczos warp ", y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format,
-                                          nullptr, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
+vstab_status vstab_warp_nv12_lanczos4(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17], int map_mode,
+                                      int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
+    return warp_nv12({.e = ENTRY_LANCZOS4, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .map_mode = map_mode,
+                      .resample = VSTAB_RESAMPLE_LANCZOS4, .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv,
+                      .dw = dw, .dh = dh, .stream = stream});
 }
 
 vstab_status vstab_warp_nv12_lanczos4_border(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
-                                             int map_mode, int out_format, int border_mode, void *dst, size_t pitch_dst, void *dst_uv,
-                                             size_t pitch_dst_uv, int dw, int dh, void *stream) {
-    return warp_resample<Lanczos4Kernels>("vstab_warp_nv12_lanczos4_border", "", y, pitch_y, uv, pitch_uv, sw, sh, params, map_mode, out_format,
-                                          &border_mode, dst, pitch_dst, dst_uv, pitch_dst_uv, dw, dh, stream);
+                                             int map_mode, int out_format, int border_mode, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh,
+                                             void *stream) {
+    return warp_nv12({.e = ENTRY_LANCZOS4_BORDER, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params,
+                      .map_mode = map_mode, .resample = VSTAB_RESAMPLE_LANCZOS4, .border_mode = border_mode, .out_format = out_format, .dst = dst,
+                      .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw, .dh = dh, .stream = stream});
 }
 
 }  // extern "C"
