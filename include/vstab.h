@@ -470,6 +470,39 @@ VSTAB_API vstab_status vstab_good_features_mask(const void *gray, size_t pitch, 
                                                 int max_corners, double quality, double min_distance, int detector,
                                                 float *xy, int *count, int *detector_used, void *stream);
 
+/* ---- Harris response -----------------------------------------------------------------------------------------------------------------
+ * goodFeaturesToTrack's `useHarrisDetector` and `k`, and cornerHarris as a dense map, as OpenCV 4.5 computes them on its CPU path:
+ * cornerHarris(gray, dst, 3, 3, k) and goodFeaturesToTrack(gray, corners, max_corners, quality, min_distance, mask, 3, true, k).
+ *   1. Covariance sums.  a, b, c are the three box sums of cornerMinEigenVal(3, 3) exactly as vstab_min_eig forms them: Sobel derivatives
+ *      scaled by 1 / (4 * 3 * 255) in the documented operation order, the float products dx dx, dx dy, dy dy, the un-normalised 3 x 3 box
+ *      sum under REFLECT_101 (exact in double), each sum rounded once to float.  They are those floats BEFORE the minimum-eigenvalue
+ *      formula halves two of them: OpenCV uses one scale for both responses.
+ *   2. Response.  kf = (float)k, t = a + c, R = (a c - b b) - (kf t) t: every operation rounded to binary32, in that order, nothing
+ *      contracted.  This is the arithmetic of OpenCV's vector path (v_float32, k set as a float), which computes all but the last few
+ *      columns of a row; its scalar tail keeps k in double.  This library uses the vector form for EVERY pixel.  It claims no bit equality
+ *      with OpenCV: like the minimum-eigenvalue detector, this is a restatement.
+ *   3. Detector.  The steps of vstab_good_features_mask ("Detection mask" above) on R in place of the eigenvalue: the maximum over the
+ *      masked-in pixels (all pixels without a mask), the threshold (float)((double)maxVal * quality) with strict >, the 3 x 3 maximum test
+ *      over all pixels, interior pixels only, the mask gate, the order of the keys, the min_distance grid and max_corners.
+ *   4. A (masked) maximum that is not positive gives no corner.  R is negative over about half of an ordinary frame, and over all of a
+ *      frame of stripes or of a ramp (edges and flat ground, no corner): with maxVal <= 0 nothing lies above maxVal * quality but what
+ *      OpenCV's THRESH_TOZERO then sets to zero and its `val != 0` test drops.  The detectors take maxima in the order of the floats' bits
+ *      read as int32; that order is wrong among negative values but right about the sign: if any value is >= +0 the maximum's bits are
+ *      >= 0.  The sign of the published maximum decides this rule, on every path.
+ *   5. k is finite with 0 <= k < 0.25: from 0.25 on, det - k tr^2 is never positive.  Anything else is refused.
+ * The minimum-eigenvalue detector keeps its definition and its caveat ("Detection mask" above) word for word.  blockSize and gradientSize
+ * other than 3 are not offered.
+ *
+ * vstab_corner_harris is vstab_min_eig's twin: response_f32 is a dense width x height device map of R.  Refused with VSTAB_ERR_INVALID
+ * before any launch: "vstab_corner_harris: bad argument" (what vstab_min_eig refuses), then "vstab_corner_harris: k lies in [0, 0.25)".
+ * vstab_good_features_harris is vstab_good_features_mask with the Harris response; mask == NULL means no mask.  Its refusals are those of
+ * vstab_good_features_mask under this name, in that order, then "vstab_good_features_harris: k lies in [0, 0.25)". */
+enum { VSTAB_CORNER_MIN_EIGENVAL = 0, VSTAB_CORNER_HARRIS = 1 };
+VSTAB_API vstab_status vstab_corner_harris(const void *gray, size_t pitch, int width, int height, double k, void *response_f32, void *stream);
+VSTAB_API vstab_status vstab_good_features_harris(const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask,
+                                                  int max_corners, double quality, double min_distance, double k, int detector,
+                                                  float *xy, int *count, int *detector_used, void *stream);
+
 /* Replaces calcOpticalFlowPyrLK with default parameters (win 21x21, maxLevel 3, 30 iterations,
  * eps 0.01, minEigThreshold 1e-4), FrameSourceWarp.cpp:252.  prev/next: device gray images of the
  * same size; prev_xy: n host (x,y) pairs; next_xy / status: host outputs (n pairs / n bytes). */
@@ -1010,6 +1043,14 @@ VSTAB_API vstab_status vstab_set_readout_warp(vstab_handle *h, int mode);
  * A static overlay (a burnt-in clock, a logo, a bonnet) is best masked out together with a margin of about 16 px: the tracker's 21 x 21
  * window reaches that far from a corner on the first pyramid level. */
 VSTAB_API vstab_status vstab_set_detection_mask(vstab_handle *h, const void *mask, size_t pitch_mask, int mem);
+/* The corner response of a handle ("Harris response" above): every corner detection of the handle -- the first frame's, a key frame's, the
+ * one run ahead of a planned key frame -- uses it, with a detection mask or without, on pixel_depth 10 handles too.  response:
+ * VSTAB_CORNER_HARRIS with k (goodFeaturesToTrack's useHarrisDetector = true), or VSTAB_CORNER_MIN_EIGENVAL, which does not look at k and
+ * restores the handle as it always was.  Allowed before the first pull only.  Refused with VSTAB_ERR_INVALID, the handle unchanged, in this
+ * order: "vstab_set_corner_response: null handle"; "vstab_set_corner_response: no detector runs on this handle (tracking = 0)";
+ * "vstab_set_corner_response: the response must be set before the first pull"; "vstab_set_corner_response: response must be
+ * VSTAB_CORNER_MIN_EIGENVAL (0) or VSTAB_CORNER_HARRIS (1)"; "vstab_set_corner_response: k lies in [0, 0.25)". */
+VSTAB_API vstab_status vstab_set_corner_response(vstab_handle *h, int response, double k);
 /* vstab_pull_frame / vstab_pull_frame_nv12_planar with kept edges ("Keep edges" above): the next frame, warped by vstab_warp_nv12_keep with
  * the caller's previous output prev (prev_y / prev_uv) -- a second buffer (a ring of two outputs), or dst itself (in place).  A frame that
  * carries a read-out rotation is warped per row, as a plain INTER_LINEAR pull warps it.  Keep pulls and plain pulls may alternate frame by

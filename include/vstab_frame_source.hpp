@@ -147,6 +147,16 @@ class FrameSourceWarp : public FrameSource {
             throw (int)st;
         }
     }
+    // goodFeaturesToTrack's useHarrisDetector and k for find_corners (FrameSourceWarp.cpp:228-240 passes neither: the minimum eigenvalue,
+    // whatever the comment at :416 says): VSTAB_CORNER_HARRIS with k, or VSTAB_CORNER_MIN_EIGENVAL; before the first pull_frame --
+    // vstab_set_corner_response
+    void set_corner_response(int response, double k = 0.04) {
+        const vstab_status st = vstab_set_corner_response(m_handle, response, k);
+        if (st != VSTAB_OK) {
+            std::fprintf(stderr, "FrameSourceWarp: %s\n", vstab_last_error());
+            throw (int)st;
+        }
+    }
 
     BGRFrame pull_frame() override {  // FrameSourceWarp.cpp:452-476
         if (!m_out) throw -1;

@@ -1,9 +1,12 @@
 """Run the corner detectors at 4K and 1080p a few times (for rocprofv3 --kernel-trace --stats).
-usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overlay,roi}] [--alternations K]
+usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overlay,roi}] [--harris [--k K]] [--alternations K]
    LIB: another build of the library (tools/devlib.py), for parent / branch runs
    --mask: K alternations of N unmasked detections (k_corners_fused) and N detections under the mask (k_corners_fused_masked,
            vstab_good_features_mask) per size, in one process: `full` is non-zero everywhere, `overlay` is zero on a box over 9 % of the frame
            grown by 16 px (the lower left), `roi` leaves a window of a tenth of the fused detector's tiles.
+   --harris: K alternations (rounds) of N detections with the minimum eigenvalue and N with the Harris response (vstab_good_features_harris,
+           k_corners_fused_harris) per size, in one process; with --mask both run under the mask (k_corners_fused_masked and
+           k_corners_fused_harris_masked).  tools/kernel_medians.py <dir> k_corners rounds gives the figures per round.
    tools/kernel_medians.py <dir> turns the kernel trace into medians per kernel and grid."""
 import argparse, hashlib, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -18,6 +21,8 @@ ap.add_argument("--lib", default=None)
 ap.add_argument("--n", type=int, default=20)
 ap.add_argument("--fused-only", action="store_true")
 ap.add_argument("--mask", choices=("full", "overlay", "roi"), default=None)
+ap.add_argument("--harris", action="store_true")
+ap.add_argument("--k", type=float, default=0.04)
 ap.add_argument("--alternations", type=int, default=3)
 a = ap.parse_args()
 if a.lib:
@@ -41,6 +46,20 @@ def make_mask(kind, w, h):
 
 for w, h in ((3840, 2160), (1920, 1080)):
     g = torch.from_numpy(np.ascontiguousarray(synth.luma(41, w, h, rects=400))).cuda()
+    if a.harris:
+        m = torch.from_numpy(make_mask(a.mask, w, h)).cuda() if a.mask else None
+        for _ in range(a.alternations):
+            for harris in (False, True):
+                info = {}
+                for _ in range(a.n):
+                    if harris:
+                        c = vs.good_features_harris(g, m, k=a.k, detector=vs.DETECTOR_FUSED, info=info)
+                    else:
+                        c = vs.good_features_mask(g, m, detector=vs.DETECTOR_FUSED, info=info)
+                torch.cuda.synchronize()
+                print(w, h, "mask", a.mask, "harris k %g" % a.k if harris else "minimum eigenvalue", "detector", info["detector_used"], "corners", len(c),
+                      hashlib.sha1(np.ascontiguousarray(c).tobytes()).hexdigest()[:12], flush=True)
+        continue
     if a.mask:
         mh = make_mask(a.mask, w, h)
         m = torch.from_numpy(mh).cuda()

@@ -192,6 +192,9 @@ SIGNATURES = {
     "vstab_warp_nv12_pinhole": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_good_features_mask": (_i, [_vp, _sz, _i, _i, _vp, _sz, _i, _d, _d, _i, _fp, _ip, _ip, _vp]),
     "vstab_set_detection_mask": (_i, [_vp, _vp, _sz, _i]),
+    "vstab_corner_harris": (_i, [_vp, _sz, _i, _i, _d, _vp, _vp]),
+    "vstab_good_features_harris": (_i, [_vp, _sz, _i, _i, _vp, _sz, _i, _d, _d, _d, _i, _fp, _ip, _ip, _vp]),
+    "vstab_set_corner_response": (_i, [_vp, _i, _d]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -208,6 +211,8 @@ _L.vstabx_corners_fused.restype = _i
 _L.vstabx_corners_fused.argtypes = [_vp, _sz, _i, _i, _d, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _vp]
 _L.vstabx_corners_fused_mask.restype = _i
 _L.vstabx_corners_fused_mask.argtypes = [_vp, _sz, _i, _i, _vp, _sz, _d, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _vp]
+_L.vstabx_corners_fused_harris.restype = _i
+_L.vstabx_corners_fused_harris.argtypes = [_vp, _sz, _i, _i, _vp, _sz, _d, _d, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _ip, _vp]
 _L.vstabx_detector_counters.restype = _i
 _L.vstabx_detector_counters.argtypes = [_vp, _c.POINTER(_c.c_long)]
 
@@ -795,6 +800,32 @@ def good_features_mask(gray, mask, max_corners=200, quality=0.01, min_distance=3
     return xy[:n.value].copy()
 
 
+CORNER_MIN_EIGENVAL, CORNER_HARRIS = 0, 1
+
+
+def corner_harris(gray, k=0.04):
+    """vstab_corner_harris: cornerHarris(gray, 3, 3, k) as an (h, w) float32 device map (include/vstab.h, "Harris response")"""
+    import torch
+    h, w = gray.shape
+    out = torch.empty((h, w), dtype=torch.float32, device=gray.device)
+    _check(_L.vstab_corner_harris(gray.data_ptr(), gray.stride(0), w, h, float(k), out.data_ptr(), _stream()), "vstab_corner_harris")
+    return out
+
+
+def good_features_harris(gray, mask=None, max_corners=200, quality=0.01, min_distance=30.0, k=0.04, detector=DETECTOR_AUTO, info=None):
+    """vstab_good_features_harris: good_features_mask with the Harris response (goodFeaturesToTrack's useHarrisDetector = true and k);
+    mask None = no mask."""
+    h, w = gray.shape
+    xy = np.zeros((max_corners, 2), np.float32)
+    n, used = _c.c_int(), _c.c_int()
+    _check(_L.vstab_good_features_harris(gray.data_ptr(), gray.stride(0), w, h, None if mask is None else mask.data_ptr(), 0 if mask is None else mask.stride(0),
+                                         max_corners, quality, min_distance, float(k), detector, _fptr(xy), _c.byref(n), _c.byref(used), _stream()),
+           "vstab_good_features_harris")
+    if info is not None:
+        info["detector_used"] = used.value
+    return xy[:n.value].copy()
+
+
 CORNERS_FUSED_FILL = 0xA5A5A5A5A5A5A5A5  # what vstabx_corners_fused fills its key buffer with before the kernels run
 
 
@@ -834,6 +865,27 @@ def corners_fused_mask(gray, mask, quality=0.01, cap=1 << 18, canary=64, w=None,
                                         keys.ctypes.data_as(_c.POINTER(_u64)), counts.ctypes.data_as(_c.POINTER(_c.c_uint)),
                                         tiles.ctypes.data_as(_c.POINTER(_c.c_uint)), _stream() if stream is None else stream), "vstabx_corners_fused_mask")
     return keys, int(counts[0]), int(counts[1]), tiles
+
+
+def corners_fused_harris(gray, mask=None, k=0.04, quality=0.01, cap=1 << 18, canary=64, w=None, h=None, stream=None):
+    """Test hook vstabx_corners_fused_harris: corners_fused / corners_fused_mask (mask None = no mask) with the Harris response.
+    -> (keys, keys kept, tiles that spilled, per-tile survivor counts, max_bits): max_bits is the frame maximum the kernels published, the
+    float's bits as int32 -- negative: no response above zero, the host reports no corner whatever the keys say."""
+    h = gray.shape[0] if h is None else h
+    w = gray.shape[1] if w is None else w
+    cap, canary = int(cap), int(canary)
+    ok = 0 < cap <= 1 << 24 and 0 < canary <= 1 << 16
+    keys = np.zeros(cap + canary if ok else 1, np.uint64)
+    counts = np.zeros(2, np.uint32)
+    tx, ty = max(1, (int(w) + 63) // 64), max(1, (int(h) + 30) // 31)
+    tiles = np.zeros((ty, tx) if tx * ty < 1 << 21 else (1, 1), np.uint32)
+    mx = _c.c_int()
+    _check(_L.vstabx_corners_fused_harris(gray.data_ptr(), gray.stride(0), int(w), int(h), None if mask is None else mask.data_ptr(),
+                                          0 if mask is None else mask.stride(0), float(quality), float(k), cap & 0xFFFFFFFF, canary & 0xFFFFFFFF,
+                                          keys.ctypes.data_as(_c.POINTER(_u64)), counts.ctypes.data_as(_c.POINTER(_c.c_uint)),
+                                          tiles.ctypes.data_as(_c.POINTER(_c.c_uint)), _c.byref(mx), _stream() if stream is None else stream),
+           "vstabx_corners_fused_harris")
+    return keys, int(counts[0]), int(counts[1]), tiles, mx.value
 
 
 def pyr_lk(prev, nxt, pts):
@@ -984,8 +1036,9 @@ class Stabilizer:
     source for `total` pulls) or a Python iterable of such tensors (python callback source)."""
 
     def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, calibration=None,
-                 calibration_ex=None, pinhole=None, detection_mask=None, **cfg_kw):
-        """detection_mask: set_detection_mask right after create (a device tensor or a numpy array of the luma plane's size).
+                 calibration_ex=None, pinhole=None, detection_mask=None, corner_response=None, harris_k=0.04, **cfg_kw):
+        """corner_response: set_corner_response(corner_response, harris_k) right after create (CORNER_HARRIS or CORNER_MIN_EIGENVAL).
+        detection_mask: set_detection_mask right after create (a device tensor or a numpy array of the luma plane's size).
         border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
         calibration: (K, D) for set_input_calibration right after create, applied after border_mode (K None keeps the camera from in_dfov).
         calibration_ex: the same through set_input_calibration_ex (every resampler and border mode).
@@ -1059,6 +1112,13 @@ class Stabilizer:
             self.set_input_pinhole(*pinhole)
         if detection_mask is not None:
             self.set_detection_mask(detection_mask)
+        if corner_response is not None:
+            self.set_corner_response(corner_response, harris_k)
+
+    def set_corner_response(self, response, k=0.04):
+        """vstab_set_corner_response: CORNER_HARRIS with k (goodFeaturesToTrack's useHarrisDetector and k) for every detection of this
+        handle, or CORNER_MIN_EIGENVAL (k not looked at) to have the handle as it always was; before the first pull."""
+        _check(_L.vstab_set_corner_response(self._h, int(response), float(k)), "vstab_set_corner_response")
 
     def set_detection_mask(self, mask):
         """vstab_set_detection_mask: goodFeaturesToTrack's mask for every detection of this handle, before the first pull.  mask: (h, w) uint8,

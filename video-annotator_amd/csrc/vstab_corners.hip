@@ -97,6 +97,86 @@ __global__ void __launch_bounds__(256) k_min_eig(const uint8_t *__restrict__ src
     if (tid == 0) atomicMax(max_bits, bmax);
 }
 
+// k_corner_harris -- cornerHarris(blockSize 3, ksize 3, k) as a dense map (vstab.h, "Harris response"; kf = (float)k): k_min_eig line for
+// line but for the response R = (a c - b b) - (kf t) t, t = a + c, over the box sums as they are.  A kernel of its own and not a template
+// shared with k_min_eig: routed through a shared inline body the compiler schedules k_min_eig differently, and that kernel's
+// instructions are to stay what they are.  The frame maximum is taken in the same int-bit order: its SIGN is right also where the
+// order among negative values is not, and the sign is all the host asks it for when the maximum is not positive.
+__global__ void __launch_bounds__(256) k_corner_harris(const uint8_t *__restrict__ src, size_t pitch, int w, int h,
+                                                       float *__restrict__ eig, int *__restrict__ max_bits, int vec_ok, float kf) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[ME_SH][ME_SW];
+    __shared__ float dxs[ME_TH + 2][ME_TW + 2 + 1], dys[ME_TH + 2][ME_TW + 2 + 1];
+    __shared__ int bmax;
+    const int tid = threadIdx.x;
+    const int ox = blockIdx.x * ME_TW, oy = blockIdx.y * ME_TH;
+    const int sx0 = ox - 4, sy0 = oy - 2;
+    if (tid == 0) bmax = INT_MIN;
+    for (int e = tid; e < ME_SH * (ME_SW / 4); e += 256) {
+        const int ry = e / (ME_SW / 4), rd = e - ry * (ME_SW / 4);
+        reinterpret_cast<uint32_t *>(&tile[ry][0])[rd] = load4_reflect(src, (uint32_t)pitch, w, h, sx0 + 4 * rd, sy0 + ry, vec_ok != 0);
+    }
+    __syncthreads();
+    const float scale = (float)(1.0 / (4.0 * 3.0 * 255.0));
+    const float k0 = 2.0f * scale, k1 = scale;
+    // derivative entry (ry, rx) <-> image coordinate (oy - 1 + ry, ox - 1 + rx) <-> tile[ry + 1][rx + 3]
+    for (int e = tid; e < (ME_TH + 2) * (ME_TW + 2); e += 256) {
+        const int ry = e / (ME_TW + 2), rx = e - ry * (ME_TW + 2);
+        const uint8_t *c = &tile[ry + 1][rx + 3];
+        const int a00 = c[-ME_SW - 1], a01 = c[-ME_SW], a02 = c[-ME_SW + 1];
+        const int a10 = c[-1], a12 = c[1];
+        const int a20 = c[ME_SW - 1], a21 = c[ME_SW], a22 = c[ME_SW + 1];
+        const float d0 = (float)(a02 - a00), d1 = (float)(a12 - a10), d2 = (float)(a22 - a20);
+        float dx = (d0 + d2) * k1 + d1 * k0;
+        const float s0 = (float)a01 * k0 + ((float)a00 + (float)a02) * k1;
+        const float s2 = (float)a21 * k0 + ((float)a20 + (float)a22) * k1;
+        float dy = s2 - s0;
+        const int gx = ox - 1 + rx, gy = oy - 1 + ry;
+        if (gx < 0 || gx >= w) dx = -dx;
+        if (gy < 0 || gy >= h) dy = -dy;
+        dxs[ry][rx] = dx, dys[ry][rx] = dy;
+    }
+    __syncthreads();
+    const int q = tid & 15, ty = tid >> 4;
+    const int x = ox + 4 * q, y = oy + ty;
+    int best = INT_MIN;
+    if (x < w && y < h) {
+        float a_[3][6], b_[3][6];
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+#pragma unroll
+            for (int i = 0; i < 6; i++) a_[j][i] = dxs[ty + j][4 * q + i], b_[j][i] = dys[ty + j][4 * q + i];
+        float ev[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            double sxx = 0, sxy = 0, syy = 0;
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+#pragma unroll
+                for (int i = 0; i < 3; i++) {
+                    const float a = a_[j][c + i], b = b_[j][c + i];
+                    sxx += (double)(a * a), sxy += (double)(a * b), syy += (double)(b * b);
+                }
+            const float a = (float)sxx, b = (float)sxy, cc = (float)syy, t = a + cc;
+            ev[c] = (a * cc - b * b) - (kf * t) * t;
+            if (x + c < w) best = max(best, __float_as_int(ev[c]));
+        }
+        float *o = eig + (size_t)y * w + x;
+        if (vec_ok && (w & 3) == 0 && x + 4 <= w) {
+            *reinterpret_cast<float4 *>(o) = make_float4(ev[0], ev[1], ev[2], ev[3]);
+        } else {
+            for (int c = 0; c < 4 && x + c < w; c++) o[c] = ev[c];
+        }
+    }
+    // frame maximum: DPP max inside each 16-lane row, one LDS atomic per row, one global atomic per block
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x111, 0xf, 0xf, false));
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x112, 0xf, 0xf, false));
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x114, 0xf, 0xf, false));
+    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x118, 0xf, 0xf, false));
+    if (q == 15) atomicMax(&bmax, best);
+    __syncthreads();
+    if (tid == 0) atomicMax(max_bits, bmax);
+}
+
 // =============================================================================================
 // k_corner_candidates -- goodFeaturesToTrack steps 4-5: threshold at
 // quality*max (THRESH_TOZERO, strict >), 3x3 dilate-compare, interior pixels only.  A candidate is
@@ -185,7 +265,7 @@ __device__ __forceinline__ float ubyte_f32(uint32_t v) {
 // eigenvalue for a survivor and -inf otherwise.  INTERIOR: every pixel of the tile is an interior pixel of the image.
 // MASKED (k_corners_fused_masked): a survivor also has a non-zero mask byte; `mtile` holds the tile's mask bytes in the layout of the
 // source tile (pixel (ty, tx) of the tile <-> mtile[ty + 3][tx + 4]).  Its neighbours compete in the maximum whatever their mask bytes say.
-template <bool DENSE, bool INTERIOR, bool MASKED = false>
+template <bool DENSE, bool INTERIOR, bool MASKED = false, bool HARRIS = false>
 __device__ __forceinline__ void cf_nonmax(const float (&es)[CF_EH][CF_EP], int tid, int ox, int oy, int w, int h, float thr_lb,
                                           unsigned long long *__restrict__ my_slots, unsigned int *bcount, float *__restrict__ dense,
                                           const uint8_t (*mtile)[CF_SW] = nullptr) {
@@ -236,9 +316,10 @@ __device__ __forceinline__ void cf_nonmax(const float (&es)[CF_EH][CF_EP], int t
 // load: the source tile, dword e of it <-> row e / 18, bytes 4 (e % 18) ..; a thread's three loads are in flight together
 // (MASKED, here and in cf_store, cf_products and cf_interior, changes nothing in the function: it gives k_corners_fused_masked instantiations of
 //  its own.  An instantiation that both kernels inlined would be cloned where k_corners_fused alone has it moved into its only caller, and
-//  the optimiser's choices behind that differ: the unmasked kernel's instructions stay exactly what they were this way.)
+//  the optimiser's choices behind that differ: the unmasked kernel's instructions stay exactly what they were this way.
+//  HARRIS is the same kind of tag for k_corners_fused_harris and k_corners_fused_harris_masked; it changes the code in cf_eigenvalues alone.)
 constexpr int CF_LOADS = (CF_SH * (CF_SW / 4) + 255) / 256;
-template <bool INTERIOR, bool MASKED = false>
+template <bool INTERIOR, bool MASKED = false, bool HARRIS = false>
 __device__ __forceinline__ void cf_load(uint32_t (&v)[CF_LOADS], const uint8_t *__restrict__ src, uint32_t pitch, int w, int h, int ox, int oy, bool vec_ok,
                                         int tid) {
 #pragma unroll
@@ -251,7 +332,7 @@ __device__ __forceinline__ void cf_load(uint32_t (&v)[CF_LOADS], const uint8_t *
         else v[k] = load4_reflect(src, pitch, w, h, ox - 4 + 4 * rd, oy - 3 + ry, vec_ok);
     }
 }
-template <bool MASKED = false>
+template <bool MASKED = false, bool HARRIS = false>
 __device__ __forceinline__ void cf_store(uint8_t (&tile)[CF_SH][CF_SW], const uint32_t (&v)[CF_LOADS], int tid) {
 #pragma unroll
     for (int k = 0; k < CF_LOADS; k++)
@@ -261,7 +342,7 @@ __device__ __forceinline__ void cf_store(uint8_t (&tile)[CF_SH][CF_SW], const ui
 // The mask bytes of the tile in the layout and with the addressing of cf_load: dwords where the mask's rows are dword aligned, bytes
 // otherwise -- but nothing is mirrored: a byte outside the image is never read and counts as zero ("masked out").  INTERIOR says that
 // the 72 x 38 bytes lie inside the image (the mask has the image's size), vec_ok that the MASK's base and pitch are 4-byte aligned.
-template <bool INTERIOR>
+template <bool INTERIOR, bool HARRIS = false>
 __device__ __forceinline__ void cf_load_mask(uint32_t (&v)[CF_LOADS], const uint8_t *__restrict__ mask, uint32_t pitch, int w, int h, int ox, int oy, bool vec_ok,
                                              int tid) {
 #pragma unroll
@@ -284,6 +365,7 @@ __device__ __forceinline__ void cf_load_mask(uint32_t (&v)[CF_LOADS], const uint
 }
 // whether one of the thread's mask dwords holds a non-zero byte of the 66 x 33 pixels the tile takes its maximum over: rows 2 .. 34 of
 // the 38, bytes 3 .. 68 of the 72 (the last byte of the first dword, the first byte of the last, every byte of those between)
+template <bool HARRIS = false>
 __device__ __forceinline__ bool cf_mask_any(const uint32_t (&v)[CF_LOADS], int tid) {
     bool any = false;
 #pragma unroll
@@ -297,7 +379,7 @@ __device__ __forceinline__ bool cf_mask_any(const uint32_t (&v)[CF_LOADS], int t
 }
 
 // prod: product entry (r, q) <-> image (oy - 2 + r, ox - 2 + q) <-> tile[r + 1][q + 2]; a thread owns q = 4c .. 4c+3, r = 5g .. 5g+4
-template <bool INTERIOR, bool MASKED = false>
+template <bool INTERIOR, bool MASKED = false, bool HARRIS = false>
 __device__ __forceinline__ void cf_products(const uint8_t (&tile)[CF_SH][CF_SW], float (&prod)[3][CF_DH][CF_DP], int ox, int oy, int w, int h, int tid) {
     if (tid >= CF_PC * CF_PG) return;
     const float scale = (float)(1.0 / (4.0 * 3.0 * 255.0));
@@ -350,9 +432,12 @@ __device__ __forceinline__ void cf_sum3of5(double p0, double p1, double p2, doub
 // eigenvalue is stored.  Returns the thread's maximum over the in-image eigenvalues (int-bit order, as k_min_eig).
 // MASKED: the maximum runs over the eigenvalues with a non-zero mask byte instead (entry (ey, ex) <-> mtile[ey + 2][ex + 3]; a byte outside
 // the image is zero there).  The mask bytes must be in `mtile` before the call: the barrier in here orders them before their readers.
-template <bool INTERIOR, bool MASKED = false>
+// HARRIS: the response is R = (a c - b b) - (kf t) t with t = a + c over the box sums as they are (vstab.h, "Harris response"; no
+// contraction in this unit); it is negative over much of an ordinary frame, and the int-bit maximum of a tile without a value >= +0 is
+// negative: cf_tile filters such a tile with -inf, and whether the FRAME's maximum is positive the host reads from its sign.
+template <bool INTERIOR, bool MASKED = false, bool HARRIS = false>
 __device__ __forceinline__ int cf_eigenvalues(const float (&prod)[3][CF_DH][CF_DP], float (&es)[CF_EH][CF_EP], int ox, int oy, int w, int h, int tid,
-                                              const uint8_t (*mtile)[CF_SW] = nullptr) {
+                                              const uint8_t (*mtile)[CF_SW] = nullptr, float kf = 0.0f) {
     const bool active = tid < CF_BX * CF_BY;
     const int t = min(tid, CF_BX * CF_BY - 1);  // the 14 threads without a block add up the last one's sums and store nothing
     const int by = __mul24(t, 2979) >> 16, bx = t - by * CF_BX;
@@ -384,8 +469,14 @@ __device__ __forceinline__ int cf_eigenvalues(const float (&prod)[3][CF_DH][CF_D
         for (int e = 0; e < 3; e++)
 #pragma unroll
             for (int i = 0; i < 3; i++) {
-                const float a = sum[0][e][i] * 0.5f, b = sum[1][e][i], cc = sum[2][e][i] * 0.5f;
-                const float ev = (a + cc) - sqrtf((a - cc) * (a - cc) + b * b);
+                float ev;
+                if (HARRIS) {
+                    const float a = sum[0][e][i], b = sum[1][e][i], cc = sum[2][e][i], t = a + cc;
+                    ev = (a * cc - b * b) - (kf * t) * t;
+                } else {
+                    const float a = sum[0][e][i] * 0.5f, b = sum[1][e][i], cc = sum[2][e][i] * 0.5f;
+                    ev = (a + cc) - sqrtf((a - cc) * (a - cc) + b * b);
+                }
                 es[3 * by + e][3 * bx + i] = ev;
                 const int gx = ox - 1 + 3 * bx + i, gy = oy - 1 + 3 * by + e;
                 if (MASKED) {
@@ -403,21 +494,21 @@ __device__ __forceinline__ int cf_eigenvalues(const float (&prod)[3][CF_DH][CF_D
 //   - the tile maximum, and with it the published frame maximum, runs over the eigenvalues with a non-zero mask byte;
 //   - a survivor has a non-zero mask byte (cf_nonmax), while the 3 x 3 maximum it is compared with knows no mask.
 // The mask bytes wait in three registers while the source tile is in use and take its place in LDS behind the products.
-template <bool INTERIOR, bool MASKED = false>
+template <bool INTERIOR, bool MASKED = false, bool HARRIS = false>
 __device__ __forceinline__ void cf_tile(uint8_t (&tile)[CF_SH][CF_SW], float (&prod)[3][CF_DH][CF_DP], int &bmax, unsigned int &bcount, unsigned int &bseen,
                                         const uint8_t *__restrict__ src, uint32_t pitch, int w, int h, double quality, unsigned int *__restrict__ max_key,
                                         unsigned long long *__restrict__ slots, unsigned int *__restrict__ tile_counts, float *__restrict__ spill, bool vec_ok,
-                                        const uint8_t *__restrict__ mask = nullptr, uint32_t mpitch = 0, bool mvec_ok = false) {
+                                        const uint8_t *__restrict__ mask = nullptr, uint32_t mpitch = 0, bool mvec_ok = false, float kf = 0.0f) {
     float (&es)[CF_EH][CF_EP] = *reinterpret_cast<float (*)[CF_EH][CF_EP]>(&prod[0][0][0]);
     const int tid = threadIdx.x;
     const int ox = blockIdx.x * CF_TW, oy = blockIdx.y * CF_TH;
     uint32_t mv[CF_LOADS];
     if (MASKED) {
-        cf_load_mask<INTERIOR>(mv, mask, mpitch, w, h, ox, oy, mvec_ok, tid);
+        cf_load_mask<INTERIOR, HARRIS>(mv, mask, mpitch, w, h, ox, oy, mvec_ok, tid);
         // one flag per wave in LDS nobody uses yet (prod is first written behind the barrier that follows cf_store), one barrier, the
         // same answer in every thread
         uint32_t *flags = reinterpret_cast<uint32_t *>(&prod[2][0][0]);
-        const bool mine = __builtin_amdgcn_ballot_w64(cf_mask_any(mv, tid)) != 0;
+        const bool mine = __builtin_amdgcn_ballot_w64(cf_mask_any<HARRIS>(mv, tid)) != 0;
         if ((tid & 63) == 0) flags[tid >> 6] = mine;
         __syncthreads();
         if ((flags[0] | flags[1] | flags[2] | flags[3]) == 0) {
@@ -426,9 +517,9 @@ __device__ __forceinline__ void cf_tile(uint8_t (&tile)[CF_SH][CF_SW], float (&p
         }
     }
     uint32_t v[CF_LOADS];
-    cf_load<INTERIOR, MASKED>(v, src, pitch, w, h, ox, oy, vec_ok, tid);
+    cf_load<INTERIOR, MASKED, HARRIS>(v, src, pitch, w, h, ox, oy, vec_ok, tid);
     if (tid == 0) bmax = INT_MIN, bcount = 0;
-    cf_store<MASKED>(tile, v, tid);
+    cf_store<MASKED, HARRIS>(tile, v, tid);
     // frame maximum published so far (biased bits): a lower bound of the final one.  Device-scope load: the atomics
     // of other XCDs do not pass through this XCD's L2.  Every workgroup reads this one address, and the memory side serves
     // such reads one after the other: ONE lane asks -- in the last wave, which has no part in the products, and behind
@@ -437,10 +528,10 @@ __device__ __forceinline__ void cf_tile(uint8_t (&tile)[CF_SH][CF_SW], float (&p
     unsigned int seen = 0;
     if (tid == 255) seen = __hip_atomic_load(max_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    cf_products<INTERIOR, MASKED>(tile, prod, ox, oy, w, h, tid);
+    cf_products<INTERIOR, MASKED, HARRIS>(tile, prod, ox, oy, w, h, tid);
     __syncthreads();
-    if (MASKED) cf_store<MASKED>(tile, mv, tid);  // the source bytes are dead; cf_eigenvalues' barrier stands between this and the first reader
-    int best = cf_eigenvalues<INTERIOR, MASKED>(prod, es, ox, oy, w, h, tid, tile);
+    if (MASKED) cf_store<MASKED, HARRIS>(tile, mv, tid);  // the source bytes are dead; cf_eigenvalues' barrier stands between this and the first reader
+    int best = cf_eigenvalues<INTERIOR, MASKED, HARRIS>(prod, es, ox, oy, w, h, tid, tile, kf);
     // tile maximum (same int-bit order as k_min_eig)
     best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x111, 0xf, 0xf, false));
     best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x112, 0xf, 0xf, false));
@@ -460,17 +551,17 @@ __device__ __forceinline__ void cf_tile(uint8_t (&tile)[CF_SH][CF_SW], float (&p
     const int lb_bits = max(tile_max, (int)(seen ^ 0x80000000u));
     const float thr_lb = lb_bits >= 0 ? (float)((double)__int_as_float(lb_bits) * quality) : -__builtin_inff();
     const int tile_idx = blockIdx.y * gridDim.x + blockIdx.x;
-    cf_nonmax<false, INTERIOR, MASKED>(es, tid, ox, oy, w, h, thr_lb, slots + (size_t)tile_idx * CF_SLOTS, &bcount, nullptr, tile);
+    cf_nonmax<false, INTERIOR, MASKED, HARRIS>(es, tid, ox, oy, w, h, thr_lb, slots + (size_t)tile_idx * CF_SLOTS, &bcount, nullptr, tile);
     __syncthreads();
     const unsigned int n = bcount;
     if (tid == 0) tile_counts[tile_idx] = n;
     // A tile with more survivors than slots (an eigenvalue plateau: a smooth ramp, a periodic texture) leaves them as a
     // dense 64 x 31 map instead (-inf = not a survivor); k_filter_keys scans that with the final threshold.
-    if (n > CF_SLOTS) cf_nonmax<true, INTERIOR, MASKED>(es, tid, ox, oy, w, h, thr_lb, nullptr, nullptr, spill + (size_t)tile_idx * (CF_TW * CF_TH), tile);
+    if (n > CF_SLOTS) cf_nonmax<true, INTERIOR, MASKED, HARRIS>(es, tid, ox, oy, w, h, thr_lb, nullptr, nullptr, spill + (size_t)tile_idx * (CF_TW * CF_TH), tile);
 }
 
 // the tile's 72 x 38 source bytes at image (oy - 3 .., ox - 4 ..) lie inside the image, and its rows are dword aligned
-template <bool MASKED = false>
+template <bool MASKED = false, bool HARRIS = false>
 __device__ __forceinline__ bool cf_interior(int ox, int oy, int w, int h, int vec_ok) {
     return vec_ok && ox >= 4 && ox - 4 + CF_SW <= w && oy >= 3 && oy - 3 + CF_SH <= h;
 }
@@ -507,6 +598,42 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     else
         cf_tile<false, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0, mask,
                              (uint32_t)mpitch, mvec_ok != 0);
+}
+
+// k_corners_fused_harris, k_corners_fused_harris_masked -- the two kernels above with the Harris response (goodFeaturesToTrack's
+// useHarrisDetector and k; vstab.h, "Harris response"): cf_tile<., ., HARRIS = true>, kf = (float)k.  Everything behind the response is
+// shared: a candidate lies above a non-negative threshold wherever the frame has a positive maximum, so its bits order as its value and
+// k_filter_keys serves both.  A frame (under a mask: its masked-in part) without a positive response publishes a maximum with the sign
+// bit set; the host reports no corner then (Tracker::good_features, Tracker::spec_select).
+// (The masked kernel does not need the amdgpu_waves_per_eu(4, 4) of its sibling: left alone the compiler takes 100 VGPRs for it, under
+//  the 128 of four workgroups per CU, and 119 for the unmasked one.  DESIGN.md section 26 has the table.)
+__global__ void __launch_bounds__(256) k_corners_fused_harris(const uint8_t *__restrict__ src, size_t pitch, int w, int h, double quality,
+                                                              unsigned int *__restrict__ max_key, unsigned long long *__restrict__ slots,
+                                                              unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok, float kf) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];
+    __shared__ __attribute__((aligned(16))) float prod[3][CF_DH][CF_DP];
+    __shared__ int bmax;
+    __shared__ unsigned int bcount, bseen;
+    if (cf_interior<false, true>(blockIdx.x * CF_TW, blockIdx.y * CF_TH, w, h, vec_ok))
+        cf_tile<true, false, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true, nullptr, 0, false, kf);
+    else
+        cf_tile<false, false, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0, nullptr, 0,
+                                    false, kf);
+}
+
+__global__ void __launch_bounds__(256) k_corners_fused_harris_masked(
+    const uint8_t *__restrict__ src, size_t pitch, int w, int h, double quality, unsigned int *__restrict__ max_key, unsigned long long *__restrict__ slots,
+    unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok, const uint8_t *__restrict__ mask, size_t mpitch, int mvec_ok, float kf) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];
+    __shared__ __attribute__((aligned(16))) float prod[3][CF_DH][CF_DP];
+    __shared__ int bmax;
+    __shared__ unsigned int bcount, bseen;
+    if (cf_interior<true, true>(blockIdx.x * CF_TW, blockIdx.y * CF_TH, w, h, vec_ok))
+        cf_tile<true, true, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true, mask, (uint32_t)mpitch,
+                                  mvec_ok != 0, kf);
+    else
+        cf_tile<false, true, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0, mask,
+                                   (uint32_t)mpitch, mvec_ok != 0, kf);
 }
 
 // The two-pass detector under a mask: k_min_eig as it is, then
@@ -636,6 +763,16 @@ vstab_status launch_min_eig(const uint8_t *src, size_t pitch, int w, int h, floa
     return VSTAB_OK;
 }
 
+// launch_min_eig with the Harris response (k_corner_harris): resp is the dense w x h map, *max_bits its int-bit maximum
+vstab_status launch_corner_harris(const uint8_t *src, size_t pitch, int w, int h, float kf, float *resp, int *max_bits, hipStream_t s) {
+    VSTAB_HIP_TRY(hipMemsetAsync(max_bits, 0x80, sizeof(int), s));  // as launch_min_eig
+    const int vec_ok = reinterpret_cast<uintptr_t>(src) % 4 == 0 && pitch % 4 == 0 && reinterpret_cast<uintptr_t>(resp) % 16 == 0;
+    dim3 grid(div_up(w, ME_TW), div_up(h, ME_TH));
+    hipLaunchKernelGGL(k_corner_harris, grid, dim3(256), 0, s, src, pitch, w, h, resp, max_bits, vec_ok, kf);
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
 // the masked maximum of an eigenvalue map (behind launch_min_eig, whose max_bits holds the maximum of the whole frame) into *masked_max_bits
 vstab_status launch_masked_max(const float *eig, int w, int h, const uint8_t *mask, size_t mpitch, int *masked_max_bits, hipStream_t s) {
     VSTAB_HIP_TRY(hipMemsetAsync(masked_max_bits, 0x80, sizeof(int), s));  // as launch_min_eig
@@ -656,14 +793,15 @@ vstab_status launch_corner_candidates(const float *eig, int w, int h, const int 
 }
 
 // Fused detector (mask, optional: a w x h plane of bytes of pitch mpitch with (uint64_t)mpitch * h < 2^32; k_corners_fused_masked takes
-// the place of k_corners_fused then, everything else is the same).  small: 8 dwords of device memory {biased maximum bits, -, -, -, keys kept, tiles that spilled, -, -};
+// the place of k_corners_fused then, everything else is the same; harris: the Harris response with kf = (float)k in place of the minimum
+// eigenvalue, k_corners_fused_harris / k_corners_fused_harris_masked -- small[0] then says whether the frame has a positive response at all).  small: 8 dwords of device memory {biased maximum bits, -, -, -, keys kept, tiles that spilled, -, -};
 // scratch: corners_fused_scratch_bytes(w, h) (per tile: 256 key slots, a count, and room for a dense 64 x 31 map that
 // only a tile with more survivors than slots writes).  On return (stream order) keys holds min(small[4], cap) keys; the
 // result is complete iff small[4] <= cap.
 size_t corners_fused_scratch_bytes(int w, int h) { return CornersFusedScratch(w, h).bytes; }
 
 vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h, double quality, void *scratch, unsigned long long *keys,
-                                  unsigned int cap, unsigned int *small, hipStream_t s, const uint8_t *mask, size_t mpitch) {
+                                  unsigned int cap, unsigned int *small, hipStream_t s, const uint8_t *mask, size_t mpitch, bool harris, float kf) {
     VSTAB_HIP_TRY(hipMemsetAsync(small, 0, 8 * sizeof(unsigned int), s));
     const int vec_ok = reinterpret_cast<uintptr_t>(src) % 4 == 0 && pitch % 4 == 0;
     const CornersFusedScratch lay(w, h);
@@ -671,7 +809,14 @@ vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h
     unsigned long long *slots = reinterpret_cast<unsigned long long *>(base + lay.slots_off);
     float *spill = reinterpret_cast<float *>(base + lay.spill_off);
     unsigned int *tile_counts = reinterpret_cast<unsigned int *>(base + lay.counts_off);
-    if (mask) {
+    if (harris && mask) {
+        const int mvec_ok = reinterpret_cast<uintptr_t>(mask) % 4 == 0 && mpitch % 4 == 0;
+        hipLaunchKernelGGL(k_corners_fused_harris_masked, dim3(lay.tiles_x, lay.tiles_y), dim3(256), 0, s, src, pitch, w, h, quality, small, slots, tile_counts, spill,
+                           vec_ok, mask, mpitch, mvec_ok, kf);
+    } else if (harris) {
+        hipLaunchKernelGGL(k_corners_fused_harris, dim3(lay.tiles_x, lay.tiles_y), dim3(256), 0, s, src, pitch, w, h, quality, small, slots, tile_counts, spill, vec_ok,
+                           kf);
+    } else if (mask) {
         const int mvec_ok = reinterpret_cast<uintptr_t>(mask) % 4 == 0 && mpitch % 4 == 0;
         hipLaunchKernelGGL(k_corners_fused_masked, dim3(lay.tiles_x, lay.tiles_y), dim3(256), 0, s, src, pitch, w, h, quality, small, slots, tile_counts, spill,
                            vec_ok, mask, mpitch, mvec_ok);
@@ -689,7 +834,7 @@ vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h
 vstab_status preload_corner_kernels() {
     hipFuncAttributes at;
     VSTAB_HIP_TRY(hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&k_corners_fused)));
-    // (k_corners_fused_masked, k_masked_max and k_corner_candidates_masked are kernels of this unit: the same code object, loaded with it)
+    // (k_corners_fused_masked, k_masked_max, k_corner_candidates_masked and the Harris kernels are kernels of this unit: the same code object, loaded with it)
     return VSTAB_OK;
 }
 

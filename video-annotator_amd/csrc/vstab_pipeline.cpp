@@ -699,6 +699,19 @@ vstab_status vstab_set_detection_mask(vstab_handle *h, const void *mask, size_t 
     return h->tracker.copy_mask(mask, pitch_mask, mem == VSTAB_MEM_HOST);
 }
 
+// The handle's corner response: read by every detection of the handle, as the mask is (Tracker::set_response).
+vstab_status vstab_set_corner_response(vstab_handle *h, int response, double k) {
+    const std::string n = "vstab_set_corner_response: ";
+    if (!h) return fail(VSTAB_ERR_INVALID, n + "null handle");
+    if (!h->cfg.tracking) return fail(VSTAB_ERR_INVALID, n + "no detector runs on this handle (tracking = 0)");
+    if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the response must be set before the first pull");
+    if (response != VSTAB_CORNER_MIN_EIGENVAL && response != VSTAB_CORNER_HARRIS)
+        return fail(VSTAB_ERR_INVALID, n + "response must be VSTAB_CORNER_MIN_EIGENVAL (0) or VSTAB_CORNER_HARRIS (1)");
+    if (response == VSTAB_CORNER_HARRIS && !harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, n + "k lies in [0, 0.25)");
+    h->tracker.set_response(response == VSTAB_CORNER_HARRIS, (float)k);
+    return VSTAB_OK;
+}
+
 vstab_status vstab_set_input_calibration_ex(vstab_handle *h, const double K[9], const double D[4]) {
     return set_input_calibration(h, K, D, "vstab_set_input_calibration_ex", true);
 }

@@ -142,20 +142,34 @@ vstab_status vstab_min_eig(const void *gray, size_t pitch, int width, int height
     return VSTAB_OK;
 }
 
-// vstab_good_features_ex (fn "vstab_good_features", no mask, VSTAB_DETECTOR_FUSED refused as ever) and vstab_good_features_mask
+// vstab_min_eig's twin: cornerHarris(gray, response, 3, 3, k) as a dense device map ("Harris response" in vstab.h)
+vstab_status vstab_corner_harris(const void *gray, size_t pitch, int width, int height, double k, void *response, void *stream) {
+    if (!gray || !response || width <= 0 || height <= 0 || pitch < (size_t)width) return fail(VSTAB_ERR_INVALID, "vstab_corner_harris: bad argument");
+    if (!harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, "vstab_corner_harris: k lies in [0, 0.25)");
+    DevBuf mb;
+    VSTAB_TRY(mb.ensure(16));
+    VSTAB_TRY(launch_corner_harris((const uint8_t *)gray, pitch, width, height, (float)k, (float *)response, mb.as<int>(), static_cast<hipStream_t>(stream)));
+    VSTAB_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    return VSTAB_OK;
+}
+
+// vstab_good_features_ex (fn "vstab_good_features", no mask, VSTAB_DETECTOR_FUSED refused as ever), vstab_good_features_mask and
+// vstab_good_features_harris (harris: the Harris response with k, checked last)
 static vstab_status good_features_op(const char *fn, bool fused_ok, const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask,
                                      int max_corners, double quality, double min_distance, int detector, float *xy, int *count, int *detector_used,
-                                     void *stream) {
+                                     void *stream, bool harris = false, double k = 0.0) {
     if (!gray || !xy || !count || width < 3 || height < 3 || pitch < (size_t)width || max_corners <= 0 ||
         (detector != VSTAB_DETECTOR_AUTO && detector != VSTAB_DETECTOR_TWO_PASS && !(fused_ok && detector == VSTAB_DETECTOR_FUSED)))
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": bad argument");
     if (mask && pitch_mask < (size_t)width) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": the mask's pitch is smaller than the image's width");
     if (mask && (uint64_t)pitch_mask * (uint64_t)height >= (1ull << 32))
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": mask planes of 4 GiB or more are not supported");
+    if (harris && !harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": k lies in [0, 0.25)");
     Tracker t;
     VSTAB_TRY(t.init(width, height));
     t.set_two_pass_detector(detector == VSTAB_DETECTOR_TWO_PASS);
     t.set_mask(static_cast<const uint8_t *>(mask), pitch_mask);
+    t.set_response(harris, (float)k);
     std::vector<float> out;
     VSTAB_TRY(t.good_features((const uint8_t *)gray, pitch, max_corners, quality, min_distance, out, static_cast<hipStream_t>(stream)));
     *count = (int)(out.size() / 2);
@@ -174,6 +188,12 @@ vstab_status vstab_good_features_mask(const void *gray, size_t pitch, int width,
                                       double quality, double min_distance, int detector, float *xy, int *count, int *detector_used, void *stream) {
     return good_features_op("vstab_good_features_mask", true, gray, pitch, width, height, mask, pitch_mask, max_corners, quality, min_distance, detector, xy,
                             count, detector_used, stream);
+}
+
+vstab_status vstab_good_features_harris(const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask, int max_corners,
+                                        double quality, double min_distance, double k, int detector, float *xy, int *count, int *detector_used, void *stream) {
+    return good_features_op("vstab_good_features_harris", true, gray, pitch, width, height, mask, pitch_mask, max_corners, quality, min_distance, detector, xy,
+                            count, detector_used, stream, true, k);
 }
 
 vstab_status vstab_good_features(const void *gray, size_t pitch, int width, int height, int max_corners, double quality,

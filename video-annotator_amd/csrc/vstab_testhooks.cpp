@@ -159,9 +159,10 @@ __attribute__((visibility("default"))) int vstabx_lk_segments(const void *const 
 }
 
 // the body of vstabx_corners_fused and vstabx_corners_fused_mask (both below); fn names the hook in the refusals, masked says whether `mask` is looked at
+// harris: the Harris response with k, checked last; max_out (optional) receives the frame maximum the kernels published, as int32 float bits
 static int corners_fused_hook(const std::string &fn, const void *gray, size_t pitch, int w, int h, const void *mask, size_t pitch_mask, bool masked, double quality,
                               unsigned int cap, unsigned int canary, unsigned long long *keys_out, unsigned int *counts_out, unsigned int *tile_counts,
-                              void *stream) {
+                              void *stream, bool harris = false, double k = 0.0, int *max_out = nullptr) {
     if (!gray || !keys_out || !counts_out || !tile_counts || (masked && !mask)) return fail(VSTAB_ERR_INVALID, fn + ": bad argument");
     if (w < 3 || h < 3 || pitch < (size_t)w) return fail(VSTAB_ERR_INVALID, fn + ": an image is at least 3 x 3 and its pitch at least its width");
     if ((uint64_t)pitch * (uint64_t)h >= (1ull << 32) || (uint64_t)w * (uint64_t)h >= (1ull << 31))
@@ -171,6 +172,7 @@ static int corners_fused_hook(const std::string &fn, const void *gray, size_t pi
     if (canary < 1 || canary > (1u << 16)) return fail(VSTAB_ERR_INVALID, fn + ": canary is 1 .. 2^16 keys");
     if (masked && pitch_mask < (size_t)w) return fail(VSTAB_ERR_INVALID, fn + ": the mask's pitch is smaller than the image's width");
     if (masked && (uint64_t)pitch_mask * (uint64_t)h >= (1ull << 32)) return fail(VSTAB_ERR_INVALID, fn + ": mask planes of 4 GiB or more are not supported");
+    if (harris && !harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, fn + ": k lies in [0, 0.25)");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const CornersFusedScratch lay(w, h);  // the layout launch_corners_fused uses: the survivor counts are read back from it below
     const size_t scratch_bytes = lay.bytes;
@@ -183,11 +185,13 @@ static int corners_fused_hook(const std::string &fn, const void *gray, size_t pi
     VSTAB_HIP_TRY(hipMemsetAsync(scratch.p, masked ? 0xA5 : 0, scratch_bytes, st));
     VSTAB_HIP_TRY(hipMemsetAsync(keys.p, 0xA5, n_keys * sizeof(unsigned long long), st));
     VSTAB_TRY(launch_corners_fused(static_cast<const uint8_t *>(gray), pitch, w, h, quality, scratch.p, keys.as<unsigned long long>(), cap, small.as<unsigned int>(), st,
-                                   static_cast<const uint8_t *>(mask), pitch_mask));
+                                   static_cast<const uint8_t *>(mask), pitch_mask, harris, (float)k));
     VSTAB_HIP_TRY(hipMemcpyAsync(keys_out, keys.p, n_keys * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipMemcpyAsync(counts_out, small.as<unsigned int>() + 4, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    if (max_out) VSTAB_HIP_TRY(hipMemcpyAsync(max_out, small.p, sizeof(int), hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipMemcpyAsync(tile_counts, scratch.as<uint8_t>() + lay.counts_off, (size_t)lay.tiles * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipStreamSynchronize(st));
+    if (max_out) *max_out = (int)((unsigned int)*max_out ^ 0x80000000u);  // the kernels keep it biased (unsigned order); 0 there = nothing published = INT_MIN here
     return VSTAB_OK;
 }
 // THE RAW OUTPUT OF THE ONE-PASS DETECTOR (tests/test_corner_paths_gpu.py; its argument checks run without a device:
@@ -212,6 +216,16 @@ __attribute__((visibility("default"))) int vstabx_corners_fused_mask(const void 
                                                                       unsigned int cap, unsigned int canary, unsigned long long *keys_out, unsigned int *counts_out,
                                                                       unsigned int *tile_counts, void *stream) {
     return corners_fused_hook("vstabx_corners_fused_mask", gray, pitch, w, h, mask, pitch_mask, true, quality, cap, canary, keys_out, counts_out, tile_counts, stream);
+}
+// vstabx_corners_fused / vstabx_corners_fused_mask with the Harris response (tests/test_harris_gpu.py, tests/harris_def.py):
+// k_corners_fused_harris or, with a mask (optional here: NULL = none), k_corners_fused_harris_masked, then k_filter_keys.  The same outputs
+// and refusals under this hook's name, then "k lies in [0, 0.25)"; max_bits_out (optional): the frame maximum the kernels published, the
+// bits of a float read as int32 -- negative means "no response above zero", where the host reports no corner whatever the keys say.
+__attribute__((visibility("default"))) int vstabx_corners_fused_harris(const void *gray, size_t pitch, int w, int h, const void *mask, size_t pitch_mask, double quality,
+                                                                        double k, unsigned int cap, unsigned int canary, unsigned long long *keys_out,
+                                                                        unsigned int *counts_out, unsigned int *tile_counts, int *max_bits_out, void *stream) {
+    return corners_fused_hook("vstabx_corners_fused_harris", gray, pitch, w, h, mask, pitch_mask, mask != nullptr, quality, cap, canary, keys_out, counts_out,
+                              tile_counts, stream, true, k, max_bits_out);
 }
 
 // The cost-weighted XCD bands of the fused warp (vstab_warp_bands.hpp; tests/test_band_schedule_cpu.py), no device needed.

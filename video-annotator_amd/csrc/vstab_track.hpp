@@ -40,6 +40,10 @@ bool pyr_down_x2_ok(int sw, int sh);
 vstab_status launch_pyr_down_x2(const uint8_t *src, size_t spitch, int sw, int sh, uint8_t *mid, size_t mpitch, uint8_t *dst, size_t dpitch, hipStream_t s,
                                 hipEvent_t done = nullptr);
 vstab_status launch_min_eig(const uint8_t *src, size_t pitch, int w, int h, float *eig, int *max_bits, hipStream_t s);
+// k of the Harris response (vstab.h, "Harris response"): finite, 0 <= k < 0.25 -- from 0.25 on det - k tr^2 is never positive
+inline bool harris_k_ok(double k) { return k >= 0.0 && k < 0.25; }
+// launch_min_eig with the Harris response (kf = (float)k): cornerHarris(3, 3, k) as a dense map and its int-bit maximum
+vstab_status launch_corner_harris(const uint8_t *src, size_t pitch, int w, int h, float kf, float *resp, int *max_bits, hipStream_t s);
 // mask (optional, here and in launch_corners_fused): the detection mask, a w x h plane of bytes of pitch mpitch, non-zero = "a corner may
 // be reported here" (vstab.h, "Detection mask").  Without one the launches are those of the unmasked detector.  With one, max_bits of
 // launch_corner_candidates is the MASKED maximum (launch_masked_max behind launch_min_eig).
@@ -61,7 +65,8 @@ struct CornersFusedScratch {
 };
 size_t corners_fused_scratch_bytes(int w, int h);
 vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h, double quality, void *scratch, unsigned long long *keys,
-                                  unsigned int cap, unsigned int *small, hipStream_t s, const uint8_t *mask = nullptr, size_t mpitch = 0);
+                                  unsigned int cap, unsigned int *small, hipStream_t s, const uint8_t *mask = nullptr, size_t mpitch = 0, bool harris = false,
+                                  float kf = 0.0f);
 // One tracker launch = a SEGMENT of up to LK_SEG_MAX consecutive frame pairs (k_lk_track): pair i is (pyr[i], pyr[i + 1]).
 //   prev_pts  the n start points of pair 0 (device-readable), or NULL when
 //   chain_in  the device records of the parent launch's last pair, whose sequence number is parent_seq: slot f starts from the

@@ -154,21 +154,31 @@ vstab_status Tracker::good_features(const uint8_t *gray, size_t pitch, int max_c
         // one pass: eigenvalue, threshold and 3x3 maximum test fused, the eigenvalue map never stored
         VSTAB_TRY(raw_keys_.ensure(corners_fused_scratch_bytes(w_, h_)));
 #ifdef VSTAB_DEV
-        if (getenv("VSTAB_DEV_DET_TWICE")) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st, mask_, mask_pitch_));
+        if (getenv("VSTAB_DEV_DET_TWICE")) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st, mask_, mask_pitch_, harris_, harris_kf_));
 #endif
-        VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st, mask_, mask_pitch_));
+        VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st, mask_, mask_pitch_,
+                                       harris_, harris_kf_));
         VSTAB_HIP_TRY(hipMemcpyAsync(hsmall_.p, count, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+        if (harris_) VSTAB_HIP_TRY(hipMemcpyAsync(hsmall_.as<unsigned int>() + 2, small_.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));  // the biased maximum
         VSTAB_HIP_TRY(hipStreamSynchronize(st));
+        // Harris: a maximum with the sign bit set (biased: below 2^31; 0 = no tile published one) means no response above zero, and no corner
+        if (harris_ && hsmall_.as<unsigned int>()[2] < 0x80000000u) return VSTAB_OK;
         const unsigned int kept = hsmall_.as<unsigned int>()[0];
         if (kept <= cap_) return select_from_keys(kept, max_corners, min_distance, xy, st);
         fused_overflows_++;  // more corners above the threshold than the key buffer holds: the two-pass detector below grows it
     }
     VSTAB_TRY(eig_.ensure(sizeof(float) * (size_t)w_ * h_));
     if (!eig) eig = eig_.as<float>();
-    VSTAB_TRY(launch_min_eig(gray, pitch, w_, h_, eig, max_bits, st));
+    if (harris_) VSTAB_TRY(launch_corner_harris(gray, pitch, w_, h_, harris_kf_, eig, max_bits, st));
+    else VSTAB_TRY(launch_min_eig(gray, pitch, w_, h_, eig, max_bits, st));
     if (mask_) {  // the threshold of a masked detection comes from the maximum over the masked-in pixels: small_[1], beside the frame's
         VSTAB_TRY(launch_masked_max(eig, w_, h_, mask_, mask_pitch_, max_bits + 1, st));
         max_bits += 1;
+    }
+    if (harris_) {  // as above: the sign of the (masked) maximum, before a key buffer grows for candidates above a negative threshold
+        VSTAB_HIP_TRY(hipMemcpyAsync(hsmall_.p, max_bits, sizeof(int), hipMemcpyDeviceToHost, st));
+        VSTAB_HIP_TRY(hipStreamSynchronize(st));
+        if (*hsmall_.as<int>() < 0) return VSTAB_OK;
     }
     unsigned int n = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
@@ -193,10 +203,12 @@ vstab_status Tracker::spec_launch(const uint8_t *gray, size_t pitch, double qual
     unsigned int *count = spec_small_.as<unsigned int>() + 4;
 #ifdef VSTAB_DEV
     static const bool det_twice = getenv("VSTAB_DEV_DET_TWICE") != nullptr;  // sensitivity of the frame rate to the detector: everything twice, same result
-    if (det_twice) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st, mask_, mask_pitch_));
+    if (det_twice) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st, mask_, mask_pitch_, harris_, harris_kf_));
 #endif
-    VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st, mask_, mask_pitch_));
+    VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st, mask_, mask_pitch_,
+                                   harris_, harris_kf_));
     VSTAB_HIP_TRY(hipMemcpyAsync(spec_host_.p, count, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));  // {keys kept, tiles that spilled}
+    if (harris_) VSTAB_HIP_TRY(hipMemcpyAsync(spec_host_.as<unsigned int>() + 2, spec_small_.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));  // the biased maximum
     VSTAB_HIP_TRY(hipMemcpyAsync(spec_host_.as<uint8_t>() + 64, spec_keys_.p, sizeof(unsigned long long) * SPEC_CAP, hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipEventRecord(spec_ev_, st));
     spec_tag_ = tag;
@@ -204,7 +216,8 @@ vstab_status Tracker::spec_launch(const uint8_t *gray, size_t pitch, double qual
 }
 
 int Tracker::spec_select(int max_corners, double min_distance, std::vector<float> &xy, unsigned int *n_seen) {
-    const unsigned int n = spec_host_.as<unsigned int>()[0];
+    unsigned int n = spec_host_.as<unsigned int>()[0];
+    if (harris_ && spec_host_.as<unsigned int>()[2] < 0x80000000u) n = 0;  // no response above zero: no corner (good_features has the same test)
     if (n_seen) *n_seen = n;
     if (n > SPEC_CAP) {
         spec_over_cap_.fetch_add(1, std::memory_order_relaxed);

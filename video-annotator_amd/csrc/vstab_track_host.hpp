@@ -78,6 +78,11 @@ class Tracker {
     vstab_status copy_mask(const void *mask, size_t pitch, bool host);
     const uint8_t *mask() const { return mask_; }
     size_t mask_pitch() const { return mask_pitch_; }
+    // The corner response (vstab.h, "Harris response"): harris = false is cornerMinEigenVal(3, 3), the Tracker as it always was (kf is
+    // not looked at); harris = true is cornerHarris(3, 3, k) with kf = (float)k, read by every detection from now on -- good_features (its
+    // three paths, and the map it hands out through eig_out) and spec_launch.  Under it a frame whose (masked) maximum is not positive has
+    // no corner: decided on the host from the sign of the maximum the kernels publish.  Only while nothing is in flight.
+    void set_response(bool harris, float kf) { harris_ = harris, harris_kf_ = harris ? kf : 0.0f; }
     long fused_overflows() const { return fused_overflows_; }
     // (vstabx_detector_counters) speculative selections that found more than SPEC_CAP candidates; the key capacity of good_features now
     long spec_over_cap() const { return spec_over_cap_.load(std::memory_order_relaxed); }
@@ -198,6 +203,8 @@ class Tracker {
     const uint8_t *mask_ = nullptr;  // the detection mask in force (mask_buf_'s, or a caller's), NULL for none
     size_t mask_pitch_ = 0;
     DevBuf mask_buf_;
+    bool harris_ = false;  // the response in force: cornerHarris(3, 3, k) with harris_kf_ = (float)k, or cornerMinEigenVal(3, 3)
+    float harris_kf_ = 0.0f;
     const bool single_level_pyramid_ = getenv("VSTAB_PYR_SINGLE") != nullptr;  // development: one launch per pyramid level
     long fused_overflows_ = 0;
     PinnedBuf spec_host_;
