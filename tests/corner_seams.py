@@ -1,4 +1,4 @@
-"""Frames for the ownership seams inside a tile of k_corners_fused (csrc/vstab_corners.hip), and the kernel's ownership restated.  No GPU here.
+"""Frames for the ownership seams inside a tile of k_corners_fused (csrc/vstab_corners_fused.hip), and the kernel's ownership restated.  No GPU here.
 
 Inside a 64 x 31 tile at (ox, oy) the kernel hands out work three ways:
 

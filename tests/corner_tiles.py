@@ -1,4 +1,4 @@
-"""The one-pass corner detector (k_corners_fused, then k_filter_keys; csrc/vstab_corners.hip) restated per tile on the oracle's
+"""The one-pass corner detector (k_corners_fused, then k_filter_keys; csrc/vstab_corners_fused.hip) restated per tile on the oracle's
 eigenvalue map, and the frames that put its tiles, its k_filter_keys workgroups and its key buffer into a chosen state.  No GPU here.
 
 A tile is 64 x 31 output pixels (TW x TH).  k_corners_fused takes the tile's own maximum over the in-image part of the 66 x 33
@@ -22,7 +22,7 @@ import oracle
 import synth
 
 TW, TH, SLOTS, FK_TILES = 64, 31, 256, 16
-SPEC_CAP, KEY_CAP = 1 << 15, 1 << 18          # Tracker::SPEC_CAP; the key capacity a Tracker starts with
+SPEC_CAP, KEY_CAP = 1 << 15, 1 << 18          # Detector::SPEC_CAP; the key capacity a Detector starts with
 GROUND = 50
 
 
@@ -245,7 +245,7 @@ def make(name):
     return SETS[name]()
 
 
-# the frames around the key capacity 2^18 of a fresh Tracker (stateless operator)
+# the frames around the key capacity 2^18 of a fresh Detector (stateless operator)
 def cap_frame(which):
     # 570 x 468 (570 x 464, whose plain checkerboard has 260,360, is under the capacity): 262,624 survivors, and a flat patch of 21 x 14
     # takes 480 of them, one of 23 x 13 takes 479 -- the same frame but for the patch on either side of the capacity

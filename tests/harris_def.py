@@ -187,5 +187,5 @@ def rule4_masked_model():
 
 
 def fall_back_frame():
-    """the 2-px checkerboard at 640 x 512: more Harris candidates than the key capacity of a fresh Tracker"""
+    """the 2-px checkerboard at 640 x 512: more Harris candidates than the key capacity of a fresh Detector"""
     return C.checker(640, 512)

@@ -53,7 +53,7 @@ def candidates(gray, mask, quality=0.01):
 
 
 def select(e, cand, max_corners, min_distance):
-    """step 6, as vo_good_features and Tracker::select_corners run it: keys descending, the grid of cells of round(min_distance) px"""
+    """step 6, as vo_good_features and select_corners (vstab_hostlogic.hpp) run it: keys descending, the grid of cells of round(min_distance) px"""
     h, w = e.shape
     ys, xs = np.nonzero(cand)
     keys = (e[ys, xs].view(np.uint32).astype(np.uint64) << np.uint64(32)) | (ys * w + xs).astype(np.uint64)

@@ -103,7 +103,7 @@ def test_key_buffer_cap(vs, cuda, name):
 
 
 def test_public_operator_at_the_key_capacity(vs, cuda):
-    """Exactly 2^18 candidates fit the key buffer of a fresh Tracker: the fused detector's corners.  One more: the two-pass detector's."""
+    """Exactly 2^18 candidates fit the key buffer of a fresh Detector: the fused detector's corners.  One more: the two-pass detector's."""
     for which, used in (("2^18", vs.DETECTOR_FUSED), ("2^18+1", vs.DETECTOR_TWO_PASS)):
         img = C.cap_frame(which)
         g = dev(img, cuda)
@@ -130,7 +130,7 @@ def test_min_eig_bits(vs, cuda):
 
 @pytest.mark.parametrize("which", ["under_spec_cap", "at_spec_cap", "over_spec_cap", "middle_320", "middle", "large"])
 def test_pipeline_around_the_caps(vs, cuda, monkeypatch, which):
-    """A handle on clips whose key frames hold fewer candidates than Tracker::SPEC_CAP, exactly as many, one more, far more, and more than
+    """A handle on clips whose key frames hold fewer candidates than Detector::SPEC_CAP, exactly as many, one more, far more, and more than
     the key capacity: decisions, counts, rotations and every output frame are the oracle state machine's (the check of test_pipeline_gpu.py),
     and the handle's counters say which way the detections went."""
     import test_pipeline_gpu as P

@@ -90,7 +90,7 @@ def test_k_separates(vs, cuda):
 
 # ---- the raw hook ---------------------------------------------------------------------------------------------------------------------------
 def host_half(vs, m, keys, kept, max_bits, mc, md):
-    """what Tracker::good_features does behind the kernels: rule 4 from the sign of the published maximum, then the selection"""
+    """what Detector::good_features does behind the kernels: rule 4 from the sign of the published maximum, then the selection"""
     if max_bits < 0:
         return np.zeros((0, 2), np.float32)
     k = np.sort(keys[:kept])

@@ -1,15 +1,23 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of two device assembly listings of one translation unit (hipcc --offload-arch=gfx950 --cuda-device-only -S):
-which kernels are the same instruction for instruction, which differ, which exist on one side only.  No GPU needed.
+which kernels are the same instruction for instruction, which are the same instructions in another order or with other register numbers
+(`reordered`: the same multiset of mnemonics and the same resource figures), which differ, which exist on one side only.  No GPU needed.
 
     hipcc --offload-arch=gfx950 <the Makefile's CXXFLAGS> --cuda-device-only -S csrc/vstab_corners.hip -o branch.s     (and parent.s)
+    cat branch_corners.s branch_corners_fused.s > branch.s                                    (a unit the branch split in two)
     python tools/asm_kernel_diff.py parent.s branch.s
 
 A kernel's text is what stands between its label and its .Lfunc_end; basic-block labels are renumbered per function (adding a kernel to
 the unit shifts the function index inside every .LBB<function>_<block>), comments and blank lines are dropped.  The resource figures
-(VGPRs, SGPRs, LDS, private segment) come from the .amdhsa metadata of each listing.  Exit status 1 if a kernel present in both differs."""
+(VGPRs, SGPRs, LDS, private segment) come from the .amdhsa metadata of each listing.  Exit status 1 if a kernel present in both is DIFFERENT."""
+import collections
 import re
 import sys
+
+
+def mnemonics(body):
+    """the multiset of instruction mnemonics of a kernel's text: labels and directives left out"""
+    return collections.Counter(line.split()[0] for line in body if not line.rstrip().endswith(":") and not line.lstrip().startswith("."))
 
 
 def kernels(path):
@@ -42,6 +50,9 @@ def main():
             print(f"gone       {name}")
         elif a[name] == b[name] and ra.get(name) == rb.get(name):
             print(f"identical  {name}: {len(a[name])} lines; {fig}")
+        elif mnemonics(a[name]) == mnemonics(b[name]) and ra.get(name) == rb.get(name):
+            n = sum(x != y for x, y in zip(a[name], b[name])) + abs(len(a[name]) - len(b[name]))
+            print(f"reordered  {name}: {len(a[name])} lines, {n} of them differ in place (order or register numbers only); {fig}")
         else:
             bad += 1
             print(f"DIFFERENT  {name}: {len(a[name])} -> {len(b[name])} lines; {ra.get(name)} -> {rb.get(name)}")

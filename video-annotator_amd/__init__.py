@@ -213,6 +213,8 @@ _L.vstabx_corners_fused_mask.restype = _i
 _L.vstabx_corners_fused_mask.argtypes = [_vp, _sz, _i, _i, _vp, _sz, _d, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _vp]
 _L.vstabx_corners_fused_harris.restype = _i
 _L.vstabx_corners_fused_harris.argtypes = [_vp, _sz, _i, _i, _vp, _sz, _d, _d, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _ip, _vp]
+_L.vstabx_select_corners.restype = _i
+_L.vstabx_select_corners.argtypes = [_c.POINTER(_u64), _c.c_uint, _i, _i, _i, _d, _fp, _ip]
 _L.vstabx_detector_counters.restype = _i
 _L.vstabx_detector_counters.argtypes = [_vp, _c.POINTER(_c.c_long)]
 
@@ -767,37 +769,36 @@ def min_eig(gray):
 DETECTOR_AUTO, DETECTOR_TWO_PASS, DETECTOR_FUSED = 0, 1, 2
 
 
+def _good_features(name, gray, max_corners, info, head, with_used=True):
+    """One call shape for the vstab_good_features* entry points: fn(gray, pitch, w, h, *head, xy, &count[, &detector_used], stream);
+    head is what stands between the image and xy.  info["detector_used"] is filled where the entry point reports it."""
+    h, w = gray.shape
+    xy = np.zeros((max_corners, 2), np.float32)
+    n, used = _c.c_int(), _c.c_int()
+    out = (_fptr(xy), _c.byref(n)) + ((_c.byref(used),) if with_used else ())
+    _check(getattr(_L, name)(gray.data_ptr(), gray.stride(0), w, h, *head, *out, _stream()), name)
+    if with_used and info is not None:
+        info["detector_used"] = used.value
+    return xy[:n.value].copy()
+
+
+def _mask_args(mask):
+    return (None, 0) if mask is None else (mask.data_ptr(), mask.stride(0))
+
+
 def good_features(gray, max_corners=200, quality=0.01, min_distance=30.0, detector=None, info=None):
     """detector: None -> vstab_good_features; DETECTOR_AUTO / DETECTOR_TWO_PASS -> vstab_good_features_ex, and
     info["detector_used"] (if a dict is given) says which kernel path produced the corners."""
-    h, w = gray.shape
-    xy = np.zeros((max_corners, 2), np.float32)
-    n = _c.c_int()
     if detector is None:
-        _check(_L.vstab_good_features(gray.data_ptr(), gray.stride(0), w, h, max_corners, quality, min_distance, _fptr(xy),
-                                      _c.byref(n), _stream()), "vstab_good_features")
-    else:
-        used = _c.c_int()
-        _check(_L.vstab_good_features_ex(gray.data_ptr(), gray.stride(0), w, h, max_corners, quality, min_distance, detector, _fptr(xy),
-                                         _c.byref(n), _c.byref(used), _stream()), "vstab_good_features_ex")
-        if info is not None:
-            info["detector_used"] = used.value
-    return xy[:n.value].copy()
+        return _good_features("vstab_good_features", gray, max_corners, None, (max_corners, quality, min_distance), with_used=False)
+    return _good_features("vstab_good_features_ex", gray, max_corners, info, (max_corners, quality, min_distance, detector))
 
 
 def good_features_mask(gray, mask, max_corners=200, quality=0.01, min_distance=30.0, detector=DETECTOR_AUTO, info=None):
     """vstab_good_features_mask: good_features under a detection mask, an (h, w) uint8 device tensor or view (any pitch and base address;
     non-zero = "a corner may be reported here"), or None for no mask.  detector: DETECTOR_AUTO, DETECTOR_FUSED or DETECTOR_TWO_PASS;
     info["detector_used"] (if a dict is given) says which kernel path produced the corners."""
-    h, w = gray.shape
-    xy = np.zeros((max_corners, 2), np.float32)
-    n, used = _c.c_int(), _c.c_int()
-    _check(_L.vstab_good_features_mask(gray.data_ptr(), gray.stride(0), w, h, None if mask is None else mask.data_ptr(), 0 if mask is None else mask.stride(0),
-                                       max_corners, quality, min_distance, detector, _fptr(xy), _c.byref(n), _c.byref(used), _stream()),
-           "vstab_good_features_mask")
-    if info is not None:
-        info["detector_used"] = used.value
-    return xy[:n.value].copy()
+    return _good_features("vstab_good_features_mask", gray, max_corners, info, _mask_args(mask) + (max_corners, quality, min_distance, detector))
 
 
 CORNER_MIN_EIGENVAL, CORNER_HARRIS = 0, 1
@@ -815,25 +816,15 @@ def corner_harris(gray, k=0.04):
 def good_features_harris(gray, mask=None, max_corners=200, quality=0.01, min_distance=30.0, k=0.04, detector=DETECTOR_AUTO, info=None):
     """vstab_good_features_harris: good_features_mask with the Harris response (goodFeaturesToTrack's useHarrisDetector = true and k);
     mask None = no mask."""
-    h, w = gray.shape
-    xy = np.zeros((max_corners, 2), np.float32)
-    n, used = _c.c_int(), _c.c_int()
-    _check(_L.vstab_good_features_harris(gray.data_ptr(), gray.stride(0), w, h, None if mask is None else mask.data_ptr(), 0 if mask is None else mask.stride(0),
-                                         max_corners, quality, min_distance, float(k), detector, _fptr(xy), _c.byref(n), _c.byref(used), _stream()),
-           "vstab_good_features_harris")
-    if info is not None:
-        info["detector_used"] = used.value
-    return xy[:n.value].copy()
+    return _good_features("vstab_good_features_harris", gray, max_corners, info, _mask_args(mask) + (max_corners, quality, min_distance, float(k), detector))
 
 
 CORNERS_FUSED_FILL = 0xA5A5A5A5A5A5A5A5  # what vstabx_corners_fused fills its key buffer with before the kernels run
 
 
-def corners_fused(gray, quality=0.01, cap=1 << 18, canary=64, w=None, h=None, stream=None):
-    """Test hook vstabx_corners_fused (not part of include/vstab.h): the one-pass detector's raw output on the (h, w) uint8 device luma
-    view `gray` (pitched views allowed) with a key buffer of exactly `cap` keys and `canary` more behind it.
-    -> (keys (cap + canary,) uint64 as the kernels left them over the fill, keys kept, tiles that spilled, per-tile survivor counts
-    (tiles_y, tiles_x) uint32).  w / h / stream are taken as given, so that a test of the refusals needs no device."""
+def _corners_fused(name, gray, w, h, stream, cap, canary, head, tail=()):
+    """One buffer set-up and call shape for the vstabx_corners_fused* hooks: fn(gray, pitch, w, h, *head, cap, canary, keys, counts,
+    tiles, *tail, stream) -> (keys, keys kept, tiles that spilled, per-tile survivor counts).  w / h / stream are taken as given."""
     h = gray.shape[0] if h is None else h
     w = gray.shape[1] if w is None else w
     cap, canary = int(cap), int(canary)
@@ -842,50 +833,46 @@ def corners_fused(gray, quality=0.01, cap=1 << 18, canary=64, w=None, h=None, st
     counts = np.zeros(2, np.uint32)
     tx, ty = max(1, (int(w) + 63) // 64), max(1, (int(h) + 30) // 31)
     tiles = np.zeros((ty, tx) if tx * ty < 1 << 21 else (1, 1), np.uint32)   # (2^21 tiles are over 2^31 pixels: refused)
-    _check(_L.vstabx_corners_fused(gray.data_ptr(), gray.stride(0), int(w), int(h), float(quality), cap & 0xFFFFFFFF, canary & 0xFFFFFFFF,
-                                   keys.ctypes.data_as(_c.POINTER(_u64)), counts.ctypes.data_as(_c.POINTER(_c.c_uint)),
-                                   tiles.ctypes.data_as(_c.POINTER(_c.c_uint)), _stream() if stream is None else stream), "vstabx_corners_fused")
+    _check(getattr(_L, name)(gray.data_ptr(), gray.stride(0), int(w), int(h), *head, cap & 0xFFFFFFFF, canary & 0xFFFFFFFF,
+                             keys.ctypes.data_as(_c.POINTER(_u64)), counts.ctypes.data_as(_c.POINTER(_c.c_uint)),
+                             tiles.ctypes.data_as(_c.POINTER(_c.c_uint)), *tail, _stream() if stream is None else stream), name)
     return keys, int(counts[0]), int(counts[1]), tiles
+
+
+def corners_fused(gray, quality=0.01, cap=1 << 18, canary=64, w=None, h=None, stream=None):
+    """Test hook vstabx_corners_fused (not part of include/vstab.h): the one-pass detector's raw output on the (h, w) uint8 device luma
+    view `gray` (pitched views allowed) with a key buffer of exactly `cap` keys and `canary` more behind it.
+    -> (keys (cap + canary,) uint64 as the kernels left them over the fill, keys kept, tiles that spilled, per-tile survivor counts
+    (tiles_y, tiles_x) uint32).  w / h / stream are taken as given, so that a test of the refusals needs no device."""
+    return _corners_fused("vstabx_corners_fused", gray, w, h, stream, cap, canary, (float(quality),))
 
 
 def corners_fused_mask(gray, mask, quality=0.01, cap=1 << 18, canary=64, w=None, h=None, stream=None, mask_ptr=None, mask_pitch=None):
     """Test hook vstabx_corners_fused_mask: corners_fused under the detection mask `mask`, an (h, w) uint8 device tensor or view; the same
     outputs.  mask_ptr / mask_pitch (for a test of the refusals, which needs no device) stand in for the tensor's."""
-    h = gray.shape[0] if h is None else h
-    w = gray.shape[1] if w is None else w
-    cap, canary = int(cap), int(canary)
-    ok = 0 < cap <= 1 << 24 and 0 < canary <= 1 << 16
-    keys = np.zeros(cap + canary if ok else 1, np.uint64)
-    counts = np.zeros(2, np.uint32)
-    tx, ty = max(1, (int(w) + 63) // 64), max(1, (int(h) + 30) // 31)
-    tiles = np.zeros((ty, tx) if tx * ty < 1 << 21 else (1, 1), np.uint32)
     mp = mask.data_ptr() if mask_ptr is None else mask_ptr
     mpitch = mask.stride(0) if mask_pitch is None else mask_pitch
-    _check(_L.vstabx_corners_fused_mask(gray.data_ptr(), gray.stride(0), int(w), int(h), mp, mpitch, float(quality), cap & 0xFFFFFFFF, canary & 0xFFFFFFFF,
-                                        keys.ctypes.data_as(_c.POINTER(_u64)), counts.ctypes.data_as(_c.POINTER(_c.c_uint)),
-                                        tiles.ctypes.data_as(_c.POINTER(_c.c_uint)), _stream() if stream is None else stream), "vstabx_corners_fused_mask")
-    return keys, int(counts[0]), int(counts[1]), tiles
+    return _corners_fused("vstabx_corners_fused_mask", gray, w, h, stream, cap, canary, (mp, mpitch, float(quality)))
 
 
 def corners_fused_harris(gray, mask=None, k=0.04, quality=0.01, cap=1 << 18, canary=64, w=None, h=None, stream=None):
     """Test hook vstabx_corners_fused_harris: corners_fused / corners_fused_mask (mask None = no mask) with the Harris response.
     -> (keys, keys kept, tiles that spilled, per-tile survivor counts, max_bits): max_bits is the frame maximum the kernels published, the
     float's bits as int32 -- negative: no response above zero, the host reports no corner whatever the keys say."""
-    h = gray.shape[0] if h is None else h
-    w = gray.shape[1] if w is None else w
-    cap, canary = int(cap), int(canary)
-    ok = 0 < cap <= 1 << 24 and 0 < canary <= 1 << 16
-    keys = np.zeros(cap + canary if ok else 1, np.uint64)
-    counts = np.zeros(2, np.uint32)
-    tx, ty = max(1, (int(w) + 63) // 64), max(1, (int(h) + 30) // 31)
-    tiles = np.zeros((ty, tx) if tx * ty < 1 << 21 else (1, 1), np.uint32)
     mx = _c.c_int()
-    _check(_L.vstabx_corners_fused_harris(gray.data_ptr(), gray.stride(0), int(w), int(h), None if mask is None else mask.data_ptr(),
-                                          0 if mask is None else mask.stride(0), float(quality), float(k), cap & 0xFFFFFFFF, canary & 0xFFFFFFFF,
-                                          keys.ctypes.data_as(_c.POINTER(_u64)), counts.ctypes.data_as(_c.POINTER(_c.c_uint)),
-                                          tiles.ctypes.data_as(_c.POINTER(_c.c_uint)), _c.byref(mx), _stream() if stream is None else stream),
-           "vstabx_corners_fused_harris")
-    return keys, int(counts[0]), int(counts[1]), tiles, mx.value
+    out = _corners_fused("vstabx_corners_fused_harris", gray, w, h, stream, cap, canary, _mask_args(mask) + (float(quality), float(k)), (_c.byref(mx),))
+    return out + (mx.value,)
+
+
+def select_corners(keys, w, h, max_corners=200, min_distance=30.0):
+    """Test hook vstabx_select_corners (no device needed): the host half of goodFeaturesToTrack over candidate keys (uint64: float bits
+    << 32 | raster index) of a w x h image -> (n, 2) float32 corners in the order they were accepted.  max_corners <= 0: no limit."""
+    keys = np.ascontiguousarray(keys, np.uint64)
+    xy = np.zeros((max(1, keys.size if max_corners <= 0 else min(keys.size, max_corners)), 2), np.float32)
+    n = _c.c_int()
+    _check(_L.vstabx_select_corners(keys.ctypes.data_as(_c.POINTER(_u64)), keys.size, int(w), int(h), int(max_corners), float(min_distance), _fptr(xy),
+                                    _c.byref(n)), "vstabx_select_corners")
+    return xy[:n.value].copy()
 
 
 def pyr_lk(prev, nxt, pts):
@@ -1162,7 +1149,7 @@ class Stabilizer:
         return int(_L.vstabx_warps_from_cache(self._h))
 
     def detector_counters(self):
-        """Test hook vstabx_detector_counters: speculative selections that found more than Tracker::SPEC_CAP candidates, fused detections
+        """Test hook vstabx_detector_counters: speculative selections that found more than Detector::SPEC_CAP candidates, fused detections
         that overflowed the key buffer, the key capacity now in force."""
         out = (_c.c_long * 3)()
         _check(_L.vstabx_detector_counters(self._h, out), "vstabx_detector_counters")

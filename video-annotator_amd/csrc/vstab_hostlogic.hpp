@@ -1,8 +1,11 @@
 // vstab_hostlogic.hpp -- host-side bookkeeping of the pipeline that does not need a device: the parser of the tracker's result
-// records and the import cache of DMA-BUF objects.  Kept apart from the units that use them (vstab_track_host.cpp, vstab_pipeline.cpp) so
+// records, the host half of goodFeaturesToTrack and the import cache of DMA-BUF objects.  Kept apart from the units that use them
+// (vstab_track_host.cpp, vstab_detect_host.cpp, vstab_pipeline.cpp) so
 // that the CPU test suite (and its sanitizer build, tools/run_sanitized_tests.sh) can drive them with hand-made buffers through the
 // vstabx_* test hooks (vstab_testhooks.cpp).
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -38,6 +41,55 @@ inline LkParse lk_parse_records(const volatile uint32_t *rec, int first, int n, 
     }
     *next = n;
     return status.size() == expect_n ? LK_PARSE_OK : LK_PARSE_COUNT_MISMATCH;
+}
+
+// ---- corner selection ----------------------------------------------------------------------------------------------------------
+// host half of goodFeaturesToTrack over the n candidate keys (float bits << 32 | raster index) of a w x h image: sort them (value
+// descending, ties -> later raster position first: greaterThanPtr in OpenCV) and run the minimum-distance grid.
+// Sorts k in place.
+inline void select_corners(unsigned long long *k, unsigned int n, int w, int h, int max_corners, double min_distance, std::vector<float> &xy) {
+    xy.clear();
+    const int cell = (int)std::nearbyint(min_distance);
+    const int gw = cell >= 1 ? (w + cell - 1) / cell : 0, gh = cell >= 1 ? (h + cell - 1) / cell : 0;
+    const double md2 = min_distance * min_distance;
+    static thread_local std::vector<int> grid_head_, grid_next_;  // min-distance grid: per-cell lists of accepted corners
+    if (cell >= 1) grid_head_.assign((size_t)gw * gh, -1), grid_next_.clear();
+    // The greedy pass consumes candidates in sorted order and usually stops after a few hundred, so the
+    // keys are sorted lazily in chunks: nth_element splits off the next `chunk` largest keys (O(n)),
+    // only that chunk is sorted.  The visiting order is exactly the fully sorted order.
+    unsigned int done = 0;
+    const auto greater = [](unsigned long long a, unsigned long long b) { return a > b; };
+    while (done < n) {
+        const unsigned int chunk = std::min(n - done, 1024u);
+        if (done + chunk < n) std::nth_element(k + done, k + done + chunk, k + n, greater);
+        std::sort(k + done, k + done + chunk, greater);
+        for (unsigned int i = done; i < done + chunk; i++) {
+            const unsigned int idx = (unsigned int)(k[i] & 0xffffffffu);
+            const int x = (int)(idx % w), y = (int)(idx / w);
+            if (cell < 1) {
+                xy.push_back((float)x), xy.push_back((float)y);
+            } else {
+                const int xc = x / cell, yc = y / cell;
+                const int x1 = std::max(0, xc - 1), y1 = std::max(0, yc - 1), x2 = std::min(gw - 1, xc + 1), y2 = std::min(gh - 1, yc + 1);
+                bool good = true;
+                for (int yy = y1; yy <= y2 && good; yy++)
+                    for (int xx = x1; xx <= x2 && good; xx++)
+                        for (int j = grid_head_[(size_t)yy * gw + xx]; j >= 0; j = grid_next_[j]) {
+                            const float dx = (float)x - xy[2 * j], dy = (float)y - xy[2 * j + 1];
+                            if ((double)(dx * dx + dy * dy) < md2) {
+                                good = false;
+                                break;
+                            }
+                        }
+                if (!good) continue;
+                grid_next_.push_back(grid_head_[(size_t)yc * gw + xc]);
+                grid_head_[(size_t)yc * gw + xc] = (int)(xy.size() / 2);
+                xy.push_back((float)x), xy.push_back((float)y);
+            }
+            if (max_corners > 0 && (int)(xy.size() / 2) == max_corners) return;
+        }
+        done += chunk;
+    }
 }
 
 // ---- DMA-BUF import cache ----------------------------------------------------------------------------------------------------

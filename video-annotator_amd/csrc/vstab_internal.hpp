@@ -38,6 +38,7 @@ LaunchEvents take_launch_events();
 // one per translation unit with kernels: loads that unit's code object now (vstab_preload_kernels)
 vstab_status preload_pyramid_kernels();
 vstab_status preload_corner_kernels();
+vstab_status preload_corners_fused_kernels();
 vstab_status preload_lk_kernels();
 vstab_status preload_plane_kernels();
 vstab_status preload_warp_kernels();

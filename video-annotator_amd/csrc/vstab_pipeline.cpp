@@ -248,8 +248,8 @@ vstab_status prefetch_next(vstab_handle *H) {
             const vstab_handle::Slot &DS = H->slots[slot];
             if (!DS.borrowed) VSTAB_HIP_TRY(hipStreamWaitEvent(ds, DS.copied_valid ? DS.copied : DS.ingested, 0));
         }
-        VSTAB_TRY(H->tracker.spec_launch(H->gray(slot), H->gpitch(slot), 0.01, ds, H->prefetch_count));
-        H->tracker.spec_select_async(200, 30.0);
+        VSTAB_TRY(H->detector.spec_launch(H->gray(slot), H->gpitch(slot), 0.01, ds, H->prefetch_count));
+        H->detector.spec_select_async(200, 30.0);
     }
     H->prefetched.emplace_back(slot, pyr);
     H->prefetch_count++;
@@ -275,7 +275,7 @@ static vstab_status seed_corners(vstab_handle *H, int slot, const uint8_t *g, si
     VSTAB_HIP_TRY(hipStreamWaitEvent(H->tstream, H->slots[slot].ingested, 0));
     {
         HostStage hs(&H->prof.host_corners_ms);
-        VSTAB_TRY(H->tracker.good_features(g, pitch, 200, 0.01, 30.0, H->corners, H->tstream));
+        VSTAB_TRY(H->detector.good_features(g, pitch, 200, 0.01, 30.0, H->corners, H->tstream));
     }
     H->prof.key_frames++;
     H->slots[slot].queued = false;
@@ -353,9 +353,9 @@ static vstab_status track_frame(vstab_handle *H, int slot, int pyr, const uint8_
             H->key_prelaunched++;
         } else {
             // the previous frame is F - 1: use its speculative detection if there is one
-            const bool spec = H->tracker.spec_tag() == F - 1 && H->tracker.spec_finish(200, 30.0, H->corners);
-            if (debug_spec()) std::fprintf(stderr, "key frame at %ld: spec_tag %ld used %d\n", F, H->tracker.spec_tag(), (int)spec);
-            if (!spec) VSTAB_TRY(H->tracker.good_features(pg, ppitch, 200, 0.01, 30.0, H->corners, H->tstream));
+            const bool spec = H->detector.spec_tag() == F - 1 && H->detector.spec_finish(200, 30.0, H->corners);
+            if (debug_spec()) std::fprintf(stderr, "key frame at %ld: spec_tag %ld used %d\n", F, H->detector.spec_tag(), (int)spec);
+            if (!spec) VSTAB_TRY(H->detector.good_features(pg, ppitch, 200, 0.01, 30.0, H->corners, H->tstream));
         }
         T.lg.key_frame = 1;
         H->prof.key_frames++;
@@ -394,14 +394,14 @@ static vstab_status track_frame(vstab_handle *H, int slot, int pyr, const uint8_
         if (avail <= 0 || back.launch.n_slots == 0) break;
         const long kc = back.last_key_after + 21;  // next planned key frame
         if (next == kc) {
-            if (H->tracker.spec_tag() == tail) H->tracker.spec_poll_inline();
-            if (H->tracker.spec_tag() != tail || H->tracker.spec_state() != 2) {
-                if (debug_spec() && H->tracker.spec_tag() == tail)
-                    std::fprintf(stderr, "frame %ld: corners for key frame %ld not selected yet (state %d)\n", F, next, H->tracker.spec_state());
+            if (H->detector.spec_tag() == tail) H->detector.spec_poll_inline();
+            if (H->detector.spec_tag() != tail || H->detector.spec_state() != 2) {
+                if (debug_spec() && H->detector.spec_tag() == tail)
+                    std::fprintf(stderr, "frame %ld: corners for key frame %ld not selected yet (state %d)\n", F, next, H->detector.spec_state());
                 break;  // not detected / selected yet: next pull, or on demand when the host gets there
             }
             std::vector<float> fresh;
-            H->tracker.spec_take(fresh);
+            H->detector.spec_take(fresh);
             const int n = (int)std::min<long>({(long)seg_max, avail, 21});
             const int es = H->epoch_overlap ? H->spec_stream : 0;  // where its detection ran: not the stream of the epoch before it
             VSTAB_TRY(launch_segment(next, n, true, &fresh, nullptr, next - 1, false, es));
@@ -621,7 +621,10 @@ vstab_status vstab_create(const vstab_config *cfg, const vstab_source *src, vsta
     }
     // a frame stays in the pipeline from its pull until its warp: read-ahead + look-ahead queue + the frames in between
     H->borrow_hold = getenv("VSTAB_ALWAYS_COPY") ? (1 << 30) + 1 : cfg->smooth_radius + H->prefetch_depth + 6;
-    if (cfg->tracking) VSTAB_TRY(H->tracker.init(H->w, H->h));
+    if (cfg->tracking) {
+        VSTAB_TRY(H->tracker.init(H->w, H->h));
+        VSTAB_TRY(H->detector.init(H->w, H->h));
+    }
     *out = H.release();
     return VSTAB_OK;
 }
@@ -687,8 +690,8 @@ vstab_status vstab_set_input_calibration(vstab_handle *h, const double K[9], con
     return set_input_calibration(h, K, D, "vstab_set_input_calibration", false);
 }
 
-// The handle's detection mask: the Tracker keeps a copy and every detection of the handle reads it (seed_corners, track_frame's detection on
-// demand, Tracker::spec_launch).  Before the first pull nothing is in flight, so no stream has to be ordered behind the copy.
+// The handle's detection mask: the Detector keeps a copy and every detection of the handle reads it (seed_corners, track_frame's detection on
+// demand, Detector::spec_launch).  Before the first pull nothing is in flight, so no stream has to be ordered behind the copy.
 vstab_status vstab_set_detection_mask(vstab_handle *h, const void *mask, size_t pitch_mask, int mem) {
     const std::string n = "vstab_set_detection_mask: ";
     if (!h) return fail(VSTAB_ERR_INVALID, n + "null handle");
@@ -696,10 +699,10 @@ vstab_status vstab_set_detection_mask(vstab_handle *h, const void *mask, size_t 
     if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the mask must be set before the first pull");
     if (mask && pitch_mask < (size_t)h->w) return fail(VSTAB_ERR_INVALID, n + "the mask's pitch is smaller than the frame's width");
     if (mask && mem != VSTAB_MEM_DEVICE && mem != VSTAB_MEM_HOST) return fail(VSTAB_ERR_INVALID, n + "mem must be VSTAB_MEM_DEVICE (0) or VSTAB_MEM_HOST (1)");
-    return h->tracker.copy_mask(mask, pitch_mask, mem == VSTAB_MEM_HOST);
+    return h->detector.copy_mask(mask, pitch_mask, mem == VSTAB_MEM_HOST);
 }
 
-// The handle's corner response: read by every detection of the handle, as the mask is (Tracker::set_response).
+// The handle's corner response: read by every detection of the handle, as the mask is (Detector::set_response).
 vstab_status vstab_set_corner_response(vstab_handle *h, int response, double k) {
     const std::string n = "vstab_set_corner_response: ";
     if (!h) return fail(VSTAB_ERR_INVALID, n + "null handle");
@@ -707,8 +710,9 @@ vstab_status vstab_set_corner_response(vstab_handle *h, int response, double k) 
     if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the response must be set before the first pull");
     if (response != VSTAB_CORNER_MIN_EIGENVAL && response != VSTAB_CORNER_HARRIS)
         return fail(VSTAB_ERR_INVALID, n + "response must be VSTAB_CORNER_MIN_EIGENVAL (0) or VSTAB_CORNER_HARRIS (1)");
-    if (response == VSTAB_CORNER_HARRIS && !harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, n + "k lies in [0, 0.25)");
-    h->tracker.set_response(response == VSTAB_CORNER_HARRIS, (float)k);
+    DetectSpec d;
+    VSTAB_TRY(check_detect_spec("vstab_set_corner_response", nullptr, 0, response == VSTAB_CORNER_HARRIS, k, h->w, h->h, d));
+    h->detector.set_response(d.harris, d.kf);
     return VSTAB_OK;
 }
 
@@ -729,7 +733,7 @@ vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out) {
     if (!h || !out) return fail(VSTAB_ERR_INVALID, "vstab_get_profile: null argument");
     h->fold_pending();
     h->prof.dmabuf_imports = h->dmabufs.imports, h->prof.dmabuf_evictions = h->dmabufs.evictions, h->prof.dmabuf_cached = (long)h->dmabufs.size();
-    h->prof.corner_selections_by_caller = h->tracker.selections_by_caller(), h->prof.corner_selections_by_helper = h->tracker.selections_by_helper();
+    h->prof.corner_selections_by_caller = h->detector.selections_by_caller(), h->prof.corner_selections_by_helper = h->detector.selections_by_helper();
     h->prof.epochs_in_turn = h->epochs_on_second_stream;
     *out = h->prof;
     return VSTAB_OK;

@@ -6,6 +6,7 @@
 #include <deque>
 #include <memory>
 
+#include "vstab_detect_host.hpp"
 #include "vstab_hostlogic.hpp"
 #include "vstab_motion.hpp"
 #include "vstab_track_host.hpp"
@@ -140,6 +141,7 @@ struct vstab_handle {
     // the coefficients the rotation estimate undistorts with: k1..k4 where in_fish, the five of a rectilinear lens otherwise
     const double *distortion() const { return calibrated ? dist : pinhole ? pdist : nullptr; }
     Tracker tracker;
+    Detector detector;  // (both initialised only where cfg.tracking)
 
     struct Slot {
         DevBuf buf;  // packed NV12, pitch = w (allocated on the first copy into the slot)

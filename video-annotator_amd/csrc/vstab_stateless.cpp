@@ -2,6 +2,7 @@
 // source, the stateless tracking / motion operators and the rotation-filter object.
 #include <cstring>
 
+#include "vstab_detect_host.hpp"
 #include "vstab_motion.hpp"
 #include "vstab_track_host.hpp"
 
@@ -41,6 +42,7 @@ void vstab_config_default(vstab_config *cfg) {
 vstab_status vstab_preload_kernels(void) {
     VSTAB_TRY(preload_pyramid_kernels());
     VSTAB_TRY(preload_corner_kernels());
+    VSTAB_TRY(preload_corners_fused_kernels());
     VSTAB_TRY(preload_lk_kernels());
     VSTAB_TRY(preload_plane_kernels());
     VSTAB_TRY(preload_warp_kernels());
@@ -137,7 +139,7 @@ vstab_status vstab_min_eig(const void *gray, size_t pitch, int width, int height
     if (!gray || !eig || width <= 0 || height <= 0 || pitch < (size_t)width) return fail(VSTAB_ERR_INVALID, "vstab_min_eig: bad argument");
     DevBuf mb;
     VSTAB_TRY(mb.ensure(16));
-    VSTAB_TRY(launch_min_eig((const uint8_t *)gray, pitch, width, height, (float *)eig, mb.as<int>(), static_cast<hipStream_t>(stream)));
+    VSTAB_TRY(launch_corner_response((const uint8_t *)gray, pitch, width, height, false, 0.0f, (float *)eig, mb.as<int>(), static_cast<hipStream_t>(stream)));
     VSTAB_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return VSTAB_OK;
 }
@@ -148,7 +150,7 @@ vstab_status vstab_corner_harris(const void *gray, size_t pitch, int width, int 
     if (!harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, "vstab_corner_harris: k lies in [0, 0.25)");
     DevBuf mb;
     VSTAB_TRY(mb.ensure(16));
-    VSTAB_TRY(launch_corner_harris((const uint8_t *)gray, pitch, width, height, (float)k, (float *)response, mb.as<int>(), static_cast<hipStream_t>(stream)));
+    VSTAB_TRY(launch_corner_response((const uint8_t *)gray, pitch, width, height, true, (float)k, (float *)response, mb.as<int>(), static_cast<hipStream_t>(stream)));
     VSTAB_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return VSTAB_OK;
 }
@@ -161,15 +163,13 @@ static vstab_status good_features_op(const char *fn, bool fused_ok, const void *
     if (!gray || !xy || !count || width < 3 || height < 3 || pitch < (size_t)width || max_corners <= 0 ||
         (detector != VSTAB_DETECTOR_AUTO && detector != VSTAB_DETECTOR_TWO_PASS && !(fused_ok && detector == VSTAB_DETECTOR_FUSED)))
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": bad argument");
-    if (mask && pitch_mask < (size_t)width) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": the mask's pitch is smaller than the image's width");
-    if (mask && (uint64_t)pitch_mask * (uint64_t)height >= (1ull << 32))
-        return fail(VSTAB_ERR_INVALID, std::string(fn) + ": mask planes of 4 GiB or more are not supported");
-    if (harris && !harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": k lies in [0, 0.25)");
-    Tracker t;
+    DetectSpec spec;
+    VSTAB_TRY(check_detect_spec(fn, mask, pitch_mask, harris, k, width, height, spec));
+    Detector t;
     VSTAB_TRY(t.init(width, height));
     t.set_two_pass_detector(detector == VSTAB_DETECTOR_TWO_PASS);
-    t.set_mask(static_cast<const uint8_t *>(mask), pitch_mask);
-    t.set_response(harris, (float)k);
+    t.set_mask(spec.mask, spec.mask_pitch);
+    t.set_response(spec.harris, spec.kf);
     std::vector<float> out;
     VSTAB_TRY(t.good_features((const uint8_t *)gray, pitch, max_corners, quality, min_distance, out, static_cast<hipStream_t>(stream)));
     *count = (int)(out.size() / 2);

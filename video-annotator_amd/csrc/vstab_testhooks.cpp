@@ -1,6 +1,7 @@
 // vstab_testhooks.cpp -- the vstabx_* test hooks.
 #include <algorithm>
 
+#include "vstab_detect_host.hpp"
 #include "vstab_hostlogic.hpp"
 #include "vstab_pipeline.hpp"
 #include "vstab_track_host.hpp"
@@ -170,9 +171,8 @@ static int corners_fused_hook(const std::string &fn, const void *gray, size_t pi
     if (!(quality > 0.0) || !(quality <= 1.0)) return fail(VSTAB_ERR_INVALID, fn + ": quality lies in (0, 1]");
     if (cap < 1 || cap > (1u << 24)) return fail(VSTAB_ERR_INVALID, fn + ": cap is 1 .. 2^24 keys");
     if (canary < 1 || canary > (1u << 16)) return fail(VSTAB_ERR_INVALID, fn + ": canary is 1 .. 2^16 keys");
-    if (masked && pitch_mask < (size_t)w) return fail(VSTAB_ERR_INVALID, fn + ": the mask's pitch is smaller than the image's width");
-    if (masked && (uint64_t)pitch_mask * (uint64_t)h >= (1ull << 32)) return fail(VSTAB_ERR_INVALID, fn + ": mask planes of 4 GiB or more are not supported");
-    if (harris && !harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, fn + ": k lies in [0, 0.25)");
+    DetectSpec spec;
+    VSTAB_TRY(check_detect_spec(fn, masked ? mask : nullptr, pitch_mask, harris, k, w, h, spec));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const CornersFusedScratch lay(w, h);  // the layout launch_corners_fused uses: the survivor counts are read back from it below
     const size_t scratch_bytes = lay.bytes;
@@ -181,14 +181,14 @@ static int corners_fused_hook(const std::string &fn, const void *gray, size_t pi
     VSTAB_TRY(scratch.ensure(scratch_bytes));
     VSTAB_TRY(keys.ensure(n_keys * sizeof(unsigned long long)));
     VSTAB_TRY(small.ensure(256));
-    // (under a mask the scratch starts out as garbage, as a Tracker's does: a tile that returns early has to WRITE its count of 0)
+    // (under a mask the scratch starts out as garbage, as a Detector's does: a tile that returns early has to WRITE its count of 0)
     VSTAB_HIP_TRY(hipMemsetAsync(scratch.p, masked ? 0xA5 : 0, scratch_bytes, st));
     VSTAB_HIP_TRY(hipMemsetAsync(keys.p, 0xA5, n_keys * sizeof(unsigned long long), st));
-    VSTAB_TRY(launch_corners_fused(static_cast<const uint8_t *>(gray), pitch, w, h, quality, scratch.p, keys.as<unsigned long long>(), cap, small.as<unsigned int>(), st,
-                                   static_cast<const uint8_t *>(mask), pitch_mask, harris, (float)k));
+    DetectorWords *words = small.as<DetectorWords>();
+    VSTAB_TRY(launch_corners_fused(static_cast<const uint8_t *>(gray), pitch, w, h, quality, scratch.p, keys.as<unsigned long long>(), cap, words, st, spec));
     VSTAB_HIP_TRY(hipMemcpyAsync(keys_out, keys.p, n_keys * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    VSTAB_HIP_TRY(hipMemcpyAsync(counts_out, small.as<unsigned int>() + 4, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    if (max_out) VSTAB_HIP_TRY(hipMemcpyAsync(max_out, small.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    VSTAB_HIP_TRY(hipMemcpyAsync(counts_out, &words->kept, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    if (max_out) VSTAB_HIP_TRY(hipMemcpyAsync(max_out, &words->max, sizeof(int), hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipMemcpyAsync(tile_counts, scratch.as<uint8_t>() + lay.counts_off, (size_t)lay.tiles * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     VSTAB_HIP_TRY(hipStreamSynchronize(st));
     if (max_out) *max_out = (int)((unsigned int)*max_out ^ 0x80000000u);  // the kernels keep it biased (unsigned order); 0 there = nothing published = INT_MIN here
@@ -283,12 +283,29 @@ __attribute__((visibility("default"))) int vstabx_warp_route(int map_mode, int l
     return VSTAB_OK;
 }
 
+// The host half of goodFeaturesToTrack alone, no device needed (select_corners, vstab_hostlogic.hpp; tests/test_select_corners_cpu.py): the n
+// candidate keys (float bits << 32 | raster index) of a w x h image -> up to max_corners corners in xy (room for min(n, max_corners)
+// pairs; max_corners <= 0: all of them), *count of them.  The keys are copied: select_corners sorts in place.
+__attribute__((visibility("default"))) int vstabx_select_corners(const unsigned long long *keys, unsigned int n, int w, int h, int max_corners, double min_distance,
+                                                                  float *xy, int *count) {
+    if ((n > 0 && !keys) || !xy || !count || w < 1 || h < 1 || !(min_distance >= 0.0) || !(min_distance < 1e9))
+        return fail(VSTAB_ERR_INVALID, "vstabx_select_corners: bad argument");
+    for (unsigned int i = 0; i < n; i++)  // (the grid is indexed by the pixel a key names)
+        if ((keys[i] & 0xffffffffu) >= (uint64_t)w * (uint64_t)h) return fail(VSTAB_ERR_INVALID, "vstabx_select_corners: a key names a pixel outside the image");
+    std::vector<unsigned long long> k(keys, keys + n);
+    std::vector<float> out;
+    select_corners(k.data(), n, w, h, max_corners, min_distance, out);
+    std::copy(out.begin(), out.end(), xy);
+    *count = (int)(out.size() / 2);
+    return VSTAB_OK;
+}
+
 // The detector's bookkeeping of a handle (not in vstab_profile: the ABI layout stays): out = {speculative selections that found more
-// candidates than Tracker::SPEC_CAP (the key frame then detects synchronously), fused detections that overflowed the key buffer (the
+// candidates than Detector::SPEC_CAP (the key frame then detects synchronously), fused detections that overflowed the key buffer (the
 // two-pass detector re-ran them), the key capacity now in force (0 before the first synchronous detection)}.
 __attribute__((visibility("default"))) int vstabx_detector_counters(const vstab_handle *h, long *out) {
     if (!h || !out) return fail(VSTAB_ERR_INVALID, "vstabx_detector_counters: bad argument");
-    out[0] = h->tracker.spec_over_cap(), out[1] = h->tracker.fused_overflows(), out[2] = (long)h->tracker.key_capacity();
+    out[0] = h->detector.spec_over_cap(), out[1] = h->detector.fused_overflows(), out[2] = (long)h->detector.key_capacity();
     return VSTAB_OK;
 }
 }  // extern "C"

@@ -1,4 +1,4 @@
-// vstab_track.hpp -- launchers of the tracking kernels (vstab_pyramid.hip, vstab_corners.hip, vstab_lk.hip).
+// vstab_track.hpp -- launchers of the tracking kernels (vstab_pyramid.hip, vstab_corners.hip, vstab_corners_fused.hip, vstab_lk.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,17 +39,38 @@ vstab_status launch_pack_pyr(const uint8_t *y, size_t pitch_y, const uint8_t *uv
 bool pyr_down_x2_ok(int sw, int sh);
 vstab_status launch_pyr_down_x2(const uint8_t *src, size_t spitch, int sw, int sh, uint8_t *mid, size_t mpitch, uint8_t *dst, size_t dpitch, hipStream_t s,
                                 hipEvent_t done = nullptr);
-vstab_status launch_min_eig(const uint8_t *src, size_t pitch, int w, int h, float *eig, int *max_bits, hipStream_t s);
 // k of the Harris response (vstab.h, "Harris response"): finite, 0 <= k < 0.25 -- from 0.25 on det - k tr^2 is never positive
 inline bool harris_k_ok(double k) { return k >= 0.0 && k < 0.25; }
-// launch_min_eig with the Harris response (kf = (float)k): cornerHarris(3, 3, k) as a dense map and its int-bit maximum
-vstab_status launch_corner_harris(const uint8_t *src, size_t pitch, int w, int h, float kf, float *resp, int *max_bits, hipStream_t s);
-// mask (optional, here and in launch_corners_fused): the detection mask, a w x h plane of bytes of pitch mpitch, non-zero = "a corner may
-// be reported here" (vstab.h, "Detection mask").  Without one the launches are those of the unmasked detector.  With one, max_bits of
-// launch_corner_candidates is the MASKED maximum (launch_masked_max behind launch_min_eig).
+// cornerMinEigenVal(3, 3) or, harris, cornerHarris(3, 3, k) with kf = (float)k as a dense w x h map, and its int-bit maximum
+vstab_status launch_corner_response(const uint8_t *src, size_t pitch, int w, int h, bool harris, float kf, float *resp, int *max_bits, hipStream_t s);
+// What a detection reads beside the image (vstab.h, "Detection mask" and "Harris response"), as every launcher and the Detector take it:
+//   mask    the detection mask, a w x h plane of bytes of pitch mask_pitch, non-zero = "a corner may be reported here"; NULL: none, the
+//           launches of the unmasked detector
+//   harris  cornerHarris(3, 3, k) with kf = (float)k in place of cornerMinEigenVal(3, 3) (kf is not looked at then)
+// check_detect_spec (vstab_detect_host.hpp) is where the entry points refuse a bad one.
+struct DetectSpec {
+    const uint8_t *mask = nullptr;
+    size_t mask_pitch = 0;
+    bool harris = false;
+    float kf = 0.0f;
+    DetectSpec() = default;
+    DetectSpec(const uint8_t *m, size_t pitch, bool h = false, float k = 0.0f) : mask(m), mask_pitch(m ? pitch : 0), harris(h), kf(h ? k : 0.0f) {}
+};
+// The detectors' 8 dwords of device memory (the fused launch zeroes all of them):
+struct DetectorWords {
+    unsigned int max;         // the frame maximum: biased float bits (unsigned order; 0 = no tile published one) from the fused kernels, int bits from the dense ones
+    unsigned int masked_max;  // two-pass under a mask: the maximum over the masked-in pixels (launch_masked_max), int bits
+    unsigned int pad0[2];
+    unsigned int kept;        // keys above the final threshold (may exceed the key buffer's capacity: the result is complete iff it does not)
+    unsigned int spilled;     // tiles of the fused detector that left a dense map (statistics)
+    unsigned int pad1[2];
+};
+static_assert(sizeof(DetectorWords) == 32, "8 dwords");
+// Harris: "this maximum says no response above zero", and then no corner -- its sign bit, in either encoding
+inline bool no_positive_response(unsigned int max_word, bool biased) { return (int)(biased ? max_word ^ 0x80000000u : max_word) < 0; }
+// Under a mask, max_bits of launch_corner_candidates is the MASKED maximum (launch_masked_max behind launch_corner_response); spec.harris is not looked at.
 vstab_status launch_corner_candidates(const float *eig, int w, int h, const int *max_bits, double quality,
-                                      unsigned long long *keys, unsigned int *count, unsigned int cap, hipStream_t s, const uint8_t *mask = nullptr,
-                                      size_t mpitch = 0);
+                                      unsigned long long *keys, unsigned int *count, unsigned int cap, hipStream_t s, const DetectSpec &spec = DetectSpec());
 vstab_status launch_masked_max(const float *eig, int w, int h, const uint8_t *mask, size_t mpitch, int *masked_max_bits, hipStream_t s);
 // The scratch of the fused detector for a w x h image, laid out in ONE place: a tile is CF_TW x CF_TH output pixels, and the buffer holds
 // CF_SLOTS key slots per tile, then a dense CF_TW x CF_TH float map per tile (written only by a tile with more survivors than slots),
@@ -65,8 +86,7 @@ struct CornersFusedScratch {
 };
 size_t corners_fused_scratch_bytes(int w, int h);
 vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h, double quality, void *scratch, unsigned long long *keys,
-                                  unsigned int cap, unsigned int *small, hipStream_t s, const uint8_t *mask = nullptr, size_t mpitch = 0, bool harris = false,
-                                  float kf = 0.0f);
+                                  unsigned int cap, DetectorWords *words, hipStream_t s, const DetectSpec &spec = DetectSpec());
 // One tracker launch = a SEGMENT of up to LK_SEG_MAX consecutive frame pairs (k_lk_track): pair i is (pyr[i], pyr[i + 1]).
 //   prev_pts  the n start points of pair 0 (device-readable), or NULL when
 //   chain_in  the device records of the parent launch's last pair, whose sequence number is parent_seq: slot f starts from the

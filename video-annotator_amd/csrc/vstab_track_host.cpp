@@ -1,8 +1,7 @@
-// vstab_track_host.cpp -- class Tracker (vstab_track_host.hpp): the pyramid sets, the host half of goodFeaturesToTrack, the speculative
-// detection with its helper thread, and the LK segment launches whose records the host polls.  Host C++; the kernels are those of vstab_pyramid.hip, vstab_corners.hip and vstab_lk.hip.
+// vstab_track_host.cpp -- class Tracker (vstab_track_host.hpp): the pyramid sets and the LK segment launches whose records the host polls.
+// Host C++; the kernels are those of vstab_pyramid.hip and vstab_lk.hip.  (The corner detector is vstab_detect_host.cpp.)
 #include <algorithm>
 #include <chrono>
-#include <cmath>
 #include <cstdlib>
 
 #include "vstab_hostlogic.hpp"
@@ -11,16 +10,7 @@
 namespace vstab {
 
 Tracker::~Tracker() {
-    // the helper thread polls spec_ev_ while a selection is running: stop and join it BEFORE the events go
-    if (spec_thread_started_) {
-        {
-            std::lock_guard<std::mutex> lk(spec_m_);
-            spec_quit_ = true;
-        }
-        spec_cv_.notify_one();
-        spec_thread_.join();
-    }
-    for (hipEvent_t e : {spec_ev_, ev_a_, ev_b_})
+    for (hipEvent_t e : {ev_a_, ev_b_})
         if (e) (void)hipEventDestroy(e);
 }
 
@@ -33,8 +23,6 @@ vstab_status Tracker::init(int w, int h) {
         for (int s = 0; s < PYR_SETS + PYR_DEV_EXTRA; s++) VSTAB_TRY(pyr_[s][l].ensure((size_t)lw * lh));
     }
     lvl_w_[0] = w, lvl_h_[0] = h;
-    VSTAB_TRY(small_.ensure(256));
-    VSTAB_TRY(hsmall_.ensure(256));
     // record and point buffers for the pipeline's 200 features (FrameSourceWarp.cpp:230), so that nothing is
     // reallocated while a launch that uses them is queued
     for (int b = 0; b < REC_BUFS; b++) {
@@ -71,234 +59,6 @@ vstab_status Tracker::build_pyramid(int s, const uint8_t *gray, size_t pitch, hi
         src = pyr_[s][l].as<uint8_t>(), sp = (size_t)lvl_w_[l];
     }
     return VSTAB_OK;
-}
-
-vstab_status Tracker::copy_mask(const void *mask, size_t pitch, bool host) {
-    if (!mask) {
-        set_mask(nullptr, 0);
-        return VSTAB_OK;
-    }
-    const size_t own_pitch = ((size_t)w_ + 3) & ~(size_t)3;
-    VSTAB_TRY(mask_buf_.ensure(own_pitch * (size_t)h_));
-    VSTAB_HIP_TRY(hipMemset(mask_buf_.p, 0, own_pitch * (size_t)h_));  // the padding bytes are never read; zero all the same
-    VSTAB_HIP_TRY(hipMemcpy2D(mask_buf_.p, own_pitch, mask, pitch, (size_t)w_, (size_t)h_, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
-    VSTAB_HIP_TRY(hipDeviceSynchronize());  // (a device-to-device copy may return before it is done: the caller may free the mask after this call)
-    set_mask(mask_buf_.as<uint8_t>(), own_pitch);
-    return VSTAB_OK;
-}
-
-void Tracker::select_corners(unsigned long long *k, unsigned int n, int max_corners, double min_distance, std::vector<float> &xy) {
-    xy.clear();
-    const int cell = (int)std::nearbyint(min_distance);
-    const int gw = cell >= 1 ? (w_ + cell - 1) / cell : 0, gh = cell >= 1 ? (h_ + cell - 1) / cell : 0;
-    const double md2 = min_distance * min_distance;
-    static thread_local std::vector<int> grid_head_, grid_next_;  // min-distance grid: per-cell lists of accepted corners
-    if (cell >= 1) grid_head_.assign((size_t)gw * gh, -1), grid_next_.clear();
-    // The greedy pass consumes candidates in sorted order and usually stops after a few hundred, so the
-    // keys are sorted lazily in chunks: nth_element splits off the next `chunk` largest keys (O(n)),
-    // only that chunk is sorted.  The visiting order is exactly the fully sorted order.
-    unsigned int done = 0;
-    const auto greater = [](unsigned long long a, unsigned long long b) { return a > b; };
-    while (done < n) {
-        const unsigned int chunk = std::min(n - done, 1024u);
-        if (done + chunk < n) std::nth_element(k + done, k + done + chunk, k + n, greater);
-        std::sort(k + done, k + done + chunk, greater);
-        for (unsigned int i = done; i < done + chunk; i++) {
-            const unsigned int idx = (unsigned int)(k[i] & 0xffffffffu);
-            const int x = (int)(idx % w_), y = (int)(idx / w_);
-            if (cell < 1) {
-                xy.push_back((float)x), xy.push_back((float)y);
-            } else {
-                const int xc = x / cell, yc = y / cell;
-                const int x1 = std::max(0, xc - 1), y1 = std::max(0, yc - 1), x2 = std::min(gw - 1, xc + 1), y2 = std::min(gh - 1, yc + 1);
-                bool good = true;
-                for (int yy = y1; yy <= y2 && good; yy++)
-                    for (int xx = x1; xx <= x2 && good; xx++)
-                        for (int j = grid_head_[(size_t)yy * gw + xx]; j >= 0; j = grid_next_[j]) {
-                            const float dx = (float)x - xy[2 * j], dy = (float)y - xy[2 * j + 1];
-                            if ((double)(dx * dx + dy * dy) < md2) {
-                                good = false;
-                                break;
-                            }
-                        }
-                if (!good) continue;
-                grid_next_.push_back(grid_head_[(size_t)yc * gw + xc]);
-                grid_head_[(size_t)yc * gw + xc] = (int)(xy.size() / 2);
-                xy.push_back((float)x), xy.push_back((float)y);
-            }
-            if (max_corners > 0 && (int)(xy.size() / 2) == max_corners) return;
-        }
-        done += chunk;
-    }
-}
-
-vstab_status Tracker::select_from_keys(unsigned int n, int max_corners, double min_distance, std::vector<float> &xy, hipStream_t st) {
-    if (n == 0) return VSTAB_OK;
-    VSTAB_TRY(hkeys_.ensure(sizeof(unsigned long long) * n));
-    VSTAB_HIP_TRY(hipMemcpyAsync(hkeys_.p, keys_.p, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, st));
-    VSTAB_HIP_TRY(hipStreamSynchronize(st));
-    select_corners(hkeys_.as<unsigned long long>(), n, max_corners, min_distance, xy);
-    return VSTAB_OK;
-}
-
-vstab_status Tracker::good_features(const uint8_t *gray, size_t pitch, int max_corners, double quality, double min_distance, std::vector<float> &xy, hipStream_t st, float *eig_out) {
-    xy.clear();
-    float *eig = eig_out;
-    int *max_bits = small_.as<int>();
-    unsigned int *count = small_.as<unsigned int>() + 4;
-    if (cap_ == 0) {
-        cap_ = 1u << 18;
-        VSTAB_TRY(keys_.ensure(sizeof(unsigned long long) * cap_));
-    }
-    if (!eig_out && !two_pass_detector_) {
-        // one pass: eigenvalue, threshold and 3x3 maximum test fused, the eigenvalue map never stored
-        VSTAB_TRY(raw_keys_.ensure(corners_fused_scratch_bytes(w_, h_)));
-#ifdef VSTAB_DEV
-        if (getenv("VSTAB_DEV_DET_TWICE")) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st, mask_, mask_pitch_, harris_, harris_kf_));
-#endif
-        VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, raw_keys_.p, keys_.as<unsigned long long>(), cap_, small_.as<unsigned int>(), st, mask_, mask_pitch_,
-                                       harris_, harris_kf_));
-        VSTAB_HIP_TRY(hipMemcpyAsync(hsmall_.p, count, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-        if (harris_) VSTAB_HIP_TRY(hipMemcpyAsync(hsmall_.as<unsigned int>() + 2, small_.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));  // the biased maximum
-        VSTAB_HIP_TRY(hipStreamSynchronize(st));
-        // Harris: a maximum with the sign bit set (biased: below 2^31; 0 = no tile published one) means no response above zero, and no corner
-        if (harris_ && hsmall_.as<unsigned int>()[2] < 0x80000000u) return VSTAB_OK;
-        const unsigned int kept = hsmall_.as<unsigned int>()[0];
-        if (kept <= cap_) return select_from_keys(kept, max_corners, min_distance, xy, st);
-        fused_overflows_++;  // more corners above the threshold than the key buffer holds: the two-pass detector below grows it
-    }
-    VSTAB_TRY(eig_.ensure(sizeof(float) * (size_t)w_ * h_));
-    if (!eig) eig = eig_.as<float>();
-    if (harris_) VSTAB_TRY(launch_corner_harris(gray, pitch, w_, h_, harris_kf_, eig, max_bits, st));
-    else VSTAB_TRY(launch_min_eig(gray, pitch, w_, h_, eig, max_bits, st));
-    if (mask_) {  // the threshold of a masked detection comes from the maximum over the masked-in pixels: small_[1], beside the frame's
-        VSTAB_TRY(launch_masked_max(eig, w_, h_, mask_, mask_pitch_, max_bits + 1, st));
-        max_bits += 1;
-    }
-    if (harris_) {  // as above: the sign of the (masked) maximum, before a key buffer grows for candidates above a negative threshold
-        VSTAB_HIP_TRY(hipMemcpyAsync(hsmall_.p, max_bits, sizeof(int), hipMemcpyDeviceToHost, st));
-        VSTAB_HIP_TRY(hipStreamSynchronize(st));
-        if (*hsmall_.as<int>() < 0) return VSTAB_OK;
-    }
-    unsigned int n = 0;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        VSTAB_TRY(launch_corner_candidates(eig, w_, h_, max_bits, quality, keys_.as<unsigned long long>(), count, cap_, st, mask_, mask_pitch_));
-        VSTAB_HIP_TRY(hipMemcpyAsync(hsmall_.p, count, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-        VSTAB_HIP_TRY(hipStreamSynchronize(st));
-        n = *hsmall_.as<unsigned int>();
-        if (n <= cap_) break;
-        cap_ = n;  // more local maxima than the buffer holds: grow and re-run the compaction
-        VSTAB_TRY(keys_.ensure(sizeof(unsigned long long) * cap_));
-    }
-    return select_from_keys(n, max_corners, min_distance, xy, st);
-}
-
-vstab_status Tracker::spec_launch(const uint8_t *gray, size_t pitch, double quality, hipStream_t st, long tag) {
-    spec_join();  // (a previous asynchronous selection still reading the pinned buffer: never in practice)
-    VSTAB_TRY(spec_raw_.ensure(corners_fused_scratch_bytes(w_, h_)));
-    VSTAB_TRY(spec_keys_.ensure(sizeof(unsigned long long) * SPEC_CAP));
-    VSTAB_TRY(spec_small_.ensure(256));
-    VSTAB_TRY(spec_host_.ensure(64 + sizeof(unsigned long long) * SPEC_CAP));
-    if (!spec_ev_) VSTAB_HIP_TRY(hipEventCreateWithFlags(&spec_ev_, hipEventDisableTiming));
-    unsigned int *count = spec_small_.as<unsigned int>() + 4;
-#ifdef VSTAB_DEV
-    static const bool det_twice = getenv("VSTAB_DEV_DET_TWICE") != nullptr;  // sensitivity of the frame rate to the detector: everything twice, same result
-    if (det_twice) VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st, mask_, mask_pitch_, harris_, harris_kf_));
-#endif
-    VSTAB_TRY(launch_corners_fused(gray, pitch, w_, h_, quality, spec_raw_.p, spec_keys_.as<unsigned long long>(), SPEC_CAP, spec_small_.as<unsigned int>(), st, mask_, mask_pitch_,
-                                   harris_, harris_kf_));
-    VSTAB_HIP_TRY(hipMemcpyAsync(spec_host_.p, count, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));  // {keys kept, tiles that spilled}
-    if (harris_) VSTAB_HIP_TRY(hipMemcpyAsync(spec_host_.as<unsigned int>() + 2, spec_small_.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));  // the biased maximum
-    VSTAB_HIP_TRY(hipMemcpyAsync(spec_host_.as<uint8_t>() + 64, spec_keys_.p, sizeof(unsigned long long) * SPEC_CAP, hipMemcpyDeviceToHost, st));
-    VSTAB_HIP_TRY(hipEventRecord(spec_ev_, st));
-    spec_tag_ = tag;
-    return VSTAB_OK;
-}
-
-int Tracker::spec_select(int max_corners, double min_distance, std::vector<float> &xy, unsigned int *n_seen) {
-    unsigned int n = spec_host_.as<unsigned int>()[0];
-    if (harris_ && spec_host_.as<unsigned int>()[2] < 0x80000000u) n = 0;  // no response above zero: no corner (good_features has the same test)
-    if (n_seen) *n_seen = n;
-    if (n > SPEC_CAP) {
-        spec_over_cap_.fetch_add(1, std::memory_order_relaxed);
-        return 3;
-    }
-    select_corners(reinterpret_cast<unsigned long long *>(spec_host_.as<uint8_t>() + 64), n, max_corners, min_distance, xy);
-    return 2;
-}
-
-void Tracker::spec_select_async(int max_corners, double min_distance) {
-    spec_join();
-    spec_owner_.store(0, std::memory_order_release);  // nobody has taken this selection yet (the helper thread, or the caller: spec_poll_inline)
-    spec_state_.store(1, std::memory_order_release);
-    if (!spec_thread_started_) {
-        spec_thread_started_ = true;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        spec_thread_ = std::thread([this, dev] {
-            (void)hipSetDevice(dev);  // the handle's device, not the new thread's default
-            std::unique_lock<std::mutex> lk(spec_m_);
-            for (;;) {
-                spec_cv_.wait(lk, [this] { return spec_job_ || spec_quit_; });
-                if (spec_quit_) return;
-                spec_job_ = false;
-                {
-                    // (development: VSTAB_SPEC_HELPER_DELAY_US=n makes this thread wake up late, so that a test reaches spec_poll_inline;
-                    //  read ONCE, when the Tracker is constructed -- getenv beside a setenv of the host process is undefined behaviour)
-                    const long late_us = spec_late_us_;
-                    if (late_us > 0) {
-                        lk.unlock();
-                        std::this_thread::sleep_for(std::chrono::microseconds(late_us));
-                        lk.lock();
-                        if (spec_quit_) return;
-                    }
-                    int unclaimed = 0;  // the caller may have done this selection itself while this thread was waking up
-                    if (!spec_owner_.compare_exchange_strong(unclaimed, 1, std::memory_order_acq_rel)) continue;
-                    selections_by_helper_.fetch_add(1, std::memory_order_relaxed);
-                }
-                lk.unlock();
-                int result = 3;
-                const auto t0 = std::chrono::steady_clock::now();
-                // poll instead of a blocking wait: the wake-up latency of hipEventSynchronize (hundreds of microseconds
-                // on this runtime) would eat the lead the detection was given
-                hipError_t q = hipErrorNotReady;
-                if (spec_ev_) {
-                    for (long spins = 0; (q = hipEventQuery(spec_ev_)) == hipErrorNotReady && spins < 4000000; spins++) __builtin_ia32_pause();
-                    if (q == hipErrorNotReady) q = hipEventSynchronize(spec_ev_);
-                }
-                if (q == hipSuccess) {
-                    const auto t1 = std::chrono::steady_clock::now();
-                    unsigned int n = 0;
-                    result = spec_select(spec_max_, spec_dist_, spec_xy_, &n);
-                    if (debug_spec())
-                        std::fprintf(stderr, "async selection: waited %.0f us for the detection, selected %zu of %u candidates in %.0f us\n",
-                                     std::chrono::duration<double, std::micro>(t1 - t0).count(), spec_xy_.size() / 2, n,
-                                     std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count());
-                }
-                spec_state_.store(result, std::memory_order_release);
-                lk.lock();
-            }
-        });
-    }
-    {
-        std::lock_guard<std::mutex> lk(spec_m_);
-        spec_max_ = max_corners, spec_dist_ = min_distance, spec_job_ = true;
-    }
-    spec_cv_.notify_one();
-}
-
-void Tracker::spec_poll_inline() {
-    if (spec_state_.load(std::memory_order_acquire) != 1 || !spec_ev_ || hipEventQuery(spec_ev_) != hipSuccess) {
-        (void)hipGetLastError();  // "not ready" is an answer, not an error the next launch check should find
-        return;
-    }
-    int unclaimed = 0;
-    if (!spec_owner_.compare_exchange_strong(unclaimed, 2, std::memory_order_acq_rel)) return;  // the helper thread has it
-    selections_by_caller_++;
-    unsigned int n = 0;
-    const int result = spec_select(spec_max_, spec_dist_, spec_xy_, &n);
-    if (debug_spec()) std::fprintf(stderr, "selection done by the caller (the helper thread had not woken up): %zu of %u candidates\n", spec_xy_.size() / 2, n);
-    spec_state_.store(result, std::memory_order_release);
 }
 
 vstab_status Tracker::track_wait(const Launch &L, int idx, size_t expect_n, std::vector<float> &next_xy, std::vector<uint8_t> &status, hipStream_t st, double *gpu_ms) {

@@ -1,12 +1,8 @@
-// vstab_track_host.hpp -- class Tracker, the host side of the tracker (defined in vstab_track_host.cpp): used by the pipeline object, the
-// stateless vstab_good_features* / vstab_pyr_lk and the vstabx_lk_segments hook.
+// vstab_track_host.hpp -- class Tracker, the host side of the LK tracker (defined in vstab_track_host.cpp): used by the pipeline object, the
+// stateless vstab_pyr_lk and the vstabx_lk_segments hook.  The corner detector beside it is class Detector (vstab_detect_host.hpp).
 #pragma once
-#include <atomic>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 #include "vstab_internal.hpp"
@@ -14,13 +10,8 @@
 
 namespace vstab {
 
-inline bool debug_spec() {  // VSTAB_DEBUG_SPEC=1: the key-frame speculation narrated on stderr (development aid)
-    static const bool on = getenv("VSTAB_DEBUG_SPEC") != nullptr;
-    return on;
-}
-
 // ---------------------------------------------------------------------------------------------
-// Tracker: device workspace for goodFeaturesToTrack + calcOpticalFlowPyrLK
+// Tracker: device workspace for calcOpticalFlowPyrLK
 // ---------------------------------------------------------------------------------------------
 constexpr int PREFETCH_MAX = 16;             // upper bound of the read-ahead (the ring and the pyramid sets are sized for it)
 constexpr int PYR_SETS = PREFETCH_MAX + 2;  // previous + current (in flight) + the prefetched frames
@@ -53,70 +44,6 @@ class Tracker {
         p.img[0] = gray, p.pitch[0] = pitch, p.w[0] = w_, p.h[0] = h_;
         for (int l = 1; l < levels_; l++) p.img[l] = pyr_[s][l].as<uint8_t>(), p.pitch[l] = (size_t)lvl_w_[l], p.w[l] = lvl_w_[l], p.h[l] = lvl_h_[l];
         return p;
-    }
-
-    // host half of goodFeaturesToTrack: sort the candidate keys (value descending, ties -> later raster
-    // position first: greaterThanPtr in OpenCV) and run the minimum-distance grid
-    void select_corners(unsigned long long *k, unsigned int n, int max_corners, double min_distance, std::vector<float> &xy);
-    // goodFeaturesToTrack(gray, max_corners, quality, min_distance); synchronises the stream
-    vstab_status good_features(const uint8_t *gray, size_t pitch, int max_corners, double quality, double min_distance, std::vector<float> &xy, hipStream_t st, float *eig_out = nullptr);
-
-    // Speculative detection: the same two kernels enqueued on another stream ahead of time (the counter
-    // half of the key-frame rule is predictable), with the count and the first SPEC_CAP keys copied to
-    // pinned memory behind them.  spec_finish() only has to wait for the event and run the host half.
-    static constexpr unsigned int SPEC_CAP = 1u << 15;
-    vstab_status spec_launch(const uint8_t *gray, size_t pitch, double quality, hipStream_t st, long tag);
-    long spec_tag() const { return spec_tag_; }
-    long selections_by_caller() const { return selections_by_caller_; }
-    long selections_by_helper() const { return selections_by_helper_.load(std::memory_order_relaxed); }
-    void set_two_pass_detector(bool on) { two_pass_detector_ = on; }
-    // The detection mask (vstab.h, "Detection mask"): a device plane of w x h bytes, non-zero = "a corner may be reported here", read by
-    // every detection from now on -- good_features (fused, two-pass and the fall-back between them) and spec_launch.  NULL: no mask, the
-    // launches of the unmasked detector.  set_mask borrows the caller's plane; copy_mask keeps a copy in device memory of the Tracker's
-    // own (base and pitch 4-byte aligned: the kernels' dword path) and returns when the copy is complete.  Only while nothing is in flight.
-    void set_mask(const uint8_t *mask, size_t pitch) { mask_ = mask, mask_pitch_ = mask ? pitch : 0; }
-    vstab_status copy_mask(const void *mask, size_t pitch, bool host);
-    const uint8_t *mask() const { return mask_; }
-    size_t mask_pitch() const { return mask_pitch_; }
-    // The corner response (vstab.h, "Harris response"): harris = false is cornerMinEigenVal(3, 3), the Tracker as it always was (kf is
-    // not looked at); harris = true is cornerHarris(3, 3, k) with kf = (float)k, read by every detection from now on -- good_features (its
-    // three paths, and the map it hands out through eig_out) and spec_launch.  Under it a frame whose (masked) maximum is not positive has
-    // no corner: decided on the host from the sign of the maximum the kernels publish.  Only while nothing is in flight.
-    void set_response(bool harris, float kf) { harris_ = harris, harris_kf_ = harris ? kf : 0.0f; }
-    long fused_overflows() const { return fused_overflows_; }
-    // (vstabx_detector_counters) speculative selections that found more than SPEC_CAP candidates; the key capacity of good_features now
-    long spec_over_cap() const { return spec_over_cap_.load(std::memory_order_relaxed); }
-    unsigned int key_capacity() const { return cap_; }
-    // Host half of the speculative detection on a helper thread: waits for the kernels' results and runs the
-    // sort + minimum-distance pass, so that by the time the key frame comes its corners are simply there.
-    void spec_select_async(int max_corners, double min_distance);
-    // The helper thread sleeps on a condition variable between two detections (720 us apart at 4K); on a busy host its wake-up can take
-    // longer than the detection itself.  Whoever looks for the corners first while the job is still unclaimed and the detection's event
-    // has completed does the selection on the spot (45 us of host time instead of a wait for another thread's wake-up).
-    void spec_poll_inline();
-    // 0 = no asynchronous selection, 1 = running, 2 = corners ready, 3 = failed (candidate overflow / device error)
-    int spec_state() const { return spec_state_.load(std::memory_order_acquire); }
-    void spec_join() {
-        while (spec_state_.load(std::memory_order_acquire) == 1) std::this_thread::yield();
-    }
-    // take the asynchronously selected corners (state must be 2)
-    void spec_take(std::vector<float> &xy) {
-        xy = spec_xy_;
-        spec_state_.store(0, std::memory_order_release), spec_tag_ = -1;
-    }
-    // returns true and fills xy if the speculative result is usable (candidate count within SPEC_CAP)
-    bool spec_finish(int max_corners, double min_distance, std::vector<float> &xy) {
-        if (spec_state() != 0) {  // the helper thread has (or is about to have) the answer -- or nobody yet: then this thread, if the kernels are through
-            spec_poll_inline();
-            spec_join();
-            const bool ok = spec_state() == 2;
-            if (ok) xy = spec_xy_;
-            spec_state_.store(0, std::memory_order_release), spec_tag_ = -1;
-            return ok;
-        }
-        spec_tag_ = -1;
-        if (!spec_ev_ || hipEventSynchronize(spec_ev_) != hipSuccess) return false;
-        return spec_select(max_corners, min_distance, xy) == 2;
     }
 
     // calcOpticalFlowPyrLK(prev, next, pts), split in two so the caller can enqueue more work behind the
@@ -190,45 +117,15 @@ class Tracker {
 
   private:
     vstab_status launch_segment(const LkPyramid *pyr, int n_frames, const float2 *prev_pts, const void *chain_in, uint32_t parent_seq, hipStream_t st, Launch &L);
-    // host half of a finished speculative detection: the corners into xy and spec_state's 2, or 3 for more candidates than SPEC_CAP; *n_seen = their count
-    int spec_select(int max_corners, double min_distance, std::vector<float> &xy, unsigned int *n_seen = nullptr);
-    // the tail of good_features: the first n keys of keys_ to the host (synchronises the stream), then select_corners
-    vstab_status select_from_keys(unsigned int n, int max_corners, double min_distance, std::vector<float> &xy, hipStream_t st);
-
     int w_ = 0, h_ = 0, levels_ = 1;
     int lvl_w_[LK_MAX_LEVELS] = {0}, lvl_h_[LK_MAX_LEVELS] = {0};
-    DevBuf pyr_[PYR_SETS + PYR_DEV_EXTRA][LK_MAX_LEVELS], eig_, keys_, small_;  // pyramid sets: previous, current, prefetched x2
-    DevBuf spec_raw_, spec_keys_, spec_small_, raw_keys_;
-    bool two_pass_detector_ = false;
-    const uint8_t *mask_ = nullptr;  // the detection mask in force (mask_buf_'s, or a caller's), NULL for none
-    size_t mask_pitch_ = 0;
-    DevBuf mask_buf_;
-    bool harris_ = false;  // the response in force: cornerHarris(3, 3, k) with harris_kf_ = (float)k, or cornerMinEigenVal(3, 3)
-    float harris_kf_ = 0.0f;
+    DevBuf pyr_[PYR_SETS + PYR_DEV_EXTRA][LK_MAX_LEVELS];  // pyramid sets: previous, current, prefetched x2
     const bool single_level_pyramid_ = getenv("VSTAB_PYR_SINGLE") != nullptr;  // development: one launch per pyramid level
-    long fused_overflows_ = 0;
-    PinnedBuf spec_host_;
-    hipEvent_t spec_ev_ = nullptr;
-    long spec_tag_ = -1;
-    std::thread spec_thread_;
-    bool spec_thread_started_ = false, spec_job_ = false, spec_quit_ = false;
-    std::mutex spec_m_;
-    std::condition_variable spec_cv_;
-    std::atomic<int> spec_state_{0};
-    std::atomic<int> spec_owner_{0};  // who runs the posted selection: 0 nobody yet, 1 the helper thread, 2 the caller (spec_poll_inline)
-    const long spec_late_us_ = getenv("VSTAB_SPEC_HELPER_DELAY_US") ? atol(getenv("VSTAB_SPEC_HELPER_DELAY_US")) : 0;  // development: the helper wakes up late
-    long selections_by_caller_ = 0;                 // speculative detections whose corners the caller selected itself / the helper thread selected
-    std::atomic<long> selections_by_helper_{0};
-    std::atomic<long> spec_over_cap_{0};            // selections (by either thread) that ended in state 3 for their count
-    int spec_max_ = 200;
-    double spec_dist_ = 30.0;
-    std::vector<float> spec_xy_;
     static constexpr int CLK_N = 4096;
     DevBuf clk_;
     int clk_used_ = 0;
-    PinnedBuf hsmall_, hkeys_, hpts_[PTS_BUFS], hrec_[REC_BUFS];
+    PinnedBuf hpts_[PTS_BUFS], hrec_[REC_BUFS];
     DevBuf drec_[REC_BUFS];
-    unsigned int cap_ = 0;
     hipEvent_t ev_a_ = nullptr, ev_b_ = nullptr;
     unsigned long rec_next_ = 0, pts_launches_ = 0;
     uint32_t seq_ = 0;
