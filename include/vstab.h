@@ -426,7 +426,12 @@ VSTAB_API vstab_status vstab_min_eig(const void *gray, size_t pitch, int width, 
 
 /* Replaces find_corners -> goodFeaturesToTrack(gray, max_corners, quality, min_distance),
  * FrameSourceWarp.cpp:228-240 (the reference passes 200, 0.01, 30).  xy receives up to
- * max_corners (x,y) float pairs in acceptance order; *count the number found. */
+ * max_corners (x,y) float pairs in acceptance order; *count the number found.
+ * Arguments, as goodFeaturesToTrack asserts them: quality > 0 and min_distance >= 0; NaN fails either.  quality = +inf passes and finds
+ * no corner (nothing lies above an infinite threshold), as every quality >= 1 does under the strict >.  min_distance = +inf or beyond the
+ * image's diagonal passes and gives one corner, the strongest.  vstab_good_features, _ex, _mask and _harris refuse anything else with
+ * VSTAB_ERR_INVALID and "<function>: quality must be > 0 and min_distance >= 0" -- behind "<function>: bad argument" (max_corners <= 0
+ * is one) and before the mask's and k's checks. */
 VSTAB_API vstab_status vstab_good_features(const void *gray, size_t pitch, int width, int height,
                                            int max_corners, double quality, double min_distance,
                                            float *xy, int *count, void *stream);
@@ -464,7 +469,8 @@ VSTAB_API vstab_status vstab_good_features_ex(const void *gray, size_t pitch, in
  * vstab_good_features_ex.  detector: VSTAB_DETECTOR_AUTO and VSTAB_DETECTOR_FUSED (the same here: the fused pass, and the two-pass detector
  * behind it when more than 2^18 keys survive) or VSTAB_DETECTOR_TWO_PASS; all honour the mask and give the same corners.  Refused with
  * VSTAB_ERR_INVALID before any launch, in this order: "vstab_good_features_mask: bad argument" (what vstab_good_features_ex refuses, an
- * unknown detector included); with a mask, "vstab_good_features_mask: the mask's pitch is smaller than the image's width" and
+ * unknown detector included); "vstab_good_features_mask: quality must be > 0 and min_distance >= 0" (vstab_good_features above);
+ * with a mask, "vstab_good_features_mask: the mask's pitch is smaller than the image's width" and
  * "vstab_good_features_mask: mask planes of 4 GiB or more are not supported" ((uint64_t)pitch_mask * height >= 2^32). */
 VSTAB_API vstab_status vstab_good_features_mask(const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask,
                                                 int max_corners, double quality, double min_distance, int detector,
@@ -505,7 +511,9 @@ VSTAB_API vstab_status vstab_good_features_harris(const void *gray, size_t pitch
 
 /* Replaces calcOpticalFlowPyrLK with default parameters (win 21x21, maxLevel 3, 30 iterations,
  * eps 0.01, minEigThreshold 1e-4), FrameSourceWarp.cpp:252.  prev/next: device gray images of the
- * same size; prev_xy: n host (x,y) pairs; next_xy / status: host outputs (n pairs / n bytes). */
+ * same size; prev_xy: n host (x,y) pairs; next_xy / status: host outputs (n pairs / n bytes).
+ * A start point with a NaN or infinite coordinate, or one whose window origin lies outside int, is never tracked: status 0 and the
+ * point returned as it came (a NaN stays a NaN), as OpenCV's float-to-int conversion (INT_MIN for all of these) decides it. */
 VSTAB_API vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const void *next,
                                     size_t pitch_next, int width, int height, const float *prev_xy,
                                     int n, float *next_xy, unsigned char *status, void *stream);

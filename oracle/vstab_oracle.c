@@ -739,7 +739,10 @@ VO_API int vo_good_features(const uint8_t *gray, size_t pitch, int w, int h, int
             if (v == m) cand[nc].v = v, cand[nc].idx = y * w + x, nc++;
         }
     qsort(cand, nc, sizeof(vo_cand), vo_cand_cmp);
-    int cell = (int)lrint(min_distance);
+    /* the cell is clamped to the longer side before it becomes an int: any larger cell is the same 1 x 1 grid, and lrint of a
+     * double beyond long (or of inf) is undefined.  The distance test below runs on min_distance as given. */
+    double longer = (double)(w > h ? w : h);
+    int cell = (int)lrint(min_distance < longer ? min_distance : longer);
     int n = 0;
     if (cell < 1) {
         for (size_t i = 0; i < nc && (max_corners <= 0 || n < max_corners); i++) {
@@ -888,7 +891,11 @@ VO_API int vo_pyramid_levels(int w, int h) {
     return nl;
 }
 
-static inline int vo_cvfloor(float v) { return (int)floorf(v); }
+/* cvFloor = SSE cvtss2si and a correction: NaN / out of int range -> INT_MIN (as vo_cvround), which every range test below refuses */
+static inline int vo_cvfloor(float v) {
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return INT_MIN;
+    return (int)floorf(v);
+}
 
 /* Accumulation of the LK sums.  0 (normative for this project): exact int64 sums converted once.  1: fp32 accumulation in
  * raster order, the literal reading of OpenCV's scalar loop -- only used to MEASURE what the documented

@@ -46,10 +46,13 @@ inline LkParse lk_parse_records(const volatile uint32_t *rec, int first, int n, 
 // ---- corner selection ----------------------------------------------------------------------------------------------------------
 // host half of goodFeaturesToTrack over the n candidate keys (float bits << 32 | raster index) of a w x h image: sort them (value
 // descending, ties -> later raster position first: greaterThanPtr in OpenCV) and run the minimum-distance grid.
-// Sorts k in place.
+// Sorts k in place.  min_distance >= 0 (the entry points refuse the rest), +inf included: the grid's cell is clamped to the image's longer
+// side BEFORE it becomes an int -- any larger cell is the same 1 x 1 grid with the same answers, and the conversion of a double beyond int
+// (or of inf) is undefined; the distance test itself runs on min_distance as given (its square may be +inf: one corner).
 inline void select_corners(unsigned long long *k, unsigned int n, int w, int h, int max_corners, double min_distance, std::vector<float> &xy) {
     xy.clear();
-    const int cell = (int)std::nearbyint(min_distance);
+    const double longer = (double)std::max(w, h);
+    const int cell = (int)std::nearbyint(min_distance < longer ? min_distance : longer);
     const int gw = cell >= 1 ? (w + cell - 1) / cell : 0, gh = cell >= 1 ? (h + cell - 1) / cell : 0;
     const double md2 = min_distance * min_distance;
     static thread_local std::vector<int> grid_head_, grid_next_;  // min-distance grid: per-cell lists of accepted corners

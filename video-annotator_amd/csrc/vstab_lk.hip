@@ -234,9 +234,16 @@ __device__ __forceinline__ void lk_bilinear_weights(float a, float b, int &w00, 
     w10 = (int)rintf((1.f - a) * b * 16384.f);
     w11 = 16384 - w00 - w01 - w10;
 }
+// The range test of a window origin floor(q) against [-LKW, w) x [-LKW, h), on the floats themselves: floor(q) >= -LKW iff q >= -LKW and
+// floor(q) < w iff q < w (both bounds are integers a float holds exactly), so every finite q decides as the reference's integer test
+// does.  A NaN fails it, as it fails the reference's -- whose conversion turns NaN and everything outside int into INT_MIN; the
+// conversion here turns NaN into 0, which the integer test would take for a window at the image's corner.
+__device__ __forceinline__ bool lk_origin_in_range(float qx, float qy, int w, int h) {
+    return qx >= -(float)LKW && qx < (float)w && qy >= -(float)LKW && qy < (float)h;
+}
 // Where the window of a point sits in level l (w x h) of the previous image: its top-left pixel floor(p 2^-l - half), whether the level
-// is tracked at all (the origin lies in [-LKW, w) x [-LKW, h): the staging, the preparation and the level loop all skip it otherwise),
-// and the weights of the four taps of a window pixel.
+// is tracked at all (the origin lies in [-LKW, w) x [-LKW, h): the staging, the preparation and the level loop all skip it otherwise;
+// never for a NaN or infinite coordinate), and the weights of the four taps of a window pixel.
 struct LkLevelGeom {
     int ipx, ipy, iw00, iw01, iw10, iw11;
     bool ok;
@@ -247,7 +254,7 @@ __device__ __forceinline__ LkLevelGeom lk_level_geom(float2 p, int l, int w, int
     qx -= LK_HALF, qy -= LK_HALF;
     LkLevelGeom g;
     g.ipx = (int)floorf(qx), g.ipy = (int)floorf(qy);
-    g.ok = !(g.ipx < -LKW || g.ipx >= w || g.ipy < -LKW || g.ipy >= h);
+    g.ok = lk_origin_in_range(qx, qy, w, h);
     lk_bilinear_weights(qx - (float)g.ipx, qy - (float)g.ipy, g.iw00, g.iw01, g.iw10, g.iw11);
     return g;
 }
@@ -629,7 +636,7 @@ __global__ void __launch_bounds__(LK_THREADS, 3) k_lk_track(LkSegArgs args) {
                 for (int j = 0; j < 30; j++) {
                     n_iter++;
                     const int inx = (int)floorf(npx), iny = (int)floorf(npy);
-                    if (inx < -LKW || inx >= w || iny < -LKW || iny >= h) {
+                    if (!lk_origin_in_range(npx, npy, w, h)) {
                         if (level == 0) st = 0;
                         break;
                     }
@@ -668,8 +675,7 @@ __global__ void __launch_bounds__(LK_THREADS, 3) k_lk_track(LkSegArgs args) {
                 // level 0 the final position -- the stored point minus the half window -- is tested against the image once
                 // more, and a feature whose last step (or half-step correction) carried its window out is dropped.
                 if (level == 0 && st) {
-                    const int fnx = (int)floorf(np.x - LK_HALF), fny = (int)floorf(np.y - LK_HALF);
-                    if (fnx < -LKW || fnx >= w || fny < -LKW || fny >= h) st = 0;
+                    if (!lk_origin_in_range(np.x - LK_HALF, np.y - LK_HALF, w, h)) st = 0;
                 }
             } while (false);
             if (t.tid == 0) sh.s_est[level & 1][0] = np.x, sh.s_est[level & 1][1] = np.y;  // (a skipped level leaves np at its start value, as the reference does)

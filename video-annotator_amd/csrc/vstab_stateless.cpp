@@ -163,6 +163,8 @@ static vstab_status good_features_op(const char *fn, bool fused_ok, const void *
     if (!gray || !xy || !count || width < 3 || height < 3 || pitch < (size_t)width || max_corners <= 0 ||
         (detector != VSTAB_DETECTOR_AUTO && detector != VSTAB_DETECTOR_TWO_PASS && !(fused_ok && detector == VSTAB_DETECTOR_FUSED)))
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": bad argument");
+    // goodFeaturesToTrack's own assertion (NaN fails both halves; quality = +inf passes and finds no corner)
+    if (!(quality > 0.0) || !(min_distance >= 0.0)) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": quality must be > 0 and min_distance >= 0");
     DetectSpec spec;
     VSTAB_TRY(check_detect_spec(fn, mask, pitch_mask, harris, k, width, height, spec));
     Detector t;

@@ -288,7 +288,7 @@ __attribute__((visibility("default"))) int vstabx_warp_route(int map_mode, int l
 // pairs; max_corners <= 0: all of them), *count of them.  The keys are copied: select_corners sorts in place.
 __attribute__((visibility("default"))) int vstabx_select_corners(const unsigned long long *keys, unsigned int n, int w, int h, int max_corners, double min_distance,
                                                                   float *xy, int *count) {
-    if ((n > 0 && !keys) || !xy || !count || w < 1 || h < 1 || !(min_distance >= 0.0) || !(min_distance < 1e9))
+    if ((n > 0 && !keys) || !xy || !count || w < 1 || h < 1 || !(min_distance >= 0.0))  // (+inf is a distance: select_corners clamps its cell)
         return fail(VSTAB_ERR_INVALID, "vstabx_select_corners: bad argument");
     for (unsigned int i = 0; i < n; i++)  // (the grid is indexed by the pixel a key names)
         if ((keys[i] & 0xffffffffu) >= (uint64_t)w * (uint64_t)h) return fail(VSTAB_ERR_INVALID, "vstabx_select_corners: a key names a pixel outside the image");
