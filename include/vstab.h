@@ -518,6 +518,41 @@ VSTAB_API vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const v
                                     size_t pitch_next, int width, int height, const float *prev_xy,
                                     int n, float *next_xy, unsigned char *status, void *stream);
 
+/* ---- Tracker options -----------------------------------------------------------------------------------------------------------------
+ * calcOpticalFlowPyrLK's maxLevel, criteria (count and epsilon), minEigThreshold, flags and err: a restatement of OpenCV 4.5's CPU
+ * LKTrackerInvoker in this library's arithmetic (exact integer sums converted once, the float operations in the documented order).  It
+ * claims no bit equality with OpenCV.  winSize stays 21 x 21 and is not offered, as blockSize other than 3 is not offered for the detector:
+ * the kernel's staging, its seven window pixels per lane and its LDS layout are built on it.
+ *   1. Levels.  The pyramid has min(levels of vstab_pyr_lk, max_level + 1) levels.  Everything else about a level is as in vstab_pyr_lk.
+ *   2. Start of the top level.  With VSTAB_LK_USE_INITIAL_FLOW next_xy is also an input: the top level L starts the next-image estimate at
+ *      next_xy[i] * (float)(1.0 / (1 << L)); without the flag at the scaled previous point.  The previous image's side -- the window, the
+ *      derivatives, the matrix and the per-level range test of the previous point -- is untouched.  A guess is caller data and may be any
+ *      float; vstab_pyr_lk's rule holds with the guess in the start point's place: a NaN, infinite or out-of-int guess fails the range test
+ *      of the first iteration at every level and gives status 0 and the guess back bit for bit.  A guess equal to prev_xy gives the bytes
+ *      of the call without the flag.
+ *   3. Iterations.  A level runs at most max_iter Gauss-Newton steps and ends on (double)dx*dx + (double)dy*dy <= (double)eps * (double)eps.
+ *      The oscillation rule (two successive steps that cancel to within 0.01) keeps OpenCV's fixed 0.01.
+ *   4. Rejection.  A level is rejected when minEig < (float)min_eig_threshold || D < FLT_EPSILON, minEig being the smaller eigenvalue of the
+ *      level's 2 x 2 gradient matrix divided by 2 * 21 * 21, in float.
+ *   5. err, default mode.  At level 0, for a point whose status is still 1 after the final range test: f = next - 10 in float, the origin is
+ *      floor(f), the four 14-bit weights are those of its fraction, S = the sum over the 441 window pixels of
+ *      |DESCALE(interpolated next image, 9) - interpolated previous window|.  S is an integer <= 441 * 8160 < 2^24, so OpenCV's float
+ *      accumulation of it is exact and its order free.  err = (float)S / 14112.0f (32 * 21 * 21), one binary32 division.  Every point with
+ *      status 0 gets err = 0.
+ *   6. err with VSTAB_LK_GET_MIN_EIGENVALS.  err is the minEig of rule 4 of the finest level whose matrix was formed -- a level whose
+ *      previous-point range test passed --, written before the rejection test, so a rejected point still reports it; 0 if no level got
+ *      that far.  Status does not gate it.
+ * OpenCV clamps where this library refuses.  vstab_pyr_lk_ex is refused with VSTAB_ERR_INVALID before any launch, in this order:
+ * "vstab_pyr_lk_ex: bad argument" (what vstab_pyr_lk refuses); "vstab_pyr_lk_ex: max_level lies in 0 .. 3"; "vstab_pyr_lk_ex: max_iter
+ * lies in 1 .. 100"; "vstab_pyr_lk_ex: eps is finite and lies in [0, 10]"; "vstab_pyr_lk_ex: min_eig_threshold is finite and not
+ * negative"; "vstab_pyr_lk_ex: unknown flag"; "vstab_pyr_lk_ex: VSTAB_LK_GET_MIN_EIGENVALS needs err".
+ * err: n host floats, or NULL.  With every option at its default (3, 30, 0.01, 1e-4), no flag and err == NULL the call is vstab_pyr_lk:
+ * the same kernel and the same bytes. */
+enum { VSTAB_LK_USE_INITIAL_FLOW = 4, VSTAB_LK_GET_MIN_EIGENVALS = 8 }; /* OpenCV's values */
+VSTAB_API vstab_status vstab_pyr_lk_ex(const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height,
+                                       const float *prev_xy, int n, float *next_xy, unsigned char *status, float *err /* may be NULL */,
+                                       int max_level, int max_iter, double eps, double min_eig_threshold, int flags, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Host-side motion model.
  * ------------------------------------------------------------------------------------------ */
@@ -1059,6 +1094,14 @@ VSTAB_API vstab_status vstab_set_detection_mask(vstab_handle *h, const void *mas
  * "vstab_set_corner_response: the response must be set before the first pull"; "vstab_set_corner_response: response must be
  * VSTAB_CORNER_MIN_EIGENVAL (0) or VSTAB_CORNER_HARRIS (1)"; "vstab_set_corner_response: k lies in [0, 0.25)". */
 VSTAB_API vstab_status vstab_set_corner_response(vstab_handle *h, int response, double k);
+
+/* The handle's tracker options ("Tracker options" above, rules 1, 3 and 4): every tracker launch of the handle runs with them, and the
+ * handle's pyramids have min(levels, max_level + 1) levels.  It takes no flags: err and the initial flow are stateless only
+ * (vstab_pyr_lk_ex).  Without this call, or with (3, 30, 0.01, 1e-4), the handle runs what it ran before the options existed.
+ * Refused with VSTAB_ERR_INVALID and the handle unchanged, in this order: "vstab_set_tracker_options: null handle";
+ * "vstab_set_tracker_options: no tracker runs on this handle (tracking = 0)"; "vstab_set_tracker_options: the options must be set before
+ * the first pull"; then vstab_pyr_lk_ex's four option messages under this name. */
+VSTAB_API vstab_status vstab_set_tracker_options(vstab_handle *h, int max_level, int max_iter, double eps, double min_eig_threshold);
 /* vstab_pull_frame / vstab_pull_frame_nv12_planar with kept edges ("Keep edges" above): the next frame, warped by vstab_warp_nv12_keep with
  * the caller's previous output prev (prev_y / prev_uv) -- a second buffer (a ring of two outputs), or dst itself (in place).  A frame that
  * carries a read-out rotation is warped per row, as a plain INTER_LINEAR pull warps it.  Keep pulls and plain pulls may alternate frame by

@@ -158,6 +158,16 @@ class FrameSourceWarp : public FrameSource {
         }
     }
 
+    // calcOpticalFlowPyrLK's maxLevel, criteria (count, epsilon) and minEigThreshold for the tracking at FrameSourceWarp.cpp:252, which passes
+    // none of them (3, 30, 0.01, 1e-4); before the first pull_frame -- vstab_set_tracker_options
+    void set_tracker_options(int max_level = 3, int max_iter = 30, double eps = 0.01, double min_eig_threshold = 1e-4) {
+        const vstab_status st = vstab_set_tracker_options(m_handle, max_level, max_iter, eps, min_eig_threshold);
+        if (st != VSTAB_OK) {
+            std::fprintf(stderr, "FrameSourceWarp: %s\n", vstab_last_error());
+            throw (int)st;
+        }
+    }
+
     BGRFrame pull_frame() override {  // FrameSourceWarp.cpp:452-476
         if (!m_out) throw -1;
         const vstab_status st = vstab_pull_frame(m_handle, m_out, m_pitch);

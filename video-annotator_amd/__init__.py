@@ -122,6 +122,7 @@ SIGNATURES = {
     "vstab_warp_p010": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _vp, _sz, _i, _i, _vp]),
     "vstab_good_features_ex": (_i, [_vp, _sz, _i, _i, _i, _d, _d, _i, _fp, _ip, _ip, _vp]),
     "vstab_pyr_lk": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _fp, _u8p, _vp]),
+    "vstab_pyr_lk_ex": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _fp, _u8p, _fp, _i, _i, _d, _d, _i, _vp]),
     "vstab_estimate_rotation": (_i, [_fp, _fp, _i, _dp, _dp, _u64, _dp, _ip]),
     "vstab_time_next_launch": (None, [_vp, _vp]),
     "vstab_sg_weights": (_i, [_i, _dp]),
@@ -195,6 +196,7 @@ SIGNATURES = {
     "vstab_corner_harris": (_i, [_vp, _sz, _i, _i, _d, _vp, _vp]),
     "vstab_good_features_harris": (_i, [_vp, _sz, _i, _i, _vp, _sz, _i, _d, _d, _d, _i, _fp, _ip, _ip, _vp]),
     "vstab_set_corner_response": (_i, [_vp, _i, _d]),
+    "vstab_set_tracker_options": (_i, [_vp, _i, _i, _d, _d]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -886,6 +888,27 @@ def pyr_lk(prev, nxt, pts):
     return out, st
 
 
+LK_USE_INITIAL_FLOW, LK_GET_MIN_EIGENVALS = 4, 8   # calcOpticalFlowPyrLK's flags (OpenCV's values)
+
+
+def pyr_lk_ex(prev, nxt, pts, max_level=3, max_iter=30, eps=0.01, min_eig_threshold=1e-4, flags=0, guess=None, want_err=True):
+    """vstab_pyr_lk_ex (include/vstab.h, "Tracker options"): calcOpticalFlowPyrLK with maxLevel, the criteria's count and epsilon,
+    minEigThreshold, flags and err; winSize stays 21 x 21.  guess: the n start positions in the next image, read with LK_USE_INITIAL_FLOW
+    (any float).  -> (next points (n, 2) float32, status (n,) uint8, err (n,) float32 or None without want_err)."""
+    h, w = prev.shape
+    p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+    n = p.shape[0]
+    out = np.zeros((n, 2), np.float32)
+    if guess is not None:
+        out[:] = np.asarray(guess, np.float32).reshape(-1, 2)
+    st = np.zeros(n, np.uint8)
+    err = np.zeros(n, np.float32) if want_err else None
+    _check(_L.vstab_pyr_lk_ex(prev.data_ptr(), prev.stride(0), nxt.data_ptr(), nxt.stride(0), w, h, _fptr(p), n, _fptr(out), st.ctypes.data_as(_u8p),
+                              _fptr(err) if want_err else None, int(max_level), int(max_iter), float(eps), float(min_eig_threshold), int(flags), _stream()),
+           "vstab_pyr_lk_ex")
+    return out, st, err
+
+
 def lk_segments(frames, pts, segs, uv=None, rings=None, bad_parent=-1, want_pyr=False, w=None, h=None, stream=None):
     """Test hook vstabx_lk_segments (not part of include/vstab.h): the K + 1 (h, w) uint8 device luma views `frames` (pitched views
     allowed), n start points, launches of segs[s] frame pairs each (sum K), the first from pts and every later one chained behind the
@@ -1023,8 +1046,9 @@ class Stabilizer:
     source for `total` pulls) or a Python iterable of such tensors (python callback source)."""
 
     def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, calibration=None,
-                 calibration_ex=None, pinhole=None, detection_mask=None, corner_response=None, harris_k=0.04, **cfg_kw):
-        """corner_response: set_corner_response(corner_response, harris_k) right after create (CORNER_HARRIS or CORNER_MIN_EIGENVAL).
+                 calibration_ex=None, pinhole=None, detection_mask=None, corner_response=None, harris_k=0.04, tracker_options=None, **cfg_kw):
+        """tracker_options: (max_level, max_iter, eps, min_eig) for set_tracker_options right after create.
+        corner_response: set_corner_response(corner_response, harris_k) right after create (CORNER_HARRIS or CORNER_MIN_EIGENVAL).
         detection_mask: set_detection_mask right after create (a device tensor or a numpy array of the luma plane's size).
         border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
         calibration: (K, D) for set_input_calibration right after create, applied after border_mode (K None keeps the camera from in_dfov).
@@ -1101,6 +1125,13 @@ class Stabilizer:
             self.set_detection_mask(detection_mask)
         if corner_response is not None:
             self.set_corner_response(corner_response, harris_k)
+        if tracker_options is not None:
+            self.set_tracker_options(*tracker_options)
+
+    def set_tracker_options(self, max_level=3, max_iter=30, eps=0.01, min_eig=1e-4):
+        """vstab_set_tracker_options: calcOpticalFlowPyrLK's maxLevel, criteria and minEigThreshold for every tracker launch of this handle,
+        before the first pull; (3, 30, 0.01, 1e-4) is the handle as it always was."""
+        _check(_L.vstab_set_tracker_options(self._h, int(max_level), int(max_iter), float(eps), float(min_eig)), "vstab_set_tracker_options")
 
     def set_corner_response(self, response, k=0.04):
         """vstab_set_corner_response: CORNER_HARRIS with k (goodFeaturesToTrack's useHarrisDetector and k) for every detection of this

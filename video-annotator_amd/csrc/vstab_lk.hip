@@ -59,13 +59,21 @@ constexpr int LK_WPAD = (LKW * LKW + 63) & ~63;  // window pixels rounded up to 
 // rejected (minEig < 1e-4 or D < FLT_EPSILON), in the reference's float operation order.  Evaluated by whoever prepared the level --
 // for the lower levels a wave in the shadow of the top level's iterations -- so that the square root and the two divisions are not
 // on the iterating wave's dependent chain; the same instructions give the same bits wherever they run.
-__device__ __forceinline__ void lk_level_matrix(float s0, float s1, float s2, float *out) {
+// OPT (k_lk_track_opt; vstab.h, "Tracker options"): the threshold is the launch's (rule 4), and minEig itself leaves through the spare
+// slot 5 -- what VSTAB_LK_GET_MIN_EIGENVALS reports (rule 6), rejected or not.
+template <bool OPT>
+__device__ __forceinline__ void lk_level_matrix(const LkSegArgs &args, float s0, float s1, float s2, float *out) {
     const float FLT_SCALE = 1.0f / (1 << 20);
     const float A11 = s0 * FLT_SCALE, A12 = s1 * FLT_SCALE, A22 = s2 * FLT_SCALE;
     const float D = A11 * A22 - A12 * A12;
     const float minEig = ((A22 + A11) - sqrtf((A11 - A22) * (A11 - A22) + (4.f * A12) * A12)) / (float)(2 * LKW * LKW);
     out[0] = A11, out[1] = A12, out[2] = A22, out[3] = 1.f / D;
-    out[4] = minEig < 1e-4f || D < 1.1920928955078125e-7f ? 1.0f : 0.0f;
+    if constexpr (OPT) {
+        out[4] = minEig < args.min_eig || D < 1.1920928955078125e-7f ? 1.0f : 0.0f;
+        out[5] = minEig;
+    } else {
+        out[4] = minEig < 1e-4f || D < 1.1920928955078125e-7f ? 1.0f : 0.0f;
+    }
 }
 
 // Full-wave integer sums by DPP (row_shr 1, 2, 4, 8, then row_bcast 15 / 31); the totals are read from lane 63 and broadcast through
@@ -212,7 +220,7 @@ struct LkShared {
     uint32_t dpk[LK_MAX_LEVELS][LKT * LKT];       // Scharr derivative pairs of the 22 x 22 taps: dx | dy << 16 (int16 each)
     short patch_i[LK_MAX_LEVELS][LK_WPAD];        // the interpolated window of every level: I ...
     uint32_t patch_xy[LK_MAX_LEVELS][LK_WPAD];    // ... and Ix | Iy << 16 (int16 each), as the iterations hold them in registers
-    float level_mat[LK_MAX_LEVELS][8];            // A11, A12, A22, 1 / D of the level's 2 x 2 matrix and its rejection flag (lk_level_matrix)
+    float level_mat[LK_MAX_LEVELS][8];            // A11, A12, A22, 1 / D of the level's 2 x 2 matrix, its rejection flag and (k_lk_track_opt) minEig (lk_level_matrix)
     int s_pf[LK_MAX_LEVELS][4];                   // origins of the blocks fetched ahead: neighbourhood x, y, next-image block x, y (PF_NONE: no block)
     int s_top[LK_WAVES][6];                       // the waves' shares of the top level's matrix sums
     float s_est[2][2];                            // wave 0 -> all, by level parity: where the feature stands in the next image after that level
@@ -336,8 +344,17 @@ struct LkAhead {
 //   jorg_x, jorg_y  origin of the block in regJ[0], staged for the top level (PF_NONE: the top level is not tracked)
 //   own_dx, own_dy  waves 1 - 3: the neighbourhood of the level this wave prepares lies in pf.Io, at this offset (-1: it is in regI)
 // Returns what was served from the blocks fetched ahead (bit 0: the top neighbourhood, bit 1: the top next-image block; LK_STAMP 17).
-__device__ __forceinline__ int lk_stage_pair(LkShared &sh, const LkPyramid &I, const LkPyramid &J, float2 pp, int fi, int max_level, const LkThread &t, const LkAhead &pf,
-                                             int &jorg_x, int &jorg_y, int &own_dx, int &own_dy) {
+// OPT with VSTAB_LK_USE_INITIAL_FLOW: the top level's search starts at the caller's guess gp (level-0 pixels), so its next-image block
+// is staged around the guess.  A guess is any float.  The previous point passed the range test before anything of it became an address
+// (g.ok); the guess has to pass one too: lk_block_origin lets only a window corner in (-22, w) x (-22, h) through -- never a NaN or an
+// infinity, which fail every comparison, and never a value whose floor would leave int -- so the block's origin lies in [-27, w - 6] x
+// [-27, h - 6] and LkStage::load's REFLECT_101 folds every tap into the image (it folds any overshoot; here at most 27 pixels).  A
+// refused guess stages nothing and leaves PF_NONE: the first iteration refuses the same estimate with its own, narrower range test
+// ([-21, w) x [-21, h)) before it looks at the block, so an estimate it accepts always has its block; and were the origin PF_NONE all
+// the same, "window outside the block" holds for it and the loop stages afresh around the window it has just range-tested.
+template <bool OPT>
+__device__ __forceinline__ int lk_stage_pair(LkShared &sh, const LkSegArgs &args, const LkPyramid &I, const LkPyramid &J, float2 pp, float2 gp, int fi, int max_level,
+                                             const LkThread &t, const LkAhead &pf, int &jorg_x, int &jorg_y, int &own_dx, int &own_dy) {
     const int tid = t.tid, wave = t.wave;
     LkStage<LKR> si[LK_MAX_LEVELS];
     LkStage<LKJR> sj;
@@ -360,7 +377,16 @@ __device__ __forceinline__ int lk_stage_pair(LkShared &sh, const LkPyramid &I, c
             iok[l] = true;
             si[l].load(I.img[l], (uint32_t)I.pitch[l], I.w[l], I.h[l], g.ipx - 1, g.ipy - 1, tid);
         }
-        if (l == max_level) {  // the top level starts at the feature position itself
+        bool guessed = false;
+        if constexpr (OPT) guessed = (args.flags & VSTAB_LK_USE_INITIAL_FLOW) != 0;  // uniform
+        if (l == max_level && guessed) {  // the top level starts at the caller's guess (see above): range test, then the load
+            const float ls = lk_level_scale(l);
+            int ox = PF_NONE, oy = PF_NONE;
+            if (lk_block_origin(gp.x * ls - LK_HALF, gp.y * ls - LK_HALF, LKJM, I.w[l], I.h[l], false, ox, oy)) {
+                jorg_x = ox, jorg_y = oy;
+                sj.load(J.img[l], (uint32_t)J.pitch[l], I.w[l], I.h[l], jorg_x, jorg_y, tid);
+            }
+        } else if (l == max_level) {  // the top level starts at the feature position itself
             int bx = PF_NONE, by = PF_NONE;
             if (fi) bx = __builtin_amdgcn_readfirstlane(sh.s_pf[l][2]), by = __builtin_amdgcn_readfirstlane(sh.s_pf[l][3]);
             if (g.ipx - 2 >= bx && g.ipy - 2 >= by && g.ipx + LKT + 2 <= bx + LKJR && g.ipy + LKT + 2 <= by + LKJR) {
@@ -426,7 +452,8 @@ __device__ __forceinline__ void lk_level_window(LkShared &sh, int l, const LkLev
 // on it while waves 1 .. 3 prepare the lower levels, one level each, in its shadow (lk_prepare_lower_level) -- before,
 // every level was prepared up front, one wave per level, and the top level's iterations waited for all of them (3.8 of a
 // feature's ~19 us).  The sums are exact integers whatever the decomposition, so every float derived from them is unchanged.
-__device__ __forceinline__ void lk_prepare_top_level(LkShared &sh, const LkPyramid &I, float2 pp, int max_level, const LkThread &t) {
+template <bool OPT>
+__device__ __forceinline__ void lk_prepare_top_level(LkShared &sh, const LkSegArgs &args, const LkPyramid &I, float2 pp, int max_level, const LkThread &t) {
     const LkLevelGeom gt = lk_level_geom(pp, max_level, I.w[max_level], I.h[max_level]);
     const bool ok = max_level >= 0 && gt.ok;
     __syncthreads();  // the staged neighbourhoods are visible
@@ -448,7 +475,7 @@ __device__ __forceinline__ void lk_prepare_top_level(LkShared &sh, const LkPyram
             for (int wv = 0; wv < LK_WAVES; wv++) hi += sh.s_top[wv][2 * q], lo += sh.s_top[wv][2 * q + 1];
             sums[q] = lk_exact_total(hi, lo);
         }
-        lk_level_matrix(sums[0], sums[1], sums[2], sh.level_mat[max_level]);  // (read back by this wave only)
+        lk_level_matrix<OPT>(args, sums[0], sums[1], sums[2], sh.level_mat[max_level]);  // (read back by this wave only)
     }
 }
 
@@ -459,10 +486,12 @@ __device__ __forceinline__ void lk_prepare_top_level(LkShared &sh, const LkPyram
 // previous frame's position a frame-to-frame motion of more than LKJM pixels at that level (the 4K bench clip moves 4 - 12)
 // meant staging the block again inside the iteration loop, a global-memory latency on the dependent chain.  A window that leaves
 // its block is staged afresh by wave 0.  Loads only: the caller stores the block (sn, origin nx0, ny0) behind its other work.
-__device__ __forceinline__ void lk_fetch_finer_block(LkShared &sh, const LkPyramid &I, const LkPyramid &J, float2 pp, int level, int max_level, float lscale, int jb,
+// gp: where the top level's search started, in level-0 pixels -- the previous point pp or, k_lk_track_opt with VSTAB_LK_USE_INITIAL_FLOW, the
+// caller's guess (any float: lk_block_origin's range test stands before the load here too, see lk_stage_pair).
+__device__ __forceinline__ void lk_fetch_finer_block(LkShared &sh, const LkPyramid &I, const LkPyramid &J, float2 gp, int level, int max_level, float lscale, int jb,
                                                      const LkThread &t, LkStage<LKJR, LK_THREADS - 64> &sn, int &nx0, int &ny0) {
     const int w1 = I.w[level - 1], h1 = I.h[level - 1];
-    const float ex = level == max_level ? pp.x * lscale : sh.s_est[(level + 1) & 1][0] * 2.0f, ey = level == max_level ? pp.y * lscale : sh.s_est[(level + 1) & 1][1] * 2.0f;
+    const float ex = level == max_level ? gp.x * lscale : sh.s_est[(level + 1) & 1][0] * 2.0f, ey = level == max_level ? gp.y * lscale : sh.s_est[(level + 1) & 1][1] * 2.0f;
     if (lk_block_origin(ex * 2.0f - LK_HALF, ey * 2.0f - LK_HALF, LKJM, w1, h1, false, nx0, ny0))
         sn.load(J.img[level - 1], (uint32_t)J.pitch[level - 1], w1, h1, nx0, ny0, t.tid - 64);  // (else nx0, ny0 stay PF_NONE)
     if (t.tid == 64) sh.s_jorg[jb ^ 1][0] = nx0, sh.s_jorg[jb ^ 1][1] = ny0;
@@ -508,24 +537,27 @@ __device__ __forceinline__ void lk_fetch_ahead(LkShared &sh, const LkSegArgs &ar
 // In the shadow of the top level's iterations: this wave prepares level l on its own (a wave reads back only what it wrote
 // itself: LDS operations of one wave execute in order); published by that level's barrier.  The matrix is evaluated here too, so
 // that the square root and the two divisions are not on the iterating wave's dependent chain (lk_level_matrix).
-__device__ __forceinline__ void lk_prepare_lower_level(LkShared &sh, const LkPyramid &I, float2 pp, int l, int own_dx, int own_dy, const LkThread &t, const LkAhead &pf) {
+template <bool OPT>
+__device__ __forceinline__ void lk_prepare_lower_level(LkShared &sh, const LkSegArgs &args, const LkPyramid &I, float2 pp, int l, int own_dx, int own_dy, const LkThread &t,
+                                                       const LkAhead &pf) {
     const LkLevelGeom g = lk_level_geom(pp, l, I.w[l], I.h[l]);
     if (!g.ok) return;
     if (own_dx >= 0) pf.Io.store_window<LKR>(sh.regI[l], t.lane, own_dx, own_dy);  // fetched ahead by this wave
     lk_level_derivatives(sh, l, g, I.w[l], I.h[l], t.lane, 64);
     int s[6];
     lk_level_window(sh, l, g, t.lane, 64, s);
-    if (t.lane == 0) lk_level_matrix(lk_exact_total(s[0], s[1]), lk_exact_total(s[2], s[3]), lk_exact_total(s[4], s[5]), sh.level_mat[l]);
+    if (t.lane == 0) lk_level_matrix<OPT>(args, lk_exact_total(s[0], s[1]), lk_exact_total(s[2], s[3]), lk_exact_total(s[4], s[5]), sh.level_mat[l]);
 }
 // the helper waves' work of a level: the next finer level's block or, at level 0, the fetch-ahead for the next pair; in the top level's
 // shadow the lower levels' preparation, wave w level max_level - w
-__device__ __forceinline__ void lk_helper_level(LkShared &sh, const LkSegArgs &args, const LkPyramid &I, const LkPyramid &J, int fi, float2 pp, int level, int max_level,
-                                                float lscale, int jb, int own_dx, int own_dy, const LkThread &t, LkAhead &pf) {
+template <bool OPT>
+__device__ __forceinline__ void lk_helper_level(LkShared &sh, const LkSegArgs &args, const LkPyramid &I, const LkPyramid &J, int fi, float2 pp, float2 gp, int level,
+                                                int max_level, float lscale, int jb, int own_dx, int own_dy, const LkThread &t, LkAhead &pf) {
     LkStage<LKJR, LK_THREADS - 64> sn;
     int nx0 = PF_NONE, ny0 = PF_NONE;
-    if (level > 0) lk_fetch_finer_block(sh, I, J, pp, level, max_level, lscale, jb, t, sn, nx0, ny0);
+    if (level > 0) lk_fetch_finer_block(sh, I, J, gp, level, max_level, lscale, jb, t, sn, nx0, ny0);
     else lk_fetch_ahead(sh, args, I, J, fi, pp, max_level, t, pf);
-    if (level == max_level && t.wave <= max_level) lk_prepare_lower_level(sh, I, pp, max_level - t.wave, own_dx, own_dy, t, pf);
+    if (level == max_level && t.wave <= max_level) lk_prepare_lower_level<OPT>(sh, args, I, pp, max_level - t.wave, own_dx, own_dy, t, pf);
     // the finer level's block goes into the other buffer: nobody reads that one now (wave 0 left it before this level's
     // barrier); the next barrier publishes it
     if (nx0 != PF_NONE) sn.store(sh.regJ[jb ^ 1], t.tid - 64);
@@ -553,143 +585,28 @@ __device__ __forceinline__ void lk_publish_pair(LkShared &sh, const LkSegArgs &a
 // lasts as long as the slowest slot's SUM over the frames instead of the sum over the frames of each frame's slowest slot, and
 // the gap between launches is paid once per segment.  Results leave per frame pair (host_rec[i], dev_rec[i]) as soon as the
 // slot has them.  A slot that loses its feature reports status 0 for that pair and status 2 ("lost earlier") for the rest.
+//
+// ONE BODY, TWO KERNELS (vstab.h, "Tracker options").  k_lk_track is calcOpticalFlowPyrLK with default parameters and what every launch
+// without options runs; k_lk_track_opt reads the launch's options.  Every option is read under `if constexpr (OPT)`, so the default
+// instantiation is the kernel it was before the options existed: the same instructions (profiles/lk_options.txt).  launch_lk routes.
+// The body is ONE TEXT (vstab_lk_body.hpp) that stands in both kernels, not a __forceinline__ function template they call.  It was
+// written as one first: the compiler then simplifies the body once as a function of its own and a second time after inlining it into the
+// kernel, and what came out for OPT = false was a different k_lk_track (148 VGPRs against 150, 25 instructions fewer, another schedule) --
+// with the parent's statements word for word.  This kernel's schedule is what its time is made of (see the iteration loop's comment), so
+// "the same kernel" is kept as a property of the build, tools/asm_kernel_diff.py on the two listings, rather than measured again.  The
+// helpers above ARE function templates on OPT: they were functions before.
+#define VSTAB_LK_BODY_FROM_KERNEL
 __global__ void __launch_bounds__(LK_THREADS, 3) k_lk_track(LkSegArgs args) {
     __shared__ __attribute__((aligned(16))) LkShared sh;
-    const LkThread t = {(int)blockIdx.x, (int)threadIdx.x, (int)threadIdx.x & 63, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6)};
-    if (t.f >= args.n) return;
-    __builtin_amdgcn_s_setprio(VSTAB_LK_PRIO);  // with the warp, above the pyramid and detector kernels (vstab_warp_fused.hip: VSTAB_WARP_PRIO)
-    // development aid (VSTAB_LK_CLOCK): first workgroup start / last workgroup end on the 100 MHz wall clock
-    if (args.clk && t.tid == 0) atomicMin(&args.clk[0], wall_clock64());
-    unsigned int seq = args.seq[0];
-    LK_STAMP(0, LK_NOW());
-    float2 pp;
-    if (!lk_start_point(args, t, pp)) return;
-    int koff[LK_PPL];
-    lk_window_offsets(koff, t.lane);
-    LkAhead pf;
-#pragma unroll 1
-    for (int fi = 0; fi < args.n_frames; fi++) {
-        const LkPyramid &I = args.pyr[fi], &J = args.pyr[fi + 1];
-        seq = args.seq[fi];
-        if (fi) LK_STAMP(0, LK_NOW());
-        LK_STAMP(1, LK_NOW());
-        float2 np = make_float2(0.f, 0.f);
-        int st = 1;
-        const int max_level = I.levels - 1;
-        int jb = 0;                               // regJ[jb] holds the block staged for the level about to run
-        int jorg_x = PF_NONE, jorg_y = PF_NONE;   // its origin (none yet)
-        int own_dx = -1, own_dy = -1;
-        const int served = lk_stage_pair(sh, I, J, pp, fi, max_level, t, pf, jorg_x, jorg_y, own_dx, own_dy);
-        LK_STAMP(17, (unsigned long long)served);
-        (void)served;  // read by the development build's stamps only
-        LK_STAMP(2, LK_NOW());
-        LK_STAMP(16, (unsigned long long)fi);
-        lk_prepare_top_level(sh, I, pp, max_level, t);
-        for (int level = max_level; level >= 0; level--) {
-            int n_iter = 0;
-            const uint8_t *jmg = J.img[level];
-            const int w = I.w[level], h = I.h[level];
-            const uint32_t jpitch = (uint32_t)J.pitch[level];
-            const float lscale = lk_level_scale(level);
-            // the block staged for this level, wave 0's estimate after the level above and the level's window are visible (the top level:
-            // behind the last barrier of lk_prepare_top_level)
-            if (level != max_level) __syncthreads();
-            LK_STAMP(18 + 3 * (max_level - level), LK_NOW());
-            if (t.wave != 0) lk_helper_level(sh, args, I, J, fi, pp, level, max_level, lscale, jb, own_dx, own_dy, t, pf);
-            if (t.wave == 0 && level != max_level) jorg_x = sh.s_jorg[jb][0], jorg_y = sh.s_jorg[jb][1];  // (published by this level's barrier)
-            LK_STAMP(19 + 3 * (max_level - level), LK_NOW());
-            // ---- wave 0: the Gauss-Newton iterations of the level ("break" = the reference's "continue").  jorg_x, jorg_y: origin of the block
-            // staged for it in regJ[jb]; np: in, the estimate after the level above, out, after this level (a skipped level leaves it at its
-            // start value); st: cleared when level 0 loses the feature.  Left in the kernel body on purpose: as a function of its own the same
-            // statements were scheduled with every LDS read of the seven window pixels waiting for the one before it (14 round trips per
-            // iteration on the dependent chain instead of 5 waits; k_lk_track 129 us against 98 in the isolated 4K timing, profiles/track_split_4k.txt).
-            if (t.wave == 0) do {
-                float npx, npy;
-                if (level == max_level)
-                    npx = pp.x * lscale, npy = pp.y * lscale;
-                else
-                    npx = np.x * 2.0f, npy = np.y * 2.0f;
-                np = make_float2(npx, npy);
-                if (!lk_level_geom(pp, level, w, h).ok) {
-                    if (level == 0) st = 0;
-                    break;
-                }
-                int *rJ = sh.regJ[jb];
-                int jx0 = jorg_x, jy0 = jorg_y;  // origin of the next-image block staged for this level
-                int Iw[LK_PPL], Ixy[LK_PPL];     // this lane's pixels of the interpolated window: I, and Ix | Iy << 16
-#pragma unroll
-                for (int m = 0; m < LK_PPL; m++) {
-                    const int k = t.lane + 64 * m;
-                    const bool have = k < LKW * LKW;  // (the pad entries of the last row of lanes are never written)
-                    Iw[m] = have ? (int)sh.patch_i[level][k] : 0;
-                    Ixy[m] = have ? (int)sh.patch_xy[level][k] : 0;
-                }
-                const float FLT_SCALE = 1.0f / (1 << 20);
-                const float A11 = sh.level_mat[level][0], A12 = sh.level_mat[level][1], A22 = sh.level_mat[level][2], D = sh.level_mat[level][3];
-                if (sh.level_mat[level][4] != 0.0f) {  // minEig < 1e-4 || D < FLT_EPSILON
-                    if (level == 0) st = 0;
-                    break;
-                }
-                npx -= LK_HALF, npy -= LK_HALF;
-                float pdx = 0.f, pdy = 0.f;
-                LK_STAMP(3 + 3 * (max_level - level), LK_NOW());
-                for (int j = 0; j < 30; j++) {
-                    n_iter++;
-                    const int inx = (int)floorf(npx), iny = (int)floorf(npy);
-                    if (!lk_origin_in_range(npx, npy, w, h)) {
-                        if (level == 0) st = 0;
-                        break;
-                    }
-                    int iw00, iw01, iw10, iw11;
-                    lk_bilinear_weights(npx - (float)inx, npy - (float)iny, iw00, iw01, iw10, iw11);
-                    if (inx < jx0 || iny < jy0 || inx + LKT > jx0 + LKJR || iny + LKT > jy0 + LKJR) {
-                        // the window is outside the staged block: this wave stages a block centred on the window (wave-uniform branch;
-                        // LDS operations of one wave execute in order, and the other waves write the OTHER buffer)
-                        jx0 = inx - LKJM, jy0 = iny - LKJM;
-                        LkStage<LKJR, 64> sj;
-                        sj.load(jmg, jpitch, w, h, jx0, jy0, t.lane);
-                        sj.store(rJ, t.lane);
-                    }
-                    const int jbase = lk_mul(iny - jy0, LKJR) + (inx - jx0);
-                    int pb0 = 0, pb1 = 0;  // per-lane partial sums: 7 * 16320 * 4080 < 2^29
-#pragma unroll
-                    for (int m = 0; m < LK_PPL; m++) {
-                        const int *c = &rJ[jbase + koff[m]];
-                        const int diff = LK_DESCALE(lk_mul(c[0], iw00) + lk_mul(c[1], iw01) + lk_mul(c[LKJR], iw10) + lk_mul(c[LKJR + 1], iw11), 9) - Iw[m];
-                        pb0 += lk_mul(diff, (int)(short)(Ixy[m] & 0xffff)), pb1 += lk_mul(diff, Ixy[m] >> 16);
-                    }
-                    int s[4] = {pb0 >> 16, pb0 & 0xffff, pb1 >> 16, pb1 & 0xffff};  // (lk_exact_total)
-                    wave_sums_i32(s);  // uniform (SGPR) results
-                    const float b1 = lk_exact_total(s[0], s[1]) * FLT_SCALE, b2 = lk_exact_total(s[2], s[3]) * FLT_SCALE;
-                    const float dx = (A12 * b2 - A22 * b1) * D, dy = (A12 * b1 - A11 * b2) * D;
-                    npx += dx, npy += dy;
-                    np = make_float2(npx + LK_HALF, npy + LK_HALF);
-                    if ((double)dx * dx + (double)dy * dy <= 0.01 * 0.01) break;
-                    if (j > 0 && fabs((double)(dx + pdx)) < 0.01 && fabs((double)(dy + pdy)) < 0.01) {
-                        np.x -= dx * 0.5f, np.y -= dy * 0.5f;
-                        break;
-                    }
-                    pdx = dx, pdy = dy;
-                }
-                // OpenCV's LKTrackerInvoker, behind the loop (the reference passes `err`, FrameSourceWarp.cpp:250-259): at
-                // level 0 the final position -- the stored point minus the half window -- is tested against the image once
-                // more, and a feature whose last step (or half-step correction) carried its window out is dropped.
-                if (level == 0 && st) {
-                    if (!lk_origin_in_range(np.x - LK_HALF, np.y - LK_HALF, w, h)) st = 0;
-                }
-            } while (false);
-            if (t.tid == 0) sh.s_est[level & 1][0] = np.x, sh.s_est[level & 1][1] = np.y;  // (a skipped level leaves np at its start value, as the reference does)
-            LK_STAMP(4 + 3 * (max_level - level), LK_NOW());
-            LK_STAMP(5 + 3 * (max_level - level), (unsigned long long)n_iter);
-            (void)n_iter;  // read by the development build's stamps only
-            jb ^= 1;
-        }
-        lk_publish_pair(sh, args, fi, seq, t, np, st);
-        if (!st) return;  // uniform
-        pp = np;          // FrameSourceWarp.cpp:427
-        __syncthreads();  // the last readers of this pair's LDS state are through before the next pair's staging overwrites it
-    }
+    constexpr bool OPT = false;
+#include "vstab_lk_body.hpp"
 }
+__global__ void __launch_bounds__(LK_THREADS, 3) k_lk_track_opt(LkSegArgs args) {
+    __shared__ __attribute__((aligned(16))) LkShared sh;
+    constexpr bool OPT = true;
+#include "vstab_lk_body.hpp"
+}
+#undef VSTAB_LK_BODY_FROM_KERNEL
 
 vstab_status launch_lk(const LkSegArgs &a, hipStream_t s) {
     if (a.n <= 0 || a.n_frames <= 0) return VSTAB_OK;
@@ -702,7 +619,14 @@ vstab_status launch_lk(const LkSegArgs &a, hipStream_t s) {
             if (a.pyr[i].pitch[l] >= (1u << 24) || (uint64_t)a.pyr[i].pitch[l] * (uint64_t)a.pyr[i].h[l] >= (1ull << 32))
                 return fail(VSTAB_ERR_INVALID, "launch_lk: image pitch must be below 2^24 and planes below 4 GiB");
     }
-    hipLaunchKernelGGL(k_lk_track, dim3(a.n), dim3(LK_THREADS), 0, s, a);
+    if (a.max_iter < 1 || !(a.min_eig >= 0.0f) || !(a.eps2 >= 0.0)) return fail(VSTAB_ERR_INVALID, "launch_lk: the tracker's options are not set (lk_set_options)");
+    if ((a.flags & ~(VSTAB_LK_USE_INITIAL_FLOW | VSTAB_LK_GET_MIN_EIGENVALS)) || ((a.flags & VSTAB_LK_USE_INITIAL_FLOW) != 0) != (a.init_pts != nullptr) ||
+        ((a.flags & VSTAB_LK_GET_MIN_EIGENVALS) && !a.err))
+        return fail(VSTAB_ERR_INVALID, "launch_lk: flags, guesses and err do not agree");
+    if ((a.flags || a.err) && (a.n_frames != 1 || !a.prev_pts || a.chain_in))
+        return fail(VSTAB_ERR_INVALID, "launch_lk: the initial flow and err belong to a launch of one frame pair from host points");
+    if (lk_default_launch(a)) hipLaunchKernelGGL(k_lk_track, dim3(a.n), dim3(LK_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(k_lk_track_opt, dim3(a.n), dim3(LK_THREADS), 0, s, a);
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }

@@ -716,6 +716,19 @@ vstab_status vstab_set_corner_response(vstab_handle *h, int response, double k) 
     return VSTAB_OK;
 }
 
+// The handle's tracker options: read by every tracker launch of the handle, and the pyramids are capped to max_level + 1 levels
+// (Tracker::set_options).  Before the first pull no pyramid has been built and no launch is in flight.
+vstab_status vstab_set_tracker_options(vstab_handle *h, int max_level, int max_iter, double eps, double min_eig_threshold) {
+    const std::string n = "vstab_set_tracker_options: ";
+    if (!h) return fail(VSTAB_ERR_INVALID, n + "null handle");
+    if (!h->cfg.tracking) return fail(VSTAB_ERR_INVALID, n + "no tracker runs on this handle (tracking = 0)");
+    if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the options must be set before the first pull");
+    LkOptions opt;
+    VSTAB_TRY(check_lk_options("vstab_set_tracker_options", max_level, max_iter, eps, min_eig_threshold, opt));
+    h->tracker.set_options(opt);
+    return VSTAB_OK;
+}
+
 vstab_status vstab_set_input_calibration_ex(vstab_handle *h, const double K[9], const double D[4]) {
     return set_input_calibration(h, K, D, "vstab_set_input_calibration_ex", true);
 }

@@ -203,24 +203,47 @@ vstab_status vstab_good_features(const void *gray, size_t pitch, int width, int 
     return vstab_good_features_ex(gray, pitch, width, height, max_corners, quality, min_distance, VSTAB_DETECTOR_AUTO, xy, count, nullptr, stream);
 }
 
-vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height,
-                          const float *prev_xy, int n, float *next_xy, unsigned char *status, void *stream) {
+// vstab_pyr_lk and vstab_pyr_lk_ex (vstab.h, "Tracker options"): `ex` is whether the options, the flags and err are the caller's; without it
+// they are calcOpticalFlowPyrLK's defaults and the launches are the ones vstab_pyr_lk always made
+static vstab_status pyr_lk_op(const char *fn, bool ex, const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height,
+                              const float *prev_xy, int n, float *next_xy, unsigned char *status, float *err, int max_level, int max_iter, double eps,
+                              double min_eig_threshold, int flags, void *stream) {
     if (!prev || !next || (n > 0 && (!prev_xy || !next_xy || !status)) || n < 0 || width <= 0 || height <= 0 ||
         pitch_prev < (size_t)width || pitch_next < (size_t)width)
-        return fail(VSTAB_ERR_INVALID, "vstab_pyr_lk: bad argument");
+        return fail(VSTAB_ERR_INVALID, std::string(fn) + ": bad argument");
+    LkOptions opt;
+    if (ex) {
+        VSTAB_TRY(check_lk_options(fn, max_level, max_iter, eps, min_eig_threshold, opt));
+        if (flags & ~(VSTAB_LK_USE_INITIAL_FLOW | VSTAB_LK_GET_MIN_EIGENVALS)) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": unknown flag");
+        if ((flags & VSTAB_LK_GET_MIN_EIGENVALS) && !err) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": VSTAB_LK_GET_MIN_EIGENVALS needs err");
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     Tracker t;
-    VSTAB_TRY(t.init(width, height));
+    VSTAB_TRY(t.init(width, height, opt));
     VSTAB_TRY(t.build_pyramid(0, (const uint8_t *)prev, pitch_prev, st));
     VSTAB_TRY(t.build_pyramid(1, (const uint8_t *)next, pitch_next, st));
     std::vector<float> p(prev_xy, prev_xy + 2 * (size_t)n), q;
     std::vector<uint8_t> s;
-    VSTAB_TRY(t.track(t.pyramid(0, (const uint8_t *)prev, pitch_prev), t.pyramid(1, (const uint8_t *)next, pitch_next), p, q, s, st));
+    const LkPyramid I = t.pyramid(0, (const uint8_t *)prev, pitch_prev), J = t.pyramid(1, (const uint8_t *)next, pitch_next);
+    if (flags || err) VSTAB_TRY(t.track_ex(I, J, p, next_xy, flags, err, q, s, st));
+    else VSTAB_TRY(t.track(I, J, p, q, s, st));
     if (n > 0) {
         std::memcpy(next_xy, q.data(), sizeof(float) * q.size());
         std::memcpy(status, s.data(), s.size());
     }
     return VSTAB_OK;
+}
+
+vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height,
+                          const float *prev_xy, int n, float *next_xy, unsigned char *status, void *stream) {
+    return pyr_lk_op("vstab_pyr_lk", false, prev, pitch_prev, next, pitch_next, width, height, prev_xy, n, next_xy, status, nullptr, 0, 0, 0.0, 0.0, 0, stream);
+}
+
+vstab_status vstab_pyr_lk_ex(const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height, const float *prev_xy, int n,
+                             float *next_xy, unsigned char *status, float *err, int max_level, int max_iter, double eps, double min_eig_threshold, int flags,
+                             void *stream) {
+    return pyr_lk_op("vstab_pyr_lk_ex", true, prev, pitch_prev, next, pitch_next, width, height, prev_xy, n, next_xy, status, err, max_level, max_iter, eps,
+                     min_eig_threshold, flags, stream);
 }
 
 }  // extern "C"

@@ -95,6 +95,12 @@ vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h
 //   host_rec[i] / dev_rec[i] (either may be NULL): where pair i's n 16-byte records {x, seq[i], y, seq[i] << 2 | status} go --
 //             mapped host memory the host polls / device memory for the launch chained behind this one
 //   clk       development aid (VSTAB_LK_CLOCK): first-workgroup start / last-workgroup end stamps
+// The options (vstab.h, "Tracker options") come last, so that everything k_lk_track reads stays where it was:
+//   max_iter, min_eig, eps2   rules 3 and 4: the iteration cap, (float)min_eig_threshold and eps * eps in double
+//   flags     VSTAB_LK_USE_INITIAL_FLOW: init_pts holds the n guesses (device-readable); VSTAB_LK_GET_MIN_EIGENVALS: what err reports
+//   err       n floats (device-writable), or NULL; written with plain stores: read it behind a synchronisation of the stream
+// launch_lk takes k_lk_track exactly when lk_default_launch(args), else k_lk_track_opt; flags, init_pts and err belong to a launch of ONE
+// pair from host points (prev_pts) and are refused elsewhere.
 constexpr int LK_SEG_MAX = 8;
 struct LkSegArgs {
     LkPyramid pyr[LK_SEG_MAX + 1];
@@ -106,7 +112,23 @@ struct LkSegArgs {
     const uint4 *chain_in;
     unsigned int parent_seq;
     unsigned long long *clk;
+    int max_iter;
+    float min_eig;
+    double eps2;
+    int flags;
+    const float2 *init_pts;
+    float *err;
 };
+// The tracker's options as an entry point takes them, checked by check_lk_options (vstab_track_host.hpp); the defaults are
+// calcOpticalFlowPyrLK's.  max_level caps the pyramid (Tracker::init) and never reaches the kernel.
+struct LkOptions {
+    int max_level = LK_MAX_LEVELS - 1, max_iter = 30;
+    double eps = 0.01, min_eig = 1e-4;
+};
+inline void lk_set_options(LkSegArgs &a, const LkOptions &o) { a.max_iter = o.max_iter, a.min_eig = (float)o.min_eig, a.eps2 = o.eps * o.eps; }
+inline bool lk_default_launch(const LkSegArgs &a) {
+    return a.max_iter == 30 && a.min_eig == 1e-4f && a.eps2 == 0.01 * 0.01 && a.flags == 0 && !a.init_pts && !a.err;
+}
 vstab_status launch_lk(const LkSegArgs &args, hipStream_t s);
 
 }  // namespace vstab

@@ -2,7 +2,9 @@
 // Host C++; the kernels are those of vstab_pyramid.hip and vstab_lk.hip.  (The corner detector is vstab_detect_host.cpp.)
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
+#include <string>
 
 #include "vstab_hostlogic.hpp"
 #include "vstab_track_host.hpp"
@@ -14,8 +16,19 @@ Tracker::~Tracker() {
         if (e) (void)hipEventDestroy(e);
 }
 
-vstab_status Tracker::init(int w, int h) {
-    w_ = w, h_ = h, levels_ = lk_levels(w, h);
+vstab_status check_lk_options(const char *fn, int max_level, int max_iter, double eps, double min_eig_threshold, LkOptions &out) {
+    const std::string n = std::string(fn) + ": ";
+    if (max_level < 0 || max_level > LK_MAX_LEVELS - 1) return fail(VSTAB_ERR_INVALID, n + "max_level lies in 0 .. 3");
+    if (max_iter < 1 || max_iter > 100) return fail(VSTAB_ERR_INVALID, n + "max_iter lies in 1 .. 100");
+    if (!(eps >= 0.0 && eps <= 10.0)) return fail(VSTAB_ERR_INVALID, n + "eps is finite and lies in [0, 10]");
+    if (!(min_eig_threshold >= 0.0) || !std::isfinite(min_eig_threshold)) return fail(VSTAB_ERR_INVALID, n + "min_eig_threshold is finite and not negative");
+    out.max_level = max_level, out.max_iter = max_iter, out.eps = eps, out.min_eig = min_eig_threshold;
+    return VSTAB_OK;
+}
+
+vstab_status Tracker::init(int w, int h, const LkOptions &opt) {
+    w_ = w, h_ = h;
+    set_options(opt);
     int lw = w, lh = h;
     for (int l = 1; l < levels_; l++) {
         lw = (lw + 1) / 2, lh = (lh + 1) / 2;
@@ -92,6 +105,33 @@ vstab_status Tracker::track_wait(const Launch &L, int idx, size_t expect_n, std:
     return VSTAB_OK;
 }
 
+vstab_status Tracker::track_ex(const LkPyramid &I, const LkPyramid &J, const std::vector<float> &prev_xy, const float *guess_xy, int flags, float *err,
+                               std::vector<float> &next_xy, std::vector<uint8_t> &status, hipStream_t st) {
+    const size_t n = prev_xy.size() / 2;
+    next_xy.clear(), status.clear();
+    if (n == 0) return VSTAB_OK;
+    const float2 *guess = nullptr;
+    if (flags & VSTAB_LK_USE_INITIAL_FLOW) {
+        VSTAB_TRY(guess_.ensure(n * sizeof(float2)));
+        VSTAB_HIP_TRY(hipMemcpy(guess_.p, guess_xy, n * sizeof(float2), hipMemcpyHostToDevice));  // complete before the launch below is enqueued
+        guess = guess_.as<float2>();
+    }
+    if (err) VSTAB_TRY(err_.ensure(n * sizeof(float)));
+    Launch L;
+    const LkPyramid pyr[2] = {I, J};
+    ex_flags_ = flags, ex_guess_ = guess, ex_err_ = err ? err_.as<float>() : nullptr;
+    const vstab_status launched = track_launch(pyr, 1, prev_xy, st, false, L);
+    ex_flags_ = 0, ex_guess_ = nullptr, ex_err_ = nullptr;
+    VSTAB_TRY(launched);
+    VSTAB_TRY(track_wait(L, 0, n, next_xy, status, st, nullptr));
+    if (err) {
+        // err leaves the kernel by plain stores behind the records: complete once the stream is
+        VSTAB_HIP_TRY(hipStreamSynchronize(st));
+        VSTAB_HIP_TRY(hipMemcpy(err, err_.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return VSTAB_OK;
+}
+
 void *Tracker::clock_slot() {
     static const bool on = getenv("VSTAB_LK_CLOCK") != nullptr;
     if (!on) return nullptr;
@@ -146,6 +186,8 @@ vstab_status Tracker::launch_segment(const LkPyramid *pyr, int n_frames, const f
     }
     a.n_frames = n_frames, a.n = L.n_slots;
     a.prev_pts = prev_pts, a.chain_in = static_cast<const uint4 *>(chain_in), a.parent_seq = parent_seq;
+    lk_set_options(a, opt_);
+    a.flags = ex_flags_, a.init_pts = ex_guess_, a.err = ex_err_;  // (track_ex only; launch_lk refuses them on a segment or a chained launch)
     a.clk = static_cast<unsigned long long *>(clock_slot());
     if (L.timed && !ev_a_) (void)hipEventCreate(&ev_a_), (void)hipEventCreate(&ev_b_);
     if (L.timed) (void)hipEventRecord(ev_a_, st);

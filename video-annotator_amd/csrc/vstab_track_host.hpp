@@ -1,6 +1,7 @@
 // vstab_track_host.hpp -- class Tracker, the host side of the LK tracker (defined in vstab_track_host.cpp): used by the pipeline object, the
 // stateless vstab_pyr_lk and the vstabx_lk_segments hook.  The corner detector beside it is class Detector (vstab_detect_host.hpp).
 #pragma once
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -21,6 +22,11 @@ constexpr int PYR_DEV_EXTRA = 1;  // a set nobody reads: VSTAB_DEV_PYR_TWICE=1 b
 constexpr int PYR_DEV_EXTRA = 0;
 #endif
 
+// The tracker's options as vstab_pyr_lk_ex and vstab_set_tracker_options take them (vstab.h, "Tracker options"): refused with
+// "<fn>: max_level lies in 0 .. 3", "<fn>: max_iter lies in 1 .. 100", "<fn>: eps is finite and lies in [0, 10]" and
+// "<fn>: min_eig_threshold is finite and not negative", in this order (a NaN fails every comparison).
+vstab_status check_lk_options(const char *fn, int max_level, int max_iter, double eps, double min_eig_threshold, LkOptions &out);
+
 class Tracker {
   public:
     // One record buffer per tracked frame pair, in rotation: a launch covers up to LK_SEG_MAX pairs and launches run up to
@@ -28,7 +34,13 @@ class Tracker {
     // (and after any launch whose results were dropped has finished: it precedes its replacement on the tracker stream).
     static constexpr int REC_BUFS = 32, PTS_BUFS = 8;
     ~Tracker();
-    vstab_status init(int w, int h);
+    vstab_status init(int w, int h, const LkOptions &opt = LkOptions());
+    // the options of every launch from here on; the pyramids get min(lk_levels(w, h), max_level + 1) levels, so fewer levels are fewer
+    // pyramid launches.  Only while nothing is in flight (before the first launch).
+    void set_options(const LkOptions &opt) {
+        opt_ = opt;
+        levels_ = std::min(lk_levels(w_, h_), opt.max_level + 1);
+    }
     // levels 1.. of the pyramid of `gray` into slot s (level 0 is the frame itself)
     // `done` (optional) completes with the LAST kernel of the pyramid, bound to that launch (launch_pyr_down); *done_bound says whether a kernel
     // took it (an image too small for a second level has no pyramid kernel: the caller records the event itself)
@@ -92,6 +104,11 @@ class Tracker {
         return track_wait(L, 0, prev_xy.size() / 2, next_xy, status, st, gpu_ms);
     }
 
+    // One pair from host points with the stateless-only arguments (vstab.h, "Tracker options", rules 2, 5 and 6): guess_xy, n host pairs
+    // read iff flags has VSTAB_LK_USE_INITIAL_FLOW; err, n host floats or NULL, filled behind a synchronisation of the stream.
+    vstab_status track_ex(const LkPyramid &I, const LkPyramid &J, const std::vector<float> &prev_xy, const float *guess_xy, int flags, float *err,
+                          std::vector<float> &next_xy, std::vector<uint8_t> &status, hipStream_t st);
+
     int levels() const { return levels_; }
     int level_w(int l) const { return lvl_w_[l]; }
     int level_h(int l) const { return lvl_h_[l]; }
@@ -118,6 +135,11 @@ class Tracker {
   private:
     vstab_status launch_segment(const LkPyramid *pyr, int n_frames, const float2 *prev_pts, const void *chain_in, uint32_t parent_seq, hipStream_t st, Launch &L);
     int w_ = 0, h_ = 0, levels_ = 1;
+    LkOptions opt_;
+    DevBuf guess_, err_;  // track_ex: the guesses and the error measures of its one launch ...
+    int ex_flags_ = 0;    // ... and what launch_segment hands to that launch (zero for every other launch)
+    const float2 *ex_guess_ = nullptr;
+    float *ex_err_ = nullptr;
     int lvl_w_[LK_MAX_LEVELS] = {0}, lvl_h_[LK_MAX_LEVELS] = {0};
     DevBuf pyr_[PYR_SETS + PYR_DEV_EXTRA][LK_MAX_LEVELS];  // pyramid sets: previous, current, prefetched x2
     const bool single_level_pyramid_ = getenv("VSTAB_PYR_SINGLE") != nullptr;  // development: one launch per pyramid level
