@@ -219,6 +219,11 @@ _L.vstabx_select_corners.restype = _i
 _L.vstabx_select_corners.argtypes = [_c.POINTER(_u64), _c.c_uint, _i, _i, _i, _d, _fp, _ip]
 _L.vstabx_detector_counters.restype = _i
 _L.vstabx_detector_counters.argtypes = [_vp, _c.POINTER(_c.c_long)]
+# test hooks of the pyramid (pack_pyr below; tests/test_pyr_paths_cpu.py calls vstabx_pyr_down_check through lib)
+for _f in (_L.vstabx_pack_pyr, _L.vstabx_launch_pack_pyr):
+    _f.restype, _f.argtypes = _i, [_vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _sz, _vp]
+_L.vstabx_pyr_down_check.restype = _i
+_L.vstabx_pyr_down_check.argtypes = [_sz, _i, _i, _sz, _sz, _i]
 
 lib = _L
 ABI_VERSION = 0x56534206  # include/vstab.h: VSTAB_ABI_VERSION ("VSB" + layout version 6)
@@ -741,23 +746,48 @@ def warp_nv12_mapped(nv12, qmap, dw, dh, out_format=OUT_BGR8, out=None):
     return _warp_nv12(_L.vstab_warp_nv12_mapped, nv12, dw, dh, out_format, out, (qmap.data_ptr(),))
 
 
-def pyr_down(img):
+def _caller_plane(out, rows, cols, device, what):
+    """A plane the caller laid out for an operator to write: 2-D uint8 of (rows, cols) on `device`, unit column stride, any row stride >= cols."""
+    import torch
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 2 or tuple(out.shape) != (rows, cols) or out.device != device
+            or out.stride(1) != 1 or out.stride(0) < cols):
+        raise ValueError(f"{what}: out must be a ({rows}, {cols}) uint8 tensor on {device} with stride(1) == 1 and stride(0) >= {cols}")
+    return out
+
+
+def pyr_down(img, out=None):
+    """vstab_pyr_down -> the level, in a fresh dense tensor or in `out` (a caller's plane, _caller_plane)."""
     import torch
     h, w = img.shape
-    out = torch.empty(((h + 1) // 2, (w + 1) // 2), dtype=torch.uint8, device=img.device)
+    dh, dw = (h + 1) // 2, (w + 1) // 2
+    out = torch.empty((dh, dw), dtype=torch.uint8, device=img.device) if out is None else _caller_plane(out, dh, dw, img.device, "pyr_down")
     _check(_L.vstab_pyr_down(img.data_ptr(), img.stride(0), w, h, out.data_ptr(), out.stride(0), _stream()), "vstab_pyr_down")
     return out
 
 
-def pyr_down_x2(img):
-    """vstab_pyr_down_x2: two pyramid levels in one launch -> (mid, dst)."""
+def pyr_down_x2(img, out=None):
+    """vstab_pyr_down_x2: two pyramid levels in one launch -> (mid, dst), fresh dense tensors or out = (mid, dst) (caller's planes, _caller_plane)."""
     import torch
     h, w = img.shape
     mw, mh = (w + 1) // 2, (h + 1) // 2
-    mid = torch.empty((mh, mw), dtype=torch.uint8, device=img.device)
-    dst = torch.empty(((mh + 1) // 2, (mw + 1) // 2), dtype=torch.uint8, device=img.device)
+    dw, dh = (mw + 1) // 2, (mh + 1) // 2
+    if out is None:
+        mid = torch.empty((mh, mw), dtype=torch.uint8, device=img.device)
+        dst = torch.empty((dh, dw), dtype=torch.uint8, device=img.device)
+    else:
+        mid, dst = out
+        _caller_plane(mid, mh, mw, img.device, "pyr_down_x2 (mid)"), _caller_plane(dst, dh, dw, img.device, "pyr_down_x2 (dst)")
     _check(_L.vstab_pyr_down_x2(img.data_ptr(), img.stride(0), w, h, mid.data_ptr(), mid.stride(0), dst.data_ptr(), dst.stride(0), _stream()), "vstab_pyr_down_x2")
     return mid, dst
+
+
+def pack_pyr(y, pitch_y, uv, pitch_uv, w, h, ring, dst, dpitch, launch_anyway=False, stream=None):
+    """Test hook vstabx_pack_pyr (not part of include/vstab.h): k_pack_pyr alone on raw device addresses -- the NV12 frame (y, uv) copied into
+    `ring` (w * h * 3 / 2 bytes) and pyrDown of its luma written to dst (pitch dpitch).  -> -1 where pack_pyr_ok refuses the planes (nothing is
+    launched), else the status of launch_pack_pyr.  launch_anyway: vstabx_launch_pack_pyr, the launcher without the question -- its own refusal.
+    Addresses are taken as given, so the refusals can be asked for without a device."""
+    fn = _L.vstabx_launch_pack_pyr if launch_anyway else _L.vstabx_pack_pyr
+    return fn(y, pitch_y, uv, pitch_uv, int(w), int(h), ring, dst, dpitch, _stream() if stream is None else stream)
 
 
 def min_eig(gray):

@@ -119,7 +119,7 @@ template <bool EDGE, bool NEAR, bool COPY = false>
 __device__ __forceinline__ void pyr_down_group(const uint8_t *__restrict__ src, uint32_t spitch, int sw, int sh, uint8_t *__restrict__ dst, size_t dpitch,
                                                int dw, int x0, int y, bool vec_ok, uint8_t *__restrict__ cp = nullptr, uint32_t cpitch = 0) {
     const uint32_t out = pyr_down_group4<EDGE, NEAR, COPY>(src, spitch, sw, sh, x0, y, vec_ok, cp, cpitch);
-    uint8_t *o = dst + (size_t)((uint32_t)y * (uint32_t)dpitch) + x0;  // one 32-bit multiply (images are at most 32767 x 32767 bytes)
+    uint8_t *o = dst + (size_t)((uint32_t)y * (uint32_t)dpitch) + x0;  // one 32-bit multiply (the launchers refuse dpitch * dh >= 2^32)
     if (!EDGE) {
         *reinterpret_cast<uint32_t *>(o) = out;
     } else {
@@ -323,12 +323,16 @@ static PyrGrid pyr_grid(int sw, int dw, int dh, bool wide) {
 // `done` (optional): an event that completes with this kernel -- bound to the launch itself (hipExtLaunchKernelGGL's stop event), so that the
 // stream carries no marker packet of its own behind the kernel: a hipEventRecord after every frame's pyramid cost the prefetch stream ~6 us
 // per frame (rocprofv3 kernel trace: the next frame's first kernel started 6.5 us after this frame's last one ended, 0.0 us between two kernels)
+vstab_status check_pyr_down(size_t spitch, int /*sw*/, int sh, size_t dpitch) {
+    // the kernel forms row offsets as 32-bit products
+    if ((uint64_t)spitch * (uint64_t)sh >= (1ull << 32) || (uint64_t)dpitch * (uint64_t)((sh + 1) / 2) >= (1ull << 32))
+        return fail(VSTAB_ERR_INVALID, "pyr_down: planes of 4 GiB or more are not supported");
+    return VSTAB_OK;
+}
 vstab_status launch_pyr_down(const uint8_t *src, size_t spitch, int sw, int sh, uint8_t *dst, size_t dpitch,
                              hipStream_t s, hipEvent_t done) {
     const int dw = (sw + 1) / 2, dh = (sh + 1) / 2;
-    // the kernel forms row offsets as 32-bit products
-    if ((uint64_t)spitch * (uint64_t)sh >= (1ull << 32) || (uint64_t)dpitch * (uint64_t)dh >= (1ull << 32))
-        return fail(VSTAB_ERR_INVALID, "pyr_down: planes of 4 GiB or more are not supported");
+    VSTAB_TRY(check_pyr_down(spitch, sw, sh, dpitch));
     const int vec_ok = reinterpret_cast<uintptr_t>(src) % 4 == 0 && spitch % 4 == 0 && reinterpret_cast<uintptr_t>(dst) % 4 == 0 && dpitch % 4 == 0;
     const int near = sw >= 16 && sh >= 4;
     const PyrGrid g = pyr_grid(sw, dw, dh, vec_ok && near);
@@ -344,6 +348,7 @@ bool pack_pyr_ok(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv,
     return w >= 16 && h >= 4 && !(w & 7) && !(h & 1) && reinterpret_cast<uintptr_t>(y) % 4 == 0 && pitch_y % 4 == 0 && reinterpret_cast<uintptr_t>(ring) % 8 == 0 &&
            reinterpret_cast<uintptr_t>(dst) % 4 == 0 && dpitch % 4 == 0 && pitch_y < (1u << 24) && pitch_uv < (1u << 24) && (uint64_t)pitch_y * (uint64_t)h < (1ull << 32) &&
            (uint64_t)pitch_uv * (uint64_t)(h / 2) < (1ull << 32) &&  // (k_pack_pyr forms row * pitch_uv in 32 bits)
+           (uint64_t)dpitch * (uint64_t)((h + 1) / 2) < (1ull << 32) &&  // (and row * dpitch, as k_pyr_down does)
            (uint64_t)w * (uint64_t)h * 3 / 2 < (1ull << 32);
 }
 vstab_status launch_pack_pyr(const uint8_t *y, size_t pitch_y, const uint8_t *uv, size_t pitch_uv, int sw, int sh, uint8_t *ring, uint8_t *dst, size_t dpitch,
@@ -362,12 +367,17 @@ vstab_status launch_pack_pyr(const uint8_t *y, size_t pitch_y, const uint8_t *uv
 // Two levels in one launch (k_pyr_down_x2): mid = pyrDown(src), dst = pyrDown(mid).  Needs an image a reflected tap never leaves
 // twice (>= 4 x 4 at the middle level); the caller falls back to two single-level launches otherwise.
 bool pyr_down_x2_ok(int sw, int sh) { return (sw + 1) / 2 >= 8 && (sh + 1) / 2 >= 8; }
-vstab_status launch_pyr_down_x2(const uint8_t *src, size_t spitch, int sw, int sh, uint8_t *mid, size_t mpitch, uint8_t *dst, size_t dpitch, hipStream_t s,
-                                hipEvent_t done) {
-    const int mw = (sw + 1) / 2, mh = (sh + 1) / 2, dw = (mw + 1) / 2, dh = (mh + 1) / 2;
+vstab_status check_pyr_down_x2(size_t spitch, int sw, int sh, size_t mpitch, size_t dpitch) {
+    const int mh = (sh + 1) / 2, dh = (mh + 1) / 2;
     if (!pyr_down_x2_ok(sw, sh)) return fail(VSTAB_ERR_INVALID, "pyr_down_x2: image too small");
     if ((uint64_t)spitch * (uint64_t)sh >= (1ull << 32) || (uint64_t)mpitch * (uint64_t)mh >= (1ull << 32) || (uint64_t)dpitch * (uint64_t)dh >= (1ull << 32))
         return fail(VSTAB_ERR_INVALID, "pyr_down_x2: planes of 4 GiB or more are not supported");
+    return VSTAB_OK;
+}
+vstab_status launch_pyr_down_x2(const uint8_t *src, size_t spitch, int sw, int sh, uint8_t *mid, size_t mpitch, uint8_t *dst, size_t dpitch, hipStream_t s,
+                                hipEvent_t done) {
+    const int mw = (sw + 1) / 2, mh = (sh + 1) / 2, dw = (mw + 1) / 2, dh = (mh + 1) / 2;
+    VSTAB_TRY(check_pyr_down_x2(spitch, sw, sh, mpitch, dpitch));
     const int vec_ok = reinterpret_cast<uintptr_t>(src) % 4 == 0 && spitch % 4 == 0 && reinterpret_cast<uintptr_t>(mid) % 4 == 0 && mpitch % 4 == 0;
     const int dst_vec_ok = reinterpret_cast<uintptr_t>(dst) % 4 == 0 && dpitch % 4 == 0;
     const int near = sw >= 16 && sh >= 4;

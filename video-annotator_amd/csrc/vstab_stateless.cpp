@@ -129,6 +129,9 @@ vstab_status vstab_pyr_down_x2(const void *src, size_t pitch_src, int width, int
     if (!src || !mid || !dst || width <= 0 || height <= 0 || pitch_src < (size_t)width || pitch_mid < (size_t)mw || pitch_dst < (size_t)((mw + 1) / 2))
         return fail(VSTAB_ERR_INVALID, "vstab_pyr_down_x2: bad argument");
     if (!pyr_down_x2_ok(width, height)) {  // tiny images: two single-level launches, the same bytes
+        // (both launches' planes are looked at before the first kernel runs: a call that is refused writes nothing)
+        VSTAB_TRY(check_pyr_down(pitch_src, width, height, pitch_mid));
+        VSTAB_TRY(check_pyr_down(pitch_mid, mw, mh, pitch_dst));
         VSTAB_TRY(launch_pyr_down((const uint8_t *)src, pitch_src, width, height, (uint8_t *)mid, pitch_mid, static_cast<hipStream_t>(stream)));
         return launch_pyr_down((const uint8_t *)mid, pitch_mid, mw, mh, (uint8_t *)dst, pitch_dst, static_cast<hipStream_t>(stream));
     }

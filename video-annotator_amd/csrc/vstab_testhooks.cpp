@@ -308,4 +308,26 @@ __attribute__((visibility("default"))) int vstabx_detector_counters(const vstab_
     out[0] = h->detector.spec_over_cap(), out[1] = h->detector.fused_overflows(), out[2] = (long)h->detector.key_capacity();
     return VSTAB_OK;
 }
+
+// k_pack_pyr ALONE, on planes the caller lays out (tests/test_pyr_paths_gpu.py, tests/pyr_paths.py): the copy of the NV12 frame (y, uv) into `ring`
+// (w * h * 3 / 2 bytes, rows of pitch w) and pyrDown of its luma into dst (pitch dpitch) by launch_pack_pyr, as the pipeline's ingest of a frame upstream
+// recycles does.  Returns -1 where pack_pyr_ok says no (nothing is launched: the pipeline takes its two-kernel path there), else the status of
+// launch_pack_pyr.  No launch logic of its own.
+__attribute__((visibility("default"))) int vstabx_pack_pyr(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int w, int h, void *ring, void *dst,
+                                                            size_t dpitch, void *stream) {
+    if (!pack_pyr_ok(y, pitch_y, uv, pitch_uv, w, h, ring, dst, dpitch)) return -1;
+    return launch_pack_pyr(static_cast<const uint8_t *>(y), pitch_y, static_cast<const uint8_t *>(uv), pitch_uv, w, h, static_cast<uint8_t *>(ring),
+                           static_cast<uint8_t *>(dst), dpitch, static_cast<hipStream_t>(stream));
+}
+// launch_pack_pyr as it stands, for its own refusal: planes pack_pyr_ok refuses are VSTAB_ERR_INVALID before anything touches the device.
+__attribute__((visibility("default"))) int vstabx_launch_pack_pyr(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int w, int h, void *ring, void *dst,
+                                                                   size_t dpitch, void *stream) {
+    return launch_pack_pyr(static_cast<const uint8_t *>(y), pitch_y, static_cast<const uint8_t *>(uv), pitch_uv, w, h, static_cast<uint8_t *>(ring),
+                           static_cast<uint8_t *>(dst), dpitch, static_cast<hipStream_t>(stream));
+}
+// What launch_pyr_down (two_levels = 0; pitch_mid is not looked at) or launch_pyr_down_x2 refuses for planes of these pitches, without a launch and
+// without a device (tests/test_pyr_paths_cpu.py): VSTAB_OK, or the launcher's status with its message in vstab_last_error.
+__attribute__((visibility("default"))) int vstabx_pyr_down_check(size_t pitch_src, int w, int h, size_t pitch_mid, size_t pitch_dst, int two_levels) {
+    return two_levels ? check_pyr_down_x2(pitch_src, w, h, pitch_mid, pitch_dst) : check_pyr_down(pitch_src, w, h, pitch_dst);
+}
 }  // extern "C"

@@ -30,6 +30,9 @@ inline int lk_levels(int w, int h) {
 
 // done (optional): an event that completes with the kernel, bound to the launch itself (no marker packet of its own on the stream)
 vstab_status launch_pyr_down(const uint8_t *src, size_t spitch, int sw, int sh, uint8_t *dst, size_t dpitch, hipStream_t s, hipEvent_t done = nullptr);
+// what launch_pyr_down / launch_pyr_down_x2 refuse, without the launch: VSTAB_OK, or the launcher's own status and message
+vstab_status check_pyr_down(size_t spitch, int sw, int sh, size_t dpitch);
+vstab_status check_pyr_down_x2(size_t spitch, int sw, int sh, size_t mpitch, size_t dpitch);
 // the copy of an NV12 frame into the ring (what vstab_pack_nv12 writes: luma rows of pitch w, chroma rows behind them) and the first pyramid
 // level of its luma in one launch; `copied` (optional) completes with it
 bool pack_pyr_ok(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int w, int h, const void *ring, const void *dst, size_t dpitch);
