@@ -20,6 +20,8 @@ namespace vstab {
 // dword of row j holds k_j * (1 4 6 4 1) at the byte positions of the taps (<= 36, a byte), two
 // dot products per output and row, so no byte is ever unpacked.  One dword store.  No LDS, no
 // barriers: the kernel is a pure stream and overlaps with the LK kernel of the previous frame.
+// (That is the one-row body: the edge groups, k_pack_pyr and k_pyr_down_x2.  The interior workgroups of k_pyr_down
+// run pyr_down_rows below: PYR_ROWS output rows a thread, every source row loaded and summed horizontally once.)
 // =============================================================================================
 __device__ __forceinline__ uint32_t udot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
 
@@ -127,16 +129,77 @@ __device__ __forceinline__ void pyr_down_group(const uint8_t *__restrict__ src, 
     }
 }
 
-// Groups of 4 outputs [g_lo, g_hi) of every row are interior (64 groups x 4 rows per workgroup); the remaining groups --
+// The interior body of k_pyr_down: one thread produces outputs 4g .. 4g+3 of the R rows y0 .. y0+R-1 from 2R + 3 source rows, each loaded
+// once (16 bytes at 8g - 4) and summed horizontally once.  The filter is separable and everything is an integer, so the order is free:
+//   horizontal, per source row: h_c = (1 4 6 4 1) . bytes 2c+2 .. 2c+6, two dot products per output against the unscaled weights
+//     (h <= 16 * 255 = 4080), and the four sums paired into 16-bit halves of two dwords (h0 | h1 << 16, h2 | h3 << 16);
+//   vertical, per output row and pair: h[0] + h[4] + 4 (h[1] + h[2] + h[3]) + 2 h[2] + 128 in plain 32-bit adds on the pairs -- the
+//     largest half is 255 * 256 + 128 = 65408 < 2^16, so nothing carries from the low half into the high one;
+//   the result bytes are bits 8 .. 15 of the four halves: one v_perm, one dword store per row.
+// A wave is 64 groups of ONE row group (y0 is made a scalar), so the row addresses, REFLECT_101 of the row index at the top and bottom
+// of the image, and the test that drops the rows past dh of the last row group are scalar instructions; a load's address is the thread's
+// column address plus a scalar row offset (one 64-bit add).  A row index still negative after the fold -- only dropped rows tap it --
+// is clamped to row 0: read, never used.
+// All 2R + 3 loads are issued before the first dependent instruction: one memory latency per thread, as before.
+template <int R>
+__device__ __forceinline__ void pyr_down_rows(const uint8_t *__restrict__ src, uint32_t spitch, int sh, uint8_t *__restrict__ dst, uint32_t dpitch, int dh, int g,
+                                              int y0) {
+    constexpr int NS = 2 * R + 3;
+    const uint32_t sx0 = 8u * (uint32_t)g - 4u;  // (g >= 1)
+    uint4 v[NS];
+#pragma unroll
+    for (int j = 0; j < NS; j++) {
+        const int a = abs(2 * y0 - 2 + j), ry = max(min(a, 2 * sh - 2 - a), 0);
+        v[j] = *reinterpret_cast<const uint4 *>(src + (size_t)((uint32_t)ry * spitch) + sx0);  // (16 bytes at a 4-byte aligned address: global loads take any alignment)
+    }
+    uint32_t p[NS][2];
+#pragma unroll
+    for (int j = 0; j < NS; j++) {
+        // weight dwords (byte 0 = lowest address), as in pyr_down_dot4x4 with k = 1
+        const uint32_t w_hi2 = 0x04010000u, w_lo3 = 0x00010406u, w_all = 0x04060401u;
+        const uint32_t h0 = udot4(v[j].y, w_lo3, udot4(v[j].x, w_hi2, 0u)), h1 = udot4(v[j].z, 1u, udot4(v[j].y, w_all, 0u));
+        const uint32_t h2 = udot4(v[j].z, w_lo3, udot4(v[j].y, w_hi2, 0u)), h3 = udot4(v[j].w, 1u, udot4(v[j].z, w_all, 0u));
+        p[j][0] = (h1 << 16) | h0, p[j][1] = (h3 << 16) | h2;
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        uint32_t s[2];
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const uint32_t mid = p[2 * r + 1][q] + p[2 * r + 3][q] + p[2 * r + 2][q];
+            const uint32_t out = p[2 * r][q] + p[2 * r + 4][q] + 0x00800080u;
+            s[q] = (mid << 2) + ((p[2 * r + 2][q] << 1) + out);
+        }
+        if (y0 + r < dh) *reinterpret_cast<uint32_t *>(dst + (size_t)((uint32_t)(y0 + r) * dpitch) + 4u * (uint32_t)g) = __builtin_amdgcn_perm(s[1], s[0], 0x07050301u);
+    }
+}
+
+// Output rows a thread of k_pyr_down's interior workgroups produces (R above).  4 and 2 were built and measured (DESIGN section 31,
+// profiles/pyr_rows_4k.txt): 4 is kept for every height; -DVSTAB_PYR_ROWS=2 rebuilds the other for a comparison.
+#ifndef VSTAB_PYR_ROWS
+#define VSTAB_PYR_ROWS 4
+#endif
+constexpr int PYR_ROWS = VSTAB_PYR_ROWS;
+
+// Groups of 4 outputs [g_lo, g_hi) of every row are interior (64 groups x 4 rows per workgroup; in k_pyr_down, R > 1, 64 groups x
+// 4 row groups of R rows, a wave being one row group); the remaining groups --
 // the first of a row, the last one to three, or all of them for an unaligned or tiny image -- are gathered in workgroups
 // of their own, so that no wavefront of the bulk ever runs the byte path.  Those come first in the grid: they are the
 // slow ones.  (pyr_grid on the host side.)
-template <bool COPY>
+template <bool COPY, int R = 1>
 __device__ __forceinline__ void pyr_down_dispatch(const uint8_t *__restrict__ src, uint32_t spitch, int sw, int sh, uint8_t *__restrict__ dst, size_t dpitch, int dw,
                                                   int dh, int vec_ok, int g_lo, int g_hi, int nbx, int nb_edge, int n_groups, int near,
                                                   uint8_t *__restrict__ cp = nullptr, uint32_t cpitch = 0) {
     if ((int)blockIdx.x >= nb_edge) {
         const int b = blockIdx.x - nb_edge, by = b / nbx, bx = b - by * nbx;
+        if constexpr (R > 1) {
+            static_assert(!COPY, "the fused copy keeps the one-row body");
+            const int g = g_lo + bx * 64 + (threadIdx.x & 63);
+            const int y0 = R * __builtin_amdgcn_readfirstlane(by * 4 + (threadIdx.x >> 6));  // (a wave is one row group)
+            if (g >= g_hi || y0 >= dh) return;
+            pyr_down_rows<R>(src, spitch, sh, dst, (uint32_t)dpitch, dh, g, y0);
+            return;
+        }
         const int g = g_lo + bx * 64 + (threadIdx.x & 63), y = by * 4 + (threadIdx.x >> 6);
         if (g >= g_hi || y >= dh) return;
         pyr_down_group<false, true, COPY>(src, spitch, sw, sh, dst, dpitch, dw, 4 * g, y, true, cp, cpitch);
@@ -156,7 +219,7 @@ __device__ __forceinline__ void pyr_down_dispatch(const uint8_t *__restrict__ sr
 __global__ void __launch_bounds__(256) k_pyr_down(const uint8_t *__restrict__ src, size_t spitch, int sw, int sh,
                                                   uint8_t *__restrict__ dst, size_t dpitch, int dw, int dh, int vec_ok, int g_lo, int g_hi,
                                                   int nbx, int nb_edge, int n_groups, int near) {
-    pyr_down_dispatch<false>(src, (uint32_t)spitch, sw, sh, dst, dpitch, dw, dh, vec_ok, g_lo, g_hi, nbx, nb_edge, n_groups, near);
+    pyr_down_dispatch<false, PYR_ROWS>(src, (uint32_t)spitch, sw, sh, dst, dpitch, dw, dh, vec_ok, g_lo, g_hi, nbx, nb_edge, n_groups, near);
 }
 
 // k_pack_pyr -- the copy of an upstream NV12 frame into the library's ring AND the first pyramid level of its luma plane in one launch
@@ -310,14 +373,15 @@ __global__ void __launch_bounds__(256) k_pyr_down_x2(const uint8_t *__restrict__
 // ---------------------------------------------------------------------------------------------
 // The grid of k_pyr_down / k_pack_pyr: group g = outputs 4g .. 4g+3 reads source bytes [8g - 4, 8g + 12), so it is interior iff g >= 1,
 // 8g + 12 <= sw and 4g + 4 <= dw -- and only where rows are dword aligned and every tap within one reflection (`wide` = vec_ok && near).
-// nb_edge workgroups of 256 edge groups come first, then nb_int = nbx x div_up(dh, 4) workgroups of 64 interior groups x 4 rows.
+// nb_edge workgroups of 256 edge groups come first, then nb_int = nbx x div_up(dh, 4 rows) workgroups of 64 interior groups x 4 row groups
+// of `rows` rows each (k_pack_pyr: 1; k_pyr_down: PYR_ROWS).
 struct PyrGrid {
     int n_groups, g_lo, g_hi, nbx, nb_int, nb_edge;
 };
-static PyrGrid pyr_grid(int sw, int dw, int dh, bool wide) {
+static PyrGrid pyr_grid(int sw, int dw, int dh, bool wide, int rows = 1) {
     const int n_groups = div_up(dw, 4), g_lo = 1, g_hi = wide ? std::max(g_lo, std::min(sw >= 12 ? (sw - 12) / 8 + 1 : 0, dw / 4)) : g_lo;
     const int nbx = div_up(g_hi - g_lo, 64);
-    return {n_groups, g_lo, g_hi, nbx, nbx * (int)div_up(dh, 4), (int)div_up(dh * (n_groups - (g_hi - g_lo)), 256)};
+    return {n_groups, g_lo, g_hi, nbx, nbx * (int)div_up(dh, 4 * rows), (int)div_up(dh * (n_groups - (g_hi - g_lo)), 256)};
 }
 
 // `done` (optional): an event that completes with this kernel -- bound to the launch itself (hipExtLaunchKernelGGL's stop event), so that the
@@ -335,7 +399,7 @@ vstab_status launch_pyr_down(const uint8_t *src, size_t spitch, int sw, int sh, 
     VSTAB_TRY(check_pyr_down(spitch, sw, sh, dpitch));
     const int vec_ok = reinterpret_cast<uintptr_t>(src) % 4 == 0 && spitch % 4 == 0 && reinterpret_cast<uintptr_t>(dst) % 4 == 0 && dpitch % 4 == 0;
     const int near = sw >= 16 && sh >= 4;
-    const PyrGrid g = pyr_grid(sw, dw, dh, vec_ok && near);
+    const PyrGrid g = pyr_grid(sw, dw, dh, vec_ok && near, PYR_ROWS);
     hipExtLaunchKernelGGL(k_pyr_down, dim3(g.nb_edge + g.nb_int), dim3(256), 0, s, nullptr, done, 0, src, spitch, sw, sh, dst, dpitch, dw, dh, vec_ok, g.g_lo, g.g_hi, g.nbx,
                           g.nb_edge, g.n_groups, near);
     VSTAB_HIP_TRY(hipGetLastError());
