@@ -1113,6 +1113,56 @@ VSTAB_API vstab_status vstab_set_tracker_options(vstab_handle *h, int max_level,
 VSTAB_API vstab_status vstab_pull_frame_keep(vstab_handle *h, void *dst_bgr, size_t pitch_dst, const void *prev_bgr, size_t pitch_prev);
 VSTAB_API vstab_status vstab_pull_frame_nv12_planar_keep(vstab_handle *h, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv,
                                                          const void *prev_y, size_t pitch_prev_y, const void *prev_uv, size_t pitch_prev_uv);
+/* ---- Colour matrix and range ----------------------------------------------------------------------------------------------------------
+ * The NV12 <-> BGR conversion of the BGR path as a choice of (matrix, range).  (VSTAB_COLOUR_CVTCOLOR, VSTAB_RANGE_LIMITED) is
+ * cvtColor(COLOR_YUV2BGR_NV12) / cvtColor(COLOR_BGR2YUV_I420) with OpenCV's constants, byte for byte, and is the default everywhere;
+ * (VSTAB_COLOUR_CVTCOLOR, VSTAB_RANGE_FULL) does not exist and is refused.  The other six specs use the same 20-bit fixed-point forms with
+ * coefficients derived from (Kr, Kb): BT601 (0.299, 0.114), BT709 (0.2126, 0.0722), BT2020 non-constant luminance (0.2627, 0.0593);
+ * Kg = 1 - Kr - Kb.  Limited range: sy = 255/219, sc = 255/224, yoff = 16.  Full range: sy = sc = 1, yoff = 0.  rint is round half to even
+ * of the exact rational value.
+ *   forward   CY = rint(2^20 sy), CVR = rint(2^20 sc 2(1 - Kr)), CUB = rint(2^20 sc 2(1 - Kb)),
+ *             CUG = -rint(2^20 sc 2 Kb (1 - Kb) / Kg), CVG = -rint(2^20 sc 2 Kr (1 - Kr) / Kg); with u = U - 128, v = V - 128 and
+ *             y = max(Y - yoff, 0) CY + 2^19:
+ *               B = sat8((y + CUB u) >> 20), G = sat8((y + CVG v + CUG u) >> 20), R = sat8((y + CVR v) >> 20)
+ *   inverse   CRY = rint(2^20 Kr / sy), CGY = rint(2^20 Kg / sy), CBY = rint(2^20 Kb / sy), CBU = rint(2^20 / (2 sc)) (also R's in V),
+ *             CRU = -rint(2^20 Kr / (2(1 - Kb) sc)), CGU = -rint(2^20 Kg / (2(1 - Kb) sc)),
+ *             CGV = -rint(2^20 Kg / (2(1 - Kr) sc)), CBV = -rint(2^20 Kb / (2(1 - Kr) sc));
+ *               Y = sat8((CRY R + CGY G + CBY B + 2^19 + (yoff << 20)) >> 20)
+ *               U = sat8((CRU R + CGU G + CBU B + 2^19 + (128 << 20)) >> 20)
+ *               V = sat8((CBU R + CGV G + CBV B + 2^19 + (128 << 20)) >> 20)
+ *             chroma from the top-left pixel of each 2 x 2 block.  The saturation is part of the definition: with CVTCOLOR it never acts,
+ *             with full range it does (pure blue gives an unsaturated U of 256).
+ * Every coefficient is below 2^23 and every forward sum below 5.8e8 in magnitude, so 24-bit multiplies and int32 sums hold for every spec.
+ * A warp with a colour spec is the warp with the conversion exchanged: BGR8 = cvt(frame, spec) then cv::remap INTER_LINEAR with border 0;
+ * NV12 through BGR = that frame converted back with the inverse of the same spec. */
+enum { VSTAB_COLOUR_CVTCOLOR = 0, VSTAB_COLOUR_BT601 = 1, VSTAB_COLOUR_BT709 = 2, VSTAB_COLOUR_BT2020 = 3 }; /* matrix */
+enum { VSTAB_RANGE_LIMITED = 0, VSTAB_RANGE_FULL = 1 };                                                   /* range  */
+/* out = CY, CUB, CUG, CVG, CVR, yoff, CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV of a spec (host memory; no device needed).  An unknown matrix,
+ * an unknown range, (CVTCOLOR, FULL) and a NULL pointer are VSTAB_ERR_INVALID. */
+VSTAB_API vstab_status vstab_colour_coefficients(int matrix, int range, int32_t out[14]);
+/* vstab_cvt_nv12_bgr with a colour spec. */
+VSTAB_API vstab_status vstab_cvt_nv12_bgr_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int width, int height, void *dst,
+                                                 size_t pitch_dst, int matrix, int range, void *stream);
+/* The inverse as an operator: 8-bit BGR (even width and height) to NV12 planes, dst_uv with width bytes per row, 2-byte aligned. */
+VSTAB_API vstab_status vstab_cvt_bgr_nv12_colour(const void *src_bgr, size_t pitch, int width, int height, void *dst_y, size_t pitch_y, void *dst_uv,
+                                                 size_t pitch_uv, int matrix, int range, void *stream);
+/* vstab_warp_nv12_ex with a colour spec: VSTAB_OUT_BGR8 and VSTAB_OUT_NV12 (through BGR, converted back with the spec's inverse).
+ * VSTAB_OUT_NV12_PLANAR converts nothing and is refused with VSTAB_ERR_INVALID, as is a bad spec.  (CVTCOLOR, LIMITED) is vstab_warp_nv12_ex
+ * itself.  With any other spec, source planes of 4 GiB and more are VSTAB_ERR_UNSUPPORTED. */
+VSTAB_API vstab_status vstab_warp_nv12_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                              const float params[17], int map_mode, int out_format, void *dst, size_t pitch_dst, void *dst_uv,
+                                              size_t pitch_dst_uv, int dst_width, int dst_height, int matrix, int range, void *stream);
+/* The colour spec of a handle's BGR path, from the next pull on; it may change between pulls.  Served on 8-bit handles with INTER_LINEAR, the
+ * constant border and an ideal lens: there vstab_pull_frame, _frames, _host, vstab_peek_frame and vstab_pull_frame_nv12 convert with the
+ * spec (vstab_warp_nv12_colour); the plane-wise pull converts nothing and is served unchanged.  With a spec other than the default the
+ * quantised-map cache steps aside (as it does for keep pulls).  A handle that never calls this, or sets (CVTCOLOR, LIMITED), runs what it
+ * ran before.  Refused, the handle unchanged: a NULL handle and a bad spec (VSTAB_ERR_INVALID); a spec other than the default on a handle
+ * with pixel_depth 10, interpolation 0, resample VSTAB_RESAMPLE_CUBIC / _LANCZOS4, a calibration (vstab_set_input_calibration[_ex],
+ * vstab_set_input_pinhole) or a non-constant border mode in force (VSTAB_ERR_UNSUPPORTED).  While such a spec is set,
+ * vstab_set_border_mode[_ex] refuse non-constant modes, the calibration setters and the keep pulls refuse (VSTAB_ERR_UNSUPPORTED), and a
+ * frame that carries a readout_rotation is refused and consumed by the converting pulls, as INTER_NEAREST does. */
+VSTAB_API vstab_status vstab_set_colour(vstab_handle *h, int matrix, int range);
+
 /* Synchronises the stream, folds all pending event pairs into the sums and returns them. */
 VSTAB_API vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out);
 

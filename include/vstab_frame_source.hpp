@@ -138,6 +138,15 @@ class FrameSourceWarp : public FrameSource {
             throw (int)st;
         }
     }
+    // the colour matrix and range of the NV12 -> BGR conversion (FrameSourceWarp.cpp:401 calls cvtColor: VSTAB_COLOUR_CVTCOLOR, the default)
+    // for the frames pulled from now on: VSTAB_COLOUR_BT601 / _BT709 / _BT2020 with VSTAB_RANGE_LIMITED or _FULL -- vstab_set_colour
+    void set_colour(int matrix, int range = VSTAB_RANGE_LIMITED) {
+        const vstab_status st = vstab_set_colour(m_handle, matrix, range);
+        if (st != VSTAB_OK) {
+            std::fprintf(stderr, "FrameSourceWarp: %s\n", vstab_last_error());
+            throw (int)st;
+        }
+    }
     // goodFeaturesToTrack's mask for find_corners (FrameSourceWarp.cpp:228-240 passes none): bytes of the input's size, non-zero = "a corner
     // may be reported here", in host (VSTAB_MEM_HOST) or device memory; before the first pull_frame -- vstab_set_detection_mask
     void set_detection_mask(const void *mask, size_t pitch, int mem = VSTAB_MEM_HOST) {

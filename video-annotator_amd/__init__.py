@@ -85,6 +85,9 @@ RESAMPLE_DEFAULT, RESAMPLE_CUBIC, RESAMPLE_LANCZOS4 = 0, 2, 4  # vstab_config.re
 # cv::remap's borderMode (cv::BorderTypes values): vstab_remap_bilinear_border, vstab_warp_nv12_border, vstab_set_border_mode; with INTER_CUBIC /
 # INTER_LANCZOS4: vstab_remap_{cubic,lanczos4}_border, vstab_warp_nv12_{cubic,lanczos4}_border, vstab_set_border_mode_ex
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 = 0, 1, 2, 4
+# the colour spec of the BGR path (include/vstab.h, "Colour matrix and range"): matrix, range
+COLOUR_CVTCOLOR, COLOUR_BT601, COLOUR_BT709, COLOUR_BT2020 = range(4)
+RANGE_LIMITED, RANGE_FULL = 0, 1
 READOUT_REFUSE, READOUT_PER_ROW = 0, 1  # vstab_set_readout_warp
 _pp = _c.POINTER(_vp)
 
@@ -167,6 +170,11 @@ SIGNATURES = {
     "vstab_remap_bilinear_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _vp, _sz, _i, _i, _vp]),
     "vstab_warp_nv12_border": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_set_border_mode": (_i, [_vp, _i]),
+    "vstab_colour_coefficients": (_i, [_i, _i, _c.POINTER(_c.c_int32)]),
+    "vstab_cvt_nv12_bgr_colour": (_i, [_vp, _sz, _vp, _sz, _i, _i, _vp, _sz, _i, _i, _vp]),
+    "vstab_cvt_bgr_nv12_colour": (_i, [_vp, _sz, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_warp_nv12_colour": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "vstab_set_colour": (_i, [_vp, _i, _i]),
     "vstab_warp_nv12_rs_ex": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_set_readout_warp": (_i, [_vp, _i]),
     "vstab_remap_cubic_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _ip, _vp, _sz, _i, _i, _vp]),
@@ -369,6 +377,52 @@ def cvt_nv12_bgr(nv12, out=None):
         out = torch.empty((h, w, 3), dtype=torch.uint8, device=nv12.device)
     _check(_L.vstab_cvt_nv12_bgr(yp, pitch, uvp, pitch, w, h, out.data_ptr(), out.stride(0), _stream()),
            "vstab_cvt_nv12_bgr")
+    return out
+
+
+def colour_coefficients(matrix, range_):
+    """vstab_colour_coefficients: CY, CUB, CUG, CVG, CVR, yoff, CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV of a spec (host only) -> int32 array of 14."""
+    out = np.zeros(14, np.int32)
+    _check(_L.vstab_colour_coefficients(int(matrix), int(range_), out.ctypes.data_as(_c.POINTER(_c.c_int32))), "vstab_colour_coefficients")
+    return out
+
+
+def cvt_nv12_bgr_colour(nv12, matrix, range_, out=None):
+    """vstab_cvt_nv12_bgr_colour: cvt_nv12_bgr with a colour spec."""
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=nv12.device)
+    _check(_L.vstab_cvt_nv12_bgr_colour(yp, pitch, uvp, pitch, w, h, out.data_ptr(), out.stride(0), int(matrix), int(range_), _stream()),
+           "vstab_cvt_nv12_bgr_colour")
+    return out
+
+
+def cvt_bgr_nv12_colour(bgr, matrix, range_, out=None):
+    """vstab_cvt_bgr_nv12_colour: (h, w, 3) BGR, even sizes -> packed NV12 (h*3/2, w) with the spec's inverse."""
+    import torch
+    h, w, _ = bgr.shape
+    if out is None:
+        out = torch.empty((h * 3 // 2, w), dtype=torch.uint8, device=bgr.device)
+    yp, uvp, pitch, _, _ = _planes(out)
+    _check(_L.vstab_cvt_bgr_nv12_colour(bgr.data_ptr(), bgr.stride(0), w, h, yp, pitch, uvp, pitch, int(matrix), int(range_), _stream()),
+           "vstab_cvt_bgr_nv12_colour")
+    return out
+
+
+def warp_nv12_colour(nv12, params, dw, dh, matrix, range_, mode=MAP_CREATEMAP_CL, out_format=OUT_BGR8, out=None):
+    """vstab_warp_nv12_colour: warp_nv12 with a colour spec.  OUT_BGR8 -> (dh, dw, 3) tensor; OUT_NV12 -> (luma, chroma) tensors."""
+    import torch
+    yp, uvp, pitch, w, h = _planes(nv12)
+    if out_format == OUT_BGR8:
+        if out is None:
+            out = torch.empty((dh, dw, 3), dtype=torch.uint8, device=nv12.device)
+        planes = (out.data_ptr(), out.stride(0), None, 0)
+    else:
+        yo, co = out = tuple(out) if out is not None else nv12_out_planes(dw, dh, nv12.device)
+        planes = (yo.data_ptr(), yo.stride(0), co.data_ptr(), co.stride(0))
+    _check(_L.vstab_warp_nv12_colour(yp, pitch, uvp, pitch, w, h, _fptr(_f32(params)), int(mode), int(out_format), *planes, dw, dh, int(matrix), int(range_),
+                                     _stream()), "vstab_warp_nv12_colour")
     return out
 
 
@@ -1215,6 +1269,10 @@ class Stabilizer:
         out = (_c.c_long * 3)()
         _check(_L.vstabx_detector_counters(self._h, out), "vstabx_detector_counters")
         return dict(spec_over_cap=out[0], fused_overflows=out[1], key_capacity=out[2])
+
+    def set_colour(self, matrix, range_=RANGE_LIMITED):
+        """vstab_set_colour: the colour spec of the converting pulls (BGR, host, NV12 through BGR), from the next pull on."""
+        _check(_L.vstab_set_colour(self._h, int(matrix), int(range_)), "vstab_set_colour")
 
     def set_border_mode(self, border_mode):
         """vstab_set_border_mode: cv::remap's borderMode for the frames pulled from now on."""

@@ -532,6 +532,55 @@ __device__ __forceinline__ uint32_t pack_bgrx(int Y, const ChromaTerm &c) {
     return d;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Colour matrix and range (include/vstab.h, "Colour matrix and range"): the same 20-bit fixed-point forms with the
+// coefficients in a block of kernel arguments, so that one kernel serves every spec.  The block is what
+// vstab_colour_coefficients writes: five forward coefficients, yoff, eight inverse ones.  With the cvtColor row
+// every function below returns what its namesake above returns.  Every coefficient is below 2^23 (24-bit
+// multiplies hold) and every forward sum below 5.8e8 in magnitude (int32 holds).
+// ---------------------------------------------------------------------------------------------
+struct ColourCoef {
+    int cy, cub, cug, cvg, cvr, yoff;
+    int cry, cgy, cby, cru, cgu, cbu, cgv, cbv;
+};
+__device__ __forceinline__ ChromaTerm chroma_term(const ColourCoef &k, int U, int V) {
+    const int u = U - 128, v = V - 128;
+    return {(1 << 19) + k.cvr * v, (1 << 19) + k.cvg * v + k.cug * u, (1 << 19) + k.cub * u};
+}
+__device__ __forceinline__ void yuv_to_bgr(const ColourCoef &k, int Y, const ChromaTerm &c, int &b, int &g, int &r) {
+    const int y = max(Y - k.yoff, 0) * k.cy;
+    b = sat8(ashr20(y + c.buv));
+    g = sat8(ashr20(y + c.guv));
+    r = sat8(ashr20(y + c.ruv));
+}
+// channel = sat8((max(Y, yoff) * CY + term) >> 20): the luma offset folded into the chroma terms, as chroma_term_folded does
+__device__ __forceinline__ ChromaTerm chroma_term_folded(const ColourCoef &k, int U, int V) {
+    const int u = U - 128, v = V - 128;
+    const int K = (1 << 19) - k.yoff * k.cy;  // uniform
+    return {K + __mul24(k.cvr, v), K + __mul24(k.cvg, v) + __mul24(k.cug, u), K + __mul24(k.cub, u)};
+}
+__device__ __forceinline__ uint32_t pack_bgrx(const ColourCoef &k, int Y, const ChromaTerm &c) {
+    const int y = max(Y, k.yoff);
+    const int b = __mul24(y, k.cy) + c.buv, g = __mul24(y, k.cy) + c.guv, r = __mul24(y, k.cy) + c.ruv;
+    uint32_t d;
+    asm("v_ashr_pk_u8_i32 %0, %1, %2, 20" : "=v"(d) : "v"(b), "v"(g));
+    asm("v_ashr_pk_u8_i32 %0, %1, 0, 20 op_sel:[0,0,0,1]" : "+v"(d) : "v"(r));
+    return d;
+}
+// The inverse, v = B | G << 8 | R << 16.  The saturation is part of the definition: full range reaches an unsaturated U or V of 256
+// (pure blue, pure red); no sum leaves int32 (|coefficient| < 2^20, three bytes, 129 << 20).  ashr20: see above -- the compiler must not
+// fuse the shift and the saturation of two bytes that are then packed.
+__device__ __forceinline__ uint32_t bgr_to_y(const ColourCoef &k, uint32_t v) {
+    const int B = v & 255, G = (v >> 8) & 255, R = (v >> 16) & 255;
+    return (uint32_t)sat8(ashr20(__mul24(k.cry, R) + __mul24(k.cgy, G) + __mul24(k.cby, B) + (1 << 19) + (k.yoff << 20)));
+}
+__device__ __forceinline__ uint32_t bgr_to_uv(const ColourCoef &k, uint32_t v) {  // U | V << 8
+    const int B = v & 255, G = (v >> 8) & 255, R = (v >> 16) & 255;
+    const uint32_t U = (uint32_t)sat8(ashr20(__mul24(k.cru, R) + __mul24(k.cgu, G) + __mul24(k.cbu, B) + (1 << 19) + (128 << 20)));
+    const uint32_t V = (uint32_t)sat8(ashr20(__mul24(k.cbu, R) + __mul24(k.cgv, G) + __mul24(k.cbv, B) + (1 << 19) + (128 << 20)));
+    return U | (V << 8);
+}
+
 // cv::remap fixed-point bilinear blend of four BGRx taps:
 //   out_c = (p00*(32-fx)(32-fy) + p01*fx(32-fy) + p10*(32-fx)fy + p11*fx*fy + 512) >> 10
 // evaluated as an exact two-stage integer lerp (vertical per column with v_dot4_u32_u8 on byte pairs gathered by

@@ -654,6 +654,7 @@ static vstab_status set_input_calibration(vstab_handle *h, const double K[9], co
     if (!resamplers && h->border_mode != VSTAB_BORDER_CONSTANT)
         return fail(VSTAB_ERR_INVALID, n + "the distorted-lens warp has the constant border, this handle has another border mode set (vstab_set_border_mode)");
     if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the calibration must be set before the first pull");
+    if (h->colour()) return fail(VSTAB_ERR_UNSUPPORTED, n + "a colour spec is set (vstab_set_colour), and the distorted-lens warp converts with cvtColor's arithmetic");
     if (K && !(std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5]) && K[0] > 0 && K[4] > 0 && K[1] == 0 && K[3] == 0 &&
                K[6] == 0 && K[7] == 0 && K[8] == 1))
         return fail(VSTAB_ERR_INVALID, n + "K must be a camera matrix with fx, fy > 0, zero skew and last row 0 0 1");
@@ -676,6 +677,7 @@ vstab_status vstab_set_input_pinhole(vstab_handle *h, const double K[9], const d
     if (c.interpolation == 0 && c.resample == VSTAB_RESAMPLE_DEFAULT)
         return fail(VSTAB_ERR_INVALID, n + "the pinhole-lens warp resamples with INTER_LINEAR, INTER_CUBIC or INTER_LANCZOS4, this handle with INTER_NEAREST");
     if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the calibration must be set before the first pull");
+    if (h->colour()) return fail(VSTAB_ERR_UNSUPPORTED, n + "a colour spec is set (vstab_set_colour), and the pinhole-lens warp converts with cvtColor's arithmetic");
     if (K && !(std::isfinite(K[0]) && std::isfinite(K[4]) && std::isfinite(K[2]) && std::isfinite(K[5]) && K[0] > 0 && K[4] > 0 && K[1] == 0 && K[3] == 0 &&
                K[6] == 0 && K[7] == 0 && K[8] == 1))
         return fail(VSTAB_ERR_INVALID, n + "K must be a camera matrix with fx, fy > 0, zero skew and last row 0 0 1");

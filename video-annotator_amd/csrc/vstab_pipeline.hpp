@@ -329,6 +329,9 @@ struct vstab_handle {
     float qmap_params[17] = {0}, last_params[17] = {0};
     bool qmap_valid = false, have_last_params = false, map_cache = true;  // VSTAB_MAP_CACHE=0 disables
     int border_mode = VSTAB_BORDER_CONSTANT;  // vstab_set_border_mode: applies from the next pull
+    // vstab_set_colour: the colour spec of the converting pulls (BGR, NV12 through BGR), from the next pull on
+    int colour_matrix = VSTAB_COLOUR_CVTCOLOR, colour_range = VSTAB_RANGE_LIMITED;
+    bool colour() const { return colour_matrix != VSTAB_COLOUR_CVTCOLOR || colour_range != VSTAB_RANGE_LIMITED; }
     int readout_warp = VSTAB_READOUT_REFUSE;  // vstab_set_readout_warp: applies from the next pull
     long warps_from_cache = 0;
     PinnedBuf marker_pts;           // vstab_config.debug: rotating sets of marker centres, read by the kernel in place

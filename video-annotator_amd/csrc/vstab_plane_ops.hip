@@ -1,4 +1,4 @@
-// vstab_plane_ops.hip -- operators on whole planes for gfx950 (MI355X): NV12 / P010 packing, NV12 -> BGR, the map planes (createMap and the
+// vstab_plane_ops.hip -- operators on whole planes for gfx950 (MI355X): NV12 / P010 packing, NV12 -> BGR and, with a colour spec, both ways, the map planes (createMap and the
 // generalised map), the quantised map, remap from map planes and the debug markers, with their C entry points.  Compiled with
 // -ffp-contract=off.
 //
@@ -6,6 +6,7 @@
 // fill 256 CUs, and keeping the map in registers.
 #include <climits>
 
+#include "vstab_colour.hpp"
 #include "vstab_warp_host.hpp"
 
 namespace vstab {
@@ -115,6 +116,88 @@ __global__ void __launch_bounds__(256) k_cvt_nv12_bgr(const uint8_t *__restrict_
             }
         }
     }
+}
+
+// =============================================================================================
+// k_cvt_nv12_bgr_colour -- k_cvt_nv12_bgr with a colour spec's coefficients (include/vstab.h, "Colour matrix and range"): the same
+// 8 x 2 block per thread, the conversion through the ColourCoef forms of vstab_device.hpp.
+// =============================================================================================
+__global__ void __launch_bounds__(256) k_cvt_nv12_bgr_colour(const uint8_t *__restrict__ yp, size_t pitch_y, const uint8_t *__restrict__ uvp, size_t pitch_uv,
+                                                             int w, int h, uint8_t *__restrict__ dst, size_t pitch_dst, int vec_ok, ColourCoef k) {
+    const int bx = (blockIdx.x * blockDim.x + threadIdx.x) * 8;
+    const int by = (blockIdx.y * blockDim.y + threadIdx.y) * 2;
+    if (bx >= w || by >= h) return;
+    const uint8_t *y0 = yp + (size_t)by * pitch_y + bx;
+    const uint8_t *y1 = y0 + pitch_y;
+    const uint8_t *uv = uvp + (size_t)(by >> 1) * pitch_uv + bx;
+    uint8_t *d0 = dst + (size_t)by * pitch_dst + (size_t)bx * 3;
+    uint8_t *d1 = d0 + pitch_dst;
+    if (vec_ok && bx + 8 <= w) {
+        const uint2 a = *reinterpret_cast<const uint2 *>(y0);
+        const uint2 b = *reinterpret_cast<const uint2 *>(y1);
+        const uint2 c = *reinterpret_cast<const uint2 *>(uv);
+        const uint32_t ya[2] = {a.x, a.y}, yb[2] = {b.x, b.y}, cc[2] = {c.x, c.y};
+        uint32_t o0[6], o1[6];
+        uint8_t t0[24], t1[24];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int pair = i >> 1;
+            const uint32_t cw = cc[pair >> 1] >> ((pair & 1) * 16);
+            const ChromaTerm ct = chroma_term(k, cw & 255, (cw >> 8) & 255);
+            int bb, gg, rr;
+            yuv_to_bgr(k, (ya[i >> 2] >> ((i & 3) * 8)) & 255, ct, bb, gg, rr);
+            t0[3 * i] = bb, t0[3 * i + 1] = gg, t0[3 * i + 2] = rr;
+            yuv_to_bgr(k, (yb[i >> 2] >> ((i & 3) * 8)) & 255, ct, bb, gg, rr);
+            t1[3 * i] = bb, t1[3 * i + 1] = gg, t1[3 * i + 2] = rr;
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            o0[i] = t0[4 * i] | (t0[4 * i + 1] << 8) | (t0[4 * i + 2] << 16) | ((uint32_t)t0[4 * i + 3] << 24);
+            o1[i] = t1[4 * i] | (t1[4 * i + 1] << 8) | (t1[4 * i + 2] << 16) | ((uint32_t)t1[4 * i + 3] << 24);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            reinterpret_cast<uint2 *>(d0)[i] = make_uint2(o0[2 * i], o0[2 * i + 1]);
+            reinterpret_cast<uint2 *>(d1)[i] = make_uint2(o1[2 * i], o1[2 * i + 1]);
+        }
+    } else {
+        for (int i = 0; i < 8 && bx + i < w; i++) {
+            const ChromaTerm ct = chroma_term(k, uv[i & ~1], uv[(i & ~1) + 1]);
+            int bb, gg, rr;
+            yuv_to_bgr(k, y0[i], ct, bb, gg, rr);
+            d0[3 * i] = bb, d0[3 * i + 1] = gg, d0[3 * i + 2] = rr;
+            if (by + 1 < h) {
+                yuv_to_bgr(k, y1[i], ct, bb, gg, rr);
+                d1[3 * i] = bb, d1[3 * i + 1] = gg, d1[3 * i + 2] = rr;
+            }
+        }
+    }
+}
+
+// =============================================================================================
+// k_cvt_bgr_nv12_colour -- the inverse (cvtColor(COLOR_BGR2YUV_I420)'s form with a spec's coefficients, NV12 planes out): luma for every
+// pixel, chroma from the top-left pixel of each 2 x 2 block, through bgr_to_y / bgr_to_uv -- the functions the fused kernel's NV12 store
+// calls.  One thread per 2 x 2 block (w and h are even): a parity operator, byte accesses.
+// =============================================================================================
+__global__ void __launch_bounds__(256) k_cvt_bgr_nv12_colour(const uint8_t *__restrict__ src, size_t pitch, int w, int h, uint8_t *__restrict__ dy,
+                                                             size_t pitch_y, uint8_t *__restrict__ duv, size_t pitch_uv, ColourCoef k) {
+    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * 2, y = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 2;
+    if (x >= w || y >= h) return;
+    uint32_t px[2][2];
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const uint8_t *s = src + (size_t)(y + j) * pitch + (size_t)(x + i) * 3;
+            px[j][i] = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16);
+        }
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        uint8_t *o = dy + (size_t)(y + j) * pitch_y + x;
+        o[0] = (uint8_t)bgr_to_y(k, px[j][0]), o[1] = (uint8_t)bgr_to_y(k, px[j][1]);
+    }
+    const uint32_t c = bgr_to_uv(k, px[0][0]);
+    *reinterpret_cast<uint16_t *>(duv + (size_t)(y >> 1) * pitch_uv + x) = (uint16_t)c;
 }
 
 // Four adjacent entries of both map planes, columns x0 .. x0 + 3 of row y: one 16-B store per plane when the planes are aligned
@@ -418,6 +501,37 @@ vstab_status vstab_cvt_nv12_bgr(const void *y, size_t pitch_y, const void *uv, s
     dim3 grid(div_up(div_up(width, 8), 32), div_up(div_up(height, 2), 8));
     hipLaunchKernelGGL(k_cvt_nv12_bgr, grid, block, 0, static_cast<hipStream_t>(stream), (const uint8_t *)y,
                        pitch_y, (const uint8_t *)uv, pitch_uv, width, height, (uint8_t *)dst, pitch_dst, vec_ok);
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
+vstab_status vstab_cvt_nv12_bgr_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int width, int height, void *dst, size_t pitch_dst,
+                                       int matrix, int range, void *stream) {
+    VSTAB_TRY(check_colour_spec("vstab_cvt_nv12_bgr_colour", matrix, range));
+    if (colour_spec_default(matrix, range)) return vstab_cvt_nv12_bgr(y, pitch_y, uv, pitch_uv, width, height, dst, pitch_dst, stream);
+    if (!y || !uv || !dst) return fail(VSTAB_ERR_INVALID, "vstab_cvt_nv12_bgr_colour: null pointer");
+    if (width <= 0 || height <= 0 || (width & 1) || (height & 1)) return fail(VSTAB_ERR_INVALID, "vstab_cvt_nv12_bgr_colour: width and height must be even");
+    if (pitch_y < (size_t)width || pitch_uv < (size_t)width || pitch_dst < (size_t)width * 3)
+        return fail(VSTAB_ERR_INVALID, "vstab_cvt_nv12_bgr_colour: pitch smaller than row");
+    const int vec_ok = ptr_aligned(y, 8) && ptr_aligned(uv, 8) && ptr_aligned(dst, 8) && pitch_y % 8 == 0 && pitch_uv % 8 == 0 && pitch_dst % 8 == 0;
+    dim3 block(32, 8);
+    dim3 grid(div_up(div_up(width, 8), 32), div_up(div_up(height, 2), 8));
+    hipLaunchKernelGGL(k_cvt_nv12_bgr_colour, grid, block, 0, static_cast<hipStream_t>(stream), (const uint8_t *)y, pitch_y, (const uint8_t *)uv, pitch_uv, width,
+                       height, (uint8_t *)dst, pitch_dst, vec_ok, colour_coefficients(matrix, range));
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
+vstab_status vstab_cvt_bgr_nv12_colour(const void *src_bgr, size_t pitch, int width, int height, void *dst_y, size_t pitch_y, void *dst_uv, size_t pitch_uv,
+                                       int matrix, int range, void *stream) {
+    VSTAB_TRY(check_colour_spec("vstab_cvt_bgr_nv12_colour", matrix, range));
+    if (!src_bgr || !dst_y || !dst_uv) return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr_nv12_colour: null pointer");
+    if (width <= 0 || height <= 0 || (width & 1) || (height & 1)) return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr_nv12_colour: width and height must be even");
+    if (pitch < (size_t)width * 3 || pitch_y < (size_t)width || pitch_uv < (size_t)width)
+        return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr_nv12_colour: pitch smaller than row");
+    if (!ptr_aligned(dst_uv, 2) || pitch_uv % 2) return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr_nv12_colour: chroma plane must be 2-B aligned");
+    hipLaunchKernelGGL(k_cvt_bgr_nv12_colour, dim3(div_up(width / 2, 64), div_up(height / 2, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (const uint8_t *)src_bgr, pitch, width, height, (uint8_t *)dst_y, pitch_y, (uint8_t *)dst_uv, pitch_uv, colour_coefficients(matrix, range));
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }

@@ -2,6 +2,7 @@
 // vstab_set_border_mode / _ex and vstab_set_readout_warp, whose modes those steps read.
 #include <cmath>
 
+#include "vstab_colour.hpp"
 #include "vstab_pipeline.hpp"
 #include "vstab_warp_request.hpp"
 
@@ -22,7 +23,9 @@ struct Pull {  // one pull on its way through the steps: what the caller asked f
     void *const dst, *const dst_uv;
     const size_t pitch_dst, pitch_dst_uv;
     const int border_mode;
+    const int colour_matrix, colour_range;  // the colour spec in force (vstab_set_colour)
     const KeepPrev *const keep = nullptr;  // a keep pull
+    bool colour() const { return colour_matrix != VSTAB_COLOUR_CVTCOLOR || colour_range != VSTAB_RANGE_LIMITED; }
     int slot = -1;
     Mat3 warp_R;
     float p[17], p_bottom[17];
@@ -56,6 +59,7 @@ static vstab_status refuse_keep(const vstab_handle *H, const Pull &P) {
         return fail(VSTAB_ERR_UNSUPPORTED, n + ": a border mode other than VSTAB_BORDER_CONSTANT is in force (vstab_set_border_mode)");
     if (H->calibrated) return fail(VSTAB_ERR_UNSUPPORTED, n + ": a calibrated handle (vstab_set_input_calibration) has no keep-edge warp");
     if (H->pinhole) return fail(VSTAB_ERR_UNSUPPORTED, n + ": a calibrated handle (vstab_set_input_pinhole) has no keep-edge warp");
+    if (P.colour()) return fail(VSTAB_ERR_UNSUPPORTED, n + ": a colour spec is set (vstab_set_colour), and the keep-edge warp converts with cvtColor's arithmetic");
     const bool planar = P.out_format == VSTAB_OUT_NV12_PLANAR;
     const KeepPlane planes[2] = {{k.prev, k.pitch_prev, P.dst, P.pitch_dst, (size_t)H->ow * (planar ? 1 : 3), H->oh},
                                  {k.prev_uv, k.pitch_prev_uv, P.dst_uv, P.pitch_dst_uv, (size_t)((H->ow + 1) / 2) * 2, (H->oh + 1) / 2}};
@@ -133,7 +137,8 @@ static vstab_status choose_cached_map(vstab_handle *H, Pull &P) {
     //  map's kernel has the constant border built in)
     // (a keep pull neither reads nor updates this state: plain pulls around it see the parameters of the plain pull before)
     // (nor does the pinhole-lens warp: vstab_set_input_pinhole)
-    if (P.keep || H->pinhole) return VSTAB_OK;
+    // (nor does a converting pull with a colour spec: the cached map's kernel has cvtColor's constants.  It steps aside as for a keep pull.)
+    if (P.keep || H->pinhole || (P.colour() && P.out_format != VSTAB_OUT_NV12_PLANAR)) return VSTAB_OK;
     if (!H->map_cache || H->cfg.resample != VSTAB_RESAMPLE_DEFAULT || P.border_mode != VSTAB_BORDER_CONSTANT || P.rot_bottom || out_is_10bit(P.out_format) ||
         P.out_format == VSTAB_OUT_NV12_PLANAR)
         return VSTAB_OK;
@@ -213,6 +218,12 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
     WarpRequest q = {.e = ENTRY_EX, .y = S.y, .pitch_y = S.pitch_y, .uv = S.uv, .pitch_uv = S.pitch_uv, .sw = w, .sh = h, .params = P.p, .rot_bottom = P.rot_bottom,
                      .map_mode = mode, .out_format = out_format, .dst = P.dst, .pitch_dst = P.pitch_dst, .dst_uv = P.dst_uv, .pitch_dst_uv = P.pitch_dst_uv,
                      .dw = ow, .dh = oh, .stream = H->stream};
+    // a colour spec (vstab_set_colour: INTER_LINEAR, constant border, ideal lens, no keep pull): the converting pulls; the plane-wise pull converts nothing
+    if (P.colour() && out_format != VSTAB_OUT_NV12_PLANAR) {
+        if (P.rot_bottom) return refuse_launch("a handle with a colour spec (vstab_set_colour) warps frames without a read-out rotation");
+        q.e = ENTRY_COLOUR, q.colour_matrix = P.colour_matrix, q.colour_range = P.colour_range;
+        return warp_nv12(q);
+    }
     if (P.keep) {  // (refuse_keep: INTER_LINEAR, constant border, ideal lens)
         q.e = ENTRY_KEEP, q.keep = true;
         q.prev = P.keep->prev, q.pitch_prev = P.keep->pitch_prev, q.prev_uv = P.keep->prev_uv, q.pitch_prev_uv = P.keep->pitch_prev_uv;
@@ -294,7 +305,7 @@ static vstab_status pull_frame_impl(vstab_handle *H, int out_format, void *dst, 
     if (keep && (!H || !dst || !keep->prev || (out_has_chroma_plane(out_format) && (!dst_uv || !keep->prev_uv))))
         return fail(VSTAB_ERR_INVALID, std::string(keep->fn) + ": null argument");
     if (!H || !dst || (out_has_chroma_plane(out_format) && !dst_uv)) return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: null argument");
-    Pull P{out_format, dst, dst_uv, pitch_dst, pitch_dst_uv, H->border_mode, keep};
+    Pull P{out_format, dst, dst_uv, pitch_dst, pitch_dst_uv, H->border_mode, H->colour_matrix, H->colour_range, keep};
     VSTAB_TRY(refuse_formats(H, P));
     if (keep) VSTAB_TRY(refuse_keep(H, P));
     H->pulled = true;
@@ -321,6 +332,8 @@ static vstab_status set_border_mode(vstab_handle *h, int border_mode, const char
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)");
     if (border_mode != VSTAB_BORDER_CONSTANT && (h->cfg.pixel_depth == 10 || h->cfg.interpolation == 0 || (!resamplers && h->cfg.resample != VSTAB_RESAMPLE_DEFAULT)))
         return fail(VSTAB_ERR_UNSUPPORTED, std::string(fn) + ": border modes other than VSTAB_BORDER_CONSTANT are served for 8-bit pixels with " + served);
+    if (border_mode != VSTAB_BORDER_CONSTANT && h->colour())
+        return fail(VSTAB_ERR_UNSUPPORTED, std::string(fn) + ": a colour spec is set (vstab_set_colour), and the border warps convert with cvtColor's arithmetic");
     if (border_mode != VSTAB_BORDER_CONSTANT && h->calibrated && !h->calibrated_borders)
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": a calibrated handle (vstab_set_input_calibration) warps with VSTAB_BORDER_CONSTANT");
     h->border_mode = border_mode;
@@ -336,6 +349,22 @@ vstab_status vstab_set_readout_warp(vstab_handle *h, int mode) {
     if (h->cfg.pixel_depth == 10 || h->cfg.interpolation == 0)
         return fail(VSTAB_ERR_UNSUPPORTED, "vstab_set_readout_warp: served for 8-bit pixels with INTER_LINEAR, INTER_CUBIC or INTER_LANCZOS4");
     h->readout_warp = mode;
+    return VSTAB_OK;
+}
+
+// The colour spec of the converting pulls.  The handles that are served are those whose warp is the bilinear fused kernel with one rotation
+// per frame: every other kernel has cvtColor's constants.
+vstab_status vstab_set_colour(vstab_handle *h, int matrix, int range) {
+    const std::string n = "vstab_set_colour: ";
+    if (!h) return fail(VSTAB_ERR_INVALID, n + "null handle");
+    VSTAB_TRY(check_colour_spec("vstab_set_colour", matrix, range));
+    if (!colour_spec_default(matrix, range)) {
+        const char *why = h->cfg.pixel_depth == 10 ? "a pixel_depth 10 handle" : h->cfg.interpolation == 0 ? "INTER_NEAREST" :
+                          h->cfg.resample != VSTAB_RESAMPLE_DEFAULT ? resample_name(h->cfg.resample) : h->calibrated ? "a calibrated handle (vstab_set_input_calibration)" :
+                          h->pinhole ? "a calibrated handle (vstab_set_input_pinhole)" : h->border_mode != VSTAB_BORDER_CONSTANT ? "a border mode other than VSTAB_BORDER_CONSTANT (vstab_set_border_mode)" : nullptr;
+        if (why) return fail(VSTAB_ERR_UNSUPPORTED, n + "a colour spec other than (VSTAB_COLOUR_CVTCOLOR, VSTAB_RANGE_LIMITED) is served for 8-bit pixels with INTER_LINEAR, the constant border and an ideal lens; this handle has " + why);
+    }
+    h->colour_matrix = matrix, h->colour_range = range;
     return VSTAB_OK;
 }
 

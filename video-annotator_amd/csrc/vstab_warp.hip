@@ -6,6 +6,7 @@
 // HBM-bound gather work (no MFMA): coalesced wide stores, enough workgroups to fill 256 CUs, the map in registers.
 #include <cstdlib>
 
+#include "vstab_colour.hpp"
 #include "vstab_warp_host.hpp"
 
 namespace vstab {
@@ -115,6 +116,10 @@ vstab_status check_warp_bilinear(const WarpRequest &q, WarpArgs &a) {
     if (!ptr_aligned(q.uv, 2) || q.pitch_uv % 2) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: chroma plane must be 2-B aligned");
     if (q.rot_bottom && !map_mode_fish_to_pinhole(q.map_mode))
         return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12_rs: the per-row warp exists for the fisheye -> pinhole modes (0, 1, 5) only");
+    // a colour spec (ENTRY_COLOUR, a pull of a handle with vstab_set_colour): behind every other check, under the entry point's own name
+    VSTAB_TRY(check_colour_spec(q.e.name, q.colour_matrix, q.colour_range));
+    if (q.colour() && q.out_format == VSTAB_OUT_NV12_PLANAR)
+        return fail(VSTAB_ERR_INVALID, std::string(q.e.name) + ": VSTAB_OUT_NV12_PLANAR converts nothing, a colour spec belongs to VSTAB_OUT_BGR8 and VSTAB_OUT_NV12");
     fill_warp_args(a, q, true);
     return VSTAB_OK;
 }
@@ -131,6 +136,8 @@ vstab_status launch_warp_bilinear(const WarpArgs &a, const WarpRequest &q) {
     const StagedOffsets32 off32 = staged_offsets32(a.pitch_y, a.pitch_uv, a.sh);
     const bool small_pitch = off32.rows, stage32 = off32.chroma;
     const bool plain = q.map_mode == VSTAB_MAP_CREATEMAP_CL && !nv12_out && !q.qmap && !q.rot_bottom;
+    // (the direct-gather kernel has cvtColor's constants: with a colour spec only the tiled kernels serve, staged or not)
+    if (q.colour() && !small_pitch) return fail(VSTAB_ERR_UNSUPPORTED, std::string(q.e.name) + ": source planes of 4 GiB and more are served with (VSTAB_COLOUR_CVTCOLOR, VSTAB_RANGE_LIMITED) only");
     if (!plain && !small_pitch) return fail(VSTAB_ERR_INVALID, "vstab_warp_nv12: source pitch too large for this mode");
     if (planar) {  // the plane-wise warp: its own kernel (vstab_warp_planar.hip); the map is always evaluated
         if (q.qmap) return fail(VSTAB_ERR_UNSUPPORTED, "vstab_warp_nv12_mapped: the quantised map holds no chroma positions -- VSTAB_OUT_NV12_PLANAR goes through vstab_warp_nv12_ex");
@@ -141,6 +148,10 @@ vstab_status launch_warp_bilinear(const WarpArgs &a, const WarpRequest &q) {
     }
     const bool vec_ok = ptr_aligned(a.dst, 4) && a.pitch_dst % 4 == 0 && (!nv12_out || (ptr_aligned(a.dst_uv, 4) && a.pitch_dst_uv % 4 == 0));
     const bool src_vec_ok = stage32 && ptr_aligned(a.y, 8) && ptr_aligned(a.uv, 8) && a.pitch_y % 8 == 0 && a.pitch_uv % 8 == 0;  // 8-byte staging loads
+    if (q.colour()) {
+        if (q.qmap || q.rot_bottom || q.dist) return fail(VSTAB_ERR_UNSUPPORTED, std::string(q.e.name) + ": a colour spec is served with one rotation per frame through an ideal lens, the map evaluated");
+        return launch_warp_fused_colour(a, q.params, q.map_mode, nv12_out, src_vec_ok, vec_ok, colour_coefficients(q.colour_matrix, q.colour_range), st);
+    }
     bool direct = !small_pitch || (plain && !stage32);
 #ifdef VSTAB_DEV
     static const int variant = getenv("VSTAB_WARP_VARIANT") ? atoi(getenv("VSTAB_WARP_VARIANT")) : 2;
@@ -195,6 +206,14 @@ vstab_status vstab_warp_nv12_ex(const void *y, size_t pitch_y, const void *uv, s
                                 void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
     return warp_nv12({.e = ENTRY_EX, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .map_mode = map_mode,
                       .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw, .dh = dh, .stream = stream});
+}
+
+vstab_status vstab_warp_nv12_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17], int map_mode,
+                                    int out_format, void *dst, size_t pitch_dst, void *dst_uv, size_t pitch_dst_uv, int dw, int dh, int matrix, int range,
+                                    void *stream) {
+    return warp_nv12({.e = ENTRY_COLOUR, .y = y, .pitch_y = pitch_y, .uv = uv, .pitch_uv = pitch_uv, .sw = sw, .sh = sh, .params = params, .map_mode = map_mode,
+                      .out_format = out_format, .dst = dst, .pitch_dst = pitch_dst, .dst_uv = dst_uv, .pitch_dst_uv = pitch_dst_uv, .dw = dw, .dh = dh, .stream = stream,
+                      .colour_matrix = matrix, .colour_range = range});
 }
 
 vstab_status vstab_warp_nv12_rs(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],

@@ -33,6 +33,8 @@ struct FusedArgs {
     int ablate;                  // timing-only ablations (wrong pixels): 1 linear map, 2 xor blend, 4 raw conversion, 8 no stores
     int lds_pad;                 // experiment: dwords added to the LDS row pitch of the staged box (multiple of 4)
 #endif
+    // the COLOUR kernels' coefficients (vstab_warp_nv12_colour); behind everything the other kernels read, which stays where it was
+    ColourCoef col;
 };
 
 // One NV12 tap converted with the cvtColor arithmetic; outside the source -> 0 (cv::remap BORDER_CONSTANT).
@@ -62,6 +64,31 @@ __device__ __forceinline__ uint32_t gather_pixel(const WarpArgs &a, int sx, int 
     return B | (G << 8) | (R << 16);
 }
 
+// The same two with a colour spec's coefficients (the COLOUR kernels' gather path)
+__device__ __forceinline__ void fetch_tap(const WarpArgs &a, const ColourCoef &k, int X, int Y, int &b, int &g, int &r) {
+    if ((unsigned)X < (unsigned)a.sw && (unsigned)Y < (unsigned)a.sh) {
+        const int yv = a.y[(size_t)Y * a.pitch_y + X];
+        const uint16_t c = *reinterpret_cast<const uint16_t *>(a.uv + (size_t)(Y >> 1) * a.pitch_uv + (X & ~1));
+        yuv_to_bgr(k, yv, chroma_term(k, c & 255, c >> 8), b, g, r);
+    } else {
+        b = g = r = 0;
+    }
+}
+__device__ __forceinline__ uint32_t gather_pixel(const WarpArgs &a, const ColourCoef &k, int sx, int sy) {
+    const int X = sx >> 5, Y = sy >> 5;
+    const uint32_t fx = sx & 31, fy = sy & 31;
+    const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
+    int b0, g0, r0, b1, g1, r1, b2, g2, r2, b3, g3, r3;
+    fetch_tap(a, k, X, Y, b0, g0, r0);
+    fetch_tap(a, k, X + 1, Y, b1, g1, r1);
+    fetch_tap(a, k, X, Y + 1, b2, g2, r2);
+    fetch_tap(a, k, X + 1, Y + 1, b3, g3, r3);
+    const uint32_t B = (uint32_t)(b0 * w00 + b1 * w01 + b2 * w10 + b3 * w11 + 512) >> 10;
+    const uint32_t G = (uint32_t)(g0 * w00 + g1 * w01 + g2 * w10 + g3 * w11 + 512) >> 10;
+    const uint32_t R = (uint32_t)(r0 * w00 + r1 * w01 + r2 * w10 + r3 * w11 + 512) >> 10;
+    return B | (G << 8) | (R << 16);
+}
+
 __device__ __forceinline__ uint32_t load_u32_bytes(const uint8_t *p, int valid) {
     uint32_t v = 0;
     for (int i = 0; i < 4; i++)
@@ -72,6 +99,9 @@ __device__ __forceinline__ uint32_t load_u32_bytes(const uint8_t *p, int valid) 
 // dist: k1..k4 of the input lens (map modes 1 and 2, BGR8, no quantised map, one rotation per frame: the MAP_FISHD_* kernels), else null
 vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int map_mode, bool nv12_out, bool src_vec_ok, bool dst_vec_ok,
                                const void *qmap, int qpitch, const float *rot_bottom, hipStream_t st, const float *dist = nullptr);
+// the COLOUR kernels (map modes 0 .. 5, one rotation per frame, the map always evaluated, BGR8 or NV12 through BGR); col: a spec's coefficients
+vstab_status launch_warp_fused_colour(const WarpArgs &a, const float params[17], int map_mode, bool nv12_out, bool src_vec_ok, bool dst_vec_ok, const ColourCoef &col,
+                                      hipStream_t st);
 // the 10-bit pixel path on the LDS-tiled kernel: a.y / a.uv = P010 planes (16-byte aligned, pitches multiples of 16), a.dst = 16-bit
 // BGR with a.pitch_dst bytes per row; map modes 0 / 1 only.  src_vec_ok false: nothing is staged, every pixel is sampled from global memory
 vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int map_mode, int blend, const float *rot_bottom, bool p010_out, bool src_vec_ok,

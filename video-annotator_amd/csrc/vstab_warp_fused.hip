@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 
 #include "vstab_device10.hpp"
@@ -150,9 +151,24 @@ __device__ __forceinline__ int edge_wave(const WarpArgs &a, const int bx0, const
 // LDS budget: the caller then covers the tile with two tiles of half the height.
 // DEPTH 8: NV12 bytes in, the reference's pixel path.  DEPTH 10 (FMT 2, BASELINE config 5): P010 words in, the box staged as
 // B | G << 10 | R << 20 dwords -- the same 4-byte LDS pixel -- blended by BLEND (vstab_device10.hpp), 16-bit BGR out.
-template <int RWB, int RW, int MODE, int FMT, bool CACHED, bool SPLIT, int DEPTH = 8, int BLEND = 0>
+// The COLOUR kernels' coefficients, read from the kernel argument (FusedArgs is the kernel's one argument, so ta.col stands at offsetof(FusedArgs, col)
+// of the kernarg segment) where they are used and not before: the compiler loads every field of a kernel argument in the entry block, and
+// fourteen more scalars alive across the probe and the map phase are what the 64 x 32 kernels have no scalar registers for (mode 1 to BGR
+// spilled two of them into a vector register, and that one to scratch).  The empty asm pins the loads behind the phase before them.
+__device__ __forceinline__ ColourCoef colour_coef_here() {
+    typedef const __attribute__((address_space(4))) char *KernargBytes;
+    KernargBytes p = (KernargBytes)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    const __attribute__((address_space(4))) int *q = (const __attribute__((address_space(4))) int *)(p + offsetof(FusedArgs, col));
+    static_assert(sizeof(ColourCoef) == 14 * sizeof(int), "ColourCoef is fourteen ints");
+    return {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11], q[12], q[13]};
+}
+
+// COLOUR (vstab_warp_nv12_colour): the convert phase, the gather path and the NV12 store read their coefficients from ta.col (colour_coef_here).
+template <int RWB, int RW, int MODE, int FMT, bool CACHED, bool SPLIT, int DEPTH = 8, int BLEND = 0, bool COLOUR = false>
 __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, const int x0, const int y0) {
     static_assert((DEPTH == 8 && FMT < 2) || (DEPTH == 10 && FMT >= 2), "10-bit pixels leave as 16-bit BGR (FMT 2) or P010 planes (FMT 3)");
+    static_assert(!COLOUR || (DEPTH == 8 && !CACHED && MODE <= MAP_CREATEMAP_CL_OPENCL), "a colour spec: 8 bits, the map evaluated, one rotation through an ideal lens");
     using SrcVec = typename std::conditional<DEPTH == 10, uint4, uint2>::type;  // 8 source samples of a block row
     constexpr uint32_t BPS = DEPTH == 10 ? 2 : 1;                              // bytes per sample
     constexpr int TH = 4 * RW;
@@ -260,6 +276,8 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
     VSTAB_STAMP(3);
     // ---- convert: cvtColor once per source pixel, BGRx dwords to LDS --------------------------------------------
     if (use_lds) {
+        ColourCoef kc = {};
+        if constexpr (COLOUR) kc = colour_coef_here();
 #pragma unroll
         for (int it = 0; it < STAGE_MAX; it++) {
             if (ldsoff[it] >= ZERO_BLOCK) {
@@ -308,13 +326,22 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
 #pragma unroll
                 for (int half = 0; half < 2; half++) {
                     const uint32_t cw = half ? uvw[it].y : uvw[it].x, ya = half ? y0w[it].y : y0w[it].x, yb = half ? y1w[it].y : y1w[it].x;
-                    const ChromaTerm c0 = chroma_term_folded(cw & 255, (cw >> 8) & 255);
-                    const ChromaTerm c1 = chroma_term_folded((cw >> 16) & 255, cw >> 24);
                     uint4 r0, r1;
-                    r0.x = pack_bgrx(ya & 255, c0), r0.y = pack_bgrx((ya >> 8) & 255, c0);
-                    r0.z = pack_bgrx((ya >> 16) & 255, c1), r0.w = pack_bgrx(ya >> 24, c1);
-                    r1.x = pack_bgrx(yb & 255, c0), r1.y = pack_bgrx((yb >> 8) & 255, c0);
-                    r1.z = pack_bgrx((yb >> 16) & 255, c1), r1.w = pack_bgrx(yb >> 24, c1);
+                    if constexpr (COLOUR) {
+                        const ChromaTerm c0 = chroma_term_folded(kc, cw & 255, (cw >> 8) & 255);
+                        const ChromaTerm c1 = chroma_term_folded(kc, (cw >> 16) & 255, cw >> 24);
+                        r0.x = pack_bgrx(kc, ya & 255, c0), r0.y = pack_bgrx(kc, (ya >> 8) & 255, c0);
+                        r0.z = pack_bgrx(kc, (ya >> 16) & 255, c1), r0.w = pack_bgrx(kc, ya >> 24, c1);
+                        r1.x = pack_bgrx(kc, yb & 255, c0), r1.y = pack_bgrx(kc, (yb >> 8) & 255, c0);
+                        r1.z = pack_bgrx(kc, (yb >> 16) & 255, c1), r1.w = pack_bgrx(kc, yb >> 24, c1);
+                    } else {
+                        const ChromaTerm c0 = chroma_term_folded(cw & 255, (cw >> 8) & 255);
+                        const ChromaTerm c1 = chroma_term_folded((cw >> 16) & 255, cw >> 24);
+                        r0.x = pack_bgrx(ya & 255, c0), r0.y = pack_bgrx((ya >> 8) & 255, c0);
+                        r0.z = pack_bgrx((ya >> 16) & 255, c1), r0.w = pack_bgrx(ya >> 24, c1);
+                        r1.x = pack_bgrx(yb & 255, c0), r1.y = pack_bgrx((yb >> 8) & 255, c0);
+                        r1.z = pack_bgrx((yb >> 16) & 255, c1), r1.w = pack_bgrx(yb >> 24, c1);
+                    }
                     *reinterpret_cast<uint4 *>(d + 4 * half) = r0;
                     *reinterpret_cast<uint4 *>(d + pw + 4 * half) = r1;
                 }
@@ -395,7 +422,9 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
 #pragma unroll
                     for (int k = 1; k < RW; k++) sx = j == k ? qxb[k] : sx, sy = j == k ? qyb[k] : sy;
                     if ((slow >> j) & 1u) {
-                        const uint32_t v = DEPTH == 10 ? gather_pixel10<BLEND>(a, sx - QB, sy - QB) : gather_pixel_far(a, sx - QB, sy - QB);
+                        uint32_t v;
+                        if constexpr (COLOUR) v = gather_pixel_far(a, colour_coef_here(), sx - QB, sy - QB);
+                        else v = DEPTH == 10 ? gather_pixel10<BLEND>(a, sx - QB, sy - QB) : gather_pixel_far(a, sx - QB, sy - QB);
 #pragma unroll
                         for (int k = 0; k < RW; k++) out[k] = j == k ? v : out[k];
                     }
@@ -501,8 +530,8 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                 else if (lane == nfull && rem) {
                     uint32_t l4 = 4u * (uint32_t)lane;
                     // formed here: hoisted out of the tile loop as a 64-bit offset, it is the one value the 64 x 32 kernels of the distorted-lens
-                    // modes have no register for (8 bytes of scratch)
-                    if constexpr (ModeTraits<BASE>::dist) asm volatile("" : "+v"(l4));
+                    // modes have no register for (8 bytes of scratch); nor has the COLOUR kernel of mode 1
+                    if constexpr (ModeTraits<BASE>::dist || COLOUR) asm volatile("" : "+v"(l4));
                     for (int i = 0; i < rem; i++) o[l4 + i] = (d >> (8 * i)) & 255;
                 }
             } else if (col_live) {
@@ -512,11 +541,15 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
     } else {
         // NV12 output: luma for every pixel, chroma from the even-row / even-column pixels; four lanes' bytes are
         // collected in the first lane of each quad (DPP quad_perm) and stored as one dword
+        ColourCoef kc = {};
+        if constexpr (COLOUR) kc = colour_coef_here();
 #pragma unroll
         for (int j = 0; j < RW; j++) {
             const int y = y0 + wave * RW + j;
             if (y >= a.dh) break;  // uniform
-            const uint32_t yb = bgr_to_y(out[j]);
+            uint32_t yb;
+            if constexpr (COLOUR) yb = bgr_to_y(kc, out[j]);
+            else yb = bgr_to_y(out[j]);
             const uint32_t y1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0x55, 0xf, 0xf, true);
             const uint32_t y2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0xaa, 0xf, 0xf, true);
             const uint32_t y3 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0xff, 0xf, 0xf, true);
@@ -530,7 +563,9 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                 }
             }
             if (!(y & 1)) {
-                const uint32_t cb = bgr_to_uv(out[j]);
+                uint32_t cb;
+                if constexpr (COLOUR) cb = bgr_to_uv(kc, out[j]);
+                else cb = bgr_to_uv(out[j]);
                 const uint32_t c2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)cb, 0xaa, 0xf, 0xf, true);
                 const uint32_t cw = cb | (c2 << 16);
                 uint8_t *c = a.dst_uv + ((size_t)(uint32_t)(y >> 1) * a.pitch_dst_uv + (uint32_t)x);
@@ -558,7 +593,7 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
 // the per-row kernels (nine matrix entries per row on top of everything else) spilled inside the map phase (4K, reference
 // arithmetic, per row: 36.1 -> 33.2 us; per frame in the pipeline 26.8 -> 27.0 k frames/s, three alternating runs on one box).
 // Their LDS holds them to four waves per SIMD anyway; 80 registers still leave room for a tracker wave (123) beside them.
-template <int RWB, int MODE, int FMT, bool CACHED, int DEPTH = 8, int BLEND = 0>
+template <int RWB, int MODE, int FMT, bool CACHED, int DEPTH = 8, int BLEND = 0, bool COLOUR = false>
 __global__ void __launch_bounds__(256, DEPTH == 10 ? 5 : (RWB == 8 || map_mode_is_rs(MODE)) ? VSTAB_WARP_WAVES - 1 : VSTAB_WARP_WAVES) k_warp_fused(FusedArgs ta) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     constexpr int TH = 4 * RWB, TS = TH / 2;
@@ -573,14 +608,14 @@ __global__ void __launch_bounds__(256, DEPTH == 10 ? 5 : (RWB == 8 || map_mode_i
         x0 = (idx - row * ta.tiles_x) * 64, ys = y_lo + row * TH;
         // a tall tile whose box is over the LDS budget (the image centre, where the lens compresses most) is done as two
         // half-height tiles, one after the other
-        n_half = warp_tile<RWB, RWB, MODE, FMT, CACHED, true, DEPTH, BLEND>(ta, smem, x0, ys) ? 0 : 2;
+        n_half = warp_tile<RWB, RWB, MODE, FMT, CACHED, true, DEPTH, BLEND, COLOUR>(ta, smem, x0, ys) ? 0 : 2;
     } else {
         const int i2 = idx - n_tall, row = i2 / ta.tiles_x;
         x0 = (i2 - row * ta.tiles_x) * 64, ys = y_sp + row * TS, n_half = 1;
         if (ys >= y_hi) return;  // uniform for the workgroup (before any barrier)
     }
 #pragma unroll 1
-    for (int i = 0; i < n_half; i++) warp_tile<RWB, RWB / 2, MODE, FMT, CACHED, false, DEPTH, BLEND>(ta, smem, x0, ys + i * TS);
+    for (int i = 0; i < n_half; i++) warp_tile<RWB, RWB / 2, MODE, FMT, CACHED, false, DEPTH, BLEND, COLOUR>(ta, smem, x0, ys + i * TS);
 }
 
 }  // namespace vstab
@@ -626,16 +661,15 @@ vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int 
     return VSTAB_OK;
 }
 
-vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int map_mode, bool nv12_out, bool src_vec_ok, bool dst_vec_ok,
-                               const void *qmap, int qpitch, const float *rot_bottom, hipStream_t st, const float *dist) {
-    FusedArgs ta;
-    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, qmap, qpitch, rot_bottom, dist);
-#ifdef VSTAB_DEV
-    ta.timing = g_dev_timing;
-    static const int ablate = getenv("VSTAB_ABLATE") ? atoi(getenv("VSTAB_ABLATE")) : 0;
-    ta.ablate = ablate;
-    ta.lds_pad = getenv("VSTAB_LDS_PAD") ? atoi(getenv("VSTAB_LDS_PAD")) & ~3 : 0;
-#endif
+// The tile shape, LDS budget and schedule of an 8-bit launch, ta filled but for them: rows per wave (8: 64 x 32 tiles, 4: 64 x 16), the LDS bytes, the grid.
+// per_frame_ideal: one rotation per frame through an ideal lens with the map evaluated -- what the cost-weighted bands are made for.
+struct FusedShape {
+    int rwb;
+    size_t lds_bytes;
+    unsigned grid;
+};
+static FusedShape fused_shape(FusedArgs &ta, const float params[17], int map_mode, bool per_frame_ideal) {
+    const WarpArgs &a = ta.w;
     // Tile shape: 64 x 32 output pixels and 40 KB of LDS (4 workgroups per CU) when that gives the 1024 workgroup
     // slots of the chip a few rounds of tiles; 64 x 16 with 20 KB (8 per CU: 2048 slots, a 1080p output in ONE round)
     // for small outputs.
@@ -649,16 +683,32 @@ vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int ma
     if (const char *e = getenv("VSTAB_LDS_KB")) lds_kb = atoi(e);
     if (const char *e = getenv("VSTAB_TAIL_ROUNDS")) tail_rounds = atof(e);
 #endif
-    const size_t lds_bytes = (size_t)lds_kb * 1024;
     // Bands by cost instead of by rows (vstab_warp_bands.hpp) where the launch has several rounds of tiles -- the condition that turns the
     // tail on; a launch that is resident at once gains nothing from it -- and the kernel knows dead tiles (warp_tile: DEAD)
-    bool weighted = tail_rounds > 0.0 && !dist && !qmap && !rot_bottom &&
+    bool weighted = tail_rounds > 0.0 && per_frame_ideal &&
                     (map_mode == MAP_CREATEMAP_CL || map_mode == MAP_FISH_TO_RECT || map_mode == MAP_CREATEMAP_CL_OPENCL);
 #ifdef VSTAB_DEV
     if (const char *e = getenv("VSTAB_BANDS")) weighted = weighted && atoi(e) != 0;
 #endif
     static BandCache band_cache;
-    const dim3 grid(weighted ? band_cache.schedule(ta, params, map_mode, rwb, lds_kb, tail_rounds) : tile_schedule(ta, rwb, lds_kb, tail_rounds));
+    const unsigned grid = weighted ? band_cache.schedule(ta, params, map_mode, rwb, lds_kb, tail_rounds) : tile_schedule(ta, rwb, lds_kb, tail_rounds);
+    return {rwb, (size_t)lds_kb * 1024, grid};
+}
+
+vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int map_mode, bool nv12_out, bool src_vec_ok, bool dst_vec_ok,
+                               const void *qmap, int qpitch, const float *rot_bottom, hipStream_t st, const float *dist) {
+    FusedArgs ta;
+    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, qmap, qpitch, rot_bottom, dist);
+#ifdef VSTAB_DEV
+    ta.timing = g_dev_timing;
+    static const int ablate = getenv("VSTAB_ABLATE") ? atoi(getenv("VSTAB_ABLATE")) : 0;
+    ta.ablate = ablate;
+    ta.lds_pad = getenv("VSTAB_LDS_PAD") ? atoi(getenv("VSTAB_LDS_PAD")) & ~3 : 0;
+#endif
+    const FusedShape shape = fused_shape(ta, params, map_mode, !dist && !qmap && !rot_bottom);
+    const int rwb = shape.rwb;
+    const size_t lds_bytes = shape.lds_bytes;
+    const dim3 grid(shape.grid);
     if (dist) {  // the input lens's polynomial: modes 1 / 2 to BGR8, the map always evaluated (the caller has checked all of it)
         if (nv12_out || qmap || rot_bottom) return fail(VSTAB_ERR_INVALID, "launch_warp_fused: the distorted-lens kernels emit BGR8 from one rotation per frame");
         with_dist_mode(map_mode, [&](auto mode) {
@@ -686,6 +736,25 @@ vstab_status launch_warp_fused(const WarpArgs &a, const float params[17], int ma
     return VSTAB_OK;
 }
 
+
+// The same launch with a colour spec: the COLOUR instantiations, both tile heights, map modes 0 .. 5, BGR8 and NV12 through BGR.
+vstab_status launch_warp_fused_colour(const WarpArgs &a, const float params[17], int map_mode, bool nv12_out, bool src_vec_ok, bool dst_vec_ok, const ColourCoef &col,
+                                      hipStream_t st) {
+    FusedArgs ta;
+    fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, nullptr, 0, nullptr);
+    ta.col = col;
+    const FusedShape shape = fused_shape(ta, params, map_mode, true);
+    with_map_mode(map_mode, [&](auto mode) {
+        with_either<8, 4>(shape.rwb == 8, [&](auto rows) {
+            with_either<1, 0>(nv12_out, [&](auto fmt) {
+                launch_kernel(k_warp_fused<decltype(rows)::value, decltype(mode)::value, decltype(fmt)::value, false, 8, 0, true>, dim3(shape.grid), dim3(256),
+                              shape.lds_bytes, st, ta);
+            });
+        });
+    });
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
 
 // Kernels of this translation unit are one code object, loaded by the runtime at the first launch of any of them.  Touching one of them
 // here (vstab_preload_kernels) moves that load to a moment the caller chooses.

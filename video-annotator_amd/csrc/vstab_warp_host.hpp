@@ -59,6 +59,7 @@ inline void fill_fused_args(FusedArgs &ta, const WarpArgs &a, const float params
 #ifdef VSTAB_DEV
     ta.timing = nullptr, ta.ablate = 0, ta.lds_pad = 0;
 #endif
+    ta.col = ColourCoef{};  // (read by the COLOUR kernels alone: launch_warp_fused_colour)
 }
 
 // staged_offsets32 -- when the staged loads of the tiled kernels (warp_tile, warp_tile_planar) may form their row offsets in 32 bits.

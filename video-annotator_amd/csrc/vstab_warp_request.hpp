@@ -36,6 +36,7 @@ constexpr WarpEntry ENTRY_CUBIC = {"vstab_warp_nv12_cubic", "the cubic warp ", B
 constexpr WarpEntry ENTRY_CUBIC_BORDER = {"vstab_warp_nv12_cubic_border", "", BORDER_ENTRY_OWN, LENS_IDEAL};
 constexpr WarpEntry ENTRY_LANCZOS4 = {"vstab_warp_nv12_lanczos4", "the Lanczos warp ", BORDER_ENTRY_NONE, LENS_IDEAL};
 constexpr WarpEntry ENTRY_LANCZOS4_BORDER = {"vstab_warp_nv12_lanczos4_border", "", BORDER_ENTRY_OWN, LENS_IDEAL};
+constexpr WarpEntry ENTRY_COLOUR = {"vstab_warp_nv12_colour", nullptr, BORDER_ENTRY_NONE, LENS_IDEAL};  // a bilinear entry point with a colour spec
 constexpr WarpEntry ENTRY_KEEP = {"vstab_warp_nv12_keep", "the keep-edge warp ", BORDER_ENTRY_NONE, LENS_IDEAL};
 
 // One call of an 8-bit NV12 warp.  Null / zero / default where the entry point has no such argument.
@@ -64,7 +65,12 @@ struct WarpRequest {
     size_t pitch_dst_uv;
     int dw, dh;
     void *stream;
+    // the colour spec (vstab_warp_nv12_colour, vstab_set_colour); the default: cvtColor's arithmetic, every kernel as it was.  The routing does
+    // not look at it: a spec other than the default is served by the COLOUR instantiations of the route's own fused kernel, or refused
+    // (launch_warp_bilinear).
+    int colour_matrix = VSTAB_COLOUR_CVTCOLOR, colour_range = VSTAB_RANGE_LIMITED;
 
+    bool colour() const { return colour_matrix != VSTAB_COLOUR_CVTCOLOR || colour_range != VSTAB_RANGE_LIMITED; }
     bool planar() const { return out_format == VSTAB_OUT_NV12_PLANAR; }
     int lens() const {
         if (dist) return LENS_FISHEYE;

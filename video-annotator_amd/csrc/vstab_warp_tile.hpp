@@ -76,6 +76,11 @@ __device__ __forceinline__ uint32_t gather_pixel_far(const WarpArgs &a, int sx, 
     if (!(X < a.sw && X + 1 >= 0 && Y < a.sh && Y + 1 >= 0)) return 0;
     return gather_pixel(a, sx, sy);
 }
+__device__ __forceinline__ uint32_t gather_pixel_far(const WarpArgs &a, const ColourCoef &k, int sx, int sy) {
+    const int X = sx >> 5, Y = sy >> 5;
+    if (!(X < a.sw && X + 1 >= 0 && Y < a.sh && Y + 1 >= 0)) return 0;
+    return gather_pixel(a, k, sx, sy);
+}
 
 // Trips of the staging loop: STAGE_MAX * 256 blocks of 8 x 2 source pixels must cover the largest box the tile's LDS
 // budget admits (40 KB for kernels whose tall tiles have 32 rows, 24 KB for 16; half-height tiles have smaller boxes).
