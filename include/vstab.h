@@ -1163,6 +1163,58 @@ VSTAB_API vstab_status vstab_warp_nv12_colour(const void *y, size_t pitch_y, con
  * frame that carries a readout_rotation is refused and consumed by the converting pulls, as INTER_NEAREST does. */
 VSTAB_API vstab_status vstab_set_colour(vstab_handle *h, int matrix, int range);
 
+/* ---- Colour matrix and range at 10 bits -----------------------------------------------------------------------------------------------
+ * The P010 <-> 16-bit BGR conversion of the 10-bit path (vstab_warp_p010, vstab_warp_p010_planes, vstab_cvt_bgr16_p010, the pulls of a
+ * pixel_depth 10 handle) as a choice of the same (matrix, range) pair, with a coefficient table of its own.  (CVTCOLOR, FULL) does not
+ * exist and is refused.
+ *   table     (VSTAB_COLOUR_CVTCOLOR, VSTAB_RANGE_LIMITED) is the 8-bit cvtColor row with yoff = 64: the 10-bit path's arithmetic as it
+ *             always was, byte for byte, and the default everywhere.  The other six specs use the formulas of "Colour matrix and range"
+ *             with the 10-bit scales: limited range sy = 1023/876, sc = 1023/896, yoff = 64; full range sy = sc = 1, yoff = 0.  The chroma
+ *             offset is 512.  rint is round half to even of the exact rational value.  E.g. BT2020 limited: CY 1224536, CUB 2252416,
+ *             CUG -197003, CVG -684025, CVR 1765394; BT709 full: 1048576, 1945738, -196424, -490864, 1651297.
+ *   forward   y10 = word >> 6 (the low six bits of a P010 word are ignored), u = (U >> 6) - 512, v = (V >> 6) - 512, and with
+ *             y = max(y10 - yoff, 0) CY + 2^19, the sums exact (64-bit):
+ *               B = sat10((y + CUB u) >> 20), G = sat10((y + CVG v + CUG u) >> 20), R = sat10((y + CVR v) >> 20)
+ *   inverse   B, G, R in [0, 1023] (the low ten bits of a 16-bit container):
+ *               Y = sat10((CRY R + CGY G + CBY B + 2^19 + (yoff << 20)) >> 20)
+ *               U = sat10((CRU R + CGU G + CBU B + 2^19 + (512 << 20)) >> 20)
+ *               V = sat10((CBU R + CGV G + CBV B + 2^19 + (512 << 20)) >> 20)
+ *             chroma from the top-left pixel of each 2 x 2 block; the output word is value << 6.  The saturation is part of the definition:
+ *             with full range, pure blue's U is 1024 before it.
+ *   overflow  Every coefficient is below 2^23 (the largest is 2 252 416).  The luma term is at most 1023 CY <= 1.2527e9; every chroma term
+ *             with the luma offset folded in, 2^19 - yoff CY + C uv, lies in [-1.2311e9, 1.0732e9].  Each fits int32 and 24-bit multiplies
+ *             hold; only their single sum can pass 2^31 (2.3259e9 at most, BT2020 limited), and whenever it does the true channel is at
+ *             least 2048 and saturates to 1023, which is what a saturating 32-bit add gives; the sum never goes below -1.24e9.  Inverse sums
+ *             are at most 2^30 (U of pure blue at full range).
+ * A 10-bit warp with a colour spec is the warp with the conversion exchanged: the frame converted with the spec's forward form, then the
+ * bilinear remap with the chosen blend; planes out are that frame through the inverse of the same spec. */
+/* out = the 14 integers of a spec's 10-bit row, in vstab_colour_coefficients' order (host memory; no device needed).  Same refusals. */
+VSTAB_API vstab_status vstab_colour_coefficients10(int matrix, int range, int32_t out[14]);
+/* vstab_warp_p010 / vstab_warp_p010_planes with a colour spec: the argument lists, routing and refusals of their twins (VSTAB_ERR_UNSUPPORTED
+ * from _planes included); a bad spec is VSTAB_ERR_INVALID under the entry point's own name, behind the other argument checks and before
+ * any launch.  (CVTCOLOR, LIMITED) launches the twin's kernel.  vstab_warp_p010_planar converts nothing and has no such twin. */
+VSTAB_API vstab_status vstab_warp_p010_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                              const float params[17], const float *rot_bottom, int map_mode, int blend, void *dst_bgr16,
+                                              size_t pitch_dst, int dst_width, int dst_height, int matrix, int range, void *stream);
+VSTAB_API vstab_status vstab_warp_p010_planes_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                                     const float params[17], const float *rot_bottom, int map_mode, int blend, void *dst_y,
+                                                     size_t pitch_dst_y, void *dst_uv, size_t pitch_dst_uv, int dst_width, int dst_height,
+                                                     int matrix, int range, void *stream);
+/* The forward conversion as an operator: P010 planes (even width and height in [2, 32767]; luma 2-byte, chroma pairs 4-byte aligned) to 16-bit
+ * BGR, values 0..1023, 2-byte aligned rows of at least 6 * width bytes. */
+VSTAB_API vstab_status vstab_cvt_p010_bgr16_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int width, int height, void *dst_bgr16,
+                                                   size_t pitch_dst, int matrix, int range, void *stream);
+/* vstab_cvt_bgr16_p010 with a colour spec (any size). */
+VSTAB_API vstab_status vstab_cvt_bgr16_p010_colour(const void *src_bgr16, size_t pitch_src, int width, int height, void *dst_y, size_t pitch_y,
+                                                   void *dst_uv, size_t pitch_uv, int matrix, int range, void *stream);
+/* The colour spec of a pixel_depth 10 handle, from the next pull on; it may change between pulls.  vstab_pull_frame_bgr16 converts with the
+ * spec (vstab_warp_p010_colour); vstab_pull_frame_p010 converts with it on both of its routes, which give the same bytes
+ * (vstab_warp_p010_planes_colour, or vstab_warp_p010_colour into the handle's buffer and vstab_cvt_bgr16_p010_colour);
+ * vstab_pull_frame_p010_planar converts nothing and is served unchanged.  Frames that carry a readout_rotation are warped per row, as they
+ * are without a spec.  Refused, the handle unchanged: a NULL handle and a bad spec (VSTAB_ERR_INVALID); an 8-bit handle
+ * (VSTAB_ERR_UNSUPPORTED: its spec is vstab_set_colour's). */
+VSTAB_API vstab_status vstab_set_colour10(vstab_handle *h, int matrix, int range);
+
 /* Synchronises the stream, folds all pending event pairs into the sums and returns them. */
 VSTAB_API vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out);
 

@@ -175,6 +175,12 @@ SIGNATURES = {
     "vstab_cvt_bgr_nv12_colour": (_i, [_vp, _sz, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_warp_nv12_colour": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _vp]),
     "vstab_set_colour": (_i, [_vp, _i, _i]),
+    "vstab_colour_coefficients10": (_i, [_i, _i, _c.POINTER(_c.c_int32)]),
+    "vstab_warp_p010_colour": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "vstab_warp_p010_planes_colour": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "vstab_cvt_p010_bgr16_colour": (_i, [_vp, _sz, _vp, _sz, _i, _i, _vp, _sz, _i, _i, _vp]),
+    "vstab_cvt_bgr16_p010_colour": (_i, [_vp, _sz, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_set_colour10": (_i, [_vp, _i, _i]),
     "vstab_warp_nv12_rs_ex": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_set_readout_warp": (_i, [_vp, _i]),
     "vstab_remap_cubic_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _ip, _vp, _sz, _i, _i, _vp]),
@@ -384,6 +390,13 @@ def colour_coefficients(matrix, range_):
     """vstab_colour_coefficients: CY, CUB, CUG, CVG, CVR, yoff, CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV of a spec (host only) -> int32 array of 14."""
     out = np.zeros(14, np.int32)
     _check(_L.vstab_colour_coefficients(int(matrix), int(range_), out.ctypes.data_as(_c.POINTER(_c.c_int32))), "vstab_colour_coefficients")
+    return out
+
+
+def colour_coefficients10(matrix, range_):
+    """vstab_colour_coefficients10: the same 14 integers of a spec's row in the 10-bit table (host only) -> int32 array of 14."""
+    out = np.zeros(14, np.int32)
+    _check(_L.vstab_colour_coefficients10(int(matrix), int(range_), out.ctypes.data_as(_c.POINTER(_c.c_int32))), "vstab_colour_coefficients10")
     return out
 
 
@@ -709,23 +722,27 @@ def warp_nv12_rs(nv12, params, rot_bottom, dw, dh, mode=MAP_CREATEMAP_CL, out_fo
 BLEND_EXACT, BLEND_FP16 = 0, 1
 
 
-def warp_p010(y, uv, params, dw, dh, rot_bottom=None, mode=MAP_CREATEMAP_CL, blend=BLEND_EXACT, out=None):
+def warp_p010(y, uv, params, dw, dh, rot_bottom=None, mode=MAP_CREATEMAP_CL, blend=BLEND_EXACT, out=None, colour=None):
     """vstab_warp_p010 (config 5): y (h, w) / uv (h/2, w) int16-or-uint16 CUDA tensors holding P010 samples ->
-    (dh, dw, 3) int16 tensor of BGR values 0..1023."""
+    (dh, dw, 3) int16 tensor of BGR values 0..1023.  colour=(matrix, range): vstab_warp_p010_colour."""
     import torch
     h, w = y.shape
     p = np.ascontiguousarray(params, np.float32)
     rb = None if rot_bottom is None else np.ascontiguousarray(rot_bottom, np.float32).reshape(9)
     if out is None:
         out = torch.empty((dh, dw, 3), dtype=torch.int16, device=y.device)
-    _check(_L.vstab_warp_p010(y.data_ptr(), y.stride(0) * 2, uv.data_ptr(), uv.stride(0) * 2, w, h, _fptr(p), None if rb is None else _fptr(rb),
-                              int(mode), int(blend), out.data_ptr(), out.stride(0) * 2, dw, dh, _stream()), "vstab_warp_p010")
+    args = (y.data_ptr(), y.stride(0) * 2, uv.data_ptr(), uv.stride(0) * 2, w, h, _fptr(p), None if rb is None else _fptr(rb), int(mode), int(blend), out.data_ptr(),
+            out.stride(0) * 2, dw, dh)
+    if colour is None:
+        _check(_L.vstab_warp_p010(*args, _stream()), "vstab_warp_p010")
+    else:
+        _check(_L.vstab_warp_p010_colour(*args, int(colour[0]), int(colour[1]), _stream()), "vstab_warp_p010_colour")
     return out
 
 
-def warp_p010_planes(y, uv, params, dw, dh, rot_bottom=None, mode=MAP_CREATEMAP_CL, blend=BLEND_EXACT, out_y=None, out_uv=None):
+def warp_p010_planes(y, uv, params, dw, dh, rot_bottom=None, mode=MAP_CREATEMAP_CL, blend=BLEND_EXACT, out_y=None, out_uv=None, colour=None):
     """vstab_warp_p010_planes: the 10-bit warp with P010 planes out, one kernel.  Raises VstabError (ERR_UNSUPPORTED) for planes the
-    tiled kernel cannot take."""
+    tiled kernel cannot take.  colour=(matrix, range): vstab_warp_p010_planes_colour."""
     import torch
     h, w = y.shape
     p = np.ascontiguousarray(params, np.float32)
@@ -734,9 +751,12 @@ def warp_p010_planes(y, uv, params, dw, dh, rot_bottom=None, mode=MAP_CREATEMAP_
         out_y = torch.empty((dh, dw), dtype=torch.int16, device=y.device)
     if out_uv is None:
         out_uv = torch.empty(((dh + 1) // 2, 2 * ((dw + 1) // 2)), dtype=torch.int16, device=y.device)
-    _check(_L.vstab_warp_p010_planes(y.data_ptr(), y.stride(0) * 2, uv.data_ptr(), uv.stride(0) * 2, w, h, _fptr(p), None if rb is None else _fptr(rb),
-                                     int(mode), int(blend), out_y.data_ptr(), out_y.stride(0) * 2, out_uv.data_ptr(), out_uv.stride(0) * 2, dw, dh, _stream()),
-           "vstab_warp_p010_planes")
+    args = (y.data_ptr(), y.stride(0) * 2, uv.data_ptr(), uv.stride(0) * 2, w, h, _fptr(p), None if rb is None else _fptr(rb), int(mode), int(blend),
+            out_y.data_ptr(), out_y.stride(0) * 2, out_uv.data_ptr(), out_uv.stride(0) * 2, dw, dh)
+    if colour is None:
+        _check(_L.vstab_warp_p010_planes(*args, _stream()), "vstab_warp_p010_planes")
+    else:
+        _check(_L.vstab_warp_p010_planes_colour(*args, int(colour[0]), int(colour[1]), _stream()), "vstab_warp_p010_planes_colour")
     return out_y, out_uv
 
 
@@ -756,17 +776,34 @@ def warp_p010_planar(y, uv, params, dw, dh, rot_bottom=None, mode=MAP_CREATEMAP_
     return out_y, out_uv
 
 
-def cvt_bgr16_p010(bgr16, out_y=None, out_uv=None):
-    """vstab_cvt_bgr16_p010: (h, w, 3) int16 CUDA tensor of BGR values 0..1023 -> P010 planes (h, w) and (ceil(h/2), 2 * ceil(w/2)), int16 bit patterns."""
+def cvt_bgr16_p010(bgr16, out_y=None, out_uv=None, colour=None):
+    """vstab_cvt_bgr16_p010: (h, w, 3) int16 CUDA tensor of BGR values 0..1023 -> P010 planes (h, w) and (ceil(h/2), 2 * ceil(w/2)), int16 bit patterns.
+    colour=(matrix, range): vstab_cvt_bgr16_p010_colour."""
     import torch
     h, w = bgr16.shape[:2]
     if out_y is None:
         out_y = torch.empty((h, w), dtype=torch.int16, device=bgr16.device)
     if out_uv is None:
         out_uv = torch.empty(((h + 1) // 2, 2 * ((w + 1) // 2)), dtype=torch.int16, device=bgr16.device)
-    _check(_L.vstab_cvt_bgr16_p010(bgr16.data_ptr(), bgr16.stride(0) * 2, w, h, out_y.data_ptr(), out_y.stride(0) * 2, out_uv.data_ptr(), out_uv.stride(0) * 2,
-                                   _stream()), "vstab_cvt_bgr16_p010")
+    args = (bgr16.data_ptr(), bgr16.stride(0) * 2, w, h, out_y.data_ptr(), out_y.stride(0) * 2, out_uv.data_ptr(), out_uv.stride(0) * 2)
+    if colour is None:
+        _check(_L.vstab_cvt_bgr16_p010(*args, _stream()), "vstab_cvt_bgr16_p010")
+    else:
+        _check(_L.vstab_cvt_bgr16_p010_colour(*args, int(colour[0]), int(colour[1]), _stream()), "vstab_cvt_bgr16_p010_colour")
     return out_y, out_uv
+
+
+def cvt_p010_bgr16(y, uv, colour=None, out=None):
+    """vstab_cvt_p010_bgr16_colour: P010 planes y (h, w) / uv (h/2, w), int16 CUDA tensors -> (h, w, 3) int16 tensor of BGR values 0..1023.
+    colour=(matrix, range); None: (COLOUR_CVTCOLOR, RANGE_LIMITED), the 10-bit path's own arithmetic."""
+    import torch
+    h, w = y.shape
+    m, r = (COLOUR_CVTCOLOR, RANGE_LIMITED) if colour is None else colour
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.int16, device=y.device)
+    _check(_L.vstab_cvt_p010_bgr16_colour(y.data_ptr(), y.stride(0) * 2, uv.data_ptr(), uv.stride(0) * 2, w, h, out.data_ptr(), out.stride(0) * 2, int(m), int(r),
+                                          _stream()), "vstab_cvt_p010_bgr16_colour")
+    return out
 
 
 def time_next_launch(start_event, stop_event):
@@ -1273,6 +1310,10 @@ class Stabilizer:
     def set_colour(self, matrix, range_=RANGE_LIMITED):
         """vstab_set_colour: the colour spec of the converting pulls (BGR, host, NV12 through BGR), from the next pull on."""
         _check(_L.vstab_set_colour(self._h, int(matrix), int(range_)), "vstab_set_colour")
+
+    def set_colour10(self, matrix, range_=RANGE_LIMITED):
+        """vstab_set_colour10: the colour spec of a pixel_depth 10 handle's converting pulls (16-bit BGR, P010), from the next pull on."""
+        _check(_L.vstab_set_colour10(self._h, int(matrix), int(range_)), "vstab_set_colour10")
 
     def set_border_mode(self, border_mode):
         """vstab_set_border_mode: cv::remap's borderMode for the frames pulled from now on."""

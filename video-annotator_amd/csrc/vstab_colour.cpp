@@ -23,22 +23,20 @@ bool colour_spec_valid(int matrix, int range) {
     return !(matrix == VSTAB_COLOUR_CVTCOLOR && range == VSTAB_RANGE_FULL);
 }
 
-ColourCoef colour_coefficients(int matrix, int range) {
-    if (matrix == VSTAB_COLOUR_CVTCOLOR) return {CY, CUB, CUG, CVG, CVR, 16, CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV};
-    // Kr = kr / D, Kb = kb / D, Kg = kg / D; sy = yn / yd, sc = cn / cd.  The largest product below, 2^21 * 255 * D * D, is 5.4e16.
+// The six derived rows at either depth: sy = yn / yd, sc = cn / cd and the luma offset are what the depth and the range decide.
+// Kr = kr / D, Kb = kb / D, Kg = kg / D.  The largest product below, 2^21 * 1023 * D * D, is 2.2e17.
+static ColourCoef derive(int matrix, int64_t yn, int64_t yd, int64_t cn, int64_t cd, int yoff) {
     const int64_t D = 10000, one = 1 << 20;
     const int64_t kr = matrix == VSTAB_COLOUR_BT601 ? 2990 : matrix == VSTAB_COLOUR_BT709 ? 2126 : 2627;
     const int64_t kb = matrix == VSTAB_COLOUR_BT601 ? 1140 : matrix == VSTAB_COLOUR_BT709 ? 722 : 593;
     const int64_t kg = D - kr - kb;
-    const bool full = range == VSTAB_RANGE_FULL;
-    const int64_t yn = full ? 1 : 255, yd = full ? 1 : 219, cn = full ? 1 : 255, cd = full ? 1 : 224;
     ColourCoef c;
     c.cy = (int)rint_ratio(one * yn, yd);
     c.cvr = (int)rint_ratio(one * cn * 2 * (D - kr), cd * D);
     c.cub = (int)rint_ratio(one * cn * 2 * (D - kb), cd * D);
     c.cug = -(int)rint_ratio(one * cn * 2 * kb * (D - kb), cd * D * kg);
     c.cvg = -(int)rint_ratio(one * cn * 2 * kr * (D - kr), cd * D * kg);
-    c.yoff = full ? 0 : 16;
+    c.yoff = yoff;
     c.cry = (int)rint_ratio(one * kr * yd, D * yn);
     c.cgy = (int)rint_ratio(one * kg * yd, D * yn);
     c.cby = (int)rint_ratio(one * kb * yd, D * yn);
@@ -48,6 +46,20 @@ ColourCoef colour_coefficients(int matrix, int range) {
     c.cgv = -(int)rint_ratio(one * kg * cd, 2 * (D - kr) * cn);
     c.cbv = -(int)rint_ratio(one * kb * cd, 2 * (D - kr) * cn);
     return c;
+}
+
+ColourCoef colour_coefficients(int matrix, int range) {
+    if (matrix == VSTAB_COLOUR_CVTCOLOR) return {CY, CUB, CUG, CVG, CVR, 16, CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV};
+    if (range == VSTAB_RANGE_FULL) return derive(matrix, 1, 1, 1, 1, 0);
+    return derive(matrix, 255, 219, 255, 224, 16);
+}
+
+// The 10-bit table (include/vstab.h, "Colour matrix and range at 10 bits"): cvtColor's row with the luma offset of 10-bit video, which is the
+// 10-bit path's arithmetic as it always was; the other six with the 10-bit scales 1023/876 and 1023/896.
+ColourCoef colour_coefficients10(int matrix, int range) {
+    if (matrix == VSTAB_COLOUR_CVTCOLOR) return {CY, CUB, CUG, CVG, CVR, 64, CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV};
+    if (range == VSTAB_RANGE_FULL) return derive(matrix, 1, 1, 1, 1, 0);
+    return derive(matrix, 1023, 876, 1023, 896, 64);
 }
 
 vstab_status check_colour_spec(const char *n, int matrix, int range) {
@@ -64,11 +76,19 @@ vstab_status check_colour_spec(const char *n, int matrix, int range) {
 
 using namespace vstab;
 
-extern "C" vstab_status vstab_colour_coefficients(int matrix, int range, int32_t out[14]) {
-    if (!out) return fail(VSTAB_ERR_INVALID, "vstab_colour_coefficients: null pointer");
-    VSTAB_TRY(check_colour_spec("vstab_colour_coefficients", matrix, range));
-    const ColourCoef c = colour_coefficients(matrix, range);
+static vstab_status write_coefficients(const char *n, int matrix, int range, bool ten, int32_t out[14]) {
+    if (!out) return fail(VSTAB_ERR_INVALID, std::string(n) + ": null pointer");
+    VSTAB_TRY(check_colour_spec(n, matrix, range));
+    const ColourCoef c = ten ? colour_coefficients10(matrix, range) : colour_coefficients(matrix, range);
     const int v[14] = {c.cy, c.cub, c.cug, c.cvg, c.cvr, c.yoff, c.cry, c.cgy, c.cby, c.cru, c.cgu, c.cbu, c.cgv, c.cbv};
     for (int i = 0; i < 14; i++) out[i] = v[i];
     return VSTAB_OK;
+}
+
+extern "C" vstab_status vstab_colour_coefficients(int matrix, int range, int32_t out[14]) {
+    return write_coefficients("vstab_colour_coefficients", matrix, range, false, out);
+}
+
+extern "C" vstab_status vstab_colour_coefficients10(int matrix, int range, int32_t out[14]) {
+    return write_coefficients("vstab_colour_coefficients10", matrix, range, true, out);
 }

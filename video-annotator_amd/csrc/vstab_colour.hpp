@@ -11,5 +11,7 @@ bool colour_spec_valid(int matrix, int range);
 vstab_status check_colour_spec(const char *n, int matrix, int range);
 // the block of a valid spec, in vstab_colour_coefficients' order
 ColourCoef colour_coefficients(int matrix, int range);
+// the 10-bit path's block of the same spec, in vstab_colour_coefficients10's order ("Colour matrix and range at 10 bits")
+ColourCoef colour_coefficients10(int matrix, int range);
 
 }  // namespace vstab

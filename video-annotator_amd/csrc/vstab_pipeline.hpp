@@ -332,6 +332,8 @@ struct vstab_handle {
     // vstab_set_colour: the colour spec of the converting pulls (BGR, NV12 through BGR), from the next pull on
     int colour_matrix = VSTAB_COLOUR_CVTCOLOR, colour_range = VSTAB_RANGE_LIMITED;
     bool colour() const { return colour_matrix != VSTAB_COLOUR_CVTCOLOR || colour_range != VSTAB_RANGE_LIMITED; }
+    // vstab_set_colour10: the colour spec of a pixel_depth 10 handle's converting pulls (16-bit BGR, P010 through BGR), from the next pull on
+    int colour10_matrix = VSTAB_COLOUR_CVTCOLOR, colour10_range = VSTAB_RANGE_LIMITED;
     int readout_warp = VSTAB_READOUT_REFUSE;  // vstab_set_readout_warp: applies from the next pull
     long warps_from_cache = 0;
     PinnedBuf marker_pts;           // vstab_config.debug: rotating sets of marker centres, read by the kernel in place

@@ -183,20 +183,30 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
         return VSTAB_OK;
     }
 #endif
-    if (out_format == OUT_BGR16)
-        return vstab_warp_p010(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, P.dst, P.pitch_dst, ow, oh, H->stream);
+    // The converting 10-bit pulls with a colour spec (vstab_set_colour10) go through the _colour twins; without one they call what they always called,
+    // messages included.
+    const int m10 = H->colour10_matrix, r10 = H->colour10_range;
+    const bool c10 = !colour_spec_default(m10, r10);
+    const auto warp_bgr16 = [&](void *dst, size_t pitch_dst) {
+        return c10 ? vstab_warp_p010_colour(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, dst, pitch_dst, ow, oh, m10, r10, H->stream)
+                   : vstab_warp_p010(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, dst, pitch_dst, ow, oh, H->stream);
+    };
+    if (out_format == OUT_BGR16) return warp_bgr16(P.dst, P.pitch_dst);
     if (out_format == OUT_P010_PLANAR)
         return vstab_warp_p010_planar(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, P.dst, P.pitch_dst, P.dst_uv,
                                       P.pitch_dst_uv, ow, oh, H->stream);
     if (out_format == OUT_P010) {
-        vstab_status st = vstab_warp_p010_planes(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, P.dst, P.pitch_dst,
-                                                 P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
+        vstab_status st = c10 ? vstab_warp_p010_planes_colour(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, P.dst, P.pitch_dst,
+                                                              P.dst_uv, P.pitch_dst_uv, ow, oh, m10, r10, H->stream)
+                              : vstab_warp_p010_planes(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, P.dst, P.pitch_dst, P.dst_uv,
+                                                       P.pitch_dst_uv, ow, oh, H->stream);
         if (st == VSTAB_ERR_UNSUPPORTED) {
             const size_t bpitch = ((size_t)ow * 6 + 255) & ~(size_t)255;
             st = H->bgr16_out.ensure(bpitch * oh);
+            if (st == VSTAB_OK) st = warp_bgr16(H->bgr16_out.p, bpitch);
             if (st == VSTAB_OK)
-                st = vstab_warp_p010(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, H->bgr16_out.p, bpitch, ow, oh, H->stream);
-            if (st == VSTAB_OK) st = vstab_cvt_bgr16_p010(H->bgr16_out.p, bpitch, ow, oh, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, H->stream);
+                st = c10 ? vstab_cvt_bgr16_p010_colour(H->bgr16_out.p, bpitch, ow, oh, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, m10, r10, H->stream)
+                         : vstab_cvt_bgr16_p010(H->bgr16_out.p, bpitch, ow, oh, P.dst, P.pitch_dst, P.dst_uv, P.pitch_dst_uv, H->stream);
         }
         return st;
     }
@@ -365,6 +375,16 @@ vstab_status vstab_set_colour(vstab_handle *h, int matrix, int range) {
         if (why) return fail(VSTAB_ERR_UNSUPPORTED, n + "a colour spec other than (VSTAB_COLOUR_CVTCOLOR, VSTAB_RANGE_LIMITED) is served for 8-bit pixels with INTER_LINEAR, the constant border and an ideal lens; this handle has " + why);
     }
     h->colour_matrix = matrix, h->colour_range = range;
+    return VSTAB_OK;
+}
+
+// The colour spec of a pixel_depth 10 handle's converting pulls: every 10-bit warp kernel has its COLOUR form, so nothing about the handle refuses.
+vstab_status vstab_set_colour10(vstab_handle *h, int matrix, int range) {
+    if (!h) return fail(VSTAB_ERR_INVALID, "vstab_set_colour10: null handle");
+    VSTAB_TRY(check_colour_spec("vstab_set_colour10", matrix, range));
+    if (h->cfg.pixel_depth != 10)
+        return fail(VSTAB_ERR_UNSUPPORTED, "vstab_set_colour10: served for pixel_depth 10 handles; the colour spec of an 8-bit handle is set with vstab_set_colour");
+    h->colour10_matrix = matrix, h->colour10_range = range;
     return VSTAB_OK;
 }
 

@@ -33,7 +33,7 @@ struct FusedArgs {
     int ablate;                  // timing-only ablations (wrong pixels): 1 linear map, 2 xor blend, 4 raw conversion, 8 no stores
     int lds_pad;                 // experiment: dwords added to the LDS row pitch of the staged box (multiple of 4)
 #endif
-    // the COLOUR kernels' coefficients (vstab_warp_nv12_colour); behind everything the other kernels read, which stays where it was
+    // the COLOUR kernels' coefficients (vstab_warp_nv12_colour; at 10 bits vstab_warp_p010[_planes]_colour); behind everything the other kernels read, which stays where it was
     ColourCoef col;
 };
 
@@ -105,7 +105,7 @@ vstab_status launch_warp_fused_colour(const WarpArgs &a, const float params[17],
 // the 10-bit pixel path on the LDS-tiled kernel: a.y / a.uv = P010 planes (16-byte aligned, pitches multiples of 16), a.dst = 16-bit
 // BGR with a.pitch_dst bytes per row; map modes 0 / 1 only.  src_vec_ok false: nothing is staged, every pixel is sampled from global memory
 vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int map_mode, int blend, const float *rot_bottom, bool p010_out, bool src_vec_ok,
-                                 bool dst_vec_ok, hipStream_t st);
+                                 bool dst_vec_ok, hipStream_t st, const ColourCoef *col = nullptr);  // col: a spec's 10-bit row, the COLOUR kernels
 
 // the plane-wise warp (vstab_warp_planar.hip): a.dst / a.dst_uv = the output planes; depth 8 (NV12 bytes) or 10 (P010 words)
 // dist: as for launch_warp_fused (depth 8 only)

@@ -168,7 +168,8 @@ __device__ __forceinline__ ColourCoef colour_coef_here() {
 template <int RWB, int RW, int MODE, int FMT, bool CACHED, bool SPLIT, int DEPTH = 8, int BLEND = 0, bool COLOUR = false>
 __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, const int x0, const int y0) {
     static_assert((DEPTH == 8 && FMT < 2) || (DEPTH == 10 && FMT >= 2), "10-bit pixels leave as 16-bit BGR (FMT 2) or P010 planes (FMT 3)");
-    static_assert(!COLOUR || (DEPTH == 8 && !CACHED && MODE <= MAP_CREATEMAP_CL_OPENCL), "a colour spec: 8 bits, the map evaluated, one rotation through an ideal lens");
+    static_assert(!COLOUR || (DEPTH == 8 && !CACHED && MODE <= MAP_CREATEMAP_CL_OPENCL) || (DEPTH == 10 && map_mode_fish_to_pinhole(map_mode_base(MODE))),
+                  "a colour spec: at 8 bits the map evaluated, one rotation through an ideal lens; at 10 bits the 10-bit kernels' modes (vstab_warp_p010_colour)");
     using SrcVec = typename std::conditional<DEPTH == 10, uint4, uint2>::type;  // 8 source samples of a block row
     constexpr uint32_t BPS = DEPTH == 10 ? 2 : 1;                              // bytes per sample
     constexpr int TH = 4 * RW;
@@ -301,7 +302,11 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                     const uint32_t cw[4] = {uvw[it].x, uvw[it].y, uvw[it].z, uvw[it].w};
 #pragma unroll
                     for (int half = 0; half < 2; half++) {
-                        const ChromaTerm c0 = chroma_term10(cw[2 * half]), c1 = chroma_term10(cw[2 * half + 1]);
+                        // (COLOUR: the same calls with the spec's coefficients in front)
+                        const auto term = [&](uint32_t w) { if constexpr (COLOUR) return chroma_term10(kc, w); else return chroma_term10(w); };
+                        const auto pack_bgr10 = [&](int yv, const ChromaTerm &c) { if constexpr (COLOUR) return vstab::pack_bgr10(kc, yv, c); else return vstab::pack_bgr10(yv, c); };
+                        const auto pack_bgr10h = [&](int yv, const ChromaTerm &c) { if constexpr (COLOUR) return vstab::pack_bgr10h(kc, yv, c); else return vstab::pack_bgr10h(yv, c); };
+                        const ChromaTerm c0 = term(cw[2 * half]), c1 = term(cw[2 * half + 1]);
                         if constexpr (PIX8) {  // four pixels of each row as halves: two 16-byte stores per row
                             const uint32_t la = ya[2 * half], lb = ya[2 * half + 1], ma = yb[2 * half], mb = yb[2 * half + 1];
                             const uint2 a0 = pack_bgr10h((int)((la & 0xffffu) >> 6), c0), a1 = pack_bgr10h((int)(la >> 22), c0);
@@ -423,7 +428,14 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                     for (int k = 1; k < RW; k++) sx = j == k ? qxb[k] : sx, sy = j == k ? qyb[k] : sy;
                     if ((slow >> j) & 1u) {
                         uint32_t v;
-                        if constexpr (COLOUR) v = gather_pixel_far(a, colour_coef_here(), sx - QB, sy - QB);
+                        if constexpr (COLOUR && DEPTH == 10) {
+                            // the six forward coefficients in vector registers: as scalars beside the per-row kernels' matrices they cost the
+                            // kernel of mode 5 per row with planes out a private segment (36 bytes, never touched); this rare path has the room
+                            ColourCoef kg = colour_coef_here();
+                            asm volatile("" : "+v"(kg.cy), "+v"(kg.cub), "+v"(kg.cug), "+v"(kg.cvg), "+v"(kg.cvr), "+v"(kg.yoff));
+                            v = gather_pixel10<BLEND>(a, kg, sx - QB, sy - QB);
+                        }
+                        else if constexpr (COLOUR) v = gather_pixel_far(a, colour_coef_here(), sx - QB, sy - QB);
                         else v = DEPTH == 10 ? gather_pixel10<BLEND>(a, sx - QB, sy - QB) : gather_pixel_far(a, sx - QB, sy - QB);
 #pragma unroll
                         for (int k = 0; k < RW; k++) out[k] = j == k ? v : out[k];
@@ -461,12 +473,16 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
         // P010 planes (the 10-bit path's encoder hand-off; definition: include/vstab.h, vstab_cvt_bgr16_p010): luma word for every
         // pixel, (U, V) words from the even-row / even-column pixels; four lanes' words are collected in the first lane of each
         // quad (DPP quad_perm) and stored as 8 bytes
+        ColourCoef kc = {};
+        if constexpr (COLOUR) kc = colour_coef_here();
 #pragma unroll
         for (int j = 0; j < RW; j++) {
             const int y = y0 + wave * RW + j;
             if (y >= a.dh) break;  // uniform
             const int B = (int)(out[j] & 1023u), G = (int)((out[j] >> 10) & 1023u), R = (int)(out[j] >> 20);
-            const uint32_t yb = (uint32_t)sat10((CRY * R + CGY * G + CBY * B + (1 << 19) + (64 << 20)) >> 20) << 6;
+            uint32_t yb;
+            if constexpr (COLOUR) yb = bgr10_to_y(kc, B, G, R) << 6;
+            else yb = (uint32_t)sat10((CRY * R + CGY * G + CBY * B + (1 << 19) + (64 << 20)) >> 20) << 6;
             const uint32_t y1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0x55, 0xf, 0xf, true);
             const uint32_t y2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0xaa, 0xf, 0xf, true);
             const uint32_t y3 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0xff, 0xf, 0xf, true);
@@ -480,9 +496,13 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                 }
             }
             if (!(y & 1)) {
-                const uint32_t U = (uint32_t)sat10((CRU * R + CGU * G + CBU * B + (1 << 19) + (512 << 20)) >> 20) << 6;
-                const uint32_t V = (uint32_t)sat10((CBU * R + CGV * G + CBV * B + (1 << 19) + (512 << 20)) >> 20) << 6;
-                const uint32_t cb = U | (V << 16);
+                uint32_t cb;
+                if constexpr (COLOUR) cb = bgr10_to_uv(kc, B, G, R) << 6;
+                else {
+                    const uint32_t U = (uint32_t)sat10((CRU * R + CGU * G + CBU * B + (1 << 19) + (512 << 20)) >> 20) << 6;
+                    const uint32_t V = (uint32_t)sat10((CBU * R + CGV * G + CBV * B + (1 << 19) + (512 << 20)) >> 20) << 6;
+                    cb = U | (V << 16);
+                }
                 const uint32_t c2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)cb, 0xaa, 0xf, 0xf, true);
                 uint16_t *c = reinterpret_cast<uint16_t *>(a.dst_uv + (size_t)(uint32_t)(y >> 1) * a.pitch_dst_uv) + x;
                 if (!(lane & 3) && col_live) {
@@ -631,10 +651,12 @@ extern "C" __attribute__((visibility("default"))) void vstab_dev_set_timing(void
 
 // The 10-bit pixel path on the same kernel (DEPTH 10): fisheye -> pinhole maps (modes 0 / 1 / 5, optionally a rotation per
 // output row), both blends; called by vstab_warp_p010 when the planes allow 16-byte staging loads.
+// col: a spec's row of the 10-bit table (vstab_warp_p010_colour), the COLOUR instantiations; null: the default kernels.  One tile shape, LDS budget and schedule.
 vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int map_mode, int blend, const float *rot_bottom, bool p010_out, bool src_vec_ok,
-                                 bool dst_vec_ok, hipStream_t st) {
+                                 bool dst_vec_ok, hipStream_t st, const ColourCoef *col) {
     FusedArgs ta;
     fill_fused_args(ta, a, params, src_vec_ok, dst_vec_ok, nullptr, 0, rot_bottom);
+    if (col) ta.col = *col;
     // 64 x 32 tiles, 40 KB of LDS.  The fp16 blend stages 8-byte pixels (three halves): half as many fit, and a tall tile whose box is
     // over that is done as two half-height tiles (SPLIT) -- measured faster than 64 x 16 tiles throughout (47.3 against 49.1 us at 4K).
     const int lds_kb = 40;
@@ -648,11 +670,14 @@ vstab_status launch_warp_fused10(const WarpArgs &a, const float params[17], int 
     with_map_mode(map_mode, rot_bottom != nullptr, [&](auto mode) {
         with_either<VSTAB_BLEND_FP16, VSTAB_BLEND_EXACT>(half, [&](auto blend_c) {
             with_either<3, 2>(p010_out, [&](auto fmt) {
-                constexpr int MODE = decltype(mode)::value;
-                if constexpr (map_mode_fish_to_pinhole(map_mode_base(MODE)))
-                    launch_kernel(k_warp_fused<8, MODE, decltype(fmt)::value, false, 10, decltype(blend_c)::value>, grid, dim3(256), lds_bytes, st, ta);
-                else  // the callers check the mode first; no kernel exists, and nothing is launched
-                    status = fail(VSTAB_ERR_INVALID, "launch_warp_fused10: the 10-bit tiled kernels serve map modes 0, 1 and 5 only");
+                with_bool(col != nullptr, [&](auto colour) {
+                    constexpr int MODE = decltype(mode)::value;
+                    if constexpr (map_mode_fish_to_pinhole(map_mode_base(MODE)))
+                        launch_kernel(k_warp_fused<8, MODE, decltype(fmt)::value, false, 10, decltype(blend_c)::value, decltype(colour)::value>, grid, dim3(256),
+                                      lds_bytes, st, ta);
+                    else  // the callers check the mode first; no kernel exists, and nothing is launched
+                        status = fail(VSTAB_ERR_INVALID, "launch_warp_fused10: the 10-bit tiled kernels serve map modes 0, 1 and 5 only");
+                });
             });
         });
     });

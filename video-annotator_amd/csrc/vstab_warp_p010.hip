@@ -14,6 +14,7 @@
 // Direct gather, two output pixels per thread: this path is about the format, the 8-bit kernel carries the rate.
 #include <cstdlib>
 
+#include "vstab_colour.hpp"
 #include "vstab_device10.hpp"
 #include "vstab_warp_host.hpp"
 
@@ -28,10 +29,12 @@ struct P010Args {
     float rs_d[9];  // rotation of the last output row minus rotation of the first (all zero: one rotation)
     float rs_den;   // (float)max(dh - 1, 1)
     int rs;
+    // the COLOUR kernels' coefficients (vstab_warp_p010_colour); behind everything the other kernels read, which stays where it was
+    ColourCoef col;
 };
 
 // the four taps of one output pixel, converted and blended; sx, sy = cvRound(32 * map)
-template <int BLEND>
+template <int BLEND, bool COLOUR>
 __device__ __forceinline__ void sample10(const P010Args &a, float ax, float ay, uint16_t *o) {
     const bool far = !(fabsf(ax) < 1073741824.0f) || !(fabsf(ay) < 1073741824.0f);
     const int sx = (int)__builtin_rintf(ax), sy = (int)__builtin_rintf(ay);
@@ -40,8 +43,13 @@ __device__ __forceinline__ void sample10(const P010Args &a, float ax, float ay, 
     if (!(far || X >= a.sw || X + 1 < 0 || Y >= a.sh || Y + 1 < 0)) {
         const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
         int b0, g0, r0, b1, g1, r1, b2, g2, r2, b3, g3, r3;
-        fetch_row10(a, X, Y, b0, g0, r0, b1, g1, r1);
-        fetch_row10(a, X, Y + 1, b2, g2, r2, b3, g3, r3);
+        if constexpr (COLOUR) {
+            fetch_row10(a, a.col, X, Y, b0, g0, r0, b1, g1, r1);
+            fetch_row10(a, a.col, X, Y + 1, b2, g2, r2, b3, g3, r3);
+        } else {
+            fetch_row10(a, X, Y, b0, g0, r0, b1, g1, r1);
+            fetch_row10(a, X, Y + 1, b2, g2, r2, b3, g3, r3);
+        }
         if constexpr (BLEND == VSTAB_BLEND_FP16) {
             B = blend_fp16(b0, b1, b2, b3, w00, w01, w10, w11);
             G = blend_fp16(g0, g1, g2, g3, w00, w01, w10, w11);
@@ -58,7 +66,8 @@ __device__ __forceinline__ void sample10(const P010Args &a, float ax, float ay, 
 // A thread owns two vertically adjacent output pixels, so that the map of the fisheye-input modes runs as packed fp32
 // (map_pixel32_x2: the hand-scheduled IEEE sequences of the 8-bit kernel, two pixels per instruction; 32 * map, an
 // exact power-of-two scaling of the map the definition quantises).
-template <int MODE, int BLEND>
+// COLOUR (vstab_warp_p010_colour): the taps are converted with the coefficients of a.col, a spec's row of the 10-bit table.
+template <int MODE, int BLEND, bool COLOUR = false>
 __global__ void __launch_bounds__(256) k_warp_p010(P010Args a) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 2;
     if (x >= a.dw || y0 >= a.dh) return;
@@ -99,7 +108,7 @@ __global__ void __launch_bounds__(256) k_warp_p010(P010Args a) {
 #pragma unroll
     for (int r = 0; r < 2; r++) {
         if (y0 + r >= a.dh) break;
-        sample10<BLEND>(a, ax[r], ay[r], reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(a.dst) + (size_t)(y0 + r) * a.pitch_dst) + 3 * (size_t)x);
+        sample10<BLEND, COLOUR>(a, ax[r], ay[r], reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(a.dst) + (size_t)(y0 + r) * a.pitch_dst) + 3 * (size_t)x);
     }
 }
 
@@ -125,6 +134,47 @@ __global__ void __launch_bounds__(256) k_cvt_bgr10_p010(const uint8_t *__restric
     if (!(y & 1)) {
         const int U = sat10((CRU * R0 + CGU * G0 + CBU * B0 + half + (512 << 20)) >> 20), V = sat10((CBU * R0 + CGV * G0 + CBV * B0 + half + (512 << 20)) >> 20);
         *reinterpret_cast<uint32_t *>(duv + (size_t)(y >> 1) * pitch_uv + (size_t)px * 2) = ((uint32_t)U << 6) | ((uint32_t)V << 22);
+    }
+}
+
+// k_cvt_bgr10_p010 with a colour spec: the inverse of "Colour matrix and range at 10 bits" (include/vstab.h), k: the spec's row.
+__global__ void __launch_bounds__(256) k_cvt_bgr10_p010_colour(const uint8_t *__restrict__ src, size_t pitch_src, int w, int h, uint8_t *__restrict__ dy,
+                                                               size_t pitch_y, uint8_t *__restrict__ duv, size_t pitch_uv, ColourCoef k) {
+    const int px = (blockIdx.x * 64 + (threadIdx.x & 63)) * 2, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (px >= w || y >= h) return;
+    const uint16_t *s = reinterpret_cast<const uint16_t *>(src + (size_t)y * pitch_src) + 3 * (size_t)px;
+    const bool two = px + 1 < w;
+    // (the definition takes B, G, R in [0, 1023]; the low ten bits of a container are what every sum below is sized for)
+    const int B0 = s[0] & 1023, G0 = s[1] & 1023, R0 = s[2] & 1023, B1 = two ? s[3] & 1023 : 0, G1 = two ? s[4] & 1023 : 0, R1 = two ? s[5] & 1023 : 0;
+    const uint32_t y0 = bgr10_to_y(k, B0, G0, R0), y1 = bgr10_to_y(k, B1, G1, R1);
+    uint16_t *oy = reinterpret_cast<uint16_t *>(dy + (size_t)y * pitch_y) + px;
+    if (two && (reinterpret_cast<uintptr_t>(oy) & 3) == 0) *reinterpret_cast<uint32_t *>(oy) = (y0 << 6) | (y1 << 22);
+    else {
+        oy[0] = (uint16_t)(y0 << 6);
+        if (two) oy[1] = (uint16_t)(y1 << 6);
+    }
+    if (!(y & 1)) *reinterpret_cast<uint32_t *>(duv + (size_t)(y >> 1) * pitch_uv + (size_t)px * 2) = bgr10_to_uv(k, B0, G0, R0) << 6;
+}
+
+// k_cvt_p010_bgr16_colour -- P010 planes -> BGR (0..1023 in 16-bit containers) with a colour spec: the forward conversion of "Colour matrix
+// and range at 10 bits", the low six bits of every source word ignored.  One thread converts the two pixels of a chroma pair: one luma
+// dword and one chroma dword in, 12 bytes out, as three dwords where the row is 4-byte aligned, as six words otherwise.
+__global__ void __launch_bounds__(256) k_cvt_p010_bgr16_colour(const uint8_t *__restrict__ sy, size_t pitch_y, const uint8_t *__restrict__ suv, size_t pitch_uv,
+                                                               int w, int h, uint8_t *__restrict__ dst, size_t pitch_dst, ColourCoef k) {
+    const int px = (blockIdx.x * 64 + (threadIdx.x & 63)) * 2, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (px >= w || y >= h) return;  // (w is even: a pair is whole)
+    const uint32_t yy = reinterpret_cast<const Dword1 *>(sy + (size_t)y * pitch_y + (size_t)px * 2)->v;  // (a luma row is 2-byte aligned)
+    const uint32_t cw = *reinterpret_cast<const uint32_t *>(suv + (size_t)(y >> 1) * pitch_uv + (size_t)px * 2);
+    int b0, g0, r0, b1, g1, r1;
+    convert_tap10(k, yy & 0xffffu, cw, true, b0, g0, r0);
+    convert_tap10(k, yy >> 16, cw, true, b1, g1, r1);
+    uint8_t *o = dst + (size_t)y * pitch_dst + (size_t)px * 6;
+    if ((reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+        uint32_t *o4 = reinterpret_cast<uint32_t *>(o);
+        o4[0] = (uint32_t)b0 | ((uint32_t)g0 << 16), o4[1] = (uint32_t)r0 | ((uint32_t)b1 << 16), o4[2] = (uint32_t)g1 | ((uint32_t)r1 << 16);
+    } else {
+        uint16_t *o2 = reinterpret_cast<uint16_t *>(o);
+        o2[0] = (uint16_t)b0, o2[1] = (uint16_t)g0, o2[2] = (uint16_t)r0, o2[3] = (uint16_t)b1, o2[4] = (uint16_t)g1, o2[5] = (uint16_t)r1;
     }
 }
 
@@ -185,20 +235,38 @@ bool source_16(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv) {
 
 // The same warp with P010 planes out, fused (FMT 3 of the tiled kernel): VSTAB_ERR_UNSUPPORTED when the planes do not allow the tiled
 // kernel (the caller then warps to 16-bit BGR and converts: vstab_pull_frame_p010 does).
-extern "C" vstab_status vstab_warp_p010_planes(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
-                                               const float *rot_bottom, int map_mode, int blend, void *dst_y, size_t pitch_dst_y, void *dst_uv,
-                                               size_t pitch_dst_uv, int dw, int dh, void *stream) {
+// n: the entry point's name; matrix, range: its colour spec (the twin without one passes the default, which launches the default kernel)
+static vstab_status warp_p010_planes(const char *n, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                     const float *rot_bottom, int map_mode, int blend, void *dst_y, size_t pitch_dst_y, void *dst_uv, size_t pitch_dst_uv,
+                                     int dw, int dh, int matrix, int range, void *stream) {
     WarpArgs wa;
-    const vstab_status st = check_warp_p010("vstab_warp_p010_planes", P010_PLANES, y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst_y,
+    const vstab_status st = check_warp_p010(n, P010_PLANES, y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst_y,
                                             pitch_dst_y, dst_uv, pitch_dst_uv, dw, dh, wa);
     if (st != VSTAB_OK) return st;
     const StagedOffsets32 off32 = staged_offsets32(pitch_y, pitch_uv, sh);
     const bool tiled_ok = map_mode_fish_to_pinhole(map_mode) && source_16(y, pitch_y, uv, pitch_uv) && pitch_y >= (size_t)sw * 2 && pitch_uv >= (size_t)sw * 2 &&
                           off32.rows && (uint64_t)pitch_dst_y * dh < (1ull << 32);
-    if (!tiled_ok) return fail(VSTAB_ERR_UNSUPPORTED, "vstab_warp_p010_planes: needs 16-byte aligned source planes and a fisheye -> pinhole map");
+    if (!tiled_ok) return fail(VSTAB_ERR_UNSUPPORTED, std::string(n) + ": needs 16-byte aligned source planes and a fisheye -> pinhole map");
+    VSTAB_TRY(check_colour_spec(n, matrix, range));
     // a chroma plane of 4 GiB or more (staged_offsets32) is sampled from global memory (64-bit addresses)
     const bool vec = ptr_aligned(dst_y, 8) && ptr_aligned(dst_uv, 8) && pitch_dst_y % 8 == 0 && pitch_dst_uv % 8 == 0;
-    return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, true, off32.chroma, vec, static_cast<hipStream_t>(stream));
+    const ColourCoef col = colour_coefficients10(matrix, range);
+    return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, true, off32.chroma, vec, static_cast<hipStream_t>(stream),
+                               colour_spec_default(matrix, range) ? nullptr : &col);
+}
+
+extern "C" vstab_status vstab_warp_p010_planes(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                               const float *rot_bottom, int map_mode, int blend, void *dst_y, size_t pitch_dst_y, void *dst_uv,
+                                               size_t pitch_dst_uv, int dw, int dh, void *stream) {
+    return warp_p010_planes("vstab_warp_p010_planes", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst_y, pitch_dst_y, dst_uv, pitch_dst_uv, dw,
+                            dh, VSTAB_COLOUR_CVTCOLOR, VSTAB_RANGE_LIMITED, stream);
+}
+
+extern "C" vstab_status vstab_warp_p010_planes_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                                      const float *rot_bottom, int map_mode, int blend, void *dst_y, size_t pitch_dst_y, void *dst_uv,
+                                                      size_t pitch_dst_uv, int dw, int dh, int matrix, int range, void *stream) {
+    return warp_p010_planes("vstab_warp_p010_planes_colour", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst_y, pitch_dst_y, dst_uv, pitch_dst_uv,
+                            dw, dh, matrix, range, stream);
 }
 
 // The plane-wise 10-bit warp (vstab_warp_planar.hip, DEPTH 10): P010 planes in and out, no colour conversion at all.
@@ -215,30 +283,68 @@ extern "C" vstab_status vstab_warp_p010_planar(const void *y, size_t pitch_y, co
     return launch_warp_planar(wa, params, map_mode, 10, blend, src16, dst16, rot_bottom, static_cast<hipStream_t>(stream));
 }
 
-extern "C" vstab_status vstab_cvt_bgr16_p010(const void *src_bgr16, size_t pitch_src, int width, int height, void *dst_y, size_t pitch_y, void *dst_uv,
-                                             size_t pitch_uv, void *stream) {
-    if (!src_bgr16 || !dst_y || !dst_uv) return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr16_p010: null pointer");
-    if (width <= 0 || height <= 0 || width > 32767 || height > 32767) return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr16_p010: sizes must be in [1, 32767]");
+static vstab_status cvt_bgr16_p010(const std::string &n, const void *src_bgr16, size_t pitch_src, int width, int height, void *dst_y, size_t pitch_y, void *dst_uv,
+                                   size_t pitch_uv, int matrix, int range, void *stream) {
+    if (!src_bgr16 || !dst_y || !dst_uv) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
+    if (width <= 0 || height <= 0 || width > 32767 || height > 32767) return fail(VSTAB_ERR_INVALID, n + ": sizes must be in [1, 32767]");
     if (pitch_src < (size_t)width * 6 || pitch_src % 2 || pitch_y < (size_t)width * 2 || pitch_y % 2 || pitch_uv < (size_t)((width + 1) / 2) * 4 || pitch_uv % 4 ||
         !ptr_aligned(src_bgr16, 2) || !ptr_aligned(dst_y, 2) || !ptr_aligned(dst_uv, 4))
-        return fail(VSTAB_ERR_INVALID, "vstab_cvt_bgr16_p010: bad pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
-    hipLaunchKernelGGL(k_cvt_bgr10_p010, dim3(div_up(div_up(width, 2), 64), div_up(height, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const uint8_t *>(src_bgr16), pitch_src, width, height, static_cast<uint8_t *>(dst_y), pitch_y, static_cast<uint8_t *>(dst_uv), pitch_uv);
+        return fail(VSTAB_ERR_INVALID, n + ": bad pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
+    VSTAB_TRY(check_colour_spec(n.c_str(), matrix, range));
+    const dim3 grid(div_up(div_up(width, 2), 64), div_up(height, 4));
+    if (colour_spec_default(matrix, range))
+        hipLaunchKernelGGL(k_cvt_bgr10_p010, grid, dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const uint8_t *>(src_bgr16), pitch_src, width, height,
+                           static_cast<uint8_t *>(dst_y), pitch_y, static_cast<uint8_t *>(dst_uv), pitch_uv);
+    else
+        hipLaunchKernelGGL(k_cvt_bgr10_p010_colour, grid, dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const uint8_t *>(src_bgr16), pitch_src, width,
+                           height, static_cast<uint8_t *>(dst_y), pitch_y, static_cast<uint8_t *>(dst_uv), pitch_uv, colour_coefficients10(matrix, range));
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
 }
 
-extern "C" vstab_status vstab_warp_p010(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
-                                        const float *rot_bottom, int map_mode, int blend, void *dst, size_t pitch_dst, int dw, int dh, void *stream) {
+extern "C" vstab_status vstab_cvt_bgr16_p010(const void *src_bgr16, size_t pitch_src, int width, int height, void *dst_y, size_t pitch_y, void *dst_uv,
+                                             size_t pitch_uv, void *stream) {
+    return cvt_bgr16_p010("vstab_cvt_bgr16_p010", src_bgr16, pitch_src, width, height, dst_y, pitch_y, dst_uv, pitch_uv, VSTAB_COLOUR_CVTCOLOR, VSTAB_RANGE_LIMITED, stream);
+}
+
+extern "C" vstab_status vstab_cvt_bgr16_p010_colour(const void *src_bgr16, size_t pitch_src, int width, int height, void *dst_y, size_t pitch_y, void *dst_uv,
+                                                    size_t pitch_uv, int matrix, int range, void *stream) {
+    return cvt_bgr16_p010("vstab_cvt_bgr16_p010_colour", src_bgr16, pitch_src, width, height, dst_y, pitch_y, dst_uv, pitch_uv, matrix, range, stream);
+}
+
+// The forward conversion as an operator: P010 planes (even width and height) -> 16-bit BGR.  Every spec, the default included, runs the one kernel.
+extern "C" vstab_status vstab_cvt_p010_bgr16_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int width, int height, void *dst, size_t pitch_dst,
+                                                    int matrix, int range, void *stream) {
+    const std::string n = "vstab_cvt_p010_bgr16_colour";
+    if (!y || !uv || !dst) return fail(VSTAB_ERR_INVALID, n + ": null pointer");
+    if (width < 2 || height < 2 || (width & 1) || (height & 1) || width > 32767 || height > 32767)
+        return fail(VSTAB_ERR_INVALID, n + ": sizes must be even and in [2, 32767]");
+    if (pitch_y < (size_t)width * 2 || pitch_y % 2 || pitch_uv < (size_t)width * 2 || pitch_uv % 4 || pitch_dst < (size_t)width * 6 || pitch_dst % 2 ||
+        !ptr_aligned(y, 2) || !ptr_aligned(uv, 4) || !ptr_aligned(dst, 2))
+        return fail(VSTAB_ERR_INVALID, n + ": bad pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
+    VSTAB_TRY(check_colour_spec(n.c_str(), matrix, range));
+    hipLaunchKernelGGL(k_cvt_p010_bgr16_colour, dim3(div_up(width / 2, 64), div_up(height, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t *>(y), pitch_y, static_cast<const uint8_t *>(uv), pitch_uv, width, height, static_cast<uint8_t *>(dst), pitch_dst,
+                       colour_coefficients10(matrix, range));
+    VSTAB_HIP_TRY(hipGetLastError());
+    return VSTAB_OK;
+}
+
+static vstab_status warp_p010(const char *n, const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                              const float *rot_bottom, int map_mode, int blend, void *dst, size_t pitch_dst, int dw, int dh, int matrix, int range, void *stream) {
     WarpArgs wa;
-    const vstab_status st = check_warp_p010("vstab_warp_p010", P010_BGR16, y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst, pitch_dst,
+    const vstab_status st = check_warp_p010(n, P010_BGR16, y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst, pitch_dst,
                                             nullptr, 0, dw, dh, wa);
     if (st != VSTAB_OK) return st;
+    VSTAB_TRY(check_colour_spec(n, matrix, range));
+    const bool colour = !colour_spec_default(matrix, range);
+    const ColourCoef col = colour_coefficients10(matrix, range);
     // The LDS-tiled kernel (the 8-bit hot kernel's structure with a 10:10:10 LDS pixel) serves the fisheye -> pinhole maps when
     // the planes allow its 16-byte staging loads and 32-bit staged offsets; everything else takes the direct-gather kernel below.  Same results.
     const bool tiled_ok = map_mode_fish_to_pinhole(map_mode) && sw >= 8 && source_16(y, pitch_y, uv, pitch_uv) && staged_offsets32(pitch_y, pitch_uv, sh).chroma;
     static const bool force_direct = getenv("VSTAB_P010_DIRECT") != nullptr;  // development: the direct-gather kernel for every call
-    if (tiled_ok && !force_direct) return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, false, true, true, static_cast<hipStream_t>(stream));
+    if (tiled_ok && !force_direct)
+        return launch_warp_fused10(wa, params, map_mode, blend, rot_bottom, false, true, true, static_cast<hipStream_t>(stream), colour ? &col : nullptr);
     P010Args a;
     a.y = wa.y, a.uv = wa.uv, a.dst = static_cast<uint16_t *>(dst);
     a.pitch_y = pitch_y, a.pitch_uv = pitch_uv, a.pitch_dst = pitch_dst;
@@ -246,12 +352,28 @@ extern "C" vstab_status vstab_warp_p010(const void *y, size_t pitch_y, const voi
     a.p = wa.p;
     a.rs = rot_bottom != nullptr;
     fill_rolling_shutter(a, params, rot_bottom, dh);
+    a.col = col;  // (read by the COLOUR kernels alone)
     const dim3 grid(div_up(dw, 64), div_up(dh, 8));  // 64 columns x 4 pairs of rows per workgroup
     with_map_mode(map_mode, [&](auto mode) {  // (the rotation per row is the kernel's run-time a.rs: no MAP_RS_* forms here)
         with_either<VSTAB_BLEND_FP16, VSTAB_BLEND_EXACT>(blend == VSTAB_BLEND_FP16, [&](auto blend_c) {
-            launch_kernel(k_warp_p010<decltype(mode)::value, decltype(blend_c)::value>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+            with_bool(colour, [&](auto colour_c) {
+                launch_kernel(k_warp_p010<decltype(mode)::value, decltype(blend_c)::value, decltype(colour_c)::value>, grid, dim3(256), 0,
+                              static_cast<hipStream_t>(stream), a);
+            });
         });
     });
     VSTAB_HIP_TRY(hipGetLastError());
     return VSTAB_OK;
+}
+
+extern "C" vstab_status vstab_warp_p010(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                        const float *rot_bottom, int map_mode, int blend, void *dst, size_t pitch_dst, int dw, int dh, void *stream) {
+    return warp_p010("vstab_warp_p010", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst, pitch_dst, dw, dh, VSTAB_COLOUR_CVTCOLOR,
+                     VSTAB_RANGE_LIMITED, stream);
+}
+
+extern "C" vstab_status vstab_warp_p010_colour(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                               const float *rot_bottom, int map_mode, int blend, void *dst, size_t pitch_dst, int dw, int dh, int matrix, int range,
+                                               void *stream) {
+    return warp_p010("vstab_warp_p010_colour", y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, blend, dst, pitch_dst, dw, dh, matrix, range, stream);
 }
