@@ -1,6 +1,6 @@
 // vstab_colour.cpp -- the coefficient table of a colour spec (include/vstab.h, "Colour matrix and range"): host only, no device needed.
-// The cvtColor row is the constants of vstab_device.hpp; the other six are derived here from (Kr, Kb) and the range in exact integer
-// rational arithmetic, rounded half to even.
+// The cvtColor row is read from the constant types of vstab_device.hpp (CvtColor8 / CvtColor10), which the default kernels are compiled
+// with; the other six are derived here from (Kr, Kb) and the range in exact integer rational arithmetic, rounded half to even.
 #include "vstab_colour.hpp"
 
 namespace vstab {
@@ -48,8 +48,14 @@ static ColourCoef derive(int matrix, int64_t yn, int64_t yd, int64_t cn, int64_t
     return c;
 }
 
+// cvtColor's row: the constants the default kernels are compiled with, K = CvtColor8 or CvtColor10
+template <typename K>
+static ColourCoef cvtcolor_row() {
+    return {K::cy, K::cub, K::cug, K::cvg, K::cvr, K::yoff, K::cry, K::cgy, K::cby, K::cru, K::cgu, K::cbu, K::cgv, K::cbv};
+}
+
 ColourCoef colour_coefficients(int matrix, int range) {
-    if (matrix == VSTAB_COLOUR_CVTCOLOR) return {CY, CUB, CUG, CVG, CVR, 16, CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV};
+    if (matrix == VSTAB_COLOUR_CVTCOLOR) return cvtcolor_row<CvtColor8>();
     if (range == VSTAB_RANGE_FULL) return derive(matrix, 1, 1, 1, 1, 0);
     return derive(matrix, 255, 219, 255, 224, 16);
 }
@@ -57,7 +63,7 @@ ColourCoef colour_coefficients(int matrix, int range) {
 // The 10-bit table (include/vstab.h, "Colour matrix and range at 10 bits"): cvtColor's row with the luma offset of 10-bit video, which is the
 // 10-bit path's arithmetic as it always was; the other six with the 10-bit scales 1023/876 and 1023/896.
 ColourCoef colour_coefficients10(int matrix, int range) {
-    if (matrix == VSTAB_COLOUR_CVTCOLOR) return {CY, CUB, CUG, CVG, CVR, 64, CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV};
+    if (matrix == VSTAB_COLOUR_CVTCOLOR) return cvtcolor_row<CvtColor10>();
     if (range == VSTAB_RANGE_FULL) return derive(matrix, 1, 1, 1, 1, 0);
     return derive(matrix, 1023, 876, 1023, 896, 64);
 }

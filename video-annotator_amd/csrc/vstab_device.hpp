@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace vstab {
 
 // ---------------------------------------------------------------------------------------------
@@ -466,32 +468,46 @@ __device__ __forceinline__ Tap quantise(float mx, float my) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// cvtColor(COLOR_YUV2BGR_NV12) arithmetic (OpenCV 4.5 CPU path): BT.601 limited
-// range, 20-bit fixed point.
+// Colour conversion: cvtColor(COLOR_YUV2BGR_NV12) / cvtColor(COLOR_BGR2YUV_I420) arithmetic (OpenCV 4.5 CPU path, SURVEY.md A.1: BT.601
+// limited range, 20-bit fixed point) and, in the same forms, a colour spec's (include/vstab.h, "Colour matrix and range").  Each function is
+// stated once, over the source K of its coefficients:
+//   CvtColor8 / CvtColor10   cvtColor's constants as a type: every product folds;
+//   ColourCoef               a spec's row in a block of kernel arguments, so that one kernel serves every spec.  The block is what
+//                            vstab_colour_coefficients[10] writes: five forward coefficients, yoff, eight inverse ones.
+// Every coefficient is below 2^23 (24-bit multiplies hold) and every forward sum of the 8-bit path below 5.8e8 in magnitude (int32 holds).
 // ---------------------------------------------------------------------------------------------
+// cvtColor's numbers, forward and inverse: stated here once (tests/test_colour_cpu.py reads these two lines) and used through the types below
 constexpr int CY = 1220542, CUB = 2116026, CUG = -409993, CVG = -852492, CVR = 1673527;
+constexpr int CRY = 269484, CGY = 528482, CBY = 102760, CRU = -155188, CGU = -305135, CBU = 460324, CGV = -385875, CBV = -74448;
+template <int YOFF>  // the luma offset: 16 at 8 bits, 64 at 10
+struct CvtColor {
+    static constexpr int cy = CY, cub = CUB, cug = CUG, cvg = CVG, cvr = CVR, yoff = YOFF;
+    static constexpr int cry = CRY, cgy = CGY, cby = CBY, cru = CRU, cgu = CGU, cbu = CBU, cgv = CGV, cbv = CBV;
+};
+using CvtColor8 = CvtColor<16>;
+using CvtColor10 = CvtColor<64>;
+struct ColourCoef {
+    int cy, cub, cug, cvg, cvr, yoff;
+    int cry, cgy, cby, cru, cgu, cbu, cgv, cbv;
+};
+template <typename K>
+constexpr bool coef_at_run_time = std::is_same<K, ColourCoef>::value;
+// coefficient * value: 24 bits wide where the coefficient arrives at run time, a plain product the compiler folds as it likes where it is
+// a constant.  The multiply belongs to the source: __mul24 of a constant made every default k_warp_fused kernel 40 to 85 lines longer and
+// gave two of them a private segment.  And it is written in place, not called: a product inside a helper function is out of sight of the
+// value-range passes that run before inlining, which then no longer see that U | V << 8 of cvtColor's inverse has no common bits (six
+// instructions more per store loop of every default NV12 kernel).  DESIGN.md section 32, "The coefficient source".
+#define VSTAB_CMUL(k, c, v) (coef_at_run_time<std::decay_t<decltype(k)>> ? __mul24(c, v) : (c) * (v))
 
 struct ChromaTerm {
     int ruv, guv, buv;
 };
-__device__ __forceinline__ ChromaTerm chroma_term(int U, int V) {
+template <typename K>
+__device__ __forceinline__ ChromaTerm chroma_term(const K &k, int U, int V) {
     const int u = U - 128, v = V - 128;
-    return {(1 << 19) + CVR * v, (1 << 19) + CVG * v + CUG * u, (1 << 19) + CUB * u};
+    return {(1 << 19) + k.cvr * v, (1 << 19) + k.cvg * v + k.cug * u, (1 << 19) + k.cub * u};
 }
-// OpenCV 4.5 cvtColor(COLOR_BGR2YUV_I420) arithmetic (RGB8toYUV420pInvoker): BT.601 limited range, 20-bit
-// fixed point; chroma from the top-left pixel of each 2x2 block.  No saturation is needed: Y in [16, 235],
-// U / V in [16, 240] for every 8-bit BGR.  v = B | G << 8 | R << 16.
-constexpr int CRY = 269484, CGY = 528482, CBY = 102760, CRU = -155188, CGU = -305135, CBU = 460324, CGV = -385875, CBV = -74448;
-__device__ __forceinline__ uint32_t bgr_to_y(uint32_t v) {
-    const int B = v & 255, G = (v >> 8) & 255, R = (v >> 16) & 255;
-    return (uint32_t)(CRY * R + CGY * G + CBY * B + (1 << 19) + (16 << 20)) >> 20;
-}
-__device__ __forceinline__ uint32_t bgr_to_uv(uint32_t v) {  // U | V << 8
-    const int B = v & 255, G = (v >> 8) & 255, R = (v >> 16) & 255;
-    const uint32_t U = (uint32_t)(CRU * R + CGU * G + CBU * B + (1 << 19) + (128 << 20)) >> 20;
-    const uint32_t V = (uint32_t)(CBU * R + CGV * G + CBV * B + (1 << 19) + (128 << 20)) >> 20;
-    return U | (V << 8);
-}
+__device__ __forceinline__ ChromaTerm chroma_term(int U, int V) { return chroma_term(CvtColor8{}, U, V); }
 __device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
 
 // gfx950's v_ashr_pk_u8_i32 D, S0, S1, n writes {sat_u8(S0 >> n), sat_u8(S1 >> n)} into ONE 16-bit
@@ -506,60 +522,27 @@ __device__ __forceinline__ int ashr20(int v) {
     return v;
 }
 
-__device__ __forceinline__ void yuv_to_bgr(int Y, const ChromaTerm &c, int &b, int &g, int &r) {
-    const int y = max(Y - 16, 0) * CY;
-    b = sat8(ashr20(y + c.buv));
-    g = sat8(ashr20(y + c.guv));
-    r = sat8(ashr20(y + c.ruv));
-}
-
-
-// Chroma terms with the luma offset folded in: channel = sat8((max(Y,16)*CY + term) >> 20), which is
-// the same integer as sat8((max(Y-16,0)*CY + (1<<19) + C*uv) >> 20).
-__device__ __forceinline__ ChromaTerm chroma_term_folded(int U, int V) {
-    const int u = U - 128, v = V - 128;
-    constexpr int K = (1 << 19) - 16 * CY;
-    return {K + CVR * v, K + CVG * v + CUG * u, K + CUB * u};
-}
-
-// One BGRx pixel (byte 3 = 0) from a luma byte and folded chroma terms: 1 max + 3 mad + 2 pack.
-__device__ __forceinline__ uint32_t pack_bgrx(int Y, const ChromaTerm &c) {
-    const int y = max(Y, 16);
-    const int b = __mul24(y, CY) + c.buv, g = __mul24(y, CY) + c.guv, r = __mul24(y, CY) + c.ruv;
-    uint32_t d;
-    asm("v_ashr_pk_u8_i32 %0, %1, %2, 20" : "=v"(d) : "v"(b), "v"(g));
-    asm("v_ashr_pk_u8_i32 %0, %1, 0, 20 op_sel:[0,0,0,1]" : "+v"(d) : "v"(r));
-    return d;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Colour matrix and range (include/vstab.h, "Colour matrix and range"): the same 20-bit fixed-point forms with the
-// coefficients in a block of kernel arguments, so that one kernel serves every spec.  The block is what
-// vstab_colour_coefficients writes: five forward coefficients, yoff, eight inverse ones.  With the cvtColor row
-// every function below returns what its namesake above returns.  Every coefficient is below 2^23 (24-bit
-// multiplies hold) and every forward sum below 5.8e8 in magnitude (int32 holds).
-// ---------------------------------------------------------------------------------------------
-struct ColourCoef {
-    int cy, cub, cug, cvg, cvr, yoff;
-    int cry, cgy, cby, cru, cgu, cbu, cgv, cbv;
-};
-__device__ __forceinline__ ChromaTerm chroma_term(const ColourCoef &k, int U, int V) {
-    const int u = U - 128, v = V - 128;
-    return {(1 << 19) + k.cvr * v, (1 << 19) + k.cvg * v + k.cug * u, (1 << 19) + k.cub * u};
-}
-__device__ __forceinline__ void yuv_to_bgr(const ColourCoef &k, int Y, const ChromaTerm &c, int &b, int &g, int &r) {
+template <typename K>
+__device__ __forceinline__ void yuv_to_bgr(const K &k, int Y, const ChromaTerm &c, int &b, int &g, int &r) {
     const int y = max(Y - k.yoff, 0) * k.cy;
     b = sat8(ashr20(y + c.buv));
     g = sat8(ashr20(y + c.guv));
     r = sat8(ashr20(y + c.ruv));
 }
-// channel = sat8((max(Y, yoff) * CY + term) >> 20): the luma offset folded into the chroma terms, as chroma_term_folded does
-__device__ __forceinline__ ChromaTerm chroma_term_folded(const ColourCoef &k, int U, int V) {
+__device__ __forceinline__ void yuv_to_bgr(int Y, const ChromaTerm &c, int &b, int &g, int &r) { yuv_to_bgr(CvtColor8{}, Y, c, b, g, r); }
+
+// Chroma terms with the luma offset folded in: channel = sat8((max(Y, yoff) * CY + term) >> 20), which is
+// the same integer as sat8((max(Y - yoff, 0) * CY + (1 << 19) + C * uv) >> 20).
+template <typename K>
+__device__ __forceinline__ ChromaTerm chroma_term_folded(const K &k, int U, int V) {
     const int u = U - 128, v = V - 128;
-    const int K = (1 << 19) - k.yoff * k.cy;  // uniform
-    return {K + __mul24(k.cvr, v), K + __mul24(k.cvg, v) + __mul24(k.cug, u), K + __mul24(k.cub, u)};
+    const int K0 = (1 << 19) - k.yoff * k.cy;  // a constant, or uniform
+    return {K0 + VSTAB_CMUL(k, k.cvr, v), K0 + VSTAB_CMUL(k, k.cvg, v) + VSTAB_CMUL(k, k.cug, u), K0 + VSTAB_CMUL(k, k.cub, u)};
 }
-__device__ __forceinline__ uint32_t pack_bgrx(const ColourCoef &k, int Y, const ChromaTerm &c) {
+
+// One BGRx pixel (byte 3 = 0) from a luma byte and folded chroma terms: 1 max + 3 mad + 2 pack.
+template <typename K>
+__device__ __forceinline__ uint32_t pack_bgrx(const K &k, int Y, const ChromaTerm &c) {
     const int y = max(Y, k.yoff);
     const int b = __mul24(y, k.cy) + c.buv, g = __mul24(y, k.cy) + c.guv, r = __mul24(y, k.cy) + c.ruv;
     uint32_t d;
@@ -567,17 +550,27 @@ __device__ __forceinline__ uint32_t pack_bgrx(const ColourCoef &k, int Y, const 
     asm("v_ashr_pk_u8_i32 %0, %1, 0, 20 op_sel:[0,0,0,1]" : "+v"(d) : "v"(r));
     return d;
 }
-// The inverse, v = B | G << 8 | R << 16.  The saturation is part of the definition: full range reaches an unsaturated U or V of 256
-// (pure blue, pure red); no sum leaves int32 (|coefficient| < 2^20, three bytes, 129 << 20).  ashr20: see above -- the compiler must not
-// fuse the shift and the saturation of two bytes that are then packed.
-__device__ __forceinline__ uint32_t bgr_to_y(const ColourCoef &k, uint32_t v) {
-    const int B = v & 255, G = (v >> 8) & 255, R = (v >> 16) & 255;
-    return (uint32_t)sat8(ashr20(__mul24(k.cry, R) + __mul24(k.cgy, G) + __mul24(k.cby, B) + (1 << 19) + (k.yoff << 20)));
+
+// The inverse, cvtColor(COLOR_BGR2YUV_I420)'s form (RGB8toYUV420pInvoker): v = B | G << 8 | R << 16; chroma from the top-left pixel of each
+// 2 x 2 block.  No sum leaves int32 (|coefficient| < 2^20, three bytes, 129 << 20).  The saturation is part of the definition: full range
+// reaches an unsaturated U or V of 256 (pure blue, pure red).  ashr20: see above -- the compiler must not fuse the shift and the saturation
+// of two bytes that are then packed.
+template <typename K>
+__device__ __forceinline__ uint32_t inverse_byte(const K &, int sum) {
+    // cvtColor's constants keep Y in [16, 235] and U, V in [16, 240] for every 8-bit BGR: the saturation never acts and is left out
+    if constexpr (coef_at_run_time<K>) return (uint32_t)sat8(ashr20(sum));
+    else return (uint32_t)sum >> 20;
 }
-__device__ __forceinline__ uint32_t bgr_to_uv(const ColourCoef &k, uint32_t v) {  // U | V << 8
+template <typename K>
+__device__ __forceinline__ uint32_t bgr_to_y(const K &k, uint32_t v) {
     const int B = v & 255, G = (v >> 8) & 255, R = (v >> 16) & 255;
-    const uint32_t U = (uint32_t)sat8(ashr20(__mul24(k.cru, R) + __mul24(k.cgu, G) + __mul24(k.cbu, B) + (1 << 19) + (128 << 20)));
-    const uint32_t V = (uint32_t)sat8(ashr20(__mul24(k.cbu, R) + __mul24(k.cgv, G) + __mul24(k.cbv, B) + (1 << 19) + (128 << 20)));
+    return inverse_byte(k, VSTAB_CMUL(k, k.cry, R) + VSTAB_CMUL(k, k.cgy, G) + VSTAB_CMUL(k, k.cby, B) + (1 << 19) + (k.yoff << 20));
+}
+template <typename K>
+__device__ __forceinline__ uint32_t bgr_to_uv(const K &k, uint32_t v) {  // U | V << 8
+    const int B = v & 255, G = (v >> 8) & 255, R = (v >> 16) & 255;
+    const uint32_t U = inverse_byte(k, VSTAB_CMUL(k, k.cru, R) + VSTAB_CMUL(k, k.cgu, G) + VSTAB_CMUL(k, k.cbu, B) + (1 << 19) + (128 << 20));
+    const uint32_t V = inverse_byte(k, VSTAB_CMUL(k, k.cbu, R) + VSTAB_CMUL(k, k.cgv, G) + VSTAB_CMUL(k, k.cbv, B) + (1 << 19) + (128 << 20));
     return U | (V << 8);
 }
 

@@ -120,7 +120,9 @@ __global__ void __launch_bounds__(256) k_cvt_nv12_bgr(const uint8_t *__restrict_
 
 // =============================================================================================
 // k_cvt_nv12_bgr_colour -- k_cvt_nv12_bgr with a colour spec's coefficients (include/vstab.h, "Colour matrix and range"): the same
-// 8 x 2 block per thread, the conversion through the ColourCoef forms of vstab_device.hpp.
+// 8 x 2 block per thread, chroma_term / yuv_to_bgr (vstab_device.hpp) with the block k as their coefficient source.  A kernel of its own
+// and not a second caller of one __device__ body: through such a body k_cvt_nv12_bgr's listing grows by three lines and this one's
+// changes its order ("The coefficient source").
 // =============================================================================================
 __global__ void __launch_bounds__(256) k_cvt_nv12_bgr_colour(const uint8_t *__restrict__ yp, size_t pitch_y, const uint8_t *__restrict__ uvp, size_t pitch_uv,
                                                              int w, int h, uint8_t *__restrict__ dst, size_t pitch_dst, int vec_ok, ColourCoef k) {

@@ -37,35 +37,10 @@ struct FusedArgs {
     ColourCoef col;
 };
 
-// One NV12 tap converted with the cvtColor arithmetic; outside the source -> 0 (cv::remap BORDER_CONSTANT).
-__device__ __forceinline__ void fetch_tap(const WarpArgs &a, int X, int Y, int &b, int &g, int &r) {
-    if ((unsigned)X < (unsigned)a.sw && (unsigned)Y < (unsigned)a.sh) {
-        const int yv = a.y[(size_t)Y * a.pitch_y + X];
-        const uint16_t c = *reinterpret_cast<const uint16_t *>(a.uv + (size_t)(Y >> 1) * a.pitch_uv + (X & ~1));
-        yuv_to_bgr(yv, chroma_term(c & 255, c >> 8), b, g, r);
-    } else {
-        b = g = r = 0;
-    }
-}
-
-// cv::remap's four-product fixed-point blend of taps fetched straight from global memory.  sx, sy = rint(32 * map).
-__device__ __forceinline__ uint32_t gather_pixel(const WarpArgs &a, int sx, int sy) {
-    const int X = sx >> 5, Y = sy >> 5;
-    const uint32_t fx = sx & 31, fy = sy & 31;
-    const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
-    int b0, g0, r0, b1, g1, r1, b2, g2, r2, b3, g3, r3;
-    fetch_tap(a, X, Y, b0, g0, r0);
-    fetch_tap(a, X + 1, Y, b1, g1, r1);
-    fetch_tap(a, X, Y + 1, b2, g2, r2);
-    fetch_tap(a, X + 1, Y + 1, b3, g3, r3);
-    const uint32_t B = (uint32_t)(b0 * w00 + b1 * w01 + b2 * w10 + b3 * w11 + 512) >> 10;
-    const uint32_t G = (uint32_t)(g0 * w00 + g1 * w01 + g2 * w10 + g3 * w11 + 512) >> 10;
-    const uint32_t R = (uint32_t)(r0 * w00 + r1 * w01 + r2 * w10 + r3 * w11 + 512) >> 10;
-    return B | (G << 8) | (R << 16);
-}
-
-// The same two with a colour spec's coefficients (the COLOUR kernels' gather path)
-__device__ __forceinline__ void fetch_tap(const WarpArgs &a, const ColourCoef &k, int X, int Y, int &b, int &g, int &r) {
+// One NV12 tap converted with the coefficients of k (vstab_device.hpp; without k: cvtColor's); outside the source -> 0 (cv::remap
+// BORDER_CONSTANT).
+template <typename K>
+__device__ __forceinline__ void fetch_tap(const WarpArgs &a, const K &k, int X, int Y, int &b, int &g, int &r) {
     if ((unsigned)X < (unsigned)a.sw && (unsigned)Y < (unsigned)a.sh) {
         const int yv = a.y[(size_t)Y * a.pitch_y + X];
         const uint16_t c = *reinterpret_cast<const uint16_t *>(a.uv + (size_t)(Y >> 1) * a.pitch_uv + (X & ~1));
@@ -74,7 +49,11 @@ __device__ __forceinline__ void fetch_tap(const WarpArgs &a, const ColourCoef &k
         b = g = r = 0;
     }
 }
-__device__ __forceinline__ uint32_t gather_pixel(const WarpArgs &a, const ColourCoef &k, int sx, int sy) {
+__device__ __forceinline__ void fetch_tap(const WarpArgs &a, int X, int Y, int &b, int &g, int &r) { fetch_tap(a, CvtColor8{}, X, Y, b, g, r); }
+
+// cv::remap's four-product fixed-point blend of taps fetched straight from global memory.  sx, sy = rint(32 * map).
+template <typename K>
+__device__ __forceinline__ uint32_t gather_pixel(const WarpArgs &a, const K &k, int sx, int sy) {
     const int X = sx >> 5, Y = sy >> 5;
     const uint32_t fx = sx & 31, fy = sy & 31;
     const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;

@@ -172,6 +172,9 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                   "a colour spec: at 8 bits the map evaluated, one rotation through an ideal lens; at 10 bits the 10-bit kernels' modes (vstab_warp_p010_colour)");
     using SrcVec = typename std::conditional<DEPTH == 10, uint4, uint2>::type;  // 8 source samples of a block row
     constexpr uint32_t BPS = DEPTH == 10 ? 2 : 1;                              // bytes per sample
+    // a phase's coefficient source (vstab_device.hpp): cvtColor's constants as a type, or -- COLOUR -- the block read from the kernel argument
+    using Cvt = typename std::conditional<DEPTH == 10, CvtColor10, CvtColor8>::type;
+    using Coef = typename std::conditional<COLOUR, ColourCoef, Cvt>::type;
     constexpr int TH = 4 * RW;
     constexpr int STAGE_MAX = StageTrips<RWB, RW>::value;
     constexpr int QB = CACHED ? 0 : QMAGIC_BITS;  // offset of the quantised-coordinate representation kept in registers
@@ -277,7 +280,7 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
     VSTAB_STAMP(3);
     // ---- convert: cvtColor once per source pixel, BGRx dwords to LDS --------------------------------------------
     if (use_lds) {
-        ColourCoef kc = {};
+        Coef kc = {};
         if constexpr (COLOUR) kc = colour_coef_here();
 #pragma unroll
         for (int it = 0; it < STAGE_MAX; it++) {
@@ -302,17 +305,13 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                     const uint32_t cw[4] = {uvw[it].x, uvw[it].y, uvw[it].z, uvw[it].w};
 #pragma unroll
                     for (int half = 0; half < 2; half++) {
-                        // (COLOUR: the same calls with the spec's coefficients in front)
-                        const auto term = [&](uint32_t w) { if constexpr (COLOUR) return chroma_term10(kc, w); else return chroma_term10(w); };
-                        const auto pack_bgr10 = [&](int yv, const ChromaTerm &c) { if constexpr (COLOUR) return vstab::pack_bgr10(kc, yv, c); else return vstab::pack_bgr10(yv, c); };
-                        const auto pack_bgr10h = [&](int yv, const ChromaTerm &c) { if constexpr (COLOUR) return vstab::pack_bgr10h(kc, yv, c); else return vstab::pack_bgr10h(yv, c); };
-                        const ChromaTerm c0 = term(cw[2 * half]), c1 = term(cw[2 * half + 1]);
+                        const ChromaTerm c0 = chroma_term10(kc, cw[2 * half]), c1 = chroma_term10(kc, cw[2 * half + 1]);
                         if constexpr (PIX8) {  // four pixels of each row as halves: two 16-byte stores per row
                             const uint32_t la = ya[2 * half], lb = ya[2 * half + 1], ma = yb[2 * half], mb = yb[2 * half + 1];
-                            const uint2 a0 = pack_bgr10h((int)((la & 0xffffu) >> 6), c0), a1 = pack_bgr10h((int)(la >> 22), c0);
-                            const uint2 a2 = pack_bgr10h((int)((lb & 0xffffu) >> 6), c1), a3 = pack_bgr10h((int)(lb >> 22), c1);
-                            const uint2 b0 = pack_bgr10h((int)((ma & 0xffffu) >> 6), c0), b1 = pack_bgr10h((int)(ma >> 22), c0);
-                            const uint2 b2 = pack_bgr10h((int)((mb & 0xffffu) >> 6), c1), b3 = pack_bgr10h((int)(mb >> 22), c1);
+                            const uint2 a0 = pack_bgr10h(kc, (int)((la & 0xffffu) >> 6), c0), a1 = pack_bgr10h(kc, (int)(la >> 22), c0);
+                            const uint2 a2 = pack_bgr10h(kc, (int)((lb & 0xffffu) >> 6), c1), a3 = pack_bgr10h(kc, (int)(lb >> 22), c1);
+                            const uint2 b0 = pack_bgr10h(kc, (int)((ma & 0xffffu) >> 6), c0), b1 = pack_bgr10h(kc, (int)(ma >> 22), c0);
+                            const uint2 b2 = pack_bgr10h(kc, (int)((mb & 0xffffu) >> 6), c1), b3 = pack_bgr10h(kc, (int)(mb >> 22), c1);
                             *reinterpret_cast<uint4 *>(d + 8 * half) = make_uint4(a0.x, a0.y, a1.x, a1.y);
                             *reinterpret_cast<uint4 *>(d + 8 * half + 4) = make_uint4(a2.x, a2.y, a3.x, a3.y);
                             *reinterpret_cast<uint4 *>(d + pw + 8 * half) = make_uint4(b0.x, b0.y, b1.x, b1.y);
@@ -320,10 +319,10 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                             continue;
                         }
                         uint4 r0, r1;
-                        r0.x = pack_bgr10((int)((ya[2 * half] & 0xffffu) >> 6), c0), r0.y = pack_bgr10((int)(ya[2 * half] >> 22), c0);
-                        r0.z = pack_bgr10((int)((ya[2 * half + 1] & 0xffffu) >> 6), c1), r0.w = pack_bgr10((int)(ya[2 * half + 1] >> 22), c1);
-                        r1.x = pack_bgr10((int)((yb[2 * half] & 0xffffu) >> 6), c0), r1.y = pack_bgr10((int)(yb[2 * half] >> 22), c0);
-                        r1.z = pack_bgr10((int)((yb[2 * half + 1] & 0xffffu) >> 6), c1), r1.w = pack_bgr10((int)(yb[2 * half + 1] >> 22), c1);
+                        r0.x = pack_bgr10(kc, (int)((ya[2 * half] & 0xffffu) >> 6), c0), r0.y = pack_bgr10(kc, (int)(ya[2 * half] >> 22), c0);
+                        r0.z = pack_bgr10(kc, (int)((ya[2 * half + 1] & 0xffffu) >> 6), c1), r0.w = pack_bgr10(kc, (int)(ya[2 * half + 1] >> 22), c1);
+                        r1.x = pack_bgr10(kc, (int)((yb[2 * half] & 0xffffu) >> 6), c0), r1.y = pack_bgr10(kc, (int)(yb[2 * half] >> 22), c0);
+                        r1.z = pack_bgr10(kc, (int)((yb[2 * half + 1] & 0xffffu) >> 6), c1), r1.w = pack_bgr10(kc, (int)(yb[2 * half + 1] >> 22), c1);
                         *reinterpret_cast<uint4 *>(d + 4 * half) = r0;
                         *reinterpret_cast<uint4 *>(d + pw + 4 * half) = r1;
                     }
@@ -332,21 +331,12 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                 for (int half = 0; half < 2; half++) {
                     const uint32_t cw = half ? uvw[it].y : uvw[it].x, ya = half ? y0w[it].y : y0w[it].x, yb = half ? y1w[it].y : y1w[it].x;
                     uint4 r0, r1;
-                    if constexpr (COLOUR) {
-                        const ChromaTerm c0 = chroma_term_folded(kc, cw & 255, (cw >> 8) & 255);
-                        const ChromaTerm c1 = chroma_term_folded(kc, (cw >> 16) & 255, cw >> 24);
-                        r0.x = pack_bgrx(kc, ya & 255, c0), r0.y = pack_bgrx(kc, (ya >> 8) & 255, c0);
-                        r0.z = pack_bgrx(kc, (ya >> 16) & 255, c1), r0.w = pack_bgrx(kc, ya >> 24, c1);
-                        r1.x = pack_bgrx(kc, yb & 255, c0), r1.y = pack_bgrx(kc, (yb >> 8) & 255, c0);
-                        r1.z = pack_bgrx(kc, (yb >> 16) & 255, c1), r1.w = pack_bgrx(kc, yb >> 24, c1);
-                    } else {
-                        const ChromaTerm c0 = chroma_term_folded(cw & 255, (cw >> 8) & 255);
-                        const ChromaTerm c1 = chroma_term_folded((cw >> 16) & 255, cw >> 24);
-                        r0.x = pack_bgrx(ya & 255, c0), r0.y = pack_bgrx((ya >> 8) & 255, c0);
-                        r0.z = pack_bgrx((ya >> 16) & 255, c1), r0.w = pack_bgrx(ya >> 24, c1);
-                        r1.x = pack_bgrx(yb & 255, c0), r1.y = pack_bgrx((yb >> 8) & 255, c0);
-                        r1.z = pack_bgrx((yb >> 16) & 255, c1), r1.w = pack_bgrx(yb >> 24, c1);
-                    }
+                    const ChromaTerm c0 = chroma_term_folded(kc, cw & 255, (cw >> 8) & 255);
+                    const ChromaTerm c1 = chroma_term_folded(kc, (cw >> 16) & 255, cw >> 24);
+                    r0.x = pack_bgrx(kc, ya & 255, c0), r0.y = pack_bgrx(kc, (ya >> 8) & 255, c0);
+                    r0.z = pack_bgrx(kc, (ya >> 16) & 255, c1), r0.w = pack_bgrx(kc, ya >> 24, c1);
+                    r1.x = pack_bgrx(kc, yb & 255, c0), r1.y = pack_bgrx(kc, (yb >> 8) & 255, c0);
+                    r1.z = pack_bgrx(kc, (yb >> 16) & 255, c1), r1.w = pack_bgrx(kc, yb >> 24, c1);
                     *reinterpret_cast<uint4 *>(d + 4 * half) = r0;
                     *reinterpret_cast<uint4 *>(d + pw + 4 * half) = r1;
                 }
@@ -435,8 +425,9 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                             asm volatile("" : "+v"(kg.cy), "+v"(kg.cub), "+v"(kg.cug), "+v"(kg.cvg), "+v"(kg.cvr), "+v"(kg.yoff));
                             v = gather_pixel10<BLEND>(a, kg, sx - QB, sy - QB);
                         }
+                        else if constexpr (DEPTH == 10) v = gather_pixel10<BLEND>(a, Cvt{}, sx - QB, sy - QB);
                         else if constexpr (COLOUR) v = gather_pixel_far(a, colour_coef_here(), sx - QB, sy - QB);
-                        else v = DEPTH == 10 ? gather_pixel10<BLEND>(a, sx - QB, sy - QB) : gather_pixel_far(a, sx - QB, sy - QB);
+                        else v = gather_pixel_far(a, Cvt{}, sx - QB, sy - QB);
 #pragma unroll
                         for (int k = 0; k < RW; k++) out[k] = j == k ? v : out[k];
                     }
@@ -473,16 +464,18 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
         // P010 planes (the 10-bit path's encoder hand-off; definition: include/vstab.h, vstab_cvt_bgr16_p010): luma word for every
         // pixel, (U, V) words from the even-row / even-column pixels; four lanes' words are collected in the first lane of each
         // quad (DPP quad_perm) and stored as 8 bytes
-        ColourCoef kc = {};
+        Coef kc = {};
         if constexpr (COLOUR) kc = colour_coef_here();
 #pragma unroll
         for (int j = 0; j < RW; j++) {
             const int y = y0 + wave * RW + j;
             if (y >= a.dh) break;  // uniform
             const int B = (int)(out[j] & 1023u), G = (int)((out[j] >> 10) & 1023u), R = (int)(out[j] >> 20);
+            // (the default form stays written out: through bgr10_to_y / bgr10_to_uv the sums of the default kernels associate in another
+            // order and their listings move)
             uint32_t yb;
             if constexpr (COLOUR) yb = bgr10_to_y(kc, B, G, R) << 6;
-            else yb = (uint32_t)sat10((CRY * R + CGY * G + CBY * B + (1 << 19) + (64 << 20)) >> 20) << 6;
+            else yb = (uint32_t)sat10((Cvt::cry * R + Cvt::cgy * G + Cvt::cby * B + (1 << 19) + (Cvt::yoff << 20)) >> 20) << 6;
             const uint32_t y1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0x55, 0xf, 0xf, true);
             const uint32_t y2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0xaa, 0xf, 0xf, true);
             const uint32_t y3 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0xff, 0xf, 0xf, true);
@@ -499,8 +492,8 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                 uint32_t cb;
                 if constexpr (COLOUR) cb = bgr10_to_uv(kc, B, G, R) << 6;
                 else {
-                    const uint32_t U = (uint32_t)sat10((CRU * R + CGU * G + CBU * B + (1 << 19) + (512 << 20)) >> 20) << 6;
-                    const uint32_t V = (uint32_t)sat10((CBU * R + CGV * G + CBV * B + (1 << 19) + (512 << 20)) >> 20) << 6;
+                    const uint32_t U = (uint32_t)sat10((Cvt::cru * R + Cvt::cgu * G + Cvt::cbu * B + (1 << 19) + (512 << 20)) >> 20) << 6;
+                    const uint32_t V = (uint32_t)sat10((Cvt::cbu * R + Cvt::cgv * G + Cvt::cbv * B + (1 << 19) + (512 << 20)) >> 20) << 6;
                     cb = U | (V << 16);
                 }
                 const uint32_t c2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)cb, 0xaa, 0xf, 0xf, true);
@@ -561,15 +554,13 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
     } else {
         // NV12 output: luma for every pixel, chroma from the even-row / even-column pixels; four lanes' bytes are
         // collected in the first lane of each quad (DPP quad_perm) and stored as one dword
-        ColourCoef kc = {};
+        Coef kc = {};
         if constexpr (COLOUR) kc = colour_coef_here();
 #pragma unroll
         for (int j = 0; j < RW; j++) {
             const int y = y0 + wave * RW + j;
             if (y >= a.dh) break;  // uniform
-            uint32_t yb;
-            if constexpr (COLOUR) yb = bgr_to_y(kc, out[j]);
-            else yb = bgr_to_y(out[j]);
+            const uint32_t yb = bgr_to_y(kc, out[j]);
             const uint32_t y1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0x55, 0xf, 0xf, true);
             const uint32_t y2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0xaa, 0xf, 0xf, true);
             const uint32_t y3 = (uint32_t)__builtin_amdgcn_mov_dpp((int)yb, 0xff, 0xf, 0xf, true);
@@ -583,9 +574,7 @@ __device__ __forceinline__ bool warp_tile(const FusedArgs &ta, uint32_t *smem, c
                 }
             }
             if (!(y & 1)) {
-                uint32_t cb;
-                if constexpr (COLOUR) cb = bgr_to_uv(kc, out[j]);
-                else cb = bgr_to_uv(out[j]);
+                const uint32_t cb = bgr_to_uv(kc, out[j]);
                 const uint32_t c2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)cb, 0xaa, 0xf, 0xf, true);
                 const uint32_t cw = cb | (c2 << 16);
                 uint8_t *c = a.dst_uv + ((size_t)(uint32_t)(y >> 1) * a.pitch_dst_uv + (uint32_t)x);

@@ -43,13 +43,10 @@ __device__ __forceinline__ void sample10(const P010Args &a, float ax, float ay, 
     if (!(far || X >= a.sw || X + 1 < 0 || Y >= a.sh || Y + 1 < 0)) {
         const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
         int b0, g0, r0, b1, g1, r1, b2, g2, r2, b3, g3, r3;
-        if constexpr (COLOUR) {
-            fetch_row10(a, a.col, X, Y, b0, g0, r0, b1, g1, r1);
-            fetch_row10(a, a.col, X, Y + 1, b2, g2, r2, b3, g3, r3);
-        } else {
-            fetch_row10(a, X, Y, b0, g0, r0, b1, g1, r1);
-            fetch_row10(a, X, Y + 1, b2, g2, r2, b3, g3, r3);
-        }
+        // the coefficient source (vstab_device10.hpp): a.col itself, not a copy of it, or cvtColor's constants
+        const auto &k = [&]() -> decltype(auto) { if constexpr (COLOUR) return (a.col); else return CvtColor10{}; }();
+        fetch_row10(a, k, X, Y, b0, g0, r0, b1, g1, r1);
+        fetch_row10(a, k, X, Y + 1, b2, g2, r2, b3, g3, r3);
         if constexpr (BLEND == VSTAB_BLEND_FP16) {
             B = blend_fp16(b0, b1, b2, b3, w00, w01, w10, w11);
             G = blend_fp16(g0, g1, g2, g3, w00, w01, w10, w11);
@@ -123,8 +120,9 @@ __global__ void __launch_bounds__(256) k_cvt_bgr10_p010(const uint8_t *__restric
     const uint16_t *s = reinterpret_cast<const uint16_t *>(src + (size_t)y * pitch_src) + 3 * (size_t)px;
     const bool two = px + 1 < w;
     const int B0 = s[0], G0 = s[1], R0 = s[2], B1 = two ? s[3] : 0, G1 = two ? s[4] : 0, R1 = two ? s[5] : 0;
+    using C = CvtColor10;  // cvtColor's constants at 10 bits (vstab_device.hpp)
     constexpr int half = 1 << 19;
-    const int y0 = sat10((CRY * R0 + CGY * G0 + CBY * B0 + half + (64 << 20)) >> 20), y1 = sat10((CRY * R1 + CGY * G1 + CBY * B1 + half + (64 << 20)) >> 20);
+    const int y0 = sat10((C::cry * R0 + C::cgy * G0 + C::cby * B0 + half + (C::yoff << 20)) >> 20), y1 = sat10((C::cry * R1 + C::cgy * G1 + C::cby * B1 + half + (C::yoff << 20)) >> 20);
     uint16_t *oy = reinterpret_cast<uint16_t *>(dy + (size_t)y * pitch_y) + px;
     if (two && (reinterpret_cast<uintptr_t>(oy) & 3) == 0) *reinterpret_cast<uint32_t *>(oy) = ((uint32_t)y0 << 6) | ((uint32_t)y1 << 22);
     else {
@@ -132,12 +130,13 @@ __global__ void __launch_bounds__(256) k_cvt_bgr10_p010(const uint8_t *__restric
         if (two) oy[1] = (uint16_t)(y1 << 6);
     }
     if (!(y & 1)) {
-        const int U = sat10((CRU * R0 + CGU * G0 + CBU * B0 + half + (512 << 20)) >> 20), V = sat10((CBU * R0 + CGV * G0 + CBV * B0 + half + (512 << 20)) >> 20);
+        const int U = sat10((C::cru * R0 + C::cgu * G0 + C::cbu * B0 + half + (512 << 20)) >> 20), V = sat10((C::cbu * R0 + C::cgv * G0 + C::cbv * B0 + half + (512 << 20)) >> 20);
         *reinterpret_cast<uint32_t *>(duv + (size_t)(y >> 1) * pitch_uv + (size_t)px * 2) = ((uint32_t)U << 6) | ((uint32_t)V << 22);
     }
 }
 
-// k_cvt_bgr10_p010 with a colour spec: the inverse of "Colour matrix and range at 10 bits" (include/vstab.h), k: the spec's row.
+// k_cvt_bgr10_p010 with a colour spec: the inverse of "Colour matrix and range at 10 bits" (include/vstab.h), k: the spec's row.  Its own
+// body: bgr10_to_y / bgr10_to_uv with cvtColor's constants do not compile to k_cvt_bgr10_p010's instructions.
 __global__ void __launch_bounds__(256) k_cvt_bgr10_p010_colour(const uint8_t *__restrict__ src, size_t pitch_src, int w, int h, uint8_t *__restrict__ dy,
                                                                size_t pitch_y, uint8_t *__restrict__ duv, size_t pitch_uv, ColourCoef k) {
     const int px = (blockIdx.x * 64 + (threadIdx.x & 63)) * 2, y = blockIdx.y * 4 + (threadIdx.x >> 6);

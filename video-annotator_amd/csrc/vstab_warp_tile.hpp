@@ -71,12 +71,8 @@ __device__ __forceinline__ uint32_t wave_reduce_pk_i16(uint32_t v) {
 }
 
 // One pixel sampled straight from global memory (per-tap zeroing): the rare path.  sx, sy = rint(32 * map).
-__device__ __forceinline__ uint32_t gather_pixel_far(const WarpArgs &a, int sx, int sy) {
-    const int X = sx >> 5, Y = sy >> 5;
-    if (!(X < a.sw && X + 1 >= 0 && Y < a.sh && Y + 1 >= 0)) return 0;
-    return gather_pixel(a, sx, sy);
-}
-__device__ __forceinline__ uint32_t gather_pixel_far(const WarpArgs &a, const ColourCoef &k, int sx, int sy) {
+template <typename K>
+__device__ __forceinline__ uint32_t gather_pixel_far(const WarpArgs &a, const K &k, int sx, int sy) {
     const int X = sx >> 5, Y = sy >> 5;
     if (!(X < a.sw && X + 1 >= 0 && Y < a.sh && Y + 1 >= 0)) return 0;
     return gather_pixel(a, k, sx, sy);
