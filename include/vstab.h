@@ -521,8 +521,8 @@ VSTAB_API vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const v
 /* ---- Tracker options -----------------------------------------------------------------------------------------------------------------
  * calcOpticalFlowPyrLK's maxLevel, criteria (count and epsilon), minEigThreshold, flags and err: a restatement of OpenCV 4.5's CPU
  * LKTrackerInvoker in this library's arithmetic (exact integer sums converted once, the float operations in the documented order).  It
- * claims no bit equality with OpenCV.  winSize stays 21 x 21 and is not offered, as blockSize other than 3 is not offered for the detector:
- * the kernel's staging, its seven window pixels per lane and its LDS layout are built on it.
+ * claims no bit equality with OpenCV.  winSize is 21 x 21 here; the other offered windows are "Tracker window" below (blockSize other than
+ * 3 is still not offered for the detector).
  *   1. Levels.  The pyramid has min(levels of vstab_pyr_lk, max_level + 1) levels.  Everything else about a level is as in vstab_pyr_lk.
  *   2. Start of the top level.  With VSTAB_LK_USE_INITIAL_FLOW next_xy is also an input: the top level L starts the next-image estimate at
  *      next_xy[i] * (float)(1.0 / (1 << L)); without the flag at the scaled previous point.  The previous image's side -- the window, the
@@ -552,6 +552,28 @@ enum { VSTAB_LK_USE_INITIAL_FLOW = 4, VSTAB_LK_GET_MIN_EIGENVALS = 8 }; /* OpenC
 VSTAB_API vstab_status vstab_pyr_lk_ex(const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height,
                                        const float *prev_xy, int n, float *next_xy, unsigned char *status, float *err /* may be NULL */,
                                        int max_level, int max_iter, double eps, double min_eig_threshold, int flags, void *stream);
+
+/* ---- Tracker window ------------------------------------------------------------------------------------------------------------------
+ * calcOpticalFlowPyrLK's winSize: a square odd window of W x W pixels, W = 15, 21 or 31.  Every other value is refused, not clamped -- even
+ * sizes, other odd sizes; there is no rectangular form.  "Tracker options" rules 1 - 6 hold with W in the place of 21:
+ *   Half.          half = (float)((W - 1) / 2): 7, 10 or 15.
+ *   Window origin. floor(p * 2^-l - half) in float, for the previous point, an iteration's estimate and the final position alike.
+ *   Range test.    The origin is tested against [-W, w_l) x [-W, h_l); NaN, infinities and values outside int fail, as in vstab_pyr_lk.
+ *   Levels.        The pyramid has min(levels_W(width, height), max_level + 1) levels, at most 4.  levels_W halves with (n + 1) / 2 and stops
+ *                  before the first level with w_l <= W || h_l <= W: the window sets the pyramid's depth as buildOpticalFlowPyramid does.
+ *   Padding.       REFLECT_101 of both images, folded as often as it takes (a 31-pixel window on a 20-pixel image folds more than once);
+ *                  derivatives outside the image are zero.
+ *   minEig.        The divisor of rule 4 (and what rule 6 reports) is (float)(2 * W * W).
+ *   err.           Rule 5 with f = next - half over the W * W window pixels and err = (float)S / (float)(32 * W * W); S is an integer
+ *                  <= W * W * 8160 < 2^24 for W <= 31.
+ *   Unchanged.     The iteration cap, eps^2, the oscillation rule's 0.01, the 2^-20 scale of the sums and the 14-bit weights.
+ * With W = 21 this is "Tracker options" bit for bit.  No bit equality with OpenCV is claimed, as before.
+ * vstab_pyr_lk_win takes vstab_pyr_lk_ex's arguments and win_size.  With win_size = 21 it is vstab_pyr_lk_ex: the same kernel and the same
+ * bytes.  Refused with VSTAB_ERR_INVALID before any launch, in this order: "vstab_pyr_lk_win: bad argument"; "vstab_pyr_lk_win: win_size
+ * is 15, 21 or 31"; then vstab_pyr_lk_ex's option and flag messages under this name, in their order. */
+VSTAB_API vstab_status vstab_pyr_lk_win(const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height,
+                                        const float *prev_xy, int n, float *next_xy, unsigned char *status, float *err /* may be NULL */,
+                                        int max_level, int max_iter, double eps, double min_eig_threshold, int flags, int win_size, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side motion model.
@@ -1102,6 +1124,13 @@ VSTAB_API vstab_status vstab_set_corner_response(vstab_handle *h, int response, 
  * "vstab_set_tracker_options: no tracker runs on this handle (tracking = 0)"; "vstab_set_tracker_options: the options must be set before
  * the first pull"; then vstab_pyr_lk_ex's four option messages under this name. */
 VSTAB_API vstab_status vstab_set_tracker_options(vstab_handle *h, int max_level, int max_iter, double eps, double min_eig_threshold);
+/* The handle's tracker window ("Tracker window" above): every tracker launch of the handle -- its segments, its chained launches and what
+ * they fetch ahead -- runs with it, and the handle's pyramids have min(levels_W(width, height), max_level + 1) levels.  Independent of
+ * vstab_set_tracker_options: the two may be called in either order.  Without this call, or with 21, the handle runs what it always ran.
+ * Refused with VSTAB_ERR_INVALID and the handle unchanged, in this order: "vstab_set_tracker_window: null handle";
+ * "vstab_set_tracker_window: no tracker runs on this handle (tracking = 0)"; "vstab_set_tracker_window: the window must be set before the
+ * first pull"; "vstab_set_tracker_window: win_size is 15, 21 or 31". */
+VSTAB_API vstab_status vstab_set_tracker_window(vstab_handle *h, int win_size);
 /* vstab_pull_frame / vstab_pull_frame_nv12_planar with kept edges ("Keep edges" above): the next frame, warped by vstab_warp_nv12_keep with
  * the caller's previous output prev (prev_y / prev_uv) -- a second buffer (a ring of two outputs), or dst itself (in place).  A frame that
  * carries a read-out rotation is warped per row, as a plain INTER_LINEAR pull warps it.  Keep pulls and plain pulls may alternate frame by

@@ -177,6 +177,16 @@ class FrameSourceWarp : public FrameSource {
         }
     }
 
+    // calcOpticalFlowPyrLK's winSize for the same call, which passes none (21 x 21): Size(win_size, win_size) for 15, 21 or 31; before the
+    // first pull_frame, in either order with set_tracker_options -- vstab_set_tracker_window
+    void set_tracker_window(int win_size = 21) {
+        const vstab_status st = vstab_set_tracker_window(m_handle, win_size);
+        if (st != VSTAB_OK) {
+            std::fprintf(stderr, "FrameSourceWarp: %s\n", vstab_last_error());
+            throw (int)st;
+        }
+    }
+
     BGRFrame pull_frame() override {  // FrameSourceWarp.cpp:452-476
         if (!m_out) throw -1;
         const vstab_status st = vstab_pull_frame(m_handle, m_out, m_pitch);

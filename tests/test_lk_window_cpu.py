@@ -1,0 +1,291 @@
+"""The tracker's window without a GPU (tests/lk_window_def.py; include/vstab.h, "Tracker window").  (1) At W = 21 the definition is
+lk_options_def.track in every field.  (2) levels_W against a hand table; the residual by brute force at 15 and 31; invariants.  (3) Every
+refusal of vstab_pyr_lk_win, vstab_set_tracker_window and the vstabx_lk_segments_win hook that needs no device, in order, with its message.
+(4) The known-answer set reproduces.  (5) What the GPU test's fixtures reach, asserted against the definition alone."""
+import ctypes
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+import lk_edges as E
+import lk_options_def as D
+import lk_segments as S
+import lk_window_def as W
+
+vs = importlib.import_module("video-annotator_amd")
+
+
+def same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return bool(E.same_floats(a, b).all()) if a.dtype == np.float32 else bool(np.array_equal(a, b))
+
+
+# ---- (1) W = 21 is "Tracker options" -----------------------------------------------------------------------------------------------------
+def both_agree(prev, nxt, pts, what, **kw):
+    a, b = D.track(prev, nxt, pts, **kw), W.track(prev, nxt, pts, 21, **kw)
+    assert set(a) == set(b)
+    for k in a:
+        assert same(a[k], b[k]), (what, k)
+
+
+@pytest.mark.parametrize("size", E.SIZES, ids=E.size_id)
+def test_window_21_is_the_options_definition_on_the_edge_cases(size):
+    w, h = size
+    f = E.frames(w, h, 2)
+    pts = np.concatenate([E.boundary_cases(w, h)[0], E.special_points(w, h)[0]])
+    both_agree(f[0], f[1], pts, size)
+    both_agree(f[0], f[1], pts, (size, "options"), max_level=1, max_iter=4, eps=0.05, min_eig=1e-3, guess=pts + np.float32(0.75))
+
+
+def test_window_21_is_the_options_definition_on_a_segment_pair():
+    frames, pts, _ = S.make_set("jump_640", n=120)
+    both_agree(frames[3], frames[4], pts, "jump_640 3 -> 4")
+    both_agree(frames[3], frames[4], pts, "jump_640 3 -> 4, one iteration", max_iter=1)
+    assert W.geometry(21) == {"LKT": 22, "LKR": S.LKR, "LKJM": S.LKJM, "LKJR": S.LKJR, "SLACK": S.SLACK, "PPL": 7} and W.half(21) == S.HALF
+
+
+def test_window_21_fetch_ahead_model_is_lk_segments():
+    frames, pts, _ = S.make_set("jump_640", n=60)
+    exp = S.expected(frames, pts, [8])
+    a, b = S.fetch_ahead(exp, 640, 360), W.fetch_ahead(exp, 640, 360, 21)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+# ---- (2) levels, geometry, residual ------------------------------------------------------------------------------------------------------
+def test_geometry_table():
+    assert W.geometry(15) == {"LKT": 16, "LKR": 20, "LKJM": 5, "LKJR": 28, "SLACK": 4, "PPL": 4}
+    assert W.geometry(31) == {"LKT": 32, "LKR": 36, "LKJM": 5, "LKJR": 44, "SLACK": 4, "PPL": 16}
+    assert (W.half(15), W.half(21), W.half(31)) == (7.0, 10.0, 15.0)
+    for win in W.WINDOWS:
+        assert win * win * 8160 < 1 << 24 and W.geometry(win)["PPL"] * 16320 * 4080 < 1 << 31 and W.geometry(win)["PPL"] * 4080 ** 2 < 1 << 31
+
+
+# a level exists iff BOTH sides of it are larger than W: the long side is 400 (50 at level 3), the short side decides.  Level k needs
+# ceil(s / 2^k) > W, i.e. s >= W 2^k + 1: the thresholds are 30|31, 60|61, 120|121 at 15; 42|43, 84|85, 168|169 at 21; 62|63, 124|125,
+# 248|249 at 31 -- written out by hand per window, with the sizes next to each (31 / 32 k +- 1 at 31)
+LEVEL_TABLE = {15: {16: 1, 29: 1, 30: 1, 31: 2, 32: 2, 60: 2, 61: 3, 62: 3, 120: 3, 121: 4, 122: 4, 400: 4},
+               21: {22: 1, 41: 1, 42: 1, 43: 2, 44: 2, 84: 2, 85: 3, 86: 3, 168: 3, 169: 4, 170: 4, 400: 4},
+               31: {31: 1, 32: 1, 61: 1, 62: 1, 63: 2, 64: 2, 124: 2, 125: 3, 126: 3, 248: 3, 249: 4, 250: 4, 400: 4}}
+
+
+@pytest.mark.parametrize("win", W.WINDOWS)
+def test_levels_against_the_hand_table(win):
+    for s, nl in LEVEL_TABLE[win].items():
+        assert W.level_sizes(400, s, win)[0] == nl and W.level_sizes(s, 400, win)[0] == nl, (win, s)
+        for ml in range(4):
+            assert W.levels_of(400, s, win, ml) == min(nl, ml + 1)
+    assert [W.level_sizes(130, 80, win)[0] for win in W.WINDOWS] == [3, 2, 2]
+    assert W.level_sizes(333, 181, 21) == S.level_sizes(333, 181)
+    for win in W.NEW_WINDOWS:
+        assert [W.level_sizes(w, h, win)[0] for w, h in W.GPU_SIZES[win]] == W.GPU_LEVELS[win]
+
+
+@pytest.mark.parametrize("win", W.NEW_WINDOWS)
+def test_the_residual_by_brute_force(win):
+    for (w, h), opt in (((130, 80), {}), ((24, 20), {}), ((130, 80), dict(max_iter=2, max_level=0))):
+        prev, nxt = W.pair(w, h)
+        pts = W.points(w, h, win)[::4]
+        r = W.track(prev, nxt, pts, win, **opt)
+        alive = np.flatnonzero(r["status"] == 1)
+        assert alive.size >= 4 and (r["err"][r["status"] == 0] == 0).all()
+        for i in alive[:8]:
+            assert W.residual_brute_force(prev, nxt, pts[i], r["xy"][i], win).view(np.uint32) == r["err"][i].view(np.uint32), (win, w, h, i)
+
+
+@pytest.mark.parametrize("win", W.NEW_WINDOWS)
+def test_invariants(win):
+    prev, nxt = W.pair(130, 80)
+    pts = W.points(130, 80, win)
+    r = W.track(prev, nxt, pts, win)
+    g = W.track(prev, nxt, pts, win, guess=pts.copy())          # a guess equal to the previous point is no guess
+    for k in r:
+        assert same(r[k], g[k]), k
+    hi = W.track(prev, nxt, pts, win, min_eig=1e30)             # a threshold above every window rejects everything
+    assert not hi["status"].any() and same(hi["min_eig"], r["min_eig"]) and (hi["err"] == 0).all()
+    assert (r["min_eig"][r["status"] == 1] >= np.float32(1e-4)).all()             # a tracked point passed the rejection test at level 0
+    # the boundary cases: a start point is tracked at level l iff its origin lies in [-W, n_l)
+    bp, tags = W.boundary_cases(130, 80, win)
+    trk = W.tracked(bp, 130, 80, win)
+    for i, (l, axis, side, io) in enumerate(tags):
+        assert trk[i, l] == (io == "in"), (win, tags[i])
+
+
+# ---- (3) refusals ------------------------------------------------------------------------------------------------------------------------
+def _win(**kw):
+    """vstab_pyr_lk_win with pointers nobody dereferences before the refusal: -> (status, message)"""
+    L = vs.lib
+    a = dict(prev=4096, pp=640, nxt=8192, pn=640, w=640, h=360, n=4, max_level=3, max_iter=30, eps=0.01, min_eig=1e-4, flags=0, err=True, win=31)
+    a.update(kw)
+    xy, out, st, err = np.zeros(8, np.float32), np.zeros(8, np.float32), np.zeros(4, np.uint8), np.zeros(4, np.float32)
+    fp = lambda x: x.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    s = L.vstab_pyr_lk_win(a["prev"], a["pp"], a["nxt"], a["pn"], a["w"], a["h"], fp(xy), a["n"], fp(out), st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                           fp(err) if a["err"] else None, a["max_level"], a["max_iter"], a["eps"], a["min_eig"], a["flags"], a["win"], None)
+    return s, L.vstab_last_error().decode()
+
+
+NAN, INF = float("nan"), float("inf")
+BAD_WINDOWS = (0, 1, 3, 13, 14, 16, 17, 19, 20, 22, 23, 29, 30, 32, 33, 63, -15, -21, 1 << 30, -(1 << 31))
+REFUSALS = [("bad argument", [dict(prev=None), dict(nxt=None), dict(n=-1), dict(w=0), dict(h=-2), dict(pp=639), dict(pn=1)]),
+            ("win_size is 15, 21 or 31", [dict(win=v) for v in BAD_WINDOWS]),
+            ("max_level lies in 0 .. 3", [dict(max_level=-1), dict(max_level=4)]),
+            ("max_iter lies in 1 .. 100", [dict(max_iter=0), dict(max_iter=101)]),
+            ("eps is finite and lies in [0, 10]", [dict(eps=-1e-300), dict(eps=NAN), dict(eps=INF)]),
+            ("min_eig_threshold is finite and not negative", [dict(min_eig=-1e-300), dict(min_eig=NAN), dict(min_eig=INF)]),
+            ("unknown flag", [dict(flags=1), dict(flags=16), dict(flags=-1)]),
+            ("VSTAB_LK_GET_MIN_EIGENVALS needs err", [dict(flags=8, err=False), dict(flags=12, err=False)])]
+
+
+def test_pyr_lk_win_refusals_in_order():
+    for k, (msg, bads) in enumerate(REFUSALS):
+        want = (vs.ERR_INVALID, "vstab_pyr_lk_win: " + msg)
+        for bad in bads:
+            assert _win(**bad) == want, bad
+            for later_msg, later in REFUSALS[k + 1:]:       # everything later in the order is wrong too: the earlier message wins
+                assert _win(**{**later[0], **bad}) == want, (bad, later[0])
+    for win in W.WINDOWS:                                    # the option refusals hold under every offered window
+        assert _win(win=win, max_level=7) == (vs.ERR_INVALID, "vstab_pyr_lk_win: max_level lies in 0 .. 3")
+
+
+def test_the_binding_knows_the_entry_points():
+    assert "vstab_pyr_lk_win" in vs.SIGNATURES and "vstab_set_tracker_window" in vs.SIGNATURES
+    assert hasattr(vs.lib, "vstabx_lk_segments_win") and hasattr(vs.lib, "vstabx_lk_segments")
+    assert callable(vs.pyr_lk_win) and callable(vs.Stabilizer.set_tracker_window)
+
+
+def test_set_tracker_window_refuses_a_null_handle():
+    for win in (21, 31, 16):                                 # before the window's own message
+        assert vs.lib.vstab_set_tracker_window(None, win) == vs.ERR_INVALID
+        assert vs.lib.vstab_last_error().decode() == "vstab_set_tracker_window: null handle"
+
+
+def test_hook_refuses_without_a_device():
+    class Fake:   # a "device" plane: only its pointer and pitch reach the library, which refuses before using them
+        def __init__(self, ptr, pitch, shape):
+            self.ptr, self.pitch, self.shape = ptr, pitch, shape
+
+        def data_ptr(self):
+            return self.ptr
+
+        def stride(self, d):
+            return self.pitch
+
+    def refused(msg, frames, pts, segs, **kw):
+        with pytest.raises(vs.VstabError) as e:
+            vs.lk_segments(frames, pts, segs, stream=ctypes.c_void_p(), **kw)
+        assert e.value.status == vs.ERR_INVALID and vs.lib.vstab_last_error().decode() == "vstabx_lk_segments_win: " + msg, str(e.value)
+
+    w, h = 640, 360
+    fr = [Fake(4096 * (i + 1), 640, (h, w)) for i in range(9)]
+    pts = np.array([[100.0, 100.0]], np.float32)
+    for win in (0, 14, 16, 20, 22, 32, -31):
+        refused("win_size is 15, 21 or 31", fr, pts, [8], win=win)
+        refused("win_size is 15, 21 or 31", fr, pts, [9], win=win)           # before the segment's message
+        refused("bad argument", fr, pts, [8], win=win, w=0)                  # behind the argument check
+    for win in W.NEW_WINDOWS:
+        refused("a launch covers 1 .. LK_SEG_MAX frame pairs", fr, pts, [9], win=win)
+        refused("bad_parent is not a chained launch", fr, pts, [4, 4], bad_parent=0, win=win)
+        refused("bad frame", [Fake(4096, 639, (h, w))] + fr[1:], pts, [8], win=win)
+    # pack mode needs a second level: 40 x 32 has one at 15 and none at 31; 40 x 30 has none at either
+    for (sw, sh), win, ok in (((40, 32), 31, False), ((40, 30), 15, False), ((40, 32), 15, True)):
+        small = [Fake(4096, 64, (sh, sw))] * 9
+        msg = "planes not aligned for the fused copy" if ok else "a one-level pyramid has no level 1 to pack"
+        refused(msg, small, pts, [8], uv=small, rings=[Fake(4100, 0, (sh, sw))] * 9, win=win)
+
+
+# ---- (4) the known answers ----------------------------------------------------------------------------------------------------------------
+def test_known_answers_reproduce():
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_lk_window_golden as G
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lk_window_kat.npz")
+    assert os.path.getsize(path) < 100 * 1024
+    kat = np.load(path)
+    for name, (prev, nxt, pts, win, opt, guess) in G.cases().items():
+        assert 16 <= len(pts) <= 64
+        assert np.array_equal(kat[name + "_pts"].view(np.uint32), pts.view(np.uint32)), name
+        if guess is not None:
+            assert np.array_equal(kat[name + "_guess"].view(np.uint32), guess.view(np.uint32)), name
+        r = W.track(prev, nxt, pts, win, guess=guess, **opt)
+        for k in G.KEYS:
+            assert same(kat[f"{name}_{k}"], r[k]), (name, k)
+        assert r["status"].any() and not r["status"].all(), name
+
+
+# ---- (5) what the GPU test's fixtures reach -----------------------------------------------------------------------------------------------
+def differs_from_21(prev, nxt, pts, win, **kw):
+    a, b = W.track(prev, nxt, pts, win, **kw), W.track(prev, nxt, pts, 21, **kw)
+    return a, int((~E.same_floats(a["xy"], b["xy"]).all(1)).sum())
+
+
+@pytest.mark.parametrize("win", W.NEW_WINDOWS)
+def test_main_cases(win):
+    """each main case: at least half of the grid tracked, other bits than W = 21 somewhere, and every boundary of the range test on both sides"""
+    for (w, h), nl in zip(W.GPU_SIZES[win], W.GPU_LEVELS[win]):
+        prev, nxt = W.pair(w, h)
+        pts = W.points(w, h, win)
+        ng = len(D.grid(w, h))
+        r, diff = differs_from_21(prev, nxt, pts, win)
+        assert r["nl"] == nl and 2 * int(r["status"][:ng].sum()) >= ng and diff > 0, (win, w, h)
+        trk = W.tracked(pts[ng:], w, h, win)
+        tags = W.boundary_cases(w, h, win)[1]
+        assert {(l, a, s, io) for l, a, s, io in tags} == {(l, a, s, io) for l in range(nl) for a in (0, 1) for s in ("lo", "hi") for io in ("in", "out")}
+        assert all(trk[i, l] == (io == "in") for i, (l, a, s, io) in enumerate(tags))
+    assert min(h for w, h in W.GPU_SIZES[15]) <= 16 and (24, 20) in W.GPU_SIZES[31]
+
+
+@pytest.mark.parametrize("win", W.NEW_WINDOWS)
+def test_option_cases(win):
+    w, h = W.GPU_SIZES[win][0]
+    ng = len(D.grid(w, h))
+    prev, nxt = D.moved_pair(w, h)
+    pts = W.points(w, h, win)
+    r, diff = differs_from_21(prev, nxt, pts, win, **W.COMBINED)
+    plain = W.track(prev, nxt, pts, win)
+    assert 2 * int(r["status"][:ng].sum()) >= ng and diff > 0 and not same(r["xy"], plain["xy"])
+    a, b = W.pair(w, h)
+    g = W.guesses(w, h, win)
+    assert set(g) == {"truth_pm3", "far_side", "block_across_border", "specials"}
+    for name, (p, guess) in g.items():
+        r, r21 = W.track(a, b, p, win, guess=guess), W.track(a, b, p, 21, guess=guess)
+        if name in ("truth_pm3", "far_side"):
+            assert 2 * int(r["status"].sum()) >= len(p) and not same(r["xy"], r21["xy"]), (win, name)
+    # the blocks of block_across_border do cross the border of the top level, one side each and two corners
+    nl, sizes = W.level_sizes(w, h, win)
+    (wl, hl), jr = sizes[nl - 1], W.geometry(win)["LKJR"]
+    org = W._floor_i(g["block_across_border"][1] * np.float32(2.0 ** -(nl - 1)) - W.half(win)) - 5
+    # (left, right, top, bottom; on a top level lower than the block a block crosses top or bottom wherever it sits: only the sides meant are asked)
+    sides = [(bool(x < 0), bool(x + jr > wl), bool(y < 0), bool(y + jr > hl)) for x, y in org]
+    meant = [(0,), (1,), (2,), (3,), (0, 2), (1, 3)]
+    assert len(sides) == len(meant) and all(all(s[i] for i in m) for s, m in zip(sides, meant)), (win, sides)
+    assert W.tracked(g["block_across_border"][0], w, h, win).all()
+    # max_iter = 1 on the jump pair: the residual's window leaves the staged block
+    jp, jn, jpts = W.jump_pair()
+    r, diff = differs_from_21(jp, jn, jpts, win, max_iter=1)
+    assert r["resid_restaged"].sum() >= 5 and 2 * int(r["status"].sum()) >= len(jpts) and diff > 0
+
+
+@pytest.mark.parametrize("win", W.NEW_WINDOWS)
+def test_segment_clips_reach_every_fetch_ahead_branch(win):
+    """over the three clips, with fi > 0: every level's neighbourhood and the top block are served, missed and not fetched; slots are lost
+    mid-segment (status 0, then 2); and the records differ from the 21-pixel window's"""
+    total = {}
+    for name in W.SEGMENT_CLIPS:
+        frames, pts, exps = W.segment_case(name, win)
+        assert set(exps) == set(W.SEGMENTATIONS)
+        for segs, exp in exps.items():
+            assert exp["nl"] == 4
+            neigh, top = W.fetch_ahead(exp, 640, 360, win)
+            for k, v in S.reached(neigh, top, exp["fi"], exp["nl"]).items():
+                total[(segs,) + k] = total.get((segs,) + k, 0) + v
+            assert (exp["status"] == 2).any() and ((exp["status"] == 0) & (exp["fi"][:, None] > 0)).any(), (win, name)
+            assert 2 * int((exp["status"][0] == 1).sum()) >= len(pts)
+        a, b = exps[(8,)], exps[(3, 3, 2)]
+        assert np.array_equal(a["status"], b["status"]) and same(a["xy"], b["xy"])      # the definition does not see the segmentation
+        assert not same(a["xy"][0], W.track(frames[0], frames[1], pts, 21)["xy"]), (win, name)
+    for segs in W.SEGMENTATIONS:
+        for c in ("served", "missed", "not_fetched"):
+            for l in range(4):
+                assert total.get((segs, "neigh", l, c), 0) > 0, (win, segs, l, c)
+            assert total.get((segs, "top", c), 0) > 0, (win, segs, c)

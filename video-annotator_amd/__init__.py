@@ -211,6 +211,8 @@ SIGNATURES = {
     "vstab_good_features_harris": (_i, [_vp, _sz, _i, _i, _vp, _sz, _i, _d, _d, _d, _i, _fp, _ip, _ip, _vp]),
     "vstab_set_corner_response": (_i, [_vp, _i, _d]),
     "vstab_set_tracker_options": (_i, [_vp, _i, _i, _d, _d]),
+    "vstab_pyr_lk_win": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _fp, _u8p, _fp, _i, _i, _d, _d, _i, _i, _vp]),
+    "vstab_set_tracker_window": (_i, [_vp, _i]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(_L, _name)  # AttributeError here = header/library mismatch: fail loudly
@@ -219,6 +221,8 @@ for _name, (_res, _args) in SIGNATURES.items():
 _L.vstabx_lk_segments.restype = _i
 _L.vstabx_lk_segments.argtypes = [_pp, _c.POINTER(_sz), _i, _i, _fp, _i, _ip, _i, _pp, _c.POINTER(_sz), _pp, _i, _c.POINTER(_c.c_uint32),
                                   _c.POINTER(_c.c_uint32), _u8p, _vp]
+_L.vstabx_lk_segments_win.restype = _i
+_L.vstabx_lk_segments_win.argtypes = _L.vstabx_lk_segments.argtypes[:-1] + [_i, _vp]   # ... pyr_out, win, stream
 
 _L.vstabx_warps_from_cache.restype = _c.c_long
 _L.vstabx_warps_from_cache.argtypes = [_vp]
@@ -1012,10 +1016,8 @@ def pyr_lk(prev, nxt, pts):
 LK_USE_INITIAL_FLOW, LK_GET_MIN_EIGENVALS = 4, 8   # calcOpticalFlowPyrLK's flags (OpenCV's values)
 
 
-def pyr_lk_ex(prev, nxt, pts, max_level=3, max_iter=30, eps=0.01, min_eig_threshold=1e-4, flags=0, guess=None, want_err=True):
-    """vstab_pyr_lk_ex (include/vstab.h, "Tracker options"): calcOpticalFlowPyrLK with maxLevel, the criteria's count and epsilon,
-    minEigThreshold, flags and err; winSize stays 21 x 21.  guess: the n start positions in the next image, read with LK_USE_INITIAL_FLOW
-    (any float).  -> (next points (n, 2) float32, status (n,) uint8, err (n,) float32 or None without want_err)."""
+def _pyr_lk_with_options(name, tail, prev, nxt, pts, max_level, max_iter, eps, min_eig_threshold, flags, guess, want_err):
+    """the call of vstab_pyr_lk_ex and vstab_pyr_lk_win: `tail` is what stands between flags and the stream"""
     h, w = prev.shape
     p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
     n = p.shape[0]
@@ -1024,19 +1026,32 @@ def pyr_lk_ex(prev, nxt, pts, max_level=3, max_iter=30, eps=0.01, min_eig_thresh
         out[:] = np.asarray(guess, np.float32).reshape(-1, 2)
     st = np.zeros(n, np.uint8)
     err = np.zeros(n, np.float32) if want_err else None
-    _check(_L.vstab_pyr_lk_ex(prev.data_ptr(), prev.stride(0), nxt.data_ptr(), nxt.stride(0), w, h, _fptr(p), n, _fptr(out), st.ctypes.data_as(_u8p),
-                              _fptr(err) if want_err else None, int(max_level), int(max_iter), float(eps), float(min_eig_threshold), int(flags), _stream()),
-           "vstab_pyr_lk_ex")
+    _check(getattr(_L, name)(prev.data_ptr(), prev.stride(0), nxt.data_ptr(), nxt.stride(0), w, h, _fptr(p), n, _fptr(out), st.ctypes.data_as(_u8p),
+                             _fptr(err) if want_err else None, int(max_level), int(max_iter), float(eps), float(min_eig_threshold), int(flags), *tail,
+                             _stream()), name)
     return out, st, err
 
 
-def lk_segments(frames, pts, segs, uv=None, rings=None, bad_parent=-1, want_pyr=False, w=None, h=None, stream=None):
+def pyr_lk_ex(prev, nxt, pts, max_level=3, max_iter=30, eps=0.01, min_eig_threshold=1e-4, flags=0, guess=None, want_err=True):
+    """vstab_pyr_lk_ex (include/vstab.h, "Tracker options"): calcOpticalFlowPyrLK with maxLevel, the criteria's count and epsilon,
+    minEigThreshold, flags and err; winSize is 21 x 21 (pyr_lk_win takes another).  guess: the n start positions in the next image, read
+    with LK_USE_INITIAL_FLOW (any float).  -> (next points (n, 2) float32, status (n,) uint8, err (n,) float32 or None without want_err)."""
+    return _pyr_lk_with_options("vstab_pyr_lk_ex", (), prev, nxt, pts, max_level, max_iter, eps, min_eig_threshold, flags, guess, want_err)
+
+
+def pyr_lk_win(prev, nxt, pts, win_size, max_level=3, max_iter=30, eps=0.01, min_eig_threshold=1e-4, flags=0, guess=None, want_err=True):
+    """vstab_pyr_lk_win (include/vstab.h, "Tracker window"): pyr_lk_ex with calcOpticalFlowPyrLK's winSize, win_size x win_size for 15, 21
+    or 31; with 21 it is pyr_lk_ex."""
+    return _pyr_lk_with_options("vstab_pyr_lk_win", (int(win_size),), prev, nxt, pts, max_level, max_iter, eps, min_eig_threshold, flags, guess, want_err)
+
+
+def lk_segments(frames, pts, segs, uv=None, rings=None, bad_parent=-1, want_pyr=False, w=None, h=None, stream=None, win=21):
     """Test hook vstabx_lk_segments (not part of include/vstab.h): the K + 1 (h, w) uint8 device luma views `frames` (pitched views
     allowed), n start points, launches of segs[s] frame pairs each (sum K), the first from pts and every later one chained behind the
     one before.  uv / rings (K + 1 device tensors each): level 1 and the ring copy by k_pack_pyr.  bad_parent: the launch that gets a
     wrong parent tag.  -> (host records (K, n, 4) uint32, device records (K, n, 4) uint32, pyramid bytes (K + 1, ...) uint8 or None).
     w / h / pts / frames are taken as given, and stream (default: torch's current one), so that a test of the refusals can hand in what
-    it likes without a device."""
+    it likes without a device.  win: the tracker's window; any other than 21 goes through vstabx_lk_segments_win."""
     n_fr = len(frames)
     h = frames[0].shape[0] if h is None else h
     w = frames[0].shape[1] if w is None else w
@@ -1059,13 +1074,17 @@ def lk_segments(frames, pts, segs, uv=None, rings=None, bad_parent=-1, want_pyr=
         lw, lh, nb = w, h, 0
         for _ in range(3):
             lw, lh = (lw + 1) // 2, (lh + 1) // 2
-            if lw <= 21 or lh <= 21:
+            if lw <= win or lh <= win:
                 break
             nb += lw * lh
         pyr = np.zeros((n_fr, max(nb, 1)), np.uint8)
-    _check(_L.vstabx_lk_segments(fptrs, fpit, int(w), int(h), _fptr(p), n, sg.ctypes.data_as(_ip), int(sg.size), uptrs, upit, rptrs,
-                                 int(bad_parent), hrec.ctypes.data_as(_c.POINTER(_c.c_uint32)), drec.ctypes.data_as(_c.POINTER(_c.c_uint32)),
-                                 None if pyr is None else pyr.ctypes.data_as(_u8p), _stream() if stream is None else stream), "vstabx_lk_segments")
+    args = (fptrs, fpit, int(w), int(h), _fptr(p), n, sg.ctypes.data_as(_ip), int(sg.size), uptrs, upit, rptrs, int(bad_parent),
+            hrec.ctypes.data_as(_c.POINTER(_c.c_uint32)), drec.ctypes.data_as(_c.POINTER(_c.c_uint32)), None if pyr is None else pyr.ctypes.data_as(_u8p))
+    st = _stream() if stream is None else stream
+    if win == 21:   # the hook as it always was
+        _check(_L.vstabx_lk_segments(*args, st), "vstabx_lk_segments")
+    else:           # vstabx_lk_segments_win: the tracker's window (15 or 31; anything else is refused there)
+        _check(_L.vstabx_lk_segments_win(*args, int(win), st), "vstabx_lk_segments_win")
     return hrec, drec, pyr
 
 
@@ -1167,8 +1186,9 @@ class Stabilizer:
     source for `total` pulls) or a Python iterable of such tensors (python callback source)."""
 
     def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, calibration=None,
-                 calibration_ex=None, pinhole=None, detection_mask=None, corner_response=None, harris_k=0.04, tracker_options=None, **cfg_kw):
+                 calibration_ex=None, pinhole=None, detection_mask=None, corner_response=None, harris_k=0.04, tracker_options=None, tracker_window=None, **cfg_kw):
         """tracker_options: (max_level, max_iter, eps, min_eig) for set_tracker_options right after create.
+        tracker_window: 15, 21 or 31 for set_tracker_window right after create.
         corner_response: set_corner_response(corner_response, harris_k) right after create (CORNER_HARRIS or CORNER_MIN_EIGENVAL).
         detection_mask: set_detection_mask right after create (a device tensor or a numpy array of the luma plane's size).
         border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
@@ -1248,6 +1268,13 @@ class Stabilizer:
             self.set_corner_response(corner_response, harris_k)
         if tracker_options is not None:
             self.set_tracker_options(*tracker_options)
+        if tracker_window is not None:
+            self.set_tracker_window(tracker_window)
+
+    def set_tracker_window(self, win_size):
+        """vstab_set_tracker_window: calcOpticalFlowPyrLK's winSize (15, 21 or 31) for every tracker launch of this handle, before the first
+        pull; 21 is the handle as it always was.  Independent of set_tracker_options."""
+        _check(_L.vstab_set_tracker_window(self._h, int(win_size)), "vstab_set_tracker_window")
 
     def set_tracker_options(self, max_level=3, max_iter=30, eps=0.01, min_eig=1e-4):
         """vstab_set_tracker_options: calcOpticalFlowPyrLK's maxLevel, criteria and minEigThreshold for every tracker launch of this handle,

@@ -40,6 +40,7 @@ vstab_status preload_pyramid_kernels();
 vstab_status preload_corner_kernels();
 vstab_status preload_corners_fused_kernels();
 vstab_status preload_lk_kernels();
+vstab_status preload_lk_win_kernels();
 vstab_status preload_plane_kernels();
 vstab_status preload_warp_kernels();
 vstab_status preload_fused_kernels();

@@ -1,8 +1,10 @@
-// vstab_lk_body.hpp -- the body of the tracker kernels, included by vstab_lk.hip into k_lk_track (OPT = false) and k_lk_track_opt (OPT = true)
-// and by nothing else.  No include guard: it is statements, not declarations.  In scope where it is included: the kernel's argument `args`
-// (LkSegArgs), its LDS state `sh` (LkShared) and `constexpr bool OPT`.  Why a text and not a function: vstab_lk.hip, above the two kernels.
+// vstab_lk_body.hpp -- the body of the tracker kernels, included by vstab_lk_window.hpp into k_lk_track (OPT = false) and k_lk_track_opt
+// (OPT = true) of the 21 x 21 window and into k_lk_track_win (OPT = true) of every other one, and by nothing else.  No include guard: it is
+// statements, not declarations.  In scope where it is included: the kernel's argument `args` (LkSegArgs), its LDS state `sh` (LkShared),
+// `constexpr bool OPT` and the window's constants (LKW, LKT, LKJR, LK_PPL, LK_HALF ...).  Why a text and not a function:
+// vstab_lk_window.hpp, above the kernels.
 #ifndef VSTAB_LK_BODY_FROM_KERNEL
-#error "vstab_lk_body.hpp is the body of the kernels of vstab_lk.hip"
+#error "vstab_lk_body.hpp is the body of the kernels of vstab_lk_window.hpp"
 #endif
     const LkThread t = {(int)blockIdx.x, (int)threadIdx.x, (int)threadIdx.x & 63, __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6)};
     if (t.f >= args.n) return;

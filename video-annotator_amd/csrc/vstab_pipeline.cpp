@@ -731,6 +731,17 @@ vstab_status vstab_set_tracker_options(vstab_handle *h, int max_level, int max_i
     return VSTAB_OK;
 }
 
+// The handle's tracker window (vstab.h, "Tracker window"): read by every tracker launch of the handle -- segments, chained launches and
+// their fetch-ahead -- and the pyramids get the depth that window asks for (Tracker::set_window).
+vstab_status vstab_set_tracker_window(vstab_handle *h, int win_size) {
+    const std::string n = "vstab_set_tracker_window: ";
+    if (!h) return fail(VSTAB_ERR_INVALID, n + "null handle");
+    if (!h->cfg.tracking) return fail(VSTAB_ERR_INVALID, n + "no tracker runs on this handle (tracking = 0)");
+    if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the window must be set before the first pull");
+    if (!lk_window_offered(win_size)) return fail(VSTAB_ERR_INVALID, n + "win_size is 15, 21 or 31");
+    return h->tracker.set_window(win_size);
+}
+
 vstab_status vstab_set_input_calibration_ex(vstab_handle *h, const double K[9], const double D[4]) {
     return set_input_calibration(h, K, D, "vstab_set_input_calibration_ex", true);
 }

@@ -44,6 +44,7 @@ vstab_status vstab_preload_kernels(void) {
     VSTAB_TRY(preload_corner_kernels());
     VSTAB_TRY(preload_corners_fused_kernels());
     VSTAB_TRY(preload_lk_kernels());
+    VSTAB_TRY(preload_lk_win_kernels());
     VSTAB_TRY(preload_plane_kernels());
     VSTAB_TRY(preload_warp_kernels());
     VSTAB_TRY(preload_fused_kernels());
@@ -210,16 +211,18 @@ vstab_status vstab_good_features(const void *gray, size_t pitch, int width, int 
 // they are calcOpticalFlowPyrLK's defaults and the launches are the ones vstab_pyr_lk always made
 static vstab_status pyr_lk_op(const char *fn, bool ex, const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height,
                               const float *prev_xy, int n, float *next_xy, unsigned char *status, float *err, int max_level, int max_iter, double eps,
-                              double min_eig_threshold, int flags, void *stream) {
+                              double min_eig_threshold, int flags, void *stream, int win_size = LK_WIN) {
     if (!prev || !next || (n > 0 && (!prev_xy || !next_xy || !status)) || n < 0 || width <= 0 || height <= 0 ||
         pitch_prev < (size_t)width || pitch_next < (size_t)width)
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": bad argument");
+    if (!lk_window_offered(win_size)) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": win_size is 15, 21 or 31");  // (vstab_pyr_lk_win only)
     LkOptions opt;
     if (ex) {
         VSTAB_TRY(check_lk_options(fn, max_level, max_iter, eps, min_eig_threshold, opt));
         if (flags & ~(VSTAB_LK_USE_INITIAL_FLOW | VSTAB_LK_GET_MIN_EIGENVALS)) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": unknown flag");
         if ((flags & VSTAB_LK_GET_MIN_EIGENVALS) && !err) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": VSTAB_LK_GET_MIN_EIGENVALS needs err");
     }
+    opt.win = win_size;
     hipStream_t st = static_cast<hipStream_t>(stream);
     Tracker t;
     VSTAB_TRY(t.init(width, height, opt));
@@ -247,6 +250,14 @@ vstab_status vstab_pyr_lk_ex(const void *prev, size_t pitch_prev, const void *ne
                              void *stream) {
     return pyr_lk_op("vstab_pyr_lk_ex", true, prev, pitch_prev, next, pitch_next, width, height, prev_xy, n, next_xy, status, err, max_level, max_iter, eps,
                      min_eig_threshold, flags, stream);
+}
+
+// vstab.h, "Tracker window": with win_size 21 this is vstab_pyr_lk_ex -- the same launches
+vstab_status vstab_pyr_lk_win(const void *prev, size_t pitch_prev, const void *next, size_t pitch_next, int width, int height, const float *prev_xy, int n,
+                              float *next_xy, unsigned char *status, float *err, int max_level, int max_iter, double eps, double min_eig_threshold, int flags,
+                              int win_size, void *stream) {
+    return pyr_lk_op("vstab_pyr_lk_win", true, prev, pitch_prev, next, pitch_next, width, height, prev_xy, n, next_xy, status, err, max_level, max_iter, eps,
+                     min_eig_threshold, flags, stream, win_size);
 }
 
 }  // extern "C"

@@ -77,34 +77,37 @@ __attribute__((visibility("default"))) int vstabx_dmabuf_cache_sim(const unsigne
 //   bad_parent: the launch of this index (1 .. n_seg - 1; -1 = none) is handed a parent tag that is not its parent's.
 //   host_rec, dev_rec: K * n records of 4 uint32 each, pair-major -- what the kernel left in the mapped and in the device copy.
 //   pyr_out (optional): levels 1 .. of every frame's pyramid, dense, frame after frame.
-// Bad arguments are refused with VSTAB_ERR_INVALID before anything touches the device.
-__attribute__((visibility("default"))) int vstabx_lk_segments(const void *const *frames, const size_t *pitches, int w, int h, const float *pts, int n,
-                                                               const int *seg, int n_seg, const void *const *uv, const size_t *uv_pitches,
-                                                               void *const *rings, int bad_parent, uint32_t *host_rec, uint32_t *dev_rec,
-                                                               uint8_t *pyr_out, void *stream) {
+//   win (vstabx_lk_segments_win; vstabx_lk_segments: 21): the tracker's window, 15, 21 or 31 -- the pyramids get its depth, every launch runs with it.
+// Bad arguments are refused with VSTAB_ERR_INVALID before anything touches the device; fn names the hook in the refusals.
+static int lk_segments_hook(const std::string &fn, const void *const *frames, const size_t *pitches, int w, int h, const float *pts, int n, const int *seg, int n_seg,
+                            const void *const *uv, const size_t *uv_pitches, void *const *rings, int bad_parent, uint32_t *host_rec, uint32_t *dev_rec,
+                            uint8_t *pyr_out, int win, void *stream) {
     if (!frames || !pitches || !pts || !seg || !host_rec || !dev_rec || w <= 0 || h <= 0 || n <= 0 || n_seg <= 0 || n_seg > Tracker::REC_BUFS)
-        return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: bad argument");
+        return fail(VSTAB_ERR_INVALID, fn + ": bad argument");
+    if (!lk_window_offered(win)) return fail(VSTAB_ERR_INVALID, fn + ": win_size is 15, 21 or 31");
     int K = 0;
     for (int s = 0; s < n_seg; s++) {
-        if (seg[s] < 1 || seg[s] > LK_SEG_MAX) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: a launch covers 1 .. LK_SEG_MAX frame pairs");
+        if (seg[s] < 1 || seg[s] > LK_SEG_MAX) return fail(VSTAB_ERR_INVALID, fn + ": a launch covers 1 .. LK_SEG_MAX frame pairs");
         K += seg[s];
     }
     // (the record buffers rotate through REC_BUFS: every pair of the call keeps its own)
-    if (K > Tracker::REC_BUFS) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: more frame pairs than record buffers");
-    if (bad_parent != -1 && (bad_parent < 1 || bad_parent >= n_seg)) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: bad_parent is not a chained launch");
+    if (K > Tracker::REC_BUFS) return fail(VSTAB_ERR_INVALID, fn + ": more frame pairs than record buffers");
+    if (bad_parent != -1 && (bad_parent < 1 || bad_parent >= n_seg)) return fail(VSTAB_ERR_INVALID, fn + ": bad_parent is not a chained launch");
     const bool pack = uv || uv_pitches || rings;
-    if (pack && (!uv || !uv_pitches || !rings)) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: uv, uv_pitches and rings go together");
-    if (pack && lk_levels(w, h) < 2) return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: a one-level pyramid has no level 1 to pack");
+    if (pack && (!uv || !uv_pitches || !rings)) return fail(VSTAB_ERR_INVALID, fn + ": uv, uv_pitches and rings go together");
+    if (pack && lk_levels(w, h, win) < 2) return fail(VSTAB_ERR_INVALID, fn + ": a one-level pyramid has no level 1 to pack");
     for (int i = 0; i <= K; i++) {
         if (!frames[i] || pitches[i] < (size_t)w || pitches[i] >= (1u << 24) || (uint64_t)pitches[i] * (uint64_t)h >= (1ull << 32))
-            return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: bad frame");
+            return fail(VSTAB_ERR_INVALID, fn + ": bad frame");
         // (level 1 is the Tracker's: a hipMalloc'd buffer, pitch (w + 1) / 2 -- the ring stands in for its base, which is aligned)
         if (pack && (!uv[i] || !rings[i] || !pack_pyr_ok(frames[i], pitches[i], uv[i], uv_pitches[i], w, h, rings[i], rings[i], (size_t)((w + 1) / 2))))
-            return fail(VSTAB_ERR_INVALID, "vstabx_lk_segments: planes not aligned for the fused copy");
+            return fail(VSTAB_ERR_INVALID, fn + ": planes not aligned for the fused copy");
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     Tracker t;
-    VSTAB_TRY(t.init(w, h));
+    LkOptions opt;
+    opt.win = win;
+    VSTAB_TRY(t.init(w, h, opt));
     VSTAB_TRY(t.reserve_slots(n));
     const int levels = t.levels();
     size_t pyr_bytes = 0;
@@ -157,6 +160,21 @@ __attribute__((visibility("default"))) int vstabx_lk_segments(const void *const 
             VSTAB_HIP_TRY(hipMemcpy(dev_rec + (size_t)k * n * 4, t.dev_records(launches[s], i), (size_t)n * 16, hipMemcpyDeviceToHost));
         }
     return VSTAB_OK;
+}
+
+__attribute__((visibility("default"))) int vstabx_lk_segments(const void *const *frames, const size_t *pitches, int w, int h, const float *pts, int n,
+                                                               const int *seg, int n_seg, const void *const *uv, const size_t *uv_pitches,
+                                                               void *const *rings, int bad_parent, uint32_t *host_rec, uint32_t *dev_rec,
+                                                               uint8_t *pyr_out, void *stream) {
+    return lk_segments_hook("vstabx_lk_segments", frames, pitches, w, h, pts, n, seg, n_seg, uv, uv_pitches, rings, bad_parent, host_rec, dev_rec, pyr_out, LK_WIN,
+                            stream);
+}
+__attribute__((visibility("default"))) int vstabx_lk_segments_win(const void *const *frames, const size_t *pitches, int w, int h, const float *pts, int n,
+                                                                   const int *seg, int n_seg, const void *const *uv, const size_t *uv_pitches,
+                                                                   void *const *rings, int bad_parent, uint32_t *host_rec, uint32_t *dev_rec,
+                                                                   uint8_t *pyr_out, int win, void *stream) {
+    return lk_segments_hook("vstabx_lk_segments_win", frames, pitches, w, h, pts, n, seg, n_seg, uv, uv_pitches, rings, bad_parent, host_rec, dev_rec, pyr_out, win,
+                            stream);
 }
 
 // the body of vstabx_corners_fused and vstabx_corners_fused_mask (both below); fn names the hook in the refusals, masked says whether `mask` is looked at

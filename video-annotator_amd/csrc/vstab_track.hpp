@@ -8,7 +8,7 @@
 namespace vstab {
 
 constexpr int LK_MAX_LEVELS = 4;  // maxLevel 3 (calcOpticalFlowPyrLK default)
-constexpr int LK_WIN = 21;
+constexpr int LK_WIN = 21;        // winSize 21 x 21 (calcOpticalFlowPyrLK default); the other offered windows: lk_window_offered
 
 struct LkPyramid {
     const uint8_t *img[LK_MAX_LEVELS];
@@ -17,12 +17,12 @@ struct LkPyramid {
     int levels;
 };
 
-// number of levels buildOpticalFlowPyramid produces for maxLevel 3, winSize 21
-inline int lk_levels(int w, int h) {
+// number of levels buildOpticalFlowPyramid produces for maxLevel 3, winSize win x win
+inline int lk_levels(int w, int h, int win = LK_WIN) {
     int n = 1;
     for (int l = 1; l < LK_MAX_LEVELS; l++) {
         w = (w + 1) / 2, h = (h + 1) / 2;
-        if (w <= LK_WIN || h <= LK_WIN) break;
+        if (w <= win || h <= win) break;
         n++;
     }
     return n;
@@ -121,14 +121,20 @@ struct LkSegArgs {
     int flags;
     const float2 *init_pts;
     float *err;
+    int win;  // the window (vstab.h, "Tracker window"): picks the kernel (launch_lk), which has the size compiled in; allowed on every launch
 };
 // The tracker's options as an entry point takes them, checked by check_lk_options (vstab_track_host.hpp); the defaults are
-// calcOpticalFlowPyrLK's.  max_level caps the pyramid (Tracker::init) and never reaches the kernel.
+// calcOpticalFlowPyrLK's.  max_level caps the pyramid (Tracker::init) and never reaches the kernel; win also sets the pyramid's depth.
 struct LkOptions {
     int max_level = LK_MAX_LEVELS - 1, max_iter = 30;
     double eps = 0.01, min_eig = 1e-4;
+    int win = LK_WIN;
 };
-inline void lk_set_options(LkSegArgs &a, const LkOptions &o) { a.max_iter = o.max_iter, a.min_eig = (float)o.min_eig, a.eps2 = o.eps * o.eps; }
+inline void lk_set_options(LkSegArgs &a, const LkOptions &o) { a.max_iter = o.max_iter, a.min_eig = (float)o.min_eig, a.eps2 = o.eps * o.eps, a.win = o.win; }
+// 15, 21 or 31: the windows a kernel exists for (vstab_lk_win.hip holds the table)
+bool lk_window_offered(int win);
+// launch_lk's second half for a window other than LK_WIN: "launch_lk: no kernel for this window" where there is none
+vstab_status launch_lk_win(const LkSegArgs &args, hipStream_t s);
 inline bool lk_default_launch(const LkSegArgs &a) {
     return a.max_iter == 30 && a.min_eig == 1e-4f && a.eps2 == 0.01 * 0.01 && a.flags == 0 && !a.init_pts && !a.err;
 }

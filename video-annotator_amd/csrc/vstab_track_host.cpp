@@ -28,14 +28,9 @@ vstab_status check_lk_options(const char *fn, int max_level, int max_iter, doubl
 
 vstab_status Tracker::init(int w, int h, const LkOptions &opt) {
     w_ = w, h_ = h;
+    opt_.win = opt.win;
     set_options(opt);
-    int lw = w, lh = h;
-    for (int l = 1; l < levels_; l++) {
-        lw = (lw + 1) / 2, lh = (lh + 1) / 2;
-        lvl_w_[l] = lw, lvl_h_[l] = lh;
-        for (int s = 0; s < PYR_SETS + PYR_DEV_EXTRA; s++) VSTAB_TRY(pyr_[s][l].ensure((size_t)lw * lh));
-    }
-    lvl_w_[0] = w, lvl_h_[0] = h;
+    VSTAB_TRY(ensure_levels(levels_));
     // record and point buffers for the pipeline's 200 features (FrameSourceWarp.cpp:230), so that nothing is
     // reallocated while a launch that uses them is queued
     for (int b = 0; b < REC_BUFS; b++) {
@@ -44,6 +39,26 @@ vstab_status Tracker::init(int w, int h, const LkOptions &opt) {
         VSTAB_HIP_TRY(hipMemset(drec_[b].p, 0, 256 * 16));  // tag 0 is never a sequence number: a chained slot never mistakes stale bytes for its predecessor
     }
     for (int b = 0; b < PTS_BUFS; b++) VSTAB_TRY(hpts_[b].ensure(256 * sizeof(float2)));
+    return VSTAB_OK;
+}
+
+// level sizes 0 .. n - 1 and the buffers of levels 1 .. n - 1 in every pyramid set (a buffer that is large enough stays)
+vstab_status Tracker::ensure_levels(int n) {
+    int lw = w_, lh = h_;
+    lvl_w_[0] = lw, lvl_h_[0] = lh;
+    for (int l = 1; l < n; l++) {
+        lw = (lw + 1) / 2, lh = (lh + 1) / 2;
+        lvl_w_[l] = lw, lvl_h_[l] = lh;
+        for (int s = 0; s < PYR_SETS + PYR_DEV_EXTRA; s++) VSTAB_TRY(pyr_[s][l].ensure((size_t)lw * lh));
+    }
+    return VSTAB_OK;
+}
+
+vstab_status Tracker::set_window(int win) {
+    // every level this window can ask for, whatever max_level says now: set_options may raise it afterwards
+    VSTAB_TRY(ensure_levels(lk_levels(w_, h_, win)));
+    opt_.win = win;
+    set_options(opt_);
     return VSTAB_OK;
 }
 

@@ -35,12 +35,17 @@ class Tracker {
     static constexpr int REC_BUFS = 32, PTS_BUFS = 8;
     ~Tracker();
     vstab_status init(int w, int h, const LkOptions &opt = LkOptions());
-    // the options of every launch from here on; the pyramids get min(lk_levels(w, h), max_level + 1) levels, so fewer levels are fewer
-    // pyramid launches.  Only while nothing is in flight (before the first launch).
+    // the options of every launch from here on; the pyramids get min(lk_levels(w, h, window), max_level + 1) levels, so fewer levels are
+    // fewer pyramid launches.  Only while nothing is in flight (before the first launch).  The window is set_window's: opt.win is not read.
     void set_options(const LkOptions &opt) {
-        opt_ = opt;
-        levels_ = std::min(lk_levels(w_, h_), opt.max_level + 1);
+        const int win = opt_.win;
+        opt_ = opt, opt_.win = win;
+        levels_ = std::min(lk_levels(w_, h_, win), opt.max_level + 1);
     }
+    // the window of every launch from here on (vstab.h, "Tracker window"; the caller checked lk_window_offered), independent of
+    // set_options and in either order with it.  A smaller window can mean a deeper pyramid than init() allocated: the level buffers of
+    // every set are brought up to lk_levels(w, h, win).  Only while nothing is in flight.  A failed allocation leaves the tracker as it was.
+    vstab_status set_window(int win);
     // levels 1.. of the pyramid of `gray` into slot s (level 0 is the frame itself)
     // `done` (optional) completes with the LAST kernel of the pyramid, bound to that launch (launch_pyr_down); *done_bound says whether a kernel
     // took it (an image too small for a second level has no pyramid kernel: the caller records the event itself)
@@ -133,6 +138,7 @@ class Tracker {
     void report_clock();
 
   private:
+    vstab_status ensure_levels(int n);
     vstab_status launch_segment(const LkPyramid *pyr, int n_frames, const float2 *prev_pts, const void *chain_in, uint32_t parent_seq, hipStream_t st, Launch &L);
     int w_ = 0, h_ = 0, levels_ = 1;
     LkOptions opt_;
