@@ -496,8 +496,8 @@ VSTAB_API vstab_status vstab_good_features_mask(const void *gray, size_t pitch, 
  *      read as int32; that order is wrong among negative values but right about the sign: if any value is >= +0 the maximum's bits are
  *      >= 0.  The sign of the published maximum decides this rule, on every path.
  *   5. k is finite with 0 <= k < 0.25: from 0.25 on, det - k tr^2 is never positive.  Anything else is refused.
- * The minimum-eigenvalue detector keeps its definition and its caveat ("Detection mask" above) word for word.  blockSize and gradientSize
- * other than 3 are not offered.
+ * The minimum-eigenvalue detector keeps its definition and its caveat ("Detection mask" above) word for word.  gradientSize other than 3
+ * is not offered; blockSize 5 and 7 are "Corner block size" below.
  *
  * vstab_corner_harris is vstab_min_eig's twin: response_f32 is a dense width x height device map of R.  Refused with VSTAB_ERR_INVALID
  * before any launch: "vstab_corner_harris: bad argument" (what vstab_min_eig refuses), then "vstab_corner_harris: k lies in [0, 0.25)".
@@ -508,6 +508,41 @@ VSTAB_API vstab_status vstab_corner_harris(const void *gray, size_t pitch, int w
 VSTAB_API vstab_status vstab_good_features_harris(const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask,
                                                   int max_corners, double quality, double min_distance, double k, int detector,
                                                   float *xy, int *count, int *detector_used, void *stream);
+
+/* ---- Corner block size ------------------------------------------------------------------------------------------------------------
+ * goodFeaturesToTrack's `blockSize`: the window of the covariance sums.  B = block_size is 3, 5 or 7, r = (B - 1) / 2; everything else is
+ * refused, not clamped (even sizes, 1, 9 and larger).  gradientSize stays 3.  Like the rest of the detector this restates OpenCV 4.5's CPU
+ * path -- cornerMinEigenVal(gray, B, 3), cornerHarris(gray, B, 3, k), goodFeaturesToTrack(..., mask, B, useHarris, k) -- in this library's
+ * arithmetic; no bit equality with OpenCV is claimed.
+ *   1. Derivatives.  The 3 x 3 Sobel pair of vstab_min_eig in its documented operation order, REFLECT_101 of the source, with the scale
+ *      scale_B = (float)(1.0 / (4.0 * B * 255.0)), k1 = scale_B, k0 = 2.0f * scale_B.
+ *   2. Products.  dx dx, dx dy, dy dy, each one binary32 product.
+ *   3. Box sum.  The un-normalised B x B sum centred on the pixel, over the product planes extended by REFLECT_101: the product AT the
+ *      mirrored position.  The extension folds as often as it takes (an image narrower than r + 1 folds more than once; a 1-pixel axis
+ *      repeats its pixel).  The order is part of the definition, all in double: column sums first, top to bottom,
+ *      c(y, x') = (((p(y-r, x') + p(y-r+1, x')) + ...) + p(y+r, x')); then left to right, S(y, x) = (((c(y, x-r) + c(y, x-r+1)) + ...) +
+ *      c(y, x+r)); then ONE rounding to float.  The order matters: within one frame the float products can span 77 bits (dy may be a
+ *      rounding residue far below k1), and sums of 25 or 49 of them are not always exact in double; the 9 of block 3 are.
+ *   4. Response.  On a = S_xx, b = S_xy, c = S_yy: the minimum-eigenvalue formula of vstab_min_eig with its two halvings, or the formula of
+ *      "Harris response" rule 2; both unchanged, nothing contracted.
+ *   5. Detector.  Everything behind the response is untouched by B: the maximum (over the masked-in pixels under a mask), the threshold
+ *      (float)((double)maxVal * quality) with strict >, the 3 x 3 maximum test over all pixels (OpenCV's dilate does not grow with
+ *      blockSize), interior pixels only (1 .. width - 2, 1 .. height - 2, whatever B is), the mask gate, rule 4 of the Harris response,
+ *      the order of the keys, the min_distance grid and max_corners.
+ * With block_size 3 each of the three calls below IS its block-3 twin (vstab_min_eig, vstab_corner_harris, and vstab_good_features_mask or
+ * vstab_good_features_harris): the same kernels, the same bytes.
+ *
+ * vstab_good_features_block is goodFeaturesToTrack's whole argument list in one call: mask == NULL means no mask; use_harris is 0 or 1, and
+ * k is looked at only with use_harris = 1.  Refused with VSTAB_ERR_INVALID before any launch, in this order (fn = the call's name):
+ * "<fn>: bad argument" (what the block-3 twin refuses; use_harris outside {0, 1} belongs here); "<fn>: block_size is 3, 5 or 7"; then
+ * the twin's remaining messages under this name in their order -- "quality must be > 0 and min_distance >= 0", the mask's pitch, the
+ * mask's size, "k lies in [0, 0.25)". */
+VSTAB_API vstab_status vstab_min_eig_block(const void *gray, size_t pitch, int width, int height, int block_size, void *eig_f32, void *stream);
+VSTAB_API vstab_status vstab_corner_harris_block(const void *gray, size_t pitch, int width, int height, int block_size, double k, void *response_f32,
+                                                 void *stream);
+VSTAB_API vstab_status vstab_good_features_block(const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask,
+                                                 int max_corners, double quality, double min_distance, int block_size, int use_harris, double k,
+                                                 int detector, float *xy, int *count, int *detector_used, void *stream);
 
 /* Replaces calcOpticalFlowPyrLK with default parameters (win 21x21, maxLevel 3, 30 iterations,
  * eps 0.01, minEigThreshold 1e-4), FrameSourceWarp.cpp:252.  prev/next: device gray images of the
@@ -521,7 +556,7 @@ VSTAB_API vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const v
 /* ---- Tracker options -----------------------------------------------------------------------------------------------------------------
  * calcOpticalFlowPyrLK's maxLevel, criteria (count and epsilon), minEigThreshold, flags and err: a restatement of OpenCV 4.5's CPU
  * LKTrackerInvoker in this library's arithmetic (exact integer sums converted once, the float operations in the documented order).  It
- * claims no bit equality with OpenCV.  winSize is 21 x 21 here; the other offered windows are "Tracker window" below (blockSize other than
+ * claims no bit equality with OpenCV.  winSize is 21 x 21 here; the other offered windows are "Tracker window" below (gradientSize other than
  * 3 is still not offered for the detector).
  *   1. Levels.  The pyramid has min(levels of vstab_pyr_lk, max_level + 1) levels.  Everything else about a level is as in vstab_pyr_lk.
  *   2. Start of the top level.  With VSTAB_LK_USE_INITIAL_FLOW next_xy is also an input: the top level L starts the next-image estimate at
@@ -1116,6 +1151,13 @@ VSTAB_API vstab_status vstab_set_detection_mask(vstab_handle *h, const void *mas
  * "vstab_set_corner_response: the response must be set before the first pull"; "vstab_set_corner_response: response must be
  * VSTAB_CORNER_MIN_EIGENVAL (0) or VSTAB_CORNER_HARRIS (1)"; "vstab_set_corner_response: k lies in [0, 0.25)". */
 VSTAB_API vstab_status vstab_set_corner_response(vstab_handle *h, int response, double k);
+/* The corner block size of a handle ("Corner block size" above): every corner detection of the handle uses block_size (3, 5 or 7) as
+ * goodFeaturesToTrack's blockSize, with any response and with a detection mask or without, on pixel_depth 10 handles too.  Independent of
+ * vstab_set_corner_response and vstab_set_detection_mask: the three may be called in any order.  Without this call, or with 3, the handle
+ * runs what it always ran.  Allowed before the first pull only.  Refused with VSTAB_ERR_INVALID, the handle unchanged, in this order:
+ * "vstab_set_corner_block: null handle"; "vstab_set_corner_block: no detector runs on this handle (tracking = 0)";
+ * "vstab_set_corner_block: the block size must be set before the first pull"; "vstab_set_corner_block: block_size is 3, 5 or 7". */
+VSTAB_API vstab_status vstab_set_corner_block(vstab_handle *h, int block_size);
 
 /* The handle's tracker options ("Tracker options" above, rules 1, 3 and 4): every tracker launch of the handle runs with them, and the
  * handle's pyramids have min(levels, max_level + 1) levels.  It takes no flags: err and the initial flow are stateless only

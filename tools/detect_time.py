@@ -1,5 +1,5 @@
 """Run the corner detectors at 4K and 1080p a few times (for rocprofv3 --kernel-trace --stats).
-usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overlay,roi}] [--harris [--k K]] [--alternations K]
+usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overlay,roi}] [--harris [--k K]] [--alternations K] [--block B]
    LIB: another build of the library (tools/devlib.py), for parent / branch runs
    --mask: K alternations of N unmasked detections (k_corners_fused) and N detections under the mask (k_corners_fused_masked,
            vstab_good_features_mask) per size, in one process: `full` is non-zero everywhere, `overlay` is zero on a box over 9 % of the frame
@@ -7,6 +7,10 @@ usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overla
    --harris: K alternations (rounds) of N detections with the minimum eigenvalue and N with the Harris response (vstab_good_features_harris,
            k_corners_fused_harris) per size, in one process; with --mask both run under the mask (k_corners_fused_masked and
            k_corners_fused_harris_masked).  tools/kernel_medians.py <dir> k_corners rounds gives the figures per round.
+   --block B: N one-pass detections and N dense maps with goodFeaturesToTrack's blockSize B per size (5, 7: vstab_good_features_block and
+           vstab_min_eig_block, k_corners_fused_block and k_corner_response_block of that size; 3: the entry points and kernels without a
+           block, so that the figures of one session stand beside each other); with --harris the Harris response, with --mask under the mask.
+           One block size per run: the kernels of 5 and of 7 carry the same name in a trace.
    tools/kernel_medians.py <dir> turns the kernel trace into medians per kernel and grid."""
 import argparse, hashlib, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -24,6 +28,7 @@ ap.add_argument("--mask", choices=("full", "overlay", "roi"), default=None)
 ap.add_argument("--harris", action="store_true")
 ap.add_argument("--k", type=float, default=0.04)
 ap.add_argument("--alternations", type=int, default=3)
+ap.add_argument("--block", type=int, default=None)
 a = ap.parse_args()
 if a.lib:
     import devlib
@@ -46,6 +51,23 @@ def make_mask(kind, w, h):
 
 for w, h in ((3840, 2160), (1920, 1080)):
     g = torch.from_numpy(np.ascontiguousarray(synth.luma(41, w, h, rects=400))).cuda()
+    if a.block is not None:
+        m = torch.from_numpy(make_mask(a.mask, w, h)).cuda() if a.mask else None
+        info = {}
+        for _ in range(a.n):
+            if a.block != 3:
+                c = vs.good_features_block(g, m, block_size=a.block, use_harris=a.harris, k=a.k, detector=vs.DETECTOR_FUSED, info=info)
+                e = vs.corner_harris_block(g, a.block, a.k) if a.harris else vs.min_eig_block(g, a.block)
+            elif a.harris:
+                c = vs.good_features_harris(g, m, k=a.k, detector=vs.DETECTOR_FUSED, info=info)
+                e = vs.corner_harris(g, a.k)
+            else:
+                c = vs.good_features_mask(g, m, detector=vs.DETECTOR_FUSED, info=info)
+                e = vs.min_eig(g)
+        torch.cuda.synchronize()
+        print(w, h, "block", a.block, "mask", a.mask, "harris k %g" % a.k if a.harris else "minimum eigenvalue", "detector", info["detector_used"], "corners", len(c),
+              hashlib.sha1(np.ascontiguousarray(c).tobytes()).hexdigest()[:12], "map", hashlib.sha1(e.cpu().numpy().tobytes()).hexdigest()[:12], flush=True)
+        continue
     if a.harris:
         m = torch.from_numpy(make_mask(a.mask, w, h)).cuda() if a.mask else None
         for _ in range(a.alternations):

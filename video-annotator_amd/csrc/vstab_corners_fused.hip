@@ -513,7 +513,8 @@ __global__ void __launch_bounds__(256) k_filter_keys(const unsigned long long *_
 
 // Fused detector.  spec.mask (optional: (uint64_t)mask_pitch * h < 2^32): k_corners_fused_masked takes the place of k_corners_fused,
 // everything else is the same; spec.harris: the Harris response in place of the minimum eigenvalue, k_corners_fused_harris /
-// k_corners_fused_harris_masked -- words->max then says whether the frame has a positive response at all (no_positive_response).
+// k_corners_fused_harris_masked -- words->max then says whether the frame has a positive response at all (no_positive_response);
+// spec.block other than 3: k_corners_fused_block of that size in their place.
 // scratch: corners_fused_scratch_bytes(w, h) (per tile: 256 key slots, a count, and room for a dense 64 x 31 map that only a tile with
 // more survivors than slots writes).  On return (stream order) keys holds min(words->kept, cap) keys; the result is complete iff
 // words->kept <= cap.
@@ -530,7 +531,9 @@ vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h
     float *spill = reinterpret_cast<float *>(base + lay.spill_off);
     unsigned int *tile_counts = reinterpret_cast<unsigned int *>(base + lay.counts_off);
     const dim3 grid(lay.tiles_x, lay.tiles_y);
-    if (spec.harris && spec.mask)
+    if (spec.block != 3)  // one kernel per block size, mask and response as its arguments (vstab_corners_block.hip)
+        VSTAB_TRY(launch_corners_fused_block(src, pitch, w, h, quality, &words->max, slots, tile_counts, spill, grid, s, spec));
+    else if (spec.harris && spec.mask)
         hipLaunchKernelGGL(k_corners_fused_harris_masked, grid, dim3(256), 0, s, src, pitch, w, h, quality, &words->max, slots, tile_counts, spill, vec_ok, spec.mask,
                            spec.mask_pitch, mvec_ok, spec.kf);
     else if (spec.harris)

@@ -39,6 +39,7 @@ LaunchEvents take_launch_events();
 vstab_status preload_pyramid_kernels();
 vstab_status preload_corner_kernels();
 vstab_status preload_corners_fused_kernels();
+vstab_status preload_corner_block_kernels();
 vstab_status preload_lk_kernels();
 vstab_status preload_lk_win_kernels();
 vstab_status preload_plane_kernels();

@@ -44,20 +44,26 @@ vstab_status launch_pyr_down_x2(const uint8_t *src, size_t spitch, int sw, int s
                                 hipEvent_t done = nullptr);
 // k of the Harris response (vstab.h, "Harris response"): finite, 0 <= k < 0.25 -- from 0.25 on det - k tr^2 is never positive
 inline bool harris_k_ok(double k) { return k >= 0.0 && k < 0.25; }
-// cornerMinEigenVal(3, 3) or, harris, cornerHarris(3, 3, k) with kf = (float)k as a dense w x h map, and its int-bit maximum
-vstab_status launch_corner_response(const uint8_t *src, size_t pitch, int w, int h, bool harris, float kf, float *resp, int *max_bits, hipStream_t s);
+// 3, 5 or 7: the block sizes a kernel exists for (vstab.h, "Corner block size"; vstab_corners_block.hip holds the table)
+bool corner_block_offered(int block);
+// cornerMinEigenVal(block, 3) or, harris, cornerHarris(block, 3, k) with kf = (float)k as a dense w x h map, and its int-bit maximum; with
+// block 3 exactly the launches there were before there was a block
+vstab_status launch_corner_response(const uint8_t *src, size_t pitch, int w, int h, bool harris, float kf, float *resp, int *max_bits, hipStream_t s, int block = 3);
+vstab_status launch_corner_response_block(const uint8_t *src, size_t pitch, int w, int h, int block, bool harris, float kf, float *resp, int *max_bits, hipStream_t s);
 // What a detection reads beside the image (vstab.h, "Detection mask" and "Harris response"), as every launcher and the Detector take it:
 //   mask    the detection mask, a w x h plane of bytes of pitch mask_pitch, non-zero = "a corner may be reported here"; NULL: none, the
 //           launches of the unmasked detector
-//   harris  cornerHarris(3, 3, k) with kf = (float)k in place of cornerMinEigenVal(3, 3) (kf is not looked at then)
+//   harris  cornerHarris(block, 3, k) with kf = (float)k in place of cornerMinEigenVal(block, 3) (kf is not looked at then)
+//   block   goodFeaturesToTrack's blockSize, 3, 5 or 7: the window of the covariance sums; 3 makes the launches of a spec without one
 // check_detect_spec (vstab_detect_host.hpp) is where the entry points refuse a bad one.
 struct DetectSpec {
     const uint8_t *mask = nullptr;
     size_t mask_pitch = 0;
     bool harris = false;
     float kf = 0.0f;
+    int block = 3;
     DetectSpec() = default;
-    DetectSpec(const uint8_t *m, size_t pitch, bool h = false, float k = 0.0f) : mask(m), mask_pitch(m ? pitch : 0), harris(h), kf(h ? k : 0.0f) {}
+    DetectSpec(const uint8_t *m, size_t pitch, bool h = false, float k = 0.0f, int b = 3) : mask(m), mask_pitch(m ? pitch : 0), harris(h), kf(h ? k : 0.0f), block(b) {}
 };
 // The detectors' 8 dwords of device memory (the fused launch zeroes all of them):
 struct DetectorWords {
@@ -90,6 +96,9 @@ struct CornersFusedScratch {
 size_t corners_fused_scratch_bytes(int w, int h);
 vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h, double quality, void *scratch, unsigned long long *keys,
                                   unsigned int cap, DetectorWords *words, hipStream_t s, const DetectSpec &spec = DetectSpec());
+// launch_corners_fused's first kernel for spec.block other than 3 (vstab_corners_block.hip), into the same scratch
+vstab_status launch_corners_fused_block(const uint8_t *src, size_t pitch, int w, int h, double quality, unsigned int *max_key, unsigned long long *slots,
+                                        unsigned int *tile_counts, float *spill, dim3 grid, hipStream_t s, const DetectSpec &spec);
 // One tracker launch = a SEGMENT of up to LK_SEG_MAX consecutive frame pairs (k_lk_track): pair i is (pyr[i], pyr[i + 1]).
 //   prev_pts  the n start points of pair 0 (device-readable), or NULL when
 //   chain_in  the device records of the parent launch's last pair, whose sequence number is parent_seq: slot f starts from the
