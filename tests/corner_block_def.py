@@ -172,7 +172,7 @@ def dark_noise(seed=3):
 
 
 # The one-pass kernel of block B takes its path without reflection arithmetic for a tile whose source box -- columns ox - SX0 .. ox - SX0 +
-# SW - 1, rows oy - SY0 .. oy - SY0 + SH - 1 -- lies inside the image (cb_interior, csrc/vstab_corners_block.hpp).  For tile (1, 1), ox = 64
+# SW - 1, rows oy - SY0 .. oy - SY0 + SH - 1 -- lies inside the image (tile_interior over SourceTile<B>, csrc/vstab_corners_tile.hpp).  For tile (1, 1), ox = 64
 # and oy = 31, the box ends on the image's last column at w = 64 - SX0 + SW and on its last row at h = 31 - SY0 + SH.
 INTERIOR_BOX = {5: dict(SX0=4, SY0=4, SW=72, SH=39), 7: dict(SX0=8, SY0=5, SW=80, SH=41)}
 

@@ -42,7 +42,7 @@ def tiles(w, h):
 
 
 def interior(tx, ty, w, h, aligned=True):
-    """the kernel's test (cf_interior) RESTATED: the source bytes of tile (tx, ty) lie inside the image, and the rows are dword aligned.
+    """the kernel's test (tile_interior over SourceTile3) RESTATED: the source bytes of tile (tx, ty) lie inside the image, and the rows are dword aligned.
     Nothing here reads the kernel's choice, and both paths give the same bits, so a kernel that takes the border path more often than this
     says passes every test; a tile that wrongly takes the interior path reads outside the image or skips a sign flip, and that the GPU
     comparisons of test_corner_seams_gpu.py catch (eigenvalues and keys of the tiles next to every border)."""

@@ -36,7 +36,7 @@ def check_dense(vs, gd, g, block, what):
 
 # ---- the dense maps ---------------------------------------------------------------------------------------------------------------------
 # 3 x 3 and 4 x 5 fold more than once; 65 x 32 and 66 x 33 are the tile seams; 322 x 182 has interior tiles; dark_noise has double sums that
-# are not exact.  interior_edge: tile (1, 1)'s source box ends exactly on the image's last byte (the kernel's interior path, cb_interior);
+# are not exact.  interior_edge: tile (1, 1)'s source box ends exactly on the image's last byte (the kernel's interior path, tile_interior);
 # interior_edge_less_h: one row less, that tile takes the border path on dword-aligned rows; interior_edge_less_w: one column less (rows
 # that are no longer dword aligned: every tile takes the border path and its byte loads).
 @pytest.mark.parametrize("block", NEW)

@@ -8,9 +8,9 @@ usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overla
            k_corners_fused_harris) per size, in one process; with --mask both run under the mask (k_corners_fused_masked and
            k_corners_fused_harris_masked).  tools/kernel_medians.py <dir> k_corners rounds gives the figures per round.
    --block B: N one-pass detections and N dense maps with goodFeaturesToTrack's blockSize B per size (5, 7: vstab_good_features_block and
-           vstab_min_eig_block, k_corners_fused_block and k_corner_response_block of that size; 3: the entry points and kernels without a
+           vstab_min_eig_block, k_corners_fused_block<B> and k_corner_response_block<B>; 3: the entry points and kernels without a
            block, so that the figures of one session stand beside each other); with --harris the Harris response, with --mask under the mask.
-           One block size per run: the kernels of 5 and of 7 carry the same name in a trace.
+           One block size per run; a trace names the kernels with their size (k_corners_fused_block<5>), and so does tools/kernel_medians.py.
    tools/kernel_medians.py <dir> turns the kernel trace into medians per kernel and grid."""
 import argparse, hashlib, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))

@@ -4,9 +4,8 @@
 // Compiled with -ffp-contract=off: float results are bit-reproducible.
 #include <climits>
 
+#include "vstab_corners_tile.hpp"
 #include "vstab_internal.hpp"
-#include "vstab_track.hpp"
-#include "vstab_track_device.hpp"
 
 namespace vstab {
 
@@ -93,11 +92,8 @@ __device__ __forceinline__ void me_response(const uint8_t *__restrict__ src, siz
             for (int c = 0; c < 4 && x + c < w; c++) o[c] = ev[c];
         }
     }
-    // frame maximum: DPP max inside each 16-lane row, one LDS atomic per row, one global atomic per block
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x111, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x112, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x114, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x118, 0xf, 0xf, false));
+    // frame maximum: the maximum inside each 16-lane row, one LDS atomic per row, one global atomic per block
+    best = row_max_i32(best);
     if (q == 15) atomicMax(&bmax, best);
     __syncthreads();
     if (tid == 0) atomicMax(max_bits, bmax);
@@ -178,12 +174,7 @@ __global__ void __launch_bounds__(256) k_masked_max(const float *__restrict__ ei
             if (y < h && mask[(size_t)y * mpitch + x] != 0) best = max(best, __float_as_int(eig[(size_t)y * w + x]));
         }
     }
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x111, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x112, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x114, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x118, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x142, 0xa, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x143, 0xc, 0xf, false));
+    best = wave_max_i32(best);
     if (lane == 63) atomicMax(&bmax, best);
     __syncthreads();
     if (tid == 0) atomicMax(max_bits, bmax);

@@ -3,11 +3,8 @@
 // k_corners_fused_harris_masked), then k_filter_keys with the final threshold.  The two-pass detector behind it is vstab_corners.hip.
 // Replaces the OpenCV call at FrameSourceWarp.cpp:230 (goodFeaturesToTrack).  Compiled with -ffp-contract=off: float results are
 // bit-reproducible.
-#include <climits>
-
+#include "vstab_corners_tile.hpp"
 #include "vstab_internal.hpp"
-#include "vstab_track.hpp"
-#include "vstab_track_device.hpp"
 
 namespace vstab {
 
@@ -42,7 +39,8 @@ namespace vstab {
 // maxima; fine noise reaches ~220 -- are part of the scratch layout: vstab_track.hpp)
 constexpr int CF_EH = CF_TH + 2;                      // eigenvalue region: 66 x 33, image (oy - 1 .., ox - 1 ..)
 constexpr int CF_DH = 35, CF_DP = 68;                 // derivative-product region: 68 x 35, image (oy - 2 .., ox - 2 ..)
-constexpr int CF_SW = 72, CF_SH = 38;                  // source tile: image (oy - 3 .., ox - 4 ..); 37 rows used
+using CfSource = SourceTile3;                           // source tile: 72 x 38 from image (oy - 3 .., ox - 4 ..); 37 rows used
+constexpr int CF_SW = CfSource::SW, CF_SH = CfSource::SH;
 constexpr int CF_EP = 67;
 constexpr int CF_PC = CF_DP / 4, CF_PR = 5, CF_PG = CF_DH / CF_PR;  // prod: 17 column groups of 4, 7 row groups of 5
 constexpr int CF_BX = 22, CF_BY = 11;                  // box / eig: 22 x 11 blocks of 3 x 3
@@ -50,8 +48,12 @@ static_assert(CF_PC * 4 == CF_DP && CF_PG * CF_PR == CF_DH && CF_DH + 2 <= CF_SH
 static_assert(CF_BX * 3 == CF_TW + 2 && CF_BY * 3 == CF_EH && CF_EH + 2 == CF_DH && CF_BX * CF_BY <= 256, "box ownership covers the region");
 static_assert(CF_EH * CF_EP <= CF_DH * CF_DP, "the eigenvalues fit the plane they take over");
 
-// row and column of a dword, a product group and a box block as one 24-bit multiply and a shift (div_magic_ok)
-static_assert(div_magic_ok(CF_SW / 4, 3641, CF_SH * (CF_SW / 4) + 256) && div_magic_ok(CF_PC, 3856, 256) && div_magic_ok(CF_BX, 2979, 256), "division constants");
+// row and column of a product group and a box block as one 24-bit multiply and a shift (div_magic_ok)
+static_assert(div_magic_ok(CF_PC, 3856, 256) && div_magic_ok(CF_BX, 2979, 256), "division constants");
+// the kernel a helper is instantiated for (vstab_corners_tile.hpp has the reason).  In the helpers of this unit MASKED and HARRIS are such
+// tags too wherever the text does not use them: HARRIS changes the code in cf_eigenvalues alone.
+template <bool MASKED, bool HARRIS>
+struct CfTag {};
 
 // byte B of v as a float.  Written as the instruction: from (float)((v >> 8 B) & 255) the compiler builds the differences and sums of two
 // bytes in integers (an SDWA operation and a conversion apiece) where the six floats of a row, converted once, serve all of them.
@@ -66,125 +68,6 @@ __device__ __forceinline__ float ubyte_f32(uint32_t v) {
     if (B == 2) asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(f) : "v"(v));
     if (B == 3) asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(f) : "v"(v));
     return f;
-}
-
-// threshold + 3x3 maximum test over the eigenvalues in LDS: lane = column, a wave walks its 8 rows (the last wave 7) with a rolling
-// row maximum.  DENSE = false: survivors are appended to the tile's slots, one LDS atomic per wave for the rows' survivors together
-// (*bcount counts all of them, also those past the last slot); DENSE = true: every pixel of the tile is written, the
-// eigenvalue for a survivor and -inf otherwise.  INTERIOR: every pixel of the tile is an interior pixel of the image.
-// MASKED (k_corners_fused_masked): a survivor also has a non-zero mask byte; `mtile` holds the tile's mask bytes in the layout of the
-// source tile (pixel (ty, tx) of the tile <-> mtile[ty + 3][tx + 4]).  Its neighbours compete in the maximum whatever their mask bytes say.
-template <bool DENSE, bool INTERIOR, bool MASKED = false, bool HARRIS = false>
-__device__ __forceinline__ void cf_nonmax(const float (&es)[CF_EH][CF_EP], int tid, int ox, int oy, int w, int h, float thr_lb,
-                                          unsigned long long *__restrict__ my_slots, unsigned int *bcount, float *__restrict__ dense,
-                                          const uint8_t (*mtile)[CF_SW] = nullptr) {
-    const int tx = tid & 63, r0 = __builtin_amdgcn_readfirstlane(tid >> 6) * 8;  // the rows are the wave's: scalar
-    const int x = ox + tx;
-    const bool x_in = INTERIOR || (x >= 1 && x < w - 1);
-    float rm0 = fmaxf(fmaxf(es[r0][tx], es[r0][tx + 1]), es[r0][tx + 2]);
-    float c1 = es[r0 + 1][tx + 1];
-    float rm1 = fmaxf(fmaxf(es[r0 + 1][tx], c1), es[r0 + 1][tx + 2]);
-    float v[8];
-    bool cand[8];
-    unsigned long long ballot[8];
-    unsigned int total = 0;
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const int ty = r0 + r;
-        const bool row = r < 7 || ty < CF_TH;            // scalar; false only for the last wave's eighth row
-        const int below = r < 7 ? ty + 2 : min(ty + 2, CF_EH - 1);
-        const float c2 = es[below][tx + 1];
-        const float rm2 = fmaxf(fmaxf(es[below][tx], c2), es[below][tx + 2]);
-        const float m = fmaxf(fmaxf(rm0, rm1), rm2);
-        const int y = oy + ty;
-        cand[r] = row && x_in && (INTERIOR || (y >= 1 && y < h - 1)) && c1 > thr_lb && c1 == m;
-        if (MASKED) cand[r] = cand[r] && mtile[ty + 3][tx + 4] != 0;  // (ty + 3 <= 34 < CF_SH also for the last wave's eighth row)
-        if (DENSE) {
-            if (row) dense[ty * CF_TW + tx] = cand[r] ? c1 : -__builtin_inff();
-        } else {
-            v[r] = c1;
-            ballot[r] = __builtin_amdgcn_ballot_w64(cand[r]);
-            total += (unsigned int)__popcll(ballot[r]);
-        }
-        rm0 = rm1, rm1 = rm2, c1 = c2;
-    }
-    if (!DENSE && total) {
-        unsigned int base = 0;
-        if (tx == 0) base = atomicAdd(bcount, total);  // LDS
-        base = __builtin_amdgcn_readfirstlane(base);
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            if (!ballot[r]) continue;
-            const unsigned int slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot[r] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot[r], 0));
-            if (cand[r] && slot < CF_SLOTS) my_slots[slot] = ((unsigned long long)__float_as_uint(v[r]) << 32) | (unsigned int)((oy + r0 + r) * w + x);
-            base += (unsigned int)__popcll(ballot[r]);
-        }
-    }
-}
-
-// load: the source tile, dword e of it <-> row e / 18, bytes 4 (e % 18) ..; a thread's three loads are in flight together
-// (MASKED, here and in cf_store, cf_products and cf_interior, changes nothing in the function: it gives k_corners_fused_masked instantiations of
-//  its own.  An instantiation that both kernels inlined would be cloned where k_corners_fused alone has it moved into its only caller, and
-//  the optimiser's choices behind that differ: the unmasked kernel's instructions stay exactly what they were this way.
-//  HARRIS is the same kind of tag for k_corners_fused_harris and k_corners_fused_harris_masked; it changes the code in cf_eigenvalues alone.)
-constexpr int CF_LOADS = (CF_SH * (CF_SW / 4) + 255) / 256;
-template <bool INTERIOR, bool MASKED = false, bool HARRIS = false>
-__device__ __forceinline__ void cf_load(uint32_t (&v)[CF_LOADS], const uint8_t *__restrict__ src, uint32_t pitch, int w, int h, int ox, int oy, bool vec_ok,
-                                        int tid) {
-#pragma unroll
-    for (int k = 0; k < CF_LOADS; k++) {
-        const int e = tid + 256 * k;
-        const int ry = __mul24(e, 3641) >> 16, rd = e - ry * (CF_SW / 4);
-        v[k] = 0;
-        if (e >= CF_SH * (CF_SW / 4)) continue;
-        if (INTERIOR) v[k] = *reinterpret_cast<const uint32_t *>(src + ((uint32_t)(oy - 3 + ry) * pitch + (uint32_t)(ox - 4 + 4 * rd)));
-        else v[k] = load4_reflect(src, pitch, w, h, ox - 4 + 4 * rd, oy - 3 + ry, vec_ok);
-    }
-}
-template <bool MASKED = false, bool HARRIS = false>
-__device__ __forceinline__ void cf_store(uint8_t (&tile)[CF_SH][CF_SW], const uint32_t (&v)[CF_LOADS], int tid) {
-#pragma unroll
-    for (int k = 0; k < CF_LOADS; k++)
-        if (tid + 256 * k < CF_SH * (CF_SW / 4)) reinterpret_cast<uint32_t *>(&tile[0][0])[tid + 256 * k] = v[k];
-}
-
-// The mask bytes of the tile in the layout and with the addressing of cf_load: dwords where the mask's rows are dword aligned, bytes
-// otherwise -- but nothing is mirrored: a byte outside the image is never read and counts as zero ("masked out").  INTERIOR says that
-// the 72 x 38 bytes lie inside the image (the mask has the image's size), vec_ok that the MASK's base and pitch are 4-byte aligned.
-template <bool INTERIOR, bool HARRIS = false>
-__device__ __forceinline__ void cf_load_mask(uint32_t (&v)[CF_LOADS], const uint8_t *__restrict__ mask, uint32_t pitch, int w, int h, int ox, int oy, bool vec_ok,
-                                             int tid) {
-#pragma unroll
-    for (int k = 0; k < CF_LOADS; k++) {
-        const int e = tid + 256 * k;
-        const int ry = __mul24(e, 3641) >> 16, rd = e - ry * (CF_SW / 4);
-        v[k] = 0;
-        if (e >= CF_SH * (CF_SW / 4)) continue;
-        const int gx = ox - 4 + 4 * rd, gy = oy - 3 + ry;
-        if (!INTERIOR && (gy < 0 || gy >= h)) continue;
-        const uint8_t *row = mask + (uint32_t)gy * pitch;
-        if (vec_ok && (INTERIOR || (gx >= 0 && gx + 4 <= w))) {
-            v[k] = *reinterpret_cast<const uint32_t *>(row + gx);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (INTERIOR || (gx + i >= 0 && gx + i < w)) v[k] |= (uint32_t)row[gx + i] << (8 * i);
-        }
-    }
-}
-// whether one of the thread's mask dwords holds a non-zero byte of the 66 x 33 pixels the tile takes its maximum over: rows 2 .. 34 of
-// the 38, bytes 3 .. 68 of the 72 (the last byte of the first dword, the first byte of the last, every byte of those between)
-template <bool HARRIS = false>
-__device__ __forceinline__ bool cf_mask_any(const uint32_t (&v)[CF_LOADS], int tid) {
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < CF_LOADS; k++) {
-        const int e = tid + 256 * k;
-        const int ry = __mul24(e, 3641) >> 16, rd = e - ry * (CF_SW / 4);
-        const uint32_t sel = rd == 0 ? 0xff000000u : rd == CF_SW / 4 - 1 ? 0x000000ffu : 0xffffffffu;
-        any = any || (ry >= 2 && ry <= CF_EH + 1 && (v[k] & sel) != 0);  // (a dword past the tile is zero: cf_load_mask)
-    }
-    return any;
 }
 
 // prod: product entry (r, q) <-> image (oy - 2 + r, ox - 2 + q) <-> tile[r + 1][q + 2]; a thread owns q = 4c .. 4c+3, r = 5g .. 5g+4
@@ -243,7 +126,7 @@ __device__ __forceinline__ void cf_sum3of5(double p0, double p1, double p2, doub
 // the image is zero there).  The mask bytes must be in `mtile` before the call: the barrier in here orders them before their readers.
 // HARRIS: the response is R = (a c - b b) - (kf t) t with t = a + c over the box sums as they are (vstab.h, "Harris response"; no
 // contraction in this unit); it is negative over much of an ordinary frame, and the int-bit maximum of a tile without a value >= +0 is
-// negative: cf_tile filters such a tile with -inf, and whether the FRAME's maximum is positive the host reads from its sign.
+// negative: tile_select filters such a tile with -inf, and whether the FRAME's maximum is positive the host reads from its sign.
 template <bool INTERIOR, bool MASKED = false, bool HARRIS = false>
 __device__ __forceinline__ int cf_eigenvalues(const float (&prod)[3][CF_DH][CF_DP], float (&es)[CF_EH][CF_EP], int ox, int oy, int w, int h, int tid,
                                               const uint8_t (*mtile)[CF_SW] = nullptr, float kf = 0.0f) {
@@ -296,96 +179,65 @@ __device__ __forceinline__ int cf_eigenvalues(const float (&prod)[3][CF_DH][CF_D
     return best;
 }
 
+// One tile, source to keys: the toolkit of vstab_corners_tile.hpp around cf_products and cf_eigenvalues.
 // MASKED (k_corners_fused_masked; `mask`: a w x h plane of bytes, non-zero = "a corner may be reported here"):
 //   - a tile without a non-zero mask byte among the in-image pixels of its 66 x 33 eigenvalues writes a count of 0 and returns before it
-//     loads the source: it publishes no maximum and no key.  The test is one value for the workgroup (a flag per wave in LDS behind one barrier), so every barrier
-//     below is reached by all of its threads or by none;
+//     loads the source (tile_masked_out; its flags lie in prod, which is first written behind the barrier that follows tile_store);
 //   - the tile maximum, and with it the published frame maximum, runs over the eigenvalues with a non-zero mask byte;
-//   - a survivor has a non-zero mask byte (cf_nonmax), while the 3 x 3 maximum it is compared with knows no mask.
+//   - a survivor has a non-zero mask byte (tile_nonmax), while the 3 x 3 maximum it is compared with knows no mask.
 // The mask bytes wait in three registers while the source tile is in use and take its place in LDS behind the products.
 template <bool INTERIOR, bool MASKED = false, bool HARRIS = false>
 __device__ __forceinline__ void cf_tile(uint8_t (&tile)[CF_SH][CF_SW], float (&prod)[3][CF_DH][CF_DP], int &bmax, unsigned int &bcount, unsigned int &bseen,
                                         const uint8_t *__restrict__ src, uint32_t pitch, int w, int h, double quality, unsigned int *__restrict__ max_key,
                                         unsigned long long *__restrict__ slots, unsigned int *__restrict__ tile_counts, float *__restrict__ spill, bool vec_ok,
                                         const uint8_t *__restrict__ mask = nullptr, uint32_t mpitch = 0, bool mvec_ok = false, float kf = 0.0f) {
+    using G = CfSource;
+    using TAG = CfTag<MASKED, HARRIS>;
     float (&es)[CF_EH][CF_EP] = *reinterpret_cast<float (*)[CF_EH][CF_EP]>(&prod[0][0][0]);
     const int tid = threadIdx.x;
     const int ox = blockIdx.x * CF_TW, oy = blockIdx.y * CF_TH;
-    uint32_t mv[CF_LOADS];
+    uint32_t mv[G::LOADS];
     if (MASKED) {
-        cf_load_mask<INTERIOR, HARRIS>(mv, mask, mpitch, w, h, ox, oy, mvec_ok, tid);
-        // one flag per wave in LDS nobody uses yet (prod is first written behind the barrier that follows cf_store), one barrier, the
-        // same answer in every thread
-        uint32_t *flags = reinterpret_cast<uint32_t *>(&prod[2][0][0]);
-        const bool mine = __builtin_amdgcn_ballot_w64(cf_mask_any<HARRIS>(mv, tid)) != 0;
-        if ((tid & 63) == 0) flags[tid >> 6] = mine;
-        __syncthreads();
-        if ((flags[0] | flags[1] | flags[2] | flags[3]) == 0) {
+        tile_load_mask<G, INTERIOR, TAG>(mv, mask, mpitch, w, h, ox, oy, mvec_ok, tid);
+        if (tile_masked_out<G, TAG>(mv, reinterpret_cast<uint32_t *>(&prod[2][0][0]), tid)) {
             if (tid == 0) tile_counts[blockIdx.y * gridDim.x + blockIdx.x] = 0;
             return;
         }
     }
-    uint32_t v[CF_LOADS];
-    cf_load<INTERIOR, MASKED, HARRIS>(v, src, pitch, w, h, ox, oy, vec_ok, tid);
+    uint32_t v[G::LOADS];
+    tile_load<G, INTERIOR, TAG>(v, src, pitch, w, h, ox, oy, vec_ok, tid);
     if (tid == 0) bmax = INT_MIN, bcount = 0;
-    cf_store<MASKED, HARRIS>(tile, v, tid);
-    // frame maximum published so far (biased bits): a lower bound of the final one.  Device-scope load: the atomics
-    // of other XCDs do not pass through this XCD's L2.  Every workgroup reads this one address, and the memory side serves
-    // such reads one after the other: ONE lane asks -- in the last wave, which has no part in the products, and behind
-    // the tile's loads, so that no wait for those waits for this -- and nothing needs the answer before the eigenvalues
-    // are done.
-    unsigned int seen = 0;
-    if (tid == 255) seen = __hip_atomic_load(max_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tile_store<G, TAG>(tile, v, tid);
+    const unsigned int seen = tile_seen<TAG>(max_key, tid);
     __syncthreads();
     cf_products<INTERIOR, MASKED, HARRIS>(tile, prod, ox, oy, w, h, tid);
     __syncthreads();
-    if (MASKED) cf_store<MASKED, HARRIS>(tile, mv, tid);  // the source bytes are dead; cf_eigenvalues' barrier stands between this and the first reader
-    int best = cf_eigenvalues<INTERIOR, MASKED, HARRIS>(prod, es, ox, oy, w, h, tid, tile, kf);
-    // tile maximum (same int-bit order as k_min_eig)
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x111, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x112, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x114, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x118, 0xf, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x142, 0xa, 0xf, false));
-    best = max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x143, 0xc, 0xf, false));
-    if ((tid & 63) == 63) atomicMax(&bmax, best);
-    if (tid == 255) bseen = seen;
-    __syncthreads();
-    const int tile_max = bmax;
-    seen = bseen;
-    // Every workgroup hitting one address costs ~11 ns apiece on this part (all XCDs meet at the memory side):
-    // only a tile that raises the maximum it saw publishes.
-    if (tid == 0 && ((unsigned int)tile_max ^ 0x80000000u) > seen) atomicMax(max_key, (unsigned int)tile_max ^ 0x80000000u);
-    // lower bound of the frame threshold; only meaningful for a non-negative maximum (float order == int order)
-    const int lb_bits = max(tile_max, (int)(seen ^ 0x80000000u));
-    const float thr_lb = lb_bits >= 0 ? (float)((double)__int_as_float(lb_bits) * quality) : -__builtin_inff();
-    const int tile_idx = blockIdx.y * gridDim.x + blockIdx.x;
-    cf_nonmax<false, INTERIOR, MASKED, HARRIS>(es, tid, ox, oy, w, h, thr_lb, slots + (size_t)tile_idx * CF_SLOTS, &bcount, nullptr, tile);
-    __syncthreads();
-    const unsigned int n = bcount;
-    if (tid == 0) tile_counts[tile_idx] = n;
-    // A tile with more survivors than slots (an eigenvalue plateau: a smooth ramp, a periodic texture) leaves them as a
-    // dense 64 x 31 map instead (-inf = not a survivor); k_filter_keys scans that with the final threshold.
-    if (n > CF_SLOTS) cf_nonmax<true, INTERIOR, MASKED, HARRIS>(es, tid, ox, oy, w, h, thr_lb, nullptr, nullptr, spill + (size_t)tile_idx * (CF_TW * CF_TH), tile);
+    if (MASKED) tile_store<G, TAG>(tile, mv, tid);  // the source bytes are dead; cf_eigenvalues' barrier stands between this and the first reader
+    const int best = cf_eigenvalues<INTERIOR, MASKED, HARRIS>(prod, es, ox, oy, w, h, tid, tile, kf);
+    tile_select<G, INTERIOR, TAG>(best, seen, es, tile, std::bool_constant<MASKED>(), bmax, bcount, bseen, w, h, quality, max_key, slots, tile_counts, spill);
 }
 
-// the tile's 72 x 38 source bytes at image (oy - 3 .., ox - 4 ..) lie inside the image, and its rows are dword aligned
-template <bool MASKED = false, bool HARRIS = false>
-__device__ __forceinline__ bool cf_interior(int ox, int oy, int w, int h, int vec_ok) {
-    return vec_ok && ox >= 4 && ox - 4 + CF_SW <= w && oy >= 3 && oy - 3 + CF_SH <= h;
+// what each of the four kernels is: the tile's LDS, and cf_tile on the interior path or on the other
+template <bool MASKED, bool HARRIS>
+__device__ __forceinline__ void cf_kernel(const uint8_t *__restrict__ src, size_t pitch, int w, int h, double quality, unsigned int *__restrict__ max_key,
+                                          unsigned long long *__restrict__ slots, unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok,
+                                          const uint8_t *__restrict__ mask = nullptr, size_t mpitch = 0, int mvec_ok = 0, float kf = 0.0f) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];   // the source bytes; MASKED: behind the products, the mask bytes
+    __shared__ __attribute__((aligned(16))) float prod[3][CF_DH][CF_DP];  // dx dx, dx dy, dy dy; then the eigenvalues in place of dx dx
+    __shared__ int bmax;
+    __shared__ unsigned int bcount, bseen;
+    if (tile_interior<CfSource, CfTag<MASKED, HARRIS>>(blockIdx.x * CF_TW, blockIdx.y * CF_TH, w, h, vec_ok))
+        cf_tile<true, MASKED, HARRIS>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true, mask, (uint32_t)mpitch,
+                                      mvec_ok != 0, kf);
+    else
+        cf_tile<false, MASKED, HARRIS>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0, mask,
+                                       (uint32_t)mpitch, mvec_ok != 0, kf);
 }
 
 __global__ void __launch_bounds__(256) k_corners_fused(const uint8_t *__restrict__ src, size_t pitch, int w, int h, double quality,
                                                        unsigned int *__restrict__ max_key, unsigned long long *__restrict__ slots,
                                                        unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok) {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];
-    __shared__ __attribute__((aligned(16))) float prod[3][CF_DH][CF_DP];  // dx dx, dx dy, dy dy; then the eigenvalues in place of dx dx
-    __shared__ int bmax;
-    __shared__ unsigned int bcount, bseen;
-    if (cf_interior(blockIdx.x * CF_TW, blockIdx.y * CF_TH, w, h, vec_ok))
-        cf_tile<true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true);
-    else
-        cf_tile<false>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0);
+    cf_kernel<false, false>(src, pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok);
 }
 
 // k_corners_fused_masked -- k_corners_fused under a detection mask (goodFeaturesToTrack's `mask`; vstab.h, "Detection mask"): the same
@@ -397,16 +249,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                                                               unsigned int *__restrict__ max_key, unsigned long long *__restrict__ slots,
                                                               unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok,
                                                               const uint8_t *__restrict__ mask, size_t mpitch, int mvec_ok) {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];  // the source bytes; behind the products, the mask bytes
-    __shared__ __attribute__((aligned(16))) float prod[3][CF_DH][CF_DP];
-    __shared__ int bmax;
-    __shared__ unsigned int bcount, bseen;
-    if (cf_interior<true>(blockIdx.x * CF_TW, blockIdx.y * CF_TH, w, h, vec_ok))
-        cf_tile<true, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true, mask, (uint32_t)mpitch,
-                            mvec_ok != 0);
-    else
-        cf_tile<false, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0, mask,
-                             (uint32_t)mpitch, mvec_ok != 0);
+    cf_kernel<true, false>(src, pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok, mask, mpitch, mvec_ok);
 }
 
 // k_corners_fused_harris, k_corners_fused_harris_masked -- the two kernels above with the Harris response (goodFeaturesToTrack's
@@ -419,30 +262,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
 __global__ void __launch_bounds__(256) k_corners_fused_harris(const uint8_t *__restrict__ src, size_t pitch, int w, int h, double quality,
                                                               unsigned int *__restrict__ max_key, unsigned long long *__restrict__ slots,
                                                               unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok, float kf) {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];
-    __shared__ __attribute__((aligned(16))) float prod[3][CF_DH][CF_DP];
-    __shared__ int bmax;
-    __shared__ unsigned int bcount, bseen;
-    if (cf_interior<false, true>(blockIdx.x * CF_TW, blockIdx.y * CF_TH, w, h, vec_ok))
-        cf_tile<true, false, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true, nullptr, 0, false, kf);
-    else
-        cf_tile<false, false, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0, nullptr, 0,
-                                    false, kf);
+    cf_kernel<false, true>(src, pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok, nullptr, 0, 0, kf);
 }
 
 __global__ void __launch_bounds__(256) k_corners_fused_harris_masked(
     const uint8_t *__restrict__ src, size_t pitch, int w, int h, double quality, unsigned int *__restrict__ max_key, unsigned long long *__restrict__ slots,
     unsigned int *__restrict__ tile_counts, float *__restrict__ spill, int vec_ok, const uint8_t *__restrict__ mask, size_t mpitch, int mvec_ok, float kf) {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[CF_SH][CF_SW];
-    __shared__ __attribute__((aligned(16))) float prod[3][CF_DH][CF_DP];
-    __shared__ int bmax;
-    __shared__ unsigned int bcount, bseen;
-    if (cf_interior<true, true>(blockIdx.x * CF_TW, blockIdx.y * CF_TH, w, h, vec_ok))
-        cf_tile<true, true, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, true, mask, (uint32_t)mpitch,
-                                  mvec_ok != 0, kf);
-    else
-        cf_tile<false, true, true>(tile, prod, bmax, bcount, bseen, src, (uint32_t)pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok != 0, mask,
-                                   (uint32_t)mpitch, mvec_ok != 0, kf);
+    cf_kernel<true, true>(src, pitch, w, h, quality, max_key, slots, tile_counts, spill, vec_ok, mask, mpitch, mvec_ok, kf);
 }
 
 // k_filter_keys -- the final threshold quality * max(frame) over the survivors of k_corners_fused.  A workgroup
@@ -532,7 +358,7 @@ vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h
     unsigned int *tile_counts = reinterpret_cast<unsigned int *>(base + lay.counts_off);
     const dim3 grid(lay.tiles_x, lay.tiles_y);
     if (spec.block != 3)  // one kernel per block size, mask and response as its arguments (vstab_corners_block.hip)
-        VSTAB_TRY(launch_corners_fused_block(src, pitch, w, h, quality, &words->max, slots, tile_counts, spill, grid, s, spec));
+        VSTAB_TRY(launch_corners_fused_block(src, pitch, w, h, quality, &words->max, slots, tile_counts, spill, grid, s, spec, vec_ok, mvec_ok));
     else if (spec.harris && spec.mask)
         hipLaunchKernelGGL(k_corners_fused_harris_masked, grid, dim3(256), 0, s, src, pitch, w, h, quality, &words->max, slots, tile_counts, spill, vec_ok, spec.mask,
                            spec.mask_pitch, mvec_ok, spec.kf);

@@ -246,7 +246,7 @@ __attribute__((visibility("default"))) int vstabx_corners_fused_harris(const voi
                               tile_counts, stream, true, k, max_bits_out);
 }
 // vstabx_corners_fused_harris with the block size and the response as arguments (tests/test_corner_block_gpu.py, tests/corner_block_def.py):
-// k_corners_fused_block of that size or, with block 3, the kernel vstabx_corners_fused* runs for this mask and response; then k_filter_keys.
+// k_corners_fused_block<block> or, with block 3, the kernel vstabx_corners_fused* runs for this mask and response; then k_filter_keys.
 // response: VSTAB_CORNER_MIN_EIGENVAL (k is not looked at) or VSTAB_CORNER_HARRIS.  The same outputs; the refusals under this hook's name:
 // first "response is 0 or 1", then vstabx_corners_fused_harris', with "block_size is 3, 5 or 7" ahead of the mask's and k's.
 __attribute__((visibility("default"))) int vstabx_corners_fused_block(const void *gray, size_t pitch, int w, int h, const void *mask, size_t pitch_mask, double quality,

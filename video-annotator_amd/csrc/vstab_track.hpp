@@ -96,9 +96,10 @@ struct CornersFusedScratch {
 size_t corners_fused_scratch_bytes(int w, int h);
 vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h, double quality, void *scratch, unsigned long long *keys,
                                   unsigned int cap, DetectorWords *words, hipStream_t s, const DetectSpec &spec = DetectSpec());
-// launch_corners_fused's first kernel for spec.block other than 3 (vstab_corners_block.hip), into the same scratch
+// launch_corners_fused's first kernel for spec.block other than 3 (vstab_corners_block.hip), into the same scratch; vec_ok, mvec_ok: the
+// image's and the mask's base and pitch are 4-byte aligned, as launch_corners_fused found them
 vstab_status launch_corners_fused_block(const uint8_t *src, size_t pitch, int w, int h, double quality, unsigned int *max_key, unsigned long long *slots,
-                                        unsigned int *tile_counts, float *spill, dim3 grid, hipStream_t s, const DetectSpec &spec);
+                                        unsigned int *tile_counts, float *spill, dim3 grid, hipStream_t s, const DetectSpec &spec, int vec_ok, int mvec_ok);
 // One tracker launch = a SEGMENT of up to LK_SEG_MAX consecutive frame pairs (k_lk_track): pair i is (pyr[i], pyr[i + 1]).
 //   prev_pts  the n start points of pair 0 (device-readable), or NULL when
 //   chain_in  the device records of the parent launch's last pair, whose sequence number is parent_seq: slot f starts from the

@@ -1,4 +1,5 @@
-// vstab_track_device.hpp -- device-side helpers shared by the tracking kernels (vstab_pyramid.hip, vstab_corners.hip, vstab_lk.hip).
+// vstab_track_device.hpp -- device-side helpers shared by the tracking kernels: vstab_pyramid.hip, vstab_lk.hip and vstab_lk_win.hip
+// (vstab_lk_window.hpp) and, through vstab_corners_tile.hpp, the corner units (vstab_corners.hip, vstab_corners_fused.hip, vstab_corners_block.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
