@@ -13,7 +13,7 @@ DEFAULT, CUBIC, LANCZOS4 = 0, 2, 4
 NONE, OWN, OPTION = 0, 1, 2
 CONSTANT, REPLICATE, REFLECT, REFLECT_101 = 0, 1, 2, 4
 BGR8, NV12, PLANAR = 0, 1, 2
-# the route: family, argument block, mode tag (csrc/vstab_device.hpp, MapMode)
+# the route: family, argument block, mode tag (csrc/vstab_map.hpp, MapMode)
 NO_ROUTE, K_FUSED, K_PLANAR, K_BORDER, K_CUBIC, K_LANCZOS4, K_KEEP = range(7)
 WARP_ARGS, CUBIC_ARGS, BORDER_ARGS, KEEP_ARGS = range(4)
 RS0, RS1, RS5, FISHD_RECT, FISHD_FISH, RS_FISHD, RECTD_RECT, RECTD_FISH = 6, 7, 8, 9, 10, 11, 12, 13

@@ -233,7 +233,7 @@ __global__ void __launch_bounds__(256) k_create_map(float *__restrict__ mapx, si
     store_map4(mapx, pitch_x, mapy, pitch_y, x0, y, cols, vec_ok, mx, my);
 }
 
-// k_create_map_ex -- the generalised map (modes 1..4, vstab_device.hpp map_pixel_ex) as map planes.  Lens: the input lens's coefficients --
+// k_create_map_ex -- the generalised map (modes 1..4, vstab_map.hpp map_pixel_ex) as map planes.  Lens: the input lens's coefficients --
 // Distortion (k1..k4 of a fisheye lens, MAP_FISHD_*; zero for the ideal modes) or PinholeLens (the five of a rectilinear lens, MAP_RECTD_*).
 struct PinholeLens {
     float k[5];  // k1, k2, p1, p2, k3
@@ -252,16 +252,14 @@ __global__ void __launch_bounds__(256) k_create_map_ex(float *__restrict__ mapx,
     const MapParams32 in = {p.icx, p.icy, p.ifx, p.ify, p.r[2], p.r[5], p.r[8], lens_fisheye(d)};  // unscaled here
     constexpr bool OCL = MODE == MAP_CREATEMAP_CL_OPENCL;
     const float vy = OCL ? ocl_div((float)y - p.ocy, p.ofy) : ((float)y - p.ocy) / p.ofy;
-    const RowTerm rt = {p.r[1] * vy, p.r[4] * vy, p.r[7] * vy};
     float mx[4], my[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const float vx = OCL ? ocl_div((float)(x0 + i) - p.ocx, p.ofx) : ((float)(x0 + i) - p.ocx) / p.ofx;
-        const ColTerm ct = {p.r[0] * vx, p.r[3] * vx, p.r[6] * vx};
         // the map-plane operator runs the OpenCL build's instruction stream literally; the fused kernel and the
-        // quantised map use its shortened form with this one as the fall-back (vstab_device.hpp)
-        if constexpr (OCL) map_pixel_ocl_literal(p.icx, p.icy, p.ifx, p.ify, p.r, ct.a0, ct.a1, ct.a2, vy, mx[i], my[i]);
-        else map_pixel_ex<MODE>(in, p, ct, rt, vx, vy, mx[i], my[i], lens_pinhole(d));
+        // quantised map use its shortened form with this one as the fall-back (vstab_map.hpp)
+        if constexpr (OCL) map_pixel_ocl_literal(p.icx, p.icy, p.ifx, p.ify, p.r, p.r[0] * vx, p.r[3] * vx, p.r[6] * vx, vy, mx[i], my[i]);
+        else map_at<MODE>(in, p, vx, vy, mx[i], my[i], lens_pinhole(d));
     }
     store_map4(mapx, pitch_x, mapy, pitch_y, x0, y, cols, vec_ok, mx, my);
 }
@@ -310,14 +308,11 @@ __global__ void __launch_bounds__(256) k_quantised_map(int2 *__restrict__ qmap, 
     if (x0 >= qpitch || y >= dh) return;
     const float rfx = rcp_refined(p.ofx), rfy = rcp_refined(p.ofy);
     const float vy = norm_coord<MODE>((float)y - p.ocy, p.ofy, rfy);
-    const RowTerm rt = {p.r[1] * vy, p.r[4] * vy, p.r[7] * vy};
     int q[8];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        const float vx = norm_coord<MODE>((float)(x0 + i) - p.ocx, p.ofx, rfx);
-        const ColTerm ct = {p.r[0] * vx, p.r[3] * vx, p.r[6] * vx};
         float ax, ay;
-        map_pixel_ex<MODE>(p32, p, ct, rt, vx, vy, ax, ay);
+        map_at<MODE>(p32, p, norm_coord<MODE>((float)(x0 + i) - p.ocx, p.ofx, rfx), vy, ax, ay);
         const bool ok = !__builtin_isunordered(ax, ay);
         q[2 * i] = ok ? (int)__builtin_rintf(ax) : INT_MIN, q[2 * i + 1] = (int)__builtin_rintf(ay);
     }

@@ -49,25 +49,14 @@ __device__ __forceinline__ CubicTap cubic_tap(float ax32, float ay32) {  // ax32
     return {min(max(sx >> 5, -32768), 32767), min(max(sy >> 5, -32768), 32767), (sy & 31) * 32 + (sx & 31)};
 }
 
-// 32 * map of output pixel (x, y): k_quantised_map's arithmetic (the fused kernels' map, bit for bit, in every mode)
-// pd: BorderArgs::pd for the MAP_RECTD_* modes
-template <int MODE>
-__device__ __forceinline__ void cubic_map(const CubicArgs &c, int x, int y, float rfx, float rfy, float &ax, float &ay, const float *pd = nullptr) {
-    const MapParams &p = c.w.p;
-    const float vy = norm_coord<MODE>((float)y - p.ocy, p.ofy, rfy);
-    const RowTerm rt = {p.r[1] * vy, p.r[4] * vy, p.r[7] * vy};
-    const float vx = norm_coord<MODE>((float)x - p.ocx, p.ofx, rfx);
-    const ColTerm ct = {p.r[0] * vx, p.r[3] * vx, p.r[6] * vx};
-    map_pixel_ex<MODE>(c.p32, p, ct, rt, vx, vy, ax, ay, pd);
-}
-
-// 32 * map of output pixel (x, y): cubic_map's arithmetic; RS: the row's own rotation, m_k = fmaf(t, rs_d[k], r[k]) with
-// t = (float)y / rs_den, fed to the mode's arithmetic as the per-row warp (vstab_warp_tile.hpp, map_phase) does
+// 32 * map of output pixel (x, y) for the kernels that take BorderArgs: map_at (vstab_map.hpp), with BorderArgs::pd for the MAP_RECTD_* modes.
+// RS: the row's own rotation, m_k = fmaf(t, rs_d[k], r[k]) with t = (float)y / rs_den, fed to the mode's arithmetic as the per-row warp
+// (vstab_warp_tile.hpp, map_phase) does.  Its preamble stands in place: through map_at, with the rotation a per-thread value, the four
+// k_warp_keep kernels with a rotation per row came out another (modes 0 and 1: 2015 -> 2007, 2586 -> 2587, 2031 -> 2034, 2627 -> 2612
+// lines), and so did every such k_warp_border, k_warp_cubic_rs and k_warp_lanczos4_rs kernel of modes 0, 1 and 11.
 template <int MODE, bool RS>
 __device__ __forceinline__ void border_map(const BorderArgs &ba, int x, int y, float rfx, float rfy, float &ax, float &ay) {
-    if constexpr (!RS) {
-        cubic_map<MODE>(ba.c, x, y, rfx, rfy, ax, ay, ba.pd);
-    } else {
+    if constexpr (RS) {
         const MapParams &p0 = ba.c.w.p;
         MapParams P = p0;
         const float t = div_with_rcp((float)y, ba.rs_den, rcp_refined(ba.rs_den));
@@ -80,6 +69,8 @@ __device__ __forceinline__ void border_map(const BorderArgs &ba, int x, int y, f
         const float vx = norm_coord<MODE>((float)x - P.ocx, P.ofx, rfx);
         const ColTerm ct = {P.r[0] * vx, P.r[3] * vx, P.r[6] * vx};
         map_pixel_ex<MODE>(p32, P, ct, rt, vx, vy, ax, ay);
+    } else {
+        map_at<MODE>(ba.c.p32, ba.c.w.p, x, y, rfx, rfy, ax, ay, ba.pd);
     }
 }
 
@@ -368,7 +359,7 @@ __device__ __forceinline__ void resample_tile(const CubicArgs &c, uint8_t *stage
     float ax[RESAMPLE_RW], ay[RESAMPLE_RW];
 #pragma unroll
     for (int j = 0; j < RESAMPLE_RW; j++) {
-        cubic_map<MODE>(c, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
+        map_at<MODE>(c.p32, c.w.p, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
         t[j] = cubic_tap(ax[j], ay[j]);
     }
     // 2. box of the luma / BGR footprints: every pixel, no "touches the source" filter

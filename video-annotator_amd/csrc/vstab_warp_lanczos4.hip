@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(256) k_warp_lanczos4(CubicArgs c) {
     float ax[RESAMPLE_RW], ay[RESAMPLE_RW];
 #pragma unroll
     for (int j = 0; j < RESAMPLE_RW; j++) {
-        cubic_map<MODE>(c, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
+        map_at<MODE>(c.p32, c.w.p, min(x, a.dw - 1), min(y0 + j, a.dh - 1), rfx, rfy, ax[j], ay[j]);
         t[j] = cubic_tap(ax[j], ay[j]);
     }
     // 2. box of the luma / BGR taps

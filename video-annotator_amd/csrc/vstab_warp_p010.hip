@@ -60,8 +60,24 @@ __device__ __forceinline__ void sample10(const P010Args &a, float ax, float ay, 
     o[0] = (uint16_t)B, o[1] = (uint16_t)G, o[2] = (uint16_t)R;
 }
 
+// The map of two pixels of one column, map mode 0 or 1 (FISH_TO_RECT): fish_chain (vstab_map.hpp) over f32x2.  a = column terms, b = row terms,
+// r = third column of the rotation, each for the two rows.  The rays are formed here, not in the kernel: there its eight instantiations
+// came out another (903 -> 905 lines, 30 -> 29 registers, and the like).
+template <bool FISH_TO_RECT>
+__device__ __forceinline__ void map_pair(float icx32, float icy32, float ifx32, float ify32, f32x2 r02, f32x2 r12, f32x2 r22,
+                                         f32x2 a0, f32x2 a1, f32x2 a2, f32x2 b0, f32x2 b1, f32x2 b2, f32x2 &ax, f32x2 &ay) {
+    const f32x2 wz = (a2 + b2) + r22;
+    const struct {
+        f32x2 icx32, icy32, ifx32, ify32;
+    } cam = {splat2(icx32), splat2(icy32), splat2(ifx32), splat2(ify32)};
+    fish_chain<FISH_TO_RECT, false>(cam, (a0 + b0) + r02, (a1 + b1) + r12, wz, ax, ay);
+    if constexpr (FISH_TO_RECT) {  // behind the camera: outside
+        const i32x2 ok = wz > splat2(0.0f);
+        ax = ok ? ax : splat2(__builtin_nanf("")), ay = ok ? ay : splat2(__builtin_nanf(""));
+    }
+}
 // A thread owns two vertically adjacent output pixels, so that the map of the fisheye-input modes runs as packed fp32
-// (map_pixel32_x2: the hand-scheduled IEEE sequences of the 8-bit kernel, two pixels per instruction; 32 * map, an
+// (fish_chain over f32x2: the hand-scheduled IEEE sequences of the 8-bit kernel, two pixels per instruction; 32 * map, an
 // exact power-of-two scaling of the map the definition quantises).
 // COLOUR (vstab_warp_p010_colour): the taps are converted with the coefficients of a.col, a spec's row of the 10-bit table.
 template <int MODE, int BLEND, bool COLOUR = false>
@@ -81,12 +97,13 @@ __global__ void __launch_bounds__(256) k_warp_p010(P010Args a) {
                          OCL ? ocl_div((float)(y0 + 1) - a.p.ocy, a.p.ofy) : ((float)(y0 + 1) - a.p.ocy) / a.p.ofy};
     float ax[2], ay[2];
     if constexpr (MODE == MAP_CREATEMAP_CL || MODE == MAP_FISH_TO_RECT) {
+        // the rays of the two rows: column terms, row terms and third column each of the row's own rotation
         f32x2 px, py;
-        map_pixel32_x2<MODE == MAP_FISH_TO_RECT>(a.p.icx * 32.0f, a.p.icy * 32.0f, a.p.ifx * 32.0f, a.p.ify * 32.0f, (f32x2){m[0][2], m[1][2]},
-                                                 (f32x2){m[0][5], m[1][5]}, (f32x2){m[0][8], m[1][8]}, (f32x2){m[0][0] * vx, m[1][0] * vx},
-                                                 (f32x2){m[0][3] * vx, m[1][3] * vx}, (f32x2){m[0][6] * vx, m[1][6] * vx},
-                                                 (f32x2){m[0][1] * vy[0], m[1][1] * vy[1]}, (f32x2){m[0][4] * vy[0], m[1][4] * vy[1]},
-                                                 (f32x2){m[0][7] * vy[0], m[1][7] * vy[1]}, px, py);
+        map_pair<MODE == MAP_FISH_TO_RECT>(a.p.icx * 32.0f, a.p.icy * 32.0f, a.p.ifx * 32.0f, a.p.ify * 32.0f, (f32x2){m[0][2], m[1][2]},
+                                           (f32x2){m[0][5], m[1][5]}, (f32x2){m[0][8], m[1][8]}, (f32x2){m[0][0] * vx, m[1][0] * vx},
+                                           (f32x2){m[0][3] * vx, m[1][3] * vx}, (f32x2){m[0][6] * vx, m[1][6] * vx},
+                                           (f32x2){m[0][1] * vy[0], m[1][1] * vy[1]}, (f32x2){m[0][4] * vy[0], m[1][4] * vy[1]},
+                                           (f32x2){m[0][7] * vy[0], m[1][7] * vy[1]}, px, py);
         ax[0] = px.x, ax[1] = px.y, ay[0] = py.x, ay[1] = py.y;
     } else {
 #pragma unroll
@@ -94,6 +111,7 @@ __global__ void __launch_bounds__(256) k_warp_p010(P010Args a) {
             MapParams q = a.p;
 #pragma unroll
             for (int k = 0; k < 9; k++) q.r[k] = m[r][k];
+            // the preamble in place, not through map_at: that reorders the four MAP_RECT_TO_RECT kernels (19 to 44 lines in place)
             const ColTerm ct = {q.r[0] * vx, q.r[3] * vx, q.r[6] * vx};
             const RowTerm rt = {q.r[1] * vy[r], q.r[4] * vy[r], q.r[7] * vy[r]};
             const MapParams32 in = {q.icx, q.icy, q.ifx, q.ify, q.r[2], q.r[5], q.r[8]};  // unscaled

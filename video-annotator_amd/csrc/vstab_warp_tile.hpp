@@ -168,7 +168,8 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
             // The box needs the map to a fraction of a pixel only (it has a pixel of margin and never decides a result; the dead-tile rule
             // that reads the same samples has a margin of 16),
             // so the probe uses the approximate reciprocal / rsqrt instructions and fused operations: a third of the
-            // dependent chain of the exact evaluation, on the one wave the other three are waiting for.
+            // dependent chain of the exact evaluation, on the one wave the other three are waiting for.  Its own operation order,
+            // therefore; the arc tangent's coefficients and pi/2 are vstab_map.hpp's.
             const float vx = ((float)(x0 + px) - a.p.ocx) * rfx, vy = ((float)(y0 + py) - a.p.ocy) * rfy;
             float m[9];
 #pragma unroll
@@ -185,16 +186,16 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
             const float q = __builtin_fmaf(ux, ux, uy * uy), rs = __builtin_amdgcn_rsqf(q), rad = q * rs;
             const bool inv = rad > 1.0f;
             const float t = inv ? rs : rad, s2 = t * t;
-            float g = 0.0028423243202269077f;
-            g = __builtin_fmaf(g, s2, -0.016053270548582077f);
-            g = __builtin_fmaf(g, s2, 0.04269874095916748f);
-            g = __builtin_fmaf(g, s2, -0.07508683204650879f);
-            g = __builtin_fmaf(g, s2, 0.1064559817314148f);
-            g = __builtin_fmaf(g, s2, -0.14205896854400635f);
-            g = __builtin_fmaf(g, s2, 0.19993145763874054f);
-            g = __builtin_fmaf(g, s2, -0.33333125710487366f);
+            float g = ATAN_Q[0];
+            g = __builtin_fmaf(g, s2, ATAN_Q[1]);
+            g = __builtin_fmaf(g, s2, ATAN_Q[2]);
+            g = __builtin_fmaf(g, s2, ATAN_Q[3]);
+            g = __builtin_fmaf(g, s2, ATAN_Q[4]);
+            g = __builtin_fmaf(g, s2, ATAN_Q[5]);
+            g = __builtin_fmaf(g, s2, ATAN_Q[6]);
+            g = __builtin_fmaf(g, s2, ATAN_Q[7]);
             float at = __builtin_fmaf(t * s2, g, t);
-            at = inv ? 1.57079637050628662109375f - at : at;
+            at = inv ? PIO2_HI - at : at;
             if constexpr (BASE == MAP_FISHD_TO_RECT) {  // theta -> theta_d (fused: the probe decides no result)
                 const Distortion &dk = ta.p32.d;
                 const float a2 = at * at;
@@ -206,6 +207,8 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
             if ((BASE == MAP_FISH_TO_RECT || BASE == MAP_FISHD_TO_RECT) && !(wz > 0.0f)) ax = ay = __builtin_nanf("");
             if constexpr (DEAD) dead = tile_dead_rule(ax, ay, wz, rz, __builtin_fmaxf(ta.p32.ifx32, ta.p32.ify32) * __builtin_fmaxf(rfx, rfy), a.sw, a.sh);
         } else {
+            // the preamble in place, not through map_at (vstab_map.hpp): that made every k_warp_fused / k_warp_planar kernel of modes 2, 4
+            // and 10 another by one to five lines (same registers)
             const float vx = div_with_rcp((float)(x0 + px) - a.p.ocx, a.p.ofx, rfx);
             const float vy = div_with_rcp((float)(y0 + py) - a.p.ocy, a.p.ofy, rfy);
             const ColTerm ct = {a.p.r[0] * vx, a.p.r[3] * vx, a.p.r[6] * vx};
@@ -251,10 +254,11 @@ __device__ __forceinline__ void probe_tile(const FusedArgs &ta, int x0, int y0, 
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The exact map of NP row pairs of one column (lane), IEEE mode (MAP_CREATEMAP_CL / MAP_FISH_TO_RECT): the operation
-// sequence of map_pixel32_x2 (vstab_device.hpp) for every pair, written step by step ACROSS the pairs, so that NP
+// sequence of fish_chain<FISH_TO_RECT, DIST, f32x2> (vstab_map.hpp) for every pair, written step by step ACROSS the pairs, so that NP
 // independent packed instructions stand between an instruction and the one that needs its result (the compiler
 // otherwise emits the chains one after the other, separated by the s_nop a dependent packed-fp32 instruction needs).
-// DIST (MAP_FISHD_TO_RECT): distort_theta's steps (vstab_device.hpp) between the arc tangent and the division by the radius, every
+// That is why this form keeps its own text; the arc tangent's coefficients and pi/2 are read from vstab_map.hpp.
+// DIST (MAP_FISHD_TO_RECT): distort_theta's steps (vstab_map.hpp) between the arc tangent and the division by the radius, every
 // multiplication and addition an instruction of its own.
 // ---------------------------------------------------------------------------------------------------------------------
 #define VSTAB_EACH _Pragma("unroll") for (int c = 0; c < NP; c++)
@@ -264,46 +268,46 @@ __device__ __forceinline__ void map_pairs_ieee(float icx32, float icy32, float i
     f32x2 rz[NP], e[NP], px[NP], py[NP], ex[NP], ey[NP], q[NP], y[NP], g[NP], h[NP], d[NP], rad[NP], rr[NP], t[NP], s[NP], at[NP], k[NP];
     i32x2 inv[NP];
     const f32x2 one = splat2(1.0f), half = splat2(0.5f);
-    // rz = rcp_refined2(wz)
-    VSTAB_EACH rz[c] = (f32x2){__builtin_amdgcn_rcpf(wz[c].x), __builtin_amdgcn_rcpf(wz[c].y)};
-    VSTAB_EACH e[c] = fma2(-wz[c], rz[c], one);
-    VSTAB_EACH rz[c] = fma2(e[c], rz[c], rz[c]);
-    // px = div_with_rcp2(wx, wz, rz), py = div_with_rcp2(wy, wz, rz)
+    // rz = rcp_refined(wz)
+    VSTAB_EACH rz[c] = rcp_seed(wz[c]);
+    VSTAB_EACH e[c] = vfma(-wz[c], rz[c], one);
+    VSTAB_EACH rz[c] = vfma(e[c], rz[c], rz[c]);
+    // px = div_with_rcp(wx, wz, rz), py = div_with_rcp(wy, wz, rz)
     VSTAB_EACH px[c] = wx[c] * rz[c], py[c] = wy[c] * rz[c];
-    VSTAB_EACH ex[c] = fma2(-wz[c], px[c], wx[c]), ey[c] = fma2(-wz[c], py[c], wy[c]);
-    VSTAB_EACH px[c] = fma2(ex[c], rz[c], px[c]), py[c] = fma2(ey[c], rz[c], py[c]);
-    VSTAB_EACH ex[c] = fma2(-wz[c], px[c], wx[c]), ey[c] = fma2(-wz[c], py[c], wy[c]);
-    VSTAB_EACH px[c] = fma2(ex[c], rz[c], px[c]), py[c] = fma2(ey[c], rz[c], py[c]);
-    // q = px * px + py * py ; rad = sqrt_rn2(q)
+    VSTAB_EACH ex[c] = vfma(-wz[c], px[c], wx[c]), ey[c] = vfma(-wz[c], py[c], wy[c]);
+    VSTAB_EACH px[c] = vfma(ex[c], rz[c], px[c]), py[c] = vfma(ey[c], rz[c], py[c]);
+    VSTAB_EACH ex[c] = vfma(-wz[c], px[c], wx[c]), ey[c] = vfma(-wz[c], py[c], wy[c]);
+    VSTAB_EACH px[c] = vfma(ex[c], rz[c], px[c]), py[c] = vfma(ey[c], rz[c], py[c]);
+    // q = px * px + py * py ; rad = sqrt_rn(q)
     VSTAB_EACH q[c] = px[c] * px[c] + py[c] * py[c];
-    VSTAB_EACH y[c] = (f32x2){__builtin_amdgcn_rsqf(q[c].x), __builtin_amdgcn_rsqf(q[c].y)};
+    VSTAB_EACH y[c] = rsq_seed(q[c]);
     VSTAB_EACH g[c] = q[c] * y[c], h[c] = half * y[c];
-    VSTAB_EACH e[c] = fma2(-h[c], g[c], half);
-    VSTAB_EACH h[c] = fma2(h[c], e[c], h[c]), g[c] = fma2(g[c], e[c], g[c]);
-    VSTAB_EACH d[c] = fma2(-g[c], g[c], q[c]);
-    VSTAB_EACH rad[c] = fma2(d[c], h[c], g[c]);
-    // rr = rcp_refined2(rad)
-    VSTAB_EACH rr[c] = (f32x2){__builtin_amdgcn_rcpf(rad[c].x), __builtin_amdgcn_rcpf(rad[c].y)};
-    VSTAB_EACH e[c] = fma2(-rad[c], rr[c], one);
-    VSTAB_EACH rr[c] = fma2(e[c], rr[c], rr[c]);
-    // t = inv ? div_with_rcp2(1, rad, rr) : rad
+    VSTAB_EACH e[c] = vfma(-h[c], g[c], half);
+    VSTAB_EACH h[c] = vfma(h[c], e[c], h[c]), g[c] = vfma(g[c], e[c], g[c]);
+    VSTAB_EACH d[c] = vfma(-g[c], g[c], q[c]);
+    VSTAB_EACH rad[c] = vfma(d[c], h[c], g[c]);
+    // rr = rcp_refined(rad)
+    VSTAB_EACH rr[c] = rcp_seed(rad[c]);
+    VSTAB_EACH e[c] = vfma(-rad[c], rr[c], one);
+    VSTAB_EACH rr[c] = vfma(e[c], rr[c], rr[c]);
+    // t = inv ? div_with_rcp(1, rad, rr) : rad
     VSTAB_EACH inv[c] = rad[c] > one, t[c] = one * rr[c];
-    VSTAB_EACH e[c] = fma2(-rad[c], t[c], one);
-    VSTAB_EACH t[c] = fma2(e[c], rr[c], t[c]);
-    VSTAB_EACH e[c] = fma2(-rad[c], t[c], one);
-    VSTAB_EACH t[c] = fma2(e[c], rr[c], t[c]);
+    VSTAB_EACH e[c] = vfma(-rad[c], t[c], one);
+    VSTAB_EACH t[c] = vfma(e[c], rr[c], t[c]);
+    VSTAB_EACH e[c] = vfma(-rad[c], t[c], one);
+    VSTAB_EACH t[c] = vfma(e[c], rr[c], t[c]);
     VSTAB_EACH t[c] = inv[c] ? t[c] : rad[c];
     VSTAB_EACH s[c] = t[c] * t[c];
-    // atan_pos polynomial
-    VSTAB_EACH g[c] = fma2(splat2(0.0028423243202269077f), s[c], splat2(-0.016053270548582077f));
-    VSTAB_EACH g[c] = fma2(g[c], s[c], splat2(0.04269874095916748f));
-    VSTAB_EACH g[c] = fma2(g[c], s[c], splat2(-0.07508683204650879f));
-    VSTAB_EACH g[c] = fma2(g[c], s[c], splat2(0.1064559817314148f));
-    VSTAB_EACH g[c] = fma2(g[c], s[c], splat2(-0.14205896854400635f));
-    VSTAB_EACH g[c] = fma2(g[c], s[c], splat2(0.19993145763874054f));
-    VSTAB_EACH g[c] = fma2(g[c], s[c], splat2(-0.33333125710487366f));
-    VSTAB_EACH at[c] = fma2(t[c] * s[c], g[c], t[c]);
-    VSTAB_EACH at[c] = inv[c] ? (splat2(1.57079637050628662109375f) - at[c]) + splat2(-4.37113900018624283e-8f) : at[c];
+    // VSTAB_ATAN_WITH_RCP's polynomial
+    VSTAB_EACH g[c] = vfma(splat2(ATAN_Q[0]), s[c], splat2(ATAN_Q[1]));
+    VSTAB_EACH g[c] = vfma(g[c], s[c], splat2(ATAN_Q[2]));
+    VSTAB_EACH g[c] = vfma(g[c], s[c], splat2(ATAN_Q[3]));
+    VSTAB_EACH g[c] = vfma(g[c], s[c], splat2(ATAN_Q[4]));
+    VSTAB_EACH g[c] = vfma(g[c], s[c], splat2(ATAN_Q[5]));
+    VSTAB_EACH g[c] = vfma(g[c], s[c], splat2(ATAN_Q[6]));
+    VSTAB_EACH g[c] = vfma(g[c], s[c], splat2(ATAN_Q[7]));
+    VSTAB_EACH at[c] = vfma(t[c] * s[c], g[c], t[c]);
+    VSTAB_EACH at[c] = inv[c] ? (splat2(PIO2_HI) - at[c]) + splat2(PIO2_LO) : at[c];
     if constexpr (DIST) {  // at = distort_theta(at, dk); s and g are free again
         VSTAB_EACH s[c] = at[c] * at[c];
         VSTAB_EACH g[c] = splat2(dk.k4) * s[c];
@@ -316,12 +320,12 @@ __device__ __forceinline__ void map_pairs_ieee(float icx32, float icy32, float i
         VSTAB_EACH g[c] = one + g[c];
         VSTAB_EACH at[c] = at[c] * g[c];
     }
-    // k = div_with_rcp2(at, rad, rr)
+    // k = div_with_rcp(at, rad, rr)
     VSTAB_EACH k[c] = at[c] * rr[c];
-    VSTAB_EACH e[c] = fma2(-rad[c], k[c], at[c]);
-    VSTAB_EACH k[c] = fma2(e[c], rr[c], k[c]);
-    VSTAB_EACH e[c] = fma2(-rad[c], k[c], at[c]);
-    VSTAB_EACH k[c] = fma2(e[c], rr[c], k[c]);
+    VSTAB_EACH e[c] = vfma(-rad[c], k[c], at[c]);
+    VSTAB_EACH k[c] = vfma(e[c], rr[c], k[c]);
+    VSTAB_EACH e[c] = vfma(-rad[c], k[c], at[c]);
+    VSTAB_EACH k[c] = vfma(e[c], rr[c], k[c]);
     if constexpr (FISH_TO_RECT) {
         VSTAB_EACH k[c] = (q[c] == splat2(0.0f)) ? one : k[c];
     }
@@ -334,7 +338,7 @@ __device__ __forceinline__ void map_pairs_ieee(float icx32, float icy32, float i
     }
 }
 
-// The same for MAP_CREATEMAP_CL_OPENCL: map_pixel_ocl_fast (vstab_device.hpp) on NP row pairs in lock-step.  qmin / qmax
+// The same for MAP_CREATEMAP_CL_OPENCL: map_pixel_ocl_fast (vstab_map.hpp) on NP row pairs in lock-step.  qmin / qmax
 // collect the range of q (its bits as unsigned) over all the caller's pixels: when some intermediate may have left the
 // normal range the caller re-evaluates the wave's pixels with the code object's literal instruction stream.
 // q in [2^-80, 2^80] is the whole test (map_q_irregular): a rotated ray has a component >= 1/2, so a reciprocal, quotient
@@ -345,28 +349,28 @@ __device__ __forceinline__ void map_pairs_ocl(float icx32, float icy32, float if
                                               const f32x2 (&wz)[NP], f32x2 (&ax)[NP], f32x2 (&ay)[NP], uint32_t &qmin, uint32_t &qmax) {
     f32x2 rz[NP], px[NP], py[NP], q[NP], rad[NP], rr[NP], t[NP], s[NP], p[NP], r[NP], k[NP];
     i32x2 inv[NP];
-    VSTAB_EACH rz[c] = (f32x2){__builtin_amdgcn_rcpf(wz[c].x), __builtin_amdgcn_rcpf(wz[c].y)};
+    VSTAB_EACH rz[c] = rcp_seed(wz[c]);
     VSTAB_EACH px[c] = wx[c] * rz[c], py[c] = wy[c] * rz[c];
-    VSTAB_EACH q[c] = fma2(py[c], py[c], px[c] * px[c]);
+    VSTAB_EACH q[c] = vfma(py[c], py[c], px[c] * px[c]);
     VSTAB_EACH rad[c] = (f32x2){__builtin_amdgcn_sqrtf(q[c].x), __builtin_amdgcn_sqrtf(q[c].y)};
     VSTAB_EACH {
         qmin = min(min(qmin, __float_as_uint(q[c].x)), __float_as_uint(q[c].y));
         qmax = max(max(qmax, __float_as_uint(q[c].x)), __float_as_uint(q[c].y));
     }
-    VSTAB_EACH rr[c] = (f32x2){__builtin_amdgcn_rcpf(rad[c].x), __builtin_amdgcn_rcpf(rad[c].y)};
+    VSTAB_EACH rr[c] = rcp_seed(rad[c]);
     VSTAB_EACH inv[c] = rad[c] > splat2(1.0f), t[c] = inv[c] ? rr[c] : rad[c];
     VSTAB_EACH s[c] = t[c] * t[c];
-    VSTAB_EACH p[c] = fma2(splat2(f32_bits(0x3b2d2a58u)), s[c], splat2(f32_bits(0xbc7a590cu)));
-    VSTAB_EACH p[c] = fma2(s[c], p[c], splat2(f32_bits(0x3d29fb3fu)));
-    VSTAB_EACH p[c] = fma2(s[c], p[c], splat2(f32_bits(0xbd97d4d7u)));
-    VSTAB_EACH p[c] = fma2(s[c], p[c], splat2(f32_bits(0x3dd931b2u)));
-    VSTAB_EACH p[c] = fma2(s[c], p[c], splat2(f32_bits(0xbe1160e6u)));
-    VSTAB_EACH p[c] = fma2(s[c], p[c], splat2(f32_bits(0x3e4cb8bfu)));
-    VSTAB_EACH p[c] = fma2(s[c], p[c], splat2(f32_bits(0xbeaaaa62u)));
-    VSTAB_EACH r[c] = fma2(t[c], s[c] * p[c], t[c]);
-    VSTAB_EACH r[c] = inv[c] ? splat2(f32_bits(0x3fc90fdbu)) - r[c] : r[c];
+    VSTAB_EACH p[c] = vfma(splat2(OCML_ATAN[0]), s[c], splat2(OCML_ATAN[1]));
+    VSTAB_EACH p[c] = vfma(s[c], p[c], splat2(OCML_ATAN[2]));
+    VSTAB_EACH p[c] = vfma(s[c], p[c], splat2(OCML_ATAN[3]));
+    VSTAB_EACH p[c] = vfma(s[c], p[c], splat2(OCML_ATAN[4]));
+    VSTAB_EACH p[c] = vfma(s[c], p[c], splat2(OCML_ATAN[5]));
+    VSTAB_EACH p[c] = vfma(s[c], p[c], splat2(OCML_ATAN[6]));
+    VSTAB_EACH p[c] = vfma(s[c], p[c], splat2(OCML_ATAN[7]));
+    VSTAB_EACH r[c] = vfma(t[c], s[c] * p[c], t[c]);
+    VSTAB_EACH r[c] = inv[c] ? splat2(OCML_PIO2) - r[c] : r[c];
     VSTAB_EACH k[c] = r[c] * rr[c];
-    VSTAB_EACH ax[c] = fma2(splat2(ifx32), px[c] * k[c], splat2(icx32)), ay[c] = fma2(splat2(ify32), py[c] * k[c], splat2(icy32));
+    VSTAB_EACH ax[c] = vfma(splat2(ifx32), px[c] * k[c], splat2(icx32)), ay[c] = vfma(splat2(ify32), py[c] * k[c], splat2(icy32));
 }
 #undef VSTAB_EACH
 
@@ -470,13 +474,13 @@ __device__ __forceinline__ void map_phase(const FusedArgs &ta, const int x, cons
                     const int j = 2 * (g0 + c);
                     const f32x2 vy2 = bcast2(vy_l, j);
                     if constexpr (RS) {  // every row has its own matrix (the definition's fp32 interpolation), fed to createMap.cl's stream
-                        wz[c] = fma2(bcast2(m_l[7], j), vy2, bcast2(m_l[6], j) * splat2(vx)) + bcast2(m_l[8], j);
-                        wx[c] = fma2(bcast2(m_l[1], j), vy2, bcast2(m_l[0], j) * splat2(vx)) + bcast2(m_l[2], j);
-                        wy[c] = fma2(bcast2(m_l[4], j), vy2, bcast2(m_l[3], j) * splat2(vx)) + bcast2(m_l[5], j);
+                        wz[c] = vfma(bcast2(m_l[7], j), vy2, bcast2(m_l[6], j) * splat2(vx)) + bcast2(m_l[8], j);
+                        wx[c] = vfma(bcast2(m_l[1], j), vy2, bcast2(m_l[0], j) * splat2(vx)) + bcast2(m_l[2], j);
+                        wy[c] = vfma(bcast2(m_l[4], j), vy2, bcast2(m_l[3], j) * splat2(vx)) + bcast2(m_l[5], j);
                     } else {
-                        wz[c] = fma2(splat2(a.p.r[7]), vy2, splat2(ct.a2)) + splat2(a.p.r[8]);
-                        wx[c] = fma2(splat2(a.p.r[1]), vy2, splat2(ct.a0)) + splat2(a.p.r[2]);
-                        wy[c] = fma2(splat2(a.p.r[4]), vy2, splat2(ct.a1)) + splat2(a.p.r[5]);
+                        wz[c] = vfma(splat2(a.p.r[7]), vy2, splat2(ct.a2)) + splat2(a.p.r[8]);
+                        wx[c] = vfma(splat2(a.p.r[1]), vy2, splat2(ct.a0)) + splat2(a.p.r[2]);
+                        wy[c] = vfma(splat2(a.p.r[4]), vy2, splat2(ct.a1)) + splat2(a.p.r[5]);
                     }
                 }
                 map_pairs_ocl<NP>(icx32, icy32, ifx32, ify32, wx, wy, wz, ax, ay, qmin, qmax);
@@ -516,7 +520,7 @@ __device__ __forceinline__ void map_phase(const FusedArgs &ta, const int x, cons
 #pragma unroll
             for (int j = 0; j < RW; j++) {
                 const float vy = bcast(vy_l, j);
-                const RowTerm rt = {bcast(b0_l, j), bcast(b1_l, j), bcast(b2_l, j)};
+                const RowTerm rt = {bcast(b0_l, j), bcast(b1_l, j), bcast(b2_l, j)};  // the row's terms come from its lane: not map_at
                 float fx, fy;
                 map_pixel_ex<BASE>(ta.p32, a.p, ct, rt, vx, vy, fx, fy);
                 qxb[j] = __float_as_int(fx + QMX), qyb[j] = __float_as_int(fy + QMY);
