@@ -496,8 +496,8 @@ VSTAB_API vstab_status vstab_good_features_mask(const void *gray, size_t pitch, 
  *      read as int32; that order is wrong among negative values but right about the sign: if any value is >= +0 the maximum's bits are
  *      >= 0.  The sign of the published maximum decides this rule, on every path.
  *   5. k is finite with 0 <= k < 0.25: from 0.25 on, det - k tr^2 is never positive.  Anything else is refused.
- * The minimum-eigenvalue detector keeps its definition and its caveat ("Detection mask" above) word for word.  gradientSize other than 3
- * is not offered; blockSize 5 and 7 are "Corner block size" below.
+ * The minimum-eigenvalue detector keeps its definition and its caveat ("Detection mask" above) word for word.  gradientSize 5 and 7 are
+ * "Corner gradient size" below; blockSize 5 and 7 are "Corner block size" below.
  *
  * vstab_corner_harris is vstab_min_eig's twin: response_f32 is a dense width x height device map of R.  Refused with VSTAB_ERR_INVALID
  * before any launch: "vstab_corner_harris: bad argument" (what vstab_min_eig refuses), then "vstab_corner_harris: k lies in [0, 0.25)".
@@ -511,7 +511,7 @@ VSTAB_API vstab_status vstab_good_features_harris(const void *gray, size_t pitch
 
 /* ---- Corner block size ------------------------------------------------------------------------------------------------------------
  * goodFeaturesToTrack's `blockSize`: the window of the covariance sums.  B = block_size is 3, 5 or 7, r = (B - 1) / 2; everything else is
- * refused, not clamped (even sizes, 1, 9 and larger).  gradientSize stays 3.  Like the rest of the detector this restates OpenCV 4.5's CPU
+ * refused, not clamped (even sizes, 1, 9 and larger).  gradientSize is "Corner gradient size" below.  Like the rest of the detector this restates OpenCV 4.5's CPU
  * path -- cornerMinEigenVal(gray, B, 3), cornerHarris(gray, B, 3, k), goodFeaturesToTrack(..., mask, B, useHarris, k) -- in this library's
  * arithmetic; no bit equality with OpenCV is claimed.
  *   1. Derivatives.  The 3 x 3 Sobel pair of vstab_min_eig in its documented operation order, REFLECT_101 of the source, with the scale
@@ -544,6 +544,39 @@ VSTAB_API vstab_status vstab_good_features_block(const void *gray, size_t pitch,
                                                  int max_corners, double quality, double min_distance, int block_size, int use_harris, double k,
                                                  int detector, float *xy, int *count, int *detector_used, void *stream);
 
+/* ---- Corner gradient size ---------------------------------------------------------------------------------------------------------
+ * goodFeaturesToTrack's `gradientSize`: the Sobel aperture of cornerMinEigenVal / cornerHarris.  G = gradient_size is 3, 5 or 7,
+ * g = (G - 1) / 2; everything else is refused, not clamped (1, even sizes, 9 and larger, OpenCV's -1 for Scharr).  B = block_size is 3, 5
+ * or 7 as in "Corner block size"; all nine pairs are served.  Like the rest of the detector this restates OpenCV 4.5's CPU path --
+ * cornerMinEigenVal(gray, B, G), cornerHarris(gray, B, G, k), goodFeaturesToTrack(gray, corners, maxCorners, quality, minDistance, mask, B,
+ * G, useHarris, k) -- in this library's arithmetic; no bit equality with OpenCV is claimed.
+ *   1. Kernels.  getDerivKernels' integer Sobel pair.  Smoothing s, from the centre outwards: G = 3 (2, 1); G = 5 (6, 4, 1); G = 7
+ *      (20, 15, 6, 1).  Derivative d on the positive side, antisymmetric, d_0 = 0: G = 3 (1); G = 5 (2, 1); G = 7 (5, 4, 1).
+ *   2. Scale.  sigma = 1.0 / ((double)(1 << (G - 1)) * B * 255.0) in double; the scaled smoothing coefficients are
+ *      k_i = (float)((double)s_i * sigma).  For G = 3 these are k1 = scale_B, k0 = 2.0f * scale_B of "Corner block size" bit for bit.
+ *   3. dx.  Row pass: D(y, x) = sum over i = 1 .. g of d_i * (I(y, x + i) - I(y, x - i)) over the REFLECT_101 extension of the source:
+ *      whole numbers of magnitude <= 2550, exact as floats.  Column pass in binary32, nothing contracted, the outermost pair first and the
+ *      centre last: dx = (...((D(y - g) + D(y + g)) * k_g + (D(y - g + 1) + D(y + g - 1)) * k_(g-1)) + ...) + D(y) * k_0.
+ *   4. dy.  Row pass in binary32, the centre first and outwards, added left to right:
+ *      S(y, x) = ((I(x) * k_0 + (I(x - 1) + I(x + 1)) * k_1) + (I(x - 2) + I(x + 2)) * k_2) + ...; column pass
+ *      dy = ((float)d_1 * (S(y + 1) - S(y - 1)) + (float)d_2 * (S(y + 2) - S(y - 2))) + ..., ascending i.
+ *   5. Everything else is "Corner block size" rules 2 - 5, unchanged: the three float products, the B x B box sum over the product planes
+ *      extended by REFLECT_101 in its defined order, the two response formulas, and a detector in which nothing depends on G (interior
+ *      pixels are 1 .. width - 2 and 1 .. height - 2 whatever G is).  With G other than 3 the order of the box sum is part of the
+ *      definition for B = 3 as well: the nine-product sums that are exact in double at G = 3 are not always exact at G = 5 and 7.
+ * With gradient_size 3 each of the three calls below IS its "Corner block size" twin: the same kernels, the same bytes.
+ *
+ * vstab_good_features_grad is goodFeaturesToTrack's ten-argument overload.  The refusals (VSTAB_ERR_INVALID, before any launch) are those
+ * of the _block twin under the new name, in its order, with "<fn>: gradient_size is 3, 5 or 7" directly behind
+ * "<fn>: block_size is 3, 5 or 7". */
+VSTAB_API vstab_status vstab_min_eig_grad(const void *gray, size_t pitch, int width, int height, int block_size, int gradient_size, void *eig_f32,
+                                          void *stream);
+VSTAB_API vstab_status vstab_corner_harris_grad(const void *gray, size_t pitch, int width, int height, int block_size, int gradient_size, double k,
+                                                void *response_f32, void *stream);
+VSTAB_API vstab_status vstab_good_features_grad(const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask,
+                                                int max_corners, double quality, double min_distance, int block_size, int gradient_size,
+                                                int use_harris, double k, int detector, float *xy, int *count, int *detector_used, void *stream);
+
 /* Replaces calcOpticalFlowPyrLK with default parameters (win 21x21, maxLevel 3, 30 iterations,
  * eps 0.01, minEigThreshold 1e-4), FrameSourceWarp.cpp:252.  prev/next: device gray images of the
  * same size; prev_xy: n host (x,y) pairs; next_xy / status: host outputs (n pairs / n bytes).
@@ -556,8 +589,8 @@ VSTAB_API vstab_status vstab_pyr_lk(const void *prev, size_t pitch_prev, const v
 /* ---- Tracker options -----------------------------------------------------------------------------------------------------------------
  * calcOpticalFlowPyrLK's maxLevel, criteria (count and epsilon), minEigThreshold, flags and err: a restatement of OpenCV 4.5's CPU
  * LKTrackerInvoker in this library's arithmetic (exact integer sums converted once, the float operations in the documented order).  It
- * claims no bit equality with OpenCV.  winSize is 21 x 21 here; the other offered windows are "Tracker window" below (gradientSize other than
- * 3 is still not offered for the detector).
+ * claims no bit equality with OpenCV.  winSize is 21 x 21 here; the other offered windows are "Tracker window" below (the detector's gradientSize is
+ * "Corner gradient size" above).
  *   1. Levels.  The pyramid has min(levels of vstab_pyr_lk, max_level + 1) levels.  Everything else about a level is as in vstab_pyr_lk.
  *   2. Start of the top level.  With VSTAB_LK_USE_INITIAL_FLOW next_xy is also an input: the top level L starts the next-image estimate at
  *      next_xy[i] * (float)(1.0 / (1 << L)); without the flag at the scaled previous point.  The previous image's side -- the window, the
@@ -1158,6 +1191,14 @@ VSTAB_API vstab_status vstab_set_corner_response(vstab_handle *h, int response, 
  * "vstab_set_corner_block: null handle"; "vstab_set_corner_block: no detector runs on this handle (tracking = 0)";
  * "vstab_set_corner_block: the block size must be set before the first pull"; "vstab_set_corner_block: block_size is 3, 5 or 7". */
 VSTAB_API vstab_status vstab_set_corner_block(vstab_handle *h, int block_size);
+/* The corner gradient size of a handle ("Corner gradient size" above): every corner detection of the handle uses gradient_size (3, 5 or 7)
+ * as goodFeaturesToTrack's gradientSize, with any block size and response and with a detection mask or without, on pixel_depth 10 handles
+ * too.  Independent of vstab_set_corner_block, vstab_set_corner_response and vstab_set_detection_mask: the four may be called in any
+ * order.  Without this call, or with 3, the handle runs what it always ran.  Allowed before the first pull only.  Refused with
+ * VSTAB_ERR_INVALID, the handle unchanged, in this order: "vstab_set_corner_gradient: null handle"; "vstab_set_corner_gradient: no detector
+ * runs on this handle (tracking = 0)"; "vstab_set_corner_gradient: the gradient size must be set before the first pull";
+ * "vstab_set_corner_gradient: gradient_size is 3, 5 or 7". */
+VSTAB_API vstab_status vstab_set_corner_gradient(vstab_handle *h, int gradient_size);
 
 /* The handle's tracker options ("Tracker options" above, rules 1, 3 and 4): every tracker launch of the handle runs with them, and the
  * handle's pyramids have min(levels, max_level + 1) levels.  It takes no flags: err and the initial flow are stateless only

@@ -177,6 +177,16 @@ class FrameSourceWarp : public FrameSource {
         }
     }
 
+    // goodFeaturesToTrack's gradientSize for find_corners (FrameSourceWarp.cpp:228-240 passes none: 3): 3, 5 or 7; before the first
+    // pull_frame, in any order with set_corner_block, set_corner_response and set_detection_mask -- vstab_set_corner_gradient
+    void set_corner_gradient(int gradient_size = 3) {
+        const vstab_status st = vstab_set_corner_gradient(m_handle, gradient_size);
+        if (st != VSTAB_OK) {
+            std::fprintf(stderr, "FrameSourceWarp: %s\n", vstab_last_error());
+            throw (int)st;
+        }
+    }
+
     // calcOpticalFlowPyrLK's maxLevel, criteria (count, epsilon) and minEigThreshold for the tracking at FrameSourceWarp.cpp:252, which passes
     // none of them (3, 30, 0.01, 1e-4); before the first pull_frame -- vstab_set_tracker_options
     void set_tracker_options(int max_level = 3, int max_iter = 30, double eps = 0.01, double min_eig_threshold = 1e-4) {

@@ -1,5 +1,5 @@
 """Run the corner detectors at 4K and 1080p a few times (for rocprofv3 --kernel-trace --stats).
-usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overlay,roi}] [--harris [--k K]] [--alternations K] [--block B]
+usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overlay,roi}] [--harris [--k K]] [--alternations K] [--block B] [--gradient G]
    LIB: another build of the library (tools/devlib.py), for parent / branch runs
    --mask: K alternations of N unmasked detections (k_corners_fused) and N detections under the mask (k_corners_fused_masked,
            vstab_good_features_mask) per size, in one process: `full` is non-zero everywhere, `overlay` is zero on a box over 9 % of the frame
@@ -10,7 +10,9 @@ usage: detect_time.py [--lib LIB.so] [--n N] [--fused-only] [--mask {full,overla
    --block B: N one-pass detections and N dense maps with goodFeaturesToTrack's blockSize B per size (5, 7: vstab_good_features_block and
            vstab_min_eig_block, k_corners_fused_block<B> and k_corner_response_block<B>; 3: the entry points and kernels without a
            block, so that the figures of one session stand beside each other); with --harris the Harris response, with --mask under the mask.
-           One block size per run; a trace names the kernels with their size (k_corners_fused_block<5>), and so does tools/kernel_medians.py.
+           One block size per run; a trace names the kernels with their sizes (k_corners_fused_block<5, 3>), and so does tools/kernel_medians.py.
+   --gradient G: with --block B, goodFeaturesToTrack's gradientSize G beside it (5, 7: vstab_good_features_grad and vstab_min_eig_grad or
+           vstab_corner_harris_grad, k_corners_fused_block<B, G> and k_corner_response_block<B, G>; 3 or none: what --block B alone runs).
    tools/kernel_medians.py <dir> turns the kernel trace into medians per kernel and grid."""
 import argparse, hashlib, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -29,7 +31,11 @@ ap.add_argument("--harris", action="store_true")
 ap.add_argument("--k", type=float, default=0.04)
 ap.add_argument("--alternations", type=int, default=3)
 ap.add_argument("--block", type=int, default=None)
+ap.add_argument("--gradient", type=int, default=None)
 a = ap.parse_args()
+if a.gradient is not None and a.block is None:
+    ap.error("--gradient goes with --block")
+grad = a.gradient not in (None, 3)
 if a.lib:
     import devlib
     vs = devlib.load(a.lib)
@@ -55,7 +61,10 @@ for w, h in ((3840, 2160), (1920, 1080)):
         m = torch.from_numpy(make_mask(a.mask, w, h)).cuda() if a.mask else None
         info = {}
         for _ in range(a.n):
-            if a.block != 3:
+            if grad:
+                c = vs.good_features_grad(g, m, block_size=a.block, gradient_size=a.gradient, use_harris=a.harris, k=a.k, detector=vs.DETECTOR_FUSED, info=info)
+                e = vs.corner_harris_grad(g, a.block, a.gradient, a.k) if a.harris else vs.min_eig_grad(g, a.block, a.gradient)
+            elif a.block != 3:
                 c = vs.good_features_block(g, m, block_size=a.block, use_harris=a.harris, k=a.k, detector=vs.DETECTOR_FUSED, info=info)
                 e = vs.corner_harris_block(g, a.block, a.k) if a.harris else vs.min_eig_block(g, a.block)
             elif a.harris:
@@ -65,7 +74,7 @@ for w, h in ((3840, 2160), (1920, 1080)):
                 c = vs.good_features_mask(g, m, detector=vs.DETECTOR_FUSED, info=info)
                 e = vs.min_eig(g)
         torch.cuda.synchronize()
-        print(w, h, "block", a.block, "mask", a.mask, "harris k %g" % a.k if a.harris else "minimum eigenvalue", "detector", info["detector_used"], "corners", len(c),
+        print(w, h, "block", a.block, "gradient", a.gradient or 3, "mask", a.mask, "harris k %g" % a.k if a.harris else "minimum eigenvalue", "detector", info["detector_used"], "corners", len(c),
               hashlib.sha1(np.ascontiguousarray(c).tobytes()).hexdigest()[:12], "map", hashlib.sha1(e.cpu().numpy().tobytes()).hexdigest()[:12], flush=True)
         continue
     if a.harris:

@@ -214,6 +214,10 @@ SIGNATURES = {
     "vstab_corner_harris_block": (_i, [_vp, _sz, _i, _i, _i, _d, _vp, _vp]),
     "vstab_good_features_block": (_i, [_vp, _sz, _i, _i, _vp, _sz, _i, _d, _d, _i, _i, _d, _i, _fp, _ip, _ip, _vp]),
     "vstab_set_corner_block": (_i, [_vp, _i]),
+    "vstab_min_eig_grad": (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp]),
+    "vstab_corner_harris_grad": (_i, [_vp, _sz, _i, _i, _i, _i, _d, _vp, _vp]),
+    "vstab_good_features_grad": (_i, [_vp, _sz, _i, _i, _vp, _sz, _i, _d, _d, _i, _i, _i, _d, _i, _fp, _ip, _ip, _vp]),
+    "vstab_set_corner_gradient": (_i, [_vp, _i]),
     "vstab_set_tracker_options": (_i, [_vp, _i, _i, _d, _d]),
     "vstab_pyr_lk_win": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _i, _fp, _u8p, _fp, _i, _i, _d, _d, _i, _i, _vp]),
     "vstab_set_tracker_window": (_i, [_vp, _i]),
@@ -239,6 +243,8 @@ _L.vstabx_corners_fused_harris.restype = _i
 _L.vstabx_corners_fused_harris.argtypes = [_vp, _sz, _i, _i, _vp, _sz, _d, _d, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _ip, _vp]
 _L.vstabx_corners_fused_block.restype = _i
 _L.vstabx_corners_fused_block.argtypes = [_vp, _sz, _i, _i, _vp, _sz, _d, _d, _i, _i, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _ip, _vp]
+_L.vstabx_corners_fused_grad.restype = _i
+_L.vstabx_corners_fused_grad.argtypes = [_vp, _sz, _i, _i, _vp, _sz, _d, _d, _i, _i, _i, _c.c_uint, _c.c_uint, _c.POINTER(_u64), _c.POINTER(_c.c_uint), _c.POINTER(_c.c_uint), _ip, _vp]
 _L.vstabx_select_corners.restype = _i
 _L.vstabx_select_corners.argtypes = [_c.POINTER(_u64), _c.c_uint, _i, _i, _i, _d, _fp, _ip]
 _L.vstabx_detector_counters.restype = _i
@@ -979,6 +985,35 @@ def good_features_block(gray, mask=None, max_corners=200, quality=0.01, min_dist
                           _mask_args(mask) + (max_corners, quality, min_distance, int(block_size), int(use_harris), float(k), detector))
 
 
+def min_eig_grad(gray, block_size, gradient_size):
+    """vstab_min_eig_grad: cornerMinEigenVal(gray, block_size, gradient_size) as an (h, w) float32 device map, both sizes 3, 5 or 7
+    (include/vstab.h, "Corner gradient size"); with gradient_size 3 it is min_eig_block"""
+    import torch
+    h, w = gray.shape
+    out = torch.empty((h, w), dtype=torch.float32, device=gray.device)
+    _check(_L.vstab_min_eig_grad(gray.data_ptr(), gray.stride(0), w, h, int(block_size), int(gradient_size), out.data_ptr(), _stream()), "vstab_min_eig_grad")
+    return out
+
+
+def corner_harris_grad(gray, block_size, gradient_size, k=0.04):
+    """vstab_corner_harris_grad: cornerHarris(gray, block_size, gradient_size, k) as an (h, w) float32 device map; with gradient_size 3 it
+    is corner_harris_block"""
+    import torch
+    h, w = gray.shape
+    out = torch.empty((h, w), dtype=torch.float32, device=gray.device)
+    _check(_L.vstab_corner_harris_grad(gray.data_ptr(), gray.stride(0), w, h, int(block_size), int(gradient_size), float(k), out.data_ptr(), _stream()),
+           "vstab_corner_harris_grad")
+    return out
+
+
+def good_features_grad(gray, mask=None, max_corners=200, quality=0.01, min_distance=30.0, block_size=3, gradient_size=3, use_harris=False, k=0.04,
+                       detector=DETECTOR_AUTO, info=None):
+    """vstab_good_features_grad: goodFeaturesToTrack's ten-argument overload -- good_features_block with gradientSize (3, 5 or 7) behind
+    blockSize"""
+    return _good_features("vstab_good_features_grad", gray, max_corners, info,
+                          _mask_args(mask) + (max_corners, quality, min_distance, int(block_size), int(gradient_size), int(use_harris), float(k), detector))
+
+
 CORNERS_FUSED_FILL = 0xA5A5A5A5A5A5A5A5  # what vstabx_corners_fused fills its key buffer with before the kernels run
 
 
@@ -1030,6 +1065,16 @@ def corners_fused_block(gray, mask=None, block_size=3, response=CORNER_MIN_EIGEN
     mx = _c.c_int()
     out = _corners_fused("vstabx_corners_fused_block", gray, w, h, stream, cap, canary,
                          _mask_args(mask) + (float(quality), float(k), int(block_size), int(response)), (_c.byref(mx),))
+    return out + (mx.value,)
+
+
+def corners_fused_grad(gray, mask=None, block_size=3, gradient_size=3, response=CORNER_MIN_EIGENVAL, k=0.04, quality=0.01, cap=1 << 18, canary=64, w=None, h=None,
+                       stream=None):
+    """Test hook vstabx_corners_fused_grad: corners_fused_block with the gradient size (3, 5 or 7) behind the block size; the same five
+    outputs."""
+    mx = _c.c_int()
+    out = _corners_fused("vstabx_corners_fused_grad", gray, w, h, stream, cap, canary,
+                         _mask_args(mask) + (float(quality), float(k), int(block_size), int(gradient_size), int(response)), (_c.byref(mx),))
     return out + (mx.value,)
 
 
@@ -1229,11 +1274,12 @@ class Stabilizer:
 
     def __init__(self, frames, total=None, use_torch_stream=True, hold=12, bit_depth=8, readouts=None, ring_hold=None, border_mode=None, calibration=None,
                  calibration_ex=None, pinhole=None, detection_mask=None, corner_response=None, harris_k=0.04, tracker_options=None, tracker_window=None, corner_block=None,
-                 **cfg_kw):
+                 corner_gradient=None, **cfg_kw):
         """tracker_options: (max_level, max_iter, eps, min_eig) for set_tracker_options right after create.
         tracker_window: 15, 21 or 31 for set_tracker_window right after create.
         corner_response: set_corner_response(corner_response, harris_k) right after create (CORNER_HARRIS or CORNER_MIN_EIGENVAL).
         corner_block: 3, 5 or 7 for set_corner_block right after create.
+        corner_gradient: 3, 5 or 7 for set_corner_gradient right after create.
         detection_mask: set_detection_mask right after create (a device tensor or a numpy array of the luma plane's size).
         border_mode: vstab_set_border_mode_ex right after create (BORDER_* constants; None keeps the constant border).
         calibration: (K, D) for set_input_calibration right after create, applied after border_mode (K None keeps the camera from in_dfov).
@@ -1316,6 +1362,8 @@ class Stabilizer:
             self.set_tracker_window(tracker_window)
         if corner_block is not None:
             self.set_corner_block(corner_block)
+        if corner_gradient is not None:
+            self.set_corner_gradient(corner_gradient)
 
     def set_tracker_window(self, win_size):
         """vstab_set_tracker_window: calcOpticalFlowPyrLK's winSize (15, 21 or 31) for every tracker launch of this handle, before the first
@@ -1331,6 +1379,11 @@ class Stabilizer:
         """vstab_set_corner_block: goodFeaturesToTrack's blockSize (3, 5 or 7) for every detection of this handle, before the first pull; in
         any order with set_corner_response and set_detection_mask"""
         _check(_L.vstab_set_corner_block(self._h, int(block_size)), "vstab_set_corner_block")
+
+    def set_corner_gradient(self, gradient_size):
+        """vstab_set_corner_gradient: goodFeaturesToTrack's gradientSize (3, 5 or 7) for every detection of this handle, before the first
+        pull; in any order with set_corner_block, set_corner_response and set_detection_mask"""
+        _check(_L.vstab_set_corner_gradient(self._h, int(gradient_size)), "vstab_set_corner_gradient")
 
     def set_corner_response(self, response, k=0.04):
         """vstab_set_corner_response: CORNER_HARRIS with k (goodFeaturesToTrack's useHarrisDetector and k) for every detection of this

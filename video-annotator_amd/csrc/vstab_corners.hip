@@ -181,10 +181,11 @@ __global__ void __launch_bounds__(256) k_masked_max(const float *__restrict__ ei
 }
 
 // the dense response map (k_min_eig, or k_corner_harris with kf = (float)k) and *max_bits, its int-bit maximum
-// (block other than 3: the kernels of vstab_corners_block.hip)
-vstab_status launch_corner_response(const uint8_t *src, size_t pitch, int w, int h, bool harris, float kf, float *resp, int *max_bits, hipStream_t s, int block) {
+// (block or gradient other than 3: the kernels of vstab_corners_block.hip)
+vstab_status launch_corner_response(const uint8_t *src, size_t pitch, int w, int h, bool harris, float kf, float *resp, int *max_bits, hipStream_t s, int block,
+                                    int gradient) {
     VSTAB_HIP_TRY(hipMemsetAsync(max_bits, 0x80, sizeof(int), s));  // INT_MIN-ish (0x80808080): any value wins
-    if (block != 3) return launch_corner_response_block(src, pitch, w, h, block, harris, kf, resp, max_bits, s);
+    if (block != 3 || gradient != 3) return launch_corner_response_block(src, pitch, w, h, block, harris, kf, resp, max_bits, s, gradient);
     const int vec_ok = reinterpret_cast<uintptr_t>(src) % 4 == 0 && pitch % 4 == 0 && reinterpret_cast<uintptr_t>(resp) % 16 == 0;
     dim3 grid(div_up(w, ME_TW), div_up(h, ME_TH));
     if (harris) hipLaunchKernelGGL(k_corner_harris, grid, dim3(256), 0, s, src, pitch, w, h, resp, max_bits, vec_ok, kf);

@@ -340,7 +340,7 @@ __global__ void __launch_bounds__(256) k_filter_keys(const unsigned long long *_
 // Fused detector.  spec.mask (optional: (uint64_t)mask_pitch * h < 2^32): k_corners_fused_masked takes the place of k_corners_fused,
 // everything else is the same; spec.harris: the Harris response in place of the minimum eigenvalue, k_corners_fused_harris /
 // k_corners_fused_harris_masked -- words->max then says whether the frame has a positive response at all (no_positive_response);
-// spec.block other than 3: k_corners_fused_block of that size in their place.
+// spec.block or spec.gradient other than 3: k_corners_fused_block of that pair in their place.
 // scratch: corners_fused_scratch_bytes(w, h) (per tile: 256 key slots, a count, and room for a dense 64 x 31 map that only a tile with
 // more survivors than slots writes).  On return (stream order) keys holds min(words->kept, cap) keys; the result is complete iff
 // words->kept <= cap.
@@ -357,7 +357,7 @@ vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h
     float *spill = reinterpret_cast<float *>(base + lay.spill_off);
     unsigned int *tile_counts = reinterpret_cast<unsigned int *>(base + lay.counts_off);
     const dim3 grid(lay.tiles_x, lay.tiles_y);
-    if (spec.block != 3)  // one kernel per block size, mask and response as its arguments (vstab_corners_block.hip)
+    if (spec.block != 3 || spec.gradient != 3)  // one kernel per pair of sizes, mask and response as its arguments (vstab_corners_block.hip)
         VSTAB_TRY(launch_corners_fused_block(src, pitch, w, h, quality, &words->max, slots, tile_counts, spill, grid, s, spec, vec_ok, mvec_ok));
     else if (spec.harris && spec.mask)
         hipLaunchKernelGGL(k_corners_fused_harris_masked, grid, dim3(256), 0, s, src, pitch, w, h, quality, &words->max, slots, tile_counts, spill, vec_ok, spec.mask,

@@ -1,10 +1,12 @@
 // vstab_corners_tile.hpp -- what the one-pass corner detector does with a tile whatever the block size of its response: the geometry of the
 // source tile, its load (image and mask), the masked tile's early return, and everything behind the responses (tile maximum, lower bound of
-// the threshold, 3 x 3 maximum test, keys or a dense spill).  k_corners_fused and its siblings (vstab_corners_fused.hip, block 3) and
-// k_corners_fused_block / k_corner_response_block (vstab_corners_block.hip, blocks 5 and 7) are built from it; what they keep for themselves
-// is how the responses of a tile are formed.  The wave maximum also serves vstab_corners.hip.
+// the threshold, 3 x 3 maximum test, keys or a dense spill).  k_corners_fused and its siblings (vstab_corners_fused.hip, block 3 with
+// gradient 3) and k_corners_fused_block / k_corner_response_block (vstab_corners_block.hip, every other pair of block and gradient size)
+// are built from it; what they keep for themselves is how the responses of a tile are formed.  The wave maximum also serves
+// vstab_corners.hip.
 //
-// Every tile_ function is a template over the geometry G of the source tile and over a TAG that changes nothing in the function: it
+// Every tile_ function is a template over the geometry G of the source tile (a type; the gradient size is SourceTile's second argument)
+// and over a TAG that changes nothing in the function: it
 // gives the kernel that names it instantiations of its own.  An instantiation that two kernels of a unit inlined would be cloned where a
 // single kernel has it moved into its only caller, and the optimiser's choices behind that differ: with a tag per kernel the instructions of
 // k_corners_fused stay exactly what they were before it had siblings (k_corners_fused_masked, then the Harris pair; CfTag in
@@ -31,18 +33,21 @@ __device__ __forceinline__ int wave_max_i32(int best) {
     return max(best, __builtin_amdgcn_update_dpp(INT_MIN, best, 0x143, 0xc, 0xf, false));
 }
 
-// The source tile of a CF_TW x CF_TH = 64 x 31 tile whose responses sum a B x B block, r = (B - 1) / 2: the 66 x 33 responses around the
-// tile need products r further out and those one Sobel ring more, from a dword-aligned column: SW x SH bytes from image (oy - SY0, ox - SX0)
-// -- 72 x 39 from (oy - 4, ox - 4) for B = 5, 80 x 41 from (oy - 5, ox - 8) for B = 7.  A thread holds LOADS dwords of it, dword e <-> row
-// row(e), bytes 4 (e - row(e) SW / 4) ..; sel(rd) selects, of dword rd of a row, the bytes that belong to the 66 columns of the responses:
-// bytes SX0 - 1 .. SX0 + 64 of the row.
-template <int B>
+// The source tile of a CF_TW x CF_TH = 64 x 31 tile whose responses sum a B x B block of products of a G x G derivative, r = (B - 1) / 2 and
+// g = (G - 1) / 2: the 66 x 33 responses around the tile need products r further out and those a ring of g source pixels more, from a
+// dword-aligned column: SW x SH bytes from image (oy - SY0, ox - SX0).  (B, G) -> SW x SH from (oy - SY0, ox - SX0):
+//   (3, 3) 72 x 37 (3, 4)   (3, 5) 72 x 39 (4, 4)   (3, 7) 80 x 41 (5, 8)
+//   (5, 3) 72 x 39 (4, 4)   (5, 5) 80 x 41 (5, 8)   (5, 7) 80 x 43 (6, 8)
+//   (7, 3) 80 x 41 (5, 8)   (7, 5) 80 x 43 (6, 8)   (7, 7) 80 x 45 (7, 8)
+// A thread holds LOADS dwords of it, dword e <-> row row(e), bytes 4 (e - row(e) SW / 4) ..; sel(rd) selects, of dword rd of a row, the
+// bytes that belong to the 66 columns of the responses: bytes SX0 - 1 .. SX0 + 64 of the row.
+template <int B, int G = 3>
 struct SourceTile {
-    static constexpr int R = (B - 1) / 2;
-    static constexpr int SY0 = R + 2, SX0 = (R + 2 + 3) & ~3;
-    static constexpr int SW = (SX0 + CF_TW + R + 2 + 3) & ~3, SH = CF_TH + 2 + B - 1 + 2;
+    static constexpr int R = (B - 1) / 2, GR = (G - 1) / 2;
+    static constexpr int SY0 = R + 1 + GR, SX0 = (R + 1 + GR + 3) & ~3;
+    static constexpr int SW = (SX0 + CF_TW + R + 1 + GR + 3) & ~3, SH = CF_TH + 2 + B - 1 + 2 * GR;
     static constexpr int LOADS = (SH * (SW / 4) + 255) / 256;
-    static_assert(SX0 % 4 == 0 && SW % 4 == 0 && SX0 >= R + 2 && SW - SX0 >= CF_TW + R + 2, "the source tile is dword aligned and holds the ring");
+    static_assert(SX0 % 4 == 0 && SW % 4 == 0 && SX0 >= R + 1 + GR && SW - SX0 >= CF_TW + R + 1 + GR, "the source tile is dword aligned and holds the ring");
     static __device__ __forceinline__ int row(int e) { return e / (SW / 4); }
     static __device__ __forceinline__ uint32_t sel(int rd) {
         uint32_t s = 0;
@@ -52,6 +57,9 @@ struct SourceTile {
         return s;
     }
 };
+static_assert(SourceTile<5>::SW == 72 && SourceTile<5>::SH == 39 && SourceTile<5>::SY0 == 4 && SourceTile<5>::SX0 == 4, "gradient 3: the tile block 5 has always had");
+static_assert(SourceTile<7>::SW == 80 && SourceTile<7>::SH == 41 && SourceTile<7>::SY0 == 5 && SourceTile<7>::SX0 == 8, "gradient 3: the tile block 7 has always had");
+static_assert(SourceTile<7, 7>::SW == 80 && SourceTile<7, 7>::SH == 45, "the largest tile");
 // Block 3's, as k_corners_fused has always had it: 72 x 38 bytes from (oy - 3, ox - 4), one row more than the formula (37 are used); the
 // row of a dword as one 24-bit multiply and a shift (div_magic_ok); and of a row's 18 dwords the last byte of the first, the first byte of
 // the last, every byte of those between, said in that form: the generic loop costs both masked block-3 kernels 60 to 160 instructions.

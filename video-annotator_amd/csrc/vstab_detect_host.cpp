@@ -87,7 +87,7 @@ vstab_status Detector::good_features(const uint8_t *gray, size_t pitch, int max_
     float *eig = eig_out ? eig_out : eig_.as<float>();
     // the threshold of a masked detection comes from the maximum over the masked-in pixels, a word beside the frame's
     unsigned int DetectorWords::*const max_word = spec_.mask ? &DetectorWords::masked_max : &DetectorWords::max;
-    VSTAB_TRY(launch_corner_response(gray, pitch, w_, h_, spec_.harris, spec_.kf, eig, reinterpret_cast<int *>(&words->max), st, spec_.block));
+    VSTAB_TRY(launch_corner_response(gray, pitch, w_, h_, spec_.harris, spec_.kf, eig, reinterpret_cast<int *>(&words->max), st, spec_.block, spec_.gradient));
     if (spec_.mask) VSTAB_TRY(launch_masked_max(eig, w_, h_, spec_.mask, spec_.mask_pitch, reinterpret_cast<int *>(&words->masked_max), st));
     if (spec_.harris) {  // as above: the sign of the (masked) maximum, before a key buffer grows for candidates above a negative threshold
         VSTAB_TRY(read_words(st));

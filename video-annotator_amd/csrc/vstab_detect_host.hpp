@@ -23,14 +23,21 @@ inline vstab_status check_corner_block(const std::string &fn, int block) {
     return corner_block_offered(block) ? VSTAB_OK : fail(VSTAB_ERR_INVALID, fn + ": block_size is 3, 5 or 7");
 }
 
+// "<fn>: gradient_size is 3, 5 or 7" for a gradient size no kernel exists for
+inline vstab_status check_corner_gradient(const std::string &fn, int gradient) {
+    return corner_gradient_offered(gradient) ? VSTAB_OK : fail(VSTAB_ERR_INVALID, fn + ": gradient_size is 3, 5 or 7");
+}
+
 // The DetectSpec of an entry point's arguments (mask NULL: none; harris false: k is not looked at), or its refusal under the name fn:
-// the block, the mask's pitch, then its size, then k -- on the double, before it is narrowed.
-inline vstab_status check_detect_spec(const std::string &fn, const void *mask, size_t pitch_mask, bool harris, double k, int w, int h, DetectSpec &out, int block = 3) {
+// the block, the gradient, the mask's pitch, then its size, then k -- on the double, before it is narrowed.
+inline vstab_status check_detect_spec(const std::string &fn, const void *mask, size_t pitch_mask, bool harris, double k, int w, int h, DetectSpec &out, int block = 3,
+                                      int gradient = 3) {
     VSTAB_TRY(check_corner_block(fn, block));
+    VSTAB_TRY(check_corner_gradient(fn, gradient));
     if (mask && pitch_mask < (size_t)w) return fail(VSTAB_ERR_INVALID, fn + ": the mask's pitch is smaller than the image's width");
     if (mask && (uint64_t)pitch_mask * (uint64_t)h >= (1ull << 32)) return fail(VSTAB_ERR_INVALID, fn + ": mask planes of 4 GiB or more are not supported");
     if (harris && !harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, fn + ": k lies in [0, 0.25)");
-    out = DetectSpec(static_cast<const uint8_t *>(mask), pitch_mask, harris, (float)k, block);
+    out = DetectSpec(static_cast<const uint8_t *>(mask), pitch_mask, harris, (float)k, block, gradient);
     return VSTAB_OK;
 }
 
@@ -52,11 +59,13 @@ class Detector {
     //   set_response: under the Harris response a frame whose (masked) maximum is not positive has no corner, decided on the host from the
     //   sign of the maximum the kernels publish (no_positive_response).
     //   set_block: the window of the covariance sums; everything behind the response is the same for every size.
+    //   set_gradient: the Sobel aperture of the derivatives; everything behind the products is the same for every size.
     const DetectSpec &spec() const { return spec_; }
-    void set_mask(const uint8_t *mask, size_t pitch) { spec_ = DetectSpec(mask, pitch, spec_.harris, spec_.kf, spec_.block); }
+    void set_mask(const uint8_t *mask, size_t pitch) { spec_ = DetectSpec(mask, pitch, spec_.harris, spec_.kf, spec_.block, spec_.gradient); }
     vstab_status copy_mask(const void *mask, size_t pitch, bool host);
-    void set_response(bool harris, float kf) { spec_ = DetectSpec(spec_.mask, spec_.mask_pitch, harris, kf, spec_.block); }
+    void set_response(bool harris, float kf) { spec_ = DetectSpec(spec_.mask, spec_.mask_pitch, harris, kf, spec_.block, spec_.gradient); }
     void set_block(int block) { spec_.block = block; }  // 3, 5 or 7 (check_corner_block)
+    void set_gradient(int gradient) { spec_.gradient = gradient; }  // 3, 5 or 7 (check_corner_gradient)
 
     // Speculative detection: the same two kernels enqueued on another stream ahead of time (the counter
     // half of the key-frame rule is predictable), with the words and the first SPEC_CAP keys copied to

@@ -729,6 +729,17 @@ vstab_status vstab_set_corner_block(vstab_handle *h, int block_size) {
     return VSTAB_OK;
 }
 
+// The handle's corner gradient size (vstab.h, "Corner gradient size"): read by every detection of the handle, as the block size is (Detector::set_gradient).
+vstab_status vstab_set_corner_gradient(vstab_handle *h, int gradient_size) {
+    const std::string n = "vstab_set_corner_gradient: ";
+    if (!h) return fail(VSTAB_ERR_INVALID, n + "null handle");
+    if (!h->cfg.tracking) return fail(VSTAB_ERR_INVALID, n + "no detector runs on this handle (tracking = 0)");
+    if (h->pulled) return fail(VSTAB_ERR_INVALID, n + "the gradient size must be set before the first pull");
+    VSTAB_TRY(check_corner_gradient("vstab_set_corner_gradient", gradient_size));
+    h->detector.set_gradient(gradient_size);
+    return VSTAB_OK;
+}
+
 // The handle's tracker options: read by every tracker launch of the handle, and the pyramids are capped to max_level + 1 levels
 // (Tracker::set_options).  Before the first pull no pyramid has been built and no launch is in flight.
 vstab_status vstab_set_tracker_options(vstab_handle *h, int max_level, int max_iter, double eps, double min_eig_threshold) {

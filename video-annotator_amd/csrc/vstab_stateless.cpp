@@ -140,15 +140,18 @@ vstab_status vstab_pyr_down_x2(const void *src, size_t pitch_src, int width, int
     return launch_pyr_down_x2((const uint8_t *)src, pitch_src, width, height, (uint8_t *)mid, pitch_mid, (uint8_t *)dst, pitch_dst, static_cast<hipStream_t>(stream));
 }
 
-// the dense maps: vstab_min_eig, vstab_corner_harris (harris: k is checked, last) and their _block forms ("Corner block size" in vstab.h)
-static vstab_status corner_response_op(const char *fn, const void *gray, size_t pitch, int width, int height, int block, bool harris, double k, void *out, void *stream) {
+// the dense maps: vstab_min_eig, vstab_corner_harris (harris: k is checked, last) and their _block and _grad forms ("Corner block size" and
+// "Corner gradient size" in vstab.h)
+static vstab_status corner_response_op(const char *fn, const void *gray, size_t pitch, int width, int height, int block, bool harris, double k, void *out, void *stream,
+                                       int gradient = 3) {
     if (!gray || !out || width <= 0 || height <= 0 || pitch < (size_t)width) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": bad argument");
     VSTAB_TRY(check_corner_block(fn, block));
+    VSTAB_TRY(check_corner_gradient(fn, gradient));  // (the _grad forms only)
     if (harris && !harris_k_ok(k)) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": k lies in [0, 0.25)");
     DevBuf mb;
     VSTAB_TRY(mb.ensure(16));
     VSTAB_TRY(launch_corner_response((const uint8_t *)gray, pitch, width, height, harris, harris ? (float)k : 0.0f, (float *)out, mb.as<int>(),
-                                     static_cast<hipStream_t>(stream), block));
+                                     static_cast<hipStream_t>(stream), block, gradient));
     VSTAB_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return VSTAB_OK;
 }
@@ -170,26 +173,36 @@ vstab_status vstab_corner_harris_block(const void *gray, size_t pitch, int width
     return corner_response_op("vstab_corner_harris_block", gray, pitch, width, height, block_size, true, k, response, stream);
 }
 
+vstab_status vstab_min_eig_grad(const void *gray, size_t pitch, int width, int height, int block_size, int gradient_size, void *eig, void *stream) {
+    return corner_response_op("vstab_min_eig_grad", gray, pitch, width, height, block_size, false, 0.0, eig, stream, gradient_size);
+}
+
+vstab_status vstab_corner_harris_grad(const void *gray, size_t pitch, int width, int height, int block_size, int gradient_size, double k, void *response, void *stream) {
+    return corner_response_op("vstab_corner_harris_grad", gray, pitch, width, height, block_size, true, k, response, stream, gradient_size);
+}
+
 // vstab_good_features_ex (fn "vstab_good_features", no mask, VSTAB_DETECTOR_FUSED refused as ever), vstab_good_features_mask and
-// vstab_good_features_harris (harris: the Harris response with k, checked last); vstab_good_features_block: all of them in one call, with
-// the block size and use_harris as the caller gives them (use_harris -1: the caller has no such argument)
+// vstab_good_features_harris (harris: the Harris response with k, checked last); vstab_good_features_block and vstab_good_features_grad: all
+// of them in one call, with the block size, the gradient size and use_harris as the caller gives them
 static vstab_status good_features_op(const char *fn, bool fused_ok, const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask,
                                      int max_corners, double quality, double min_distance, int detector, float *xy, int *count, int *detector_used,
-                                     void *stream, bool harris = false, double k = 0.0, int block = 3) {
+                                     void *stream, bool harris = false, double k = 0.0, int block = 3, int gradient = 3) {
     if (!gray || !xy || !count || width < 3 || height < 3 || pitch < (size_t)width || max_corners <= 0 ||
         (detector != VSTAB_DETECTOR_AUTO && detector != VSTAB_DETECTOR_TWO_PASS && !(fused_ok && detector == VSTAB_DETECTOR_FUSED)))
         return fail(VSTAB_ERR_INVALID, std::string(fn) + ": bad argument");
-    VSTAB_TRY(check_corner_block(fn, block));  // (vstab_good_features_block only)
+    VSTAB_TRY(check_corner_block(fn, block));        // (vstab_good_features_block and _grad only)
+    VSTAB_TRY(check_corner_gradient(fn, gradient));  // (vstab_good_features_grad only)
     // goodFeaturesToTrack's own assertion (NaN fails both halves; quality = +inf passes and finds no corner)
     if (!(quality > 0.0) || !(min_distance >= 0.0)) return fail(VSTAB_ERR_INVALID, std::string(fn) + ": quality must be > 0 and min_distance >= 0");
     DetectSpec spec;
-    VSTAB_TRY(check_detect_spec(fn, mask, pitch_mask, harris, k, width, height, spec, block));
+    VSTAB_TRY(check_detect_spec(fn, mask, pitch_mask, harris, k, width, height, spec, block, gradient));
     Detector t;
     VSTAB_TRY(t.init(width, height));
     t.set_two_pass_detector(detector == VSTAB_DETECTOR_TWO_PASS);
     t.set_mask(spec.mask, spec.mask_pitch);
     t.set_response(spec.harris, spec.kf);
     t.set_block(spec.block);
+    t.set_gradient(spec.gradient);
     std::vector<float> out;
     VSTAB_TRY(t.good_features((const uint8_t *)gray, pitch, max_corners, quality, min_distance, out, static_cast<hipStream_t>(stream)));
     *count = (int)(out.size() / 2);
@@ -223,6 +236,15 @@ vstab_status vstab_good_features_block(const void *gray, size_t pitch, int width
     if (use_harris != 0 && use_harris != 1) return fail(VSTAB_ERR_INVALID, "vstab_good_features_block: bad argument");
     return good_features_op("vstab_good_features_block", true, gray, pitch, width, height, mask, pitch_mask, max_corners, quality, min_distance, detector, xy, count,
                             detector_used, stream, use_harris == 1, k, block_size);
+}
+
+// vstab.h, "Corner gradient size": goodFeaturesToTrack's ten-argument overload; with gradient_size 3 it is vstab_good_features_block
+vstab_status vstab_good_features_grad(const void *gray, size_t pitch, int width, int height, const void *mask, size_t pitch_mask, int max_corners, double quality,
+                                      double min_distance, int block_size, int gradient_size, int use_harris, double k, int detector, float *xy, int *count,
+                                      int *detector_used, void *stream) {
+    if (use_harris != 0 && use_harris != 1) return fail(VSTAB_ERR_INVALID, "vstab_good_features_grad: bad argument");
+    return good_features_op("vstab_good_features_grad", true, gray, pitch, width, height, mask, pitch_mask, max_corners, quality, min_distance, detector, xy, count,
+                            detector_used, stream, use_harris == 1, k, block_size, gradient_size);
 }
 
 vstab_status vstab_good_features(const void *gray, size_t pitch, int width, int height, int max_corners, double quality,

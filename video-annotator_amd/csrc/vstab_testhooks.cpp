@@ -181,7 +181,7 @@ __attribute__((visibility("default"))) int vstabx_lk_segments_win(const void *co
 // harris: the Harris response with k, checked last; max_out (optional) receives the frame maximum the kernels published, as int32 float bits
 static int corners_fused_hook(const std::string &fn, const void *gray, size_t pitch, int w, int h, const void *mask, size_t pitch_mask, bool masked, double quality,
                               unsigned int cap, unsigned int canary, unsigned long long *keys_out, unsigned int *counts_out, unsigned int *tile_counts,
-                              void *stream, bool harris = false, double k = 0.0, int *max_out = nullptr, int block = 3) {
+                              void *stream, bool harris = false, double k = 0.0, int *max_out = nullptr, int block = 3, int gradient = 3) {
     if (!gray || !keys_out || !counts_out || !tile_counts || (masked && !mask)) return fail(VSTAB_ERR_INVALID, fn + ": bad argument");
     if (w < 3 || h < 3 || pitch < (size_t)w) return fail(VSTAB_ERR_INVALID, fn + ": an image is at least 3 x 3 and its pitch at least its width");
     if ((uint64_t)pitch * (uint64_t)h >= (1ull << 32) || (uint64_t)w * (uint64_t)h >= (1ull << 31))
@@ -190,7 +190,7 @@ static int corners_fused_hook(const std::string &fn, const void *gray, size_t pi
     if (cap < 1 || cap > (1u << 24)) return fail(VSTAB_ERR_INVALID, fn + ": cap is 1 .. 2^24 keys");
     if (canary < 1 || canary > (1u << 16)) return fail(VSTAB_ERR_INVALID, fn + ": canary is 1 .. 2^16 keys");
     DetectSpec spec;
-    VSTAB_TRY(check_detect_spec(fn, masked ? mask : nullptr, pitch_mask, harris, k, w, h, spec, block));
+    VSTAB_TRY(check_detect_spec(fn, masked ? mask : nullptr, pitch_mask, harris, k, w, h, spec, block, gradient));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const CornersFusedScratch lay(w, h);  // the layout launch_corners_fused uses: the survivor counts are read back from it below
     const size_t scratch_bytes = lay.bytes;
@@ -256,6 +256,18 @@ __attribute__((visibility("default"))) int vstabx_corners_fused_block(const void
     if (response != VSTAB_CORNER_MIN_EIGENVAL && response != VSTAB_CORNER_HARRIS) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused_block: response is 0 or 1");
     return corners_fused_hook("vstabx_corners_fused_block", gray, pitch, w, h, mask, pitch_mask, mask != nullptr, quality, cap, canary, keys_out, counts_out, tile_counts,
                               stream, response == VSTAB_CORNER_HARRIS, k, max_bits_out, block);
+}
+// vstabx_corners_fused_block with the gradient size behind the block size (tests/test_corner_gradient_gpu.py, tests/corner_gradient_def.py):
+// k_corners_fused_block<block, gradient> or, with both 3, the kernel vstabx_corners_fused* runs for this mask and response; then
+// k_filter_keys.  The same outputs; the refusals of vstabx_corners_fused_block under this hook's name, with "gradient_size is 3, 5 or 7"
+// directly behind the block's.
+__attribute__((visibility("default"))) int vstabx_corners_fused_grad(const void *gray, size_t pitch, int w, int h, const void *mask, size_t pitch_mask, double quality,
+                                                                      double k, int block, int gradient, int response, unsigned int cap, unsigned int canary,
+                                                                      unsigned long long *keys_out, unsigned int *counts_out, unsigned int *tile_counts,
+                                                                      int *max_bits_out, void *stream) {
+    if (response != VSTAB_CORNER_MIN_EIGENVAL && response != VSTAB_CORNER_HARRIS) return fail(VSTAB_ERR_INVALID, "vstabx_corners_fused_grad: response is 0 or 1");
+    return corners_fused_hook("vstabx_corners_fused_grad", gray, pitch, w, h, mask, pitch_mask, mask != nullptr, quality, cap, canary, keys_out, counts_out, tile_counts,
+                              stream, response == VSTAB_CORNER_HARRIS, k, max_bits_out, block, gradient);
 }
 
 // The cost-weighted XCD bands of the fused warp (vstab_warp_bands.hpp; tests/test_band_schedule_cpu.py), no device needed.

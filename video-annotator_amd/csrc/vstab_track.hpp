@@ -46,15 +46,20 @@ vstab_status launch_pyr_down_x2(const uint8_t *src, size_t spitch, int sw, int s
 inline bool harris_k_ok(double k) { return k >= 0.0 && k < 0.25; }
 // 3, 5 or 7: the block sizes a kernel exists for (vstab.h, "Corner block size"; vstab_corners_block.hip holds the table)
 bool corner_block_offered(int block);
-// cornerMinEigenVal(block, 3) or, harris, cornerHarris(block, 3, k) with kf = (float)k as a dense w x h map, and its int-bit maximum; with
-// block 3 exactly the launches there were before there was a block
-vstab_status launch_corner_response(const uint8_t *src, size_t pitch, int w, int h, bool harris, float kf, float *resp, int *max_bits, hipStream_t s, int block = 3);
-vstab_status launch_corner_response_block(const uint8_t *src, size_t pitch, int w, int h, int block, bool harris, float kf, float *resp, int *max_bits, hipStream_t s);
+// 3, 5 or 7: the gradient sizes a kernel exists for, with every block size (vstab.h, "Corner gradient size")
+bool corner_gradient_offered(int gradient);
+// cornerMinEigenVal(block, gradient) or, harris, cornerHarris(block, gradient, k) with kf = (float)k as a dense w x h map, and its int-bit
+// maximum; with block 3 and gradient 3 exactly the launches there were before there was a block
+vstab_status launch_corner_response(const uint8_t *src, size_t pitch, int w, int h, bool harris, float kf, float *resp, int *max_bits, hipStream_t s, int block = 3,
+                                    int gradient = 3);
+vstab_status launch_corner_response_block(const uint8_t *src, size_t pitch, int w, int h, int block, bool harris, float kf, float *resp, int *max_bits, hipStream_t s,
+                                          int gradient = 3);
 // What a detection reads beside the image (vstab.h, "Detection mask" and "Harris response"), as every launcher and the Detector take it:
 //   mask    the detection mask, a w x h plane of bytes of pitch mask_pitch, non-zero = "a corner may be reported here"; NULL: none, the
 //           launches of the unmasked detector
 //   harris  cornerHarris(block, 3, k) with kf = (float)k in place of cornerMinEigenVal(block, 3) (kf is not looked at then)
 //   block   goodFeaturesToTrack's blockSize, 3, 5 or 7: the window of the covariance sums; 3 makes the launches of a spec without one
+//   gradient  goodFeaturesToTrack's gradientSize, 3, 5 or 7: the Sobel aperture of the derivatives; 3 makes the launches of a spec without one
 // check_detect_spec (vstab_detect_host.hpp) is where the entry points refuse a bad one.
 struct DetectSpec {
     const uint8_t *mask = nullptr;
@@ -62,8 +67,10 @@ struct DetectSpec {
     bool harris = false;
     float kf = 0.0f;
     int block = 3;
+    int gradient = 3;
     DetectSpec() = default;
-    DetectSpec(const uint8_t *m, size_t pitch, bool h = false, float k = 0.0f, int b = 3) : mask(m), mask_pitch(m ? pitch : 0), harris(h), kf(h ? k : 0.0f), block(b) {}
+    DetectSpec(const uint8_t *m, size_t pitch, bool h = false, float k = 0.0f, int b = 3, int g = 3)
+        : mask(m), mask_pitch(m ? pitch : 0), harris(h), kf(h ? k : 0.0f), block(b), gradient(g) {}
 };
 // The detectors' 8 dwords of device memory (the fused launch zeroes all of them):
 struct DetectorWords {
@@ -96,7 +103,7 @@ struct CornersFusedScratch {
 size_t corners_fused_scratch_bytes(int w, int h);
 vstab_status launch_corners_fused(const uint8_t *src, size_t pitch, int w, int h, double quality, void *scratch, unsigned long long *keys,
                                   unsigned int cap, DetectorWords *words, hipStream_t s, const DetectSpec &spec = DetectSpec());
-// launch_corners_fused's first kernel for spec.block other than 3 (vstab_corners_block.hip), into the same scratch; vec_ok, mvec_ok: the
+// launch_corners_fused's first kernel for a (spec.block, spec.gradient) other than (3, 3) (vstab_corners_block.hip), into the same scratch; vec_ok, mvec_ok: the
 // image's and the mask's base and pitch are 4-byte aligned, as launch_corners_fused found them
 vstab_status launch_corners_fused_block(const uint8_t *src, size_t pitch, int w, int h, double quality, unsigned int *max_key, unsigned long long *slots,
                                         unsigned int *tile_counts, float *spill, dim3 grid, hipStream_t s, const DetectSpec &spec, int vec_ok, int mvec_ok);
