@@ -1,4 +1,4 @@
-"""Generates tests/golden/corner_block_kat.npz, the known-answer vectors of the corner block size (tests/corner_block_def.py; include/vstab.h
+"""Generates tests/golden/corner_block_kat.npz, the known-answer vectors of the corner block size (tests/corner_def.py; include/vstab.h
 "Corner block size"): python tests/golden/make_corner_block_golden.py
 
 The frames are small: a 4 x 5 cut (several folds of the border), synth.luma(13) at 40 x 24, the 2-px checkerboard at 33 x 20 and the
@@ -20,7 +20,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
-import corner_block_def as D  # noqa: E402
+import corner_def as D  # noqa: E402
 import corner_tiles as C  # noqa: E402
 import mask_def as M  # noqa: E402
 import synth  # noqa: E402
@@ -37,7 +37,7 @@ def answers(g, block):
     mc, q, md = PARAMS
     mask = M.checkerboard(*g.shape, 3, 5)
     return {"min_eig": D.min_eig(g, block), "harris": D.corner_harris(g, block),
-            "corners": D.good_features(g, None, mc, q, md, block), "corners_harris": D.good_features(g, None, mc, q, md, block, True),
+            "corners": D.good_features(g, None, mc, q, md, block), "corners_harris": D.good_features(g, None, mc, q, md, block, harris=True),
             "corners_masked": D.good_features(g, mask, mc, q, md, block)}
 
 

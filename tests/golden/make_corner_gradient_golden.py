@@ -1,7 +1,7 @@
-"""Generates tests/golden/corner_gradient_kat.npz, the known-answer vectors of the corner gradient size (tests/corner_gradient_def.py;
+"""Generates tests/golden/corner_gradient_kat.npz, the known-answer vectors of the corner gradient size (tests/corner_def.py;
 include/vstab.h "Corner gradient size"): python tests/golden/make_corner_gradient_golden.py
 
-One frame, the 66 x 33 cut of synth.luma(13) (corner_gradient_def.dense_frames' "66x33"), and per pair (B, G) of the six that no "Corner block
+One frame, the 66 x 33 cut of synth.luma(13) (corner_def.dense_frames' "66x33"), and per pair (B, G) of the six that no "Corner block
 size" call serves -- G in (5, 7), B in (3, 5, 7):
 
   gray                              the frame
@@ -17,7 +17,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
-import corner_gradient_def as D  # noqa: E402
+import corner_def as D  # noqa: E402
 
 
 def gray():

@@ -1,11 +1,11 @@
-"""Generates tests/golden/lk_options_kat.npz, the known-answer vectors of the tracker's options (tests/lk_options_def.py; include/vstab.h
+"""Generates tests/golden/lk_options_kat.npz, the known-answer vectors of the tracker's options (tests/lk_def.py at window 21; include/vstab.h
 "Tracker options"): python tests/golden/make_lk_options_golden.py
 
-The frames are lk_edges.frames(130, 80) (two levels) and lk_options_def.moved_pair(240, 144) (three levels, a 9-pixel motion); the points a
-few dozen of lk_options_def.points.  Per case <name>:
+The frames are lk_edges.frames(130, 80) (two levels) and lk_def.moved_pair(240, 144) (three levels, a 9-pixel motion); the points a
+few dozen of lk_def.points.  Per case <name>:
 
   <name>_pts, <name>_guess   the start points and (initial-flow cases) the guesses
-  <name>_xy, _status, _err, _min_eig, _iterations   what lk_options_def.track answers
+  <name>_xy, _status, _err, _min_eig, _iterations   what lk_def.track answers
 
 Fixtures are data only: inputs and expected outputs.  Their purpose is that an edit of the definition shows.
 """
@@ -17,7 +17,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
-import lk_options_def as D  # noqa: E402
+import lk_def as D  # noqa: E402
 
 KEYS = ("xy", "status", "err", "min_eig", "iterations")
 

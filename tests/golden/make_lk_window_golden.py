@@ -1,11 +1,11 @@
-"""Generates tests/golden/lk_window_kat.npz, the known-answer vectors of the tracker's window (tests/lk_window_def.py; include/vstab.h
+"""Generates tests/golden/lk_window_kat.npz, the known-answer vectors of the tracker's window (tests/lk_def.py; include/vstab.h
 "Tracker window"): python tests/golden/make_lk_window_golden.py
 
-The frames are lk_edges.frames(130, 80) (three levels at 15, two at 31), lk_options_def.moved_pair(240, 144) (a 9-pixel motion) and
-lk_edges.frames(24, 20) (smaller than the 31-pixel window: several folds); the points a few dozen of lk_window_def.points.  Per case <name>:
+The frames are lk_edges.frames(130, 80) (three levels at 15, two at 31), lk_def.moved_pair(240, 144) (a 9-pixel motion) and
+lk_edges.frames(24, 20) (smaller than the 31-pixel window: several folds); the points a few dozen of lk_def.window_points.  Per case <name>:
 
   <name>_pts, <name>_guess   the start points and (initial-flow cases) the guesses
-  <name>_xy, _status, _err, _min_eig, _iterations   what lk_window_def.track answers
+  <name>_xy, _status, _err, _min_eig, _iterations   what lk_def.track answers
 
 Fixtures are data only: inputs and expected outputs.  Their purpose is that an edit of the definition shows.
 """
@@ -17,8 +17,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
-import lk_options_def as D  # noqa: E402
-import lk_window_def as W  # noqa: E402
+import lk_def as W  # noqa: E402
 
 KEYS = ("xy", "status", "err", "min_eig", "iterations")
 
@@ -26,15 +25,15 @@ KEYS = ("xy", "status", "err", "min_eig", "iterations")
 def cases():
     """name -> (prev, next, pts, window, options, guess)"""
     out = {}
-    a, b, c = D.pair(130, 80), D.moved_pair(240, 144), D.pair(24, 20)
+    a, b, c = W.pair(130, 80), W.moved_pair(240, 144), W.pair(24, 20)
     rng = np.random.default_rng(20261020)
     for win in W.NEW_WINDOWS:
-        pa, pb = W.points(130, 80, win)[::3], W.points(240, 144, win)[::4]
+        pa, pb = W.window_points(130, 80, win)[::3], W.window_points(240, 144, win)[::4]
         out["default_130_w%d" % win] = (*a, pa, win, {}, None)
         out["guess_130_w%d" % win] = (*a, pa, win, dict(max_iter=6), (pa + np.float32([1.3, -0.7]) + rng.uniform(-3, 3, pa.shape)).astype(np.float32))
         out["default_240_w%d" % win] = (*b, pb, win, {}, None)
         out["options_240_w%d" % win] = (*b, pb, win, dict(max_level=1, max_iter=5, eps=0.1, min_eig=1e-3), None)
-    out["folds_24_w31"] = (*c, W.points(24, 20, 31)[::2], 31, {}, None)
+    out["folds_24_w31"] = (*c, W.window_points(24, 20, 31)[::2], 31, {}, None)
     return out
 
 

@@ -17,13 +17,14 @@ Non-finite and huge points (SPECIALS): the reference's float-to-int conversion g
 so no level is tracked: status 0 and the point back as it came.  -0.0 and the smallest denormal are ordinary points."""
 import numpy as np
 
+import lk_def as L
 import lk_segments as S
 import oracle
 import synth
+from lk_def import FLT_EPSILON, pyramid  # noqa: F401  (pyramid(img): the levels of buildOpticalFlowPyramid at window 21)
 
 LKW = S.LKW
 HALF = S.HALF
-FLT_EPSILON = np.float32(1.1920928955078125e-7)
 
 # (w, h): 4, 4, 3, 2 and 1 levels; both sides of each level-count threshold of the shorter side (42|43, 84|85, 168|169) on each axis
 # against a long side of 200; frames smaller than the 21-pixel window (every tap reflected, several folds), and 21 / 22
@@ -61,63 +62,73 @@ def frames(w, h, n=3):
     return [np.ascontiguousarray(f, np.uint8) for f in out]
 
 
-def origins(c, l):
-    """window origin of float32 coordinates c at level l, as lk_segments.fetch_ahead computes it: floor(c * 2^-l - 10) in float32, int64
-    (finite coordinates inside int only)"""
-    return S._floor_i(np.asarray(c, np.float32) * np.float32(2.0 ** -l) - HALF)
+def origins(c, l, W=21):
+    """window origin of float32 coordinates c at level l, as lk_segments.fetch_ahead computes it: floor(c * 2^-l - half(W)) in float32,
+    int64 (finite coordinates inside int only)"""
+    return S._floor_i(np.asarray(c, np.float32) * np.float32(2.0 ** -l) - L.half(W))
 
 
-def tracked(pts, w, h):
+def tracked(pts, w, h, W=21):
     """(n, nl) bool: level l of start point i passes the range test.  A non-finite coordinate, or one whose origin lies outside int,
     passes at no level (the reference's conversion gives INT_MIN for it)."""
     pts = np.asarray(pts, np.float32).reshape(-1, 2)
-    nl, sizes = S.level_sizes(w, h)
+    nl, sizes = S.level_sizes(w, h, W)
     out = np.zeros((pts.shape[0], nl), bool)
     for l in range(nl):
         with np.errstate(invalid="ignore", over="ignore"):
-            q = pts * np.float32(2.0 ** -l) - HALF
+            q = pts * np.float32(2.0 ** -l) - L.half(W)
         ok = np.isfinite(q).all(1) & (np.abs(q) < 2.0 ** 31).all(1)
         ip = S._floor_i(np.where(ok[:, None], q, 0))
         wl, hl = sizes[l]
-        out[:, l] = ok & (ip[:, 0] >= -LKW) & (ip[:, 0] < wl) & (ip[:, 1] >= -LKW) & (ip[:, 1] < hl)
+        out[:, l] = ok & (ip[:, 0] >= -W) & (ip[:, 0] < wl) & (ip[:, 1] >= -W) & (ip[:, 1] < hl)
     return out
 
 
-def boundary_pair(l, b):
+def boundary_pair(l, b, W=21):
     """-> (below, at): `at` is the smallest float32 whose level-l origin is >= b, `below` its float32 neighbour towards -inf (origin
-    b - 1): walked over the float32 expression, starting from the real-number answer (b + 10) * 2^l."""
-    x = np.float32((b + 10) * 2.0 ** l)
+    b - 1): walked over the float32 expression, starting from the real-number answer (b + (W - 1) / 2) * 2^l."""
+    x = np.float32((b + (W - 1) // 2) * 2.0 ** l)
     lo = np.float32(-np.inf)
-    while origins(x, l) < b:
+    while origins(x, l, W) < b:
         x = np.nextafter(x, np.float32(np.inf), dtype=np.float32)
-    while origins(np.nextafter(x, lo, dtype=np.float32), l) >= b:
+    while origins(np.nextafter(x, lo, dtype=np.float32), l, W) >= b:
         x = np.nextafter(x, lo, dtype=np.float32)
     below = np.nextafter(x, lo, dtype=np.float32)
-    assert origins(x, l) == b and origins(below, l) == b - 1, (l, b, x, below)
+    assert origins(x, l, W) == b and origins(below, l, W) == b - 1, (l, b, x, below)
     return below, x
 
 
-def edge_values(l, n_l):
+def edge_values(l, n_l, W=21):
     """the four float32 coordinates around the two boundaries of an axis of n_l pixels at level l:
     {("lo", "out"), ("lo", "in"), ("hi", "in"), ("hi", "out")}: value"""
-    lo_out, lo_in = boundary_pair(l, -LKW)
-    hi_in, hi_out = boundary_pair(l, n_l)
+    lo_out, lo_in = boundary_pair(l, -W, W)
+    hi_in, hi_out = boundary_pair(l, n_l, W)
     return {("lo", "out"): lo_out, ("lo", "in"): lo_in, ("hi", "in"): hi_in, ("hi", "out"): hi_out}
 
 
-def boundary_cases(w, h):
-    """-> (pts (n, 2) float32, tags): tags[i] is ("edge", level, axis, side, "in" | "out") -- axis 0 = x, 1 = y; the other coordinate is the
-    frame's centre --, ("corner", (level_x, side_x, io_x), (level_y, side_y, io_y)) or ("plain",)."""
-    nl, sizes = S.level_sizes(w, h)
+def edge_cases(w, h, W=21):
+    """-> (pts, tags): for every level the window's pyramid has and each axis, the four float32 coordinates around -W (origin -W - 1 | -W)
+    and n_l (origin n_l - 1 | n_l), the other coordinate at the frame's centre; tags[i] = (level, axis, "lo" | "hi", "in" | "out")"""
+    nl, sizes = S.level_sizes(w, h, W)
     centre = (np.float32(w * 0.5 + 0.25), np.float32(h * 0.5 - 0.25))
-    vals = [[edge_values(l, sizes[l][axis]) for l in range(nl)] for axis in (0, 1)]
     pts, tags = [], []
     for l in range(nl):
         for axis in (0, 1):
-            for (side, io), v in vals[axis][l].items():
+            for (side, io), v in edge_values(l, sizes[l][axis], W).items():
                 p = list(centre)
                 p[axis] = v
-                pts.append(p), tags.append(("edge", l, axis, side, io))
+                pts.append(p), tags.append((l, axis, side, io))
+    return np.asarray(pts, np.float32), tags
+
+
+def boundary_cases(w, h, W=21):
+    """-> (pts (n, 2) float32, tags): edge_cases, tagged ("edge", level, axis, side, "in" | "out") -- axis 0 = x, 1 = y; the other
+    coordinate is the frame's centre --, then ("corner", (level_x, side_x, io_x), (level_y, side_y, io_y)) and ("plain",)."""
+    nl, sizes = S.level_sizes(w, h, W)
+    centre = (np.float32(w * 0.5 + 0.25), np.float32(h * 0.5 - 0.25))
+    vals = [[edge_values(l, sizes[l][axis], W) for l in range(nl)] for axis in (0, 1)]
+    edges, edge_tags = edge_cases(w, h, W)
+    pts, tags = edges.tolist(), [("edge",) + t for t in edge_tags]
     # corners: x on a boundary of level a, y on one of level b -- the finest with the coarsest, both ways, and the coarsest with itself
     for a, b in sorted({(0, nl - 1), (nl - 1, 0), (nl - 1, nl - 1)}):
         for sx in ("lo", "hi"):
@@ -138,17 +149,6 @@ def pattern(row):
         if not row[:L].any() and row[L:].all():
             return L
     return None
-
-
-def pyramid(img):
-    """the levels of buildOpticalFlowPyramid: oracle.pyr_down chained over lk_segments.level_sizes"""
-    h, w = img.shape
-    nl, sizes = S.level_sizes(w, h)
-    out = [np.ascontiguousarray(img, np.uint8)]
-    for l in range(1, nl):
-        out.append(oracle.pyr_down(out[-1]))
-        assert out[-1].shape == (sizes[l][1], sizes[l][0])
-    return out
 
 
 def matrix_rejected(prev, pts):

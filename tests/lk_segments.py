@@ -23,29 +23,23 @@ float32 values: the oracle's per-level estimates are bit for bit the kernel's (t
 A slot that reached pair fi + 1 survived pair fi, whose level-0 final-position test is the level-0 range test of pair fi + 1: at fi > 0
 level 0 is never skipped, and no coarser level either (floor(x / 2^l - 10) stays inside [-21, w_l) when floor(x - 10) does), so
 `skipped` is reached only by start points of a launch's first pair."""
+import functools
+
 import numpy as np
 
+import lk_def as L
 import oracle
+from lk_def import _floor_i, level_sizes  # noqa: F401  (level_sizes(w, h, W=21): the pyramid's sizes, defined once)
 
-LKW, LKR, LKJR, LKJM, SLACK = 21, 24, 32, 5, 4
+LKW, LKR, LKJR, LKJM, SLACK = 21, 24, 32, 5, 4      # lk_def.geometry(21), by hand
 NONE = None
 HALF = np.float32(10.0)
 CATS = ("served", "missed", "not_fetched", "skipped")
 
 
-def level_sizes(w, h):
-    """(levels, [(w_l, h_l)]) of buildOpticalFlowPyramid with maxLevel 3, winSize 21."""
-    sizes = [(w, h)]
-    for _ in range(3):
-        w, h = (w + 1) // 2, (h + 1) // 2
-        if w <= LKW or h <= LKW:
-            break
-        sizes.append((w, h))
-    return len(sizes), sizes
-
-
-def expected(frames, pts, segs, bad_parent=-1):
-    """frames: K + 1 (h, w) uint8; pts (n, 2); segs: launch lengths (sum K).  -> dict with, per pair k (axis 0) and slot (axis 1):
+def expected(frames, pts, segs, bad_parent=-1, W=None):
+    """frames: K + 1 (h, w) uint8; pts (n, 2); segs: launch lengths (sum K); W: None chains oracle.pyr_lk_trace (window 21), a window
+    chains the definition lk_def.track(..., W) in its place.  -> dict with, per pair k (axis 0) and slot (axis 1):
     status (K, n) uint8, xy (K, n, 2) float32 (the record's x, y), start (K, n, 2) float32 (the pair's start point; NaN where the
     slot is not tracked), levels (K, n, 4, 2) float32 (oracle per-level estimates; NaN where not tracked), fi (K,) index of the pair in
     its launch, launch (K,) index of the launch, nl (pyramid levels)."""
@@ -60,7 +54,7 @@ def expected(frames, pts, segs, bad_parent=-1):
     cur = pts.copy()
     alive = np.ones(n, bool)      # tracked into the next pair
     chain3 = False                # a launch with a wrong parent tag (and every launch behind it): status 3
-    nl = level_sizes(frames[0].shape[1], frames[0].shape[0])[0]
+    nl = level_sizes(frames[0].shape[1], frames[0].shape[0], 21 if W is None else W)[0]
     for k in range(K):
         if fi[k] == 0 and launch[k] == bad_parent:
             chain3 = True
@@ -70,7 +64,11 @@ def expected(frames, pts, segs, bad_parent=-1):
         status[k] = np.where(alive, 0, 2)
         idx = np.flatnonzero(alive)
         if idx.size:
-            nxt, st, lvl, nl = oracle.pyr_lk_trace(frames[k], frames[k + 1], cur[idx])
+            if W is None:
+                nxt, st, lvl, nl = oracle.pyr_lk_trace(frames[k], frames[k + 1], cur[idx])
+            else:
+                r = L.track(frames[k], frames[k + 1], cur[idx], W)
+                nxt, st, lvl = r["xy"], r["status"], r["levels"]
             start[k, idx] = cur[idx]
             lv[k, idx] = lvl
             status[k, idx] = st
@@ -80,26 +78,26 @@ def expected(frames, pts, segs, bad_parent=-1):
     return {"status": status, "xy": xy, "start": start, "levels": lv, "fi": fi, "launch": launch, "nl": nl}
 
 
-def _floor_i(v):
-    return np.floor(v).astype(np.int64)
-
-
-def _ahead_origin(c, size, off):
+def _ahead_origin(c, size, off, W=21):
     """the kernel's range test and interior test of a block fetched ahead: c = (cx, cy) float32 positions (window corner at the level),
     off = the block's margin (1 + SLACK for a neighbourhood, LKJM for the top block) -> (ox, oy) int64, valid bool."""
     w, h = size
+    jr = L.geometry(W)["LKJR"]
     cx, cy = c[..., 0], c[..., 1]
-    ok = (cx > np.float32(-(LKW + 1))) & (cx < np.float32(w)) & (cy > np.float32(-(LKW + 1))) & (cy < np.float32(h))
+    ok = (cx > np.float32(-(W + 1))) & (cx < np.float32(w)) & (cy > np.float32(-(W + 1))) & (cy < np.float32(h))
     with np.errstate(invalid="ignore"):
         ox, oy = _floor_i(np.where(ok, cx, 0)) - off, _floor_i(np.where(ok, cy, 0)) - off
-    ok &= (ox >= 0) & (oy >= 0) & (ox + LKJR <= w) & (oy + LKJR <= h)
+    ok &= (ox >= 0) & (oy >= 0) & (ox + jr <= w) & (oy + jr <= h)
     return ox, oy, ok
 
 
-def fetch_ahead(exp, w, h):
+def fetch_ahead(exp, w, h, W=21):
     """-> (neigh, top): neigh (K, n, 4) object array of CATS (None: the slot is not tracked in that pair, or the level is absent),
-    top (K, n) the same for the top level's next-image block."""
-    nl, sizes = level_sizes(w, h)
+    top (K, n) the same for the top level's next-image block.  For a window W the module docstring's numbers become lk_def.geometry(W)'s:
+    half(W) for 10, LKJR for 32, 1 + SLACK and LKJM for the margins, 2 SLACK for 8, LKT + 2 for 24."""
+    G = L.geometry(W)
+    HALF, SLACK, LKJM, LKJR, LKT = L.half(W), G["SLACK"], G["LKJM"], G["LKJR"], G["LKT"]
+    nl, sizes = level_sizes(w, h, W)
     K, n = exp["status"].shape
     neigh = np.full((K, n, 4), None, object)
     top = np.full((K, n), None, object)
@@ -118,11 +116,11 @@ def fetch_ahead(exp, w, h):
             ls = np.float32(2.0 ** -l)
             ip = _floor_i(np.where(tracked[:, None], pp, 0) * ls - HALF)
             wl, hl = sizes[l]
-            skipped = (ip[:, 0] < -LKW) | (ip[:, 0] >= wl) | (ip[:, 1] < -LKW) | (ip[:, 1] >= hl)
+            skipped = (ip[:, 0] < -W) | (ip[:, 0] >= wl) | (ip[:, 1] < -W) | (ip[:, 1] >= hl)
             cat = np.full(n, "not_fetched", object)
             if have_prev:
                 with np.errstate(invalid="ignore"):
-                    ox, oy, ok = _ahead_origin(np.where(np.isnan(e0), 0, e0) * ls - HALF, sizes[l], 1 + SLACK)
+                    ox, oy, ok = _ahead_origin(np.where(np.isnan(e0), 0, e0) * ls - HALF, sizes[l], 1 + SLACK, W)
                 dx, dy = ip[:, 0] - 1 - ox, ip[:, 1] - 1 - oy
                 hit = ok & (dx >= 0) & (dx <= 2 * SLACK) & (dy >= 0) & (dy <= 2 * SLACK)
                 cat = np.where(ok, np.where(hit, "served", "missed"), "not_fetched")
@@ -132,8 +130,8 @@ def fetch_ahead(exp, w, h):
                 tc = np.full(n, "not_fetched", object)
                 if have_prev:
                     with np.errstate(invalid="ignore"):
-                        bx, by, ok = _ahead_origin(np.where(np.isnan(p0), 0, p0) * ls - HALF, sizes[l], LKJM)
-                    hit = ok & (ip[:, 0] - 2 >= bx) & (ip[:, 1] - 2 >= by) & (ip[:, 0] + LKW + 3 <= bx + LKJR) & (ip[:, 1] + LKW + 3 <= by + LKJR)
+                        bx, by, ok = _ahead_origin(np.where(np.isnan(p0), 0, p0) * ls - HALF, sizes[l], LKJM, W)
+                    hit = ok & (ip[:, 0] - 2 >= bx) & (ip[:, 1] - 2 >= by) & (ip[:, 0] + LKT + 2 <= bx + LKJR) & (ip[:, 1] + LKT + 2 <= by + LKJR)
                     tc = np.where(ok, np.where(hit, "served", "missed"), "not_fetched")
                 tc = np.where(skipped, "skipped", tc)
                 top[k, tracked] = tc[tracked]
@@ -262,3 +260,17 @@ def make_set(name, n=None):
         if name == "steady_640":
             pts[-3:] = [(-120.0, 50.0), (700.0, -130.0), (320.0, 480.0)]
     return frames, np.asarray(pts, np.float32), off
+
+
+# the clips the window's segment tests run on: the steady and the jump clip, and the coarse-blind one -- the only one on which level 0
+# carries a feature further than the slack, i.e. a neighbourhood fetched ahead is `missed` (test_lk_window_cpu.py asserts the reach)
+SEGMENT_CLIPS = ("steady_640", "jump_640", "blind_640")
+SEGMENT_POINTS = 100
+SEGMENTATIONS = ((8,), (3, 3, 2))
+
+
+@functools.lru_cache(maxsize=None)
+def segment_case(name, W):
+    """-> (frames, pts, {segs: expected dict}) of a segment clip at window W, computed once per process (the definition is slow)"""
+    frames, pts, _ = make_set(name, n=SEGMENT_POINTS)
+    return frames, pts, {segs: expected(frames, pts, segs, W=W) for segs in SEGMENTATIONS}

@@ -1,19 +1,7 @@
-"""The detection mask (include/vstab.h, "Detection mask") restated in numpy on top of oracle.min_eig: OpenCV 4.5's
-goodFeaturesToTrack(gray, corners, max_corners, quality, min_distance, mask, 3, false, 0.04) on its CPU path, and the one-pass detector
-under a mask (k_corners_fused_masked, then k_filter_keys) restated per tile as corner_tiles.Model restates k_corners_fused.  No GPU here.
-
-    1  the eigenvalue map is that of the whole image: the mask plays no part in it
-    2  maxVal = the maximum of the map over the pixels with mask != 0; none: no corner
-    3  threshold (float)((double)maxVal * quality), strict >, for every pixel
-    4  the 3 x 3 maximum test runs over all pixels: a masked-out neighbour competes
-    5  a candidate is an interior pixel that passes 3 and 4 and has mask != 0
-    6  order (value descending, ties: later raster index first), the min_distance grid and max_corners as without a mask
-
-What a tile's own maximum runs over: the pixels with mask != 0 among the in-image part of the 66 x 33 eigenvalues around the tile -- the
-region k_corners_fused takes it over, restricted by the mask.  A tile with no such pixel returns early (`early`): it computes nothing,
-publishes no maximum and reports a count of 0."""
-import functools
-
+"""Masks, masked cases and clips for the detector tests (include/vstab.h, "Detection mask").  The definition of the
+detector under a mask is corner_def's (candidates, select, Model); this module holds what the tests feed it: mask shapes, the cases that
+separate the definition from its near misses, the named raw-detector sets, and the clips and state machine of the pipeline tests.  No GPU
+here.  A plain module, imported by corner_def and the tests."""
 import numpy as np
 
 import corner_tiles as C
@@ -21,127 +9,6 @@ import oracle
 import synth
 
 TW, TH, SLOTS = C.TW, C.TH, C.SLOTS
-
-
-def _is_max(e):
-    """interior pixels that equal the maximum of their 3 x 3 neighbourhood (every neighbour of an interior pixel is in the image)"""
-    h, w = e.shape
-    pad = np.full((h + 2, w + 2), -np.inf, np.float32)
-    pad[1:-1, 1:-1] = e
-    m = e.copy()
-    for dy in range(3):
-        for dx in range(3):
-            m = np.maximum(m, pad[dy:dy + h, dx:dx + w])
-    inner = np.zeros((h, w), bool)
-    inner[1:h - 1, 1:w - 1] = True
-    return inner & (e == m)
-
-
-def candidates(gray, mask, quality=0.01):
-    """steps 1-5: (eigenvalue map, boolean map of the candidates, maxVal or None)"""
-    gray = np.ascontiguousarray(gray, np.uint8)
-    e = oracle.min_eig(gray)
-    sel = np.asarray(mask) != 0
-    assert sel.shape == e.shape
-    if not sel.any():
-        return e, np.zeros(e.shape, bool), None
-    maxv = e[sel].max()
-    thr = np.float32(np.float64(maxv) * quality)
-    # (OpenCV sets what fails the threshold to zero and dilates that map: a pixel above a non-negative threshold that equals the maximum of
-    #  the thresholded map equals the maximum of the raw one, and the other way round, since zeroed neighbours lie below it either way)
-    return e, _is_max(e) & (e > thr) & sel, maxv
-
-
-def select(e, cand, max_corners, min_distance):
-    """step 6, as vo_good_features and select_corners (vstab_hostlogic.hpp) run it: keys descending, the grid of cells of round(min_distance) px"""
-    h, w = e.shape
-    ys, xs = np.nonzero(cand)
-    keys = (e[ys, xs].view(np.uint32).astype(np.uint64) << np.uint64(32)) | (ys * w + xs).astype(np.uint64)
-    order = np.argsort(keys)[::-1]
-    xs, ys = xs[order], ys[order]
-    cell = int(np.rint(min_distance))
-    if cell < 1:
-        n = len(xs) if max_corners <= 0 else min(len(xs), max_corners)
-        return np.stack([xs[:n], ys[:n]], 1).astype(np.float32).reshape(-1, 2)
-    gw, gh = -(-w // cell), -(-h // cell)
-    grid = [[] for _ in range(gw * gh)]
-    md2 = min_distance * min_distance
-    out = []
-    for x, y in zip(xs.tolist(), ys.tolist()):
-        xc, yc = x // cell, y // cell
-        good = True
-        for yy in range(max(yc - 1, 0), min(yc + 1, gh - 1) + 1):
-            for xx in range(max(xc - 1, 0), min(xc + 1, gw - 1) + 1):
-                for (a, b) in grid[yy * gw + xx]:
-                    if (x - a) * (x - a) + (y - b) * (y - b) < md2:   # (whole numbers below 2^24: exact in the float the detectors use)
-                        good = False
-                        break
-                if not good:
-                    break
-            if not good:
-                break
-        if good:
-            grid[yc * gw + xc].append((x, y))
-            out.append((x, y))
-            if max_corners > 0 and len(out) == max_corners:
-                break
-    return np.array(out, np.float32).reshape(-1, 2)
-
-
-def good_features(gray, mask, max_corners=200, quality=0.01, min_distance=30.0):
-    """goodFeaturesToTrack(gray, max_corners, quality, min_distance, mask): (n, 2) float32 (x, y) in acceptance order"""
-    e, cand, _ = candidates(gray, mask, quality)
-    return select(e, cand, max_corners, min_distance)
-
-
-class Model:
-    """corner_tiles.Model under a mask: `final`, `keys`, and per tile `early`, `lo` and `hi` -- the count k_corners_fused_masked reports lies
-    between the survivors under the final threshold quality * maxVal and those under quality * the tile's own masked maximum."""
-
-    def __init__(self, img, mask, quality=0.01):
-        img = np.ascontiguousarray(img, np.uint8)
-        self.img, self.mask, self.quality = img, np.ascontiguousarray(mask, np.uint8), quality
-        h, w = img.shape
-        self.w, self.h = w, h
-        e, self.final, maxv = candidates(img, mask, quality)
-        self.eig = e
-        sel = self.sel = self.mask != 0
-        bits = e.view(np.int32)
-        if maxv is not None:
-            fmax = int(bits[sel].max())
-            assert fmax >= 0 and np.int32(fmax).view(np.float32) == maxv, "a negative masked maximum: outside the definition"
-        self.frame_max = maxv
-        is_max = _is_max(e) & sel
-        ys, xs = np.nonzero(self.final)
-        self.keys = np.sort((e[ys, xs].view(np.uint32).astype(np.uint64) << np.uint64(32)) | (ys * w + xs).astype(np.uint64))
-        self.n = len(self.keys)
-        self.tiles_x, self.tiles_y = -(-w // TW), -(-h // TH)
-        shape = (self.tiles_y, self.tiles_x)
-        self.lo, self.hi = np.zeros(shape, np.int64), np.zeros(shape, np.int64)
-        self.early = np.zeros(shape, bool)
-        for ty in range(self.tiles_y):
-            for tx in range(self.tiles_x):
-                oy, ox = ty * TH, tx * TW
-                around = (slice(max(oy - 1, 0), min(oy + TH + 1, h)), slice(max(ox - 1, 0), min(ox + TW + 1, w)))
-                if not sel[around].any():
-                    self.early[ty, tx] = True
-                    continue
-                own = int(bits[around][sel[around]].max())
-                assert own >= 0, "a tile whose masked maximum is negative"
-                thr_own = np.float32(np.float64(np.int32(own).view(np.float32)) * quality)
-                sl = (slice(oy, min(oy + TH, h)), slice(ox, min(ox + TW, w)))
-                self.lo[ty, tx] = int(self.final[sl].sum())
-                self.hi[ty, tx] = int((is_max[sl] & (e[sl] > thr_own)).sum())
-        self.spills = self.lo > SLOTS
-        self.timing = (self.lo <= SLOTS) & (self.hi > SLOTS)
-        self.keyed = self.hi <= SLOTS
-        self.full = (self.lo == SLOTS) & (self.hi == SLOTS)
-
-    def spilled_range(self):
-        return int(self.spills.sum()), int((self.hi > SLOTS).sum())
-
-    def corners(self, max_corners, min_distance):
-        return select(self.eig, self.final, max_corners, min_distance)
 
 
 # ---- masks -------------------------------------------------------------------------------------------------------------------------
@@ -190,7 +57,7 @@ def case_neighbours_compete():
     return g, m
 
 
-# ---- the named raw-detector sets of the GPU test (test_detection_mask_cpu.py asserts what they reach) -----------------------------------
+# ---- the named raw-detector sets of the GPU test (corner_def.raw_masked_model; test_detection_mask_cpu.py asserts what they reach) -----------------------------------
 def _tiles_off(name, off):
     """the frame of corner_tiles set `name` with the whole tiles `off` (tile numbers, tile rows first) masked out"""
     g = C.make(name)
@@ -250,13 +117,6 @@ def _raw_sets():
 
 
 RAW_SETS = _raw_sets()
-
-
-@functools.lru_cache(maxsize=None)
-def raw_model(name):
-    """the masked model of a named raw set, computed once per process and shared"""
-    g, m = RAW_SETS[name]()
-    return Model(g, m)
 
 
 # ---- the clips of the pipeline tests ----------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-"""CPU half of the corner-block tests (include/vstab.h, "Corner block size"): the definition tests/corner_block_def.py against the
-definitions it extends and against its golden file, the exactness of its double sums, what the frames of the GPU test reach at each block
+"""CPU half of the corner-block tests (include/vstab.h, "Corner block size"): the definition tests/corner_def.py at block 3 against the
+recorded answers of the definitions it replaced and the oracle, at blocks 5 and 7 against its golden file, the exactness of its double sums, what the frames of the GPU test reach at each block
 size, and every refusal that needs no device, in order, with its message."""
 import ctypes
 import importlib
@@ -8,9 +8,8 @@ import os
 import numpy as np
 import pytest
 
-import corner_block_def as D
+import corner_def as D
 import corner_tiles as C
-import harris_def as H
 import mask_def as M
 import oracle
 
@@ -22,18 +21,30 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+def definitions_kat():
+    """(make_definitions_golden, its file): the answers of the definitions there were before tests/corner_def.py"""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_definitions_golden as G
+    return G, G.load()
+
+
 # ---- the definition -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", MEASURED)
 def test_block_3_is_the_definition_there_was(name):
+    """against the oracle on the whole frame; against what harris_def and mask_def answered (golden/definitions_kat.npz) on the frame CROPPED
+    to its top-left 40 x 24 pixels -- the planes of the whole frames would not fit a fixture"""
     g = D.frame(name)
-    for mine, theirs in zip(D.covariance_sums(g, 3), H.covariance_sums(g)):
-        assert np.array_equal(bits(mine), bits(theirs))
     assert np.array_equal(bits(D.min_eig(g, 3)), bits(oracle.min_eig(g)))
-    assert np.array_equal(bits(D.corner_harris(g, 3, 0.06)), bits(H.corner_harris(g, 0.06)))
     assert np.array_equal(D.good_features(g), oracle.good_features(g))
-    assert np.array_equal(D.good_features(g, harris=True), H.good_features(g))
-    mask = M.overlay_box(*g.shape)
-    assert np.array_equal(D.good_features(g, mask), M.good_features(g, mask))
+    G, kat = definitions_kat()
+    g = G.crop(g, "block3")
+    assert g.shape == (24, 40)
+    for p, mine in zip("abc", D.covariance_sums(g, 3)):
+        assert np.array_equal(bits(mine), bits(kat[f"block3_{name}_{p}"])), p
+    assert np.array_equal(bits(D.corner_harris(g, 3, 3, 0.06)), bits(kat[f"block3_{name}_harris"]))
+    assert np.array_equal(bits(D.good_features(g, None, *G.PARAMS, harris=True)), bits(kat[f"block3_{name}_corners_harris"]))
+    assert np.array_equal(bits(D.good_features(g, M.overlay_box(*g.shape), *G.PARAMS)), bits(kat[f"block3_{name}_corners_masked"]))
 
 
 def test_golden_file():
@@ -87,31 +98,31 @@ def test_sums_are_not_exact_on_dark_noise():
 @pytest.mark.parametrize("block", NEW)
 def test_states_of_the_raw_frames(block):
     for harris, names in ((False, D.RAW_FRAMES_MIN_EIG), (True, D.RAW_FRAMES)):
-        models = {n: D.raw_model(n, block, harris) for n in names}
+        models = {n: D.raw_model(n, block, 3, harris) for n in names}
         assert any(m.spills.any() for m in models.values()), "no tile that always spills"
         assert any(m.timing.any() for m in models.values()), "no tile that spills by timing"
         assert any(m.positive and m.lo.any() and m.keyed.any() for m in models.values())
         if harris:
             assert any(m.negative.any() and m.positive for m in models.values()), "no tile with a negative maximum in a frame with corners"
-            for n in H.NON_POSITIVE:
+            for n in D.NON_POSITIVE:
                 assert not models[n].positive and models[n].negative.all(), n
         else:
             assert all(m.positive for m in models.values())     # the minimum-eigenvalue definition covers every frame it is given
     for harris in (False, True):
         for n in D.RAW_MASKED:
-            m = D.raw_masked_model(n, block, harris)
+            m = D.raw_masked_model(n, block, 3, harris)
             assert m.early.any() and m.positive and m.n > 0 and not m.final[m.mask == 0].any(), n
-        assert any(D.raw_masked_model(n, block, harris).timing.any() or D.raw_masked_model(n, block, harris).spills.any() for n in D.RAW_MASKED)
+        assert any(D.raw_masked_model(n, block, 3, harris).timing.any() or D.raw_masked_model(n, block, 3, harris).spills.any() for n in D.RAW_MASKED)
     r4 = D.rule4_masked_model(block)
     assert not r4.positive and r4.frame_max < 0 and r4.early.any()
-    assert len(D.good_features(r4.img, None, 4000, 0.01, 0.0, block, True)) > 0
+    assert len(D.good_features(r4.img, None, 4000, 0.01, 0.0, block, 3, True)) > 0
 
 
 @pytest.mark.parametrize("block", NEW)
 def test_fall_back_frame_is_over_the_key_capacity(block):
     """the 2-px checkerboard at 640 x 512 keeps its plateau under a 5 x 5 and a 7 x 7 box"""
     for harris in (False, True):
-        _, cand, maxv = D.candidates(H.fall_back_frame(), None, 0.01, block, harris)
+        _, cand, maxv = D.candidates(D.fall_back_frame(), None, 0.01, block, 3, harris)
         assert maxv > 0 and int(cand.sum()) > C.KEY_CAP
 
 

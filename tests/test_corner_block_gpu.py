@@ -1,14 +1,13 @@
 """GPU half of the corner-block tests (include/vstab.h, "Corner block size"): vstab_min_eig_block / vstab_corner_harris_block against the
 definition bit for bit, vstab_good_features_block with its three detectors, the raw output of k_corners_fused_block + k_filter_keys (test
-hook vstabx_corners_fused_block), the two-pass fall-back and a handle with vstab_set_corner_block, against tests/corner_block_def.py.  What
+hook vstabx_corners_fused_block), the two-pass fall-back and a handle with vstab_set_corner_block, against tests/corner_def.py.  What
 the named frames reach is asserted without a GPU in test_corner_block_cpu.py.  Every comparison is exact (rotations: the 1e-9 of
 test_pipeline_gpu.py)."""
 import numpy as np
 import pytest
 
-import corner_block_def as D
+import corner_def as D
 import corner_tiles as C
-import harris_def as H
 import mask_def as M
 import oracle
 from test_detection_mask_gpu import FILL, LAYOUTS, PARAMS, dev, mask_view
@@ -28,10 +27,10 @@ def bits(a):
 def check_dense(vs, gd, g, block, what):
     sums = D.covariance_sums(g, block)
     got = vs.min_eig_block(gd, block).cpu().numpy()
-    assert np.array_equal(bits(got), bits(H.min_eig_from_sums(*sums))), (what, block, "min_eig")
+    assert np.array_equal(bits(got), bits(D.min_eig_from_sums(*sums))), (what, block, "min_eig")
     for k in KS:
         got = vs.corner_harris_block(gd, block, k).cpu().numpy()
-        assert np.array_equal(bits(got), bits(H.response_from_sums(*sums, k))), (what, block, k)
+        assert np.array_equal(bits(got), bits(D.response_from_sums(*sums, k))), (what, block, k)
 
 
 # ---- the dense maps ---------------------------------------------------------------------------------------------------------------------
@@ -72,8 +71,8 @@ def test_block_3_through_the_new_names(vs, cuda):
 # ---- the stateless detector ----------------------------------------------------------------------------------------------------------------
 def check_stateless(vs, cuda, g, mask, what, block, harris, k=D.K_DEFAULT):
     gd = dev(g, cuda)
-    e, cand, _ = D.candidates(g, mask, 0.01, block, harris, k)
-    exp = [M.select(e, cand, mc, md) for mc, _, md in PARAMS]
+    e, cand, _ = D.candidates(g, mask, 0.01, block, 3, harris, k)
+    exp = [D.select(e, cand, mc, md) for mc, _, md in PARAMS]
     for layout in LAYOUTS if mask is not None else ("none",):
         md_ = None if mask is None else mask_view(mask, cuda, layout)
         for det in (vs.DETECTOR_AUTO, vs.DETECTOR_FUSED, vs.DETECTOR_TWO_PASS):
@@ -103,10 +102,10 @@ def test_block_3_entry_points_give_what_they_gave(vs, cuda, name):
     gd = dev(g, cuda)
     full = mask_view(M.full(*g.shape), cuda, "aligned")
     assert np.array_equal(vs.good_features_mask(gd, None, 200, 0.01, 30.0, detector=vs.DETECTOR_FUSED), oracle.good_features(g))
-    assert np.array_equal(vs.good_features_harris(gd, full, 200, 0.01, 30.0), H.good_features(g))
+    assert np.array_equal(vs.good_features_harris(gd, full, 200, 0.01, 30.0), D.good_features(g, harris=True))
     for det in (vs.DETECTOR_AUTO, vs.DETECTOR_FUSED, vs.DETECTOR_TWO_PASS):
         assert np.array_equal(vs.good_features_block(gd, None, 200, 0.01, 30.0, 3, False, float("nan"), detector=det), oracle.good_features(g))   # k is not looked at
-        assert np.array_equal(vs.good_features_block(gd, full, 200, 0.01, 30.0, 3, True, 0.04, detector=det), H.good_features(g))
+        assert np.array_equal(vs.good_features_block(gd, full, 200, 0.01, 30.0, 3, True, 0.04, detector=det), D.good_features(g, harris=True))
 
 
 def test_block_sizes_separate(vs, cuda):
@@ -151,14 +150,14 @@ def check_raw(vs, cuda, m, mask_dev=None):
 def test_raw_output_against_the_model(vs, cuda, name, block):
     for harris in RESPONSES:
         if harris or name in D.RAW_FRAMES_MIN_EIG:
-            check_raw(vs, cuda, D.raw_model(name, block, harris))
+            check_raw(vs, cuda, D.raw_model(name, block, 3, harris))
 
 
 @pytest.mark.parametrize("block", NEW)
 @pytest.mark.parametrize("name", D.RAW_MASKED)
 def test_raw_output_under_a_mask(vs, cuda, name, block):
     for harris in RESPONSES:
-        m = D.raw_masked_model(name, block, harris)
+        m = D.raw_masked_model(name, block, 3, harris)
         for layout in LAYOUTS:
             check_raw(vs, cuda, m, mask_view(m.mask, cuda, layout))
 
@@ -178,19 +177,19 @@ def test_rule_4_under_a_mask(vs, cuda, block):
 
 @pytest.mark.parametrize("block,harris", [(5, False), (7, True)])
 def test_two_pass_fall_back(vs, cuda, block, harris):
-    g = H.fall_back_frame()
-    e, cand, _ = D.candidates(g, None, 0.01, block, harris)
+    g = D.fall_back_frame()
+    e, cand, _ = D.candidates(g, None, 0.01, block, 3, harris)
     assert int(cand.sum()) > C.KEY_CAP
     for mc, q, md in PARAMS:
         info = {}
         got = vs.good_features_block(dev(g, cuda), None, mc, q, md, block, harris, detector=vs.DETECTOR_AUTO, info=info)
         assert info["detector_used"] == vs.DETECTOR_TWO_PASS
-        assert np.array_equal(got, M.select(e, cand, mc, md)), mc
+        assert np.array_equal(got, D.select(e, cand, mc, md)), mc
 
 
 # ---- the pipeline -----------------------------------------------------------------------------------------------------------------------
 def check_against_state_machine(vs, cuda, frames, K, w, h, r, seed, block, mask=None, harris=False, k=D.K_DEFAULT):
-    """test_harris_gpu.check_against_state_machine with find = corner_block_def.good_features"""
+    """test_harris_gpu.check_against_state_machine with find = corner_def.good_features at a block size"""
     import expect
     import test_pipeline_gpu as P
     cfg = dict(smooth_radius=r, seed=seed, corner_block=block)

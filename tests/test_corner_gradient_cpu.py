@@ -1,5 +1,5 @@
-"""CPU half of the corner-gradient tests (include/vstab.h, "Corner gradient size"): the definition tests/corner_gradient_def.py against the
-definition it extends and against its golden file, its coefficients, the inexact double sums that bind the box order for block 3, and every
+"""CPU half of the corner-gradient tests (include/vstab.h, "Corner gradient size"): the definition tests/corner_def.py at gradient 3 against the
+recorded answers of the definition it replaced, at gradients 5 and 7 against its golden file, its coefficients, the inexact double sums that bind the box order for block 3, and every
 refusal that needs no device, in order, with its message."""
 import ctypes
 import importlib
@@ -8,8 +8,7 @@ import os
 import numpy as np
 import pytest
 
-import corner_block_def as B
-import corner_gradient_def as D
+import corner_def as D
 
 BAD_GRADIENTS = (-1, 0, 1, 2, 4, 6, 8, 9, 11, -3)
 BAD_BLOCKS = (0, 1, 2, 4, 6, 8, 9, 11, -3)
@@ -19,18 +18,31 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+def definitions_kat():
+    """(make_definitions_golden, its file): the answers of the definitions there were before tests/corner_def.py"""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_definitions_golden as G
+    return G, G.load()
+
+
 # ---- the definition -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("block", D.BLOCKS)
 def test_gradient_3_is_the_definition_there_was(block):
-    """every dense frame of both block sizes' GPU tests (ten names, the interior-edge ones at both sizes), and the named frames"""
-    frames = [g for b in (5, 7) for g in B.dense_frames(b).values()] + [D.frame(n) for n in ("luma_322x182", "cut_66x33", "timing")]
-    for g in frames:
-        for mine, theirs in zip(D.products(g, block, 3), B.products(g, block)):
-            assert np.array_equal(bits(mine), bits(theirs)), g.shape
-    g = D.frame("luma_322x182")
-    assert np.array_equal(bits(D.min_eig(g, block, 3)), bits(B.min_eig(g, block)))
-    assert np.array_equal(bits(D.corner_harris(g, block, 3, 0.06)), bits(B.corner_harris(g, block, 0.06)))
-    assert np.array_equal(D.good_features(g, block=block, gradient=3), B.good_features(g, block=block))
+    """every dense frame of both block sizes' GPU tests (ten names, the interior-edge ones at both sizes), and the named frames, against what
+    corner_block_def answered (golden/definitions_kat.npz).  The frames are CROPPED to their top-left corner, 20 x 13 pixels for the products
+    and 66 x 33 for the responses ("3x3" and "4x5" stay whole): the planes of the whole frames would not fit a fixture"""
+    G, kat = definitions_kat()
+    frames = G.product_frames()
+    assert len(frames) == 23 and all(g.shape == (min(13, g.shape[0]), min(20, g.shape[1])) for g in frames.values())
+    for name, g in frames.items():
+        for p, mine in zip(G.PLANES, D.products(g, block, 3)):
+            assert np.array_equal(bits(mine), bits(kat[f"products_{name}_B{block}_{p}"])), (name, p)
+    g = G.crop(D.frame("luma_322x182"), "response")
+    assert g.shape == (33, 66)
+    assert np.array_equal(bits(D.min_eig(g, block, 3)), bits(kat[f"response_B{block}_min_eig"]))
+    assert np.array_equal(bits(D.corner_harris(g, block, 3, 0.06)), bits(kat[f"response_B{block}_harris"]))
+    assert np.array_equal(bits(D.good_features(g, None, *G.PARAMS, block=block, gradient=3)), bits(kat[f"response_B{block}_corners"]))
 
 
 def test_row_differences_are_whole_and_coefficients_are_the_stated_casts():
@@ -105,7 +117,7 @@ def test_interior_edge_sizes():
     want = {(3, 5): (132, 66), (3, 7): (136, 67), (5, 5): (136, 67), (5, 7): (136, 68), (7, 5): (136, 68), (7, 7): (136, 69)}
     assert {p: D.interior_edge_size(*p) for p in D.NEW_PAIRS} == want
     for b in (5, 7):
-        assert D.interior_edge_size(b, 3) == B.interior_edge_size(b) and D.source_box(b, 3) == B.INTERIOR_BOX[b]
+        assert D.interior_edge_size(b, 3) == D.interior_edge_size(b) and D.source_box(b, 3) == D.INTERIOR_BOX[b]
     for b, G in D.NEW_PAIRS:
         w, h = D.interior_edge_size(b, G)
         assert w % 4 == 0 and w > 64 + 4 and h > 31

@@ -1,13 +1,12 @@
 """GPU half of the corner-gradient tests (include/vstab.h, "Corner gradient size"): vstab_min_eig_grad / vstab_corner_harris_grad against the
 definition bit for bit for the six new pairs of block and gradient size, vstab_good_features_grad with its three detectors, the raw output
 of k_corners_fused_block<B, G> + k_filter_keys (test hook vstabx_corners_fused_grad), the two-pass fall-back and a handle with
-vstab_set_corner_gradient, against tests/corner_gradient_def.py.  Every comparison is exact (rotations: the 1e-9 of test_pipeline_gpu.py)."""
+vstab_set_corner_gradient, against tests/corner_def.py.  Every comparison is exact (rotations: the 1e-9 of test_pipeline_gpu.py)."""
 import numpy as np
 import pytest
 
-import corner_gradient_def as D
+import corner_def as D
 import corner_tiles as C
-import harris_def as H
 import mask_def as M
 import oracle
 from test_detection_mask_gpu import FILL, LAYOUTS, PARAMS, dev, mask_view
@@ -29,10 +28,10 @@ def bits(a):
 def check_dense(vs, gd, g, block, gradient, what):
     sums = D.covariance_sums(g, block, gradient)
     got = vs.min_eig_grad(gd, block, gradient).cpu().numpy()
-    assert np.array_equal(bits(got), bits(H.min_eig_from_sums(*sums))), (what, block, gradient, "min_eig")
+    assert np.array_equal(bits(got), bits(D.min_eig_from_sums(*sums))), (what, block, gradient, "min_eig")
     for k in KS:
         got = vs.corner_harris_grad(gd, block, gradient, k).cpu().numpy()
-        assert np.array_equal(bits(got), bits(H.response_from_sums(*sums, k))), (what, block, gradient, k)
+        assert np.array_equal(bits(got), bits(D.response_from_sums(*sums, k))), (what, block, gradient, k)
 
 
 # ---- the dense maps ---------------------------------------------------------------------------------------------------------------------
@@ -83,7 +82,7 @@ def test_gradient_3_through_the_new_names(vs, cuda, block):
 def check_stateless(vs, cuda, g, mask, what, block, gradient, harris, detectors, k=D.K_DEFAULT):
     gd = dev(g, cuda)
     e, cand, _ = D.candidates(g, mask, 0.01, block, gradient, harris, k)
-    exp = [M.select(e, cand, mc, md) for mc, _, md in PARAMS]
+    exp = [D.select(e, cand, mc, md) for mc, _, md in PARAMS]
     for layout in LAYOUTS if mask is not None else ("none",):
         md_ = None if mask is None else mask_view(mask, cuda, layout)
         for det in detectors:
@@ -162,7 +161,7 @@ def test_raw_output_against_the_model(vs, cuda, name, pair):
     for harris in RESPONSES:
         if harris or name in D.RAW_FRAMES_MIN_EIG:
             m = D.raw_model(name, *pair, harris)
-            if harris and name in H.NON_POSITIVE:
+            if harris and name in D.NON_POSITIVE:
                 assert not m.positive                                 # the Harris frames whose maximum is not positive
             check_raw(vs, cuda, m)
 
@@ -180,19 +179,19 @@ def test_raw_output_under_a_mask(vs, cuda, pair):
 @pytest.mark.parametrize("pair,harris", [((3, 5), True), ((5, 7), False)], ids=lambda p: str(p))
 def test_two_pass_fall_back(vs, cuda, pair, harris):
     """more candidates than the key buffer holds: the one-pass detector hands over to the new dense kernels"""
-    g = H.fall_back_frame()
+    g = D.fall_back_frame()
     e, cand, _ = D.candidates(g, None, 0.01, *pair, harris)
     assert int(cand.sum()) > C.KEY_CAP
     for mc, q, md in PARAMS:
         info = {}
         got = vs.good_features_grad(dev(g, cuda), None, mc, q, md, *pair, harris, detector=vs.DETECTOR_AUTO, info=info)
         assert info["detector_used"] == vs.DETECTOR_TWO_PASS
-        assert np.array_equal(got, M.select(e, cand, mc, md)), mc
+        assert np.array_equal(got, D.select(e, cand, mc, md)), mc
 
 
 # ---- the pipeline -----------------------------------------------------------------------------------------------------------------------
 def check_against_state_machine(vs, cuda, frames, K, w, h, r, seed, block, gradient, mask=None, harris=False, k=D.K_DEFAULT):
-    """test_corner_block_gpu.check_against_state_machine with find = corner_gradient_def.good_features"""
+    """test_corner_block_gpu.check_against_state_machine with find = corner_def.good_features at a pair of sizes"""
     import expect
     import test_pipeline_gpu as P
     cfg = dict(smooth_radius=r, seed=seed, corner_gradient=gradient)

@@ -13,7 +13,7 @@ import importlib
 import numpy as np
 import pytest
 
-import mask_def
+import corner_def
 import oracle
 import synth
 
@@ -128,7 +128,7 @@ def frame_keys(name):
     """the candidate keys (float bits << 32 | raster index) of a frame at quality 0.01: oracle.min_eig, thresholded, 3 x 3 maxima"""
     seed, w, h = FRAMES[name]
     g = synth.luma(seed, w, h, rects=24)
-    e, cand, _ = mask_def.candidates(g, np.ones((h, w), np.uint8), 0.01)
+    e, cand, _ = corner_def.candidates(g, np.ones((h, w), np.uint8), 0.01)
     ys, xs = np.nonzero(cand)
     keys = (e[ys, xs].view(np.uint32).astype(np.uint64) << np.uint64(32)) | (ys * w + xs).astype(np.uint64)
     assert len(keys) > 60

@@ -1,6 +1,6 @@
 """GPU half of the detector-argument tests: the edge values of `quality` that the contract accepts (tests/test_detect_args_cpu.py has
-what it refuses) through every detector of every entry point, against the definitions: oracle.good_features (plain), mask_def (masked),
-harris_def (Harris, with and without a mask).
+what it refuses) through every detector of every entry point, against the definitions: oracle.good_features (plain), corner_def (masked,
+Harris, Harris with a mask).
 
     1e-300           the threshold (float)((double)maxVal * quality) rounds to 0: every positive 3 x 3 maximum is a corner
     nextafter(1, 0)  the threshold rounds to maxVal itself
@@ -11,8 +11,7 @@ quality > 0; these values are where that product leaves the floats it was tuned 
 import numpy as np
 import pytest
 
-import harris_def
-import mask_def
+import corner_def
 import oracle
 import synth
 
@@ -50,11 +49,11 @@ def test_accepted_quality_edges(vs, cuda, name, quality):
     g, dg, mask, dmask = _device(name, cuda)
     md = 5.0
     want = {"plain": oracle.good_features(g, MAX_CORNERS, quality, md),
-            "masked": mask_def.good_features(g, mask, MAX_CORNERS, quality, md),
-            "harris": harris_def.good_features(g, None, MAX_CORNERS, quality, md),
-            "harris_masked": harris_def.good_features(g, mask, MAX_CORNERS, quality, md)}
+            "masked": corner_def.good_features(g, mask, MAX_CORNERS, quality, md),
+            "harris": corner_def.good_features(g, None, MAX_CORNERS, quality, md, harris=True),
+            "harris_masked": corner_def.good_features(g, mask, MAX_CORNERS, quality, md, harris=True)}
     # the unmasked definition and the oracle are one definition
-    assert np.array_equal(want["plain"], mask_def.good_features(g, np.ones_like(mask), MAX_CORNERS, quality, md))
+    assert np.array_equal(want["plain"], corner_def.good_features(g, np.ones_like(mask), MAX_CORNERS, quality, md))
     print(name, quality, {k: len(v) for k, v in want.items()})
     if quality < 1.0:
         assert quality > 1e-3 or all(len(v) > 20 for v in want.values())
@@ -81,7 +80,7 @@ def test_accepted_min_distance_edges(vs, cuda, name):
     h, w = g.shape
     for md in (0.0, -0.0, float(np.hypot(w, h)) + 1.0, 2147483000.0, 1e300, float("inf")):
         want = oracle.good_features(g, MAX_CORNERS, 0.01, md)
-        want_m = mask_def.good_features(g, mask, MAX_CORNERS, 0.01, min(md, 1e6))   # (its grid is python's: any cell beyond the image is one cell)
+        want_m = corner_def.good_features(g, mask, MAX_CORNERS, 0.01, min(md, 1e6))   # (its grid is python's: any cell beyond the image is one cell)
         assert len(want) == (1 if md > 1 else MAX_CORNERS) or (md <= 1 and len(want) > 20)
         assert np.array_equal(vs.good_features(dg, MAX_CORNERS, 0.01, md), want), md
         for det in (vs.DETECTOR_AUTO, vs.DETECTOR_FUSED, vs.DETECTOR_TWO_PASS):

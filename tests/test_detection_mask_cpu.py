@@ -1,4 +1,4 @@
-"""CPU half of the detection-mask tests: the definition (tests/mask_def.py) against the oracle's detector and against the two wrong
+"""CPU half of the detection-mask tests: the definition (tests/corner_def.py under the masks of tests/mask_def.py) against the oracle's detector and against the two wrong
 versions it has to separate from, what the masked tile model reaches, the property that motivates the feature on the oracle alone, the
 clip the GPU test needs, and the refusals that need no device."""
 import ctypes
@@ -7,6 +7,7 @@ import importlib
 import numpy as np
 import pytest
 
+import corner_def as D
 import corner_tiles as C
 import mask_def as M
 import oracle
@@ -20,14 +21,14 @@ def test_full_mask_is_the_unmasked_detector(name):
     g = {"timing": C.timing_frame, "banded_under": lambda: C.banded("under")}.get(name, lambda: synth.luma(int(name[5:]), 320, 124))()
     for value in (1, 255):
         for mc, q, md in PARAMS:
-            assert np.array_equal(M.good_features(g, M.full(*g.shape, value), mc, q, md), oracle.good_features(g, mc, q, md)), (name, mc)
+            assert np.array_equal(D.good_features(g, M.full(*g.shape, value), mc, q, md), oracle.good_features(g, mc, q, md)), (name, mc)
 
 
 def test_filtering_afterwards_is_another_detector():
     g, m = M.case_filter_afterwards()
     e = oracle.min_eig(g)
     assert 0.0137 < e[m != 0].max() / e.max() < 0.0139
-    assert len(M.good_features(g, m, 0, 0.01, 0.0)) == 5154 and len(M.good_features(g, m, 200, 0.01, 30.0)) == 13
+    assert len(D.good_features(g, m, 0, 0.01, 0.0)) == 5154 and len(D.good_features(g, m, 200, 0.01, 30.0)) == 13
     unmasked = oracle.good_features(g, 0, 0.01, 0.0)
     assert len(unmasked) == 89 and int((m[unmasked[:, 1].astype(int), unmasked[:, 0].astype(int)] != 0).sum()) == 8
 
@@ -37,40 +38,41 @@ def test_masked_out_neighbours_compete():
     assert int((m == 0).sum()) == 156
     e = oracle.min_eig(g)
     assert 0.888 < e[m != 0].max() / e.max() < 0.890
-    assert len(M.good_features(g, m, 0, 0.01, 0.0)) == 3
+    assert len(D.good_features(g, m, 0, 0.01, 0.0)) == 3
 
 
 def test_all_zero_mask_has_no_corner():
     g = synth.luma(7, 320, 124)
-    assert M.good_features(g, np.zeros(g.shape, np.uint8)).shape == (0, 2)
-    m = M.Model(g, np.zeros(g.shape, np.uint8))
+    assert D.good_features(g, np.zeros(g.shape, np.uint8)).shape == (0, 2)
+    m = D.Model(g, np.zeros(g.shape, np.uint8))
     assert m.n == 0 and m.early.all() and not m.lo.any() and not m.hi.any()
 
 
 def test_masked_model_invariants_and_what_the_gpu_sets_reach():
     states = set()
     for name in M.RAW_SETS:
-        m = M.raw_model(name)
+        m = D.raw_masked_model(name)
         assert (m.lo <= m.hi).all() and int(m.lo.sum()) == m.n, name
         assert not m.lo[m.early].any() and not m.hi[m.early].any(), name
         assert (m.mask == 0).any() and (m.mask != 0).any(), name                       # a mask is in force
+        assert m.positive and not m.negative.any(), name                               # no negative masked maximum: inside the definition
         states |= {s for s, a in (("keys", m.keyed & (m.lo > 0)), ("full", m.full), ("spills", m.spills), ("timing", m.timing), ("early", m.early)) if a.any()}
     assert states == {"keys", "full", "spills", "timing", "early"}
-    assert all(M.raw_model(n).early.any() and not M.raw_model(n).early.all() for n in ("grid_7x5_tiles_off", "full_16_tiles_off", "timing_top_off", "timing_rows"))
+    assert all(D.raw_masked_model(n).early.any() and not D.raw_masked_model(n).early.all() for n in ("grid_7x5_tiles_off", "full_16_tiles_off", "timing_top_off", "timing_rows"))
     # whole tiles switched off, with their ring (early) and without it (a count of 0, yet computed)
-    m = M.raw_model("grid_5x3_tiles_off")
+    m = D.raw_masked_model("grid_5x3_tiles_off")
     assert not m.early.any() and [int(m.hi.ravel()[t]) for t in (0, 4, 7, 11)] == [0, 0, 0, 0] and m.spills.any()
-    assert int(M.raw_model("grid_7x5_tiles_off").early.sum()) == 7 and int(M.raw_model("full_16_tiles_off").early.sum()) == 4
+    assert int(D.raw_masked_model("grid_7x5_tiles_off").early.sum()) == 7 and int(D.raw_masked_model("full_16_tiles_off").early.sum()) == 4
     # plateau tiles cut in half still spill; exactly 256 and 257 survivors in what was a plateau tile
     for name in ("mixed_wave_half", "grid_7x5_half"):
-        m, whole = M.raw_model(name), C.model(name[:-5])
+        m, whole = D.raw_masked_model(name), C.model(name[:-5])
         plateau = whole.lo > 1000
         assert plateau.any() and m.spills[plateau].all() and (m.lo[plateau] < whole.lo[plateau]).all()
-    m = M.raw_model("mixed_wave_256")
+    m = D.raw_masked_model("mixed_wave_256")
     assert (m.lo.ravel()[2], m.hi.ravel()[2]) == (256, 256) and C.model("mixed_wave").spills.ravel()[2]
-    m = M.raw_model("grid_5x3_257")
+    m = D.raw_masked_model("grid_5x3_257")
     assert (m.lo.ravel()[2], m.hi.ravel()[2]) == (257, 257)
-    assert M.raw_model("timing_top_off").timing.any()
+    assert D.raw_masked_model("timing_top_off").timing.any()
 
 
 @pytest.fixture(scope="module")
@@ -80,7 +82,7 @@ def overlay_runs():
     out = {}
     for name, frames, find in (("clean", clean, lambda g: oracle.good_features(np.ascontiguousarray(g))),
                                ("overlay", over, lambda g: oracle.good_features(np.ascontiguousarray(g))),
-                               ("masked", over, lambda g: M.good_features(g, mask))):
+                               ("masked", over, lambda g: D.good_features(g, mask))):
         sm, _, _, _ = M.run_state_machine(frames, K, w, h, 5, 5, find)
         errs = [oracle.rotation_angle(lg["R"] @ (rots[k] @ rots[k - 1].T).T) for k, lg in enumerate(sm.log, start=1)]
         out[name] = (float(np.median(errs)), float(max(errs)), min(lg["inliers"] for lg in sm.log))
@@ -99,10 +101,10 @@ def test_the_mask_brings_the_rotation_error_back(overlay_runs):
 def test_planned_key_clip_under_the_mask():
     (w, h), frames, mask = M.planned_key_clip()
     K = oracle.get_preset_camera(4, w, h)
-    sm, _, counts, _ = M.run_state_machine(frames, K, w, h, 2, 1, lambda g: M.good_features(g, mask))
+    sm, _, counts, _ = M.run_state_machine(frames, K, w, h, 2, 1, lambda g: D.good_features(g, mask))
     assert [k for k, lg in enumerate(sm.log) if lg["key"]] == [20]
     assert min(min(c) for c in counts) >= 150
-    assert len(M.good_features(frames[0][:h], mask, 0, 0.01, 0.0)) <= C.SPEC_CAP
+    assert len(D.good_features(frames[0][:h], mask, 0, 0.01, 0.0)) <= C.SPEC_CAP
 
 
 class Fake:   # a "device" plane: only its pointer and pitch reach the library, which refuses before using them

@@ -8,6 +8,7 @@ import pytest
 
 import corner_tiles as C
 import expect
+import corner_def as D
 import mask_def as M
 import oracle
 import synth
@@ -57,8 +58,8 @@ def masks_for(g):
 
 def check_stateless(vs, cuda, g, mask, what):
     gd = dev(g, cuda)
-    e, cand, _ = M.candidates(g, mask)
-    exp = [M.select(e, cand, mc, md) for mc, _, md in PARAMS]
+    e, cand, _ = D.candidates(g, mask)
+    exp = [D.select(e, cand, mc, md) for mc, _, md in PARAMS]
     for layout in LAYOUTS:
         md_ = mask_view(mask, cuda, layout)
         for det in (vs.DETECTOR_AUTO, vs.DETECTOR_FUSED, vs.DETECTOR_TWO_PASS):
@@ -108,7 +109,7 @@ def check_raw(vs, m, gray, mask, cap=None):
 
 @pytest.mark.parametrize("name", list(M.RAW_SETS))
 def test_raw_output_against_the_masked_model(vs, cuda, name):
-    m = M.raw_model(name)
+    m = D.raw_masked_model(name)
     g = dev(m.img, cuda)
     for layout in LAYOUTS:
         check_raw(vs, m, g, mask_view(m.mask, cuda, layout))
@@ -129,7 +130,7 @@ def test_two_pass_fall_back_under_a_mask(vs, cuda):
     keep[15, 15] = 0
     drop[100:108, 100:140] = 0
     for mask, used in ((keep, vs.DETECTOR_TWO_PASS), (drop, vs.DETECTOR_FUSED)):
-        e, cand, _ = M.candidates(img, mask)
+        e, cand, _ = D.candidates(img, mask)
         n = int(cand.sum())
         assert (n > C.KEY_CAP) == (used == vs.DETECTOR_TWO_PASS) and n >= C.KEY_CAP - 400, n
         md_ = mask_view(mask, cuda, "aligned")
@@ -137,7 +138,7 @@ def test_two_pass_fall_back_under_a_mask(vs, cuda):
             info = {}
             got = vs.good_features_mask(g, md_, mc, q, md, detector=vs.DETECTOR_AUTO, info=info)
             assert info["detector_used"] == used
-            assert np.array_equal(got, M.select(e, cand, mc, md)), (used, mc)
+            assert np.array_equal(got, D.select(e, cand, mc, md)), (used, mc)
 
 
 # ---- the pipeline -----------------------------------------------------------------------------------------------------------------------
@@ -154,7 +155,7 @@ def check_against_state_machine(vs, cuda, frames, K, w, h, r, seed, mask, mask_a
     n = len(frames)
     assert len(outs) == max(n - 1, 0) and len(log) == max(n - 1, 0)
     Ko, (cw, ch) = oracle.get_output_camera(K, w, h)
-    sm, exp, counts, warp_rots = reference or M.run_state_machine(frames, K, w, h, r, seed, lambda g: M.good_features(g, mask))
+    sm, exp, counts, warp_rots = reference or M.run_state_machine(frames, K, w, h, r, seed, lambda g: D.good_features(g, mask))
     assert [l["key"] for l in log] == [l["key"] for l in sm.log]
     assert [(l["n_corners"], l["n_tracked"]) for l in log] == counts
     assert [l["inliers"] for l in log] == [l["inliers"] for l in sm.log]
@@ -169,7 +170,7 @@ def check_against_state_machine(vs, cuda, frames, K, w, h, r, seed, mask, mask_a
 def test_pipeline_overlay_clip_device_and_host_mask(vs, cuda):
     K, _, frames, _, mask = M.overlay_clip()
     w, h = 640, 360
-    ref = M.run_state_machine(frames, K, w, h, 5, 5, lambda g: M.good_features(g, mask))
+    ref = M.run_state_machine(frames, K, w, h, 5, 5, lambda g: D.good_features(g, mask))
     _, log = check_against_state_machine(vs, cuda, frames, K, w, h, 5, 5, mask, dev(mask, cuda), ref)
     assert min(l["inliers"] for l in log) >= 40
     padded = np.full((h, w + 13), 255, np.uint8)
@@ -192,7 +193,7 @@ def test_pipeline_planned_key_frame_is_detected_ahead_under_the_mask(vs, cuda):
     assert c["spec_over_cap"] == 0 and c["fused_overflows"] == 0
     assert min(l["n_tracked"] for l in log) >= 150
     # the corners of the planned key frame lie inside the mask: the speculative detection read it
-    assert (M.good_features(frames[20][:h], mask)[:, 1] >= 70).all()
+    assert (D.good_features(frames[20][:h], mask)[:, 1] >= 70).all()
 
 
 def test_pipeline_all_zero_and_full_masks(vs, cuda):

@@ -1,12 +1,12 @@
 """GPU half of the Harris tests: vstab_corner_harris against the definition bit for bit, vstab_good_features_harris with its three
 detectors, the raw output of k_corners_fused_harris(_masked) + k_filter_keys (test hook vstabx_corners_fused_harris), the two-pass
-fall-back and a handle with vstab_set_corner_response, against tests/harris_def.py.  What the named frames reach is asserted without a
+fall-back and a handle with vstab_set_corner_response, against tests/corner_def.py.  What the named frames reach is asserted without a
 GPU in test_harris_cpu.py.  Every comparison is exact (rotations: the 1e-9 of test_pipeline_gpu.py)."""
 import numpy as np
 import pytest
 
 import corner_tiles as C
-import harris_def as H
+import corner_def as H
 import mask_def as M
 import oracle
 import synth
@@ -55,8 +55,8 @@ def masks_for(g):
 
 def check_stateless(vs, cuda, g, mask, what, k=H.K_DEFAULT):
     gd = dev(g, cuda)
-    e, cand, _ = H.candidates(g, mask, 0.01, k)
-    exp = [M.select(e, cand, mc, md) for mc, _, md in PARAMS]
+    e, cand, _ = H.candidates(g, mask, 0.01, harris=True, k=k)
+    exp = [H.select(e, cand, mc, md) for mc, _, md in PARAMS]
     for layout in LAYOUTS if mask is not None else ("none",):
         md_ = None if mask is None else mask_view(mask, cuda, layout)
         for det in (vs.DETECTOR_AUTO, vs.DETECTOR_FUSED, vs.DETECTOR_TWO_PASS):
@@ -97,7 +97,7 @@ def host_half(vs, m, keys, kept, max_bits, mc, md):
     cand = np.zeros((m.h, m.w), bool)
     idx = (k & np.uint64(0xffffffff)).astype(np.int64)
     cand[idx // m.w, idx % m.w] = True
-    return M.select(m.eig, cand, mc, md)
+    return H.select(m.eig, cand, mc, md)
 
 
 def check_raw(vs, cuda, m, mask_dev=None):
@@ -128,7 +128,7 @@ def check_raw(vs, cuda, m, mask_dev=None):
 
 @pytest.mark.parametrize("name", H.RAW_FRAMES)
 def test_raw_output_against_the_model(vs, cuda, name):
-    m = H.raw_model(name)
+    m = H.raw_model(name, harris=True)
     check_raw(vs, cuda, m)
     g = dev(m.img, cuda)
     for det in (vs.DETECTOR_AUTO, vs.DETECTOR_FUSED, vs.DETECTOR_TWO_PASS):
@@ -152,13 +152,13 @@ def test_rule_4_under_a_mask(vs, cuda):
 
 def test_two_pass_fall_back(vs, cuda):
     g = H.fall_back_frame()
-    e, cand, _ = H.candidates(g)
+    e, cand, _ = H.candidates(g, harris=True)
     assert int(cand.sum()) > C.KEY_CAP
     for mc, q, md in PARAMS:
         info = {}
         got = vs.good_features_harris(dev(g, cuda), None, mc, q, md, detector=vs.DETECTOR_AUTO, info=info)
         assert info["detector_used"] == vs.DETECTOR_TWO_PASS
-        assert np.array_equal(got, M.select(e, cand, mc, md)), mc
+        assert np.array_equal(got, H.select(e, cand, mc, md)), mc
 
 
 # ---- the pipeline -----------------------------------------------------------------------------------------------------------------------
@@ -168,14 +168,14 @@ def run_product(vs, cuda, frames, mask=None, k=H.K_DEFAULT, **cfg):
 
 
 def check_against_state_machine(vs, cuda, frames, K, w, h, r, seed, mask, mask_arg, k=H.K_DEFAULT):
-    """test_detection_mask_gpu.check_against_state_machine with find = harris_def.good_features"""
+    """test_detection_mask_gpu.check_against_state_machine with find = corner_def.good_features with the Harris response"""
     import expect
     stab, outs = run_product(vs, cuda, frames, mask_arg, k, smooth_radius=r, seed=seed)
     log = stab.frame_log()
     n = len(frames)
     assert len(outs) == max(n - 1, 0) and len(log) == max(n - 1, 0)
     Ko, (cw, ch) = oracle.get_output_camera(K, w, h)
-    sm, exp, counts, warp_rots = M.run_state_machine(frames, K, w, h, r, seed, lambda g: H.good_features(g, mask, k=k))
+    sm, exp, counts, warp_rots = M.run_state_machine(frames, K, w, h, r, seed, lambda g: H.good_features(g, mask, harris=True, k=k))
     assert [l["key"] for l in log] == [l["key"] for l in sm.log]
     assert [(l["n_corners"], l["n_tracked"]) for l in log] == counts
     assert [l["inliers"] for l in log] == [l["inliers"] for l in sm.log]

@@ -1,4 +1,4 @@
-"""The tracker's options without a GPU (tests/lk_options_def.py; include/vstab.h, "Tracker options").  (1) At default options the numpy
+"""The tracker's options without a GPU (tests/lk_def.py; include/vstab.h, "Tracker options").  (1) At default options the numpy
 definition is the oracle bit for bit -- points, status, iteration counts and per-level positions -- over every case of lk_edges and two
 lk_segments sets.  (2) Invariants of the new rules.  (3) Every refusal of vstab_pyr_lk_ex and vstab_set_tracker_options that needs no
 device, in order, with its message.  (4) The known-answer set reproduces.  (5) What the GPU test's fixtures reach, asserted against the
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import lk_edges as E
-import lk_options_def as D
+import lk_def as D
 import lk_segments as S
 import oracle
 
@@ -55,7 +55,7 @@ def same_result(a, b):
             np.array_equal(a["err"].view(np.uint32), b["err"].view(np.uint32)) and np.array_equal(a["min_eig"].view(np.uint32), b["min_eig"].view(np.uint32)))
 
 
-@pytest.mark.parametrize("size", D.GPU_SIZES, ids=E.size_id)
+@pytest.mark.parametrize("size", D.GPU_SIZES[21], ids=E.size_id)
 def test_a_guess_equal_to_the_previous_point_is_no_guess(size):
     prev, nxt = D.pair(*size)
     pts = np.concatenate([D.points(*size), E.special_points(*size)[0]])
@@ -64,7 +64,7 @@ def test_a_guess_equal_to_the_previous_point_is_no_guess(size):
 
 
 def test_a_threshold_above_every_window_rejects_everything():
-    w, h = D.GPU_SIZES[0]
+    w, h = D.GPU_SIZES[21][0]
     prev, nxt = D.pair(w, h)
     pts = D.points(w, h)
     top = float(D.track(prev, nxt, pts, min_eig=0.0)["min_eig"].max())
@@ -81,7 +81,7 @@ def test_a_threshold_above_every_window_rejects_everything():
 
 @pytest.mark.parametrize("opt", [{}, dict(max_iter=2), dict(eps=10.0), dict(max_level=0)], ids=str)
 def test_the_residual_by_brute_force(opt):
-    w, h = D.GPU_SIZES[2]
+    w, h = D.GPU_SIZES[21][2]
     prev, nxt = D.pair(w, h)
     pts = D.points(w, h)
     r = D.track(prev, nxt, pts, **opt)
@@ -97,7 +97,7 @@ def test_the_residual_by_brute_force(opt):
 def test_the_minimum_eigenvalue_against_the_threshold(thr):
     """level 0 is the finest level: where its matrix was formed, status 0 by rejection means minEig < threshold (or D < FLT_EPSILON, which these
     frames do not reach without it), and a point that went on to iterate has minEig >= threshold"""
-    w, h = D.GPU_SIZES[1]
+    w, h = D.GPU_SIZES[21][1]
     prev, nxt = D.pair(w, h)
     pts = D.points(w, h)
     r = D.track(prev, nxt, pts, min_eig=thr)
@@ -111,9 +111,9 @@ def test_the_minimum_eigenvalue_against_the_threshold(thr):
 
 def test_fewer_levels_is_the_capped_pyramid():
     """rule 1 on its own: max_level = 3 on a 2-level frame changes nothing, and the level count is min(levels, max_level + 1)"""
-    for size in D.GPU_SIZES:
+    for size in D.GPU_SIZES[21]:
         for ml in range(4):
-            assert D.levels_of(*size, ml) == min(E.LEVELS.get(size, S.level_sizes(*size)[0]), ml + 1)
+            assert D.levels_of(*size, max_level=ml) == min(E.LEVELS.get(size, S.level_sizes(*size)[0]), ml + 1)
     prev, nxt = D.pair(130, 80)
     pts = D.points(130, 80)
     assert same_result(D.track(prev, nxt, pts, max_level=1), D.track(prev, nxt, pts, max_level=3))
@@ -190,7 +190,7 @@ def test_known_answers_reproduce():
 
 
 # ---- (5) what the GPU test's fixtures reach ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("size", D.GPU_SIZES, ids=E.size_id)
+@pytest.mark.parametrize("size", D.GPU_SIZES[21], ids=E.size_id)
 def test_main_cases_have_both_statuses(size):
     prev, nxt = D.pair(*size)
     pts = D.points(*size)
@@ -215,7 +215,7 @@ def test_each_option_separates():
     assert on_truth(D.track(prev, nxt, pts, max_level=0)) < on_truth(base[True]) and on_truth(base[True]) >= 40
 
 
-@pytest.mark.parametrize("size", D.GPU_SIZES, ids=E.size_id)
+@pytest.mark.parametrize("size", D.GPU_SIZES[21], ids=E.size_id)
 def test_initial_flow_cases(size):
     w, h = size
     prev, nxt = D.pair(w, h)

@@ -1,5 +1,5 @@
-"""The tracker's window without a GPU (tests/lk_window_def.py; include/vstab.h, "Tracker window").  (1) At W = 21 the definition is
-lk_options_def.track in every field.  (2) levels_W against a hand table; the residual by brute force at 15 and 31; invariants.  (3) Every
+"""The tracker's window without a GPU (tests/lk_def.py; include/vstab.h, "Tracker window").  (1) At W = 21 the definition answers what
+lk_options_def.track answered, in every field (golden/definitions_kat.npz).  (2) levels_W against a hand table; the residual by brute force at 15 and 31; invariants.  (3) Every
 refusal of vstab_pyr_lk_win, vstab_set_tracker_window and the vstabx_lk_segments_win hook that needs no device, in order, with its message.
 (4) The known-answer set reproduces.  (5) What the GPU test's fixtures reach, asserted against the definition alone."""
 import ctypes
@@ -10,9 +10,8 @@ import numpy as np
 import pytest
 
 import lk_edges as E
-import lk_options_def as D
+import lk_def as W
 import lk_segments as S
-import lk_window_def as W
 
 vs = importlib.import_module("video-annotator_amd")
 
@@ -23,34 +22,45 @@ def same(a, b):
 
 
 # ---- (1) W = 21 is "Tracker options" -----------------------------------------------------------------------------------------------------
-def both_agree(prev, nxt, pts, what, **kw):
-    a, b = D.track(prev, nxt, pts, **kw), W.track(prev, nxt, pts, 21, **kw)
-    assert set(a) == set(b)
-    for k in a:
-        assert same(a[k], b[k]), (what, k)
+def definitions_kat():
+    """(make_definitions_golden, its file): what lk_options_def.track (window 21), lk_window_def.track (15, 31) and lk_segments.fetch_ahead
+    answered before there was one definition; no input is cropped"""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_definitions_golden as G
+    return G, G.load()
+
+
+def answers_what_there_was(name):
+    G, kat = definitions_kat()
+    prev, nxt, pts, win, opt = G.tracker_cases()[name]
+    r = W.track(prev, nxt, pts, win, **opt)
+    assert set(r) == set(G.TRACK_KEYS)
+    for k in r:
+        want = kat[f"track_{name}_{k}"]
+        assert want.shape == np.shape(r[k]) and same(want, G.stored(k, r[k])), (name, k)
+    return r
 
 
 @pytest.mark.parametrize("size", E.SIZES, ids=E.size_id)
 def test_window_21_is_the_options_definition_on_the_edge_cases(size):
-    w, h = size
-    f = E.frames(w, h, 2)
-    pts = np.concatenate([E.boundary_cases(w, h)[0], E.special_points(w, h)[0]])
-    both_agree(f[0], f[1], pts, size)
-    both_agree(f[0], f[1], pts, (size, "options"), max_level=1, max_iter=4, eps=0.05, min_eig=1e-3, guess=pts + np.float32(0.75))
+    """lk_edges' boundary cases and special points of the size, at default options and with max_level=1, max_iter=4, eps=0.05, min_eig=1e-3
+    and a guess of pts + 0.75"""
+    for name in ("edge_" + E.size_id(size), "edge_" + E.size_id(size) + "_options"):
+        assert len(answers_what_there_was(name)["xy"]) == len(E.boundary_cases(*size)[0]) + len(E.special_points(*size)[0])
 
 
 def test_window_21_is_the_options_definition_on_a_segment_pair():
-    frames, pts, _ = S.make_set("jump_640", n=120)
-    both_agree(frames[3], frames[4], pts, "jump_640 3 -> 4")
-    both_agree(frames[3], frames[4], pts, "jump_640 3 -> 4, one iteration", max_iter=1)
+    for name in ("jump", "jump_one_iteration") + tuple("moved_w%d" % win for win in W.WINDOWS):
+        assert answers_what_there_was(name)["status"].any(), name
     assert W.geometry(21) == {"LKT": 22, "LKR": S.LKR, "LKJM": S.LKJM, "LKJR": S.LKJR, "SLACK": S.SLACK, "PPL": 7} and W.half(21) == S.HALF
 
 
 def test_window_21_fetch_ahead_model_is_lk_segments():
-    frames, pts, _ = S.make_set("jump_640", n=60)
-    exp = S.expected(frames, pts, [8])
-    a, b = S.fetch_ahead(exp, 640, 360), W.fetch_ahead(exp, 640, 360, 21)
-    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    G, kat = definitions_kat()
+    neigh, top = S.fetch_ahead(G.fetch_case(), 640, 360, 21)
+    assert np.array_equal(G.fetch_codes(neigh), kat["fetch_neigh"]) and np.array_equal(G.fetch_codes(top), kat["fetch_top"])
+    assert len(np.unique(kat["fetch_neigh"])) >= 3 and len(np.unique(kat["fetch_top"])) >= 3          # the file holds more than one answer
 
 
 # ---- (2) levels, geometry, residual ------------------------------------------------------------------------------------------------------
@@ -86,7 +96,7 @@ def test_levels_against_the_hand_table(win):
 def test_the_residual_by_brute_force(win):
     for (w, h), opt in (((130, 80), {}), ((24, 20), {}), ((130, 80), dict(max_iter=2, max_level=0))):
         prev, nxt = W.pair(w, h)
-        pts = W.points(w, h, win)[::4]
+        pts = W.window_points(w, h, win)[::4]
         r = W.track(prev, nxt, pts, win, **opt)
         alive = np.flatnonzero(r["status"] == 1)
         assert alive.size >= 4 and (r["err"][r["status"] == 0] == 0).all()
@@ -97,7 +107,7 @@ def test_the_residual_by_brute_force(win):
 @pytest.mark.parametrize("win", W.NEW_WINDOWS)
 def test_invariants(win):
     prev, nxt = W.pair(130, 80)
-    pts = W.points(130, 80, win)
+    pts = W.window_points(130, 80, win)
     r = W.track(prev, nxt, pts, win)
     g = W.track(prev, nxt, pts, win, guess=pts.copy())          # a guess equal to the previous point is no guess
     for k in r:
@@ -106,8 +116,8 @@ def test_invariants(win):
     assert not hi["status"].any() and same(hi["min_eig"], r["min_eig"]) and (hi["err"] == 0).all()
     assert (r["min_eig"][r["status"] == 1] >= np.float32(1e-4)).all()             # a tracked point passed the rejection test at level 0
     # the boundary cases: a start point is tracked at level l iff its origin lies in [-W, n_l)
-    bp, tags = W.boundary_cases(130, 80, win)
-    trk = W.tracked(bp, 130, 80, win)
+    bp, tags = E.edge_cases(130, 80, win)
+    trk = E.tracked(bp, 130, 80, win)
     for i, (l, axis, side, io) in enumerate(tags):
         assert trk[i, l] == (io == "in"), (win, tags[i])
 
@@ -224,12 +234,12 @@ def test_main_cases(win):
     """each main case: at least half of the grid tracked, other bits than W = 21 somewhere, and every boundary of the range test on both sides"""
     for (w, h), nl in zip(W.GPU_SIZES[win], W.GPU_LEVELS[win]):
         prev, nxt = W.pair(w, h)
-        pts = W.points(w, h, win)
-        ng = len(D.grid(w, h))
+        pts = W.window_points(w, h, win)
+        ng = len(W.grid(w, h))
         r, diff = differs_from_21(prev, nxt, pts, win)
         assert r["nl"] == nl and 2 * int(r["status"][:ng].sum()) >= ng and diff > 0, (win, w, h)
-        trk = W.tracked(pts[ng:], w, h, win)
-        tags = W.boundary_cases(w, h, win)[1]
+        trk = E.tracked(pts[ng:], w, h, win)
+        tags = E.edge_cases(w, h, win)[1]
         assert {(l, a, s, io) for l, a, s, io in tags} == {(l, a, s, io) for l in range(nl) for a in (0, 1) for s in ("lo", "hi") for io in ("in", "out")}
         assert all(trk[i, l] == (io == "in") for i, (l, a, s, io) in enumerate(tags))
     assert min(h for w, h in W.GPU_SIZES[15]) <= 16 and (24, 20) in W.GPU_SIZES[31]
@@ -238,14 +248,14 @@ def test_main_cases(win):
 @pytest.mark.parametrize("win", W.NEW_WINDOWS)
 def test_option_cases(win):
     w, h = W.GPU_SIZES[win][0]
-    ng = len(D.grid(w, h))
-    prev, nxt = D.moved_pair(w, h)
-    pts = W.points(w, h, win)
+    ng = len(W.grid(w, h))
+    prev, nxt = W.moved_pair(w, h)
+    pts = W.window_points(w, h, win)
     r, diff = differs_from_21(prev, nxt, pts, win, **W.COMBINED)
     plain = W.track(prev, nxt, pts, win)
     assert 2 * int(r["status"][:ng].sum()) >= ng and diff > 0 and not same(r["xy"], plain["xy"])
     a, b = W.pair(w, h)
-    g = W.guesses(w, h, win)
+    g = W.window_guesses(w, h, win)
     assert set(g) == {"truth_pm3", "far_side", "block_across_border", "specials"}
     for name, (p, guess) in g.items():
         r, r21 = W.track(a, b, p, win, guess=guess), W.track(a, b, p, 21, guess=guess)
@@ -259,7 +269,7 @@ def test_option_cases(win):
     sides = [(bool(x < 0), bool(x + jr > wl), bool(y < 0), bool(y + jr > hl)) for x, y in org]
     meant = [(0,), (1,), (2,), (3,), (0, 2), (1, 3)]
     assert len(sides) == len(meant) and all(all(s[i] for i in m) for s, m in zip(sides, meant)), (win, sides)
-    assert W.tracked(g["block_across_border"][0], w, h, win).all()
+    assert E.tracked(g["block_across_border"][0], w, h, win).all()
     # max_iter = 1 on the jump pair: the residual's window leaves the staged block
     jp, jn, jpts = W.jump_pair()
     r, diff = differs_from_21(jp, jn, jpts, win, max_iter=1)
@@ -271,12 +281,12 @@ def test_segment_clips_reach_every_fetch_ahead_branch(win):
     """over the three clips, with fi > 0: every level's neighbourhood and the top block are served, missed and not fetched; slots are lost
     mid-segment (status 0, then 2); and the records differ from the 21-pixel window's"""
     total = {}
-    for name in W.SEGMENT_CLIPS:
-        frames, pts, exps = W.segment_case(name, win)
-        assert set(exps) == set(W.SEGMENTATIONS)
+    for name in S.SEGMENT_CLIPS:
+        frames, pts, exps = S.segment_case(name, win)
+        assert set(exps) == set(S.SEGMENTATIONS)
         for segs, exp in exps.items():
             assert exp["nl"] == 4
-            neigh, top = W.fetch_ahead(exp, 640, 360, win)
+            neigh, top = S.fetch_ahead(exp, 640, 360, win)
             for k, v in S.reached(neigh, top, exp["fi"], exp["nl"]).items():
                 total[(segs,) + k] = total.get((segs,) + k, 0) + v
             assert (exp["status"] == 2).any() and ((exp["status"] == 0) & (exp["fi"][:, None] > 0)).any(), (win, name)
@@ -284,7 +294,7 @@ def test_segment_clips_reach_every_fetch_ahead_branch(win):
         a, b = exps[(8,)], exps[(3, 3, 2)]
         assert np.array_equal(a["status"], b["status"]) and same(a["xy"], b["xy"])      # the definition does not see the segmentation
         assert not same(a["xy"][0], W.track(frames[0], frames[1], pts, 21)["xy"]), (win, name)
-    for segs in W.SEGMENTATIONS:
+    for segs in S.SEGMENTATIONS:
         for c in ("served", "missed", "not_fetched"):
             for l in range(4):
                 assert total.get((segs, "neigh", l, c), 0) > 0, (win, segs, l, c)

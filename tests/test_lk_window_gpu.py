@@ -1,12 +1,13 @@
 """GPU half of the tracker-window tests: vstab_pyr_lk_win, the vstabx_lk_segments_win hook and a handle with vstab_set_tracker_window
-(k_lk_track_win for the windows 15 and 31) against tests/lk_window_def.py.  Every comparison is bit-exact -- points, status, err in both
+(k_lk_track_win for the windows 15 and 31) against tests/lk_def.py.  Every comparison is bit-exact -- points, status, err in both
 modes as float bits, the records of every pair of a segment -- and no point is left out; the pipeline's rotations carry the 1e-9 of
 test_lk_options_gpu.py.  What the fixtures reach is asserted without a GPU in test_lk_window_cpu.py."""
 import numpy as np
 import pytest
 
+import lk_def as W
 import lk_edges as E
-import lk_window_def as W
+import lk_segments as S
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -48,7 +49,7 @@ def both_err_modes(vs, cuda, prev, nxt, pts, win, opt, guess, what):
 def test_every_level_count(vs, cuda, win, size):
     w, h = size
     prev, nxt = W.pair(w, h)
-    pts = np.concatenate([W.points(w, h, win), E.special_points(w, h)[0]])
+    pts = np.concatenate([W.window_points(w, h, win), E.special_points(w, h)[0]])
     want = both_err_modes(vs, cuda, prev, nxt, pts, win, {}, None, (win, size))
     print(win, size, "levels", want["nl"], "status 1:", int(want["status"].sum()), "of", len(pts))
 
@@ -56,17 +57,16 @@ def test_every_level_count(vs, cuda, win, size):
 # ---- options on the 4-level frame -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("win", W.NEW_WINDOWS)
 def test_combined_options(vs, cuda, win):
-    import lk_options_def as D
     w, h = W.GPU_SIZES[win][0]
-    prev, nxt = D.moved_pair(w, h)
-    both_err_modes(vs, cuda, prev, nxt, W.points(w, h, win), win, W.COMBINED, None, (win, "combined"))
+    prev, nxt = W.moved_pair(w, h)
+    both_err_modes(vs, cuda, prev, nxt, W.window_points(w, h, win), win, W.COMBINED, None, (win, "combined"))
 
 
 @pytest.mark.parametrize("win", W.NEW_WINDOWS)
 def test_initial_flow(vs, cuda, win):
     w, h = W.GPU_SIZES[win][0]
     prev, nxt = W.pair(w, h)
-    for name, (pts, guess) in W.guesses(w, h, win).items():
+    for name, (pts, guess) in W.window_guesses(w, h, win).items():
         want = both_err_modes(vs, cuda, prev, nxt, pts, win, {}, guess, (win, name))
         print(win, name, "status 1:", int(want["status"].sum()), "of", len(pts))
 
@@ -98,10 +98,10 @@ def check_records(exp, hrec, drec, what):
     assert not (~tracked[..., None] & (xy != 0)).any(), what
 
 
-@pytest.mark.parametrize("name", W.SEGMENT_CLIPS)
+@pytest.mark.parametrize("name", S.SEGMENT_CLIPS)
 @pytest.mark.parametrize("win", W.NEW_WINDOWS)
 def test_segments_and_chains(vs, cuda, win, name):
-    frames, pts, exps = W.segment_case(name, win)
+    frames, pts, exps = S.segment_case(name, win)
     df = [dev(f, cuda) for f in frames]
     recs = []
     for segs, exp in exps.items():
@@ -112,7 +112,7 @@ def test_segments_and_chains(vs, cuda, win, name):
     assert np.array_equal(recs[0], recs[1]), (win, name, "segment invariance")
     # a wrong parent tag: status 3 from that launch on
     hrec, drec, _ = vs.lk_segments(df, pts, [3, 3, 2], bad_parent=1, win=win)
-    check_records(W.expected(frames[:4], pts, (3,), win), hrec[:3], drec[:3], (win, name, "before the bad parent"))
+    check_records(S.expected(frames[:4], pts, (3,), W=win), hrec[:3], drec[:3], (win, name, "before the bad parent"))
     assert (hrec[3:, :, 3] & 3 == 3).all() and np.array_equal(hrec, drec)
 
 
@@ -240,10 +240,9 @@ def test_setter_refusals_that_need_a_handle(vs, cuda):
 
 @pytest.mark.parametrize("size", [(360, 200), (40, 30)], ids=E.size_id)
 def test_window_21_is_pyr_lk_ex(vs, cuda, size):
-    import lk_options_def as D
     w, h = size
     prev, nxt = W.pair(w, h)
-    pts = D.points(w, h)
+    pts = W.points(w, h)
     dp, dn = dev(prev, cuda), dev(nxt, cuda)
     for kw in (dict(), dict(max_level=2, max_iter=8, eps=0.03, min_eig_threshold=1e-3), dict(flags=vs.LK_GET_MIN_EIGENVALS)):
         a, b = vs.pyr_lk_win(dp, dn, pts, 21, **kw), vs.pyr_lk_ex(dp, dn, pts, **kw)

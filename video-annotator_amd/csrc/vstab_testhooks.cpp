@@ -226,7 +226,7 @@ __attribute__((visibility("default"))) int vstabx_corners_fused(const void *gray
                                                                  void *stream) {
     return corners_fused_hook("vstabx_corners_fused", gray, pitch, w, h, nullptr, 0, false, quality, cap, canary, keys_out, counts_out, tile_counts, stream);
 }
-// vstabx_corners_fused under a detection mask (tests/test_detection_mask_gpu.py, tests/mask_def.py): k_corners_fused_masked, then
+// vstabx_corners_fused under a detection mask (tests/test_detection_mask_gpu.py, tests/corner_def.py): k_corners_fused_masked, then
 // k_filter_keys.  mask: a w x h device plane of bytes of pitch pitch_mask, not NULL.  The same outputs (the scratch is filled with the byte 0xA5 first, so
 // the count of 0 a tile that returns early reports is one it wrote) and the same refusals under this hook's name, then the mask's: a pitch below w, a
 // plane of 4 GiB or more.
@@ -235,7 +235,7 @@ __attribute__((visibility("default"))) int vstabx_corners_fused_mask(const void 
                                                                       unsigned int *tile_counts, void *stream) {
     return corners_fused_hook("vstabx_corners_fused_mask", gray, pitch, w, h, mask, pitch_mask, true, quality, cap, canary, keys_out, counts_out, tile_counts, stream);
 }
-// vstabx_corners_fused / vstabx_corners_fused_mask with the Harris response (tests/test_harris_gpu.py, tests/harris_def.py):
+// vstabx_corners_fused / vstabx_corners_fused_mask with the Harris response (tests/test_harris_gpu.py, tests/corner_def.py):
 // k_corners_fused_harris or, with a mask (optional here: NULL = none), k_corners_fused_harris_masked, then k_filter_keys.  The same outputs
 // and refusals under this hook's name, then "k lies in [0, 0.25)"; max_bits_out (optional): the frame maximum the kernels published, the
 // bits of a float read as int32 -- negative means "no response above zero", where the host reports no corner whatever the keys say.
@@ -245,7 +245,7 @@ __attribute__((visibility("default"))) int vstabx_corners_fused_harris(const voi
     return corners_fused_hook("vstabx_corners_fused_harris", gray, pitch, w, h, mask, pitch_mask, mask != nullptr, quality, cap, canary, keys_out, counts_out,
                               tile_counts, stream, true, k, max_bits_out);
 }
-// vstabx_corners_fused_harris with the block size and the response as arguments (tests/test_corner_block_gpu.py, tests/corner_block_def.py):
+// vstabx_corners_fused_harris with the block size and the response as arguments (tests/test_corner_block_gpu.py, tests/corner_def.py):
 // k_corners_fused_block<block> or, with block 3, the kernel vstabx_corners_fused* runs for this mask and response; then k_filter_keys.
 // response: VSTAB_CORNER_MIN_EIGENVAL (k is not looked at) or VSTAB_CORNER_HARRIS.  The same outputs; the refusals under this hook's name:
 // first "response is 0 or 1", then vstabx_corners_fused_harris', with "block_size is 3, 5 or 7" ahead of the mask's and k's.
@@ -257,7 +257,7 @@ __attribute__((visibility("default"))) int vstabx_corners_fused_block(const void
     return corners_fused_hook("vstabx_corners_fused_block", gray, pitch, w, h, mask, pitch_mask, mask != nullptr, quality, cap, canary, keys_out, counts_out, tile_counts,
                               stream, response == VSTAB_CORNER_HARRIS, k, max_bits_out, block);
 }
-// vstabx_corners_fused_block with the gradient size behind the block size (tests/test_corner_gradient_gpu.py, tests/corner_gradient_def.py):
+// vstabx_corners_fused_block with the gradient size behind the block size (tests/test_corner_gradient_gpu.py, tests/corner_def.py):
 // k_corners_fused_block<block, gradient> or, with both 3, the kernel vstabx_corners_fused* runs for this mask and response; then
 // k_filter_keys.  The same outputs; the refusals of vstabx_corners_fused_block under this hook's name, with "gradient_size is 3, 5 or 7"
 // directly behind the block's.
