@@ -245,7 +245,7 @@ VSTAB_API vstab_status vstab_cvt_bgr16_p010(const void *src_bgr16, size_t pitch_
 
 /* ------------------------------------------------------------------------------------------
  * Bicubic resampling: cv::remap's INTER_CUBIC, which FrameSourceWarp.hpp:90 admits and FrameSourceWarp.cpp:311 hands to cv::remap.
- * OpenCV 4.5's CPU path for 8-bit data, restated (tests/cubic_def.py holds it in numpy, tests/golden/cubic_kat.npz pins it):
+ * OpenCV 4.5's CPU path for 8-bit data, restated (tests/warp_def.py holds it in numpy, tests/golden/cubic_kat.npz pins it):
  *   quantisation  as INTER_LINEAR: sx = cvRound(32 * mapx) (half to even; NaN / out of int range -> INT_MIN), X = saturate_cast<short>(sx >> 5),
  *                 fx = sx & 31; the same for y;
  *   footprint     rows Y - 1 .. Y + 2, columns X - 1 .. X + 2;
@@ -273,7 +273,7 @@ VSTAB_API vstab_status vstab_warp_nv12_cubic(const void *y, size_t pitch_y, cons
 
 /* ------------------------------------------------------------------------------------------
  * Lanczos resampling: cv::remap's INTER_LANCZOS4 (4), the fourth mode FrameSourceWarp.hpp:90 can hand to cv::remap.  OpenCV 4.5's CPU
- * path for 8-bit data, restated (tests/lanczos4_def.py holds it in numpy, tests/golden/lanczos4_kat.npz pins it):
+ * path for 8-bit data, restated (tests/warp_def.py holds it in numpy, tests/golden/lanczos4_kat.npz pins it):
  *   quantisation  as INTER_LINEAR and INTER_CUBIC (above);
  *   footprint     rows Y - 3 .. Y + 4, columns X - 3 .. X + 4;
  *   1-D rows      interpolateLanczos4(x), x = k / 32: s0 = sin(y0), c0 = cos(y0) of y0 = -(x + 3) * pi / 4 in double; coefficient i =
@@ -300,7 +300,7 @@ VSTAB_API vstab_status vstab_warp_nv12_lanczos4(const void *y, size_t pitch_y, c
  * Border modes: cv::remap(src, dst, mapx, mapy, INTER_LINEAR, borderMode, borderValue), whose borderMode FrameSourceWarp.cpp:306-312 leaves
  * at BORDER_CONSTANT / Scalar().  The values are OpenCV's cv::BorderTypes.  ffmpeg's deshake `edge` option maps onto them: clamp =
  * BORDER_REPLICATE, mirror = BORDER_REFLECT_101, blank = BORDER_CONSTANT.  OpenCV 4.5's CPU path for 8-bit data, restated
- * (tests/border_def.py holds it in numpy, tests/golden/border_kat.npz pins it):
+ * (tests/warp_def.py holds it in numpy, tests/golden/border_kat.npz pins it):
  *   quantisation  as INTER_LINEAR above: sx = cvRound(32 * mapx), X = saturate_cast<short>(sx >> 5), fx = sx & 31; the same for y;
  *   taps          (X + i, Y + j), i, j in {0, 1}, read at (borderInterpolate(X + i, w, mode), borderInterpolate(Y + j, h, mode)):
  *                 REPLICATE clamps to [0, len - 1]; REFLECT / REFLECT_101 run OpenCV's loop
@@ -335,7 +335,7 @@ VSTAB_API vstab_status vstab_warp_nv12_border(const void *y, size_t pitch_y, con
 /* ------------------------------------------------------------------------------------------
  * Border modes of the cubic and Lanczos resamplers: cv::remap(src, dst, mapx, mapy, INTER_CUBIC or INTER_LANCZOS4, borderMode, borderValue),
  * the interpolation and the border chosen independently as cv::remap takes them.  OpenCV 4.5's CPU remapBicubic / remapLanczos4 for 8-bit
- * data on the branch taken when borderMode is not BORDER_CONSTANT (tests/resample_border_def.py holds it in numpy,
+ * data on the branch taken when borderMode is not BORDER_CONSTANT (tests/warp_def.py holds it in numpy,
  * tests/golden/resample_border_kat.npz pins it):
  *   quantisation, weights, blend  as "Bicubic resampling" / "Lanczos resampling" above: (sum + 2^14) >> 15, saturated;
  *   taps          tap (X - 1 + i, Y - 1 + j) (cubic) or (X - 3 + i, Y - 3 + j) (Lanczos) is read at (borderInterpolate(x, w, mode),
@@ -370,7 +370,7 @@ VSTAB_API vstab_status vstab_warp_nv12_lanczos4_border(const void *y, size_t pit
  * (`keep`), how deshake and Gyroflow users hide moving black wedges without inventing mirrored picture, and cv::remap's own
  * BORDER_TRANSPARENT.  The feature has entry points of its own (the border modes above keep refusing TRANSPARENT (5)), and the history
  * belongs to the caller, who passes the frame to keep as `prev`: encoders and players hold their last output anyway.  INTER_LINEAR, 8-bit
- * (tests/keep_def.py holds the definition in numpy, tests/golden/keep_kat.npz pins it):
+ * (tests/warp_def.py holds the definition in numpy, tests/golden/keep_kat.npz pins it):
  *   quantisation  as INTER_LINEAR above: sx = cvRound(32 * mapx) (NaN / outside the int range: INT_MIN), X = saturate_cast<short>(sx >> 5),
  *                 fx = sx & 31; the same for y;
  *   written       an output sample is WRITTEN iff its 2 x 2 footprint lies wholly inside the plane it reads: 0 <= X <= len_x - 2 and
@@ -768,8 +768,8 @@ VSTAB_API vstab_status vstab_warp_nv12_dist(const void *y, size_t pitch_y, const
 /* vstab_warp_nv12_dist for every 8-bit resampler and border mode.  resample: VSTAB_RESAMPLE_DEFAULT (INTER_LINEAR), _CUBIC or _LANCZOS4;
  * border_mode: VSTAB_BORDER_CONSTANT, _REPLICATE, _REFLECT or _REFLECT_101; map_mode: 1 or 2; out_format: VSTAB_OUT_BGR8 or
  * VSTAB_OUT_NV12_PLANAR.  Nothing new is defined: the frame is the map of "Lens distortion" above (tests/distort_def.py: maps) fed to the
- * resampler's own definition -- vstab_warp_nv12_cubic / _lanczos4 (tests/cubic_def.py, tests/lanczos4_def.py: remap_* and planar_mapped),
- * vstab_warp_nv12_border (tests/border_def.py) and the border modes of the cubic and Lanczos resamplers (tests/resample_border_def.py).
+ * resampler's own definition -- vstab_warp_nv12_cubic / _lanczos4 (tests/warp_def.py: remap, bgr and planar),
+ * vstab_warp_nv12_border and the border modes of the cubic and Lanczos resamplers (the same remap with another border_mode).
  * DEFAULT with CONSTANT is vstab_warp_nv12_dist itself, same bytes; DEFAULT with another mode runs vstab_warp_nv12_border's tile kernel,
  * CUBIC / LANCZOS4 the resampler's tile kernel for that border, each with the distorted map: the tile's source box is the exact
  * reduction over the tile's own map, as without distortion.  The quantised map (vstab_quantised_map_dist) serves DEFAULT + CONSTANT only.
@@ -789,7 +789,7 @@ VSTAB_API vstab_status vstab_warp_nv12_dist_ex(const void *y, size_t pitch_y, co
 /* The whole 8-bit surface behind one call: a rotation per output row (rot_bottom, as vstab_warp_nv12_rs; NULL: one rotation), a
  * calibrated lens (dist = k1..k4; NULL: the ideal lens), a resampler (VSTAB_RESAMPLE_DEFAULT, _CUBIC, _LANCZOS4), a border mode
  * (VSTAB_BORDER_*), out_format VSTAB_OUT_BGR8 or VSTAB_OUT_NV12_PLANAR.  Nothing new is defined: the frame is the map fed to the
- * resampler's own definition (tests/rs_resample_def.py).  The map without dist: map_mode's, row y with the rotation
+ * resampler's own definition (tests/warp_def.py: maps).  The map without dist: map_mode's, row y with the rotation
  * m_k = fmaf(t, rot_bottom[k] - params[8 + k], params[8 + k]), t = (float)y / (float)max(dst_height - 1, 1) (IEEE), for map modes 0, 1
  * and 5.  With dist: the map of "Lens distortion" above, modes 1 and 2 without rot_bottom, mode 1 with it, the row's m in place of the
  * rotation.  Chroma from map(2cx, 2cy) * 0.5f over the chroma plane's own size, as everywhere else.

@@ -74,10 +74,10 @@ def bgr10_to_p010(bgr, spec):
 
 def warp_p010(y, uv, params, dw, dh, spec, rot_bottom=None, mode=0, blend=0):
     """The 10-bit warp with a spec: the oracle's chain (its map, its 10-bit remap) with the conversion exchanged.  Modes 0..4: the maps
-    oracle.warp_p010 composes (create_map_ex / create_map_rs); mode 5: the reference kernel's own map, run on this GPU (border_def.maps)."""
-    import border_def
+    oracle.warp_p010 composes (create_map_ex / create_map_rs); mode 5: the reference kernel's own map, run on this GPU (warp_def.maps)."""
+    import warp_def as wd
     import oracle
-    mx, my = border_def.maps(params, dw, dh, mode, rot_bottom)
+    mx, my = wd.maps(params, dw, dh, mode, rot_bottom)
     return oracle.remap_bilinear10(p010_to_bgr10(y, uv, spec), mx, my, blend)
 
 

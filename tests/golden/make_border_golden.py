@@ -1,11 +1,11 @@
-"""Generates tests/golden/border_kat.npz, the known-answer vectors of the border modes (tests/border_def.py; include/vstab.h "Border
+"""Generates tests/golden/border_kat.npz, the known-answer vectors of the border modes (tests/warp_def.py; include/vstab.h "Border
 modes"):  python tests/golden/make_border_golden.py
 
   case<k>_src      small sources of width and height 1, 2, 3 and even sizes, with 1, 2 and 3 channels
   case<k>_mapx/y   maps over the source and several frame widths around it, exact half-steps of 1/32 pixel (cvRound's ties), NaN, +-inf,
                    +-1e30 and +-32768 entries
   case<k>_mode     the border mode (REPLICATE, REFLECT, REFLECT_101)
-  case<k>_out      cv::remap(INTER_LINEAR, mode) as border_def states it
+  case<k>_out      cv::remap(INTER_LINEAR, mode) as warp_def states it
 
 Fixtures are data only: inputs and expected outputs.
 """
@@ -17,7 +17,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
-import border_def  # noqa: E402
+import warp_def as wd  # noqa: E402
 
 # (sw, sh, channels, dw, dh): widths and heights 1, 2, 3 and even sizes
 SHAPES = [(1, 1, 1, 12, 9), (2, 2, 3, 16, 11), (3, 3, 2, 15, 10), (1, 3, 3, 11, 8), (3, 1, 1, 13, 7), (2, 3, 2, 9, 9), (8, 6, 3, 19, 13),
@@ -53,11 +53,11 @@ def main():
     k = 0
     for sw, sh, cn, dw, dh in SHAPES:
         src = rng.integers(0, 256, (sh, sw, cn) if cn > 1 else (sh, sw), dtype=np.uint8)
-        for mode in border_def.MODES:
+        for mode in wd.MODES:
             mx, my = kat_maps(rng, sw, sh, dw, dh)
             out[f"case{k}_src"], out[f"case{k}_mapx"], out[f"case{k}_mapy"] = src, mx, my
             out[f"case{k}_mode"] = np.array(mode, np.int32)
-            out[f"case{k}_out"] = border_def.remap_border(src, mx, my, mode)
+            out[f"case{k}_out"] = wd.remap(src, mx, my, "linear", mode)
             k += 1
     np.savez_compressed(os.path.join(HERE, "border_kat.npz"), **out)
     print("wrote border_kat.npz:", k, "cases")

@@ -1,4 +1,4 @@
-"""Generates tests/golden/cubic_kat.npz, the known-answer vectors of the bicubic resampler (tests/cubic_def.py; include/vstab.h "Bicubic
+"""Generates tests/golden/cubic_kat.npz, the known-answer vectors of the bicubic resampler (tests/warp_def.py; include/vstab.h "Bicubic
 resampling"):  python tests/golden/make_cubic_golden.py
 
   table            the (1024, 4, 4) integer weight table
@@ -6,7 +6,7 @@ resampling"):  python tests/golden/make_cubic_golden.py
   case<k>_mapx/y   maps with footprints straddling every edge and corner, exact half-steps of 1/32 pixel (cvRound's ties), NaN, +-inf
                    and +-1e9 entries
   case<k>_border   the border value per channel
-  case<k>_out      cv::remap(INTER_CUBIC, BORDER_CONSTANT) as cubic_def states it
+  case<k>_out      cv::remap(INTER_CUBIC, BORDER_CONSTANT) as warp_def states it
 
 Fixtures are data only: inputs and expected outputs.
 """
@@ -18,7 +18,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
-import cubic_def  # noqa: E402
+import warp_def as wd  # noqa: E402
 
 
 def kat_maps(rng, sw, sh, dw, dh):
@@ -47,7 +47,7 @@ def kat_maps(rng, sw, sh, dw, dh):
 
 def main():
     rng = np.random.default_rng(20261015)
-    out = {"table": cubic_def.cubic_table().astype(np.int16)}
+    out = {"table": wd.cubic_table().astype(np.int16)}
     cases = [(1, 1, 1, 12, 9, (37,)), (3, 3, 1, 16, 11, (200,)), (17, 9, 1, 23, 13, (16,)), (12, 8, 2, 19, 10, (128, 128)),
              (21, 14, 3, 25, 17, (0, 0, 0)), (5, 4, 3, 14, 12, (255, 7, 90))]
     for i, (sw, sh, cn, dw, dh, border) in enumerate(cases):
@@ -55,7 +55,7 @@ def main():
         mx, my = kat_maps(rng, sw, sh, dw, dh)
         out[f"case{i}_src"], out[f"case{i}_mapx"], out[f"case{i}_mapy"] = src, mx, my
         out[f"case{i}_border"] = np.array(border, np.int32)
-        out[f"case{i}_out"] = cubic_def.remap_cubic(src, mx, my, border)
+        out[f"case{i}_out"] = wd.remap(src, mx, my, "cubic", wd.CONSTANT, border)
     np.savez_compressed(os.path.join(HERE, "cubic_kat.npz"), **out)
     print("wrote cubic_kat.npz:", len(cases), "cases")
 

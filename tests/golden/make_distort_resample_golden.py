@@ -1,4 +1,4 @@
-"""Generates tests/golden/distort_resample_kat.npz, the known-answer vectors of vstab_warp_nv12_dist_ex (tests/distort_resample_def.py;
+"""Generates tests/golden/distort_resample_kat.npz, the known-answer vectors of vstab_warp_nv12_dist_ex (tests/warp_def.py;
 include/vstab.h):  python tests/golden/make_distort_resample_golden.py
 
   case<k>_src       a small packed NV12 frame (64 x 36 or smaller)
@@ -23,17 +23,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
 import distort_def  # noqa: E402
-import distort_resample_def as drd  # noqa: E402
+import warp_def as wd  # noqa: E402
 import oracle  # noqa: E402
 import synth  # noqa: E402
 
 # (sw, sh, dw, dh, mode, D, rotation vector, fy / fx of the input camera, resampler, border mode)
 CASES = [
-    (64, 36, 70, 37, 1, distort_def.D_A, (0.02, -0.03, 0.01), 1.0, "linear", drd.REFLECT_101),
-    (64, 36, 67, 35, 2, distort_def.D_B, (-0.15, 0.1, 0.3), 1.0, "cubic", drd.CONSTANT),
-    (48, 32, 66, 20, 1, distort_def.D_A, (0.0, 1.2, 0.0), 1.0, "lanczos4", drd.CONSTANT),     # part of the frame is behind the camera
-    (64, 36, 65, 33, 2, distort_def.D_C, (0.0, 0.0, 0.0), 1.25, "cubic", drd.REPLICATE),      # anisotropic input camera, axis pixel
-    (32, 16, 70, 18, 1, distort_def.D_B, (0.05, 0.4, -0.1), 1.0, "lanczos4", drd.REFLECT),
+    (64, 36, 70, 37, 1, distort_def.D_A, (0.02, -0.03, 0.01), 1.0, "linear", wd.REFLECT_101),
+    (64, 36, 67, 35, 2, distort_def.D_B, (-0.15, 0.1, 0.3), 1.0, "cubic", wd.CONSTANT),
+    (48, 32, 66, 20, 1, distort_def.D_A, (0.0, 1.2, 0.0), 1.0, "lanczos4", wd.CONSTANT),     # part of the frame is behind the camera
+    (64, 36, 65, 33, 2, distort_def.D_C, (0.0, 0.0, 0.0), 1.25, "cubic", wd.REPLICATE),      # anisotropic input camera, axis pixel
+    (32, 16, 70, 18, 1, distort_def.D_B, (0.05, 0.4, -0.1), 1.0, "lanczos4", wd.REFLECT),
 ]
 
 
@@ -49,11 +49,12 @@ def build():
     for k, (sw, sh, dw, dh, mode, D, rv, aniso, resampler, border) in enumerate(CASES):
         f = synth.nv12(300 + k, sw, sh, full_range=True)
         p = np.asarray(case_params(sw, sh, dw, dh, mode, rv, aniso), np.float32)
-        e = drd.Expected(resampler, f, p, dw, dh, mode, D, border)
+        e = wd.Expected(f, *wd.maps(p, dw, dh, mode, None, D))
         out[f"case{k}_src"], out[f"case{k}_params"], out[f"case{k}_dist"] = f, p, np.array(D, np.float64)
         out[f"case{k}_mode"], out[f"case{k}_size"] = np.array(mode, np.int32), np.array([dw, dh], np.int32)
-        out[f"case{k}_resample"], out[f"case{k}_border"] = np.array(drd.RESAMPLE[resampler], np.int32), np.array(border, np.int32)
-        out[f"case{k}_bgr"], out[f"case{k}_luma"], out[f"case{k}_chroma"] = e.bgr, e.luma, e.chroma
+        out[f"case{k}_resample"], out[f"case{k}_border"] = np.array(wd.RESAMPLE[resampler], np.int32), np.array(border, np.int32)
+        out[f"case{k}_bgr"] = e.bgr(resampler, border)
+        out[f"case{k}_luma"], out[f"case{k}_chroma"] = e.planar(resampler, border)
     return out
 
 

@@ -1,4 +1,4 @@
-"""Generates tests/golden/lanczos4_kat.npz, the known-answer vectors of the Lanczos resampler (tests/lanczos4_def.py; include/vstab.h
+"""Generates tests/golden/lanczos4_kat.npz, the known-answer vectors of the Lanczos resampler (tests/warp_def.py; include/vstab.h
 "Lanczos resampling"), and prints the sin / cos literals video-annotator_amd/csrc/vstab_lanczos4.hpp commits:
 python tests/golden/make_lanczos4_golden.py
 
@@ -8,7 +8,7 @@ python tests/golden/make_lanczos4_golden.py
   case<k>_mapx/y   maps with footprints straddling every edge and corner, exact half-steps of 1/32 pixel (cvRound's ties), NaN, +-inf
                    and +-1e9 entries
   case<k>_border   the border value per channel
-  case<k>_out      cv::remap(INTER_LANCZOS4, BORDER_CONSTANT) as lanczos4_def states it
+  case<k>_out      cv::remap(INTER_LANCZOS4, BORDER_CONSTANT) as warp_def states it
 
 Fixtures are data only: inputs and expected outputs.
 """
@@ -20,7 +20,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
-import lanczos4_def  # noqa: E402
+import warp_def as wd  # noqa: E402
 
 
 def kat_maps(rng, sw, sh, dw, dh):
@@ -55,8 +55,8 @@ def literals(name, vals):
 
 def main():
     rng = np.random.default_rng(20261016)
-    s0, c0 = lanczos4_def.sincos()
-    out = {"s0": np.array(s0, np.float64), "c0": np.array(c0, np.float64), "table": lanczos4_def.lanczos4_table().astype(np.int16)}
+    s0, c0 = wd.sincos()
+    out = {"s0": np.array(s0, np.float64), "c0": np.array(c0, np.float64), "table": wd.lanczos4_table().astype(np.int16)}
     cases = [(1, 1, 1, 12, 9, (37,)), (3, 5, 1, 16, 11, (200,)), (17, 9, 1, 23, 13, (16,)), (12, 8, 2, 19, 10, (128, 128)),
              (21, 14, 3, 25, 17, (0, 0, 0)), (7, 4, 3, 14, 12, (255, 7, 90))]
     for i, (sw, sh, cn, dw, dh, border) in enumerate(cases):
@@ -64,7 +64,7 @@ def main():
         mx, my = kat_maps(rng, sw, sh, dw, dh)
         out[f"case{i}_src"], out[f"case{i}_mapx"], out[f"case{i}_mapy"] = src, mx, my
         out[f"case{i}_border"] = np.array(border, np.int32)
-        out[f"case{i}_out"] = lanczos4_def.remap_lanczos4(src, mx, my, border)
+        out[f"case{i}_out"] = wd.remap(src, mx, my, "lanczos4", wd.CONSTANT, border)
     np.savez_compressed(os.path.join(HERE, "lanczos4_kat.npz"), **out)
     print(literals("S0", s0))
     print(literals("C0", c0))

@@ -1,4 +1,4 @@
-"""Generates tests/golden/rs_resample_kat.npz, the known-answer vectors of vstab_warp_nv12_rs_ex (tests/rs_resample_def.py;
+"""Generates tests/golden/rs_resample_kat.npz, the known-answer vectors of vstab_warp_nv12_rs_ex (tests/warp_def.py;
 include/vstab.h):  python tests/golden/make_rs_resample_golden.py
 
   case<k>_src         a packed NV12 frame, 48 x 32
@@ -24,34 +24,34 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
 import distort_def  # noqa: E402
-import rs_resample_def as rsd  # noqa: E402
+import warp_def as wd  # noqa: E402
 import synth  # noqa: E402
 
 SW, SH, DW, DH = 48, 32, 64, 32
 # (mode, D or None, resampler, border mode)
 CASES = [
-    (0, None, "cubic", rsd.CONSTANT),
-    (1, None, "cubic", rsd.REFLECT_101),
-    (0, None, "lanczos4", rsd.REPLICATE),
-    (1, None, "lanczos4", rsd.CONSTANT),
-    (1, distort_def.D_A, "cubic", rsd.REFLECT),
-    (1, distort_def.D_B, "lanczos4", rsd.REFLECT_101),
-    (1, distort_def.D_A, "linear", rsd.CONSTANT),
-    (1, distort_def.D_B, "linear", rsd.REPLICATE),
+    (0, None, "cubic", wd.CONSTANT),
+    (1, None, "cubic", wd.REFLECT_101),
+    (0, None, "lanczos4", wd.REPLICATE),
+    (1, None, "lanczos4", wd.CONSTANT),
+    (1, distort_def.D_A, "cubic", wd.REFLECT),
+    (1, distort_def.D_B, "lanczos4", wd.REFLECT_101),
+    (1, distort_def.D_A, "linear", wd.CONSTANT),
+    (1, distort_def.D_B, "linear", wd.REPLICATE),
 ]
 
 
 def build():
     out = {}
-    p, rb = rsd.case_params(SW, SH, DW, DH, 24.0, 16.0)
+    p, rb = wd.case_params(SW, SH, DW, DH, 24.0, 16.0)
     for k, (mode, D, resampler, border) in enumerate(CASES):
         f = synth.nv12(500 + k, SW, SH, full_range=True)
-        e = rsd.Expected(f, p, DW, DH, mode, rb, D)
+        e = wd.Expected(f, *wd.maps(p, DW, DH, mode, rb, D))
         out[f"case{k}_src"], out[f"case{k}_params"], out[f"case{k}_rot_bottom"] = f, np.asarray(p, np.float32), rb
         if D is not None:
             out[f"case{k}_dist"] = np.array(D, np.float64)
         out[f"case{k}_mode"], out[f"case{k}_size"] = np.array(mode, np.int32), np.array([DW, DH], np.int32)
-        out[f"case{k}_resample"], out[f"case{k}_border"] = np.array(rsd.RESAMPLE[resampler], np.int32), np.array(border, np.int32)
+        out[f"case{k}_resample"], out[f"case{k}_border"] = np.array(wd.RESAMPLE[resampler], np.int32), np.array(border, np.int32)
         out[f"case{k}_bgr"] = e.bgr(resampler, border)
         out[f"case{k}_luma"], out[f"case{k}_chroma"] = e.planar(resampler, border)
     return out

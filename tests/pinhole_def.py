@@ -13,7 +13,7 @@ section 23): OpenCV's Brown-Conrady model on a RECTILINEAR input camera, D = (k1
           negative 1 / (radial factor) gives the point back as it came.
 
 sin / cos are the oracle's (oracle.sincosf); colour conversion and every resampler behind the map are the existing definitions
-(distort_resample_def.remap_bgr / remap_planar): the distorted warp differs from modes 3 / 4 in the map alone."""
+(warp_def.bgr / planar): the distorted warp differs from modes 3 / 4 in the map alone."""
 import numpy as np
 
 import oracle

@@ -1,4 +1,4 @@
-"""Border modes (cv::remap borderMode) without a GPU: the numpy statement (tests/border_def.py) against its golden vectors, OpenCV's
+"""Border modes (cv::remap borderMode) without a GPU: the numpy statement (tests/warp_def.py) against its golden vectors, OpenCV's
 borderInterpolate loop against the closed form the kernels use, the constant border against the oracle's bilinear warp, and the argument
 checks of the new entry points."""
 import ctypes
@@ -7,35 +7,30 @@ import os
 import numpy as np
 import pytest
 
-import border_def
 import oracle
 import synth
+import warp_def as wd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "border_kat.npz")
 SWEEP = np.arange(-32768, 32768, dtype=np.int64)
 
 
 def golden_cases():
-    g = np.load(GOLDEN)
-    k = 0
-    while f"case{k}_src" in g:
-        yield k, g[f"case{k}_src"], g[f"case{k}_mapx"], g[f"case{k}_mapy"], int(g[f"case{k}_mode"]), g[f"case{k}_out"]
-        k += 1
+    return wd.golden_cases("border_kat", "src", "mapx", "mapy", "mode", "out")
 
 
 def test_golden_remaps():
     n = 0
     seen = set()
     for k, src, mx, my, mode, out in golden_cases():
-        got = border_def.remap_border(src, mx, my, mode)
+        got = wd.remap(src, mx, my, "linear", mode)
         assert np.array_equal(got, out), k
         seen.add((mode, 1 if src.ndim == 2 else src.shape[2]))
         seen.add(("w", src.shape[1]))
         seen.add(("h", src.shape[0]))
         n += 1
     assert n >= 27
-    assert {(m, c) for m in border_def.MODES for c in (1, 2, 3)} <= seen
+    assert {(m, c) for m in wd.MODES for c in (1, 2, 3)} <= seen
     assert {("w", 1), ("w", 2), ("w", 3), ("h", 1), ("h", 2), ("h", 3)} <= seen
 
 
@@ -59,24 +54,24 @@ def test_golden_maps_hold_the_special_entries():
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 1919, 1920, 32767])
-@pytest.mark.parametrize("mode", border_def.MODES)
+@pytest.mark.parametrize("mode", wd.MODES)
 def test_closed_form_equals_opencv_loop(n, mode):
     """The kernels' borderInterpolate (fold by the period 2 len / 2 len - 2, clamp) equals OpenCV's do-while loop for every position in
     [-32768, 32767] (and the 32768 that X + 1 reaches)."""
     p = np.concatenate([SWEEP, [32768]])
-    loop = border_def.border_interpolate_loop(p, n, mode)
+    loop = wd.border_interpolate_loop(p, n, mode)
     assert ((loop >= 0) & (loop < n)).all()
-    assert np.array_equal(border_def.border_interpolate(p, n, mode), loop)
+    assert np.array_equal(wd.border_interpolate(p, n, mode), loop)
 
 
 def test_loop_spot_values():
-    L = border_def.border_interpolate_loop
+    L = wd.border_interpolate_loop
     # OpenCV's documentation: REPLICATE aaaaaa|abcdefgh|hhhhhhh, REFLECT fedcba|abcdefgh|hgfedcb, REFLECT_101 gfedcb|abcdefgh|gfedcba
     p = np.arange(-6, 15)
-    assert list(L(p, 8, border_def.REPLICATE)) == [0] * 6 + list(range(8)) + [7] * 7
-    assert list(L(p, 8, border_def.REFLECT)) == [5, 4, 3, 2, 1, 0] + list(range(8)) + [7, 6, 5, 4, 3, 2, 1]
-    assert list(L(p, 8, border_def.REFLECT_101)) == [6, 5, 4, 3, 2, 1] + list(range(8)) + [6, 5, 4, 3, 2, 1, 0]
-    assert list(L(np.array([-5, -1, 1, 7]), 1, border_def.REFLECT_101)) == [0, 0, 0, 0]
+    assert list(L(p, 8, wd.REPLICATE)) == [0] * 6 + list(range(8)) + [7] * 7
+    assert list(L(p, 8, wd.REFLECT)) == [5, 4, 3, 2, 1, 0] + list(range(8)) + [7, 6, 5, 4, 3, 2, 1]
+    assert list(L(p, 8, wd.REFLECT_101)) == [6, 5, 4, 3, 2, 1] + list(range(8)) + [6, 5, 4, 3, 2, 1, 0]
+    assert list(L(np.array([-5, -1, 1, 7]), 1, wd.REFLECT_101)) == [0, 0, 0, 0]
 
 
 def test_constant_equals_oracle_bilinear():
@@ -86,7 +81,7 @@ def test_constant_equals_oracle_bilinear():
         mx = rng.uniform(-40, 70, (17, 29)).astype(np.float32)
         my = rng.uniform(-30, 50, (17, 29)).astype(np.float32)
         mx[0, :4] = [np.nan, np.inf, -1e30, 32768.0]
-        assert np.array_equal(border_def.remap_border(src, mx, my, border_def.CONSTANT), oracle.remap_bilinear(src, mx, my))
+        assert np.array_equal(wd.remap(src, mx, my, "linear", wd.CONSTANT), oracle.remap_bilinear(src, mx, my))
 
 
 def test_constant_warp_equals_oracle_warps():
@@ -97,15 +92,21 @@ def test_constant_warp_equals_oracle_warps():
     R = oracle.rodrigues([0.05, -0.04, 0.1])
     p = oracle.map_params(K, Ko, R)
     rb = oracle.map_params(K, Ko, oracle.rodrigues([0.02, 0.03, 0.12]))[8:]
+    def numpy_warps(mx, my):
+        """The warps of wd.bgr / wd.planar from wd.remap itself: under linear + CONSTANT those two answer with the oracle."""
+        y, uv = wd.planes_of(frame)
+        ouv = wd.remap(uv, *oracle.chroma_maps(mx, my), "linear", wd.CONSTANT, (128, 128))
+        bgr = wd.remap(oracle.cvt_nv12_bgr(frame), mx, my, "linear", wd.CONSTANT, 0)
+        return bgr, wd.remap(y, mx, my, "linear", wd.CONSTANT, 16), ouv.reshape(ouv.shape[0], -1)
+
     for mode in range(5):
-        assert np.array_equal(border_def.warp_nv12_border(frame, p, cw, ch, mode, border_def.CONSTANT), oracle.warp_nv12_ex(frame, p, cw, ch, mode, 0))
-        y, uv = border_def.warp_nv12_planar_border(frame, p, cw, ch, mode, border_def.CONSTANT)
+        bgr, y, uv = numpy_warps(*wd.maps(p, cw, ch, mode))
+        assert np.array_equal(bgr, oracle.warp_nv12_ex(frame, p, cw, ch, mode, 0))
         ey, euv = oracle.warp_nv12_planar(frame, p, cw, ch, mode)
         assert np.array_equal(y, ey) and np.array_equal(uv, euv), mode
     for mode in (0, 1):
-        assert np.array_equal(border_def.warp_nv12_border(frame, p, cw, ch, mode, border_def.CONSTANT, rb),
-                              oracle.warp_nv12_rs(frame, p, rb, cw, ch, mode, 0))
-        y, uv = border_def.warp_nv12_planar_border(frame, p, cw, ch, mode, border_def.CONSTANT, rb)
+        bgr, y, uv = numpy_warps(*wd.maps(p, cw, ch, mode, rb))
+        assert np.array_equal(bgr, oracle.warp_nv12_rs(frame, p, rb, cw, ch, mode, 0))
         ey, euv = oracle.warp_nv12_planar(frame, p, cw, ch, mode, rot_bottom=rb)
         assert np.array_equal(y, ey) and np.array_equal(uv, euv), mode
 
@@ -116,9 +117,9 @@ def test_replicate_inside_equals_constant():
     src = rng.integers(0, 256, (20, 30, 3), dtype=np.uint8)
     mx = rng.uniform(1.0, 28.0, (15, 25)).astype(np.float32)   # X in [1, 27], X + 1 <= 28 < 30
     my = rng.uniform(1.0, 18.0, (15, 25)).astype(np.float32)
-    ref = border_def.remap_border(src, mx, my, border_def.CONSTANT)
-    for mode in border_def.MODES:
-        assert np.array_equal(border_def.remap_border(src, mx, my, mode), ref)
+    ref = wd.remap(src, mx, my, "linear", wd.CONSTANT)
+    for mode in wd.MODES:
+        assert np.array_equal(wd.remap(src, mx, my, "linear", mode), ref)
 
 
 def test_reflect_far_outside_reads_picture():
@@ -128,12 +129,12 @@ def test_reflect_far_outside_reads_picture():
     src = rng.integers(0, 256, (9, 12), dtype=np.uint8)
     xs = np.arange(0, 12, dtype=np.float32)
     mx, my = np.stack([-1 - xs, xs]), np.full((2, 12), 4.0, np.float32)
-    out = border_def.remap_border(src, mx, my, border_def.REFLECT)
+    out = wd.remap(src, mx, my, "linear", wd.REFLECT)
     assert np.array_equal(out[0], out[1])
     mx = np.stack([-xs, xs])
-    out = border_def.remap_border(src, mx, my, border_def.REFLECT_101)
+    out = wd.remap(src, mx, my, "linear", wd.REFLECT_101)
     assert np.array_equal(out[0], out[1])
-    assert border_def.remap_border(src, mx - 100, my, border_def.CONSTANT).max() == 0
+    assert wd.remap(src, mx - 100, my, "linear", wd.CONSTANT).max() == 0
 
 
 def test_border_matches_opencv_when_present():
@@ -149,8 +150,8 @@ def test_border_matches_opencv_when_present():
         src = rng.integers(0, 256, (13, 17, cn) if cn > 1 else (13, 17), dtype=np.uint8)
         mx = rng.uniform(-60, 80, (19, 23)).astype(np.float32)
         my = rng.uniform(-40, 60, (19, 23)).astype(np.float32)
-        for mode in border_def.MODES:
-            assert np.array_equal(cv2.remap(src, mx, my, cv2.INTER_LINEAR, borderMode=mode), border_def.remap_border(src, mx, my, mode)), (cn, mode)
+        for mode in wd.MODES:
+            assert np.array_equal(cv2.remap(src, mx, my, cv2.INTER_LINEAR, borderMode=mode), wd.remap(src, mx, my, "linear", mode)), (cn, mode)
 
 
 def test_header_binding_and_opencv_values(vs):

@@ -1,6 +1,6 @@
 """GPU parity of the border modes (cv::remap borderMode; include/vstab.h "Border modes") through the C ABI and the pipeline object:
 vstab_remap_bilinear_border, vstab_warp_nv12_border (BGR8 and plane-wise NV12, with and without a rotation per output row) and
-vstab_set_border_mode.  Bar: every byte equals the numpy definition (tests/border_def.py) fed by the oracle's maps -- the reference kernel's own
+vstab_set_border_mode.  Bar: every byte equals the numpy definition (tests/warp_def.py) fed by the oracle's maps -- the reference kernel's own
 map, run on this GPU, for VSTAB_MAP_CREATEMAP_CL_OPENCL -- and every output plane is guarded by canary bytes (tests/layouts.py).  Under
 BORDER_CONSTANT the new entry points give the bytes of the pinned ones (vstab_warp_nv12_ex / _rs, vstab_remap_bilinear)."""
 import ctypes
@@ -8,17 +8,17 @@ import ctypes
 import numpy as np
 import pytest
 
-import border_def
-import border_tiles
 import expect
 import layouts
 import oracle
 import synth
+import warp_def as wd
+import warp_tiles as wt
 from test_layouts_gpu import PITCH_UV_4G
 
 pytestmark = pytest.mark.gpu
 
-MODES = border_def.MODES
+MODES = wd.MODES
 ROT = (0.02, -0.03, 0.01)
 PAST = (0.35, -0.25, 0.2)   # looks past the source: wide border areas, tiles wholly outside
 
@@ -76,9 +76,9 @@ def check_warp(vs, cuda, s, f, p, dw, dh, mode, border_mode, what, rot_bottom=No
     """BGR and plane-wise border warps of Src s (packed NV12 f on the host) against the definition."""
     ob, op = outs if outs else (None, None)
     eq(warp_border(vs, s, p, dw, dh, mode, vs.OUT_BGR8, border_mode, cuda, rot_bottom, ob),
-       border_def.warp_nv12_border(f, p, dw, dh, mode, border_mode, rot_bottom), (what, "bgr", mode, border_mode))
+       wd.bgr(f, *wd.maps(p, dw, dh, mode, rot_bottom), "linear", border_mode), (what, "bgr", mode, border_mode))
     gy, guv = warp_border(vs, s, p, dw, dh, mode, vs.OUT_NV12_PLANAR, border_mode, cuda, rot_bottom, op)
-    ey, euv = border_def.warp_nv12_planar_border(f, p, dw, dh, mode, border_mode, rot_bottom)
+    ey, euv = wd.planar(f, *wd.maps(p, dw, dh, mode, rot_bottom), "linear", border_mode)
     eq(gy, ey, (what, "luma", mode, border_mode)), eq(guv, euv, (what, "chroma", mode, border_mode))
 
 
@@ -105,7 +105,7 @@ def test_remap_border_random_maps_every_channel_count(vs, cuda):
                 pick = rng.random((dh, dw)) < 0.05
                 m[pick] = rng.choice(special, int(pick.sum()))
             for mode in MODES:
-                eq(remap_border(vs, cuda, src, mx, my, mode), border_def.remap_border(src, mx, my, mode), (sw, sh, cn, mode))
+                eq(remap_border(vs, cuda, src, mx, my, mode), wd.remap(src, mx, my, "linear", mode), (sw, sh, cn, mode))
 
 
 @pytest.mark.parametrize("sw", [1, 2, 3, 5, 1920, 32767])
@@ -119,7 +119,7 @@ def test_remap_border_sweeps_every_position(vs, cuda, sw):
     my = np.full(mx.shape, 1.25, np.float32)
     fx = 13
     for mode in MODES:
-        x0, x1 = border_def.border_interpolate(X, sw, mode), border_def.border_interpolate(X + 1, sw, mode)
+        x0, x1 = wd.border_interpolate(X, sw, mode), wd.border_interpolate(X + 1, sw, mode)
         row = src[1].astype(np.int64)   # my = 1.25: taps on rows 1 and 2, fy = 8
         row2 = src[2].astype(np.int64)
         acc = 512 + (32 - fx) * 24 * row[x0] + fx * 24 * row[x1] + (32 - fx) * 8 * row2[x0] + fx * 8 * row2[x1]
@@ -190,17 +190,18 @@ def test_warp_border_binding(vs, cuda):
     f = synth.nv12(34, w, h)
     p, dw, dh, K, Ko = cams(w, h, PAST)
     got = vs.warp_nv12_border(dev(f, cuda), p, dw, dh, 0, vs.OUT_BGR8, vs.BORDER_REPLICATE).cpu().numpy()
-    eq(got, border_def.warp_nv12_border(f, p, dw, dh, 0, vs.BORDER_REPLICATE), "binding bgr")
+    eq(got, wd.bgr(f, *wd.maps(p, dw, dh, 0), "linear", vs.BORDER_REPLICATE), "binding bgr")
     y, uv = vs.warp_nv12_border(dev(f, cuda), p, dw, dh, 1, vs.OUT_NV12_PLANAR, vs.BORDER_REFLECT, rot_bottom=p[8:])
-    ey, euv = border_def.warp_nv12_planar_border(f, p, dw, dh, 1, vs.BORDER_REFLECT, p[8:])
+    ey, euv = wd.planar(f, *wd.maps(p, dw, dh, 1, p[8:]), "linear", vs.BORDER_REFLECT)
     eq(y.cpu().numpy(), ey, "binding y"), eq(uv.cpu().numpy(), euv, "binding uv")
 
 
 # ---- tile and layout paths ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", sorted(border_tiles.TILE_SETS))
+@pytest.mark.parametrize("name", sorted(wt.TILE_SETS["border"]))
 def test_border_tile_sets(vs, cuda, name):
-    """The sets of tests/border_tiles.py: staged, gathered, exactly-the-budget, wholly-outside and edge-crossing tiles on every plane."""
-    p, sw, sh, dw, dh, mode = border_tiles.set_params(name)
+    """The sets of tests/warp_tiles.py for k_warp_border: staged, gathered, exactly-the-budget, wholly-outside and edge-crossing tiles on every
+    plane."""
+    p, sw, sh, dw, dh, mode = wt.set_params("border", name)
     f = synth.nv12(sum(map(ord, name)), sw, sh, full_range=True)
     s = layouts.place(f[:sh], f[sh:], "packed", cuda)
     for bm in MODES:
@@ -318,13 +319,13 @@ def pulls(vs, cuda, frames, how, border_mode=None, **cfg):
     return stab, outs
 
 
-def expect_frame(vs, f, K, Ko, R, cw, ch, out, how, map_mode=0, border_mode=border_def.REFLECT_101, rot_bottom=None, what=None):
+def expect_frame(vs, f, K, Ko, R, cw, ch, out, how, map_mode=0, border_mode=wd.REFLECT_101, rot_bottom=None, what=None):
     p = oracle.map_params(K, Ko, R)
     if how == "planar":
-        ey, euv = border_def.warp_nv12_planar_border(f, p, cw, ch, map_mode, border_mode, rot_bottom)
+        ey, euv = wd.planar(f, *wd.maps(p, cw, ch, map_mode, rot_bottom), "linear", border_mode)
         eq(out[0], ey, (what, "y")), eq(out[1], euv, (what, "uv"))
     else:
-        eq(out, border_def.warp_nv12_border(f, p, cw, ch, map_mode, border_mode, rot_bottom), what)
+        eq(out, wd.bgr(f, *wd.maps(p, cw, ch, map_mode, rot_bottom), "linear", border_mode), what)
 
 
 @pytest.mark.parametrize("tracking", [1, 0])
@@ -365,10 +366,10 @@ def test_pipeline_border_lens_mode(vs, cuda, clip):
         for i, o in enumerate(outs):
             p = oracle.map_params(stab.K_in, Kout, stab.warp_rotation(i))
             if how == "planar":
-                ey, euv = border_def.warp_nv12_planar_border(frames[i + 1], p, 480, 270, oracle.MAP_FISH_TO_FISH)
+                ey, euv = wd.planar(frames[i + 1], *wd.maps(p, 480, 270, oracle.MAP_FISH_TO_FISH), "linear", wd.REFLECT_101)
                 eq(o[0], ey, ("lens y", i)), eq(o[1], euv, ("lens uv", i))
             else:
-                eq(o, border_def.warp_nv12_border(frames[i + 1], p, 480, 270, oracle.MAP_FISH_TO_FISH), ("lens", i))
+                eq(o, wd.bgr(frames[i + 1], *wd.maps(p, 480, 270, oracle.MAP_FISH_TO_FISH), "linear", wd.REFLECT_101), ("lens", i))
         stab.close()
 
 

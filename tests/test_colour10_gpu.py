@@ -10,12 +10,12 @@ import os
 import numpy as np
 import pytest
 
-import border_def
 import colour10_def as C
 import expect
 import layouts
 import oracle
 import synth
+import warp_def as wd
 
 pytestmark = pytest.mark.gpu
 
@@ -158,7 +158,7 @@ def gather_case(mode, per_row):
         Ko, _ = oracle.get_output_camera(Ki, GW, GH)
     p = oracle.map_params(Ki, Ko, oracle.rodrigues((0.05, -0.1, 0.2)))
     rb = oracle.map_params(Ki, Ko, oracle.rodrigues((0.07, -0.09, 0.18)))[8:] if per_row else None
-    return p, rb, border_def.maps(p, GDW, GDH, mode, rb)
+    return p, rb, wd.maps(p, GDW, GDH, mode, rb)
 
 
 def gather_modes():
@@ -187,7 +187,7 @@ def small_case(rv, mode, per_row):
     Ko, _ = oracle.get_output_camera(K, SW, SH)
     p = oracle.map_params(K, Ko, oracle.rodrigues(rv))
     rb = oracle.map_params(K, Ko, oracle.rodrigues(tuple(v + d for v, d in zip(rv, (0.02, 0.01, -0.02)))))[8:] if per_row else None
-    return p, rb, border_def.maps(p, DW, DH, mode, rb)
+    return p, rb, wd.maps(p, DW, DH, mode, rb)
 
 
 def check_tiled(vs, cuda, s, seed, w, h, p, rb, maps, dw, dh, mode, blend, spec, what, shift=False):
@@ -241,10 +241,10 @@ def test_tiled_kernel_split_tiles_at_640x360(vs, cuda):
     s = layouts.place(*picture(31, w, h), "decoder", cuda)
     for rot in [(0.0, 0.0, 0.0), (0.02, -0.03, 0.01), (-0.15, 0.1, 0.3), (0.0, 2.6, 0.0)]:
         p = oracle.map_params(K, Ko, oracle.rodrigues(rot))
-        check_tiled(vs, cuda, s, 31, w, h, p, None, border_def.maps(p, cw, ch, 0), cw, ch, 0, FP16, BT2020L, ("640", rot))
+        check_tiled(vs, cuda, s, 31, w, h, p, None, wd.maps(p, cw, ch, 0), cw, ch, 0, FP16, BT2020L, ("640", rot))
     p = oracle.map_params(K, Ko, oracle.rodrigues((0.01, -0.02, 0.005)))
     rb = oracle.map_params(K, Ko, oracle.rodrigues((0.03, -0.01, -0.01)))[8:]
-    check_tiled(vs, cuda, s, 31, w, h, p, rb, border_def.maps(p, cw, ch, 1, rb), cw, ch, 1, FP16, BT709F, "640 per row")
+    check_tiled(vs, cuda, s, 31, w, h, p, rb, wd.maps(p, cw, ch, 1, rb), cw, ch, 1, FP16, BT709F, "640 per row")
 
 
 def test_planes_out_is_warp_then_inverse_converter(vs, cuda):
@@ -364,7 +364,7 @@ def test_pipeline_pulls_and_a_switch_mid_stream(vs, cuda, clip, blend):
             ey, euv = expect.warp_p010_planar(y, uv, p, cw, ch, None, blend, expect.IEEE)
             eq(got[0][0], ey, ("planar y", i)), eq(got[0][1], euv, ("planar uv", i))
             continue
-        exp = oracle.remap_bilinear10(C.p010_to_bgr10(y, uv, spec), *border_def.maps(p, cw, ch, 0), blend)
+        exp = oracle.remap_bilinear10(C.p010_to_bgr10(y, uv, spec), *wd.maps(p, cw, ch, 0), blend)
         s = layouts.place(y, uv, "decoder", cuda)
         eq(warp_bgr16(vs, cuda, s, p, cw, ch, 0, blend, spec), exp, ("stateless", i, spec))
         if how == "bgr16":

@@ -10,12 +10,12 @@ import os
 import numpy as np
 import pytest
 
-import border_def
 import colour_def as C
 import expect
 import layouts
 import oracle
 import synth
+import warp_def as wd
 
 pytestmark = pytest.mark.gpu
 
@@ -151,7 +151,7 @@ def small_case(rv, mode):
     K = oracle.get_preset_camera(4, SW, SH)
     Ko, _ = oracle.get_output_camera(K, SW, SH)
     p = oracle.map_params(K, Ko, oracle.rodrigues(rv))
-    return p, border_def.maps(p, DW, DH, mode)
+    return p, wd.maps(p, DW, DH, mode)
 
 
 @functools.lru_cache(maxsize=None)
@@ -190,7 +190,7 @@ def tall_case():
     Ko[1, 1] *= 0.8 * dh / h
     Ko[0, 2], Ko[1, 2] = dw / 2.0, dh / 2.0
     p = oracle.map_params(K, Ko, oracle.rodrigues(ROT))
-    return f, p, border_def.maps(p, dw, dh, 0)
+    return f, p, wd.maps(p, dw, dh, 0)
 
 
 @pytest.mark.parametrize("spec", [BT709L, BT601F], ids=["bt709_limited", "bt601_full"])
@@ -245,7 +245,7 @@ def stabilizer(vs, cuda, frames, **cfg):
 
 def expect_pull(f, K, Ko, R, cw, ch, spec):
     p = oracle.map_params(K, Ko, R)
-    return expected_bgr(f, border_def.maps(p, cw, ch, 0), spec)
+    return expected_bgr(f, wd.maps(p, cw, ch, 0), spec)
 
 
 def test_pipeline_pulls_and_a_switch_mid_stream(vs, cuda, clip):

@@ -1,4 +1,4 @@
-"""The bicubic resampler's definition (tests/cubic_def.py) and its ABI, without a GPU: the integer weight table's properties, the table the
+"""The bicubic resampler's definition (tests/warp_def.py) and its ABI, without a GPU: the integer weight table's properties, the table the
 library's kernels embed, the numpy remap's behaviour, the committed known answers, and vstab_create's refusals of bad `resample` values."""
 import ctypes
 import os
@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-import cubic_def
+import warp_def as wd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KAT = os.path.join(ROOT, "tests", "golden", "cubic_kat.npz")
@@ -14,7 +14,7 @@ KAT = os.path.join(ROOT, "tests", "golden", "cubic_kat.npz")
 
 @pytest.fixture(scope="module")
 def tab():
-    return cubic_def.cubic_table()
+    return wd.cubic_table()
 
 
 def test_every_entry_sums_to_one(tab):
@@ -33,7 +33,7 @@ def test_entries_mirror_within_one(tab):
     """The rounded products for fx mirror those for 32 - fx about the centre (columns 0..3 -> 3..0) within 1 per weight -- c3 is a
     remainder, so exact symmetry is not promised -- and likewise for fy.  The sum correction then moves at most one weight of an entry, inside
     the window (rows and columns 2, 3), by the entry's rounding excess: it is not mirrored, so corrected entries can differ by a few more."""
-    c = cubic_def.cubic_coeffs()
+    c = wd.cubic_coeffs()
     raw = np.clip(np.rint(((c[:, None, :, None] * c[None, :, None, :]).astype(np.float32) * np.float32(32768)).astype(np.float32)), -32768, 32767)
     raw = raw.astype(np.int64)                      # [fy, fx, k1, k2] before the correction
     for f in range(1, 32):
@@ -52,11 +52,9 @@ def test_table_matches_golden_and_library(tab, vs):
 
 
 def test_golden_remaps():
-    kat = np.load(KAT)
     n = 0
-    while f"case{n}_src" in kat:
-        got = cubic_def.remap_cubic(kat[f"case{n}_src"], kat[f"case{n}_mapx"], kat[f"case{n}_mapy"], kat[f"case{n}_border"])
-        assert np.array_equal(got, kat[f"case{n}_out"]), n
+    for k, src, mx, my, border, out in wd.golden_cases("cubic_kat", "src", "mapx", "mapy", "border", "out"):
+        assert np.array_equal(wd.remap(src, mx, my, "cubic", wd.CONSTANT, border), out), k
         n += 1
     assert n >= 6
 
@@ -65,7 +63,7 @@ def test_integer_translation_copies(tab):
     rng = np.random.default_rng(1)
     src = rng.integers(0, 256, (40, 50, 3), dtype=np.uint8)
     yy, xx = np.mgrid[0:30, 0:40].astype(np.float32)
-    out = cubic_def.remap_cubic(src, xx + 5, yy + 3)
+    out = wd.remap(src, xx + 5, yy + 3, "cubic")
     assert np.array_equal(out, src[3:33, 5:45])
 
 
@@ -74,14 +72,14 @@ def test_fractional_positions_within_a_level_of_float_bicubic():
     src = rng.integers(0, 256, (30, 30), dtype=np.uint8)
     mx = rng.uniform(2, 26, (40, 40)).astype(np.float32)
     my = rng.uniform(2, 26, (40, 40)).astype(np.float32)
-    got = cubic_def.remap_cubic(src, mx, my).astype(np.int64)
-    ref = cubic_def.remap_cubic_float(src, mx, my)
+    got = wd.remap(src, mx, my, "cubic").astype(np.int64)
+    ref = wd.remap_float(src, mx, my, "cubic")
     assert np.abs(got - ref).max() <= 1
     # cubic overshoots: a step edge saturates instead of wrapping
     step = np.zeros((8, 8), np.uint8)
     step[:, 4:] = 255
     yy, xx = np.mgrid[0:8, 0:64].astype(np.float32)
-    out = cubic_def.remap_cubic(step, xx / 8.0, yy * 0 + 4)
+    out = wd.remap(step, xx / 8.0, yy * 0 + 4, "cubic")
     assert out.min() == 0 and out.max() == 255
 
 
@@ -89,22 +87,22 @@ def test_border_rule_per_tap():
     """A tap outside the source enters the blend as the border value; a footprint wholly outside gives the border value."""
     src = np.full((6, 6), 100, np.uint8)
     # footprint X - 1 .. X + 2 at X = -1: two columns outside (border 20), two inside (100); fx = fy = 0 -> the centre tap (column -1) alone
-    assert cubic_def.remap_cubic(src, np.array([[-1.0]], np.float32), np.array([[2.0]], np.float32), 20)[0, 0] == 20
-    assert cubic_def.remap_cubic(src, np.array([[0.0]], np.float32), np.array([[2.0]], np.float32), 20)[0, 0] == 100
+    assert wd.remap(src, np.array([[-1.0]], np.float32), np.array([[2.0]], np.float32), "cubic", wd.CONSTANT, 20)[0, 0] == 20
+    assert wd.remap(src, np.array([[0.0]], np.float32), np.array([[2.0]], np.float32), "cubic", wd.CONSTANT, 20)[0, 0] == 100
     # half a pixel left of the source: the blend of border and source per the table's weights
-    w = cubic_def.cubic_table()[16].sum(axis=0)   # fx = 16, fy = 0: column weights
+    w = wd.cubic_table()[16].sum(axis=0)   # fx = 16, fy = 0: column weights
     exp = (int(w[0] * 20 + w[1] * 20 + w[2] * 100 + w[3] * 100) + (1 << 14)) >> 15
-    assert cubic_def.remap_cubic(src, np.array([[-0.5]], np.float32), np.array([[2.0]], np.float32), 20)[0, 0] == exp
+    assert wd.remap(src, np.array([[-0.5]], np.float32), np.array([[2.0]], np.float32), "cubic", wd.CONSTANT, 20)[0, 0] == exp
     for far in (-3.0, 8.0, 40.0):
-        assert cubic_def.remap_cubic(src, np.array([[far]], np.float32), np.array([[2.0]], np.float32), 20)[0, 0] == 20
+        assert wd.remap(src, np.array([[far]], np.float32), np.array([[2.0]], np.float32), "cubic", wd.CONSTANT, 20)[0, 0] == 20
 
 
 def test_nan_and_huge_entries_give_the_border():
     src = np.full((5, 5, 2), 9, np.uint8)
     vals = np.array([[np.nan, np.inf, -np.inf, 1e9, -1e9, 3e9, -3e9]], np.float32)
-    out = cubic_def.remap_cubic(src, vals, np.full_like(vals, 2.0), (128, 77))
+    out = wd.remap(src, vals, np.full_like(vals, 2.0), "cubic", wd.CONSTANT, (128, 77))
     assert (out[..., 0] == 128).all() and (out[..., 1] == 77).all()
-    out = cubic_def.remap_cubic(src, np.full_like(vals, 2.0), vals, (128, 77))
+    out = wd.remap(src, np.full_like(vals, 2.0), vals, "cubic", wd.CONSTANT, (128, 77))
     assert (out[..., 0] == 128).all() and (out[..., 1] == 77).all()
 
 
@@ -119,7 +117,7 @@ def test_cubic_matches_opencv_when_present():
         mx[::7, ::5] = np.floor(mx[::7, ::5] * 32 + 0.5) / 32 + 1.0 / 64   # ties
         bv = (border,) * 4 if np.isscalar(border) else tuple(border) + (0,) * (4 - len(border))
         exp = cv2.remap(src, mx, my, cv2.INTER_CUBIC, borderMode=cv2.BORDER_CONSTANT, borderValue=bv)
-        assert np.array_equal(cubic_def.remap_cubic(src, mx, my, border), exp), cn
+        assert np.array_equal(wd.remap(src, mx, my, "cubic", wd.CONSTANT, border), exp), cn
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,13 +1,13 @@
 """GPU parity of the bicubic resampler (cv::remap INTER_CUBIC; include/vstab.h "Bicubic resampling") through the C ABI and the pipeline
 object: vstab_remap_cubic, vstab_warp_nv12_cubic (BGR8 and plane-wise NV12) and vstab_config.resample.  Bar: every byte equals the numpy
-definition (tests/cubic_def.py) fed by the oracle's maps -- the reference kernel's own map, run on this GPU, for VSTAB_MAP_CREATEMAP_CL_OPENCL."""
+definition (tests/warp_def.py) fed by the oracle's maps -- the reference kernel's own map, run on this GPU, for VSTAB_MAP_CREATEMAP_CL_OPENCL."""
 import numpy as np
 import pytest
 
-import cubic_def
 import expect
 import oracle
 import synth
+import warp_def as wd
 
 pytestmark = pytest.mark.gpu
 
@@ -51,7 +51,7 @@ def test_remap_cubic_matches_definition(vs, cuda):
             dw, dh = (71, 33) if sw < 100 else (333, 190)
             mx, my = special_maps(rng, sw, sh, dw, dh)
             got = gpu_remap(vs, cuda, src, mx, my, border)
-            exp = cubic_def.remap_cubic(src, mx, my, border)
+            exp = wd.remap(src, mx, my, "cubic", wd.CONSTANT, border)
             assert np.array_equal(got, exp), (sw, sh, cn, int((got != exp).sum()))
 
 
@@ -99,11 +99,11 @@ def run_planar(vs, cuda, f, p, dw, dh, mode, pad=0):
 
 def check(vs, cuda, f, p, dw, dh, mode, pad=0, planar=True):
     got = run_bgr(vs, cuda, f, p, dw, dh, mode, pad)
-    exp = cubic_def.warp_nv12_cubic(f, p, dw, dh, mode)
+    exp = wd.bgr(f, *wd.maps(p, dw, dh, mode), "cubic")
     assert np.array_equal(got, exp), ("bgr", mode, dw, dh, int((got != exp).sum()))
     if planar:
         gy, guv = run_planar(vs, cuda, f, p, dw, dh, mode, pad)
-        ey, euv = cubic_def.warp_nv12_planar_cubic(f, p, dw, dh, mode)
+        ey, euv = wd.planar(f, *wd.maps(p, dw, dh, mode), "cubic")
         assert np.array_equal(gy, ey), ("luma", mode, dw, dh, int((gy != ey).sum()))
         assert np.array_equal(guv, euv), ("chroma", mode, dw, dh, int((guv != euv).sum()))
 
@@ -156,8 +156,8 @@ def test_warp_cubic_unaligned_and_pitched_planes(vs, cuda):
     w, h = 320, 180
     f = synth.nv12(31, w, h)
     p, dw, dh = cams(w, h, ROTS[1])
-    exp_bgr = cubic_def.warp_nv12_cubic(f, p, dw, dh, 0)
-    ey, euv = cubic_def.warp_nv12_planar_cubic(f, p, dw, dh, 0)
+    exp_bgr = wd.bgr(f, *wd.maps(p, dw, dh, 0), "cubic")
+    ey, euv = wd.planar(f, *wd.maps(p, dw, dh, 0), "cubic")
     # separate planes through the C ABI: luma at offset 1, pitch w + 37; chroma at offset 6, pitch w + 14
     py, puv = w + 37, w + 14
     ybuf = torch.zeros(h * py + 64, dtype=torch.uint8, device=cuda)
@@ -264,10 +264,10 @@ def test_pipeline_cubic_frames(vs, cuda, clip, tracking):
             assert np.array_equal(stab.warp_rotation(i), ref.warp_rotation(i)), (how, i)   # rotations are the bilinear handle's
             p = oracle.map_params(K, Ko, stab.warp_rotation(i))
             if how == "planar":
-                ey, euv = cubic_def.warp_nv12_planar_cubic(frames[i + 1], p, cw, ch, 0)
+                ey, euv = wd.planar(frames[i + 1], *wd.maps(p, cw, ch, 0), "cubic")
                 assert np.array_equal(o[0], ey) and np.array_equal(o[1], euv), (how, tracking, i)
             else:
-                assert np.array_equal(o, cubic_def.warp_nv12_cubic(frames[i + 1], p, cw, ch, 0)), (how, tracking, i)
+                assert np.array_equal(o, wd.bgr(frames[i + 1], *wd.maps(p, cw, ch, 0), "cubic")), (how, tracking, i)
 
 
 def test_pipeline_cubic_default_precision(vs, cuda, clip):
@@ -278,7 +278,7 @@ def test_pipeline_cubic_default_precision(vs, cuda, clip):
     stab, outs = pulls(vs, cuda, frames[:6], "pull", smooth_radius=2, tracking=0, resample=vs.RESAMPLE_CUBIC)
     for i in (0, len(outs) - 1):
         p = oracle.map_params(K, Ko, stab.warp_rotation(i))
-        assert np.array_equal(outs[i], cubic_def.warp_nv12_cubic(frames[i + 1], p, cw, ch, 5)), i
+        assert np.array_equal(outs[i], wd.bgr(frames[i + 1], *wd.maps(p, cw, ch, 5), "cubic")), i
 
 
 def test_pipeline_cubic_lens_mode(vs, cuda, clip):
@@ -288,7 +288,7 @@ def test_pipeline_cubic_lens_mode(vs, cuda, clip):
     Kout = oracle.lens_camera(oracle.PROJ_RECT, 110.0, 480, 270)
     for i in (0, len(outs) - 1):
         p = oracle.map_params(stab.K_in, Kout, stab.warp_rotation(i))
-        assert np.array_equal(outs[i], cubic_def.warp_nv12_cubic(frames[i + 1], p, 480, 270, oracle.MAP_FISH_TO_RECT)), i
+        assert np.array_equal(outs[i], wd.bgr(frames[i + 1], *wd.maps(p, 480, 270, oracle.MAP_FISH_TO_RECT), "cubic")), i
 
 
 def test_pipeline_cubic_refusals(vs, cuda, clip):

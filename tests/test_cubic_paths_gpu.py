@@ -1,7 +1,7 @@
-"""Every path of the bicubic kernels (vstab_warp_cubic.hip) against the numpy definition (tests/cubic_def.py), byte for byte, with
+"""Every path of the bicubic kernels (vstab_warp_cubic.hip) against the numpy definition (tests/warp_def.py), byte for byte, with
 canary bands above, below and right of every output plane (tests/layouts.py):
-  - the tile sets of tests/test_cubic_tiles_cpu.py, whose model proves the luma / chroma / BGR tiles they gather, stage at exactly
-    the LDS budget and one element over it, both output formats;
+  - the tile sets of tests/warp_tiles.py (TILE_SETS["cubic"]; tests/test_cubic_tiles_cpu.py), whose model proves the luma / chroma / BGR
+    tiles they gather, stage at exactly the LDS budget and one element over it, both output formats;
   - the seven plane layouts of the layout matrix;
   - source and output planes whose row offsets pass 2^32 bytes;
   - the pipeline's cubic pulls: decoder-style, host-memory and DMA-BUF frames, the host and peek pulls, repeated parameters;
@@ -11,12 +11,12 @@ import ctypes
 import numpy as np
 import pytest
 
-import cubic_def
 import expect
 import layouts
 import oracle
 import synth
-from test_cubic_tiles_cpu import TILE_SETS, set_params
+import warp_def as wd
+import warp_tiles as wt
 from test_layouts_gpu import PITCH_UV_4G, run_pipeline
 
 pytestmark = pytest.mark.gpu
@@ -42,16 +42,16 @@ def modes_of(mode):
 
 def check_cubic(vs, cuda, s, f, p, dw, dh, mode, what, out_bgr=None, out_planar=None):
     """BGR and plane-wise cubic warps of Src s (packed NV12 f on the host) against the definition."""
-    eq(layouts.warp_nv12_cubic(vs, s, p, dw, dh, mode, vs.OUT_BGR8, cuda, out_bgr), cubic_def.warp_nv12_cubic(f, p, dw, dh, mode), (what, "bgr", mode))
+    eq(layouts.warp_nv12_cubic(vs, s, p, dw, dh, mode, vs.OUT_BGR8, cuda, out_bgr), wd.bgr(f, *wd.maps(p, dw, dh, mode), "cubic"), (what, "bgr", mode))
     gy, guv = layouts.warp_nv12_cubic(vs, s, p, dw, dh, mode, vs.OUT_NV12_PLANAR, cuda, out_planar)
-    ey, euv = cubic_def.warp_nv12_planar_cubic(f, p, dw, dh, mode)
+    ey, euv = wd.planar(f, *wd.maps(p, dw, dh, mode), "cubic")
     eq(gy, ey, (what, "luma", mode)), eq(guv, euv, (what, "chroma", mode))
 
 
 # ---- the tile sets: staged, gathered, at the budget and over it -----------------------------------------------------------------
-@pytest.mark.parametrize("name", sorted(TILE_SETS))
+@pytest.mark.parametrize("name", sorted(wt.TILE_SETS["cubic"]))
 def test_cubic_tile_sets(vs, cuda, name):
-    p, sw, sh, dw, dh, mode = set_params(name)
+    p, sw, sh, dw, dh, mode = wt.set_params("cubic", name)
     f = synth.nv12(sum(map(ord, name)), sw, sh, full_range=True)
     s = layouts.place(f[:sh], f[sh:], "packed", cuda)
     for m in modes_of(mode):
@@ -69,7 +69,7 @@ def test_cubic_every_layout(vs, cuda, name, cam):
         p, dw, dh, _, _ = cams(w, h)
         mode = 0
     else:
-        p, w, h, dw, dh, mode = set_params(cam)
+        p, w, h, dw, dh, mode = wt.set_params("cubic", cam)
     f = synth.nv12(21, w, h)
     s = layouts.place(f[:h], f[h:], name, cuda)
     for m in modes_of(mode):
@@ -107,7 +107,7 @@ def frames_4g():
     rows = np.arange(H4 // 2, dtype=np.uint16)[:, None]
     f[H4:] = ((f[H4:].astype(np.uint16) + 37 * rows) % 256).astype(np.uint8)
     p, dw, dh, K, Ko = cams(W4, H4)
-    pg, sw, sh, gw, gh, _ = set_params("gather_540")
+    pg, sw, sh, gw, gh, _ = wt.set_params("cubic", "gather_540")
     assert (sw, sh) == (W4, H4)
     return f, [(p, dw, dh, "staged"), (pg, gw, gh, "gathered")], K, Ko
 
@@ -128,9 +128,9 @@ def _pipeline_4g(vs, cuda, s, f, K, Ko, what):
                 p = oracle.map_params(K, Ko, R)
                 ch, cw = (o.shape[:2] if pulls == "bgr" else o[0].shape)
                 if pulls == "bgr":
-                    eq(o, cubic_def.warp_nv12_cubic(f, p, cw, ch, 0), (what, "pipeline", hold, i))
+                    eq(o, wd.bgr(f, *wd.maps(p, cw, ch, 0), "cubic"), (what, "pipeline", hold, i))
                 else:
-                    ey, euv = cubic_def.warp_nv12_planar_cubic(f, p, cw, ch, 0)
+                    ey, euv = wd.planar(f, *wd.maps(p, cw, ch, 0), "cubic")
                     eq(o[0], ey, (what, "pipeline y", hold, i)), eq(o[1], euv, (what, "pipeline uv", hold, i))
 
 
@@ -181,12 +181,12 @@ def test_cubic_output_plane_past_4_gib(vs, cuda, plane):
         cw2, ch2 = 2 * ((dw + 1) // 2), (dh + 1) // 2
         if plane == "bgr":
             o = _plane_past_4g(dh, 3 * dw, cuda)
-            eq(layouts.warp_nv12_cubic(vs, s, p, dw, dh, 0, vs.OUT_BGR8, cuda, o), cubic_def.warp_nv12_cubic(f, p, dw, dh, 0), (plane, label))
+            eq(layouts.warp_nv12_cubic(vs, s, p, dw, dh, 0, vs.OUT_BGR8, cuda, o), wd.bgr(f, *wd.maps(p, dw, dh, 0), "cubic"), (plane, label))
         else:
             o = (_plane_past_4g(dh, dw, cuda), layouts.Plane(ch2, cw2, cuda)) if plane == "luma" else \
                 (layouts.Plane(dh, dw, cuda), _plane_past_4g(ch2, cw2, cuda))
             gy, guv = layouts.warp_nv12_cubic(vs, s, p, dw, dh, 0, vs.OUT_NV12_PLANAR, cuda, o)
-            ey, euv = cubic_def.warp_nv12_planar_cubic(f, p, dw, dh, 0)
+            ey, euv = wd.planar(f, *wd.maps(p, dw, dh, 0), "cubic")
             eq(gy, ey, (plane, label, "luma")), eq(guv, euv, (plane, label, "chroma"))
         del o
         _release()
@@ -209,10 +209,10 @@ def expect_cubic(frames, K, Ko, outs, pulls, what):
         p = oracle.map_params(K, Ko, R)
         if pulls == "bgr":
             ch, cw = o.shape[:2]
-            eq(o, cubic_def.warp_nv12_cubic(frames[i + 1], p, cw, ch, 0), (what, i))
+            eq(o, wd.bgr(frames[i + 1], *wd.maps(p, cw, ch, 0), "cubic"), (what, i))
         else:
             ch, cw = o[0].shape
-            ey, euv = cubic_def.warp_nv12_planar_cubic(frames[i + 1], p, cw, ch, 0)
+            ey, euv = wd.planar(frames[i + 1], *wd.maps(p, cw, ch, 0), "cubic")
             eq(o[0], ey, (what, "y", i)), eq(o[1], euv, (what, "uv", i))
 
 
@@ -345,12 +345,12 @@ def test_pipeline_cubic_repeated_parameters(vs, cuda, clip):
             if pulls == "bgr":
                 a, b = a.cpu().numpy(), b.cpu().numpy()
                 eq(a, expect.warp(f, p, cw, ch, expect.IEEE), ("bilinear", i))
-                eq(b, cubic_def.warp_nv12_cubic(f, p, cw, ch, 0), ("cubic", i))
+                eq(b, wd.bgr(f, *wd.maps(p, cw, ch, 0), "cubic"), ("cubic", i))
                 assert not np.array_equal(a, b), i
             else:
                 ly, luv = expect.warp_planar(f, p, cw, ch, expect.IEEE)
                 eq(a[0].cpu().numpy(), ly, ("bilinear y", i)), eq(a[1].cpu().numpy(), luv, ("bilinear uv", i))
-                ey, euv = cubic_def.warp_nv12_planar_cubic(f, p, cw, ch, 0)
+                ey, euv = wd.planar(f, *wd.maps(p, cw, ch, 0), "cubic")
                 eq(b[0].cpu().numpy(), ey, ("cubic y", i)), eq(b[1].cpu().numpy(), euv, ("cubic uv", i))
                 assert not np.array_equal(ly, ey), i
             n += 1
@@ -407,7 +407,7 @@ def test_remap_cubic_pitched_maps_odd_source_canaried_outputs(vs, cuda):
         mxt, myt = pitched_map(mx, 5, cuda), pitched_map(my, 17, cuda)
         assert mxt.stride(0) != myt.stride(0)
         got = remap_c(vs, cuda, ptr, pitch, sw, sh, cn, mxt, myt, border, dw, dh)
-        eq(got, cubic_def.remap_cubic(src, mx, my, border), ("remap", cn))
+        eq(got, wd.remap(src, mx, my, "cubic", wd.CONSTANT, border), ("remap", cn))
         del keep
 
 
@@ -428,9 +428,9 @@ def test_remap_cubic_int16_saturation_edges(vs, cuda):
             dh, dw = mx.shape
             st = torch.from_numpy(src).to(cuda)
             got = remap_c(vs, cuda, st.data_ptr(), st.stride(0), sw, sh, cn, pitched_map(mx, 3, cuda), pitched_map(my, 0, cuda), border, dw, dh)
-            exp = cubic_def.remap_cubic(src, mx, my, border)
+            exp = wd.remap(src, mx, my, "cubic", wd.CONSTANT, border)
             eq(got, exp, ("saturation", cn, tall))
-            X, Y, _ = cubic_def.quantise(mx, my)
+            X, Y, _ = wd.quantise(mx, my)
             assert ((Y if tall else X) == 32767).sum() >= 2 * len(ys)   # the saturated taps are there, and inside the source (column / row 32766)
             ins = exp != (np.array(border[:cn], np.uint8) if cn > 1 else border[0])
             assert ins.any()

@@ -1,67 +1,24 @@
-"""CPU model of the cubic warp's tile boxes (tests/cubic_tiles.py: k_warp_cubic's box restated on the oracle's exact map).  It proves
+"""CPU model of the cubic warp's tile boxes (tests/warp_tiles.py, rule `touching`: k_warp_cubic's box restated on the oracle's exact map).  It proves
 that the parameter sets of the GPU tests (test_cubic_paths_gpu.py) reach every path of the kernel: luma / chroma / BGR tiles with no
 box, staged in LDS and gathered from global memory, boxes of exactly the LDS budget and just over it, partial tiles that stage, and
 staged boxes of odd and even width.  The model is exact (no margin): the counts below are what the kernel does, tile for tile."""
 import numpy as np
 import pytest
 
-import cubic_tiles
 import oracle
+import warp_def as wd
+import warp_tiles as wt
 
 
-def anamorphic(sw, sh, dw, dh, sx, sy, roll):
-    """Source focal lengths 100 sx / 100 sy against an output camera of focal length 100, both principal points centred, rolled
-    about the optical axis: the source box of a 64 x 16 tile is about 64 sx wide and 16 sy tall."""
-    Ki = np.array([[100.0 * sx, 0, sw / 2], [0, 100.0 * sy, sh / 2], [0, 0, 1]])
-    Ko = np.array([[100.0, 0, dw / 2], [0, 100.0, dh / 2], [0, 0, 1]])
-    return oracle.map_params(Ki, Ko, oracle.rodrigues((0.0, 0.0, roll)))
-
-
-# name: (sw, sh, dw, dh, sx, sy, roll, map mode, {plane: {state: count}}) -- the counts each set is committed to reach.
-#   (a) BGR gathered               bgr_at_budget, luma_gathers, all_states, all_gather
-#   (b) luma gathered, chroma staged in the same launch              luma_at_budget, luma_gathers
-#   (c) luma and chroma gathered                                     all_states, all_gather
-#   (d) a box of exactly the budget: bgr_at_budget(_m0), luma_at_budget(_m0), chroma_at_budget; one element over it:
-#       bgr_over_by_one, chroma_over_by_one.  Luma's budget + 1 = 12289 is prime and a box is at least 4 x 4, so no box has it:
-#       luma_least_over has 12290 (5 x 2458), the least element count over the budget a box can have
-#   (e) no-box, staged and gathered tiles in one launch, every plane  all_states
-#   (f) partial right / bottom tiles (odd dw and dh) that stage       luma_gathers, all_states
-#   (g) odd and even staged widths, luma and chroma                   luma_gathers, all_states
-TILE_SETS = {
-    "bgr_at_budget": (4096, 256, 192, 48, 4.0, 1.3, 0.003, oracle.MAP_RECT_TO_RECT,
-                      {"bgr": {"at_budget": 5, "staged": 7, "gathered": 2}, "luma": {"gathered": 0}, "chroma": {"gathered": 0}}),
-    "bgr_at_budget_m0": (4096, 256, 192, 48, 4.13, 1.3, 0.003, 0, {"bgr": {"at_budget": 1, "gathered": 0}}),
-    "luma_at_budget": (4096, 256, 192, 48, 8.07, 1.3, 0.003, oracle.MAP_RECT_TO_RECT,
-                       {"bgr": {"gathered": 9}, "luma": {"at_budget": 2, "staged": 4, "gathered": 5}, "chroma": {"staged": 9, "gathered": 0}}),
-    "luma_at_budget_m0": (4096, 256, 192, 48, 8.33, 1.3, 0.003, 0, {"bgr": {"gathered": 9}, "luma": {"at_budget": 1, "gathered": 0}}),
-    "luma_gathers": (4096, 256, 767, 47, 12.0, 1.3, 0.003, 0,
-                     {"bgr": {"staged": 24, "gathered": 12}, "luma": {"staged": 30, "gathered": 6, "partial_staged": 12, "odd_w": 11, "even_w": 19},
-                      "chroma": {"staged": 36, "gathered": 0, "partial_staged": 14, "odd_w": 21, "even_w": 15}}),
-    "all_states": (4096, 256, 1023, 47, 16.0, 2.0, 0.003, 0,
-                   {"bgr": {"none": 12, "staged": 18, "gathered": 18, "partial_staged": 6},
-                    "luma": {"none": 12, "staged": 24, "gathered": 12, "partial_staged": 8, "odd_w": 11, "even_w": 13},
-                    "chroma": {"none": 12, "staged": 30, "gathered": 6, "partial_staged": 10, "odd_w": 10, "even_w": 20}}),
-    "all_gather": (4096, 256, 192, 48, 16.0, 3.0, 0.003, 0, {"bgr": {"gathered": 9}, "luma": {"gathered": 9}, "chroma": {"gathered": 9}}),
-    "chroma_at_budget": (64, 4096, 64, 32, 0.26, 72.9, 0.0, 0, {"luma": {"gathered": 2}, "chroma": {"at_budget": 1, "staged": 2}}),
-    "bgr_over_by_one": (64, 4096, 64, 32, 0.02, 82.25, 0.0, 0, {"bgr": {"over_by_one": 1, "staged": 1, "gathered": 1}, "luma": {"staged": 2}}),
-    "luma_least_over": (64, 8192, 64, 32, 0.02, 164.85, 0.0, 0, {"luma": {"gathered": 2, "least_over": 2}, "chroma": {"staged": 2}}),
-    "chroma_over_by_one": (64, 8192, 64, 32, 0.02, 175.9, 0.0, 0, {"chroma": {"over_by_one": 1, "staged": 1, "gathered": 1}}),
-    # the gathered set of the 4 GiB tests (their 640 x 540 frame)
-    "gather_540": (640, 540, 256, 160, 4.0, 8.0, 0.003, 0,
-                   {"bgr": {"none": 16, "staged": 0, "gathered": 24}, "luma": {"none": 16, "staged": 15, "gathered": 9},
-                    "chroma": {"none": 16, "staged": 16, "gathered": 8}}),
-}
-
-
-def set_params(name):
-    """-> (params, sw, sh, dw, dh, mode) of a TILE_SETS entry."""
-    sw, sh, dw, dh, sx, sy, roll, mode, _ = TILE_SETS[name]
-    return anamorphic(sw, sh, dw, dh, sx, sy, roll), sw, sh, dw, dh, mode
+TILE_SETS = wt.TILE_SETS["cubic"]
 
 
 def states(name):
-    p, sw, sh, dw, dh, mode = set_params(name)
-    return cubic_tiles.states_of(p, dw, dh, sw, sh, mode)
+    return wt.states_of("cubic", name)
+
+
+def states_of(params, dw, dh, sw, sh, mode):
+    return wt.tile_states(*wd.maps(params, dw, dh, mode), sw, sh, "cubic", "touching")
 
 
 @pytest.mark.parametrize("name", sorted(TILE_SETS))
@@ -95,13 +52,13 @@ def test_preset_camera_of_the_4_gib_frame_stages_every_tile():
     """The staged set of the 4 GiB tests: the preset camera on their 640 x 540 frame gathers no tile."""
     K = oracle.get_preset_camera(4, 640, 540)
     Ko, (dw, dh) = oracle.get_output_camera(K, 640, 540)
-    s = cubic_tiles.states_of(oracle.map_params(K, Ko, oracle.rodrigues((0.02, -0.03, 0.01))), dw, dh, 640, 540, 0)
+    s = states_of(oracle.map_params(K, Ko, oracle.rodrigues((0.02, -0.03, 0.01))), dw, dh, 640, 540, 0)
     assert all(s[p]["gathered"] == 0 and s[p]["staged"] > 0 for p in s), s
 
 
 def test_luma_budget_plus_one_has_no_box():
     """12289 elements: prime, so only a 1-wide or 1-tall box could have it; every box is at least 4 x 4."""
-    n = cubic_tiles.BUDGET["luma"] + 1
+    n = wt.BUDGET["luma"] + 1
     assert all(n % d for d in range(2, int(n ** 0.5) + 1))
 
 
@@ -114,7 +71,7 @@ def test_model_counts_of_the_existing_gpu_tests():
     mode = oracle.map_mode(oracle.PROJ_RECT, oracle.PROJ_FISH)
     got = []
     for rv in [(0.02, -0.03, 0.01), (-0.15, 0.1, 0.3), (0.0, 1.2, 0.0)]:
-        s = cubic_tiles.states_of(oracle.map_params(Kin, Kout, oracle.rodrigues(rv)), dw, dh, w, h, mode)
+        s = states_of(oracle.map_params(Kin, Kout, oracle.rodrigues(rv)), dw, dh, w, h, mode)
         got.append((s["luma"]["gathered"], s["chroma"]["gathered"]))
     assert got == [(11, 0), (18, 6), (11, 0)], got
     for sw, sh, dw, dh, sx, sy, bgr_gathers in [(2048, 32, 128, 64, 15.0, 0.25, 8), (64, 1024, 128, 64, 0.125, 15.0, 0),
@@ -122,7 +79,7 @@ def test_model_counts_of_the_existing_gpu_tests():
         Ki = np.array([[100.0 * sx, 0, sw / 2], [0, 100.0 * sy, sh / 2], [0, 0, 1]])
         Ko = np.array([[100.0, 0, dw / 2], [0, 100.0, dh / 2], [0, 0, 1]])
         for rot in [(0.0, 0.0, 0.0), (0.0, 0.0, 0.002)]:
-            s = cubic_tiles.states_of(oracle.map_params(Ki, Ko, oracle.rodrigues(rot)), dw, dh, sw, sh, oracle.MAP_RECT_TO_RECT)
+            s = states_of(oracle.map_params(Ki, Ko, oracle.rodrigues(rot)), dw, dh, sw, sh, oracle.MAP_RECT_TO_RECT)
             assert s["bgr"]["gathered"] == bgr_gathers and s["luma"]["gathered"] == 0 and s["chroma"]["gathered"] == 0, (sw, sh, rot, s)
 
 
@@ -132,10 +89,10 @@ def test_model_box_is_the_footprint_extremes():
     mx = np.full((16, 70), 10.5, np.float32)
     my = np.full((16, 70), 7.0, np.float32)
     mx[5, 3], my[5, 3] = 40.25, 7.0          # odd column: luma only
-    x0, y0, bw, bh, have = (a[0, 0] for a in cubic_tiles.tile_boxes(mx, my, 100, 100)["luma"])
+    x0, y0, bw, bh, have = (a[0, 0] for a in wt.tile_boxes(mx, my, 100, 100, "cubic", "touching")["luma"])
     assert have and (x0, y0, bw, bh) == (9, 6, 34, 4)
-    x0, y0, bw, bh, have = (a[0, 0] for a in cubic_tiles.tile_boxes(mx, my, 100, 100)["chroma"])
+    x0, y0, bw, bh, have = (a[0, 0] for a in wt.tile_boxes(mx, my, 100, 100, "cubic", "touching")["chroma"])
     assert have and (x0, y0, bw, bh) == (4, 2, 4, 4)    # 0.5 * (10.5, 7.0) -> (5, 3) after quantisation, X - 1 .. X + 2
     mx[:, 64:] = 1e6                         # the second tile column holds x = 64 .. 69: all outside
-    s = cubic_tiles.tile_states(mx, my, 100, 100)
+    s = wt.tile_states(mx, my, 100, 100, "cubic", "touching")
     assert s["luma"]["none"] == 1 and s["luma"]["staged"] == 1 and s["luma"]["partial_staged"] == 0

@@ -2,8 +2,8 @@
 vstab_set_input_calibration_ex): the refusals as a table in the style of test_distort_refusals_cpu.py (every distinct message, calls that
 break two checks at once -- the earlier check's message wins, which pins the documented order --, every call refused before any device
 work: the device pointers are a dummy address), the unchanged ABI, the tile states the GPU tests' shapes are there for (from the committed
-CPU models of the kernels' boxes over the distorted maps), the golden file against the definition, and the new kernels' private segments
-against their siblings' (from the built library's kernel metadata)."""
+CPU model of the kernels' boxes, tests/warp_tiles.py, over the distorted maps), the golden file against the definition, and the new
+kernels' private segments against their siblings' (from the built library's kernel metadata)."""
 import ctypes
 import os
 import re
@@ -15,8 +15,9 @@ import numpy as np
 import pytest
 
 import distort_def as dd
-import distort_resample_def as drd
 import oracle
+import warp_def as wd
+import warp_tiles as wt
 from test_distort_gpu import cameras
 from test_distort_refusals_cpu import BGR8, D_BAD, DD, DF, FISH, FOLD, FP, INVALID, K9, M16, NV12, OTHER_MODES, P, PLANAR, f32, f64
 from test_lens_gpu import ROTS
@@ -125,7 +126,7 @@ def shape_maps(w, h, dw, dh, mode, rv, D=dd.D_A):
     return dd.maps(oracle.map_params(Kin, Kout, oracle.rodrigues(rv)), dw, dh, mode, D)
 
 
-KERNELS = [(r, b) for r in drd.RESAMPLERS for b in (drd.CONSTANT, drd.REFLECT_101) if (r, b) != ("linear", drd.CONSTANT)]
+KERNELS = [(r, b) for r in wd.RESAMPLERS for b in (wd.CONSTANT, wd.REFLECT_101) if (r, b) != ("linear", wd.CONSTANT)]
 PLANES = ("bgr", "luma", "chroma")
 
 
@@ -133,18 +134,18 @@ def test_tile_states_640x360_every_tile_staged_partial_tiles_and_crossings():
     w, h, dw, dh = 640, 360, 333, 201
     mx, my = shape_maps(w, h, dw, dh, 1, ROTS[1])
     for r, b in KERNELS:
-        st = drd.tile_states(r, mx, my, w, h, b)
+        st = wt.tile_states(mx, my, w, h, r, wt.kernel_rule(r, b))
         for pl in PLANES:
             s = st[pl]
             assert s["staged"] == 78 and s["gathered"] == 0 and s["odd_w"] > 0 and s["even_w"] > 0, (r, b, pl, s)
-            if b == drd.CONSTANT:
+            if b == wd.CONSTANT:
                 assert s["none"] == 0 and s["partial_staged"] == 18, (r, b, pl, s)
     mx, my = shape_maps(w, h, dw, dh, 2, ROTS[1])
     for r, b in KERNELS:
-        st = drd.tile_states(r, mx, my, w, h, b)
+        st = wt.tile_states(mx, my, w, h, r, wt.kernel_rule(r, b))
         s = st["bgr"]
         assert s["gathered"] == 0
-        if b == drd.CONSTANT:
+        if b == wd.CONSTANT:
             assert s["none"] > 0 and s["staged"] > 0 and s["partial_staged"] > 0, (r, s)       # tiles with no box beside staged ones
         else:
             assert s["outside_staged"] > 0 and min(s["cross_l"], s["cross_r"], s["cross_t"], s["cross_b"]) > 0, (r, s)
@@ -156,16 +157,16 @@ def test_tile_states_1024x576_staged_and_gathered_in_one_launch():
     w, h, dw, dh = 1024, 576, 200, 72
     mx, my = shape_maps(w, h, dw, dh, 1, ROTS[1])
     for r, b in KERNELS:
-        st = drd.tile_states(r, mx, my, w, h, b)
+        st = wt.tile_states(mx, my, w, h, r, wt.kernel_rule(r, b))
         for pl in PLANES:
             assert st[pl]["staged"] > 0 and st[pl]["gathered"] > 0, (r, b, pl, st[pl])
         assert st["bgr"]["staged"] + st["bgr"]["gathered"] == 20
     mx, my = shape_maps(w, h, dw, dh, 2, ROTS[1])
     for r, b in KERNELS:
-        st = drd.tile_states(r, mx, my, w, h, b)
+        st = wt.tile_states(mx, my, w, h, r, wt.kernel_rule(r, b))
         for pl in PLANES:
             assert st[pl]["gathered"] > 0, (r, b, pl, st[pl])
-            if b == drd.CONSTANT:
+            if b == wd.CONSTANT:
                 assert st[pl]["none"] > 0, (r, pl, st[pl])         # mode 2 adds tiles with no box
             else:
                 assert st[pl]["staged"] > 0 and st[pl]["outside_staged"] > 0, (r, pl, st[pl])
@@ -177,7 +178,7 @@ def test_tile_states_2048x1152_every_tile_gathers():
     for mode in (1, 2):
         mx, my = shape_maps(w, h, dw, dh, mode, ROTS[1])
         for r, b in KERNELS:
-            st = drd.tile_states(r, mx, my, w, h, b)
+            st = wt.tile_states(mx, my, w, h, r, wt.kernel_rule(r, b))
             for pl in PLANES:
                 assert st[pl]["staged"] == 0 and st[pl]["gathered"] == 32 and st[pl].get("none", 0) == 0, (mode, r, b, pl, st[pl])
 
@@ -192,14 +193,14 @@ def test_tile_states_nan_third_of_the_map():
         mixed, all_nan = sum(bool(t.any() and not t.all()) for t in tiles), sum(bool(t.all()) for t in tiles)
         assert mixed > 0 and all_nan > 0
         for r, b in KERNELS:
-            st = drd.tile_states(r, mx, my, w, h, b)
+            st = wt.tile_states(mx, my, w, h, r, wt.kernel_rule(r, b))
             for pl in PLANES:
                 s = st[pl]
-                if b == drd.CONSTANT:       # a NaN entry quantises to (-32768, -32768): it touches nothing and stays out of the box
+                if b == wd.CONSTANT:       # a NaN entry quantises to (-32768, -32768): it touches nothing and stays out of the box
                     assert s["gathered"] == 0 and s["none"] > 0 and s["staged"] > 0, (mode, r, pl, s)
                 else:                       # every footprint counts: the box of a tile that holds a NaN entry beside a number reaches -32768
                     assert s["gathered"] > 0 and s["staged"] > 0, (mode, r, pl, s)
-            if b != drd.CONSTANT:           # (a tile of NaN entries alone has a small box at -32768: staged, wholly outside)
+            if b != wd.CONSTANT:           # (a tile of NaN entries alone has a small box at -32768: staged, wholly outside)
                 assert st["bgr"]["gathered"] == mixed and st["bgr"]["outside_staged"] == all_nan, (mode, r, st["bgr"])
 
 

@@ -1,6 +1,6 @@
 """GPU tests of the calibrated lens in the cubic, Lanczos and border warps (include/vstab.h, vstab_warp_nv12_dist_ex and
 vstab_set_input_calibration_ex): every byte, BGR and plane-wise, against the numpy definition -- the distorted map (tests/distort_def.py)
-fed to the resampler's own definition (tests/distort_resample_def.py) --, against the entry points the new one must agree with, and
+fed to the resampler's own definition (tests/warp_def.py) --, against the entry points the new one must agree with, and
 against the route it replaces (vstab_create_map_dist + a stateless vstab_remap_*).  Shapes: the smallest that reach the tile states
 test_distort_resample_cpu.py asserts for them (all staged with partial tiles and edge crossings; staged and gathered in one launch; every
 tile gathered; a third of the map NaN), a source plane off its alignment, a 16 x 2 source, and a calibrated handle through every pull."""
@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 
 import distort_def as dd
-import distort_resample_def as drd
 import layouts
 import oracle
 import synth
+import warp_def as wd
 from test_border_gpu import pulls
 from test_distort_gpu import H, K_CAL, LENS, OH, OW, W, cameras, dev, refused
 from test_lens_gpu import ROTS
@@ -22,8 +22,8 @@ from test_lens_gpu import ROTS
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-RESAMPLERS, RESAMPLE, BORDERS = drd.RESAMPLERS, drd.RESAMPLE, drd.BORDERS
-CONSTANT, REPLICATE, REFLECT, REFLECT_101 = drd.CONSTANT, drd.REPLICATE, drd.REFLECT, drd.REFLECT_101
+RESAMPLERS, RESAMPLE, BORDERS = wd.RESAMPLERS, wd.RESAMPLE, wd.MODES
+CONSTANT, REPLICATE, REFLECT, REFLECT_101 = wd.CONSTANT, wd.REPLICATE, wd.REFLECT, wd.REFLECT_101
 
 
 def eq(got, exp, what):
@@ -44,10 +44,10 @@ class Case:
         self.mx, self.my = dd.maps(self.p, dw, dh, mode, D)
 
     def bgr(self, resampler, border):
-        return drd.remap_bgr(resampler, self.f, self.mx, self.my, border)
+        return wd.bgr(self.f, self.mx, self.my, resampler, border)
 
     def planar(self, resampler, border):
-        return drd.remap_planar(resampler, self.f, self.mx, self.my, border)
+        return wd.planar(self.f, self.mx, self.my, resampler, border)
 
     def check(self, vs, fd, resampler, border, what=None):
         """Both output formats of vstab_warp_nv12_dist_ex (through the binding, packed source fd) against the definition."""
@@ -81,7 +81,7 @@ def test_every_resampler_border_and_mode(vs, cuda, resampler, mode):
     zx, zy = dd.maps(c.p, dw, dh, mode, dd.D_0)
     for border in BORDERS:
         got = c.check(vs, fd, resampler, border, "all").cpu().numpy()
-        plain = drd.remap_bgr(resampler, c.f, zx, zy, border)                     # the D = 0 frame
+        plain = wd.bgr(c.f, zx, zy, resampler, border)                     # the D = 0 frame
         assert (got != 0).mean() >= 0.1, ("black", resampler, border, mode)
         assert (got != plain).any(axis=-1).mean() >= 0.5, ("the distortion moved too few pixels", resampler, border, mode)
         eq(stateless_bgr(vs, fd, c, resampler, border).cpu().numpy(), got, ("stateless route", resampler, border, mode))
@@ -278,10 +278,10 @@ def still_maps():
 def expect_pull(still_maps, f, resampler, border, out, how, what):
     mx, my = still_maps
     if how == "planar":
-        ey, ec = drd.remap_planar(resampler, f, mx, my, border)
+        ey, ec = wd.planar(f, mx, my, resampler, border)
         eq(out[0], ey, (what, "luma")), eq(out[1], ec, (what, "chroma"))
     else:
-        eq(out, drd.remap_bgr(resampler, f, mx, my, border), what)
+        eq(out, wd.bgr(f, mx, my, resampler, border), what)
 
 
 @pytest.mark.parametrize("how", ["pull", "frames", "host", "peek", "planar"])
@@ -358,8 +358,7 @@ def test_pipeline_refusals_of_a_calibrated_handle(vs, cuda, still_clip, still_ma
     assert refused(vs, s.set_input_calibration_ex, bad_K, (-0.5, 0, 0, 0))[1] == SETX + "K must be a camera matrix with fx, fy > 0, zero skew and last row 0 0 1"
     Kin = oracle.lens_camera(oracle.PROJ_FISH, 150.0, W, H)
     Kout = oracle.lens_camera(oracle.PROJ_RECT, 110.0, OW, OH)
-    import resample_border_def as rbd
-    plain = rbd.warp_nv12("cubic", frames[1], oracle.map_params(Kin, Kout, np.eye(3)), OW, OH, 1, REFLECT_101)
+    plain = wd.bgr(frames[1], *wd.maps(oracle.map_params(Kin, Kout, np.eye(3)), OW, OH, 1), "cubic", REFLECT_101)
     eq(s.pull().cpu().numpy(), plain, "uncalibrated after the refusals")
     assert refused(vs, s.set_input_calibration_ex, K_CAL, dd.D_A) == (INV, SETX + "the calibration must be set before the first pull")
     s.close()
@@ -447,5 +446,5 @@ def test_pipeline_rotation_estimate_does_not_depend_on_the_resampler(vs, cuda):
     Kout = oracle.lens_camera(oracle.PROJ_RECT, 110.0, ow, oh)
     for i in (0, n - 2):
         p = oracle.map_params(K, Kout, b.warp_rotation(i))
-        eq(outs[i], drd.warp_bgr("cubic", frames[i + 1], p, ow, oh, 1, dd.D_A, REFLECT_101), ("tracked frame", i))
+        eq(outs[i], wd.bgr(frames[i + 1], *wd.maps(p, ow, oh, 1, None, dd.D_A), "cubic", REFLECT_101), ("tracked frame", i))
     a.close(), b.close()

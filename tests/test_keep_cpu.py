@@ -1,4 +1,4 @@
-"""CPU tests of the keep-edge warp's definition (tests/keep_def.py; include/vstab.h "Keep edges"), of the refusals of its two stateless entry
+"""CPU tests of the keep-edge warp's definition (tests/warp_def.py; include/vstab.h "Keep edges"), of the refusals of its two stateless entry
 points, and of the built kernels' resources.  The definition: a sample whose 2 x 2 footprint lies wholly inside the plane it reads has the
 bytes of the constant-border bilinear warp; every other sample is the caller's previous frame."""
 import ctypes
@@ -8,53 +8,39 @@ import re
 import numpy as np
 import pytest
 
-import border_def
-import cubic_def
 import expect
-import keep_def
 import oracle
 import synth
-
-GOLD = os.path.join(os.path.dirname(__file__), "golden", "keep_kat.npz")
+import warp_def as wd
+import warp_tiles as wt
 
 
 def golden_cases():
-    kat = np.load(GOLD)
-    k = 0
-    while f"case{k}_src" in kat:
-        yield k, kat[f"case{k}_src"], kat[f"case{k}_mapx"], kat[f"case{k}_mapy"], kat[f"case{k}_prev"], kat[f"case{k}_out"]
-        k += 1
+    return wd.golden_cases("keep_kat", "src", "mapx", "mapy", "prev", "out")
 
 
 def test_golden_remaps():
     n = kept = written = 0
     for k, src, mx, my, prev, out in golden_cases():
-        assert np.array_equal(keep_def.remap_keep(src, mx, my, prev), out), k
-        m = keep_def.written(mx, my, src.shape[1], src.shape[0])
+        assert np.array_equal(wd.remap(src, mx, my, "linear", wd.TRANSPARENT, 0, prev), out), k
+        m = wd.written(mx, my, src.shape[1], src.shape[0])
         kept, written, n = kept + int((~m).sum()), written + int(m.sum()), n + 1
     assert n == 9 and kept > 500 and written > 100     # (sources of width or height 1 write nothing)
 
 
-def _random_case(rng, cn, sw=31, sh=23, dw=29, dh=17):
-    src = rng.integers(0, 256, (sh, sw, cn) if cn > 1 else (sh, sw), dtype=np.uint8)
-    prev = rng.integers(0, 256, (dh, dw, cn) if cn > 1 else (dh, dw), dtype=np.uint8)
-    mx = rng.uniform(-0.4 * sw, 1.4 * sw, (dh, dw)).astype(np.float32)
-    my = rng.uniform(-0.4 * sh, 1.4 * sh, (dh, dw)).astype(np.float32)
-    mx[0, :5] = [np.nan, np.inf, -1e30, 32768.0, 3e9]
-    my[1, :3] = [np.nan, -3e9, 3e9]
-    return src, mx, my, prev
-
-
 def test_written_samples_are_the_constant_border_warp_and_kept_ones_are_prev():
-    rng = np.random.default_rng(6)
+    """The constant-border warps are what the bilinear border definition answered while it was a layer of its own, on inputs recorded with
+    them (tests/golden/warp_definitions_kat.npz, keep_c<cn>_*): random 23 x 31 sources and 17 x 29 maps with NaN, inf and out-of-range entries."""
+    kat = wd.golden("warp_definitions_kat")
     for cn in (1, 2, 3):
-        src, mx, my, prev = _random_case(rng, cn)
+        src, mx, my, prev = (kat[f"keep_c{cn}_{k}"] for k in ("src", "mapx", "mapy", "prev"))
+        assert src.shape[:2] == (23, 31) and prev.shape[:2] == mx.shape == (17, 29) and np.isnan(mx[0, 0]) and np.isnan(my[1, 0])
         before = prev.copy()
-        out = keep_def.remap_keep(src, mx, my, prev)
-        m = keep_def.written(mx, my, src.shape[1], src.shape[0])
+        out = wd.remap(src, mx, my, "linear", wd.TRANSPARENT, 0, prev)
+        m = wd.written(mx, my, src.shape[1], src.shape[0])
         assert 0.2 < m.mean() < 0.8
         for border in (0, 255):      # no border value enters a written sample
-            assert np.array_equal(out[m], border_def.remap_border(src, mx, my, border_def.CONSTANT, border)[m]), cn
+            assert np.array_equal(out[m], kat[f"keep_c{cn}_border{border}"][m]), cn
         assert np.array_equal(out[~m], prev[~m]) and np.array_equal(prev, before)
         if cn != 2:
             assert np.array_equal(out[m], oracle.remap_bilinear(src, mx, my)[m])
@@ -72,14 +58,15 @@ def test_warps_equal_the_pinned_warps_where_written():
     py = rng.integers(0, 256, (ch, cw), dtype=np.uint8)
     puv = rng.integers(0, 256, ((ch + 1) // 2, 2 * ((cw + 1) // 2)), dtype=np.uint8)
     for mode, r in [(m, None) for m in range(5)] + [(0, rb), (1, rb)]:
-        my_, mc = keep_def.masks(p, w, h, cw, ch, mode, r)
+        mx, my = wd.maps(p, cw, ch, mode, r)
+        my_, mc = wd.written(mx, my, w, h), wd.written(*oracle.chroma_maps(mx, my), w >> 1, h >> 1)
         assert 0.05 < my_.mean() < 0.98, mode
-        got = keep_def.warp_nv12_keep(frame, p, cw, ch, pb, mode, r)
+        got = wd.bgr(frame, mx, my, "linear", wd.TRANSPARENT, pb)
         ref = oracle.warp_nv12_ex(frame, p, cw, ch, mode, 0) if r is None else oracle.warp_nv12_rs(frame, p, r, cw, ch, mode, 0)
         assert np.array_equal(got[my_], ref[my_]) and np.array_equal(got[~my_], pb[~my_]), mode
         if mode == 0:
             assert np.array_equal(ref, expect.warp(frame, p, cw, ch, expect.IEEE, r))
-        gy, guv = keep_def.warp_nv12_planar_keep(frame, p, cw, ch, py, puv, mode, r)
+        gy, guv = wd.planar(frame, mx, my, "linear", wd.TRANSPARENT, py, puv)
         ey, euv = oracle.warp_nv12_planar(frame, p, cw, ch, mode, rot_bottom=r)
         assert np.array_equal(gy[my_], ey[my_]) and np.array_equal(gy[~my_], py[~my_]), mode
         pair = lambda a: a.reshape(a.shape[0], -1, 2)
@@ -88,18 +75,23 @@ def test_warps_equal_the_pinned_warps_where_written():
 
 @pytest.mark.parametrize("n", [2, 5, 64])
 def test_the_rule_at_the_edges(n):
-    """X = -1, 0, n - 2, n - 1 with and without a fraction, NaN, +-3e9: written iff 0 <= X <= n - 2, on either axis."""
+    """X = -1, 0, n - 2, n - 1 with and without a fraction, NaN, +-3e9: written iff 0 <= X <= n - 2, on either axis.  The written samples are
+    the constant-border warp's as the bilinear border definition answered them while it was a layer of its own
+    (tests/golden/warp_definitions_kat.npz, edges_n<n>_a<axis>_*, recorded with these inputs)."""
+    kat = wd.golden("warp_definitions_kat")
     src = np.arange(n * n, dtype=np.uint8).reshape(n, n)
     pos = np.array([-1.0, -0.5, -1 / 64, 0.0, 0.25, n - 2.0, n - 1.5, n - 1.0 - 1 / 32, n - 1.0, n - 0.5, np.nan, 3e9, -3e9, np.inf], np.float32)
     want = np.array([0, 0, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0], bool)   # -1/64 rounds to sx = 0 (half to even); n - 1 - 1/32 has X = n - 2
     inside = np.zeros(len(pos), np.float32)
     prev = np.full((1, len(pos)), 200, np.uint8)
-    for mx, my in ((pos[None], inside[None]), (inside[None], pos[None])):
-        assert np.array_equal(keep_def.written(mx, my, n, n)[0], want), n
-        out = keep_def.remap_keep(src, mx, my, prev)
+    for axis, (mx, my) in enumerate(((pos[None], inside[None]), (inside[None], pos[None]))):
+        k = f"edges_n{n}_a{axis}_"
+        assert all(np.array_equal(a, kat[k + name], equal_nan=True) for a, name in ((src, "src"), (mx, "mapx"), (my, "mapy"), (prev, "prev")))
+        assert np.array_equal(wd.written(mx, my, n, n)[0], want), n
+        out = wd.remap(src, mx, my, "linear", wd.TRANSPARENT, 0, prev)
         assert np.array_equal(out[0][~want], prev[0][~want])
-        assert np.array_equal(out[0][want], border_def.remap_border(src, mx, my, border_def.CONSTANT)[0][want])
-    X, _, _ = cubic_def.quantise(pos, pos)
+        assert np.array_equal(out[0][want], kat[k + "constant"][0][want])
+    X, _, _ = wd.quantise(pos, pos)
     assert X[10] == -32768 and X[11] == -32768 and X[12] == -32768      # NaN and out-of-range: INT_MIN >> 5, saturated
 
 
@@ -111,19 +103,18 @@ def test_a_plane_of_length_one_keeps_everything():
         my = rng.uniform(-1, sh, (5, 9)).astype(np.float32)
         mx[0, 0] = my[0, 0] = 0.0
         prev = rng.integers(0, 256, (5, 9), dtype=np.uint8)
-        assert not keep_def.written(mx, my, sw, sh).any() and np.array_equal(keep_def.remap_keep(src, mx, my, prev), prev)
+        assert not wd.written(mx, my, sw, sh).any() and np.array_equal(wd.remap(src, mx, my, "linear", wd.TRANSPARENT, 0, prev), prev)
 
 
 def test_camera_shape_keeps_a_third_or_more():
     """Preset camera 4 at 256 x 144 -> 230 x 131: the GPU tests' ordinary shape has kept, written and mixed tiles under both rotations."""
-    import keep_tiles
     K = oracle.get_preset_camera(4, 256, 144)
     Ko, (dw, dh) = oracle.get_output_camera(K, 256, 144)
     assert (dw, dh) == (230, 131)
     for rv in ((0.02, -0.03, 0.01), (0.35, -0.25, 0.2)):
-        mx, my = cubic_def.maps(oracle.map_params(K, Ko, oracle.rodrigues(rv)), dw, dh, 0)
-        assert 0.36 <= keep_tiles.kept_share(mx, my, 256, 144) <= 0.49
-        for plane, c in keep_tiles.tile_states(mx, my, 256, 144).items():
+        mx, my = wd.maps(oracle.map_params(K, Ko, oracle.rodrigues(rv)), dw, dh, 0)
+        assert 0.36 <= 1.0 - float(wd.written(mx, my, 256, 144).mean()) <= 0.49
+        for plane, c in wt.tile_states(mx, my, 256, 144, "linear", "written").items():
             assert c["all_kept"] and c["all_written"] and c["mixed"], (rv, plane, c)
 
 

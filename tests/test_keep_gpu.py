@@ -1,6 +1,6 @@
 """GPU parity of the keep-edge warp (include/vstab.h "Keep edges") through the C ABI and the pipeline object: vstab_remap_bilinear_keep,
 vstab_warp_nv12_keep (BGR8 and plane-wise NV12, with and without a rotation per output row), vstab_pull_frame_keep and
-vstab_pull_frame_nv12_planar_keep.  Bar: every byte equals the numpy definition (tests/keep_def.py) fed by the oracle's maps -- the reference
+vstab_pull_frame_nv12_planar_keep.  Bar: every byte equals the numpy definition (tests/warp_def.py) fed by the oracle's maps -- the reference
 kernel's own map, run on this GPU, for VSTAB_MAP_CREATEMAP_CL_OPENCL; prev and dst are planes of their own inside canaried buffers, or one
 plane (in place); after a call with a separate prev, prev is unchanged."""
 import ctypes
@@ -9,11 +9,11 @@ import numpy as np
 import pytest
 
 import expect
-import keep_def
-import keep_tiles
 import layouts
 import oracle
 import synth
+import warp_def as wd
+import warp_tiles as wt
 
 pytestmark = pytest.mark.gpu
 
@@ -93,7 +93,7 @@ def check_warp(vs, cuda, s, f, p, dw, dh, mode, what, rot_bottom=None, seed=1, p
     pb, py, puv = history(seed, dw, dh)
     other = lambda a: np.full_like(a, 0x3C)   # what dst holds before a call with a separate prev: every byte must be overwritten
     if "bgr" in formats:
-        exp = keep_def.warp_nv12_keep(f, p, dw, dh, pb, mode, rot_bottom)
+        exp = wd.bgr(f, *wd.maps(p, dw, dh, mode, rot_bottom), "linear", wd.TRANSPARENT, pb)
         assert not np.array_equal(exp.reshape(pb.shape), pb), (what, "nothing written")
         for way in ways:
             prev = place(pb, "prev")
@@ -103,7 +103,7 @@ def check_warp(vs, cuda, s, f, p, dw, dh, mode, what, rot_bottom=None, seed=1, p
             if way == "separate":
                 eq(prev.host(), pb, (what, "bgr prev", mode))
     if "planar" in formats:
-        ey, euv = keep_def.warp_nv12_planar_keep(f, p, dw, dh, py, puv, mode, rot_bottom)
+        ey, euv = wd.planar(f, *wd.maps(p, dw, dh, mode, rot_bottom), "linear", wd.TRANSPARENT, py, puv)
         for way in ways:
             prev = (place(py, "prev"), place(puv, "prev"))
             dst = prev if way == "in_place" else (place(other(py), "dst"), place(other(puv), "dst"))
@@ -128,7 +128,7 @@ def remap_keep(vs, cuda, src, mx, my, prev, in_place):
 
 
 def check_remap(vs, cuda, src, mx, my, prev, what):
-    exp = keep_def.remap_keep(src, mx, my, prev)
+    exp = wd.remap(src, mx, my, "linear", wd.TRANSPARENT, 0, prev)
     out, after = remap_keep(vs, cuda, src, mx, my, prev, False)
     eq(out, exp, (what, "separate")), eq(after, prev, (what, "prev"))
     out, _ = remap_keep(vs, cuda, src, mx, my, prev, True)
@@ -139,7 +139,7 @@ def test_remap_keep_golden_vectors(vs, cuda):
     import test_keep_cpu
     n = 0
     for k, src, mx, my, prev, out in test_keep_cpu.golden_cases():
-        assert np.array_equal(keep_def.remap_keep(src, mx, my, prev), out)
+        assert np.array_equal(wd.remap(src, mx, my, "linear", wd.TRANSPARENT, 0, prev), out)
         check_remap(vs, cuda, src, mx, my, prev, k)
         n += 1
     assert n == 9
@@ -174,7 +174,7 @@ def test_remap_keep_sweeps_every_position(vs, cuda, sw):
     for fx in (13, 0):
         mx = ((X * 32 + fx) / 32.0).astype(np.float32)
         for my in (np.full(mx.shape, 1.25, np.float32), np.full(mx.shape, 0.5, np.float32), np.full(mx.shape, 2.0, np.float32)):
-            m = keep_def.written(mx, my, sw, 3)
+            m = wd.written(mx, my, sw, 3)
             assert int(m.sum()) == (0 if my[0, 0] == 2.0 else sw - 1)
             check_remap(vs, cuda, src, mx, my, prev, (sw, fx, float(my[0, 0])))
 
@@ -184,7 +184,7 @@ def test_remap_keep_binding(vs, cuda):
     src = rng.integers(0, 256, (21, 33, 2), dtype=np.uint8)
     prev = rng.integers(0, 256, (12, 40, 2), dtype=np.uint8)
     mx, my = rng.uniform(-10, 43, (12, 40)).astype(np.float32), rng.uniform(-8, 29, (12, 40)).astype(np.float32)
-    exp = keep_def.remap_keep(src, mx, my, prev)
+    exp = wd.remap(src, mx, my, "linear", wd.TRANSPARENT, 0, prev)
     pv = dev(prev, cuda)
     eq(vs.remap_bilinear_keep(dev(src, cuda), dev(mx, cuda), dev(my, cuda), pv).cpu().numpy(), exp, "binding")
     eq(pv.cpu().numpy(), prev, "binding prev")
@@ -227,19 +227,20 @@ def test_warp_keep_binding(vs, cuda):
     p, dw, dh, K, Ko = cams(w, h, PAST)
     pb, py, puv = history(2, dw, dh)
     got = vs.warp_nv12_keep(dev(f, cuda), p, dw, dh, dev(pb.reshape(dh, dw, 3), cuda)).cpu().numpy()
-    eq(got, keep_def.warp_nv12_keep(f, p, dw, dh, pb), "binding bgr")
+    eq(got, wd.bgr(f, *wd.maps(p, dw, dh), "linear", wd.TRANSPARENT, pb), "binding bgr")
     prev = (dev(py, cuda), dev(puv, cuda))
     y, uv = vs.warp_nv12_keep(dev(f, cuda), p, dw, dh, prev, 1, vs.OUT_NV12_PLANAR, rot_bottom=p[8:], out=prev)
-    ey, euv = keep_def.warp_nv12_planar_keep(f, p, dw, dh, py, puv, 1, p[8:])
+    ey, euv = wd.planar(f, *wd.maps(p, dw, dh, 1, p[8:]), "linear", wd.TRANSPARENT, py, puv)
     assert y is prev[0] and uv is prev[1]
     eq(y.cpu().numpy(), ey, "binding y"), eq(uv.cpu().numpy(), euv, "binding uv")
 
 
 # ---- tile and layout paths ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", sorted(keep_tiles.TILE_SETS))
+@pytest.mark.parametrize("name", sorted(wt.TILE_SETS["keep"]))
 def test_keep_tile_sets(vs, cuda, name):
-    """The sets of tests/keep_tiles.py: tiles with no written sample, written throughout, mixed; staged and gathered; cut by the image's edges."""
-    p, sw, sh, dw, dh, mode = keep_tiles.set_params(name)
+    """The sets of tests/warp_tiles.py for k_warp_keep: tiles with no written sample, written throughout, mixed; staged and gathered; cut by
+    the image's edges."""
+    p, sw, sh, dw, dh, mode = wt.set_params("keep", name)
     f = synth.nv12(sum(map(ord, name)), sw, sh, full_range=True)
     s = layouts.place(f[:sh], f[sh:], "packed", cuda)
     check_warp(vs, cuda, s, f, p, dw, dh, mode, name)
@@ -255,7 +256,7 @@ def test_keep_axis_pixel_is_kept(vs, cuda):
     Ko = np.array([[100.0, 0, 64.0], [0, 100.0, 40.0], [0, 0, 1]])
     p = oracle.map_params(K, Ko, np.eye(3))
     mx, my = oracle.create_map_ex(p, 130, 70, 0)
-    assert np.isnan(mx[40, 64]) and not keep_def.written(mx, my, w, h)[40, 64]
+    assert np.isnan(mx[40, 64]) and not wd.written(mx, my, w, h)[40, 64]
     check_warp(vs, cuda, s, f, p, 130, 70, 0, "axis")
 
 
@@ -295,7 +296,8 @@ def test_keep_smallest_source_keeps_all_chroma(vs, cuda):
     Ki = np.array([[40.0, 0, 0.5], [0, 40.0, 0.5], [0, 0, 1]])
     Ko = np.array([[100.0, 0, 35.0], [0, 100.0, 10.0], [0, 0, 1]])
     p = oracle.map_params(Ki, Ko, np.eye(3))
-    my_, mc = keep_def.masks(p, 2, 2, 70, 21, 3)
+    mx, my = wd.maps(p, 70, 21, 3)
+    my_, mc = wd.written(mx, my, 2, 2), wd.written(*oracle.chroma_maps(mx, my), 1, 1)
     assert my_.any() and not my_.all() and not mc.any()
     check_warp(vs, cuda, s, f, p, 70, 21, 3, "2x2")
 
@@ -345,8 +347,8 @@ def first_history(cuda, cw, ch, planar):
 def expect_keep(f, K, Ko, R, cw, ch, last, planar, mode=0, rot_bottom=None):
     p = oracle.map_params(K, Ko, R)
     if planar:
-        return keep_def.warp_nv12_planar_keep(f, p, cw, ch, last[0], last[1], mode, rot_bottom)
-    return keep_def.warp_nv12_keep(f, p, cw, ch, last, mode, rot_bottom)
+        return wd.planar(f, *wd.maps(p, cw, ch, mode, rot_bottom), "linear", wd.TRANSPARENT, last[0], last[1])
+    return wd.bgr(f, *wd.maps(p, cw, ch, mode, rot_bottom), "linear", wd.TRANSPARENT, last)
 
 
 def same(out, exp, planar, what):
@@ -435,8 +437,6 @@ def test_pipeline_keep_default_precision(vs, cuda, clip):
 def test_pipeline_keep_refusals(vs, cuda, clip):
     """Every refusal comes before a frame is dequeued: after it the whole stream is delivered by plain pulls, frame for frame."""
     import torch
-    import cubic_def
-    import border_def
     K, Ko, cw, ch, frames = clip
     fr = frames[:4]
     out, prev = torch.zeros((ch, cw, 3), dtype=torch.uint8, device=cuda), torch.zeros((ch, cw, 3), dtype=torch.uint8, device=cuda)
@@ -451,12 +451,12 @@ def test_pipeline_keep_refusals(vs, cuda, clip):
     first = lambda stab: oracle.map_params(K, Ko, stab.warp_rotation(0))
     table = [
         (dict(resample=vs.RESAMPLE_CUBIC, **ieee), None, vs.ERR_UNSUPPORTED, ": VSTAB_RESAMPLE_CUBIC has no keep-edge warp",
-         lambda stab: cubic_def.warp_nv12_cubic(fr[1], first(stab), cw, ch)),
+         lambda stab: wd.bgr(fr[1], *wd.maps(first(stab), cw, ch), "cubic")),
         (dict(resample=vs.RESAMPLE_LANCZOS4), None, vs.ERR_UNSUPPORTED, ": VSTAB_RESAMPLE_LANCZOS4 has no keep-edge warp", None),
         (dict(interpolation=0), None, vs.ERR_UNSUPPORTED, ": INTER_NEAREST has no keep-edge warp", None),
         (dict(border_mode=vs.BORDER_REFLECT_101, **ieee), None, vs.ERR_UNSUPPORTED,
          ": a border mode other than VSTAB_BORDER_CONSTANT is in force (vstab_set_border_mode)",
-         lambda stab: border_def.warp_nv12_border(fr[1], first(stab), cw, ch, 0, border_def.REFLECT_101)),
+         lambda stab: wd.bgr(fr[1], *wd.maps(first(stab), cw, ch, 0), "linear", wd.REFLECT_101)),
         (dict(lens_mode=1, in_projection=1, out_projection=0, in_dfov=150.0, out_dfov=110.0, out_width=cw, out_height=ch, calibration=(None, 0)),
          None, vs.ERR_UNSUPPORTED, ": a calibrated handle (vstab_set_input_calibration) has no keep-edge warp", None),
         (ieee, "pitch", vs.ERR_INVALID, ": prev pitch smaller than row", lambda stab: expect.warp(fr[1], first(stab), cw, ch, expect.IEEE)),

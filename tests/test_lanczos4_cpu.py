@@ -1,4 +1,4 @@
-"""The Lanczos resampler's definition (tests/lanczos4_def.py) and its ABI, without a GPU: the integer weight table's properties and its
+"""The Lanczos resampler's definition (tests/warp_def.py) and its ABI, without a GPU: the integer weight table's properties and its
 independence of the libm, the table the library's kernels embed, the numpy remap's behaviour, the committed known answers, vstab_create's
 handling of `resample = 4`, and the stateless functions' argument checks."""
 import ctypes
@@ -9,7 +9,7 @@ import re
 import numpy as np
 import pytest
 
-import lanczos4_def
+import warp_def as wd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KAT = os.path.join(ROOT, "tests", "golden", "lanczos4_kat.npz")
@@ -18,7 +18,7 @@ HEADER = os.path.join(ROOT, "video-annotator_amd", "csrc", "vstab_lanczos4.hpp")
 
 @pytest.fixture(scope="module")
 def tab():
-    return lanczos4_def.lanczos4_table()
+    return wd.lanczos4_table()
 
 
 def header_literals(name):
@@ -43,15 +43,15 @@ def test_entry_zero_is_not_the_identity(tab):
 def test_both_forms_of_the_x0_special_case_give_the_same_table(tab):
     """OpenCV has returned the unit row early at x = 0, and has put a 1e30f sentinel in tap 3 and normalised: the float rows differ (the
     sentinel leaves ~1e-30 in the other taps), the integer table does not."""
-    early, sentinel = lanczos4_def.lanczos4_coeffs(variant="early"), lanczos4_def.lanczos4_coeffs(variant="sentinel")
+    early, sentinel = wd.lanczos4_coeffs(variant="early"), wd.lanczos4_coeffs(variant="sentinel")
     assert np.array_equal(early[1:], sentinel[1:])
     assert not np.array_equal(early[0], sentinel[0]) and sentinel[0, 3] == 1.0
-    assert np.array_equal(lanczos4_def.lanczos4_table(variant="sentinel"), tab)
+    assert np.array_equal(wd.lanczos4_table(variant="sentinel"), tab)
 
 
 def test_correction_stays_in_its_window(tab):
     """The correction moves at most one weight of an entry, inside rows and columns 4, 5."""
-    _, prod = lanczos4_def.lanczos4_table(products=True)
+    _, prod = wd.lanczos4_table(products=True)
     raw = np.clip(np.rint(prod).astype(np.int64), -32768, 32767)
     moved = tab != raw
     assert moved.sum(axis=(1, 2)).max() == 1
@@ -62,17 +62,17 @@ def test_correction_stays_in_its_window(tab):
 def test_table_does_not_depend_on_the_libm(tab):
     """Every s0 / c0 moved by one double ulp, up or down, all at once and in random mixtures: no entry changes.  (The table does depend
     on fp32 operation order and on cvRound's ties: a few products are exact ties, ~120 lie within 1e-3 of one.)"""
-    s0, c0 = lanczos4_def.sincos()
+    s0, c0 = wd.sincos()
     for d in (np.inf, -np.inf):
-        assert np.array_equal(lanczos4_def.lanczos4_table([np.nextafter(v, d) for v in s0], [np.nextafter(v, d) for v in c0]), tab)
-        assert np.array_equal(lanczos4_def.lanczos4_table([np.nextafter(v, d) for v in s0], [np.nextafter(v, -d) for v in c0]), tab)
+        assert np.array_equal(wd.lanczos4_table([np.nextafter(v, d) for v in s0], [np.nextafter(v, d) for v in c0]), tab)
+        assert np.array_equal(wd.lanczos4_table([np.nextafter(v, d) for v in s0], [np.nextafter(v, -d) for v in c0]), tab)
     rng = np.random.default_rng(7)
     for _ in range(4):
         ds, dc = rng.choice([np.inf, -np.inf, 0.0], 32), rng.choice([np.inf, -np.inf, 0.0], 32)
         ps = [np.nextafter(v, d) if d else v for v, d in zip(s0, ds)]
         pc = [np.nextafter(v, d) if d else v for v, d in zip(c0, dc)]
-        assert np.array_equal(lanczos4_def.lanczos4_table(ps, pc), tab)
-    _, prod = lanczos4_def.lanczos4_table(products=True)
+        assert np.array_equal(wd.lanczos4_table(ps, pc), tab)
+    _, prod = wd.lanczos4_table(products=True)
     frac = np.abs(prod - np.floor(prod) - 0.5)
     assert (frac == 0).sum() == 4 and (frac < 1e-3).sum() == 120
 
@@ -82,10 +82,10 @@ def test_committed_literals(tab):
     kat = np.load(KAT)
     s0, c0 = header_literals("S0"), header_literals("C0")
     assert np.array_equal(np.array(s0), kat["s0"]) and np.array_equal(np.array(c0), kat["c0"])
-    here_s, here_c = lanczos4_def.sincos()
+    here_s, here_c = wd.sincos()
     for a, b in zip(s0 + c0, here_s + here_c):
         assert abs(a - b) <= math.ulp(b)
-    assert np.array_equal(lanczos4_def.lanczos4_table(s0, c0), tab)
+    assert np.array_equal(wd.lanczos4_table(s0, c0), tab)
 
 
 def test_table_matches_golden_and_library(tab, vs):
@@ -95,11 +95,9 @@ def test_table_matches_golden_and_library(tab, vs):
 
 
 def test_golden_remaps():
-    kat = np.load(KAT)
     n = 0
-    while f"case{n}_src" in kat:
-        got = lanczos4_def.remap_lanczos4(kat[f"case{n}_src"], kat[f"case{n}_mapx"], kat[f"case{n}_mapy"], kat[f"case{n}_border"])
-        assert np.array_equal(got, kat[f"case{n}_out"]), n
+    for k, src, mx, my, border, out in wd.golden_cases("lanczos4_kat", "src", "mapx", "mapy", "border", "out"):
+        assert np.array_equal(wd.remap(src, mx, my, "lanczos4", wd.CONSTANT, border), out), k
         n += 1
     assert n >= 6
 
@@ -108,7 +106,7 @@ def test_integer_translation_copies():
     rng = np.random.default_rng(1)
     src = rng.integers(0, 256, (40, 50, 3), dtype=np.uint8)
     yy, xx = np.mgrid[0:30, 0:40].astype(np.float32)
-    out = lanczos4_def.remap_lanczos4(src, xx + 5, yy + 3)
+    out = wd.remap(src, xx + 5, yy + 3, "lanczos4")
     assert np.array_equal(out, src[3:33, 5:45])
 
 
@@ -117,25 +115,25 @@ def test_fractional_positions_within_a_level_of_float_lanczos():
     src = rng.integers(0, 256, (30, 30), dtype=np.uint8)
     mx = rng.uniform(4, 24, (40, 40)).astype(np.float32)
     my = rng.uniform(4, 24, (40, 40)).astype(np.float32)
-    got = lanczos4_def.remap_lanczos4(src, mx, my).astype(np.int64)
-    ref = lanczos4_def.remap_lanczos4_float(src, mx, my)
+    got = wd.remap(src, mx, my, "lanczos4").astype(np.int64)
+    ref = wd.remap_float(src, mx, my, "lanczos4")
     assert np.abs(got - ref).max() <= 1
     # Lanczos overshoots: a step edge saturates instead of wrapping
     step = np.zeros((12, 12), np.uint8)
     step[:, 6:] = 255
     yy, xx = np.mgrid[0:12, 0:96].astype(np.float32)
-    out = lanczos4_def.remap_lanczos4(step, xx / 8.0, yy * 0 + 6)
+    out = wd.remap(step, xx / 8.0, yy * 0 + 6, "lanczos4")
     assert out.min() == 0 and out.max() == 255
 
 
 def test_border_rule_per_tap():
     """A tap outside the source enters the blend as the border value; a footprint wholly outside gives the border value."""
     src = np.full((10, 10), 100, np.uint8)
-    one = lambda x, y, b: lanczos4_def.remap_lanczos4(src, np.array([[x]], np.float32), np.array([[y]], np.float32), b)[0, 0]
+    one = lambda x, y, b: wd.remap(src, np.array([[x]], np.float32), np.array([[y]], np.float32), "lanczos4", wd.CONSTANT, b)[0, 0]
     # fx = fy = 0: tap (X, Y) alone (32767) plus tap (X + 1, Y + 1) (1)
     assert one(-1.0, 4.0, 20) == 20 and one(0.0, 4.0, 20) == 100
     # half a pixel left of the source: the blend of border and source per the table's weights
-    w = lanczos4_def.lanczos4_table()[16].sum(axis=0)   # fx = 16, fy = 0: column weights
+    w = wd.lanczos4_table()[16].sum(axis=0)   # fx = 16, fy = 0: column weights
     exp = (int(sum(w[k] * (20 if k < 4 else 100) for k in range(8))) + (1 << 14)) >> 15   # X = -1: columns -4 .. 3
     assert one(-0.5, 4.0, 20) == exp
     for far in (-5.0, 14.0, 40.0):
@@ -147,9 +145,9 @@ def test_border_rule_per_tap():
 def test_nan_and_huge_entries_give_the_border():
     src = np.full((9, 9, 2), 9, np.uint8)
     vals = np.array([[np.nan, np.inf, -np.inf, 1e9, -1e9, 3e9, -3e9]], np.float32)
-    out = lanczos4_def.remap_lanczos4(src, vals, np.full_like(vals, 4.0), (128, 77))
+    out = wd.remap(src, vals, np.full_like(vals, 4.0), "lanczos4", wd.CONSTANT, (128, 77))
     assert (out[..., 0] == 128).all() and (out[..., 1] == 77).all()
-    out = lanczos4_def.remap_lanczos4(src, np.full_like(vals, 4.0), vals, (128, 77))
+    out = wd.remap(src, np.full_like(vals, 4.0), vals, "lanczos4", wd.CONSTANT, (128, 77))
     assert (out[..., 0] == 128).all() and (out[..., 1] == 77).all()
 
 
@@ -165,7 +163,7 @@ def test_lanczos4_matches_opencv_when_present():
         my[::3, ::4] = np.floor(my[::3, ::4])                              # fy = 0
         bv = (border,) * 4 if np.isscalar(border) else tuple(border) + (0,) * (4 - len(border))
         exp = cv2.remap(src, mx, my, cv2.INTER_LANCZOS4, borderMode=cv2.BORDER_CONSTANT, borderValue=bv)
-        assert np.array_equal(lanczos4_def.remap_lanczos4(src, mx, my, border), exp), cn
+        assert np.array_equal(wd.remap(src, mx, my, "lanczos4", wd.CONSTANT, border), exp), cn
 
 
 # ---------------------------------------------------------------------------------------------

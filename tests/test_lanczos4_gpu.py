@@ -1,6 +1,6 @@
 """GPU parity of the Lanczos resampler (cv::remap INTER_LANCZOS4; include/vstab.h "Lanczos resampling") through the C ABI and the
 pipeline object: vstab_remap_lanczos4, vstab_warp_nv12_lanczos4 (BGR8 and plane-wise NV12) and vstab_config.resample = 4.  Bar: every
-byte equals the numpy definition (tests/lanczos4_def.py) fed by the oracle's maps, and no byte around an output plane is written
+byte equals the numpy definition (tests/warp_def.py) fed by the oracle's maps, and no byte around an output plane is written
 (canary bands above, below and right of each plane, tests/layouts.py).  Covered:
   - the stateless remap for 1..3 channels: the KAT, pitched maps, an odd source address and pitch, NaN / +-inf / huge / tie entries, the
     int16 saturation edges and the refusal of 32768;
@@ -15,14 +15,14 @@ import numpy as np
 import pytest
 
 import expect
-import lanczos4_def
 import layouts
 import oracle
 import synth
+import warp_def as wd
+import warp_tiles as wt
 from test_cubic_gpu import special_maps
 from test_cubic_paths_gpu import PITCH_Y_4G, W4, H4, _plane_past_4g, _release, drive, frames_4g, odd_source, pitched_map
 from test_layouts_gpu import PITCH_UV_4G, run_pipeline
-from test_lanczos4_tiles_cpu import TILE_SETS, set_params
 
 pytestmark = pytest.mark.gpu
 
@@ -64,9 +64,9 @@ def warp_c(vs, s, params, dw, dh, mode, out_format, cuda, out=None):
 
 def check(vs, cuda, s, f, p, dw, dh, mode, what, out_bgr=None, out_planar=None):
     """BGR and plane-wise Lanczos warps of Src s (packed NV12 f on the host) against the definition."""
-    eq(warp_c(vs, s, p, dw, dh, mode, vs.OUT_BGR8, cuda, out_bgr), lanczos4_def.warp_nv12_lanczos4(f, p, dw, dh, mode), (what, "bgr", mode))
+    eq(warp_c(vs, s, p, dw, dh, mode, vs.OUT_BGR8, cuda, out_bgr), wd.bgr(f, *wd.maps(p, dw, dh, mode), "lanczos4"), (what, "bgr", mode))
     gy, guv = warp_c(vs, s, p, dw, dh, mode, vs.OUT_NV12_PLANAR, cuda, out_planar)
-    ey, euv = lanczos4_def.warp_nv12_planar_lanczos4(f, p, dw, dh, mode)
+    ey, euv = wd.planar(f, *wd.maps(p, dw, dh, mode), "lanczos4")
     eq(gy, ey, (what, "luma", mode)), eq(guv, euv, (what, "chroma", mode))
 
 
@@ -118,7 +118,7 @@ def test_remap_lanczos4_pitched_maps_odd_source_canaried_outputs(vs, cuda):
             mxt, myt = pitched_map(mx, 5, cuda), pitched_map(my, 17, cuda)
             assert mxt.stride(0) != myt.stride(0)
             got = remap_c(vs, cuda, ptr, pitch, sw, sh, cn, mxt, myt, border, dw, dh)
-            eq(got, lanczos4_def.remap_lanczos4(src, mx, my, border), ("remap", sw, cn))
+            eq(got, wd.remap(src, mx, my, "lanczos4", wd.CONSTANT, border), ("remap", sw, cn))
             del keep
 
 
@@ -139,9 +139,9 @@ def test_remap_lanczos4_int16_saturation_edges(vs, cuda):
             dh, dw = mx.shape
             st = torch.from_numpy(src).to(cuda)
             got = remap_c(vs, cuda, st.data_ptr(), st.stride(0), sw, sh, cn, pitched_map(mx, 3, cuda), pitched_map(my, 0, cuda), border, dw, dh)
-            exp = lanczos4_def.remap_lanczos4(src, mx, my, border)
+            exp = wd.remap(src, mx, my, "lanczos4", wd.CONSTANT, border)
             eq(got, exp, ("saturation", cn, tall))
-            X, Y, _ = lanczos4_def.quantise(mx, my)
+            X, Y, _ = wd.quantise(mx, my)
             assert ((Y if tall else X) == 32767).sum() >= 2 * len(ys)
 
 
@@ -203,7 +203,7 @@ def test_warp_lanczos4_refuses_other_formats(vs, cuda):
     with pytest.raises(vs.VstabError):
         vs.warp_nv12_lanczos4(f, p, dw, dh, 6, vs.OUT_BGR8)
     out = vs.warp_nv12_lanczos4(f, p, dw, dh)   # the binding's own path
-    eq(out.cpu().numpy(), lanczos4_def.warp_nv12_lanczos4(synth.nv12(1, w, h), p, dw, dh, 0), "binding")
+    eq(out.cpu().numpy(), wd.bgr(synth.nv12(1, w, h), *wd.maps(p, dw, dh, 0), "lanczos4"), "binding")
 
 
 def torch_dev(a, cuda):
@@ -212,9 +212,9 @@ def torch_dev(a, cuda):
 
 
 # ---- the tile sets: staged, gathered, at the budget and over it -----------------------------------------------------------------
-@pytest.mark.parametrize("name", sorted(TILE_SETS))
+@pytest.mark.parametrize("name", sorted(wt.TILE_SETS["lanczos4"]))
 def test_lanczos4_tile_sets(vs, cuda, name):
-    p, sw, sh, dw, dh, mode = set_params(name)
+    p, sw, sh, dw, dh, mode = wt.set_params("lanczos4", name)
     f = synth.nv12(sum(map(ord, name)), sw, sh, full_range=True)
     s = packed(f, sh, cuda)
     for m in modes_of(mode):
@@ -230,7 +230,7 @@ def test_lanczos4_every_layout(vs, cuda, name, cam):
         p, dw, dh, _, _ = cams(w, h)
         mode = 0
     else:
-        p, w, h, dw, dh, mode = set_params(cam)
+        p, w, h, dw, dh, mode = wt.set_params("lanczos4", cam)
     f = synth.nv12(21, w, h)
     s = layouts.place(f[:h], f[h:], name, cuda)
     for m in modes_of(mode):
@@ -272,9 +272,9 @@ def _pipeline_4g(vs, cuda, s, f, K, Ko, what):
                 p = oracle.map_params(K, Ko, R)
                 ch, cw = (o.shape[:2] if pulls == "bgr" else o[0].shape)
                 if pulls == "bgr":
-                    eq(o, lanczos4_def.warp_nv12_lanczos4(f, p, cw, ch, 0), (what, "pipeline", hold, i))
+                    eq(o, wd.bgr(f, *wd.maps(p, cw, ch, 0), "lanczos4"), (what, "pipeline", hold, i))
                 else:
-                    ey, euv = lanczos4_def.warp_nv12_planar_lanczos4(f, p, cw, ch, 0)
+                    ey, euv = wd.planar(f, *wd.maps(p, cw, ch, 0), "lanczos4")
                     eq(o[0], ey, (what, "pipeline y", hold, i)), eq(o[1], euv, (what, "pipeline uv", hold, i))
 
 
@@ -300,12 +300,12 @@ def test_lanczos4_output_plane_past_4_gib(vs, cuda, plane):
         cw2, ch2 = 2 * ((dw + 1) // 2), (dh + 1) // 2
         if plane == "bgr":
             o = _plane_past_4g(dh, 3 * dw, cuda)
-            eq(warp_c(vs, s, p, dw, dh, 0, vs.OUT_BGR8, cuda, o), lanczos4_def.warp_nv12_lanczos4(f, p, dw, dh, 0), (plane, label))
+            eq(warp_c(vs, s, p, dw, dh, 0, vs.OUT_BGR8, cuda, o), wd.bgr(f, *wd.maps(p, dw, dh, 0), "lanczos4"), (plane, label))
         else:
             o = (_plane_past_4g(dh, dw, cuda), layouts.Plane(ch2, cw2, cuda)) if plane == "luma" else \
                 (layouts.Plane(dh, dw, cuda), _plane_past_4g(ch2, cw2, cuda))
             gy, guv = warp_c(vs, s, p, dw, dh, 0, vs.OUT_NV12_PLANAR, cuda, o)
-            ey, euv = lanczos4_def.warp_nv12_planar_lanczos4(f, p, dw, dh, 0)
+            ey, euv = wd.planar(f, *wd.maps(p, dw, dh, 0), "lanczos4")
             eq(gy, ey, (plane, label, "luma")), eq(guv, euv, (plane, label, "chroma"))
         del o
         _release()
@@ -328,10 +328,10 @@ def expect_lz(frames, K, Ko, outs, pulls, what, mode=0):
         p = oracle.map_params(K, Ko, R)
         if pulls == "bgr":
             ch, cw = o.shape[:2]
-            eq(o, lanczos4_def.warp_nv12_lanczos4(frames[i + 1], p, cw, ch, mode), (what, i))
+            eq(o, wd.bgr(frames[i + 1], *wd.maps(p, cw, ch, mode), "lanczos4"), (what, i))
         else:
             ch, cw = o[0].shape
-            ey, euv = lanczos4_def.warp_nv12_planar_lanczos4(frames[i + 1], p, cw, ch, mode)
+            ey, euv = wd.planar(frames[i + 1], *wd.maps(p, cw, ch, mode), "lanczos4")
             eq(o[0], ey, (what, "y", i)), eq(o[1], euv, (what, "uv", i))
 
 
@@ -386,9 +386,9 @@ def test_pipeline_lanczos4_default_precision_and_lens_mode(vs, cuda, clip):
         for i, o in enumerate(outs):
             p = oracle.map_params(stab.K_in, Kout, stab.warp_rotation(i))
             if how == "pull":
-                eq(o, lanczos4_def.warp_nv12_lanczos4(frames[i + 1], p, 480, 270, oracle.MAP_FISH_TO_RECT), ("lens", i))
+                eq(o, wd.bgr(frames[i + 1], *wd.maps(p, 480, 270, oracle.MAP_FISH_TO_RECT), "lanczos4"), ("lens", i))
             else:
-                ey, euv = lanczos4_def.warp_nv12_planar_lanczos4(frames[i + 1], p, 480, 270, oracle.MAP_FISH_TO_RECT)
+                ey, euv = wd.planar(frames[i + 1], *wd.maps(p, 480, 270, oracle.MAP_FISH_TO_RECT), "lanczos4")
                 eq(o[0], ey, ("lens y", i)), eq(o[1], euv, ("lens uv", i))
         stab.close()
 
@@ -543,7 +543,7 @@ def test_pipeline_lanczos4_refusals_keep_the_handle_serving(vs, cuda, clip):
         vs.lib.vstab_destroy(h)
     assert refused == [2] and sorted(got) == [0, 1, 3, 4], (refused, sorted(got))
     for k, (o, R) in got.items():
-        eq(o, lanczos4_def.warp_nv12_lanczos4(frames[k + 1], oracle.map_params(K, Ko, R), cw, ch, 0), ("after read-out refusal", k))
+        eq(o, wd.bgr(frames[k + 1], *wd.maps(oracle.map_params(K, Ko, R), cw, ch, 0), "lanczos4"), ("after read-out refusal", k))
     for bad in (dict(pixel_depth=10), dict(interpolation=0)):
         with pytest.raises(vs.VstabError):
             vs.Stabilizer(fr, total=6, smooth_radius=1, **dict(dict(resample=vs.RESAMPLE_LANCZOS4), **bad))

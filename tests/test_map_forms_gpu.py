@@ -9,10 +9,9 @@ a rotation of about 100 degrees about the vertical axis for the rays behind the 
 import numpy as np
 import pytest
 
-import border_def
-import cubic_def
 import distort_def as dd
 import oracle
+import warp_def as wd
 
 pytestmark = pytest.mark.gpu
 
@@ -125,8 +124,8 @@ def check_kernels(vs, cuda, p, mode, D, mx, my, what, rot_bottom=None):
         border = vs.warp_nv12_border(fd, p, DW, DH, mode, vs.OUT_BGR8, vs.BORDER_REFLECT_101)
         cubic = vs.warp_nv12_cubic(fd, p, DW, DH, mode)
     assert np.array_equal(fused.cpu().numpy(), oracle.remap_bilinear(bgr, mx, my)), (what, "fused")
-    assert np.array_equal(border.cpu().numpy(), border_def.remap_border(bgr, mx, my, border_def.REFLECT_101)), (what, "border")
-    assert np.array_equal(cubic.cpu().numpy(), cubic_def.remap_cubic(bgr, mx, my, 0)), (what, "cubic")
+    assert np.array_equal(border.cpu().numpy(), wd.remap(bgr, mx, my, "linear", wd.REFLECT_101)), (what, "border")
+    assert np.array_equal(cubic.cpu().numpy(), wd.remap(bgr, mx, my, "cubic", wd.CONSTANT, 0)), (what, "cubic")
     if D is None:   # the 10-bit warp has no lens coefficients
         import torch
         exp = oracle.remap_bilinear10(oracle.cvt_p010_bgr10(y16, uv16), mx, my, 0)

@@ -12,11 +12,10 @@ import sys
 import numpy as np
 import pytest
 
-import border_tiles
-import distort_resample_def as drd
 import oracle
 import pinhole_def as pd
-import rs_resample_def
+import warp_def as wd
+import warp_tiles as wt
 from test_distort_refusals_cpu import BGR8, FP, INL, INVALID, K9, NV12, OUT, P, PLANAR, PTS, R9, XY, f32, f64
 from test_lens_gpu import LENSES, ROTS
 
@@ -305,17 +304,15 @@ def test_rotation_estimate_through_a_distorted_pinhole_lens(vs):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # tile states of the shapes test_pinhole_gpu.py runs.  The kernels behind vstab_warp_nv12_pinhole: k_warp_border for INTER_LINEAR (every border
-# mode: border_tiles), k_warp_cubic_rs / k_warp_lanczos4_rs for the other two (rs_resample_def.tile_states: resample_border_tiles' boxes, and
-# cubic_tiles' / lanczos4_tiles' for BORDER_CONSTANT).
+# mode: BORDER_CONSTANT is the rule `clamp` of tests/warp_tiles.py), k_warp_cubic_rs / k_warp_lanczos4_rs for the other two (wt.kernel_rule).
 # ---------------------------------------------------------------------------------------------------------------------
-KERNELS = [(r, b) for r in drd.RESAMPLERS for b in (drd.CONSTANT, drd.REFLECT_101)]
+KERNELS = [(r, b) for r in wd.RESAMPLERS for b in (wd.CONSTANT, wd.REFLECT_101)]
 PLANES = ("bgr", "luma", "chroma")
 
 
 def tile_states(resampler, mx, my, sw, sh, border):
-    if resampler == "linear":
-        return border_tiles.tile_states(mx, my, sw, sh, border)
-    return rs_resample_def.tile_states(resampler, mx, my, sw, sh, border)
+    rule = "clamp" if (resampler, border) == ("linear", wd.CONSTANT) else wt.kernel_rule(resampler, border)
+    return wt.tile_states(mx, my, sw, sh, resampler, rule)
 
 
 def test_tile_states_640x360_staged_partial_crossing_and_mixed():
@@ -326,21 +323,21 @@ def test_tile_states_640x360_staged_partial_crossing_and_mixed():
         for pl in PLANES:
             s = st[pl]
             assert s["staged"] == 78 and s["gathered"] == 0 and s["odd_w"] > 0 and s["even_w"] > 0, (r, b, pl, s)
-            if b == drd.CONSTANT and r != "linear":
+            if b == wd.CONSTANT and r != "linear":
                 assert s["none"] == 0 and s["partial_staged"] == 18, (r, b, pl, s)      # the partial tiles at the right and bottom edge
     mx, my = shape_maps(w, h, dw, dh, 4, ROTS[1])                                        # staged and gathered tiles in one launch
     for r, b in KERNELS:
         st = tile_states(r, mx, my, w, h, b)
         for pl in PLANES:
             assert st[pl]["staged"] > 0 and st[pl]["gathered"] > 0, (r, b, pl, st[pl])
-        if r != "linear" and b == drd.CONSTANT:
+        if r != "linear" and b == wd.CONSTANT:
             assert st["bgr"]["none"] > 0, (r, st["bgr"])                                 # tiles with no box beside them
         else:
             assert st["bgr"]["outside_staged"] > 0, (r, b, st["bgr"])
         c = st["chroma"]
-        if r == "linear" and b == drd.CONSTANT:                                          # clamped taps: boxes that cross every edge of the source
+        if r == "linear" and b == wd.CONSTANT:                                          # clamped taps: boxes that cross every edge of the source
             assert min(c["cross_l"], c["cross_r"], c["cross_t"], c["cross_b"]) > 0 and min(st["bgr"][k] for k in ("cross_l", "cross_r", "cross_t", "cross_b")) > 0
-        elif b != drd.CONSTANT:
+        elif b != wd.CONSTANT:
             assert c["cross_r"] > 0 and c["cross_t"] > 0 and c["cross_b"] > 0, (r, c)
 
 
@@ -355,7 +352,7 @@ def test_tile_states_1024x576_staged_and_gathered_in_one_launch():
     for r, b in KERNELS:
         st = tile_states(r, mx, my, w, h, b)
         assert st["bgr"]["gathered"] == 15, (r, b, st["bgr"])
-        if r != "linear" and b == drd.CONSTANT:
+        if r != "linear" and b == wd.CONSTANT:
             assert st["bgr"]["none"] == 5 and st["chroma"]["staged"] > 0, (r, st)
         else:
             assert st["bgr"]["outside_staged"] == 5, (r, b, st["bgr"])
@@ -389,12 +386,12 @@ def test_tile_states_a_quarter_of_the_map_behind_the_camera():
     tiles = [nan[y:y + 16, x:x + 64] for y in range(0, dh, 16) for x in range(0, dw, 64)]
     mixed, all_nan = sum(bool(t.any() and not t.all()) for t in tiles), sum(bool(t.all()) for t in tiles)
     assert mixed > 0 and all_nan > 0
-    for r, b in [(r, b) for r in drd.RESAMPLERS for b in (drd.CONSTANT, drd.REPLICATE)]:
+    for r, b in [(r, b) for r in wd.RESAMPLERS for b in (wd.CONSTANT, wd.REPLICATE)]:
         st = tile_states(r, mx, my, w, h, b)
         s = st["bgr"]
-        if b == drd.CONSTANT and r != "linear":     # a NaN entry quantises to (-32768, -32768): it touches nothing and stays out of the box
+        if b == wd.CONSTANT and r != "linear":     # a NaN entry quantises to (-32768, -32768): it touches nothing and stays out of the box
             assert s["none"] >= all_nan and s["staged"] > 0, (r, s)
-        elif b == drd.CONSTANT:                     # INTER_LINEAR clamps such a tap to (-2, -2): a tile of NaN entries stages a 2 x 2 box outside
+        elif b == wd.CONSTANT:                     # INTER_LINEAR clamps such a tap to (-2, -2): a tile of NaN entries stages a 2 x 2 box outside
             assert s["outside_staged"] >= all_nan and s["staged"] > 0, (r, s)
         else:                                       # every footprint counts: the box of a tile that holds a NaN entry beside a number reaches -32768
             assert s["gathered"] >= mixed and s["outside_staged"] >= all_nan, (r, s)

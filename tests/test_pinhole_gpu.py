@@ -1,6 +1,6 @@
 """GPU tests of the pinhole lens distortion (include/vstab.h, "Pinhole lens distortion"): every byte of vstab_warp_nv12_pinhole, BGR, luma and
 chroma, against the numpy definition -- the distorted map (tests/pinhole_def.py) fed to the resamplers' existing definitions
-(tests/distort_resample_def.py: remap_bgr / remap_planar) --, against the older entry points it must agree with at D = 0, and against the
+(tests/warp_def.py: bgr / planar) --, against the older entry points it must agree with at D = 0, and against the
 stateless route (vstab_create_map_pinhole + a vstab_remap_*_border).  Shapes: the smallest that reach the tile states test_pinhole_cpu.py
 asserts for them, a source plane off its alignment, a 16 x 2 source, padded destinations, and a handle with vstab_set_input_pinhole through
 every pull, its refusals, and a tracked clip."""
@@ -9,11 +9,11 @@ import ctypes
 import numpy as np
 import pytest
 
-import distort_resample_def as drd
 import layouts
 import oracle
 import pinhole_def as pd
 import synth
+import warp_def as wd
 from test_border_gpu import pulls
 from test_distort_gpu import dev, refused, same_map
 from test_lens_gpu import ROTS
@@ -21,8 +21,8 @@ from test_pinhole_cpu import cameras
 
 pytestmark = pytest.mark.gpu
 
-RESAMPLERS, RESAMPLE, BORDERS = drd.RESAMPLERS, drd.RESAMPLE, drd.BORDERS
-CONSTANT, REPLICATE, REFLECT, REFLECT_101 = drd.CONSTANT, drd.REPLICATE, drd.REFLECT, drd.REFLECT_101
+RESAMPLERS, RESAMPLE, BORDERS = wd.RESAMPLERS, wd.RESAMPLE, wd.MODES
+CONSTANT, REPLICATE, REFLECT, REFLECT_101 = wd.CONSTANT, wd.REPLICATE, wd.REFLECT, wd.REFLECT_101
 MODES = [3, 4]
 
 
@@ -44,10 +44,10 @@ class Case:
         self.mx, self.my = pd.maps(self.p, dw, dh, mode, D)
 
     def bgr(self, resampler, border):
-        return drd.remap_bgr(resampler, self.f, self.mx, self.my, border)
+        return wd.bgr(self.f, self.mx, self.my, resampler, border)
 
     def planar(self, resampler, border):
-        return drd.remap_planar(resampler, self.f, self.mx, self.my, border)
+        return wd.planar(self.f, self.mx, self.my, resampler, border)
 
     def check(self, vs, fd, resampler, border, what=None):
         """Both output formats of vstab_warp_nv12_pinhole (through the binding, packed source fd) against the definition."""
@@ -81,7 +81,7 @@ def test_every_resampler_border_and_mode(vs, cuda, resampler, mode):
     zx, zy = pd.maps(c.p, dw, dh, mode, pd.D_0)
     for border in BORDERS:
         got = c.check(vs, fd, resampler, border, "all").cpu().numpy()
-        plain = drd.remap_bgr(resampler, c.f, zx, zy, border)                     # the D = 0 frame
+        plain = wd.bgr(c.f, zx, zy, resampler, border)                     # the D = 0 frame
         assert (got != 0).mean() >= 0.1, ("black", resampler, border, mode)
         assert (got != plain).any(axis=-1).mean() >= 0.5, ("the distortion moved too few pixels", resampler, border, mode)
         eq(stateless_bgr(vs, fd, c, resampler, border).cpu().numpy(), got, ("stateless route", resampler, border, mode))
@@ -299,10 +299,10 @@ def still_maps():
 def expect_pull(still_maps, f, resampler, border, out, how, what):
     mx, my = still_maps
     if how == "planar":
-        ey, ec = drd.remap_planar(resampler, f, mx, my, border)
+        ey, ec = wd.planar(f, mx, my, resampler, border)
         eq(out[0], ey, (what, "luma")), eq(out[1], ec, (what, "chroma"))
     else:
-        eq(out, drd.remap_bgr(resampler, f, mx, my, border), what)
+        eq(out, wd.bgr(f, mx, my, resampler, border), what)
 
 
 @pytest.mark.parametrize("how", ["pull", "frames", "host", "peek", "planar"])
@@ -393,8 +393,7 @@ def test_pipeline_refusals_of_a_pinhole_handle(vs, cuda, still_clip, still_maps)
     assert refused(vs, s.set_input_pinhole, K_CAL, nan_D) == (INV, SETP + "the five distortion coefficients must be finite")
     assert refused(vs, s.set_input_pinhole, K_CAL, (1e39, 0, 0, 0, 0)) == (INV, SETP + "the five distortion coefficients must be finite")
     assert refused(vs, s.set_input_pinhole, bad_K, nan_D)[1] == SETP + "K must be a camera matrix with fx, fy > 0, zero skew and last row 0 0 1"
-    import resample_border_def as rbd
-    plain = rbd.warp_nv12("cubic", frames[1], oracle.map_params(Kin, Kout, np.eye(3)), OW, OH, 3, REFLECT_101)
+    plain = wd.bgr(frames[1], *wd.maps(oracle.map_params(Kin, Kout, np.eye(3)), OW, OH, 3), "cubic", REFLECT_101)
     eq(s.pull().cpu().numpy(), plain, "uncalibrated after the refusals")
     assert refused(vs, s.set_input_pinhole, K_CAL, pd.D_P) == (INV, SETP + "the calibration must be set before the first pull")
     s.close()
@@ -412,7 +411,7 @@ def test_pipeline_refusals_of_a_pinhole_handle(vs, cuda, still_clip, still_maps)
     s.close()
     s = handle(pinhole=(None, pd.D_Q))
     mx, my = pd.maps(oracle.map_params(Kin, Kout, np.eye(3)), OW, OH, 3, pd.D_Q)
-    eq(s.pull().cpu().numpy(), drd.remap_bgr("linear", frames[1], mx, my, CONSTANT), "K from in_dfov")
+    eq(s.pull().cpu().numpy(), wd.bgr(frames[1], mx, my, "linear", CONSTANT), "K from in_dfov")
     s.close()
 
 
@@ -503,8 +502,8 @@ def test_pipeline_tracked_clip_through_a_distorted_pinhole_lens(vs, cuda):
     Kout = oracle.lens_camera(oracle.PROJ_RECT, 80.0, ow, oh)
     for i in (0, n - 2):
         mx, my = pd.maps(oracle.map_params(K, Kout, b.warp_rotation(i)), ow, oh, 3, pd.D_M)
-        eq(outs_b[i], drd.remap_bgr("cubic", frames[i + 1], mx, my, REFLECT_101), ("tracked cubic frame", i))
-        eq(outs_a[i], drd.remap_bgr("linear", frames[i + 1], mx, my, CONSTANT), ("tracked linear frame", i))
+        eq(outs_b[i], wd.bgr(frames[i + 1], mx, my, "cubic", REFLECT_101), ("tracked cubic frame", i))
+        eq(outs_a[i], wd.bgr(frames[i + 1], mx, my, "linear", CONSTANT), ("tracked linear frame", i))
     a.close(), b.close(), z.close()
 
 

@@ -9,12 +9,10 @@ import ctypes
 import numpy as np
 import pytest
 
-import border_def
-import cubic_def
 import expect
-import lanczos4_def
 import oracle
 import synth
+import warp_def as wd
 
 pytestmark = pytest.mark.gpu
 
@@ -63,11 +61,11 @@ def expected(clip, kind, k, border_mode=0):
         w = wide_frames(frames)[k]
         return expect.warp_p010(w[:H], w[H:], p, cw, ch, None, 0, expect.IEEE)
     if kind == "cubic":
-        return cubic_def.warp_nv12_cubic(frames[k], p, cw, ch, 0)
+        return wd.bgr(frames[k], *wd.maps(p, cw, ch, 0), "cubic")
     if kind == "lanczos4":
-        return lanczos4_def.warp_nv12_lanczos4(frames[k], p, cw, ch, 0)
+        return wd.bgr(frames[k], *wd.maps(p, cw, ch, 0), "lanczos4")
     if border_mode:
-        return border_def.warp_nv12_border(frames[k], p, cw, ch, 0, border_mode)
+        return wd.bgr(frames[k], *wd.maps(p, cw, ch, 0), "linear", border_mode)
     return expect.warp(frames[k], p, cw, ch, expect.IEEE, nearest=kind == "nearest")
 
 

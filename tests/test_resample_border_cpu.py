@@ -1,48 +1,40 @@
-"""Border modes of the cubic and Lanczos resamplers without a GPU: the numpy statement (tests/resample_border_def.py) against a literal
+"""Border modes of the cubic and Lanczos resamplers without a GPU: the numpy statement (tests/warp_def.py) against a literal
 per-pixel restatement of OpenCV's non-constant branch, its golden vectors and OpenCV itself where installed; the constant border against the
 constant-border definitions; the closed-form borderInterpolate over every position a footprint reaches; the tile-box model of the kernels
-(tests/resample_border_tiles.py); and the argument checks of the new entry points."""
+(tests/warp_tiles.py, rule `every`); and the argument checks of the new entry points."""
 import ctypes
 import os
 
 import numpy as np
 import pytest
 
-import border_def
-import cubic_def
-import lanczos4_def
-import resample_border_def as rbd
-import resample_border_tiles
+import warp_def as wd
+import warp_tiles as wt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "resample_border_kat.npz")
 RESAMPLERS = ("cubic", "lanczos4")
 
 
 def golden_cases():
-    g = np.load(GOLDEN)
-    k = 0
-    while f"case{k}_src" in g:
-        yield (k, RESAMPLERS[int(g[f"case{k}_resampler"])], g[f"case{k}_src"], g[f"case{k}_mapx"], g[f"case{k}_mapy"], int(g[f"case{k}_mode"]),
-               g[f"case{k}_out"])
-        k += 1
+    for k, r, *rest in wd.golden_cases("resample_border_kat", "resampler", "src", "mapx", "mapy", "mode", "out"):
+        yield (k, RESAMPLERS[r], *rest)
 
 
 def opencv_literal(resampler, src, mapx, mapy, mode):
     """OpenCV's remapBicubic / remapLanczos4 for one pixel at a time, on the branch of a non-constant borderMode: every tap's column and row
     through borderInterpolate (OpenCV's loop), cval * ONE + sum((S - cval) * w) with cval = 0, then (+ 2^14) >> 15 saturated."""
-    K, LO = rbd.FOOTPRINT[resampler]
-    tab = rbd.table(resampler)
+    K, LO = wd.FOOTPRINT[resampler]
+    tab = wd.table(resampler)
     s = np.asarray(src, np.uint8)
     flat = s.ndim == 2
     if flat:
         s = s[:, :, None]
     sh, sw, cn = s.shape
-    X, Y, f = cubic_def.quantise(mapx, mapy)
+    X, Y, f = wd.quantise(mapx, mapy)
     out = np.zeros(X.shape + (cn,), np.uint8)
     for (i, j), _ in np.ndenumerate(X):
-        xs = border_def.border_interpolate_loop(np.arange(K) + X[i, j] - LO, sw, mode)
-        ys = border_def.border_interpolate_loop(np.arange(K) + Y[i, j] - LO, sh, mode)
+        xs = wd.border_interpolate_loop(np.arange(K) + X[i, j] - LO, sw, mode)
+        ys = wd.border_interpolate_loop(np.arange(K) + Y[i, j] - LO, sh, mode)
         w = tab[f[i, j]]
         for c in range(cn):
             acc = 0
@@ -61,39 +53,39 @@ def test_definition_equals_opencv_literal(resampler):
         mx = rng.uniform(-3 * sw - 4, 4 * sw + 4, (5, 7)).astype(np.float32)
         my = rng.uniform(-3 * sh - 4, 4 * sh + 4, (5, 7)).astype(np.float32)
         mx[0, :3], my[0, :3] = [np.nan, 1e30, -32768.0], [np.nan, -1e30, 32768.0]
-        for mode in rbd.MODES:
-            assert np.array_equal(rbd.remap_resample_border(resampler, src, mx, my, mode), opencv_literal(resampler, src, mx, my, mode)), \
+        for mode in wd.MODES:
+            assert np.array_equal(wd.remap(src, mx, my, resampler, mode), opencv_literal(resampler, src, mx, my, mode)), \
                 (resampler, sw, sh, mode)
 
 
 def test_tables_sum_to_one():
     """cval * ONE + sum((S - cval) * w) == sum(S * w) needs every entry to sum to 32768."""
-    assert (cubic_def._table().sum(axis=(1, 2)) == 32768).all()
-    assert (lanczos4_def._table().sum(axis=(1, 2)) == 32768).all()
+    assert (wd.table("cubic").sum(axis=(1, 2)) == 32768).all()
+    assert (wd.table("lanczos4").sum(axis=(1, 2)) == 32768).all()
 
 
 def test_constant_equals_constant_definitions():
-    rng = np.random.default_rng(12)
+    """The constant border of the one remap against what the constant-border definitions of the cubic and Lanczos resamplers answered while
+    they were layers of their own (tests/golden/warp_definitions_kat.npz, constant_c<cn>_*)."""
+    kat = wd.golden("warp_definitions_kat")
     for cn in (1, 2, 3):
-        src = rng.integers(0, 256, (13, 17, cn) if cn > 1 else (13, 17), dtype=np.uint8)
-        mx = rng.uniform(-20, 40, (11, 15)).astype(np.float32)
-        my = rng.uniform(-15, 30, (11, 15)).astype(np.float32)
-        bd = (7, 200, 33)[:cn]
-        assert np.array_equal(rbd.remap_cubic_border(src, mx, my, rbd.CONSTANT, bd), cubic_def.remap_cubic(src, mx, my, bd))
-        assert np.array_equal(rbd.remap_lanczos4_border(src, mx, my, rbd.CONSTANT, bd), lanczos4_def.remap_lanczos4(src, mx, my, bd))
+        src, mx, my, bd = (kat[f"constant_c{cn}_{k}"] for k in ("src", "mapx", "mapy", "border"))
+        assert src.shape[:2] == (13, 17) and mx.shape == (11, 15) and len(bd) == cn
+        for r in RESAMPLERS:
+            assert np.array_equal(wd.remap(src, mx, my, r, wd.CONSTANT, bd), kat[f"constant_c{cn}_{r}"]), (cn, r)
 
 
 def test_golden_remaps():
     seen = set()
     n = 0
     for k, resampler, src, mx, my, mode, out in golden_cases():
-        assert np.array_equal(rbd.remap_resample_border(resampler, src, mx, my, mode), out), k
+        assert np.array_equal(wd.remap(src, mx, my, resampler, mode), out), k
         cn = 1 if src.ndim == 2 else src.shape[2]
         seen |= {(resampler, mode, cn), (resampler, "w", src.shape[1]), (resampler, "h", src.shape[0])}
         n += 1
     assert n >= 54
     for r in RESAMPLERS:
-        assert {(r, m, c) for m in rbd.MODES for c in (1, 2, 3)} <= seen
+        assert {(r, m, c) for m in wd.MODES for c in (1, 2, 3)} <= seen
         assert {(r, a, v) for a in ("w", "h") for v in (1, 2, 3)} <= seen
 
 
@@ -127,34 +119,35 @@ def test_resample_border_matches_opencv_when_present():
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 1919, 1920, 32767])
-@pytest.mark.parametrize("mode", rbd.MODES)
+@pytest.mark.parametrize("mode", wd.MODES)
 def test_closed_form_equals_opencv_loop_over_footprints(n, mode):
     """Footprints reach X - 3 .. X + 4 with X in [-32768, 32767]: the closed form equals OpenCV's loop over [-32772, 32772]."""
     p = np.arange(-32772, 32773, dtype=np.int64)
-    loop = border_def.border_interpolate_loop(p, n, mode)
+    loop = wd.border_interpolate_loop(p, n, mode)
     assert ((loop >= 0) & (loop < n)).all()
-    assert np.array_equal(border_def.border_interpolate(p, n, mode), loop)
+    assert np.array_equal(wd.border_interpolate(p, n, mode), loop)
 
 
-@pytest.mark.parametrize("key", sorted(resample_border_tiles.TILE_SETS))
+TILE_KEYS = sorted((r, name) for r in RESAMPLERS for name in wt.TILE_SETS[r + "_border"])
+
+
+@pytest.mark.parametrize("key", TILE_KEYS)
 def test_tile_set_reaches_its_committed_states(key):
-    got = resample_border_tiles.states_of(key)
-    for plane, want in resample_border_tiles.TILE_SETS[key][-1].items():
+    got = wt.states_of(key[0] + "_border", key[1])
+    for plane, want in wt.TILE_SETS[key[0] + "_border"][key[1]][-1].items():
         for state, least in want.items():
             assert got[plane][state] >= least, (key, plane, state, got[plane])
 
 
 @pytest.mark.parametrize("resampler", RESAMPLERS)
 def test_tile_sets_cover_every_path_of_every_plane(resampler):
-    total = {p: dict.fromkeys(resample_border_tiles.STATES, 0) for p in ("bgr", "luma", "chroma")}
-    for key in resample_border_tiles.TILE_SETS:
-        if key[0] != resampler:
-            continue
-        for plane, counts in resample_border_tiles.states_of(key).items():
-            for k, v in counts.items():
-                total[plane][k] += v
+    total = {p: dict.fromkeys(wt.BORDER_STATES, 0) for p in ("bgr", "luma", "chroma")}
+    for name in wt.TILE_SETS[resampler + "_border"]:
+        for plane, counts in wt.states_of(resampler + "_border", name).items():
+            for k in wt.BORDER_STATES:
+                total[plane][k] += counts[k]
     for plane, counts in total.items():
-        for state in resample_border_tiles.STATES:
+        for state in wt.BORDER_STATES:
             assert counts[state] > 0, (resampler, plane, state, counts)
 
 
@@ -164,8 +157,8 @@ def test_axis_pixel_gathers_its_tile():
     my = np.full((16, 64), 10.0, np.float32)
     mx[5, 7] = my[5, 7] = np.nan
     for r, lo in (("cubic", 1), ("lanczos4", 3)):
-        x0, y0, bw, bh = resample_border_tiles.tile_boxes(r, mx, my, 64, 32)["bgr"]
-        assert x0[0, 0] == -32768 - lo and bw[0, 0] * bh[0, 0] > resample_border_tiles.BUDGET["bgr"]
+        x0, y0, bw, bh, _ = wt.tile_boxes(mx, my, 64, 32, r, "every")["bgr"]
+        assert x0[0, 0] == -32768 - lo and bw[0, 0] * bh[0, 0] > wt.BUDGET["bgr"]
 
 
 def test_header_and_binding(vs):

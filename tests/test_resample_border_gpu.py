@@ -1,6 +1,6 @@
 """GPU parity of the border modes of the cubic and Lanczos resamplers (include/vstab.h "Border modes of the cubic and Lanczos resamplers")
 through the C ABI and the pipeline object: vstab_remap_{cubic,lanczos4}_border, vstab_warp_nv12_{cubic,lanczos4}_border (BGR8 and plane-wise
-NV12) and vstab_set_border_mode_ex.  Bar: every byte equals the numpy definition (tests/resample_border_def.py) fed by the oracle's maps, and
+NV12) and vstab_set_border_mode_ex.  Bar: every byte equals the numpy definition (tests/warp_def.py) fed by the oracle's maps, and
 every output plane is guarded by canary bytes (tests/layouts.py).  Under BORDER_CONSTANT the new entry points give the bytes of the pinned
 ones (vstab_remap_cubic / _lanczos4, vstab_warp_nv12_cubic / _lanczos4)."""
 import ctypes
@@ -11,15 +11,16 @@ import pytest
 import expect
 import layouts
 import oracle
-import resample_border_def as rbd
-import resample_border_tiles
+import warp_def as wd
+import warp_tiles as wt
+from test_resample_border_cpu import TILE_KEYS
 import synth
 from test_border_gpu import PAST, ROT, cams, dev, eq, map_modes
 from test_layouts_gpu import PITCH_UV_4G
 
 pytestmark = pytest.mark.gpu
 
-MODES = rbd.MODES
+MODES = wd.MODES
 RESAMPLERS = ("cubic", "lanczos4")
 RESAMPLE = {"cubic": 2, "lanczos4": 4}   # vstab_config.resample
 
@@ -55,10 +56,10 @@ def remap_rb(vs, resampler, cuda, src, mx, my, border_mode, border=(0, 0, 0)):
 
 def check_warp(vs, resampler, cuda, s, f, p, dw, dh, mode, border_mode, what):
     """BGR and plane-wise warps of Src s (packed NV12 f on the host) against the definition."""
-    eq(warp_rb(vs, resampler, s, p, dw, dh, mode, vs.OUT_BGR8, border_mode, cuda), rbd.warp_nv12(resampler, f, p, dw, dh, mode, border_mode),
+    eq(warp_rb(vs, resampler, s, p, dw, dh, mode, vs.OUT_BGR8, border_mode, cuda), wd.bgr(f, *wd.maps(p, dw, dh, mode), resampler, border_mode),
        (what, resampler, "bgr", mode, border_mode))
     gy, guv = warp_rb(vs, resampler, s, p, dw, dh, mode, vs.OUT_NV12_PLANAR, border_mode, cuda)
-    ey, euv = rbd.warp_nv12_planar(resampler, f, p, dw, dh, mode, border_mode)
+    ey, euv = wd.planar(f, *wd.maps(p, dw, dh, mode), resampler, border_mode)
     eq(gy, ey, (what, resampler, "luma", mode, border_mode)), eq(guv, euv, (what, resampler, "chroma", mode, border_mode))
 
 
@@ -86,7 +87,7 @@ def test_remap_resample_border_every_channel_count(vs, cuda, resampler):
                 pick = rng.random((dh, dw)) < 0.05
                 m[pick] = rng.choice(special, int(pick.sum()))
             for mode in MODES:
-                eq(remap_rb(vs, resampler, cuda, src, mx, my, mode), rbd.remap_resample_border(resampler, src, mx, my, mode), (sw, sh, cn, mode))
+                eq(remap_rb(vs, resampler, cuda, src, mx, my, mode), wd.remap(src, mx, my, resampler, mode), (sw, sh, cn, mode))
 
 
 @pytest.mark.parametrize("resampler", RESAMPLERS)
@@ -104,7 +105,7 @@ def test_remap_resample_border_constant_equals_pinned_remap(vs, cuda, resampler)
         eq(remap_rb(vs, resampler, cuda, src, mx, my, vs.BORDER_CONSTANT, bd), ref, cn)
         eq(mine(dev(src, cuda), dev(mx, cuda), dev(my, cuda), vs.BORDER_CONSTANT, bd).cpu().numpy(), ref, ("binding", cn))
         eq(mine(dev(src, cuda), dev(mx, cuda), dev(my, cuda), vs.BORDER_REFLECT).cpu().numpy(),
-           rbd.remap_resample_border(resampler, src, mx, my, vs.BORDER_REFLECT), ("binding reflect", cn))
+           wd.remap(src, mx, my, resampler, vs.BORDER_REFLECT), ("binding reflect", cn))
 
 
 # ---- the warp ---------------------------------------------------------------------------------------------------------------------------
@@ -143,10 +144,10 @@ def test_warp_resample_border_binding_and_tiny_source(vs, cuda, resampler):
     w, h = 128, 72
     f = synth.nv12(44, w, h)
     p, dw, dh, K, Ko = cams(w, h, PAST)
-    eq(fn(dev(f, cuda), p, dw, dh, 0, vs.OUT_BGR8, vs.BORDER_REPLICATE).cpu().numpy(), rbd.warp_nv12(resampler, f, p, dw, dh, 0, vs.BORDER_REPLICATE),
+    eq(fn(dev(f, cuda), p, dw, dh, 0, vs.OUT_BGR8, vs.BORDER_REPLICATE).cpu().numpy(), wd.bgr(f, *wd.maps(p, dw, dh, 0), resampler, vs.BORDER_REPLICATE),
        "binding bgr")
     y, uv = fn(dev(f, cuda), p, dw, dh, 1, vs.OUT_NV12_PLANAR, vs.BORDER_REFLECT)
-    ey, euv = rbd.warp_nv12_planar(resampler, f, p, dw, dh, 1, vs.BORDER_REFLECT)
+    ey, euv = wd.planar(f, *wd.maps(p, dw, dh, 1), resampler, vs.BORDER_REFLECT)
     eq(y.cpu().numpy(), ey, "binding y"), eq(uv.cpu().numpy(), euv, "binding uv")
     tiny = np.array([[10, 200], [90, 250], [60, 180]], np.uint8)
     s = layouts.place(tiny[:2], tiny[2:], "packed", cuda)
@@ -157,11 +158,12 @@ def test_warp_resample_border_binding_and_tiny_source(vs, cuda, resampler):
         check_warp(vs, resampler, cuda, s, tiny, pt, 70, 41, 3, bm, "tiny")
 
 
-@pytest.mark.parametrize("key", sorted(resample_border_tiles.TILE_SETS))
+@pytest.mark.parametrize("key", TILE_KEYS)
 def test_resample_border_tile_sets(vs, cuda, key):
-    """The sets of tests/resample_border_tiles.py: staged, gathered, exactly-the-budget, wholly-outside and edge-crossing tiles."""
+    """The sets of tests/warp_tiles.py for k_warp_cubic_border / k_warp_lanczos4_border: staged, gathered, exactly-the-budget, wholly-outside
+    and edge-crossing tiles."""
     resampler, name = key
-    p, sw, sh, dw, dh, mode = resample_border_tiles.set_params(key)
+    p, sw, sh, dw, dh, mode = wt.set_params(key[0] + "_border", key[1])
     f = synth.nv12(sum(map(ord, name)), sw, sh, full_range=True)
     s = layouts.place(f[:sh], f[sh:], "packed", cuda)
     for bm in MODES:
@@ -212,10 +214,10 @@ def clip():
 def expect_frame(resampler, f, K, Ko, R, cw, ch, out, how, border_mode, what):
     p = oracle.map_params(K, Ko, R)
     if how == "planar":
-        ey, euv = rbd.warp_nv12_planar(resampler, f, p, cw, ch, 0, border_mode)
+        ey, euv = wd.planar(f, *wd.maps(p, cw, ch, 0), resampler, border_mode)
         eq(out[0], ey, (what, "y")), eq(out[1], euv, (what, "uv"))
     else:
-        eq(out, rbd.warp_nv12(resampler, f, p, cw, ch, 0, border_mode), what)
+        eq(out, wd.bgr(f, *wd.maps(p, cw, ch, 0), resampler, border_mode), what)
 
 
 @pytest.mark.parametrize("how", ["pull", "frames", "host", "peek", "planar"])

@@ -1,17 +1,18 @@
-"""CPU tests of vstab_warp_nv12_rs_ex's definition (tests/rs_resample_def.py) and of what the entry point decides before any device work:
+"""CPU tests of vstab_warp_nv12_rs_ex's definition (tests/warp_def.py) and of what the entry point decides before any device work:
 the two anchors of the per-row distorted map, every refusal in its order with its whole message, the tile states the GPU cases are
 committed to reach, and the known-answer file."""
 import ctypes
 import os
 import sys
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import distort_def as dd
 import oracle
-import resample_border_tiles
-import rs_resample_def as rsd
+import warp_def as wd
+import warp_tiles as wt
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -25,12 +26,12 @@ def bits(a):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def anchor():
-    return rsd.case_params(128, 72, 300, 170, 60.0, 40.0) + (300, 170)
+    return wd.case_params(128, 72, 300, 170, 60.0, 40.0) + (300, 170)
 
 
 def test_zero_distortion_is_the_oracles_per_row_map(anchor):
     p, rb, dw, dh = anchor
-    got, exp = rsd.maps(p, dw, dh, 1, rb, dd.D_0), oracle.create_map_rs(p, rb, dw, dh, 1)
+    got, exp = wd.maps(p, dw, dh, 1, rb, dd.D_0), oracle.create_map_rs(p, rb, dw, dh, 1)
     assert np.array_equal(bits(got[0]), bits(exp[0])) and np.array_equal(bits(got[1]), bits(exp[1]))
     plain = oracle.create_map_ex(p, dw, dh, 1)
     assert not np.array_equal(bits(got[0]), bits(plain[0]))            # the rotation per row moves the map
@@ -38,18 +39,18 @@ def test_zero_distortion_is_the_oracles_per_row_map(anchor):
 
 def test_one_rotation_is_the_distorted_map(anchor):
     p, _, dw, dh = anchor
-    got, exp = rsd.maps(p, dw, dh, 1, np.asarray(p[8:], np.float32), dd.D_A), dd.maps(p, dw, dh, 1, dd.D_A)
+    got, exp = wd.maps(p, dw, dh, 1, np.asarray(p[8:], np.float32), dd.D_A), dd.maps(p, dw, dh, 1, dd.D_A)
     assert np.array_equal(bits(got[0]), bits(exp[0])) and np.array_equal(bits(got[1]), bits(exp[1]))
 
 
 def test_fma_rounds_once():
     F = np.float32
     a, b, c = F(1 + 2.0 ** -12), F(1 + 2.0 ** -12), F(-1.0)              # a * b = 1 + 2^-11 + 2^-24: the last bit is lost to a rounded product
-    assert rsd.fma_f32(a, b, c) == F(2.0 ** -11 + 2.0 ** -24) != a * b + c
+    assert wd.fma_f32(a, b, c) == F(2.0 ** -11 + 2.0 ** -24) != a * b + c
     # a tie that a sum rounded to double first would break the wrong way: 1 + 2^-24 + 2^-60 is above the halfway point
-    assert rsd.round_f32(1 + rsd.Fraction(1, 2 ** 24) + rsd.Fraction(1, 2 ** 60)) == F(1 + 2.0 ** -23)
-    assert rsd.round_f32(1 + rsd.Fraction(1, 2 ** 24)) == F(1.0)        # the tie itself: to even
-    m = rsd.row_matrices(np.arange(17, dtype=F), np.arange(9, dtype=F) + 9, 1)
+    assert wd.round_f32(1 + Fraction(1, 2 ** 24) + Fraction(1, 2 ** 60)) == F(1 + 2.0 ** -23)
+    assert wd.round_f32(1 + Fraction(1, 2 ** 24)) == F(1.0)        # the tie itself: to even
+    m = wd.row_matrices(np.arange(17, dtype=F), np.arange(9, dtype=F) + 9, 1)
     assert np.array_equal(m[0], np.arange(8, 17, dtype=F))             # one row: t = 0, the first row's rotation
 
 
@@ -120,29 +121,29 @@ def test_set_readout_warp_refuses_a_null_handle_without_a_device(vs):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def zoomed_out():
-    sw, sh, dw, dh, fi, fo = rsd.ZOOMED_OUT
-    p, rb = rsd.case_params(sw, sh, dw, dh, fi, fo)
-    return {mode: (rsd.maps(p, dw, dh, mode, rb), rsd.maps(p, dw, dh, mode, None)) for mode in (0, 1)}
+    sw, sh, dw, dh, fi, fo = wd.ZOOMED_OUT
+    p, rb = wd.case_params(sw, sh, dw, dh, fi, fo)
+    return {mode: (wd.maps(p, dw, dh, mode, rb), wd.maps(p, dw, dh, mode, None)) for mode in (0, 1)}
 
 
 @pytest.mark.parametrize("mode", [0, 1])
 def test_zoomed_out_tile_states(zoomed_out, mode):
-    import cubic_def
-    sw, sh, dw, dh = rsd.ZOOMED_OUT[:4]
+    sw, sh, dw, dh = wd.ZOOMED_OUT[:4]
     (mx, my), (zx, zy) = zoomed_out[mode]
-    q, z = cubic_def.quantise(mx, my), cubic_def.quantise(zx, zy)
+    q, z = wd.quantise(mx, my), wd.quantise(zx, zy)
     assert int(((q[0] != z[0]) | (q[1] != z[1]) | (q[2] != z[2])).sum()) == 19738       # a kernel that ignores rot_bottom fails
     assert dw % 64 and dh % 16                                                          # partial tiles
     for resampler in ("cubic", "lanczos4"):
-        st = rsd.tile_states(resampler, mx, my, sw, sh, rsd.REFLECT_101)
-        assert st == resample_border_tiles.tile_states(resampler, mx, my, sw, sh)
+        st = wt.tile_states(mx, my, sw, sh, resampler, wt.kernel_rule(resampler, wd.REFLECT_101))
+        recorded = wd.golden("warp_definitions_kat")[f"states_rs_zoomed_out_m{mode}_{resampler}_every"]     # the border kernels' model, as it was
+        assert [[st[p][k] for k in wt.BORDER_STATES] for p in ("bgr", "luma", "chroma")] == recorded.tolist()
         for plane in ("bgr", "luma", "chroma"):
             s = st[plane]
             assert s["staged"] == 28 and s["gathered"] == 0, (resampler, plane, s)
             assert min(s["cross_l"], s["cross_r"], s["cross_t"], s["cross_b"], s["odd_w"], s["even_w"]) >= 1, (resampler, plane, s)
             assert (s["outside_staged"] >= 1) == (not (resampler == "lanczos4" and plane == "chroma")), (resampler, plane, s)
         # the constant border: the tiles wholly outside have no box, every other stages
-        sc = rsd.tile_states(resampler, mx, my, sw, sh, rsd.CONSTANT)
+        sc = wt.tile_states(mx, my, sw, sh, resampler, wt.kernel_rule(resampler, wd.CONSTANT))
         for plane in ("bgr", "luma", "chroma"):
             c = sc[plane]
             assert c["none"] == st[plane]["outside_staged"] and c["none"] + c["staged"] == 28 and c["gathered"] == 0, (resampler, plane, c)
@@ -153,22 +154,22 @@ def test_the_constant_border_keeps_the_axis_pixel_of_mode_0_out_of_the_box():
     """Map mode 0 at the identity: the axis pixel's map is NaN (0 / 0), its tap at -32768.  Under a non-constant border its tile gathers;
     under the constant border that footprint does not touch the source and stays out of the box."""
     sw, sh, dw, dh = 64, 36, 65, 37
-    p, rb = rsd.case_params(sw, sh, dw, dh, 30.0, 30.0, r0=(0.0, 0.0, 0.0), r_bottom=(0.0, 0.0, 0.0))
+    p, rb = wd.case_params(sw, sh, dw, dh, 30.0, 30.0, r0=(0.0, 0.0, 0.0), r_bottom=(0.0, 0.0, 0.0))
     p[4], p[5] = 32.0, 16.0                                   # the output camera's centre on a pixel: that pixel looks along the axis
-    mx, my = rsd.maps(p, dw, dh, 0, rb)
+    mx, my = wd.maps(p, dw, dh, 0, rb)
     assert np.isnan(mx).sum() == 1
     for resampler in ("cubic", "lanczos4"):
-        assert rsd.tile_states(resampler, mx, my, sw, sh, rsd.REPLICATE)["bgr"]["gathered"] == 1
-        assert rsd.tile_states(resampler, mx, my, sw, sh, rsd.CONSTANT)["bgr"]["gathered"] == 0
+        assert wt.tile_states(mx, my, sw, sh, resampler, wt.kernel_rule(resampler, wd.REPLICATE))["bgr"]["gathered"] == 1
+        assert wt.tile_states(mx, my, sw, sh, resampler, wt.kernel_rule(resampler, wd.CONSTANT))["bgr"]["gathered"] == 0
 
 
 def test_gathers_every_tile_over_the_budget():
-    sw, sh, dw, dh, fi, fo = rsd.GATHERS
-    p, rb = rsd.case_params(sw, sh, dw, dh, fi, fo, rsd.GATHERS_R0, rsd.GATHERS_R_BOTTOM)
-    mx, my = rsd.maps(p, dw, dh, 1, rb)
+    sw, sh, dw, dh, fi, fo = wd.GATHERS
+    p, rb = wd.case_params(sw, sh, dw, dh, fi, fo, wd.GATHERS_R0, wd.GATHERS_R_BOTTOM)
+    mx, my = wd.maps(p, dw, dh, 1, rb)
     for resampler in ("cubic", "lanczos4"):
-        for border in (rsd.CONSTANT, rsd.REFLECT_101):
-            for plane, s in rsd.tile_states(resampler, mx, my, sw, sh, border).items():
+        for border in (wd.CONSTANT, wd.REFLECT_101):
+            for plane, s in wt.tile_states(mx, my, sw, sh, resampler, wt.kernel_rule(resampler, border)).items():
                 assert s["staged"] == 0 and s["gathered"] == 4, (resampler, border, plane, s)
 
 

@@ -1,5 +1,5 @@
 """GPU tests of vstab_warp_nv12_rs_ex and vstab_set_readout_warp (include/vstab.h): every byte, BGR and plane-wise, against the numpy
-definition (tests/rs_resample_def.py: the per-row map fed to the resampler's own definition), against the older entry points wherever one
+definition (tests/warp_def.py: the per-row map fed to the resampler's own definition), against the older entry points wherever one
 serves the combination, and through the pipeline.  Shapes: the smallest that reach the tile states tests/test_rs_resample_cpu.py asserts for
 them (every tile staged, tiles wholly outside, boxes across all four edges, partial tiles; every tile gathered; one output row)."""
 import ctypes
@@ -8,19 +8,18 @@ import numpy as np
 import pytest
 
 import distort_def as dd
-import distort_resample_def as drd
 import expect
 import oracle
-import rs_resample_def as rsd
 import synth
+import warp_def as wd
 from test_border_gpu import clip  # noqa: F401  (the module's fixture: 640 x 360 frames of a shaky clip)
 from test_distort_gpu import H, K_CAL, LENS, OH, OW, W, refused
 
 pytestmark = pytest.mark.gpu
 
-CONSTANT, REPLICATE, REFLECT, REFLECT_101 = rsd.CONSTANT, rsd.REPLICATE, rsd.REFLECT, rsd.REFLECT_101
-BORDERS = rsd.ALL_BORDERS
-RESAMPLE = rsd.RESAMPLE
+CONSTANT, REPLICATE, REFLECT, REFLECT_101 = wd.CONSTANT, wd.REPLICATE, wd.REFLECT, wd.REFLECT_101
+BORDERS = wd.ALL_BORDERS
+RESAMPLE = wd.RESAMPLE
 FORMATS = ("bgr", "planar")
 
 
@@ -55,13 +54,13 @@ class Case:
     """One frame, parameter set, size and lens: the definition's map evaluated once, shared by every test that asks for the same key."""
     _made = {}
 
-    def __init__(self, geometry, mode, D=None, r0=rsd.R0, r_bottom=rsd.R_BOTTOM, with_rot=True):
+    def __init__(self, geometry, mode, D=None, r0=wd.R0, r_bottom=wd.R_BOTTOM, with_rot=True):
         self.sw, self.sh, self.dw, self.dh, fi, fo = geometry
         self.mode, self.D = mode, D
-        self.p, rb = rsd.case_params(self.sw, self.sh, self.dw, self.dh, fi, fo, r0, r_bottom)
+        self.p, rb = wd.case_params(self.sw, self.sh, self.dw, self.dh, fi, fo, r0, r_bottom)
         self.rb = rb if with_rot else None
         self.f = np.random.default_rng(700 + mode).integers(0, 256, (self.sh * 3 // 2, self.sw), dtype=np.uint8)     # seeded random NV12
-        self.e = rsd.Expected(self.f, self.p, self.dw, self.dh, mode, self.rb, D)
+        self.e = wd.Expected(self.f, *wd.maps(self.p, self.dw, self.dh, mode, self.rb, D))
 
     @classmethod
     def get(cls, *key, **kw):
@@ -90,7 +89,7 @@ def test_zoomed_out(vs, cuda, mode, resampler, fmt, border):
     """128 x 72 -> 200 x 100: every tile stages, some lie wholly outside the source, boxes cross all four edges, partial tiles; mode 5's
     map is the reference kernel's, run row by row on this GPU.  98.7 % of the quantised map entries differ from the map without rot_bottom
     (test_rs_resample_cpu.py), and on random content another tap or fraction is another byte nearly always: a fifth is a loose floor."""
-    c = Case.get(rsd.ZOOMED_OUT, mode)
+    c = Case.get(wd.ZOOMED_OUT, mode)
     got = c.check(vs, cuda, resampler, border, fmt, "zoomed out")
     one = call(vs, dev(c.f, cuda), c.p, c.dw, c.dh, mode, None, None, resampler, border, fmt)     # the same call without rot_bottom
     a, b = (got[0], one[0]) if fmt == "planar" else (got, one)
@@ -102,7 +101,7 @@ def test_zoomed_out(vs, cuda, mode, resampler, fmt, border):
 @pytest.mark.parametrize("resampler", ["cubic", "lanczos4"])
 def test_gathers(vs, cuda, resampler, fmt, border):
     """2048 x 512 -> 128 x 32: every tile of every plane is over the LDS budget, every pixel is sampled from global memory."""
-    c = Case.get(rsd.GATHERS, 1, r0=rsd.GATHERS_R0, r_bottom=rsd.GATHERS_R_BOTTOM)
+    c = Case.get(wd.GATHERS, 1, r0=wd.GATHERS_R0, r_bottom=wd.GATHERS_R_BOTTOM)
     c.check(vs, cuda, resampler, border, fmt, "gathers")
 
 
@@ -124,9 +123,9 @@ def test_one_row(vs, cuda, resampler, fmt, border):
 @pytest.mark.parametrize("resampler", ["linear", "cubic", "lanczos4"])
 @pytest.mark.parametrize("D", [dd.D_A, dd.D_B], ids=["D_A", "D_B"])
 def test_dist_and_rot_bottom(vs, cuda, D, resampler, fmt, border):
-    c = Case.get(rsd.ZOOMED_OUT, 1, D=D)
+    c = Case.get(wd.ZOOMED_OUT, 1, D=D)
     got = c.check(vs, cuda, resampler, border, fmt, "dist + rot_bottom")
-    plain = Case.get(rsd.ZOOMED_OUT, 1).expected(resampler, border, fmt)
+    plain = Case.get(wd.ZOOMED_OUT, 1).expected(resampler, border, fmt)
     a, b = (got[0], plain[0]) if fmt == "planar" else (got, plain)
     assert (a != b).mean() > 0.2, "the distortion moved too few bytes"
 
@@ -134,7 +133,7 @@ def test_dist_and_rot_bottom(vs, cuda, D, resampler, fmt, border):
 @pytest.mark.parametrize("fmt", FORMATS)
 @pytest.mark.parametrize("resampler", ["linear", "cubic", "lanczos4"])
 def test_zero_distortion_is_the_ideal_lens(vs, cuda, resampler, fmt):
-    c = Case.get(rsd.ZOOMED_OUT, 1)
+    c = Case.get(wd.ZOOMED_OUT, 1)
     fd = dev(c.f, cuda)
     for border in BORDERS:
         zero = call(vs, fd, c.p, c.dw, c.dh, 1, c.rb, dd.D_0, resampler, border, fmt)
@@ -198,7 +197,7 @@ def test_pipeline_per_row_on_resampled_handles(vs, cuda, clip, resampler, border
         o = pull_one(stab, how)
         Wr = stab.warp_rotation(i)
         p, rb = oracle.map_params(K, Ko, Wr), oracle.map_params(K, Ko, READOUTS[i + 1] @ Wr)[8:]
-        e = rsd.Expected(frames[i + 1], p, cw, ch, 0, rb)
+        e = wd.Expected(frames[i + 1], *wd.maps(p, cw, ch, 0, rb))
         same(o, e.bgr(resampler, border) if how == "pull" else e.planar(resampler, border), ("pipeline", resampler, how, i))
     assert stab.pull() is None
     stab.close()
@@ -216,7 +215,7 @@ def test_pipeline_per_row_on_a_calibrated_cubic_handle(vs, cuda, how):
         o = pull_one(stab, how)
         Wr = stab.warp_rotation(i)
         p, rb = oracle.map_params(K_CAL, Kout, Wr), oracle.map_params(K_CAL, Kout, READOUTS[i + 1] @ Wr)[8:]
-        e = rsd.Expected(frames[i + 1], p, OW, OH, 1, rb, dd.D_A)
+        e = wd.Expected(frames[i + 1], *wd.maps(p, OW, OH, 1, rb, dd.D_A))
         same(o, e.bgr("cubic", CONSTANT) if how == "pull" else e.planar("cubic", CONSTANT), ("calibrated pipeline", how, i))
     assert stab.pull() is None
     stab.close()
@@ -247,7 +246,7 @@ def test_pipeline_default_refuses_and_the_mode_toggles_between_pulls(vs, cuda, c
         o = host(stab.pull())
         Wr = stab.warp_rotation(i)
         p, rb = oracle.map_params(K, Ko, Wr), oracle.map_params(K, Ko, READOUTS[i + 1] @ Wr)[8:]
-        eq(o, rsd.warp_bgr("cubic", frames[i + 1], p, cw, ch, 0, rb, None, CONSTANT), ("toggled", i))
+        eq(o, wd.bgr(frames[i + 1], *wd.maps(p, cw, ch, 0, rb, None), "cubic", CONSTANT), ("toggled", i))
     # NV12 through BGR stays refused, before a frame is taken
     assert refused(vs, stab.pull_nv12)[0] == vs.ERR_INVALID
     assert stab.pull() is None
@@ -297,8 +296,8 @@ def test_pipeline_frames_without_a_readout_keep_the_quantised_map(vs, cuda):
             o = torch.zeros((OH, OW, 3), dtype=torch.uint8, device=cuda)
             assert vs.lib.vstab_pull_frame(h, o.data_ptr(), o.stride(0)) == vs.OK, (k, vs.lib.vstab_last_error())
             if k in (1, 3):
-                per_row = per_row or rsd.maps(p, OW, OH, 1, rb, dd.D_A)
-                eq(o.cpu().numpy(), drd.remap_bgr("linear", frames[k], per_row[0], per_row[1], CONSTANT), ("per row", k))
+                per_row = per_row or wd.maps(p, OW, OH, 1, rb, dd.D_A)
+                eq(o.cpu().numpy(), wd.bgr(frames[k], per_row[0], per_row[1], "linear", CONSTANT), ("per row", k))
                 assert not np.array_equal(o.cpu().numpy(), base[k - 1])
             else:
                 eq(o.cpu().numpy(), base[k - 1], ("untouched", k))

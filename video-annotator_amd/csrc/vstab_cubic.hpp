@@ -7,7 +7,7 @@
 //   w[k1][k2]  saturate_cast<short>(cvRound(c_fy[k1] * c_fx[k2] * 32768.f)), the product in fp32;
 //   then initInterTab2D's correction when the 16 weights do not sum to 32768 (CUBIC_FIX_LO below).
 // Every entry then sums to 32768, so a blend with the border value substituted for each tap outside the source equals OpenCV's
-// cval * ONE + sum((S - cval) * w).  The same definition is restated in numpy by tests/cubic_def.py and pinned by tests/golden/cubic_kat.npz.
+// cval * ONE + sum((S - cval) * w).  The same definition is restated in numpy by tests/warp_def.py and pinned by tests/golden/cubic_kat.npz.
 #pragma once
 #include <stdint.h>
 

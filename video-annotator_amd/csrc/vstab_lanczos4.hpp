@@ -11,7 +11,7 @@
 //   then initInterTab2D's correction when the 64 weights do not sum to 32768 (LANCZOS4_FIX_LO below).
 // Every entry then sums to 32768, so a blend with the border value substituted for each tap outside the source equals OpenCV's
 // cval * ONE + sum((S - cval) * w).  Entry 0 is not the identity: 32768 saturates to 32767 at tap (3, 3), outside the correction window, and
-// the correction adds 1 at tap (4, 4).  The same definition is restated in numpy by tests/lanczos4_def.py and pinned by
+// the correction adds 1 at tap (4, 4).  The same definition is restated in numpy by tests/warp_def.py and pinned by
 // tests/golden/lanczos4_kat.npz.
 #pragma once
 #include <stdint.h>

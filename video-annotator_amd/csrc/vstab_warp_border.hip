@@ -1,5 +1,5 @@
 // vstab_warp_border.hip -- cv::remap's INTER_LINEAR with a border mode for gfx950: the fused NV12 -> BGR8 warp, the plane-wise NV12 -> NV12
-// warp and the stateless remap of map planes.  Definition (include/vstab.h, vstab_warp_nv12_border; tests/border_def.py): the map quantised
+// warp and the stateless remap of map planes.  Definition (include/vstab.h, vstab_warp_nv12_border; tests/warp_def.py): the map quantised
 // to 1/32 pixel and blended as the bilinear warp does it ((sum of four products + 512) >> 10), each of the four taps (X + i, Y + j) read at
 // (borderInterpolate(X + i, w), borderInterpolate(Y + j, h)) -- BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101 -- or, BORDER_CONSTANT,
 // the border value where it lies outside the source.

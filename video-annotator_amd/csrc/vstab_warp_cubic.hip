@@ -1,6 +1,6 @@
 // vstab_warp_cubic.hip -- cv::remap's INTER_CUBIC for gfx950, with every border mode: the fused NV12 -> BGR8 warp, the plane-wise
 // NV12 -> NV12 warp and the stateless remap of map planes.  Definition (include/vstab.h, vstab_warp_nv12_cubic and "Border modes of the cubic
-// and Lanczos resamplers"; tests/cubic_def.py, tests/resample_border_def.py): the map quantised to 1/32 pixel as for INTER_LINEAR, a 4 x 4
+// and Lanczos resamplers"; tests/warp_def.py): the map quantised to 1/32 pixel as for INTER_LINEAR, a 4 x 4
 // footprint at (X - 1 .. X + 2, Y - 1 .. Y + 2), 16 integer weights from OpenCV's fixed-point table (vstab_cubic.hpp), each tap outside the
 // source the border value (BORDER_CONSTANT) or read at its borderInterpolate position, (sum + 2^14) >> 15 saturated to 0..255.
 //

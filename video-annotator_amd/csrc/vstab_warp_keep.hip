@@ -1,7 +1,7 @@
 // vstab_warp_keep.hip -- the keep-edge warp for gfx950: cv::remap's INTER_LINEAR where the 2 x 2 footprint lies wholly inside the plane it
 // reads, the caller's previous frame everywhere else (vid.stab's `keep` border; cv::remap's BORDER_TRANSPARENT for 1- and 2-channel data).
 // The fused NV12 -> BGR8 warp, the plane-wise NV12 -> NV12 warp and the stateless remap of map planes.  Definition (include/vstab.h, "Keep
-// edges"; tests/keep_def.py): the map quantised to 1/32 pixel as everywhere; a sample is WRITTEN iff 0 <= X <= len_x - 2 and
+// edges"; tests/warp_def.py): the map quantised to 1/32 pixel as everywhere; a sample is WRITTEN iff 0 <= X <= len_x - 2 and
 // 0 <= Y <= len_y - 2, with the bytes of the bilinear warp ((sum of four products + 512) >> 10); every other sample is KEPT: dst receives
 // the byte of prev at the same position, or is not stored at all when prev is dst (in place).
 //

@@ -1,6 +1,6 @@
 // vstab_warp_lanczos4.hip -- cv::remap's INTER_LANCZOS4 for gfx950, with every border mode: the fused NV12 -> BGR8 warp, the plane-wise
 // NV12 -> NV12 warp and the stateless remap of map planes.  Definition (include/vstab.h, vstab_warp_nv12_lanczos4 and "Border modes of the
-// cubic and Lanczos resamplers"; tests/lanczos4_def.py, tests/resample_border_def.py): the map quantised to 1/32 pixel as for INTER_LINEAR,
+// cubic and Lanczos resamplers"; tests/warp_def.py): the map quantised to 1/32 pixel as for INTER_LINEAR,
 // an 8 x 8 footprint at (X - 3 .. X + 4, Y - 3 .. Y + 4), 64 integer weights from OpenCV's fixed-point table (vstab_lanczos4.hpp), each tap
 // outside the source the border value (BORDER_CONSTANT) or read at its borderInterpolate position, (sum + 2^14) >> 15 saturated to 0..255.
 //
