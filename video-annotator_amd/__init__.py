@@ -249,6 +249,8 @@ _L.vstabx_select_corners.restype = _i
 _L.vstabx_select_corners.argtypes = [_c.POINTER(_u64), _c.c_uint, _i, _i, _i, _d, _fp, _ip]
 _L.vstabx_detector_counters.restype = _i
 _L.vstabx_detector_counters.argtypes = [_vp, _c.POINTER(_c.c_long)]
+_L.vstabx_tracker_counters.restype = _i
+_L.vstabx_tracker_counters.argtypes = [_vp, _c.POINTER(_c.c_long)]
 # test hooks of the pyramid (pack_pyr below; tests/test_pyr_paths_cpu.py calls vstabx_pyr_down_check through lib)
 for _f in (_L.vstabx_pack_pyr, _L.vstabx_launch_pack_pyr):
     _f.restype, _f.argtypes = _i, [_vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _sz, _vp]
@@ -1437,6 +1439,14 @@ class Stabilizer:
         out = (_c.c_long * 3)()
         _check(_L.vstabx_detector_counters(self._h, out), "vstabx_detector_counters")
         return dict(spec_over_cap=out[0], fused_overflows=out[1], key_capacity=out[2])
+
+    def tracker_counters(self):
+        """Test hook vstabx_tracker_counters: the handle's tracker launches, the frame pairs they cover and the pairs dropped with launches
+        nobody read; frames that took the launch enqueued ahead of them, frames whose launch was replaced on demand, and planned key frames
+        whose tracker was already running on the speculated corners."""
+        out = (_c.c_long * 6)()
+        _check(_L.vstabx_tracker_counters(self._h, out), "vstabx_tracker_counters")
+        return dict(zip(("segs_launched", "seg_frames_launched", "seg_frames_dropped", "chained_adopted", "chained_discarded", "key_prelaunched"), out))
 
     def set_colour(self, matrix, range_=RANGE_LIMITED):
         """vstab_set_colour: the colour spec of the converting pulls (BGR, host, NV12 through BGR), from the next pull on."""

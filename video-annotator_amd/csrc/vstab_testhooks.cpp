@@ -351,6 +351,16 @@ __attribute__((visibility("default"))) int vstabx_detector_counters(const vstab_
     return VSTAB_OK;
 }
 
+// The launch bookkeeping of a handle's tracker (track_frame; not in vstab_profile: the ABI layout stays): out = {tracker launches, the frame
+// pairs they cover, the pairs of launches dropped before the host reached them, frames that took the launch enqueued ahead of them, frames
+// whose launch enqueued ahead was replaced on demand, planned key frames whose tracker already ran on the speculated corners}.
+__attribute__((visibility("default"))) int vstabx_tracker_counters(const vstab_handle *h, long *out) {
+    if (!h || !out) return fail(VSTAB_ERR_INVALID, "vstabx_tracker_counters: bad argument");
+    out[0] = h->segs_launched, out[1] = h->seg_frames_launched, out[2] = h->seg_frames_dropped;
+    out[3] = h->chained_adopted, out[4] = h->chained_discarded, out[5] = h->key_prelaunched;
+    return VSTAB_OK;
+}
+
 // k_pack_pyr ALONE, on planes the caller lays out (tests/test_pyr_paths_gpu.py, tests/pyr_paths.py): the copy of the NV12 frame (y, uv) into `ring`
 // (w * h * 3 / 2 bytes, rows of pitch w) and pyrDown of its luma into dst (pitch dpitch) by launch_pack_pyr, as the pipeline's ingest of a frame upstream
 // recycles does.  Returns -1 where pack_pyr_ok says no (nothing is launched: the pipeline takes its two-kernel path there), else the status of
