@@ -1327,6 +1327,54 @@ VSTAB_API vstab_status vstab_cvt_bgr16_p010_colour(const void *src_bgr16, size_t
  * (VSTAB_ERR_UNSUPPORTED: its spec is vstab_set_colour's). */
 VSTAB_API vstab_status vstab_set_colour10(vstab_handle *h, int matrix, int range);
 
+/* Cubic and Lanczos resampling at 10 bits: the plane-wise 10-bit warp (vstab_warp_p010_planar; no colour conversion) with cv::remap's
+ * INTER_CUBIC or INTER_LANCZOS4 and a border mode.  A definition of this library's, like the rest of the 10-bit path (OpenCV's own CV_16U
+ * remap blends with float tables): the 8-bit definition -- "Bicubic resampling", "Lanczos resampling", "Border modes of the cubic and Lanczos
+ * resamplers" -- applied to the ten significant bits, as VSTAB_BLEND_EXACT defines the bilinear 10-bit blend.
+ *   sample    s = word >> 6, in 0..1023 (the low six bits of a source word are ignored); the output word is v << 6.
+ *   map       the map, its quantisation (cvRound(32 map), X = sat16(sx >> 5), f = fy * 32 + fx), the footprints (cubic 4 x 4 at X - 1, Y - 1;
+ *             Lanczos 8 x 8 at X - 3, Y - 3) and the int16 tables (vstab_cubic_weights, vstab_lanczos4_weights; every entry sums to 32768)
+ *             are the 8-bit path's, unchanged.
+ *   chroma    as VSTAB_OUT_NV12_PLANAR: sampled at the even pixels of even rows, with 0.5f * map quantised again, the border decided over
+ *             the chroma plane's own size (src_width / 2, src_height / 2), U and V blended separately.
+ *   taps      VSTAB_BORDER_CONSTANT: a tap outside the plane enters as 64 (luma) or 512 (chroma), vstab_warp_p010_planar's border values,
+ *             and a pixel whose footprint does not touch the plane is that value.  _REPLICATE, _REFLECT, _REFLECT_101: every tap is read
+ *             at its borderInterpolate position.
+ *   blend     v = clamp((sum w s + 2^14) >> 15, 0, 1023), an arithmetic shift: overshoot clamps at both ends, the upper one at 1023.
+ *             int32 holds the sum: the largest sum of |w| of an entry is 61952 (cubic) and 96336 (Lanczos), so |sum| <= 96336 * 1023 + 2^14.
+ * vstab_config.blend plays no part: these blends have no binary16 form.
+ *
+ * vstab_warp_p010_planar_ex: planes, pitches, alignments and sizes as for vstab_warp_p010_planar (source even and at least 8 x 2, 16-bit
+ * samples 2-byte aligned, chroma pairs 4-byte aligned); all six map modes; rot_bottom (may be NULL) with map modes 0, 1 and 5.  Addresses
+ * are formed in 64 bits: the bilinear kernel's "source pitch too large" limit does not apply.  Refusals, each before any launch, in this
+ * order and with these texts behind "vstab_warp_p010_planar_ex: " (VSTAB_ERR_INVALID unless stated):
+ *   "null pointer"; "sizes must be in [1, 32767], source even and at least 8 x 2";
+ *   "bad source pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)";
+ *   "bad output pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)"; "unknown map mode";
+ *   "the per-row warp exists for the fisheye -> pinhole modes (0, 1, 5) only";
+ *   resample VSTAB_RESAMPLE_DEFAULT: VSTAB_ERR_UNSUPPORTED, "VSTAB_RESAMPLE_DEFAULT (the bilinear warp) is served by vstab_warp_p010_planar";
+ *   any other value but _CUBIC and _LANCZOS4: "resample must be VSTAB_RESAMPLE_CUBIC (2) or VSTAB_RESAMPLE_LANCZOS4 (4)";
+ *   "border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)". */
+VSTAB_API vstab_status vstab_warp_p010_planar_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int src_width, int src_height,
+                                                 const float params[17], const float *rot_bottom, int map_mode, int resample, int border_mode,
+                                                 void *dst_y, size_t pitch_dst_y, void *dst_uv, size_t pitch_dst_uv, int dst_width, int dst_height,
+                                                 void *stream);
+/* The resampler and border mode of a pixel_depth 10 handle's plane-wise pull, from the next pull on; it may be called between pulls.
+ * (vstab_create still refuses vstab_config.resample with pixel_depth 10, and vstab_set_border_mode / _ex such a handle: this is the way in.)
+ * While a resampler is set, vstab_pull_frame_p010_planar warps with vstab_warp_p010_planar_ex (a frame that carries a readout_rotation per
+ * row, as without one), and vstab_pull_frame_bgr16 / vstab_pull_frame_p010 are refused with VSTAB_ERR_INVALID before a frame is taken
+ * ("vstab_pull_frame: VSTAB_RESAMPLE_CUBIC on a pixel_depth 10 handle (vstab_set_resample10) emits plane-wise P010 frames
+ * (vstab_pull_frame_p010_planar), not 16-bit BGR or P010 through BGR"; or ..._LANCZOS4 ...): the frame stays pullable plane-wise.
+ * (VSTAB_RESAMPLE_DEFAULT, VSTAB_BORDER_CONSTANT) restores the handle as it always was.  vstab_set_colour10 is untouched: the plane-wise
+ * pull converts nothing.  Refusals, the handle unchanged, in this order and with these texts behind "vstab_set_resample10: ":
+ *   VSTAB_ERR_INVALID      "null handle"; "resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)";
+ *                          "border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)"
+ *   VSTAB_ERR_UNSUPPORTED  _DEFAULT with another border mode than _CONSTANT: "VSTAB_RESAMPLE_DEFAULT (the bilinear warp) has the constant
+ *                          border at 10 bits; border modes are served with _CUBIC and _LANCZOS4";
+ *                          an 8-bit handle: "served for pixel_depth 10 handles; an 8-bit handle takes its resampler from
+ *                          vstab_config.resample and its border mode from vstab_set_border_mode_ex" */
+VSTAB_API vstab_status vstab_set_resample10(vstab_handle *h, int resample, int border_mode);
+
 /* Synchronises the stream, folds all pending event pairs into the sums and returns them. */
 VSTAB_API vstab_status vstab_get_profile(vstab_handle *h, vstab_profile *out);
 

@@ -181,6 +181,8 @@ SIGNATURES = {
     "vstab_cvt_p010_bgr16_colour": (_i, [_vp, _sz, _vp, _sz, _i, _i, _vp, _sz, _i, _i, _vp]),
     "vstab_cvt_bgr16_p010_colour": (_i, [_vp, _sz, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_set_colour10": (_i, [_vp, _i, _i]),
+    "vstab_warp_p010_planar_ex": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
+    "vstab_set_resample10": (_i, [_vp, _i, _i]),
     "vstab_warp_nv12_rs_ex": (_i, [_vp, _sz, _vp, _sz, _i, _i, _fp, _fp, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _i, _vp]),
     "vstab_set_readout_warp": (_i, [_vp, _i]),
     "vstab_remap_cubic_border": (_i, [_vp, _sz, _i, _i, _i, _vp, _sz, _vp, _sz, _i, _ip, _vp, _sz, _i, _i, _vp]),
@@ -791,6 +793,24 @@ def warp_p010_planar(y, uv, params, dw, dh, rot_bottom=None, mode=MAP_CREATEMAP_
     _check(_L.vstab_warp_p010_planar(y.data_ptr(), y.stride(0) * 2, uv.data_ptr(), uv.stride(0) * 2, w, h, _fptr(p), None if rb is None else _fptr(rb),
                                      int(mode), int(blend), out_y.data_ptr(), out_y.stride(0) * 2, out_uv.data_ptr(), out_uv.stride(0) * 2, dw, dh, _stream()),
            "vstab_warp_p010_planar")
+    return out_y, out_uv
+
+
+def warp_p010_planar_ex(y, uv, params, dw, dh, rot_bottom=None, mode=MAP_CREATEMAP_CL, resample=RESAMPLE_CUBIC, border_mode=BORDER_CONSTANT, out_y=None,
+                        out_uv=None):
+    """vstab_warp_p010_planar_ex: warp_p010_planar with cv::remap's INTER_CUBIC or INTER_LANCZOS4 (RESAMPLE_*) and a border mode (BORDER_*)."""
+    import torch
+    h, w = y.shape
+    p = np.ascontiguousarray(params, np.float32)
+    rb = None if rot_bottom is None else np.ascontiguousarray(rot_bottom, np.float32).reshape(9)
+    if out_y is None:
+        out_y = torch.empty((dh, dw), dtype=torch.int16, device=y.device)
+    if out_uv is None:
+        out_uv = torch.empty(((dh + 1) // 2, 2 * ((dw + 1) // 2)), dtype=torch.int16, device=y.device)
+    _check(_L.vstab_warp_p010_planar_ex(y.data_ptr(), y.stride(0) * 2, uv.data_ptr(), uv.stride(0) * 2, w, h, _fptr(p), None if rb is None else _fptr(rb),
+                                        int(mode), int(resample), int(border_mode), out_y.data_ptr(), out_y.stride(0) * 2, out_uv.data_ptr(),
+                                        out_uv.stride(0) * 2, dw, dh, _stream()),
+           "vstab_warp_p010_planar_ex")
     return out_y, out_uv
 
 
@@ -1455,6 +1475,11 @@ class Stabilizer:
     def set_colour10(self, matrix, range_=RANGE_LIMITED):
         """vstab_set_colour10: the colour spec of a pixel_depth 10 handle's converting pulls (16-bit BGR, P010), from the next pull on."""
         _check(_L.vstab_set_colour10(self._h, int(matrix), int(range_)), "vstab_set_colour10")
+
+    def set_resample10(self, resample, border_mode=BORDER_CONSTANT):
+        """vstab_set_resample10: the resampler (RESAMPLE_*) and border mode (BORDER_*) of a pixel_depth 10 handle's plane-wise pull, from the
+        next pull on; (RESAMPLE_DEFAULT, BORDER_CONSTANT) restores the bilinear warp."""
+        _check(_L.vstab_set_resample10(self._h, int(resample), int(border_mode)), "vstab_set_resample10")
 
     def set_border_mode(self, border_mode):
         """vstab_set_border_mode: cv::remap's borderMode for the frames pulled from now on."""

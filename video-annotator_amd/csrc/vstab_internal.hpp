@@ -51,6 +51,7 @@ vstab_status preload_cubic_kernels();
 vstab_status preload_lanczos4_kernels();
 vstab_status preload_border_kernels();
 vstab_status preload_keep_kernels();
+vstab_status preload_p010_resample_kernels();
 bool launch_events_pending();
 
 // the cv::BorderTypes the border warps serve (vstab_warp_nv12_border, vstab_warp_nv12_cubic_border / _lanczos4_border, vstab_set_border_mode / _ex)

@@ -334,6 +334,8 @@ struct vstab_handle {
     bool colour() const { return colour_matrix != VSTAB_COLOUR_CVTCOLOR || colour_range != VSTAB_RANGE_LIMITED; }
     // vstab_set_colour10: the colour spec of a pixel_depth 10 handle's converting pulls (16-bit BGR, P010 through BGR), from the next pull on
     int colour10_matrix = VSTAB_COLOUR_CVTCOLOR, colour10_range = VSTAB_RANGE_LIMITED;
+    // vstab_set_resample10: the resampler and border mode of a pixel_depth 10 handle's plane-wise pull, from the next pull on
+    int resample10 = VSTAB_RESAMPLE_DEFAULT, border10 = VSTAB_BORDER_CONSTANT;
     int readout_warp = VSTAB_READOUT_REFUSE;  // vstab_set_readout_warp: applies from the next pull
     long warps_from_cache = 0;
     PinnedBuf marker_pts;           // vstab_config.debug: rotating sets of marker centres, read by the kernel in place

@@ -37,6 +37,10 @@ struct Pull {  // one pull on its way through the steps: what the caller asked f
 static vstab_status refuse_formats(const vstab_handle *H, const Pull &P) {
     if ((H->cfg.pixel_depth == 10) != out_is_10bit(P.out_format))
         return fail(VSTAB_ERR_INVALID, "vstab_pull_frame: a pixel_depth 10 handle emits through vstab_pull_frame_bgr16, an 8-bit handle through the others");
+    // (a 10-bit handle with a resampler set warps plane by plane alone; refused before any frame is dequeued: the frame stays pullable plane-wise)
+    if (H->resample10 != VSTAB_RESAMPLE_DEFAULT && (P.out_format == OUT_BGR16 || P.out_format == OUT_P010))
+        return fail(VSTAB_ERR_INVALID, std::string("vstab_pull_frame: ") + resample_name(H->resample10) +
+                                           " on a pixel_depth 10 handle (vstab_set_resample10) emits plane-wise P010 frames (vstab_pull_frame_p010_planar), not 16-bit BGR or P010 through BGR");
     if (P.out_format == VSTAB_OUT_BGR8 || P.out_format == VSTAB_OUT_NV12_PLANAR) return VSTAB_OK;
     static const char served[] = " emits 8-bit BGR or plane-wise NV12 frames (vstab_pull_frame / _frames / _host / vstab_peek_frame / vstab_pull_frame_nv12_planar), not NV12 through BGR";
     // (refused before any frame is dequeued: the caller can pull the same frame in a format the cubic warp serves)
@@ -192,6 +196,9 @@ static vstab_status launch_warp(vstab_handle *H, const Pull &P) {
                    : vstab_warp_p010(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, dst, pitch_dst, ow, oh, H->stream);
     };
     if (out_format == OUT_BGR16) return warp_bgr16(P.dst, P.pitch_dst);
+    if (out_format == OUT_P010_PLANAR && H->resample10 != VSTAB_RESAMPLE_DEFAULT)  // vstab_set_resample10
+        return vstab_warp_p010_planar_ex(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->resample10, H->border10, P.dst, P.pitch_dst,
+                                         P.dst_uv, P.pitch_dst_uv, ow, oh, H->stream);
     if (out_format == OUT_P010_PLANAR)
         return vstab_warp_p010_planar(S.y16, S.pitch_y16, S.uv16, S.pitch_uv16, w, h, P.p, P.rot_bottom, mode, H->cfg.blend, P.dst, P.pitch_dst, P.dst_uv,
                                       P.pitch_dst_uv, ow, oh, H->stream);
@@ -385,6 +392,23 @@ vstab_status vstab_set_colour10(vstab_handle *h, int matrix, int range) {
     if (h->cfg.pixel_depth != 10)
         return fail(VSTAB_ERR_UNSUPPORTED, "vstab_set_colour10: served for pixel_depth 10 handles; the colour spec of an 8-bit handle is set with vstab_set_colour");
     h->colour10_matrix = matrix, h->colour10_range = range;
+    return VSTAB_OK;
+}
+
+// The resampler and border mode of a pixel_depth 10 handle's plane-wise pull.  The values are checked before the handle is read; the handle
+// is unchanged on every refusal.
+vstab_status vstab_set_resample10(vstab_handle *h, int resample, int border_mode) {
+    const std::string n = "vstab_set_resample10: ";
+    if (!h) return fail(VSTAB_ERR_INVALID, n + "null handle");
+    if (resample != VSTAB_RESAMPLE_DEFAULT && resample != VSTAB_RESAMPLE_CUBIC && resample != VSTAB_RESAMPLE_LANCZOS4)
+        return fail(VSTAB_ERR_INVALID, n + "resample must be VSTAB_RESAMPLE_DEFAULT (0), _CUBIC (2) or _LANCZOS4 (4)");
+    if (!border_mode_valid(border_mode))
+        return fail(VSTAB_ERR_INVALID, n + "border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)");
+    if (resample == VSTAB_RESAMPLE_DEFAULT && border_mode != VSTAB_BORDER_CONSTANT)
+        return fail(VSTAB_ERR_UNSUPPORTED, n + "VSTAB_RESAMPLE_DEFAULT (the bilinear warp) has the constant border at 10 bits; border modes are served with _CUBIC and _LANCZOS4");
+    if (h->cfg.pixel_depth != 10)
+        return fail(VSTAB_ERR_UNSUPPORTED, n + "served for pixel_depth 10 handles; an 8-bit handle takes its resampler from vstab_config.resample and its border mode from vstab_set_border_mode_ex");
+    h->resample10 = resample, h->border10 = border_mode;
     return VSTAB_OK;
 }
 

@@ -55,6 +55,7 @@ vstab_status vstab_preload_kernels(void) {
     VSTAB_TRY(preload_lanczos4_kernels());
     VSTAB_TRY(preload_border_kernels());
     VSTAB_TRY(preload_keep_kernels());
+    VSTAB_TRY(preload_p010_resample_kernels());
     return VSTAB_OK;
 }
 

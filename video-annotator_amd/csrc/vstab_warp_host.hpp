@@ -1,5 +1,5 @@
 // vstab_warp_host.hpp -- the host side of every warp translation unit (vstab_warp.hip, vstab_warp_fused.hip, vstab_warp_planar.hip,
-// vstab_warp_p010.hip, vstab_warp_cubic.hip, vstab_warp_lanczos4.hip, vstab_warp_border.hip) and of vstab_plane_ops.hip: each fact once.  The alignment predicate, the
+// vstab_warp_p010.hip, vstab_warp_p010_resample.hip, vstab_warp_cubic.hip, vstab_warp_lanczos4.hip, vstab_warp_border.hip) and of vstab_plane_ops.hip: each fact once.  The alignment predicate, the
 // kernel arguments from the C arguments (MapParams, MapParams32, WarpArgs, the rolling-shutter pair, FusedArgs' common part), the conditions
 // for 32-bit staged offsets, the dispatch of a run-time mode to a template argument, the launch with a profiler's event pair, the
 // argument checks of a WarpRequest (vstab_warp_request.hpp) and of the stateless remaps (every one before any launch, in one order, each
@@ -287,6 +287,9 @@ vstab_status launch_warp_cubic(const BorderArgs &ba, const WarpRoute &r, int out
 vstab_status launch_warp_lanczos4(const BorderArgs &ba, const WarpRoute &r, int out_format, int border_mode, void *stream);
 vstab_status launch_warp_border(const BorderArgs &ba, const WarpRoute &r, int out_format, int border_mode, void *stream);
 vstab_status launch_warp_keep(const BorderArgs &ba, const WarpRoute &r, const WarpRequest &q, bool in_place);
+// the 10-bit plane-wise kernels (vstab_warp_p010_resample.hip): ba.c.w the P010 planes; map_mode 0 .. 5, rs (a rotation per output row) with
+// 0, 1 and 5 alone; resample VSTAB_RESAMPLE_CUBIC or _LANCZOS4; every border mode
+vstab_status launch_warp_resample10(const BorderArgs &ba, int map_mode, bool rs, int resample, int border_mode, void *stream);
 
 template <typename KS>
 vstab_status remap_resample(const char *name, const void *src, size_t pitch_src, int sw, int sh, int channels, const void *map_x, size_t pitch_x,

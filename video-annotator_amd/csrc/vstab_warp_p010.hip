@@ -211,8 +211,9 @@ using namespace vstab;
 namespace {
 
 // The three P010 warps differ in what leaves them -- 16-bit BGR (vstab_warp_p010), P010 planes from the fused kernel (_planes), P010 planes
-// plane by plane (_planar) -- and in which of the shared checks they make.
-enum P010Out { P010_BGR16, P010_PLANES, P010_PLANAR };
+// plane by plane (_planar; _planar_ex, the cubic and Lanczos resamplers: _planar's checks but for the pitch limit of its 32-bit offsets) --
+// and in which of the shared checks they make.
+enum P010Out { P010_BGR16, P010_PLANES, P010_PLANAR, P010_PLANAR_EX };
 
 // Their arguments, checked in one order with each message under the entry point's own name n, into the kernel argument.  dst / dst_uv: the
 // output planes (BGR16: dst alone).  _planes leaves the source planes and the map mode to its tiled_ok (VSTAB_ERR_UNSUPPORTED, not _INVALID).
@@ -228,16 +229,17 @@ vstab_status check_warp_p010(const std::string &n, P010Out out, const void *y, s
                                       !ptr_aligned(dst, 2) || !ptr_aligned(dst_uv, 4)
                                 : pitch_dst < (size_t)dw * 6 || pitch_dst % 2 || !ptr_aligned(dst, 2);
     if (out == P010_BGR16 && (src_bad || dst_bad)) return fail(VSTAB_ERR_INVALID, n + ": bad pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
-    if (out == P010_PLANAR && src_bad)
+    const bool planar = out == P010_PLANAR || out == P010_PLANAR_EX;
+    if (planar && src_bad)
         return fail(VSTAB_ERR_INVALID, n + ": bad source pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
     if (planes && dst_bad) return fail(VSTAB_ERR_INVALID, n + ": bad output pitch or alignment (16-bit samples; chroma pairs 4-byte aligned)");
     if (out != P010_PLANES && (map_mode < VSTAB_MAP_CREATEMAP_CL || map_mode > VSTAB_MAP_CREATEMAP_CL_OPENCL))
         return fail(VSTAB_ERR_INVALID, n + ": unknown map mode");
     if (blend != VSTAB_BLEND_EXACT && blend != VSTAB_BLEND_FP16) return fail(VSTAB_ERR_INVALID, n + ": unknown blend");
-    if (out == P010_PLANAR) {
+    if (planar) {
         if (rot_bottom && !map_mode_fish_to_pinhole(map_mode))
             return fail(VSTAB_ERR_INVALID, n + ": the per-row warp exists for the fisheye -> pinhole modes (0, 1, 5) only");
-        if (!staged_offsets32(pitch_y, pitch_uv, sh).rows) return fail(VSTAB_ERR_INVALID, n + ": source pitch too large");
+        if (out == P010_PLANAR && !staged_offsets32(pitch_y, pitch_uv, sh).rows) return fail(VSTAB_ERR_INVALID, n + ": source pitch too large");
     }
     fill_warp_args(a, y, pitch_y, uv, pitch_uv, sw, sh, params, dst, pitch_dst, planes ? dst_uv : nullptr, planes ? pitch_dst_uv : 0, dw, dh);
     return VSTAB_OK;
@@ -298,6 +300,27 @@ extern "C" vstab_status vstab_warp_p010_planar(const void *y, size_t pitch_y, co
     const bool src16 = source_16(y, pitch_y, uv, pitch_uv) && staged_offsets32(pitch_y, pitch_uv, sh).chroma;
     const bool dst16 = ptr_aligned(dst_y, 16) && ptr_aligned(dst_uv, 16) && pitch_dst_y % 16 == 0 && pitch_dst_uv % 16 == 0;
     return launch_warp_planar(wa, params, map_mode, 10, blend, src16, dst16, rot_bottom, static_cast<hipStream_t>(stream));
+}
+
+// The plane-wise 10-bit warp with cv::remap's cubic or Lanczos resampler and a border mode (vstab_warp_p010_resample.hip): _planar's
+// argument checks under this name, then the resampler, then the border mode -- all before any launch.
+extern "C" vstab_status vstab_warp_p010_planar_ex(const void *y, size_t pitch_y, const void *uv, size_t pitch_uv, int sw, int sh, const float params[17],
+                                                  const float *rot_bottom, int map_mode, int resample, int border_mode, void *dst_y, size_t pitch_dst_y,
+                                                  void *dst_uv, size_t pitch_dst_uv, int dw, int dh, void *stream) {
+    const std::string n = "vstab_warp_p010_planar_ex";
+    BorderArgs ba;
+    const vstab_status st = check_warp_p010(n, P010_PLANAR_EX, y, pitch_y, uv, pitch_uv, sw, sh, params, rot_bottom, map_mode, VSTAB_BLEND_EXACT, dst_y,
+                                            pitch_dst_y, dst_uv, pitch_dst_uv, dw, dh, ba.c.w);
+    if (st != VSTAB_OK) return st;
+    if (resample == VSTAB_RESAMPLE_DEFAULT)
+        return fail(VSTAB_ERR_UNSUPPORTED, n + ": VSTAB_RESAMPLE_DEFAULT (the bilinear warp) is served by vstab_warp_p010_planar");
+    if (resample != VSTAB_RESAMPLE_CUBIC && resample != VSTAB_RESAMPLE_LANCZOS4)
+        return fail(VSTAB_ERR_INVALID, n + ": resample must be VSTAB_RESAMPLE_CUBIC (2) or VSTAB_RESAMPLE_LANCZOS4 (4)");
+    if (!border_mode_valid(border_mode))
+        return fail(VSTAB_ERR_INVALID, n + ": border_mode must be VSTAB_BORDER_CONSTANT (0), _REPLICATE (1), _REFLECT (2) or _REFLECT_101 (4)");
+    ba.c.p32 = map_params32(params);
+    fill_rolling_shutter(ba, params, rot_bottom, dh);
+    return launch_warp_resample10(ba, map_mode, rot_bottom != nullptr, resample, border_mode, stream);
 }
 
 static vstab_status cvt_bgr16_p010(const std::string &n, const void *src_bgr16, size_t pitch_src, int width, int height, void *dst_y, size_t pitch_y, void *dst_uv,
